@@ -11,10 +11,14 @@ stoch=30 (6 categoricals x 5 classes), action=4, vision 1x64x64 + audio 1x128x32
 frames); the dims BASELINE leaves open are build-chosen and printed in ``config``.  N > 1 shards the
 sequence batch data-parallel (weak scaling: 64 sequences per GPU), one process per GPU.
 
-Rank 0 prints ONE JSON line.  ``roofline`` is for the dominant hand-written kernel of the step (HIP events
-on the launch stream, 3 steps right after the timed region); ``cpu_baseline`` times the oracle
-(``oracle/ref_model.py``, the op-for-op eager restatement of the reference loop) on this box's host cores at the
-SAME batch (B = 64); ``elbo_rel_delta`` is the loss of the trained weights against that oracle on a 2-row sub-batch.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times ``--steps`` steps and prints the line
+(``value``, ``ms_per_step`` = wall time of the timed steps / steps).  ``--dump-outputs DIR`` writes what the last timed
+step computed to ``DIR/*.npy`` (see ``dump_outputs``); that step starts from the seeded state (``training_state``), so its
+inputs, and its outputs up to rounding, are the same on every run with the same arguments.  ``--full`` adds everything
+else, after the timed region: ``roofline`` for the dominant hand-written kernel of the step (HIP events on the launch
+stream, 3 more steps); ``cpu_baseline``, the oracle (``oracle/ref_model.py``, the op-for-op eager restatement of the
+reference loop) timed on this box's host cores at the SAME batch (B = 64); ``elbo_rel_delta``, the loss of the trained
+weights against that oracle on a 2-row sub-batch; ``data_feed``.
 """
 
 from __future__ import annotations
@@ -211,6 +215,143 @@ def feed_benchmark(device: str, batches: int = 20) -> dict[str, object]:
             "what": f"6-tuple batch B={b} T={t} from {n} HBM-resident episodes x {t_full} steps; gather + TakeFirstN + GaussianNoise fused (mtrssm_episode_gather) + torch.randn"}
 
 
+def _state_tensors(flat, opt) -> list[torch.Tensor]:  # noqa: ANN001
+    return [flat.param] + [getattr(opt, n) for n in ("exp_avg", "exp_avg_sq", "state") if hasattr(opt, n)]
+
+
+def training_state(flat, opt, noise) -> tuple:  # noqa: ANN001
+    """Copies of what a train step reads besides the batch: the parameters, the optimizer's moments, device-side scalars and
+    step count, and the noise generator (the set ``graph.CapturedTrainStep`` puts back after its warm-up).
+
+    ``--dump-outputs`` takes them before the first step and puts them back before the last timed step, so the dumped step
+    has the same inputs on every run.  The steps before it do not: reductions split over workgroups meet by fp32 atomics in
+    varying order (``linear.py``), and a few AdamW steps turn those last-bit differences into larger ones."""
+    return [t.clone() for t in _state_tensors(flat, opt)], getattr(opt, "steps", None), noise.gen.get_state()
+
+
+@torch.no_grad()
+def restore_training_state(flat, opt, noise, saved: tuple) -> None:  # noqa: ANN001
+    from multimodal_mtrssm_amd import conv
+
+    tensors, steps, gen = saved
+    for dst, src in zip(_state_tensors(flat, opt), tensors, strict=True):
+        dst.copy_(src)
+    if steps is not None:
+        opt.steps = steps
+    noise.gen.set_state(gen)
+    conv.invalidate_packs()  # the parameters changed behind autograd's version counters
+
+
+DUMP_MAX_ELEMS = 6 << 20  # the gradient buffer + the loss terms stay under 64 MB of float32
+
+
+def dump_outputs(directory: str, scalars: dict[str, torch.Tensor], flat) -> None:  # noqa: ANN001
+    """``--dump-outputs``: what the last timed step (run from the seeded state, see ``training_state``) computed, as float32
+    ``.npy`` files -- every loss term it returned (``<key>.npy``, "/" in a key written as "_") and the gradient buffer it
+    applied (``grads.npy``).  A gradient buffer longer than ``DUMP_MAX_ELEMS`` (the Large model) is written as a fixed
+    sample: the same seeded positions, in ascending order, on every run.
+
+    The updated parameters are not written: AdamW moves a parameter by lr * g / (|g| + eps), which for gradients near eps
+    turns last-bit differences of g (``training_state``) into differences of a sizeable fraction of lr."""
+    import numpy as np
+
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    arrays = {k.replace("/", "_"): v.detach().reshape(1) for k, v in scalars.items()}
+    grads = flat.grad.detach()
+    if grads.numel() > DUMP_MAX_ELEMS:
+        pick = torch.randperm(grads.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMS].sort().values
+        grads = grads[pick.to(grads.device)]
+    arrays["grads"] = grads
+    for name, value in arrays.items():
+        np.save(out / f"{name}.npy", value.float().cpu().numpy())
+
+
+def roofline(kernel_ms: dict[str, dict[str, float]], n_steps: int, ms: float, conv_mfma: str, b: int, t: int) -> dict[str, object]:
+    """``--full``: the roofline entry of the JSON line from the HIP-event kernel times of ``n_steps`` steps (``ms`` = the
+    timed step's wall time)."""
+    # dominant hand-written kernel of the step = the device kernel with the largest total time (HIP events on the
+    # launch stream).  Its algorithmic work is stated by the caller of each launch (conv.py / scan.py): conv kernels
+    # are MFMA-bound, the scan is latency-bound and is priced against HBM (DESIGN.md section 4).
+    timed = {k: v for k, v in kernel_ms.items() if v["flops"] or v["bytes"]}
+    name, row = max(timed.items(), key=lambda kv: kv[1]["total_ms"]) if timed else ("none", None)
+    roof: dict[str, object] = {"kernel": name}
+    if row:
+        secs = row["total_ms"] * 1e-3
+        if "conv" in name and "thin" not in name:
+            # algorithmic FLOPs (each multiply-add counted once) against the rate at which the MFMA pipe can deliver
+            # them in this operand format: fp32 MFMA 157.3 TFLOP/s; split kernels issue `products` bf16 MFMAs per
+            # algorithmic block, so their ceiling is the dense bf16 peak / products (bf16x2: 2500 / 3 = 833).  The roof
+            # that binds is the roofline model's: a kernel whose arithmetic intensity (algorithmic FLOPs per
+            # algorithmic byte) lies below the ridge peak / HBM rate is priced against HBM, above it against the MFMA.
+            split = any(tag in name for tag in ("split_kernel", "resident_kernel", "stream_kernel", "staged_kernel"))
+            products = MFMA_PRODUCTS[conv_mfma] if split else 1
+            peak = MFMA_BF16_PEAK_TFLOPS / products if split else MFMA_F32_PEAK_TFLOPS
+            achieved = row["flops"] / secs / 1e12
+            gbs = row["bytes"] / secs / 1e9
+            intensity = row["flops"] / row["bytes"] if row["bytes"] else float("inf")
+            ridge = peak * 1e12 / (HBM_PEAK_GBS * 1e9)
+            if intensity >= ridge:
+                roof.update(bound="mfma", achieved=achieved, peak=peak, unit="TFLOP/s", frac=achieved / peak)
+            else:
+                roof.update(bound="hbm", achieved=gbs, peak=HBM_PEAK_GBS, unit="GB/s", frac=gbs / HBM_PEAK_GBS)
+            roof.update(mfma_products_per_block=products, mfma_frac=achieved / peak, hbm_frac=gbs / HBM_PEAK_GBS,
+                        flops_per_byte=intensity, ridge_flops_per_byte=ridge,
+                        frac_of_raw_bf16_peak=achieved / MFMA_BF16_PEAK_TFLOPS)
+        else:
+            achieved = row["bytes"] / secs / 1e9
+            roof.update(bound="hbm", achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s", frac=achieved / HBM_PEAK_GBS)
+        roof.update(traffic=measured_traffic(name), launches_per_step=row["launches"] / n_steps, avg_us=row["avg_ms"] * 1e3,
+                    algorithmic_flops_per_launch=row["flops"] / row["launches"],
+                    algorithmic_bytes_per_launch=row["bytes"] / row["launches"],
+                    share_of_step=row["total_ms"] / n_steps / ms)
+    # ---- the step against the machine (never a substitute for the dominant-kernel entry above, which may be latency-bound):
+    # every library launch states its algorithmic FLOPs and bytes (conv.py / scan.py / linear.py); their sums per step,
+    # the end-to-end algorithmic I/O of SURVEY section 8d (103 KB fp32 per seq-step: inputs, targets, states, once) and the
+    # MFMA ceiling of the operand format (dense bf16 peak / products per multiply-add block)
+    products = MFMA_PRODUCTS[conv_mfma]
+    ceiling = MFMA_BF16_PEAK_TFLOPS / products if conv_mfma != "f32" else MFMA_F32_PEAK_TFLOPS
+    step_s = ms * 1e-3
+    flops_step = sum(v["flops"] for v in kernel_ms.values()) / n_steps
+    bytes_step = sum(v["bytes"] for v in kernel_ms.values()) / n_steps
+    io_step = 103.0e3 * b * t
+    roof["step"] = {
+        "algorithmic_flops": flops_step, "achieved_TFLOPs": flops_step / step_s / 1e12, "mfma_ceiling_TFLOPs": ceiling,
+        "frac_of_mfma_ceiling": flops_step / step_s / 1e12 / ceiling, "frac_of_raw_bf16_peak": flops_step / step_s / 1e12 / MFMA_BF16_PEAK_TFLOPS,
+        "sum_of_kernel_algorithmic_bytes": bytes_step, "its_GBps": bytes_step / step_s / 1e9,
+        "its_frac_of_hbm": bytes_step / step_s / 1e9 / HBM_PEAK_GBS,
+        "end_to_end_algorithmic_bytes": io_step, "end_to_end_GBps": io_step / step_s / 1e9,
+        "inter_kernel_traffic_ratio": bytes_step / io_step,
+        "library_launches_per_step": sum(v["launches"] for v in kernel_ms.values()) / n_steps,
+        "library_kernel_ms_per_step": sum(v["total_ms"] for v in kernel_ms.values()) / n_steps,
+    }
+    # the largest kernel that a pipe bounds (the dominant one above may be the latency-bound recurrence)
+    best = None
+    for k, v in kernel_ms.items():
+        if "conv" not in k or "thin" in k or not v["flops"] or not v["total_ms"]:
+            continue
+        split = any(tag in k for tag in ("split_kernel", "resident_kernel", "stream_kernel", "staged_kernel"))
+        peak = MFMA_BF16_PEAK_TFLOPS / (products if split else 1) if split else MFMA_F32_PEAK_TFLOPS
+        secs = v["total_ms"] * 1e-3
+        tf, gbs = v["flops"] / secs / 1e12, v["bytes"] / secs / 1e9
+        ridge = peak * 1e12 / (HBM_PEAK_GBS * 1e9)
+        bound_mfma = v["flops"] / max(v["bytes"], 1.0) >= ridge
+        frac = tf / peak if bound_mfma else gbs / HBM_PEAK_GBS
+        if best is None or v["total_ms"] > best[1]["total_ms"]:
+            best = (k, v, "mfma" if bound_mfma else "hbm", tf, gbs, peak, frac)
+    if best is not None:
+        k, v, bound, tf, gbs, peak, frac = best
+        roof["largest_pipe_bound"] = {"kernel": k, "bound": bound, "ms_per_step": v["total_ms"] / n_steps, "avg_us": v["avg_ms"] * 1e3,
+                                      "achieved_TFLOPs": tf, "achieved_GBps": gbs, "peak": peak if bound == "mfma" else HBM_PEAK_GBS,
+                                      "unit": "TFLOP/s" if bound == "mfma" else "GB/s", "frac": frac, "traffic": measured_traffic(k)}
+    roof["kernels"] = {k: {"launches_per_step": v["launches"] / 3, "avg_us": round(v["avg_ms"] * 1e3, 1),
+                           "ms_per_step": round(v["total_ms"] / 3, 3),
+                           "tflops": round(v["flops"] / (v["total_ms"] * 1e-3) / 1e12, 2) if v["total_ms"] else None,
+                           "gbs": round(v["bytes"] / (v["total_ms"] * 1e-3) / 1e9, 1) if v["total_ms"] else None}
+                       for k, v in sorted(kernel_ms.items(), key=lambda kv: -kv[1]["total_ms"])}
+    return roof
+
+
 class _StubModel(torch.nn.Module):
     """``--device cpu`` rehearsal only (tests/test_parallel_gloo.py): a CPU module with the model's bench-facing surface
     (``shared_step(batch, noise)`` -> loss dict, ``noise_shapes``), so that THIS file's argument parsing, self-launch, sharded
@@ -274,8 +415,13 @@ def launch_workers(n: int, script: Path | None = None, argv: list[str] | None = 
 def parse_args() -> argparse.Namespace:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline (3 more steps with per-launch HIP events), the ELBO check "
+                         "against the oracle, the data feed and the CPU baseline; a plain run prints the headline figures only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step, run from the seeded state, computed (loss terms, gradients) as float32 DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-elbo-check", action="store_true")
     ap.add_argument("--model", choices=("mrssm", "mmtrssm", "large"), default="mrssm",
@@ -297,7 +443,10 @@ def parse_args() -> argparse.Namespace:
                     help="conv MFMA operand format: bf16x2 = two bf16 pieces per fp32 operand, three products, fp32 accumulate (the mode "
                          "the parity tests run in; errors vs golden 7e-7 / 1.3e-7 / 8e-6, tests/mode_errors.py), bf16x3 = three pieces, "
                          "six products (~2^-24), f32 = fp32 MFMA, bf16 = plain bf16 operands (outside the posterior tolerance: dtype bf16)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 DTYPE_LABEL = {"bf16x2": "bf16x2-split, fp32 accumulate", "bf16x3": "bf16x3-split, fp32 accumulate", "f32": "f32", "bf16": "bf16"}
@@ -390,6 +539,7 @@ def main() -> None:  # noqa: PLR0914, PLR0915
     # global batch drawn, this rank's rows kept -- a row's trajectory does not depend on the number of ranks
     noise_source = dp.noise_source(seed=7)
     shapes = model.noise_shapes(b, t)
+    seeded = training_state(flat, opt, noise_source) if args.dump_outputs else None
 
     def eager_step() -> dict[str, torch.Tensor]:
         noise = noise_source.draw(shapes)
@@ -425,6 +575,8 @@ def main() -> None:  # noqa: PLR0914, PLR0915
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
+        if seeded is not None and i == args.steps - 1:
+            restore_training_state(flat, opt, noise_source, seeded)  # every rank: the ranks hold identical copies
         marks[i].record()
         scalars = train_step()
     marks[args.steps].record()
@@ -433,18 +585,22 @@ def main() -> None:  # noqa: PLR0914, PLR0915
     scan.check_cluster_status()  # a cluster-scan exchange that timed out would have left invalid results
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     median_ms = step_ms[len(step_ms) // 2]
-    # Kernel durations, right AFTER the timed region (HIP events around every launch cost the step ~3 %): 3 more steps
-    # with an event pair around each library launch, on the launch stream (agrees with rocprofv3 --kernel-trace --stats
-    # of this command, profiles/).
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, scalars, flat)
+    # --full: kernel durations, right AFTER the timed region (HIP events around every launch cost the step ~3 %): 3 more
+    # steps with an event pair around each library launch, on the launch stream (agrees with rocprofv3 --kernel-trace
+    # --stats of this command, profiles/).
     kernel_ms: dict[str, dict[str, float]] = {}
-    if rank == 0 and not cpu:
-        scan.KERNEL_TIMERS.enable()
-    for _ in range(3):  # EVERY rank takes these steps (each holds an all-reduce); only rank 0 times its launches
-        eager_step()  # never the captured graph: events cannot be recorded into a replay
-    sync()
-    if rank == 0 and not cpu:
-        kernel_ms = scan.KERNEL_TIMERS.summary()
-        scan.KERNEL_TIMERS.disable()
+    n_steps = 3
+    if args.full:
+        if rank == 0 and not cpu:
+            scan.KERNEL_TIMERS.enable()
+        for _ in range(n_steps):  # EVERY rank takes these steps (each holds an all-reduce); only rank 0 times its launches
+            eager_step()  # never the captured graph: events cannot be recorded into a replay
+        sync()
+        if rank == 0 and not cpu:
+            kernel_ms = scan.KERNEL_TIMERS.summary()
+            scan.KERNEL_TIMERS.disable()
     tt = torch.tensor([elapsed, median_ms], device=device, dtype=torch.float64)
     if use_dist:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -453,86 +609,6 @@ def main() -> None:  # noqa: PLR0914, PLR0915
     if rank == 0:
         seq_steps = b * world * t
         ms = elapsed / args.steps * 1e3
-        # dominant hand-written kernel of the step = the device kernel with the largest total time (HIP events on the
-        # launch stream).  Its algorithmic work is stated by the caller of each launch (conv.py / scan.py): conv kernels
-        # are MFMA-bound, the scan is latency-bound and is priced against HBM.
-        timed = {k: v for k, v in kernel_ms.items() if v["flops"] or v["bytes"]}
-        name, row = max(timed.items(), key=lambda kv: kv[1]["total_ms"]) if timed else ("none", None)
-        n_steps = 3
-        roof: dict[str, object] = {"kernel": name}
-        if row:
-            secs = row["total_ms"] * 1e-3
-            if "conv" in name and "thin" not in name:
-                # algorithmic FLOPs (each multiply-add counted once) against the rate at which the MFMA pipe can deliver
-                # them in this operand format: fp32 MFMA 157.3 TFLOP/s; split kernels issue `products` bf16 MFMAs per
-                # algorithmic block, so their ceiling is the dense bf16 peak / products (bf16x2: 2500 / 3 = 833).  The roof
-                # that binds is the roofline model's: a kernel whose arithmetic intensity (algorithmic FLOPs per
-                # algorithmic byte) lies below the ridge peak / HBM rate is priced against HBM, above it against the MFMA.
-                split = any(tag in name for tag in ("split_kernel", "resident_kernel", "stream_kernel", "staged_kernel"))
-                products = MFMA_PRODUCTS[args.conv_mfma] if split else 1
-                peak = MFMA_BF16_PEAK_TFLOPS / products if split else MFMA_F32_PEAK_TFLOPS
-                achieved = row["flops"] / secs / 1e12
-                gbs = row["bytes"] / secs / 1e9
-                intensity = row["flops"] / row["bytes"] if row["bytes"] else float("inf")
-                ridge = peak * 1e12 / (HBM_PEAK_GBS * 1e9)
-                if intensity >= ridge:
-                    roof.update(bound="mfma", achieved=achieved, peak=peak, unit="TFLOP/s", frac=achieved / peak)
-                else:
-                    roof.update(bound="hbm", achieved=gbs, peak=HBM_PEAK_GBS, unit="GB/s", frac=gbs / HBM_PEAK_GBS)
-                roof.update(mfma_products_per_block=products, mfma_frac=achieved / peak, hbm_frac=gbs / HBM_PEAK_GBS,
-                            flops_per_byte=intensity, ridge_flops_per_byte=ridge,
-                            frac_of_raw_bf16_peak=achieved / MFMA_BF16_PEAK_TFLOPS)
-            else:
-                achieved = row["bytes"] / secs / 1e9
-                roof.update(bound="hbm", achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s", frac=achieved / HBM_PEAK_GBS)
-            roof.update(traffic=measured_traffic(name), launches_per_step=row["launches"] / n_steps, avg_us=row["avg_ms"] * 1e3,
-                        algorithmic_flops_per_launch=row["flops"] / row["launches"],
-                        algorithmic_bytes_per_launch=row["bytes"] / row["launches"],
-                        share_of_step=row["total_ms"] / n_steps / ms)
-        # ---- the step against the machine (never a substitute for the dominant-kernel entry above, which may be latency-bound):
-        # every library launch states its algorithmic FLOPs and bytes (conv.py / scan.py / linear.py); their sums per step,
-        # the end-to-end algorithmic I/O of SURVEY section 8d (103 KB fp32 per seq-step: inputs, targets, states, once) and the
-        # MFMA ceiling of the operand format (dense bf16 peak / products per multiply-add block)
-        products = MFMA_PRODUCTS[args.conv_mfma]
-        ceiling = MFMA_BF16_PEAK_TFLOPS / products if args.conv_mfma != "f32" else MFMA_F32_PEAK_TFLOPS
-        step_s = ms * 1e-3
-        flops_step = sum(v["flops"] for v in kernel_ms.values()) / n_steps
-        bytes_step = sum(v["bytes"] for v in kernel_ms.values()) / n_steps
-        io_step = 103.0e3 * b * t
-        roof["step"] = {
-            "algorithmic_flops": flops_step, "achieved_TFLOPs": flops_step / step_s / 1e12, "mfma_ceiling_TFLOPs": ceiling,
-            "frac_of_mfma_ceiling": flops_step / step_s / 1e12 / ceiling, "frac_of_raw_bf16_peak": flops_step / step_s / 1e12 / MFMA_BF16_PEAK_TFLOPS,
-            "sum_of_kernel_algorithmic_bytes": bytes_step, "its_GBps": bytes_step / step_s / 1e9,
-            "its_frac_of_hbm": bytes_step / step_s / 1e9 / HBM_PEAK_GBS,
-            "end_to_end_algorithmic_bytes": io_step, "end_to_end_GBps": io_step / step_s / 1e9,
-            "inter_kernel_traffic_ratio": bytes_step / io_step,
-            "library_launches_per_step": sum(v["launches"] for v in kernel_ms.values()) / n_steps,
-            "library_kernel_ms_per_step": sum(v["total_ms"] for v in kernel_ms.values()) / n_steps,
-        }
-        # the largest kernel that a pipe bounds (the dominant one above may be the latency-bound recurrence)
-        best = None
-        for k, v in kernel_ms.items():
-            if "conv" not in k or "thin" in k or not v["flops"] or not v["total_ms"]:
-                continue
-            split = any(tag in k for tag in ("split_kernel", "resident_kernel", "stream_kernel", "staged_kernel"))
-            peak = MFMA_BF16_PEAK_TFLOPS / (products if split else 1) if split else MFMA_F32_PEAK_TFLOPS
-            secs = v["total_ms"] * 1e-3
-            tf, gbs = v["flops"] / secs / 1e12, v["bytes"] / secs / 1e9
-            ridge = peak * 1e12 / (HBM_PEAK_GBS * 1e9)
-            bound_mfma = v["flops"] / max(v["bytes"], 1.0) >= ridge
-            frac = tf / peak if bound_mfma else gbs / HBM_PEAK_GBS
-            if best is None or v["total_ms"] > best[1]["total_ms"]:
-                best = (k, v, "mfma" if bound_mfma else "hbm", tf, gbs, peak, frac)
-        if best is not None:
-            k, v, bound, tf, gbs, peak, frac = best
-            roof["largest_pipe_bound"] = {"kernel": k, "bound": bound, "ms_per_step": v["total_ms"] / n_steps, "avg_us": v["avg_ms"] * 1e3,
-                                          "achieved_TFLOPs": tf, "achieved_GBps": gbs, "peak": peak if bound == "mfma" else HBM_PEAK_GBS,
-                                          "unit": "TFLOP/s" if bound == "mfma" else "GB/s", "frac": frac, "traffic": measured_traffic(k)}
-        roof["kernels"] = {k: {"launches_per_step": v["launches"] / 3, "avg_us": round(v["avg_ms"] * 1e3, 1),
-                               "ms_per_step": round(v["total_ms"] / 3, 3),
-                               "tflops": round(v["flops"] / (v["total_ms"] * 1e-3) / 1e12, 2) if v["total_ms"] else None,
-                               "gbs": round(v["bytes"] / (v["total_ms"] * 1e-3) / 1e9, 1) if v["total_ms"] else None}
-                           for k, v in sorted(kernel_ms.items(), key=lambda kv: -kv[1]["total_ms"])}
         line = {
             "metric": {"mrssm": "seq-steps/s (BxT) MoPoE-MRSSM train step", "mmtrssm": "seq-steps/s (BxT) MoPoE-MMTRSSM train step",
                        "large": "seq-steps/s (BxT) MoPoE-MRSSM Large train step"}[args.model],
@@ -567,17 +643,18 @@ def main() -> None:  # noqa: PLR0914, PLR0915
                               "f32": "fp32 MFMA", "bf16": "bf16 operands, fp32 accumulate; tensors, scan, losses, optimizer fp32"}[args.conv_mfma],
             },
             "loss": float(scalars["loss"]),
-            "roofline": roof,
         }
-        if not args.no_elbo_check:
+        if args.full:
+            line["roofline"] = roofline(kernel_ms, n_steps, ms, args.conv_mfma, b, t)
+        if args.full and not args.no_elbo_check:
             # "ELBO delta vs ref" (the metric's second half): the trained weights of THIS run against the oracle on a 2-row
             # sub-batch, outside the timed region
             delta = elbo_delta(model, batch, args.model)
             line["elbo_rel_delta"] = delta["loss"]
             line["elbo_check"] = delta
-        if world == 1 and not cpu:
+        if args.full and world == 1 and not cpu:
             line["data_feed"] = feed_benchmark(device)
-        if not args.no_cpu_baseline and world == 1 and args.model != "large":  # (Large: one CPU step takes minutes)
+        if args.full and not args.no_cpu_baseline and world == 1 and args.model != "large":  # (Large: one CPU step takes minutes)
             base = cpu_baseline(args.model)
             line["cpu_baseline"] = base
             line["speedup_vs_cpu"] = line["value"] / base["value"]

@@ -1,12 +1,14 @@
 """CPU: the C-ABI library loads and exports every symbol ``include/mtrssm.h`` declares.
 
-No compute call is made here (there is no GPU): argument validation returns before any launch.
+No compute call is made here (none needs a GPU): argument validation returns before any launch.
 """
 
 from __future__ import annotations
 
 import ctypes as C
 import re
+import subprocess
+import sys
 from pathlib import Path
 
 import pytest
@@ -15,6 +17,14 @@ from multimodal_mtrssm_amd import _lib
 
 ROOT = Path(__file__).resolve().parents[1]
 HEADER = (ROOT / "include" / "mtrssm.h").read_text()
+
+
+def device_cu_count() -> int:
+    """CU count of device 0, 0 without a device.  Asked in a child process: this module needs no GPU and leaves the
+    GPU runtime of the test process as it found it."""
+    code = "import torch; print(torch.cuda.get_device_properties(0).multi_processor_count if torch.cuda.is_available() else 0)"
+    run = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, check=True)
+    return int(run.stdout.split()[-1])
 
 
 def declared_functions() -> list[str]:
@@ -113,8 +123,11 @@ def test_invalid_arguments_are_rejected_without_a_launch() -> None:
     assert lib.mtrssm_residual_block_fwd_supported(C.byref(block_geom(5, 64))) == 0   # two frames per tile: whole tiles only
     assert lib.mtrssm_residual_block_fwd_supported(C.byref(block_geom(6, 64, act=3))) == 0  # Tanh has no fused instance
     assert lib.mtrssm_residual_block_fwd_supported(C.byref(block_geom(6, 64, pre=0))) == 0  # not a residual block's first conv
+    # the wide and cluster scans size their grids by the device's CU count (0 without a device): the Large dims need 128 CUs
+    # for the wide scan, the bench dims 256 for the cluster scan
+    cus = device_cu_count()
     large = _lib.MrssmDims(32, 100, 1024, 1024, 16, 8, 2, 1, 0.2, 0.8, 0, 0)
-    assert lib.mtrssm_mrssm_wide_supported(C.byref(large), 3) == 0  # no device here: the grid cannot be sized
+    assert lib.mtrssm_mrssm_wide_supported(C.byref(large), 3) == int(cus >= 128)
     assert lib.mtrssm_mrssm_wide_workspace_bytes(C.byref(large), 3) > 60e6  # six bytes per weight of the ~10 M scan weights
     assert lib.mtrssm_mrssm_wide_bwd_workspace_bytes(C.byref(large), 2) > 40e6
     assert lib.mtrssm_mrssm_wide_workspace_bytes(C.byref(large), 4) == 0  # pieces: 2 or 3
@@ -123,7 +136,7 @@ def test_invalid_arguments_are_rejected_without_a_launch() -> None:
     assert lib.mtrssm_mrssm_rollout_fwd_wide(C.byref(large), C.byref(_lib.MrssmClusterWeights()), C.byref(_lib.MrssmFwdIO()), 3, None, 0, None) == -1
     assert b"wide" in lib.mtrssm_last_error()
     assert lib.mtrssm_mrssm_rollout_bwd_wide(C.byref(large), C.byref(_lib.MrssmClusterWeights()), C.byref(_lib.MrssmBwdIO()), 3, None, 0, None) == -1
-    assert lib.mtrssm_mrssm_cluster_supported(C.byref(_lib.MrssmDims(64, 50, 200, 200, 6, 5, 2, 1, 0.2, 0.8, 0, 0))) == 0  # no CUs to count
+    assert lib.mtrssm_mrssm_cluster_supported(C.byref(_lib.MrssmDims(64, 50, 200, 200, 6, 5, 2, 1, 0.2, 0.8, 0, 0))) == int(cus >= 256)
 
 
 def test_missing_library_fails_loudly(monkeypatch: pytest.MonkeyPatch, tmp_path: Path) -> None:

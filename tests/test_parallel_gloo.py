@@ -156,3 +156,49 @@ def test_bench_main_runs_two_ranks_end_to_end_and_fails_when_a_rank_dies() -> No
     dead = subprocess.run(cmd, capture_output=True, text=True, env=dict(env, MTRSSM_BENCH_REHEARSAL_DIE_RANK="1"), timeout=300, check=False)
     assert dead.returncode != 0
     assert not [ln for ln in dead.stdout.splitlines() if ln.startswith("{")]
+
+
+def test_bench_dump_outputs_are_reproducible_and_full_adds_the_extras(tmp_path: Path) -> None:
+    """``bench.py --dump-outputs DIR`` (the ``--device cpu`` rehearsal, two ranks): rank 0 writes the last timed step's loss
+    terms and gradients as float32 ``.npy``.  That step starts from the seeded state, so a second run writes the
+    same arrays even with other step counts and ``--full`` (whose extra measurements come after the dump).  A plain line
+    carries no roofline, a ``--full`` one does."""
+    import json
+    import subprocess
+
+    import numpy as np
+
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    lines, dirs = [], [tmp_path / "plain", tmp_path / "full"]
+    for d, extra in zip(dirs, (["--steps", "3", "--warmup", "1"], ["--steps", "4", "--warmup", "2", "--full"]), strict=True):
+        cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--device", "cpu", "--dump-outputs", str(d), *extra]
+        run = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=300, check=False)
+        assert run.returncode == 0, run.stderr[-2000:]
+        lines.append(json.loads(run.stdout.strip().splitlines()[-1]))
+    assert "roofline" not in lines[0] and "roofline" in lines[1]
+    names = sorted(p.name for p in dirs[0].glob("*.npy"))
+    assert names == sorted(p.name for p in dirs[1].glob("*.npy"))
+    assert {"loss.npy", "recon.npy", "kl.npy", "grads.npy"} <= set(names) and "params.npy" not in names
+    for name in names:
+        a, b = np.load(dirs[0] / name), np.load(dirs[1] / name)
+        assert a.dtype == np.float32 and np.array_equal(a, b), name
+    assert np.load(dirs[0] / "grads.npy").size == lines[0]["config"]["params"]
+    assert float(np.load(dirs[0] / "loss.npy")[0]) == np.float32(lines[0]["loss"])
+
+
+def test_bench_dump_outputs_samples_a_large_buffer_at_fixed_positions(tmp_path: Path, monkeypatch) -> None:  # noqa: ANN001
+    import types
+
+    import numpy as np
+
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 100)
+    flat = types.SimpleNamespace(param=torch.zeros(1000), grad=torch.arange(1000, dtype=torch.float32))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"recon/audio": torch.tensor(2.5)}, flat)
+    g = np.load(tmp_path / "a" / "grads.npy")
+    assert g.shape == (100,) and (np.diff(g) > 0).all() and g[-1] > 100  # ascending positions from the whole buffer
+    assert np.array_equal(g, np.load(tmp_path / "b" / "grads.npy"))
+    assert np.load(tmp_path / "a" / "recon_audio.npy").tolist() == [2.5]

@@ -5,7 +5,7 @@ ROOT=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp && cd $ROOT && export PYTHONPATH=$ROOT
 OUT=gpurun_out/quick
 rm -rf $OUT && mkdir -p $OUT
-rocprofv3 --kernel-trace --stats -d $OUT/stats -o bench --output-format csv -- python3 bench.py --steps 25 --warmup 3 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/stats.log || exit 1
+rocprofv3 --kernel-trace --stats -d $OUT/stats -o bench --output-format csv -- python3 bench.py --full --steps 25 --warmup 3 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/stats.log || exit 1
 find $OUT -name "*kernel_trace.csv" -delete
 python3 - "$OUT/stats/bench_kernel_stats.csv" "${1:-.}" <<'PY'
 import csv, re, sys

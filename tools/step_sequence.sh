@@ -5,7 +5,7 @@ ROOT=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp && cd $ROOT && export PYTHONPATH=$ROOT
 OUT=gpurun_out/seq
 rm -rf $OUT && mkdir -p $OUT
-rocprofv3 --kernel-trace -d $OUT/t -o k --output-format csv -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-elbo-check "$@" > $OUT/bench.json 2> $OUT/log.txt || exit 1
+rocprofv3 --kernel-trace -d $OUT/t -o k --output-format csv -- python3 bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-elbo-check "$@" > $OUT/bench.json 2> $OUT/log.txt || exit 1
 python3 - <<'PY'
 import csv, glob, re
 f = glob.glob("gpurun_out/seq/t/**/*kernel_trace.csv", recursive=True)[0]
