@@ -117,6 +117,7 @@ typedef struct MtrssmMrssmFwdIO {
   float* sv_heads;      /* [B,T,3H] act of prior / audio / vision head layer 0 */
   float* sv_la;         /* [B,T,S]  audio logits */
   float* sv_lv;         /* [B,T,S]  vision logits */
+  const int32_t* modality; /* [B,T] bit0 audio, bit1 vision; NULL = both everywhere */
 } MtrssmMrssmFwdIO;
 
 int mtrssm_mrssm_rollout_fwd(const MtrssmMrssmDims* dims, const MtrssmMrssmFwdWeights* w,
@@ -196,6 +197,7 @@ typedef struct MtrssmMrssmBwdIO {
   float* d_lp;      /* [B,T,S]  grad at prior logits */
   float* d_la;      /* [B,T,S]  grad at audio logits */
   float* d_lv;      /* [B,T,S]  grad at vision logits */
+  const int32_t* modality; /* [B,T] bit0 audio, bit1 vision; NULL = both everywhere */
 } MtrssmMrssmBwdIO;
 
 /* The reverse-time scan on the same four-CU clusters (csrc/mrssm_cluster.hip: mrssm_bwd_cluster_kernel): weights as in
@@ -310,6 +312,7 @@ typedef struct MtrssmMmtrssmFwdIO {
   float* sv_h1;           /* [B,T,H]  act of h_prior layer 0 */
   float* sv_la;           /* [B,T,LS] */
   float* sv_lv;           /* [B,T,LS] */
+  const int32_t* modality; /* [B,T] bit0 audio, bit1 vision; NULL = both everywhere */
 } MtrssmMmtrssmFwdIO;
 
 int mtrssm_mmtrssm_rollout_fwd(const MtrssmMmtrssmDims* dims, const MtrssmMmtrssmFwdWeights* w,
@@ -373,6 +376,7 @@ typedef struct MtrssmMmtrssmBwdIO {
   float* d_lv;    /* [B,T,LS] */
   float* d_lph;   /* [B,T,HS] grad at higher prior logits */
   float* d_lqh;   /* [B,T,HS] grad at higher posterior logits */
+  const int32_t* modality; /* [B,T] bit0 audio, bit1 vision; NULL = both everywhere */
 } MtrssmMmtrssmBwdIO;
 
 int mtrssm_mmtrssm_rollout_bwd(const MtrssmMmtrssmDims* dims, const MtrssmMmtrssmBwdWeights* w,
@@ -590,6 +594,17 @@ int mtrssm_gaussian_nll_fwd(const float* pred, const float* target, int64_t fram
                             float* out, void* stream);
 int mtrssm_gaussian_nll_bwd(const float* pred, const float* target, const float* g_out,
                             int64_t frames, int64_t event, int32_t act, float* g_pred, void* stream);
+
+/* The same loss over the frames where a modality is present (missing-modality training, DESIGN.md section "Missing
+ * modalities"): present[n] in {0, 1} per frame, count = sum_n present[n],
+ *   nll = sum_n present[n] sum_e [ 0.5 (target - pred)^2 + 0.5 log(2 pi) ] / count   (0 when count = 0),
+ * d pred = g_out * present[n] * (act(pred) - target) * act'(pred) / count (0 when count = 0).  `count` is a device scalar
+ * (float) the caller forms, so neither call reads anything back to the host.  With every frame present the result is bitwise
+ * the unmasked call's.  Null pointers, non-positive sizes or frames * event >= 2^31 return -1 without a launch. */
+int mtrssm_gaussian_nll_masked_fwd(const float* pred, const float* target, const float* present, const float* count,
+                                   int64_t frames, int64_t event, int32_t act, float* out, void* stream);
+int mtrssm_gaussian_nll_masked_bwd(const float* pred, const float* target, const float* present, const float* count,
+                                   const float* g_out, int64_t frames, int64_t event, int32_t act, float* g_pred, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Fused AdamW over one flat fp32 parameter buffer, with global-norm gradient clipping

@@ -160,6 +160,61 @@ def _rand(like: Tensor, *shape: int) -> Tensor:
     return torch.rand(shape, device=like.device, dtype=torch.float32)
 
 
+def _check_modality_mask(mask: Tensor, B: int, T: int | None, device: torch.device, *, first_step: bool) -> None:  # noqa: N803
+    """Host-side checks of a modality mask (DESIGN.md "Missing modalities"): bool ``[B, T, 2]`` (``[B, 2]`` when ``T`` is
+    None) on ``device``; ``first_step``: every row observes something at t = 0 (the initial state averages those embeddings)."""
+    shape = (B, 2) if T is None else (B, T, 2)
+    if not isinstance(mask, Tensor) or mask.dtype != torch.bool:
+        msg = f"modality_mask must be a bool tensor, got {getattr(mask, 'dtype', type(mask))}"
+        raise ValueError(msg)
+    if tuple(mask.shape) != shape:
+        msg = f"modality_mask must have shape {shape} (ordered audio, vision), got {tuple(mask.shape)}"
+        raise ValueError(msg)
+    if mask.device != torch.device(device):
+        msg = f"modality_mask is on {mask.device}, the model's tensors on {device}"
+        raise ValueError(msg)
+    if first_step:
+        m0 = mask if T is None else mask[:, 0]
+        if not bool(m0.any(dim=-1).all()):
+            msg = "modality_mask: every row must observe at least one modality at t = 0 (the initial state needs an embedding)"
+            raise ValueError(msg)
+
+
+def _absent_mask(observations: tuple, B: int, T: int, device: torch.device) -> Tensor:  # noqa: N803
+    """The mask an observation tuple with ``None`` entries stands for: a None modality is absent at every step."""
+    present = torch.tensor([observations[0] is not None, observations[1] is not None], device=device)
+    return present.expand(B, T, 2)
+
+
+def _resolve_modality_mask(observations: tuple, mask: Tensor | None, B: int, T: int, device: torch.device) -> Tensor | None:  # noqa: N803
+    """Validated mask of a rollout (None: both modalities everywhere, the unmasked kernels).  A None observation must be
+    masked out at every step."""
+    if observations[0] is None and observations[1] is None:
+        msg = "observations: at least one of (audio_obs, vision_obs) must be given"
+        raise ValueError(msg)
+    if mask is None:
+        if observations[0] is None or observations[1] is None:
+            return _absent_mask(observations, B, T, device)
+        return None
+    _check_modality_mask(mask, B, T, device, first_step=False)
+    for j, name in enumerate(("audio", "vision")):
+        if observations[j] is None and bool(mask[..., j].any()):
+            msg = f"modality_mask marks {name} present, but observations carries None for it"
+            raise ValueError(msg)
+    return mask
+
+
+def _masked_mean_embed(ea: Tensor | None, ev: Tensor | None, mask0: Tensor | None) -> Tensor:
+    """t = 0 embedding: the mean over the present modalities of each row; both present is exactly ``(ea + ev) / 2``."""
+    if ea is None or ev is None:
+        return ea if ev is None else ev
+    both = (ea + ev) / 2.0
+    if mask0 is None:
+        return both
+    a, v = mask0[:, 0:1], mask0[:, 1:2]
+    return torch.where(a & v, both, torch.where(a, ea, ev))
+
+
 class MoPoE_MRSSM(_Base):  # noqa: N801
     """Multimodal RSSM with MoPoE posteriors: PoE of {audio, vision}, then MoE over {A, V, A+V}."""
 
@@ -208,22 +263,39 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
     def get_targets_from_batch(batch: tuple[Tensor, ...]) -> dict[str, Tensor]:
         return {"recon/audio": batch[4], "recon/vision": batch[5]}
 
+    @staticmethod
+    def get_modality_mask_from_batch(batch: tuple[Tensor, ...]) -> Tensor | None:
+        """The optional 7th batch entry: bool ``[B, T, 2]`` (audio, vision), True = observed.  None for the reference's
+        6-tuple (both modalities everywhere)."""
+        return batch[6] if len(batch) > 6 else None  # noqa: PLR2004
+
     # -- encoders / decoders / losses ---------------------------------------------------------
-    def encode_observation(self, observation: tuple[Tensor, Tensor] | Tensor) -> Tensor:
+    def encode_observation(self, observation: tuple[Tensor, Tensor] | Tensor, modality_mask: Tensor | None = None) -> Tensor:
+        """Fused t = 0 embedding: the mean of the present modalities' embeddings (``modality_mask``: bool ``[B, 2]``; a None
+        entry of the tuple is absent for every row and its encoder is not run)."""
         if isinstance(observation, tuple):
             audio_obs, vision_obs = observation
-            return (self.audio_encoder(audio_obs) + self.vision_encoder(vision_obs)) / 2.0
+            ea = None if audio_obs is None else self.audio_encoder(audio_obs)
+            ev = None if vision_obs is None else self.vision_encoder(vision_obs)
+            if ea is None and ev is None:
+                msg = "observation: at least one of (audio_obs, vision_obs) must be given"
+                raise ValueError(msg)
+            return _masked_mean_embed(ea, ev, modality_mask)
         return observation
 
     def decode_state(self, state: State | MTState) -> dict[str, Tensor]:
         return {"recon/audio": self.audio_decoder(state.feature), "recon/vision": self.vision_decoder(state.feature)}
 
     @staticmethod
-    def compute_reconstruction_loss(reconstructions: dict[str, Tensor], targets: dict[str, Tensor]) -> dict[str, Tensor]:
-        audio = likelihood(prediction=reconstructions["recon/audio"], target=targets["recon/audio"], event_ndims=3)
-        vision = likelihood(prediction=reconstructions["recon/vision"], target=targets["recon/vision"], event_ndims=3)
-        if not sum_recon:  # (shared_step adds them in its fused scalar epilogue)
-            return {"recon/audio": audio, "recon/vision": vision}
+    def compute_reconstruction_loss(reconstructions: dict[str, Tensor], targets: dict[str, Tensor],
+                                    modality_mask: Tensor | None = None) -> dict[str, Tensor]:
+        """``mrssm core.py:279-308``.  ``modality_mask`` (bool ``[B, T, 2]``): each modality's NLL averages over the frames
+        where it is present (0 where it is present nowhere)."""
+        fa = fv = None
+        if modality_mask is not None:
+            fa, fv = modality_mask[..., 0], modality_mask[..., 1]
+        audio = likelihood(prediction=reconstructions["recon/audio"], target=targets["recon/audio"], event_ndims=3, frame_mask=fa)
+        vision = likelihood(prediction=reconstructions["recon/vision"], target=targets["recon/vision"], event_ndims=3, frame_mask=fv)
         return {"recon": audio + vision, "recon/audio": audio, "recon/vision": vision}
 
     def _encode_both(self, audio_obs: Tensor, vision_obs: Tensor) -> tuple[Tensor, Tensor]:
@@ -232,7 +304,8 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
             return cnn.encode_pair(self.audio_encoder, self.vision_encoder, audio_obs, vision_obs)
         return self.audio_encoder(audio_obs), self.vision_encoder(vision_obs)
 
-    def _reconstruction_losses(self, feature: Tensor, targets: dict[str, Tensor], *, sum_recon: bool = True) -> dict[str, Tensor]:
+    def _reconstruction_losses(self, feature: Tensor, targets: dict[str, Tensor], *, sum_recon: bool = True,
+                               modality_mask: Tensor | None = None) -> dict[str, Tensor]:
         """``decode_state`` + ``compute_reconstruction_loss`` (``mrssm core.py:262-308``).  With this package's decoders the
         out_activation (Tanh) is applied inside the NLL kernels: the activated reconstructions are never written in training."""
         da, dv = self.audio_decoder, self.vision_decoder
@@ -243,8 +316,13 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
             pa, pv = da(feature, raw=True), dv(feature, raw=True)
         else:
             pa, pv = da(feature), dv(feature)
-        audio = likelihood(prediction=pa, target=targets["recon/audio"], event_ndims=3, out_act=da.out_act_id if fused else 0)
-        vision = likelihood(prediction=pv, target=targets["recon/vision"], event_ndims=3, out_act=dv.out_act_id if fused else 0)
+        fa = fv = None
+        if modality_mask is not None:
+            fa, fv = modality_mask[..., 0], modality_mask[..., 1]
+        audio = likelihood(prediction=pa, target=targets["recon/audio"], event_ndims=3, out_act=da.out_act_id if fused else 0,
+                           frame_mask=fa)
+        vision = likelihood(prediction=pv, target=targets["recon/vision"], event_ndims=3, out_act=dv.out_act_id if fused else 0,
+                            frame_mask=fv)
         if not sum_recon:  # (shared_step adds them in its fused scalar epilogue)
             return {"recon/audio": audio, "recon/vision": vision}
         return {"recon": audio + vision, "recon/audio": audio, "recon/vision": vision}
@@ -256,10 +334,25 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         dist, stoch = _sampled_head(self.representation.distribution_factory, logits, u_init)
         return State(deter=deter, distribution=dist, stoch=stoch)
 
-    def initial_state(self, observation: tuple[Tensor, Tensor] | Tensor, noise: Noise | None = None) -> State:
-        """``core.py:121-135``: fused embedding -> ``init_proj`` -> prior head -> sampled State."""
+    def _initial_embed(self, observation: tuple[Tensor, Tensor] | Tensor, modality_mask: Tensor | None) -> Tensor:
+        if modality_mask is not None:
+            if not isinstance(observation, tuple):
+                msg = "modality_mask needs the (audio_obs, vision_obs) tuple"
+                raise ValueError(msg)
+            ref = observation[0] if observation[0] is not None else observation[1]
+            _check_modality_mask(modality_mask, ref.shape[0], None, ref.device, first_step=True)
+            for j, name in enumerate(("audio", "vision")):
+                if observation[j] is None and bool(modality_mask[:, j].any()):
+                    msg = f"modality_mask marks {name} present, but the observation carries None for it"
+                    raise ValueError(msg)
+        return self.encode_observation(observation, modality_mask)
+
+    def initial_state(self, observation: tuple[Tensor, Tensor] | Tensor, noise: Noise | None = None,
+                      modality_mask: Tensor | None = None) -> State:
+        """``core.py:121-135``: fused embedding -> ``init_proj`` -> prior head -> sampled State.  ``modality_mask``: bool
+        ``[B, 2]`` (audio, vision) of the t = 0 frame; the embedding is the mean over the present modalities."""
         u = None if noise is None else noise.get("u_init")
-        return self._initial_from_embed(self.encode_observation(observation), u).to(self.device)
+        return self._initial_from_embed(self._initial_embed(observation, modality_mask), u).to(self.device)
 
     def noise_shapes(self, batch: int, steps: int) -> dict[str, tuple[int, ...]]:
         """Uniforms one ``shared_step`` consumes (one per categorical and draw; row = batch row).  Data-parallel runs
@@ -267,8 +360,8 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         k = self.transition.distribution_factory.category_size
         return {"u_init": (batch, k), "u_post": (batch, steps, k)}
 
-    def _rollout_embedded(self, actions: Tensor, audio_embed: Tensor, vision_embed: Tensor, prev_state: State,
-                          noise: Noise | None, *, sample_prior: bool) -> dict[str, Tensor]:
+    def _rollout_embedded(self, actions: Tensor, audio_embed: Tensor | None, vision_embed: Tensor | None, prev_state: State,  # noqa: PLR0913
+                          noise: Noise | None, *, sample_prior: bool, modality: Tensor | None = None) -> dict[str, Tensor]:
         noise = noise or {}
         B, T = actions.shape[:2]
         K = self.transition.distribution_factory.category_size
@@ -281,7 +374,7 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         return scan.mrssm_posterior_rollout(
             self.transition, self.audio_representation, self.vision_representation, actions, audio_embed, vision_embed,
             prev_state.deter, prev_state.stoch, u_post, u_prior, balancing=bool(self.use_kl_balancing),
-            rows_per_block=self.scan_rows_per_block, threads=self.scan_threads,
+            rows_per_block=self.scan_rows_per_block, threads=self.scan_threads, modality=modality,
         )
 
     def _states_from_rollout(self, out: dict[str, Tensor]) -> tuple[State, State]:
@@ -298,14 +391,23 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         observations: Tensor | tuple[Tensor, ...],
         prev_state: State,
         noise: Noise | None = None,
+        modality_mask: Tensor | None = None,
     ) -> tuple[State, State]:
-        """``mrssm core.py:184-260``: returns (mixed posterior, prior), each ``[B, T, .]``."""
+        """``mrssm core.py:184-260``: returns (mixed posterior, prior), each ``[B, T, .]``.
+
+        ``modality_mask``: optional bool ``[B, T, 2]`` (audio, vision), True = observed.  At each (b, t) the posterior mixes
+        the present modalities only; with none present it is the prior (DESIGN.md "Missing modalities").  An entry of
+        ``observations`` may be None: that modality is absent at every step and its encoder is not run."""
         if not isinstance(observations, tuple):
             msg = "MoPoE-MRSSM requires tuple of (audio_obs, vision_obs)"
             raise TypeError(msg)
         audio_obs, vision_obs = observations
-        out = self._rollout_embedded(actions, self.audio_encoder(audio_obs), self.vision_encoder(vision_obs), prev_state,
-                                     noise, sample_prior=True)
+        B, T = actions.shape[:2]
+        mask = _resolve_modality_mask(observations, modality_mask, B, T, actions.device)
+        codes = None if mask is None else scan.modality_codes(mask)
+        audio_embed = None if audio_obs is None else self.audio_encoder(audio_obs)
+        vision_embed = None if vision_obs is None else self.vision_encoder(vision_obs)
+        out = self._rollout_embedded(actions, audio_embed, vision_embed, prev_state, noise, sample_prior=True, modality=codes)
         return self._states_from_rollout(out)
 
     def rollout_transition(self, *, actions: Tensor, prev_state: State, noise: Noise | None = None) -> State:
@@ -317,17 +419,30 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         return State(deter=out["deter"], distribution=dist, stoch=out["prior_stoch"])
 
     # -- train / val ----------------------------------------------------------------------------
-    def shared_step(self, batch: tuple[Tensor, ...], noise: Noise | None = None) -> dict[str, Tensor]:
-        """``core.py:187-221``: ``loss = recon + kl_coeff * KL(post || prior)``."""
+    def _step_mask(self, batch: tuple[Tensor, ...], modality_mask: Tensor | None) -> tuple[Tensor | None, Tensor | None]:
+        """(mask, scan codes) of a training step: the kwarg, else the batch's 7th entry; validated on the host."""
+        mask = modality_mask if modality_mask is not None else self.get_modality_mask_from_batch(batch)
+        if mask is None:
+            return None, None
+        B, T = batch[0].shape[:2]
+        _check_modality_mask(mask, B, T, batch[0].device, first_step=True)
+        return mask, scan.modality_codes(mask)
+
+    def shared_step(self, batch: tuple[Tensor, ...], noise: Noise | None = None, modality_mask: Tensor | None = None) -> dict[str, Tensor]:
+        """``core.py:187-221``: ``loss = recon + kl_coeff * KL(post || prior)``.  ``modality_mask`` (or a 7th batch entry,
+        bool ``[B, T, 2]``): each recon term averages over the frames where its modality is present; the KL stays the mean over
+        all B*T (0 on steps with no modality)."""
         action_input = batch[0]
+        mask, codes = self._step_mask(batch, modality_mask)
         audio_obs, vision_obs = self.get_observations_from_batch(batch)
         conv.begin_step(audio_obs.device)
         audio_embed, vision_embed = self._encode_both(audio_obs, vision_obs)
         u_init = None if noise is None else noise.get("u_init")
-        state0 = self._initial_from_embed((audio_embed[:, 0] + vision_embed[:, 0]) / 2.0, u_init)
-        out = self._rollout_embedded(action_input, audio_embed, vision_embed, state0, noise, sample_prior=False)
+        state0 = self._initial_from_embed(_masked_mean_embed(audio_embed[:, 0], vision_embed[:, 0], None if mask is None else mask[:, 0]),
+                                          u_init)
+        out = self._rollout_embedded(action_input, audio_embed, vision_embed, state0, noise, sample_prior=False, modality=codes)
         feature = torch.cat([out["deter"], out["post_stoch"]], dim=-1)
-        parts = self._reconstruction_losses(feature, self.get_targets_from_batch(batch), sum_recon=False)
+        parts = self._reconstruction_losses(feature, self.get_targets_from_batch(batch), sum_recon=False, modality_mask=mask)
         recon, kl_div, _, loss = _elbo(parts["recon/audio"], parts["recon/vision"], out["kl"], float(self.kl_coeff))
         return {"recon": recon, **parts, "kl": kl_div, "loss": loss}
 
@@ -415,9 +530,11 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
             stoch_h=stoch_h, stoch_l=stoch_l,
         )
 
-    def initial_state(self, observation: tuple[Tensor, Tensor] | Tensor, noise: Noise | None = None) -> MTState:  # type: ignore[override]
-        """``mmtrssm core.py:321-362``: ``init_proj`` output split into raw hiddens = deters (no tanh at t=0)."""
-        obs_embed = self.encode_observation(observation) if isinstance(observation, tuple) else observation
+    def initial_state(self, observation: tuple[Tensor, Tensor] | Tensor, noise: Noise | None = None,  # type: ignore[override]
+                      modality_mask: Tensor | None = None) -> MTState:
+        """``mmtrssm core.py:321-362``: ``init_proj`` output split into raw hiddens = deters (no tanh at t=0).
+        ``modality_mask``: as ``MoPoE_MRSSM.initial_state``."""
+        obs_embed = self._initial_embed(observation, modality_mask) if isinstance(observation, tuple) else observation
         return self._initial_from_embed(obs_embed, noise).to(obs_embed.device)
 
     def noise_shapes(self, batch: int, steps: int) -> dict[str, tuple[int, ...]]:  # type: ignore[override]
@@ -429,8 +546,9 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
         return {"deter_l": state.deter_l, "deter_h": state.deter_h, "hidden_l": state.hidden_l, "hidden_h": state.hidden_h,
                 "stoch_l": state.stoch_l, "stoch_h": state.stoch_h}
 
-    def _rollout_embedded(self, actions: Tensor, audio_embed: Tensor, vision_embed: Tensor, prev_state: MTState,  # type: ignore[override]
-                          noise: Noise | None, *, sample_prior: bool) -> dict[str, Tensor]:
+    def _rollout_embedded(self, actions: Tensor, audio_embed: Tensor | None, vision_embed: Tensor | None,  # type: ignore[override]  # noqa: PLR0913
+                          prev_state: MTState, noise: Noise | None, *, sample_prior: bool,
+                          modality: Tensor | None = None) -> dict[str, Tensor]:
         noise = dict(noise or {})
         B, T = actions.shape[:2]
         KL, KH = self.l_dist.category_size, self.h_dist.category_size
@@ -442,7 +560,7 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
                 if noise.get(key) is None:
                     noise[key] = _rand(actions, B, T, k)
         return scan.mmtrssm_posterior_rollout(self, actions, audio_embed, vision_embed, self._state_dict_of(prev_state), noise,
-                                              rows_per_block=self.scan_rows_per_block, threads=self.scan_threads)
+                                              rows_per_block=self.scan_rows_per_block, threads=self.scan_threads, modality=modality)
 
     def _states_from_rollout(self, out: dict[str, Tensor]) -> tuple[MTState, MTState]:  # type: ignore[override]
         common = dict(deter_h=out["deter_h"], deter_l=out["deter_l"], hidden_h=out["hidden_h"], hidden_l=out["hidden_l"])
@@ -460,14 +578,23 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
         observations: Tensor | tuple[Tensor, ...],
         prev_state: MTState,
         noise: Noise | None = None,
+        modality_mask: Tensor | None = None,
     ) -> tuple[MTState, MTState]:
-        """``mmtrssm core.py:364-494``."""
+        """``mmtrssm core.py:364-494``.
+
+        ``modality_mask``: optional bool ``[B, T, 2]`` (audio, vision), True = observed.  At each (b, t) the posterior mixes
+        the present modalities only; with none present it is the prior (DESIGN.md "Missing modalities").  An entry of
+        ``observations`` may be None: that modality is absent at every step and its encoder is not run."""
         if not isinstance(observations, tuple):
             msg = "MoPoE-MMTRSSM requires tuple of (audio_obs, vision_obs)"
             raise TypeError(msg)
         audio_obs, vision_obs = observations
-        out = self._rollout_embedded(actions, self.audio_encoder(audio_obs), self.vision_encoder(vision_obs), prev_state,
-                                     noise, sample_prior=True)
+        B, T = actions.shape[:2]
+        mask = _resolve_modality_mask(observations, modality_mask, B, T, actions.device)
+        codes = None if mask is None else scan.modality_codes(mask)
+        audio_embed = None if audio_obs is None else self.audio_encoder(audio_obs)
+        vision_embed = None if vision_obs is None else self.vision_encoder(vision_obs)
+        out = self._rollout_embedded(actions, audio_embed, vision_embed, prev_state, noise, sample_prior=True, modality=codes)
         return self._states_from_rollout(out)
 
     def rollout_transition(self, *, actions: Tensor, prev_state: MTState, noise: Noise | None = None) -> MTState:  # type: ignore[override]
@@ -480,16 +607,19 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
             stoch_h=out["prior_stoch_h"], stoch_l=out["prior_stoch_l"],
         )
 
-    def shared_step(self, batch: tuple[Tensor, ...], noise: Noise | None = None) -> dict[str, Tensor]:
-        """``mmtrssm core.py:563-606``: ``loss = recon + kl_coeff KL_l + kl_coeff w_kl_h KL_h``."""
+    def shared_step(self, batch: tuple[Tensor, ...], noise: Noise | None = None, modality_mask: Tensor | None = None) -> dict[str, Tensor]:
+        """``mmtrssm core.py:563-606``: ``loss = recon + kl_coeff KL_l + kl_coeff w_kl_h KL_h``.  ``modality_mask``: as
+        ``MoPoE_MRSSM.shared_step``."""
         action_input = batch[0]
+        mask, codes = self._step_mask(batch, modality_mask)
         audio_obs, vision_obs = self.get_observations_from_batch(batch)
         conv.begin_step(audio_obs.device)
         audio_embed, vision_embed = self._encode_both(audio_obs, vision_obs)
-        state0 = self._initial_from_embed((audio_embed[:, 0] + vision_embed[:, 0]) / 2.0, noise)
-        out = self._rollout_embedded(action_input, audio_embed, vision_embed, state0, noise, sample_prior=False)
+        state0 = self._initial_from_embed(_masked_mean_embed(audio_embed[:, 0], vision_embed[:, 0], None if mask is None else mask[:, 0]),
+                                          noise)
+        out = self._rollout_embedded(action_input, audio_embed, vision_embed, state0, noise, sample_prior=False, modality=codes)
         feature = torch.cat([out["deter_h"], out["post_stoch_h"], out["deter_l"], out["post_stoch_l"]], dim=-1)
-        parts = self._reconstruction_losses(feature, self.get_targets_from_batch(batch), sum_recon=False)
+        parts = self._reconstruction_losses(feature, self.get_targets_from_batch(batch), sum_recon=False, modality_mask=mask)
         recon, kl_div_l, kl_div_h, loss = _elbo(parts["recon/audio"], parts["recon/vision"], out["kl_l"], float(self.kl_coeff), out["kl_h"],
                                                 float(self.kl_coeff * self.w_kl_h))
         return {"recon": recon, **parts, "kl": kl_div_l, "kl_h": kl_div_h, "loss": loss}

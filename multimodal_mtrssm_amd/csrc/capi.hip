@@ -50,6 +50,8 @@ int elbo_combine_fwd_launch(const float*, const float*, const float*, const floa
 int elbo_combine_bwd_launch(const float*, const float*, const float*, const float*, int64_t, float, float, float*, float*, float*, float*, hipStream_t);
 int nll_fwd_launch(const float*, const float*, int64_t, int64_t, int, float*, hipStream_t);
 int nll_bwd_launch(const float*, const float*, const float*, int64_t, int64_t, int, float*, hipStream_t);
+int nll_masked_fwd_launch(const float*, const float*, const float*, const float*, int64_t, int64_t, int, float*, hipStream_t);
+int nll_masked_bwd_launch(const float*, const float*, const float*, const float*, const float*, int64_t, int64_t, int, float*, hipStream_t);
 int sumsq_launch(const float*, int64_t, float*, hipStream_t);
 int adamw_launch(float*, const float*, float*, float*, int64_t, const float*, float, float, float, float, float, float, float, int, hipStream_t);
 int gemm_launch(const MtrssmGemm*, hipStream_t);
@@ -136,6 +138,14 @@ MTRSSM_API int mtrssm_gaussian_nll_fwd(const float* pred, const float* target, i
 MTRSSM_API int mtrssm_gaussian_nll_bwd(const float* pred, const float* target, const float* g_out, int64_t frames, int64_t event, int32_t act,
                                        float* g_pred, void* stream) {
   return nll_bwd_launch(pred, target, g_out, frames, event, act, g_pred, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_gaussian_nll_masked_fwd(const float* pred, const float* target, const float* present, const float* count, int64_t frames,
+                                              int64_t event, int32_t act, float* out, void* stream) {
+  return nll_masked_fwd_launch(pred, target, present, count, frames, event, act, out, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_gaussian_nll_masked_bwd(const float* pred, const float* target, const float* present, const float* count,
+                                              const float* g_out, int64_t frames, int64_t event, int32_t act, float* g_pred, void* stream) {
+  return nll_masked_bwd_launch(pred, target, present, count, g_out, frames, event, act, g_pred, static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int mtrssm_sumsq(const float* x, int64_t n, float* out, void* stream) {
   return sumsq_launch(x, n, out, static_cast<hipStream_t>(stream));

@@ -25,7 +25,7 @@ struct MmtLds {
   }
 };
 
-template <int RB, bool POST, bool VEC>
+template <int RB, bool POST, bool VEC, bool MASKED>
 __global__ __launch_bounds__(1024) void mmtrssm_fwd_kernel(const MtrssmMmtrssmDims dm, const MtrssmMmtrssmFwdWeights w, const MtrssmMmtrssmFwdIO io) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int LD = dm.LD, HD = dm.HD, H = dm.H, KL = dm.KL, CL = dm.CL, KH = dm.KH, CH = dm.CH;
@@ -152,7 +152,9 @@ __global__ __launch_bounds__(1024) void mmtrssm_fwd_kernel(const MtrssmMmtrssmDi
       float* r = lds + rb * L.stride;
       const size_t q = bt[rb];
       const bool ok = valid[rb];
-      if (POST) wave_mopoe_mix(r + L.la, r + L.lv, r + L.mx, LS, lane);
+      const int code = modality_code<MASKED>(io.modality, q);
+      if (POST) wave_mopoe_mix_masked<false, MASKED>(r + L.la, r + L.lv, r + L.lpl, r + L.mx, LS, lane, code);
+      if (POST && MASKED && code == 0) wave_copy(r + L.lph, r + L.lqh, HS, lane);  // no modality: higher posterior = prior
       if (ok) {
         for (int s = lane; s < LS; s += kWave) {
           io.prior_logits_l[q * LS + s] = r[L.lpl + s];
@@ -208,7 +210,7 @@ struct MmtBwdLds {
   }
 };
 
-template <int RB, bool VEC>
+template <int RB, bool VEC, bool MASKED>
 __global__ __launch_bounds__(1024) void mmtrssm_bwd_kernel(const MtrssmMmtrssmDims dm, const MtrssmMmtrssmBwdWeights w, const MtrssmMmtrssmBwdIO io) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int LD = dm.LD, HD = dm.HD, H = dm.H, KL = dm.KL, CL = dm.CL, KH = dm.KH, CH = dm.CH;
@@ -274,7 +276,9 @@ __global__ __launch_bounds__(1024) void mmtrssm_bwd_kernel(const MtrssmMmtrssmDi
                     io.g_post_logits_h ? io.g_post_logits_h + q * HS : nullptr,
                     io.g_prior_logits_h ? io.g_prior_logits_h + q * HS : nullptr, io.g_kl_h ? io.g_kl_h[q] : 0.f,
                     dm.kl_w_post, dm.kl_w_prior, r + L.dlqh, r + L.dlph);
-      wave_mopoe_mix_bwd(r + L.la, r + L.lv, r + L.mx, r + L.dmx, r + L.dla, r + L.dlv, LS, lane);
+      const int code = modality_code<MASKED>(io.modality, q);
+      if (MASKED && code == 0) wave_route_to_prior(r + L.dlqh, r + L.dlph, HS, lane);
+      wave_mopoe_mix_bwd_masked<false, MASKED>(r + L.la, r + L.lv, r + L.mx, r + L.dmx, r + L.dla, r + L.dlv, r + L.dlpl, LS, lane, code);
       if (valid[rb]) {
         for (int s = lane; s < LS; s += kWave) {
           io.d_lpl[q * LS + s] = r[L.dlpl + s];
@@ -449,12 +453,13 @@ int mmtrssm_fwd_launch(const MtrssmMmtrssmDims* d, const MtrssmMmtrssmFwdWeights
   if (rb > threads / kWave) { set_error("rows_per_block %d exceeds waves per block %d", rb, threads / kWave); return MTRSSM_EINVAL; }
   const bool vec = d->LD % 4 == 0 && d->HD % 4 == 0 && d->H % 4 == 0 &&
                    mmt_aligned16({w->wxl_s_t, w->wdl_t, w->wxh_t, w->wdh_t, w->wl1_t, w->wh1_t});
-#define MTRSSM_VARIANT(R, P, V) \
-  launch_mmt("mtrssm::mmtrssm_fwd_kernel<" #R ", " #P ", " #V ">", mmtrssm_fwd_kernel<R, P, V>, grid, threads, lds, stream, *d, *w, *io)
-#define MTRSSM_CASE(R)                                                                      \
-  case R:                                                                                    \
-    if (d->post) return vec ? MTRSSM_VARIANT(R, true, true) : MTRSSM_VARIANT(R, true, false); \
-    return vec ? MTRSSM_VARIANT(R, false, true) : MTRSSM_VARIANT(R, false, false);
+#define MTRSSM_VARIANT(R, P, V, M) \
+  launch_mmt("mtrssm::mmtrssm_fwd_kernel<" #R ", " #P ", " #V ", " #M ">", mmtrssm_fwd_kernel<R, P, V, M>, grid, threads, lds, stream, *d, *w, *io)
+#define MTRSSM_CASE(R)                                                                                                    \
+  case R:                                                                                                                  \
+    if (d->post && io->modality) return vec ? MTRSSM_VARIANT(R, true, true, true) : MTRSSM_VARIANT(R, true, false, true); \
+    if (d->post) return vec ? MTRSSM_VARIANT(R, true, true, false) : MTRSSM_VARIANT(R, true, false, false);             \
+    return vec ? MTRSSM_VARIANT(R, false, true, false) : MTRSSM_VARIANT(R, false, false, false);
   switch (rb) {
     MTRSSM_CASE(1)
     MTRSSM_CASE(2)
@@ -484,10 +489,12 @@ int mmtrssm_bwd_launch(const MtrssmMmtrssmDims* d, const MtrssmMmtrssmBwdWeights
   if (rb > threads / kWave) { set_error("rows_per_block %d exceeds waves per block %d", rb, threads / kWave); return MTRSSM_EINVAL; }
   const bool vec = d->LD % 4 == 0 && d->HD % 4 == 0 && d->H % 4 == 0 &&
                    mmt_aligned16({w->wdl, w->wdh, w->wl1, w->wh1, w->wlp2, w->wa2, w->wv2, w->whp2, w->whq2});
-#define MTRSSM_CASE(R)                                                                                                         \
-  case R:                                                                                                                       \
-    return vec ? launch_mmt("mtrssm::mmtrssm_bwd_kernel<" #R ", true>", mmtrssm_bwd_kernel<R, true>, grid, threads, lds, stream, *d, *w, *io) \
-               : launch_mmt("mtrssm::mmtrssm_bwd_kernel<" #R ", false>", mmtrssm_bwd_kernel<R, false>, grid, threads, lds, stream, *d, *w, *io);
+#define MTRSSM_VARIANT(R, V, M) \
+  launch_mmt("mtrssm::mmtrssm_bwd_kernel<" #R ", " #V ", " #M ">", mmtrssm_bwd_kernel<R, V, M>, grid, threads, lds, stream, *d, *w, *io)
+#define MTRSSM_CASE(R)                                                                                        \
+  case R:                                                                                                      \
+    if (io->modality) return vec ? MTRSSM_VARIANT(R, true, true) : MTRSSM_VARIANT(R, false, true);            \
+    return vec ? MTRSSM_VARIANT(R, true, false) : MTRSSM_VARIANT(R, false, false);
   switch (rb) {
     MTRSSM_CASE(1)
     MTRSSM_CASE(2)
@@ -495,6 +502,7 @@ int mmtrssm_bwd_launch(const MtrssmMmtrssmDims* d, const MtrssmMmtrssmBwdWeights
     default: set_error("rows_per_block must be 1, 2 or 4 (got %d)", rb); return MTRSSM_EINVAL;
   }
 #undef MTRSSM_CASE
+#undef MTRSSM_VARIANT
 }
 
 }  // namespace mtrssm

@@ -73,7 +73,7 @@ struct MmtWideFwdArgs {
   int acquire;
 };
 
-template <int P>
+template <int P, bool MASKED>
 __global__ __launch_bounds__(kWT) void mmtrssm_wide_fwd_kernel(const MmtWideFwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const MtrssmMmtrssmFwdIO& io = a.io;
@@ -135,6 +135,7 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_fwd_kernel(const MmtWideFwdA
         const size_t b = (size_t)(rb + r);
         if (t > 0) {
           const size_t q = b * T + (t - 1);
+          const int code = modality_code<MASKED>(io.modality, q);
           if (wave == 0) {
             if (lane < KL) { Lu[lane] = io.u_post_l[q * KL + lane]; Lu[64 + lane] = io.u_prior_l ? io.u_prior_l[q * KL + lane] : 0.f; }
             if (lane < KH) { Lu[128 + lane] = io.u_post_h[q * KH + lane]; Lu[192 + lane] = io.u_prior_h ? io.u_prior_h[q * KH + lane] : 0.f; }
@@ -154,7 +155,7 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_fwd_kernel(const MmtWideFwdA
           lds_barrier();
           MTRSSM_MMT_STAMP(10);
           if (wave == 0) {   // lower level: MoPoE mix, categorical block
-            wave_mopoe_mix<true>(Lla, Llv, Lmx, LS, lane);
+            wave_mopoe_mix_masked<true, MASKED>(Lla, Llv, Llpl, Lmx, LS, lane, code);
             for (int s2 = lane; s2 < LS; s2 += kWave) {
               io.prior_logits_l[q * LS + s2] = Llpl[s2];
               io.post_logits_l[q * LS + s2] = Lmx[s2];
@@ -168,6 +169,7 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_fwd_kernel(const MmtWideFwdA
             if (lane == 0 && io.kl_l) io.kl_l[q] = kll;
             MTRSSM_MMT_STAMP(11);
           } else if (wave == 1) {   // higher level, beside it on another SIMD
+            if (MASKED && code == 0) wave_copy(Llph, Llqh, HS, lane);  // no modality: higher posterior = prior
             for (int s2 = lane; s2 < HS; s2 += kWave) {
               io.prior_logits_h[q * HS + s2] = Llph[s2];
               io.post_logits_h[q * HS + s2] = Llqh[s2];
@@ -328,7 +330,7 @@ struct MmtWideBwdArgs {
   int acquire;
 };
 
-template <int P>
+template <int P, bool MASKED>
 __global__ __launch_bounds__(kWT) void mmtrssm_wide_bwd_kernel(const MmtWideBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const MtrssmMmtrssmBwdIO& io = a.io;
@@ -369,6 +371,7 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_bwd_kernel(const MmtWideBwdA
       // ============ R0: categorical blocks + MoPoE mix backward, one workgroup per batch row ============
       for (int r = nblk - 1 - blk; r < nrows; r += nblk) {
         const size_t q = (size_t)(rb + r) * T + t;
+        const int code = modality_code<MASKED>(io.modality, q);
         for (int s2 = tid; s2 < LS; s2 += kWT) {
           Lla[s2] = io.sv_la[q * LS + s2];
           Llv[s2] = io.sv_lv[q * LS + s2];
@@ -391,7 +394,7 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_bwd_kernel(const MmtWideBwdA
           const float* gprl = io.g_prior_logits_l ? io.g_prior_logits_l + q * LS : nullptr;
           if (CL <= 8) cat_block_bwd_fast8(Lmx, Llpl, KL, CL, lane, Lgps, Lcs, gpsl, gpll, gprl, gkl, a.dm.kl_w_post, a.dm.kl_w_prior, Ldmx, Ldlpl);
           else cat_block_bwd<true>(Lmx, Llpl, KL, CL, lane, Lgps, Lcs, gpsl, gpll, gprl, gkl, a.dm.kl_w_post, a.dm.kl_w_prior, Ldmx, Ldlpl);
-          wave_mopoe_mix_bwd<true>(Lla, Llv, Lmx, Ldmx, Ldla, Ldlv, LS, lane);
+          wave_mopoe_mix_bwd_masked<true, MASKED>(Lla, Llv, Lmx, Ldmx, Ldla, Ldlv, Ldlpl, LS, lane, code);
           MTRSSM_MMT_STAMP(11);
         } else if (wave == 1) {   // higher level, beside it on another SIMD
           const float gkh = io.g_kl_h ? io.g_kl_h[q] : 0.f;
@@ -400,6 +403,7 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_bwd_kernel(const MmtWideBwdA
           const float* gprh = io.g_prior_logits_h ? io.g_prior_logits_h + q * HS : nullptr;
           if (CH <= 8) cat_block_bwd_fast8(Llqh, Llph, KH, CH, lane, Lgps + LS, Lcs + LS, gpsh, gplh, gprh, gkh, a.dm.kl_w_post, a.dm.kl_w_prior, Ldlqh, Ldlph);
           else cat_block_bwd<true>(Llqh, Llph, KH, CH, lane, Lgps + LS, Lcs + LS, gpsh, gplh, gprh, gkh, a.dm.kl_w_post, a.dm.kl_w_prior, Ldlqh, Ldlph);
+          if (MASKED && code == 0) wave_route_to_prior(Ldlqh, Ldlph, HS, lane);
         }
         lds_barrier();
         // outputs and exchange vectors: lpl, la, lv (K = LS), lqh, lph (K = HS)
@@ -705,14 +709,18 @@ int mmtrssm_wide_fwd_launch(const MtrssmMmtrssmDims* d, const MtrssmMmtrssmFwdWe
   const size_t lds = mmt_fwd_lds(G);
   if (lds > 160 * 1024) { set_error("mmtrssm_rollout_fwd_wide: %zu bytes of LDS", lds); return MTRSSM_ELDS; }
   hipError_t e;
-#define MTRSSM_MMT_WIDE_FWD(PV)                                                                                                        \
+#define MTRSSM_MMT_WIDE_FWD(PV, MV)                                                                                                        \
   {                                                                                                                                   \
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(mmtrssm_wide_fwd_kernel<PV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(mmtrssm_wide_fwd_kernel<PV, MV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
     if (e != hipSuccess) { set_error("hipFuncSetAttribute(max dynamic LDS=%zu): %s", lds, hipGetErrorString(e)); return MTRSSM_ELAUNCH; }     \
-    set_last_kernel("mtrssm::mmtrssm_wide_fwd_kernel<" #PV ">");                                                                      \
-    hipLaunchKernelGGL(mmtrssm_wide_fwd_kernel<PV>, dim3(a.nblk), dim3(kWT), lds, stream, a);                                        \
+    set_last_kernel("mtrssm::mmtrssm_wide_fwd_kernel<" #PV ", " #MV ">");                                                                      \
+    hipLaunchKernelGGL((mmtrssm_wide_fwd_kernel<PV, MV>), dim3(a.nblk), dim3(kWT), lds, stream, a);                                        \
   }
-  if (pieces == 3) MTRSSM_MMT_WIDE_FWD(3) else MTRSSM_MMT_WIDE_FWD(2)
+  if (io->modality) {
+    if (pieces == 3) MTRSSM_MMT_WIDE_FWD(3, true) else MTRSSM_MMT_WIDE_FWD(2, true)
+  } else {
+    if (pieces == 3) MTRSSM_MMT_WIDE_FWD(3, false) else MTRSSM_MMT_WIDE_FWD(2, false)
+  }
 #undef MTRSSM_MMT_WIDE_FWD
   e = hipGetLastError();
   if (e != hipSuccess) { set_error("wide MMTRSSM forward scan launch failed: %s", hipGetErrorString(e)); return MTRSSM_ELAUNCH; }
@@ -781,14 +789,18 @@ int mmtrssm_wide_bwd_launch(const MtrssmMmtrssmDims* d, const MtrssmMmtrssmBwdWe
   const size_t lds = mmt_bwd_lds(G);
   if (lds > 160 * 1024) { set_error("mmtrssm_rollout_bwd_wide: %zu bytes of LDS", lds); return MTRSSM_ELDS; }
   hipError_t e;
-#define MTRSSM_MMT_WIDE_BWD(PV)                                                                                                        \
+#define MTRSSM_MMT_WIDE_BWD(PV, MV)                                                                                                        \
   {                                                                                                                                   \
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(mmtrssm_wide_bwd_kernel<PV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(mmtrssm_wide_bwd_kernel<PV, MV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
     if (e != hipSuccess) { set_error("hipFuncSetAttribute(max dynamic LDS=%zu): %s", lds, hipGetErrorString(e)); return MTRSSM_ELAUNCH; }     \
-    set_last_kernel("mtrssm::mmtrssm_wide_bwd_kernel<" #PV ">");                                                                      \
-    hipLaunchKernelGGL(mmtrssm_wide_bwd_kernel<PV>, dim3(a.nblk), dim3(kWT), lds, stream, a);                                        \
+    set_last_kernel("mtrssm::mmtrssm_wide_bwd_kernel<" #PV ", " #MV ">");                                                                      \
+    hipLaunchKernelGGL((mmtrssm_wide_bwd_kernel<PV, MV>), dim3(a.nblk), dim3(kWT), lds, stream, a);                                        \
   }
-  if (pieces == 3) MTRSSM_MMT_WIDE_BWD(3) else MTRSSM_MMT_WIDE_BWD(2)
+  if (io->modality) {
+    if (pieces == 3) MTRSSM_MMT_WIDE_BWD(3, true) else MTRSSM_MMT_WIDE_BWD(2, true)
+  } else {
+    if (pieces == 3) MTRSSM_MMT_WIDE_BWD(3, false) else MTRSSM_MMT_WIDE_BWD(2, false)
+  }
 #undef MTRSSM_MMT_WIDE_BWD
   e = hipGetLastError();
   if (e != hipSuccess) { set_error("wide MMTRSSM backward scan launch failed: %s", hipGetErrorString(e)); return MTRSSM_ELAUNCH; }

@@ -78,7 +78,7 @@ __device__ __forceinline__ bool wave_gather(const unsigned long long* g, float* 
 
 // DH: D = H (compile time: every stride an immediate).  The 2 * 3 * DH / 4 gate columns are cut into NP pieces of KP = DH / NP
 // reduction terms; thread t holds pieces t * PPT .. t * PPT + PPT - 1 (column = piece / NP, part = piece % NP).
-template <int DH, int NP, int PPT>
+template <int DH, int NP, int PPT, bool MASKED>
 __global__ __launch_bounds__(kCluThreads) void mrssm_fwd_cluster_kernel(const MtrssmMrssmDims dm, const MtrssmMrssmClusterWeights w,
                                                                         const MtrssmMrssmFwdIO io, unsigned long long* __restrict__ gran,
                                                                         int* __restrict__ status, int nclusters) {
@@ -177,7 +177,8 @@ __global__ __launch_bounds__(kCluThreads) void mrssm_fwd_cluster_kernel(const Mt
 
     // The streamed inputs of a step (xa, pa / pv of the own head units, the uniforms) are loaded one step AHEAD into registers:
     // loaded at the top of the step that consumes them, their HBM latency (~1 us) sat on the step's critical path.
-    auto load_inputs = [&](size_t q, float& xa_r, float& pa_r, float& up_r, float& ur_r) {
+    auto load_inputs = [&](size_t q, float& xa_r, float& pa_r, float& up_r, float& ur_r, int& code_r) {
+      code_r = modality_code<MASKED>(io.modality, q);  // every member reads its row's code (the mix runs on each of them)
       xa_r = tid < H ? io.xa[q * H + tid] : 0.f;
       pa_r = 0.f;
       if (tid >= UH && tid < NH) {
@@ -188,14 +189,16 @@ __global__ __launch_bounds__(kCluThreads) void mrssm_fwd_cluster_kernel(const Mt
       ur_r = (wave == 3 && lane < K && io.u_prior) ? io.u_prior[q * K + lane] : 0.f;
     };
     float xa_n, pav_n, up_n, ur_n;
-    load_inputs((size_t)row * T, xa_n, pav_n, up_n, ur_n);
+    int code_n;
+    load_inputs((size_t)row * T, xa_n, pav_n, up_n, ur_n, code_n);
 
     for (int t = 0; t < T; ++t) {
       const size_t bt = (size_t)row * T + t;
       unsigned long long* gpar = gbase + (size_t)(t & 1) * per_parity;
       const float xa_v = xa_n, pav = pav_n;
+      const int code = code_n;
       if (wave == 3 && lane < K) { lds[Lu + lane] = up_n; lds[Lu + 64 + lane] = ur_n; }
-      if (t + 1 < T) load_inputs(bt + 1, xa_n, pav_n, up_n, ur_n);
+      if (t + 1 < T) load_inputs(bt + 1, xa_n, pav_n, up_n, ur_n, code_n);
 
       MTRSSM_CLU_STAMP(0);
       // (1) h1 = act(xa + W1s s): every member, all H outputs                    networks.py:165-166
@@ -340,7 +343,7 @@ __global__ __launch_bounds__(kCluThreads) void mrssm_fwd_cluster_kernel(const Mt
           for (int m2 = 0; m2 < kClu; ++m2) v += lds[Lpart + m2 * 3 * S + i];
           lds[(which == 0 ? Llp : (which == 1 ? Lla : Llv)) + s2] = v;
         }
-        wave_mopoe_mix<true>(lds + Lla, lds + Llv, lds + Lmx, S, lane);
+        wave_mopoe_mix_masked<true, MASKED>(lds + Lla, lds + Llv, lds + Llp, lds + Lmx, S, lane, code);
         for (int s = lane; s < S; s += kWave) {
           if (writer) {
             io.prior_logits[bt * S + s] = lds[Llp + s];
@@ -406,7 +409,7 @@ __device__ __forceinline__ bool wave_gather_map(int total, unsigned epoch, int l
 
 // NPB parts of KPB = 3 UD / NPB own gate columns per row piece; thread t holds row pieces t * PPT .. (row = piece / NPB of
 // the stacked [W_hh^T rows ; (W_ih W2)^T rows] (2 DH rows), part = piece % NPB).
-template <int DH, int NPB, int PPT>
+template <int DH, int NPB, int PPT, bool MASKED>
 __global__ __launch_bounds__(kCluThreads) void mrssm_bwd_cluster_kernel(const MtrssmMrssmDims dm, const MtrssmMrssmClusterWeights w,
                                                                         const MtrssmMrssmBwdIO io, unsigned long long* __restrict__ gran,
                                                                         int* __restrict__ status, int nclusters) {
@@ -504,8 +507,10 @@ __global__ __launch_bounds__(kCluThreads) void mrssm_bwd_cluster_kernel(const Mt
     // staged values of one step, five registers per thread: r0 logits (4 S), r1 head units (NH) | g_post_stoch (S, threads
     // NH..), r2 gates (4 UD) | g_kl (thread 4 UD), r3 h1 (H), r4 d_prev (UD) | g_deter (UD, threads 64..)
     float r0 = 0.f, r1 = 0.f, r2 = 0.f, r3 = 0.f, r4 = 0.f;
+    int code_n = kModBoth;  // the step's modality code (every member: the mix backward runs on each of them)
     auto stage_load = [&](int tt) {
       const size_t q = (size_t)row * T + tt;
+      code_n = modality_code<MASKED>(io.modality, q);
       if (tid < 4 * S) {
         const int which = tid / S, s2 = tid - which * S;
         const float* src = which == 0 ? io.sv_la : (which == 1 ? io.sv_lv : (which == 2 ? io.post_logits : io.prior_logits));
@@ -553,6 +558,7 @@ __global__ __launch_bounds__(kCluThreads) void mrssm_bwd_cluster_kernel(const Mt
       // (a) this step's saved vectors and incoming gradients (own parts) were loaded one step ahead into registers
       //     (stage_load below): to LDS now, then the loads of step t - 1 go out and fly during this whole step
       stage_store();
+      const int code = code_n;
       if (t > 0) stage_load(t - 1);
       lds_barrier();
 
@@ -566,7 +572,8 @@ __global__ __launch_bounds__(kCluThreads) void mrssm_bwd_cluster_kernel(const Mt
           cat_block_bwd<true>(lds + Lmx, lds + Llp, K, C, lane, lds + Lgps, lds + Lcs, io.g_prior_stoch ? io.g_prior_stoch + bt * S : nullptr,
                               io.g_post_logits ? io.g_post_logits + bt * S : nullptr, io.g_prior_logits ? io.g_prior_logits + bt * S : nullptr,
                               *gk_lds, dm.kl_w_post, dm.kl_w_prior, lds + Ldmx, lds + Ldlp);
-        wave_mopoe_mix_bwd<true>(lds + Lla, lds + Llv, lds + Lmx, lds + Ldmx, lds + Ldla, lds + Ldlv, S, lane);
+        wave_mopoe_mix_bwd_masked<true, MASKED>(lds + Lla, lds + Llv, lds + Lmx, lds + Ldmx, lds + Ldla, lds + Ldlv, lds + Ldlp, S, lane,
+                                                code);
         if (member == 0) {
           for (int s2 = lane; s2 < S; s2 += kWave) {
             io.d_la[bt * S + s2] = lds[Ldla + s2];
@@ -789,14 +796,19 @@ int mrssm_bwd_cluster_launch(const MtrssmMrssmDims* d, const MtrssmMrssmClusterW
   hipError_t e = hipSuccess;
   int* status = reinterpret_cast<int*>(workspace);
   unsigned long long* gran = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(workspace) + 16);
-#define MTRSSM_CLUB_LAUNCH(DHV, NPV, PPTV)                                                                                         \
+#define MTRSSM_CLUB_LAUNCH_M(DHV, NPV, PPTV, MV)                                                                                    \
   {                                                                                                                               \
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(mrssm_bwd_cluster_kernel<DHV, NPV, PPTV>),                              \
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(mrssm_bwd_cluster_kernel<DHV, NPV, PPTV, MV>),                          \
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                               \
     if (e != hipSuccess) { set_error("hipFuncSetAttribute(max dynamic LDS=%zu): %s", lds, hipGetErrorString(e)); return MTRSSM_ELAUNCH; } \
-    set_last_kernel("mtrssm::mrssm_bwd_cluster_kernel<" #DHV ", " #NPV ", " #PPTV ">");                                          \
-    hipLaunchKernelGGL((mrssm_bwd_cluster_kernel<DHV, NPV, PPTV>), dim3(grid), dim3(kCluThreads), lds, stream, *d, *w, *io, gran,   \
-                       status, nclusters);                                                                                        \
+    set_last_kernel("mtrssm::mrssm_bwd_cluster_kernel<" #DHV ", " #NPV ", " #PPTV ", " #MV ">");                                 \
+    hipLaunchKernelGGL((mrssm_bwd_cluster_kernel<DHV, NPV, PPTV, MV>), dim3(grid), dim3(kCluThreads), lds, stream, *d, *w, *io,     \
+                       gran, status, nclusters);                                                                                  \
+  }
+#define MTRSSM_CLUB_LAUNCH(DHV, NPV, PPTV)                      \
+  {                                                            \
+    if (io->modality) MTRSSM_CLUB_LAUNCH_M(DHV, NPV, PPTV, true) \
+    else MTRSSM_CLUB_LAUNCH_M(DHV, NPV, PPTV, false)             \
   }
   // row pieces per thread = ceil(2 DH NPB / 256)
   if (d->D == 32) MTRSSM_CLUB_LAUNCH(32, 1, 1)
@@ -804,6 +816,7 @@ int mrssm_bwd_cluster_launch(const MtrssmMrssmDims* d, const MtrssmMrssmClusterW
   else if (d->D == 128) MTRSSM_CLUB_LAUNCH(128, 3, 3)
   else MTRSSM_CLUB_LAUNCH(200, 3, 5)
 #undef MTRSSM_CLUB_LAUNCH
+#undef MTRSSM_CLUB_LAUNCH_M
   e = hipGetLastError();
   if (e != hipSuccess) { set_error("cluster backward scan launch failed: %s", hipGetErrorString(e)); return MTRSSM_ELAUNCH; }
   return MTRSSM_OK;
@@ -884,14 +897,19 @@ int mrssm_fwd_cluster_launch(const MtrssmMrssmDims* d, const MtrssmMrssmClusterW
   int* status = reinterpret_cast<int*>(workspace);
   unsigned long long* gran = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(workspace) + 16);
   const int kw = cluster_kw(d->D, d->H);
-#define MTRSSM_CLU_LAUNCH(DHV, NPV, PPTV)                                                                                          \
+#define MTRSSM_CLU_LAUNCH_M(DHV, NPV, PPTV, MV)                                                                                     \
   {                                                                                                                               \
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(mrssm_fwd_cluster_kernel<DHV, NPV, PPTV>),                              \
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(mrssm_fwd_cluster_kernel<DHV, NPV, PPTV, MV>),                          \
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                               \
     if (e != hipSuccess) { set_error("hipFuncSetAttribute(max dynamic LDS=%zu): %s", lds, hipGetErrorString(e)); return MTRSSM_ELAUNCH; } \
-    set_last_kernel("mtrssm::mrssm_fwd_cluster_kernel<" #DHV ", " #NPV ", " #PPTV ">");                                          \
-    hipLaunchKernelGGL((mrssm_fwd_cluster_kernel<DHV, NPV, PPTV>), dim3(grid), dim3(kCluThreads), lds, stream, *d, *w, *io, gran,   \
-                       status, nclusters);                                                                                        \
+    set_last_kernel("mtrssm::mrssm_fwd_cluster_kernel<" #DHV ", " #NPV ", " #PPTV ", " #MV ">");                                 \
+    hipLaunchKernelGGL((mrssm_fwd_cluster_kernel<DHV, NPV, PPTV, MV>), dim3(grid), dim3(kCluThreads), lds, stream, *d, *w, *io,     \
+                       gran, status, nclusters);                                                                                  \
+  }
+#define MTRSSM_CLU_LAUNCH(DHV, NPV, PPTV)                      \
+  {                                                           \
+    if (io->modality) MTRSSM_CLU_LAUNCH_M(DHV, NPV, PPTV, true) \
+    else MTRSSM_CLU_LAUNCH_M(DHV, NPV, PPTV, false)             \
   }
   // pieces per thread = ceil(2 * (3 DH / 4) * NP / 256)
   if (kw == 32) MTRSSM_CLU_LAUNCH(32, 1, 1)
@@ -899,6 +917,7 @@ int mrssm_fwd_cluster_launch(const MtrssmMrssmDims* d, const MtrssmMrssmClusterW
   else if (kw == 128) MTRSSM_CLU_LAUNCH(128, 4, 3)
   else MTRSSM_CLU_LAUNCH(200, 5, 6)
 #undef MTRSSM_CLU_LAUNCH
+#undef MTRSSM_CLU_LAUNCH_M
   e = hipGetLastError();
   if (e != hipSuccess) { set_error("cluster scan launch failed: %s", hipGetErrorString(e)); return MTRSSM_ELAUNCH; }
   return MTRSSM_OK;

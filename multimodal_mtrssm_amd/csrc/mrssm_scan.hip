@@ -27,7 +27,7 @@ struct MrssmLds {
 // ------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------
-template <int RB, bool POST, bool VEC>
+template <int RB, bool POST, bool VEC, bool MASKED>
 __global__ __launch_bounds__(1024) void mrssm_fwd_kernel(const MtrssmMrssmDims dm, const MtrssmMrssmFwdWeights w, const MtrssmMrssmFwdIO io) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int D = dm.D, H = dm.H, K = dm.K, C = dm.C, S = K * C, T = dm.T, act = dm.act;
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(1024) void mrssm_fwd_kernel(const MtrssmMrssmDims d
       float* r_ = lds + rb * L.stride;
       const size_t q = bt[rb];
       const bool ok = valid[rb];
-      if (POST) wave_mopoe_mix(r_ + L.la, r_ + L.lv, r_ + L.mx, S, lane);
+      if (POST) wave_mopoe_mix_masked<false, MASKED>(r_ + L.la, r_ + L.lv, r_ + L.lp, r_ + L.mx, S, lane, modality_code<MASKED>(io.modality, q));
       for (int s = lane; s < S; s += kWave) {
         if (ok) {
           io.prior_logits[q * S + s] = r_[L.lp + s];
@@ -177,7 +177,7 @@ struct MrssmBwdLds {
   }
 };
 
-template <int RB, bool VEC>
+template <int RB, bool VEC, bool MASKED>
 __global__ __launch_bounds__(1024) void mrssm_bwd_kernel(const MtrssmMrssmDims dm, const MtrssmMrssmBwdWeights w, const MtrssmMrssmBwdIO io) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int D = dm.D, H = dm.H, K = dm.K, C = dm.C, S = K * C, T = dm.T, act = dm.act;
@@ -232,8 +232,9 @@ __global__ __launch_bounds__(1024) void mrssm_bwd_kernel(const MtrssmMrssmDims d
                     io.g_post_logits ? io.g_post_logits + q * S : nullptr,
                     io.g_prior_logits ? io.g_prior_logits + q * S : nullptr, gk, dm.kl_w_post, dm.kl_w_prior,
                     r + L.dmx, r + L.dlp);
-      // back through logsumexp over {A, V, A+V} and the two flat log-softmaxes
-      wave_mopoe_mix_bwd(r + L.la, r + L.lv, r + L.mx, r + L.dmx, r + L.dla, r + L.dlv, S, lane);
+      // back through logsumexp over {A, V, A+V} and the two flat log-softmaxes (masked: over the present experts)
+      wave_mopoe_mix_bwd_masked<false, MASKED>(r + L.la, r + L.lv, r + L.mx, r + L.dmx, r + L.dla, r + L.dlv, r + L.dlp, S, lane,
+                                               modality_code<MASKED>(io.modality, q));
       if (valid[rb]) {
         for (int s = lane; s < S; s += kWave) {
           io.d_la[q * S + s] = r[L.dla + s];
@@ -418,12 +419,13 @@ int mrssm_fwd_launch(const MtrssmMrssmDims* d, const MtrssmMrssmFwdWeights* w, c
     return MTRSSM_EINVAL;
   }
   const bool vec = d->D % 4 == 0 && d->H % 4 == 0 && aligned16({w->w1s_t, w->w2_t, w->wih_t, w->whh_t, w->wh1_t});
-#define MTRSSM_FWD_VARIANT(R, P, V) \
-  launch("mtrssm::mrssm_fwd_kernel<" #R ", " #P ", " #V ">", mrssm_fwd_kernel<R, P, V>, grid, threads, lds, stream, *d, *w, *io)
-#define MTRSSM_FWD_CASE(R)                                                                       \
-  case R:                                                                                         \
-    if (d->post) return vec ? MTRSSM_FWD_VARIANT(R, true, true) : MTRSSM_FWD_VARIANT(R, true, false); \
-    return vec ? MTRSSM_FWD_VARIANT(R, false, true) : MTRSSM_FWD_VARIANT(R, false, false);
+#define MTRSSM_FWD_VARIANT(R, P, V, M) \
+  launch("mtrssm::mrssm_fwd_kernel<" #R ", " #P ", " #V ", " #M ">", mrssm_fwd_kernel<R, P, V, M>, grid, threads, lds, stream, *d, *w, *io)
+#define MTRSSM_FWD_CASE(R)                                                                                                  \
+  case R:                                                                                                                    \
+    if (d->post && io->modality) return vec ? MTRSSM_FWD_VARIANT(R, true, true, true) : MTRSSM_FWD_VARIANT(R, true, false, true); \
+    if (d->post) return vec ? MTRSSM_FWD_VARIANT(R, true, true, false) : MTRSSM_FWD_VARIANT(R, true, false, false);             \
+    return vec ? MTRSSM_FWD_VARIANT(R, false, true, false) : MTRSSM_FWD_VARIANT(R, false, false, false);
   switch (rb) {
     MTRSSM_FWD_CASE(1)
     MTRSSM_FWD_CASE(2)
@@ -455,10 +457,12 @@ int mrssm_bwd_launch(const MtrssmMrssmDims* d, const MtrssmMrssmBwdWeights* w, c
     return MTRSSM_EINVAL;
   }
   const bool vec = d->D % 4 == 0 && d->H % 4 == 0 && aligned16({w->w2, w->wih, w->whh, w->wh1, w->w4, w->wa2, w->wv2});
-#define MTRSSM_BWD_CASE(R)                                                                                              \
-  case R:                                                                                                                \
-    return vec ? launch("mtrssm::mrssm_bwd_kernel<" #R ", true>", mrssm_bwd_kernel<R, true>, grid, threads, lds, stream, *d, *w, *io) \
-               : launch("mtrssm::mrssm_bwd_kernel<" #R ", false>", mrssm_bwd_kernel<R, false>, grid, threads, lds, stream, *d, *w, *io);
+#define MTRSSM_BWD_VARIANT(R, V, M) \
+  launch("mtrssm::mrssm_bwd_kernel<" #R ", " #V ", " #M ">", mrssm_bwd_kernel<R, V, M>, grid, threads, lds, stream, *d, *w, *io)
+#define MTRSSM_BWD_CASE(R)                                                                                          \
+  case R:                                                                                                            \
+    if (io->modality) return vec ? MTRSSM_BWD_VARIANT(R, true, true) : MTRSSM_BWD_VARIANT(R, false, true);          \
+    return vec ? MTRSSM_BWD_VARIANT(R, true, false) : MTRSSM_BWD_VARIANT(R, false, false);
   switch (rb) {
     MTRSSM_BWD_CASE(1)
     MTRSSM_BWD_CASE(2)
@@ -468,6 +472,7 @@ int mrssm_bwd_launch(const MtrssmMrssmDims* d, const MtrssmMrssmBwdWeights* w, c
       return MTRSSM_EINVAL;
   }
 #undef MTRSSM_BWD_CASE
+#undef MTRSSM_BWD_VARIANT
 }
 
 }  // namespace mtrssm

@@ -100,7 +100,7 @@ struct WideFwdArgs {
   int acquire;                                         // 1: an agent acquire fence after every barrier (A/B switch)
 };
 
-template <int P>
+template <int P, bool MASKED>
 __global__ __launch_bounds__(kWT) void mrssm_wide_fwd_kernel(const WideFwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const MtrssmMrssmFwdIO& io = a.io;
@@ -181,6 +181,7 @@ __global__ __launch_bounds__(kWT) void mrssm_wide_fwd_kernel(const WideFwdArgs a
         }
         if (t > 0) {
           const size_t q = b * T + (t - 1);
+          const int code = modality_code<MASKED>(io.modality, q);
           if (wave == 0 && lane < K) {
             Lu[lane] = io.u_post[q * K + lane];
             Lu[64 + lane] = io.u_prior ? io.u_prior[q * K + lane] : 0.f;
@@ -193,7 +194,7 @@ __global__ __launch_bounds__(kWT) void mrssm_wide_fwd_kernel(const WideFwdArgs a
           lds_barrier();
           MTRSSM_WIDE_STAMP(10);
           if (wave == 0) {
-            wave_mopoe_mix<true>(Lla, Llv, Lmx, S, lane);
+            wave_mopoe_mix_masked<true, MASKED>(Lla, Llv, Llp, Lmx, S, lane, code);
             MTRSSM_WIDE_STAMP(11);
             for (int s2 = lane; s2 < S; s2 += kWave) {
               io.prior_logits[q * S + s2] = Llp[s2];
@@ -385,7 +386,7 @@ struct WideBwdArgs {
   int acquire;                                         // 1: an agent acquire fence after every barrier (A/B switch)
 };
 
-template <int P>
+template <int P, bool MASKED>
 __global__ __launch_bounds__(kWT) void mrssm_wide_bwd_kernel(const WideBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const MtrssmMrssmBwdIO& io = a.io;
@@ -446,6 +447,7 @@ __global__ __launch_bounds__(kWT) void mrssm_wide_bwd_kernel(const WideBwdArgs a
       // ============ R0: categorical block + MoPoE mix backward, one workgroup per batch row ============
       for (int r = nblk - 1 - blk; r < nrows; r += nblk) {
         const size_t q = (size_t)(rb + r) * T + t;
+        const int code = modality_code<MASKED>(io.modality, q);
         for (int s2 = tid; s2 < S; s2 += kWT) {
           Lla[s2] = io.sv_la[q * S + s2];
           Llv[s2] = io.sv_lv[q * S + s2];
@@ -467,7 +469,7 @@ __global__ __launch_bounds__(kWT) void mrssm_wide_bwd_kernel(const WideBwdArgs a
                                 io.g_post_logits ? io.g_post_logits + q * S : nullptr, io.g_prior_logits ? io.g_prior_logits + q * S : nullptr,
                                 gk, a.dm.kl_w_post, a.dm.kl_w_prior, Ldmx, Ldlp);
           MTRSSM_WIDE_STAMP(12);
-          wave_mopoe_mix_bwd<true>(Lla, Llv, Lmx, Ldmx, Ldla, Ldlv, S, lane);
+          wave_mopoe_mix_bwd_masked<true, MASKED>(Lla, Llv, Lmx, Ldmx, Ldla, Ldlv, Ldlp, S, lane, code);
           MTRSSM_WIDE_STAMP(13);
         }
         lds_barrier();
@@ -784,14 +786,18 @@ int mrssm_wide_fwd_launch(const MtrssmMrssmDims* d, const MtrssmMrssmClusterWeig
   const size_t lds = wide_fwd_lds(d);
   if (lds > 160 * 1024) { set_error("mrssm_rollout_fwd_wide: %zu bytes of LDS", lds); return MTRSSM_ELDS; }
   hipError_t e;
-#define MTRSSM_WIDE_FWD(PV)                                                                                                          \
+#define MTRSSM_WIDE_FWD(PV, MV)                                                                                                          \
   {                                                                                                                                 \
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(mrssm_wide_fwd_kernel<PV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(mrssm_wide_fwd_kernel<PV, MV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
     if (e != hipSuccess) { set_error("hipFuncSetAttribute(max dynamic LDS=%zu): %s", lds, hipGetErrorString(e)); return MTRSSM_ELAUNCH; }   \
-    set_last_kernel("mtrssm::mrssm_wide_fwd_kernel<" #PV ">");                                                                      \
-    hipLaunchKernelGGL(mrssm_wide_fwd_kernel<PV>, dim3(a.nblk), dim3(kWT), lds, stream, a);                                        \
+    set_last_kernel("mtrssm::mrssm_wide_fwd_kernel<" #PV ", " #MV ">");                                                                      \
+    hipLaunchKernelGGL((mrssm_wide_fwd_kernel<PV, MV>), dim3(a.nblk), dim3(kWT), lds, stream, a);                                        \
   }
-  if (pieces == 3) MTRSSM_WIDE_FWD(3) else MTRSSM_WIDE_FWD(2)
+  if (io->modality) {
+    if (pieces == 3) MTRSSM_WIDE_FWD(3, true) else MTRSSM_WIDE_FWD(2, true)
+  } else {
+    if (pieces == 3) MTRSSM_WIDE_FWD(3, false) else MTRSSM_WIDE_FWD(2, false)
+  }
 #undef MTRSSM_WIDE_FWD
   e = hipGetLastError();
   if (e != hipSuccess) { set_error("wide forward scan launch failed: %s", hipGetErrorString(e)); return MTRSSM_ELAUNCH; }
@@ -851,14 +857,18 @@ int mrssm_wide_bwd_launch(const MtrssmMrssmDims* d, const MtrssmMrssmClusterWeig
   const size_t lds = wide_bwd_lds(d);
   if (lds > 160 * 1024) { set_error("mrssm_rollout_bwd_wide: %zu bytes of LDS", lds); return MTRSSM_ELDS; }
   hipError_t e;
-#define MTRSSM_WIDE_BWD(PV)                                                                                                          \
+#define MTRSSM_WIDE_BWD(PV, MV)                                                                                                          \
   {                                                                                                                                 \
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(mrssm_wide_bwd_kernel<PV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(mrssm_wide_bwd_kernel<PV, MV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
     if (e != hipSuccess) { set_error("hipFuncSetAttribute(max dynamic LDS=%zu): %s", lds, hipGetErrorString(e)); return MTRSSM_ELAUNCH; }   \
-    set_last_kernel("mtrssm::mrssm_wide_bwd_kernel<" #PV ">");                                                                      \
-    hipLaunchKernelGGL(mrssm_wide_bwd_kernel<PV>, dim3(a.nblk), dim3(kWT), lds, stream, a);                                        \
+    set_last_kernel("mtrssm::mrssm_wide_bwd_kernel<" #PV ", " #MV ">");                                                                      \
+    hipLaunchKernelGGL((mrssm_wide_bwd_kernel<PV, MV>), dim3(a.nblk), dim3(kWT), lds, stream, a);                                        \
   }
-  if (pieces == 3) MTRSSM_WIDE_BWD(3) else MTRSSM_WIDE_BWD(2)
+  if (io->modality) {
+    if (pieces == 3) MTRSSM_WIDE_BWD(3, true) else MTRSSM_WIDE_BWD(2, true)
+  } else {
+    if (pieces == 3) MTRSSM_WIDE_BWD(3, false) else MTRSSM_WIDE_BWD(2, false)
+  }
 #undef MTRSSM_WIDE_BWD
   e = hipGetLastError();
   if (e != hipSuccess) { set_error("wide backward scan launch failed: %s", hipGetErrorString(e)); return MTRSSM_ELAUNCH; }

@@ -230,6 +230,33 @@ __device__ __forceinline__ void wave_mopoe_mix(const float* la, const float* lv,
   }
 }
 
+// Modality code of step q of a masked rollout (mtrssm.h, the `modality` field of the IO structs): bit 0 audio, bit 1 vision.
+// MASKED = false is the unmasked kernel: the code is the constant "both" and every masked branch folds away.
+constexpr int kModBoth = 3;
+template <bool MASKED>
+__device__ __forceinline__ int modality_code(const int32_t* modality, size_t q) {
+  return MASKED ? (modality[q] & 3) : kModBoth;
+}
+
+// MoPoE mix over the non-empty subsets of the PRESENT experts (code: wave-uniform).  Both: wave_mopoe_mix, the same bits; one:
+// the flat log-softmax of that expert's logits; none: the prior's raw logits lp (posterior = prior, KL = 0 exactly).
+template <bool FAST, bool MASKED>
+__device__ __forceinline__ void wave_mopoe_mix_masked(const float* la, const float* lv, const float* lp, float* mixed, int S, int lane,
+                                                      int code) {
+  if (!MASKED || code == kModBoth) {
+    wave_mopoe_mix<FAST>(la, lv, mixed, S, lane);
+    return;
+  }
+  if (code == 0) {
+    for (int s = lane; s < S; s += kWave) mixed[s] = lp[s];
+    return;
+  }
+  const float* l = code == 1 ? la : lv;
+  float m, ls;
+  wave_flat_lse<FAST>(l, S, lane, m, ls);
+  for (int s = lane; s < S; s += kWave) mixed[s] = (l[s] - m) - ls;
+}
+
 // Per-categorical softmax statistics for category k: max and log-sum
 template <bool FAST = false>
 __device__ __forceinline__ void cat_stats(const float* x, int C, float& mx, float& sum) {
@@ -494,6 +521,50 @@ __device__ __forceinline__ void wave_mopoe_mix_bwd(const float* la, const float*
   for (int s = lane; s < S; s += kWave) {
     dla[s] -= cexp<FAST>((la[s] - ma) - lsa) * suma;
     dlv[s] -= cexp<FAST>((lv[s] - mv) - lsv) * sumv;
+  }
+}
+
+// Backward of wave_mopoe_mix_masked.  Both: wave_mopoe_mix_bwd.  One: through that expert's flat log-softmax, zero for the
+// absent one.  None: d mixed is routed into the prior logits (dlp += dmx; dlp holds the categorical block's own d prior), zero
+// for both experts.
+template <bool FAST, bool MASKED>
+__device__ __forceinline__ void wave_mopoe_mix_bwd_masked(const float* la, const float* lv, const float* mixed, const float* dmx,
+                                                          float* dla, float* dlv, float* dlp, int S, int lane, int code) {
+  if (!MASKED || code == kModBoth) {
+    wave_mopoe_mix_bwd<FAST>(la, lv, mixed, dmx, dla, dlv, S, lane);
+    return;
+  }
+  if (code == 0) {
+    for (int s = lane; s < S; s += kWave) {
+      dlp[s] += dmx[s];
+      dla[s] = 0.f;
+      dlv[s] = 0.f;
+    }
+    return;
+  }
+  const float* l = code == 1 ? la : lv;
+  float* dl = code == 1 ? dla : dlv;
+  float* dz = code == 1 ? dlv : dla;
+  float m, ls;
+  wave_flat_lse<FAST>(l, S, lane, m, ls);
+  float sum = 0.f;
+  for (int s = lane; s < S; s += kWave) {
+    sum += dmx[s];
+    dz[s] = 0.f;
+  }
+  sum = wave_sum(sum);
+  for (int s = lane; s < S; s += kWave) dl[s] = dmx[s] - cexp<FAST>((l[s] - m) - ls) * sum;
+}
+
+// The higher level of a masked MMTRSSM step with no modality: posterior = prior (forward: q logits <- p logits) ...
+__device__ __forceinline__ void wave_copy(const float* src, float* dst, int S, int lane) {
+  for (int s = lane; s < S; s += kWave) dst[s] = src[s];
+}
+// ... and the gradient reaching the posterior logits goes to the prior logits (backward, after the categorical block).
+__device__ __forceinline__ void wave_route_to_prior(float* dq, float* dp, int S, int lane) {
+  for (int s = lane; s < S; s += kWave) {
+    dp[s] += dq[s];
+    dq[s] = 0.f;
   }
 }
 

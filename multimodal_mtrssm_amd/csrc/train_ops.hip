@@ -88,6 +88,91 @@ __global__ void nll_bwd_kernel(const float* __restrict__ pred, const float* __re
     }
 }
 
+// The NLL over the frames a modality is present in (core.py, missing modalities): an element of frame n counts when
+// present[n] != 0, the sum is divided by the device scalar *count (0 -> the loss is 0).  An absent element's difference is
+// zeroed before it is squared, so with every frame present the arithmetic -- and the launch shape -- is nll_fwd_kernel's.
+// EV4: event % 4 == 0, one frame per quad (one frame index per quad).  Frame indices are 32-bit divisions: the launchers
+// take n < 2^31 elements only.
+__device__ __forceinline__ bool frame_present(const float* __restrict__ present, uint32_t e, uint32_t event) {
+  return present[e / event] != 0.f;
+}
+
+template <bool EV4>
+__device__ __forceinline__ float4 masked_diff(const float* __restrict__ present, uint32_t e0, uint32_t event, float4 t, float4 p) {
+  float4 a = make_float4(t.x - p.x, t.y - p.y, t.z - p.z, t.w - p.w);
+  if (EV4) {
+    if (!frame_present(present, e0, event)) a = make_float4(0.f, 0.f, 0.f, 0.f);
+  } else {
+    if (!frame_present(present, e0, event)) a.x = 0.f;
+    if (!frame_present(present, e0 + 1, event)) a.y = 0.f;
+    if (!frame_present(present, e0 + 2, event)) a.z = 0.f;
+    if (!frame_present(present, e0 + 3, event)) a.w = 0.f;
+  }
+  return a;
+}
+
+template <bool TANH, bool EV4>
+__global__ void nll_masked_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ target, const float* __restrict__ present,
+                                      const float* __restrict__ count, int64_t n, int64_t event, float constant, float* __restrict__ out) {
+  __shared__ float red[kThreads / kWave];
+  const int64_t n4 = n / 4;
+  const float4* p4 = reinterpret_cast<const float4*>(pred);
+  const float4* t4 = reinterpret_cast<const float4*>(target);
+  float acc = 0.f;
+  auto term = [&](int64_t i, float4 p, const float4 t) {
+    if (TANH) { p.x = tanh_fast(p.x); p.y = tanh_fast(p.y); p.z = tanh_fast(p.z); p.w = tanh_fast(p.w); }
+    const float4 q = masked_diff<EV4>(present, (uint32_t)(4 * i), (uint32_t)event, t, p);
+    const float a = q.x, b = q.y, c = q.z, d = q.w;
+    return 0.5f * (a * a) + 0.5f * (b * b) + 0.5f * (c * c) + 0.5f * (d * d);
+  };
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (; i + 3 * stride < n4; i += 4 * stride) {
+    const float4 pa = p4[i], pb = p4[i + stride], pc = p4[i + 2 * stride], pd = p4[i + 3 * stride];
+    const float4 ta = t4[i], tb = t4[i + stride], tc = t4[i + 2 * stride], td = t4[i + 3 * stride];
+    acc += (term(i, pa, ta) + term(i + stride, pb, tb)) + (term(i + 2 * stride, pc, tc) + term(i + 3 * stride, pd, td));
+  }
+  for (; i < n4; i += stride) acc += term(i, p4[i], t4[i]);
+  if (blockIdx.x == 0) {
+    for (int64_t i = n4 * 4 + threadIdx.x; i < n; i += blockDim.x) {
+      const float a = frame_present(present, (uint32_t)i, (uint32_t)event) ? target[i] - (TANH ? tanh_fast(pred[i]) : pred[i]) : 0.f;
+      acc += 0.5f * a * a;
+    }
+  }
+  const float tot = block_sum(acc, red);
+  const float cnt = count[0];
+  if (threadIdx.x == 0 && cnt > 0.f) atomicAdd(out, tot * (1.f / cnt) + (blockIdx.x == 0 ? constant : 0.f));
+}
+
+template <bool TANH, bool EV4>
+__global__ void nll_masked_bwd_kernel(const float* __restrict__ pred, const float* __restrict__ target, const float* __restrict__ present,
+                                      const float* __restrict__ count, const float* __restrict__ g_out, int64_t n, int64_t event,
+                                      float* __restrict__ g_pred) {
+  const float cnt = count[0];
+  const float g = cnt > 0.f ? g_out[0] * (1.f / cnt) : 0.f;
+  const int64_t n4 = n / 4;
+  const float4* p4 = reinterpret_cast<const float4*>(pred);
+  const float4* t4 = reinterpret_cast<const float4*>(target);
+  float4* o4 = reinterpret_cast<float4*>(g_pred);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    float4 p = p4[i];
+    const float4 t = t4[i];
+    float4 d = make_float4(1.f, 1.f, 1.f, 1.f);
+    if (TANH) {
+      p.x = tanh_fast(p.x); p.y = tanh_fast(p.y); p.z = tanh_fast(p.z); p.w = tanh_fast(p.w);
+      d = make_float4(1.f - p.x * p.x, 1.f - p.y * p.y, 1.f - p.z * p.z, 1.f - p.w * p.w);
+    }
+    // (p - t) with absent elements zeroed: the negated masked difference
+    const float4 q = masked_diff<EV4>(present, (uint32_t)(4 * i), (uint32_t)event, p, t);
+    o4[i] = make_float4(g * q.x * d.x, g * q.y * d.y, g * q.z * d.z, g * q.w * d.w);
+  }
+  if (blockIdx.x == 0)
+    for (int64_t i = n4 * 4 + threadIdx.x; i < n; i += blockDim.x) {
+      const float p = TANH ? tanh_fast(pred[i]) : pred[i];
+      g_pred[i] = frame_present(present, (uint32_t)i, (uint32_t)event) ? g * (p - target[i]) * (TANH ? 1.f - p * p : 1.f) : 0.f;
+    }
+}
+
 __global__ void sumsq_kernel(const float* __restrict__ x, int64_t n, float* __restrict__ out) {
   __shared__ float red[kThreads / kWave];
   const int64_t n4 = n / 4;
@@ -357,6 +442,53 @@ int nll_bwd_launch(const float* pred, const float* target, const float* g_out, i
   else
     hipLaunchKernelGGL(nll_bwd_kernel<false>, dim3(grid_for(n / 4)), dim3(kThreads), 0, s, pred, target, g_out, n, 1.f / (float)frames, g_pred);
   return check_launch("gaussian_nll_bwd");
+}
+
+int nll_masked_fwd_launch(const float* pred, const float* target, const float* present, const float* count, int64_t frames,
+                          int64_t event, int act, float* out, hipStream_t s) {
+  if (!pred || !target || !present || !count || !out || frames <= 0 || event <= 0) {
+    set_error("gaussian_nll_masked_fwd: bad argument");
+    return MTRSSM_EINVAL;
+  }
+  if (act != MTRSSM_ACT_IDENTITY && act != MTRSSM_ACT_TANH) { set_error("gaussian_nll: the fused output activation is Identity or Tanh (got %d)", act); return MTRSSM_EINVAL; }
+  if (((uintptr_t)pred | (uintptr_t)target) & 15) { set_error("gaussian_nll_masked_fwd: pred/target must be 16-byte aligned"); return MTRSSM_EINVAL; }
+  const int64_t n = frames * event;
+  if (n >= (int64_t)1 << 31) {
+    set_error("gaussian_nll_masked_fwd: %lld elements (the frame index is 32-bit: < 2^31)", (long long)n);
+    return MTRSSM_EINVAL;
+  }
+  if (int rc = clear_async(out, sizeof(float), s)) return rc;
+  const float constant = 0.5f * 1.8378770664093453f * (float)event;  // as nll_fwd_launch
+  const int sum_grid = grid_for(n / 4) < 512 ? grid_for(n / 4) : 512;
+  const bool ev4 = event % 4 == 0, tanh = act == MTRSSM_ACT_TANH;
+  set_last_kernel("mtrssm::nll_masked_fwd_kernel");
+#define MTRSSM_NLLM_FWD(TV, EV) hipLaunchKernelGGL((nll_masked_fwd_kernel<TV, EV>), dim3(sum_grid), dim3(kThreads), 0, s, pred, target, present, count, n, event, constant, out)
+  if (tanh) { if (ev4) MTRSSM_NLLM_FWD(true, true); else MTRSSM_NLLM_FWD(true, false); }
+  else { if (ev4) MTRSSM_NLLM_FWD(false, true); else MTRSSM_NLLM_FWD(false, false); }
+#undef MTRSSM_NLLM_FWD
+  return check_launch("gaussian_nll_masked_fwd");
+}
+
+int nll_masked_bwd_launch(const float* pred, const float* target, const float* present, const float* count, const float* g_out,
+                          int64_t frames, int64_t event, int act, float* g_pred, hipStream_t s) {
+  if (!pred || !target || !present || !count || !g_out || !g_pred || frames <= 0 || event <= 0) {
+    set_error("gaussian_nll_masked_bwd: bad argument");
+    return MTRSSM_EINVAL;
+  }
+  if (act != MTRSSM_ACT_IDENTITY && act != MTRSSM_ACT_TANH) { set_error("gaussian_nll: the fused output activation is Identity or Tanh (got %d)", act); return MTRSSM_EINVAL; }
+  if (((uintptr_t)pred | (uintptr_t)target | (uintptr_t)g_pred) & 15) { set_error("gaussian_nll_masked_bwd: buffers must be 16-byte aligned"); return MTRSSM_EINVAL; }
+  const int64_t n = frames * event;
+  if (n >= (int64_t)1 << 31) {
+    set_error("gaussian_nll_masked_bwd: %lld elements (the frame index is 32-bit: < 2^31)", (long long)n);
+    return MTRSSM_EINVAL;
+  }
+  const bool ev4 = event % 4 == 0, tanh = act == MTRSSM_ACT_TANH;
+  set_last_kernel("mtrssm::nll_masked_bwd_kernel");
+#define MTRSSM_NLLM_BWD(TV, EV) hipLaunchKernelGGL((nll_masked_bwd_kernel<TV, EV>), dim3(grid_for(n / 4)), dim3(kThreads), 0, s, pred, target, present, count, g_out, n, event, g_pred)
+  if (tanh) { if (ev4) MTRSSM_NLLM_BWD(true, true); else MTRSSM_NLLM_BWD(true, false); }
+  else { if (ev4) MTRSSM_NLLM_BWD(false, true); else MTRSSM_NLLM_BWD(false, false); }
+#undef MTRSSM_NLLM_BWD
+  return check_launch("gaussian_nll_masked_bwd");
 }
 
 int sumsq_launch(const float* x, int64_t n, float* out, hipStream_t s) {

@@ -31,6 +31,14 @@ from multimodal_mtrssm_amd.optim import FlatAdamW, FlatParameters
 from multimodal_mtrssm_amd.parallel import FlatDataParallel, GlobalRowNoise
 
 
+def _refuse_modality_mask(model: torch.nn.Module, batch: tuple[Tensor, ...]) -> None:
+    """The captured step runs the unmasked kernels: a batch that carries a modality mask (7th entry) would be trained as if
+    every modality were present.  Refused instead (run such batches eagerly: ``model.shared_step``)."""
+    if model.get_modality_mask_from_batch(batch) is not None:
+        msg = "CapturedTrainStep does not support modality masks (a 7-tuple batch): train masked batches with the eager step"
+        raise NotImplementedError(msg)
+
+
 class CapturedTrainStep:
     """``step(batch)`` = one train step of ``model`` on a batch of the captured shape; returns the loss scalars
     (device tensors, averaged over ranks) exactly as the eager sequence would.
@@ -42,6 +50,7 @@ class CapturedTrainStep:
 
     def __init__(self, model: torch.nn.Module, flat: FlatParameters, opt: FlatAdamW, dp: FlatDataParallel,  # noqa: PLR0913
                  batch: tuple[Tensor, ...], noise: GlobalRowNoise, *, warmup: int = 3) -> None:
+        _refuse_modality_mask(model, batch)
         self.model, self.flat, self.opt, self.dp, self.noise = model, flat, opt, dp, noise
         self.batch = tuple(x.clone() for x in batch)
         b, t = batch[0].shape[:2]
@@ -121,6 +130,8 @@ class CapturedTrainStep:
     # one step ---------------------------------------------------------------------------------------
     def step(self, batch: tuple[Tensor, ...] | None = None) -> dict[str, Tensor]:
         scan.STATUS.poll()  # a cooperative scan launch of an earlier replay gave up (the device skipped that update): raise
+        if batch is not None:
+            _refuse_modality_mask(self.model, batch)
         if batch is not None and batch[0] is not self.batch[0]:
             for dst, src in zip(self.batch, batch, strict=True):
                 dst.copy_(src)

@@ -42,13 +42,60 @@ class _GaussianNLL(torch.autograd.Function):
         return g_pred, None, None, None
 
 
-def likelihood(prediction: Tensor, target: Tensor, event_ndims: int, scale: float = 1.0, *, out_act: int = 0) -> Tensor:
+class _GaussianNLLMasked(torch.autograd.Function):
+    """The NLL averaged over the frames whose ``present`` entry is 1 (``mtrssm_gaussian_nll_masked_fwd / _bwd``); ``count`` is
+    the device scalar sum(present): nothing is read back to the host."""
+
+    @staticmethod
+    def forward(ctx, prediction: Tensor, target: Tensor, present: Tensor, count: Tensor, event_ndims: int, act: int = 0) -> Tensor:  # noqa: ANN001, PLR0913
+        lib = _lib.load()
+        pred, tgt = prediction.contiguous(), target.contiguous()
+        event = math.prod(pred.shape[-event_ndims:])
+        frames = pred.numel() // event
+        out = torch.empty((), device=pred.device, dtype=torch.float32)
+        _lib.check(_lib.TIMERS.call("mtrssm_gaussian_nll_masked_fwd", lib.mtrssm_gaussian_nll_masked_fwd, _lib.ptr(pred), _lib.ptr(tgt),
+                                    _lib.ptr(present), _lib.ptr(count), frames, event, int(act), _lib.ptr(out), _lib.stream_ptr(pred.device),
+                                    nbytes=8.0 * pred.numel()), "mtrssm_gaussian_nll_masked_fwd")
+        ctx.save_for_backward(pred, tgt, present, count)
+        ctx.frames, ctx.event, ctx.act = frames, event, int(act)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out: Tensor):  # noqa: ANN001, ANN205
+        lib = _lib.load()
+        pred, tgt, present, count = ctx.saved_tensors
+        g_pred = torch.empty_like(pred)
+        g = g_out.contiguous()
+        _lib.check(_lib.TIMERS.call("mtrssm_gaussian_nll_masked_bwd", lib.mtrssm_gaussian_nll_masked_bwd, _lib.ptr(pred), _lib.ptr(tgt),
+                                    _lib.ptr(present), _lib.ptr(count), _lib.ptr(g), ctx.frames, ctx.event, ctx.act, _lib.ptr(g_pred),
+                                    _lib.stream_ptr(pred.device), nbytes=12.0 * pred.numel()), "mtrssm_gaussian_nll_masked_bwd")
+        return g_pred, None, None, None, None, None
+
+
+def likelihood(prediction: Tensor, target: Tensor, event_ndims: int, scale: float = 1.0, *, out_act: int = 0,
+               frame_mask: Tensor | None = None) -> Tensor:
     """Negative mean log-likelihood of ``target`` under ``Normal(act(prediction), scale)`` (``objective.py:7``).  ``out_act``
     (0 = Identity as in the reference's signature, 3 = Tanh) lets the decoder hand in its raw last-layer output: the
-    out_activation is applied while the kernel reads it and its derivative in the backward."""
+    out_activation is applied while the kernel reads it and its derivative in the backward.
+
+    ``frame_mask``: optional bool tensor over the frame dims (``prediction.shape[:-event_ndims]``).  The mean then runs over the
+    frames where it is True only; a mask with no True entry gives 0 and a zero gradient."""
     if prediction.shape != target.shape:
         msg = f"prediction {tuple(prediction.shape)} and target {tuple(target.shape)} must have the same shape"
         raise ValueError(msg)
+    if frame_mask is not None:
+        frame_shape = tuple(prediction.shape[: prediction.dim() - event_ndims])
+        if frame_mask.dtype != torch.bool or tuple(frame_mask.shape) != frame_shape:
+            msg = f"frame_mask must be a bool tensor of shape {frame_shape}, got {frame_mask.dtype} {tuple(frame_mask.shape)}"
+            raise ValueError(msg)
+        present = frame_mask.reshape(-1).to(torch.float32)
+        count = present.sum()
+        if scale != 1.0:
+            if out_act:
+                prediction = torch.tanh(prediction) if out_act == 3 else prediction  # noqa: PLR2004
+            unit = _GaussianNLLMasked.apply(prediction / scale, target / scale, present, count, event_ndims, 0)
+            return unit + (count > 0).to(unit) * (math.prod(prediction.shape[-event_ndims:]) * math.log(scale))
+        return _GaussianNLLMasked.apply(prediction, target, present, count, event_ndims, int(out_act))
     if scale != 1.0:
         # Normal(pred, s): 0.5 ((t-p)/s)^2 + log s + 0.5 log 2pi, by rescaling the unit-scale kernel
         event = math.prod(prediction.shape[-event_ndims:])

@@ -224,6 +224,29 @@ class _WeightGrads:
         return self.own.get(id(w))
 
 
+def _modality(modality: Tensor | None, B: int, T: int) -> Tensor | None:  # noqa: N803
+    """The scans' per-step modality codes: int32 [B, T] on the device, or None (both modalities everywhere)."""
+    if modality is None:
+        return None
+    if modality.dtype != torch.int32 or tuple(modality.shape) != (B, T):
+        msg = f"modality codes must be int32 [{B}, {T}], got {modality.dtype} {tuple(modality.shape)}"
+        raise ValueError(msg)
+    return _c(modality)
+
+
+def modality_codes(mask: Tensor) -> Tensor:
+    """bool [B, T, 2] (audio, vision) -> the scans' int32 [B, T] codes (bit 0 audio, bit 1 vision)."""
+    return (mask[..., 0].to(torch.int32) + 2 * mask[..., 1].to(torch.int32)).contiguous()
+
+
+def _projection(embed: Tensor | None, layer, deter: int, like: Tensor) -> Tensor:  # noqa: ANN001
+    """The hoisted embedding half of a posterior head's first layer; an absent modality (None) is not run: zeros (the kernels
+    read the row, a masked step ignores it)."""
+    if embed is None:
+        return like.new_zeros(*like.shape[:-1], layer.weight.shape[0])
+    return linear(embed, layer.weight[:, deter:], layer.bias)
+
+
 def _expect(**named: tuple[Tensor | None, tuple[int, ...]]) -> None:
     """Host-side shape check of every operand before a launch (a wrong extent would fault the GPU)."""
     for name, (t, shape) in named.items():
@@ -241,7 +264,7 @@ class _MrssmScan(torch.autograd.Function):
     @staticmethod
     def forward(  # noqa: PLR0913, PLR0914
         ctx, cfg: ScanConfig, xa, pa, pv, deter0, stoch0, u_post, u_prior,  # noqa: ANN001
-        w1, w2, b2, wih, bih, whh, bhh, w3, b3, w4, b4, wa1, wa2, ba2, wv1, wv2, bv2,  # noqa: ANN001
+        w1, w2, b2, wih, bih, whh, bhh, w3, b3, w4, b4, wa1, wa2, ba2, wv1, wv2, bv2, modality=None,  # noqa: ANN001
     ):
         # outputs the loss does not touch get NO gradient tensor (autograd would materialise zeros: a fill kernel per unused output
         # and a read of it in the backward scan); the kernels take null pointers for absent gradients
@@ -261,6 +284,7 @@ class _MrssmScan(torch.autograd.Function):
             msg = "weight shapes are inconsistent with (deter, stoch, action, embed)"
             raise ValueError(msg)
         xa, pa, pv, deter0, stoch0, u_post = map(_c, (xa, pa, pv, deter0, stoch0, u_post))
+        modality = _modality(modality, B, T)
         u_prior = _opt(u_prior)
         # forward layouts (include/mtrssm.h: wide outputs stream W^T, narrow outputs stream W)
         w1s_t = _c(w1[:, A:].t())
@@ -278,7 +302,7 @@ class _MrssmScan(torch.autograd.Function):
         io = _lib.fill(
             _lib.MrssmFwdIO(), xa=xa, pa=pa, pv=pv, deter0=deter0, stoch0=stoch0, u_post=u_post, u_prior=u_prior,
             deter=deter, prior_logits=prior_logits, prior_stoch=prior_stoch, post_logits=post_logits, post_stoch=post_stoch,
-            kl=kl, **sv,
+            kl=kl, **sv, modality=modality,
         )
         wp, wq = cfg.kl_weights
         dims = _lib.MrssmDims(B, T, D, H, cfg.cats, cfg.classes, cfg.act, 1, wp, wq, cfg.rows_per_block, cfg.threads)
@@ -323,7 +347,7 @@ class _MrssmScan(torch.autograd.Function):
                                         _lib.stream_ptr(xa.device), flops=2.0 * B * T * macs, nbytes=4.0 * B * T * per_bt),
                        "mtrssm_mrssm_rollout_fwd")
         if need_grad:
-            ctx.cfg, ctx.A = cfg, A
+            ctx.cfg, ctx.A, ctx.modality = cfg, A, modality
             ctx.biases, ctx.w3 = (b2, bih, bhh, b3, b4, ba2, bv2), w3
             ctx.save_for_backward(deter0, stoch0, deter, prior_logits, post_logits, post_stoch, sv["sv_h1"], sv["sv_h2"],
                                   sv["sv_gates"], sv["sv_heads"], sv["sv_la"], sv["sv_lv"], w1s_t, wh1,
@@ -358,7 +382,7 @@ class _MrssmScan(torch.autograd.Function):
             g_deter=_opt(g_deter), g_post_stoch=_opt(g_post_stoch), g_prior_stoch=_opt(g_prior_stoch),
             g_post_logits=_opt(g_post_logits), g_prior_logits=_opt(g_prior_logits), g_kl=_opt(g_kl),
             g_deter0=g_deter0, g_stoch0=g_stoch0, d_z1=d_z1, d_h2=d_h2, d_gi=d_gi, d_gh=d_gh, d_zh=d_zh, d_lp=d_lp, d_la=d_la,
-            d_lv=d_lv,
+            d_lv=d_lv, modality=ctx.modality,
         )
         wp, wq = cfg.kl_weights
         dims = _lib.MrssmDims(B, T, D, H, cfg.cats, cfg.classes, cfg.act, 1, wp, wq, cfg.rows_per_block, cfg.threads)
@@ -416,15 +440,18 @@ class _MrssmScan(torch.autograd.Function):
         r = wg.result
         return (None, d_z1, g_pa, g_pv, g_deter0, g_stoch0, None, None,
                 r(w1), r(w2), r(b2), r(wih), r(bih), r(whh), r(bhh), r(w3), r(b3), r(w4), r(b4), r(wa1), r(wa2), r(ba2), r(wv1), r(wv2),
-                r(bv2))
+                r(bv2), None)
 
 
 def mrssm_posterior_rollout(  # noqa: PLR0913
     transition, audio_rep, vision_rep, actions: Tensor, audio_embed: Tensor, vision_embed: Tensor,  # noqa: ANN001
     deter0: Tensor, stoch0: Tensor, u_post: Tensor, u_prior: Tensor | None, *, balancing: bool, rows_per_block: int = 0,
-    threads: int = 0,
+    threads: int = 0, modality: Tensor | None = None,
 ) -> dict[str, Tensor]:
-    """Run ``mrssm/mopoe_mrssm/core.py:221-256`` for all T steps on the GPU."""
+    """Run ``mrssm/mopoe_mrssm/core.py:221-256`` for all T steps on the GPU.
+
+    ``modality``: optional int32 ``[B, T]`` codes (bit 0 audio, bit 1 vision; ``modality_codes``) of a missing-modality
+    rollout.  An embedding may then be ``None`` when its modality is absent at every step: its projection is not run."""
     factory = transition.distribution_factory
     K, Cc = factory.category_size, factory.class_size
     D = transition.deterministic_size
@@ -441,13 +468,13 @@ def mrssm_posterior_rollout(  # noqa: PLR0913
     cfg = ScanConfig(K, Cc, _lib.ACT_IDS[act_names.pop()], balancing, rows_per_block, threads)
     # hoisted, recurrence-independent halves of the first layers: plain library GEMMs
     xa = linear(actions, l1.weight[:, :A], l1.bias)
-    pa = linear(audio_embed, a1.weight[:, D:], a1.bias)
-    pv = linear(vision_embed, v1.weight[:, D:], v1.bias)
+    pa = _projection(audio_embed, a1, D, xa)
+    pv = _projection(vision_embed, v1, D, xa)
     cell = transition.rnn_cell
     deter, prior_logits, post_logits, post_stoch, prior_stoch, kl = _MrssmScan.apply(
         cfg, xa, pa, pv, deter0, stoch0, u_post, u_prior,
         l1.weight, l2.weight, l2.bias, cell.weight_ih, cell.bias_ih, cell.weight_hh, cell.bias_hh,
-        p1.weight, p1.bias, p2.weight, p2.bias, a1.weight, a2.weight, a2.bias, v1.weight, v2.weight, v2.bias,
+        p1.weight, p1.bias, p2.weight, p2.bias, a1.weight, a2.weight, a2.bias, v1.weight, v2.weight, v2.bias, modality,
     )
     return {"deter": deter, "prior_logits": prior_logits, "post_logits": post_logits, "post_stoch": post_stoch,
             "prior_stoch": prior_stoch if u_prior is not None else None, "kl": kl}
@@ -566,6 +593,7 @@ class _MmtrssmScan(torch.autograd.Function):
         ctx, cfg: MTScanConfig, xl, pa, pv, deter_l0, deter_h0, hidden_l0, hidden_h0, stoch_l0, stoch_h0,  # noqa: ANN001
         u_post_l, u_post_h, u_prior_l, u_prior_h,  # noqa: ANN001
         wxl, wdl, wxh, wdh, bh, wlp1, blp1, wlp2, blp2, wa1, wa2, ba2, wv1, wv2, bv2, whp1, bhp1, whp2, bhp2, whq1, bhq1, whq2, bhq2,  # noqa: ANN001
+        modality=None,  # noqa: ANN001
     ):
         # outputs the loss does not touch get NO gradient tensor (autograd would materialise zeros: a fill kernel per unused output
         # and a read of it in the backward scan); the kernels take null pointers for absent gradients
@@ -608,6 +636,7 @@ class _MmtrssmScan(torch.autograd.Function):
             post_logits_l=_new(xl, B, T, LS), post_logits_h=_new(xl, B, T, HS),
             post_stoch_l=_new(xl, B, T, LS), post_stoch_h=_new(xl, B, T, HS), kl_l=_new(xl, B, T), kl_h=_new(xl, B, T),
         )
+        modality = _modality(modality, B, T)
         need_grad = any(ctx.needs_input_grad)
         sv = dict(sv_l1=None, sv_h1=None, sv_la=None, sv_lv=None)
         if need_grad:
@@ -615,7 +644,7 @@ class _MmtrssmScan(torch.autograd.Function):
         io = _lib.fill(
             _lib.MmtrssmFwdIO(), xl=xl, pa=pa, pv=pv, deter_l0=deter_l0, deter_h0=deter_h0, hidden_l0=hidden_l0,
             hidden_h0=hidden_h0, stoch_l0=stoch_l0, stoch_h0=stoch_h0, u_post_l=u_post_l, u_post_h=u_post_h,
-            u_prior_l=u_prior_l, u_prior_h=u_prior_h, **o, **sv,
+            u_prior_l=u_prior_l, u_prior_h=u_prior_h, **o, **sv, modality=modality,
         )
         dims = cfg.dims(B, T, LD, HD, H, 1)
         macs = (LS + HS) * LD + LD * LD + HS * HD + HD * HD + 4 * H * LD + 2 * H * HD + 3 * LS * H + 2 * HS * H
@@ -634,7 +663,7 @@ class _MmtrssmScan(torch.autograd.Function):
                        "mtrssm_mmtrssm_rollout_fwd")
         del tensors
         if need_grad:
-            ctx.cfg, ctx.A = cfg, A
+            ctx.cfg, ctx.A, ctx.modality = cfg, A, modality
             ctx.biases, ctx.first_layers = (bh, blp1, blp2, ba2, bv2, bhp1, bhp2, bhq1, bhq2), (wlp1, whp1)
             ctx.save_for_backward(
                 deter_l0, deter_h0, stoch_l0, stoch_h0, o["deter_l"], o["deter_h"], o["prior_logits_l"], o["prior_logits_h"],
@@ -676,7 +705,7 @@ class _MmtrssmScan(torch.autograd.Function):
             g_deter_l=_opt(g_dl), g_deter_h=_opt(g_dh), g_hidden_l=_opt(g_hl), g_hidden_h=_opt(g_hh),
             g_post_stoch_l=_opt(g_qsl), g_post_stoch_h=_opt(g_qsh), g_prior_stoch_l=_opt(g_psl), g_prior_stoch_h=_opt(g_psh),
             g_post_logits_l=_opt(g_qll), g_post_logits_h=_opt(g_qlh), g_prior_logits_l=_opt(g_pll), g_prior_logits_h=_opt(g_plh),
-            g_kl_l=_opt(g_kll), g_kl_h=_opt(g_klh), **g0, **d,
+            g_kl_l=_opt(g_kll), g_kl_h=_opt(g_klh), **g0, **d, modality=ctx.modality,
         )
         dims = cfg.dims(B, T, LD, HD, H, 1)
         macs = (LS + HS) * LD + LD * LD + HS * HD + HD * HD + 4 * H * LD + 2 * H * HD + 3 * LS * H + 2 * HS * H
@@ -724,7 +753,7 @@ class _MmtrssmScan(torch.autograd.Function):
         return (None, d["d_ul"], zl[..., H : 2 * H], zl[..., 2 * H : 3 * H], g0["g_deter_l0"], g0["g_deter_h0"], g0["g_hidden_l0"],
                 g0["g_hidden_h0"], g0["g_stoch_l0"], g0["g_stoch_h0"], None, None, None, None,
                 r(wxl), r(wdl), r(wxh), r(wdh), r(bh), r(wlp1), r(blp1), r(wlp2), r(blp2), r(wa1), r(wa2), r(ba2), r(wv1), r(wv2), r(bv2),
-                r(whp1), r(bhp1), r(whp2), r(bhp2), r(whq1), r(bhq1), r(whq2), r(bhq2))
+                r(whp1), r(bhp1), r(whp2), r(bhp2), r(whq1), r(bhq1), r(whq2), r(bhq2), None)
 
 
 def _mt_act(model) -> int:  # noqa: ANN001
@@ -738,8 +767,9 @@ def _mt_act(model) -> int:  # noqa: ANN001
 
 
 def mmtrssm_posterior_rollout(model, actions: Tensor, audio_embed: Tensor, vision_embed: Tensor, state0: dict[str, Tensor],  # noqa: ANN001
-                              noise: dict[str, Tensor | None], *, rows_per_block: int = 0, threads: int = 0) -> dict[str, Tensor]:
-    """Run ``mmtrssm/mopoe_mmtrssm/core.py:405-490`` for all T steps on the GPU."""
+                              noise: dict[str, Tensor | None], *, rows_per_block: int = 0, threads: int = 0,
+                              modality: Tensor | None = None) -> dict[str, Tensor]:
+    """Run ``mmtrssm/mopoe_mmtrssm/core.py:405-490`` for all T steps on the GPU (``modality``: as ``mrssm_posterior_rollout``)."""
     LD = model.ld_dim
     A = actions.shape[-1]
     cfg = MTScanConfig(model.l_dist.category_size, model.l_dist.class_size, model.h_dist.category_size, model.h_dist.class_size,
@@ -752,15 +782,15 @@ def mmtrssm_posterior_rollout(model, actions: Tensor, audio_embed: Tensor, visio
     v1, v2 = model.vision_representation.rnn_to_post_projector.two_layer()
     lr, hr = model.l_rnn, model.h_rnn
     xl = linear(actions, lr._input2h.weight[:, :A], lr._input2h.bias + lr._d2h.bias)  # noqa: SLF001
-    pa = linear(audio_embed, a1.weight[:, LD:], a1.bias)
-    pv = linear(vision_embed, v1.weight[:, LD:], v1.bias)
+    pa = _projection(audio_embed, a1, LD, xl)
+    pv = _projection(vision_embed, v1, LD, xl)
     bh = hr._input2h.bias + hr._d2h.bias  # noqa: SLF001
     out = _MmtrssmScan.apply(
         cfg, xl, pa, pv, state0["deter_l"], state0["deter_h"], state0["hidden_l"], state0["hidden_h"], state0["stoch_l"],
         state0["stoch_h"], noise["u_post_l"], noise["u_post_h"], noise.get("u_prior_l"), noise.get("u_prior_h"),
         lr._input2h.weight, lr._d2h.weight, hr._input2h.weight, hr._d2h.weight, bh,  # noqa: SLF001
         lp1.weight, lp1.bias, lp2.weight, lp2.bias, a1.weight, a2.weight, a2.bias, v1.weight, v2.weight, v2.bias,
-        hp1.weight, hp1.bias, hp2.weight, hp2.bias, hq1.weight, hq1.bias, hq2.weight, hq2.bias,
+        hp1.weight, hp1.bias, hp2.weight, hp2.bias, hq1.weight, hq1.bias, hq2.weight, hq2.bias, modality,
     )
     names = ("deter_l", "deter_h", "hidden_l", "hidden_h", "prior_logits_l", "prior_logits_h", "post_logits_l", "post_logits_h",
              "post_stoch_l", "post_stoch_h", "prior_stoch_l", "prior_stoch_h", "kl_l", "kl_h")
