@@ -606,6 +606,20 @@ int mtrssm_gaussian_nll_masked_fwd(const float* pred, const float* target, const
 int mtrssm_gaussian_nll_masked_bwd(const float* pred, const float* target, const float* present, const float* count,
                                    const float* g_out, int64_t frames, int64_t event, int32_t act, float* g_pred, void* stream);
 
+/* Modality dropout: one call turns uniforms into everything a masked train step reads.
+ *   u: [b_global][S][2] fp32 uniforms, S = ceil(steps / span) (a draw is shared by `span` consecutive steps); modality m
+ *   (0 audio, 1 vision) is present at (b, t) iff u[b][t / span][m] >= p_m (fp32 compare).  At t = 0 only, a row with neither
+ *   present gets the one with the larger u (tie: audio); later steps may have none.
+ * Written for the rows row0 .. row0 + b_local - 1 (a data-parallel rank's slice): codes [b_local][steps] (bit 0 audio, bit 1
+ * vision, the scans' `modality`), present_audio / present_vision [b_local * steps] in {0, 1} (the masked NLL's `present`),
+ * mask0 [b_local][2] bytes in {0, 1} (the t = 0 frame).  counts[2]: the present frames of audio and of vision over ALL b_global
+ * rows (zeroed, then one atomic per workgroup; whole numbers below 2^24, so exact).  Nothing is read back to the host.
+ * Null pointers, non-positive sizes, a slice outside the batch, p outside [0, 1) or b_global * steps >= 2^24 return -1 without
+ * a launch. */
+int mtrssm_modality_dropout(const float* u, int64_t b_global, int64_t steps, int64_t span, float p_audio, float p_vision,
+                            int64_t row0, int64_t b_local, int32_t* codes, float* present_audio, float* present_vision,
+                            uint8_t* mask0, float* counts, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Fused AdamW over one flat fp32 parameter buffer, with global-norm gradient clipping
  * (yaml: torch.optim.AdamW lr 1e-3; trainer.gradient_clip_val 10 -- default.yaml:103-107,119).

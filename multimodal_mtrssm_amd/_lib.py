@@ -136,6 +136,7 @@ SYMBOLS: dict[str, tuple[type | None, list[type]]] = {
     "mtrssm_gaussian_nll_bwd": (C.c_int, [_p, _p, _p, C.c_int64, C.c_int64, _i, _p, _p]),
     "mtrssm_gaussian_nll_masked_fwd": (C.c_int, [_p, _p, _p, _p, C.c_int64, C.c_int64, _i, _p, _p]),
     "mtrssm_gaussian_nll_masked_bwd": (C.c_int, [_p, _p, _p, _p, _p, C.c_int64, C.c_int64, _i, _p, _p]),
+    "mtrssm_modality_dropout": (C.c_int, [_p, C.c_int64, C.c_int64, C.c_int64, _f, _f, C.c_int64, C.c_int64, _p, _p, _p, _p, _p, _p]),
     "mtrssm_sumsq": (C.c_int, [_p, C.c_int64, _p, _p]),
     "mtrssm_adamw_step": (C.c_int, [_p, _p, _p, _p, C.c_int64, _p, _f, _f, _f, _f, _f, _f, _f, _i, _p]),
     "mtrssm_gemm": (C.c_int, [C.POINTER(Gemm), _p]),

@@ -52,6 +52,8 @@ int nll_fwd_launch(const float*, const float*, int64_t, int64_t, int, float*, hi
 int nll_bwd_launch(const float*, const float*, const float*, int64_t, int64_t, int, float*, hipStream_t);
 int nll_masked_fwd_launch(const float*, const float*, const float*, const float*, int64_t, int64_t, int, float*, hipStream_t);
 int nll_masked_bwd_launch(const float*, const float*, const float*, const float*, const float*, int64_t, int64_t, int, float*, hipStream_t);
+int modality_dropout_launch(const float*, int64_t, int64_t, int64_t, float, float, int64_t, int64_t, int32_t*, float*, float*, unsigned char*, float*,
+                            hipStream_t);
 int sumsq_launch(const float*, int64_t, float*, hipStream_t);
 int adamw_launch(float*, const float*, float*, float*, int64_t, const float*, float, float, float, float, float, float, float, int, hipStream_t);
 int gemm_launch(const MtrssmGemm*, hipStream_t);
@@ -146,6 +148,12 @@ MTRSSM_API int mtrssm_gaussian_nll_masked_fwd(const float* pred, const float* ta
 MTRSSM_API int mtrssm_gaussian_nll_masked_bwd(const float* pred, const float* target, const float* present, const float* count,
                                               const float* g_out, int64_t frames, int64_t event, int32_t act, float* g_pred, void* stream) {
   return nll_masked_bwd_launch(pred, target, present, count, g_out, frames, event, act, g_pred, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_modality_dropout(const float* u, int64_t b_global, int64_t steps, int64_t span, float p_audio, float p_vision, int64_t row0,
+                                       int64_t b_local, int32_t* codes, float* present_audio, float* present_vision, uint8_t* mask0,
+                                       float* counts, void* stream) {
+  return modality_dropout_launch(u, b_global, steps, span, p_audio, p_vision, row0, b_local, codes, present_audio, present_vision, mask0, counts,
+                                 static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int mtrssm_sumsq(const float* x, int64_t n, float* out, void* stream) {
   return sumsq_launch(x, n, out, static_cast<hipStream_t>(stream));

@@ -491,6 +491,78 @@ int nll_masked_bwd_launch(const float* pred, const float* target, const float* p
   return check_launch("gaussian_nll_masked_bwd");
 }
 
+// ------------------------------------------------------------------------------------------------
+// Modality dropout: uniforms -> everything a masked train step reads, no host involvement.
+//   present_m(b, t) = u[b, t / span, m] >= p_m   (fp32 compare), m = 0 audio, 1 vision;
+//   at t = 0 only, a row with neither present gets the modality with the larger u (tie: audio).
+// Every (b, t) of the GLOBAL batch is visited (grid-stride); the rank's rows [row0, row0 + b_local) are written out, all rows are
+// counted: wave shuffle + LDS reduction, then ONE vector atomic per workgroup and modality.  The counts are whole numbers
+// below 2^24 (checked by the launch), so the fp32 atomic sums are exact whatever order they arrive in.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void modality_dropout_kernel(
+    const float* __restrict__ u, float p_audio, float p_vision, int span, int T, int S, long b_global, long row0, long b_local,
+    int* __restrict__ codes, float* __restrict__ present_audio, float* __restrict__ present_vision, unsigned char* __restrict__ mask0,
+    float* __restrict__ counts) {
+  __shared__ float red_a[kThreads / kWave], red_v[kThreads / kWave];
+  const long total = b_global * T;
+  float na = 0.f, nv = 0.f;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long b = i / T;
+    const int t = (int)(i - b * T);
+    const float2 uu = reinterpret_cast<const float2*>(u)[b * S + t / span];
+    bool a = uu.x >= p_audio, v = uu.y >= p_vision;
+    if (t == 0 && !a && !v) {
+      a = uu.x >= uu.y;
+      v = !a;
+    }
+    na += a ? 1.f : 0.f;
+    nv += v ? 1.f : 0.f;
+    const long r = b - row0;
+    if (r >= 0 && r < b_local) {
+      const long o = r * T + t;
+      codes[o] = (a ? 1 : 0) | (v ? 2 : 0);
+      present_audio[o] = a ? 1.f : 0.f;
+      present_vision[o] = v ? 1.f : 0.f;
+      if (t == 0) {
+        mask0[2 * r] = a ? 1 : 0;
+        mask0[2 * r + 1] = v ? 1 : 0;
+      }
+    }
+  }
+  const float ta = block_sum(na, red_a), tv = block_sum(nv, red_v);
+  if (threadIdx.x == 0) {
+    atomicAdd(counts, ta);
+    atomicAdd(counts + 1, tv);
+  }
+}
+
+int modality_dropout_launch(const float* u, int64_t b_global, int64_t T, int64_t span, float p_audio, float p_vision, int64_t row0,
+                            int64_t b_local, int32_t* codes, float* present_audio, float* present_vision, unsigned char* mask0,
+                            float* counts, hipStream_t s) {
+  if (!u || !codes || !present_audio || !present_vision || !mask0 || !counts) { set_error("modality_dropout: null pointer"); return MTRSSM_EINVAL; }
+  if (b_global <= 0 || T <= 0 || span <= 0 || b_local <= 0 || row0 < 0 || row0 + b_local > b_global) {
+    set_error("modality_dropout: need B_global, T, span, B_local > 0 and 0 <= row0 <= B_global - B_local (got %lld %lld %lld %lld %lld)",
+              (long long)b_global, (long long)T, (long long)span, (long long)b_local, (long long)row0);
+    return MTRSSM_EINVAL;
+  }
+  if (!(p_audio >= 0.f && p_audio < 1.f) || !(p_vision >= 0.f && p_vision < 1.f)) {
+    set_error("modality_dropout: probabilities must be in [0, 1) (got %g, %g)", (double)p_audio, (double)p_vision);
+    return MTRSSM_EINVAL;
+  }
+  if (b_global * T >= (int64_t)1 << 24 || span >= (int64_t)1 << 31) {
+    set_error("modality_dropout: %lld frames (the fp32 present-frame counts are exact below 2^24)", (long long)(b_global * T));
+    return MTRSSM_EINVAL;
+  }
+  if ((uintptr_t)u & 7) { set_error("modality_dropout: u must be 8-byte aligned"); return MTRSSM_EINVAL; }
+  if (int rc = clear_async(counts, 2 * sizeof(float), s)) return rc;
+  const int64_t S = (T + span - 1) / span;
+  set_last_kernel("mtrssm::modality_dropout_kernel");
+  hipLaunchKernelGGL(modality_dropout_kernel, dim3(grid_for(b_global * T) < 64 ? grid_for(b_global * T) : 64), dim3(kThreads), 0, s, u, p_audio,
+                     p_vision, (int)span, (int)T, (int)S, (long)b_global, (long)row0, (long)b_local, codes, present_audio, present_vision,
+                     mask0, counts);
+  return check_launch("modality_dropout");
+}
+
 int sumsq_launch(const float* x, int64_t n, float* out, hipStream_t s) {
   if (!x || !out || n <= 0) { set_error("sumsq: bad argument"); return MTRSSM_EINVAL; }
   if ((uintptr_t)x & 15) { set_error("sumsq: x must be 16-byte aligned"); return MTRSSM_EINVAL; }

@@ -17,6 +17,15 @@ What makes that legal here:
 * the conv layer's zeroed accumulation chunks and packed-weight buffers are (re)created inside the capture
   (``conv.reset_scratch``), so each replay starts from the state the capture started from.
 
+Masked steps are captured in one of two modes, fixed for the graph's life:
+
+* ``modality_dropout=``: the ``u_mask`` uniforms are drawn outside the graph with the others; the sampler launch and everything
+  downstream of it is inside, so every replay trains on a fresh mask with no host round trip;
+* ``masked=True``: batches are 7-tuples; ``step`` validates the mask's t = 0 frame on the host and copies the mask into a fixed
+  buffer, from which the captured region derives the scans' codes and the NLL's planes.
+
+Observations that are ``None`` stay eager-only: a capture cannot drop an encoder per step.
+
 With more than one rank the gradient all-reduce (RCCL) and the optimizer run eagerly after the replay: the
 exchange stays a plain ``torch.distributed`` call.
 """
@@ -27,6 +36,8 @@ import torch
 from torch import Tensor
 
 from multimodal_mtrssm_amd import conv, scan
+from multimodal_mtrssm_amd.core import _check_modality_mask
+from multimodal_mtrssm_amd.dropout import ModalityDropout, StepMask
 from multimodal_mtrssm_amd.optim import FlatAdamW, FlatParameters
 from multimodal_mtrssm_amd.parallel import FlatDataParallel, GlobalRowNoise
 
@@ -35,7 +46,8 @@ def _refuse_modality_mask(model: torch.nn.Module, batch: tuple[Tensor, ...]) -> 
     """The captured step runs the unmasked kernels: a batch that carries a modality mask (7th entry) would be trained as if
     every modality were present.  Refused instead (run such batches eagerly: ``model.shared_step``)."""
     if model.get_modality_mask_from_batch(batch) is not None:
-        msg = "CapturedTrainStep does not support modality masks (a 7-tuple batch): train masked batches with the eager step"
+        msg = ("CapturedTrainStep without masked=True does not take a modality mask (a 7-tuple batch): capture with masked=True "
+               "(or modality_dropout=), or train masked batches with the eager step")
         raise NotImplementedError(msg)
 
 
@@ -46,26 +58,64 @@ class CapturedTrainStep:
     Construction runs ``warmup`` real steps on the capture stream (every lazy allocation, plan entry and workspace must
     exist before the capture) and then puts parameters, Adam moments, the device-side step count and the noise generator
     BACK where they were: a run with the graph is step for step the eager run.  ``close()`` (or garbage collection) releases
-    the pin on the conv layer's packed-weight plan."""
+    the pin on the conv layer's packed-weight plan.
+
+    ``modality_dropout`` (a ``ModalityDropout``) or ``masked=True`` capture the masked step (module docstring); the graph then
+    takes only that kind of batch, an unmasked graph only 6-tuples."""
 
     def __init__(self, model: torch.nn.Module, flat: FlatParameters, opt: FlatAdamW, dp: FlatDataParallel,  # noqa: PLR0913
-                 batch: tuple[Tensor, ...], noise: GlobalRowNoise, *, warmup: int = 3) -> None:
-        _refuse_modality_mask(model, batch)
-        self.model, self.flat, self.opt, self.dp, self.noise = model, flat, opt, dp, noise
-        self.batch = tuple(x.clone() for x in batch)
+                 batch: tuple[Tensor, ...], noise: GlobalRowNoise, *, warmup: int = 3,
+                 modality_dropout: ModalityDropout | None = None, masked: bool = False) -> None:
+        if modality_dropout is not None and masked:
+            msg = "give modality_dropout= (the graph samples its masks) or masked=True (the batches carry them), not both"
+            raise ValueError(msg)
+        if modality_dropout is not None and not isinstance(modality_dropout, ModalityDropout):
+            msg = f"modality_dropout must be a ModalityDropout, got {type(modality_dropout).__name__}"
+            raise ValueError(msg)
+        self.model, self.masked, self.dropout = model, bool(masked), modality_dropout
+        self._check_batch_kind(batch)
+        self.flat, self.opt, self.dp, self.noise = flat, opt, dp, noise
         b, t = batch[0].shape[:2]
-        self.shapes = model.noise_shapes(b, t)
         dev = batch[0].device
-        self.uniforms = {k: torch.empty(s, device=dev, dtype=torch.float32) for k, s in self.shapes.items()}
+        self.mask: Tensor | None = None
+        if self.masked:
+            _check_modality_mask(batch[6], b, t, dev, first_step=True)
+            self.mask = batch[6].clone()
+        self.batch = tuple(x.clone() for x in batch[:6])
+        self.shapes = dict(model.noise_shapes(b, t))
+        if self.dropout is not None:
+            self.dropout = self.dropout.for_rank(dp.world, dp.rank)
+            self.shapes["u_mask"] = self.dropout.noise_shape(b, t)
+        # (a GLOBAL_KEYS entry keeps the rows of every rank: GlobalRowNoise.draw)
+        self.uniforms = {k: torch.empty((s[0] * noise.world if k in noise.GLOBAL_KEYS else s[0], *s[1:]), device=dev, dtype=torch.float32)
+                         for k, s in self.shapes.items()}
         self.fused_optimizer = dp.world == 1
         self.keys: list[str] = []
         self.graph: torch.cuda.CUDAGraph | None = None
         self._capture(warmup)
 
+    def _check_batch_kind(self, batch: tuple[Tensor, ...]) -> None:
+        """A graph is masked or unmasked for life: refuse the other kind of batch, and ``None`` observations always."""
+        if batch[1] is None or batch[2] is None:
+            msg = "CapturedTrainStep needs both observations: a None modality is eager-only (a capture cannot drop an encoder per step)"
+            raise ValueError(msg)
+        has_mask = self.model.get_modality_mask_from_batch(batch) is not None
+        if self.masked and not has_mask:
+            msg = "this CapturedTrainStep was captured with masked=True: every batch must be a 7-tuple carrying its modality mask"
+            raise ValueError(msg)
+        if self.dropout is not None and has_mask:
+            msg = "this CapturedTrainStep samples its modality masks (modality_dropout=): it takes 6-tuple batches without a mask"
+            raise ValueError(msg)
+        if not self.masked and self.dropout is None:
+            _refuse_modality_mask(self.model, batch)
+
     # the captured region -------------------------------------------------------------------------
     def _body(self) -> list[str]:
         self.opt.zero_grad()
-        out = self.model.shared_step(self.batch, self.uniforms)
+        if self.masked:  # (validated on the host by step(); codes, planes and counts are derived here, inside the capture)
+            out = self.model._elbo_step(self.batch, self.uniforms, StepMask.from_mask(self.mask))  # noqa: SLF001
+        else:
+            out = self.model.shared_step(self.batch, self.uniforms, modality_dropout=self.dropout)
         out["loss"].backward()
         keys = list(out)
         if self.fused_optimizer:
@@ -131,10 +181,14 @@ class CapturedTrainStep:
     def step(self, batch: tuple[Tensor, ...] | None = None) -> dict[str, Tensor]:
         scan.STATUS.poll()  # a cooperative scan launch of an earlier replay gave up (the device skipped that update): raise
         if batch is not None:
-            _refuse_modality_mask(self.model, batch)
+            self._check_batch_kind(batch)
+            if self.masked:  # the t = 0 check reads the mask back: here, before the replay, never inside the capture
+                _check_modality_mask(batch[6], *self.batch[0].shape[:2], self.batch[0].device, first_step=True)
         if batch is not None and batch[0] is not self.batch[0]:
-            for dst, src in zip(self.batch, batch, strict=True):
+            for dst, src in zip(self.batch, batch[:6], strict=True):
                 dst.copy_(src)
+        if batch is not None and self.masked and batch[6] is not self.mask:
+            self.mask.copy_(batch[6])
         self.noise.draw(self.shapes, out=self.uniforms)
         self.opt.sync_lr()
         assert self.graph is not None

@@ -72,24 +72,38 @@ class _GaussianNLLMasked(torch.autograd.Function):
         return g_pred, None, None, None, None, None
 
 
-def likelihood(prediction: Tensor, target: Tensor, event_ndims: int, scale: float = 1.0, *, out_act: int = 0,
-               frame_mask: Tensor | None = None) -> Tensor:
+def likelihood(prediction: Tensor, target: Tensor, event_ndims: int, scale: float = 1.0, *, out_act: int = 0,  # noqa: PLR0913
+               frame_mask: Tensor | None = None, frame_present: tuple[Tensor, Tensor] | None = None) -> Tensor:
     """Negative mean log-likelihood of ``target`` under ``Normal(act(prediction), scale)`` (``objective.py:7``).  ``out_act``
     (0 = Identity as in the reference's signature, 3 = Tanh) lets the decoder hand in its raw last-layer output: the
     out_activation is applied while the kernel reads it and its derivative in the backward.
 
     ``frame_mask``: optional bool tensor over the frame dims (``prediction.shape[:-event_ndims]``).  The mean then runs over the
-    frames where it is True only; a mask with no True entry gives 0 and a zero gradient."""
+    frames where it is True only; a mask with no True entry gives 0 and a zero gradient.
+
+    ``frame_present``: the same mask already in the kernels' form, ``(present, count)``: float32 {0, 1} per frame (flat) and the
+    device scalar the masked sum is divided by.  ``count`` need not be ``present.sum()``: a data-parallel rank passes
+    ``global count / world`` (``dropout.DropoutSample.step_mask``)."""
     if prediction.shape != target.shape:
         msg = f"prediction {tuple(prediction.shape)} and target {tuple(target.shape)} must have the same shape"
         raise ValueError(msg)
-    if frame_mask is not None:
+    if frame_mask is not None and frame_present is not None:
+        msg = "give frame_mask or frame_present, not both"
+        raise ValueError(msg)
+    if frame_mask is not None or frame_present is not None:
         frame_shape = tuple(prediction.shape[: prediction.dim() - event_ndims])
-        if frame_mask.dtype != torch.bool or tuple(frame_mask.shape) != frame_shape:
-            msg = f"frame_mask must be a bool tensor of shape {frame_shape}, got {frame_mask.dtype} {tuple(frame_mask.shape)}"
-            raise ValueError(msg)
-        present = frame_mask.reshape(-1).to(torch.float32)
-        count = present.sum()
+        if frame_present is not None:
+            present, count = frame_present
+            if present.dtype != torch.float32 or present.numel() != math.prod(frame_shape) or count.numel() != 1:
+                msg = f"frame_present must be (float32 [{math.prod(frame_shape)}], scalar), got {present.dtype} {tuple(present.shape)}"
+                raise ValueError(msg)
+            present = present.reshape(-1)
+        else:
+            if frame_mask.dtype != torch.bool or tuple(frame_mask.shape) != frame_shape:
+                msg = f"frame_mask must be a bool tensor of shape {frame_shape}, got {frame_mask.dtype} {tuple(frame_mask.shape)}"
+                raise ValueError(msg)
+            present = frame_mask.reshape(-1).to(torch.float32)
+            count = present.sum()
         if scale != 1.0:
             if out_act:
                 prediction = torch.tanh(prediction) if out_act == 3 else prediction  # noqa: PLR2004

@@ -17,6 +17,7 @@ import torch.distributed as dist
 from torch import Tensor
 
 from multimodal_mtrssm_amd import conv, linear
+from multimodal_mtrssm_amd.dropout import ModalityDropout
 from multimodal_mtrssm_amd.optim import FlatParameters
 
 
@@ -27,7 +28,12 @@ class GlobalRowNoise:
     (``[B_global, ...]`` per key, keys in sorted order -- a few hundred KB), then keeps its own rows.  Row g
     of the global batch therefore sees the same numbers whether the job runs on 1, 2 or 8 ranks, and B=64 on one
     rank equals 2 x 32 on two ranks bit for bit.  ``out`` lets a caller keep the result in fixed buffers (the captured
-    train step reads them; the draw itself stays outside the capture)."""
+    train step reads them; the draw itself stays outside the capture).
+
+    Keys in ``GLOBAL_KEYS`` are not sliced: ``u_mask`` (modality dropout) reaches every rank with all ``B_global`` rows, because
+    the sampler counts the present frames of the whole global batch."""
+
+    GLOBAL_KEYS = frozenset({"u_mask"})
 
     def __init__(self, seed: int, world: int, rank: int, device: torch.device | str) -> None:
         self.world, self.rank = int(world), int(rank)
@@ -41,7 +47,7 @@ class GlobalRowNoise:
         for key in sorted(shapes):
             local = tuple(shapes[key])
             full = torch.rand((local[0] * self.world, *local[1:]), generator=self.gen, device=self.device, dtype=torch.float32)
-            mine = full[self.rank * local[0] : (self.rank + 1) * local[0]]
+            mine = full if key in self.GLOBAL_KEYS else full[self.rank * local[0] : (self.rank + 1) * local[0]]
             if out is not None:
                 out[key].copy_(mine)
                 mine = out[key]
@@ -75,6 +81,11 @@ class FlatDataParallel:
     def noise_source(self, seed: int, device: torch.device | str | None = None) -> GlobalRowNoise:
         """A ``GlobalRowNoise`` for this rank: pass ``source.draw(model.noise_shapes(B_local, T))`` as ``shared_step``'s ``noise``."""
         return GlobalRowNoise(seed, self.world, self.rank, self.flat.param.device if device is None else device)
+
+    def modality_dropout(self, dropout: ModalityDropout) -> ModalityDropout:
+        """``dropout`` bound to this rank's rows of the global batch: pass the result as ``shared_step``'s ``modality_dropout``
+        (or set it as ``model.modality_dropout``) and draw ``u_mask`` with ``noise_source``."""
+        return dropout.for_rank(self.world, self.rank)
 
     @property
     def grad_scale(self) -> float:
