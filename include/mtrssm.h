@@ -565,6 +565,45 @@ int mtrssm_channel_sum(const float* x, int32_t N, int32_t C, int32_t HW, float* 
  * ------------------------------------------------------------------------------------------ */
 int mtrssm_episode_gather(const float* store, const int64_t* idx, const float* noise, int64_t n_episodes, int64_t B, int64_t T,
                           int64_t Tfull, int64_t E, float std_, float* input, float* target, void* stream);
+/* The same pair from a WINDOW of each episode (replaces the TakeFirstN of the chain by a slice
+ * [start, start + T), which the reference cannot express: it trains on the first T frames only):
+ *   target[b, t, :] = store[idx[b], start[b] + t, :]          input = target + noise * std as above (same two roundings)
+ * start: [B] int32 in DEVICE memory, read by the kernel, so that a captured graph replays with new windows and no host round
+ * trip.  The launcher therefore cannot range-check the starts: the kernel clamps start[b] into [0, Tfull - T], and the
+ * caller validates them where it makes them (dataset.DeviceEpisodeLoader draws them on the host).  start == NULL returns -1
+ * (mtrssm_episode_gather is the entry for the first T frames); everything else as mtrssm_episode_gather. */
+int mtrssm_episode_gather_window(const float* store, const int64_t* idx, const int32_t* start, const float* noise, int64_t n_episodes,
+                                 int64_t B, int64_t T, int64_t Tfull, int64_t E, float std_, float* input, float* target, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Carried state of truncated BPTT: the initial state of a train step is, per batch row, either the
+ * fresh one (core.py:121-135: the chunk's own frame 0 -> init_proj -> prior head) or the posterior the previous chunk ended
+ * with.  Both calls are ONE launch over a table of up to MTRSSM_STATE_MAX row-major fp32 tensors [B, width[k]]
+ * (MRSSM: deter, stoch; MMTRSSM: deter_l, deter_h, stoch_l, stoch_h, hidden_l, hidden_h), the table passed to the kernel by value.
+ *
+ * mtrssm_state_select: dst[k][b, :] = reset[b] ? src[k][b * src_stride[k] : + width[k]] : alt[k][b, :]
+ *   reset: [B] bytes in {0, 1} in DEVICE memory (read by the kernel: the launch sequence is the same whether a row starts an
+ *   episode or continues one, so one captured graph serves every chunk).  src = the fresh state, its rows src_stride[k] >= width[k]
+ *   floats apart (a column slice of init_proj's output needs no copy); alt = the carry, contiguous; alt[k] == NULL stands for
+ *   zeros: the backward of the select is this call with src = the incoming gradient, g_fresh[b] = reset[b] ? g[b] : 0 (the
+ *   carry never receives a gradient).  Replaces nothing upstream: the reference cannot continue a sequence.
+ * mtrssm_state_save: dst[k][b, :] = src[k][b, steps - 1, :], src = an output [B, steps, width[k]] of the scan, read in place
+ *   (no [:, -1].contiguous() copies); src_stride and alt are ignored.
+ * Entries whose width, stride and pointers are multiples of 4 floats / 16 bytes move 16 bytes per lane, the others 4.
+ * A null table, reset, src or dst, count outside 1 .. MTRSSM_STATE_MAX, non-positive B / steps / width, a stride below the
+ * width or a pointer that is not 4-byte aligned return -1 without a launch.
+ * ------------------------------------------------------------------------------------------ */
+#define MTRSSM_STATE_MAX 6
+typedef struct MtrssmStateTable {
+  int32_t count;
+  int32_t width[MTRSSM_STATE_MAX];
+  int64_t src_stride[MTRSSM_STATE_MAX];
+  const float* src[MTRSSM_STATE_MAX];
+  const float* alt[MTRSSM_STATE_MAX];
+  float* dst[MTRSSM_STATE_MAX];
+} MtrssmStateTable;
+int mtrssm_state_select(const MtrssmStateTable* table, const uint8_t* reset, int64_t B, void* stream);
+int mtrssm_state_save(const MtrssmStateTable* table, int64_t B, int64_t steps, void* stream);
 
 /* The scalar end of shared_step (core.py:187-221; mmtrssm core.py:563-606) in one launch each way:
  *   recon = nll_a + nll_v;  kl_j = c_j * mean_i kl_j[i], i < n (kl1 may be NULL);  loss = recon + kl_0 + kl_1, written to four scalars (o_k1 may be NULL).

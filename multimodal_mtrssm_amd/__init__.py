@@ -6,9 +6,10 @@ running on hand-written HIP kernels for gfx950 through the C-ABI of ``include/mt
 Importing the package does not need a GPU; running a rollout does, and fails loudly otherwise.
 """
 
+from multimodal_mtrssm_amd.carry import StateCarry
 from multimodal_mtrssm_amd.cnn import Decoder, Encoder
 from multimodal_mtrssm_amd.core import MoPoE_MMTRSSM, MoPoE_MRSSM
-from multimodal_mtrssm_amd.dataset import DeviceEpisodeLoader, EpisodeDataModule, EpisodeDataModuleConfig
+from multimodal_mtrssm_amd.dataset import DeviceEpisodeLoader, EpisodeBatch, EpisodeDataModule, EpisodeDataModuleConfig
 from multimodal_mtrssm_amd.distributions import (
     Distribution,
     MultiOneHot,
@@ -29,8 +30,8 @@ from multimodal_mtrssm_amd.state import MTState, State, cat_mtstates, cat_states
 __version__ = "0.1.0"
 
 __all__ = [
-    "MLP", "MTRNN", "Decoder", "DeviceEpisodeLoader", "Distribution", "Encoder", "EpisodeDataModule", "EpisodeDataModuleConfig", "FlatAdamW", "FlatDataParallel", "GlobalRowNoise", "MTState", "MoPoE_MMTRSSM",
-    "MoPoE_MRSSM", "ModalityDropout", "MultiOneHot", "MultiOneHotFactory", "ReduceLROnPlateau", "Representation", "State", "Transition", "cat_distribution",
+    "MLP", "MTRNN", "Decoder", "DeviceEpisodeLoader", "Distribution", "Encoder", "EpisodeBatch", "EpisodeDataModule", "EpisodeDataModuleConfig", "FlatAdamW", "FlatDataParallel", "GlobalRowNoise", "MTState", "MoPoE_MMTRSSM",
+    "MoPoE_MRSSM", "ModalityDropout", "MultiOneHot", "MultiOneHotFactory", "ReduceLROnPlateau", "Representation", "State", "StateCarry", "Transition", "cat_distribution",
     "cat_mtstates", "cat_states", "inject_uniforms", "kl_divergence", "likelihood", "load_reference_checkpoint", "make_mmtrssm", "make_mrssm",
     "stack_distribution", "stack_mtstates", "stack_states",
 ]

@@ -82,6 +82,11 @@ Gemm = _struct("MtrssmGemm", _ptrs("A", "B", "C", "bias", "zgrad", "colsum") + [
     "M", "N", "R", "lda", "ldb", "ldc", "ldz", "a_rmajor", "b_rmajor", "act_a", "act_b", "act_out", "act_z", "accumulate", "split_r")]
     + [("tickets", _p), ("n_tickets", _i), ("mfma_split", _i)])
 
+STATE_MAX = 6  # MTRSSM_STATE_MAX
+StateTable = _struct("MtrssmStateTable", [
+    ("count", _i), ("width", _i * STATE_MAX), ("src_stride", C.c_int64 * STATE_MAX), ("src", _p * STATE_MAX), ("alt", _p * STATE_MAX),
+    ("dst", _p * STATE_MAX)])
+
 # every symbol include/mtrssm.h declares (tests/test_capi.py checks the header against this list)
 SYMBOLS: dict[str, tuple[type | None, list[type]]] = {
     "mtrssm_version": (C.c_int, []),
@@ -128,6 +133,9 @@ SYMBOLS: dict[str, tuple[type | None, list[type]]] = {
                                     _p, _p, _p, _p]),
     "mtrssm_conv_tgather_thin": (C.c_int, [_i] * 11 + [_p, _p, _p, _i, _i, _p, _p, _p, _p]),
     "mtrssm_episode_gather": (C.c_int, [_p, _p, _p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _f, _p, _p, _p]),
+    "mtrssm_episode_gather_window": (C.c_int, [_p, _p, _p, _p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _f, _p, _p, _p]),
+    "mtrssm_state_select": (C.c_int, [C.POINTER(StateTable), _p, C.c_int64, _p]),
+    "mtrssm_state_save": (C.c_int, [C.POINTER(StateTable), C.c_int64, C.c_int64, _p]),
     "mtrssm_elbo_combine_fwd": (C.c_int, [_p, _p, _p, _p, C.c_int64, C.c_float, C.c_float, _p, _p, _p, _p, _p]),
     "mtrssm_elbo_combine_bwd": (C.c_int, [_p, _p, _p, _p, C.c_int64, C.c_float, C.c_float, _p, _p, _p, _p, _p]),
     "mtrssm_categorical_sample_fwd": (C.c_int, [_p, _p, C.c_int64, _i, _i, _p, _p, _p, _p]),

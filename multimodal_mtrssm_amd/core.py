@@ -20,6 +20,7 @@ import torch
 from torch import Tensor, nn
 
 from multimodal_mtrssm_amd import cnn, conv, scan
+from multimodal_mtrssm_amd.carry import StateCarry
 from multimodal_mtrssm_amd.distributions import MultiOneHot, MultiOneHotFactory, draw_uniforms, kl_divergence, onehot_from_uniforms
 from multimodal_mtrssm_amd.dropout import ModalityDropout, StepMask
 from multimodal_mtrssm_amd.networks import MTRNN, Representation, Transition
@@ -250,6 +251,7 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         self.scan_rows_per_block = 0  # 0 = library default (tuning knobs)
         self.scan_threads = 0
         self.modality_dropout: ModalityDropout | None = None  # training_step samples a modality mask with it
+        self.state_carry: StateCarry | None = None  # training_step / validation_step continue from its "train" / "val" set
 
     # -- batch accessors (mrssm core.py:310-355) --------------------------------------------
     @staticmethod
@@ -459,16 +461,68 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
             raise ValueError(msg)
         return modality_dropout.sample(u, T).step_mask()
 
-    def shared_step(self, batch: tuple[Tensor, ...], noise: Noise | None = None, modality_mask: Tensor | None = None,
-                    modality_dropout: ModalityDropout | None = None) -> dict[str, Tensor]:
+    def shared_step(self, batch: tuple[Tensor, ...], noise: Noise | None = None, modality_mask: Tensor | None = None,  # noqa: PLR0913
+                    modality_dropout: ModalityDropout | None = None, state_carry: StateCarry | None = None,
+                    reset: Tensor | None = None, *, carry_prefix: str = "train") -> dict[str, Tensor]:
         """``core.py:187-221``: ``loss = recon + kl_coeff * KL(post || prior)`` (MMTRSSM, ``mmtrssm core.py:563-606``:
         ``recon + kl_coeff KL_l + kl_coeff w_kl_h KL_h``).  ``modality_mask`` (or a 7th batch entry, bool ``[B, T, 2]``): each
         recon term averages over the frames where its modality is present; the KL stays the mean over all B*T (0 on steps with
         no modality).  ``modality_dropout``: the mask is sampled on the device from ``noise["u_mask"]`` (drawn here when
-        absent) and each recon sum is divided by the GLOBAL batch's present frames / world."""
-        return self._elbo_step(batch, noise, self._step_mask(batch, noise, modality_mask, modality_dropout))
+        absent) and each recon sum is divided by the GLOBAL batch's present frames / world.
 
-    def _elbo_step(self, batch: tuple[Tensor, ...], noise: Noise | None, sm: StepMask | None) -> dict[str, Tensor]:
+        ``state_carry``: rows with ``reset[b]`` False start from the posterior the previous step of
+        ``carry_prefix``'s set ended with instead of the chunk's own frame 0; afterwards the posterior at t = T - 1 (detached) is
+        saved there.  ``reset`` (bool ``[B]``) defaults to ``batch.reset`` of an ``EpisodeBatch``; a host tensor is also checked
+        against the carry's rules, a device tensor is trusted (an empty carry refuses it)."""
+        sm = self._step_mask(batch, noise, modality_mask, modality_dropout)
+        if state_carry is None:
+            return self._elbo_step(batch, noise, sm)
+        return self._elbo_step(batch, noise, sm, self._carry_of(batch, state_carry, reset, carry_prefix))
+
+    @staticmethod
+    def _carry_of(batch: tuple[Tensor, ...], state_carry: StateCarry, reset: Tensor | None, prefix: str) -> tuple[StateCarry, str, Tensor]:
+        """Validated ``(carry, prefix, reset on the device)`` of a step; host rules only, nothing is read back."""
+        if not isinstance(state_carry, StateCarry):
+            msg = f"state_carry must be a StateCarry, got {type(state_carry).__name__}"
+            raise ValueError(msg)
+        dev = batch[0].device
+        if reset is None:
+            reset, reset_host = getattr(batch, "reset", None), getattr(batch, "reset_host", None)
+            if reset is None:
+                msg = "state_carry needs reset= (bool [B]) or a batch that carries one (an EpisodeBatch of a windowed loader)"
+                raise ValueError(msg)
+        elif not isinstance(reset, Tensor) or reset.dtype != torch.bool:
+            msg = f"reset must be a bool tensor, got {getattr(reset, 'dtype', type(reset))}"
+            raise ValueError(msg)
+        else:
+            reset_host = None if reset.is_cuda else reset
+        if tuple(reset.shape) != (batch[0].shape[0],):
+            msg = f"reset must have shape ({batch[0].shape[0]},), got {tuple(reset.shape)}"
+            raise ValueError(msg)
+        state_carry.check(prefix, batch[0].shape[0], reset_host)
+        return state_carry, prefix, reset.to(dev).contiguous()
+
+    _FRESH_KEYS = ("deter", "stoch")  # State attributes the scan starts from
+    _LAST_KEYS = {"deter": "deter", "stoch": "post_stoch"}  # ... and the scan outputs that continue them
+
+    def _state0(self, fresh: State | MTState, carry: tuple[StateCarry, str, Tensor] | None) -> State | MTState:
+        """The scan's initial state: ``fresh`` (computed for all rows, so the launch sequence is static), or per row the carried one."""
+        if carry is None:
+            return fresh
+        sc, prefix, reset = carry
+        got = sc.select(prefix, reset, {k: getattr(fresh, k) for k in self._FRESH_KEYS})
+        return self._state_like(fresh, got)
+
+    @staticmethod
+    def _state_like(fresh: State, got: dict[str, Tensor]) -> State:
+        return State(deter=got["deter"], distribution=fresh.distribution, stoch=got["stoch"])
+
+    def _save_carry(self, out: dict[str, Tensor], carry: tuple[StateCarry, str, Tensor] | None) -> None:
+        if carry is not None:
+            carry[0].save(carry[1], {k: out[v] for k, v in self._LAST_KEYS.items()})
+
+    def _elbo_step(self, batch: tuple[Tensor, ...], noise: Noise | None, sm: StepMask | None,
+                   carry: tuple[StateCarry, str, Tensor] | None = None) -> dict[str, Tensor]:
         """``shared_step`` behind the mask handling (the captured step enters here with a mask it validated itself)."""
         action_input = batch[0]
         audio_obs, vision_obs = self.get_observations_from_batch(batch)
@@ -477,8 +531,10 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         u_init = None if noise is None else noise.get("u_init")
         state0 = self._initial_from_embed(_masked_mean_embed(audio_embed[:, 0], vision_embed[:, 0], None if sm is None else sm.mask0),
                                           u_init)
+        state0 = self._state0(state0, carry)
         out = self._rollout_embedded(action_input, audio_embed, vision_embed, state0, noise, sample_prior=False,
                                      modality=None if sm is None else sm.codes)
+        self._save_carry(out, carry)
         feature = torch.cat([out["deter"], out["post_stoch"]], dim=-1)
         parts = self._reconstruction_losses(feature, self.get_targets_from_batch(batch), sum_recon=False, step_mask=sm)
         recon, kl_div, _, loss = _elbo(parts["recon/audio"], parts["recon/vision"], out["kl"], float(self.kl_coeff))
@@ -486,7 +542,10 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
 
     def _step(self, batch: tuple[Tensor, ...], prefix: str, *, with_loss_key: bool,
               modality_dropout: ModalityDropout | None = None) -> dict[str, Tensor]:
-        loss_dict = self.shared_step(batch, modality_dropout=modality_dropout)
+        if self.state_carry is None:
+            loss_dict = self.shared_step(batch, modality_dropout=modality_dropout)
+        else:
+            loss_dict = self.shared_step(batch, modality_dropout=modality_dropout, state_carry=self.state_carry, carry_prefix=prefix)
         renamed = {"loss": loss_dict["loss"]} if with_loss_key else {}
         renamed[f"{prefix}/loss"] = loss_dict["loss"]
         for key, value in loss_dict.items():
@@ -647,7 +706,16 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
             stoch_h=out["prior_stoch_h"], stoch_l=out["prior_stoch_l"],
         )
 
-    def _elbo_step(self, batch: tuple[Tensor, ...], noise: Noise | None, sm: StepMask | None) -> dict[str, Tensor]:
+    _FRESH_KEYS = ("deter_l", "deter_h", "stoch_l", "stoch_h", "hidden_l", "hidden_h")
+    _LAST_KEYS = {"deter_l": "deter_l", "deter_h": "deter_h", "stoch_l": "post_stoch_l", "stoch_h": "post_stoch_h", "hidden_l": "hidden_l",  # noqa: RUF012
+                  "hidden_h": "hidden_h"}
+
+    @staticmethod
+    def _state_like(fresh: MTState, got: dict[str, Tensor]) -> MTState:  # type: ignore[override]
+        return MTState(distribution_h=fresh.distribution_h, distribution_l=fresh.distribution_l, **got)
+
+    def _elbo_step(self, batch: tuple[Tensor, ...], noise: Noise | None, sm: StepMask | None,
+                   carry: tuple[StateCarry, str, Tensor] | None = None) -> dict[str, Tensor]:
         """``mmtrssm core.py:563-606``: ``loss = recon + kl_coeff KL_l + kl_coeff w_kl_h KL_h`` (``shared_step``'s body)."""
         action_input = batch[0]
         audio_obs, vision_obs = self.get_observations_from_batch(batch)
@@ -655,8 +723,10 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
         audio_embed, vision_embed = self._encode_both(audio_obs, vision_obs)
         state0 = self._initial_from_embed(_masked_mean_embed(audio_embed[:, 0], vision_embed[:, 0], None if sm is None else sm.mask0),
                                           noise)
+        state0 = self._state0(state0, carry)
         out = self._rollout_embedded(action_input, audio_embed, vision_embed, state0, noise, sample_prior=False,
                                      modality=None if sm is None else sm.codes)
+        self._save_carry(out, carry)
         feature = torch.cat([out["deter_h"], out["post_stoch_h"], out["deter_l"], out["post_stoch_l"]], dim=-1)
         parts = self._reconstruction_losses(feature, self.get_targets_from_batch(batch), sum_recon=False, step_mask=sm)
         recon, kl_div_l, kl_div_h, loss = _elbo(parts["recon/audio"], parts["recon/vision"], out["kl_l"], float(self.kl_coeff), out["kl_h"],

@@ -24,6 +24,10 @@ int mmtrssm_fwd_launch(const MtrssmMmtrssmDims*, const MtrssmMmtrssmFwdWeights*,
 int mmtrssm_bwd_launch(const MtrssmMmtrssmDims*, const MtrssmMmtrssmBwdWeights*, const MtrssmMmtrssmBwdIO*, hipStream_t);
 int conv_gather_gemm_launch(const MtrssmConvGeom*, const float*, const float*, const float*, const unsigned short*, const float*, const float*, const float*, float*, hipStream_t);
 int episode_gather_launch(const float*, const int64_t*, const float*, int64_t, int64_t, int64_t, int64_t, int64_t, float, float*, float*, hipStream_t);
+int episode_gather_window_launch(const float*, const int64_t*, const int32_t*, const float*, int64_t, int64_t, int64_t, int64_t, int64_t, float, float*,
+                                 float*, hipStream_t);
+int state_select_launch(const MtrssmStateTable*, const unsigned char*, int64_t, hipStream_t);
+int state_save_launch(const MtrssmStateTable*, int64_t, int64_t, hipStream_t);
 int conv_gather_gemm_pair_launch(const MtrssmConvGeom*, const float*, const float*, const float*, const unsigned short*, const float*, const float*, const float*, float*,
                                  const MtrssmConvGeom*, const float*, const float*, const float*, const unsigned short*, const float*, const float*, const float*, float*, hipStream_t);
 int conv_residual_fwd_supported(const MtrssmConvGeom*);
@@ -233,6 +237,16 @@ MTRSSM_API int mtrssm_conv_gather_gemm(const MtrssmConvGeom* g, const float* src
 MTRSSM_API int mtrssm_episode_gather(const float* store, const int64_t* idx, const float* noise, int64_t n_episodes, int64_t B, int64_t T,
                                      int64_t Tfull, int64_t E, float std_, float* input, float* target, void* stream) {
   return episode_gather_launch(store, idx, noise, n_episodes, B, T, Tfull, E, std_, input, target, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_episode_gather_window(const float* store, const int64_t* idx, const int32_t* start, const float* noise, int64_t n_episodes,
+                                            int64_t B, int64_t T, int64_t Tfull, int64_t E, float std_, float* input, float* target, void* stream) {
+  return episode_gather_window_launch(store, idx, start, noise, n_episodes, B, T, Tfull, E, std_, input, target, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_state_select(const MtrssmStateTable* table, const uint8_t* reset, int64_t B, void* stream) {
+  return state_select_launch(table, reset, B, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_state_save(const MtrssmStateTable* table, int64_t B, int64_t steps, void* stream) {
+  return state_save_launch(table, B, steps, static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int mtrssm_conv_gather_gemm_pair(const MtrssmConvGeom* ga, const float* srca, const float* src2a, const float* wpa, const uint16_t* wqa,
                                             const float* biasa, const float* actgrada, const float* adda, float* outa,

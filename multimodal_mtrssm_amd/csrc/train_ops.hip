@@ -678,4 +678,163 @@ int episode_gather_launch(const float* store, const int64_t* idx, const float* n
   return check_launch("episode_gather");
 }
 
+// The same pair from a WINDOW of each episode: target[b, t, :] = store[idx[b], start[b] + t, :].  start[b] is read on the device
+// (a replayed graph takes new windows without a host round trip), so the launcher cannot range-check it: the kernel clamps it
+// into [0, Tfull - T] and the host validates the starts where it makes them (dataset.py).  A start shifts a row by whole frames
+// of E floats, E % 4 == 0: every access stays a 16-byte one.
+__global__ __launch_bounds__(kThreads) void episode_gather_window_kernel(
+    const float* __restrict__ store, const long* __restrict__ idx, const int* __restrict__ start, const float* __restrict__ noise,
+    long B, long T, long Tfull, long E4, float std_, float* __restrict__ input, float* __restrict__ target) {
+#pragma clang fp contract(off)  // (as episode_gather_kernel: mul then add, each rounded)
+  const long per_b = T * E4;
+  const long total = B * per_b;
+  const long last = Tfull - T;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long b = i / per_b, r = i - b * per_b;  // r = t * E4 + e4
+    long s = start[b];
+    s = s < 0 ? 0 : (s > last ? last : s);
+    const float4 x = reinterpret_cast<const float4*>(store)[(idx[b] * Tfull + s) * E4 + r];
+    if (target) reinterpret_cast<float4*>(target)[i] = x;
+    if (input) {
+      float4 y = x;
+      if (noise) {
+        const float4 n = reinterpret_cast<const float4*>(noise)[i];
+        const float px = n.x * std_, py = n.y * std_, pz = n.z * std_, pw = n.w * std_;
+        y.x = x.x + px;
+        y.y = x.y + py;
+        y.z = x.z + pz;
+        y.w = x.w + pw;
+      }
+      reinterpret_cast<float4*>(input)[i] = y;
+    }
+  }
+}
+
+int episode_gather_window_launch(const float* store, const int64_t* idx, const int32_t* start, const float* noise, int64_t n_episodes,
+                                 int64_t B, int64_t T, int64_t Tfull, int64_t E, float std_, float* input, float* target, hipStream_t s) {
+  if (!store || !idx || (!input && !target) || n_episodes <= 0 || B <= 0 || T <= 0 || Tfull < T || E <= 0) {
+    set_error("episode_gather_window: bad argument (need 0 < T <= Tfull, B, E > 0, an output)");
+    return MTRSSM_EINVAL;
+  }
+  if (!start) { set_error("episode_gather_window: start is null (mtrssm_episode_gather reads the first T frames)"); return MTRSSM_EINVAL; }
+  if (E % 4) { set_error("episode_gather_window: the event size %ld must be a multiple of 4 floats", (long)E); return MTRSSM_EINVAL; }
+  if (((uintptr_t)store | (uintptr_t)noise | (uintptr_t)input | (uintptr_t)target) & 15) {
+    set_error("episode_gather_window: buffers must be 16-byte aligned");
+    return MTRSSM_EINVAL;
+  }
+  if ((uintptr_t)start & 3) { set_error("episode_gather_window: start must be 4-byte aligned"); return MTRSSM_EINVAL; }
+  set_last_kernel("mtrssm::episode_gather_window_kernel");
+  hipLaunchKernelGGL(episode_gather_window_kernel, dim3(grid_for(B * T * E / 4)), dim3(kThreads), 0, s, store,
+                     reinterpret_cast<const long*>(idx), reinterpret_cast<const int*>(start), noise, (long)B, (long)T, (long)Tfull,
+                     (long)(E / 4), std_, input, target);
+  return check_launch("episode_gather_window");
+}
+
+// ------------------------------------------------------------------------------------------------
+// Carried state of truncated BPTT: up to MTRSSM_STATE_MAX row-major [B, width] tensors per launch, the
+// table of pointers passed by value.  For entry k and row b:
+//   dst[b, :] = (!reset || reset[b]) ? src[b * stride : +width] : (alt ? alt[b, :] : 0)
+// select: src = the fresh initial state (rows `stride` floats apart: init_proj's halves are column slices), alt = the carry;
+// its backward is the same launch with src = the incoming gradient and alt = null (a carried row passes no gradient on);
+// save: reset = null, src = the scan's [B, T, width] output at t = T - 1 (stride T * width), dst = the carry.
+// reset is read on the device: the launch sequence of a step is the same whether a row starts an episode or continues one.
+// blockIdx.y = entry; 16-byte accesses for an entry whose width, stride and pointers allow them, 4-byte ones otherwise.
+// ------------------------------------------------------------------------------------------------
+struct StateRows {
+  const float* src[MTRSSM_STATE_MAX];
+  const float* alt[MTRSSM_STATE_MAX];
+  float* dst[MTRSSM_STATE_MAX];
+  long stride[MTRSSM_STATE_MAX];
+  int width[MTRSSM_STATE_MAX];
+  int vec[MTRSSM_STATE_MAX];
+};
+
+__device__ __forceinline__ void state_rows(const StateRows& t, const unsigned char* __restrict__ reset, long B) {
+  const int k = blockIdx.y;
+  const float* __restrict__ src = t.src[k];
+  const float* __restrict__ alt = t.alt[k];
+  float* __restrict__ dst = t.dst[k];
+  const long stride = t.stride[k], w = t.width[k];
+  if (t.vec[k]) {
+    const long w4 = w / 4, total = B * w4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+      const long b = i / w4, q = i - b * w4;
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (!reset || reset[b]) v = reinterpret_cast<const float4*>(src + b * stride)[q];
+      else if (alt) v = reinterpret_cast<const float4*>(alt + b * w)[q];
+      reinterpret_cast<float4*>(dst + b * w)[q] = v;
+    }
+  } else {
+    const long total = B * w;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+      const long b = i / w, e = i - b * w;
+      float v = 0.f;
+      if (!reset || reset[b]) v = src[b * stride + e];
+      else if (alt) v = alt[b * w + e];
+      dst[b * w + e] = v;
+    }
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void state_select_kernel(const StateRows t, const unsigned char* __restrict__ reset, long B) {
+  state_rows(t, reset, B);
+}
+__global__ __launch_bounds__(kThreads) void state_save_kernel(const StateRows t, long B) { state_rows(t, nullptr, B); }
+
+// fills `rows` from the caller's table; `steps` > 0: the save form (src is [B, steps, width], read at t = steps - 1)
+static int state_rows_fill(const char* what, const MtrssmStateTable* table, int64_t B, int64_t steps, StateRows* rows, int* grid_x) {
+  if (!table || B <= 0) { set_error("%s: null table or B <= 0", what); return MTRSSM_EINVAL; }
+  if (table->count <= 0 || table->count > MTRSSM_STATE_MAX) {
+    set_error("%s: count %d outside 1 .. %d", what, (int)table->count, MTRSSM_STATE_MAX);
+    return MTRSSM_EINVAL;
+  }
+  int64_t most = 0;
+  for (int k = 0; k < MTRSSM_STATE_MAX; ++k) {
+    rows->src[k] = rows->alt[k] = nullptr;
+    rows->dst[k] = nullptr;
+    rows->stride[k] = 0;
+    rows->width[k] = rows->vec[k] = 0;
+  }
+  for (int k = 0; k < table->count; ++k) {
+    const int64_t w = table->width[k];
+    if (!table->src[k] || !table->dst[k] || w <= 0) { set_error("%s: entry %d has a null pointer or width <= 0", what, k); return MTRSSM_EINVAL; }
+    int64_t stride = steps > 0 ? steps * w : table->src_stride[k];
+    if (stride < w) { set_error("%s: entry %d has row stride %lld < width %lld", what, k, (long long)stride, (long long)w); return MTRSSM_EINVAL; }
+    if (B * w >= (int64_t)1 << 31) { set_error("%s: entry %d has %lld elements (< 2^31)", what, k, (long long)(B * w)); return MTRSSM_EINVAL; }
+    const float* src = steps > 0 ? table->src[k] + (steps - 1) * w : table->src[k];
+    const float* alt = steps > 0 ? nullptr : table->alt[k];
+    if (((uintptr_t)src | (uintptr_t)alt | (uintptr_t)table->dst[k]) & 3) { set_error("%s: entry %d is not 4-byte aligned", what, k); return MTRSSM_EINVAL; }
+    rows->src[k] = src;
+    rows->alt[k] = alt;
+    rows->dst[k] = table->dst[k];
+    rows->stride[k] = (long)stride;
+    rows->width[k] = (int)w;
+    rows->vec[k] = (w % 4 == 0 && stride % 4 == 0 && !(((uintptr_t)src | (uintptr_t)alt | (uintptr_t)table->dst[k]) & 15)) ? 1 : 0;
+    const int64_t items = rows->vec[k] ? B * (w / 4) : B * w;
+    most = items > most ? items : most;
+  }
+  *grid_x = grid_for(most) < 64 ? grid_for(most) : 64;
+  return MTRSSM_OK;
+}
+
+int state_select_launch(const MtrssmStateTable* table, const unsigned char* reset, int64_t B, hipStream_t s) {
+  StateRows rows;
+  int gx = 1;
+  if (!reset) { set_error("state_select: reset is null"); return MTRSSM_EINVAL; }
+  if (int rc = state_rows_fill("state_select", table, B, 0, &rows, &gx)) return rc;
+  set_last_kernel("mtrssm::state_select_kernel");
+  hipLaunchKernelGGL(state_select_kernel, dim3(gx, table->count), dim3(kThreads), 0, s, rows, reset, (long)B);
+  return check_launch("state_select");
+}
+
+int state_save_launch(const MtrssmStateTable* table, int64_t B, int64_t steps, hipStream_t s) {
+  StateRows rows;
+  int gx = 1;
+  if (steps <= 0) { set_error("state_save: steps must be positive (got %lld)", (long long)steps); return MTRSSM_EINVAL; }
+  if (int rc = state_rows_fill("state_save", table, B, steps, &rows, &gx)) return rc;
+  set_last_kernel("mtrssm::state_save_kernel");
+  hipLaunchKernelGGL(state_save_kernel, dim3(gx, table->count), dim3(kThreads), 0, s, rows, (long)B);
+  return check_launch("state_save");
+}
+
 }  // namespace mtrssm

@@ -11,6 +11,10 @@ written in the same pass).  Nothing touches the host per step.  Differences: fil
 ``torch.load(weights_only=True)`` (the reference unpickles); no Google-Drive download (``gdown``): missing data raises
 with the reference's hint; the noise comes from the device generator, so the random stream differs (not a parity goal:
 ``GaussianNoise`` is unseeded in the reference's workers too).
+
+Beyond the reference: the store keeps every episode at full length, and ``window="random"`` /
+``"sequential"`` train on windows ``[start, start + T)`` anywhere in it (``mtrssm_episode_gather_window``) -- the latter walks
+an episode chunk by chunk for truncated BPTT with a carried state (``carry.StateCarry``).
 """
 
 from __future__ import annotations
@@ -24,7 +28,9 @@ import torch
 from torch import Tensor
 
 from multimodal_mtrssm_amd import _lib
-from multimodal_mtrssm_amd.transform import Transform, fused_chain
+from multimodal_mtrssm_amd.transform import TakeFirstN, Transform, fused_chain
+
+WINDOWS = ("first", "random", "sequential")
 
 try:  # Lightning is optional (absent here): the module only needs prepare_data / setup / *_dataloader
     from lightning import LightningDataModule as _Base
@@ -83,6 +89,7 @@ class EpisodeDataModuleConfig:
     vision_observation_input_transform: Transform
     vision_observation_target_transform: Transform
     data_root: Path = Path("data")
+    window: str = "first"  # "first" | "random" | "sequential": which T frames of an episode a batch holds (DeviceEpisodeLoader)
 
     @property
     def data_dir(self) -> Path:
@@ -118,13 +125,33 @@ class _Stream:
         self.chains = (fused_chain(input_transform), fused_chain(target_transform))
         self.transforms = (input_transform, target_transform)
 
-    def batch(self, idx: Tensor, noise: Tensor | None) -> tuple[Tensor, Tensor]:
-        """``(input, target)`` for the episodes ``idx``; fused when both chains are the YAML's and E % 4 == 0."""
+    @property
+    def fused(self) -> bool:
+        cin, ctg = self.chains
+        return cin is not None and ctg is not None and cin[0] == ctg[0] and ctg[1] is None and self.event % 4 == 0
+
+    @property
+    def steps(self) -> int | None:
+        """T of a batch: what the input chain's leading ``TakeFirstN`` says (None: the chain has none)."""
+        t_full = int(self.store.shape[1])
+        if self.chains[0] is not None:
+            n = self.chains[0][0]
+            return t_full if n is None else min(int(n), t_full)
+        chain = getattr(self.transforms[0], "transforms", [self.transforms[0]])
+        n = next((int(t.n) for t in chain if isinstance(t, TakeFirstN)), None)
+        return None if n is None else min(n, t_full)
+
+    def batch(self, idx: Tensor, noise: Tensor | None, start: Tensor | None = None, start_host: list[int] | None = None) -> tuple[Tensor, Tensor]:
+        """``(input, target)`` for the episodes ``idx``; fused when both chains are the YAML's and E % 4 == 0.  ``start`` (int32
+        ``[B]`` on the device, ``start_host`` its host copy): the window ``[start, start + T)`` instead of the first T frames."""
         cin, ctg = self.chains
         n_ep, t_full = self.store.shape[:2]
-        fused = (cin is not None and ctg is not None and cin[0] == ctg[0] and ctg[1] is None and self.event % 4 == 0)
-        if not fused:  # arbitrary user transforms: applied per episode on the device tensors, then stacked
-            eps = [self.store[i] for i in idx.tolist()]
+        if not self.fused:  # arbitrary user transforms: applied per episode on the device tensors, then stacked
+            if start is None:
+                eps = [self.store[i] for i in idx.tolist()]
+            else:  # the transforms see the episode from its window's first frame on
+                starts = start.tolist() if start_host is None else start_host
+                eps = [self.store[i, s:] for i, s in zip(idx.tolist(), starts, strict=True)]
             return (torch.stack([self.transforms[0](e) for e in eps]), torch.stack([self.transforms[1](e) for e in eps]))
         t = t_full if cin[0] is None else min(int(cin[0]), t_full)
         b = idx.numel()
@@ -134,11 +161,49 @@ class _Stream:
         if std is not None and noise is None:
             noise = torch.randn(b, t, *self.event_shape, device=self.store.device, dtype=torch.float32)
         lib = _lib.load()
+        nbytes = 4.0 * b * t * self.event * (4 if std is not None else 3)
+        if start is None:
+            _lib.check(_lib.TIMERS.call(
+                "mtrssm_episode_gather", lib.mtrssm_episode_gather, _lib.ptr(self.store), _lib.raw_ptr(idx), _lib.ptr(noise if std is not None else None),
+                n_ep, b, t, t_full, self.event, float(std or 0.0), _lib.ptr(inp), _lib.ptr(tgt), _lib.stream_ptr(self.store.device),
+                nbytes=nbytes), "mtrssm_episode_gather")
+            return inp, tgt
+        if tuple(start.shape) != (b,):
+            msg = f"start must have shape ({b},), got {tuple(start.shape)}"
+            raise ValueError(msg)
         _lib.check(_lib.TIMERS.call(
-            "mtrssm_episode_gather", lib.mtrssm_episode_gather, _lib.ptr(self.store), _lib.raw_ptr(idx), _lib.ptr(noise if std is not None else None),
-            n_ep, b, t, t_full, self.event, float(std or 0.0), _lib.ptr(inp), _lib.ptr(tgt), _lib.stream_ptr(self.store.device),
-            nbytes=4.0 * b * t * self.event * (4 if std is not None else 3)), "mtrssm_episode_gather")
+            "mtrssm_episode_gather_window", lib.mtrssm_episode_gather_window, _lib.ptr(self.store), _lib.raw_ptr(idx), _lib.index_ptr(start),
+            _lib.ptr(noise if std is not None else None), n_ep, b, t, t_full, self.event, float(std or 0.0), _lib.ptr(inp), _lib.ptr(tgt),
+            _lib.stream_ptr(self.store.device), nbytes=nbytes), "mtrssm_episode_gather_window")
         return inp, tgt
+
+
+def gather_window_reference(store: Tensor, idx: Tensor, start: Tensor, T: int, noise: Tensor | None, std: float | None) -> tuple[Tensor, Tensor]:  # noqa: N803, PLR0913
+    """``mtrssm_episode_gather_window`` in torch: ``target[b, t] = store[idx[b], clamp(start[b]) + t]``, ``input = target + noise * std``
+    (mul, then add; ``input = target`` without noise).  ``store`` ``[N, T_full, *event]``; returns ``(input, target)``."""
+    t_full = store.shape[1]
+    s = start.to(torch.long).clamp(0, t_full - T)
+    frames = s.unsqueeze(1) + torch.arange(T, device=store.device)
+    target = store[idx.to(torch.long).unsqueeze(1), frames]
+    if noise is None or std is None:
+        return target.clone(), target
+    return target + noise * std, target
+
+
+class EpisodeBatch(tuple):
+    """The 6-tuple of a windowed batch (``len == 6``, indexing as ever) plus where its windows lie: ``start`` (int32 ``[B]``) and
+    ``reset`` (bool ``[B]``, True = the row starts an episode) on the device, ``start_host`` / ``reset_host`` their host copies (the
+    loader makes them on the host; ``StateCarry`` checks its rules on ``reset_host`` with no device read-back)."""
+
+    start: Tensor
+    reset: Tensor
+    start_host: Tensor | None  # (None when the caller handed `DeviceEpisodeLoader.batch` starts that live on the device)
+    reset_host: Tensor
+
+    def __new__(cls, items: tuple[Tensor, ...], start: Tensor, reset: Tensor, start_host: Tensor | None, reset_host: Tensor) -> EpisodeBatch:  # noqa: PYI034
+        self = super().__new__(cls, items)
+        self.start, self.reset, self.start_host, self.reset_host = start, reset, start_host, reset_host
+        return self
 
 
 class DeviceEpisodeLoader:
@@ -153,47 +218,104 @@ class DeviceEpisodeLoader:
     (the reference's DataLoader keeps it too)."""
 
     def __init__(self, streams: tuple[_Stream, _Stream, _Stream], batch_size: int, *, shuffle: bool, rank: int = 0, world: int = 1,  # noqa: PLR0913
-                 seed: int = 0) -> None:
+                 seed: int = 0, window: str = "first") -> None:
+        if window not in WINDOWS:
+            msg = f"window must be one of {WINDOWS}, got {window!r}"
+            raise ValueError(msg)
         self.streams = streams
         self.batch_size = int(batch_size)
         self.shuffle = shuffle
         self.rank, self.world = int(rank), int(world)
         self.seed, self.epoch = int(seed), 0
         self.n = int(streams[0].store.shape[0])
+        self.window = window
+        self.t_full = int(streams[0].store.shape[1])
+        self.steps = self.t_full
+        if window != "first":
+            steps = {s.steps for s in streams}
+            if len(steps) != 1 or None in steps:
+                msg = f"window={window!r} needs the same TakeFirstN(n) at the head of every input transform chain (found T = {sorted(map(str, steps))})"
+                raise ValueError(msg)
+            self.steps = int(steps.pop())
+        self.n_chunks = self.t_full // self.steps if window == "sequential" else 1
 
     def __len__(self) -> int:
-        return (self.n + self.batch_size - 1) // self.batch_size
+        return (self.n + self.batch_size - 1) // self.batch_size * self.n_chunks
 
     def set_epoch(self, epoch: int) -> None:
         self.epoch = int(epoch)
 
-    def batch(self, idx: Tensor, noise: tuple[Tensor | None, Tensor | None, Tensor | None] = (None, None, None)) -> tuple[Tensor, ...]:
-        """The 6-tuple for episode indices ``idx`` (int64, on the device); ``noise`` injects the standard normals."""
-        pairs = [s.batch(idx, n) for s, n in zip(self.streams, noise, strict=True)]
-        return (pairs[0][0], pairs[1][0], pairs[2][0], pairs[0][1], pairs[1][1], pairs[2][1])
-
-    def index_batches(self) -> Iterator[Tensor]:
-        """This rank's episode indices, batch by batch, for the current epoch (then the epoch counter advances)."""
+    def batch(self, idx: Tensor, noise: tuple[Tensor | None, Tensor | None, Tensor | None] = (None, None, None),
+              start: Tensor | None = None, reset: Tensor | None = None) -> tuple[Tensor, ...]:
+        """The 6-tuple for episode indices ``idx`` (int64, on the device); ``noise`` injects the standard normals.  ``start``: the
+        windows' first frames, one per row -- a HOST integer tensor (validated here: ``0 <= start <= T_full - T``) or an int32
+        device tensor (not read back: the kernel clamps it into that range); the result is then an ``EpisodeBatch``, ``reset``
+        (a host bool tensor, default all True) riding along."""
+        if start is None:
+            pairs = [s.batch(idx, n) for s, n in zip(self.streams, noise, strict=True)]
+            return (pairs[0][0], pairs[1][0], pairs[2][0], pairs[0][1], pairs[1][1], pairs[2][1])
         dev = self.streams[0].store.device
-        if self.shuffle:
-            g = torch.Generator().manual_seed(self.seed + self.epoch)
-            order = torch.randperm(self.n, generator=g).to(dev)
-        else:
-            order = torch.arange(self.n, device=dev)
+        start_host = None
+        if not start.is_cuda:
+            start_host = start.to(torch.int32)
+            if start_host.numel() and (int(start_host.min()) < 0 or int(start_host.max()) > self.t_full - self.steps):
+                msg = f"start must lie in [0, {self.t_full - self.steps}] (T_full = {self.t_full}, T = {self.steps}), got {start_host.tolist()}"
+                raise ValueError(msg)
+            start = start_host.to(dev)
+        reset_host = torch.ones(idx.numel(), dtype=torch.bool) if reset is None else reset.to("cpu", torch.bool)
+        hosts = None if start_host is None else start_host.tolist()
+        pairs = [s.batch(idx, n, start.contiguous(), hosts) for s, n in zip(self.streams, noise, strict=True)]
+        items = (pairs[0][0], pairs[1][0], pairs[2][0], pairs[0][1], pairs[1][1], pairs[2][1])
+        return EpisodeBatch(items, start, reset_host.to(dev), start_host, reset_host)
+
+    def _global_batches(self) -> Iterator[tuple[Tensor, Tensor | None]]:
+        """Per global batch of the current epoch: this rank's episode indices (on the device) and, for ``window="random"``, this rank's
+        window starts (host int32) -- both cut from per-GLOBAL-row quantities, so global row g is the same episode and window on
+        any number of ranks.  Advances the epoch counter."""
+        dev = self.streams[0].store.device
+        g = torch.Generator().manual_seed(self.seed + self.epoch)
+        order = torch.randperm(self.n, generator=g) if self.shuffle else torch.arange(self.n)
+        starts = None
+        if self.window == "random":  # one start per position of the epoch's order, drawn after the permutation
+            starts = torch.randint(0, self.t_full - self.steps + 1, (self.n,), generator=g).to(torch.int32)
+        order = order.to(dev)
         self.epoch += 1
         for lo in range(0, self.n, self.batch_size):
             rows = order[lo: lo + self.batch_size]
+            st = None if starts is None else starts[lo: lo + self.batch_size]
             if self.world > 1:
                 pad = (-rows.numel()) % self.world
                 if pad:
-                    rows = torch.cat([rows, order[torch.arange(pad, device=dev) % self.n]])
+                    wrap = torch.arange(pad) % self.n
+                    rows = torch.cat([rows, order[wrap.to(dev)]])
+                    st = None if st is None else torch.cat([st, starts[wrap]])
                 per = rows.numel() // self.world  # the CONTIGUOUS block FlatDataParallel.shard / GlobalRowNoise.draw give this rank
                 rows = rows[self.rank * per: (self.rank + 1) * per]
-            yield rows.contiguous()
+                st = None if st is None else st[self.rank * per: (self.rank + 1) * per]
+            yield rows.contiguous(), st
+
+    def schedule(self) -> Iterator[tuple[Tensor, Tensor | None, Tensor | None]]:
+        """``(episode indices, start, reset)`` of this rank, batch by batch, for the current epoch; ``start`` (int32) and ``reset``
+        (bool) are HOST tensors, None in ``"first"`` mode.  ``"sequential"``: a group of episodes comes ``n_chunks`` times in a row,
+        chunk c at ``start = c * T``, ``reset`` on chunk 0."""
+        for rows, st in self._global_batches():
+            b = rows.numel()
+            if self.window == "first":
+                yield rows, None, None
+            elif self.window == "random":
+                yield rows, st, torch.ones(b, dtype=torch.bool)
+            else:
+                for c in range(self.n_chunks):
+                    yield rows, torch.full((b,), c * self.steps, dtype=torch.int32), torch.full((b,), c == 0, dtype=torch.bool)
+
+    def index_batches(self) -> Iterator[Tensor]:
+        """This rank's episode indices, batch by batch, for the current epoch (then the epoch counter advances)."""
+        for rows, _, _ in self.schedule():
+            yield rows
 
     def __iter__(self) -> Iterator[tuple[Tensor, ...]]:
-        for rows in self.index_batches():
-            yield self.batch(rows)
+        for rows, start, reset in self.schedule():
+            yield self.batch(rows) if start is None else self.batch(rows, start=start, reset=reset)
 
 
 class EpisodeDataModule(_Base):
@@ -273,10 +395,12 @@ class EpisodeDataModule(_Base):
         if self.train_streams is None:
             msg = "train_dataset is not set. Call setup() first."
             raise RuntimeError(msg)
-        return DeviceEpisodeLoader(self.train_streams, self.config.batch_size, shuffle=True, rank=self.rank, world=self.world)
+        return DeviceEpisodeLoader(self.train_streams, self.config.batch_size, shuffle=True, rank=self.rank, world=self.world,
+                                   window=self.config.window)
 
     def val_dataloader(self) -> DeviceEpisodeLoader:
         if self.val_streams is None:
             msg = "val_dataset is not set. Call setup() first."
             raise RuntimeError(msg)
-        return DeviceEpisodeLoader(self.val_streams, self.config.batch_size, shuffle=False, rank=self.rank, world=self.world)
+        return DeviceEpisodeLoader(self.val_streams, self.config.batch_size, shuffle=False, rank=self.rank, world=self.world,
+                                   window=self.config.window)

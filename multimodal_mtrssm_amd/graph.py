@@ -24,6 +24,10 @@ Masked steps are captured in one of two modes, fixed for 
 * ``masked=True``: batches are 7-tuples; ``step`` validates the mask's t = 0 frame on the host and copies the mask into a fixed
   buffer, from which the captured region derives the scans' codes and the NLL's planes.
 
+``state_carry=`` adds truncated BPTT to any of the three: ``step`` checks the carry's host rules on the
+batch's ``reset_host`` and copies ``batch.reset`` into a fixed buffer; ``mtrssm_state_select`` and ``mtrssm_state_save`` are inside
+the graph and read ``reset`` on the device, so ONE graph serves the first chunk of an episode and every later one.
+
 Observations that are ``None`` stay eager-only: a capture cannot drop an encoder per step.
 
 With more than one rank the gradient all-reduce (RCCL) and the optimizer run eagerly after the replay: the
@@ -36,6 +40,7 @@ import torch
 from torch import Tensor
 
 from multimodal_mtrssm_amd import conv, scan
+from multimodal_mtrssm_amd.carry import StateCarry
 from multimodal_mtrssm_amd.core import _check_modality_mask
 from multimodal_mtrssm_amd.dropout import ModalityDropout, StepMask
 from multimodal_mtrssm_amd.optim import FlatAdamW, FlatParameters
@@ -61,11 +66,17 @@ class CapturedTrainStep:
     the pin on the conv layer's packed-weight plan.
 
     ``modality_dropout`` (a ``ModalityDropout``) or ``masked=True`` capture the masked step (module docstring); the graph then
-    takes only that kind of batch, an unmasked graph only 6-tuples."""
+    takes only that kind of batch, an unmasked graph only 6-tuples.
+
+    ``state_carry`` (a ``StateCarry`` of the batch's rows): the step continues its ``"train"`` set (module docstring).  The warm-up
+    steps reset every row and leave the carry as they found it; a carry that was empty is empty after construction."""
 
     def __init__(self, model: torch.nn.Module, flat: FlatParameters, opt: FlatAdamW, dp: FlatDataParallel,  # noqa: PLR0913
                  batch: tuple[Tensor, ...], noise: GlobalRowNoise, *, warmup: int = 3,
-                 modality_dropout: ModalityDropout | None = None, masked: bool = False) -> None:
+                 modality_dropout: ModalityDropout | None = None, masked: bool = False, state_carry: StateCarry | None = None) -> None:
+        if state_carry is not None and not isinstance(state_carry, StateCarry):
+            msg = f"state_carry must be a StateCarry, got {type(state_carry).__name__}"
+            raise ValueError(msg)
         if modality_dropout is not None and masked:
             msg = "give modality_dropout= (the graph samples its masks) or masked=True (the batches carry them), not both"
             raise ValueError(msg)
@@ -82,6 +93,11 @@ class CapturedTrainStep:
             _check_modality_mask(batch[6], b, t, dev, first_step=True)
             self.mask = batch[6].clone()
         self.batch = tuple(x.clone() for x in batch[:6])
+        self.carry = state_carry
+        self.reset: Tensor | None = None
+        if state_carry is not None:
+            state_carry.check("train", b, torch.ones(b, dtype=torch.bool))  # (the batch size; the warm-up resets every row)
+            self.reset = torch.ones(b, dtype=torch.bool, device=dev)
         self.shapes = dict(model.noise_shapes(b, t))
         if self.dropout is not None:
             self.dropout = self.dropout.for_rank(dp.world, dp.rank)
@@ -112,8 +128,12 @@ class CapturedTrainStep:
     # the captured region -------------------------------------------------------------------------
     def _body(self) -> list[str]:
         self.opt.zero_grad()
+        carry = None if self.carry is None else (self.carry, "train", self.reset)  # (its host rules were checked by step())
         if self.masked:  # (validated on the host by step(); codes, planes and counts are derived here, inside the capture)
-            out = self.model._elbo_step(self.batch, self.uniforms, StepMask.from_mask(self.mask))  # noqa: SLF001
+            out = self.model._elbo_step(self.batch, self.uniforms, StepMask.from_mask(self.mask), carry)  # noqa: SLF001
+        elif carry is not None:
+            sm = self.model._step_mask(self.batch, self.uniforms, None, self.dropout)  # noqa: SLF001
+            out = self.model._elbo_step(self.batch, self.uniforms, sm, carry)  # noqa: SLF001
         else:
             out = self.model.shared_step(self.batch, self.uniforms, modality_dropout=self.dropout)
         out["loss"].backward()
@@ -134,7 +154,7 @@ class CapturedTrainStep:
         dev = self.batch[0].device
         # the warm-up steps are real steps: snapshot what they change and restore it afterwards
         snap = (self.flat.param.clone(), self.opt.exp_avg.clone(), self.opt.exp_avg_sq.clone(), self.opt.state.clone(), self.opt.steps,
-                self.noise.gen.get_state())
+                self.noise.gen.get_state(), None if self.carry is None else self.carry.snapshot())
         side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -152,6 +172,8 @@ class CapturedTrainStep:
             self.opt.state.copy_(snap[3])
         self.opt.steps = snap[4]
         self.noise.gen.set_state(snap[5])
+        if self.carry is not None:  # the warm-up steps saved their last posterior: put the carry back (an empty one is empty again)
+            self.carry.restore(snap[6])
         conv.invalidate_packs()
         scan.STATUS.check()  # a warm-up step whose cooperative scan gave up must not be captured
         self.flat.check_views()
@@ -161,6 +183,8 @@ class CapturedTrainStep:
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
             self.keys = self._body()
+        if self.carry is not None:  # (the recorded, not executed, save marked the set filled on the host)
+            self.carry.filled = dict(snap[6][1])
         conv.reset_scratch()
         self._pinned = True
         self.graph = graph  # capture records, it does not execute: the first step() runs it
@@ -184,6 +208,13 @@ class CapturedTrainStep:
             self._check_batch_kind(batch)
             if self.masked:  # the t = 0 check reads the mask back: here, before the replay, never inside the capture
                 _check_modality_mask(batch[6], *self.batch[0].shape[:2], self.batch[0].device, first_step=True)
+        if self.carry is not None:  # host rules first: a partial reset into an empty carry raises before anything is replayed
+            reset = getattr(batch, "reset", None)
+            if reset is None:
+                msg = "this CapturedTrainStep carries state: step() needs an EpisodeBatch (its reset says which rows start an episode)"
+                raise ValueError(msg)
+            self.carry.check("train", reset.shape[0], getattr(batch, "reset_host", None))
+            self.reset.copy_(reset)
         if batch is not None and batch[0] is not self.batch[0]:
             for dst, src in zip(self.batch, batch[:6], strict=True):
                 dst.copy_(src)
@@ -193,6 +224,8 @@ class CapturedTrainStep:
         self.opt.sync_lr()
         assert self.graph is not None
         self.graph.replay()
+        if self.carry is not None:
+            self.carry.filled["train"] = True  # host mirror of the replayed save
         self._tail()
         self.opt.steps += 1 if self.fused_optimizer else 0  # host mirror of the device-side step count
         scan.STATUS.post()
