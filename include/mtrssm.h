@@ -506,6 +506,33 @@ int mtrssm_conv_weight_grad(const MtrssmConvGeom* g, const float* a, const float
 int mtrssm_conv_weight_grad_deferred(const MtrssmConvGeom* g, const float* a, const float* src, const float* src2,
                                      int32_t pre_act_a, float* dwp, float* dbias, void* workspace, int64_t workspace_bytes, void* stream);
 int mtrssm_conv_weight_grad_reduce(void* stream);
+/* mtrssm_conv_weight_grad of a TRANSPOSED layer (a = the layer input, src = its output gradient) that also accumulates the
+ * layer's bias gradient, the per-channel sums of src, in the same pass:
+ *   dsrc_bias[c] += sum_{n, y < Hs, x < Ws} src[n, c, y, x]
+ * -- the staged kernels of the three k = 4 / stride-2 transposed convolutions (csrc/conv_wgrad_resident.h) load every frame of
+ * src exactly once and add it up while they stage it; the sums travel with the workgroup's partial set and the reduce adds
+ * them to dsrc_bias (run-to-run deterministic; with workspace NULL or too small: fp32 atomics).  A separate
+ * mtrssm_channel_sum re-reads the whole output gradient.  defer != 0: the partial-set sum is recorded as by
+ * mtrssm_conv_weight_grad_deferred.  _supported: 1 when the kernel mtrssm_conv_weight_grad picks for (g, pre_act_a) is one of
+ * those three, else 0 -- a host-side query; mtrssm_conv_weight_grad_src_bias on another geometry returns MTRSSM_EINVAL (use
+ * mtrssm_conv_weight_grad + mtrssm_channel_sum there). */
+int mtrssm_conv_weight_grad_src_bias_supported(const MtrssmConvGeom* g, int32_t pre_act_a);
+/* The whole backward of a residual block's 1x1 layer (y = x + W1 act(h) + b1) in ONE pass over g_y and h:
+ *   gh[n, m, p]  = (sum_o W1[o][m] * gy[n, o, p]) * act'(h[n, m, p])          (written)
+ *   dwp[o][m]   += sum_{n, p} gy[n, o, p] * act(h[n, m, p])                    (as mtrssm_conv_weight_grad: partial sets + reduce)
+ *   dbias[o]    += sum_{n, p} gy[n, o, p]                                      (dbias may be NULL)
+ * g is the layer's geometry exactly as mtrssm_conv_weight_grad takes it (C = the 128 or 64 mid channels, Cout = 64, 64-pixel
+ * planes, KH = KW = 1, pre_act = 1, mfma_split = 2); wq1t the two bf16 pieces of W1 transposed, [2][C][64], as
+ * mtrssm_pack_conv_weight(s) packs the permuted view for the backward-data gather.  Same arithmetic, product order and partial
+ * sets as mtrssm_conv_gather_gemm (backward-data) followed by mtrssm_conv_weight_grad: gh, dwp and dbias come out bit-identical
+ * to theirs; both tensors are read once instead of twice.  workspace: mtrssm_conv_weight_grad_workspace_bytes(g, 0) bytes
+ * (NULL / too small: atomics); defer != 0 records the partial-set sum as mtrssm_conv_weight_grad_deferred does.  _supported:
+ * 1 / 0, a host-side query; mtrssm_residual_bwd1x1 on an unsupported shape returns MTRSSM_EINVAL. */
+int mtrssm_residual_bwd1x1_supported(const MtrssmConvGeom* g);
+int mtrssm_residual_bwd1x1(const MtrssmConvGeom* g, const float* gy, const float* h, const uint16_t* wq1t, float* gh, float* dwp,
+                           float* dbias, void* workspace, int64_t workspace_bytes, int32_t defer, void* stream);
+int mtrssm_conv_weight_grad_src_bias(const MtrssmConvGeom* g, const float* a, const float* src, int32_t pre_act_a, float* dwp,
+                                     float* dsrc_bias, void* workspace, int64_t workspace_bytes, int32_t defer, void* stream);
 /* Bytes of workspace the kernel chosen for this geometry wants for its partial tile sets (0: none; -1: invalid geometry; up to
  * ~38 MB for the reference's layer shapes at B*T = 3200 frames).  A host-side query, nothing is launched. */
 int64_t mtrssm_conv_weight_grad_workspace_bytes(const MtrssmConvGeom* g, int32_t pre_act_a);

@@ -582,10 +582,13 @@ def _wgrad_workspace(geom: C.Structure, pre_act_a: int, device: torch.device, *,
 
 def _weight_grad(a: Tensor, src: Tensor, coords: Tensor | None, kh: int, kw: int, stride: int, pad: int, pre_act_a: bool,  # noqa: PLR0913
                  pre_act_src: bool, act: int, *, want_bias: bool = False, weight: Tensor | None = None,
-                 bias: Tensor | None = None) -> tuple[Tensor | None, Tensor | None]:  # noqa: FBT001
+                 bias: Tensor | None = None, want_src_bias: bool = False) -> tuple[Tensor | None, Tensor | None]:  # noqa: FBT001
     """``dw[o][i][ky][kx] = sum preA(a)[n,o,y,x] * pre(src ++ coords)[n,i,y*s-p+ky,x*s-p+kx]`` -> ``[O][I][kh][kw]``.
 
     With ``want_bias`` (only when ``a`` is the raw output gradient) the same pass also returns ``sum_{n,y,x} a``.
+    With ``want_src_bias`` (a transposed layer: ``src`` is the raw output gradient, ``bias`` that layer's bias) it returns
+    ``sum_{n,y,x} src`` instead, from the kernels that have the sum built in (``mtrssm_conv_weight_grad_src_bias``); where the
+    geometry's kernel has not, the sum is a ``_channel_sum`` launch of its own.
     ``weight`` / ``bias``: the parameters themselves; when they live in a flat gradient buffer the gradients are accumulated
     there (``_ConvGradSink``; the bias directly by the kernel's atomics) and None is returned in their place."""
     lib = _lib.load()
@@ -595,24 +598,37 @@ def _weight_grad(a: Tensor, src: Tensor, coords: Tensor | None, kh: int, kw: int
     opad, ipad = _pads(o, c + c2)
     sunk = _GRAD_SINK.target(weight, o, c + c2, kh * kw, opad, ipad)
     dwp = sunk if sunk is not None else _zeros(opad * kh * kw * ipad, a.device).view(opad, kh * kw, ipad)
+    # (the fused kernels want 16-byte aligned operands; an odd view keeps the two-launch path)
+    fuse_src_bias = want_src_bias and CONVT_BIAS_FUSE and coords is None and a.data_ptr() % 16 == 0 and src.data_ptr() % 16 == 0
     dbias = bias_sunk = None
-    if want_bias:
+    if want_bias or fuse_src_bias:
         bias_sunk = grad_target(bias) if bias is not None and bias.is_contiguous() else None
-        dbias = bias_sunk if bias_sunk is not None else _zeros(o, a.device)
     geom = _geom(N=n, C=c, Hs=hs, Ws=ws, C2=c2, Cpad=ipad, KH=kh, KW=kw, SS=stride, TS=1, OFFY=-pad, OFFX=-pad, Hq=hq, Wq=wq,
                  OS=1, QY=0, QX=0, Ho=hq, Wo=wq, Cout=o, CoutPad=opad, pre_act=int(pre_act_src), act=act)
     flops = 2.0 * n * hq * wq * o * kh * kw * (c + c2)
     nbytes = 4.0 * (a.numel() + src.numel())
     # the sums of the partial sets wait for the end of the backward pass when both results go to the flat buffer (the sink's
     # flush runs them in one launch before it unpacks); a gradient handed back to autograd as a tensor is summed on the spot
-    defer = DEFER_WGRAD_REDUCE and sunk is not None and (not want_bias or bias_sunk is not None)
+    fuse_src_bias = fuse_src_bias and bool(lib.mtrssm_conv_weight_grad_src_bias_supported(C.byref(geom), int(pre_act_a)))
+    if want_bias or fuse_src_bias:
+        dbias = bias_sunk if bias_sunk is not None else _zeros(c if fuse_src_bias else o, a.device)
+    defer = DEFER_WGRAD_REDUCE and sunk is not None and (dbias is None or bias_sunk is not None)
     ws = _wgrad_workspace(geom, int(pre_act_a), a.device, own=defer)
+    if fuse_src_bias:
+        _lib.check(_lib.TIMERS.call(
+            "mtrssm_conv_weight_grad", lib.mtrssm_conv_weight_grad_src_bias, C.byref(geom), _lib.ptr(a), _lib.ptr(src), int(pre_act_a),
+            _lib.ptr(dwp), _lib.ptr(dbias), _lib.raw_ptr(ws), 0 if ws is None else ws.numel() * 4, int(defer and ws is not None),
+            _lib.stream_ptr(a.device), flops=flops, nbytes=nbytes), "mtrssm_conv_weight_grad_src_bias")
+        g_w = None if sunk is not None else dwp[:o, :, : c + c2].reshape(o, kh, kw, c + c2).permute(0, 3, 1, 2)
+        return g_w, (None if bias_sunk is not None else dbias)
     entry = lib.mtrssm_conv_weight_grad_deferred if defer and ws is not None else lib.mtrssm_conv_weight_grad
     _lib.check(_lib.TIMERS.call(
         "mtrssm_conv_weight_grad", entry, C.byref(geom), _lib.ptr(a), _lib.ptr(src), _lib.ptr(coords),
         int(pre_act_a), _lib.ptr(dwp), _lib.ptr(dbias), _lib.raw_ptr(ws), 0 if ws is None else ws.numel() * 4, _lib.stream_ptr(a.device),
         flops=flops, nbytes=nbytes), "mtrssm_conv_weight_grad")
     g_w = None if sunk is not None else dwp[:o, :, : c + c2].reshape(o, kh, kw, c + c2).permute(0, 3, 1, 2)
+    if want_src_bias:  # another kernel takes this geometry (the f32 mode, odd shapes): the sum is a pass of its own
+        return g_w, _channel_sum(src, bias)
     return g_w, (None if bias_sunk is not None else dbias)
 
 
@@ -685,14 +701,19 @@ class _ConvTranspose2d(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             # dX[n,ci,y,x] = sum_{co,ky,kx} w[ci][co][ky][kx] dOut[n,co,y*s-p+ky,x*s-p+kx]: a plain conv gather of dOut
             g_x = _conv_forward_gather(g_out, None, weight, None, stride, pad, False, act, actgrad_in=x if pre_act else None)
-        g_w = None
+        g_w = g_b = None
+        want_b = has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1]:
-            # dW[ci][co][ky][kx] = sum pre(x)[n,ci,y,x] dOut[n,co,y*s-p+ky,x*s-p+kx]
-            g_w, _ = _weight_grad(x, g_out, None, kh, kw, stride, pad, pre_act, False, act, weight=weight)
-        g_b = _channel_sum(g_out, ctx.bias) if has_bias and ctx.needs_input_grad[2] else None
+            # dW[ci][co][ky][kx] = sum pre(x)[n,ci,y,x] dOut[n,co,y*s-p+ky,x*s-p+kx]; the bias gradient (the channel sums of
+            # dOut) rides in the same pass where the layer's kernel streams dOut once anyway
+            g_w, g_b = _weight_grad(x, g_out, None, kh, kw, stride, pad, pre_act, False, act, weight=weight, bias=ctx.bias,
+                                    want_src_bias=want_b)
+        elif want_b:
+            g_b = _channel_sum(g_out, ctx.bias)
         return g_x, g_w, g_b, None, None, None, None, None
 
 
+CONVT_BIAS_FUSE = True  # ConvTranspose2d bias gradients inside the weight-gradient kernels (mtrssm_conv_weight_grad_src_bias)
 RESBLOCK_FUSE = True  # the blocks' forward as ONE launch where the library has a fused kernel (mtrssm_residual_block_fwd)
 
 
@@ -733,6 +754,46 @@ def _residual_launch(ja: tuple, jb: tuple | None) -> None:
                                 _lib.stream_ptr(ja[1].device), flops=fa + fb, nbytes=ba + bb), "mtrssm_residual_block_fwd")
 
 
+RESBLOCK_BWD1X1_FUSE = True  # the 1x1 layer's whole backward (g_h, dW1, db1) as ONE launch where the library has it (mtrssm_residual_bwd1x1)
+
+
+def _bwd1x1_geom(g_y: Tensor, h: Tensor, w1: Tensor, act: int) -> C.Structure | None:
+    """The 1x1 layer's weight-gradient geometry when ``mtrssm_residual_bwd1x1`` takes the block, else None."""
+    if not RESBLOCK_BWD1X1_FUSE or _MFMA_SPLIT != 2 or w1.shape[2:] != (1, 1) or not g_y.is_cuda:  # noqa: PLR2004
+        return None
+    n, o, hq, wq = g_y.shape
+    c = h.shape[1]
+    if w1.shape[:2] != (o, c) or h.shape != (n, c, hq, wq) or g_y.data_ptr() % 16 or h.data_ptr() % 16:
+        return None
+    opad, ipad = _pads(o, c)
+    geom = _geom(N=n, C=c, Hs=hq, Ws=wq, C2=0, Cpad=ipad, KH=1, KW=1, SS=1, TS=1, OFFY=0, OFFX=0, Hq=hq, Wq=wq, OS=1, QY=0, QX=0,
+                 Ho=hq, Wo=wq, Cout=o, CoutPad=opad, pre_act=1, act=act)
+    return geom if _lib.load().mtrssm_residual_bwd1x1_supported(C.byref(geom)) else None
+
+
+def _bwd1x1_fused(geom: C.Structure, g_y: Tensor, h: Tensor, w1: Tensor, b1: Tensor) -> tuple[Tensor, Tensor | None, Tensor | None]:
+    """``(g_h, g_w1, g_b1)`` of ``y = x + W1 act(h) + b1`` from one pass over ``g_y`` and ``h``; the gradients as ``_weight_grad``
+    returns them (None where they went to the flat gradient buffer)."""
+    lib = _lib.load()
+    n, o, hq, wq = g_y.shape
+    c = h.shape[1]
+    _, wq1t = pack_weight(w1.permute(1, 0, 2, 3))  # [c][o][1][1]: the backward-data gather's view, one entry of the step's pack plan
+    sunk = _GRAD_SINK.target(w1, o, c, 1, geom.CoutPad, geom.Cpad)
+    dwp = sunk if sunk is not None else _zeros(geom.CoutPad * geom.Cpad, g_y.device).view(geom.CoutPad, 1, geom.Cpad)
+    bias_sunk = grad_target(b1) if b1.is_contiguous() else None
+    dbias = bias_sunk if bias_sunk is not None else _zeros(o, g_y.device)
+    defer = DEFER_WGRAD_REDUCE and sunk is not None and bias_sunk is not None
+    ws = _wgrad_workspace(geom, 0, g_y.device, own=defer)
+    g_h = torch.empty_like(h)
+    pixels = n * hq * wq
+    _lib.check(_lib.TIMERS.call(
+        "mtrssm_residual_bwd1x1", lib.mtrssm_residual_bwd1x1, C.byref(geom), _lib.ptr(g_y), _lib.ptr(h), _lib.raw_ptr(wq1t), _lib.ptr(g_h),
+        _lib.ptr(dwp), _lib.ptr(dbias), _lib.raw_ptr(ws), 0 if ws is None else ws.numel() * 4, int(defer and ws is not None),
+        _lib.stream_ptr(g_y.device), flops=2.0 * 2.0 * pixels * o * c, nbytes=4.0 * (g_y.numel() + 2 * h.numel())), "mtrssm_residual_bwd1x1")
+    g_w = None if sunk is not None else dwp[:o, :, :c].reshape(o, 1, 1, c).permute(0, 3, 1, 2)
+    return g_h, g_w, (None if bias_sunk is not None else dbias)
+
+
 class _ResidualBlock(torch.autograd.Function):
     """``y = x + Conv1x1(act(Conv3x3(act(x))))`` as ONE node: the skip add rides in the second conv's epilogue and the
     skip's gradient in the epilogue of the first conv's backward-data (``oracle/ref_cnn.py:ResidualBlock``)."""
@@ -758,9 +819,13 @@ class _ResidualBlock(torch.autograd.Function):
         act = ctx.act
         g_y = g_y.contiguous()
         p3, p1 = w3.shape[2] // 2, w1.shape[2] // 2
-        g_h = _conv_transposed_gather(g_y, w1, None, 1, p1, (h.shape[2], h.shape[3]), False, act, actgrad_in=h)
         b3, b1 = ctx.biases
-        g_w1, g_b1 = _weight_grad(g_y, h, None, w1.shape[2], w1.shape[3], 1, p1, False, True, act, want_bias=True, weight=w1, bias=b1)
+        g1 = _bwd1x1_geom(g_y, h, w1, act)
+        if g1 is not None:
+            g_h, g_w1, g_b1 = _bwd1x1_fused(g1, g_y, h, w1, b1)
+        else:
+            g_h = _conv_transposed_gather(g_y, w1, None, 1, p1, (h.shape[2], h.shape[3]), False, act, actgrad_in=h)
+            g_w1, g_b1 = _weight_grad(g_y, h, None, w1.shape[2], w1.shape[3], 1, p1, False, True, act, want_bias=True, weight=w1, bias=b1)
         g_x = None
         if ctx.needs_input_grad[0]:
             g_x = _conv_transposed_gather(g_h, w3, None, 1, p3, (x.shape[2], x.shape[3]), False, act, actgrad_in=x, add_in=g_y)
@@ -796,11 +861,18 @@ class _PairResidualBlock(torch.autograd.Function):
         act = ctx.act
         g_ya, g_yv = g_ya.contiguous(), g_yv.contiguous()
         p3, p1 = w3a.shape[2] // 2, w1a.shape[2] // 2
-        g_ha, g_hv = paired(lambda: _conv_transposed_gather(g_ya, w1a, None, 1, p1, (ha.shape[2], ha.shape[3]), False, act, actgrad_in=ha),
-                            lambda: _conv_transposed_gather(g_yv, w1v, None, 1, p1, (hv.shape[2], hv.shape[3]), False, act, actgrad_in=hv))
         b3a, b1a, b3v, b1v = ctx.biases
-        g_w1a, g_b1a = _weight_grad(g_ya, ha, None, w1a.shape[2], w1a.shape[3], 1, p1, False, True, act, want_bias=True, weight=w1a, bias=b1a)
-        g_w1v, g_b1v = _weight_grad(g_yv, hv, None, w1v.shape[2], w1v.shape[3], 1, p1, False, True, act, want_bias=True, weight=w1v, bias=b1v)
+        g1a = _bwd1x1_geom(g_ya, ha, w1a, act)
+        g1v = _bwd1x1_geom(g_yv, hv, w1v, act) if g1a is not None else None
+        if g1a is not None and g1v is not None:
+            # one launch per modality: each is a persistent grid over all CUs (as the weight gradients it replaces)
+            g_ha, g_w1a, g_b1a = _bwd1x1_fused(g1a, g_ya, ha, w1a, b1a)
+            g_hv, g_w1v, g_b1v = _bwd1x1_fused(g1v, g_yv, hv, w1v, b1v)
+        else:
+            g_ha, g_hv = paired(lambda: _conv_transposed_gather(g_ya, w1a, None, 1, p1, (ha.shape[2], ha.shape[3]), False, act, actgrad_in=ha),
+                                lambda: _conv_transposed_gather(g_yv, w1v, None, 1, p1, (hv.shape[2], hv.shape[3]), False, act, actgrad_in=hv))
+            g_w1a, g_b1a = _weight_grad(g_ya, ha, None, w1a.shape[2], w1a.shape[3], 1, p1, False, True, act, want_bias=True, weight=w1a, bias=b1a)
+            g_w1v, g_b1v = _weight_grad(g_yv, hv, None, w1v.shape[2], w1v.shape[3], 1, p1, False, True, act, want_bias=True, weight=w1v, bias=b1v)
         g_xa, g_xv = paired(
             lambda: _conv_transposed_gather(g_ha, w3a, None, 1, p3, (xa.shape[2], xa.shape[3]), False, act, actgrad_in=xa, add_in=g_ya),
             lambda: _conv_transposed_gather(g_hv, w3v, None, 1, p3, (xv.shape[2], xv.shape[3]), False, act, actgrad_in=xv, add_in=g_yv))

@@ -39,6 +39,11 @@ int conv_gather_pair_merges(const MtrssmConvGeom*, const MtrssmConvGeom*, bool);
 int conv_weight_grad_launch(const MtrssmConvGeom*, const float*, const float*, const float*, int, float*, float*, void*, size_t, size_t*, hipStream_t);
 int conv_weight_grad_deferred_launch(const MtrssmConvGeom*, const float*, const float*, const float*, int, float*, float*, void*, size_t, hipStream_t);
 int conv_weight_grad_reduce_flush(hipStream_t);
+int conv_residual_bwd1x1_supported(const MtrssmConvGeom*);
+int conv_residual_bwd1x1_launch(const MtrssmConvGeom*, const float*, const float*, const unsigned short*, float*, float*, float*, void*, size_t, int,
+                                hipStream_t);
+int conv_weight_grad_src_bias_supported(const MtrssmConvGeom*, int);
+int conv_weight_grad_src_bias_launch(const MtrssmConvGeom*, const float*, const float*, int, float*, float*, void*, size_t, int, hipStream_t);
 int channel_sum_launch(const float*, int, int, int, float*, hipStream_t);
 int convt_k4s2_band_supported(int, int, int, int, int);
 int convt_k4s2_band_launch(int, int, int, int, int, const float*, const float*, const float*, int, int, float*, hipStream_t);
@@ -280,6 +285,20 @@ MTRSSM_API int mtrssm_conv_weight_grad_deferred(const MtrssmConvGeom* g, const f
                                                float* dwp, float* dbias, void* workspace, int64_t workspace_bytes, void* stream) {
   return conv_weight_grad_deferred_launch(g, a, src, src2, pre_act_a, dwp, dbias, workspace, workspace_bytes < 0 ? 0 : (size_t)workspace_bytes,
                                           static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_residual_bwd1x1_supported(const MtrssmConvGeom* g) { return conv_residual_bwd1x1_supported(g) != 0; }
+MTRSSM_API int mtrssm_residual_bwd1x1(const MtrssmConvGeom* g, const float* gy, const float* h, const uint16_t* wq1t, float* gh, float* dwp,
+                                      float* dbias, void* workspace, int64_t workspace_bytes, int32_t defer, void* stream) {
+  return conv_residual_bwd1x1_launch(g, gy, h, wq1t, gh, dwp, dbias, workspace, workspace_bytes < 0 ? 0 : (size_t)workspace_bytes, defer,
+                                     static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_conv_weight_grad_src_bias_supported(const MtrssmConvGeom* g, int32_t pre_act_a) {
+  return conv_weight_grad_src_bias_supported(g, pre_act_a);
+}
+MTRSSM_API int mtrssm_conv_weight_grad_src_bias(const MtrssmConvGeom* g, const float* a, const float* src, int32_t pre_act_a, float* dwp,
+                                                float* dsrc_bias, void* workspace, int64_t workspace_bytes, int32_t defer, void* stream) {
+  return conv_weight_grad_src_bias_launch(g, a, src, pre_act_a, dwp, dsrc_bias, workspace, workspace_bytes < 0 ? 0 : (size_t)workspace_bytes,
+                                          defer, static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int mtrssm_conv_weight_grad_reduce(void* stream) { return conv_weight_grad_reduce_flush(static_cast<hipStream_t>(stream)); }
 MTRSSM_API int64_t mtrssm_conv_weight_grad_workspace_bytes(const MtrssmConvGeom* g, int32_t pre_act_a) {

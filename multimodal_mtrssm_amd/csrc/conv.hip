@@ -689,10 +689,10 @@ __device__ __forceinline__ void wgrad_reduce_dispatch(const ReduceJob& j, int bx
     case kRed1x1_64: wgrad_reduce_partials1x1_body<64>(j.part, j.S, j.cpad, j.dwp, j.dbias, bx, by); break;
     case kRed1x1_128: wgrad_reduce_partials1x1_body<128>(j.part, j.S, j.cpad, j.dwp, j.dbias, bx, by); break;
     case kRedThin: wgrad_reduce_partials_thin_body(j.part, j.S, j.cpad, j.dwp, j.dbias, bx, by); break;
-    case kRedThinT: wgrad_reduce_partials_thint_body(j.part, j.S, j.cpad, j.dwp, bx, by); break;
+    case kRedThinT: wgrad_reduce_partials_thint_body(j.part, j.S, j.cpad, j.dwp, j.dbias, bx, by); break;
     case kRedS2: wgrad_reduce_partials_s2_body(j.part, j.S, j.cpad, j.dwp, j.dbias, bx, by); break;
-    case kRedT4: wgrad_reduce_partials_t4_body(j.part, j.S, j.cpad, j.dwp, bx, by); break;
-    case kRedT4b: wgrad_reduce_partials_t4b_body(j.part, j.S, j.cpad, j.dwp, bx, by); break;
+    case kRedT4: wgrad_reduce_partials_t4_body(j.part, j.S, j.cpad, j.dwp, j.dbias, bx, by); break;
+    case kRedT4b: wgrad_reduce_partials_t4b_body(j.part, j.S, j.cpad, j.dwp, j.dbias, bx, by); break;
     default: wgrad_reduce_partials_s2c_body(j.part, j.S, j.cpad, j.dwp, j.dbias, bx, by); break;
   }
 }
@@ -1946,6 +1946,44 @@ static bool no_direct_wgrad() {
 // the kernels without partial sets) and return WITHOUT launching anything.
 int conv_weight_grad_launch(const MtrssmConvGeom* g, const float* a, const float* src, const float* src2, int pre_act_a,
                             float* dwp, float* dbias, void* workspace, size_t workspace_bytes, size_t* query, hipStream_t stream);
+// Bias gradient of a transposed layer = the per-channel sums of `src` (there the output gradient): the three staged k = 4 /
+// stride-2 kernels add them up while they stage src (conv_wgrad_resident.h).  A branch of conv_weight_grad_launch_ex that
+// carries the sums sets `fused` and adds them to `target` (NULL: a probe); every other branch leaves `fused` alone, and the
+// caller below refuses the call BEFORE anything is launched, so no branch can drop the sums silently.
+struct WgradSrcBias {
+  float* target = nullptr;
+  bool fused = false;
+};
+int conv_weight_grad_launch_ex(const MtrssmConvGeom* g, const float* a, const float* src, const float* src2, int pre_act_a, float* dwp,
+                               float* dbias, void* workspace, size_t workspace_bytes, size_t* query, WgradSrcBias* sb, hipStream_t stream);
+int conv_weight_grad_launch(const MtrssmConvGeom* g, const float* a, const float* src, const float* src2, int pre_act_a,
+                            float* dwp, float* dbias, void* workspace, size_t workspace_bytes, size_t* query, hipStream_t stream) {
+  return conv_weight_grad_launch_ex(g, a, src, src2, pre_act_a, dwp, dbias, workspace, workspace_bytes, query, nullptr, stream);
+}
+int conv_weight_grad_src_bias_supported(const MtrssmConvGeom* g, int pre_act_a) {
+  WgradSrcBias sb;
+  size_t need = 0;
+  const int rc = conv_weight_grad_launch_ex(g, nullptr, nullptr, nullptr, pre_act_a, nullptr, nullptr, nullptr, 0, &need, &sb, nullptr);
+  return rc == MTRSSM_OK && sb.fused;
+}
+int conv_weight_grad_src_bias_launch(const MtrssmConvGeom* g, const float* a, const float* src, int pre_act_a, float* dwp,
+                                     float* dsrcbias, void* workspace, size_t workspace_bytes, int defer, hipStream_t stream) {
+  if (!dsrcbias) { set_error("conv_weight_grad_src_bias: null dsrc_bias"); return MTRSSM_EINVAL; }
+  if (((uintptr_t)a & 15) || ((uintptr_t)src & 15)) {  // the staged kernels' own condition: nothing else may take this call
+    set_error("conv_weight_grad_src_bias: a and src must be 16-byte aligned");
+    return MTRSSM_EINVAL;
+  }
+  if (!conv_weight_grad_src_bias_supported(g, pre_act_a)) {
+    set_error("conv_weight_grad_src_bias: this geometry's kernel has no fused source sums (query mtrssm_conv_weight_grad_src_bias_supported first)");
+    return MTRSSM_EINVAL;
+  }
+  WgradSrcBias sb;
+  sb.target = dsrcbias;
+  tl_defer_reduce = defer != 0;
+  const int rc = conv_weight_grad_launch_ex(g, a, src, nullptr, pre_act_a, dwp, nullptr, workspace, workspace_bytes, nullptr, &sb, stream);
+  tl_defer_reduce = false;
+  return rc;
+}
 // the same launch with its partial-set reduction recorded for conv_weight_grad_reduce_flush (the workspace must stay untouched
 // until then)
 int conv_weight_grad_deferred_launch(const MtrssmConvGeom* g, const float* a, const float* src, const float* src2, int pre_act_a,
@@ -1956,8 +1994,60 @@ int conv_weight_grad_deferred_launch(const MtrssmConvGeom* g, const float* a, co
   return rc;
 }
 
-int conv_weight_grad_launch(const MtrssmConvGeom* g, const float* a, const float* src, const float* src2, int pre_act_a,
-                            float* dwp, float* dbias, void* workspace, size_t workspace_bytes, size_t* query, hipStream_t stream) {
+// ---- whole backward of a residual block's 1x1 layer in one pass (conv_wgrad_resident.h: conv1x1_bwd_fused_kernel) ----
+// MTRSSM_BWD1X1_FUSED=0: refuse every shape (A/B runs of the two-launch path through the same Python code)
+int conv_residual_bwd1x1_supported(const MtrssmConvGeom* g) {
+  static const bool on = [] { const char* e = getenv("MTRSSM_BWD1X1_FUSED"); return !(e && e[0] == '0'); }();
+  if (!g || !on || !wgrad_1x1_staged_enabled()) return 0;
+  return g->mfma_split == 2 && g->KH == 1 && g->KW == 1 && g->SS == 1 && g->OFFY == 0 && g->OFFX == 0 && g->C2 == 0 && g->Hs == g->Hq &&
+         g->Ws == g->Wq && g->Hq * g->Wq == 64 && (g->C == 64 || g->C == 128) && g->Cout == 64 && g->Cpad >= g->C && g->N >= 1 &&
+         g->OS == 1 && g->QY == 0 && g->QX == 0 && g->pre_act != 0 &&
+         (g->act == MTRSSM_ACT_IDENTITY || g->act == MTRSSM_ACT_ELU || g->act == MTRSSM_ACT_RELU);
+}
+int conv_residual_bwd1x1_launch(const MtrssmConvGeom* g, const float* gy, const float* h, const unsigned short* wq1t, float* gh, float* dwp,
+                                float* dbias, void* workspace, size_t workspace_bytes, int defer, hipStream_t stream) {
+  if (!conv_residual_bwd1x1_supported(g)) {
+    set_error("residual_bwd1x1: shape without a fused kernel (query mtrssm_residual_bwd1x1_supported first)");
+    return MTRSSM_EINVAL;
+  }
+  if (!gy || !h || !wq1t || !gh || !dwp) { set_error("residual_bwd1x1: null pointer"); return MTRSSM_EINVAL; }
+  if (((uintptr_t)gy & 15) || ((uintptr_t)h & 15) || ((uintptr_t)wq1t & 15) || ((uintptr_t)gh & 3) || ((uintptr_t)workspace & 255)) {
+    set_error("residual_bwd1x1: g_y, h and the weight pieces must be 16-byte aligned, the workspace 256-byte aligned");
+    return MTRSSM_EINVAL;
+  }
+  int wgs = cu_count();  // the grid of conv1x1_wgrad_staged_kernel: mtrssm_conv_weight_grad_workspace_bytes sizes the workspace
+  if (wgs > g->N) wgs = g->N;
+  const int per = (g->N + wgs - 1) / wgs;
+  const dim3 grid((unsigned)((g->N + per - 1) / per));
+  float* part = nullptr;
+  if (wgrad_partials_enabled() && workspace && workspace_bytes >= (size_t)grid.x * kWg1x1SetFloats * sizeof(float)) part = static_cast<float*>(workspace);
+#define MTRSSM_BW1_LAUNCH(C_)                                                                                                   \
+  {                                                                                                                             \
+    static bool attr_done_dev[64] = {}; bool& attr_done = attr_done_dev[device_slot()];                                         \
+    constexpr int lds_b = bwd1x1_lds_bytes<C_>();                                                                               \
+    if (!attr_done) {                                                                                                           \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_bwd_fused_kernel<C_>),                                    \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_b);                                             \
+      attr_done = true;                                                                                                         \
+    }                                                                                                                           \
+    set_last_kernel("mtrssm::conv1x1_bwd_fused_kernel<" #C_ ">");                                                               \
+    hipLaunchKernelGGL((conv1x1_bwd_fused_kernel<C_>), grid, dim3(512), lds_b, stream, *g, gy, h, wq1t, gh, dwp, part, dbias,   \
+                       per);                                                                                                    \
+  }
+  if (g->C == 64) MTRSSM_BW1_LAUNCH(64) else MTRSSM_BW1_LAUNCH(128)
+#undef MTRSSM_BW1_LAUNCH
+  if (part) {
+    const dim3 rgrid((unsigned)(2 * (g->C / 32) * 256 / 32 + (dbias ? 1 : 0)), 1);  // + the bias block
+    tl_defer_reduce = defer != 0;
+    const int rc = reduce_now_or_later(g->C == 64 ? kRed1x1_64 : kRed1x1_128, rgrid, part, (int)grid.x, g->Cpad, dwp, dbias, stream);
+    tl_defer_reduce = false;
+    if (rc) return rc;
+  }
+  return launched("residual_bwd1x1");
+}
+
+int conv_weight_grad_launch_ex(const MtrssmConvGeom* g, const float* a, const float* src, const float* src2, int pre_act_a, float* dwp,
+                               float* dbias, void* workspace, size_t workspace_bytes, size_t* query, WgradSrcBias* sb, hipStream_t stream) {
   if (int rc = check_geom(g, "conv_weight_grad")) return rc;
   if (!query && (!a || !src || !dwp || (g->C2 > 0 && !src2))) { set_error("conv_weight_grad: null pointer"); return MTRSSM_EINVAL; }
   if (workspace && ((uintptr_t)workspace & 255)) { set_error("conv_weight_grad: workspace must be 256-byte aligned"); return MTRSSM_EINVAL; }
@@ -2128,6 +2218,8 @@ int conv_weight_grad_launch(const MtrssmConvGeom* g, const float* a, const float
     if (wgs > g->N) wgs = g->N;
     const int per = (g->N + wgs - 1) / wgs;
     const dim3 grid((unsigned)((g->N + per - 1) / per));
+    if (sb) sb->fused = true;
+    float* const dsrcbias = sb ? sb->target : nullptr;
     MTRSSM_WGRAD_PART((size_t)grid.x * kWgThinTSetFloats * sizeof(float))
 #define MTRSSM_WGTHINT_LAUNCH(SP_, W_)                                                                                           \
   {                                                                                                                             \
@@ -2140,14 +2232,14 @@ int conv_weight_grad_launch(const MtrssmConvGeom* g, const float* a, const float
     }                                                                                                                           \
     set_last_kernel("mtrssm::convt4s2_thin_wgrad_staged_kernel<" #SP_ ", " #W_ ">");                                             \
     hipLaunchKernelGGL((convt4s2_thin_wgrad_staged_kernel<SP_, W_>), grid, dim3(512), lds_b, stream, *g, a, src, pre_act_a, dwp, \
-                       part, per);                                                                                              \
+                       part, dsrcbias, per);                                                                                    \
   }
     const int sp = g->mfma_split;
     if (g->Wq == 32) { if (sp == 2) MTRSSM_WGTHINT_LAUNCH(2, 32) else MTRSSM_WGTHINT_LAUNCH(1, 32) }
     else { if (sp == 2) MTRSSM_WGTHINT_LAUNCH(2, 16) else MTRSSM_WGTHINT_LAUNCH(1, 16) }
 #undef MTRSSM_WGTHINT_LAUNCH
     if (part)
-      if (int rc = reduce_now_or_later(kRedThinT, dim3(16), part, (int)grid.x, g->Cpad, dwp, nullptr, stream)) return rc;
+      if (int rc = reduce_now_or_later(kRedThinT, dim3(dsrcbias ? 17 : 16), part, (int)grid.x, g->Cpad, dwp, dsrcbias, stream)) return rc;
     return launched("conv_weight_grad(k4 s2 thin staged)");
   }
   if (g->mfma_split >= 1 && g->Cout <= 32 && taps * ctot <= 32 && g->Wq >= 8 && (g->Wq & (g->Wq - 1)) == 0 && (g->Hq * g->Wq) % 16 == 0 &&
@@ -2209,6 +2301,8 @@ int conv_weight_grad_launch(const MtrssmConvGeom* g, const float* a, const float
     if (wgs > g->N) wgs = g->N;
     const int per = (g->N + wgs - 1) / wgs;
     const dim3 grid((unsigned)((g->N + per - 1) / per));
+    if (sb) sb->fused = true;
+    float* const dsrcbias = sb ? sb->target : nullptr;
     MTRSSM_WGRAD_PART((size_t)grid.x * kWgT4SetFloats * sizeof(float))
 #define MTRSSM_WGT4_LAUNCH(SP_, W_)                                                                                              \
   {                                                                                                                             \
@@ -2221,14 +2315,14 @@ int conv_weight_grad_launch(const MtrssmConvGeom* g, const float* a, const float
     }                                                                                                                           \
     set_last_kernel("mtrssm::convt4s2_wgrad_staged_kernel<" #SP_ ", " #W_ ">");                                                  \
     hipLaunchKernelGGL((convt4s2_wgrad_staged_kernel<SP_, W_>), grid, dim3(512), lds_b, stream, *g, a, src, pre_act_a, dwp,      \
-                       part, per);                                                                                              \
+                       part, dsrcbias, per);                                                                                    \
   }
     const int sp = g->mfma_split;
     if (g->Wq == 16) { if (sp == 2) MTRSSM_WGT4_LAUNCH(2, 16) else MTRSSM_WGT4_LAUNCH(1, 16) }
     else { if (sp == 2) MTRSSM_WGT4_LAUNCH(2, 8) else MTRSSM_WGT4_LAUNCH(1, 8) }
 #undef MTRSSM_WGT4_LAUNCH
     if (part)
-      if (int rc = reduce_now_or_later(kRedT4, dim3(kWgT4SetFloats / 4 / 8), part, (int)grid.x, g->Cpad, dwp, nullptr, stream)) return rc;
+      if (int rc = reduce_now_or_later(kRedT4, dim3(kWgT4TileFloats / 4 / 8 + (dsrcbias ? 1 : 0)), part, (int)grid.x, g->Cpad, dwp, dsrcbias, stream)) return rc;
     return launched("conv_weight_grad(k4 s2 staged)");
   }
   if ((g->mfma_split == 1 || g->mfma_split == 2) && g->KH == 4 && g->KW == 4 && g->SS == 2 && g->TS == 1 && g->OFFY == -1 && g->OFFX == -1 &&
@@ -2240,6 +2334,8 @@ int conv_weight_grad_launch(const MtrssmConvGeom* g, const float* a, const float
     if (wgs > g->N) wgs = g->N;
     const int per = (g->N + wgs - 1) / wgs;
     const dim3 grid((unsigned)((g->N + per - 1) / per));
+    if (sb) sb->fused = true;
+    float* const dsrcbias = sb ? sb->target : nullptr;
     MTRSSM_WGRAD_PART((size_t)grid.x * kWgT4bSetFloats * sizeof(float))
 #define MTRSSM_WGT4B_LAUNCH(SP_, W_)                                                                                             \
   {                                                                                                                             \
@@ -2252,14 +2348,14 @@ int conv_weight_grad_launch(const MtrssmConvGeom* g, const float* a, const float
     }                                                                                                                           \
     set_last_kernel("mtrssm::convt4s2b_wgrad_staged_kernel<" #SP_ ", " #W_ ">");                                                 \
     hipLaunchKernelGGL((convt4s2b_wgrad_staged_kernel<SP_, W_>), grid, dim3(512), lds_b, stream, *g, a, src, pre_act_a, dwp,     \
-                       part, per);                                                                                              \
+                       part, dsrcbias, per);                                                                                    \
   }
     const int sp = g->mfma_split;
     if (g->Wq == 8) { if (sp == 2) MTRSSM_WGT4B_LAUNCH(2, 8) else MTRSSM_WGT4B_LAUNCH(1, 8) }
     else { if (sp == 2) MTRSSM_WGT4B_LAUNCH(2, 4) else MTRSSM_WGT4B_LAUNCH(1, 4) }
 #undef MTRSSM_WGT4B_LAUNCH
     if (part)
-      if (int rc = reduce_now_or_later(kRedT4b, dim3(kWgT4bSetFloats / 4 / 8), part, (int)grid.x, g->Cpad, dwp, nullptr, stream)) return rc;
+      if (int rc = reduce_now_or_later(kRedT4b, dim3(kWgT4bTileFloats / 4 / 8 + (dsrcbias ? 1 : 0)), part, (int)grid.x, g->Cpad, dwp, dsrcbias, stream)) return rc;
     return launched("conv_weight_grad(k4 s2 staged, 64 rows)");
   }
   if ((g->mfma_split == 1 || g->mfma_split == 2) && g->KH == 3 && g->KW == 3 && g->SS == 2 && g->TS == 1 && g->OFFY == -1 && g->OFFX == -1 &&

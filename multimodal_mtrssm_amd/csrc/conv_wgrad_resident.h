@@ -617,6 +617,233 @@ __global__ __launch_bounds__(256) void wgrad_reduce_partials1x1_kernel(const flo
 }
 
 // ------------------------------------------------------------------------------------------------
+// The WHOLE backward of a residual block's 1x1 layer (C = 128 or 64 mid channels -> 64, 64-pixel planes, two bf16 pieces) in
+// one pass over g_y (`a`) and h (`src`):
+//   g_h[n][m][p] = (sum_o W1[o][m] g_y[n][o][p]) * act'(h[n][m][p])     dW1[o][m] = sum g_y[n][o][p] act(h)[n][m][p]     db1[o] = sum g_y
+// conv1x1_stream_kernel<64, C, false> followed by conv1x1_wgrad_staged_kernel<2, C> streams both tensors twice (8 / 5 units
+// of one 64-channel tensor per block pair); this is conv1x1_wgrad_staged_kernel<2, C> -- same staging, same tiles, same
+// partial sets and bias sums, so the same reduce -- with the backward-data product added from the frame it has in LDS
+// (5 / 3 units).  Its B operand wants k = output channel, lane = pixel: the staging threads also write a PIXEL-major image of
+// g_y's pieces ([pixel][64 channels + 8], 18 KB per buffer), a fragment is one 16-byte read.  A operands: wave w owns the
+// 32-channel tile w >> 1 of g_h for the pixel half w & 1 (C = 64: waves 4 - 7 repeat the products of waves 0 - 3 and do not
+// store), its rows of W1^T in 32 registers for the whole launch.  Products per k-block in conv1x1_stream_kernel's order
+// (a0 bl, a1 bh, a0 bh), k-blocks in channel order, the same pieces: g_h is bit-identical to that kernel's.  act'(h) comes
+// from the fp32 h in accumulator layout, requested a frame ahead (an L2 hit: the workgroup has just loaded the frame).
+// Counter waits: every load of the loop is inline asm in a fixed order -- frame n issues [act' operand of n + 1][raw set
+// n + 2] -- and a wait names the number of LOADS issued behind the one it needs (loads return in order among themselves;
+// the g_h stores share the counter, return in an order of their own and can only make a wait longer).
+// ------------------------------------------------------------------------------------------------
+template <int C>
+__host__ __device__ constexpr int bwd1x1_lds_bytes() { return wg1x1_lds_bytes<2, C>() + 2 * 2 * 64 * kWgresAPitch; }
+
+template <int C>
+__global__ __launch_bounds__(512, 1) void conv1x1_bwd_fused_kernel(
+    const MtrssmConvGeom g, const float* __restrict__ a, const float* __restrict__ src, const unsigned short* __restrict__ wq,
+    float* __restrict__ gh, float* __restrict__ dwp, float* __restrict__ part, float* __restrict__ dbias, const int frames_per_wg) {
+  static_assert(C == 64 || C == 128, "mid channels");
+  constexpr int SPLIT = 2, NT = 512, P = kWgresAPitch;
+  constexpr int XI = C * 16 / NT, AI = 2, NI = XI + AI;  // float4 items per thread and frame: src (h), a (g_y: 64 co * 16)
+  constexpr int NTILE = 2 * (C / 32), KS = 8 / NTILE;
+  constexpr int APB = 64 * P, XPB = C * P;
+  constexpr int BUFB = SPLIT * (APB + XPB);              // one buffer: [a pieces][src pieces]
+  constexpr int PMB = 64 * P, PMBUF = SPLIT * PMB;       // pixel-major g_y image: one piece, one buffer
+  constexpr int PM0 = 2 * BUFB;                          // [buffer 0][buffer 1][pixel-major 0][pixel-major 1]
+  extern __shared__ __attribute__((aligned(16))) unsigned char bw1_lds[];
+  unsigned char* const lds = bw1_lds;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int il = lane & 31, kl = lane >> 5;
+  const int tile = wave % NTILE, kpart = wave / NTILE;
+  const int tco = tile & 1, tci = tile >> 1;
+  const int n0 = blockIdx.x * frames_per_wg;
+  const int n1 = n0 + frames_per_wg < g.N ? n0 + frames_per_wg : g.N;
+  if (n0 >= n1) return;  // whole workgroup
+  const int nlast = n1 - 1;
+
+  const bool act_elu = g.act == MTRSSM_ACT_ELU, act_relu = g.act == MTRSSM_ACT_RELU;
+  auto act_sel = [&](float x) __attribute__((always_inline)) {
+    float e = __expf(x) - 1.f;
+    asm volatile("" : "+v"(e));  // computed unconditionally: the compiler would branch around the exponential
+    const float neg = act_elu ? e : (act_relu ? 0.f : x);
+    return x > 0.f ? x : neg;
+  };
+
+  // backward-data job of this wave: g_h channels bct * 32 .. + 31, pixels bhalf * 32 .. + 31
+  const int bct = (wave >> 1) % (C / 32), bhalf = wave & 1;
+  const bool bstore = C == 128 || wave < 4;
+  u32x4 wa[4][2];  // [k-block][piece]: row bct * 32 + il of W1^T, output channels cb * 16 + 8 kl .. + 7
+#pragma unroll
+  for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+    for (int sp = 0; sp < 2; ++sp) {
+      wa[cb][sp] = *reinterpret_cast<const u32x4*>(wq + (size_t)sp * (C * 64) + (size_t)(bct * 32 + il) * 64 + cb * 16 + 8 * kl);
+      asm volatile("" : "+v"(wa[cb][sp]));  // landed here: no compiler-made wait for them inside the loop
+    }
+
+  const float4* const xsrc = reinterpret_cast<const float4*>(src) + tid;
+  const float4* const asrc = reinterpret_cast<const float4*>(a) + tid;
+  constexpr size_t xfr = (size_t)C * 16, afr = (size_t)64 * 16;  // float4 per frame
+  const unsigned wofs = (unsigned)((tid >> 4) * P + (tid & 15) * 8);
+  const unsigned pofs = (unsigned)(PM0 + 4 * (tid & 15) * P + (tid >> 4) * 2);  // pixel 4 (tid & 15), channel tid >> 4
+  float bsum[AI];
+#pragma unroll
+  for (int j = 0; j < AI; ++j) bsum[j] = 0.f;
+  wg_f32x4 raw[3][NI];  // [set][a items, x items]
+  auto raw_load = [&](const int rs, const int n) __attribute__((always_inline)) {
+#pragma unroll
+    for (int it = 0; it < NI; ++it) {
+      const float4* const ptr = it < AI ? asrc + (size_t)n * afr + NT * it : xsrc + (size_t)n * xfr + NT * (it - AI);
+      asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(raw[rs][it]) : "v"(ptr));
+    }
+  };
+  auto raw_wait = [&](const int rs) __attribute__((always_inline)) {  // loads behind this set: 2 raw sets + 2 act' sets
+    if constexpr (NI == 4) asm volatile("s_waitcnt vmcnt(40)" : "+v"(raw[rs][0]), "+v"(raw[rs][1]), "+v"(raw[rs][2]), "+v"(raw[rs][3]));
+    else asm volatile("s_waitcnt vmcnt(44)" : "+v"(raw[rs][0]), "+v"(raw[rs][1]), "+v"(raw[rs][2]), "+v"(raw[rs][3]), "+v"(raw[rs][4]), "+v"(raw[rs][5]));
+  };
+  // act' operand: h in accumulator layout (row (r & 3) + 8 (r >> 2) + 4 kl of the wave's channel tile, this lane's pixel)
+  const float* const hop = src + (size_t)(bct * 32 + 4 * kl) * 64 + bhalf * 32 + il;
+  float* const ghp = gh + (size_t)(bct * 32 + 4 * kl) * 64 + bhalf * 32 + il;
+  float opv[2][16];
+  auto op_load = [&](const int os, const int n) __attribute__((always_inline)) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float* const ptr = hop + (size_t)n * (C * 64) + ((r & 3) + 8 * (r >> 2)) * 64;
+      asm volatile("global_load_dword %0, %1, off" : "=v"(opv[os][r]) : "v"(ptr));
+    }
+  };
+  auto op_wait = [&](const int os) __attribute__((always_inline)) {  // loads behind this set: 2 raw sets + 1 act' set
+#define MTRSSM_OPV(os_, b_) "+v"(opv[os_][b_]), "+v"(opv[os_][b_ + 1]), "+v"(opv[os_][b_ + 2]), "+v"(opv[os_][b_ + 3]), "+v"(opv[os_][b_ + 4]), \
+                            "+v"(opv[os_][b_ + 5]), "+v"(opv[os_][b_ + 6]), "+v"(opv[os_][b_ + 7])
+    if constexpr (NI == 4) asm volatile("s_waitcnt vmcnt(24)" : MTRSSM_OPV(os, 0));
+    else asm volatile("s_waitcnt vmcnt(28)" : MTRSSM_OPV(os, 0));
+    asm volatile("" : MTRSSM_OPV(os, 8));  // (volatile: stays behind the wait)
+#undef MTRSSM_OPV
+  };
+  auto stage = [&](const int rs, const unsigned bufoff, const unsigned pmoff) __attribute__((always_inline)) {
+#pragma unroll
+    for (int it = 0; it < NI; ++it) {
+      const wg_f32x4 v = raw[rs][it];
+      unsigned d0[SPLIT], d1[SPLIT];
+      if (it < AI) {
+        bsum[it] += (v.x + v.y) + (v.z + v.w);
+        wg_split_pair<SPLIT>(v.x, v.y, d0);
+        wg_split_pair<SPLIT>(v.z, v.w, d1);
+#pragma unroll
+        for (int p = 0; p < SPLIT; ++p) {  // the pixel-major copy: channel (tid >> 4) + 32 it of pixels 4 (tid & 15) .. + 3
+          unsigned char* const q = lds + pmoff + pofs + (unsigned)(it * 64 + p * PMB);
+          *reinterpret_cast<unsigned short*>(q) = (unsigned short)(d0[p] & 0xffffu);
+          *reinterpret_cast<unsigned short*>(q + P) = (unsigned short)(d0[p] >> 16);
+          *reinterpret_cast<unsigned short*>(q + 2 * P) = (unsigned short)(d1[p] & 0xffffu);
+          *reinterpret_cast<unsigned short*>(q + 3 * P) = (unsigned short)(d1[p] >> 16);
+        }
+      } else {
+        wg_split_pair<SPLIT>(act_sel(v.x), act_sel(v.y), d0);
+        wg_split_pair<SPLIT>(act_sel(v.z), act_sel(v.w), d1);
+      }
+      const unsigned base = it < AI ? (unsigned)(it * 32 * P) : (unsigned)(SPLIT * APB + (it - AI) * 32 * P);
+      const unsigned piece = it < AI ? (unsigned)APB : (unsigned)XPB;
+#pragma unroll
+      for (int p = 0; p < SPLIT; ++p) *reinterpret_cast<uint2*>(lds + bufoff + base + wofs + p * piece) = make_uint2(d0[p], d1[p]);
+    }
+  };
+
+  const unsigned lane_a = (unsigned)((tco * 32 + il) * P + kl * 16);
+  const unsigned lane_b = (unsigned)(SPLIT * APB + (tci * 32 + il) * P + kl * 16);
+  const unsigned lane_p = (unsigned)(PM0 + (bhalf * 32 + il) * P + kl * 16);
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+
+  raw_load(0, n0);
+  op_load(0, n0);
+  raw_load(1, n0 + 1 < nlast ? n0 + 1 : nlast);
+  // One frame: rs = (n - n0) % 3 and par = (n - n0) & 1 are literals at the call sites.
+  auto frame = [&](const int n, const int rs, const int par) __attribute__((always_inline)) {
+    const unsigned bufoff = par ? (unsigned)BUFB : 0u, pmoff = par ? (unsigned)PMBUF : 0u;
+    op_load(par ^ 1, n + 1 < nlast ? n + 1 : nlast);        // its set held frame n - 1's, used a frame ago
+    raw_load((rs + 2) % 3, n + 2 < nlast ? n + 2 : nlast);  // its set held frame n - 1, staged a frame ago
+    raw_wait(rs);
+    stage(rs, bufoff, pmoff);
+    lds_barrier();  // images par complete; every wave is done reading images par ^ 1 (frame n - 1)
+#pragma unroll
+    for (int qq = 0; qq < 4 / KS; ++qq) {
+      const int q = kpart * (4 / KS) + qq;
+      u32x4 qa[SPLIT], qb[SPLIT];
+#pragma unroll
+      for (int p = 0; p < SPLIT; ++p) {
+        qa[p] = *reinterpret_cast<const u32x4*>(lds + bufoff + lane_a + (unsigned)(p * APB) + (unsigned)(q * 32));
+        qb[p] = *reinterpret_cast<const u32x4*>(lds + bufoff + lane_b + (unsigned)(p * XPB) + (unsigned)(q * 32));
+      }
+#pragma unroll
+      for (int ord = SPLIT - 1; ord >= 0; --ord)
+#pragma unroll
+        for (int sa = 0; sa <= ord; ++sa)
+          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, qa[sa]), __builtin_bit_cast(bf16x8, qb[ord - sa]), acc, 0, 0, 0);
+    }
+    // backward-data: 4 k-blocks of 16 output channels x 3 products
+    f32x16 accb;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) accb[r] = 0.f;
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) {
+      const bf16x8 bh = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(lds + pmoff + lane_p + (unsigned)(cb * 32)));
+      const bf16x8 bl = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(lds + pmoff + lane_p + (unsigned)(PMB + cb * 32)));
+      accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wa[cb][0]), bl, accb, 0, 0, 0);
+      accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wa[cb][1]), bh, accb, 0, 0, 0);
+      accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wa[cb][0]), bh, accb, 0, 0, 0);
+    }
+    op_wait(par);
+    if (bstore) {  // wave-uniform
+      float* const o = ghp + (size_t)n * (C * 64);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float x = opv[par][r];
+        const float e = __expf(x);
+        const float neg = act_elu ? e : (act_relu ? 0.f : 1.f);
+        o[((r & 3) + 8 * (r >> 2)) * 64] = accb[r] * (x > 0.f ? 1.f : neg);
+      }
+    }
+  };
+#pragma unroll 1
+  for (int n = n0; n < n1; n += 6) {
+    frame(n, 0, 0);
+    if (n + 1 < n1) frame(n + 1, 1, 1);
+    if (n + 2 < n1) frame(n + 2, 2, 0);
+    if (n + 3 < n1) frame(n + 3, 0, 1);
+    if (n + 4 < n1) frame(n + 4, 1, 0);
+    if (n + 5 < n1) frame(n + 5, 2, 1);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the clamped requests of the last frames
+
+  if (part) {  // the partial set of conv1x1_wgrad_staged_kernel: wgrad_reduce_partials1x1_body sums it
+    float4* const ps = reinterpret_cast<float4*>(part) + (size_t)blockIdx.x * (kWg1x1SetFloats / 4) + (size_t)wave * 256 + lane;
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) ps[gq * 64] = make_float4(acc[4 * gq], acc[4 * gq + 1], acc[4 * gq + 2], acc[4 * gq + 3]);
+  } else {
+    const int ci = tci * 32 + il;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row = tco * 32 + (r & 3) + 8 * (r >> 2) + 4 * kl;
+      atomicAdd(&dwp[(size_t)row * g.Cpad + ci], acc[r]);
+    }
+  }
+  if (dbias != nullptr) {
+#pragma unroll
+    for (int j = 0; j < AI; ++j) {  // the 16 lanes of a DPP row share a channel
+      float v = bsum[j];
+      v += dpp_move<0xB1, 0xF>(0.f, v);
+      v += dpp_move<0x4E, 0xF>(0.f, v);
+      v += dpp_move<0x141, 0xF>(0.f, v);
+      v += dpp_move<0x140, 0xF>(0.f, v);
+      if ((tid & 15) == 0) {
+        const int ch = (tid >> 4) + j * 32;
+        if (part) part[(size_t)blockIdx.x * kWg1x1SetFloats + 8 * 1024 + ch] = v;
+        else atomicAdd(&dbias[ch], v);
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Weight gradient of the second encoder layer (3x3 / stride 2 / pad 1, 8 -> 16 channels, 256-pixel output planes: 16x16
 // vision, 32x8 audio), staged like the kernels above:
 //   dW[co][ky][kx][ci] = sum over frames n and output pixels (oy, ox) of  a[n][co][oy][ox] * act(src)[n][ci][2 oy + ky - 1][2 ox + kx - 1]
@@ -873,9 +1100,13 @@ __global__ __launch_bounds__(256) void wgrad_reduce_partials_s2_kernel(const flo
 // (funnel shift with the element in front), kx = 1 the even image at x, kx = 2 the odd image at x, kx = 3 the even image
 // at x + 1 (funnel shift the other way with the element behind).  MFMA columns are (tap, co) pairs: 16 x 16 = 256 = one
 // 32-column tile per wave; rows are the 32 ci.  One image buffer (102 KB: two barriers per frame), raw frames (96 KB per
-// frame and workgroup) requested two frames ahead.  Partial set: float4 number (w * 4 + r / 4) * 64 + lane.
+// frame and workgroup) requested two frames ahead.  Partial set: float4 number (w * 4 + r / 4) * 64 + lane, + 16 bias sums.
+// The layer's bias gradient is the per-channel sum of src, which this kernel streams anyway: with dsrcbias != NULL every
+// thread adds up its src items while staging (item j of a thread is channel tid / 256 + 2 j: four waves per channel, met
+// in LDS) and the workgroup's 16 sums travel with its partial set -- a separate channel-sum launch re-read the tensor.
 // ------------------------------------------------------------------------------------------------
-constexpr int kWgT4SetFloats = 8 * 4 * 64 * 4;
+constexpr int kWgT4TileFloats = 8 * 4 * 64 * 4;
+constexpr int kWgT4SetFloats = kWgT4TileFloats + 16;
 template <int WO>
 __host__ __device__ constexpr int wgt4_cip() { return (((256 / WO * 2 + 2) * (2 * WO)) / 16 | 1) * 16; }
 template <int SPLIT, int WO>
@@ -884,7 +1115,7 @@ __host__ __device__ constexpr int wgt4_lds_bytes() { return SPLIT * (2 * 16 * wg
 template <int SPLIT, int WO>
 __global__ __launch_bounds__(512, 1) void convt4s2_wgrad_staged_kernel(
     const MtrssmConvGeom g, const float* __restrict__ a, const float* __restrict__ src, const int pre_act_a, float* __restrict__ dwp,
-    float* __restrict__ part, const int frames_per_wg) {
+    float* __restrict__ part, float* __restrict__ dsrcbias, const int frames_per_wg) {
   static_assert(SPLIT == 1 || SPLIT == 2, "one or two bf16 pieces");
   static_assert(WO == 16 || WO == 8, "input plane 16x16 or 32x8");
   constexpr int NT = 512, C = 16, CO = 32, HO = 256 / WO, HS = 2 * HO, WS = 2 * WO;
@@ -916,6 +1147,10 @@ __global__ __launch_bounds__(512, 1) void convt4s2_wgrad_staged_kernel(
   const float4* const xsrc = reinterpret_cast<const float4*>(src) + tid;
   const float4* const asrc = reinterpret_cast<const float4*>(a) + tid;
   constexpr size_t xfr = (size_t)C * HS * WS / 4, afr = (size_t)CO * 256 / 4;  // float4 per frame
+  static_assert(HS * WS / 4 == 256 && XI == 8, "src item j of a thread is channel tid / 256 + 2 j");
+  float bsum[XI];
+#pragma unroll
+  for (int j = 0; j < XI; ++j) bsum[j] = 0.f;
   wg_f32x4 raw[3][NI];  // [set][a items, src items]
   auto raw_load = [&](const int rs, const int n) __attribute__((always_inline)) {
 #pragma unroll
@@ -943,6 +1178,7 @@ __global__ __launch_bounds__(512, 1) void convt4s2_wgrad_staged_kernel(
         for (int p = 0; p < SPLIT; ++p) *reinterpret_cast<uint2*>(lds + o + p * APB) = make_uint2(d0[p], d1[p]);
       } else {
         unsigned de[SPLIT], dd[SPLIT];  // even columns (c0, c0 + 2), odd columns (c0 + 1, c0 + 3)
+        bsum[it - AI] += (v.x + v.y) + (v.z + v.w);
         wg_split_pair<SPLIT>(v.x, v.z, de);
         wg_split_pair<SPLIT>(v.y, v.w, dd);
         const int f = tid + NT * (it - AI);
@@ -1010,6 +1246,16 @@ __global__ __launch_bounds__(512, 1) void convt4s2_wgrad_staged_kernel(
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the clamped requests of the last frames
 
+  float* const bred = reinterpret_cast<float*>(lds);  // [item][wave]
+  if (dsrcbias != nullptr) {
+    lds_barrier();  // the images are dead
+#pragma unroll
+    for (int j = 0; j < XI; ++j) {
+      const float v = wave_sum(bsum[j]);
+      if (lane == 0) bred[j * 8 + wave] = v;
+    }
+    lds_barrier();
+  }
   if (part) {
     float4* const ps = reinterpret_cast<float4*>(part) + (size_t)blockIdx.x * (kWgT4SetFloats / 4) + (size_t)wave * 256 + lane;
 #pragma unroll
@@ -1021,16 +1267,22 @@ __global__ __launch_bounds__(512, 1) void convt4s2_wgrad_staged_kernel(
       atomicAdd(&dwp[((size_t)row * 16 + tap) * g.Cpad + co], acc[r]);
     }
   }
+  if (dsrcbias != nullptr && tid < 16) {
+    const int j = tid >> 1, w0 = 4 * (tid & 1);  // channel tid = w0 / 4 + 2 j
+    const float v = (bred[j * 8 + w0] + bred[j * 8 + w0 + 1]) + (bred[j * 8 + w0 + 2] + bred[j * 8 + w0 + 3]);
+    if (part) part[(size_t)blockIdx.x * kWgT4SetFloats + kWgT4TileFloats + tid] = v;
+    else atomicAdd(&dsrcbias[tid], v);
+  }
 }
 
-// Partial sets of convt4s2_wgrad_staged_kernel into dwp.
+// Partial sets of convt4s2_wgrad_staged_kernel into dwp / dbias (the sums of src).
 __device__ __forceinline__ void wgrad_reduce_partials_t4_body(const float4* __restrict__ part, const int S, const int cpad,
-                                                                       float* __restrict__ dwp, const int bx, const int by) {
-  constexpr int SET4 = kWgT4SetFloats / 4, NL = 8, NG = 32;
+                                                                       float* __restrict__ dwp, float* __restrict__ dbias, const int bx, const int by) {
+  constexpr int SET4 = kWgT4SetFloats / 4, TILE4 = kWgT4TileFloats / 4, NL = 8, NG = 32;
   __shared__ float4 red[NG][NL];
   const int li = threadIdx.x & (NL - 1), sg = threadIdx.x / NL;
-  const int f = bx * NL + li;  // host: grid.x * 8 == SET4
-  const float4* const p = part + f;
+  const int f = bx * NL + li;  // host: grid.x * 8 == TILE4 (+ 8: the bias block, 4 float4 of it in use, launched when dbias != NULL)
+  const float4* const p = part + (f < SET4 ? f : SET4 - 1);
   float4 acc4[4];
 #pragma unroll
   for (int u = 0; u < 4; ++u) acc4[u] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1053,6 +1305,10 @@ __device__ __forceinline__ void wgrad_reduce_partials_t4_body(const float4* __re
     float4 v = red[0][li];
 #pragma unroll
     for (int k = 1; k < NG; ++k) { v.x += red[k][li].x; v.y += red[k][li].y; v.z += red[k][li].z; v.w += red[k][li].w; }
+    if (f >= TILE4) {  // block-uniform: the bias sums of channels 4 (f - TILE4) .. + 3
+      if (f < SET4) { float* const o = dbias + 4 * (f - TILE4); o[0] += v.x; o[1] += v.y; o[2] += v.z; o[3] += v.w; }
+      return;
+    }
     const int lane = f & 63, gq = (f >> 6) & 3, wave = f >> 8, il = lane & 31, kl = lane >> 5;
     const int col = wave * 32 + il, tap = col >> 4, co = col & 15, row = 8 * gq + 4 * kl;
     float* const o = dwp + ((size_t)row * 16 + tap) * cpad + co;
@@ -1061,8 +1317,8 @@ __device__ __forceinline__ void wgrad_reduce_partials_t4_body(const float4* __re
   }
 }
 __global__ __launch_bounds__(256) void wgrad_reduce_partials_t4_kernel(const float4* __restrict__ part, const int S, const int cpad,
-                                                                       float* __restrict__ dwp) {
-  wgrad_reduce_partials_t4_body(part, S, cpad, dwp, (int)blockIdx.x, (int)blockIdx.y);
+                                                                       float* __restrict__ dwp, float* __restrict__ dbias) {
+  wgrad_reduce_partials_t4_body(part, S, cpad, dwp, dbias, (int)blockIdx.x, (int)blockIdx.y);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1072,9 +1328,11 @@ __global__ __launch_bounds__(256) void wgrad_reduce_partials_t4_kernel(const flo
 // and 2 w + 1 (even image: kx = 1 as it stands, kx = 3 shifted the other way) for both 32-row tiles of the 64 ci = four
 // accumulator tiles.  A lane's 8 pixels are one whole row (8x8) or two whole rows (16x4: two 8-byte reads two image rows
 // apart), so no neighbour element is needed.  Partial set: float4 number ((w * 4 + tile) * 4 + r / 4) * 64 + lane,
-// tile = 2 (row tile) + (tap & 1).
+// tile = 2 (row tile) + (tap & 1), + 32 bias sums (dsrcbias != NULL: the per-channel sums of src, added up while staging; src
+// item j of a thread is channel wave + 8 j, so a wave sum is a workgroup sum).
 // ------------------------------------------------------------------------------------------------
-constexpr int kWgT4bSetFloats = 8 * 4 * 4 * 64 * 4;
+constexpr int kWgT4bTileFloats = 8 * 4 * 4 * 64 * 4;
+constexpr int kWgT4bSetFloats = kWgT4bTileFloats + 32;
 template <int WO>
 __host__ __device__ constexpr int wgt4b_cip() { return (((64 / WO * 2 + 2) * (2 * WO)) / 16 | 1) * 16; }
 template <int SPLIT, int WO>
@@ -1083,7 +1341,7 @@ __host__ __device__ constexpr int wgt4b_lds_bytes() { return SPLIT * (2 * 32 * w
 template <int SPLIT, int WO>
 __global__ __launch_bounds__(512, 1) void convt4s2b_wgrad_staged_kernel(
     const MtrssmConvGeom g, const float* __restrict__ a, const float* __restrict__ src, const int pre_act_a, float* __restrict__ dwp,
-    float* __restrict__ part, const int frames_per_wg) {
+    float* __restrict__ part, float* __restrict__ dsrcbias, const int frames_per_wg) {
   static_assert(SPLIT == 1 || SPLIT == 2, "one or two bf16 pieces");
   static_assert(WO == 8 || WO == 4, "input plane 8x8 or 16x4");
   constexpr int NT = 512, C = 32, CO = 64, HO = 64 / WO, HS = 2 * HO, WS = 2 * WO;
@@ -1114,6 +1372,10 @@ __global__ __launch_bounds__(512, 1) void convt4s2b_wgrad_staged_kernel(
   const float4* const xsrc = reinterpret_cast<const float4*>(src) + tid;
   const float4* const asrc = reinterpret_cast<const float4*>(a) + tid;
   constexpr size_t xfr = (size_t)C * HS * WS / 4, afr = (size_t)CO * 64 / 4;  // float4 per frame
+  static_assert(HS * WS / 4 == 64 && XI == 4, "src item j of a thread is channel wave + 8 j");
+  float bsum[XI];
+#pragma unroll
+  for (int j = 0; j < XI; ++j) bsum[j] = 0.f;
   wg_f32x4 raw[3][NI];  // [set][a items, src items]
   auto raw_load = [&](const int rs, const int n) __attribute__((always_inline)) {
 #pragma unroll
@@ -1140,6 +1402,7 @@ __global__ __launch_bounds__(512, 1) void convt4s2b_wgrad_staged_kernel(
         for (int p = 0; p < SPLIT; ++p) *reinterpret_cast<uint2*>(lds + o + p * APB) = make_uint2(d0[p], d1[p]);
       } else {
         unsigned de[SPLIT], dd[SPLIT];  // even columns (c0, c0 + 2), odd columns (c0 + 1, c0 + 3)
+        bsum[it - AI] += (v.x + v.y) + (v.z + v.w);
         wg_split_pair<SPLIT>(v.x, v.z, de);
         wg_split_pair<SPLIT>(v.y, v.w, dd);
         const int f = tid + NT * (it - AI);
@@ -1232,15 +1495,25 @@ __global__ __launch_bounds__(512, 1) void convt4s2b_wgrad_staged_kernel(
         atomicAdd(&dwp[((size_t)row * 16 + 2 * wave + (t & 1)) * g.Cpad + il], acc[t][r]);
       }
   }
+  if (dsrcbias != nullptr) {
+#pragma unroll
+    for (int j = 0; j < XI; ++j) {
+      const float v = wave_sum(bsum[j]);
+      if (lane == 0) {
+        if (part) part[(size_t)blockIdx.x * kWgT4bSetFloats + kWgT4bTileFloats + wave + 8 * j] = v;
+        else atomicAdd(&dsrcbias[wave + 8 * j], v);
+      }
+    }
+  }
 }
 
-// Partial sets of convt4s2b_wgrad_staged_kernel into dwp.
+// Partial sets of convt4s2b_wgrad_staged_kernel into dwp / dbias (the sums of src).
 __device__ __forceinline__ void wgrad_reduce_partials_t4b_body(const float4* __restrict__ part, const int S, const int cpad,
-                                                                        float* __restrict__ dwp, const int bx, const int by) {
-  constexpr int SET4 = kWgT4bSetFloats / 4, NL = 8, NG = 32;
+                                                                        float* __restrict__ dwp, float* __restrict__ dbias, const int bx, const int by) {
+  constexpr int SET4 = kWgT4bSetFloats / 4, TILE4 = kWgT4bTileFloats / 4, NL = 8, NG = 32;
   __shared__ float4 red[NG][NL];
   const int li = threadIdx.x & (NL - 1), sg = threadIdx.x / NL;
-  const int f = bx * NL + li;  // host: grid.x * 8 == SET4
+  const int f = bx * NL + li;  // host: grid.x * 8 == TILE4 (+ 8: the bias block, launched when dbias != NULL)
   const float4* const p = part + f;
   float4 acc4[4];
 #pragma unroll
@@ -1264,6 +1537,11 @@ __device__ __forceinline__ void wgrad_reduce_partials_t4b_body(const float4* __r
     float4 v = red[0][li];
 #pragma unroll
     for (int k = 1; k < NG; ++k) { v.x += red[k][li].x; v.y += red[k][li].y; v.z += red[k][li].z; v.w += red[k][li].w; }
+    if (f >= TILE4) {  // block-uniform: the bias sums of channels 4 (f - TILE4) .. + 3
+      float* const o = dbias + 4 * (f - TILE4);
+      o[0] += v.x; o[1] += v.y; o[2] += v.z; o[3] += v.w;
+      return;
+    }
     const int lane = f & 63, gq = (f >> 6) & 3, t = (f >> 8) & 3, wave = f >> 10, il = lane & 31, kl = lane >> 5;
     const int tap = 2 * wave + (t & 1), row = (t >> 1) * 32 + 8 * gq + 4 * kl;
     float* const o = dwp + ((size_t)row * 16 + tap) * cpad + il;
@@ -1272,8 +1550,8 @@ __device__ __forceinline__ void wgrad_reduce_partials_t4b_body(const float4* __r
   }
 }
 __global__ __launch_bounds__(256) void wgrad_reduce_partials_t4b_kernel(const float4* __restrict__ part, const int S, const int cpad,
-                                                                        float* __restrict__ dwp) {
-  wgrad_reduce_partials_t4b_body(part, S, cpad, dwp, (int)blockIdx.x, (int)blockIdx.y);
+                                                                        float* __restrict__ dwp, float* __restrict__ dbias) {
+  wgrad_reduce_partials_t4b_body(part, S, cpad, dwp, dbias, (int)blockIdx.x, (int)blockIdx.y);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1515,9 +1793,11 @@ __global__ __launch_bounds__(256) void wgrad_reduce_partials_thin_kernel(const f
 // Weight gradient of the decoders' LAST ConvTranspose2d (k = 4, stride 2, pad 1, 16 -> 1 channel; input planes of 1024
 // pixels: 32x32 vision, 64x16 audio): convt4s2_wgrad_staged_kernel on a thin layer.  `a` is the layer input (16 channels,
 // activated here), src the one-channel output gradient; 16 (tap) columns and 16 rows = a quarter of one MFMA tile, held by
-// all eight waves for eight of the frame's 64 k-steps each.  Partial set: float4 number (w * 2 + r / 4) * 64 + lane, r < 8.
+// all eight waves for eight of the frame's 64 k-steps each.  Partial set: float4 number (w * 2 + r / 4) * 64 + lane, r < 8,
+// + 8 bias sums (dsrcbias != NULL: every wave's sum of the one src channel, added up while staging).
 // ------------------------------------------------------------------------------------------------
-constexpr int kWgThinTSetFloats = 8 * 2 * 64 * 4;
+constexpr int kWgThinTTileFloats = 8 * 2 * 64 * 4;
+constexpr int kWgThinTSetFloats = kWgThinTTileFloats + 8;
 template <int WO>
 __host__ __device__ constexpr int wgthint_cip() { return (((1024 / WO * 2 + 2) * (2 * WO)) / 16 | 1) * 16; }
 template <int SPLIT, int WO>
@@ -1526,7 +1806,7 @@ __host__ __device__ constexpr int wgthint_lds_bytes() { return SPLIT * (2 * wgth
 template <int SPLIT, int WO>
 __global__ __launch_bounds__(512, 1) void convt4s2_thin_wgrad_staged_kernel(
     const MtrssmConvGeom g, const float* __restrict__ a, const float* __restrict__ src, const int pre_act_a, float* __restrict__ dwp,
-    float* __restrict__ part, const int frames_per_wg) {
+    float* __restrict__ part, float* __restrict__ dsrcbias, const int frames_per_wg) {
   static_assert(SPLIT == 1 || SPLIT == 2, "one or two bf16 pieces");
   static_assert(WO == 32 || WO == 16, "input plane 32x32 or 64x16");
   constexpr int NT = 512, CO = 16, HO = 1024 / WO, HS = 2 * HO, WS = 2 * WO;
@@ -1556,6 +1836,7 @@ __global__ __launch_bounds__(512, 1) void convt4s2_thin_wgrad_staged_kernel(
   const float4* const xsrc = reinterpret_cast<const float4*>(src) + tid;
   const float4* const asrc = reinterpret_cast<const float4*>(a) + tid;
   constexpr size_t xfr = (size_t)HS * WS / 4, afr = (size_t)CO * 1024 / 4;  // float4 per frame
+  float bsum = 0.f;  // this thread's share of the one src channel
   wg_f32x4 raw[3][NI];  // [set][a items, src items]
   auto raw_load = [&](const int rs, const int n) __attribute__((always_inline)) {
 #pragma unroll
@@ -1583,6 +1864,7 @@ __global__ __launch_bounds__(512, 1) void convt4s2_thin_wgrad_staged_kernel(
         for (int p = 0; p < SPLIT; ++p) *reinterpret_cast<uint2*>(lds + o + p * APB) = make_uint2(d0[p], d1[p]);
       } else {
         unsigned de[SPLIT], dd[SPLIT];  // even columns (c0, c0 + 2), odd columns (c0 + 1, c0 + 3)
+        bsum += (v.x + v.y) + (v.z + v.w);
         wg_split_pair<SPLIT>(v.x, v.z, de);
         wg_split_pair<SPLIT>(v.y, v.w, dd);
         const int f = tid + NT * (it - AI);
@@ -1655,14 +1937,36 @@ __global__ __launch_bounds__(512, 1) void convt4s2_thin_wgrad_staged_kernel(
 #pragma unroll
     for (int r = 0; r < 8; ++r) atomicAdd(&dwp[((size_t)((r & 3) + 8 * (r >> 2) + 4 * kl) * 16 + tap) * g.Cpad], acc[r]);
   }
+  if (dsrcbias != nullptr) {
+    const float v = wave_sum(bsum);
+    if (lane == 0) {
+      if (part) part[(size_t)blockIdx.x * kWgThinTSetFloats + kWgThinTTileFloats + wave] = v;
+      else atomicAdd(&dsrcbias[0], v);
+    }
+  }
 }
 
-// Partial sets of convt4s2_thin_wgrad_staged_kernel into dwp: one tile, eight k-parts per workgroup.
+// Partial sets of convt4s2_thin_wgrad_staged_kernel into dwp: one tile, eight k-parts per workgroup; block 16 (launched when
+// dbias != NULL): the 8 S wave sums of src into dbias[0].
 __device__ __forceinline__ void wgrad_reduce_partials_thint_body(const float4* __restrict__ part, const int S, const int cpad,
-                                                                          float* __restrict__ dwp, const int bx, const int by) {
+                                                                          float* __restrict__ dwp, float* __restrict__ dbias, const int bx, const int by) {
   constexpr int SET4 = kWgThinTSetFloats / 4, NL = 8, NG = 32;
   __shared__ float4 red[NG][NL];
   const int li = threadIdx.x & (NL - 1), sg = threadIdx.x / NL;
+  if (bx >= 16) {  // block-uniform
+    const float* const pb = reinterpret_cast<const float*>(part) + kWgThinTTileFloats + li;  // wave li of every workgroup
+    float t = 0.f;
+    for (int s = sg; s < S; s += NG) t += pb[(size_t)s * kWgThinTSetFloats];
+    red[sg][li].x = t;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      float v = 0.f;
+      for (int k = 0; k < NG; ++k)
+        for (int w = 0; w < NL; ++w) v += red[k][w].x;
+      dbias[0] += v;
+    }
+    return;
+  }
   const int f = bx * NL + li;  // half * 64 + lane: 128 of them (host: 16 blocks)
   const float4* const p = part + f;
   float4 acc4[2];
@@ -1696,8 +2000,8 @@ __device__ __forceinline__ void wgrad_reduce_partials_thint_body(const float4* _
   }
 }
 __global__ __launch_bounds__(256) void wgrad_reduce_partials_thint_kernel(const float4* __restrict__ part, const int S, const int cpad,
-                                                                          float* __restrict__ dwp) {
-  wgrad_reduce_partials_thint_body(part, S, cpad, dwp, (int)blockIdx.x, (int)blockIdx.y);
+                                                                          float* __restrict__ dwp, float* __restrict__ dbias) {
+  wgrad_reduce_partials_thint_body(part, S, cpad, dwp, dbias, (int)blockIdx.x, (int)blockIdx.y);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -17,6 +17,8 @@ def group(k: str) -> str:
         return "weight-resident 3x3 gathers (forward: the whole residual block, fused)"
     if "conv1x1_stream" in k:
         return "1x1 gathers (streaming kernel; backward-data only)"
+    if "bwd_fused" in k:
+        return "1x1 backward of the residual blocks in one pass (g_h, dW1, db1)"
     if "wgrad_reduce" in k:
         return "partial-set sums of the staged weight gradients (one batched launch)"
     if "wgrad" in k:
