@@ -601,6 +601,16 @@ int mtrssm_episode_gather(const float* store, const int64_t* idx, const float* n
  * (mtrssm_episode_gather is the entry for the first T frames); everything else as mtrssm_episode_gather. */
 int mtrssm_episode_gather_window(const float* store, const int64_t* idx, const int32_t* start, const float* noise, int64_t n_episodes,
                                  int64_t B, int64_t T, int64_t Tfull, int64_t E, float std_, float* input, float* target, void* stream);
+/* The window gather for episodes of different lengths: lengths [n_episodes] int32 in DEVICE memory,
+ *   target[b, t, :] = (start[b] + t < lengths[idx[b]]) ? store[idx[b], start[b] + t, :] : 0
+ *   input = target + noise * std (the same two roundings) on a live frame, exactly 0 on a dead one; a dead frame issues no load.
+ * start[b] is clamped into [0, Tfull] -- a chunk may hang over the end of the store, the length test keeps every read inside
+ * it --, lengths into [0, Tfull], idx[b] into [0, n_episodes).  valid_out (int32 [B], may be NULL) receives
+ * clamp(lengths[idx[b]] - start[b], 0, T), the live steps of row b.  A null start or lengths returns -1; everything else as
+ * mtrssm_episode_gather_window. */
+int mtrssm_episode_gather_ragged(const float* store, const int64_t* idx, const int32_t* start, const int32_t* lengths, const float* noise,
+                                 int64_t n_episodes, int64_t B, int64_t T, int64_t Tfull, int64_t E, float std_, float* input, float* target,
+                                 int32_t* valid_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Carried state of truncated BPTT: the initial state of a train step is, per batch row, either the
@@ -631,6 +641,10 @@ typedef struct MtrssmStateTable {
 } MtrssmStateTable;
 int mtrssm_state_select(const MtrssmStateTable* table, const uint8_t* reset, int64_t B, void* stream);
 int mtrssm_state_save(const MtrssmStateTable* table, int64_t B, int64_t steps, void* stream);
+/* mtrssm_state_save at a per-row step (ragged batches): last [B] int32 in DEVICE memory,
+ *   dst[k][b, :] = src[k][b, last[b], :] when 0 <= last[b] < steps; otherwise dst[k][b, :] is left as it is (a row with no live
+ *   step keeps its carry).  Same lanes and argument rules as mtrssm_state_save; a null or misaligned `last` returns -1. */
+int mtrssm_state_save_at(const MtrssmStateTable* table, const int32_t* last, int64_t B, int64_t steps, void* stream);
 
 /* The scalar end of shared_step (core.py:187-221; mmtrssm core.py:563-606) in one launch each way:
  *   recon = nll_a + nll_v;  kl_j = c_j * mean_i kl_j[i], i < n (kl1 may be NULL);  loss = recon + kl_0 + kl_1, written to four scalars (o_k1 may be NULL).
@@ -639,6 +653,15 @@ int mtrssm_elbo_combine_fwd(const float* nll_a, const float* nll_v, const float*
                             float* o_recon, float* o_k0, float* o_k1, float* o_loss, void* stream);
 int mtrssm_elbo_combine_bwd(const float* g_recon, const float* g_k0, const float* g_k1, const float* g_loss, int64_t n, float c0, float c1,
                             float* g_nll_a, float* g_nll_v, float* g_kl0, float* g_kl1, void* stream);
+/* The same epilogue for ragged batches: live [n] in {0, 1}, count a device scalar (float),
+ *   kl_j = c_j * sum_i live[i] kl_j[i] / count   (0 when count = 0);   bwd: g_kl_j[i] = live[i] (g_kl_j + g_loss) c_j / count.
+ * Same reduction order as mtrssm_elbo_combine_fwd: with every step live and count = n the four scalars are bitwise its. */
+int mtrssm_elbo_combine_counted_fwd(const float* nll_a, const float* nll_v, const float* kl0, const float* kl1, const float* live,
+                                    const float* count, int64_t n, float c0, float c1, float* o_recon, float* o_k0, float* o_k1,
+                                    float* o_loss, void* stream);
+int mtrssm_elbo_combine_counted_bwd(const float* g_recon, const float* g_k0, const float* g_k1, const float* g_loss, const float* live,
+                                    const float* count, int64_t n, float c0, float c1, float* g_nll_a, float* g_nll_v, float* g_kl0,
+                                    float* g_kl1, void* stream);
 /* Categorical head of the initial state (core.py:121-135, mmtrssm core.py:321-362): `logits` [rows][K * C] flat (K categoricals
  * of C classes, softmax over classes), `u` [rows][K] uniforms -> logp, probs [rows][K][C] and the inverse-CDF one-hot sample
  * onehot [rows][K * C] (index = #{c <= C - 2 : cumulative probability <= u}, the cumulative sum a left fold).  The straight-through
@@ -685,6 +708,16 @@ int mtrssm_gaussian_nll_masked_bwd(const float* pred, const float* target, const
 int mtrssm_modality_dropout(const float* u, int64_t b_global, int64_t steps, int64_t span, float p_audio, float p_vision,
                             int64_t row0, int64_t b_local, int32_t* codes, float* present_audio, float* present_vision,
                             uint8_t* mask0, float* counts, void* stream);
+
+/* The masks of a ragged batch: valid [b_global] int32 in DEVICE memory (clamped into [0, steps]), step
+ * (b, t) is live iff t < valid[b].  A modality is present iff the step is live AND (u == NULL: no dropout, or the rule of
+ * mtrssm_modality_dropout says so, its t = 0 fix-up applied before the AND).  Written for the rank's rows as there, plus
+ * live [b_local * steps] in {0, 1} and last [b_local] int32 = valid - 1 (-1: a row with no live step); counts[3]: present audio
+ * frames, present vision frames and live steps over ALL b_global rows (zeroed, then one atomic per workgroup and count).
+ * Argument rules as mtrssm_modality_dropout (p is only checked when u is given). */
+int mtrssm_step_mask_ragged(const int32_t* valid, const float* u, int64_t b_global, int64_t steps, int64_t span, float p_audio,
+                            float p_vision, int64_t row0, int64_t b_local, int32_t* codes, float* present_audio, float* present_vision,
+                            float* live, uint8_t* mask0, int32_t* last, float* counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Fused AdamW over one flat fp32 parameter buffer, with global-norm gradient clipping

@@ -12,7 +12,8 @@
 continues one and ONE captured graph serves every chunk (``graph.CapturedTrainStep(state_carry=...)``).  Gradients stop at the
 chunk border: the select's backward hands ``reset[b] ? g[b] : 0`` to the fresh state and nothing to the carry.
 
-``select_reference`` / ``select_backward_reference`` / ``save_reference`` restate the two kernels in torch.
+``select_reference`` / ``select_backward_reference`` / ``save_reference`` restate the two kernels in torch; ``save_at_reference`` the
+save of a ragged batch (``mtrssm_state_save_at``, DESIGN.md section 6d: each row's LAST LIVE step, an empty row keeps its carry).
 """
 
 from __future__ import annotations
@@ -44,6 +45,15 @@ def select_backward_reference(reset: Tensor, grad: Tensor) -> Tensor:
 def save_reference(last: Tensor) -> Tensor:
     """``carry[b] = last[b, T - 1]`` for a scan output ``[B, T, W]``."""
     return last[:, -1].detach().clone()
+
+
+def save_at_reference(out: Tensor, last: Tensor, carry: Tensor) -> Tensor:
+    """``carry[b] = out[b, last[b]]`` for ``0 <= last[b] < T`` (``out``: a scan output ``[B, T, W]``); other rows keep ``carry[b]``."""
+    steps = out.shape[1]
+    at = last.to(torch.long)
+    ok = (at >= 0) & (at < steps)
+    rows = out.detach()[torch.arange(out.shape[0], device=out.device), at.clamp(0, steps - 1)]
+    return torch.where(ok.reshape(-1, 1), rows, carry)
 
 
 def _table(entries: list[tuple[Tensor, Tensor | None, Tensor]]) -> C.Structure:
@@ -89,9 +99,13 @@ def select_launch(reset: Tensor, fresh: list[Tensor], carry: list[Tensor | None]
     return out
 
 
-def save_launch(last: list[Tensor], carry: list[Tensor]) -> None:
-    """One ``mtrssm_state_save`` launch on torch's current stream: ``carry[k][b] = last[k][b, T - 1]``, read in place."""
+def save_launch(last: list[Tensor], carry: list[Tensor], at: Tensor | None = None) -> None:
+    """One ``mtrssm_state_save`` launch on torch's current stream: ``carry[k][b] = last[k][b, T - 1]``, read in place.  ``at`` (int32
+    ``[B]`` on the device): ``mtrssm_state_save_at`` instead, ``carry[k][b] = last[k][b, at[b]]`` where ``0 <= at[b] < T``."""
     b, steps = last[0].shape[:2]
+    if at is not None and (at.dtype != torch.int32 or tuple(at.shape) != (b,)):
+        msg = f"state_save_at: last must be int32 [{b}], got {at.dtype} {tuple(at.shape)}"
+        raise ValueError(msg)
     srcs = []
     for t, c in zip(last, carry, strict=True):
         if t.dim() != 3 or tuple(t.shape[:2]) != (b, steps) or tuple(c.shape) != (b, t.shape[2]):  # noqa: PLR2004
@@ -100,7 +114,11 @@ def save_launch(last: list[Tensor], carry: list[Tensor]) -> None:
         srcs.append(t.detach())
         _lib.ptr(srcs[-1])  # (contiguous fp32 on the GPU, or MtrssmLibraryError)
     table = _table([(s, None, c) for s, c in zip(srcs, carry, strict=True)])
-    _lib.check(_lib.load().mtrssm_state_save(C.byref(table), b, steps, _lib.stream_ptr(carry[0].device)), "mtrssm_state_save")
+    if at is None:
+        _lib.check(_lib.load().mtrssm_state_save(C.byref(table), b, steps, _lib.stream_ptr(carry[0].device)), "mtrssm_state_save")
+    else:
+        _lib.check(_lib.load().mtrssm_state_save_at(C.byref(table), _lib.index_ptr(at.contiguous()), b, steps, _lib.stream_ptr(carry[0].device)),
+                   "mtrssm_state_save_at")
 
 
 class _StateSelect(torch.autograd.Function):
@@ -203,10 +221,12 @@ class StateCarry:
         return dict(zip(self.fields, out, strict=True))
 
     @torch.no_grad()
-    def save(self, prefix: str, last: dict[str, Tensor]) -> None:
-        """``carry = last[:, T - 1]`` for every tensor of the state (``last``: the scan's ``[B, T, .]`` outputs) and mark the set filled."""
+    def save(self, prefix: str, tensors: dict[str, Tensor], last: Tensor | None = None) -> None:
+        """``carry = tensors[:, T - 1]`` for every tensor of the state (``tensors``: the scan's ``[B, T, .]`` outputs) and mark the set
+        filled.  ``last`` (int32 ``[B]`` on the device, ragged batches): ``carry[b] = tensors[b, last[b]]``, a row with ``last[b] = -1``
+        keeps its carry."""
         carry = self._set(prefix)
-        save_launch([last[k] for k in self.fields], [carry[k] for k in self.fields])
+        save_launch([tensors[k] for k in self.fields], [carry[k] for k in self.fields], last)
         self.filled[prefix] = True
 
     # -- snapshots (the captured step's warm-up leaves the carry as it found it) --------------------
@@ -241,4 +261,4 @@ class StateCarry:
                        stoch_h=c["stoch_h"], stoch_l=c["stoch_l"])
 
 
-__all__ = ["StateCarry", "save_reference", "select_backward_reference", "select_reference"]
+__all__ = ["StateCarry", "save_at_reference", "save_reference", "select_backward_reference", "select_reference"]

@@ -22,7 +22,7 @@ from torch import Tensor, nn
 from multimodal_mtrssm_amd import cnn, conv, scan
 from multimodal_mtrssm_amd.carry import StateCarry
 from multimodal_mtrssm_amd.distributions import MultiOneHot, MultiOneHotFactory, draw_uniforms, kl_divergence, onehot_from_uniforms
-from multimodal_mtrssm_amd.dropout import ModalityDropout, StepMask
+from multimodal_mtrssm_amd.dropout import ModalityDropout, StepMask, ragged_step_mask
 from multimodal_mtrssm_amd.networks import MTRNN, Representation, Transition
 from multimodal_mtrssm_amd.objective import likelihood
 from multimodal_mtrssm_amd.state import MTState, State
@@ -137,8 +137,60 @@ class _ElboCombine(torch.autograd.Function):
         return g_a, g_v, g_kl0, g_kl1, None, None
 
 
-def _elbo(nll_a: Tensor, nll_v: Tensor, kl0: Tensor, c0: float, kl1: Tensor | None = None, c1: float = 0.0) -> tuple[Tensor, Tensor, Tensor, Tensor]:
-    """``(recon, kl_0, kl_1, loss)``; on the GPU one fused launch, elsewhere the eager arithmetic of the reference."""
+class _ElboCombineCounted(torch.autograd.Function):
+    """``_ElboCombine`` for ragged batches (``mtrssm_elbo_combine_counted_fwd / _bwd``):
+    ``kl_j = coeff_j sum(live kl_bt_j) / count``, ``live`` float ``[B * T]`` in {0, 1}, ``count`` a device scalar."""
+
+    @staticmethod
+    def forward(ctx, nll_a: Tensor, nll_v: Tensor, kl0: Tensor, kl1: Tensor | None, live: Tensor, count: Tensor, c0: float, c1: float):  # noqa: ANN001, ANN205, PLR0913
+        from multimodal_mtrssm_amd import _lib  # noqa: PLC0415
+
+        ctx.set_materialize_grads(False)
+        nll_a, nll_v, kl0 = nll_a.contiguous().float(), nll_v.contiguous().float(), kl0.contiguous().float()
+        kl1 = None if kl1 is None else kl1.contiguous().float()
+        live, count = live.contiguous().float(), count.contiguous().float()
+        if live.numel() != kl0.numel() or count.numel() != 1:
+            msg = f"live must have one entry per KL step ({kl0.numel()}), count one; got {live.numel()} and {count.numel()}"
+            raise ValueError(msg)
+        outs = [torch.empty((), device=kl0.device, dtype=torch.float32) for _ in range(4)]
+        _lib.check(_lib.load().mtrssm_elbo_combine_counted_fwd(
+            _lib.ptr(nll_a), _lib.ptr(nll_v), _lib.ptr(kl0), _lib.ptr(kl1), _lib.ptr(live), _lib.ptr(count), kl0.numel(), float(c0), float(c1),
+            _lib.ptr(outs[0]), _lib.ptr(outs[1]), _lib.ptr(outs[2]) if kl1 is not None else None, _lib.ptr(outs[3]),
+            _lib.stream_ptr(kl0.device)), "mtrssm_elbo_combine_counted_fwd")
+        ctx.meta = (kl0.shape, None if kl1 is None else kl1.shape, float(c0), float(c1))
+        ctx.dev = kl0.device
+        ctx.save_for_backward(live, count)
+        return outs[0], outs[1], outs[2], outs[3]
+
+    @staticmethod
+    def backward(ctx, g_recon, g_k0, g_k1, g_loss):  # noqa: ANN001, ANN205
+        from multimodal_mtrssm_amd import _lib  # noqa: PLC0415
+
+        shape0, shape1, c0, c1 = ctx.meta
+        live, count = ctx.saved_tensors
+        g_a, g_v = (torch.empty((), device=ctx.dev, dtype=torch.float32) for _ in range(2))
+        g_kl0 = torch.empty(shape0, device=ctx.dev, dtype=torch.float32)
+        g_kl1 = None if shape1 is None else torch.empty(shape1, device=ctx.dev, dtype=torch.float32)
+        opt = lambda t: None if t is None else _lib.ptr(t.contiguous().float())  # noqa: E731
+        _lib.check(_lib.load().mtrssm_elbo_combine_counted_bwd(
+            opt(g_recon), opt(g_k0), opt(g_k1) if shape1 is not None else None, opt(g_loss), _lib.ptr(live), _lib.ptr(count), live.numel(), c0, c1,
+            _lib.ptr(g_a), _lib.ptr(g_v), _lib.ptr(g_kl0), _lib.ptr(g_kl1), _lib.stream_ptr(ctx.dev)), "mtrssm_elbo_combine_counted_bwd")
+        return g_a, g_v, g_kl0, g_kl1, None, None, None, None
+
+
+def _elbo(nll_a: Tensor, nll_v: Tensor, kl0: Tensor, c0: float, kl1: Tensor | None = None, c1: float = 0.0,  # noqa: PLR0913
+          step_mask: StepMask | None = None) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """``(recon, kl_0, kl_1, loss)``; on the GPU one fused launch, elsewhere the eager arithmetic of the reference.  A ``step_mask``
+    that carries ``live`` (a ragged batch) takes the counted epilogue: the KL sums over live steps / ``count_live``."""
+    if step_mask is not None and step_mask.live is not None:
+        if kl0.is_cuda and nll_a.dim() == 0 and nll_v.dim() == 0:
+            return _ElboCombineCounted.apply(nll_a, nll_v, kl0, kl1, step_mask.live, step_mask.count_live, c0, c1)
+        live, count = step_mask.live.reshape(kl0.shape).to(kl0), step_mask.count_live.to(kl0)  # the same rule in eager arithmetic
+        zero = torch.zeros((), device=kl0.device)
+        recon = nll_a + nll_v
+        k0 = torch.where(count > 0, (kl0 * live).sum() / count * c0, zero)
+        k1 = torch.where(count > 0, (kl1 * live).sum() / count * c1, zero) if kl1 is not None else zero
+        return recon, k0, k1, recon + k0 + (k1 if kl1 is not None else 0.0)
     if kl0.is_cuda and nll_a.dim() == 0 and nll_v.dim() == 0:
         return _ElboCombine.apply(nll_a, nll_v, kl0, kl1, c0, c1)
     recon = nll_a + nll_v
@@ -204,6 +256,31 @@ def _resolve_modality_mask(observations: tuple, mask: Tensor | None, B: int, T: 
             msg = f"modality_mask marks {name} present, but observations carries None for it"
             raise ValueError(msg)
     return mask
+
+
+def _check_lengths(valid: Tensor, rows: int, device: torch.device) -> None:
+    """A ragged batch's live-step counts: int32 ``[rows]`` on ``device`` (not read back)."""
+    if not isinstance(valid, Tensor) or valid.dtype != torch.int32 or tuple(valid.shape) != (rows,):
+        msg = f"lengths must be an int32 tensor of shape ({rows},), got {getattr(valid, 'dtype', type(valid))} {tuple(getattr(valid, 'shape', ()))}"
+        raise ValueError(msg)
+    if valid.device != torch.device(device):
+        msg = f"lengths is on {valid.device}, the model's tensors on {device}"
+        raise ValueError(msg)
+
+
+def check_ragged_rows(valid_host: Tensor, reset_host: Tensor | None) -> None:
+    """The host rule of a ragged step: a row that resets needs a frame at t = 0 -- ``reset_host[b]`` implies
+    ``valid_host[b] >= 1`` (``reset_host`` None: every row resets).  Raises before anything is launched."""
+    empty = valid_host.to("cpu") < 1
+    if reset_host is not None:
+        if tuple(reset_host.shape) != tuple(valid_host.shape):
+            msg = f"reset {tuple(reset_host.shape)} and valid {tuple(valid_host.shape)} do not match"
+            raise ValueError(msg)
+        empty = empty & reset_host.to("cpu", torch.bool)
+    if bool(empty.any()):
+        msg = (f"rows {empty.nonzero().flatten().tolist()} start an episode (reset) with no valid frame: a row may have nothing at "
+               "t = 0 only when it continues from the carry")
+        raise ValueError(msg)
 
 
 def _masked_mean_embed(ea: Tensor | None, ev: Tensor | None, mask0: Tensor | None) -> Tensor:
@@ -405,23 +482,38 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         prev_state: State,
         noise: Noise | None = None,
         modality_mask: Tensor | None = None,
+        lengths: Tensor | None = None,
     ) -> tuple[State, State]:
         """``mrssm core.py:184-260``: returns (mixed posterior, prior), each ``[B, T, .]``.
 
         ``modality_mask``: optional bool ``[B, T, 2]`` (audio, vision), True = observed.  At each (b, t) the posterior mixes
         the present modalities only; with none present it is the prior (DESIGN.md "Missing modalities").  An entry of
-        ``observations`` may be None: that modality is absent at every step and its encoder is not run."""
+        ``observations`` may be None: that modality is absent at every step and its encoder is not run.  ``lengths`` (int32 ``[B]`` on
+        the device) instead of a mask: both modalities on a row's first ``lengths[b]`` steps, none after."""
         if not isinstance(observations, tuple):
             msg = "MoPoE-MRSSM requires tuple of (audio_obs, vision_obs)"
             raise TypeError(msg)
         audio_obs, vision_obs = observations
         B, T = actions.shape[:2]
-        mask = _resolve_modality_mask(observations, modality_mask, B, T, actions.device)
-        codes = None if mask is None else scan.modality_codes(mask)
+        codes = self._rollout_codes(observations, modality_mask, lengths, B, T, actions.device)
         audio_embed = None if audio_obs is None else self.audio_encoder(audio_obs)
         vision_embed = None if vision_obs is None else self.vision_encoder(vision_obs)
         out = self._rollout_embedded(actions, audio_embed, vision_embed, prev_state, noise, sample_prior=True, modality=codes)
         return self._states_from_rollout(out)
+
+    @staticmethod
+    def _rollout_codes(observations: tuple, modality_mask: Tensor | None, lengths: Tensor | None, B: int, T: int,  # noqa: N803, PLR0913
+                       device: torch.device) -> Tensor | None:
+        """The scans' codes of a rollout: from a modality mask (None: the unmasked kernels), or from ``lengths`` (int32 ``[B]`` on the
+        device: row b observes both modalities on its first ``lengths[b]`` steps and nothing after)."""
+        if lengths is None:
+            mask = _resolve_modality_mask(observations, modality_mask, B, T, device)
+            return None if mask is None else scan.modality_codes(mask)
+        if modality_mask is not None or observations[0] is None or observations[1] is None:
+            msg = "give lengths or a modality_mask (or a None observation), not both"
+            raise ValueError(msg)
+        _check_lengths(lengths, B, device)
+        return ragged_step_mask(lengths, None, T).codes
 
     def rollout_transition(self, *, actions: Tensor, prev_state: State, noise: Noise | None = None) -> State:
         """``core.py:170-185``: prior-only rollout (callbacks / evaluation)."""
@@ -432,13 +524,71 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         return State(deter=out["deter"], distribution=dist, stoch=out["prior_stoch"])
 
     # -- train / val ----------------------------------------------------------------------------
-    def _step_mask(self, batch: tuple[Tensor, ...], noise: Noise | None, modality_mask: Tensor | None,
-                   modality_dropout: ModalityDropout | None) -> StepMask | None:
+    def _ragged_step_mask(self, batch: tuple[Tensor, ...], noise: Noise | None, modality_dropout: ModalityDropout | None,  # noqa: PLR0913
+                          valid_global: Tensor, world: int, rank: int) -> StepMask:
+        """The masks of a ragged step from the GLOBAL batch's live-step counts, one launch, nothing read back:
+        lengths AND the dropout rule (``noise["u_mask"]``, drawn here when absent on one rank)."""
+        B, T = batch[0].shape[:2]
+        _check_lengths(valid_global, B * world, batch[0].device)
+        u = None
+        if modality_dropout is not None:
+            if not isinstance(modality_dropout, ModalityDropout):
+                msg = f"modality_dropout must be a ModalityDropout, got {type(modality_dropout).__name__}"
+                raise ValueError(msg)
+            if modality_dropout.world not in (1, world) or (modality_dropout.world == world and modality_dropout.rank != rank):
+                msg = f"modality_dropout is bound to rank {modality_dropout.rank} of {modality_dropout.world}, the batch to rank {rank} of {world}"
+                raise ValueError(msg)
+            u = None if noise is None else noise.get("u_mask")
+            if u is None:
+                if world > 1:
+                    msg = "modality_dropout on more than one rank needs noise['u_mask'] of the global batch (GlobalRowNoise.draw)"
+                    raise ValueError(msg)
+                u = _rand(batch[0], *modality_dropout.noise_shape(B, T))
+            if u.shape[0] != B * world:
+                msg = f"noise['u_mask'] has {u.shape[0]} rows, the global batch {B} x {world}"
+                raise ValueError(msg)
+        return ragged_step_mask(valid_global, u, T, modality_dropout, world=world, rank=rank)
+
+    def _lengths_of(self, batch: tuple[Tensor, ...], lengths: Tensor | None, modality_dropout: ModalityDropout | None,
+                    reset_host: Tensor | None, *, trust_reset: bool = False) -> tuple[Tensor, int, int] | None:
+        """``(valid_global, world, rank)`` of a ragged step, None for a step without lengths.  An explicit ``lengths`` is one rank's
+        own (int32 ``[B]`` on the device, trusted); a batch's ``valid_global`` comes with its host copy, on which the t = 0 rule is
+        checked here against ``reset_host`` (None: every row resets; ``trust_reset``: the reset only exists on the device, no check)."""
+        B = batch[0].shape[0]
+        if lengths is not None:
+            _check_lengths(lengths, B, batch[0].device)
+            if modality_dropout is not None and getattr(modality_dropout, "world", 1) != 1:
+                msg = "lengths= describes one rank's own rows: with data parallelism use a batch that carries valid_global"
+                raise ValueError(msg)
+            return lengths, 1, 0
+        valid_global = getattr(batch, "valid_global", None)
+        if valid_global is None:
+            return None
+        if valid_global.numel() % B:
+            msg = f"valid_global has {valid_global.numel()} rows, no multiple of the batch's {B}"
+            raise ValueError(msg)
+        world = valid_global.numel() // B
+        rank = int(getattr(batch, "row0", 0)) // B
+        valid_host = getattr(batch, "valid_host", None)
+        if valid_host is not None and not trust_reset:
+            check_ragged_rows(valid_host, reset_host)
+        return valid_global, world, rank
+
+    def _step_mask(self, batch: tuple[Tensor, ...], noise: Noise | None, modality_mask: Tensor | None,  # noqa: PLR0913
+                   modality_dropout: ModalityDropout | None, lengths: Tensor | None = None, reset_host: Tensor | None = None, *,
+                   trust_reset: bool = False) -> StepMask | None:
         """The masks of a training step (None: every modality everywhere, the unmasked kernels).  A caller's mask (the kwarg,
         else the batch's 7th entry) is validated on the host; a dropout's comes from its sampler kernel with no host round trip
-        (the rule itself keeps a modality at t = 0)."""
+        (the rule itself keeps a modality at t = 0).  ``lengths`` (or a batch that carries ``valid_global``): the ragged step's
+        masks, lengths AND dropout, from ``mtrssm_step_mask_ragged``."""
         mask = modality_mask if modality_mask is not None else self.get_modality_mask_from_batch(batch)
         B, T = batch[0].shape[:2]
+        ragged = self._lengths_of(batch, lengths, modality_dropout, reset_host, trust_reset=trust_reset)
+        if ragged is not None:
+            if mask is not None:
+                msg = "give lengths (or a batch that carries them) or a modality_mask, not both"
+                raise ValueError(msg)
+            return self._ragged_step_mask(batch, noise, modality_dropout, *ragged)
         if modality_dropout is None:
             if mask is None:
                 return None
@@ -463,7 +613,7 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
 
     def shared_step(self, batch: tuple[Tensor, ...], noise: Noise | None = None, modality_mask: Tensor | None = None,  # noqa: PLR0913
                     modality_dropout: ModalityDropout | None = None, state_carry: StateCarry | None = None,
-                    reset: Tensor | None = None, *, carry_prefix: str = "train") -> dict[str, Tensor]:
+                    reset: Tensor | None = None, *, carry_prefix: str = "train", lengths: Tensor | None = None) -> dict[str, Tensor]:
         """``core.py:187-221``: ``loss = recon + kl_coeff * KL(post || prior)`` (MMTRSSM, ``mmtrssm core.py:563-606``:
         ``recon + kl_coeff KL_l + kl_coeff w_kl_h KL_h``).  ``modality_mask`` (or a 7th batch entry, bool ``[B, T, 2]``): each
         recon term averages over the frames where its modality is present; the KL stays the mean over all B*T (0 on steps with
@@ -473,8 +623,18 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         ``state_carry``: rows with ``reset[b]`` False start from the posterior the previous step of
         ``carry_prefix``'s set ended with instead of the chunk's own frame 0; afterwards the posterior at t = T - 1 (detached) is
         saved there.  ``reset`` (bool ``[B]``) defaults to ``batch.reset`` of an ``EpisodeBatch``; a host tensor is also checked
-        against the carry's rules, a device tensor is trusted (an empty carry refuses it)."""
-        sm = self._step_mask(batch, noise, modality_mask, modality_dropout)
+        against the carry's rules, a device tensor is trusted (an empty carry refuses it).
+
+        ``lengths`` (int32 ``[B]`` on the device, default: the ``valid`` / ``valid_global`` of a batch made by a
+        loader with lengths): row b has ``lengths[b]`` live steps.  A dead step has no modality (posterior = prior, KL 0), no
+        reconstruction term and zero gradient; each term is divided by the GLOBAL batch's count of its frames / world, the KL by the
+        live steps; the carry saves each row's last live step.  A row may be empty only when it does not reset (without a
+        ``state_carry`` every row resets)."""
+        reset_host = None  # without a carry every row starts from its fresh state: every row resets
+        if state_carry is not None:
+            reset_host = getattr(batch, "reset_host", None) if reset is None else (None if reset.is_cuda else reset)
+        on_device = state_carry is not None and isinstance(reset, Tensor) and reset.is_cuda  # (trusted, as the carry trusts it)
+        sm = self._step_mask(batch, noise, modality_mask, modality_dropout, lengths, reset_host, trust_reset=on_device)
         if state_carry is None:
             return self._elbo_step(batch, noise, sm)
         return self._elbo_step(batch, noise, sm, self._carry_of(batch, state_carry, reset, carry_prefix))
@@ -517,9 +677,9 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
     def _state_like(fresh: State, got: dict[str, Tensor]) -> State:
         return State(deter=got["deter"], distribution=fresh.distribution, stoch=got["stoch"])
 
-    def _save_carry(self, out: dict[str, Tensor], carry: tuple[StateCarry, str, Tensor] | None) -> None:
+    def _save_carry(self, out: dict[str, Tensor], carry: tuple[StateCarry, str, Tensor] | None, last: Tensor | None = None) -> None:
         if carry is not None:
-            carry[0].save(carry[1], {k: out[v] for k, v in self._LAST_KEYS.items()})
+            carry[0].save(carry[1], {k: out[v] for k, v in self._LAST_KEYS.items()}, last)
 
     def _elbo_step(self, batch: tuple[Tensor, ...], noise: Noise | None, sm: StepMask | None,
                    carry: tuple[StateCarry, str, Tensor] | None = None) -> dict[str, Tensor]:
@@ -534,10 +694,10 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         state0 = self._state0(state0, carry)
         out = self._rollout_embedded(action_input, audio_embed, vision_embed, state0, noise, sample_prior=False,
                                      modality=None if sm is None else sm.codes)
-        self._save_carry(out, carry)
+        self._save_carry(out, carry, None if sm is None else sm.last)
         feature = torch.cat([out["deter"], out["post_stoch"]], dim=-1)
         parts = self._reconstruction_losses(feature, self.get_targets_from_batch(batch), sum_recon=False, step_mask=sm)
-        recon, kl_div, _, loss = _elbo(parts["recon/audio"], parts["recon/vision"], out["kl"], float(self.kl_coeff))
+        recon, kl_div, _, loss = _elbo(parts["recon/audio"], parts["recon/vision"], out["kl"], float(self.kl_coeff), step_mask=sm)
         return {"recon": recon, **parts, "kl": kl_div, "loss": loss}
 
     def _step(self, batch: tuple[Tensor, ...], prefix: str, *, with_loss_key: bool,
@@ -678,19 +838,20 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
         prev_state: MTState,
         noise: Noise | None = None,
         modality_mask: Tensor | None = None,
+        lengths: Tensor | None = None,
     ) -> tuple[MTState, MTState]:
         """``mmtrssm core.py:364-494``.
 
         ``modality_mask``: optional bool ``[B, T, 2]`` (audio, vision), True = observed.  At each (b, t) the posterior mixes
         the present modalities only; with none present it is the prior (DESIGN.md "Missing modalities").  An entry of
-        ``observations`` may be None: that modality is absent at every step and its encoder is not run."""
+        ``observations`` may be None: that modality is absent at every step and its encoder is not run.  ``lengths`` (int32 ``[B]`` on
+        the device) instead of a mask: both modalities on a row's first ``lengths[b]`` steps, none after."""
         if not isinstance(observations, tuple):
             msg = "MoPoE-MMTRSSM requires tuple of (audio_obs, vision_obs)"
             raise TypeError(msg)
         audio_obs, vision_obs = observations
         B, T = actions.shape[:2]
-        mask = _resolve_modality_mask(observations, modality_mask, B, T, actions.device)
-        codes = None if mask is None else scan.modality_codes(mask)
+        codes = self._rollout_codes(observations, modality_mask, lengths, B, T, actions.device)
         audio_embed = None if audio_obs is None else self.audio_encoder(audio_obs)
         vision_embed = None if vision_obs is None else self.vision_encoder(vision_obs)
         out = self._rollout_embedded(actions, audio_embed, vision_embed, prev_state, noise, sample_prior=True, modality=codes)
@@ -726,12 +887,12 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
         state0 = self._state0(state0, carry)
         out = self._rollout_embedded(action_input, audio_embed, vision_embed, state0, noise, sample_prior=False,
                                      modality=None if sm is None else sm.codes)
-        self._save_carry(out, carry)
+        self._save_carry(out, carry, None if sm is None else sm.last)
         feature = torch.cat([out["deter_h"], out["post_stoch_h"], out["deter_l"], out["post_stoch_l"]], dim=-1)
         parts = self._reconstruction_losses(feature, self.get_targets_from_batch(batch), sum_recon=False, step_mask=sm)
         recon, kl_div_l, kl_div_h, loss = _elbo(parts["recon/audio"], parts["recon/vision"], out["kl_l"], float(self.kl_coeff), out["kl_h"],
-                                                float(self.kl_coeff * self.w_kl_h))
+                                                float(self.kl_coeff * self.w_kl_h), step_mask=sm)
         return {"recon": recon, **parts, "kl": kl_div_l, "kl_h": kl_div_h, "loss": loss}
 
 
-__all__ = ["MoPoE_MMTRSSM", "MoPoE_MRSSM", "kl_divergence"]
+__all__ = ["MoPoE_MMTRSSM", "MoPoE_MRSSM", "check_ragged_rows", "kl_divergence"]

@@ -28,6 +28,15 @@ int episode_gather_window_launch(const float*, const int64_t*, const int32_t*, c
                                  float*, hipStream_t);
 int state_select_launch(const MtrssmStateTable*, const unsigned char*, int64_t, hipStream_t);
 int state_save_launch(const MtrssmStateTable*, int64_t, int64_t, hipStream_t);
+int state_save_at_launch(const MtrssmStateTable*, const int32_t*, int64_t, int64_t, hipStream_t);
+int episode_gather_ragged_launch(const float*, const int64_t*, const int32_t*, const int32_t*, const float*, int64_t, int64_t, int64_t, int64_t,
+                                 int64_t, float, float*, float*, int32_t*, hipStream_t);
+int step_mask_ragged_launch(const int32_t*, const float*, int64_t, int64_t, int64_t, float, float, int64_t, int64_t, int32_t*, float*, float*, float*,
+                            unsigned char*, int32_t*, float*, hipStream_t);
+int elbo_combine_counted_fwd_launch(const float*, const float*, const float*, const float*, const float*, const float*, int64_t, float, float, float*,
+                                    float*, float*, float*, hipStream_t);
+int elbo_combine_counted_bwd_launch(const float*, const float*, const float*, const float*, const float*, const float*, int64_t, float, float, float*,
+                                    float*, float*, float*, hipStream_t);
 int conv_gather_gemm_pair_launch(const MtrssmConvGeom*, const float*, const float*, const float*, const unsigned short*, const float*, const float*, const float*, float*,
                                  const MtrssmConvGeom*, const float*, const float*, const float*, const unsigned short*, const float*, const float*, const float*, float*, hipStream_t);
 int conv_residual_fwd_supported(const MtrssmConvGeom*);
@@ -252,6 +261,33 @@ MTRSSM_API int mtrssm_state_select(const MtrssmStateTable* table, const uint8_t*
 }
 MTRSSM_API int mtrssm_state_save(const MtrssmStateTable* table, int64_t B, int64_t steps, void* stream) {
   return state_save_launch(table, B, steps, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_state_save_at(const MtrssmStateTable* table, const int32_t* last, int64_t B, int64_t steps, void* stream) {
+  return state_save_at_launch(table, last, B, steps, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_episode_gather_ragged(const float* store, const int64_t* idx, const int32_t* start, const int32_t* lengths,
+                                            const float* noise, int64_t n_episodes, int64_t B, int64_t T, int64_t Tfull, int64_t E, float std_,
+                                            float* input, float* target, int32_t* valid_out, void* stream) {
+  return episode_gather_ragged_launch(store, idx, start, lengths, noise, n_episodes, B, T, Tfull, E, std_, input, target, valid_out,
+                                      static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_step_mask_ragged(const int32_t* valid, const float* u, int64_t b_global, int64_t steps, int64_t span, float p_audio,
+                                       float p_vision, int64_t row0, int64_t b_local, int32_t* codes, float* present_audio,
+                                       float* present_vision, float* live, uint8_t* mask0, int32_t* last, float* counts, void* stream) {
+  return step_mask_ragged_launch(valid, u, b_global, steps, span, p_audio, p_vision, row0, b_local, codes, present_audio, present_vision, live,
+                                 mask0, last, counts, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_elbo_combine_counted_fwd(const float* nll_a, const float* nll_v, const float* kl0, const float* kl1, const float* live,
+                                               const float* count, int64_t n, float c0, float c1, float* o_recon, float* o_k0, float* o_k1,
+                                               float* o_loss, void* stream) {
+  return elbo_combine_counted_fwd_launch(nll_a, nll_v, kl0, kl1, live, count, n, c0, c1, o_recon, o_k0, o_k1, o_loss,
+                                         static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_elbo_combine_counted_bwd(const float* g_recon, const float* g_k0, const float* g_k1, const float* g_loss, const float* live,
+                                               const float* count, int64_t n, float c0, float c1, float* g_nll_a, float* g_nll_v, float* g_kl0,
+                                               float* g_kl1, void* stream) {
+  return elbo_combine_counted_bwd_launch(g_recon, g_k0, g_k1, g_loss, live, count, n, c0, c1, g_nll_a, g_nll_v, g_kl0, g_kl1,
+                                         static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int mtrssm_conv_gather_gemm_pair(const MtrssmConvGeom* ga, const float* srca, const float* src2a, const float* wpa, const uint16_t* wqa,
                                             const float* biasa, const float* actgrada, const float* adda, float* outa,

@@ -415,6 +415,70 @@ int elbo_combine_bwd_launch(const float* g_recon, const float* g_k0, const float
   return check_launch("elbo_combine_bwd");
 }
 
+// The same epilogue for ragged batches: the KL sums run over the LIVE steps (live[i] in {0, 1}) and are
+// divided by the device scalar *count (the global batch's live steps / world; 0 -> the term is 0) instead of n.  Same loop, same
+// reduction order as elbo_combine_fwd_kernel: with every step live and *count == n the four scalars are bitwise its.
+// Backward: g_kl_bt_j[i] = live[i] ? (g_kl_j + g_loss) * coeff_j / count : 0 -- a dead step gets an explicit zero.
+__global__ void elbo_combine_counted_fwd_kernel(const float* __restrict__ nll_a, const float* __restrict__ nll_v, const float* __restrict__ kl0,
+                                                const float* __restrict__ kl1, const float* __restrict__ live, const float* __restrict__ count,
+                                                int64_t n, float c0, float c1, float* __restrict__ o_recon, float* __restrict__ o_k0,
+                                                float* __restrict__ o_k1, float* __restrict__ o_loss) {
+  __shared__ float red[kThreads / kWave];
+  float a0 = 0.f, a1 = 0.f;
+  for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
+    const bool on = live[i] != 0.f;
+    a0 += on ? kl0[i] : 0.f;
+    if (kl1) a1 += on ? kl1[i] : 0.f;
+  }
+  const float s0 = block_sum(a0, red);
+  __syncthreads();
+  const float s1 = block_sum(a1, red);
+  if (threadIdx.x == 0) {
+    const float cnt = count[0];
+    const float recon = nll_a[0] + nll_v[0];
+    const float k0 = cnt > 0.f ? s0 / cnt * c0 : 0.f, k1 = kl1 && cnt > 0.f ? s1 / cnt * c1 : 0.f;
+    o_recon[0] = recon; o_k0[0] = k0; if (o_k1) o_k1[0] = k1; o_loss[0] = recon + k0 + k1;
+  }
+}
+__global__ void elbo_combine_counted_bwd_kernel(const float* __restrict__ g_recon, const float* __restrict__ g_k0, const float* __restrict__ g_k1,
+                                                const float* __restrict__ g_loss, const float* __restrict__ live, const float* __restrict__ count,
+                                                int64_t n, float c0, float c1, float* __restrict__ g_nll_a, float* __restrict__ g_nll_v,
+                                                float* __restrict__ g_kl0, float* __restrict__ g_kl1) {
+  const float gl = g_loss ? g_loss[0] : 0.f;
+  const float gn = (g_recon ? g_recon[0] : 0.f) + gl;
+  const float cnt = count[0];
+  const float v0 = cnt > 0.f ? ((g_k0 ? g_k0[0] : 0.f) + gl) * c0 / cnt : 0.f;
+  const float v1 = cnt > 0.f ? ((g_k1 ? g_k1[0] : 0.f) + gl) * c1 / cnt : 0.f;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i == 0) { g_nll_a[0] = gn; g_nll_v[0] = gn; }
+  if (i < n) {
+    const bool on = live[i] != 0.f;
+    g_kl0[i] = on ? v0 : 0.f;
+    if (g_kl1) g_kl1[i] = on ? v1 : 0.f;
+  }
+}
+int elbo_combine_counted_fwd_launch(const float* nll_a, const float* nll_v, const float* kl0, const float* kl1, const float* live,
+                                    const float* count, int64_t n, float c0, float c1, float* o_recon, float* o_k0, float* o_k1, float* o_loss,
+                                    hipStream_t s) {
+  if (!nll_a || !nll_v || !kl0 || !live || !count || !o_recon || !o_k0 || !o_loss || n <= 0) {
+    set_error("elbo_combine_counted_fwd: bad argument");
+    return MTRSSM_EINVAL;
+  }
+  set_last_kernel("mtrssm::elbo_combine_counted_fwd_kernel");
+  hipLaunchKernelGGL(elbo_combine_counted_fwd_kernel, dim3(1), dim3(kThreads), 0, s, nll_a, nll_v, kl0, kl1, live, count, n, c0, c1, o_recon, o_k0,
+                     o_k1, o_loss);
+  return check_launch("elbo_combine_counted_fwd");
+}
+int elbo_combine_counted_bwd_launch(const float* g_recon, const float* g_k0, const float* g_k1, const float* g_loss, const float* live,
+                                    const float* count, int64_t n, float c0, float c1, float* g_nll_a, float* g_nll_v, float* g_kl0, float* g_kl1,
+                                    hipStream_t s) {
+  if (!live || !count || !g_nll_a || !g_nll_v || !g_kl0 || n <= 0) { set_error("elbo_combine_counted_bwd: bad argument"); return MTRSSM_EINVAL; }
+  set_last_kernel("mtrssm::elbo_combine_counted_bwd_kernel");
+  hipLaunchKernelGGL(elbo_combine_counted_bwd_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, g_recon, g_k0, g_k1,
+                     g_loss, live, count, n, c0, c1, g_nll_a, g_nll_v, g_kl0, g_kl1);
+  return check_launch("elbo_combine_counted_bwd");
+}
+
 int nll_fwd_launch(const float* pred, const float* target, int64_t frames, int64_t event, int act, float* out, hipStream_t s) {
   if (!pred || !target || !out || frames <= 0 || event <= 0) { set_error("gaussian_nll_fwd: bad argument"); return MTRSSM_EINVAL; }
   if (act != MTRSSM_ACT_IDENTITY && act != MTRSSM_ACT_TANH) { set_error("gaussian_nll: the fused output activation is Identity or Tanh (got %d)", act); return MTRSSM_EINVAL; }
@@ -499,6 +563,17 @@ int nll_masked_bwd_launch(const float* pred, const float* target, const float* p
 // counted: wave shuffle + LDS reduction, then ONE vector atomic per workgroup and modality.  The counts are whole numbers
 // below 2^24 (checked by the launch), so the fp32 atomic sums are exact whatever order they arrive in.
 // ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void dropout_present(const float* __restrict__ u, long b, int t, int span, int S, float p_audio, float p_vision,
+                                                bool& a, bool& v) {
+  const float2 uu = reinterpret_cast<const float2*>(u)[b * S + t / span];
+  a = uu.x >= p_audio;
+  v = uu.y >= p_vision;
+  if (t == 0 && !a && !v) {
+    a = uu.x >= uu.y;
+    v = !a;
+  }
+}
+
 __global__ __launch_bounds__(kThreads) void modality_dropout_kernel(
     const float* __restrict__ u, float p_audio, float p_vision, int span, int T, int S, long b_global, long row0, long b_local,
     int* __restrict__ codes, float* __restrict__ present_audio, float* __restrict__ present_vision, unsigned char* __restrict__ mask0,
@@ -509,12 +584,8 @@ __global__ __launch_bounds__(kThreads) void modality_dropout_kernel(
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const long b = i / T;
     const int t = (int)(i - b * T);
-    const float2 uu = reinterpret_cast<const float2*>(u)[b * S + t / span];
-    bool a = uu.x >= p_audio, v = uu.y >= p_vision;
-    if (t == 0 && !a && !v) {
-      a = uu.x >= uu.y;
-      v = !a;
-    }
+    bool a, v;
+    dropout_present(u, b, t, span, S, p_audio, p_vision, a, v);
     na += a ? 1.f : 0.f;
     nv += v ? 1.f : 0.f;
     const long r = b - row0;
@@ -561,6 +632,83 @@ int modality_dropout_launch(const float* u, int64_t b_global, int64_t T, int64_t
                      p_vision, (int)span, (int)T, (int)S, (long)b_global, (long)row0, (long)b_local, codes, present_audio, present_vision,
                      mask0, counts);
   return check_launch("modality_dropout");
+}
+
+// Ragged batches: row b of the global batch has valid[b] live steps (clamped into [0, T] here), step
+// (b, t) is live iff t < valid[b].  A modality is present iff the step is live AND (no dropout -- u == nullptr -- or the dropout
+// rule above says so, its t = 0 fix-up applied BEFORE the AND).  Beside modality_dropout_kernel's outputs: the `live` plane the
+// counted ELBO epilogue reads, last[r] = valid - 1 (-1: an empty row) for the carry's save, and a third count, the live steps.
+__global__ __launch_bounds__(kThreads) void step_mask_ragged_kernel(
+    const int* __restrict__ valid, const float* __restrict__ u, float p_audio, float p_vision, int span, int T, int S, long b_global, long row0,
+    long b_local, int* __restrict__ codes, float* __restrict__ present_audio, float* __restrict__ present_vision, float* __restrict__ live,
+    unsigned char* __restrict__ mask0, int* __restrict__ last, float* __restrict__ counts) {
+  __shared__ float red_a[kThreads / kWave], red_v[kThreads / kWave], red_l[kThreads / kWave];
+  const long total = b_global * T;
+  float na = 0.f, nv = 0.f, nl = 0.f;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long b = i / T;
+    const int t = (int)(i - b * T);
+    int n = valid[b];
+    n = n < 0 ? 0 : (n > T ? T : n);
+    const bool on = t < n;
+    bool a = true, v = true;
+    if (u) dropout_present(u, b, t, span, S, p_audio, p_vision, a, v);
+    a = a && on;
+    v = v && on;
+    na += a ? 1.f : 0.f;
+    nv += v ? 1.f : 0.f;
+    nl += on ? 1.f : 0.f;
+    const long r = b - row0;
+    if (r >= 0 && r < b_local) {
+      const long o = r * T + t;
+      codes[o] = (a ? 1 : 0) | (v ? 2 : 0);
+      present_audio[o] = a ? 1.f : 0.f;
+      present_vision[o] = v ? 1.f : 0.f;
+      live[o] = on ? 1.f : 0.f;
+      if (t == 0) {
+        mask0[2 * r] = a ? 1 : 0;
+        mask0[2 * r + 1] = v ? 1 : 0;
+        last[r] = n - 1;
+      }
+    }
+  }
+  const float ta = block_sum(na, red_a), tv = block_sum(nv, red_v), tl = block_sum(nl, red_l);
+  if (threadIdx.x == 0) {
+    atomicAdd(counts, ta);
+    atomicAdd(counts + 1, tv);
+    atomicAdd(counts + 2, tl);
+  }
+}
+
+int step_mask_ragged_launch(const int32_t* valid, const float* u, int64_t b_global, int64_t T, int64_t span, float p_audio, float p_vision,
+                            int64_t row0, int64_t b_local, int32_t* codes, float* present_audio, float* present_vision, float* live,
+                            unsigned char* mask0, int32_t* last, float* counts, hipStream_t s) {
+  if (!valid || !codes || !present_audio || !present_vision || !live || !mask0 || !last || !counts) {
+    set_error("step_mask_ragged: null pointer");
+    return MTRSSM_EINVAL;
+  }
+  if (b_global <= 0 || T <= 0 || span <= 0 || b_local <= 0 || row0 < 0 || row0 + b_local > b_global) {
+    set_error("step_mask_ragged: need B_global, T, span, B_local > 0 and 0 <= row0 <= B_global - B_local (got %lld %lld %lld %lld %lld)",
+              (long long)b_global, (long long)T, (long long)span, (long long)b_local, (long long)row0);
+    return MTRSSM_EINVAL;
+  }
+  if (u && (!(p_audio >= 0.f && p_audio < 1.f) || !(p_vision >= 0.f && p_vision < 1.f))) {
+    set_error("step_mask_ragged: probabilities must be in [0, 1) (got %g, %g)", (double)p_audio, (double)p_vision);
+    return MTRSSM_EINVAL;
+  }
+  if (b_global * T >= (int64_t)1 << 24) {
+    set_error("step_mask_ragged: %lld frames (the fp32 counts are exact below 2^24)", (long long)(b_global * T));
+    return MTRSSM_EINVAL;
+  }
+  if (span >= (int64_t)1 << 31) { set_error("step_mask_ragged: span %lld does not fit 31 bits", (long long)span); return MTRSSM_EINVAL; }
+  if (((uintptr_t)u & 7) || ((uintptr_t)valid & 3)) { set_error("step_mask_ragged: u must be 8-byte, valid 4-byte aligned"); return MTRSSM_EINVAL; }
+  if (int rc = clear_async(counts, 3 * sizeof(float), s)) return rc;
+  const int64_t S = (T + span - 1) / span;
+  set_last_kernel("mtrssm::step_mask_ragged_kernel");
+  hipLaunchKernelGGL(step_mask_ragged_kernel, dim3(grid_for(b_global * T) < 64 ? grid_for(b_global * T) : 64), dim3(kThreads), 0, s, valid, u,
+                     p_audio, p_vision, (int)span, (int)T, (int)S, (long)b_global, (long)row0, (long)b_local, codes, present_audio,
+                     present_vision, live, mask0, last, counts);
+  return check_launch("step_mask_ragged");
 }
 
 int sumsq_launch(const float* x, int64_t n, float* out, hipStream_t s) {
@@ -730,6 +878,73 @@ int episode_gather_window_launch(const float* store, const int64_t* idx, const i
   return check_launch("episode_gather_window");
 }
 
+// The window gather for episodes of different lengths: frame start[b] + t of episode idx[b] is LIVE iff it
+// lies before lengths[idx[b]]; a dead frame is exactly 0 in target and input (no noise added) and issues no load.  start[b] is
+// clamped into [0, Tfull] (a chunk may hang over the end of the store: the length test keeps every read inside it), lengths into
+// [0, Tfull], idx[b] into [0, n_episodes).  valid_out[b] (optional) = clamp(length - start, 0, T), the row's live steps.
+__global__ __launch_bounds__(kThreads) void episode_gather_ragged_kernel(
+    const float* __restrict__ store, const long* __restrict__ idx, const int* __restrict__ start, const int* __restrict__ lengths,
+    const float* __restrict__ noise, long n_episodes, long B, long T, long Tfull, long E4, float std_, float* __restrict__ input,
+    float* __restrict__ target, int* __restrict__ valid_out) {
+#pragma clang fp contract(off)  // (as episode_gather_kernel: mul then add, each rounded)
+  const long per_b = T * E4;
+  const long total = B * per_b;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long b = i / per_b, r = i - b * per_b;  // r = t * E4 + e4
+    const long t = r / E4;
+    long s = start[b];
+    s = s < 0 ? 0 : (s > Tfull ? Tfull : s);
+    long ep = idx[b];
+    ep = ep < 0 ? 0 : (ep >= n_episodes ? n_episodes - 1 : ep);
+    long len = lengths[ep];
+    len = len < 0 ? 0 : (len > Tfull ? Tfull : len);
+    const bool on = s + t < len;  // (< Tfull: the read below stays inside the episode)
+    if (valid_out && r == 0) {
+      const long n = len - s;
+      valid_out[b] = (int)(n < 0 ? 0 : (n > T ? T : n));
+    }
+    float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (on) x = reinterpret_cast<const float4*>(store)[(ep * Tfull + s) * E4 + r];
+    if (target) reinterpret_cast<float4*>(target)[i] = x;
+    if (input) {
+      float4 y = x;
+      if (noise && on) {
+        const float4 n = reinterpret_cast<const float4*>(noise)[i];
+        const float px = n.x * std_, py = n.y * std_, pz = n.z * std_, pw = n.w * std_;
+        y.x = x.x + px;
+        y.y = x.y + py;
+        y.z = x.z + pz;
+        y.w = x.w + pw;
+      }
+      reinterpret_cast<float4*>(input)[i] = y;
+    }
+  }
+}
+
+int episode_gather_ragged_launch(const float* store, const int64_t* idx, const int32_t* start, const int32_t* lengths, const float* noise,
+                                 int64_t n_episodes, int64_t B, int64_t T, int64_t Tfull, int64_t E, float std_, float* input, float* target,
+                                 int32_t* valid_out, hipStream_t s) {
+  if (!store || !idx || (!input && !target) || n_episodes <= 0 || B <= 0 || T <= 0 || Tfull < T || E <= 0) {
+    set_error("episode_gather_ragged: bad argument (need 0 < T <= Tfull, B, E > 0, an output)");
+    return MTRSSM_EINVAL;
+  }
+  if (!start || !lengths) { set_error("episode_gather_ragged: start or lengths is null"); return MTRSSM_EINVAL; }
+  if (E % 4) { set_error("episode_gather_ragged: the event size %ld must be a multiple of 4 floats", (long)E); return MTRSSM_EINVAL; }
+  if (((uintptr_t)store | (uintptr_t)noise | (uintptr_t)input | (uintptr_t)target) & 15) {
+    set_error("episode_gather_ragged: buffers must be 16-byte aligned");
+    return MTRSSM_EINVAL;
+  }
+  if (((uintptr_t)start | (uintptr_t)lengths | (uintptr_t)valid_out) & 3) {
+    set_error("episode_gather_ragged: start, lengths and valid_out must be 4-byte aligned");
+    return MTRSSM_EINVAL;
+  }
+  set_last_kernel("mtrssm::episode_gather_ragged_kernel");
+  hipLaunchKernelGGL(episode_gather_ragged_kernel, dim3(grid_for(B * T * E / 4)), dim3(kThreads), 0, s, store,
+                     reinterpret_cast<const long*>(idx), reinterpret_cast<const int*>(start), reinterpret_cast<const int*>(lengths), noise,
+                     (long)n_episodes, (long)B, (long)T, (long)Tfull, (long)(E / 4), std_, input, target, reinterpret_cast<int*>(valid_out));
+  return check_launch("episode_gather_ragged");
+}
+
 // ------------------------------------------------------------------------------------------------
 // Carried state of truncated BPTT: up to MTRSSM_STATE_MAX row-major [B, width] tensors per launch, the
 // table of pointers passed by value.  For entry k and row b:
@@ -781,8 +996,34 @@ __global__ __launch_bounds__(kThreads) void state_select_kernel(const StateRows 
 }
 __global__ __launch_bounds__(kThreads) void state_save_kernel(const StateRows t, long B) { state_rows(t, nullptr, B); }
 
-// fills `rows` from the caller's table; `steps` > 0: the save form (src is [B, steps, width], read at t = steps - 1)
-static int state_rows_fill(const char* what, const MtrssmStateTable* table, int64_t B, int64_t steps, StateRows* rows, int* grid_x) {
+// save at a per-row step: dst[k][b, :] = src[k][b, last[b], :] for 0 <= last[b] < steps, else dst is left as
+// it is (an empty row of a ragged batch keeps its carry).  src[k] is the [B, steps, width] base; same lanes as state_rows.
+__global__ __launch_bounds__(kThreads) void state_save_at_kernel(const StateRows t, const int* __restrict__ last, long B, long steps) {
+  const int k = blockIdx.y;
+  const float* __restrict__ src = t.src[k];
+  float* __restrict__ dst = t.dst[k];
+  const long stride = t.stride[k], w = t.width[k];
+  if (t.vec[k]) {
+    const long w4 = w / 4, total = B * w4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+      const long b = i / w4, q = i - b * w4, at = last[b];
+      if (at < 0 || at >= steps) continue;
+      reinterpret_cast<float4*>(dst + b * w)[q] = reinterpret_cast<const float4*>(src + b * stride + at * w)[q];
+    }
+  } else {
+    const long total = B * w;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+      const long b = i / w, e = i - b * w, at = last[b];
+      if (at < 0 || at >= steps) continue;
+      dst[b * w + e] = src[b * stride + at * w + e];
+    }
+  }
+}
+
+// fills `rows` from the caller's table; `steps` > 0: the save forms (src is [B, steps, width], read at t = steps - 1, or from its
+// base when `base`: the kernel adds a per-row step)
+static int state_rows_fill(const char* what, const MtrssmStateTable* table, int64_t B, int64_t steps, StateRows* rows, int* grid_x,
+                           bool base = false) {
   if (!table || B <= 0) { set_error("%s: null table or B <= 0", what); return MTRSSM_EINVAL; }
   if (table->count <= 0 || table->count > MTRSSM_STATE_MAX) {
     set_error("%s: count %d outside 1 .. %d", what, (int)table->count, MTRSSM_STATE_MAX);
@@ -801,7 +1042,7 @@ static int state_rows_fill(const char* what, const MtrssmStateTable* table, int6
     int64_t stride = steps > 0 ? steps * w : table->src_stride[k];
     if (stride < w) { set_error("%s: entry %d has row stride %lld < width %lld", what, k, (long long)stride, (long long)w); return MTRSSM_EINVAL; }
     if (B * w >= (int64_t)1 << 31) { set_error("%s: entry %d has %lld elements (< 2^31)", what, k, (long long)(B * w)); return MTRSSM_EINVAL; }
-    const float* src = steps > 0 ? table->src[k] + (steps - 1) * w : table->src[k];
+    const float* src = steps > 0 && !base ? table->src[k] + (steps - 1) * w : table->src[k];
     const float* alt = steps > 0 ? nullptr : table->alt[k];
     if (((uintptr_t)src | (uintptr_t)alt | (uintptr_t)table->dst[k]) & 3) { set_error("%s: entry %d is not 4-byte aligned", what, k); return MTRSSM_EINVAL; }
     rows->src[k] = src;
@@ -835,6 +1076,18 @@ int state_save_launch(const MtrssmStateTable* table, int64_t B, int64_t steps, h
   set_last_kernel("mtrssm::state_save_kernel");
   hipLaunchKernelGGL(state_save_kernel, dim3(gx, table->count), dim3(kThreads), 0, s, rows, (long)B);
   return check_launch("state_save");
+}
+
+int state_save_at_launch(const MtrssmStateTable* table, const int32_t* last, int64_t B, int64_t steps, hipStream_t s) {
+  StateRows rows;
+  int gx = 1;
+  if (!last || ((uintptr_t)last & 3)) { set_error("state_save_at: last is null or not 4-byte aligned"); return MTRSSM_EINVAL; }
+  if (steps <= 0) { set_error("state_save_at: steps must be positive (got %lld)", (long long)steps); return MTRSSM_EINVAL; }
+  if (int rc = state_rows_fill("state_save_at", table, B, steps, &rows, &gx, true)) return rc;
+  set_last_kernel("mtrssm::state_save_at_kernel");
+  hipLaunchKernelGGL(state_save_at_kernel, dim3(gx, table->count), dim3(kThreads), 0, s, rows, reinterpret_cast<const int*>(last), (long)B,
+                     (long)steps);
+  return check_launch("state_save_at");
 }
 
 }  // namespace mtrssm

@@ -14,7 +14,9 @@ with the reference's hint; the noise comes from the device generator, so the ran
 
 Beyond the reference: the store keeps every episode at full length, and ``window="random"`` /
 ``"sequential"`` train on windows ``[start, start + T)`` anywhere in it (``mtrssm_episode_gather_window``) -- the latter walks
-an episode chunk by chunk for truncated BPTT with a carried state (``carry.StateCarry``).
+an episode chunk by chunk for truncated BPTT with a carried state (``carry.StateCarry``).  ``lengths``: the
+episodes end at different frames; the store keeps them padded to ``T_full``, a batch row carries ``valid`` live steps and its frames
+past them are exactly zero (``mtrssm_episode_gather_ragged``).
 """
 
 from __future__ import annotations
@@ -89,6 +91,7 @@ class EpisodeDataModuleConfig:
     vision_observation_input_transform: Transform
     vision_observation_target_transform: Transform
     data_root: Path = Path("data")
+    lengths: Tensor | None = None  # host int tensor [N]: valid frames of each episode of the SORTED file list, 1 .. T_full (None: all)
     window: str = "first"  # "first" | "random" | "sequential": which T frames of an episode a batch holds (DeviceEpisodeLoader)
 
     @property
@@ -141,11 +144,19 @@ class _Stream:
         n = next((int(t.n) for t in chain if isinstance(t, TakeFirstN)), None)
         return None if n is None else min(n, t_full)
 
-    def batch(self, idx: Tensor, noise: Tensor | None, start: Tensor | None = None, start_host: list[int] | None = None) -> tuple[Tensor, Tensor]:
+    def batch(self, idx: Tensor, noise: Tensor | None, start: Tensor | None = None, start_host: list[int] | None = None,  # noqa: PLR0913
+              lengths: Tensor | None = None, valid_out: Tensor | None = None, lengths_host: Tensor | None = None) -> tuple[Tensor, Tensor]:
         """``(input, target)`` for the episodes ``idx``; fused when both chains are the YAML's and E % 4 == 0.  ``start`` (int32
-        ``[B]`` on the device, ``start_host`` its host copy): the window ``[start, start + T)`` instead of the first T frames."""
+        ``[B]`` on the device, ``start_host`` its host copy): the window ``[start, start + T)`` instead of the first T frames.
+        ``lengths`` (int32 ``[N]`` on the device): frames at or past an episode's length are exactly zero, ``valid_out`` (int32
+        ``[B]``) receives each row's live steps; ``lengths_host`` is the host copy the unfused path reads."""
         cin, ctg = self.chains
         n_ep, t_full = self.store.shape[:2]
+        if lengths is not None and start is None:
+            msg = "episode lengths need window starts"
+            raise ValueError(msg)
+        if not self.fused and lengths is not None:
+            return self._unfused_ragged(idx, start, start_host, lengths if lengths_host is None else lengths_host, valid_out)
         if not self.fused:  # arbitrary user transforms: applied per episode on the device tensors, then stacked
             if start is None:
                 eps = [self.store[i] for i in idx.tolist()]
@@ -171,11 +182,42 @@ class _Stream:
         if tuple(start.shape) != (b,):
             msg = f"start must have shape ({b},), got {tuple(start.shape)}"
             raise ValueError(msg)
+        if lengths is not None:
+            _lib.check(_lib.TIMERS.call(
+                "mtrssm_episode_gather_ragged", lib.mtrssm_episode_gather_ragged, _lib.ptr(self.store), _lib.raw_ptr(idx), _lib.index_ptr(start),
+                _lib.index_ptr(lengths), _lib.ptr(noise if std is not None else None), n_ep, b, t, t_full, self.event, float(std or 0.0),
+                _lib.ptr(inp), _lib.ptr(tgt), _lib.index_ptr(valid_out), _lib.stream_ptr(self.store.device), nbytes=nbytes),
+                "mtrssm_episode_gather_ragged")
+            return inp, tgt
         _lib.check(_lib.TIMERS.call(
             "mtrssm_episode_gather_window", lib.mtrssm_episode_gather_window, _lib.ptr(self.store), _lib.raw_ptr(idx), _lib.index_ptr(start),
             _lib.ptr(noise if std is not None else None), n_ep, b, t, t_full, self.event, float(std or 0.0), _lib.ptr(inp), _lib.ptr(tgt),
             _lib.stream_ptr(self.store.device), nbytes=nbytes), "mtrssm_episode_gather_window")
         return inp, tgt
+
+    def _unfused_ragged(self, idx: Tensor, start: Tensor, start_host: list[int] | None, lengths: Tensor,
+                        valid_out: Tensor | None) -> tuple[Tensor, Tensor]:
+        """The ragged batch of a stream with arbitrary transforms (or an event size that is no multiple of 4): per episode, as the
+        unfused path always works -- the transforms see the window's frames, zero-padded to T, and the dead frames are zeroed again
+        after them (a noise transform must not reach them)."""
+        t_full = int(self.store.shape[1])
+        steps = self.steps or t_full
+        starts = start.tolist() if start_host is None else start_host
+        lens = lengths.tolist()
+        pairs, valid = [], []
+        for i, s in zip(idx.tolist(), starts, strict=True):
+            s = min(max(int(s), 0), t_full)
+            n = min(max(min(max(int(lens[i]), 0), t_full) - s, 0), steps)
+            window = self.store[i, s: s + n]
+            window = torch.cat([window, window.new_zeros(steps - n, *window.shape[1:])])
+            out = [tf(window)[:steps].clone() for tf in self.transforms]
+            for o in out:
+                o[n:] = 0.0
+            pairs.append(out)
+            valid.append(n)
+        if valid_out is not None:
+            valid_out.copy_(torch.tensor(valid, dtype=torch.int32))
+        return torch.stack([p[0] for p in pairs]), torch.stack([p[1] for p in pairs])
 
 
 def gather_window_reference(store: Tensor, idx: Tensor, start: Tensor, T: int, noise: Tensor | None, std: float | None) -> tuple[Tensor, Tensor]:  # noqa: N803, PLR0913
@@ -190,19 +232,50 @@ def gather_window_reference(store: Tensor, idx: Tensor, start: Tensor, T: int, n
     return target + noise * std, target
 
 
+def gather_ragged_reference(store: Tensor, idx: Tensor, start: Tensor, lengths: Tensor, T: int, noise: Tensor | None,  # noqa: N803, PLR0913
+                            std: float | None) -> tuple[Tensor, Tensor, Tensor]:
+    """``mtrssm_episode_gather_ragged`` in torch: ``target[b, t] = store[idx[b], start[b] + t]`` where ``start[b] + t < lengths[idx[b]]``,
+    else 0; ``input = target + noise * std`` on live frames (mul, then add), 0 on dead ones.  ``start`` is clamped into ``[0, T_full]``,
+    ``lengths`` into ``[0, T_full]``.  Returns ``(input, target, valid)``, ``valid`` int32 ``[B]`` = ``clamp(length - start, 0, T)``."""
+    t_full = store.shape[1]
+    s = start.to(torch.long).clamp(0, t_full)
+    ep = idx.to(torch.long)
+    n = lengths.to(torch.long).clamp(0, t_full)[ep]
+    frames = s.unsqueeze(1) + torch.arange(T, device=store.device)
+    live = frames < n.unsqueeze(1)
+    picked = store[ep.unsqueeze(1), frames.clamp(max=t_full - 1)]
+    shape = (*live.shape, *([1] * (store.dim() - 2)))
+    target = torch.where(live.reshape(shape), picked, torch.zeros_like(picked))
+    valid = (n - s).clamp(0, T).to(torch.int32)
+    if noise is None or std is None:
+        return target.clone(), target, valid
+    return torch.where(live.reshape(shape), target + noise * std, torch.zeros_like(picked)), target, valid
+
+
 class EpisodeBatch(tuple):
     """The 6-tuple of a windowed batch (``len == 6``, indexing as ever) plus where its windows lie: ``start`` (int32 ``[B]``) and
     ``reset`` (bool ``[B]``, True = the row starts an episode) on the device, ``start_host`` / ``reset_host`` their host copies (the
-    loader makes them on the host; ``StateCarry`` checks its rules on ``reset_host`` with no device read-back)."""
+    loader makes them on the host; ``StateCarry`` checks its rules on ``reset_host`` with no device read-back).
+
+    A loader with episode lengths adds ``valid`` (int32 ``[B]`` on the device: the live steps of each row),
+    ``valid_host`` its host copy, ``valid_global`` (int32 ``[B_global]`` on the device: every rank's rows, what the loss is
+    normalised by; ``valid`` itself on one rank) and ``row0``, the rank's first row in the global batch."""
 
     start: Tensor
     reset: Tensor
     start_host: Tensor | None  # (None when the caller handed `DeviceEpisodeLoader.batch` starts that live on the device)
     reset_host: Tensor
+    valid: Tensor | None
+    valid_host: Tensor | None
+    valid_global: Tensor | None
+    row0: int
 
-    def __new__(cls, items: tuple[Tensor, ...], start: Tensor, reset: Tensor, start_host: Tensor | None, reset_host: Tensor) -> EpisodeBatch:  # noqa: PYI034
+    def __new__(cls, items: tuple[Tensor, ...], start: Tensor, reset: Tensor, start_host: Tensor | None, reset_host: Tensor, *,  # noqa: PYI034, PLR0913
+                valid: Tensor | None = None, valid_host: Tensor | None = None, valid_global: Tensor | None = None, row0: int = 0) -> EpisodeBatch:
         self = super().__new__(cls, items)
         self.start, self.reset, self.start_host, self.reset_host = start, reset, start_host, reset_host
+        self.valid, self.valid_host, self.row0 = valid, valid_host, int(row0)
+        self.valid_global = valid if valid_global is None else valid_global
         return self
 
 
@@ -218,7 +291,7 @@ class DeviceEpisodeLoader:
     (the reference's DataLoader keeps it too)."""
 
     def __init__(self, streams: tuple[_Stream, _Stream, _Stream], batch_size: int, *, shuffle: bool, rank: int = 0, world: int = 1,  # noqa: PLR0913
-                 seed: int = 0, window: str = "first") -> None:
+                 seed: int = 0, window: str = "first", lengths: Tensor | None = None) -> None:
         if window not in WINDOWS:
             msg = f"window must be one of {WINDOWS}, got {window!r}"
             raise ValueError(msg)
@@ -238,6 +311,29 @@ class DeviceEpisodeLoader:
                 raise ValueError(msg)
             self.steps = int(steps.pop())
         self.n_chunks = self.t_full // self.steps if window == "sequential" else 1
+        self.lengths_host: Tensor | None = None  # int32 [N] on the host; `lengths` the same on the device
+        self.lengths: Tensor | None = None
+        if lengths is not None:
+            if window == "first":
+                msg = 'episode lengths need window="random" or "sequential"'
+                raise ValueError(msg)
+            self.lengths_host = self._checked_lengths(lengths, self.n, self.t_full)
+            self.lengths = self.lengths_host.to(streams[0].store.device)
+            if window == "sequential":  # every chunk that holds a frame of the longest episode; shorter episodes end earlier
+                self.n_chunks = -(-int(self.lengths_host.max()) // self.steps)
+
+    @staticmethod
+    def _checked_lengths(lengths: Tensor, n: int, t_full: int) -> Tensor:
+        if not isinstance(lengths, Tensor) or lengths.is_cuda or lengths.is_floating_point() or lengths.dtype == torch.bool:
+            msg = f"lengths must be a host integer tensor, got {getattr(lengths, 'dtype', type(lengths))}"
+            raise ValueError(msg)
+        if tuple(lengths.shape) != (n,):
+            msg = f"lengths must have shape ({n},), one entry per episode, got {tuple(lengths.shape)}"
+            raise ValueError(msg)
+        if n and (int(lengths.min()) < 1 or int(lengths.max()) > t_full):
+            msg = f"lengths must lie in [1, {t_full}] (T_full), got min {int(lengths.min())}, max {int(lengths.max())}"
+            raise ValueError(msg)
+        return lengths.to(torch.int32).contiguous()
 
     def __len__(self) -> int:
         return (self.n + self.batch_size - 1) // self.batch_size * self.n_chunks
@@ -245,12 +341,20 @@ class DeviceEpisodeLoader:
     def set_epoch(self, epoch: int) -> None:
         self.epoch = int(epoch)
 
-    def batch(self, idx: Tensor, noise: tuple[Tensor | None, Tensor | None, Tensor | None] = (None, None, None),
-              start: Tensor | None = None, reset: Tensor | None = None) -> tuple[Tensor, ...]:
+    def batch(self, idx: Tensor, noise: tuple[Tensor | None, Tensor | None, Tensor | None] = (None, None, None),  # noqa: PLR0913
+              start: Tensor | None = None, reset: Tensor | None = None, *, valid_host: Tensor | None = None,
+              valid_global: Tensor | None = None, row0: int = 0) -> tuple[Tensor, ...]:
         """The 6-tuple for episode indices ``idx`` (int64, on the device); ``noise`` injects the standard normals.  ``start``: the
         windows' first frames, one per row -- a HOST integer tensor (validated here: ``0 <= start <= T_full - T``) or an int32
         device tensor (not read back: the kernel clamps it into that range); the result is then an ``EpisodeBatch``, ``reset``
-        (a host bool tensor, default all True) riding along."""
+        (a host bool tensor, default all True) riding along.
+
+        A loader with lengths: a host ``start`` may reach ``T_full`` (a chunk may hang over the end of the store), the batch's
+        ``valid`` comes from the gather kernel, and ``valid_host`` / ``valid_global`` (host int32 ``[B]`` / ``[B_global]``, made by
+        ``schedule_ragged``) and ``row0`` ride along."""
+        if start is None and self.lengths is not None:
+            msg = "a loader with lengths needs start= (the windows' first frames)"
+            raise ValueError(msg)
         if start is None:
             pairs = [s.batch(idx, n) for s, n in zip(self.streams, noise, strict=True)]
             return (pairs[0][0], pairs[1][0], pairs[2][0], pairs[0][1], pairs[1][1], pairs[2][1])
@@ -258,55 +362,91 @@ class DeviceEpisodeLoader:
         start_host = None
         if not start.is_cuda:
             start_host = start.to(torch.int32)
-            if start_host.numel() and (int(start_host.min()) < 0 or int(start_host.max()) > self.t_full - self.steps):
-                msg = f"start must lie in [0, {self.t_full - self.steps}] (T_full = {self.t_full}, T = {self.steps}), got {start_host.tolist()}"
+            top = self.t_full - self.steps if self.lengths is None else self.t_full
+            if start_host.numel() and (int(start_host.min()) < 0 or int(start_host.max()) > top):
+                msg = f"start must lie in [0, {top}] (T_full = {self.t_full}, T = {self.steps}), got {start_host.tolist()}"
                 raise ValueError(msg)
             start = start_host.to(dev)
         reset_host = torch.ones(idx.numel(), dtype=torch.bool) if reset is None else reset.to("cpu", torch.bool)
         hosts = None if start_host is None else start_host.tolist()
-        pairs = [s.batch(idx, n, start.contiguous(), hosts) for s, n in zip(self.streams, noise, strict=True)]
+        if self.lengths is None:
+            pairs = [s.batch(idx, n, start.contiguous(), hosts) for s, n in zip(self.streams, noise, strict=True)]
+            items = (pairs[0][0], pairs[1][0], pairs[2][0], pairs[0][1], pairs[1][1], pairs[2][1])
+            return EpisodeBatch(items, start, reset_host.to(dev), start_host, reset_host)
+        valid = torch.empty(idx.numel(), dtype=torch.int32, device=dev)
+        # written by ONE launch: the first stream the gather kernel takes (a batch of unfused streams only: by the per-episode path)
+        writer = next((k for k, s in enumerate(self.streams) if s.fused), 0)
+        pairs = [s.batch(idx, n, start.contiguous(), hosts, self.lengths, valid if k == writer else None, self.lengths_host)
+                 for k, (s, n) in enumerate(zip(self.streams, noise, strict=True))]
         items = (pairs[0][0], pairs[1][0], pairs[2][0], pairs[0][1], pairs[1][1], pairs[2][1])
-        return EpisodeBatch(items, start, reset_host.to(dev), start_host, reset_host)
+        vg = None if valid_global is None else valid_global.to(dev, torch.int32)
+        return EpisodeBatch(items, start, reset_host.to(dev), start_host, reset_host, valid=valid,
+                            valid_host=None if valid_host is None else valid_host.to("cpu", torch.int32), valid_global=vg, row0=row0)
 
-    def _global_batches(self) -> Iterator[tuple[Tensor, Tensor | None]]:
-        """Per global batch of the current epoch: this rank's episode indices (on the device) and, for ``window="random"``, this rank's
-        window starts (host int32) -- both cut from per-GLOBAL-row quantities, so global row g is the same episode and window on
-        any number of ranks.  Advances the epoch counter."""
+    def _global_batches(self) -> Iterator[tuple[Tensor, Tensor | None, Tensor | None, int]]:
+        """Per global batch of the current epoch: this rank's episode indices (on the device), for ``window="random"`` this rank's
+        window starts (host int32), with lengths the episode lengths of ALL the global batch's rows (host int32, padding rows
+        included), and the rank's first global row -- all cut from per-GLOBAL-row quantities, so global row g is the same episode and
+        window on any number of ranks.  Advances the epoch counter."""
         dev = self.streams[0].store.device
         g = torch.Generator().manual_seed(self.seed + self.epoch)
         order = torch.randperm(self.n, generator=g) if self.shuffle else torch.arange(self.n)
+        lens = None if self.lengths_host is None else self.lengths_host[order]  # per position of the epoch's order
         starts = None
         if self.window == "random":  # one start per position of the epoch's order, drawn after the permutation
             starts = torch.randint(0, self.t_full - self.steps + 1, (self.n,), generator=g).to(torch.int32)
+            if lens is not None:
+                # uniform on [0, max(len - T, 0)] per row: a full-length episode keeps the draw above (all lengths T_full give the
+                # starts of a loader without lengths); a shorter one scales a second uniform, drawn AFTER it from the same generator
+                # (a modulo of the first draw would favour the low starts wherever the ranges do not divide)
+                room = (lens - self.steps).clamp(min=0).to(torch.int64) + 1
+                second = (torch.rand(self.n, generator=g, dtype=torch.float64) * room).to(torch.int64).clamp(max=room - 1)
+                starts = torch.where(room == self.t_full - self.steps + 1, starts.to(torch.int64), second).to(torch.int32)
         order = order.to(dev)
         self.epoch += 1
         for lo in range(0, self.n, self.batch_size):
             rows = order[lo: lo + self.batch_size]
             st = None if starts is None else starts[lo: lo + self.batch_size]
+            ln = None if lens is None else lens[lo: lo + self.batch_size]
+            row0 = 0
             if self.world > 1:
                 pad = (-rows.numel()) % self.world
                 if pad:
                     wrap = torch.arange(pad) % self.n
                     rows = torch.cat([rows, order[wrap.to(dev)]])
                     st = None if st is None else torch.cat([st, starts[wrap]])
+                    ln = None if ln is None else torch.cat([ln, lens[wrap]])
                 per = rows.numel() // self.world  # the CONTIGUOUS block FlatDataParallel.shard / GlobalRowNoise.draw give this rank
-                rows = rows[self.rank * per: (self.rank + 1) * per]
-                st = None if st is None else st[self.rank * per: (self.rank + 1) * per]
-            yield rows.contiguous(), st
+                row0 = self.rank * per
+                rows = rows[row0: row0 + per]
+                st = None if st is None else st[row0: row0 + per]
+            yield rows.contiguous(), st, ln, row0
 
     def schedule(self) -> Iterator[tuple[Tensor, Tensor | None, Tensor | None]]:
         """``(episode indices, start, reset)`` of this rank, batch by batch, for the current epoch; ``start`` (int32) and ``reset``
         (bool) are HOST tensors, None in ``"first"`` mode.  ``"sequential"``: a group of episodes comes ``n_chunks`` times in a row,
         chunk c at ``start = c * T``, ``reset`` on chunk 0."""
-        for rows, st in self._global_batches():
+        for rows, start, reset, _, _ in self.schedule_ragged():
+            yield rows, start, reset
+
+    def schedule_ragged(self) -> Iterator[tuple[Tensor, Tensor | None, Tensor | None, Tensor | None, int]]:
+        """``schedule`` plus, for a loader with lengths, ``valid_global`` (host int32 ``[B_global]``: the live steps
+        ``clamp(len - start, 0, T)`` of every rank's rows, None without lengths) and ``row0``, this rank's first global row: its own
+        ``valid`` is ``valid_global[row0 : row0 + B]``.  ``"sequential"``: ``n_chunks = ceil(max(len) / T)``, a row whose episode is
+        over has ``valid = 0``."""
+        for rows, st, ln, row0 in self._global_batches():
             b = rows.numel()
             if self.window == "first":
-                yield rows, None, None
+                yield rows, None, None, None, row0
             elif self.window == "random":
-                yield rows, st, torch.ones(b, dtype=torch.bool)
+                valid = None
+                if ln is not None:  # (st is this rank's cut; the global rows' starts are recomputed from the same per-row rule)
+                    valid = ln.clamp(max=self.steps).to(torch.int32)  # start <= len - T when len >= T, else 0: min(len, T) live steps
+                yield rows, st, torch.ones(b, dtype=torch.bool), valid, row0
             else:
                 for c in range(self.n_chunks):
-                    yield rows, torch.full((b,), c * self.steps, dtype=torch.int32), torch.full((b,), c == 0, dtype=torch.bool)
+                    valid = None if ln is None else (ln - c * self.steps).clamp(0, self.steps).to(torch.int32)
+                    yield rows, torch.full((b,), c * self.steps, dtype=torch.int32), torch.full((b,), c == 0, dtype=torch.bool), valid, row0
 
     def index_batches(self) -> Iterator[Tensor]:
         """This rank's episode indices, batch by batch, for the current epoch (then the epoch counter advances)."""
@@ -314,8 +454,15 @@ class DeviceEpisodeLoader:
             yield rows
 
     def __iter__(self) -> Iterator[tuple[Tensor, ...]]:
-        for rows, start, reset in self.schedule():
-            yield self.batch(rows) if start is None else self.batch(rows, start=start, reset=reset)
+        for rows, start, reset, valid_global, row0 in self.schedule_ragged():
+            if start is None:
+                yield self.batch(rows)
+            elif valid_global is None:
+                yield self.batch(rows, start=start, reset=reset)
+            else:
+                # (one rank: the gather's `valid` IS the global batch's, no copy of the host's to the device)
+                yield self.batch(rows, start=start, reset=reset, valid_host=valid_global[row0: row0 + rows.numel()],
+                                 valid_global=valid_global if self.world > 1 else None, row0=row0)
 
 
 class EpisodeDataModule(_Base):
@@ -376,6 +523,28 @@ class EpisodeDataModule(_Base):
         t = min(e.shape[0] for e in eps)  # ragged episode lengths: the common prefix (TakeFirstN cuts further)
         return torch.stack([e[:t] for e in eps]).to(self.device)
 
+    def _stack_padded(self, lists: list[list[Path]], lengths: Tensor) -> list[Tensor]:
+        """With ``config.lengths``: the three stores of one side of the split, every episode zero-padded to the side's longest file
+        (each file is read once).  Checked file by file: the three streams of an episode hold the same number of frames, and its
+        length does not claim more of them (a larger length would turn padding zeros into live frames)."""
+        eps = [[load_tensor(p).to(torch.float32) for p in paths] for paths in lists]
+        for i, trio in enumerate(zip(*eps, strict=True)):
+            frames = sorted({int(e.shape[0]) for e in trio})
+            if len(frames) != 1:
+                msg = f"{lists[0][i].name}: the action, audio and vision files of this episode hold {frames} frames, not the same number"
+                raise ValueError(msg)
+            if not 1 <= int(lengths[i]) <= frames[0]:
+                msg = f"config.lengths gives {lists[0][i].name} {int(lengths[i])} frames, but the file holds {frames[0]} (need 1 .. {frames[0]})"
+                raise ValueError(msg)
+        t = max(int(e.shape[0]) for e in eps[0])
+        return [torch.stack([torch.cat([e, e.new_zeros(t - e.shape[0], *e.shape[1:])]) for e in stream]).to(self.device) for stream in eps]
+
+    def _lengths(self, train: bool) -> Tensor | None:  # noqa: FBT001
+        """The configured lengths of one side of the split: cut by the function that cuts the sorted path lists (None: none configured)."""
+        if self.config.lengths is None:
+            return None
+        return split_path_list(self.config.lengths, 0.8)[0 if train else 1]
+
     def setup(self, stage: str = "fit") -> None:
         c = self.config
         d = c.get_effective_processed_data_dir(c.get_observation_glob_patterns())
@@ -383,24 +552,35 @@ class EpisodeDataModule(_Base):
         if not all(lists) or len({len(x) for x in lists}) != 1:
             msg = f"{d}: need the same number (> 0) of act*, audio_obs* and vision_obs* files, found {[len(x) for x in lists]}"
             raise FileNotFoundError(msg)
+        lens = c.lengths
+        if lens is not None and (not isinstance(lens, Tensor) or lens.is_floating_point() or tuple(lens.shape) != (len(lists[0]),)):
+            msg = (f"config.lengths must be a host integer tensor of shape ({len(lists[0])},), one entry per episode file, "
+                   f"got {getattr(lens, 'shape', type(lens))}")
+            raise ValueError(msg)
         splits = [split_path_list(x, 0.8) for x in lists]
         tr = ((c.action_input_transform, c.action_target_transform), (c.audio_observation_input_transform, c.audio_observation_target_transform),
               (c.vision_observation_input_transform, c.vision_observation_target_transform))
+
+        def streams(side: int) -> tuple[_Stream, _Stream, _Stream]:
+            paths = [s[side] for s in splits]
+            stores = [self._stack(p) for p in paths] if lens is None else self._stack_padded(paths, self._lengths(side == 0))
+            return tuple(_Stream(store, *t) for store, t in zip(stores, tr, strict=True))
+
         if stage == "fit" and splits[0][0]:
-            self.train_streams = tuple(_Stream(self._stack(s[0]), *t) for s, t in zip(splits, tr, strict=True))
+            self.train_streams = streams(0)
         if splits[0][1]:
-            self.val_streams = tuple(_Stream(self._stack(s[1]), *t) for s, t in zip(splits, tr, strict=True))
+            self.val_streams = streams(1)
 
     def train_dataloader(self) -> DeviceEpisodeLoader:
         if self.train_streams is None:
             msg = "train_dataset is not set. Call setup() first."
             raise RuntimeError(msg)
         return DeviceEpisodeLoader(self.train_streams, self.config.batch_size, shuffle=True, rank=self.rank, world=self.world,
-                                   window=self.config.window)
+                                   window=self.config.window, lengths=self._lengths(True))
 
     def val_dataloader(self) -> DeviceEpisodeLoader:
         if self.val_streams is None:
             msg = "val_dataset is not set. Call setup() first."
             raise RuntimeError(msg)
         return DeviceEpisodeLoader(self.val_streams, self.config.batch_size, shuffle=False, rank=self.rank, world=self.world,
-                                   window=self.config.window)
+                                   window=self.config.window, lengths=self._lengths(False))

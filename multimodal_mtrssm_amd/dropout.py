@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import copy
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import torch
 from torch import Tensor
@@ -26,7 +27,9 @@ from multimodal_mtrssm_amd import _lib
 class StepMask:
     """What one masked train step reads, all on the device: ``codes`` int32 ``[B, T]`` (bit 0 audio, bit 1 vision),
     ``present_audio`` / ``present_vision`` float32 ``[B * T]`` in {0, 1}, ``mask0`` bool ``[B, 2]`` (the t = 0 frame),
-    ``count_audio`` / ``count_vision`` float32 scalars: what each reconstruction sum is divided by."""
+    ``count_audio`` / ``count_vision`` float32 scalars: what each reconstruction sum is divided by.  A ragged batch's record
+    (``ragged_step_mask``) also carries ``live`` float32 ``[B * T]`` in {0, 1}, ``count_live`` (what the KL sums
+    are divided by) and ``last`` int32 ``[B]`` (the last live step, -1 for an empty row: where the carry is saved from)."""
 
     codes: Tensor
     present_audio: Tensor
@@ -34,6 +37,9 @@ class StepMask:
     mask0: Tensor
     count_audio: Tensor
     count_vision: Tensor
+    live: Tensor | None = None
+    count_live: Tensor | None = None
+    last: Tensor | None = None
 
     @classmethod
     def from_mask(cls, mask: Tensor) -> StepMask:
@@ -144,4 +150,84 @@ class ModalityDropout:
         return DropoutSample(codes, pa, pv, mask0, counts, world)
 
 
-__all__ = ["DropoutSample", "ModalityDropout", "StepMask"]
+class RaggedMask(NamedTuple):
+    """``ragged_reference``'s result over all rows: ``mask`` bool ``[B, T, 2]``, ``live`` bool ``[B, T]``, ``last`` int32 ``[B]``,
+    ``counts`` float32 ``[3]`` (present audio frames, present vision frames, live steps)."""
+
+    mask: Tensor
+    live: Tensor
+    last: Tensor
+    counts: Tensor
+
+    @property
+    def codes(self) -> Tensor:
+        return (self.mask[..., 0].to(torch.int32) + 2 * self.mask[..., 1].to(torch.int32)).contiguous()
+
+
+def _checked_valid(valid: Tensor, steps: int) -> None:
+    if not isinstance(valid, Tensor) or valid.dtype != torch.int32 or valid.dim() != 1 or valid.numel() == 0:
+        msg = f"valid must be an int32 [B_global] tensor, got {getattr(valid, 'dtype', type(valid))} {tuple(getattr(valid, 'shape', ()))}"
+        raise ValueError(msg)
+    if steps < 1:
+        msg = f"need steps >= 1, got {steps}"
+        raise ValueError(msg)
+
+
+def ragged_reference(valid: Tensor, u: Tensor | None, steps: int, md: ModalityDropout | None = None) -> RaggedMask:
+    """The rule of a ragged batch in torch (``mtrssm_step_mask_ragged`` is the kernel): step ``(b, t)`` is live iff
+    ``t < clamp(valid[b], 0, steps)``; a modality is present iff the step is live AND (``u`` None: no dropout, or ``md.reference``
+    says present -- its t = 0 fix-up is applied before the AND).  A dead step has code 0."""
+    _checked_valid(valid, steps)
+    n = valid.to(torch.long).clamp(0, steps)
+    live = torch.arange(steps, device=valid.device) < n.unsqueeze(1)
+    if u is None:
+        mask = live.unsqueeze(-1).expand(-1, -1, 2).clone()
+    else:
+        if md is None:
+            msg = "uniforms need the ModalityDropout whose rule they feed"
+            raise ValueError(msg)
+        if u.shape[0] != valid.numel():
+            msg = f"u has {u.shape[0]} rows, valid {valid.numel()}"
+            raise ValueError(msg)
+        mask = md.reference(u, steps) & live.unsqueeze(-1)
+    counts = torch.stack([mask[..., 0].sum(), mask[..., 1].sum(), live.sum()]).to(torch.float32)
+    return RaggedMask(mask, live, (n - 1).to(torch.int32), counts)
+
+
+def ragged_step_mask(valid: Tensor, u: Tensor | None, steps: int, md: ModalityDropout | None = None, *, world: int = 1,
+                     rank: int = 0) -> StepMask:
+    """One ``mtrssm_step_mask_ragged`` launch on torch's current stream: the ``StepMask`` of rank ``rank``'s rows of the global batch
+    ``valid`` (int32 ``[B_global]``, on the device) describes.  The three counts are the GLOBAL batch's, divided by ``world`` as
+    ``DropoutSample.step_mask`` does: the mean over ranks is the global batch's loss."""
+    _checked_valid(valid, steps)
+    if world < 1 or not 0 <= rank < world or valid.numel() % world:
+        msg = f"need 0 <= rank < world and a global batch that is a multiple of world, got rank {rank}, world {world}, {valid.numel()} rows"
+        raise ValueError(msg)
+    span, pa, pv = 1, 0.0, 0.0
+    if u is not None:
+        if md is None:
+            msg = "uniforms need the ModalityDropout whose rule they feed"
+            raise ValueError(msg)
+        md._checked(u, steps, world, rank)  # noqa: SLF001
+        if u.shape[0] != valid.numel():
+            msg = f"u has {u.shape[0]} rows, valid {valid.numel()}"
+            raise ValueError(msg)
+        u = u.contiguous()
+        span, pa, pv = md.span, md.p_audio, md.p_vision
+    valid = valid.contiguous()
+    dev = valid.device
+    local = valid.numel() // world
+    codes = torch.empty(local, steps, dtype=torch.int32, device=dev)
+    planes = [torch.empty(local * steps, dtype=torch.float32, device=dev) for _ in range(3)]
+    mask0 = torch.empty(local, 2, dtype=torch.bool, device=dev)
+    last = torch.empty(local, dtype=torch.int32, device=dev)
+    counts = torch.empty(3, dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().mtrssm_step_mask_ragged(_lib.index_ptr(valid), _lib.ptr(u), valid.numel(), steps, span, pa, pv, rank * local, local,
+                                                   _lib.index_ptr(codes), _lib.ptr(planes[0]), _lib.ptr(planes[1]), _lib.ptr(planes[2]),
+                                                   _lib.raw_ptr(mask0), _lib.index_ptr(last), _lib.ptr(counts), _lib.stream_ptr(dev)),
+               "mtrssm_step_mask_ragged")
+    norm = counts if world == 1 else counts / float(world)
+    return StepMask(codes, planes[0], planes[1], mask0, norm[0], norm[1], planes[2], norm[2], last)
+
+
+__all__ = ["DropoutSample", "ModalityDropout", "RaggedMask", "StepMask", "ragged_reference", "ragged_step_mask"]

@@ -28,6 +28,11 @@ Masked steps are captured in one of two modes, fixed for 
 batch's ``reset_host`` and copies ``batch.reset`` into a fixed buffer; ``mtrssm_state_select`` and ``mtrssm_state_save`` are inside
 the graph and read ``reset`` on the device, so ONE graph serves the first chunk of an episode and every later one.
 
+``ragged=True`` captures the step over episodes of different lengths, alone or with ``modality_dropout=`` and
+``state_carry=``: batches carry ``valid`` (an ``EpisodeBatch`` of a loader with lengths); ``step`` checks on the host that no row
+resets with nothing at t = 0 and copies ``valid_global`` into a fixed buffer; the mask launch, the counted ELBO epilogue and the
+save at each row's last live step are inside the graph.  A graph is ragged or not for life.
+
 Observations that are ``None`` stay eager-only: a capture cannot drop an encoder per step.
 
 With more than one rank the gradient all-reduce (RCCL) and the optimizer run eagerly after the replay: the
@@ -41,7 +46,7 @@ from torch import Tensor
 
 from multimodal_mtrssm_amd import conv, scan
 from multimodal_mtrssm_amd.carry import StateCarry
-from multimodal_mtrssm_amd.core import _check_modality_mask
+from multimodal_mtrssm_amd.core import _check_modality_mask, check_ragged_rows
 from multimodal_mtrssm_amd.dropout import ModalityDropout, StepMask
 from multimodal_mtrssm_amd.optim import FlatAdamW, FlatParameters
 from multimodal_mtrssm_amd.parallel import FlatDataParallel, GlobalRowNoise
@@ -73,7 +78,8 @@ class CapturedTrainStep:
 
     def __init__(self, model: torch.nn.Module, flat: FlatParameters, opt: FlatAdamW, dp: FlatDataParallel,  # noqa: PLR0913
                  batch: tuple[Tensor, ...], noise: GlobalRowNoise, *, warmup: int = 3,
-                 modality_dropout: ModalityDropout | None = None, masked: bool = False, state_carry: StateCarry | None = None) -> None:
+                 modality_dropout: ModalityDropout | None = None, masked: bool = False, state_carry: StateCarry | None = None,
+                 ragged: bool = False) -> None:
         if state_carry is not None and not isinstance(state_carry, StateCarry):
             msg = f"state_carry must be a StateCarry, got {type(state_carry).__name__}"
             raise ValueError(msg)
@@ -83,7 +89,10 @@ class CapturedTrainStep:
         if modality_dropout is not None and not isinstance(modality_dropout, ModalityDropout):
             msg = f"modality_dropout must be a ModalityDropout, got {type(modality_dropout).__name__}"
             raise ValueError(msg)
-        self.model, self.masked, self.dropout = model, bool(masked), modality_dropout
+        if ragged and masked:
+            msg = "ragged=True builds its masks from the batch's lengths: it does not combine with masked=True"
+            raise ValueError(msg)
+        self.model, self.masked, self.dropout, self.ragged = model, bool(masked), modality_dropout, bool(ragged)
         self._check_batch_kind(batch)
         self.flat, self.opt, self.dp, self.noise = flat, opt, dp, noise
         b, t = batch[0].shape[:2]
@@ -98,6 +107,13 @@ class CapturedTrainStep:
         if state_carry is not None:
             state_carry.check("train", b, torch.ones(b, dtype=torch.bool))  # (the batch size; the warm-up resets every row)
             self.reset = torch.ones(b, dtype=torch.bool, device=dev)
+        self.valid_global: Tensor | None = None
+        if self.ragged:
+            check_ragged_rows(self._valid_host(batch), None)  # (the warm-up resets every row)
+            if batch.valid_global.numel() != b * dp.world:
+                msg = f"the batch's valid_global has {batch.valid_global.numel()} rows, the global batch {b} x {dp.world}"
+                raise ValueError(msg)
+            self.valid_global = batch.valid_global.to(dev, torch.int32).clone()
         self.shapes = dict(model.noise_shapes(b, t))
         if self.dropout is not None:
             self.dropout = self.dropout.for_rank(dp.world, dp.rank)
@@ -124,6 +140,21 @@ class CapturedTrainStep:
             raise ValueError(msg)
         if not self.masked and self.dropout is None:
             _refuse_modality_mask(self.model, batch)
+        has_valid = getattr(batch, "valid", None) is not None
+        if self.ragged and not has_valid:
+            msg = "this CapturedTrainStep was captured with ragged=True: every batch must carry valid (an EpisodeBatch of a loader with lengths)"
+            raise ValueError(msg)
+        if not self.ragged and has_valid:
+            msg = "this CapturedTrainStep was captured without ragged=True: it does not take a batch that carries valid"
+            raise ValueError(msg)
+
+    @staticmethod
+    def _valid_host(batch: tuple[Tensor, ...]) -> Tensor:
+        valid_host = getattr(batch, "valid_host", None)
+        if valid_host is None:
+            msg = "a ragged CapturedTrainStep needs the batch's valid_host (the loader makes it): the t = 0 rule is checked on the host"
+            raise ValueError(msg)
+        return valid_host
 
     # the captured region -------------------------------------------------------------------------
     def _body(self) -> list[str]:
@@ -131,6 +162,9 @@ class CapturedTrainStep:
         carry = None if self.carry is None else (self.carry, "train", self.reset)  # (its host rules were checked by step())
         if self.masked:  # (validated on the host by step(); codes, planes and counts are derived here, inside the capture)
             out = self.model._elbo_step(self.batch, self.uniforms, StepMask.from_mask(self.mask), carry)  # noqa: SLF001
+        elif self.ragged:  # (the host rule was checked by step(); lengths AND dropout in one launch, inside the capture)
+            sm = self.model._ragged_step_mask(self.batch, self.uniforms, self.dropout, self.valid_global, self.dp.world, self.dp.rank)  # noqa: SLF001
+            out = self.model._elbo_step(self.batch, self.uniforms, sm, carry)  # noqa: SLF001
         elif carry is not None:
             sm = self.model._step_mask(self.batch, self.uniforms, None, self.dropout)  # noqa: SLF001
             out = self.model._elbo_step(self.batch, self.uniforms, sm, carry)  # noqa: SLF001
@@ -208,6 +242,11 @@ class CapturedTrainStep:
             self._check_batch_kind(batch)
             if self.masked:  # the t = 0 check reads the mask back: here, before the replay, never inside the capture
                 _check_modality_mask(batch[6], *self.batch[0].shape[:2], self.batch[0].device, first_step=True)
+        if self.ragged and batch is not None:  # host rule first: a row that resets with no valid frame raises before anything is replayed
+            check_ragged_rows(self._valid_host(batch), None if self.carry is None else getattr(batch, "reset_host", None))
+            if tuple(batch.valid_global.shape) != tuple(self.valid_global.shape):
+                msg = f"valid_global must have shape {tuple(self.valid_global.shape)}, got {tuple(batch.valid_global.shape)}"
+                raise ValueError(msg)
         if self.carry is not None:  # host rules first: a partial reset into an empty carry raises before anything is replayed
             reset = getattr(batch, "reset", None)
             if reset is None:
@@ -220,6 +259,8 @@ class CapturedTrainStep:
                 dst.copy_(src)
         if batch is not None and self.masked and batch[6] is not self.mask:
             self.mask.copy_(batch[6])
+        if batch is not None and self.ragged:
+            self.valid_global.copy_(batch.valid_global)
         self.noise.draw(self.shapes, out=self.uniforms)
         self.opt.sync_lr()
         assert self.graph is not None
