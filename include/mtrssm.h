@@ -611,6 +611,26 @@ int mtrssm_episode_gather_window(const float* store, const int64_t* idx, const i
 int mtrssm_episode_gather_ragged(const float* store, const int64_t* idx, const int32_t* start, const int32_t* lengths, const float* noise,
                                  int64_t n_episodes, int64_t B, int64_t T, int64_t Tfull, int64_t E, float std_, float* input, float* target,
                                  int32_t* valid_out, void* stream);
+/* The three gathers above with the standard normals GENERATED in the kernel instead of read from `noise`:
+ * start == NULL: the first T frames (mtrssm_episode_gather); start alone: windows, start[b] clamped into [0, Tfull - T]
+ * (mtrssm_episode_gather_window); start and lengths: ragged, clamps, zeros on dead frames and valid_out (may be NULL) as
+ * mtrssm_episode_gather_ragged.  target is bitwise what those entries write; input = target + z * std, mul then add, each rounded.
+ * z is a pure function of (key, epoch, episode, absolute frame, element), independent of the batch row, B and the window start.
+ * For the four elements 4 e4 .. 4 e4 + 3 of frame f = clamped start[b] + t (f = t without start) of episode idx[b]:
+ *   x[0..3] = Philox4x32-10(counter = (e4, f, idx[b] & 0xffffffff, epoch), key = (key0, key1))
+ *             (Salmon et al., SC'11: multipliers 0xD2511F53 on counter word 0 and 0xCD9E8D57 on word 2, the key advancing by
+ *             0x9E3779B9, 0xBB67AE85 between the ten rounds; Random123's philox4x32_R(10, ...))
+ *   pair (x0, x1) -> z[4 e4], z[4 e4 + 1]; pair (x2, x3) -> z[4 e4 + 2], z[4 e4 + 3]; for a pair (xa, xb), in fp32:
+ *     u1 = ((xa >> 8) + 1) * 2^-24 in (0, 1]    u2 = (xb >> 8) * 2^-24 in [0, 1)    r = sqrt(-2 log(u1))
+ *     z_first = r * cos(2 pi u2)                z_second = r * sin(2 pi u2)
+ * (log, sqrt, sincospi are the accurate device functions: a second implementation agrees to a few ulp, not bitwise.)
+ * dataset.stream_key gives the loader's keys: key0 = seed & 0xffffffff, key1 = (seed >> 32) ^ (0x9E3779B9 * (stream + 1) mod 2^32),
+ * stream = 0, 1, 2 for action, audio, vision; epoch = the loader's epoch counter (0 for a fixed stream).
+ * lengths without start, valid_out without lengths, E % 4 != 0, E / 4 >= 2^32 or a misaligned buffer return -1; a dead frame
+ * issues no load and no generator work. */
+int mtrssm_episode_gather_seeded(const float* store, const int64_t* idx, const int32_t* start, const int32_t* lengths, int32_t* valid_out,
+                                 uint32_t key0, uint32_t key1, uint32_t epoch, int64_t n_episodes, int64_t B, int64_t T, int64_t Tfull,
+                                 int64_t E, float std_, float* input, float* target, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Carried state of truncated BPTT: the initial state of a train step is, per batch row, either the

@@ -31,6 +31,8 @@ int state_save_launch(const MtrssmStateTable*, int64_t, int64_t, hipStream_t);
 int state_save_at_launch(const MtrssmStateTable*, const int32_t*, int64_t, int64_t, hipStream_t);
 int episode_gather_ragged_launch(const float*, const int64_t*, const int32_t*, const int32_t*, const float*, int64_t, int64_t, int64_t, int64_t,
                                  int64_t, float, float*, float*, int32_t*, hipStream_t);
+int episode_gather_seeded_launch(const float*, const int64_t*, const int32_t*, const int32_t*, int32_t*, uint32_t, uint32_t, uint32_t, int64_t, int64_t,
+                                 int64_t, int64_t, int64_t, float, float*, float*, hipStream_t);
 int step_mask_ragged_launch(const int32_t*, const float*, int64_t, int64_t, int64_t, float, float, int64_t, int64_t, int32_t*, float*, float*, float*,
                             unsigned char*, int32_t*, float*, hipStream_t);
 int elbo_combine_counted_fwd_launch(const float*, const float*, const float*, const float*, const float*, const float*, int64_t, float, float, float*,
@@ -269,6 +271,12 @@ MTRSSM_API int mtrssm_episode_gather_ragged(const float* store, const int64_t* i
                                             const float* noise, int64_t n_episodes, int64_t B, int64_t T, int64_t Tfull, int64_t E, float std_,
                                             float* input, float* target, int32_t* valid_out, void* stream) {
   return episode_gather_ragged_launch(store, idx, start, lengths, noise, n_episodes, B, T, Tfull, E, std_, input, target, valid_out,
+                                      static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_episode_gather_seeded(const float* store, const int64_t* idx, const int32_t* start, const int32_t* lengths,
+                                            int32_t* valid_out, uint32_t key0, uint32_t key1, uint32_t epoch, int64_t n_episodes, int64_t B,
+                                            int64_t T, int64_t Tfull, int64_t E, float std_, float* input, float* target, void* stream) {
+  return episode_gather_seeded_launch(store, idx, start, lengths, valid_out, key0, key1, epoch, n_episodes, B, T, Tfull, E, std_, input, target,
                                       static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int mtrssm_step_mask_ragged(const int32_t* valid, const float* u, int64_t b_global, int64_t steps, int64_t span, float p_audio,

@@ -945,6 +945,125 @@ int episode_gather_ragged_launch(const float* store, const int64_t* idx, const i
   return check_launch("episode_gather_ragged");
 }
 
+// The three gathers above with the standard normals made in the kernel: the noise of a frame is a pure
+// function of (key, epoch, episode, absolute frame, element), never stored, whatever row of whatever batch the frame lands in.
+//   x[0..3] = Philox4x32-10(counter = (e4, frame, low 32 bits of episode, epoch), key = (key0, key1))
+//   two Box-Muller pairs, (x0, x1) -> elements 4 e4 + 0, 1 and (x2, x3) -> elements 4 e4 + 2, 3:
+//     u1 = ((xa >> 8) + 1) * 2^-24 in (0, 1], u2 = (xb >> 8) * 2^-24 in [0, 1), r = sqrtf(-2 logf(u1)), z = r cos(2 pi u2), r sin(2 pi u2)
+// Philox as Salmon et al. (SC'11) define it: per round (c0, c1, c2, c3) <- (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1,
+// lo(M0 c0)), the key advancing by the Weyl constants between rounds.
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&out)[4]) {
+#pragma unroll
+  for (int round = 0; round < 10; ++round) {
+    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  out[0] = c0, out[1] = c1, out[2] = c2, out[3] = c3;
+}
+
+__device__ __forceinline__ void box_muller(unsigned xa, unsigned xb, float& z0, float& z1) {
+#pragma clang fp contract(off)
+  const float u1 = (float)((xa >> 8) + 1u) * 0x1p-24f;  // (0, 1]: 24-bit integers, exact in fp32
+  const float u2 = (float)(xb >> 8) * 0x1p-24f;         // [0, 1)
+  const float r = sqrtf(-2.f * logf(u1));
+  float sn, cs;
+  sincospif(2.f * u2, &sn, &cs);  // (2 u2 is exact: the argument reduction sees the 24-bit fraction itself)
+  z0 = r * cs;
+  z1 = r * sn;
+}
+
+// MODE 0: the first T frames; 1: windows (start clamped as episode_gather_window_kernel clamps it); 2: ragged (start, lengths, idx
+// clamped and valid_out written as episode_gather_ragged_kernel does; a dead frame issues no load and no generator work).
+template <int MODE>
+__global__ __launch_bounds__(kThreads) void episode_gather_seeded_kernel(
+    const float* __restrict__ store, const long* __restrict__ idx, const int* __restrict__ start, const int* __restrict__ lengths,
+    unsigned key0, unsigned key1, unsigned epoch, long n_episodes, long B, long T, long Tfull, long E4, float std_,
+    float* __restrict__ input, float* __restrict__ target, int* __restrict__ valid_out) {
+#pragma clang fp contract(off)  // (as episode_gather_kernel: mul then add, each rounded)
+  const long per_b = T * E4;
+  const long total = B * per_b;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long b = i / per_b, r = i - b * per_b;  // r = t * E4 + e4
+    const long t = r / E4, e4 = r - t * E4;
+    long ep = idx[b], s = 0;
+    bool on = true;
+    if constexpr (MODE == 1) {
+      const long last = Tfull - T;
+      s = start[b];
+      s = s < 0 ? 0 : (s > last ? last : s);
+    }
+    if constexpr (MODE == 2) {
+      s = start[b];
+      s = s < 0 ? 0 : (s > Tfull ? Tfull : s);
+      ep = ep < 0 ? 0 : (ep >= n_episodes ? n_episodes - 1 : ep);
+      long len = lengths[ep];
+      len = len < 0 ? 0 : (len > Tfull ? Tfull : len);
+      on = s + t < len;  // (< Tfull: the read below stays inside the episode)
+      if (valid_out && r == 0) {
+        const long n = len - s;
+        valid_out[b] = (int)(n < 0 ? 0 : (n > T ? T : n));
+      }
+    }
+    float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (on) x = reinterpret_cast<const float4*>(store)[(ep * Tfull + s) * E4 + r];
+    if (target) reinterpret_cast<float4*>(target)[i] = x;
+    if (input) {
+      float4 y = x;
+      if (on) {
+        unsigned w[4];
+        philox4x32_10((unsigned)e4, (unsigned)(s + t), (unsigned)ep, epoch, key0, key1, w);
+        float4 n;
+        box_muller(w[0], w[1], n.x, n.y);
+        box_muller(w[2], w[3], n.z, n.w);
+        const float px = n.x * std_, py = n.y * std_, pz = n.z * std_, pw = n.w * std_;
+        y.x = x.x + px;
+        y.y = x.y + py;
+        y.z = x.z + pz;
+        y.w = x.w + pw;
+      }
+      reinterpret_cast<float4*>(input)[i] = y;
+    }
+  }
+}
+
+int episode_gather_seeded_launch(const float* store, const int64_t* idx, const int32_t* start, const int32_t* lengths, int32_t* valid_out,
+                                 uint32_t key0, uint32_t key1, uint32_t epoch, int64_t n_episodes, int64_t B, int64_t T, int64_t Tfull,
+                                 int64_t E, float std_, float* input, float* target, hipStream_t s) {
+  if (!store || !idx || (!input && !target) || n_episodes <= 0 || B <= 0 || T <= 0 || Tfull < T || E <= 0) {
+    set_error("episode_gather_seeded: bad argument (need 0 < T <= Tfull, B, E > 0, an output)");
+    return MTRSSM_EINVAL;
+  }
+  if (lengths && !start) { set_error("episode_gather_seeded: lengths without start (a ragged batch needs its windows' starts)"); return MTRSSM_EINVAL; }
+  if (valid_out && !lengths) { set_error("episode_gather_seeded: valid_out without lengths"); return MTRSSM_EINVAL; }
+  if (E % 4) { set_error("episode_gather_seeded: the event size %ld must be a multiple of 4 floats", (long)E); return MTRSSM_EINVAL; }
+  if (E / 4 > 0xffffffffL) { set_error("episode_gather_seeded: the event size %ld exceeds the 32-bit element counter", (long)E); return MTRSSM_EINVAL; }
+  if (((uintptr_t)store | (uintptr_t)input | (uintptr_t)target) & 15) {
+    set_error("episode_gather_seeded: buffers must be 16-byte aligned");
+    return MTRSSM_EINVAL;
+  }
+  if (((uintptr_t)start | (uintptr_t)lengths | (uintptr_t)valid_out) & 3) {
+    set_error("episode_gather_seeded: start, lengths and valid_out must be 4-byte aligned");
+    return MTRSSM_EINVAL;
+  }
+  set_last_kernel("mtrssm::episode_gather_seeded_kernel");
+#define MTRSSM_SEEDED(MODE)                                                                                                                \
+  hipLaunchKernelGGL(episode_gather_seeded_kernel<MODE>, dim3(grid_for(B * T * E / 4)), dim3(kThreads), 0, s, store,                        \
+                     reinterpret_cast<const long*>(idx), reinterpret_cast<const int*>(start), reinterpret_cast<const int*>(lengths), key0, \
+                     key1, epoch, (long)n_episodes, (long)B, (long)T, (long)Tfull, (long)(E / 4), std_, input, target,                     \
+                     reinterpret_cast<int*>(valid_out))
+  if (lengths) MTRSSM_SEEDED(2);
+  else if (start) MTRSSM_SEEDED(1);
+  else MTRSSM_SEEDED(0);
+#undef MTRSSM_SEEDED
+  return check_launch("episode_gather_seeded");
+}
+
 // ------------------------------------------------------------------------------------------------
 // Carried state of truncated BPTT: up to MTRSSM_STATE_MAX row-major [B, width] tensors per launch, the
 // table of pointers passed by value.  For entry k and row b:

@@ -16,7 +16,9 @@ Beyond the reference: the store keeps every episode at fu
 ``"sequential"`` train on windows ``[start, start + T)`` anywhere in it (``mtrssm_episode_gather_window``) -- the latter walks
 an episode chunk by chunk for truncated BPTT with a carried state (``carry.StateCarry``).  ``lengths``: the
 episodes end at different frames; the store keeps them padded to ``T_full``, a batch row carries ``valid`` live steps and its frames
-past them are exactly zero (``mtrssm_episode_gather_ragged``).
+past them are exactly zero (``mtrssm_episode_gather_ragged``).  ``noise_seed``: the input noise is generated
+inside the gather (``mtrssm_episode_gather_seeded``) as a pure function of ``(seed, stream, epoch, episode, absolute frame, element)``,
+the same on any number of ranks and replayed by ``set_epoch``; without it the normals come from ``torch.randn`` as before.
 """
 
 from __future__ import annotations
@@ -30,9 +32,12 @@ import torch
 from torch import Tensor
 
 from multimodal_mtrssm_amd import _lib
-from multimodal_mtrssm_amd.transform import TakeFirstN, Transform, fused_chain
+from multimodal_mtrssm_amd.transform import GaussianNoise, TakeFirstN, Transform, fused_chain
 
 WINDOWS = ("first", "random", "sequential")
+NOISE_EPOCHS = ("advance", "fixed")
+STREAM_NAMES = ("action", "audio", "vision")
+_M32 = 0xFFFFFFFF
 
 try:  # Lightning is optional (absent here): the module only needs prepare_data / setup / *_dataloader
     from lightning import LightningDataModule as _Base
@@ -92,6 +97,7 @@ class EpisodeDataModuleConfig:
     vision_observation_target_transform: Transform
     data_root: Path = Path("data")
     lengths: Tensor | None = None  # host int tensor [N]: valid frames of each episode of the SORTED file list, 1 .. T_full (None: all)
+    noise_seed: int | None = None  # in [0, 2**64): seeded input noise made inside the gather; None: torch.randn
     window: str = "first"  # "first" | "random" | "sequential": which T frames of an episode a batch holds (DeviceEpisodeLoader)
 
     @property
@@ -134,6 +140,12 @@ class _Stream:
         return cin is not None and ctg is not None and cin[0] == ctg[0] and ctg[1] is None and self.event % 4 == 0
 
     @property
+    def noisy(self) -> bool:
+        """The input chain carries a ``GaussianNoise`` (anywhere in it: an unfused chain too)."""
+        chain = getattr(self.transforms[0], "transforms", [self.transforms[0]])
+        return any(isinstance(t, GaussianNoise) for t in chain)
+
+    @property
     def steps(self) -> int | None:
         """T of a batch: what the input chain's leading ``TakeFirstN`` says (None: the chain has none)."""
         t_full = int(self.store.shape[1])
@@ -145,11 +157,13 @@ class _Stream:
         return None if n is None else min(n, t_full)
 
     def batch(self, idx: Tensor, noise: Tensor | None, start: Tensor | None = None, start_host: list[int] | None = None,  # noqa: PLR0913
-              lengths: Tensor | None = None, valid_out: Tensor | None = None, lengths_host: Tensor | None = None) -> tuple[Tensor, Tensor]:
+              lengths: Tensor | None = None, valid_out: Tensor | None = None, lengths_host: Tensor | None = None,
+              seeded: tuple[int, int, int] | None = None) -> tuple[Tensor, Tensor]:
         """``(input, target)`` for the episodes ``idx``; fused when both chains are the YAML's and E % 4 == 0.  ``start`` (int32
         ``[B]`` on the device, ``start_host`` its host copy): the window ``[start, start + T)`` instead of the first T frames.
         ``lengths`` (int32 ``[N]`` on the device): frames at or past an episode's length are exactly zero, ``valid_out`` (int32
-        ``[B]``) receives each row's live steps; ``lengths_host`` is the host copy the unfused path reads."""
+        ``[B]``) receives each row's live steps; ``lengths_host`` is the host copy the unfused path reads.  ``seeded`` = ``(key0, key1,
+        epoch)``: a fused stream with noise and no injected ``noise`` generates its normals in the kernel (``feed_noise_reference``)."""
         cin, ctg = self.chains
         n_ep, t_full = self.store.shape[:2]
         if lengths is not None and start is None:
@@ -169,6 +183,16 @@ class _Stream:
         std = cin[1]
         inp = torch.empty(b, t, *self.event_shape, device=self.store.device, dtype=torch.float32)
         tgt = torch.empty_like(inp)
+        if std is not None and noise is None and seeded is not None:
+            if start is not None and tuple(start.shape) != (b,):
+                msg = f"start must have shape ({b},), got {tuple(start.shape)}"
+                raise ValueError(msg)
+            _lib.check(_lib.TIMERS.call(
+                "mtrssm_episode_gather_seeded", _lib.load().mtrssm_episode_gather_seeded, _lib.ptr(self.store), _lib.raw_ptr(idx),
+                _lib.index_ptr(start), _lib.index_ptr(lengths), _lib.index_ptr(valid_out), *(int(w) & _M32 for w in seeded), n_ep, b, t, t_full,
+                self.event, float(std), _lib.ptr(inp), _lib.ptr(tgt), _lib.stream_ptr(self.store.device), nbytes=4.0 * b * t * self.event * 3),
+                "mtrssm_episode_gather_seeded")
+            return inp, tgt
         if std is not None and noise is None:
             noise = torch.randn(b, t, *self.event_shape, device=self.store.device, dtype=torch.float32)
         lib = _lib.load()
@@ -252,6 +276,54 @@ def gather_ragged_reference(store: Tensor, idx: Tensor, start: Tensor, lengths: 
     return torch.where(live.reshape(shape), target + noise * std, torch.zeros_like(picked)), target, valid
 
 
+def philox4x32_10(counter: tuple, key: tuple) -> tuple:
+    """Philox4x32 with ten rounds (Salmon et al., SC'11; Random123's ``philox4x32_R(10, ...)``) in exact integers: ``counter`` four and
+    ``key`` two 32-bit words, each an int or a numpy integer array (broadcast against each other); returns the four output words as
+    ``uint64`` arrays holding 32-bit values.  What ``mtrssm_episode_gather_seeded`` computes per float4."""
+    c = [np.asarray(w, dtype=np.uint64) & np.uint64(_M32) for w in counter]
+    k = [np.asarray(w, dtype=np.uint64) & np.uint64(_M32) for w in key]
+    if len(c) != 4 or len(k) != 2:  # noqa: PLR2004
+        msg = f"philox4x32_10 takes a 4-word counter and a 2-word key, got {len(c)} and {len(k)}"
+        raise ValueError(msg)
+    m0, m1, w0, w1, mask, sh = (np.uint64(v) for v in (0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85, _M32, 32))
+    for _ in range(10):
+        p0, p1 = m0 * c[0], m1 * c[2]  # 32 x 32 -> 64 bits: no overflow in uint64
+        c = [(p1 >> sh) ^ c[1] ^ k[0], p1 & mask, (p0 >> sh) ^ c[3] ^ k[1], p0 & mask]
+        k = [(k[0] + w0) & mask, (k[1] + w1) & mask]
+    return tuple(c)
+
+
+def stream_key(seed: int, stream: int) -> tuple[int, int]:
+    """The generator key of stream ``stream`` (0, 1, 2 = action, audio, vision) under ``seed`` in ``[0, 2**64)``."""
+    return (seed & _M32, ((seed >> 32) & _M32) ^ ((0x9E3779B9 * (stream + 1)) & _M32))
+
+
+def feed_noise_reference(key: tuple[int, int], epoch: int, episodes: Tensor, frames: Tensor, event: int) -> Tensor:
+    """The standard normals of ``mtrssm_episode_gather_seeded`` in float64 from exact integers: ``episodes`` ``[B]`` (the batch's
+    ``idx``), ``frames`` ``[B, T]`` (ABSOLUTE frame numbers: clamped start + t), ``event`` = E (a multiple of 4); returns ``[B, T, E]``
+    on the host.  Elements ``4 e4 .. 4 e4 + 3`` of a frame come from ``Philox4x32-10((e4, frame, episode & 0xffffffff, epoch), key)``:
+    words (0, 1) and (2, 3) each give ``u1 = ((xa >> 8) + 1) 2^-24``, ``u2 = (xb >> 8) 2^-24``, ``r = sqrt(-2 ln u1)``,
+    ``r cos(2 pi u2)``, ``r sin(2 pi u2)``."""
+    if event % 4:
+        msg = f"the event size {event} must be a multiple of 4"
+        raise ValueError(msg)
+    ep = np.asarray(torch.as_tensor(episodes).cpu(), dtype=np.int64)
+    fr = np.asarray(torch.as_tensor(frames).cpu(), dtype=np.int64)
+    if fr.shape[:1] != ep.shape or fr.ndim != 2:  # noqa: PLR2004
+        msg = f"episodes must be [B] and frames [B, T], got {ep.shape} and {fr.shape}"
+        raise ValueError(msg)
+    e4 = np.arange(event // 4, dtype=np.int64)[None, None, :]
+    x = philox4x32_10((e4, fr[:, :, None] & _M32, ep[:, None, None] & _M32, int(epoch) & _M32), key)
+    out = np.empty((*fr.shape, event // 4, 4), dtype=np.float64)
+    for pair in (0, 1):
+        u1 = ((x[2 * pair] >> np.uint64(8)) + np.uint64(1)).astype(np.float64) * 2.0 ** -24
+        u2 = (x[2 * pair + 1] >> np.uint64(8)).astype(np.float64) * 2.0 ** -24
+        r = np.sqrt(-2.0 * np.log(u1))
+        out[..., 2 * pair] = r * np.cos(2.0 * np.pi * u2)
+        out[..., 2 * pair + 1] = r * np.sin(2.0 * np.pi * u2)
+    return torch.from_numpy(out.reshape(*fr.shape, event))
+
+
 class EpisodeBatch(tuple):
     """The 6-tuple of a windowed batch (``len == 6``, indexing as ever) plus where its windows lie: ``start`` (int32 ``[B]``) and
     ``reset`` (bool ``[B]``, True = the row starts an episode) on the device, ``start_host`` / ``reset_host`` their host copies (the
@@ -288,13 +360,36 @@ class DeviceEpisodeLoader:
     global row g meets the same noise whatever the number of ranks.  All ranks yield the same number of equally sized batches: a batch whose size
     is not a multiple of ``world`` is padded by wrapping to the head of the epoch's order (``DistributedSampler``'s rule),
     so the per-step all-reduce never waits for a rank that ran out of rows.  With one rank the last batch may be short
-    (the reference's DataLoader keeps it too)."""
+    (the reference's DataLoader keeps it too).
+
+    ``noise_seed`` (an int in ``[0, 2**64)``): every stream whose input chain carries a ``GaussianNoise`` takes its
+    normals from the generator inside ``mtrssm_episode_gather_seeded``, keyed by ``stream_key(noise_seed, stream)`` and the epoch word --
+    a frame's noise depends on ``(seed, stream, epoch, episode, absolute frame, element)`` only, so it is the same on any number of
+    ranks, at any batch size and window start, and ``set_epoch(e)`` replays epoch e bitwise.  The epoch word is the value the epoch
+    counter had when the epoch's iteration began (the one that seeds the permutation); ``noise_epoch="fixed"`` keeps it 0 and draws
+    epoch 0's order and window starts every epoch, so the loader yields the same batches each epoch (validation: losses of two epochs
+    are computed on the same inputs).  None (the default): ``torch.randn`` from the device generator, as before."""
 
     def __init__(self, streams: tuple[_Stream, _Stream, _Stream], batch_size: int, *, shuffle: bool, rank: int = 0, world: int = 1,  # noqa: PLR0913
-                 seed: int = 0, window: str = "first", lengths: Tensor | None = None) -> None:
+                 seed: int = 0, window: str = "first", lengths: Tensor | None = None, noise_seed: int | None = None,
+                 noise_epoch: str = "advance") -> None:
         if window not in WINDOWS:
             msg = f"window must be one of {WINDOWS}, got {window!r}"
             raise ValueError(msg)
+        if noise_epoch not in NOISE_EPOCHS:
+            msg = f"noise_epoch must be one of {NOISE_EPOCHS}, got {noise_epoch!r}"
+            raise ValueError(msg)
+        if noise_seed is not None:
+            if isinstance(noise_seed, bool) or not isinstance(noise_seed, int) or not 0 <= noise_seed < 2 ** 64:
+                msg = f"noise_seed must be an int in [0, 2**64), got {noise_seed!r}"
+                raise ValueError(msg)
+            for name, s in zip(STREAM_NAMES, streams, strict=True):
+                if s.noisy and not s.fused:
+                    msg = (f"noise_seed: the {name} stream needs noise but does not run in the gather kernel (its transforms must be "
+                           f"[TakeFirstN, GaussianNoise] / [TakeFirstN] and its event size a multiple of 4, got {s.event})")
+                    raise ValueError(msg)
+        self.noise_seed, self.noise_epoch = noise_seed, noise_epoch
+        self.noise_word = 0  # the epoch word of the seeded noise: set where an epoch's iteration begins, and by set_epoch
         self.streams = streams
         self.batch_size = int(batch_size)
         self.shuffle = shuffle
@@ -340,11 +435,19 @@ class DeviceEpisodeLoader:
 
     def set_epoch(self, epoch: int) -> None:
         self.epoch = int(epoch)
+        self.noise_word = self.epoch if self.noise_epoch == "advance" else 0
+
+    def _seeded(self) -> list[tuple[int, int, int] | None]:
+        """Per stream: ``(key0, key1, epoch word)`` of its seeded noise, None for a stream without noise or a loader without seed."""
+        if self.noise_seed is None:
+            return [None] * len(self.streams)
+        return [(*stream_key(self.noise_seed, k), self.noise_word & _M32) if s.noisy else None for k, s in enumerate(self.streams)]
 
     def batch(self, idx: Tensor, noise: tuple[Tensor | None, Tensor | None, Tensor | None] = (None, None, None),  # noqa: PLR0913
               start: Tensor | None = None, reset: Tensor | None = None, *, valid_host: Tensor | None = None,
               valid_global: Tensor | None = None, row0: int = 0) -> tuple[Tensor, ...]:
-        """The 6-tuple for episode indices ``idx`` (int64, on the device); ``noise`` injects the standard normals.  ``start``: the
+        """The 6-tuple for episode indices ``idx`` (int64, on the device); ``noise`` injects the standard normals (and takes precedence
+        over a ``noise_seed``, whose epoch word is that of the epoch being iterated, or of the last ``set_epoch``).  ``start``: the
         windows' first frames, one per row -- a HOST integer tensor (validated here: ``0 <= start <= T_full - T``) or an int32
         device tensor (not read back: the kernel clamps it into that range); the result is then an ``EpisodeBatch``, ``reset``
         (a host bool tensor, default all True) riding along.
@@ -355,8 +458,9 @@ class DeviceEpisodeLoader:
         if start is None and self.lengths is not None:
             msg = "a loader with lengths needs start= (the windows' first frames)"
             raise ValueError(msg)
+        seeded = self._seeded()
         if start is None:
-            pairs = [s.batch(idx, n) for s, n in zip(self.streams, noise, strict=True)]
+            pairs = [s.batch(idx, n, seeded=k) for s, n, k in zip(self.streams, noise, seeded, strict=True)]
             return (pairs[0][0], pairs[1][0], pairs[2][0], pairs[0][1], pairs[1][1], pairs[2][1])
         dev = self.streams[0].store.device
         start_host = None
@@ -370,14 +474,14 @@ class DeviceEpisodeLoader:
         reset_host = torch.ones(idx.numel(), dtype=torch.bool) if reset is None else reset.to("cpu", torch.bool)
         hosts = None if start_host is None else start_host.tolist()
         if self.lengths is None:
-            pairs = [s.batch(idx, n, start.contiguous(), hosts) for s, n in zip(self.streams, noise, strict=True)]
+            pairs = [s.batch(idx, n, start.contiguous(), hosts, seeded=k) for s, n, k in zip(self.streams, noise, seeded, strict=True)]
             items = (pairs[0][0], pairs[1][0], pairs[2][0], pairs[0][1], pairs[1][1], pairs[2][1])
             return EpisodeBatch(items, start, reset_host.to(dev), start_host, reset_host)
         valid = torch.empty(idx.numel(), dtype=torch.int32, device=dev)
         # written by ONE launch: the first stream the gather kernel takes (a batch of unfused streams only: by the per-episode path)
         writer = next((k for k, s in enumerate(self.streams) if s.fused), 0)
-        pairs = [s.batch(idx, n, start.contiguous(), hosts, self.lengths, valid if k == writer else None, self.lengths_host)
-                 for k, (s, n) in enumerate(zip(self.streams, noise, strict=True))]
+        pairs = [s.batch(idx, n, start.contiguous(), hosts, self.lengths, valid if k == writer else None, self.lengths_host, seeded=sd)
+                 for k, (s, n, sd) in enumerate(zip(self.streams, noise, seeded, strict=True))]
         items = (pairs[0][0], pairs[1][0], pairs[2][0], pairs[0][1], pairs[1][1], pairs[2][1])
         vg = None if valid_global is None else valid_global.to(dev, torch.int32)
         return EpisodeBatch(items, start, reset_host.to(dev), start_host, reset_host, valid=valid,
@@ -389,7 +493,8 @@ class DeviceEpisodeLoader:
         included), and the rank's first global row -- all cut from per-GLOBAL-row quantities, so global row g is the same episode and
         window on any number of ranks.  Advances the epoch counter."""
         dev = self.streams[0].store.device
-        g = torch.Generator().manual_seed(self.seed + self.epoch)
+        # (a fixed loader draws epoch 0's order and windows every epoch: with its epoch word 0 it yields the same batches each time)
+        g = torch.Generator().manual_seed(self.seed + (self.epoch if self.noise_epoch == "advance" else 0))
         order = torch.randperm(self.n, generator=g) if self.shuffle else torch.arange(self.n)
         lens = None if self.lengths_host is None else self.lengths_host[order]  # per position of the epoch's order
         starts = None
@@ -403,6 +508,7 @@ class DeviceEpisodeLoader:
                 second = (torch.rand(self.n, generator=g, dtype=torch.float64) * room).to(torch.int64).clamp(max=room - 1)
                 starts = torch.where(room == self.t_full - self.steps + 1, starts.to(torch.int64), second).to(torch.int32)
         order = order.to(dev)
+        self.noise_word = self.epoch if self.noise_epoch == "advance" else 0  # the epoch that seeded the permutation above
         self.epoch += 1
         for lo in range(0, self.n, self.batch_size):
             rows = order[lo: lo + self.batch_size]
@@ -576,11 +682,12 @@ class EpisodeDataModule(_Base):
             msg = "train_dataset is not set. Call setup() first."
             raise RuntimeError(msg)
         return DeviceEpisodeLoader(self.train_streams, self.config.batch_size, shuffle=True, rank=self.rank, world=self.world,
-                                   window=self.config.window, lengths=self._lengths(True))
+                                   window=self.config.window, lengths=self._lengths(True), noise_seed=self.config.noise_seed)
 
     def val_dataloader(self) -> DeviceEpisodeLoader:
         if self.val_streams is None:
             msg = "val_dataset is not set. Call setup() first."
             raise RuntimeError(msg)
         return DeviceEpisodeLoader(self.val_streams, self.config.batch_size, shuffle=False, rank=self.rank, world=self.world,
-                                   window=self.config.window, lengths=self._lengths(False))
+                                   window=self.config.window, lengths=self._lengths(False), noise_seed=self.config.noise_seed,
+                                   noise_epoch="advance" if self.config.noise_seed is None else "fixed")
