@@ -16,25 +16,11 @@
 // Backward, per timestep (four barriers): R0 categorical blocks + mix backward per row; R1 pre-activation gradients of the
 // five layer-0 heads; R2 gradients at d_l / d_h through tanh into the leaky integrators (du); R3 the carries into step t-1:
 // W_d^T du per level (kept by the workgroup of R2) and W_x^T du -> [s_l ; s_h].
-#include <cstdlib>
-
 #include "wide_common.h"
 
 namespace mtrssm {
 
-void set_error(const char* fmt, ...);
-void set_last_kernel(const char* name);
-int device_cu_count();
-WidePackJob wide_make_job(const float* src, long sn, long sk, int N, int K, uint4* dst);
-WidePackJob wide_make_block(const float* src, long sn, long sk, int N, int K, int nskip, int kskip, int nt0, int ks0, int KST, uint4* dst);
-int wide_launch_pack(const WidePackJobs& jobs, int pieces, hipStream_t stream);
-
-// Development aid (tools/wide_probe.py mmt-fwd | mmt-bwd): as g_wide_prof of mrssm_wide.hip.
-__device__ unsigned long long* g_mmt_prof = nullptr;
-#define MTRSSM_MMT_STAMP(i)                                                                                               \
-  do {                                                                                                                    \
-    if (prof && tstamp >= 8 && tstamp < 12) prof[((size_t)blockIdx.x * 4 + (tstamp - 8)) * 16 + (i)] = __builtin_amdgcn_s_memrealtime(); \
-  } while (0)
+__device__ unsigned long long* g_mmt_prof = nullptr;   // MTRSSM_WIDE_STAMP's buffer (tools/wide_probe.py mmt-fwd | mmt-bwd)
 
 constexpr int kMRT = 4;             // row tiles per pass
 constexpr int kMRows = 16 * kMRT;   // 64 batch rows
@@ -97,14 +83,14 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_fwd_kernel(const MmtWideFwdA
   WideBarrier bar;
   bar.init(a.ctl, a.status, abort_flag, nblk, blk, a.acquire != 0);
 
-  auto krange = [&](int KS, int& k0, int& k1) { k0 = KS * wave / kWW; k1 = KS * (wave + 1) / kWW; };
+  auto krange = [&](int n, int& k0, int& k1) { wide_krange(n, wave, k0, k1); };   // for MTRSSM_WIDE_TILE_PRODUCT
   const size_t tile_rnn = (size_t)KST * P * 64, tile_l0 = (size_t)KS2 * P * 64, tile_l1 = (size_t)KSH * P * 64;
-  const int e_rt = tid >> 6, e_slot = lane, e_row = 16 * e_rt + (e_slot & 15), e_cq = 4 * (e_slot >> 4);
+  const WideEpi e(tid);
 
   for (int rb = 0; rb < B; rb += kMRows) {
     const int nrows = B - rb < kMRows ? B - rb : kMRows;
-    const bool e_valid = e_row < nrows;
-    const size_t e_b = (size_t)(rb + (e_valid ? e_row : 0));
+    const bool e_valid = e.row < nrows;
+    const size_t e_b = (size_t)(rb + (e_valid ? e.row : 0));
     // ---- set-up: XS[0] <- [deter_l0 | deter_h0 | (s: written by F0)]; the launch zeroed every exchange vector
     for (int i = blk * kWT + tid; i < nrows * ((LD + HD) / 4); i += nblk * kWT) {
       const int row = i / ((LD + HD) / 4), q = i - row * ((LD + HD) / 4);
@@ -118,7 +104,7 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_fwd_kernel(const MmtWideFwdA
     float hid[4] = {0.f, 0.f, 0.f, 0.f};
     if (blk < G.NTL + G.NTHd && e_valid) {
       const bool lower = blk < G.NTL;
-      const int c = (lower ? blk : blk - G.NTL) * 16 + e_cq;
+      const int c = (lower ? blk : blk - G.NTL) * 16 + e.cq;
       if (c < (lower ? LD : HD)) {
         const float4 v4 = *reinterpret_cast<const float4*>(lower ? io.hidden_l0 + e_b * LD + c : io.hidden_h0 + e_b * HD + c);
         hid[0] = v4.x; hid[1] = v4.y; hid[2] = v4.z; hid[3] = v4.w;
@@ -129,7 +115,7 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_fwd_kernel(const MmtWideFwdA
 
     for (int t = 0; t <= T; ++t) {
       const int tstamp = t;
-      MTRSSM_MMT_STAMP(0);
+      MTRSSM_WIDE_STAMP(0);
       // ============ F0: one workgroup per batch row ============
       for (int r = nblk - 1 - blk; r < nrows; r += nblk) {
         const size_t b = (size_t)(rb + r);
@@ -153,7 +139,7 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_fwd_kernel(const MmtWideFwdA
             }
           }
           lds_barrier();
-          MTRSSM_MMT_STAMP(10);
+          MTRSSM_WIDE_STAMP(10);
           if (wave == 0) {   // lower level: MoPoE mix, categorical block
             wave_mopoe_mix_masked<true, MASKED>(Lla, Llv, Llpl, Lmx, LS, lane, code);
             for (int s2 = lane; s2 < LS; s2 += kWave) {
@@ -167,7 +153,7 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_fwd_kernel(const MmtWideFwdA
                                                             io.prior_stoch_l ? io.prior_stoch_l + q * LS : nullptr, true);
             kll = wave_sum(kll);
             if (lane == 0 && io.kl_l) io.kl_l[q] = kll;
-            MTRSSM_MMT_STAMP(11);
+            MTRSSM_WIDE_STAMP(11);
           } else if (wave == 1) {   // higher level, beside it on another SIMD
             if (MASKED && code == 0) wave_copy(Llph, Llqh, HS, lane);  // no modality: higher posterior = prior
             for (int s2 = lane; s2 < HS; s2 += kWave) {
@@ -198,28 +184,20 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_fwd_kernel(const MmtWideFwdA
         lds_barrier();
       }
       if (t == T) break;
-      MTRSSM_MMT_STAMP(1);
+      MTRSSM_WIDE_STAMP(1);
       if (!bar.sync(1 + 4 * t)) return;
-      MTRSSM_MMT_STAMP(2);
+      MTRSSM_WIDE_STAMP(2);
 
       // ============ F1: both MTRNN cells, one workgroup per 16 deter units ============
       for (int u = blk; u < G.NTL + G.NTHd; u += nblk) {
         const bool lower = u < G.NTL;
-        const int c = (lower ? u : u - G.NTL) * 16 + e_cq, width = lower ? LD : HD;
+        const int c = (lower ? u : u - G.NTL) * 16 + e.cq, width = lower ? LD : HD;
         const bool c_ok = e_valid && c < width;
         float4 add = make_float4(0.f, 0.f, 0.f, 0.f);
         if (c_ok) add = *reinterpret_cast<const float4*>(lower ? io.xl + (e_b * T + t) * LD + c : w.bh + c);
-        int k0, k1;
-        krange(KST, k0, k1);
-        wf32x4 acc[1][kMRT];
-#pragma unroll
-        for (int rt = 0; rt < kMRT; ++rt) acc[0][rt] = wf32x4{0.f, 0.f, 0.f, 0.f};
-        const uint4* const wt[1] = {a.pk_rnn + (size_t)u * tile_rnn};
-        wide_mfma_stream<1, P, kMNS, kMRT>(acc, wt, a.xs[cur], KST, k0, k1, lane);
-        wide_red_store<1, kMRT>(red, wave, 0, lane, acc[0]);
-        lds_barrier();
+        MTRSSM_WIDE_TILE_PRODUCT(P, kMNS, kMRT, a.pk_rnn + (size_t)u * tile_rnn, a.xs[cur], KST, KST);
         {
-          const wf32x4 sm = wide_red_sum<1, kMRT>(red, 0, e_rt, e_slot);
+          const wf32x4 sm = wide_red_sum<1, kMRT>(red, 0, e.rt, e.slot);
           const float keep = lower ? a.dm.keep_l : a.dm.keep_h, tau = lower ? a.dm.tau_l : a.dm.tau_h;
           const float uv[4] = {sm[0] + add.x, sm[1] + add.y, sm[2] + add.z, sm[3] + add.w};
           float d[4];
@@ -232,19 +210,19 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_fwd_kernel(const MmtWideFwdA
             const size_t q = e_b * T + t;
             *reinterpret_cast<float4*>((lower ? io.deter_l + q * LD : io.deter_h + q * HD) + c) = make_float4(d[0], d[1], d[2], d[3]);
             *reinterpret_cast<float4*>((lower ? io.hidden_l + q * LD : io.hidden_h + q * HD) + c) = make_float4(hid[0], hid[1], hid[2], hid[3]);
-            wide_x_store4<P, kMRows>(a.xs[cur ^ 1], KST, e_row, (lower ? 0 : G.KLD) + c, d);
+            wide_x_store4<P, kMRows>(a.xs[cur ^ 1], KST, e.row, (lower ? 0 : G.KLD) + c, d);
           }
         }
         lds_barrier();
       }
       cur ^= 1;
-      MTRSSM_MMT_STAMP(3);
+      MTRSSM_WIDE_STAMP(3);
       if (!bar.sync(2 + 4 * t)) return;
-      MTRSSM_MMT_STAMP(4);
+      MTRSSM_WIDE_STAMP(4);
 
       // ============ F2: layer 0 of the five heads on [d_l | d_h] ============
       for (int u = blk; u < 5 * G.NTHP; u += nblk) {
-        const int q5 = u / G.NTHP, c = (u - q5 * G.NTHP) * 16 + e_cq;
+        const int q5 = u / G.NTHP, c = (u - q5 * G.NTHP) * 16 + e.cq;
         const bool c_ok = e_valid && c < H;
         float4 add = make_float4(0.f, 0.f, 0.f, 0.f);
         if (c_ok) {
@@ -255,17 +233,9 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_fwd_kernel(const MmtWideFwdA
           else if (q5 == 3) add = *reinterpret_cast<const float4*>(w.bh1 + H + c);
           else add = *reinterpret_cast<const float4*>(w.bh1 + c);
         }
-        int k0, k1;
-        krange(KS2, k0, k1);
-        wf32x4 acc[1][kMRT];
-#pragma unroll
-        for (int rt = 0; rt < kMRT; ++rt) acc[0][rt] = wf32x4{0.f, 0.f, 0.f, 0.f};
-        const uint4* const wt[1] = {a.pk_l0 + (size_t)u * tile_l0};
-        wide_mfma_stream<1, P, kMNS, kMRT>(acc, wt, a.xs[cur], KST, k0, k1, lane);   // XS has KST k-blocks per piece; only the d part is read
-        wide_red_store<1, kMRT>(red, wave, 0, lane, acc[0]);
-        lds_barrier();
+        MTRSSM_WIDE_TILE_PRODUCT(P, kMNS, kMRT, a.pk_l0 + (size_t)u * tile_l0, a.xs[cur], KS2, KST);   // XS has KST k-blocks per piece; only the d part is read
         if (c_ok) {
-          const wf32x4 sm = wide_red_sum<1, kMRT>(red, 0, e_rt, e_slot);
+          const wf32x4 sm = wide_red_sum<1, kMRT>(red, 0, e.rt, e.slot);
           const float h[4] = {act_fwd(sm[0] + add.x, act), act_fwd(sm[1] + add.y, act), act_fwd(sm[2] + add.z, act), act_fwd(sm[3] + add.w, act)};
           const size_t q = e_b * T + t;
           if (q5 < 4) {
@@ -273,13 +243,13 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_fwd_kernel(const MmtWideFwdA
           } else if (io.sv_h1) {
             *reinterpret_cast<float4*>(io.sv_h1 + q * H + c) = make_float4(h[0], h[1], h[2], h[3]);
           }
-          wide_x_store4<P, kMRows>(a.xh[q5], KSH, e_row, c, h);
+          wide_x_store4<P, kMRows>(a.xh[q5], KSH, e.row, c, h);
         }
         lds_barrier();
       }
-      MTRSSM_MMT_STAMP(5);
+      MTRSSM_WIDE_STAMP(5);
       if (!bar.sync(3 + 4 * t)) return;
-      MTRSSM_MMT_STAMP(6);
+      MTRSSM_WIDE_STAMP(6);
 
       // ============ F3: layer 1 of the five heads: lpl | la | lv | lqh | lph ============
       {
@@ -287,27 +257,19 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_fwd_kernel(const MmtWideFwdA
         for (int u = blk; u < 3 * nl + 2 * nh; u += nblk) {
           const int q5 = u < 3 * nl ? u / nl : 3 + (u - 3 * nl) / nh;
           const int st = u < 3 * nl ? u - q5 * nl : (u - 3 * nl) - (q5 - 3) * nh;
-          int k0, k1;
-          krange(KSH, k0, k1);
-          wf32x4 acc[1][kMRT];
-#pragma unroll
-          for (int rt = 0; rt < kMRT; ++rt) acc[0][rt] = wf32x4{0.f, 0.f, 0.f, 0.f};
-          const uint4* const wt[1] = {a.pk_l1[q5] + (size_t)st * tile_l1};
-          wide_mfma_stream<1, P, kMNS, kMRT>(acc, wt, a.xh[q5], KSH, k0, k1, lane);
-          wide_red_store<1, kMRT>(red, wave, 0, lane, acc[0]);
-          lds_barrier();
+          MTRSSM_WIDE_TILE_PRODUCT(P, kMNS, kMRT, a.pk_l1[q5] + (size_t)st * tile_l1, a.xh[q5], KSH, KSH);
           if (e_valid) {
-            const wf32x4 sm = wide_red_sum<1, kMRT>(red, 0, e_rt, e_slot);
-            float* dst = a.lg + (size_t)e_row * LGW + (q5 < 3 ? q5 * G.LSp : 3 * G.LSp + (q5 - 3) * G.HSp) + st * 16 + e_cq;
+            const wf32x4 sm = wide_red_sum<1, kMRT>(red, 0, e.rt, e.slot);
+            float* dst = a.lg + (size_t)e.row * LGW + (q5 < 3 ? q5 * G.LSp : 3 * G.LSp + (q5 - 3) * G.HSp) + st * 16 + e.cq;
             wide_store_f2(dst, sm[0], sm[1]);
             wide_store_f2(dst + 2, sm[2], sm[3]);
           }
           lds_barrier();
         }
       }
-      MTRSSM_MMT_STAMP(7);
+      MTRSSM_WIDE_STAMP(7);
       if (!bar.sync(4 + 4 * t)) return;
-      MTRSSM_MMT_STAMP(8);
+      MTRSSM_WIDE_STAMP(8);
     }
     if (!bar.sync(0x40000000)) return;   // the next tile's set-up overwrites the exchange vectors
   }
@@ -354,20 +316,20 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_bwd_kernel(const MmtWideBwdA
   WideBarrier bar;
   bar.init(a.ctl, a.status, abort_flag, nblk, blk, a.acquire != 0);
 
-  auto krange = [&](int KS, int& k0, int& k1) { k0 = KS * wave / kWW; k1 = KS * (wave + 1) / kWW; };
+  auto krange = [&](int n, int& k0, int& k1) { wide_krange(n, wave, k0, k1); };   // for MTRSSM_WIDE_TILE_PRODUCT
   const size_t tile_z = (size_t)KSZ * P * 64, tile_u = (size_t)KSU * P * 64;
-  const int e_rt = tid >> 6, e_slot = lane, e_row = 16 * e_rt + (e_slot & 15), e_cq = 4 * (e_slot >> 4);
+  const WideEpi e(tid);
 
   for (int rb = 0; rb < B; rb += kMRows) {
     const int nrows = B - rb < kMRows ? B - rb : kMRows;
-    const bool e_valid = e_row < nrows;
-    const size_t e_b = (size_t)(rb + (e_valid ? e_row : 0));
+    const bool e_valid = e.row < nrows;
+    const size_t e_b = (size_t)(rb + (e_valid ? e.row : 0));
     float c_d[4] = {0.f, 0.f, 0.f, 0.f}, c_hid[4] = {0.f, 0.f, 0.f, 0.f};   // carries of the deter units this workgroup owns (R2, R3)
     unsigned long long* const prof = (tid == 0 && rb == 0) ? g_mmt_prof : nullptr;
 
     for (int t = T - 1; t >= 0; --t) {
       const int tstamp = T - 1 - t;
-      MTRSSM_MMT_STAMP(0);
+      MTRSSM_WIDE_STAMP(0);
       // ============ R0: categorical blocks + MoPoE mix backward, one workgroup per batch row ============
       for (int r = nblk - 1 - blk; r < nrows; r += nblk) {
         const size_t q = (size_t)(rb + r) * T + t;
@@ -386,7 +348,7 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_bwd_kernel(const MmtWideBwdA
         }
         for (int s2 = tid; s2 < LS + HS; s2 += kWT) Lcs[s2] = t == T - 1 ? 0.f : wide_load_f(a.cs + (size_t)r * LSHp + s2);
         lds_barrier();
-        MTRSSM_MMT_STAMP(10);
+        MTRSSM_WIDE_STAMP(10);
         if (wave == 0) {   // lower level: categorical block, then the MoPoE mix backward
           const float gkl = io.g_kl_l ? io.g_kl_l[q] : 0.f;
           const float* gpsl = io.g_prior_stoch_l ? io.g_prior_stoch_l + q * LS : nullptr;
@@ -395,7 +357,7 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_bwd_kernel(const MmtWideBwdA
           if (CL <= 8) cat_block_bwd_fast8(Lmx, Llpl, KL, CL, lane, Lgps, Lcs, gpsl, gpll, gprl, gkl, a.dm.kl_w_post, a.dm.kl_w_prior, Ldmx, Ldlpl);
           else cat_block_bwd<true>(Lmx, Llpl, KL, CL, lane, Lgps, Lcs, gpsl, gpll, gprl, gkl, a.dm.kl_w_post, a.dm.kl_w_prior, Ldmx, Ldlpl);
           wave_mopoe_mix_bwd_masked<true, MASKED>(Lla, Llv, Lmx, Ldmx, Ldla, Ldlv, Ldlpl, LS, lane, code);
-          MTRSSM_MMT_STAMP(11);
+          MTRSSM_WIDE_STAMP(11);
         } else if (wave == 1) {   // higher level, beside it on another SIMD
           const float gkh = io.g_kl_h ? io.g_kl_h[q] : 0.f;
           const float* gpsh = io.g_prior_stoch_h ? io.g_prior_stoch_h + q * HS : nullptr;
@@ -424,13 +386,13 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_bwd_kernel(const MmtWideBwdA
         }
         lds_barrier();
       }
-      MTRSSM_MMT_STAMP(1);
+      MTRSSM_WIDE_STAMP(1);
       if (!bar.sync(1 + 4 * t)) return;
-      MTRSSM_MMT_STAMP(2);
+      MTRSSM_WIDE_STAMP(2);
 
       // ============ R1: pre-activation gradients of layer 0: dz = act'(h) * (W2nd^T dl), five heads ============
       for (int u = blk; u < 5 * G.NTHP; u += nblk) {
-        const int q5 = u / G.NTHP, c = (u - q5 * G.NTHP) * 16 + e_cq;   // l_prior, audio, vision, h_posterior, h_prior
+        const int q5 = u / G.NTHP, c = (u - q5 * G.NTHP) * 16 + e.cq;   // l_prior, audio, vision, h_posterior, h_prior
         const bool c_ok = e_valid && c < H;
         float4 hs = make_float4(0.f, 0.f, 0.f, 0.f);
         if (c_ok) {
@@ -438,34 +400,26 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_bwd_kernel(const MmtWideBwdA
           hs = *reinterpret_cast<const float4*>(q5 < 4 ? io.sv_l1 + q * 4 * H + q5 * H + c : io.sv_h1 + q * H + c);
         }
         const int KS = q5 < 3 ? KSL : KSHs;
-        int k0, k1;
-        krange(KS, k0, k1);
-        wf32x4 acc[1][kMRT];
-#pragma unroll
-        for (int rt = 0; rt < kMRT; ++rt) acc[0][rt] = wf32x4{0.f, 0.f, 0.f, 0.f};
-        const uint4* const wt[1] = {a.pk_l1t[q5] + (size_t)(u - q5 * G.NTHP) * ((size_t)KS * P * 64)};
-        wide_mfma_stream<1, P, kMNS, kMRT>(acc, wt, a.x_dl[q5], KS, k0, k1, lane);
-        wide_red_store<1, kMRT>(red, wave, 0, lane, acc[0]);
-        lds_barrier();
+        MTRSSM_WIDE_TILE_PRODUCT(P, kMNS, kMRT, a.pk_l1t[q5] + (size_t)(u - q5 * G.NTHP) * ((size_t)KS * P * 64), a.x_dl[q5], KS, KS);
         if (c_ok) {
-          const wf32x4 sm = wide_red_sum<1, kMRT>(red, 0, e_rt, e_slot);
+          const wf32x4 sm = wide_red_sum<1, kMRT>(red, 0, e.rt, e.slot);
           const float g[4] = {sm[0] * act_grad_from_out(hs.x, act), sm[1] * act_grad_from_out(hs.y, act), sm[2] * act_grad_from_out(hs.z, act),
                               sm[3] * act_grad_from_out(hs.w, act)};
           const size_t q = e_b * T + t;
           if (q5 < 4) *reinterpret_cast<float4*>(io.d_zl1 + q * 4 * H + q5 * H + c) = make_float4(g[0], g[1], g[2], g[3]);
           else *reinterpret_cast<float4*>(io.d_zh1 + q * H + c) = make_float4(g[0], g[1], g[2], g[3]);
-          wide_x_store4<P, kMRows>(a.x_dz, KSZ, e_row, q5 * G.HK + c, g);
+          wide_x_store4<P, kMRows>(a.x_dz, KSZ, e.row, q5 * G.HK + c, g);
         }
         lds_barrier();
       }
-      MTRSSM_MMT_STAMP(3);
+      MTRSSM_WIDE_STAMP(3);
       if (!bar.sync(2 + 4 * t)) return;
-      MTRSSM_MMT_STAMP(4);
+      MTRSSM_WIDE_STAMP(4);
 
       // ============ R2: gradients at d_l / d_h, through tanh into the leaky integrators ============
       for (int u = blk; u < G.NTL + G.NTHd; u += nblk) {
         const bool lower = u < G.NTL;
-        const int c = (lower ? u : u - G.NTL) * 16 + e_cq, width = lower ? LD : HD;
+        const int c = (lower ? u : u - G.NTL) * 16 + e.cq, width = lower ? LD : HD;
         const bool c_ok = e_valid && c < width;
         float4 gd = make_float4(0.f, 0.f, 0.f, 0.f), gh = gd, dv = gd;
         if (c_ok) {
@@ -476,17 +430,9 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_bwd_kernel(const MmtWideBwdA
           if (ghp) gh = *reinterpret_cast<const float4*>(ghp + q * width + c);
           dv = *reinterpret_cast<const float4*>((lower ? io.deter_l : io.deter_h) + q * width + c);
         }
-        int k0, k1;
-        krange(KSZ, k0, k1);
-        wf32x4 acc[1][kMRT];
-#pragma unroll
-        for (int rt = 0; rt < kMRT; ++rt) acc[0][rt] = wf32x4{0.f, 0.f, 0.f, 0.f};
-        const uint4* const wt[1] = {a.pk_l0t + (size_t)u * tile_z};
-        wide_mfma_stream<1, P, kMNS, kMRT>(acc, wt, a.x_dz, KSZ, k0, k1, lane);
-        wide_red_store<1, kMRT>(red, wave, 0, lane, acc[0]);
-        lds_barrier();
+        MTRSSM_WIDE_TILE_PRODUCT(P, kMNS, kMRT, a.pk_l0t + (size_t)u * tile_z, a.x_dz, KSZ, KSZ);
         {
-          const wf32x4 sm = wide_red_sum<1, kMRT>(red, 0, e_rt, e_slot);
+          const wf32x4 sm = wide_red_sum<1, kMRT>(red, 0, e.rt, e.slot);
           const float keep = lower ? a.dm.keep_l : a.dm.keep_h, tau = lower ? a.dm.tau_l : a.dm.tau_h;
           const float gdv[4] = {gd.x, gd.y, gd.z, gd.w}, ghv[4] = {gh.x, gh.y, gh.z, gh.w}, dd4[4] = {dv.x, dv.y, dv.z, dv.w};
           float du[4];
@@ -500,33 +446,25 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_bwd_kernel(const MmtWideBwdA
           if (c_ok) {
             const size_t q = e_b * T + t;
             *reinterpret_cast<float4*>((lower ? io.d_ul + q * LD : io.d_uh + q * HD) + c) = make_float4(du[0], du[1], du[2], du[3]);
-            wide_x_store4<P, kMRows>(a.x_du, KSU, e_row, (lower ? 0 : G.KLD) + c, du);
+            wide_x_store4<P, kMRows>(a.x_du, KSU, e.row, (lower ? 0 : G.KLD) + c, du);
           }
         }
         lds_barrier();
       }
-      MTRSSM_MMT_STAMP(5);
+      MTRSSM_WIDE_STAMP(5);
       if (!bar.sync(3 + 4 * t)) return;
-      MTRSSM_MMT_STAMP(6);
+      MTRSSM_WIDE_STAMP(6);
 
       // ============ R3: carries into step t-1: W_d^T du (kept by the workgroups of R2) | W_x^T du -> [s_l ; s_h] ============
       for (int u = blk; u < G.NTL + G.NTHd + NTS; u += nblk) {
         const bool is_s = u >= G.NTL + G.NTHd, lower = u < G.NTL;
-        const int c = (is_s ? u - G.NTL - G.NTHd : (lower ? u : u - G.NTL)) * 16 + e_cq;
-        int k0, k1;
-        krange(KSU, k0, k1);
-        wf32x4 acc[1][kMRT];
-#pragma unroll
-        for (int rt = 0; rt < kMRT; ++rt) acc[0][rt] = wf32x4{0.f, 0.f, 0.f, 0.f};
-        const uint4* const wt[1] = {a.pk_rnnt + (size_t)u * tile_u};
-        wide_mfma_stream<1, P, kMNS, kMRT>(acc, wt, a.x_du, KSU, k0, k1, lane);
-        wide_red_store<1, kMRT>(red, wave, 0, lane, acc[0]);
-        lds_barrier();
+        const int c = (is_s ? u - G.NTL - G.NTHd : (lower ? u : u - G.NTL)) * 16 + e.cq;
+        MTRSSM_WIDE_TILE_PRODUCT(P, kMNS, kMRT, a.pk_rnnt + (size_t)u * tile_u, a.x_du, KSU, KSU);
         {
-          const wf32x4 sm = wide_red_sum<1, kMRT>(red, 0, e_rt, e_slot);
+          const wf32x4 sm = wide_red_sum<1, kMRT>(red, 0, e.rt, e.slot);
           if (is_s) {
             if (e_valid) {
-              float* dst = a.cs + (size_t)e_row * LSHp + c;
+              float* dst = a.cs + (size_t)e.row * LSHp + c;
               wide_store_f2(dst, sm[0], sm[1]);
               wide_store_f2(dst + 2, sm[2], sm[3]);
               if (t == 0) {
@@ -551,9 +489,9 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_bwd_kernel(const MmtWideBwdA
         }
         lds_barrier();
       }
-      MTRSSM_MMT_STAMP(7);
+      MTRSSM_WIDE_STAMP(7);
       if (!bar.sync(4 + 4 * t)) return;
-      MTRSSM_MMT_STAMP(8);
+      MTRSSM_WIDE_STAMP(8);
     }
   }
 }
@@ -561,12 +499,7 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_bwd_kernel(const MmtWideBwdA
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-int debug_set_mmt_profile(void* buf) {
-  unsigned long long* p = static_cast<unsigned long long*>(buf);
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_mmt_prof), &p, sizeof(p)) == hipSuccess ? MTRSSM_OK : MTRSSM_ELAUNCH;
-}
-
-static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+int debug_set_mmt_profile(void* buf) { return wide_set_profile(&g_mmt_prof, buf); }
 
 static bool mmt_wide_dims_ok(const MtrssmMmtrssmDims* d) {
   if (!d || d->B <= 0 || d->T <= 0 || d->LD <= 0 || d->HD <= 0 || d->H <= 0 || d->KL <= 0 || d->CL <= 0 || d->KH <= 0 || d->CH <= 0 || !d->post)
@@ -592,16 +525,15 @@ struct MmtFwdLayout { size_t xs[2], xh[5], lg, exch_end, rnn, l0, l1[5], total; 
 static MmtFwdLayout mmt_fwd_layout(const MtrssmMmtrssmDims* d, int P) {
   const MmtWideGeom G(*d);
   MmtFwdLayout L;
-  size_t o = kWideCtl;
-  auto take = [&](size_t bytes) { const size_t r = o; o += al256(bytes); return r; };
-  for (int i = 0; i < 2; ++i) L.xs[i] = take(wide_x_uint4(G.KT, P, kMRows) * 16);
-  for (int i = 0; i < 5; ++i) L.xh[i] = take(wide_x_uint4(G.HK, P, kMRows) * 16);
-  L.lg = take((size_t)kMRows * (3 * G.LSp + 2 * G.HSp) * sizeof(float));
-  L.exch_end = o;
-  L.rnn = take(wide_pack_uint4(16 * (G.NTL + G.NTHd), G.KT, P) * 16);
-  L.l0 = take(wide_pack_uint4(5 * G.HP, G.KLD + G.KHD, P) * 16);
-  for (int i = 0; i < 5; ++i) L.l1[i] = take(wide_pack_uint4(i < 3 ? G.LS : G.HS, G.HK, P) * 16);
-  L.total = o;
+  WideBump at;
+  for (int i = 0; i < 2; ++i) L.xs[i] = at.take(wide_x_uint4(G.KT, P, kMRows) * 16);
+  for (int i = 0; i < 5; ++i) L.xh[i] = at.take(wide_x_uint4(G.HK, P, kMRows) * 16);
+  L.lg = at.take((size_t)kMRows * (3 * G.LSp + 2 * G.HSp) * sizeof(float));
+  L.exch_end = at.o;
+  L.rnn = at.take(wide_pack_uint4(16 * (G.NTL + G.NTHd), G.KT, P) * 16);
+  L.l0 = at.take(wide_pack_uint4(5 * G.HP, G.KLD + G.KHD, P) * 16);
+  for (int i = 0; i < 5; ++i) L.l1[i] = at.take(wide_pack_uint4(i < 3 ? G.LS : G.HS, G.HK, P) * 16);
+  L.total = at.o;
   return L;
 }
 size_t mmtrssm_wide_workspace_bytes(const MtrssmMmtrssmDims* d, int pieces) {
@@ -613,17 +545,16 @@ struct MmtBwdLayout { size_t x_dl[5], x_dz, x_du, cs, exch_end, l1t[5], l0t, rnn
 static MmtBwdLayout mmt_bwd_layout(const MtrssmMmtrssmDims* d, int P) {
   const MmtWideGeom G(*d);
   MmtBwdLayout L;
-  size_t o = kWideCtl;
-  auto take = [&](size_t bytes) { const size_t r = o; o += al256(bytes); return r; };
-  for (int i = 0; i < 5; ++i) L.x_dl[i] = take(wide_x_uint4(i < 3 ? G.LS : G.HS, P, kMRows) * 16);
-  L.x_dz = take(wide_x_uint4(5 * G.HK, P, kMRows) * 16);
-  L.x_du = take(wide_x_uint4(G.KLD + G.KHD, P, kMRows) * 16);
-  L.cs = take((size_t)kMRows * ((G.LS + G.HS + 15) / 16 * 16) * sizeof(float));
-  L.exch_end = o;
-  for (int i = 0; i < 5; ++i) L.l1t[i] = take(wide_pack_uint4(G.HP, i < 3 ? G.LS : G.HS, P) * 16);
-  L.l0t = take(wide_pack_uint4(16 * (G.NTL + G.NTHd), 5 * G.HK, P) * 16);
-  L.rnnt = take(wide_pack_uint4(16 * (G.NTL + G.NTHd) + (G.LS + G.HS + 15) / 16 * 16, G.KLD + G.KHD, P) * 16);
-  L.total = o;
+  WideBump at;
+  for (int i = 0; i < 5; ++i) L.x_dl[i] = at.take(wide_x_uint4(i < 3 ? G.LS : G.HS, P, kMRows) * 16);
+  L.x_dz = at.take(wide_x_uint4(5 * G.HK, P, kMRows) * 16);
+  L.x_du = at.take(wide_x_uint4(G.KLD + G.KHD, P, kMRows) * 16);
+  L.cs = at.take((size_t)kMRows * ((G.LS + G.HS + 15) / 16 * 16) * sizeof(float));
+  L.exch_end = at.o;
+  for (int i = 0; i < 5; ++i) L.l1t[i] = at.take(wide_pack_uint4(G.HP, i < 3 ? G.LS : G.HS, P) * 16);
+  L.l0t = at.take(wide_pack_uint4(16 * (G.NTL + G.NTHd), 5 * G.HK, P) * 16);
+  L.rnnt = at.take(wide_pack_uint4(16 * (G.NTL + G.NTHd) + (G.LS + G.HS + 15) / 16 * 16, G.KLD + G.KHD, P) * 16);
+  L.total = at.o;
   return L;
 }
 size_t mmtrssm_wide_bwd_workspace_bytes(const MtrssmMmtrssmDims* d, int pieces) {
@@ -631,27 +562,18 @@ size_t mmtrssm_wide_bwd_workspace_bytes(const MtrssmMmtrssmDims* d, int pieces) 
   return mmt_bwd_layout(d, pieces).total;
 }
 
-static int mmt_acquire_fence() {
-  static const int on = [] { const char* e = getenv("MTRSSM_WIDE_ACQUIRE"); return (e && e[0] == '1') ? 1 : 0; }();
-  return on;
-}
-
+// bytes of LDS the kernels lay out (wide_lds_bytes makes the launch's request of them)
 static size_t mmt_fwd_lds(const MmtWideGeom& G) {
-  const size_t need = (size_t)kWW * kMRT * kWave * 16 + ((size_t)5 * G.LSp + 3 * G.HSp + 256 + 8) * sizeof(float);
-  return need < 84 * 1024 ? 84 * 1024 : need;   // > 80 KiB: never two workgroups on one CU
+  return (size_t)kWW * kMRT * kWave * 16 + ((size_t)5 * G.LSp + 3 * G.HSp + 256 + 8) * sizeof(float);
 }
 static size_t mmt_bwd_lds(const MmtWideGeom& G) {
   const size_t LSHp = (G.LS + G.HS + 15) / 16 * 16;
-  const size_t need = (size_t)kWW * kMRT * kWave * 16 + ((size_t)8 * G.LSp + 4 * G.HSp + 2 * LSHp + 8) * sizeof(float);
-  return need < 84 * 1024 ? 84 * 1024 : need;
+  return (size_t)kWW * kMRT * kWave * 16 + ((size_t)8 * G.LSp + 4 * G.HSp + 2 * LSHp + 8) * sizeof(float);
 }
 
 int mmtrssm_wide_fwd_launch(const MtrssmMmtrssmDims* d, const MtrssmMmtrssmFwdWeights* w, const MtrssmMmtrssmFwdIO* io, int pieces,
                             void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  if (!mmtrssm_wide_supported(d, pieces)) {
-    set_error("mmtrssm_rollout_fwd_wide: dims / device outside the wide kernel's regime (ask mtrssm_mmtrssm_wide_supported first)");
-    return MTRSSM_EINVAL;
-  }
+  if (!mmtrssm_wide_supported(d, pieces)) return wide_not_supported("mmtrssm_rollout_fwd_wide", "mmtrssm");
   if (!w || !io || !workspace || !w->wxl_s_t || !w->wdl_t || !w->wxh_t || !w->wdh_t || !w->bh || !w->wl1_t || !w->bl1 || !w->wh1_t || !w->bh1 ||
       !w->wlp2 || !w->blp2 || !w->wa2 || !w->ba2 || !w->wv2 || !w->bv2 || !w->whp2 || !w->bhp2 || !w->whq2 || !w->bhq2 || !io->xl || !io->pa ||
       !io->pv || !io->deter_l0 || !io->deter_h0 || !io->hidden_l0 || !io->hidden_h0 || !io->stoch_l0 || !io->stoch_h0 || !io->u_post_l ||
@@ -661,10 +583,7 @@ int mmtrssm_wide_fwd_launch(const MtrssmMmtrssmDims* d, const MtrssmMmtrssmFwdWe
     return MTRSSM_EINVAL;
   }
   const MmtFwdLayout L = mmt_fwd_layout(d, pieces);
-  if (workspace_bytes < L.total || ((uintptr_t)workspace & 255)) {
-    set_error("mmtrssm_rollout_fwd_wide: workspace too small (%zu < %zu) or not 256-byte aligned", workspace_bytes, L.total);
-    return MTRSSM_EINVAL;
-  }
+  if (int rc = wide_check_workspace("mmtrssm_rollout_fwd_wide", workspace, workspace_bytes, L.total)) return rc;
   char* ws = static_cast<char*>(workspace);
   const MmtWideGeom G(*d);
   const int LD = G.LD, HD = G.HD, H = G.H, LS = G.LS, HS = G.HS, P = pieces;
@@ -705,34 +624,14 @@ int mmtrssm_wide_fwd_launch(const MtrssmMmtrssmDims* d, const MtrssmMmtrssmFwdWe
   a.lg = reinterpret_cast<float*>(ws + L.lg);
   a.ctl = ws; a.status = reinterpret_cast<int*>(ws);
   a.nblk = device_cu_count();
-  a.acquire = mmt_acquire_fence();
-  const size_t lds = mmt_fwd_lds(G);
-  if (lds > 160 * 1024) { set_error("mmtrssm_rollout_fwd_wide: %zu bytes of LDS", lds); return MTRSSM_ELDS; }
-  hipError_t e;
-#define MTRSSM_MMT_WIDE_FWD(PV, MV)                                                                                                        \
-  {                                                                                                                                   \
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(mmtrssm_wide_fwd_kernel<PV, MV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    if (e != hipSuccess) { set_error("hipFuncSetAttribute(max dynamic LDS=%zu): %s", lds, hipGetErrorString(e)); return MTRSSM_ELAUNCH; }     \
-    set_last_kernel("mtrssm::mmtrssm_wide_fwd_kernel<" #PV ", " #MV ">");                                                                      \
-    hipLaunchKernelGGL((mmtrssm_wide_fwd_kernel<PV, MV>), dim3(a.nblk), dim3(kWT), lds, stream, a);                                        \
-  }
-  if (io->modality) {
-    if (pieces == 3) MTRSSM_MMT_WIDE_FWD(3, true) else MTRSSM_MMT_WIDE_FWD(2, true)
-  } else {
-    if (pieces == 3) MTRSSM_MMT_WIDE_FWD(3, false) else MTRSSM_MMT_WIDE_FWD(2, false)
-  }
-#undef MTRSSM_MMT_WIDE_FWD
-  e = hipGetLastError();
-  if (e != hipSuccess) { set_error("wide MMTRSSM forward scan launch failed: %s", hipGetErrorString(e)); return MTRSSM_ELAUNCH; }
-  return MTRSSM_OK;
+  a.acquire = wide_acquire_fence();
+  static const WideKernel<MmtWideFwdArgs> kernels[2][2] = MTRSSM_WIDE_KERNELS(mmtrssm_wide_fwd_kernel);
+  return wide_launch(kernels, "mmtrssm_rollout_fwd_wide", "wide MMTRSSM forward scan", pieces, io->modality != nullptr, a, mmt_fwd_lds(G), stream);
 }
 
 int mmtrssm_wide_bwd_launch(const MtrssmMmtrssmDims* d, const MtrssmMmtrssmBwdWeights* w, const MtrssmMmtrssmBwdIO* io, int pieces,
                             void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  if (!mmtrssm_wide_supported(d, pieces)) {
-    set_error("mmtrssm_rollout_bwd_wide: dims / device outside the wide kernel's regime (ask mtrssm_mmtrssm_wide_supported first)");
-    return MTRSSM_EINVAL;
-  }
+  if (!mmtrssm_wide_supported(d, pieces)) return wide_not_supported("mmtrssm_rollout_bwd_wide", "mmtrssm");
   if (!w || !io || !workspace || !w->wxl_s_t || !w->wdl || !w->wxh_t || !w->wdh || !w->wl1 || !w->wh1 || !w->wlp2 || !w->wa2 || !w->wv2 ||
       !w->whp2 || !w->whq2 || !io->deter_l0 || !io->deter_h0 || !io->deter_l || !io->deter_h || !io->prior_logits_l || !io->prior_logits_h ||
       !io->post_logits_l || !io->post_logits_h || !io->sv_l1 || !io->sv_h1 || !io->sv_la || !io->sv_lv || !io->g_deter_l0 || !io->g_deter_h0 ||
@@ -742,10 +641,7 @@ int mmtrssm_wide_bwd_launch(const MtrssmMmtrssmDims* d, const MtrssmMmtrssmBwdWe
     return MTRSSM_EINVAL;
   }
   const MmtBwdLayout L = mmt_bwd_layout(d, pieces);
-  if (workspace_bytes < L.total || ((uintptr_t)workspace & 255)) {
-    set_error("mmtrssm_rollout_bwd_wide: workspace too small (%zu < %zu) or not 256-byte aligned", workspace_bytes, L.total);
-    return MTRSSM_EINVAL;
-  }
+  if (int rc = wide_check_workspace("mmtrssm_rollout_bwd_wide", workspace, workspace_bytes, L.total)) return rc;
   char* ws = static_cast<char*>(workspace);
   const MmtWideGeom G(*d);
   const int LD = G.LD, HD = G.HD, H = G.H, LS = G.LS, HS = G.HS, P = pieces;
@@ -785,26 +681,9 @@ int mmtrssm_wide_bwd_launch(const MtrssmMmtrssmDims* d, const MtrssmMmtrssmBwdWe
   a.cs = reinterpret_cast<float*>(ws + L.cs);
   a.ctl = ws; a.status = reinterpret_cast<int*>(ws);
   a.nblk = device_cu_count();
-  a.acquire = mmt_acquire_fence();
-  const size_t lds = mmt_bwd_lds(G);
-  if (lds > 160 * 1024) { set_error("mmtrssm_rollout_bwd_wide: %zu bytes of LDS", lds); return MTRSSM_ELDS; }
-  hipError_t e;
-#define MTRSSM_MMT_WIDE_BWD(PV, MV)                                                                                                        \
-  {                                                                                                                                   \
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(mmtrssm_wide_bwd_kernel<PV, MV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    if (e != hipSuccess) { set_error("hipFuncSetAttribute(max dynamic LDS=%zu): %s", lds, hipGetErrorString(e)); return MTRSSM_ELAUNCH; }     \
-    set_last_kernel("mtrssm::mmtrssm_wide_bwd_kernel<" #PV ", " #MV ">");                                                                      \
-    hipLaunchKernelGGL((mmtrssm_wide_bwd_kernel<PV, MV>), dim3(a.nblk), dim3(kWT), lds, stream, a);                                        \
-  }
-  if (io->modality) {
-    if (pieces == 3) MTRSSM_MMT_WIDE_BWD(3, true) else MTRSSM_MMT_WIDE_BWD(2, true)
-  } else {
-    if (pieces == 3) MTRSSM_MMT_WIDE_BWD(3, false) else MTRSSM_MMT_WIDE_BWD(2, false)
-  }
-#undef MTRSSM_MMT_WIDE_BWD
-  e = hipGetLastError();
-  if (e != hipSuccess) { set_error("wide MMTRSSM backward scan launch failed: %s", hipGetErrorString(e)); return MTRSSM_ELAUNCH; }
-  return MTRSSM_OK;
+  a.acquire = wide_acquire_fence();
+  static const WideKernel<MmtWideBwdArgs> kernels[2][2] = MTRSSM_WIDE_KERNELS(mmtrssm_wide_bwd_kernel);
+  return wide_launch(kernels, "mmtrssm_rollout_bwd_wide", "wide MMTRSSM backward scan", pieces, io->modality != nullptr, a, mmt_bwd_lds(G), stream);
 }
 
 }  // namespace mtrssm

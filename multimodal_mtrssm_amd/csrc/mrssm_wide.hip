@@ -13,15 +13,9 @@
 // R2 dd = g + carry + Wh1^T dzh and the gate gradients; R3 carry_d += W_hh^T dgh | dz1 = act'(h1) (W_ih W2)^T dgi;
 // R4 carry_s = W1s^T dz1.  As in the four-CU cluster kernels the GRU input path is fused (wf_t = (W_ih W2)^T, sv_h2 / d_h2
 // are not produced: the caller forms them as batched GEMMs).
-#include <cstdlib>
-
 #include "wide_common.h"
 
 namespace mtrssm {
-
-void set_error(const char* fmt, ...);
-void set_last_kernel(const char* name);
-int device_cu_count();
 
 // ------------------------------------------------------------------------------------------------
 // weight packing (once per launch: the weights change every optimizer step)
@@ -60,10 +54,7 @@ WidePackJob wide_make_block(const float* src, long sn, long sk, int N, int K, in
   j.nskip = nskip; j.kskip = kskip; j.nt0 = nt0; j.ks0 = ks0; j.KST = KST;
   return j;
 }
-static WidePackJob make_job(const float* src, long sn, long sk, int N, int K, uint4* dst) { return wide_make_job(src, sn, sk, N, K, dst); }
 
-int wide_launch_pack(const WidePackJobs& jobs, int pieces, hipStream_t stream);
-static int launch_pack(const WidePackJobs& jobs, int pieces, hipStream_t stream) { return wide_launch_pack(jobs, pieces, stream); }
 int wide_launch_pack(const WidePackJobs& jobs, int pieces, hipStream_t stream) {
   dim3 grid(256, jobs.count);
   if (pieces == 3) hipLaunchKernelGGL(wide_pack_kernel<3>, grid, dim3(256), 0, stream, jobs);
@@ -73,13 +64,7 @@ int wide_launch_pack(const WidePackJobs& jobs, int pieces, hipStream_t stream) {
   return MTRSSM_OK;
 }
 
-// Development aid (tools/wide_probe.py): when set, lane 0 of EVERY workgroup stamps s_memrealtime (100 MHz) at the phase
-// boundaries of timesteps 8..11 of the first row tile into this buffer: [workgroup][step - 8][16 stamps].  Null in normal use.
-__device__ unsigned long long* g_wide_prof = nullptr;
-#define MTRSSM_WIDE_STAMP(i)                                                                                              \
-  do {                                                                                                                    \
-    if (prof && tstamp >= 8 && tstamp < 12) prof[((size_t)blockIdx.x * 4 + (tstamp - 8)) * 16 + (i)] = __builtin_amdgcn_s_memrealtime(); \
-  } while (0)
+__device__ unsigned long long* g_wide_prof = nullptr;   // MTRSSM_WIDE_STAMP's buffer (tools/wide_probe.py fwd | bwd)
 
 // ------------------------------------------------------------------------------------------------
 // forward
@@ -122,18 +107,18 @@ __global__ __launch_bounds__(kWT) void mrssm_wide_fwd_kernel(const WideFwdArgs a
   WideBarrier bar;
   bar.init(a.ctl, a.status, abort_flag, nblk, blk, a.acquire != 0);
 
-  const int ks0h = KSH * wave / kWW, ks1h = KSH * (wave + 1) / kWW;
-  const int ks0d = KSD * wave / kWW, ks1d = KSD * (wave + 1) / kWW;
+  int ks0h, ks1h, ks0d, ks1d;   // phase B's two operand streams
+  wide_krange(KSH, wave, ks0h, ks1h);
+  wide_krange(KSD, wave, ks0d, ks1d);
   const size_t tileH = (size_t)KSH * P * 64, tileD = (size_t)KSD * P * 64;   // uint4 per packed n-tile (K = H / K = D)
 
-  // epilogue item of this thread (threads 0..127): row tile, lane slot -> batch row of the tile, four consecutive columns
-  const int e_rt = tid >> 6, e_slot = lane, e_row = 16 * e_rt + (e_slot & 15), e_cq = 4 * (e_slot >> 4);
+  const WideEpi e(tid);   // threads 0..127: the two row tiles
   const bool e_thread = tid < 2 * kWave;
 
   for (int rb = 0; rb < B; rb += kWRows) {
     const int nrows = B - rb < kWRows ? B - rb : kWRows;
-    const bool e_valid = e_thread && e_row < nrows;
-    const size_t e_b = (size_t)(rb + (e_row < nrows ? e_row : 0));
+    const bool e_valid = e_thread && e.row < nrows;
+    const size_t e_b = (size_t)(rb + (e.row < nrows ? e.row : 0));
     // ---- set-up of the tile: x_d[0] <- deter0 (every workgroup converts a slice), zero rows beyond the batch
     for (int i = blk * kWT + tid; i < kWRows * (D / 4); i += nblk * kWT) {
       const int row = i / (D / 4), k = (i - row * (D / 4)) * 4;
@@ -159,7 +144,7 @@ __global__ __launch_bounds__(kWT) void mrssm_wide_fwd_kernel(const WideFwdArgs a
     // the deter columns this workgroup owns in phase B live in registers across the steps
     float dprev[4] = {0.f, 0.f, 0.f, 0.f};
     if (blk < NTD && e_valid) {
-      const float4 q = *reinterpret_cast<const float4*>(io.deter0 + e_b * D + blk * 16 + e_cq);
+      const float4 q = *reinterpret_cast<const float4*>(io.deter0 + e_b * D + blk * 16 + e.cq);
       dprev[0] = q.x; dprev[1] = q.y; dprev[2] = q.z; dprev[3] = q.w;
     }
     int cur = 0;
@@ -283,9 +268,9 @@ __global__ __launch_bounds__(kWT) void mrssm_wide_fwd_kernel(const WideFwdArgs a
         wide_red_store<4>(red, wave, 3, lane, accB[2]);
         lds_barrier();
         if (e_thread) {
-          const wf32x4 sr = wide_red_sum<4>(red, 0, e_rt, e_slot), sz = wide_red_sum<4>(red, 1, e_rt, e_slot);
-          const wf32x4 sni = wide_red_sum<4>(red, 2, e_rt, e_slot), snh = wide_red_sum<4>(red, 3, e_rt, e_slot);
-          const int c = u * 16 + e_cq;
+          const wf32x4 sr = wide_red_sum<4>(red, 0, e.rt, e.slot), sz = wide_red_sum<4>(red, 1, e.rt, e.slot);
+          const wf32x4 sni = wide_red_sum<4>(red, 2, e.rt, e.slot), snh = wide_red_sum<4>(red, 3, e.rt, e.slot);
+          const int c = u * 16 + e.cq;
           float rg[4], zg[4], ng[4], gn[4], dn[4];
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
@@ -308,7 +293,7 @@ __global__ __launch_bounds__(kWT) void mrssm_wide_fwd_kernel(const WideFwdArgs a
               *reinterpret_cast<float4*>(gs + 2 * D) = make_float4(ng[0], ng[1], ng[2], ng[3]);
               *reinterpret_cast<float4*>(gs + 3 * D) = make_float4(gn[0], gn[1], gn[2], gn[3]);
             }
-            wide_x_store4<P>(a.x_d[cur ^ 1], KSD, e_row, c, dn);
+            wide_x_store4<P>(a.x_d[cur ^ 1], KSD, e.row, c, dn);
           }
         }
         lds_barrier();
@@ -320,22 +305,18 @@ __global__ __launch_bounds__(kWT) void mrssm_wide_fwd_kernel(const WideFwdArgs a
 
       // ============ phase C: head layer 0 on the new deter, one workgroup per 16 of the 3H columns ============
       for (int u = blk; u < 3 * NTH; u += nblk) {
-        const int which = u / NTH, c = (u - which * NTH) * 16 + e_cq;
+        const int which = u / NTH, c = (u - which * NTH) * 16 + e.cq;
         float4 pin = make_float4(0.f, 0.f, 0.f, 0.f);
         if (e_valid) {
           if (which == 0) pin = *reinterpret_cast<const float4*>(w.b3 + c);
           else pin = *reinterpret_cast<const float4*>((which == 1 ? io.pa : io.pv) + (e_b * T + t) * H + c);
         }
-        wf32x4 acc[1][2] = {{wf32x4{0.f, 0.f, 0.f, 0.f}, wf32x4{0.f, 0.f, 0.f, 0.f}}};
-        const uint4* const wt[1] = {a.pk_wh1 + (size_t)u * tileD};
-        wide_mfma_stream<1, P, kNS1>(acc, wt, a.x_d[cur], KSD, ks0d, ks1d, lane);
-        wide_red_store<1>(red, wave, 0, lane, acc[0]);
-        lds_barrier();
+        wide_tile_product<P, kNS1, 2>(red, a.pk_wh1 + (size_t)u * tileD, a.x_d[cur], KSD, wave, lane);
         if (e_valid) {
-          const wf32x4 sm = wide_red_sum<1>(red, 0, e_rt, e_slot);
+          const wf32x4 sm = wide_red_sum<1>(red, 0, e.rt, e.slot);
           float h[4] = {act_fwd(sm[0] + pin.x, act), act_fwd(sm[1] + pin.y, act), act_fwd(sm[2] + pin.z, act), act_fwd(sm[3] + pin.w, act)};
           if (io.sv_heads) *reinterpret_cast<float4*>(io.sv_heads + (e_b * T + t) * 3 * H + which * H + c) = make_float4(h[0], h[1], h[2], h[3]);
-          wide_x_store4<P>(a.x_hd[which], KSH, e_row, c, h);
+          wide_x_store4<P>(a.x_hd[which], KSH, e.row, c, h);
         }
         lds_barrier();
       }
@@ -346,14 +327,10 @@ __global__ __launch_bounds__(kWT) void mrssm_wide_fwd_kernel(const WideFwdArgs a
       // ============ phase D: head layer 1, one workgroup per 16 logits ============
       for (int u = blk; u < 3 * NTS; u += nblk) {
         const int which = u / NTS, st = u - which * NTS;
-        wf32x4 acc[1][2] = {{wf32x4{0.f, 0.f, 0.f, 0.f}, wf32x4{0.f, 0.f, 0.f, 0.f}}};
-        const uint4* const wt[1] = {a.pk_h2[which] + (size_t)st * tileH};
-        wide_mfma_stream<1, P, kNS1>(acc, wt, a.x_hd[which], KSH, ks0h, ks1h, lane);
-        wide_red_store<1>(red, wave, 0, lane, acc[0]);
-        lds_barrier();
+        wide_tile_product<P, kNS1, 2>(red, a.pk_h2[which] + (size_t)st * tileH, a.x_hd[which], KSH, wave, lane);
         if (e_valid) {
-          const wf32x4 sm = wide_red_sum<1>(red, 0, e_rt, e_slot);
-          float* dst = a.lg + ((size_t)e_row * 3 + which) * Sp + st * 16 + e_cq;
+          const wf32x4 sm = wide_red_sum<1>(red, 0, e.rt, e.slot);
+          float* dst = a.lg + ((size_t)e.row * 3 + which) * Sp + st * 16 + e.cq;
           wide_store_f2(dst, sm[0], sm[1]);
           wide_store_f2(dst + 2, sm[2], sm[3]);
         }
@@ -406,15 +383,14 @@ __global__ __launch_bounds__(kWT) void mrssm_wide_bwd_kernel(const WideBwdArgs a
   WideBarrier bar;
   bar.init(a.ctl, a.status, abort_flag, nblk, blk, a.acquire != 0);
 
-  auto krange = [&](int KS, int& k0, int& k1) { k0 = KS * wave / kWW; k1 = KS * (wave + 1) / kWW; };
   const size_t tileS = (size_t)KSS * P * 64, tile3H = (size_t)KS3H * P * 64, tile3D = (size_t)KS3D * P * 64, tileH = (size_t)KSH * P * 64;
-  const int e_rt = tid >> 6, e_slot = lane, e_row = 16 * e_rt + (e_slot & 15), e_cq = 4 * (e_slot >> 4);
+  const WideEpi e(tid);
   const bool e_thread = tid < 2 * kWave;
 
   for (int rb = 0; rb < B; rb += kWRows) {
     const int nrows = B - rb < kWRows ? B - rb : kWRows;
-    const bool e_valid = e_thread && e_row < nrows;
-    const size_t e_b = (size_t)(rb + (e_row < nrows ? e_row : 0));
+    const bool e_valid = e_thread && e.row < nrows;
+    const size_t e_b = (size_t)(rb + (e.row < nrows ? e.row : 0));
     // rows beyond the batch: zero in every exchange vector (each workgroup clears a slice)
     {
       const float z4[4] = {0.f, 0.f, 0.f, 0.f};
@@ -493,22 +469,16 @@ __global__ __launch_bounds__(kWT) void mrssm_wide_bwd_kernel(const WideBwdArgs a
 
       // ============ R1: dzh = act'(hd) * (W2nd^T dl), one workgroup per 16 of the 3H head units ============
       for (int u = blk; u < 3 * NTH; u += nblk) {
-        const int which = u / NTH, c = (u - which * NTH) * 16 + e_cq;
+        const int which = u / NTH, c = (u - which * NTH) * 16 + e.cq;
         float4 hd = make_float4(0.f, 0.f, 0.f, 0.f);
         if (e_valid) hd = *reinterpret_cast<const float4*>(io.sv_heads + (e_b * T + t) * 3 * H + which * H + c);
-        int k0, k1;
-        krange(KSS, k0, k1);
-        wf32x4 acc[1][2] = {{wf32x4{0.f, 0.f, 0.f, 0.f}, wf32x4{0.f, 0.f, 0.f, 0.f}}};
-        const uint4* const wt[1] = {a.pk_h2t[which] + (size_t)(u - which * NTH) * tileS};
-        wide_mfma_stream<1, P, kNS1>(acc, wt, a.x_dl[which], KSS, k0, k1, lane);
-        wide_red_store<1>(red, wave, 0, lane, acc[0]);
-        lds_barrier();
+        wide_tile_product<P, kNS1, 2>(red, a.pk_h2t[which] + (size_t)(u - which * NTH) * tileS, a.x_dl[which], KSS, wave, lane);
         if (e_valid) {
-          const wf32x4 sm = wide_red_sum<1>(red, 0, e_rt, e_slot);
+          const wf32x4 sm = wide_red_sum<1>(red, 0, e.rt, e.slot);
           float g[4] = {sm[0] * act_grad_from_out(hd.x, act), sm[1] * act_grad_from_out(hd.y, act), sm[2] * act_grad_from_out(hd.z, act),
                         sm[3] * act_grad_from_out(hd.w, act)};
           *reinterpret_cast<float4*>(io.d_zh + (e_b * T + t) * 3 * H + which * H + c) = make_float4(g[0], g[1], g[2], g[3]);
-          wide_x_store4<P>(a.x_dzh, KS3H, e_row, which * H + c, g);
+          wide_x_store4<P>(a.x_dzh, KS3H, e.row, which * H + c, g);
         }
         lds_barrier();
       }
@@ -518,7 +488,7 @@ __global__ __launch_bounds__(kWT) void mrssm_wide_bwd_kernel(const WideBwdArgs a
 
       // ============ R2: dd = g_deter + carry + Wh1^T dzh, GRU gate gradients; one workgroup per 16 deter columns ============
       for (int u = blk; u < NTD; u += nblk) {
-        const int c = u * 16 + e_cq;
+        const int c = u * 16 + e.cq;
         float4 gd = make_float4(0.f, 0.f, 0.f, 0.f), rg4 = gd, zg4 = gd, ng4 = gd, gn4 = gd, dp4 = gd;
         if (e_valid) {
           const size_t q = e_b * T + t;
@@ -530,15 +500,9 @@ __global__ __launch_bounds__(kWT) void mrssm_wide_bwd_kernel(const WideBwdArgs a
           gn4 = *reinterpret_cast<const float4*>(gs + 3 * D);
           dp4 = *reinterpret_cast<const float4*>(t > 0 ? io.deter + (q - 1) * D + c : io.deter0 + e_b * D + c);
         }
-        int k0, k1;
-        krange(KS3H, k0, k1);
-        wf32x4 acc[1][2] = {{wf32x4{0.f, 0.f, 0.f, 0.f}, wf32x4{0.f, 0.f, 0.f, 0.f}}};
-        const uint4* const wt[1] = {a.pk_wh1t + (size_t)u * tile3H};
-        wide_mfma_stream<1, P, kNS1>(acc, wt, a.x_dzh, KS3H, k0, k1, lane);
-        wide_red_store<1>(red, wave, 0, lane, acc[0]);
-        lds_barrier();
+        wide_tile_product<P, kNS1, 2>(red, a.pk_wh1t + (size_t)u * tile3H, a.x_dzh, KS3H, wave, lane);
         if (e_valid) {
-          const wf32x4 sm = wide_red_sum<1>(red, 0, e_rt, e_slot);
+          const wf32x4 sm = wide_red_sum<1>(red, 0, e.rt, e.slot);
           const float rg[4] = {rg4.x, rg4.y, rg4.z, rg4.w}, zg[4] = {zg4.x, zg4.y, zg4.z, zg4.w}, ng[4] = {ng4.x, ng4.y, ng4.z, ng4.w};
           const float gn[4] = {gn4.x, gn4.y, gn4.z, gn4.w}, dp[4] = {dp4.x, dp4.y, dp4.z, dp4.w}, gdv[4] = {gd.x, gd.y, gd.z, gd.w};
           float gi[3][4], gh[3][4];
@@ -560,8 +524,8 @@ __global__ __launch_bounds__(kWT) void mrssm_wide_bwd_kernel(const WideBwdArgs a
           for (int g = 0; g < 3; ++g) {
             *reinterpret_cast<float4*>(io.d_gi + q * 3 * D + g * D + c) = make_float4(gi[g][0], gi[g][1], gi[g][2], gi[g][3]);
             *reinterpret_cast<float4*>(io.d_gh + q * 3 * D + g * D + c) = make_float4(gh[g][0], gh[g][1], gh[g][2], gh[g][3]);
-            wide_x_store4<P>(a.x_dgi, KS3D, e_row, g * D + c, gi[g]);
-            wide_x_store4<P>(a.x_dgh, KS3D, e_row, g * D + c, gh[g]);
+            wide_x_store4<P>(a.x_dgi, KS3D, e.row, g * D + c, gi[g]);
+            wide_x_store4<P>(a.x_dgh, KS3D, e.row, g * D + c, gh[g]);
           }
         }
         lds_barrier();
@@ -573,18 +537,12 @@ __global__ __launch_bounds__(kWT) void mrssm_wide_bwd_kernel(const WideBwdArgs a
       // ============ R3: carry_d = dd z + W_hh^T dgh (the workgroups of R2)  |  dz1 = act'(h1) (W_ih W2)^T dgi ============
       for (int u = blk; u < NTD + NTH; u += nblk) {
         const bool is_cd = u < NTD;
-        const int c = (is_cd ? u : u - NTD) * 16 + e_cq;
+        const int c = (is_cd ? u : u - NTD) * 16 + e.cq;
         float4 h1 = make_float4(0.f, 0.f, 0.f, 0.f);
         if (!is_cd && e_valid) h1 = *reinterpret_cast<const float4*>(io.sv_h1 + (e_b * T + t) * H + c);
-        int k0, k1;
-        krange(KS3D, k0, k1);
-        wf32x4 acc[1][2] = {{wf32x4{0.f, 0.f, 0.f, 0.f}, wf32x4{0.f, 0.f, 0.f, 0.f}}};
-        const uint4* const wt[1] = {is_cd ? a.pk_whht + (size_t)u * tile3D : a.pk_wft + (size_t)(u - NTD) * tile3D};
-        wide_mfma_stream<1, P, kNS1>(acc, wt, is_cd ? a.x_dgh : a.x_dgi, KS3D, k0, k1, lane);
-        wide_red_store<1>(red, wave, 0, lane, acc[0]);
-        lds_barrier();
+        wide_tile_product<P, kNS1, 2>(red, is_cd ? a.pk_whht + (size_t)u * tile3D : a.pk_wft + (size_t)(u - NTD) * tile3D, is_cd ? a.x_dgh : a.x_dgi, KS3D, wave, lane);
         if (e_valid) {
-          const wf32x4 sm = wide_red_sum<1>(red, 0, e_rt, e_slot);
+          const wf32x4 sm = wide_red_sum<1>(red, 0, e.rt, e.slot);
           if (is_cd) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) cd[j] = ddz[j] + sm[j];
@@ -593,7 +551,7 @@ __global__ __launch_bounds__(kWT) void mrssm_wide_bwd_kernel(const WideBwdArgs a
             float g[4] = {sm[0] * act_grad_from_out(h1.x, act), sm[1] * act_grad_from_out(h1.y, act), sm[2] * act_grad_from_out(h1.z, act),
                           sm[3] * act_grad_from_out(h1.w, act)};
             *reinterpret_cast<float4*>(io.d_z1 + (e_b * T + t) * H + c) = make_float4(g[0], g[1], g[2], g[3]);
-            wide_x_store4<P>(a.x_dz1, KSH, e_row, c, g);
+            wide_x_store4<P>(a.x_dz1, KSH, e.row, c, g);
           }
         }
         lds_barrier();
@@ -604,17 +562,11 @@ __global__ __launch_bounds__(kWT) void mrssm_wide_bwd_kernel(const WideBwdArgs a
 
       // ============ R4: carry_s = W1s^T dz1, one workgroup per 16 stochastic units ============
       for (int u = blk; u < NTS; u += nblk) {
-        int k0, k1;
-        krange(KSH, k0, k1);
-        wf32x4 acc[1][2] = {{wf32x4{0.f, 0.f, 0.f, 0.f}, wf32x4{0.f, 0.f, 0.f, 0.f}}};
-        const uint4* const wt[1] = {a.pk_w1s + (size_t)u * tileH};
-        wide_mfma_stream<1, P, kNS1>(acc, wt, a.x_dz1, KSH, k0, k1, lane);
-        wide_red_store<1>(red, wave, 0, lane, acc[0]);
-        lds_barrier();
+        wide_tile_product<P, kNS1, 2>(red, a.pk_w1s + (size_t)u * tileH, a.x_dz1, KSH, wave, lane);
         if (e_valid) {
-          const wf32x4 sm = wide_red_sum<1>(red, 0, e_rt, e_slot);
-          const int s0 = u * 16 + e_cq;
-          float* dst = a.cs + (size_t)e_row * Sp + s0;
+          const wf32x4 sm = wide_red_sum<1>(red, 0, e.rt, e.slot);
+          const int s0 = u * 16 + e.cq;
+          float* dst = a.cs + (size_t)e.row * Sp + s0;
           wide_store_f2(dst, sm[0], sm[1]);
           wide_store_f2(dst + 2, sm[2], sm[3]);
           if (t == 0) {
@@ -635,12 +587,7 @@ __global__ __launch_bounds__(kWT) void mrssm_wide_bwd_kernel(const WideBwdArgs a
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-int debug_set_wide_profile(void* buf) {
-  unsigned long long* p = static_cast<unsigned long long*>(buf);
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_wide_prof), &p, sizeof(p)) == hipSuccess ? MTRSSM_OK : MTRSSM_ELAUNCH;
-}
-
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+int debug_set_wide_profile(void* buf) { return wide_set_profile(&g_wide_prof, buf); }
 
 static bool wide_dims_ok(const MtrssmMrssmDims* d) {
   if (!d || d->B <= 0 || d->T <= 0 || d->D <= 0 || d->H <= 0 || d->K <= 0 || d->C <= 0 || !d->post) return false;
@@ -667,18 +614,17 @@ struct WideFwdLayout {
 static WideFwdLayout wide_fwd_layout(const MtrssmMrssmDims* d, int P) {
   const int D = d->D, H = d->H, S = d->K * d->C, Sp = (S + 15) / 16 * 16;
   WideFwdLayout L;
-  size_t o = kWideCtl;
-  auto take = [&](size_t bytes) { const size_t r = o; o += align256(bytes); return r; };
-  L.x_h1 = take(wide_x_uint4(H, P) * 16);
-  L.x_d[0] = take(wide_x_uint4(D, P) * 16);
-  L.x_d[1] = take(wide_x_uint4(D, P) * 16);
-  for (int q = 0; q < 3; ++q) L.x_hd[q] = take(wide_x_uint4(H, P) * 16);
-  L.lg = take((size_t)kWRows * 3 * Sp * sizeof(float));
-  L.wf = take(wide_pack_uint4(3 * D, H, P) * 16);
-  L.whh = take(wide_pack_uint4(3 * D, D, P) * 16);
-  L.wh1 = take(wide_pack_uint4(3 * H, D, P) * 16);
-  for (int q = 0; q < 3; ++q) L.h2[q] = take(wide_pack_uint4(S, H, P) * 16);
-  L.total = o;
+  WideBump at;
+  L.x_h1 = at.take(wide_x_uint4(H, P) * 16);
+  L.x_d[0] = at.take(wide_x_uint4(D, P) * 16);
+  L.x_d[1] = at.take(wide_x_uint4(D, P) * 16);
+  for (int q = 0; q < 3; ++q) L.x_hd[q] = at.take(wide_x_uint4(H, P) * 16);
+  L.lg = at.take((size_t)kWRows * 3 * Sp * sizeof(float));
+  L.wf = at.take(wide_pack_uint4(3 * D, H, P) * 16);
+  L.whh = at.take(wide_pack_uint4(3 * D, D, P) * 16);
+  L.wh1 = at.take(wide_pack_uint4(3 * H, D, P) * 16);
+  for (int q = 0; q < 3; ++q) L.h2[q] = at.take(wide_pack_uint4(S, H, P) * 16);
+  L.total = at.o;
   return L;
 }
 size_t mrssm_wide_workspace_bytes(const MtrssmMrssmDims* d, int pieces) {
@@ -692,20 +638,19 @@ struct WideBwdLayout {
 static WideBwdLayout wide_bwd_layout(const MtrssmMrssmDims* d, int P) {
   const int D = d->D, H = d->H, S = d->K * d->C, Sp = (S + 15) / 16 * 16;
   WideBwdLayout L;
-  size_t o = kWideCtl;
-  auto take = [&](size_t bytes) { const size_t r = o; o += align256(bytes); return r; };
-  for (int q = 0; q < 3; ++q) L.x_dl[q] = take(wide_x_uint4(Sp, P) * 16);
-  L.x_dzh = take(wide_x_uint4(3 * H, P) * 16);
-  L.x_dgi = take(wide_x_uint4(3 * D, P) * 16);
-  L.x_dgh = take(wide_x_uint4(3 * D, P) * 16);
-  L.x_dz1 = take(wide_x_uint4(H, P) * 16);
-  L.cs = take((size_t)kWRows * Sp * sizeof(float));
-  for (int q = 0; q < 3; ++q) L.h2t[q] = take(wide_pack_uint4(H, S, P) * 16);
-  L.wh1t = take(wide_pack_uint4(D, 3 * H, P) * 16);
-  L.whht = take(wide_pack_uint4(D, 3 * D, P) * 16);
-  L.wft = take(wide_pack_uint4(H, 3 * D, P) * 16);
-  L.w1s = take(wide_pack_uint4(S, H, P) * 16);
-  L.total = o;
+  WideBump at;
+  for (int q = 0; q < 3; ++q) L.x_dl[q] = at.take(wide_x_uint4(Sp, P) * 16);
+  L.x_dzh = at.take(wide_x_uint4(3 * H, P) * 16);
+  L.x_dgi = at.take(wide_x_uint4(3 * D, P) * 16);
+  L.x_dgh = at.take(wide_x_uint4(3 * D, P) * 16);
+  L.x_dz1 = at.take(wide_x_uint4(H, P) * 16);
+  L.cs = at.take((size_t)kWRows * Sp * sizeof(float));
+  for (int q = 0; q < 3; ++q) L.h2t[q] = at.take(wide_pack_uint4(H, S, P) * 16);
+  L.wh1t = at.take(wide_pack_uint4(D, 3 * H, P) * 16);
+  L.whht = at.take(wide_pack_uint4(D, 3 * D, P) * 16);
+  L.wft = at.take(wide_pack_uint4(H, 3 * D, P) * 16);
+  L.w1s = at.take(wide_pack_uint4(S, H, P) * 16);
+  L.total = at.o;
   return L;
 }
 size_t mrssm_wide_bwd_workspace_bytes(const MtrssmMrssmDims* d, int pieces) {
@@ -713,34 +658,19 @@ size_t mrssm_wide_bwd_workspace_bytes(const MtrssmMrssmDims* d, int pieces) {
   return wide_bwd_layout(d, pieces).total;
 }
 
-// MTRSSM_WIDE_ACQUIRE=1: an agent-scope acquire fence after every grid barrier on top of the sc1 loads (A/B runs)
-static int wide_acquire_fence() {
-  static const int on = [] { const char* e = getenv("MTRSSM_WIDE_ACQUIRE"); return (e && e[0] == '1') ? 1 : 0; }();
-  return on;
-}
-
-static int wide_grid(const MtrssmMrssmDims* d) {
-  (void)d;
-  return device_cu_count();   // one workgroup per CU (each asks for more than half a CU's LDS)
-}
-
+// bytes of LDS the kernels lay out (wide_lds_bytes makes the launch's request of them)
 static size_t wide_fwd_lds(const MtrssmMrssmDims* d) {
   const int Sp = (d->K * d->C + 15) / 16 * 16;
-  size_t need = (size_t)kWW * 4 * 2 * kWave * 16 + ((size_t)5 * Sp + 128 + 4 + 64) * sizeof(float);
-  return need < 84 * 1024 ? 84 * 1024 : need;    // > 80 KiB: never two workgroups on one CU
+  return (size_t)kWW * 4 * 2 * kWave * 16 + ((size_t)5 * Sp + 128 + 4 + 64) * sizeof(float);
 }
 static size_t wide_bwd_lds(const MtrssmMrssmDims* d) {
   const int Sp = (d->K * d->C + 15) / 16 * 16;
-  size_t need = (size_t)kWW * 1 * 2 * kWave * 16 + ((size_t)10 * Sp + 4) * sizeof(float);
-  return need < 84 * 1024 ? 84 * 1024 : need;
+  return (size_t)kWW * 1 * 2 * kWave * 16 + ((size_t)10 * Sp + 4) * sizeof(float);
 }
 
 int mrssm_wide_fwd_launch(const MtrssmMrssmDims* d, const MtrssmMrssmClusterWeights* w, const MtrssmMrssmFwdIO* io, int pieces,
                           void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  if (!mrssm_wide_supported(d, pieces)) {
-    set_error("mrssm_rollout_fwd_wide: dims / device outside the wide kernel's regime (ask mtrssm_mrssm_wide_supported first)");
-    return MTRSSM_EINVAL;
-  }
+  if (!mrssm_wide_supported(d, pieces)) return wide_not_supported("mrssm_rollout_fwd_wide", "mrssm");
   if (!w || !io || !workspace || !w->w1s_t || !w->wf_t || !w->bf || !w->whh_t || !w->bhh || !w->wh1_t || !w->b3 || !w->w4 || !w->b4 ||
       !w->wa2 || !w->ba2 || !w->wv2 || !w->bv2 || !io->xa || !io->pa || !io->pv || !io->deter0 || !io->stoch0 || !io->u_post ||
       !io->deter || !io->prior_logits || !io->post_logits || !io->post_stoch) {
@@ -748,23 +678,20 @@ int mrssm_wide_fwd_launch(const MtrssmMrssmDims* d, const MtrssmMrssmClusterWeig
     return MTRSSM_EINVAL;
   }
   const WideFwdLayout L = wide_fwd_layout(d, pieces);
-  if (workspace_bytes < L.total || ((uintptr_t)workspace & 255)) {
-    set_error("mrssm_rollout_fwd_wide: workspace too small (%zu < %zu) or not 256-byte aligned", workspace_bytes, L.total);
-    return MTRSSM_EINVAL;
-  }
+  if (int rc = wide_check_workspace("mrssm_rollout_fwd_wide", workspace, workspace_bytes, L.total)) return rc;
   char* ws = static_cast<char*>(workspace);
   const int D = d->D, H = d->H, S = d->K * d->C;
-  // control words after the sticky status word + the logit exchange (read before it is first written? no: zero anyway)
+  // the barrier words behind the sticky status word; every exchange buffer is written before it is read
   if (int rc = clear_async(ws + 16, kWideCtl - 16, stream)) return rc;
   WidePackJobs jobs;
   jobs.count = 6;
-  jobs.j[0] = make_job(w->wf_t, 1, 3 * D, 3 * D, H, reinterpret_cast<uint4*>(ws + L.wf));
-  jobs.j[1] = make_job(w->whh_t, 1, 3 * D, 3 * D, D, reinterpret_cast<uint4*>(ws + L.whh));
-  jobs.j[2] = make_job(w->wh1_t, 1, 3 * H, 3 * H, D, reinterpret_cast<uint4*>(ws + L.wh1));
-  jobs.j[3] = make_job(w->w4, H, 1, S, H, reinterpret_cast<uint4*>(ws + L.h2[0]));
-  jobs.j[4] = make_job(w->wa2, H, 1, S, H, reinterpret_cast<uint4*>(ws + L.h2[1]));
-  jobs.j[5] = make_job(w->wv2, H, 1, S, H, reinterpret_cast<uint4*>(ws + L.h2[2]));
-  if (int rc = launch_pack(jobs, pieces, stream)) return rc;
+  jobs.j[0] = wide_make_job(w->wf_t, 1, 3 * D, 3 * D, H, reinterpret_cast<uint4*>(ws + L.wf));
+  jobs.j[1] = wide_make_job(w->whh_t, 1, 3 * D, 3 * D, D, reinterpret_cast<uint4*>(ws + L.whh));
+  jobs.j[2] = wide_make_job(w->wh1_t, 1, 3 * H, 3 * H, D, reinterpret_cast<uint4*>(ws + L.wh1));
+  jobs.j[3] = wide_make_job(w->w4, H, 1, S, H, reinterpret_cast<uint4*>(ws + L.h2[0]));
+  jobs.j[4] = wide_make_job(w->wa2, H, 1, S, H, reinterpret_cast<uint4*>(ws + L.h2[1]));
+  jobs.j[5] = wide_make_job(w->wv2, H, 1, S, H, reinterpret_cast<uint4*>(ws + L.h2[2]));
+  if (int rc = wide_launch_pack(jobs, pieces, stream)) return rc;
 
   WideFwdArgs a;
   a.dm = *d; a.w = *w; a.io = *io;
@@ -781,35 +708,15 @@ int mrssm_wide_fwd_launch(const MtrssmMrssmDims* d, const MtrssmMrssmClusterWeig
   a.lg = reinterpret_cast<float*>(ws + L.lg);
   a.status = reinterpret_cast<int*>(ws);
   a.ctl = ws;
-  a.nblk = wide_grid(d);
+  a.nblk = device_cu_count();
   a.acquire = wide_acquire_fence();
-  const size_t lds = wide_fwd_lds(d);
-  if (lds > 160 * 1024) { set_error("mrssm_rollout_fwd_wide: %zu bytes of LDS", lds); return MTRSSM_ELDS; }
-  hipError_t e;
-#define MTRSSM_WIDE_FWD(PV, MV)                                                                                                          \
-  {                                                                                                                                 \
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(mrssm_wide_fwd_kernel<PV, MV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    if (e != hipSuccess) { set_error("hipFuncSetAttribute(max dynamic LDS=%zu): %s", lds, hipGetErrorString(e)); return MTRSSM_ELAUNCH; }   \
-    set_last_kernel("mtrssm::mrssm_wide_fwd_kernel<" #PV ", " #MV ">");                                                                      \
-    hipLaunchKernelGGL((mrssm_wide_fwd_kernel<PV, MV>), dim3(a.nblk), dim3(kWT), lds, stream, a);                                        \
-  }
-  if (io->modality) {
-    if (pieces == 3) MTRSSM_WIDE_FWD(3, true) else MTRSSM_WIDE_FWD(2, true)
-  } else {
-    if (pieces == 3) MTRSSM_WIDE_FWD(3, false) else MTRSSM_WIDE_FWD(2, false)
-  }
-#undef MTRSSM_WIDE_FWD
-  e = hipGetLastError();
-  if (e != hipSuccess) { set_error("wide forward scan launch failed: %s", hipGetErrorString(e)); return MTRSSM_ELAUNCH; }
-  return MTRSSM_OK;
+  static const WideKernel<WideFwdArgs> kernels[2][2] = MTRSSM_WIDE_KERNELS(mrssm_wide_fwd_kernel);
+  return wide_launch(kernels, "mrssm_rollout_fwd_wide", "wide forward scan", pieces, io->modality != nullptr, a, wide_fwd_lds(d), stream);
 }
 
 int mrssm_wide_bwd_launch(const MtrssmMrssmDims* d, const MtrssmMrssmClusterWeights* w, const MtrssmMrssmBwdIO* io, int pieces,
                           void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  if (!mrssm_wide_supported(d, pieces)) {
-    set_error("mrssm_rollout_bwd_wide: dims / device outside the wide kernel's regime (ask mtrssm_mrssm_wide_supported first)");
-    return MTRSSM_EINVAL;
-  }
+  if (!mrssm_wide_supported(d, pieces)) return wide_not_supported("mrssm_rollout_bwd_wide", "mrssm");
   if (!w || !io || !workspace || !w->w1s_t || !w->wf_t || !w->whh_t || !w->wh1_t || !w->w4 || !w->wa2 || !w->wv2 || !io->deter0 ||
       !io->deter || !io->prior_logits || !io->post_logits || !io->sv_h1 || !io->sv_gates || !io->sv_heads || !io->sv_la || !io->sv_lv ||
       !io->g_deter0 || !io->g_stoch0 || !io->d_z1 || !io->d_gi || !io->d_gh || !io->d_zh || !io->d_lp || !io->d_la || !io->d_lv) {
@@ -817,23 +724,20 @@ int mrssm_wide_bwd_launch(const MtrssmMrssmDims* d, const MtrssmMrssmClusterWeig
     return MTRSSM_EINVAL;
   }
   const WideBwdLayout L = wide_bwd_layout(d, pieces);
-  if (workspace_bytes < L.total || ((uintptr_t)workspace & 255)) {
-    set_error("mrssm_rollout_bwd_wide: workspace too small (%zu < %zu) or not 256-byte aligned", workspace_bytes, L.total);
-    return MTRSSM_EINVAL;
-  }
+  if (int rc = wide_check_workspace("mrssm_rollout_bwd_wide", workspace, workspace_bytes, L.total)) return rc;
   char* ws = static_cast<char*>(workspace);
   const int D = d->D, H = d->H, S = d->K * d->C;
   if (int rc = clear_async(ws + 16, kWideCtl - 16, stream)) return rc;
   WidePackJobs jobs;
   jobs.count = 7;
-  jobs.j[0] = make_job(w->w4, 1, H, H, S, reinterpret_cast<uint4*>(ws + L.h2t[0]));       // (n = head unit j, k = s): w4[s][j]
-  jobs.j[1] = make_job(w->wa2, 1, H, H, S, reinterpret_cast<uint4*>(ws + L.h2t[1]));
-  jobs.j[2] = make_job(w->wv2, 1, H, H, S, reinterpret_cast<uint4*>(ws + L.h2t[2]));
-  jobs.j[3] = make_job(w->wh1_t, 3 * H, 1, D, 3 * H, reinterpret_cast<uint4*>(ws + L.wh1t));  // (n = i, k = j): wh1_t[i][j]
-  jobs.j[4] = make_job(w->whh_t, 3 * D, 1, D, 3 * D, reinterpret_cast<uint4*>(ws + L.whht));
-  jobs.j[5] = make_job(w->wf_t, 3 * D, 1, H, 3 * D, reinterpret_cast<uint4*>(ws + L.wft));
-  jobs.j[6] = make_job(w->w1s_t, H, 1, S, H, reinterpret_cast<uint4*>(ws + L.w1s));          // (n = s, k = j): w1s_t[s][j]
-  if (int rc = launch_pack(jobs, pieces, stream)) return rc;
+  jobs.j[0] = wide_make_job(w->w4, 1, H, H, S, reinterpret_cast<uint4*>(ws + L.h2t[0]));       // (n = head unit j, k = s): w4[s][j]
+  jobs.j[1] = wide_make_job(w->wa2, 1, H, H, S, reinterpret_cast<uint4*>(ws + L.h2t[1]));
+  jobs.j[2] = wide_make_job(w->wv2, 1, H, H, S, reinterpret_cast<uint4*>(ws + L.h2t[2]));
+  jobs.j[3] = wide_make_job(w->wh1_t, 3 * H, 1, D, 3 * H, reinterpret_cast<uint4*>(ws + L.wh1t));  // (n = i, k = j): wh1_t[i][j]
+  jobs.j[4] = wide_make_job(w->whh_t, 3 * D, 1, D, 3 * D, reinterpret_cast<uint4*>(ws + L.whht));
+  jobs.j[5] = wide_make_job(w->wf_t, 3 * D, 1, H, 3 * D, reinterpret_cast<uint4*>(ws + L.wft));
+  jobs.j[6] = wide_make_job(w->w1s_t, H, 1, S, H, reinterpret_cast<uint4*>(ws + L.w1s));          // (n = s, k = j): w1s_t[s][j]
+  if (int rc = wide_launch_pack(jobs, pieces, stream)) return rc;
 
   WideBwdArgs a;
   a.dm = *d; a.io = *io;
@@ -852,27 +756,10 @@ int mrssm_wide_bwd_launch(const MtrssmMrssmDims* d, const MtrssmMrssmClusterWeig
   a.cs = reinterpret_cast<float*>(ws + L.cs);
   a.status = reinterpret_cast<int*>(ws);
   a.ctl = ws;
-  a.nblk = wide_grid(d);
+  a.nblk = device_cu_count();
   a.acquire = wide_acquire_fence();
-  const size_t lds = wide_bwd_lds(d);
-  if (lds > 160 * 1024) { set_error("mrssm_rollout_bwd_wide: %zu bytes of LDS", lds); return MTRSSM_ELDS; }
-  hipError_t e;
-#define MTRSSM_WIDE_BWD(PV, MV)                                                                                                          \
-  {                                                                                                                                 \
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(mrssm_wide_bwd_kernel<PV, MV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    if (e != hipSuccess) { set_error("hipFuncSetAttribute(max dynamic LDS=%zu): %s", lds, hipGetErrorString(e)); return MTRSSM_ELAUNCH; }   \
-    set_last_kernel("mtrssm::mrssm_wide_bwd_kernel<" #PV ", " #MV ">");                                                                      \
-    hipLaunchKernelGGL((mrssm_wide_bwd_kernel<PV, MV>), dim3(a.nblk), dim3(kWT), lds, stream, a);                                        \
-  }
-  if (io->modality) {
-    if (pieces == 3) MTRSSM_WIDE_BWD(3, true) else MTRSSM_WIDE_BWD(2, true)
-  } else {
-    if (pieces == 3) MTRSSM_WIDE_BWD(3, false) else MTRSSM_WIDE_BWD(2, false)
-  }
-#undef MTRSSM_WIDE_BWD
-  e = hipGetLastError();
-  if (e != hipSuccess) { set_error("wide backward scan launch failed: %s", hipGetErrorString(e)); return MTRSSM_ELAUNCH; }
-  return MTRSSM_OK;
+  static const WideKernel<WideBwdArgs> kernels[2][2] = MTRSSM_WIDE_KERNELS(mrssm_wide_bwd_kernel);
+  return wide_launch(kernels, "mrssm_rollout_bwd_wide", "wide backward scan", pieces, io->modality != nullptr, a, wide_bwd_lds(d), stream);
 }
 
 }  // namespace mtrssm

@@ -1,4 +1,4 @@
-// Shared pieces of the chip-wide ("wide") scan kernels (mrssm_wide.hip): gfx950, wave64.
+// Shared pieces of the chip-wide ("wide") scan kernels (mrssm_wide.hip, mmtrssm_wide.hip): gfx950, wave64.
 //
 // Regime: D, H >= 256 (BASELINE configs[4] "Large": D = H = 1024, S = 128).  One CU re-streaming the step's 42 MB of weights
 // per row (mrssm_scan.hip) takes 500 us per timestep there.  Here ALL workgroups of the chip (one per CU) work on the same
@@ -7,12 +7,19 @@
 // are the MFMA N dimension (v_mfma_f32_16x16x32_bf16, two row tiles), and the products of consecutive layers meet through an
 // exchange buffer in L2 / MALL followed by a grid-wide barrier (all workgroups resident: grid <= CU count).
 //
-// Arithmetic: an fp32 value is the sum of P bf16 pieces (P = 3: exact to 2^-24, six MFMA products per k-block -- fp32-grade,
-// the default; P = 2: 16 significant bits, three products), fp32 accumulation in the MFMA.
+// Arithmetic: an fp32 value is the sum of P bf16 pieces (P = 3: exact to 2^-24, six MFMA products per k-block -- fp32-grade;
+// P = 2: 16 significant bits, three products -- what scan.py asks for unless MTRSSM_WIDE_PIECES says 3), fp32 accumulation in
+// the MFMA.
 #pragma once
+#include <cstdlib>
+
 #include "scan_common.h"
 
 namespace mtrssm {
+
+void set_error(const char* fmt, ...);        // capi.hip
+void set_last_kernel(const char* name);
+int device_cu_count();
 
 constexpr int kWT = 256;                 // threads per workgroup: one wave per SIMD (512 registers each), the K range of a tile split over them
 constexpr int kWW = kWT / kWave;
@@ -156,6 +163,53 @@ __device__ __forceinline__ wf32x4 wide_red_sum(const wf32x4* red, int tile, int 
   return s;
 }
 
+// This wave's share [k0, k1) of KS k-blocks.
+__device__ __forceinline__ void wide_krange(int KS, int wave, int& k0, int& k1) { k0 = KS * wave / kWW; k1 = KS * (wave + 1) / kWW; }
+
+// One 16-column output tile of a product over all RT row tiles: this wave's share of KSR k-blocks of W_tile (wtile) . x (xb,
+// KSX k-blocks per piece; KSR < KSX where only the head of xb is read) into red[wave], then the workgroup's LDS barrier, after
+// which wide_red_sum<1, RT> gives the tile.  CONTAINS A WORKGROUP BARRIER: use it only where every thread of the workgroup
+// arrives (a loop over tiles u = blk, blk + nblk, ..., never under a per-thread condition).
+// The statements are a macro because the MMTRSSM kernels (RT = 4, three ring stages) need them in their own body: they
+// already spill into AGPRs, and with the accumulators inside an inlined function each allocates about 20 registers more
+// (profiles/wide_refactor_resources.md).  It declares k0, k1, acc and wt in the enclosing scope and uses that scope's `red`,
+// `wave`, `lane` and `krange`, a lambda (n, k0, k1) around wide_krange: called directly, the MMTRSSM kernels allocate 2 to 4
+// registers more and one of them gets scratch.  The MRSSM kernels (RT = 2) take the function below at unchanged resources.
+#define MTRSSM_WIDE_TILE_PRODUCT(P, NS, RT, wtile, xb, KSR, KSX)                                      \
+  int k0, k1;                                                                                         \
+  krange(KSR, k0, k1);                                                                                \
+  wf32x4 acc[1][RT];                                                                                  \
+  _Pragma("unroll") for (int rt = 0; rt < RT; ++rt) acc[0][rt] = wf32x4{0.f, 0.f, 0.f, 0.f};          \
+  const uint4* const wt[1] = {wtile};                                                                 \
+  wide_mfma_stream<1, P, NS, RT>(acc, wt, xb, KSX, k0, k1, lane);                                     \
+  wide_red_store<1, RT>(red, wave, 0, lane, acc[0]);                                                  \
+  lds_barrier()
+
+template <int P, int NS, int RT>
+__device__ __forceinline__ void wide_tile_product(wf32x4* red, const uint4* wtile, const uint4* xb, int KS, int wave, int lane) {
+  auto krange = [&](int n, int& k0, int& k1) { wide_krange(n, wave, k0, k1); };
+  MTRSSM_WIDE_TILE_PRODUCT(P, NS, RT, wtile, xb, KS, KS);
+}
+
+// Epilogue item of a thread: row tile, lane slot -> batch row of the pass, first of its four consecutive columns of the tile.
+struct WideEpi {
+  int rt, slot, row, cq;
+  __device__ __forceinline__ explicit WideEpi(int tid) : rt(tid >> 6), slot(tid & 63), row(16 * rt + (slot & 15)), cq(4 * (slot >> 4)) {}
+};
+
+// Development aid (tools/wide_probe.py): when a file's profile pointer is set, lane 0 of EVERY workgroup stamps s_memrealtime
+// (100 MHz) at the phase boundaries of timesteps 8..11 of the first row tile into that buffer: [workgroup][step - 8][16 stamps].
+// Null in normal use.  The pointer is a __device__ variable of each file (no relocatable device code: one per file); the macro
+// reads the kernel's locals `prof` and `tstamp`.
+#define MTRSSM_WIDE_STAMP(i)                                                                                              \
+  do {                                                                                                                    \
+    if (prof && tstamp >= 8 && tstamp < 12) prof[((size_t)blockIdx.x * 4 + (tstamp - 8)) * 16 + (i)] = __builtin_amdgcn_s_memrealtime(); \
+  } while (0)
+inline int wide_set_profile(const void* symbol, void* buf) {
+  unsigned long long* p = static_cast<unsigned long long*>(buf);
+  return hipMemcpyToSymbol(symbol, &p, sizeof(p)) == hipSuccess ? MTRSSM_OK : MTRSSM_ELAUNCH;
+}
+
 // Grid-wide barrier over `nblk` resident workgroups, two levels: the workgroups with equal blockIdx % 8 (one XCD under the
 // observed round-robin placement: speed only, nothing depends on it) arrive at their group's counter; the last of a group
 // arrives at the top counter; the last group releases everybody by storing the epoch into each group's generation word, which is
@@ -217,5 +271,64 @@ struct WideBarrier {
     return *abort_flag == 0;
   }
 };
+
+// ---- host side ----
+WidePackJob wide_make_job(const float* src, long sn, long sk, int N, int K, uint4* dst);   // mrssm_wide.hip
+WidePackJob wide_make_block(const float* src, long sn, long sk, int N, int K, int nskip, int kskip, int nt0, int ks0, int KST, uint4* dst);
+int wide_launch_pack(const WidePackJobs& jobs, int pieces, hipStream_t stream);
+
+// Workspace layouts: the control block, then 256-byte aligned fields in the order they are taken.
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+struct WideBump {
+  size_t o = kWideCtl;
+  size_t take(size_t bytes) { const size_t r = o; o += align256(bytes); return r; }
+};
+
+inline int wide_not_supported(const char* entry, const char* model) {
+  set_error("%s: dims / device outside the wide kernel's regime (ask mtrssm_%s_wide_supported first)", entry, model);
+  return MTRSSM_EINVAL;
+}
+inline int wide_check_workspace(const char* entry, const void* workspace, size_t workspace_bytes, size_t total) {
+  if (workspace_bytes >= total && !((uintptr_t)workspace & 255)) return MTRSSM_OK;
+  set_error("%s: workspace too small (%zu < %zu) or not 256-byte aligned", entry, workspace_bytes, total);
+  return MTRSSM_EINVAL;
+}
+
+// MTRSSM_WIDE_ACQUIRE=1: an agent-scope acquire fence after every grid barrier on top of the sc1 loads (A/B runs)
+inline int wide_acquire_fence() {
+  static const int on = [] { const char* e = getenv("MTRSSM_WIDE_ACQUIRE"); return (e && e[0] == '1') ? 1 : 0; }();
+  return on;
+}
+
+// Dynamic LDS of a wide kernel that needs `need` bytes: at least 84 KiB (> 80 KiB: never two workgroups on one CU); 0 where
+// `need` is beyond the 160 KiB of a CU.
+inline size_t wide_lds_bytes(size_t need) { return need > 160 * 1024 ? 0 : (need < 84 * 1024 ? 84 * 1024 : need); }
+
+// The four instantiations of a wide kernel template, [pieces == 3][masked], with the names set_last_kernel reports.
+template <class Args>
+struct WideKernel {
+  void (*fn)(Args);
+  const char* name;
+};
+#define MTRSSM_WIDE_KERNELS(K)                                                                                     \
+  {{{K<2, false>, "mtrssm::" #K "<2, false>"}, {K<2, true>, "mtrssm::" #K "<2, true>"}},                           \
+   {{K<3, false>, "mtrssm::" #K "<3, false>"}, {K<3, true>, "mtrssm::" #K "<3, true>"}}}
+
+// Launch kernels[pieces == 3][masked] on a.nblk workgroups (one per CU: each asks for more than half a CU's LDS).
+// `entry` / `what` name the C entry point / the scan in the error texts.
+template <class Args>
+int wide_launch(const WideKernel<Args> (&kernels)[2][2], const char* entry, const char* what, int pieces, bool masked, const Args& a,
+                size_t lds_need, hipStream_t stream) {
+  const WideKernel<Args>& k = kernels[pieces == 3][masked];
+  const size_t lds = wide_lds_bytes(lds_need);
+  if (!lds) { set_error("%s: %zu bytes of LDS", entry, lds_need); return MTRSSM_ELDS; }
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) { set_error("hipFuncSetAttribute(max dynamic LDS=%zu): %s", lds, hipGetErrorString(e)); return MTRSSM_ELAUNCH; }
+  set_last_kernel(k.name);
+  hipLaunchKernelGGL(k.fn, dim3(a.nblk), dim3(kWT), lds, stream, a);
+  e = hipGetLastError();
+  if (e != hipSuccess) { set_error("%s launch failed: %s", what, hipGetErrorString(e)); return MTRSSM_ELAUNCH; }
+  return MTRSSM_OK;
+}
 
 }  // namespace mtrssm

@@ -139,6 +139,30 @@ def test_invalid_arguments_are_rejected_without_a_launch() -> None:
     assert lib.mtrssm_mrssm_cluster_supported(C.byref(_lib.MrssmDims(64, 50, 200, 200, 6, 5, 2, 1, 0.2, 0.8, 0, 0))) == int(cus >= 256)
 
 
+def test_wide_workspace_layouts_are_pinned() -> None:
+    """The wide scans' workspace totals, (forward, backward) at pieces 2 and 3: the four layout functions take their fields in
+    a fixed order and 256-byte steps, so a field that moves, grows or goes missing changes a total.  No device is needed."""
+    lib = _lib.load()
+    mrssm = {  # (D, H, K, C)
+        (1024, 1024, 16, 8): {2: (40159744, 41224704), 3: (60213760, 61827584)},  # oracle.cases mrssm_large
+        (32, 256, 4, 4): {2: (406016, 496128), 3: (604672, 741888)},              # config_matrix w32x256
+    }
+    for (d_, h, k, c), want in mrssm.items():
+        dims = _lib.MrssmDims(32, 100, d_, h, k, c, 2, 1, 0.2, 0.8, 0, 0)
+        for pieces, (fwd, bwd) in want.items():
+            assert lib.mtrssm_mrssm_wide_workspace_bytes(C.byref(dims), pieces) == fwd, (d_, h, pieces)
+            assert lib.mtrssm_mrssm_wide_bwd_workspace_bytes(C.byref(dims), pieces) == bwd, (d_, h, pieces)
+    mmtrssm = {  # (LD, HD, H, KL, CL, KH, CH)
+        (200, 200, 200, 6, 5, 6, 5): {2: (3451392, 3318272), 3: (5155328, 4967936)},  # oracle.cases mmtrssm_cfg3dims
+        (128, 32, 32, 4, 4, 8, 2): {2: (397824, 379392), 3: (585216, 563712)},        # config_matrix mw128
+    }
+    for (ld, hd, h, kl, cl, kh, ch), want in mmtrssm.items():
+        dims = _lib.MmtrssmDims(32, 100, ld, hd, h, kl, cl, kh, ch, 2, 1, 2.0, 4.0, 0.5, 0.75, 0.2, 0.8, 0, 0)
+        for pieces, (fwd, bwd) in want.items():
+            assert lib.mtrssm_mmtrssm_wide_workspace_bytes(C.byref(dims), pieces) == fwd, (ld, hd, pieces)
+            assert lib.mtrssm_mmtrssm_wide_bwd_workspace_bytes(C.byref(dims), pieces) == bwd, (ld, hd, pieces)
+
+
 def test_missing_library_fails_loudly(monkeypatch: pytest.MonkeyPatch, tmp_path: Path) -> None:
     monkeypatch.setattr(_lib, "_LIB", None)
     monkeypatch.setenv("MTRSSM_LIB", str(tmp_path / "nope.so"))

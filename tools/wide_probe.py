@@ -1,5 +1,5 @@
 """Phase timing of the wide scans (profiling helper): s_memrealtime stamps (100 MHz) of EVERY workgroup at the phase boundaries
-of timesteps 8..11 (csrc/mrssm_wide.hip: MTRSSM_WIDE_STAMP, csrc/mmtrssm_wide.hip: MTRSSM_MMT_STAMP).
+of timesteps 8..11 (MTRSSM_WIDE_STAMP of csrc/wide_common.h in csrc/mrssm_wide.hip and csrc/mmtrssm_wide.hip).
 Usage on the GPU box: python tools/wide_probe.py [fwd|bwd|mmt-fwd|mmt-bwd]
 
 Per phase it prints, over the workgroups that had work in it, the median / maximum span of the work itself and, over all
