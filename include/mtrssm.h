@@ -739,6 +739,23 @@ int mtrssm_step_mask_ragged(const int32_t* valid, const float* u, int64_t b_glob
                             float p_vision, int64_t row0, int64_t b_local, int32_t* codes, float* present_audio, float* present_vision,
                             float* live, uint8_t* mask0, int32_t* last, float* counts, void* stream);
 
+/* The masks of a forecast step: what the model observes and what the loss reconstructs are two planes.
+ *   u_context: [b_global] fp32 uniforms in [0, 1); with n = hi - lo + 1 row b observes a context of
+ *   c_b = lo + min((int)(u_context[b] * (float)n), n - 1) frames (one fp32 multiply, truncated).  live(b, t) = t < valid[b] (clamped
+ *   into [0, steps]; valid == NULL: every row has `steps` live steps), observed = live AND t < c_b.  A modality is SEEN iff the step
+ *   is observed AND (u_mask == NULL: no dropout, or the rule of mtrssm_modality_dropout says present, its t = 0 fix-up applied
+ *   before the AND); lo >= 1, so frame 0 of a live row is always observed.
+ * Written for the rank's rows as there: codes [b_local][steps] (the seen bits; 0 on the open-loop tail and on dead steps),
+ * seen_audio / seen_vision [b_local * steps] in {0, 1}, target [b_local * steps] = live (every live frame of both modalities is
+ * reconstructed, seen or not), observed [b_local * steps] (the KL's plane: the KL is exactly 0 elsewhere), mask0 [b_local][2] (the
+ * seen bits at t = 0), last [b_local] = valid - 1.  counts[2]: live and observed steps over ALL b_global rows (zeroed, then one
+ * atomic per workgroup and count).  Argument rules as mtrssm_step_mask_ragged (valid and u_mask may be NULL, u_context may not),
+ * plus 1 <= lo <= hi < 2^31. */
+int mtrssm_step_mask_forecast(const int32_t* valid, const float* u_mask, const float* u_context, int64_t b_global, int64_t steps,
+                              int64_t span, float p_audio, float p_vision, int64_t lo, int64_t hi, int64_t row0, int64_t b_local,
+                              int32_t* codes, float* seen_audio, float* seen_vision, float* target, float* observed, uint8_t* mask0,
+                              int32_t* last, float* counts, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Fused AdamW over one flat fp32 parameter buffer, with global-norm gradient clipping
  * (yaml: torch.optim.AdamW lr 1e-3; trainer.gradient_clip_val 10 -- default.yaml:103-107,119).

@@ -20,6 +20,7 @@ from multimodal_mtrssm_amd.distributions import (
     stack_distribution,
 )
 from multimodal_mtrssm_amd.dropout import ModalityDropout
+from multimodal_mtrssm_amd.forecast import Forecast
 from multimodal_mtrssm_amd.factory import make_mmtrssm, make_mrssm
 from multimodal_mtrssm_amd.networks import MLP, MTRNN, Representation, Transition
 from multimodal_mtrssm_amd.objective import likelihood
@@ -30,7 +31,7 @@ from multimodal_mtrssm_amd.state import MTState, State, cat_mtstates, cat_states
 __version__ = "0.1.0"
 
 __all__ = [
-    "MLP", "MTRNN", "Decoder", "DeviceEpisodeLoader", "Distribution", "Encoder", "EpisodeBatch", "EpisodeDataModule", "EpisodeDataModuleConfig", "FlatAdamW", "FlatDataParallel", "GlobalRowNoise", "MTState", "MoPoE_MMTRSSM",
+    "MLP", "MTRNN", "Decoder", "DeviceEpisodeLoader", "Distribution", "Encoder", "EpisodeBatch", "EpisodeDataModule", "EpisodeDataModuleConfig", "FlatAdamW", "FlatDataParallel", "Forecast", "GlobalRowNoise", "MTState", "MoPoE_MMTRSSM",
     "MoPoE_MRSSM", "ModalityDropout", "MultiOneHot", "MultiOneHotFactory", "ReduceLROnPlateau", "Representation", "State", "StateCarry", "Transition", "cat_distribution",
     "cat_mtstates", "cat_states", "inject_uniforms", "kl_divergence", "likelihood", "load_reference_checkpoint", "make_mmtrssm", "make_mrssm",
     "stack_distribution", "stack_mtstates", "stack_states",

@@ -23,6 +23,7 @@ from multimodal_mtrssm_amd import cnn, conv, scan
 from multimodal_mtrssm_amd.carry import StateCarry
 from multimodal_mtrssm_amd.distributions import MultiOneHot, MultiOneHotFactory, draw_uniforms, kl_divergence, onehot_from_uniforms
 from multimodal_mtrssm_amd.dropout import ModalityDropout, StepMask, ragged_step_mask
+from multimodal_mtrssm_amd.forecast import Forecast
 from multimodal_mtrssm_amd.networks import MTRNN, Representation, Transition
 from multimodal_mtrssm_amd.objective import likelihood
 from multimodal_mtrssm_amd.state import MTState, State
@@ -329,6 +330,8 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         self.scan_threads = 0
         self.modality_dropout: ModalityDropout | None = None  # training_step samples a modality mask with it
         self.state_carry: StateCarry | None = None  # training_step / validation_step continue from its "train" / "val" set
+        self.forecast: Forecast | None = None  # training_step trains the forecast objective with it
+        self.val_forecast: Forecast | None = None  # validation_step adds a forecast step at this (fixed) context and logs val/forecast/*
 
     # -- batch accessors (mrssm core.py:310-355) --------------------------------------------
     @staticmethod
@@ -445,9 +448,12 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
 
     def _with_mask_noise(self, shapes: dict[str, tuple[int, ...]], batch: int, steps: int) -> dict[str, tuple[int, ...]]:
         """With ``self.modality_dropout`` set, the key ``u_mask`` joins (``GlobalRowNoise`` hands every rank ALL its rows: the
-        sampler counts the global batch's present frames); without, ``shapes`` as it is."""
+        sampler counts the global batch's present frames), with ``self.forecast`` set ``u_context`` (likewise); without, ``shapes``
+        as it is."""
         if self.modality_dropout is not None:
             shapes["u_mask"] = self.modality_dropout.noise_shape(batch, steps)
+        if self.forecast is not None:
+            shapes["u_context"] = self.forecast.noise_shape(batch)
         return shapes
 
     def _rollout_embedded(self, actions: Tensor, audio_embed: Tensor | None, vision_embed: Tensor | None, prev_state: State,  # noqa: PLR0913
@@ -467,12 +473,15 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
             rows_per_block=self.scan_rows_per_block, threads=self.scan_threads, modality=modality,
         )
 
+    def _posterior_from_rollout(self, out: dict[str, Tensor]) -> State:
+        post = State(deter=out["deter"], distribution=self.audio_representation.distribution_factory(out["post_logits"]), stoch=out["post_stoch"])
+        post.kl_per_step = out["kl"]  # sum_K KL(q||p) per (b, t), straight from the scan kernel
+        return post
+
     def _states_from_rollout(self, out: dict[str, Tensor]) -> tuple[State, State]:
         factory = self.audio_representation.distribution_factory
-        post = State(deter=out["deter"], distribution=factory(out["post_logits"]), stoch=out["post_stoch"])
         prior = State(deter=out["deter"], distribution=factory(out["prior_logits"]), stoch=out["prior_stoch"])
-        post.kl_per_step = out["kl"]  # sum_K KL(q||p) per (b, t), straight from the scan kernel
-        return post, prior
+        return self._posterior_from_rollout(out), prior
 
     def rollout_representation(
         self,
@@ -523,7 +532,81 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         dist = self.transition.distribution_factory(out["prior_logits"])
         return State(deter=out["deter"], distribution=dist, stoch=out["prior_stoch"])
 
+    @torch.no_grad()
+    def forecast_rollout(self, *, actions: Tensor, observations: tuple[Tensor, Tensor], context: int, prev_state: State | MTState,  # noqa: PLR0913
+                         noise: Noise | None = None, lengths: Tensor | None = None) -> State | MTState:
+        """Observe the first ``context`` frames, then run open loop: ONE masked posterior rollout (both modalities on steps
+        ``t < context``, none after, where the scans take posterior = prior), returned as the posterior state sequence ``[B, T, .]``.
+        It is the logging callback's ``rollout_representation`` -> ``[:, context - 1]`` -> ``rollout_transition`` -> ``cat_states`` in one
+        launch, the tail sampled with ``noise["u_post"][:, context:]`` (MMTRSSM: ``u_post_l`` / ``u_post_h``).  ``lengths`` (int32
+        ``[B]`` on the device): nothing is observed at or past a row's end either."""
+        if not isinstance(observations, tuple) or observations[0] is None or observations[1] is None:
+            msg = "forecast_rollout requires the tuple (audio_obs, vision_obs), both given"
+            raise TypeError(msg)
+        B, T = actions.shape[:2]
+        if lengths is not None:
+            _check_lengths(lengths, B, actions.device)
+        sm = Forecast(context).sample(torch.zeros(B, device=actions.device), T, lengths)  # (a fixed context: the uniforms do not matter)
+        audio_embed, vision_embed = self.audio_encoder(observations[0]), self.vision_encoder(observations[1])
+        out = self._rollout_embedded(actions, audio_embed, vision_embed, prev_state, noise, sample_prior=False, modality=sm.codes)
+        return self._posterior_from_rollout(out)
+
     # -- train / val ----------------------------------------------------------------------------
+    def _dropout_uniforms(self, batch: tuple[Tensor, ...], noise: Noise | None, modality_dropout: ModalityDropout, world: int) -> Tensor:
+        """``noise["u_mask"]`` of the GLOBAL batch (``world`` ranks of the batch's rows), drawn here when absent on one rank."""
+        B, T = batch[0].shape[:2]
+        u = None if noise is None else noise.get("u_mask")
+        if u is None:
+            if world > 1:
+                msg = "modality_dropout on more than one rank needs noise['u_mask'] of the global batch (GlobalRowNoise.draw)"
+                raise ValueError(msg)
+            u = _rand(batch[0], *modality_dropout.noise_shape(B, T))
+        if u.shape[0] != B * world:
+            msg = f"noise['u_mask'] has {u.shape[0]} rows, the global batch {B} x {world}"
+            raise ValueError(msg)
+        return u
+
+    def _forecast_step_mask(self, batch: tuple[Tensor, ...], noise: Noise | None, forecast: Forecast,  # noqa: PLR0913
+                            modality_dropout: ModalityDropout | None, lengths: Tensor | None = None,
+                            ragged: tuple[Tensor, int, int] | None = None) -> StepMask:
+        """The masks of a forecast step, one launch, nothing read back: the sampled context AND the lengths (when
+        the step has them) AND the dropout rule.  ``ragged``: ``_lengths_of``'s result when the caller has checked the lengths already."""
+        if not isinstance(forecast, Forecast):
+            msg = f"forecast must be a Forecast, got {type(forecast).__name__}"
+            raise ValueError(msg)
+        if modality_dropout is not None and not isinstance(modality_dropout, ModalityDropout):
+            msg = f"modality_dropout must be a ModalityDropout, got {type(modality_dropout).__name__}"
+            raise ValueError(msg)
+        B, T = batch[0].shape[:2]
+        if lengths is not None and forecast.world != 1:
+            msg = "lengths= describes one rank's own rows: with data parallelism use a batch that carries valid_global"
+            raise ValueError(msg)
+        if ragged is None:
+            ragged = self._lengths_of(batch, lengths, modality_dropout, None)  # (no carry: every row resets)
+        if ragged is not None:
+            valid, world, rank = ragged
+            _check_lengths(valid, B * world, batch[0].device)
+        else:
+            valid, world, rank = None, forecast.world, forecast.rank
+        for what, bound in (("forecast", forecast), ("modality_dropout", modality_dropout)):
+            if bound is not None and (bound.world not in (1, world) or (bound.world == world and bound.rank != rank)):
+                msg = f"{what} is bound to rank {bound.rank} of {bound.world}, the batch to rank {rank} of {world}"
+                raise ValueError(msg)
+        u_context = None if noise is None else noise.get("u_context")
+        if u_context is None:
+            if forecast.fixed:  # (every row observes the same number of frames: no draw)
+                u_context = torch.zeros(B * world, device=batch[0].device)
+            elif world > 1:
+                msg = "forecast on more than one rank needs noise['u_context'] of the global batch (GlobalRowNoise.draw)"
+                raise ValueError(msg)
+            else:
+                u_context = _rand(batch[0], *forecast.noise_shape(B))
+        if u_context.shape[0] != B * world:
+            msg = f"noise['u_context'] has {u_context.shape[0]} rows, the global batch {B} x {world}"
+            raise ValueError(msg)
+        u_mask = None if modality_dropout is None else self._dropout_uniforms(batch, noise, modality_dropout, world)
+        return forecast.sample(u_context, T, valid, u_mask, modality_dropout, world=world, rank=rank)
+
     def _ragged_step_mask(self, batch: tuple[Tensor, ...], noise: Noise | None, modality_dropout: ModalityDropout | None,  # noqa: PLR0913
                           valid_global: Tensor, world: int, rank: int) -> StepMask:
         """The masks of a ragged step from the GLOBAL batch's live-step counts, one launch, nothing read back:
@@ -538,15 +621,7 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
             if modality_dropout.world not in (1, world) or (modality_dropout.world == world and modality_dropout.rank != rank):
                 msg = f"modality_dropout is bound to rank {modality_dropout.rank} of {modality_dropout.world}, the batch to rank {rank} of {world}"
                 raise ValueError(msg)
-            u = None if noise is None else noise.get("u_mask")
-            if u is None:
-                if world > 1:
-                    msg = "modality_dropout on more than one rank needs noise['u_mask'] of the global batch (GlobalRowNoise.draw)"
-                    raise ValueError(msg)
-                u = _rand(batch[0], *modality_dropout.noise_shape(B, T))
-            if u.shape[0] != B * world:
-                msg = f"noise['u_mask'] has {u.shape[0]} rows, the global batch {B} x {world}"
-                raise ValueError(msg)
+            u = self._dropout_uniforms(batch, noise, modality_dropout, world)
         return ragged_step_mask(valid_global, u, T, modality_dropout, world=world, rank=rank)
 
     def _lengths_of(self, batch: tuple[Tensor, ...], lengths: Tensor | None, modality_dropout: ModalityDropout | None,
@@ -600,20 +675,12 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         if not isinstance(modality_dropout, ModalityDropout):
             msg = f"modality_dropout must be a ModalityDropout, got {type(modality_dropout).__name__}"
             raise ValueError(msg)
-        u = None if noise is None else noise.get("u_mask")
-        if u is None:
-            if modality_dropout.world > 1:
-                msg = "modality_dropout on more than one rank needs noise['u_mask'] of the global batch (GlobalRowNoise.draw)"
-                raise ValueError(msg)
-            u = _rand(batch[0], *modality_dropout.noise_shape(B, T))
-        if u.shape[0] != B * modality_dropout.world:
-            msg = f"noise['u_mask'] has {u.shape[0]} rows, the global batch {B} x {modality_dropout.world}"
-            raise ValueError(msg)
-        return modality_dropout.sample(u, T).step_mask()
+        return modality_dropout.sample(self._dropout_uniforms(batch, noise, modality_dropout, modality_dropout.world), T).step_mask()
 
     def shared_step(self, batch: tuple[Tensor, ...], noise: Noise | None = None, modality_mask: Tensor | None = None,  # noqa: PLR0913
                     modality_dropout: ModalityDropout | None = None, state_carry: StateCarry | None = None,
-                    reset: Tensor | None = None, *, carry_prefix: str = "train", lengths: Tensor | None = None) -> dict[str, Tensor]:
+                    reset: Tensor | None = None, *, carry_prefix: str = "train", lengths: Tensor | None = None,
+                    forecast: Forecast | None = None) -> dict[str, Tensor]:
         """``core.py:187-221``: ``loss = recon + kl_coeff * KL(post || prior)`` (MMTRSSM, ``mmtrssm core.py:563-606``:
         ``recon + kl_coeff KL_l + kl_coeff w_kl_h KL_h``).  ``modality_mask`` (or a 7th batch entry, bool ``[B, T, 2]``): each
         recon term averages over the frames where its modality is present; the KL stays the mean over all B*T (0 on steps with
@@ -629,7 +696,20 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         loader with lengths): row b has ``lengths[b]`` live steps.  A dead step has no modality (posterior = prior, KL 0), no
         reconstruction term and zero gradient; each term is divided by the GLOBAL batch's count of its frames / world, the KL by the
         live steps; the carry saves each row's last live step.  A row may be empty only when it does not reset (without a
-        ``state_carry`` every row resets)."""
+        ``state_carry`` every row resets).
+
+        ``forecast`` (a ``Forecast``): each row observes a context of ``c_b`` frames sampled from
+        ``noise["u_context"]`` (drawn here when absent) and runs open loop after it; both modalities are reconstructed on every live
+        frame, the KL sums over the observed steps / their count.  Alone, with ``modality_dropout`` and / or with lengths; not with a
+        modality mask (it already says what is seen) nor with a ``state_carry`` (the state it would save is an open-loop state)."""
+        if forecast is not None:
+            if modality_mask is not None or self.get_modality_mask_from_batch(batch) is not None:
+                msg = "forecast= decides what the model observes: a modality_mask (or a 7-tuple batch) already says what is seen, give one of them"
+                raise ValueError(msg)
+            if state_carry is not None:
+                msg = "forecast= does not combine with state_carry: the state a forecast step ends with is an open-loop state, not one to continue from"
+                raise ValueError(msg)
+            return self._elbo_step(batch, noise, self._forecast_step_mask(batch, noise, forecast, modality_dropout, lengths))
         reset_host = None  # without a carry every row starts from its fresh state: every row resets
         if state_carry is not None:
             reset_host = getattr(batch, "reset_host", None) if reset is None else (None if reset.is_cuda else reset)
@@ -701,8 +781,10 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         return {"recon": recon, **parts, "kl": kl_div, "loss": loss}
 
     def _step(self, batch: tuple[Tensor, ...], prefix: str, *, with_loss_key: bool,
-              modality_dropout: ModalityDropout | None = None) -> dict[str, Tensor]:
-        if self.state_carry is None:
+              modality_dropout: ModalityDropout | None = None, forecast: Forecast | None = None) -> dict[str, Tensor]:
+        if forecast is not None:  # (with a state_carry set too, shared_step refuses)
+            loss_dict = self.shared_step(batch, modality_dropout=modality_dropout, state_carry=self.state_carry, forecast=forecast)
+        elif self.state_carry is None:
             loss_dict = self.shared_step(batch, modality_dropout=modality_dropout)
         else:
             loss_dict = self.shared_step(batch, modality_dropout=modality_dropout, state_carry=self.state_carry, carry_prefix=prefix)
@@ -715,10 +797,17 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         return renamed
 
     def training_step(self, batch: tuple[Tensor, ...], _: int = 0) -> dict[str, Tensor]:
-        return self._step(batch, "train", with_loss_key=True, modality_dropout=self.modality_dropout)
+        return self._step(batch, "train", with_loss_key=True, modality_dropout=self.modality_dropout, forecast=self.forecast)
 
     def validation_step(self, batch: tuple[Tensor, ...], _batch_index: int = 0) -> dict[str, Tensor]:
-        return self._step(batch, "val", with_loss_key=False)
+        """``val/*`` of the closed-loop step; with ``self.val_forecast`` set, a second step on the same batch observes that context and
+        forecasts the rest (from the chunk's own frame 0, no carry), logged as ``val/forecast/*``."""
+        logged = self._step(batch, "val", with_loss_key=False)
+        if self.val_forecast is not None:
+            fore = {f"val/forecast/{k}": v for k, v in self.shared_step(batch, forecast=self.val_forecast).items()}
+            self.log_dict(fore, prog_bar=False, sync_dist=True, on_step=False, on_epoch=True)
+            logged.update(fore)
+        return logged
 
 
 class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
@@ -821,14 +910,18 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
         return scan.mmtrssm_posterior_rollout(self, actions, audio_embed, vision_embed, self._state_dict_of(prev_state), noise,
                                               rows_per_block=self.scan_rows_per_block, threads=self.scan_threads, modality=modality)
 
-    def _states_from_rollout(self, out: dict[str, Tensor]) -> tuple[MTState, MTState]:  # type: ignore[override]
-        common = dict(deter_h=out["deter_h"], deter_l=out["deter_l"], hidden_h=out["hidden_h"], hidden_l=out["hidden_l"])
+    def _posterior_from_rollout(self, out: dict[str, Tensor]) -> MTState:  # type: ignore[override]
         post = MTState(distribution_h=self.h_dist(out["post_logits_h"]), distribution_l=self.l_dist(out["post_logits_l"]),
-                       stoch_h=out["post_stoch_h"], stoch_l=out["post_stoch_l"], **common)
-        prior = MTState(distribution_h=self.h_dist(out["prior_logits_h"]), distribution_l=self.l_dist(out["prior_logits_l"]),
-                        stoch_h=out["prior_stoch_h"], stoch_l=out["prior_stoch_l"], **common)
+                       stoch_h=out["post_stoch_h"], stoch_l=out["post_stoch_l"], deter_h=out["deter_h"], deter_l=out["deter_l"],
+                       hidden_h=out["hidden_h"], hidden_l=out["hidden_l"])
         post.kl_per_step, post.kl_h_per_step = out["kl_l"], out["kl_h"]
-        return post, prior
+        return post
+
+    def _states_from_rollout(self, out: dict[str, Tensor]) -> tuple[MTState, MTState]:  # type: ignore[override]
+        prior = MTState(distribution_h=self.h_dist(out["prior_logits_h"]), distribution_l=self.l_dist(out["prior_logits_l"]),
+                        stoch_h=out["prior_stoch_h"], stoch_l=out["prior_stoch_l"], deter_h=out["deter_h"], deter_l=out["deter_l"],
+                        hidden_h=out["hidden_h"], hidden_l=out["hidden_l"])
+        return self._posterior_from_rollout(out), prior
 
     def rollout_representation(  # type: ignore[override]
         self,

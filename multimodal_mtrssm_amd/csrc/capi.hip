@@ -35,6 +35,8 @@ int episode_gather_seeded_launch(const float*, const int64_t*, const int32_t*, c
                                  int64_t, int64_t, int64_t, float, float*, float*, hipStream_t);
 int step_mask_ragged_launch(const int32_t*, const float*, int64_t, int64_t, int64_t, float, float, int64_t, int64_t, int32_t*, float*, float*, float*,
                             unsigned char*, int32_t*, float*, hipStream_t);
+int step_mask_forecast_launch(const int32_t*, const float*, const float*, int64_t, int64_t, int64_t, float, float, int64_t, int64_t, int64_t, int64_t,
+                              int32_t*, float*, float*, float*, float*, unsigned char*, int32_t*, float*, hipStream_t);
 int elbo_combine_counted_fwd_launch(const float*, const float*, const float*, const float*, const float*, const float*, int64_t, float, float, float*,
                                     float*, float*, float*, hipStream_t);
 int elbo_combine_counted_bwd_launch(const float*, const float*, const float*, const float*, const float*, const float*, int64_t, float, float, float*,
@@ -284,6 +286,13 @@ MTRSSM_API int mtrssm_step_mask_ragged(const int32_t* valid, const float* u, int
                                        float* present_vision, float* live, uint8_t* mask0, int32_t* last, float* counts, void* stream) {
   return step_mask_ragged_launch(valid, u, b_global, steps, span, p_audio, p_vision, row0, b_local, codes, present_audio, present_vision, live,
                                  mask0, last, counts, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_step_mask_forecast(const int32_t* valid, const float* u_mask, const float* u_context, int64_t b_global, int64_t steps,
+                                         int64_t span, float p_audio, float p_vision, int64_t lo, int64_t hi, int64_t row0, int64_t b_local,
+                                         int32_t* codes, float* seen_audio, float* seen_vision, float* target, float* observed, uint8_t* mask0,
+                                         int32_t* last, float* counts, void* stream) {
+  return step_mask_forecast_launch(valid, u_mask, u_context, b_global, steps, span, p_audio, p_vision, lo, hi, row0, b_local, codes, seen_audio,
+                                   seen_vision, target, observed, mask0, last, counts, static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int mtrssm_elbo_combine_counted_fwd(const float* nll_a, const float* nll_v, const float* kl0, const float* kl1, const float* live,
                                                const float* count, int64_t n, float c0, float c1, float* o_recon, float* o_k0, float* o_k1,

@@ -711,6 +711,94 @@ int step_mask_ragged_launch(const int32_t* valid, const float* u, int64_t b_glob
   return check_launch("step_mask_ragged");
 }
 
+// Forecast objective: row b observes a context of c_b = lo + min(int(u_context[b] * float(n)), n - 1) frames,
+// n = hi - lo + 1 (ONE fp32 multiply, truncated), and runs open loop after it.  live = t < valid[b] as above (valid == nullptr: T),
+// observed = live AND t < c_b; a modality is SEEN iff the step is observed AND (no dropout -- u_mask == nullptr -- or the dropout
+// rule says present, its t = 0 fix-up applied BEFORE the AND).  What is seen (codes, seen_*, mask0) and what is reconstructed
+// (`target` = live) are different planes here; `observed` is the KL's plane.  counts = {live, observed} over the global batch.
+__global__ __launch_bounds__(kThreads) void step_mask_forecast_kernel(
+    const int* __restrict__ valid, const float* __restrict__ u_mask, const float* __restrict__ u_context, float p_audio, float p_vision,
+    int span, int T, int S, int lo, int n_bins, long b_global, long row0, long b_local, int* __restrict__ codes,
+    float* __restrict__ seen_audio, float* __restrict__ seen_vision, float* __restrict__ target, float* __restrict__ observed,
+    unsigned char* __restrict__ mask0, int* __restrict__ last, float* __restrict__ counts) {
+  __shared__ float red_l[kThreads / kWave], red_o[kThreads / kWave];
+  const long total = b_global * T;
+  float nl = 0.f, no = 0.f;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long b = i / T;
+    const int t = (int)(i - b * T);
+    int n = valid ? valid[b] : T;
+    n = n < 0 ? 0 : (n > T ? T : n);
+    const long long bin = (long long)(u_context[b] * (float)n_bins);  // (64-bit, then clamped: above 2^24 (float)n_bins may round up, to as much as 2^31)
+    const int c = lo + (int)(bin < n_bins - 1 ? bin : n_bins - 1);
+    const bool on = t < n, obs = on && t < c;
+    bool a = true, v = true;
+    if (u_mask) dropout_present(u_mask, b, t, span, S, p_audio, p_vision, a, v);
+    a = a && obs;
+    v = v && obs;
+    nl += on ? 1.f : 0.f;
+    no += obs ? 1.f : 0.f;
+    const long r = b - row0;
+    if (r >= 0 && r < b_local) {
+      const long o = r * T + t;
+      codes[o] = (a ? 1 : 0) | (v ? 2 : 0);
+      seen_audio[o] = a ? 1.f : 0.f;
+      seen_vision[o] = v ? 1.f : 0.f;
+      target[o] = on ? 1.f : 0.f;
+      observed[o] = obs ? 1.f : 0.f;
+      if (t == 0) {
+        mask0[2 * r] = a ? 1 : 0;
+        mask0[2 * r + 1] = v ? 1 : 0;
+        last[r] = n - 1;
+      }
+    }
+  }
+  const float tl = block_sum(nl, red_l), to = block_sum(no, red_o);
+  if (threadIdx.x == 0) {
+    atomicAdd(counts, tl);
+    atomicAdd(counts + 1, to);
+  }
+}
+
+int step_mask_forecast_launch(const int32_t* valid, const float* u_mask, const float* u_context, int64_t b_global, int64_t T, int64_t span,
+                              float p_audio, float p_vision, int64_t lo, int64_t hi, int64_t row0, int64_t b_local, int32_t* codes,
+                              float* seen_audio, float* seen_vision, float* target, float* observed, unsigned char* mask0, int32_t* last,
+                              float* counts, hipStream_t s) {
+  if (!u_context || !codes || !seen_audio || !seen_vision || !target || !observed || !mask0 || !last || !counts) {
+    set_error("step_mask_forecast: null pointer");
+    return MTRSSM_EINVAL;
+  }
+  if (b_global <= 0 || T <= 0 || span <= 0 || b_local <= 0 || row0 < 0 || row0 + b_local > b_global) {
+    set_error("step_mask_forecast: need B_global, T, span, B_local > 0 and 0 <= row0 <= B_global - B_local (got %lld %lld %lld %lld %lld)",
+              (long long)b_global, (long long)T, (long long)span, (long long)b_local, (long long)row0);
+    return MTRSSM_EINVAL;
+  }
+  if (lo < 1 || hi < lo || hi >= (int64_t)1 << 31) {
+    set_error("step_mask_forecast: need 1 <= lo <= hi < 2^31 (got %lld, %lld)", (long long)lo, (long long)hi);
+    return MTRSSM_EINVAL;
+  }
+  if (u_mask && (!(p_audio >= 0.f && p_audio < 1.f) || !(p_vision >= 0.f && p_vision < 1.f))) {
+    set_error("step_mask_forecast: probabilities must be in [0, 1) (got %g, %g)", (double)p_audio, (double)p_vision);
+    return MTRSSM_EINVAL;
+  }
+  if (b_global * T >= (int64_t)1 << 24) {
+    set_error("step_mask_forecast: %lld frames (the fp32 counts are exact below 2^24)", (long long)(b_global * T));
+    return MTRSSM_EINVAL;
+  }
+  if (span >= (int64_t)1 << 31) { set_error("step_mask_forecast: span %lld does not fit 31 bits", (long long)span); return MTRSSM_EINVAL; }
+  if (((uintptr_t)u_mask & 7) || (((uintptr_t)valid | (uintptr_t)u_context) & 3)) {
+    set_error("step_mask_forecast: u_mask must be 8-byte, valid and u_context 4-byte aligned");
+    return MTRSSM_EINVAL;
+  }
+  if (int rc = clear_async(counts, 2 * sizeof(float), s)) return rc;
+  const int64_t S = (T + span - 1) / span;
+  set_last_kernel("mtrssm::step_mask_forecast_kernel");
+  hipLaunchKernelGGL(step_mask_forecast_kernel, dim3(grid_for(b_global * T) < 64 ? grid_for(b_global * T) : 64), dim3(kThreads), 0, s, valid,
+                     u_mask, u_context, p_audio, p_vision, (int)span, (int)T, (int)S, (int)lo, (int)(hi - lo + 1), (long)b_global, (long)row0,
+                     (long)b_local, codes, seen_audio, seen_vision, target, observed, mask0, last, counts);
+  return check_launch("step_mask_forecast");
+}
+
 int sumsq_launch(const float* x, int64_t n, float* out, hipStream_t s) {
   if (!x || !out || n <= 0) { set_error("sumsq: bad argument"); return MTRSSM_EINVAL; }
   if ((uintptr_t)x & 15) { set_error("sumsq: x must be 16-byte aligned"); return MTRSSM_EINVAL; }

@@ -33,6 +33,11 @@ the graph and read ``reset`` on the device, so ONE graph serves the first chunk 
 resets with nothing at t = 0 and copies ``valid_global`` into a fixed buffer; the mask launch, the counted ELBO epilogue and the
 save at each row's last live step are inside the graph.  A graph is ragged or not for life.
 
+``forecast=`` captures the forecast objective, alone or with ``modality_dropout=`` and ``ragged=True``: the
+``u_context`` uniforms are drawn outside the graph into a fixed buffer with the others; the sampler launch and everything behind it is
+inside, so every replay trains on freshly sampled contexts.  It does not combine with ``masked=True`` (a caller's mask already says
+what is seen) nor with ``state_carry=`` (the state such a step ends with is an open-loop state).
+
 Observations that are ``None`` stay eager-only: a capture cannot drop an encoder per step.
 
 With more than one rank the gradient all-reduce (RCCL) and the optimizer run eagerly after the replay: the
@@ -48,6 +53,7 @@ from multimodal_mtrssm_amd import conv, scan
 from multimodal_mtrssm_amd.carry import StateCarry
 from multimodal_mtrssm_amd.core import _check_modality_mask, check_ragged_rows
 from multimodal_mtrssm_amd.dropout import ModalityDropout, StepMask
+from multimodal_mtrssm_amd.forecast import Forecast
 from multimodal_mtrssm_amd.optim import FlatAdamW, FlatParameters
 from multimodal_mtrssm_amd.parallel import FlatDataParallel, GlobalRowNoise
 
@@ -79,7 +85,7 @@ class CapturedTrainStep:
     def __init__(self, model: torch.nn.Module, flat: FlatParameters, opt: FlatAdamW, dp: FlatDataParallel,  # noqa: PLR0913
                  batch: tuple[Tensor, ...], noise: GlobalRowNoise, *, warmup: int = 3,
                  modality_dropout: ModalityDropout | None = None, masked: bool = False, state_carry: StateCarry | None = None,
-                 ragged: bool = False) -> None:
+                 ragged: bool = False, forecast: Forecast | None = None) -> None:
         if state_carry is not None and not isinstance(state_carry, StateCarry):
             msg = f"state_carry must be a StateCarry, got {type(state_carry).__name__}"
             raise ValueError(msg)
@@ -92,7 +98,17 @@ class CapturedTrainStep:
         if ragged and masked:
             msg = "ragged=True builds its masks from the batch's lengths: it does not combine with masked=True"
             raise ValueError(msg)
+        if forecast is not None and not isinstance(forecast, Forecast):
+            msg = f"forecast must be a Forecast, got {type(forecast).__name__}"
+            raise ValueError(msg)
+        if forecast is not None and masked:
+            msg = "forecast= decides what the model observes: it does not combine with masked=True (the batches' masks already say what is seen)"
+            raise ValueError(msg)
+        if forecast is not None and state_carry is not None:
+            msg = "forecast= does not combine with state_carry=: the state a forecast step ends with is an open-loop state"
+            raise ValueError(msg)
         self.model, self.masked, self.dropout, self.ragged = model, bool(masked), modality_dropout, bool(ragged)
+        self.forecast = None if forecast is None else forecast.for_rank(dp.world, dp.rank)
         self._check_batch_kind(batch)
         self.flat, self.opt, self.dp, self.noise = flat, opt, dp, noise
         b, t = batch[0].shape[:2]
@@ -118,6 +134,8 @@ class CapturedTrainStep:
         if self.dropout is not None:
             self.dropout = self.dropout.for_rank(dp.world, dp.rank)
             self.shapes["u_mask"] = self.dropout.noise_shape(b, t)
+        if self.forecast is not None:
+            self.shapes["u_context"] = self.forecast.noise_shape(b)
         # (a GLOBAL_KEYS entry keeps the rows of every rank: GlobalRowNoise.draw)
         self.uniforms = {k: torch.empty((s[0] * noise.world if k in noise.GLOBAL_KEYS else s[0], *s[1:]), device=dev, dtype=torch.float32)
                          for k, s in self.shapes.items()}
@@ -138,7 +156,10 @@ class CapturedTrainStep:
         if self.dropout is not None and has_mask:
             msg = "this CapturedTrainStep samples its modality masks (modality_dropout=): it takes 6-tuple batches without a mask"
             raise ValueError(msg)
-        if not self.masked and self.dropout is None:
+        if self.forecast is not None and has_mask:
+            msg = "this CapturedTrainStep samples what is observed (forecast=): it takes 6-tuple batches without a mask"
+            raise ValueError(msg)
+        if not self.masked and self.dropout is None and self.forecast is None:
             _refuse_modality_mask(self.model, batch)
         has_valid = getattr(batch, "valid", None) is not None
         if self.ragged and not has_valid:
@@ -162,6 +183,10 @@ class CapturedTrainStep:
         carry = None if self.carry is None else (self.carry, "train", self.reset)  # (its host rules were checked by step())
         if self.masked:  # (validated on the host by step(); codes, planes and counts are derived here, inside the capture)
             out = self.model._elbo_step(self.batch, self.uniforms, StepMask.from_mask(self.mask), carry)  # noqa: SLF001
+        elif self.forecast is not None:  # (a ragged batch's host rule was checked by step(); context AND lengths AND dropout in one launch)
+            ragged = (self.valid_global, self.dp.world, self.dp.rank) if self.ragged else None
+            sm = self.model._forecast_step_mask(self.batch, self.uniforms, self.forecast, self.dropout, ragged=ragged)  # noqa: SLF001
+            out = self.model._elbo_step(self.batch, self.uniforms, sm)  # noqa: SLF001
         elif self.ragged:  # (the host rule was checked by step(); lengths AND dropout in one launch, inside the capture)
             sm = self.model._ragged_step_mask(self.batch, self.uniforms, self.dropout, self.valid_global, self.dp.world, self.dp.rank)  # noqa: SLF001
             out = self.model._elbo_step(self.batch, self.uniforms, sm, carry)  # noqa: SLF001

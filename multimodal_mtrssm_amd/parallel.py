@@ -18,6 +18,7 @@ from torch import Tensor
 
 from multimodal_mtrssm_amd import conv, linear
 from multimodal_mtrssm_amd.dropout import ModalityDropout
+from multimodal_mtrssm_amd.forecast import Forecast
 from multimodal_mtrssm_amd.optim import FlatParameters
 
 
@@ -30,10 +31,10 @@ class GlobalRowNoise:
     rank equals 2 x 32 on two ranks bit for bit.  ``out`` lets a caller keep the result in fixed buffers (the captured
     train step reads them; the draw itself stays outside the capture).
 
-    Keys in ``GLOBAL_KEYS`` are not sliced: ``u_mask`` (modality dropout) reaches every rank with all ``B_global`` rows, because
-    the sampler counts the present frames of the whole global batch."""
+    Keys in ``GLOBAL_KEYS`` are not sliced: ``u_mask`` (modality dropout) and ``u_context`` (the forecast objective) reach every rank
+    with all ``B_global`` rows, because their samplers count the frames of the whole global batch (DESIGN.md sections 6b, 6f)."""
 
-    GLOBAL_KEYS = frozenset({"u_mask"})
+    GLOBAL_KEYS = frozenset({"u_mask", "u_context"})
 
     def __init__(self, seed: int, world: int, rank: int, device: torch.device | str) -> None:
         self.world, self.rank = int(world), int(rank)
@@ -86,6 +87,11 @@ class FlatDataParallel:
         """``dropout`` bound to this rank's rows of the global batch: pass the result as ``shared_step``'s ``modality_dropout``
         (or set it as ``model.modality_dropout``) and draw ``u_mask`` with ``noise_source``."""
         return dropout.for_rank(self.world, self.rank)
+
+    def forecast(self, forecast: Forecast) -> Forecast:
+        """``forecast`` bound to this rank's rows of the global batch: pass the result as ``shared_step``'s ``forecast`` (or set it as
+        ``model.forecast``) and draw ``u_context`` with ``noise_source``."""
+        return forecast.for_rank(self.world, self.rank)
 
     @property
     def grad_scale(self) -> float:
