@@ -682,6 +682,30 @@ int mtrssm_elbo_combine_counted_fwd(const float* nll_a, const float* nll_v, cons
 int mtrssm_elbo_combine_counted_bwd(const float* g_recon, const float* g_k0, const float* g_k1, const float* g_loss, const float* live,
                                     const float* count, int64_t n, float c0, float c1, float* g_nll_a, float* g_nll_v, float* g_kl0,
                                     float* g_kl1, void* stream);
+/* The same epilogue under an ElboSchedule: KL free bits per (b, t), a beta warm-up read from a device
+ * scalar, per-modality reconstruction weights.  One pair serves live / count NULL (every step live, N = n) or given (N = *count)
+ * and kl1 NULL or given.  Every operation is a separately rounded fp32 operation (no fused multiply-add):
+ *   beta   = 1 when warmup = 0, else beta_start + (1 - beta_start) * min(*step / warmup, 1)   (step: device scalar, the optimizer
+ *            steps taken so far; it may be NULL only when warmup = 0, otherwise -1)
+ *   recon  = w_a nll_a + w_v nll_v;   clip_j[i] = kl_j[i] < free_j ? free_j : kl_j[i]   (a NaN stays a NaN)
+ *   k_j    = sum_live clip_j[i] / N * c_j * beta   (0 when N <= 0);   loss = recon + k_0 + k_1
+ *   stats  = { raw0, raw1, active0, active1 }: raw_j = sum_live kl_j[i] / N * c_j (the unscheduled term),
+ *            active_j = #{live i : not kl_j[i] < free_j} / N;  raw1 = active1 = 0 without kl1.
+ * fwd writes recon, k0, k1 (o_k1 may be NULL), loss, beta and the four stats.  bwd reads the STORED beta, never step:
+ *   g_nll_a = w_a (g_recon + g_loss), g_nll_v = w_v (g_recon + g_loss),
+ *   g_kl_j[i] = (g_k_j + g_loss) c_j beta / N where live[i] and not kl_j[i] < free_j (the tie passes), an explicit 0 elsewhere
+ *   and when N <= 0.
+ * Same loop and reduction order as mtrssm_elbo_combine_fwd / _counted_fwd: with free = 0 (and no negative KL), w = (1, 1) and
+ * warmup = 0 the four scalars and both gradient planes are bitwise theirs. */
+typedef struct MtrssmElboSchedule {
+  float c0, c1, free0, free1, w_a, w_v, beta_start, warmup;
+} MtrssmElboSchedule;
+int mtrssm_elbo_schedule_fwd(const float* nll_a, const float* nll_v, const float* kl0, const float* kl1, const float* live,
+                             const float* count, const float* step, int64_t n, MtrssmElboSchedule p, float* o_recon, float* o_k0,
+                             float* o_k1, float* o_loss, float* o_beta, float* o_stats, void* stream);
+int mtrssm_elbo_schedule_bwd(const float* g_recon, const float* g_k0, const float* g_k1, const float* g_loss, const float* kl0,
+                             const float* kl1, const float* live, const float* count, const float* beta, int64_t n,
+                             MtrssmElboSchedule p, float* g_nll_a, float* g_nll_v, float* g_kl0, float* g_kl1, void* stream);
 /* Categorical head of the initial state (core.py:121-135, mmtrssm core.py:321-362): `logits` [rows][K * C] flat (K categoricals
  * of C classes, softmax over classes), `u` [rows][K] uniforms -> logp, probs [rows][K][C] and the inverse-CDF one-hot sample
  * onehot [rows][K * C] (index = #{c <= C - 2 : cumulative probability <= u}, the cumulative sum a left fold).  The straight-through

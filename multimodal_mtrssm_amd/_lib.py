@@ -82,6 +82,8 @@ Gemm = _struct("MtrssmGemm", _ptrs("A", "B", "C", "bias", "zgrad", "colsum") + [
     "M", "N", "R", "lda", "ldb", "ldc", "ldz", "a_rmajor", "b_rmajor", "act_a", "act_b", "act_out", "act_z", "accumulate", "split_r")]
     + [("tickets", _p), ("n_tickets", _i), ("mfma_split", _i)])
 
+ElboSchedule = _struct("MtrssmElboSchedule", [(n, _f) for n in ("c0", "c1", "free0", "free1", "w_a", "w_v", "beta_start", "warmup")])
+
 STATE_MAX = 6  # MTRSSM_STATE_MAX
 StateTable = _struct("MtrssmStateTable", [
     ("count", _i), ("width", _i * STATE_MAX), ("src_stride", C.c_int64 * STATE_MAX), ("src", _p * STATE_MAX), ("alt", _p * STATE_MAX),
@@ -149,6 +151,8 @@ SYMBOLS: dict[str, tuple[type | None, list[type]]] = {
                                             _p, _p, _p, _p, _p, _p]),
     "mtrssm_elbo_combine_counted_fwd": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int64, C.c_float, C.c_float, _p, _p, _p, _p, _p]),
     "mtrssm_elbo_combine_counted_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int64, C.c_float, C.c_float, _p, _p, _p, _p, _p]),
+    "mtrssm_elbo_schedule_fwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, C.c_int64, ElboSchedule, _p, _p, _p, _p, _p, _p, _p]),
+    "mtrssm_elbo_schedule_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, C.c_int64, ElboSchedule, _p, _p, _p, _p, _p]),
     "mtrssm_elbo_combine_fwd": (C.c_int, [_p, _p, _p, _p, C.c_int64, C.c_float, C.c_float, _p, _p, _p, _p, _p]),
     "mtrssm_elbo_combine_bwd": (C.c_int, [_p, _p, _p, _p, C.c_int64, C.c_float, C.c_float, _p, _p, _p, _p, _p]),
     "mtrssm_categorical_sample_fwd": (C.c_int, [_p, _p, C.c_int64, _i, _i, _p, _p, _p, _p]),

@@ -26,6 +26,7 @@ from multimodal_mtrssm_amd.dropout import ModalityDropout, StepMask, ragged_step
 from multimodal_mtrssm_amd.forecast import Forecast
 from multimodal_mtrssm_amd.networks import MTRNN, Representation, Transition
 from multimodal_mtrssm_amd.objective import likelihood
+from multimodal_mtrssm_amd.schedule import ElboSchedule, ElboTerms
 from multimodal_mtrssm_amd.state import MTState, State
 
 try:  # the real trainer, when it is installed next to the reference
@@ -179,10 +180,89 @@ class _ElboCombineCounted(torch.autograd.Function):
         return g_a, g_v, g_kl0, g_kl1, None, None, None, None
 
 
+class _ElboScheduled(torch.autograd.Function):
+    """The epilogue under an ``ElboSchedule`` (``mtrssm_elbo_schedule_fwd / _bwd``), one launch each way for every
+    case: ``live`` / ``count`` None or given, ``kl1`` None or given.  Returns ``(recon, k_0, k_1, loss, beta, stats)``, ``stats`` float32
+    ``[4]`` = raw_0, raw_1, active_0, active_1; ``beta`` and ``stats`` carry no gradient.  The backward reads the stored ``beta``."""
+
+    @staticmethod
+    def forward(ctx, nll_a: Tensor, nll_v: Tensor, kl0: Tensor, kl1: Tensor | None, live: Tensor | None, count: Tensor | None,  # noqa: ANN001, ANN205, PLR0913
+                step: Tensor | None, sched: ElboSchedule, c0: float, c1: float):
+        from multimodal_mtrssm_amd import _lib  # noqa: PLC0415
+
+        ctx.set_materialize_grads(False)
+        nll_a, nll_v, kl0 = nll_a.contiguous().float(), nll_v.contiguous().float(), kl0.contiguous().float()
+        kl1 = None if kl1 is None else kl1.contiguous().float()
+        if live is not None:
+            live, count = live.contiguous().float(), count.contiguous().float()
+            if live.numel() != kl0.numel() or count.numel() != 1:
+                msg = f"live must have one entry per KL step ({kl0.numel()}), count one; got {live.numel()} and {count.numel()}"
+                raise ValueError(msg)
+        if kl1 is not None and kl1.numel() != kl0.numel():
+            msg = f"the two KL planes must have the same number of steps, got {kl0.numel()} and {kl1.numel()}"
+            raise ValueError(msg)
+        if step is not None:
+            step = step.contiguous().float()
+            if step.numel() != 1:
+                msg = f"step must be one device scalar, got {step.numel()} entries"
+                raise ValueError(msg)
+        par = _lib.ElboSchedule(float(c0), float(c1), sched.free_nats, sched.free_nats_h, sched.recon_weights[0], sched.recon_weights[1],
+                                sched.beta_start, float(sched.warmup_steps))
+        outs = [torch.empty((), device=kl0.device, dtype=torch.float32) for _ in range(5)]
+        stats = torch.empty(4, device=kl0.device, dtype=torch.float32)
+        _lib.check(_lib.load().mtrssm_elbo_schedule_fwd(
+            _lib.ptr(nll_a), _lib.ptr(nll_v), _lib.ptr(kl0), _lib.ptr(kl1), _lib.ptr(live), _lib.ptr(count), _lib.ptr(step), kl0.numel(), par,
+            *(_lib.ptr(o) for o in outs), _lib.ptr(stats), _lib.stream_ptr(kl0.device)), "mtrssm_elbo_schedule_fwd")
+        ctx.meta = (kl0.shape, None if kl1 is None else kl1.shape, par)
+        ctx.dev = kl0.device
+        ctx.save_for_backward(kl0, kl1, live, count, outs[4])
+        ctx.mark_non_differentiable(outs[4], stats)
+        return outs[0], outs[1], outs[2], outs[3], outs[4], stats
+
+    @staticmethod
+    def backward(ctx, g_recon, g_k0, g_k1, g_loss, _g_beta, _g_stats):  # noqa: ANN001, ANN205, PLR0913
+        from multimodal_mtrssm_amd import _lib  # noqa: PLC0415
+
+        shape0, shape1, par = ctx.meta
+        kl0, kl1, live, count, beta = ctx.saved_tensors
+        g_a, g_v = (torch.empty((), device=ctx.dev, dtype=torch.float32) for _ in range(2))
+        g_kl0 = torch.empty(shape0, device=ctx.dev, dtype=torch.float32)
+        g_kl1 = None if shape1 is None else torch.empty(shape1, device=ctx.dev, dtype=torch.float32)
+        opt = lambda t: None if t is None else _lib.ptr(t.contiguous().float())  # noqa: E731
+        _lib.check(_lib.load().mtrssm_elbo_schedule_bwd(
+            opt(g_recon), opt(g_k0), opt(g_k1) if shape1 is not None else None, opt(g_loss), _lib.ptr(kl0), _lib.ptr(kl1), _lib.ptr(live),
+            _lib.ptr(count), _lib.ptr(beta), kl0.numel(), par, _lib.ptr(g_a), _lib.ptr(g_v), _lib.ptr(g_kl0), _lib.ptr(g_kl1),
+            _lib.stream_ptr(ctx.dev)), "mtrssm_elbo_schedule_bwd")
+        return g_a, g_v, g_kl0, g_kl1, None, None, None, None, None, None
+
+
+def _elbo_scheduled(nll_a: Tensor, nll_v: Tensor, kl0: Tensor, c0: float, kl1: Tensor | None, c1: float, step_mask: StepMask | None,  # noqa: PLR0913
+                    schedule: ElboSchedule) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """``_elbo`` under ``schedule``: the new pair on the GPU, the rule in eager torch elsewhere; ``schedule.stats`` keeps the rest."""
+    if not isinstance(schedule, ElboSchedule):
+        msg = f"elbo_schedule must be an ElboSchedule, got {type(schedule).__name__}"
+        raise ValueError(msg)
+    live = count = None
+    if step_mask is not None and step_mask.live is not None:
+        live, count = step_mask.live, step_mask.count_live
+    step = schedule.step_on(kl0.device)
+    if kl0.is_cuda and nll_a.dim() == 0 and nll_v.dim() == 0:
+        recon, k0, k1, loss, beta, stats = _ElboScheduled.apply(nll_a, nll_v, kl0, kl1, live, count, step, schedule, c0, c1)
+        terms = ElboTerms(recon, k0, k1, loss, beta, stats[0], stats[1], stats[2], stats[3])
+    else:
+        terms = schedule.reference(nll_a, nll_v, kl0, c0, kl1, c1, live, count, step)
+    schedule.record(terms, higher=kl1 is not None)
+    return terms.recon, terms.k0, terms.k1, terms.loss
+
+
 def _elbo(nll_a: Tensor, nll_v: Tensor, kl0: Tensor, c0: float, kl1: Tensor | None = None, c1: float = 0.0,  # noqa: PLR0913
-          step_mask: StepMask | None = None) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+          step_mask: StepMask | None = None, schedule: ElboSchedule | None = None) -> tuple[Tensor, Tensor, Tensor, Tensor]:
     """``(recon, kl_0, kl_1, loss)``; on the GPU one fused launch, elsewhere the eager arithmetic of the reference.  A ``step_mask``
-    that carries ``live`` (a ragged batch) takes the counted epilogue: the KL sums over live steps / ``count_live``."""
+    that carries ``live`` (a ragged batch) takes the counted epilogue: the KL sums over live steps / ``count_live``.  With a
+    ``schedule`` the terms are weighed by its rule: ``kl_j`` is the clipped, beta-weighted term, ``recon`` the
+    weighted sum, and ``schedule.stats`` holds ``beta``, the active fractions and the unscheduled KL terms."""
+    if schedule is not None:
+        return _elbo_scheduled(nll_a, nll_v, kl0, c0, kl1, c1, step_mask, schedule)
     if step_mask is not None and step_mask.live is not None:
         if kl0.is_cuda and nll_a.dim() == 0 and nll_v.dim() == 0:
             return _ElboCombineCounted.apply(nll_a, nll_v, kl0, kl1, step_mask.live, step_mask.count_live, c0, c1)
@@ -332,6 +412,7 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         self.state_carry: StateCarry | None = None  # training_step / validation_step continue from its "train" / "val" set
         self.forecast: Forecast | None = None  # training_step trains the forecast objective with it
         self.val_forecast: Forecast | None = None  # validation_step adds a forecast step at this (fixed) context and logs val/forecast/*
+        self.elbo_schedule: ElboSchedule | None = None  # training_step (never validation_step) weighs the loss terms with it
 
     # -- batch accessors (mrssm core.py:310-355) --------------------------------------------
     @staticmethod
@@ -680,7 +761,7 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
     def shared_step(self, batch: tuple[Tensor, ...], noise: Noise | None = None, modality_mask: Tensor | None = None,  # noqa: PLR0913
                     modality_dropout: ModalityDropout | None = None, state_carry: StateCarry | None = None,
                     reset: Tensor | None = None, *, carry_prefix: str = "train", lengths: Tensor | None = None,
-                    forecast: Forecast | None = None) -> dict[str, Tensor]:
+                    forecast: Forecast | None = None, elbo_schedule: ElboSchedule | None = None) -> dict[str, Tensor]:
         """``core.py:187-221``: ``loss = recon + kl_coeff * KL(post || prior)`` (MMTRSSM, ``mmtrssm core.py:563-606``:
         ``recon + kl_coeff KL_l + kl_coeff w_kl_h KL_h``).  ``modality_mask`` (or a 7th batch entry, bool ``[B, T, 2]``): each
         recon term averages over the frames where its modality is present; the KL stays the mean over all B*T (0 on steps with
@@ -701,7 +782,12 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         ``forecast`` (a ``Forecast``): each row observes a context of ``c_b`` frames sampled from
         ``noise["u_context"]`` (drawn here when absent) and runs open loop after it; both modalities are reconstructed on every live
         frame, the KL sums over the observed steps / their count.  Alone, with ``modality_dropout`` and / or with lengths; not with a
-        modality mask (it already says what is seen) nor with a ``state_carry`` (the state it would save is an open-loop state)."""
+        modality mask (it already says what is seen) nor with a ``state_carry`` (the state it would save is an open-loop state).
+
+        ``elbo_schedule`` (an ``ElboSchedule``): free nats per step, a beta warm-up and per-modality weights in the
+        scalar epilogue, with every option above.  ``kl`` (``kl_h``) is then the clipped, beta-weighted term and ``recon`` the weighted
+        sum, so ``loss = recon + kl (+ kl_h)`` still holds; ``recon/audio`` and ``recon/vision`` stay unweighted; the dict gains ``kl_raw``
+        (``kl_h_raw``), the unscheduled term, after the existing keys."""
         if forecast is not None:
             if modality_mask is not None or self.get_modality_mask_from_batch(batch) is not None:
                 msg = "forecast= decides what the model observes: a modality_mask (or a 7-tuple batch) already says what is seen, give one of them"
@@ -709,15 +795,15 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
             if state_carry is not None:
                 msg = "forecast= does not combine with state_carry: the state a forecast step ends with is an open-loop state, not one to continue from"
                 raise ValueError(msg)
-            return self._elbo_step(batch, noise, self._forecast_step_mask(batch, noise, forecast, modality_dropout, lengths))
+            return self._elbo_step(batch, noise, self._forecast_step_mask(batch, noise, forecast, modality_dropout, lengths), schedule=elbo_schedule)
         reset_host = None  # without a carry every row starts from its fresh state: every row resets
         if state_carry is not None:
             reset_host = getattr(batch, "reset_host", None) if reset is None else (None if reset.is_cuda else reset)
         on_device = state_carry is not None and isinstance(reset, Tensor) and reset.is_cuda  # (trusted, as the carry trusts it)
         sm = self._step_mask(batch, noise, modality_mask, modality_dropout, lengths, reset_host, trust_reset=on_device)
         if state_carry is None:
-            return self._elbo_step(batch, noise, sm)
-        return self._elbo_step(batch, noise, sm, self._carry_of(batch, state_carry, reset, carry_prefix))
+            return self._elbo_step(batch, noise, sm, schedule=elbo_schedule)
+        return self._elbo_step(batch, noise, sm, self._carry_of(batch, state_carry, reset, carry_prefix), schedule=elbo_schedule)
 
     @staticmethod
     def _carry_of(batch: tuple[Tensor, ...], state_carry: StateCarry, reset: Tensor | None, prefix: str) -> tuple[StateCarry, str, Tensor]:
@@ -762,7 +848,7 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
             carry[0].save(carry[1], {k: out[v] for k, v in self._LAST_KEYS.items()}, last)
 
     def _elbo_step(self, batch: tuple[Tensor, ...], noise: Noise | None, sm: StepMask | None,
-                   carry: tuple[StateCarry, str, Tensor] | None = None) -> dict[str, Tensor]:
+                   carry: tuple[StateCarry, str, Tensor] | None = None, schedule: ElboSchedule | None = None) -> dict[str, Tensor]:
         """``shared_step`` behind the mask handling (the captured step enters here with a mask it validated itself)."""
         action_input = batch[0]
         audio_obs, vision_obs = self.get_observations_from_batch(batch)
@@ -777,17 +863,21 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         self._save_carry(out, carry, None if sm is None else sm.last)
         feature = torch.cat([out["deter"], out["post_stoch"]], dim=-1)
         parts = self._reconstruction_losses(feature, self.get_targets_from_batch(batch), sum_recon=False, step_mask=sm)
-        recon, kl_div, _, loss = _elbo(parts["recon/audio"], parts["recon/vision"], out["kl"], float(self.kl_coeff), step_mask=sm)
+        recon, kl_div, _, loss = _elbo(parts["recon/audio"], parts["recon/vision"], out["kl"], float(self.kl_coeff), step_mask=sm, schedule=schedule)
+        if schedule is not None:
+            return {"recon": recon, **parts, "kl": kl_div, "loss": loss, "kl_raw": schedule.stats["kl_raw"]}
         return {"recon": recon, **parts, "kl": kl_div, "loss": loss}
 
-    def _step(self, batch: tuple[Tensor, ...], prefix: str, *, with_loss_key: bool,
-              modality_dropout: ModalityDropout | None = None, forecast: Forecast | None = None) -> dict[str, Tensor]:
+    def _step(self, batch: tuple[Tensor, ...], prefix: str, *, with_loss_key: bool, modality_dropout: ModalityDropout | None = None,  # noqa: PLR0913
+              forecast: Forecast | None = None, elbo_schedule: ElboSchedule | None = None) -> dict[str, Tensor]:
         if forecast is not None:  # (with a state_carry set too, shared_step refuses)
-            loss_dict = self.shared_step(batch, modality_dropout=modality_dropout, state_carry=self.state_carry, forecast=forecast)
+            loss_dict = self.shared_step(batch, modality_dropout=modality_dropout, state_carry=self.state_carry, forecast=forecast,
+                                         elbo_schedule=elbo_schedule)
         elif self.state_carry is None:
-            loss_dict = self.shared_step(batch, modality_dropout=modality_dropout)
+            loss_dict = self.shared_step(batch, modality_dropout=modality_dropout, elbo_schedule=elbo_schedule)
         else:
-            loss_dict = self.shared_step(batch, modality_dropout=modality_dropout, state_carry=self.state_carry, carry_prefix=prefix)
+            loss_dict = self.shared_step(batch, modality_dropout=modality_dropout, state_carry=self.state_carry, carry_prefix=prefix,
+                                         elbo_schedule=elbo_schedule)
         renamed = {"loss": loss_dict["loss"]} if with_loss_key else {}
         renamed[f"{prefix}/loss"] = loss_dict["loss"]
         for key, value in loss_dict.items():
@@ -797,11 +887,13 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         return renamed
 
     def training_step(self, batch: tuple[Tensor, ...], _: int = 0) -> dict[str, Tensor]:
-        return self._step(batch, "train", with_loss_key=True, modality_dropout=self.modality_dropout, forecast=self.forecast)
+        return self._step(batch, "train", with_loss_key=True, modality_dropout=self.modality_dropout, forecast=self.forecast,
+                          elbo_schedule=self.elbo_schedule)
 
     def validation_step(self, batch: tuple[Tensor, ...], _batch_index: int = 0) -> dict[str, Tensor]:
         """``val/*`` of the closed-loop step; with ``self.val_forecast`` set, a second step on the same batch observes that context and
-        forecasts the rest (from the chunk's own frame 0, no carry), logged as ``val/forecast/*``."""
+        forecasts the rest (from the chunk's own frame 0, no carry), logged as ``val/forecast/*``.  ``self.elbo_schedule`` is not used
+        here: ``val/loss`` stays the plain ELBO that schedulers and checkpointing monitor."""
         logged = self._step(batch, "val", with_loss_key=False)
         if self.val_forecast is not None:
             fore = {f"val/forecast/{k}": v for k, v in self.shared_step(batch, forecast=self.val_forecast).items()}
@@ -969,7 +1061,7 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
         return MTState(distribution_h=fresh.distribution_h, distribution_l=fresh.distribution_l, **got)
 
     def _elbo_step(self, batch: tuple[Tensor, ...], noise: Noise | None, sm: StepMask | None,
-                   carry: tuple[StateCarry, str, Tensor] | None = None) -> dict[str, Tensor]:
+                   carry: tuple[StateCarry, str, Tensor] | None = None, schedule: ElboSchedule | None = None) -> dict[str, Tensor]:
         """``mmtrssm core.py:563-606``: ``loss = recon + kl_coeff KL_l + kl_coeff w_kl_h KL_h`` (``shared_step``'s body)."""
         action_input = batch[0]
         audio_obs, vision_obs = self.get_observations_from_batch(batch)
@@ -984,7 +1076,10 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
         feature = torch.cat([out["deter_h"], out["post_stoch_h"], out["deter_l"], out["post_stoch_l"]], dim=-1)
         parts = self._reconstruction_losses(feature, self.get_targets_from_batch(batch), sum_recon=False, step_mask=sm)
         recon, kl_div_l, kl_div_h, loss = _elbo(parts["recon/audio"], parts["recon/vision"], out["kl_l"], float(self.kl_coeff), out["kl_h"],
-                                                float(self.kl_coeff * self.w_kl_h), step_mask=sm)
+                                                float(self.kl_coeff * self.w_kl_h), step_mask=sm, schedule=schedule)
+        if schedule is not None:
+            return {"recon": recon, **parts, "kl": kl_div_l, "kl_h": kl_div_h, "loss": loss, "kl_raw": schedule.stats["kl_raw"],
+                    "kl_h_raw": schedule.stats["kl_h_raw"]}
         return {"recon": recon, **parts, "kl": kl_div_l, "kl_h": kl_div_h, "loss": loss}
 
 

@@ -41,6 +41,10 @@ int elbo_combine_counted_fwd_launch(const float*, const float*, const float*, co
                                     float*, float*, float*, hipStream_t);
 int elbo_combine_counted_bwd_launch(const float*, const float*, const float*, const float*, const float*, const float*, int64_t, float, float, float*,
                                     float*, float*, float*, hipStream_t);
+int elbo_schedule_fwd_launch(const float*, const float*, const float*, const float*, const float*, const float*, const float*, int64_t,
+                             MtrssmElboSchedule, float*, float*, float*, float*, float*, float*, hipStream_t);
+int elbo_schedule_bwd_launch(const float*, const float*, const float*, const float*, const float*, const float*, const float*, const float*,
+                             const float*, int64_t, MtrssmElboSchedule, float*, float*, float*, float*, hipStream_t);
 int conv_gather_gemm_pair_launch(const MtrssmConvGeom*, const float*, const float*, const float*, const unsigned short*, const float*, const float*, const float*, float*,
                                  const MtrssmConvGeom*, const float*, const float*, const float*, const unsigned short*, const float*, const float*, const float*, float*, hipStream_t);
 int conv_residual_fwd_supported(const MtrssmConvGeom*);
@@ -293,6 +297,18 @@ MTRSSM_API int mtrssm_step_mask_forecast(const int32_t* valid, const float* u_ma
                                          int32_t* last, float* counts, void* stream) {
   return step_mask_forecast_launch(valid, u_mask, u_context, b_global, steps, span, p_audio, p_vision, lo, hi, row0, b_local, codes, seen_audio,
                                    seen_vision, target, observed, mask0, last, counts, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_elbo_schedule_fwd(const float* nll_a, const float* nll_v, const float* kl0, const float* kl1, const float* live,
+                                       const float* count, const float* step, int64_t n, MtrssmElboSchedule p, float* o_recon, float* o_k0,
+                                       float* o_k1, float* o_loss, float* o_beta, float* o_stats, void* stream) {
+  return elbo_schedule_fwd_launch(nll_a, nll_v, kl0, kl1, live, count, step, n, p, o_recon, o_k0, o_k1, o_loss, o_beta, o_stats,
+                                  static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_elbo_schedule_bwd(const float* g_recon, const float* g_k0, const float* g_k1, const float* g_loss, const float* kl0,
+                                       const float* kl1, const float* live, const float* count, const float* beta, int64_t n,
+                                       MtrssmElboSchedule p, float* g_nll_a, float* g_nll_v, float* g_kl0, float* g_kl1, void* stream) {
+  return elbo_schedule_bwd_launch(g_recon, g_k0, g_k1, g_loss, kl0, kl1, live, count, beta, n, p, g_nll_a, g_nll_v, g_kl0, g_kl1,
+                                  static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int mtrssm_elbo_combine_counted_fwd(const float* nll_a, const float* nll_v, const float* kl0, const float* kl1, const float* live,
                                                const float* count, int64_t n, float c0, float c1, float* o_recon, float* o_k0, float* o_k1,

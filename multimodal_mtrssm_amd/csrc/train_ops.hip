@@ -479,6 +479,114 @@ int elbo_combine_counted_bwd_launch(const float* g_recon, const float* g_k0, con
   return check_launch("elbo_combine_counted_bwd");
 }
 
+// The epilogue under an ElboSchedule: free bits per (b, t), a beta warm-up read from the device scalar
+// *step, per-modality reconstruction weights.  ONE pair for live / count null (N = n) or given (N = *count) and kl1 null or given.
+// Every operation is rounded on its own (contraction is switched off in both kernels): schedule.py's torch rule reproduces beta and
+// the gradient planes bit for bit.  The sums take elbo_combine*_fwd_kernel's loop and block_sum's order (wave_sum, one partial per
+// wave, wave_sum over the partials), six of them behind one barrier: the neutral schedule gives those kernels' scalars bitwise.
+//   s[0..2] = sum_live clip_0, sum_live kl_0, #{live, not kl_0 < free_0};  s[3..5] the same for kl_1
+__global__ void elbo_schedule_fwd_kernel(const float* __restrict__ nll_a, const float* __restrict__ nll_v, const float* __restrict__ kl0,
+                                         const float* __restrict__ kl1, const float* __restrict__ live, const float* __restrict__ count,
+                                         const float* __restrict__ step, int64_t n, MtrssmElboSchedule p, float* __restrict__ o_recon,
+                                         float* __restrict__ o_k0, float* __restrict__ o_k1, float* __restrict__ o_loss, float* __restrict__ o_beta,
+                                         float* __restrict__ o_stats) {
+#pragma clang fp contract(off)
+  __shared__ float red[6][kThreads / kWave];
+  float a[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
+    const bool on = !live || live[i] != 0.f;
+    const float x0 = kl0[i];
+    const bool low0 = x0 < p.free0;
+    a[0] += on ? (low0 ? p.free0 : x0) : 0.f;
+    a[1] += on ? x0 : 0.f;
+    a[2] += on && !low0 ? 1.f : 0.f;
+    if (kl1) {
+      const float x1 = kl1[i];
+      const bool low1 = x1 < p.free1;
+      a[3] += on ? (low1 ? p.free1 : x1) : 0.f;
+      a[4] += on ? x1 : 0.f;
+      a[5] += on && !low1 ? 1.f : 0.f;
+    }
+  }
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const float v = wave_sum(a[k]);
+    if (lane == 0) red[k][wave] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x >= kWave) return;
+  float s[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) s[k] = wave_sum(threadIdx.x < blockDim.x / kWave ? red[k][threadIdx.x] : 0.f);
+  if (threadIdx.x == 0) {
+    const float cnt = live ? count[0] : (float)n;
+    const bool some = cnt > 0.f;
+    float beta = 1.f;
+    if (p.warmup > 0.f) {
+      const float r = step[0] / p.warmup;
+      beta = p.beta_start + (1.f - p.beta_start) * (r > 1.f ? 1.f : r);
+    }
+    const float recon = p.w_a * nll_a[0] + p.w_v * nll_v[0];
+    const float k0 = some ? s[0] / cnt * p.c0 * beta : 0.f, k1 = kl1 && some ? s[3] / cnt * p.c1 * beta : 0.f;
+    o_recon[0] = recon; o_k0[0] = k0; if (o_k1) o_k1[0] = k1; o_loss[0] = recon + k0 + k1; o_beta[0] = beta;
+    o_stats[0] = some ? s[1] / cnt * p.c0 : 0.f;
+    o_stats[1] = kl1 && some ? s[4] / cnt * p.c1 : 0.f;
+    o_stats[2] = some ? s[2] / cnt : 0.f;
+    o_stats[3] = kl1 && some ? s[5] / cnt : 0.f;
+  }
+}
+// Backward: reads the beta the forward stored.  A step that is dead or below its threshold gets an explicit zero.
+__global__ void elbo_schedule_bwd_kernel(const float* __restrict__ g_recon, const float* __restrict__ g_k0, const float* __restrict__ g_k1,
+                                         const float* __restrict__ g_loss, const float* __restrict__ kl0, const float* __restrict__ kl1,
+                                         const float* __restrict__ live, const float* __restrict__ count, const float* __restrict__ beta,
+                                         int64_t n, MtrssmElboSchedule p, float* __restrict__ g_nll_a, float* __restrict__ g_nll_v,
+                                         float* __restrict__ g_kl0, float* __restrict__ g_kl1) {
+#pragma clang fp contract(off)
+  const float gl = g_loss ? g_loss[0] : 0.f;
+  const float gn = (g_recon ? g_recon[0] : 0.f) + gl;
+  const float cnt = live ? count[0] : (float)n;
+  const float b = beta[0];
+  const float v0 = cnt > 0.f ? ((g_k0 ? g_k0[0] : 0.f) + gl) * p.c0 * b / cnt : 0.f;
+  const float v1 = cnt > 0.f ? ((g_k1 ? g_k1[0] : 0.f) + gl) * p.c1 * b / cnt : 0.f;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i == 0) { g_nll_a[0] = p.w_a * gn; g_nll_v[0] = p.w_v * gn; }
+  if (i < n) {
+    const bool on = !live || live[i] != 0.f;
+    g_kl0[i] = on && !(kl0[i] < p.free0) ? v0 : 0.f;
+    if (g_kl1) g_kl1[i] = on && !(kl1[i] < p.free1) ? v1 : 0.f;
+  }
+}
+static bool elbo_schedule_ok(const char* what, const MtrssmElboSchedule& p, const float* live, const float* count) {
+  if ((live == nullptr) != (count == nullptr)) { set_error("%s: live and count come together (both null: every step is live)", what); return false; }
+  if (!(p.warmup >= 0.f) || !(p.warmup < 16777216.f)) { set_error("%s: warmup must lie in [0, 2^24), got %g", what, (double)p.warmup); return false; }
+  return true;
+}
+int elbo_schedule_fwd_launch(const float* nll_a, const float* nll_v, const float* kl0, const float* kl1, const float* live, const float* count,
+                             const float* step, int64_t n, MtrssmElboSchedule p, float* o_recon, float* o_k0, float* o_k1, float* o_loss,
+                             float* o_beta, float* o_stats, hipStream_t s) {
+  if (!nll_a || !nll_v || !kl0 || !o_recon || !o_k0 || !o_loss || !o_beta || !o_stats || n <= 0) {
+    set_error("elbo_schedule_fwd: bad argument");
+    return MTRSSM_EINVAL;
+  }
+  if (!elbo_schedule_ok("elbo_schedule_fwd", p, live, count)) return MTRSSM_EINVAL;
+  if (p.warmup > 0.f && !step) { set_error("elbo_schedule_fwd: a warm-up of %g steps needs the device scalar step (null)", (double)p.warmup); return MTRSSM_EINVAL; }
+  set_last_kernel("mtrssm::elbo_schedule_fwd_kernel");
+  hipLaunchKernelGGL(elbo_schedule_fwd_kernel, dim3(1), dim3(kThreads), 0, s, nll_a, nll_v, kl0, kl1, live, count, step, n, p, o_recon, o_k0, o_k1,
+                     o_loss, o_beta, o_stats);
+  return check_launch("elbo_schedule_fwd");
+}
+int elbo_schedule_bwd_launch(const float* g_recon, const float* g_k0, const float* g_k1, const float* g_loss, const float* kl0, const float* kl1,
+                             const float* live, const float* count, const float* beta, int64_t n, MtrssmElboSchedule p, float* g_nll_a,
+                             float* g_nll_v, float* g_kl0, float* g_kl1, hipStream_t s) {
+  if (!kl0 || !beta || !g_nll_a || !g_nll_v || !g_kl0 || (g_kl1 && !kl1) || n <= 0) { set_error("elbo_schedule_bwd: bad argument"); return MTRSSM_EINVAL; }
+  if (!elbo_schedule_ok("elbo_schedule_bwd", p, live, count)) return MTRSSM_EINVAL;
+  set_last_kernel("mtrssm::elbo_schedule_bwd_kernel");
+  hipLaunchKernelGGL(elbo_schedule_bwd_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, g_recon, g_k0, g_k1, g_loss,
+                     kl0, kl1, live, count, beta, n, p, g_nll_a, g_nll_v, g_kl0, g_kl1);
+  return check_launch("elbo_schedule_bwd");
+}
+
 int nll_fwd_launch(const float* pred, const float* target, int64_t frames, int64_t event, int act, float* out, hipStream_t s) {
   if (!pred || !target || !out || frames <= 0 || event <= 0) { set_error("gaussian_nll_fwd: bad argument"); return MTRSSM_EINVAL; }
   if (act != MTRSSM_ACT_IDENTITY && act != MTRSSM_ACT_TANH) { set_error("gaussian_nll: the fused output activation is Identity or Tanh (got %d)", act); return MTRSSM_EINVAL; }

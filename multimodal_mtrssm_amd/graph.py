@@ -38,6 +38,10 @@ save at each row's last live step are inside the graph.  A graph is ragged or no
 inside, so every replay trains on freshly sampled contexts.  It does not combine with ``masked=True`` (a caller's mask already says
 what is seen) nor with ``state_carry=`` (the state such a step ends with is an open-loop state).
 
+``elbo_schedule=`` weighs the loss terms inside the capture, with every mode above: the schedule is bound to the
+optimizer's device-resident count of steps taken, which the captured epilogue reads, so every replay sees its own beta (the warm-up
+steps of the construction put that count back with the rest of ``opt.state``).
+
 Observations that are ``None`` stay eager-only: a capture cannot drop an encoder per step.
 
 With more than one rank the gradient all-reduce (RCCL) and the optimizer run eagerly after the replay: the
@@ -56,6 +60,7 @@ from multimodal_mtrssm_amd.dropout import ModalityDropout, StepMask
 from multimodal_mtrssm_amd.forecast import Forecast
 from multimodal_mtrssm_amd.optim import FlatAdamW, FlatParameters
 from multimodal_mtrssm_amd.parallel import FlatDataParallel, GlobalRowNoise
+from multimodal_mtrssm_amd.schedule import ElboSchedule
 
 
 def _refuse_modality_mask(model: torch.nn.Module, batch: tuple[Tensor, ...]) -> None:
@@ -80,12 +85,16 @@ class CapturedTrainStep:
     takes only that kind of batch, an unmasked graph only 6-tuples.
 
     ``state_carry`` (a ``StateCarry`` of the batch's rows): the step continues its ``"train"`` set (module docstring).  The warm-up
-    steps reset every row and leave the carry as they found it; a carry that was empty is empty after construction."""
+    steps reset every row and leave the carry as they found it; a carry that was empty is empty after construction.
+
+    ``elbo_schedule`` (an ``ElboSchedule``): the constructor calls ``elbo_schedule.bind(opt)`` on the CALLER's object -- whatever it
+    was bound to or set to before, it reads this optimizer's steps taken from now on.  Its ``stats`` are tensors of the graph's
+    memory, rewritten by every replay and valid while the capture lives; ``close()`` empties them."""
 
     def __init__(self, model: torch.nn.Module, flat: FlatParameters, opt: FlatAdamW, dp: FlatDataParallel,  # noqa: PLR0913
                  batch: tuple[Tensor, ...], noise: GlobalRowNoise, *, warmup: int = 3,
                  modality_dropout: ModalityDropout | None = None, masked: bool = False, state_carry: StateCarry | None = None,
-                 ragged: bool = False, forecast: Forecast | None = None) -> None:
+                 ragged: bool = False, forecast: Forecast | None = None, elbo_schedule: ElboSchedule | None = None) -> None:
         if state_carry is not None and not isinstance(state_carry, StateCarry):
             msg = f"state_carry must be a StateCarry, got {type(state_carry).__name__}"
             raise ValueError(msg)
@@ -107,7 +116,11 @@ class CapturedTrainStep:
         if forecast is not None and state_carry is not None:
             msg = "forecast= does not combine with state_carry=: the state a forecast step ends with is an open-loop state"
             raise ValueError(msg)
+        if elbo_schedule is not None and not isinstance(elbo_schedule, ElboSchedule):
+            msg = f"elbo_schedule must be an ElboSchedule, got {type(elbo_schedule).__name__}"
+            raise ValueError(msg)
         self.model, self.masked, self.dropout, self.ragged = model, bool(masked), modality_dropout, bool(ragged)
+        self.schedule = None if elbo_schedule is None else elbo_schedule.bind(opt)  # (beta follows opt.state[1], read on the device)
         self.forecast = None if forecast is None else forecast.for_rank(dp.world, dp.rank)
         self._check_batch_kind(batch)
         self.flat, self.opt, self.dp, self.noise = flat, opt, dp, noise
@@ -182,19 +195,19 @@ class CapturedTrainStep:
         self.opt.zero_grad()
         carry = None if self.carry is None else (self.carry, "train", self.reset)  # (its host rules were checked by step())
         if self.masked:  # (validated on the host by step(); codes, planes and counts are derived here, inside the capture)
-            out = self.model._elbo_step(self.batch, self.uniforms, StepMask.from_mask(self.mask), carry)  # noqa: SLF001
+            out = self.model._elbo_step(self.batch, self.uniforms, StepMask.from_mask(self.mask), carry, self.schedule)  # noqa: SLF001
         elif self.forecast is not None:  # (a ragged batch's host rule was checked by step(); context AND lengths AND dropout in one launch)
             ragged = (self.valid_global, self.dp.world, self.dp.rank) if self.ragged else None
             sm = self.model._forecast_step_mask(self.batch, self.uniforms, self.forecast, self.dropout, ragged=ragged)  # noqa: SLF001
-            out = self.model._elbo_step(self.batch, self.uniforms, sm)  # noqa: SLF001
+            out = self.model._elbo_step(self.batch, self.uniforms, sm, schedule=self.schedule)  # noqa: SLF001
         elif self.ragged:  # (the host rule was checked by step(); lengths AND dropout in one launch, inside the capture)
             sm = self.model._ragged_step_mask(self.batch, self.uniforms, self.dropout, self.valid_global, self.dp.world, self.dp.rank)  # noqa: SLF001
-            out = self.model._elbo_step(self.batch, self.uniforms, sm, carry)  # noqa: SLF001
+            out = self.model._elbo_step(self.batch, self.uniforms, sm, carry, self.schedule)  # noqa: SLF001
         elif carry is not None:
             sm = self.model._step_mask(self.batch, self.uniforms, None, self.dropout)  # noqa: SLF001
-            out = self.model._elbo_step(self.batch, self.uniforms, sm, carry)  # noqa: SLF001
+            out = self.model._elbo_step(self.batch, self.uniforms, sm, carry, self.schedule)  # noqa: SLF001
         else:
-            out = self.model.shared_step(self.batch, self.uniforms, modality_dropout=self.dropout)
+            out = self.model.shared_step(self.batch, self.uniforms, modality_dropout=self.dropout, elbo_schedule=self.schedule)
         out["loss"].backward()
         keys = list(out)
         if self.fused_optimizer:
@@ -251,8 +264,11 @@ class CapturedTrainStep:
             self.opt.steps -= 1  # FlatAdamW.step counted the recorded (not executed) step on the host
 
     def close(self) -> None:
-        """Drop the graph and the pin it holds on the conv layer's packed-weight plan."""
+        """Drop the graph and the pin it holds on the conv layer's packed-weight plan; the schedule's ``stats`` (tensors of the graph's
+        memory) are emptied."""
         self.graph = None
+        if getattr(self, "schedule", None) is not None:
+            self.schedule.stats = {}
         if getattr(self, "_pinned", False):
             self._pinned = False
             conv.unpin_scratch()
