@@ -780,6 +780,30 @@ int mtrssm_step_mask_forecast(const int32_t* valid, const float* u_mask, const f
                               int32_t* codes, float* seen_audio, float* seen_vision, float* target, float* observed, uint8_t* mask0,
                               int32_t* last, float* counts, void* stream);
 
+/* Forecast skill: S sampled reconstructions of every frame scored as an ensemble, in one pass.
+ *   pred [B][S][T][E] is the decoders' RAW output (`act`: MTRSSM_ACT_IDENTITY or MTRSSM_ACT_TANH, applied while it is read; nothing
+ *   activated is written), target [B][T][E], valid [B] int32 in DEVICE memory (NULL: every frame is live; (b, t) is live iff
+ *   t < valid[b]).  With y_s = act(pred[b][s][t]) and x = target[b][t], per frame and into the planes [B][T]:
+ *     se_s = sum_e 0.5 (x_e - y_s,e)^2;  mean = (se_0 + ... + se_{S-1}) / S;  best = min_s se_s;
+ *     ybar_e = (y_0,e + ... + y_{S-1},e) / S;  ens = sum_e 0.5 (x_e - ybar_e)^2;  spread = sum_e 0.5 (sum_s (y_s,e - ybar_e)^2) / S
+ *   (the sums over s are left folds; the data term only, without 0.5 E log 2 pi; mean = ens + spread in exact arithmetic; best is
+ *   per frame, not per trajectory).  se_samples [B][S][T] (may be NULL) receives se_s, so best == min_s se_samples bitwise.  A
+ *   dead frame loads nothing and scores 0 in every plane.
+ * One workgroup per frame: the target is read once and every prediction once ((S + 1) * E * 4 bytes), a lane's S quads stay in
+ * registers; the reductions run in a fixed order without float atomics, so a frame's result depends on nothing but that frame and
+ * two calls agree bitwise.  Null required pointers, B, T, E <= 0, S outside 1 .. 16, E % 4 != 0, an `act` other than the two,
+ * pred / target not 16-byte aligned, B * T >= 2^31 or B * S * T * E >= 2^60 return -1 without a launch. */
+int mtrssm_ensemble_score(const float* pred, const float* target, const int32_t* valid, int64_t B, int64_t S, int64_t T, int64_t E,
+                          int32_t act, float* mean, float* ens, float* best, float* spread, float* se_samples, void* stream);
+/* The score planes folded by horizon: planes [P][B][T], context [B] int32 (clamped into [1, T]: c_b frames of row b are observed),
+ * valid [B] int32 (may be NULL; clamped into [0, T]).  A live frame has horizon h = 0 when t < c_b, else t - c_b + 1;
+ *   sums[p][h] += planes[p][b][t],  counts[h] += 1   (sums [P][T], counts [T], both IN/OUT: batches add up in one buffer).
+ * For every bin the live frames are added in ascending b (bin 0: ascending t inside a row) onto the value already there -- a left
+ * fold by one thread per (p, h), which an fp32 loop on the host reproduces bit for bit.  Counts are whole numbers in fp32.
+ * Null pointers (valid excepted), P outside 1 .. 64, B or T <= 0 or B * T >= 2^24 return -1 without a launch. */
+int mtrssm_horizon_table(const float* planes, int64_t P, const int32_t* context, const int32_t* valid, int64_t B, int64_t T,
+                         float* sums, float* counts, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Fused AdamW over one flat fp32 parameter buffer, with global-norm gradient clipping
  * (yaml: torch.optim.AdamW lr 1e-3; trainer.gradient_clip_val 10 -- default.yaml:103-107,119).

@@ -27,13 +27,14 @@ from multimodal_mtrssm_amd.objective import likelihood
 from multimodal_mtrssm_amd.optim import FlatAdamW, ReduceLROnPlateau, load_reference_checkpoint
 from multimodal_mtrssm_amd.parallel import FlatDataParallel, GlobalRowNoise
 from multimodal_mtrssm_amd.schedule import ElboSchedule
+from multimodal_mtrssm_amd.skill import ForecastSkill, SkillTable
 from multimodal_mtrssm_amd.state import MTState, State, cat_mtstates, cat_states, stack_mtstates, stack_states
 
 __version__ = "0.1.0"
 
 __all__ = [
-    "MLP", "MTRNN", "Decoder", "DeviceEpisodeLoader", "Distribution", "Encoder", "EpisodeBatch", "EpisodeDataModule", "ElboSchedule", "EpisodeDataModuleConfig", "FlatAdamW", "FlatDataParallel", "Forecast", "GlobalRowNoise", "MTState", "MoPoE_MMTRSSM",
-    "MoPoE_MRSSM", "ModalityDropout", "MultiOneHot", "MultiOneHotFactory", "ReduceLROnPlateau", "Representation", "State", "StateCarry", "Transition", "cat_distribution",
+    "MLP", "MTRNN", "Decoder", "DeviceEpisodeLoader", "Distribution", "Encoder", "EpisodeBatch", "EpisodeDataModule", "ElboSchedule", "EpisodeDataModuleConfig", "FlatAdamW", "FlatDataParallel", "Forecast", "ForecastSkill", "GlobalRowNoise", "MTState", "MoPoE_MMTRSSM",
+    "MoPoE_MRSSM", "ModalityDropout", "MultiOneHot", "MultiOneHotFactory", "ReduceLROnPlateau", "Representation", "SkillTable", "State", "StateCarry", "Transition", "cat_distribution",
     "cat_mtstates", "cat_states", "inject_uniforms", "kl_divergence", "likelihood", "load_reference_checkpoint", "make_mmtrssm", "make_mrssm",
     "stack_distribution", "stack_mtstates", "stack_states",
 ]

@@ -149,6 +149,8 @@ SYMBOLS: dict[str, tuple[type | None, list[type]]] = {
     "mtrssm_step_mask_ragged": (C.c_int, [_p, _p, C.c_int64, C.c_int64, C.c_int64, _f, _f, C.c_int64, C.c_int64, _p, _p, _p, _p, _p, _p, _p, _p]),
     "mtrssm_step_mask_forecast": (C.c_int, [_p, _p, _p, C.c_int64, C.c_int64, C.c_int64, _f, _f, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _p, _p, _p,
                                             _p, _p, _p, _p, _p, _p]),
+    "mtrssm_ensemble_score": (C.c_int, [_p, _p, _p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _i, _p, _p, _p, _p, _p, _p]),
+    "mtrssm_horizon_table": (C.c_int, [_p, C.c_int64, _p, _p, C.c_int64, C.c_int64, _p, _p, _p]),
     "mtrssm_elbo_combine_counted_fwd": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int64, C.c_float, C.c_float, _p, _p, _p, _p, _p]),
     "mtrssm_elbo_combine_counted_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int64, C.c_float, C.c_float, _p, _p, _p, _p, _p]),
     "mtrssm_elbo_schedule_fwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, C.c_int64, ElboSchedule, _p, _p, _p, _p, _p, _p, _p]),

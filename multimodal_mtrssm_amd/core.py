@@ -27,6 +27,7 @@ from multimodal_mtrssm_amd.forecast import Forecast
 from multimodal_mtrssm_amd.networks import MTRNN, Representation, Transition
 from multimodal_mtrssm_amd.objective import likelihood
 from multimodal_mtrssm_amd.schedule import ElboSchedule, ElboTerms
+from multimodal_mtrssm_amd.skill import ForecastSkill, SkillTable
 from multimodal_mtrssm_amd.state import MTState, State
 
 try:  # the real trainer, when it is installed next to the reference
@@ -413,6 +414,8 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         self.forecast: Forecast | None = None  # training_step trains the forecast objective with it
         self.val_forecast: Forecast | None = None  # validation_step adds a forecast step at this (fixed) context and logs val/forecast/*
         self.elbo_schedule: ElboSchedule | None = None  # training_step (never validation_step) weighs the loss terms with it
+        self.val_skill: ForecastSkill | None = None  # validation_step adds a skill step into self.skill_table
+        self.skill_table: SkillTable | None = None  # ... logged as val/skill/* and cleared by on_validation_epoch_end
 
     # -- batch accessors (mrssm core.py:310-355) --------------------------------------------
     @staticmethod
@@ -631,6 +634,100 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         audio_embed, vision_embed = self.audio_encoder(observations[0]), self.vision_encoder(observations[1])
         out = self._rollout_embedded(actions, audio_embed, vision_embed, prev_state, noise, sample_prior=False, modality=sm.codes)
         return self._posterior_from_rollout(out)
+
+    def _initial_for_step(self, obs_embed: Tensor, noise: Noise | None) -> State | MTState:
+        """``_initial_from_embed`` with the step's noise dict (the two models take their initial uniforms differently)."""
+        return self._initial_from_embed(obs_embed, None if noise is None else noise.get("u_init"))
+
+    @staticmethod
+    def _feature_of(out: dict[str, Tensor]) -> Tensor:
+        """What the decoders read of a posterior rollout."""
+        return torch.cat([out["deter"], out["post_stoch"]], dim=-1)
+
+    _POST_KEYS = ("u_post",)  # the rollout's posterior uniforms; a skill step composes each with its "u_tail" twin
+
+    @torch.no_grad()
+    def forecast_skill(self, batch: tuple[Tensor, ...], skill: ForecastSkill, noise: Noise | None = None, lengths: Tensor | None = None,  # noqa: PLR0913, PLR0914
+                       table: SkillTable | None = None, *, keep_states: bool = False) -> SkillTable:
+        """One skill step: observe ``skill.context`` frames (of ``skill.observe``), roll ``skill.samples`` sampled
+        futures per row open loop in ONE masked posterior rollout over ``B * S`` rows (row ``b * S + s``; the copies of a row share
+        ``noise["u_post"]`` on the context and read ``noise["u_tail"][b, s]`` after it), decode, and score every live frame of both
+        modalities as an ensemble (``mtrssm_ensemble_score``); the planes are folded by horizon into ``table`` (a new one when None),
+        which is returned.  ``best`` is the best sample per FRAME.  ``lengths`` (or a batch that carries ``valid_global``) as in
+        ``forecast_rollout``: nothing is observed or scored at or past a row's end.  ``keep_states``: ``table.states`` is the posterior
+        state sequence ``[B * S, T, .]`` and ``table.planes`` the step's score planes ``[8, B, T]``.  Every row starts from its own
+        frame 0: no masked (7-tuple) batch, no ``state_carry``."""
+        if not isinstance(skill, ForecastSkill):
+            msg = f"skill must be a ForecastSkill, got {type(skill).__name__}"
+            raise ValueError(msg)
+        if self.get_modality_mask_from_batch(batch) is not None:
+            msg = "a skill step decides what the model observes: a masked (7-tuple) batch already says what is seen"
+            raise ValueError(msg)
+        if self.state_carry is not None:
+            msg = "a skill step starts every row from its own frame 0: it does not combine with a set state_carry"
+            raise ValueError(msg)
+        actions = batch[0]
+        audio_obs, vision_obs = self.get_observations_from_batch(batch)
+        targets = self.get_targets_from_batch(batch)
+        B, T = actions.shape[:2]
+        S, dev = skill.samples, actions.device
+        if table is not None and (not isinstance(table, SkillTable) or table.steps != T or table.buffer.device != dev):
+            msg = f"table must be a SkillTable of {T} steps on {dev}"
+            raise ValueError(msg)
+        valid = None
+        ragged = self._lengths_of(batch, lengths, None, None)
+        if ragged is not None:
+            valid_global, world, rank = ragged
+            _check_lengths(valid_global, B * world, dev)
+            valid = valid_global[rank * B : (rank + 1) * B].contiguous()
+        noise = dict(noise or {})
+        conv.begin_step(dev)
+        audio_embed, vision_embed = self._encode_both(audio_obs, vision_obs)
+        sm = Forecast(skill.context).sample(torch.zeros(B, device=dev), T, valid)  # (a fixed context: the uniforms do not matter)
+        bits = skill.bits
+        codes = sm.codes & bits
+        mask0 = sm.mask0 & skill.observed(dev)
+        state0 = self._initial_for_step(_masked_mean_embed(audio_embed[:, 0], vision_embed[:, 0], mask0), noise)
+        wide = lambda x: x.repeat_interleave(S, dim=0)  # noqa: E731  (row (b, s) -> b * S + s)
+        state0 = self._state_like(state0, {k: wide(getattr(state0, k)) for k in self._FRESH_KEYS})
+        for key in self._POST_KEYS:
+            tail_key = key.replace("post", "tail")
+            u_post, u_tail = noise.get(key), noise.get(tail_key)
+            k = self._category_size_of(key)
+            u_post = _rand(actions, B, T, k) if u_post is None else u_post
+            u_tail = _rand(actions, B, S, T, k) if u_tail is None else u_tail
+            noise[key] = skill.compose_noise(u_post, u_tail)
+        out = self._rollout_embedded(wide(actions), wide(audio_embed), wide(vision_embed), state0, noise, sample_prior=False, modality=wide(codes))
+        feature = self._feature_of(out)
+        da, dv = self.audio_decoder, self.vision_decoder
+        fused = isinstance(da, cnn.Decoder) and isinstance(dv, cnn.Decoder) and da.out_act_id is not None and dv.out_act_id is not None
+        acts = (da.out_act_id, dv.out_act_id) if fused else (0, 0)
+        planes = torch.empty(SkillTable.ROWS, B, T, device=dev, dtype=torch.float32)
+        rows = max(1, int(skill.max_frames) // (S * T))
+        for r0 in range(0, B, rows):
+            r1 = min(B, r0 + rows)
+            f = feature[r0 * S : r1 * S]
+            if fused and _pairable(da, dv, cnn.Decoder):
+                preds = cnn.decode_pair(da, dv, f, f, raw=True)
+            elif fused:
+                preds = da(f, raw=True), dv(f, raw=True)
+            else:
+                preds = da(f), dv(f)
+            part = torch.empty(SkillTable.ROWS, r1 - r0, T, device=dev, dtype=torch.float32)
+            for j, (pred, key) in enumerate(zip(preds, ("recon/audio", "recon/vision"), strict=True)):
+                ForecastSkill.score(pred.reshape(r1 - r0, S, T, -1), targets[key][r0:r1].reshape(r1 - r0, T, -1),
+                                    None if valid is None else valid[r0:r1], acts[j], out=part[4 * j : 4 * j + 4])
+            planes[:, r0:r1] = part
+        if table is None:
+            table = SkillTable(T, dev)
+        context = torch.full((B,), min(skill.context, (1 << 31) - 1), dtype=torch.int32, device=dev)
+        ForecastSkill.table_add(planes, context, valid, table.sums, table.counts)
+        table.planes = planes if keep_states else None
+        table.states = self._posterior_from_rollout(out) if keep_states else None
+        return table
+
+    def _category_size_of(self, key: str) -> int:  # noqa: ARG002
+        return self.transition.distribution_factory.category_size
 
     # -- train / val ----------------------------------------------------------------------------
     def _dropout_uniforms(self, batch: tuple[Tensor, ...], noise: Noise | None, modality_dropout: ModalityDropout, world: int) -> Tensor:
@@ -899,6 +996,19 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
             fore = {f"val/forecast/{k}": v for k, v in self.shared_step(batch, forecast=self.val_forecast).items()}
             self.log_dict(fore, prog_bar=False, sync_dist=True, on_step=False, on_epoch=True)
             logged.update(fore)
+        if self.val_skill is not None:  # (after everything above: the draws of val/* are what they are without it)
+            self.skill_table = self.forecast_skill(batch, self.val_skill, table=self.skill_table)
+        return logged
+
+    def on_validation_epoch_end(self) -> dict[str, Tensor]:
+        """Logs the epoch's ``val/skill/{audio,vision}/{mean,ens,best,spread}/{obs,h1,h2,h4,h8}`` (all-reduced once when a process group is
+        initialised; the group is the one ``FlatDataParallel.skill`` bound) and clears the table.  Without a table: nothing."""
+        table, self.skill_table = self.skill_table, None
+        if table is None:
+            return {}
+        table.all_reduce(getattr(self.val_skill, "group", None))
+        logged = table.scalars("val/skill")
+        self.log_dict(logged, prog_bar=False, sync_dist=False, on_step=False, on_epoch=True)
         return logged
 
 
@@ -1051,6 +1161,18 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
             distribution_l=self.l_dist(out["prior_logits_l"]), hidden_h=out["hidden_h"], hidden_l=out["hidden_l"],
             stoch_h=out["prior_stoch_h"], stoch_l=out["prior_stoch_l"],
         )
+
+    def _initial_for_step(self, obs_embed: Tensor, noise: Noise | None) -> MTState:  # type: ignore[override]
+        return self._initial_from_embed(obs_embed, noise)
+
+    @staticmethod
+    def _feature_of(out: dict[str, Tensor]) -> Tensor:
+        return torch.cat([out["deter_h"], out["post_stoch_h"], out["deter_l"], out["post_stoch_l"]], dim=-1)
+
+    _POST_KEYS = ("u_post_l", "u_post_h")
+
+    def _category_size_of(self, key: str) -> int:
+        return (self.l_dist if key.endswith("_l") else self.h_dist).category_size
 
     _FRESH_KEYS = ("deter_l", "deter_h", "stoch_l", "stoch_h", "hidden_l", "hidden_h")
     _LAST_KEYS = {"deter_l": "deter_l", "deter_h": "deter_h", "stoch_l": "post_stoch_l", "stoch_h": "post_stoch_h", "hidden_l": "hidden_l",  # noqa: RUF012

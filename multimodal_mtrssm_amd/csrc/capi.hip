@@ -78,6 +78,9 @@ int nll_fwd_launch(const float*, const float*, int64_t, int64_t, int, float*, hi
 int nll_bwd_launch(const float*, const float*, const float*, int64_t, int64_t, int, float*, hipStream_t);
 int nll_masked_fwd_launch(const float*, const float*, const float*, const float*, int64_t, int64_t, int, float*, hipStream_t);
 int nll_masked_bwd_launch(const float*, const float*, const float*, const float*, const float*, int64_t, int64_t, int, float*, hipStream_t);
+int ensemble_score_launch(const float*, const float*, const int32_t*, int64_t, int64_t, int64_t, int64_t, int, float*, float*, float*, float*, float*,
+                          hipStream_t);
+int horizon_table_launch(const float*, int64_t, const int32_t*, const int32_t*, int64_t, int64_t, float*, float*, hipStream_t);
 int modality_dropout_launch(const float*, int64_t, int64_t, int64_t, float, float, int64_t, int64_t, int32_t*, float*, float*, unsigned char*, float*,
                             hipStream_t);
 int sumsq_launch(const float*, int64_t, float*, hipStream_t);
@@ -402,4 +405,13 @@ MTRSSM_API int mtrssm_convt_k4s2_band(int32_t N, int32_t C, int32_t Hs, int32_t 
 MTRSSM_API int mtrssm_convt_k4s2_thin(int32_t N, int32_t C, int32_t Hs, int32_t Ws, int32_t Cout, const float* src, const float* w,
                                       const float* bias, int32_t pre_act, int32_t act, float* out, void* stream) {
   return convt_k4s2_thin_launch(N, C, Hs, Ws, Cout, src, w, bias, pre_act, act, out, static_cast<hipStream_t>(stream));
+}
+
+MTRSSM_API int mtrssm_ensemble_score(const float* pred, const float* target, const int32_t* valid, int64_t B, int64_t S, int64_t T, int64_t E,
+                                     int32_t act, float* mean, float* ens, float* best, float* spread, float* se_samples, void* stream) {
+  return ensemble_score_launch(pred, target, valid, B, S, T, E, act, mean, ens, best, spread, se_samples, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_horizon_table(const float* planes, int64_t P, const int32_t* context, const int32_t* valid, int64_t B, int64_t T,
+                                    float* sums, float* counts, void* stream) {
+  return horizon_table_launch(planes, P, context, valid, B, T, sums, counts, static_cast<hipStream_t>(stream));
 }

@@ -35,6 +35,11 @@ __device__ __forceinline__ float act_grad_from_out(float h, int act) {
   }
 }
 
+// tanh on the hardware exponential: 1 - 2 / (exp(2x) + 1), absolute error ~1e-7 (as the GEMM / conv epilogues), saturates
+// cleanly; libm's tanhf makes a streaming kernel VALU-bound.  Shared by the NLL kernels (train_ops.hip) and the ensemble scorer
+// (skill_ops.hip), whose values are compared with each other.
+__device__ __forceinline__ float tanh_fast(float x) { return 1.f - 2.f / (__expf(2.f * x) + 1.f); }
+
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
 // Workgroup barrier for kernels whose waves talk to each other through LDS only.  __syncthreads() is a workgroup-scope

@@ -24,10 +24,7 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
   return t;  // valid in wave 0
 }
 
-// tanh on the hardware exponential: 1 - 2 / (exp(2x) + 1), absolute error ~1e-7 (as the GEMM / conv epilogues), saturates
-// cleanly.  libm's tanhf made the two NLL kernels VALU-bound (41 / 25 us for a 105 MB stream).
-__device__ __forceinline__ float tanh_fast(float x) { return 1.f - 2.f / (__expf(2.f * x) + 1.f); }
-
+// tanh_fast (scan_common.h): libm's tanhf made the two NLL kernels VALU-bound (41 / 25 us for a 105 MB stream).
 // out += scale * sum 0.5 (t - p)^2   (+ the constant on block 0)
 template <bool TANH>
 __global__ void nll_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ target, int64_t n,

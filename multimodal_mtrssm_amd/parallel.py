@@ -20,6 +20,7 @@ from multimodal_mtrssm_amd import conv, linear
 from multimodal_mtrssm_amd.dropout import ModalityDropout
 from multimodal_mtrssm_amd.forecast import Forecast
 from multimodal_mtrssm_amd.optim import FlatParameters
+from multimodal_mtrssm_amd.skill import ForecastSkill
 
 
 class GlobalRowNoise:
@@ -92,6 +93,11 @@ class FlatDataParallel:
         """``forecast`` bound to this rank's rows of the global batch: pass the result as ``shared_step``'s ``forecast`` (or set it as
         ``model.forecast``) and draw ``u_context`` with ``noise_source``."""
         return forecast.for_rank(self.world, self.rank)
+
+    def skill(self, skill: ForecastSkill) -> ForecastSkill:
+        """``skill`` bound to this object's process group: set the result as ``model.val_skill`` and ``on_validation_epoch_end``
+        all-reduces the skill table over that group (its uniforms' batch dimension comes first: draw them with ``noise_source``)."""
+        return skill.for_group(self.group)
 
     @property
     def grad_scale(self) -> float:
