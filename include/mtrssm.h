@@ -531,6 +531,28 @@ int mtrssm_conv_weight_grad_src_bias_supported(const MtrssmConvGeom* g, int32_t 
 int mtrssm_residual_bwd1x1_supported(const MtrssmConvGeom* g);
 int mtrssm_residual_bwd1x1(const MtrssmConvGeom* g, const float* gy, const float* h, const uint16_t* wq1t, float* gh, float* dwp,
                            float* dbias, void* workspace, int64_t workspace_bytes, int32_t defer, void* stream);
+/* mtrssm_residual_bwd1x1 for TWO blocks with the same mid width C (the audio and the vision stack's block; frame counts and
+ * plane shapes may differ) in ONE grid of one workgroup per CU, half of them for each problem.  Every argument as in the single
+ * call, once per problem; each problem has its own workspace (mtrssm_conv_weight_grad_workspace_bytes of ITS geometry is enough:
+ * a paired call leaves at most as many partial sets per problem as the single call) and its own reduce (defer != 0: two
+ * recorded sums).  gh is bit-identical to the single call's; dwp / dbias are sums over half as many partial sets, so they
+ * agree within rounding.  A problem whose workspace is NULL / too small adds by fp32 atomics.  _supported: 1 / 0, a host-side
+ * query (0 for every shape with MTRSSM_PAIR_WGRAD=0 in the environment); the call on an unsupported pair returns MTRSSM_EINVAL. */
+int mtrssm_residual_bwd1x1_pair_supported(const MtrssmConvGeom* ga, const MtrssmConvGeom* gb);
+int mtrssm_residual_bwd1x1_pair(const MtrssmConvGeom* ga, const float* gya, const float* ha, const uint16_t* wq1ta, float* gha, float* dwpa,
+                                float* dbiasa, void* workspace_a, int64_t workspace_a_bytes, const MtrssmConvGeom* gb, const float* gyb,
+                                const float* hb, const uint16_t* wq1tb, float* ghb, float* dwpb, float* dbiasb, void* workspace_b,
+                                int64_t workspace_b_bytes, int32_t defer, void* stream);
+/* mtrssm_conv_weight_grad (pre_act_a = 0, no src2) for TWO 3x3 / stride-1 layers of the residual stacks in ONE grid: the same
+ * layer (C = 64 or 32, Cout, activation, mfma_split = 2) on a 4-wide and on an 8-wide 64-pixel plane, in either order; the
+ * frame counts may differ.  One wave per SIMD over the chip in total, half of the x blocks for each problem, so a workgroup's
+ * run of frames is twice as long as in two launches and each problem leaves half as many partial sets.  Workspaces, reduce
+ * jobs, defer and the atomics form: per problem, as in mtrssm_residual_bwd1x1_pair.  _supported: 1 / 0, a host-side query (0
+ * with MTRSSM_PAIR_WGRAD=0); the call on an unsupported pair returns MTRSSM_EINVAL. */
+int mtrssm_conv_weight_grad_pair_supported(const MtrssmConvGeom* ga, const MtrssmConvGeom* gb);
+int mtrssm_conv_weight_grad_pair(const MtrssmConvGeom* ga, const float* aa, const float* srca, float* dwpa, float* dbiasa, void* workspace_a,
+                                 int64_t workspace_a_bytes, const MtrssmConvGeom* gb, const float* ab, const float* srcb, float* dwpb,
+                                 float* dbiasb, void* workspace_b, int64_t workspace_b_bytes, int32_t defer, void* stream);
 int mtrssm_conv_weight_grad_src_bias(const MtrssmConvGeom* g, const float* a, const float* src, int32_t pre_act_a, float* dwp,
                                      float* dsrc_bias, void* workspace, int64_t workspace_bytes, int32_t defer, void* stream);
 /* Bytes of workspace the kernel chosen for this geometry wants for its partial tile sets (0: none; -1: invalid geometry; up to

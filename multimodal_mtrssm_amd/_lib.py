@@ -130,6 +130,12 @@ SYMBOLS: dict[str, tuple[type | None, list[type]]] = {
     "mtrssm_conv_weight_grad_src_bias": (C.c_int, [C.POINTER(ConvGeom), _p, _p, _i, _p, _p, _p, C.c_int64, _i, _p]),
     "mtrssm_conv_weight_grad_reduce": (C.c_int, [_p]),
     "mtrssm_conv_weight_grad_workspace_bytes": (C.c_int64, [C.POINTER(ConvGeom), _i]),
+    "mtrssm_residual_bwd1x1_pair_supported": (C.c_int, [C.POINTER(ConvGeom), C.POINTER(ConvGeom)]),
+    "mtrssm_residual_bwd1x1_pair": (C.c_int, [C.POINTER(ConvGeom), _p, _p, _p, _p, _p, _p, _p, C.c_int64,
+                                              C.POINTER(ConvGeom), _p, _p, _p, _p, _p, _p, _p, C.c_int64, _i, _p]),
+    "mtrssm_conv_weight_grad_pair_supported": (C.c_int, [C.POINTER(ConvGeom), C.POINTER(ConvGeom)]),
+    "mtrssm_conv_weight_grad_pair": (C.c_int, [C.POINTER(ConvGeom), _p, _p, _p, _p, _p, C.c_int64,
+                                               C.POINTER(ConvGeom), _p, _p, _p, _p, _p, C.c_int64, _i, _p]),
     "mtrssm_channel_sum": (C.c_int, [_p, _i, _i, _i, _p, _p]),
     "mtrssm_convt_k4s2_thin": (C.c_int, [_i, _i, _i, _i, _i, _p, _p, _p, _i, _i, _p, _p]),
     "mtrssm_convt_k4s2_band_supported": (C.c_int, [_i, _i, _i, _i, _i]),

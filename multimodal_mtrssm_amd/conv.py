@@ -554,7 +554,9 @@ def _reduce_deferred() -> None:
                        "mtrssm_conv_weight_grad_reduce")
 
 
-def _wgrad_workspace(geom: C.Structure, pre_act_a: int, device: torch.device, *, own: bool = False) -> Tensor | None:
+def _wgrad_workspace(geom: C.Structure, pre_act_a: int, device: torch.device, *, own: bool = False, second: bool = False) -> Tensor | None:
+    """``second``: the other problem of a paired launch -- the two write their sets at the same time, so it must not share the
+    stream's buffer (a buffer of its own per (device, stream); deferred launches have their own slots anyway)."""
     gkey = (tuple(getattr(geom, n) for n, _ in geom._fields_), pre_act_a)
     need = _WGRAD_NEED.get(gkey)
     if need is None:
@@ -572,6 +574,8 @@ def _wgrad_workspace(geom: C.Structure, pre_act_a: int, device: torch.device, *,
             _WGRAD_WS_RETIRED.append(slots[k])
             slots[k] = torch.empty((need + 3) // 4 + 64, device=device, dtype=torch.float32)
         return slots[k]
+    if second:
+        key = (*key, "second")
     ws = _WGRAD_WS.get(key)
     if ws is None or ws.numel() * 4 < need:
         if ws is not None:
@@ -632,6 +636,64 @@ def _weight_grad(a: Tensor, src: Tensor, coords: Tensor | None, kh: int, kw: int
     return g_w, (None if bias_sunk is not None else dbias)
 
 
+def _weight_grad_single(s: tuple[Tensor, Tensor, Tensor, Tensor | None], pad: int, act: int) -> tuple[Tensor | None, Tensor | None]:
+    """One problem of ``_weight_grad_pair`` as a launch of its own."""
+    a, src, w, b = s
+    return _weight_grad(a, src, None, w.shape[2], w.shape[3], 1, pad, False, True, act, want_bias=b is not None, weight=w, bias=b)
+
+
+RESBLOCK_WGRAD_PAIR = True  # the residual stacks' 3x3 weight gradients of both modalities as ONE launch (mtrssm_conv_weight_grad_pair)
+
+
+def _weight_grad_pair(sa: tuple[Tensor, Tensor, Tensor, Tensor | None], sv: tuple[Tensor, Tensor, Tensor, Tensor | None], pad: int, act: int,
+                      ) -> tuple[tuple[Tensor | None, Tensor | None], tuple[Tensor | None, Tensor | None]]:
+    """``_weight_grad(a, src, None, kh, kw, 1, pad, False, True, act, want_bias=True, weight=w, bias=b)`` for two layers
+    ``s* = (a, src, w, b)`` -- the audio and the vision stack's -- as ONE persistent grid where the library pairs them
+    (``mtrssm_conv_weight_grad_pair``: the 3x3 layers on a 4-wide and an 8-wide 64-pixel plane); two launches otherwise."""
+    def single(s: tuple) -> tuple[Tensor | None, Tensor | None]:
+        return _weight_grad_single(s, pad, act)
+
+    lib = _lib.load()
+    geoms = []
+    if PAIR_LAUNCH and RESBLOCK_WGRAD_PAIR and _MFMA_SPLIT == 2 and sa[2].shape == sv[2].shape and sa[0].is_cuda:  # noqa: PLR2004
+        for a, src, w, _ in (sa, sv):
+            n, o, hq, wq = a.shape
+            c = src.shape[1]
+            opad, ipad = _pads(o, c)
+            if src.shape != (n, c, hq, wq) or w.shape[:2] != (o, c) or a.data_ptr() % 16 or src.data_ptr() % 16:
+                break
+            geoms.append(_geom(N=n, C=c, Hs=hq, Ws=wq, C2=0, Cpad=ipad, KH=w.shape[2], KW=w.shape[3], SS=1, TS=1, OFFY=-pad, OFFX=-pad, Hq=hq,
+                               Wq=wq, OS=1, QY=0, QX=0, Ho=hq, Wo=wq, Cout=o, CoutPad=opad, pre_act=1, act=act))
+    if len(geoms) != 2 or not lib.mtrssm_conv_weight_grad_pair_supported(C.byref(geoms[0]), C.byref(geoms[1])):  # noqa: PLR2004
+        return single(sa), single(sv)
+    sides = []
+    for geom, (a, src, w, b) in zip(geoms, (sa, sv), strict=True):
+        taps = geom.KH * geom.KW
+        sunk = _GRAD_SINK.target(w, geom.Cout, geom.C, taps, geom.CoutPad, geom.Cpad)
+        dwp = sunk if sunk is not None else _zeros(geom.CoutPad * taps * geom.Cpad, a.device).view(geom.CoutPad, taps, geom.Cpad)
+        bias_sunk = dbias = None
+        if b is not None:
+            bias_sunk = grad_target(b) if b.is_contiguous() else None
+            dbias = bias_sunk if bias_sunk is not None else _zeros(geom.Cout, a.device)
+        sides.append((geom, a, src, sunk, dwp, bias_sunk, dbias))
+    # deferred sums only when every result of the call goes to the flat buffer (as _weight_grad decides for one layer)
+    defer = DEFER_WGRAD_REDUCE and all(s[3] is not None and (s[6] is None or s[5] is not None) for s in sides)
+    wss = [_wgrad_workspace(s[0], 0, s[1].device, own=defer, second=k == 1) for k, s in enumerate(sides)]
+    args: list = []
+    flops = nbytes = 0.0
+    for (geom, a, src, _, dwp, _, dbias), ws in zip(sides, wss, strict=True):
+        args += [C.byref(geom), _lib.ptr(a), _lib.ptr(src), _lib.ptr(dwp), _lib.ptr(dbias), _lib.raw_ptr(ws), 0 if ws is None else ws.numel() * 4]
+        flops += 2.0 * a.numel() * geom.KH * geom.KW * geom.C
+        nbytes += 4.0 * (a.numel() + src.numel())
+    _lib.check(_lib.TIMERS.call("mtrssm_conv_weight_grad_pair", lib.mtrssm_conv_weight_grad_pair, *args, int(defer and all(w is not None for w in wss)),
+                                _lib.stream_ptr(sa[0].device), flops=flops, nbytes=nbytes), "mtrssm_conv_weight_grad_pair")
+    out = []
+    for geom, _, _, sunk, dwp, bias_sunk, dbias in sides:
+        g_w = None if sunk is not None else dwp[: geom.Cout, :, : geom.C].reshape(geom.Cout, geom.KH, geom.KW, geom.C).permute(0, 3, 1, 2)
+        out.append((g_w, None if bias_sunk is not None else dbias))
+    return out[0], out[1]
+
+
 def _channel_sum(x: Tensor, bias: Tensor | None = None) -> Tensor | None:
     """``sum_{n,y,x} x[n, c, y, x]``; straight into ``bias``'s flat gradient view when it has one (None is returned then)."""
     lib = _lib.load()
@@ -670,8 +732,12 @@ class _Conv2d(torch.autograd.Function):
         g_w = g_b = None
         want_b = has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1]:
-            g_w, g_b = _weight_grad(g_out, x, coords, kh, kw, stride, pad, False, pre_act, act, want_bias=want_b, weight=weight,
-                                    bias=ctx.bias)
+            hold = getattr(ctx, "wgrad_hold", None)  # a paired node (_pair_function) collects the 3x3 layers' jobs of both branches
+            if hold is not None and coords is None and stride == 1 and pre_act and want_b and (kh, kw) == (3, 3):
+                hold.append(((g_out, x, weight, ctx.bias), pad, act))
+            else:
+                g_w, g_b = _weight_grad(g_out, x, coords, kh, kw, stride, pad, False, pre_act, act, want_bias=want_b, weight=weight,
+                                        bias=ctx.bias)
         elif want_b:
             g_b = _channel_sum(g_out, ctx.bias)
         return g_x, g_w, g_b, None, None, None, None, None
@@ -794,6 +860,43 @@ def _bwd1x1_fused(geom: C.Structure, g_y: Tensor, h: Tensor, w1: Tensor, b1: Ten
     return g_h, g_w, (None if bias_sunk is not None else dbias)
 
 
+RESBLOCK_BWD1X1_PAIR = True  # ... of both modalities as ONE launch (mtrssm_residual_bwd1x1_pair)
+
+
+def _bwd1x1_pairs(ga: C.Structure, sa: tuple[Tensor, Tensor, Tensor, Tensor], gv: C.Structure, sv: tuple[Tensor, Tensor, Tensor, Tensor]) -> bool:
+    """Whether ``_bwd1x1_fused_pair`` takes the two blocks ``s* = (g_y, h, w1, b1)``: the library pairs the shapes, and every
+    gradient of the call has a home in the flat gradient buffer with the partial-set sums deferred -- the train step.  A call
+    whose gradients go back to autograd as tensors sums its sets on the spot and keeps one launch per block."""
+    if not (PAIR_LAUNCH and RESBLOCK_BWD1X1_PAIR and DEFER_WGRAD_REDUCE):
+        return False
+    for _, _, w1, b1 in (sa, sv):
+        if not (w1.is_contiguous() and b1.is_contiguous()) or grad_target_owner(w1) is None or grad_target(b1) is None:
+            return False
+    return bool(_lib.load().mtrssm_residual_bwd1x1_pair_supported(C.byref(ga), C.byref(gv)))
+
+
+def _bwd1x1_fused_pair(ga: C.Structure, sa: tuple[Tensor, Tensor, Tensor, Tensor], gv: C.Structure,
+                       sv: tuple[Tensor, Tensor, Tensor, Tensor]) -> tuple[Tensor, Tensor]:
+    """``g_h`` of both blocks from ONE launch; their weight and bias gradients go to the flat buffer (``_bwd1x1_pairs``)."""
+    lib = _lib.load()
+    args: list = []
+    outs = []
+    flops = nbytes = 0.0
+    for k, (geom, (g_y, h, w1, b1)) in enumerate(((ga, sa), (gv, sv))):
+        _, wq1t = pack_weight(w1.permute(1, 0, 2, 3), k)  # (slot k of the pack buffer: the second block must not re-use the first's)
+        dwp = _GRAD_SINK.target(w1, geom.Cout, geom.C, 1, geom.CoutPad, geom.Cpad)
+        ws = _wgrad_workspace(geom, 0, g_y.device, own=True)
+        g_h = torch.empty_like(h)
+        outs.append(g_h)
+        args += [C.byref(geom), _lib.ptr(g_y), _lib.ptr(h), _lib.raw_ptr(wq1t), _lib.ptr(g_h), _lib.ptr(dwp), _lib.ptr(grad_target(b1)),
+                 _lib.raw_ptr(ws), 0 if ws is None else ws.numel() * 4]
+        flops += 2.0 * 2.0 * g_y.numel() * geom.C
+        nbytes += 4.0 * (g_y.numel() + 2 * h.numel())
+    _lib.check(_lib.TIMERS.call("mtrssm_residual_bwd1x1_pair", lib.mtrssm_residual_bwd1x1_pair, *args, 1, _lib.stream_ptr(sa[0].device),
+                                flops=flops, nbytes=nbytes), "mtrssm_residual_bwd1x1_pair")
+    return outs[0], outs[1]
+
+
 class _ResidualBlock(torch.autograd.Function):
     """``y = x + Conv1x1(act(Conv3x3(act(x))))`` as ONE node: the skip add rides in the second conv's epilogue and the
     skip's gradient in the epilogue of the first conv's backward-data (``oracle/ref_cnn.py:ResidualBlock``)."""
@@ -835,7 +938,8 @@ class _ResidualBlock(torch.autograd.Function):
 
 class _PairResidualBlock(torch.autograd.Function):
     """``_ResidualBlock`` of the audio and of the vision stack as ONE node: every gather of the pair (two forward, two
-    backward-data) is one launch for both branches; the weight gradients stay one launch each (persistent kernels)."""
+    backward-data) is one launch for both branches, and so is the 3x3 weight gradient where the library pairs the two persistent
+    grids (``_weight_grad_pair``)."""
 
     @staticmethod
     def forward(ctx, xa, w3a, b3a, w1a, b1a, xv, w3v, b3v, w1v, b1v, act):  # noqa: ANN001, PLR0913
@@ -864,7 +968,10 @@ class _PairResidualBlock(torch.autograd.Function):
         b3a, b1a, b3v, b1v = ctx.biases
         g1a = _bwd1x1_geom(g_ya, ha, w1a, act)
         g1v = _bwd1x1_geom(g_yv, hv, w1v, act) if g1a is not None else None
-        if g1a is not None and g1v is not None:
+        if g1a is not None and g1v is not None and _bwd1x1_pairs(g1a, (g_ya, ha, w1a, b1a), g1v, (g_yv, hv, w1v, b1v)):
+            g_ha, g_hv = _bwd1x1_fused_pair(g1a, (g_ya, ha, w1a, b1a), g1v, (g_yv, hv, w1v, b1v))
+            g_w1a = g_b1a = g_w1v = g_b1v = None
+        elif g1a is not None and g1v is not None:
             # one launch per modality: each is a persistent grid over all CUs (as the weight gradients it replaces)
             g_ha, g_w1a, g_b1a = _bwd1x1_fused(g1a, g_ya, ha, w1a, b1a)
             g_hv, g_w1v, g_b1v = _bwd1x1_fused(g1v, g_yv, hv, w1v, b1v)
@@ -876,8 +983,7 @@ class _PairResidualBlock(torch.autograd.Function):
         g_xa, g_xv = paired(
             lambda: _conv_transposed_gather(g_ha, w3a, None, 1, p3, (xa.shape[2], xa.shape[3]), False, act, actgrad_in=xa, add_in=g_ya),
             lambda: _conv_transposed_gather(g_hv, w3v, None, 1, p3, (xv.shape[2], xv.shape[3]), False, act, actgrad_in=xv, add_in=g_yv))
-        g_w3a, g_b3a = _weight_grad(g_ha, xa, None, w3a.shape[2], w3a.shape[3], 1, p3, False, True, act, want_bias=True, weight=w3a, bias=b3a)
-        g_w3v, g_b3v = _weight_grad(g_hv, xv, None, w3v.shape[2], w3v.shape[3], 1, p3, False, True, act, want_bias=True, weight=w3v, bias=b3v)
+        (g_w3a, g_b3a), (g_w3v, g_b3v) = _weight_grad_pair((g_ha, xa, w3a, b3a), (g_hv, xv, w3v, b3v), p3, act)
         return g_xa, g_w3a, g_b3a, g_w1a, g_b1a, g_xv, g_w3v, g_b3v, g_w1v, g_b1v, None
 
 
@@ -925,7 +1031,18 @@ def _pair_function(base: type) -> type:
             ca.saved_tensors, cb.saved_tensors = saved[: ctx.na], saved[ctx.na :]
             ca.cfg, cb.cfg = ctx.cfgs
             ca.bias, cb.bias = ctx.biases
+            if base is _Conv2d:  # the weight gradient of a 3x3 / stride-1 layer (the stacks' input layer): one launch for both
+                ca.wgrad_hold, cb.wgrad_hold = [], []
             ra, rb = paired(lambda: base.backward(ca, ga), lambda: base.backward(cb, gb))
+            ha, hb = getattr(ca, "wgrad_hold", None), getattr(cb, "wgrad_hold", None)
+            if ha and hb and ha[0][1:] == hb[0][1:]:
+                wa, wb = _weight_grad_pair(ha[0][0], hb[0][0], ha[0][1], ha[0][2])
+                ra, rb = (ra[0], *wa, *ra[3:]), (rb[0], *wb, *rb[3:])
+            else:
+                if ha:
+                    ra = (ra[0], *_weight_grad_single(*ha[0]), *ra[3:])
+                if hb:
+                    rb = (rb[0], *_weight_grad_single(*hb[0]), *rb[3:])
             return (None, *ra, *rb)
 
     _Pair.__name__ = f"_Pair{base.__name__}"

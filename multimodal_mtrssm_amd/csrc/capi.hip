@@ -59,6 +59,13 @@ int conv_weight_grad_reduce_flush(hipStream_t);
 int conv_residual_bwd1x1_supported(const MtrssmConvGeom*);
 int conv_residual_bwd1x1_launch(const MtrssmConvGeom*, const float*, const float*, const unsigned short*, float*, float*, float*, void*, size_t, int,
                                 hipStream_t);
+int conv_residual_bwd1x1_pair_supported(const MtrssmConvGeom*, const MtrssmConvGeom*);
+int conv_residual_bwd1x1_pair_launch(const MtrssmConvGeom*, const float*, const float*, const unsigned short*, float*, float*, float*, void*, size_t,
+                                     const MtrssmConvGeom*, const float*, const float*, const unsigned short*, float*, float*, float*, void*, size_t, int,
+                                     hipStream_t);
+int conv_weight_grad_pair_supported(const MtrssmConvGeom*, const MtrssmConvGeom*);
+int conv_weight_grad_pair_launch(const MtrssmConvGeom*, const float*, const float*, float*, float*, void*, size_t, const MtrssmConvGeom*, const float*,
+                                 const float*, float*, float*, void*, size_t, int, hipStream_t);
 int conv_weight_grad_src_bias_supported(const MtrssmConvGeom*, int);
 int conv_weight_grad_src_bias_launch(const MtrssmConvGeom*, const float*, const float*, int, float*, float*, void*, size_t, int, hipStream_t);
 int channel_sum_launch(const float*, int, int, int, float*, hipStream_t);
@@ -363,6 +370,27 @@ MTRSSM_API int mtrssm_residual_bwd1x1(const MtrssmConvGeom* g, const float* gy, 
                                       float* dbias, void* workspace, int64_t workspace_bytes, int32_t defer, void* stream) {
   return conv_residual_bwd1x1_launch(g, gy, h, wq1t, gh, dwp, dbias, workspace, workspace_bytes < 0 ? 0 : (size_t)workspace_bytes, defer,
                                      static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_residual_bwd1x1_pair_supported(const MtrssmConvGeom* ga, const MtrssmConvGeom* gb) {
+  return conv_residual_bwd1x1_pair_supported(ga, gb) != 0;
+}
+MTRSSM_API int mtrssm_residual_bwd1x1_pair(const MtrssmConvGeom* ga, const float* gya, const float* ha, const uint16_t* wq1ta, float* gha, float* dwpa,
+                                           float* dbiasa, void* workspace_a, int64_t workspace_a_bytes, const MtrssmConvGeom* gb, const float* gyb,
+                                           const float* hb, const uint16_t* wq1tb, float* ghb, float* dwpb, float* dbiasb, void* workspace_b,
+                                           int64_t workspace_b_bytes, int32_t defer, void* stream) {
+  return conv_residual_bwd1x1_pair_launch(ga, gya, ha, wq1ta, gha, dwpa, dbiasa, workspace_a, workspace_a_bytes < 0 ? 0 : (size_t)workspace_a_bytes, gb,
+                                          gyb, hb, wq1tb, ghb, dwpb, dbiasb, workspace_b, workspace_b_bytes < 0 ? 0 : (size_t)workspace_b_bytes, defer,
+                                          static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_conv_weight_grad_pair_supported(const MtrssmConvGeom* ga, const MtrssmConvGeom* gb) {
+  return conv_weight_grad_pair_supported(ga, gb) != 0;
+}
+MTRSSM_API int mtrssm_conv_weight_grad_pair(const MtrssmConvGeom* ga, const float* aa, const float* srca, float* dwpa, float* dbiasa, void* workspace_a,
+                                            int64_t workspace_a_bytes, const MtrssmConvGeom* gb, const float* ab, const float* srcb, float* dwpb,
+                                            float* dbiasb, void* workspace_b, int64_t workspace_b_bytes, int32_t defer, void* stream) {
+  return conv_weight_grad_pair_launch(ga, aa, srca, dwpa, dbiasa, workspace_a, workspace_a_bytes < 0 ? 0 : (size_t)workspace_a_bytes, gb, ab, srcb, dwpb,
+                                      dbiasb, workspace_b, workspace_b_bytes < 0 ? 0 : (size_t)workspace_b_bytes, defer,
+                                      static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int mtrssm_conv_weight_grad_src_bias_supported(const MtrssmConvGeom* g, int32_t pre_act_a) {
   return conv_weight_grad_src_bias_supported(g, pre_act_a);

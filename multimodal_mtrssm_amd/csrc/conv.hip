@@ -2046,6 +2046,164 @@ int conv_residual_bwd1x1_launch(const MtrssmConvGeom* g, const float* gy, const 
   return launched("residual_bwd1x1");
 }
 
+// MTRSSM_PAIR_WGRAD=0: both paired queries below refuse every shape (A/B runs of the one-launch-per-modality path through the
+// same Python code)
+static bool pair_wgrad_enabled() {
+  static const bool on = [] { const char* e = getenv("MTRSSM_PAIR_WGRAD"); return !(e && e[0] == '0'); }();
+  return on;
+}
+
+// ---- mtrssm_residual_bwd1x1 for the audio and the vision block in one grid (conv_wgrad_resident.h: conv1x1_bwd_fused_pair_kernel) ----
+int conv_residual_bwd1x1_pair_supported(const MtrssmConvGeom* ga, const MtrssmConvGeom* gb) {
+  if (!ga || !gb || !pair_wgrad_enabled()) return 0;
+  return conv_residual_bwd1x1_supported(ga) && conv_residual_bwd1x1_supported(gb) && ga->C == gb->C;
+}
+struct Bwd1x1PairSide {
+  const MtrssmConvGeom* g;
+  const float* gy;
+  const float* h;
+  const unsigned short* wq1t;
+  float* gh;
+  float* dwp;
+  float* dbias;
+  void* workspace;
+  size_t workspace_bytes;
+};
+int conv_residual_bwd1x1_pair_launch(const MtrssmConvGeom* ga, const float* gya, const float* ha, const unsigned short* wq1ta, float* gha, float* dwpa,
+                                     float* dbiasa, void* wsa, size_t wsa_bytes, const MtrssmConvGeom* gb, const float* gyb, const float* hb,
+                                     const unsigned short* wq1tb, float* ghb, float* dwpb, float* dbiasb, void* wsb, size_t wsb_bytes, int defer,
+                                     hipStream_t stream) {
+  const Bwd1x1PairSide sa{ga, gya, ha, wq1ta, gha, dwpa, dbiasa, wsa, wsa_bytes}, sb{gb, gyb, hb, wq1tb, ghb, dwpb, dbiasb, wsb, wsb_bytes};
+  if (!conv_residual_bwd1x1_pair_supported(sa.g, sb.g)) {
+    set_error("residual_bwd1x1_pair: shapes without a paired kernel (query mtrssm_residual_bwd1x1_pair_supported first)");
+    return MTRSSM_EINVAL;
+  }
+  const int C_ = sa.g->C;
+  const int slots = cu_count() / 2 > 0 ? cu_count() / 2 : 1;  // workgroups per problem: one per CU in total
+  Bwd1x1Problem pr[2];
+  const Bwd1x1PairSide* const sides[2] = {&sa, &sb};
+  for (int i = 0; i < 2; ++i) {
+    const Bwd1x1PairSide& s = *sides[i];
+    if (!s.gy || !s.h || !s.wq1t || !s.gh || !s.dwp) { set_error("residual_bwd1x1_pair: null pointer"); return MTRSSM_EINVAL; }
+    if (((uintptr_t)s.gy & 15) || ((uintptr_t)s.h & 15) || ((uintptr_t)s.wq1t & 15) || ((uintptr_t)s.gh & 3) || ((uintptr_t)s.workspace & 255)) {
+      set_error("residual_bwd1x1_pair: g_y, h and the weight pieces must be 16-byte aligned, the workspaces 256-byte aligned");
+      return MTRSSM_EINVAL;
+    }
+    const int wgs = slots < s.g->N ? slots : s.g->N;
+    const int per = (s.g->N + wgs - 1) / wgs;
+    const int xb = (s.g->N + per - 1) / per;
+    float* part = nullptr;
+    if (wgrad_partials_enabled() && s.workspace && s.workspace_bytes >= (size_t)xb * kWg1x1SetFloats * sizeof(float)) part = static_cast<float*>(s.workspace);
+    pr[i] = Bwd1x1Problem{s.gy, s.h, s.wq1t, s.gh, s.dwp, part, s.dbias, s.g->N, s.g->act, s.g->Cpad, per, xb};
+  }
+  const dim3 grid((unsigned)(pr[0].xblocks + pr[1].xblocks));
+#define MTRSSM_BW1P_LAUNCH(C_)                                                                                                  \
+  {                                                                                                                             \
+    static bool attr_done_dev[64] = {}; bool& attr_done = attr_done_dev[device_slot()];                                         \
+    constexpr int lds_b = bwd1x1_lds_bytes<C_>();                                                                               \
+    if (!attr_done) {                                                                                                           \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_bwd_fused_pair_kernel<C_>),                               \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_b);                                             \
+      attr_done = true;                                                                                                         \
+    }                                                                                                                           \
+    set_last_kernel("mtrssm::conv1x1_bwd_fused_pair_kernel<" #C_ ">");                                                          \
+    hipLaunchKernelGGL((conv1x1_bwd_fused_pair_kernel<C_>), grid, dim3(512), lds_b, stream, pr[0], pr[1]);                      \
+  }
+  if (C_ == 64) MTRSSM_BW1P_LAUNCH(64) else MTRSSM_BW1P_LAUNCH(128)
+#undef MTRSSM_BW1P_LAUNCH
+  for (int i = 0; i < 2; ++i) {
+    if (!pr[i].part) continue;
+    const dim3 rgrid((unsigned)(2 * (C_ / 32) * 256 / 32 + (pr[i].dbias ? 1 : 0)), 1);  // + the bias block
+    tl_defer_reduce = defer != 0;
+    const int rc = reduce_now_or_later(C_ == 64 ? kRed1x1_64 : kRed1x1_128, rgrid, pr[i].part, pr[i].xblocks, pr[i].cpad, pr[i].dwp, pr[i].dbias, stream);
+    tl_defer_reduce = false;
+    if (rc) return rc;
+  }
+  return launched("residual_bwd1x1_pair");
+}
+
+// ---- the residual stacks' 3x3 weight gradient (conv3x3_wgrad_resident_kernel) for two problems in one grid ----
+// the geometry test of that kernel's branch in conv_weight_grad_launch_ex (which adds the pointer alignments)
+static bool wgrad_resident_takes(const MtrssmConvGeom* g, int pre_act_a) {
+  return (g->mfma_split == 1 || g->mfma_split == 2) && g->KH == 3 && g->KW == 3 && g->SS == 1 && g->TS == 1 && g->OFFY == -1 && g->OFFX == -1 &&
+         g->C2 == 0 && g->Hs == g->Hq && g->Ws == g->Wq && (g->Wq == 8 || g->Wq == 4) && g->Hq * g->Wq == 64 &&
+         (g->C == 64 || (g->C == 32 && wgrad_resident_c32())) && g->Cout % 64 == 0 && g->Cout <= 65535 * 64 && g->Cpad >= g->C && !pre_act_a &&
+         (g->act == MTRSSM_ACT_IDENTITY || g->act == MTRSSM_ACT_ELU || g->act == MTRSSM_ACT_RELU) && wgrad_resident_enabled() && !no_direct_wgrad();
+}
+// one 4-wide and one 8-wide plane, the same layer otherwise (frame counts may differ), two bf16 pieces
+int conv_weight_grad_pair_supported(const MtrssmConvGeom* ga, const MtrssmConvGeom* gb) {
+  if (!ga || !gb || !pair_wgrad_enabled()) return 0;
+  if (check_geom(ga, "conv_weight_grad_pair") || check_geom(gb, "conv_weight_grad_pair")) return 0;
+  if (ga->OS != 1 || ga->QY != 0 || ga->QX != 0 || gb->OS != 1 || gb->QY != 0 || gb->QX != 0) return 0;
+  return wgrad_resident_takes(ga, 0) && wgrad_resident_takes(gb, 0) && ga->mfma_split == 2 && gb->mfma_split == 2 && ga->C == gb->C &&
+         ga->Cout == gb->Cout && ga->Wq + gb->Wq == 12 && ga->N >= 1 && gb->N >= 1;
+}
+struct WgradPairSide {
+  const MtrssmConvGeom* g;
+  const float* a;
+  const float* src;
+  float* dwp;
+  float* dbias;
+  void* workspace;
+  size_t workspace_bytes;
+};
+int conv_weight_grad_pair_launch(const MtrssmConvGeom* ga, const float* aa, const float* srca, float* dwpa, float* dbiasa, void* wsa, size_t wsa_bytes,
+                                 const MtrssmConvGeom* gb, const float* ab, const float* srcb, float* dwpb, float* dbiasb, void* wsb, size_t wsb_bytes,
+                                 int defer, hipStream_t stream) {
+  const WgradPairSide s0{ga, aa, srca, dwpa, dbiasa, wsa, wsa_bytes}, s1{gb, ab, srcb, dwpb, dbiasb, wsb, wsb_bytes};
+  if (!conv_weight_grad_pair_supported(s0.g, s1.g)) {
+    set_error("conv_weight_grad_pair: shapes without a paired kernel (query mtrssm_conv_weight_grad_pair_supported first)");
+    return MTRSSM_EINVAL;
+  }
+  const bool swap = s0.g->Wq == 8;  // the kernel's problem a is the 4-wide one
+  const WgradPairSide* const sides[2] = {swap ? &s1 : &s0, swap ? &s0 : &s1};
+  const int C_ = s0.g->C, cogroups = s0.g->Cout / 64;
+  // one wave per SIMD over the chip, as the single launch, half of the x blocks for each problem
+  int slots = (C_ == 64 ? cu_count() : 2 * cu_count()) / (2 * cogroups);
+  if (slots < 1) slots = 1;
+  WgresProblem pr[2];
+  for (int i = 0; i < 2; ++i) {
+    const WgradPairSide& s = *sides[i];
+    if (!s.a || !s.src || !s.dwp) { set_error("conv_weight_grad_pair: null pointer"); return MTRSSM_EINVAL; }
+    if (((uintptr_t)s.a & 15) || ((uintptr_t)s.src & 15) || ((uintptr_t)s.dwp & 15) || ((uintptr_t)s.workspace & 255)) {
+      set_error("conv_weight_grad_pair: a, src and dwp must be 16-byte aligned, the workspaces 256-byte aligned");
+      return MTRSSM_EINVAL;
+    }
+    const int wgs = slots < s.g->N ? slots : s.g->N;
+    const int per = (s.g->N + wgs - 1) / wgs;
+    const int xb = (s.g->N + per - 1) / per;
+    float* part = nullptr;
+    if (wgrad_partials_enabled() && s.workspace && s.workspace_bytes >= (size_t)xb * cogroups * wgres_set_floats(C_) * sizeof(float))
+      part = static_cast<float*>(s.workspace);
+    pr[i] = WgresProblem{s.a, s.src, s.dwp, part, s.dbias, s.g->N, s.g->Cout, s.g->Cpad, s.g->act, s.g->pre_act, per, xb};
+  }
+  const dim3 grid((unsigned)(pr[0].xblocks + pr[1].xblocks), cogroups);
+#define MTRSSM_WGRESP_LAUNCH(C_)                                                                                                \
+  {                                                                                                                             \
+    static bool attr_done_dev[64] = {}; bool& attr_done = attr_done_dev[device_slot()];                                         \
+    constexpr int lds_a = wgres_lds_bytes<2, C_, 4>(), lds_8 = wgres_lds_bytes<2, C_, 8>(), lds_b = lds_a > lds_8 ? lds_a : lds_8; \
+    if (!attr_done) {                                                                                                           \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wgrad_pair_resident_kernel<2, C_, 4, 8>),                 \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_b);                                             \
+      attr_done = true;                                                                                                         \
+    }                                                                                                                           \
+    set_last_kernel("mtrssm::conv3x3_wgrad_pair_resident_kernel<2, " #C_ ", 4, 8>");                                            \
+    hipLaunchKernelGGL((conv3x3_wgrad_pair_resident_kernel<2, C_, 4, 8>), grid, dim3(64 * 2 * (C_ / 32)), lds_b, stream, pr[0],  \
+                       pr[1]);                                                                                                  \
+  }
+  if (C_ == 64) MTRSSM_WGRESP_LAUNCH(64) else MTRSSM_WGRESP_LAUNCH(32)
+#undef MTRSSM_WGRESP_LAUNCH
+  for (int i = 0; i < 2; ++i) {
+    if (!pr[i].part) continue;
+    const dim3 rgrid((unsigned)(wgres_tile_floats(C_) / 4 / 32 + (pr[i].dbias ? 1 : 0)), cogroups);  // + the bias block
+    tl_defer_reduce = defer != 0;
+    const int rc = reduce_now_or_later(C_ == 64 ? kRedRes64 : kRedRes32, rgrid, pr[i].part, pr[i].xblocks, pr[i].cpad, pr[i].dwp, pr[i].dbias, stream);
+    tl_defer_reduce = false;
+    if (rc) return rc;
+  }
+  return launched("conv_weight_grad_pair");
+}
+
 int conv_weight_grad_launch_ex(const MtrssmConvGeom* g, const float* a, const float* src, const float* src2, int pre_act_a, float* dwp,
                                float* dbias, void* workspace, size_t workspace_bytes, size_t* query, WgradSrcBias* sb, hipStream_t stream) {
   if (int rc = check_geom(g, "conv_weight_grad")) return rc;
@@ -2110,11 +2268,7 @@ int conv_weight_grad_launch_ex(const MtrssmConvGeom* g, const float* a, const fl
     else hipLaunchKernelGGL((conv1x1_weight_grad_split_kernel<1>), grid, block, 0, stream, *g, a, src, pre_act_a, dwp, dbias, tiles_ci, per);
     return launched("conv_weight_grad(1x1 split)");
   }
-  if ((g->mfma_split == 1 || g->mfma_split == 2) && g->KH == 3 && g->KW == 3 && g->SS == 1 && g->TS == 1 && g->OFFY == -1 && g->OFFX == -1 &&
-      g->C2 == 0 && g->Hs == g->Hq && g->Ws == g->Wq && (g->Wq == 8 || g->Wq == 4) && g->Hq * g->Wq == 64 && (g->C == 64 || (g->C == 32 && wgrad_resident_c32())) &&
-      g->Cout % 64 == 0 && g->Cout <= 65535 * 64 && g->Cpad >= g->C && !pre_act_a &&
-      (g->act == MTRSSM_ACT_IDENTITY || g->act == MTRSSM_ACT_ELU || g->act == MTRSSM_ACT_RELU) && !((uintptr_t)a & 15) &&
-      !((uintptr_t)src & 15) && !((uintptr_t)dwp & 15) && wgrad_resident_enabled() && !no_direct_wgrad()) {
+  if (wgrad_resident_takes(g, pre_act_a) && !((uintptr_t)a & 15) && !((uintptr_t)src & 15) && !((uintptr_t)dwp & 15)) {
     // 3x3 layers of the residual stacks on 64-pixel planes: both operands staged once per frame (conv_wgrad_resident.h)
     const int cogroups = g->Cout / 64;
     int wgs = (g->C == 64 ? cu_count() : 2 * cu_count()) / cogroups;  // one wave per SIMD over the chip

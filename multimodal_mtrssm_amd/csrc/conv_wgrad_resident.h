@@ -65,10 +65,12 @@ __device__ __forceinline__ void wg_split_pair(const float f0, const float f1, un
   }
 }
 
+// One problem's work of one workgroup: bx of the problem's nbx x blocks (its run of frames_per_wg frames), co group blockIdx.y.
+// The kernels below are wrappers: one problem per grid, or two (audio and vision planes) side by side in one grid.
 template <int SPLIT, int C, int W>
-__global__ __launch_bounds__(64 * 2 * (C / 32), 1) void conv3x3_wgrad_resident_kernel(
-    const MtrssmConvGeom g, const float* __restrict__ a, const float* __restrict__ src, float* __restrict__ dwp,
-    float* __restrict__ part, float* __restrict__ dbias, const int frames_per_wg) {
+__device__ __forceinline__ void conv3x3_wgrad_resident_body(
+    const int N, const int Cout, const int cpad, const int act, const int pre_act, const float* __restrict__ a, const float* __restrict__ src, float* __restrict__ dwp,
+    float* __restrict__ part, float* __restrict__ dbias, const int frames_per_wg, const int bx, const int nbx) {
   static_assert(SPLIT == 1 || SPLIT == 2, "one or two bf16 pieces");
   constexpr int NW = 2 * (C / 32), NT = 64 * NW;
   constexpr int RB = 2 * W;  // bytes per image row
@@ -81,17 +83,17 @@ __global__ __launch_bounds__(64 * 2 * (C / 32), 1) void conv3x3_wgrad_resident_k
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int il = lane & 31, kl = lane >> 5;
   const int tci = wave >> 1, half = wave & 1;
-  const int n0 = blockIdx.x * frames_per_wg;
-  const int n1 = n0 + frames_per_wg < g.N ? n0 + frames_per_wg : g.N;
+  const int n0 = bx * frames_per_wg;
+  const int n1 = n0 + frames_per_wg < N ? n0 + frames_per_wg : N;
   if (n0 >= n1) return;  // whole workgroup
   const int nlast = n1 - 1;
   const int cob = blockIdx.y * 64;
   // development aid (tools/wgrad_probe.py): cycle stamps of workgroup 0 and of the middle workgroup
-  unsigned long long* const prof = (tid == 0 && blockIdx.y == 0 && g_res_prof) ? (blockIdx.x == 0 ? g_res_prof + 32 : (blockIdx.x == gridDim.x / 2 ? g_res_prof + 40 : nullptr)) : nullptr;
+  unsigned long long* const prof = (tid == 0 && blockIdx.y == 0 && g_res_prof) ? (bx == 0 ? g_res_prof + 32 : (bx == nbx / 2 ? g_res_prof + 40 : nullptr)) : nullptr;
   if (prof) prof[0] = __builtin_readcyclecounter();
 
   // activation switches as lane-uniform selects (no branch inside the MFMA loop: a branch ends a scheduling region)
-  const bool act_elu = g.act == MTRSSM_ACT_ELU, act_relu = g.act == MTRSSM_ACT_RELU, pre = g.pre_act != 0;
+  const bool act_elu = act == MTRSSM_ACT_ELU, act_relu = act == MTRSSM_ACT_RELU, pre = pre_act != 0;
   auto act_sel = [&](float x) __attribute__((always_inline)) {
     float e = __expf(x) - 1.f;
     asm volatile("" : "+v"(e));  // computed unconditionally: the compiler would branch around the exponential
@@ -106,7 +108,7 @@ __global__ __launch_bounds__(64 * 2 * (C / 32), 1) void conv3x3_wgrad_resident_k
   // 4 consecutive pixels of channel (tid >> 4) + j * NT / 16
   const float4* const xsrc = reinterpret_cast<const float4*>(src) + tid;
   const float4* const asrc = reinterpret_cast<const float4*>(a + (size_t)cob * 64) + tid;
-  const size_t xfr = (size_t)C * 16, afr = (size_t)g.Cout * 16;  // float4 per frame
+  const size_t xfr = (size_t)C * 16, afr = (size_t)Cout * 16;  // float4 per frame
   const int xi = tid & 15;
   const int xrow = (xi * 4) / W, xcol = (xi * 4) % W;
   const unsigned wofs = (unsigned)((tid >> 4) * PITCH + (xrow + 1) * RB + xcol * 2);
@@ -290,7 +292,7 @@ __global__ __launch_bounds__(64 * 2 * (C / 32), 1) void conv3x3_wgrad_resident_k
   if (part) {
     // accumulator order: float4 number ((wave * 9 + j) * 4 + r / 4) * 64 + lane of this workgroup's set -- every store
     // instruction writes 1 KiB in a row (wgrad_reduce_partials_kernel maps it back to dwp)
-    float4* const ps = reinterpret_cast<float4*>(part) + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (wgres_set_floats(C) / 4) + (size_t)wave * (9 * 4 * 64) + lane;
+    float4* const ps = reinterpret_cast<float4*>(part) + ((size_t)blockIdx.y * nbx + bx) * (wgres_set_floats(C) / 4) + (size_t)wave * (9 * 4 * 64) + lane;
 #pragma unroll
     for (int j = 0; j < 9; ++j)
 #pragma unroll
@@ -305,7 +307,7 @@ __global__ __launch_bounds__(64 * 2 * (C / 32), 1) void conv3x3_wgrad_resident_k
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = cot + (r & 3) + 8 * (r >> 2) + 4 * kl;
-        atomicAdd(&dwp[((size_t)row * 9 + tap) * g.Cpad + ci], acc[j][r]);
+        atomicAdd(&dwp[((size_t)row * 9 + tap) * cpad + ci], acc[j][r]);
       }
     }
   }
@@ -319,7 +321,7 @@ __global__ __launch_bounds__(64 * 2 * (C / 32), 1) void conv3x3_wgrad_resident_k
       v += dpp_move<0x140, 0xF>(0.f, v);  // row_mirror
       if (xi == 0) {
         const int ch = (tid >> 4) + j * (NT / 16);
-        if (part) part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * wgres_set_floats(C) + wgres_tile_floats(C) + ch] = v;
+        if (part) part[((size_t)blockIdx.y * nbx + bx) * wgres_set_floats(C) + wgres_tile_floats(C) + ch] = v;
         else atomicAdd(&dbias[cob + ch], v);
       }
     }
@@ -328,6 +330,34 @@ __global__ __launch_bounds__(64 * 2 * (C / 32), 1) void conv3x3_wgrad_resident_k
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     prof[3] = __builtin_readcyclecounter();
   }
+}
+
+template <int SPLIT, int C, int W>
+__global__ __launch_bounds__(64 * 2 * (C / 32), 1) void conv3x3_wgrad_resident_kernel(
+    const MtrssmConvGeom g, const float* __restrict__ a, const float* __restrict__ src, float* __restrict__ dwp,
+    float* __restrict__ part, float* __restrict__ dbias, const int frames_per_wg) {
+  conv3x3_wgrad_resident_body<SPLIT, C, W>(g.N, g.Cout, g.Cpad, g.act, g.pre_act, a, src, dwp, part, dbias, frames_per_wg, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// Two problems of the same C and Cout in ONE grid (the audio and the vision stack's layer: WA- and WB-wide planes): x blocks
+// 0 .. pa.xblocks - 1 run problem a, the rest problem b; every workgroup's run is twice as long as in two launches of their
+// own, and the fixed part of a launch (ramp, zeroing the images, the first frame's round trip, the partial-set store, the
+// drain) is paid once.  Half as many workgroups per problem = half as many partial sets.  The choice is uniform per workgroup:
+// no barrier sits under a divergent branch.  Dynamic LDS: the larger of the two wgres_lds_bytes.
+struct WgresProblem {
+  const float* a;
+  const float* src;
+  float* dwp;
+  float* part;    // this problem's partial sets [cogroups][xblocks] (NULL: fp32 atomics into dwp / dbias)
+  float* dbias;
+  int N, Cout, cpad, act, pre_act;  // of the problem's geometry
+  int frames_per_wg, xblocks;
+};
+template <int SPLIT, int C, int WA, int WB>
+__global__ __launch_bounds__(64 * 2 * (C / 32), 1) void conv3x3_wgrad_pair_resident_kernel(const WgresProblem pa, const WgresProblem pb) {
+  const int bx = (int)blockIdx.x;
+  if (bx < pa.xblocks) conv3x3_wgrad_resident_body<SPLIT, C, WA>(pa.N, pa.Cout, pa.cpad, pa.act, pa.pre_act, pa.a, pa.src, pa.dwp, pa.part, pa.dbias, pa.frames_per_wg, bx, pa.xblocks);
+  else conv3x3_wgrad_resident_body<SPLIT, C, WB>(pb.N, pb.Cout, pb.cpad, pb.act, pb.pre_act, pb.a, pb.src, pb.dwp, pb.part, pb.dbias, pb.frames_per_wg, bx - pa.xblocks, pb.xblocks);
 }
 
 // Sum of the S partial tile sets of every co group (part [cogroups][S][set floats], accumulator order) into dwp.  Thread =
@@ -636,10 +666,12 @@ __global__ __launch_bounds__(256) void wgrad_reduce_partials1x1_kernel(const flo
 template <int C>
 __host__ __device__ constexpr int bwd1x1_lds_bytes() { return wg1x1_lds_bytes<2, C>() + 2 * 2 * 64 * kWgresAPitch; }
 
+// One problem's work of workgroup bx (its run of frames_per_wg frames); `act` and `cpad` are the geometry's.
 template <int C>
-__global__ __launch_bounds__(512, 1) void conv1x1_bwd_fused_kernel(
-    const MtrssmConvGeom g, const float* __restrict__ a, const float* __restrict__ src, const unsigned short* __restrict__ wq,
-    float* __restrict__ gh, float* __restrict__ dwp, float* __restrict__ part, float* __restrict__ dbias, const int frames_per_wg) {
+__device__ __forceinline__ void conv1x1_bwd_fused_body(
+    const int N, const int act, const int cpad, const float* __restrict__ a, const float* __restrict__ src,
+    const unsigned short* __restrict__ wq, float* __restrict__ gh, float* __restrict__ dwp, float* __restrict__ part,
+    float* __restrict__ dbias, const int frames_per_wg, const int bx) {
   static_assert(C == 64 || C == 128, "mid channels");
   constexpr int SPLIT = 2, NT = 512, P = kWgresAPitch;
   constexpr int XI = C * 16 / NT, AI = 2, NI = XI + AI;  // float4 items per thread and frame: src (h), a (g_y: 64 co * 16)
@@ -654,12 +686,12 @@ __global__ __launch_bounds__(512, 1) void conv1x1_bwd_fused_kernel(
   const int il = lane & 31, kl = lane >> 5;
   const int tile = wave % NTILE, kpart = wave / NTILE;
   const int tco = tile & 1, tci = tile >> 1;
-  const int n0 = blockIdx.x * frames_per_wg;
-  const int n1 = n0 + frames_per_wg < g.N ? n0 + frames_per_wg : g.N;
+  const int n0 = bx * frames_per_wg;
+  const int n1 = n0 + frames_per_wg < N ? n0 + frames_per_wg : N;
   if (n0 >= n1) return;  // whole workgroup
   const int nlast = n1 - 1;
 
-  const bool act_elu = g.act == MTRSSM_ACT_ELU, act_relu = g.act == MTRSSM_ACT_RELU;
+  const bool act_elu = act == MTRSSM_ACT_ELU, act_relu = act == MTRSSM_ACT_RELU;
   auto act_sel = [&](float x) __attribute__((always_inline)) {
     float e = __expf(x) - 1.f;
     asm volatile("" : "+v"(e));  // computed unconditionally: the compiler would branch around the exponential
@@ -815,7 +847,7 @@ __global__ __launch_bounds__(512, 1) void conv1x1_bwd_fused_kernel(
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the clamped requests of the last frames
 
   if (part) {  // the partial set of conv1x1_wgrad_staged_kernel: wgrad_reduce_partials1x1_body sums it
-    float4* const ps = reinterpret_cast<float4*>(part) + (size_t)blockIdx.x * (kWg1x1SetFloats / 4) + (size_t)wave * 256 + lane;
+    float4* const ps = reinterpret_cast<float4*>(part) + (size_t)bx * (kWg1x1SetFloats / 4) + (size_t)wave * 256 + lane;
 #pragma unroll
     for (int gq = 0; gq < 4; ++gq) ps[gq * 64] = make_float4(acc[4 * gq], acc[4 * gq + 1], acc[4 * gq + 2], acc[4 * gq + 3]);
   } else {
@@ -823,7 +855,7 @@ __global__ __launch_bounds__(512, 1) void conv1x1_bwd_fused_kernel(
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int row = tco * 32 + (r & 3) + 8 * (r >> 2) + 4 * kl;
-      atomicAdd(&dwp[(size_t)row * g.Cpad + ci], acc[r]);
+      atomicAdd(&dwp[(size_t)row * cpad + ci], acc[r]);
     }
   }
   if (dbias != nullptr) {
@@ -836,11 +868,40 @@ __global__ __launch_bounds__(512, 1) void conv1x1_bwd_fused_kernel(
       v += dpp_move<0x140, 0xF>(0.f, v);
       if ((tid & 15) == 0) {
         const int ch = (tid >> 4) + j * 32;
-        if (part) part[(size_t)blockIdx.x * kWg1x1SetFloats + 8 * 1024 + ch] = v;
+        if (part) part[(size_t)bx * kWg1x1SetFloats + 8 * 1024 + ch] = v;
         else atomicAdd(&dbias[ch], v);
       }
     }
   }
+}
+
+template <int C>
+__global__ __launch_bounds__(512, 1) void conv1x1_bwd_fused_kernel(
+    const MtrssmConvGeom g, const float* __restrict__ a, const float* __restrict__ src, const unsigned short* __restrict__ wq,
+    float* __restrict__ gh, float* __restrict__ dwp, float* __restrict__ part, float* __restrict__ dbias, const int frames_per_wg) {
+  conv1x1_bwd_fused_body<C>(g.N, g.act, g.Cpad, a, src, wq, gh, dwp, part, dbias, frames_per_wg, (int)blockIdx.x);
+}
+
+// Two problems of the same C in ONE grid (the audio and the vision stack's block; the kernel does not depend on the plane's
+// shape): workgroups 0 .. pa.xblocks - 1 run problem a, the rest problem b.  The problem is picked by scalar selects and the
+// body instantiated once; each frame's g_h is computed as in a launch of its own, bit for bit.
+struct Bwd1x1Problem {
+  const float* a;
+  const float* src;
+  const unsigned short* wq;
+  float* gh;
+  float* dwp;
+  float* part;    // this problem's partial sets [xblocks] (NULL: fp32 atomics into dwp / dbias)
+  float* dbias;
+  int N, act, cpad, frames_per_wg, xblocks;
+};
+template <int C>
+__global__ __launch_bounds__(512, 1) void conv1x1_bwd_fused_pair_kernel(const Bwd1x1Problem pa, const Bwd1x1Problem pb) {
+  const bool first = (int)blockIdx.x < pa.xblocks;  // workgroup-uniform
+  conv1x1_bwd_fused_body<C>(first ? pa.N : pb.N, first ? pa.act : pb.act, first ? pa.cpad : pb.cpad, first ? pa.a : pb.a,
+                            first ? pa.src : pb.src, first ? pa.wq : pb.wq, first ? pa.gh : pb.gh, first ? pa.dwp : pb.dwp,
+                            first ? pa.part : pb.part, first ? pa.dbias : pb.dbias, first ? pa.frames_per_wg : pb.frames_per_wg,
+                            first ? (int)blockIdx.x : (int)blockIdx.x - pa.xblocks);
 }
 
 // ------------------------------------------------------------------------------------------------

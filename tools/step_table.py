@@ -1,4 +1,5 @@
-"""The "Where the step goes" table of DESIGN.md from profiles/<round>_*bench_kernel_stats.csv: `python tools/step_table.py round3`."""
+"""The "Where the step goes" table of DESIGN.md from profiles/<round>_*bench_kernel_stats.csv: `python tools/step_table.py round3`.
+With a second name, the groups that differ between two base tables: `python tools/step_table.py resblock_bwd_pair_parent resblock_bwd_pair_new`."""
 import csv
 import sys
 
@@ -17,10 +18,14 @@ def group(k: str) -> str:
         return "weight-resident 3x3 gathers (forward: the whole residual block, fused)"
     if "conv1x1_stream" in k:
         return "1x1 gathers (streaming kernel; backward-data only)"
+    if "bwd_fused_pair" in k:
+        return "1x1 backward of the residual blocks in one pass (g_h, dW1, db1), audio + vision in one grid"
     if "bwd_fused" in k:
         return "1x1 backward of the residual blocks in one pass (g_h, dW1, db1)"
     if "wgrad_reduce" in k:
         return "partial-set sums of the staged weight gradients (one batched launch)"
+    if "wgrad_pair" in k:
+        return "3x3 weight gradients of the residual stacks, audio + vision in one grid"
     if "wgrad" in k:
         return "conv weight gradients (staged kernels)"
     if "quad" in k or "rows" in k:
@@ -48,6 +53,15 @@ def table(path: str):
     return lines, groups, tot, nl
 
 
+if len(sys.argv) > 2:  # `python tools/step_table.py resblock_bwd_pair_parent resblock_bwd_pair_new`: two base tables, rows that differ
+    (_, ga, ta, na), (_, gb, tb, nb) = table(f"profiles/{R}_bench_kernel_stats.csv"), table(f"profiles/{sys.argv[2]}_bench_kernel_stats.csv")
+    print(f"| group | launches / step ({R} -> {sys.argv[2]}) | ms / step |\n|---|---|---|")
+    for g in sorted(set(ga) | set(gb), key=lambda g: -max(ga.get(g, [0])[0], gb.get(g, [0])[0])):
+        (ma, la), (mb, lb) = ga.get(g, [0.0, 0.0]), gb.get(g, [0.0, 0.0])
+        if abs(ma - mb) >= 0.005 or la != lb:  # noqa: PLR2004
+            print(f"| {g} | {la:.0f} -> {lb:.0f} | {ma:.3f} -> {mb:.3f} |")
+    print(f"| all kernels | {na:.1f} -> {nb:.1f} | {ta:.3f} -> {tb:.3f} |")
+    sys.exit(0)
 lines, _, tot, nl = table(f"profiles/{R}_bench_kernel_stats.csv")
 _, gm, totm, nlm = table(f"profiles/{R}_mmtrssm_bench_kernel_stats.csv")
 _, gl, totl, _ = table(f"profiles/{R}_large_bench_kernel_stats.csv")
