@@ -117,6 +117,8 @@ typedef struct MtrssmMrssmFwdIO {
   float* sv_heads;      /* [B,T,3H] act of prior / audio / vision head layer 0 */
   float* sv_la;         /* [B,T,S]  audio logits */
   float* sv_lv;         /* [B,T,S]  vision logits */
+  const float* expert_logw; /* [B,T,3] log-weights of the (audio, vision, fused) MoPoE experts, taken as given (not normalised);
+                               read where both are present; NULL = 1/3 everywhere; needs `modality`; prior-only: ignored */
   const int32_t* modality; /* [B,T] bit0 audio, bit1 vision; NULL = both everywhere */
 } MtrssmMrssmFwdIO;
 
@@ -197,6 +199,9 @@ typedef struct MtrssmMrssmBwdIO {
   float* d_lp;      /* [B,T,S]  grad at prior logits */
   float* d_la;      /* [B,T,S]  grad at audio logits */
   float* d_lv;      /* [B,T,S]  grad at vision logits */
+  const float* expert_logw; /* [B,T,3] as in the forward call; NULL = 1/3 everywhere; needs `modality` */
+  float* g_expert_logw;     /* [B,T,3] grad at expert_logw, written once per (b, t): exactly 0 where not both are present;
+                               NULL = not wanted; needs expert_logw */
   const int32_t* modality; /* [B,T] bit0 audio, bit1 vision; NULL = both everywhere */
 } MtrssmMrssmBwdIO;
 
@@ -312,6 +317,8 @@ typedef struct MtrssmMmtrssmFwdIO {
   float* sv_h1;           /* [B,T,H]  act of h_prior layer 0 */
   float* sv_la;           /* [B,T,LS] */
   float* sv_lv;           /* [B,T,LS] */
+  const float* expert_logw; /* [B,T,3] log-weights of the (audio, vision, fused) MoPoE experts, taken as given (not normalised);
+                               read where both are present; NULL = 1/3 everywhere; needs `modality`; prior-only: ignored */
   const int32_t* modality; /* [B,T] bit0 audio, bit1 vision; NULL = both everywhere */
 } MtrssmMmtrssmFwdIO;
 
@@ -376,6 +383,9 @@ typedef struct MtrssmMmtrssmBwdIO {
   float* d_lv;    /* [B,T,LS] */
   float* d_lph;   /* [B,T,HS] grad at higher prior logits */
   float* d_lqh;   /* [B,T,HS] grad at higher posterior logits */
+  const float* expert_logw; /* [B,T,3] as in the forward call; NULL = 1/3 everywhere; needs `modality` */
+  float* g_expert_logw;     /* [B,T,3] grad at expert_logw, written once per (b, t): exactly 0 where not both are present;
+                               NULL = not wanted; needs expert_logw */
   const int32_t* modality; /* [B,T] bit0 audio, bit1 vision; NULL = both everywhere */
 } MtrssmMmtrssmBwdIO;
 

@@ -8,7 +8,7 @@ Importing the package does not need a GPU; running a rollout does, and fails lou
 
 from multimodal_mtrssm_amd.carry import StateCarry
 from multimodal_mtrssm_amd.cnn import Decoder, Encoder
-from multimodal_mtrssm_amd.core import MoPoE_MMTRSSM, MoPoE_MRSSM
+from multimodal_mtrssm_amd.core import MoPoE_MMTRSSM, MoPoE_MRSSM, WeightedMoPoE_MMTRSSM, WeightedMoPoE_MRSSM
 from multimodal_mtrssm_amd.dataset import DeviceEpisodeLoader, EpisodeBatch, EpisodeDataModule, EpisodeDataModuleConfig
 from multimodal_mtrssm_amd.distributions import (
     Distribution,
@@ -20,6 +20,7 @@ from multimodal_mtrssm_amd.distributions import (
     stack_distribution,
 )
 from multimodal_mtrssm_amd.dropout import ModalityDropout
+from multimodal_mtrssm_amd.experts import ExpertWeights
 from multimodal_mtrssm_amd.forecast import Forecast
 from multimodal_mtrssm_amd.factory import make_mmtrssm, make_mrssm
 from multimodal_mtrssm_amd.networks import MLP, MTRNN, Representation, Transition
@@ -33,8 +34,8 @@ from multimodal_mtrssm_amd.state import MTState, State, cat_mtstates, cat_states
 __version__ = "0.1.0"
 
 __all__ = [
-    "MLP", "MTRNN", "Decoder", "DeviceEpisodeLoader", "Distribution", "Encoder", "EpisodeBatch", "EpisodeDataModule", "ElboSchedule", "EpisodeDataModuleConfig", "FlatAdamW", "FlatDataParallel", "Forecast", "ForecastSkill", "GlobalRowNoise", "MTState", "MoPoE_MMTRSSM",
-    "MoPoE_MRSSM", "ModalityDropout", "MultiOneHot", "MultiOneHotFactory", "ReduceLROnPlateau", "Representation", "SkillTable", "State", "StateCarry", "Transition", "cat_distribution",
+    "MLP", "MTRNN", "Decoder", "DeviceEpisodeLoader", "Distribution", "Encoder", "EpisodeBatch", "EpisodeDataModule", "ElboSchedule", "EpisodeDataModuleConfig", "ExpertWeights", "FlatAdamW", "FlatDataParallel", "Forecast", "ForecastSkill", "GlobalRowNoise", "MTState", "MoPoE_MMTRSSM",
+    "MoPoE_MRSSM", "ModalityDropout", "MultiOneHot", "MultiOneHotFactory", "ReduceLROnPlateau", "Representation", "SkillTable", "State", "StateCarry", "Transition", "WeightedMoPoE_MMTRSSM", "WeightedMoPoE_MRSSM", "cat_distribution",
     "cat_mtstates", "cat_states", "inject_uniforms", "kl_divergence", "likelihood", "load_reference_checkpoint", "make_mmtrssm", "make_mrssm",
     "stack_distribution", "stack_mtstates", "stack_states",
 ]

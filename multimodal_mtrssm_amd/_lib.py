@@ -41,14 +41,14 @@ MrssmFwdWeights = _struct("MtrssmMrssmFwdWeights", _ptrs(
 MrssmFwdIO = _struct("MtrssmMrssmFwdIO", _ptrs(
     "xa", "pa", "pv", "deter0", "stoch0", "u_post", "u_prior",
     "deter", "prior_logits", "prior_stoch", "post_logits", "post_stoch", "kl",
-    "sv_h1", "sv_h2", "sv_gates", "sv_heads", "sv_la", "sv_lv", "modality"))
+    "sv_h1", "sv_h2", "sv_gates", "sv_heads", "sv_la", "sv_lv", "expert_logw", "modality"))
 MrssmClusterWeights = _struct("MtrssmMrssmClusterWeights", _ptrs(
     "w1s_t", "wf_t", "bf", "whh_t", "bhh", "wh1_t", "b3", "w4", "b4", "wa2", "ba2", "wv2", "bv2"))
 MrssmBwdWeights = _struct("MtrssmMrssmBwdWeights", _ptrs("w1s_t", "w2", "wih", "whh", "wh1", "w4", "wa2", "wv2"))
 MrssmBwdIO = _struct("MtrssmMrssmBwdIO", _ptrs(
     "deter0", "deter", "prior_logits", "post_logits", "sv_h1", "sv_h2", "sv_gates", "sv_heads", "sv_la", "sv_lv",
     "g_deter", "g_post_stoch", "g_prior_stoch", "g_post_logits", "g_prior_logits", "g_kl",
-    "g_deter0", "g_stoch0", "d_z1", "d_h2", "d_gi", "d_gh", "d_zh", "d_lp", "d_la", "d_lv", "modality"))
+    "g_deter0", "g_stoch0", "d_z1", "d_h2", "d_gi", "d_gh", "d_zh", "d_lp", "d_la", "d_lv", "expert_logw", "g_expert_logw", "modality"))
 
 MmtrssmDims = _struct("MtrssmMmtrssmDims", [
     ("B", _i), ("T", _i), ("LD", _i), ("HD", _i), ("H", _i), ("KL", _i), ("CL", _i), ("KH", _i), ("CH", _i),
@@ -63,7 +63,7 @@ MmtrssmFwdIO = _struct("MtrssmMmtrssmFwdIO", _ptrs(
     "u_post_l", "u_post_h", "u_prior_l", "u_prior_h",
     "deter_l", "deter_h", "hidden_l", "hidden_h", "prior_logits_l", "prior_logits_h", "prior_stoch_l", "prior_stoch_h",
     "post_logits_l", "post_logits_h", "post_stoch_l", "post_stoch_h", "kl_l", "kl_h",
-    "sv_l1", "sv_h1", "sv_la", "sv_lv", "modality"))
+    "sv_l1", "sv_h1", "sv_la", "sv_lv", "expert_logw", "modality"))
 MmtrssmBwdWeights = _struct("MtrssmMmtrssmBwdWeights", _ptrs(
     "wxl_s_t", "wdl", "wxh_t", "wdh", "wl1", "wh1", "wlp2", "wa2", "wv2", "whp2", "whq2"))
 MmtrssmBwdIO = _struct("MtrssmMmtrssmBwdIO", _ptrs(
@@ -72,7 +72,7 @@ MmtrssmBwdIO = _struct("MtrssmMmtrssmBwdIO", _ptrs(
     "g_deter_l", "g_deter_h", "g_hidden_l", "g_hidden_h", "g_post_stoch_l", "g_post_stoch_h", "g_prior_stoch_l",
     "g_prior_stoch_h", "g_post_logits_l", "g_post_logits_h", "g_prior_logits_l", "g_prior_logits_h", "g_kl_l", "g_kl_h",
     "g_deter_l0", "g_deter_h0", "g_hidden_l0", "g_hidden_h0", "g_stoch_l0", "g_stoch_h0",
-    "d_ul", "d_uh", "d_zl1", "d_zh1", "d_lpl", "d_la", "d_lv", "d_lph", "d_lqh", "modality"))
+    "d_ul", "d_uh", "d_zl1", "d_zh1", "d_lpl", "d_la", "d_lv", "d_lph", "d_lqh", "expert_logw", "g_expert_logw", "modality"))
 
 ConvGeom = _struct("MtrssmConvGeom", [(n, _i) for n in (
     "N", "C", "Hs", "Ws", "C2", "Cpad", "KH", "KW", "SS", "TS", "OFFY", "OFFX", "Hq", "Wq", "OS", "QY", "QX", "Ho", "Wo",

@@ -23,6 +23,7 @@ from multimodal_mtrssm_amd import cnn, conv, scan
 from multimodal_mtrssm_amd.carry import StateCarry
 from multimodal_mtrssm_amd.distributions import MultiOneHot, MultiOneHotFactory, draw_uniforms, kl_divergence, onehot_from_uniforms
 from multimodal_mtrssm_amd.dropout import ModalityDropout, StepMask, ragged_step_mask
+from multimodal_mtrssm_amd.experts import ExpertWeights
 from multimodal_mtrssm_amd.forecast import Forecast
 from multimodal_mtrssm_amd.networks import MTRNN, Representation, Transition
 from multimodal_mtrssm_amd.objective import likelihood
@@ -416,6 +417,11 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         self.elbo_schedule: ElboSchedule | None = None  # training_step (never validation_step) weighs the loss terms with it
         self.val_skill: ForecastSkill | None = None  # validation_step adds a skill step into self.skill_table
         self.skill_table: SkillTable | None = None  # ... logged as val/skill/* and cleared by on_validation_epoch_end
+        # weighted MoPoE: assign an ExpertWeights (a submodule: before FlatParameters is built); None = 1/3 each, no new
+        # state-dict keys.  After every posterior rollout with weights, weights_timeseries is ExpertWeights.table(...) [B, T, 3]
+        self.expert_weights: ExpertWeights | None = None
+        self.weights_timeseries: Tensor | None = None
+        self._weights_both: Tensor | None = None  # bool [B, T]: where weights_timeseries belongs to a step with both modalities
 
     # -- batch accessors (mrssm core.py:310-355) --------------------------------------------
     @staticmethod
@@ -541,10 +547,13 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         return shapes
 
     def _rollout_embedded(self, actions: Tensor, audio_embed: Tensor | None, vision_embed: Tensor | None, prev_state: State,  # noqa: PLR0913
-                          noise: Noise | None, *, sample_prior: bool, modality: Tensor | None = None) -> dict[str, Tensor]:
+                          noise: Noise | None, *, sample_prior: bool, modality: Tensor | None = None,
+                          expert_log_weights: Tensor | None = None) -> dict[str, Tensor]:
         noise = noise or {}
         B, T = actions.shape[:2]
         K = self.transition.distribution_factory.category_size
+        logw = self._expert_logw(audio_embed, vision_embed, expert_log_weights, B, T)
+        self._report_weights(logw, modality, B, T, actions.device)
         u_post = noise.get("u_post")
         u_prior = noise.get("u_prior")
         if u_post is None:
@@ -554,8 +563,29 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         return scan.mrssm_posterior_rollout(
             self.transition, self.audio_representation, self.vision_representation, actions, audio_embed, vision_embed,
             prev_state.deter, prev_state.stoch, u_post, u_prior, balancing=bool(self.use_kl_balancing),
-            rows_per_block=self.scan_rows_per_block, threads=self.scan_threads, modality=modality,
+            rows_per_block=self.scan_rows_per_block, threads=self.scan_threads, modality=modality, expert_logw=logw,
         )
+
+    def _expert_logw(self, audio_embed: Tensor | None, vision_embed: Tensor | None, explicit: Tensor | None, B: int, T: int) -> Tensor | None:  # noqa: N803, PLR0913
+        """The scan's expert log-weights ``[B, T, 3]``: ``explicit`` ones, else the model's gate on the two embeddings, else None (1/3
+        each).  A modality that is absent at every step (None) leaves no step with both: the gate is not run."""
+        if audio_embed is None or vision_embed is None:
+            return None
+        if explicit is not None:
+            return scan.check_expert_logw(explicit, B, T)
+        if self.expert_weights is None:
+            return None
+        return self.expert_weights(audio_embed, vision_embed)
+
+    def _report_weights(self, logw: Tensor | None, codes: Tensor | None, B: int, T: int, device: torch.device) -> None:  # noqa: N803, PLR0913
+        """``weights_timeseries`` of a weighted rollout (detached; a model without weights keeps None)."""
+        if logw is None and self.expert_weights is None:
+            return
+        with torch.no_grad():
+            if codes is None:
+                codes = torch.full((B, T), 3, device=device, dtype=torch.int32)
+            self._weights_both = (codes & 3) == 3  # noqa: PLR2004
+            self.weights_timeseries = ExpertWeights.table(logw, codes & 3)
 
     def _posterior_from_rollout(self, out: dict[str, Tensor]) -> State:
         post = State(deter=out["deter"], distribution=self.audio_representation.distribution_factory(out["post_logits"]), stoch=out["post_stoch"])
@@ -576,13 +606,16 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         noise: Noise | None = None,
         modality_mask: Tensor | None = None,
         lengths: Tensor | None = None,
+        expert_log_weights: Tensor | None = None,
     ) -> tuple[State, State]:
         """``mrssm core.py:184-260``: returns (mixed posterior, prior), each ``[B, T, .]``.
 
         ``modality_mask``: optional bool ``[B, T, 2]`` (audio, vision), True = observed.  At each (b, t) the posterior mixes
         the present modalities only; with none present it is the prior (DESIGN.md "Missing modalities").  An entry of
         ``observations`` may be None: that modality is absent at every step and its encoder is not run.  ``lengths`` (int32 ``[B]`` on
-        the device) instead of a mask: both modalities on a row's first ``lengths[b]`` steps, none after."""
+        the device) instead of a mask: both modalities on a row's first ``lengths[b]`` steps, none after.  ``expert_log_weights``
+        (fp32 ``[B, T, 3]``): explicit log-weights of the (audio, vision, fused) experts where both are
+        present, instead of ``self.expert_weights``' (analysis, tests)."""
         if not isinstance(observations, tuple):
             msg = "MoPoE-MRSSM requires tuple of (audio_obs, vision_obs)"
             raise TypeError(msg)
@@ -591,7 +624,8 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         codes = self._rollout_codes(observations, modality_mask, lengths, B, T, actions.device)
         audio_embed = None if audio_obs is None else self.audio_encoder(audio_obs)
         vision_embed = None if vision_obs is None else self.vision_encoder(vision_obs)
-        out = self._rollout_embedded(actions, audio_embed, vision_embed, prev_state, noise, sample_prior=True, modality=codes)
+        out = self._rollout_embedded(actions, audio_embed, vision_embed, prev_state, noise, sample_prior=True, modality=codes,
+                                     expert_log_weights=expert_log_weights)
         return self._states_from_rollout(out)
 
     @staticmethod
@@ -648,7 +682,7 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
 
     @torch.no_grad()
     def forecast_skill(self, batch: tuple[Tensor, ...], skill: ForecastSkill, noise: Noise | None = None, lengths: Tensor | None = None,  # noqa: PLR0913, PLR0914
-                       table: SkillTable | None = None, *, keep_states: bool = False) -> SkillTable:
+                       table: SkillTable | None = None, *, keep_states: bool = False, expert_log_weights: Tensor | None = None) -> SkillTable:
         """One skill step: observe ``skill.context`` frames (of ``skill.observe``), roll ``skill.samples`` sampled
         futures per row open loop in ONE masked posterior rollout over ``B * S`` rows (row ``b * S + s``; the copies of a row share
         ``noise["u_post"]`` on the context and read ``noise["u_tail"][b, s]`` after it), decode, and score every live frame of both
@@ -656,7 +690,9 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         which is returned.  ``best`` is the best sample per FRAME.  ``lengths`` (or a batch that carries ``valid_global``) as in
         ``forecast_rollout``: nothing is observed or scored at or past a row's end.  ``keep_states``: ``table.states`` is the posterior
         state sequence ``[B * S, T, .]`` and ``table.planes`` the step's score planes ``[8, B, T]``.  Every row starts from its own
-        frame 0: no masked (7-tuple) batch, no ``state_carry``."""
+        frame 0: no masked (7-tuple) batch, no ``state_carry``.  A weighted model runs its gate once per row and
+        repeats the weights for the row's copies; ``expert_log_weights`` (fp32 ``[B, T, 3]``, or ``[B * S, T, 3]`` already repeated)
+        gives them explicitly."""
         if not isinstance(skill, ForecastSkill):
             msg = f"skill must be a ForecastSkill, got {type(skill).__name__}"
             raise ValueError(msg)
@@ -697,7 +733,13 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
             u_post = _rand(actions, B, T, k) if u_post is None else u_post
             u_tail = _rand(actions, B, S, T, k) if u_tail is None else u_tail
             noise[key] = skill.compose_noise(u_post, u_tail)
-        out = self._rollout_embedded(wide(actions), wide(audio_embed), wide(vision_embed), state0, noise, sample_prior=False, modality=wide(codes))
+        if expert_log_weights is not None and expert_log_weights.shape[0] == B * S:
+            logw = expert_log_weights  # (checked by the rollout)
+        else:
+            logw = self._expert_logw(audio_embed, vision_embed, expert_log_weights, B, T)  # the gate once per row ...
+            logw = None if logw is None else wide(logw)  # ... repeated for its S copies
+        out = self._rollout_embedded(wide(actions), wide(audio_embed), wide(vision_embed), state0, noise, sample_prior=False, modality=wide(codes),
+                                     expert_log_weights=logw)
         feature = self._feature_of(out)
         da, dv = self.audio_decoder, self.vision_decoder
         fused = isinstance(da, cnn.Decoder) and isinstance(dv, cnn.Decoder) and da.out_act_id is not None and dv.out_act_id is not None
@@ -858,7 +900,8 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
     def shared_step(self, batch: tuple[Tensor, ...], noise: Noise | None = None, modality_mask: Tensor | None = None,  # noqa: PLR0913
                     modality_dropout: ModalityDropout | None = None, state_carry: StateCarry | None = None,
                     reset: Tensor | None = None, *, carry_prefix: str = "train", lengths: Tensor | None = None,
-                    forecast: Forecast | None = None, elbo_schedule: ElboSchedule | None = None) -> dict[str, Tensor]:
+                    forecast: Forecast | None = None, elbo_schedule: ElboSchedule | None = None,
+                    expert_log_weights: Tensor | None = None) -> dict[str, Tensor]:
         """``core.py:187-221``: ``loss = recon + kl_coeff * KL(post || prior)`` (MMTRSSM, ``mmtrssm core.py:563-606``:
         ``recon + kl_coeff KL_l + kl_coeff w_kl_h KL_h``).  ``modality_mask`` (or a 7th batch entry, bool ``[B, T, 2]``): each
         recon term averages over the frames where its modality is present; the KL stays the mean over all B*T (0 on steps with
@@ -884,7 +927,10 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         ``elbo_schedule`` (an ``ElboSchedule``): free nats per step, a beta warm-up and per-modality weights in the
         scalar epilogue, with every option above.  ``kl`` (``kl_h``) is then the clipped, beta-weighted term and ``recon`` the weighted
         sum, so ``loss = recon + kl (+ kl_h)`` still holds; ``recon/audio`` and ``recon/vision`` stay unweighted; the dict gains ``kl_raw``
-        (``kl_h_raw``), the unscheduled term, after the existing keys."""
+        (``kl_h_raw``), the unscheduled term, after the existing keys.
+
+        ``expert_log_weights``: explicit expert log-weights as in ``rollout_representation``; a weighted model
+        (``self.expert_weights``) needs none, its gate runs inside the step."""
         if forecast is not None:
             if modality_mask is not None or self.get_modality_mask_from_batch(batch) is not None:
                 msg = "forecast= decides what the model observes: a modality_mask (or a 7-tuple batch) already says what is seen, give one of them"
@@ -892,15 +938,17 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
             if state_carry is not None:
                 msg = "forecast= does not combine with state_carry: the state a forecast step ends with is an open-loop state, not one to continue from"
                 raise ValueError(msg)
-            return self._elbo_step(batch, noise, self._forecast_step_mask(batch, noise, forecast, modality_dropout, lengths), schedule=elbo_schedule)
+            return self._elbo_step(batch, noise, self._forecast_step_mask(batch, noise, forecast, modality_dropout, lengths), schedule=elbo_schedule,
+                                   expert_log_weights=expert_log_weights)
         reset_host = None  # without a carry every row starts from its fresh state: every row resets
         if state_carry is not None:
             reset_host = getattr(batch, "reset_host", None) if reset is None else (None if reset.is_cuda else reset)
         on_device = state_carry is not None and isinstance(reset, Tensor) and reset.is_cuda  # (trusted, as the carry trusts it)
         sm = self._step_mask(batch, noise, modality_mask, modality_dropout, lengths, reset_host, trust_reset=on_device)
         if state_carry is None:
-            return self._elbo_step(batch, noise, sm, schedule=elbo_schedule)
-        return self._elbo_step(batch, noise, sm, self._carry_of(batch, state_carry, reset, carry_prefix), schedule=elbo_schedule)
+            return self._elbo_step(batch, noise, sm, schedule=elbo_schedule, expert_log_weights=expert_log_weights)
+        return self._elbo_step(batch, noise, sm, self._carry_of(batch, state_carry, reset, carry_prefix), schedule=elbo_schedule,
+                               expert_log_weights=expert_log_weights)
 
     @staticmethod
     def _carry_of(batch: tuple[Tensor, ...], state_carry: StateCarry, reset: Tensor | None, prefix: str) -> tuple[StateCarry, str, Tensor]:
@@ -945,7 +993,8 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
             carry[0].save(carry[1], {k: out[v] for k, v in self._LAST_KEYS.items()}, last)
 
     def _elbo_step(self, batch: tuple[Tensor, ...], noise: Noise | None, sm: StepMask | None,
-                   carry: tuple[StateCarry, str, Tensor] | None = None, schedule: ElboSchedule | None = None) -> dict[str, Tensor]:
+                   carry: tuple[StateCarry, str, Tensor] | None = None, schedule: ElboSchedule | None = None,
+                   expert_log_weights: Tensor | None = None) -> dict[str, Tensor]:
         """``shared_step`` behind the mask handling (the captured step enters here with a mask it validated itself)."""
         action_input = batch[0]
         audio_obs, vision_obs = self.get_observations_from_batch(batch)
@@ -956,7 +1005,7 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
                                           u_init)
         state0 = self._state0(state0, carry)
         out = self._rollout_embedded(action_input, audio_embed, vision_embed, state0, noise, sample_prior=False,
-                                     modality=None if sm is None else sm.codes)
+                                     modality=None if sm is None else sm.codes, expert_log_weights=expert_log_weights)
         self._save_carry(out, carry, None if sm is None else sm.last)
         feature = torch.cat([out["deter"], out["post_stoch"]], dim=-1)
         parts = self._reconstruction_losses(feature, self.get_targets_from_batch(batch), sum_recon=False, step_mask=sm)
@@ -992,6 +1041,13 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         forecasts the rest (from the chunk's own frame 0, no carry), logged as ``val/forecast/*``.  ``self.elbo_schedule`` is not used
         here: ``val/loss`` stays the plain ELBO that schedulers and checkpointing monitor."""
         logged = self._step(batch, "val", with_loss_key=False)
+        if self.expert_weights is not None and self.weights_timeseries is not None:
+            # the closed-loop step's reported weights, averaged over the live frames where both modalities are present
+            both = self._weights_both.unsqueeze(-1).to(torch.float32)
+            mean = (self.weights_timeseries * both).sum(dim=(0, 1)) / both.sum().clamp(min=1.0)
+            weights = {f"val/weights/{name}": mean[i] for i, name in enumerate(("audio", "vision", "fused"))}
+            self.log_dict(weights, prog_bar=False, sync_dist=True, on_step=False, on_epoch=True)
+            logged.update(weights)
         if self.val_forecast is not None:
             fore = {f"val/forecast/{k}": v for k, v in self.shared_step(batch, forecast=self.val_forecast).items()}
             self.log_dict(fore, prog_bar=False, sync_dist=True, on_step=False, on_epoch=True)
@@ -1098,9 +1154,11 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
 
     def _rollout_embedded(self, actions: Tensor, audio_embed: Tensor | None, vision_embed: Tensor | None,  # type: ignore[override]  # noqa: PLR0913
                           prev_state: MTState, noise: Noise | None, *, sample_prior: bool,
-                          modality: Tensor | None = None) -> dict[str, Tensor]:
+                          modality: Tensor | None = None, expert_log_weights: Tensor | None = None) -> dict[str, Tensor]:
         noise = dict(noise or {})
         B, T = actions.shape[:2]
+        logw = self._expert_logw(audio_embed, vision_embed, expert_log_weights, B, T)
+        self._report_weights(logw, modality, B, T, actions.device)
         KL, KH = self.l_dist.category_size, self.h_dist.category_size
         for key, k in (("u_post_l", KL), ("u_post_h", KH)):
             if noise.get(key) is None:
@@ -1110,7 +1168,8 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
                 if noise.get(key) is None:
                     noise[key] = _rand(actions, B, T, k)
         return scan.mmtrssm_posterior_rollout(self, actions, audio_embed, vision_embed, self._state_dict_of(prev_state), noise,
-                                              rows_per_block=self.scan_rows_per_block, threads=self.scan_threads, modality=modality)
+                                              rows_per_block=self.scan_rows_per_block, threads=self.scan_threads, modality=modality,
+                                              expert_logw=logw)
 
     def _posterior_from_rollout(self, out: dict[str, Tensor]) -> MTState:  # type: ignore[override]
         post = MTState(distribution_h=self.h_dist(out["post_logits_h"]), distribution_l=self.l_dist(out["post_logits_l"]),
@@ -1134,13 +1193,16 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
         noise: Noise | None = None,
         modality_mask: Tensor | None = None,
         lengths: Tensor | None = None,
+        expert_log_weights: Tensor | None = None,
     ) -> tuple[MTState, MTState]:
         """``mmtrssm core.py:364-494``.
 
         ``modality_mask``: optional bool ``[B, T, 2]`` (audio, vision), True = observed.  At each (b, t) the posterior mixes
         the present modalities only; with none present it is the prior (DESIGN.md "Missing modalities").  An entry of
         ``observations`` may be None: that modality is absent at every step and its encoder is not run.  ``lengths`` (int32 ``[B]`` on
-        the device) instead of a mask: both modalities on a row's first ``lengths[b]`` steps, none after."""
+        the device) instead of a mask: both modalities on a row's first ``lengths[b]`` steps, none after.  ``expert_log_weights``
+        (fp32 ``[B, T, 3]``): explicit log-weights of the (audio, vision, fused) experts where both are
+        present, instead of ``self.expert_weights``' (analysis, tests)."""
         if not isinstance(observations, tuple):
             msg = "MoPoE-MMTRSSM requires tuple of (audio_obs, vision_obs)"
             raise TypeError(msg)
@@ -1149,7 +1211,8 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
         codes = self._rollout_codes(observations, modality_mask, lengths, B, T, actions.device)
         audio_embed = None if audio_obs is None else self.audio_encoder(audio_obs)
         vision_embed = None if vision_obs is None else self.vision_encoder(vision_obs)
-        out = self._rollout_embedded(actions, audio_embed, vision_embed, prev_state, noise, sample_prior=True, modality=codes)
+        out = self._rollout_embedded(actions, audio_embed, vision_embed, prev_state, noise, sample_prior=True, modality=codes,
+                                     expert_log_weights=expert_log_weights)
         return self._states_from_rollout(out)
 
     def rollout_transition(self, *, actions: Tensor, prev_state: MTState, noise: Noise | None = None) -> MTState:  # type: ignore[override]
@@ -1183,7 +1246,8 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
         return MTState(distribution_h=fresh.distribution_h, distribution_l=fresh.distribution_l, **got)
 
     def _elbo_step(self, batch: tuple[Tensor, ...], noise: Noise | None, sm: StepMask | None,
-                   carry: tuple[StateCarry, str, Tensor] | None = None, schedule: ElboSchedule | None = None) -> dict[str, Tensor]:
+                   carry: tuple[StateCarry, str, Tensor] | None = None, schedule: ElboSchedule | None = None,
+                   expert_log_weights: Tensor | None = None) -> dict[str, Tensor]:
         """``mmtrssm core.py:563-606``: ``loss = recon + kl_coeff KL_l + kl_coeff w_kl_h KL_h`` (``shared_step``'s body)."""
         action_input = batch[0]
         audio_obs, vision_obs = self.get_observations_from_batch(batch)
@@ -1193,7 +1257,7 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
                                           noise)
         state0 = self._state0(state0, carry)
         out = self._rollout_embedded(action_input, audio_embed, vision_embed, state0, noise, sample_prior=False,
-                                     modality=None if sm is None else sm.codes)
+                                     modality=None if sm is None else sm.codes, expert_log_weights=expert_log_weights)
         self._save_carry(out, carry, None if sm is None else sm.last)
         feature = torch.cat([out["deter_h"], out["post_stoch_h"], out["deter_l"], out["post_stoch_l"]], dim=-1)
         parts = self._reconstruction_losses(feature, self.get_targets_from_batch(batch), sum_recon=False, step_mask=sm)
@@ -1205,4 +1269,25 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
         return {"recon": recon, **parts, "kl": kl_div_l, "kl_h": kl_div_h, "loss": loss}
 
 
-__all__ = ["MoPoE_MMTRSSM", "MoPoE_MRSSM", "check_ragged_rows", "kl_divergence"]
+def _gate_for(model: MoPoE_MRSSM, mode: str) -> ExpertWeights:
+    return ExpertWeights(mode, model.audio_representation.obs_embed_size if mode == "gated" else None)
+
+
+class WeightedMoPoE_MRSSM(MoPoE_MRSSM):  # noqa: N801
+    """``MoPoE_MRSSM`` with learned weights of the (audio, vision, fused) experts: the class a YAML names,
+    ``init_args`` gaining ``expert_weights: gated`` (a gate on the two embeddings of a frame) or ``static`` (one learned triple)."""
+
+    def __init__(self, *, expert_weights: str = "gated", **kw) -> None:  # noqa: ANN003
+        super().__init__(**kw)
+        self.expert_weights = _gate_for(self, expert_weights)
+
+
+class WeightedMoPoE_MMTRSSM(MoPoE_MMTRSSM):  # noqa: N801
+    """``MoPoE_MMTRSSM`` with learned expert weights on the lower level's mixture; ``expert_weights`` as ``WeightedMoPoE_MRSSM``."""
+
+    def __init__(self, *, expert_weights: str = "gated", **kw) -> None:  # noqa: ANN003
+        super().__init__(**kw)
+        self.expert_weights = _gate_for(self, expert_weights)
+
+
+__all__ = ["MoPoE_MMTRSSM", "MoPoE_MRSSM", "WeightedMoPoE_MMTRSSM", "WeightedMoPoE_MRSSM", "check_ragged_rows", "kl_divergence"]

@@ -138,20 +138,44 @@ int device_cu_count() {
 using namespace mtrssm;
 #define MTRSSM_API extern "C" __attribute__((visibility("default")))
 
+// expert_logw (weighted MoPoE) is read by the masked scan instances only: it needs the modality codes (all "both" when nothing is
+// missing).  A prior-only rollout has no mixture and ignores the field.
+template <typename IO>
+static bool expert_logw_ok(const IO* io, bool post, const char* entry) {
+  if (io && post && io->expert_logw && !io->modality) {
+    set_error("%s: expert_logw needs modality (pass code 3 everywhere when no modality is missing)", entry);
+    return false;
+  }
+  return true;
+}
+template <typename IO>
+static bool g_expert_logw_ok(const IO* io, const char* entry) {
+  if (!expert_logw_ok(io, true, entry)) return false;
+  if (io && io->g_expert_logw && !io->expert_logw) {
+    set_error("%s: g_expert_logw needs expert_logw", entry);
+    return false;
+  }
+  return true;
+}
+
 MTRSSM_API int mtrssm_version(void) { return MTRSSM_VERSION; }
 MTRSSM_API const char* mtrssm_last_error(void) { return g_err; }
 MTRSSM_API const char* mtrssm_last_kernel(void) { return g_kernel; }
 
 MTRSSM_API int mtrssm_mrssm_rollout_fwd(const MtrssmMrssmDims* d, const MtrssmMrssmFwdWeights* w, const MtrssmMrssmFwdIO* io, void* stream) {
+  if (!expert_logw_ok(io, d && d->post, "mrssm_rollout_fwd")) return MTRSSM_EINVAL;
   return mrssm_fwd_launch(d, w, io, static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int mtrssm_mrssm_rollout_bwd(const MtrssmMrssmDims* d, const MtrssmMrssmBwdWeights* w, const MtrssmMrssmBwdIO* io, void* stream) {
+  if (!g_expert_logw_ok(io, "mrssm_rollout_bwd")) return MTRSSM_EINVAL;
   return mrssm_bwd_launch(d, w, io, static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int mtrssm_mmtrssm_rollout_fwd(const MtrssmMmtrssmDims* d, const MtrssmMmtrssmFwdWeights* w, const MtrssmMmtrssmFwdIO* io, void* stream) {
+  if (!expert_logw_ok(io, d && d->post, "mmtrssm_rollout_fwd")) return MTRSSM_EINVAL;
   return mmtrssm_fwd_launch(d, w, io, static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int mtrssm_mmtrssm_rollout_bwd(const MtrssmMmtrssmDims* d, const MtrssmMmtrssmBwdWeights* w, const MtrssmMmtrssmBwdIO* io, void* stream) {
+  if (!g_expert_logw_ok(io, "mmtrssm_rollout_bwd")) return MTRSSM_EINVAL;
   return mmtrssm_bwd_launch(d, w, io, static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int mtrssm_categorical_sample_fwd(const float* logits, const float* u, int64_t rows, int32_t K, int32_t C, float* logp, float* probs,
@@ -207,6 +231,7 @@ MTRSSM_API int mtrssm_mrssm_cluster_supported(const MtrssmMrssmDims* d) { return
 MTRSSM_API int64_t mtrssm_mrssm_cluster_workspace_bytes(const MtrssmMrssmDims* d) { return (int64_t)mrssm_cluster_workspace_bytes(d); }
 MTRSSM_API int mtrssm_mrssm_rollout_fwd_cluster(const MtrssmMrssmDims* d, const MtrssmMrssmClusterWeights* w, const MtrssmMrssmFwdIO* io,
                                                 void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!expert_logw_ok(io, true, "mrssm_rollout_fwd_cluster")) return MTRSSM_EINVAL;
   return mrssm_fwd_cluster_launch(d, w, io, workspace, workspace_bytes < 0 ? 0 : (size_t)workspace_bytes, static_cast<hipStream_t>(stream));
 }
 /* development aid, not part of the documented ABI (tools/cluster_probe.py) */
@@ -217,6 +242,7 @@ extern "C" __attribute__((visibility("default"))) int mtrssm_debug_set_mmt_profi
 MTRSSM_API int64_t mtrssm_mrssm_cluster_bwd_workspace_bytes(const MtrssmMrssmDims* d) { return (int64_t)mrssm_cluster_bwd_workspace_bytes(d); }
 MTRSSM_API int mtrssm_mrssm_rollout_bwd_cluster(const MtrssmMrssmDims* d, const MtrssmMrssmClusterWeights* w, const MtrssmMrssmBwdIO* io,
                                                 void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!g_expert_logw_ok(io, "mrssm_rollout_bwd_cluster")) return MTRSSM_EINVAL;
   return mrssm_bwd_cluster_launch(d, w, io, workspace, workspace_bytes < 0 ? 0 : (size_t)workspace_bytes, static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int mtrssm_mrssm_wide_supported(const MtrssmMrssmDims* d, int32_t pieces) { return mrssm_wide_supported(d, pieces); }
@@ -226,10 +252,12 @@ MTRSSM_API int64_t mtrssm_mrssm_wide_bwd_workspace_bytes(const MtrssmMrssmDims* 
 }
 MTRSSM_API int mtrssm_mrssm_rollout_fwd_wide(const MtrssmMrssmDims* d, const MtrssmMrssmClusterWeights* w, const MtrssmMrssmFwdIO* io, int32_t pieces,
                                              void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!expert_logw_ok(io, true, "mrssm_rollout_fwd_wide")) return MTRSSM_EINVAL;
   return mrssm_wide_fwd_launch(d, w, io, pieces, workspace, workspace_bytes < 0 ? 0 : (size_t)workspace_bytes, static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int mtrssm_mrssm_rollout_bwd_wide(const MtrssmMrssmDims* d, const MtrssmMrssmClusterWeights* w, const MtrssmMrssmBwdIO* io, int32_t pieces,
                                              void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!g_expert_logw_ok(io, "mrssm_rollout_bwd_wide")) return MTRSSM_EINVAL;
   return mrssm_wide_bwd_launch(d, w, io, pieces, workspace, workspace_bytes < 0 ? 0 : (size_t)workspace_bytes, static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int mtrssm_mmtrssm_wide_supported(const MtrssmMmtrssmDims* d, int32_t pieces) { return mmtrssm_wide_supported(d, pieces); }
@@ -239,10 +267,12 @@ MTRSSM_API int64_t mtrssm_mmtrssm_wide_bwd_workspace_bytes(const MtrssmMmtrssmDi
 }
 MTRSSM_API int mtrssm_mmtrssm_rollout_fwd_wide(const MtrssmMmtrssmDims* d, const MtrssmMmtrssmFwdWeights* w, const MtrssmMmtrssmFwdIO* io, int32_t pieces,
                                                void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!expert_logw_ok(io, true, "mmtrssm_rollout_fwd_wide")) return MTRSSM_EINVAL;
   return mmtrssm_wide_fwd_launch(d, w, io, pieces, workspace, workspace_bytes < 0 ? 0 : (size_t)workspace_bytes, static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int mtrssm_mmtrssm_rollout_bwd_wide(const MtrssmMmtrssmDims* d, const MtrssmMmtrssmBwdWeights* w, const MtrssmMmtrssmBwdIO* io, int32_t pieces,
                                                void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!g_expert_logw_ok(io, "mmtrssm_rollout_bwd_wide")) return MTRSSM_EINVAL;
   return mmtrssm_wide_bwd_launch(d, w, io, pieces, workspace, workspace_bytes < 0 ? 0 : (size_t)workspace_bytes, static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int mtrssm_gemm(const MtrssmGemm* g, void* stream) { return gemm_launch(g, static_cast<hipStream_t>(stream)); }

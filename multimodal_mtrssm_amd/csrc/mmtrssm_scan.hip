@@ -153,7 +153,7 @@ __global__ __launch_bounds__(1024) void mmtrssm_fwd_kernel(const MtrssmMmtrssmDi
       const size_t q = bt[rb];
       const bool ok = valid[rb];
       const int code = modality_code<MASKED>(io.modality, q);
-      if (POST) wave_mopoe_mix_masked<false, MASKED>(r + L.la, r + L.lv, r + L.lpl, r + L.mx, LS, lane, code);
+      if (POST) wave_mopoe_mix_masked<false, MASKED>(r + L.la, r + L.lv, r + L.lpl, r + L.mx, LS, lane, code, expert_logw<MASKED>(io.expert_logw, q));
       if (POST && MASKED && code == 0) wave_copy(r + L.lph, r + L.lqh, HS, lane);  // no modality: higher posterior = prior
       if (ok) {
         for (int s = lane; s < LS; s += kWave) {
@@ -278,7 +278,10 @@ __global__ __launch_bounds__(1024) void mmtrssm_bwd_kernel(const MtrssmMmtrssmDi
                     dm.kl_w_post, dm.kl_w_prior, r + L.dlqh, r + L.dlph);
       const int code = modality_code<MASKED>(io.modality, q);
       if (MASKED && code == 0) wave_route_to_prior(r + L.dlqh, r + L.dlph, HS, lane);
-      wave_mopoe_mix_bwd_masked<false, MASKED>(r + L.la, r + L.lv, r + L.mx, r + L.dmx, r + L.dla, r + L.dlv, r + L.dlpl, LS, lane, code);
+      const ExpertLogW g_lw =
+          wave_mopoe_mix_bwd_masked<false, MASKED>(r + L.la, r + L.lv, r + L.mx, r + L.dmx, r + L.dla, r + L.dlv, r + L.dlpl, LS, lane, code,
+                                                   expert_logw<MASKED>(io.expert_logw, q), MASKED && io.expert_logw != nullptr);
+      if (MASKED) store_g_expert_logw(io.g_expert_logw, q, g_lw, lane, valid[rb]);
       if (valid[rb]) {
         for (int s = lane; s < LS; s += kWave) {
           io.d_lpl[q * LS + s] = r[L.dlpl + s];

@@ -122,6 +122,7 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_fwd_kernel(const MmtWideFwdA
         if (t > 0) {
           const size_t q = b * T + (t - 1);
           const int code = modality_code<MASKED>(io.modality, q);
+          const ExpertLogW lw = expert_logw<MASKED>(io.expert_logw, q);
           if (wave == 0) {
             if (lane < KL) { Lu[lane] = io.u_post_l[q * KL + lane]; Lu[64 + lane] = io.u_prior_l ? io.u_prior_l[q * KL + lane] : 0.f; }
             if (lane < KH) { Lu[128 + lane] = io.u_post_h[q * KH + lane]; Lu[192 + lane] = io.u_prior_h ? io.u_prior_h[q * KH + lane] : 0.f; }
@@ -141,7 +142,7 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_fwd_kernel(const MmtWideFwdA
           lds_barrier();
           MTRSSM_WIDE_STAMP(10);
           if (wave == 0) {   // lower level: MoPoE mix, categorical block
-            wave_mopoe_mix_masked<true, MASKED>(Lla, Llv, Llpl, Lmx, LS, lane, code);
+            wave_mopoe_mix_masked<true, MASKED>(Lla, Llv, Llpl, Lmx, LS, lane, code, lw);
             for (int s2 = lane; s2 < LS; s2 += kWave) {
               io.prior_logits_l[q * LS + s2] = Llpl[s2];
               io.post_logits_l[q * LS + s2] = Lmx[s2];
@@ -334,6 +335,7 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_bwd_kernel(const MmtWideBwdA
       for (int r = nblk - 1 - blk; r < nrows; r += nblk) {
         const size_t q = (size_t)(rb + r) * T + t;
         const int code = modality_code<MASKED>(io.modality, q);
+        const ExpertLogW lw = expert_logw<MASKED>(io.expert_logw, q);
         for (int s2 = tid; s2 < LS; s2 += kWT) {
           Lla[s2] = io.sv_la[q * LS + s2];
           Llv[s2] = io.sv_lv[q * LS + s2];
@@ -356,7 +358,9 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_bwd_kernel(const MmtWideBwdA
           const float* gprl = io.g_prior_logits_l ? io.g_prior_logits_l + q * LS : nullptr;
           if (CL <= 8) cat_block_bwd_fast8(Lmx, Llpl, KL, CL, lane, Lgps, Lcs, gpsl, gpll, gprl, gkl, a.dm.kl_w_post, a.dm.kl_w_prior, Ldmx, Ldlpl);
           else cat_block_bwd<true>(Lmx, Llpl, KL, CL, lane, Lgps, Lcs, gpsl, gpll, gprl, gkl, a.dm.kl_w_post, a.dm.kl_w_prior, Ldmx, Ldlpl);
-          wave_mopoe_mix_bwd_masked<true, MASKED>(Lla, Llv, Lmx, Ldmx, Ldla, Ldlv, Ldlpl, LS, lane, code);
+          const ExpertLogW g_lw =
+              wave_mopoe_mix_bwd_masked<true, MASKED>(Lla, Llv, Lmx, Ldmx, Ldla, Ldlv, Ldlpl, LS, lane, code, lw, MASKED && io.expert_logw != nullptr);
+          if (MASKED) store_g_expert_logw(io.g_expert_logw, q, g_lw, lane, true);
           MTRSSM_WIDE_STAMP(11);
         } else if (wave == 1) {   // higher level, beside it on another SIMD
           const float gkh = io.g_kl_h ? io.g_kl_h[q] : 0.f;

@@ -177,8 +177,9 @@ __global__ __launch_bounds__(kCluThreads) void mrssm_fwd_cluster_kernel(const Mt
 
     // The streamed inputs of a step (xa, pa / pv of the own head units, the uniforms) are loaded one step AHEAD into registers:
     // loaded at the top of the step that consumes them, their HBM latency (~1 us) sat on the step's critical path.
-    auto load_inputs = [&](size_t q, float& xa_r, float& pa_r, float& up_r, float& ur_r, int& code_r) {
+    auto load_inputs = [&](size_t q, float& xa_r, float& pa_r, float& up_r, float& ur_r, int& code_r, ExpertLogW& lw_r) {
       code_r = modality_code<MASKED>(io.modality, q);  // every member reads its row's code (the mix runs on each of them)
+      lw_r = expert_logw<MASKED>(io.expert_logw, q);   // ... and the step's three expert log-weights (weighted MoPoE)
       xa_r = tid < H ? io.xa[q * H + tid] : 0.f;
       pa_r = 0.f;
       if (tid >= UH && tid < NH) {
@@ -190,15 +191,17 @@ __global__ __launch_bounds__(kCluThreads) void mrssm_fwd_cluster_kernel(const Mt
     };
     float xa_n, pav_n, up_n, ur_n;
     int code_n;
-    load_inputs((size_t)row * T, xa_n, pav_n, up_n, ur_n, code_n);
+    ExpertLogW lw_n;
+    load_inputs((size_t)row * T, xa_n, pav_n, up_n, ur_n, code_n, lw_n);
 
     for (int t = 0; t < T; ++t) {
       const size_t bt = (size_t)row * T + t;
       unsigned long long* gpar = gbase + (size_t)(t & 1) * per_parity;
       const float xa_v = xa_n, pav = pav_n;
       const int code = code_n;
+      const ExpertLogW lw = lw_n;
       if (wave == 3 && lane < K) { lds[Lu + lane] = up_n; lds[Lu + 64 + lane] = ur_n; }
-      if (t + 1 < T) load_inputs(bt + 1, xa_n, pav_n, up_n, ur_n, code_n);
+      if (t + 1 < T) load_inputs(bt + 1, xa_n, pav_n, up_n, ur_n, code_n, lw_n);
 
       MTRSSM_CLU_STAMP(0);
       // (1) h1 = act(xa + W1s s): every member, all H outputs                    networks.py:165-166
@@ -343,7 +346,7 @@ __global__ __launch_bounds__(kCluThreads) void mrssm_fwd_cluster_kernel(const Mt
           for (int m2 = 0; m2 < kClu; ++m2) v += lds[Lpart + m2 * 3 * S + i];
           lds[(which == 0 ? Llp : (which == 1 ? Lla : Llv)) + s2] = v;
         }
-        wave_mopoe_mix_masked<true, MASKED>(lds + Lla, lds + Llv, lds + Llp, lds + Lmx, S, lane, code);
+        wave_mopoe_mix_masked<true, MASKED>(lds + Lla, lds + Llv, lds + Llp, lds + Lmx, S, lane, code, lw);
         for (int s = lane; s < S; s += kWave) {
           if (writer) {
             io.prior_logits[bt * S + s] = lds[Llp + s];
@@ -508,9 +511,11 @@ __global__ __launch_bounds__(kCluThreads) void mrssm_bwd_cluster_kernel(const Mt
     // NH..), r2 gates (4 UD) | g_kl (thread 4 UD), r3 h1 (H), r4 d_prev (UD) | g_deter (UD, threads 64..)
     float r0 = 0.f, r1 = 0.f, r2 = 0.f, r3 = 0.f, r4 = 0.f;
     int code_n = kModBoth;  // the step's modality code (every member: the mix backward runs on each of them)
+    ExpertLogW lw_n = kThirds;  // ... and its three expert log-weights (weighted MoPoE)
     auto stage_load = [&](int tt) {
       const size_t q = (size_t)row * T + tt;
       code_n = modality_code<MASKED>(io.modality, q);
+      lw_n = expert_logw<MASKED>(io.expert_logw, q);
       if (tid < 4 * S) {
         const int which = tid / S, s2 = tid - which * S;
         const float* src = which == 0 ? io.sv_la : (which == 1 ? io.sv_lv : (which == 2 ? io.post_logits : io.prior_logits));
@@ -559,6 +564,7 @@ __global__ __launch_bounds__(kCluThreads) void mrssm_bwd_cluster_kernel(const Mt
       //     (stage_load below): to LDS now, then the loads of step t - 1 go out and fly during this whole step
       stage_store();
       const int code = code_n;
+      const ExpertLogW lw = lw_n;
       if (t > 0) stage_load(t - 1);
       lds_barrier();
 
@@ -572,8 +578,9 @@ __global__ __launch_bounds__(kCluThreads) void mrssm_bwd_cluster_kernel(const Mt
           cat_block_bwd<true>(lds + Lmx, lds + Llp, K, C, lane, lds + Lgps, lds + Lcs, io.g_prior_stoch ? io.g_prior_stoch + bt * S : nullptr,
                               io.g_post_logits ? io.g_post_logits + bt * S : nullptr, io.g_prior_logits ? io.g_prior_logits + bt * S : nullptr,
                               *gk_lds, dm.kl_w_post, dm.kl_w_prior, lds + Ldmx, lds + Ldlp);
-        wave_mopoe_mix_bwd_masked<true, MASKED>(lds + Lla, lds + Llv, lds + Lmx, lds + Ldmx, lds + Ldla, lds + Ldlv, lds + Ldlp, S, lane,
-                                                code);
+        const ExpertLogW g_lw = wave_mopoe_mix_bwd_masked<true, MASKED>(lds + Lla, lds + Llv, lds + Lmx, lds + Ldmx, lds + Ldla, lds + Ldlv,
+                                                                        lds + Ldlp, S, lane, code, lw, MASKED && io.expert_logw != nullptr);
+        if (MASKED) store_g_expert_logw(io.g_expert_logw, bt, g_lw, lane, member == 0);
         if (member == 0) {
           for (int s2 = lane; s2 < S; s2 += kWave) {
             io.d_la[bt * S + s2] = lds[Ldla + s2];

@@ -135,7 +135,9 @@ __global__ __launch_bounds__(1024) void mrssm_fwd_kernel(const MtrssmMrssmDims d
       float* r_ = lds + rb * L.stride;
       const size_t q = bt[rb];
       const bool ok = valid[rb];
-      if (POST) wave_mopoe_mix_masked<false, MASKED>(r_ + L.la, r_ + L.lv, r_ + L.lp, r_ + L.mx, S, lane, modality_code<MASKED>(io.modality, q));
+      if (POST)
+        wave_mopoe_mix_masked<false, MASKED>(r_ + L.la, r_ + L.lv, r_ + L.lp, r_ + L.mx, S, lane, modality_code<MASKED>(io.modality, q),
+                                             expert_logw<MASKED>(io.expert_logw, q));
       for (int s = lane; s < S; s += kWave) {
         if (ok) {
           io.prior_logits[q * S + s] = r_[L.lp + s];
@@ -233,8 +235,11 @@ __global__ __launch_bounds__(1024) void mrssm_bwd_kernel(const MtrssmMrssmDims d
                     io.g_prior_logits ? io.g_prior_logits + q * S : nullptr, gk, dm.kl_w_post, dm.kl_w_prior,
                     r + L.dmx, r + L.dlp);
       // back through logsumexp over {A, V, A+V} and the two flat log-softmaxes (masked: over the present experts)
-      wave_mopoe_mix_bwd_masked<false, MASKED>(r + L.la, r + L.lv, r + L.mx, r + L.dmx, r + L.dla, r + L.dlv, r + L.dlp, S, lane,
-                                               modality_code<MASKED>(io.modality, q));
+      const ExpertLogW g_lw =
+          wave_mopoe_mix_bwd_masked<false, MASKED>(r + L.la, r + L.lv, r + L.mx, r + L.dmx, r + L.dla, r + L.dlv, r + L.dlp, S, lane,
+                                                   modality_code<MASKED>(io.modality, q), expert_logw<MASKED>(io.expert_logw, q),
+                                                   MASKED && io.expert_logw != nullptr);
+      if (MASKED) store_g_expert_logw(io.g_expert_logw, q, g_lw, lane, valid[rb]);
       if (valid[rb]) {
         for (int s = lane; s < S; s += kWave) {
           io.d_la[q * S + s] = r[L.dla + s];

@@ -167,6 +167,7 @@ __global__ __launch_bounds__(kWT) void mrssm_wide_fwd_kernel(const WideFwdArgs a
         if (t > 0) {
           const size_t q = b * T + (t - 1);
           const int code = modality_code<MASKED>(io.modality, q);
+          const ExpertLogW lw = expert_logw<MASKED>(io.expert_logw, q);
           if (wave == 0 && lane < K) {
             Lu[lane] = io.u_post[q * K + lane];
             Lu[64 + lane] = io.u_prior ? io.u_prior[q * K + lane] : 0.f;
@@ -179,7 +180,7 @@ __global__ __launch_bounds__(kWT) void mrssm_wide_fwd_kernel(const WideFwdArgs a
           lds_barrier();
           MTRSSM_WIDE_STAMP(10);
           if (wave == 0) {
-            wave_mopoe_mix_masked<true, MASKED>(Lla, Llv, Llp, Lmx, S, lane, code);
+            wave_mopoe_mix_masked<true, MASKED>(Lla, Llv, Llp, Lmx, S, lane, code, lw);
             MTRSSM_WIDE_STAMP(11);
             for (int s2 = lane; s2 < S; s2 += kWave) {
               io.prior_logits[q * S + s2] = Llp[s2];
@@ -424,6 +425,7 @@ __global__ __launch_bounds__(kWT) void mrssm_wide_bwd_kernel(const WideBwdArgs a
       for (int r = nblk - 1 - blk; r < nrows; r += nblk) {
         const size_t q = (size_t)(rb + r) * T + t;
         const int code = modality_code<MASKED>(io.modality, q);
+        const ExpertLogW lw = expert_logw<MASKED>(io.expert_logw, q);
         for (int s2 = tid; s2 < S; s2 += kWT) {
           Lla[s2] = io.sv_la[q * S + s2];
           Llv[s2] = io.sv_lv[q * S + s2];
@@ -445,7 +447,9 @@ __global__ __launch_bounds__(kWT) void mrssm_wide_bwd_kernel(const WideBwdArgs a
                                 io.g_post_logits ? io.g_post_logits + q * S : nullptr, io.g_prior_logits ? io.g_prior_logits + q * S : nullptr,
                                 gk, a.dm.kl_w_post, a.dm.kl_w_prior, Ldmx, Ldlp);
           MTRSSM_WIDE_STAMP(12);
-          wave_mopoe_mix_bwd_masked<true, MASKED>(Lla, Llv, Lmx, Ldmx, Ldla, Ldlv, Ldlp, S, lane, code);
+          const ExpertLogW g_lw =
+              wave_mopoe_mix_bwd_masked<true, MASKED>(Lla, Llv, Lmx, Ldmx, Ldla, Ldlv, Ldlp, S, lane, code, lw, MASKED && io.expert_logw != nullptr);
+          if (MASKED) store_g_expert_logw(io.g_expert_logw, q, g_lw, lane, true);
           MTRSSM_WIDE_STAMP(13);
         }
         lds_barrier();

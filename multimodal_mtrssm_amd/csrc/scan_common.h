@@ -219,9 +219,17 @@ __device__ __forceinline__ void wave_flat_lse(const float* x, int S, int lane, f
   lsum = clog<FAST>(acc);
 }
 
-// MoPoE mix of two experts' flat logits (core.py:241-243 + 112-163) -> mixed[S] (LDS)
+// The three expert log-weights (audio, vision, fused) of one step's MoPoE mix.  The unweighted mixture is 1/3 each: with these
+// constants inlined the helpers below compile to the code they were before the weights existed.
+struct ExpertLogW {
+  float a, v, f;
+};
+constexpr ExpertLogW kThirds = {kLogThird, kLogThird, kLogThird};
+
+// MoPoE mix of two experts' flat logits (core.py:241-243 + 112-163) -> mixed[S] (LDS).  The weights are taken as given (not
+// normalised: the per-categorical softmax downstream removes a common offset).
 template <bool FAST = false>
-__device__ __forceinline__ void wave_mopoe_mix(const float* la, const float* lv, float* mixed, int S, int lane) {
+__device__ __forceinline__ void wave_mopoe_mix(const float* la, const float* lv, float* mixed, int S, int lane, const ExpertLogW lw = kThirds) {
   float ma, lsa, mv, lsv;
   wave_flat_lse<FAST>(la, S, lane, ma, lsa);
   wave_flat_lse<FAST>(lv, S, lane, mv, lsv);
@@ -229,7 +237,7 @@ __device__ __forceinline__ void wave_mopoe_mix(const float* la, const float* lv,
     const float a = (la[s] - ma) - lsa;
     const float v = (lv[s] - mv) - lsv;
     const float f = a + v;
-    const float x1 = kLogThird + a, x2 = kLogThird + v, x3 = kLogThird + f;
+    const float x1 = lw.a + a, x2 = lw.v + v, x3 = lw.f + f;
     const float m = fmaxf(x1, fmaxf(x2, x3));
     mixed[s] = clog<FAST>(cexp<FAST>(x1 - m) + cexp<FAST>(x2 - m) + cexp<FAST>(x3 - m)) + m;
   }
@@ -243,13 +251,31 @@ __device__ __forceinline__ int modality_code(const int32_t* modality, size_t q) 
   return MASKED ? (modality[q] & 3) : kModBoth;
 }
 
+// Expert log-weights of step q (mtrssm.h, the `expert_logw` field: [B,T,3]).  NULL (a workgroup-uniform test), or the unmasked
+// kernel: the constant 1/3 each, which gives the unweighted mix bit for bit.  Only the MASKED instances carry the load.
+template <bool MASKED>
+__device__ __forceinline__ ExpertLogW expert_logw(const float* logw, size_t q) {
+  ExpertLogW lw = kThirds;
+  if (MASKED && logw) {
+    lw.a = logw[q * 3];
+    lw.v = logw[q * 3 + 1];
+    lw.f = logw[q * 3 + 2];
+  }
+  return lw;
+}
+
 // MoPoE mix over the non-empty subsets of the PRESENT experts (code: wave-uniform).  Both: wave_mopoe_mix, the same bits; one:
-// the flat log-softmax of that expert's logits; none: the prior's raw logits lp (posterior = prior, KL = 0 exactly).
+// the flat log-softmax of that expert's logits (a single subset: the weights cancel); none: the prior's raw logits lp
+// (posterior = prior, KL = 0 exactly).
 template <bool FAST, bool MASKED>
 __device__ __forceinline__ void wave_mopoe_mix_masked(const float* la, const float* lv, const float* lp, float* mixed, int S, int lane,
-                                                      int code) {
-  if (!MASKED || code == kModBoth) {
+                                                      int code, const ExpertLogW lw = kThirds) {
+  if (!MASKED) {
     wave_mopoe_mix<FAST>(la, lv, mixed, S, lane);
+    return;
+  }
+  if (code == kModBoth) {
+    wave_mopoe_mix<FAST>(la, lv, mixed, S, lane, lw);
     return;
   }
   if (code == 0) {
@@ -501,25 +527,34 @@ __device__ __forceinline__ void cat_block_bwd_fast8(const float* q_logits, const
   }
 }
 
-// Backward of wave_mopoe_mix: given d mixed (dmx, LDS) and the saved expert logits, writes d la / d lv (LDS).
-template <bool FAST = false>
+// Backward of wave_mopoe_mix: given d mixed (dmx, LDS) and the saved expert logits, writes d la / d lv (LDS).  GLW: also sums
+// the responsibilities into the gradient at the three log-weights, g_i = sum_s dmx[s] r_i[s]; the three wave reductions run only
+// when `weighted` (wave-uniform) says the caller wants them, else g is zero.
+template <bool FAST = false, bool GLW = false>
 __device__ __forceinline__ void wave_mopoe_mix_bwd(const float* la, const float* lv, const float* mixed, const float* dmx,
-                                                   float* dla, float* dlv, int S, int lane) {
+                                                   float* dla, float* dlv, int S, int lane, const ExpertLogW lw = kThirds,
+                                                   bool weighted = false, ExpertLogW* g_lw = nullptr) {
   float ma, lsa, mv, lsv;
   wave_flat_lse<FAST>(la, S, lane, ma, lsa);
   wave_flat_lse<FAST>(lv, S, lane, mv, lsv);
   float suma = 0.f, sumv = 0.f;
+  float ga = 0.f, gv = 0.f, gf = 0.f;
   for (int s = lane; s < S; s += kWave) {
     const float a = (la[s] - ma) - lsa;
     const float v = (lv[s] - mv) - lsv;
     const float mx = mixed[s];
-    const float wa = cexp<FAST>(kLogThird + a - mx), wv = cexp<FAST>(kLogThird + v - mx), wf = cexp<FAST>(kLogThird + a + v - mx);
+    const float wa = cexp<FAST>(lw.a + a - mx), wv = cexp<FAST>(lw.v + v - mx), wf = cexp<FAST>(lw.f + a + v - mx);
     const float g = dmx[s];
     const float da = g * (wa + wf), dv = g * (wv + wf);
     dla[s] = da;
     dlv[s] = dv;
     suma += da;
     sumv += dv;
+    if (GLW) {
+      ga = fmaf(g, wa, ga);
+      gv = fmaf(g, wv, gv);
+      gf = fmaf(g, wf, gf);
+    }
   }
   suma = wave_sum(suma);
   sumv = wave_sum(sumv);
@@ -527,17 +562,31 @@ __device__ __forceinline__ void wave_mopoe_mix_bwd(const float* la, const float*
     dla[s] -= cexp<FAST>((la[s] - ma) - lsa) * suma;
     dlv[s] -= cexp<FAST>((lv[s] - mv) - lsv) * sumv;
   }
+  if (GLW) {
+    if (weighted) {
+      g_lw->a = wave_sum(ga);
+      g_lw->v = wave_sum(gv);
+      g_lw->f = wave_sum(gf);
+    }
+  }
 }
 
 // Backward of wave_mopoe_mix_masked.  Both: wave_mopoe_mix_bwd.  One: through that expert's flat log-softmax, zero for the
 // absent one.  None: d mixed is routed into the prior logits (dlp += dmx; dlp holds the categorical block's own d prior), zero
-// for both experts.
+// for both experts.  Returns the gradient at the step's log-weights (every lane): exactly zero unless both are present and the
+// rollout is `weighted`.
 template <bool FAST, bool MASKED>
-__device__ __forceinline__ void wave_mopoe_mix_bwd_masked(const float* la, const float* lv, const float* mixed, const float* dmx,
-                                                          float* dla, float* dlv, float* dlp, int S, int lane, int code) {
-  if (!MASKED || code == kModBoth) {
+__device__ __forceinline__ ExpertLogW wave_mopoe_mix_bwd_masked(const float* la, const float* lv, const float* mixed, const float* dmx,
+                                                                float* dla, float* dlv, float* dlp, int S, int lane, int code,
+                                                                const ExpertLogW lw = kThirds, bool weighted = false) {
+  ExpertLogW g_lw = {0.f, 0.f, 0.f};
+  if (!MASKED) {
     wave_mopoe_mix_bwd<FAST>(la, lv, mixed, dmx, dla, dlv, S, lane);
-    return;
+    return g_lw;
+  }
+  if (code == kModBoth) {
+    wave_mopoe_mix_bwd<FAST, true>(la, lv, mixed, dmx, dla, dlv, S, lane, lw, weighted, &g_lw);
+    return g_lw;
   }
   if (code == 0) {
     for (int s = lane; s < S; s += kWave) {
@@ -545,7 +594,7 @@ __device__ __forceinline__ void wave_mopoe_mix_bwd_masked(const float* la, const
       dla[s] = 0.f;
       dlv[s] = 0.f;
     }
-    return;
+    return g_lw;
   }
   const float* l = code == 1 ? la : lv;
   float* dl = code == 1 ? dla : dlv;
@@ -559,6 +608,16 @@ __device__ __forceinline__ void wave_mopoe_mix_bwd_masked(const float* la, const
   }
   sum = wave_sum(sum);
   for (int s = lane; s < S; s += kWave) dl[s] = dmx[s] - cexp<FAST>((l[s] - m) - ls) * sum;
+  return g_lw;
+}
+
+// One lane stores the step's gradient at the log-weights (plain stores, once per (b, t): no atomics).
+__device__ __forceinline__ void store_g_expert_logw(float* g_logw, size_t q, const ExpertLogW g, int lane, bool ok) {
+  if (g_logw && lane == 0 && ok) {
+    g_logw[q * 3] = g.a;
+    g_logw[q * 3 + 1] = g.v;
+    g_logw[q * 3 + 2] = g.f;
+  }
 }
 
 // The higher level of a masked MMTRSSM step with no modality: posterior = prior (forward: q logits <- p logits) ...

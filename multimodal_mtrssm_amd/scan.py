@@ -234,6 +234,24 @@ def _modality(modality: Tensor | None, B: int, T: int) -> Tensor | None:  # noqa
     return _c(modality)
 
 
+def check_expert_logw(expert_logw: Tensor | None, B: int, T: int) -> Tensor | None:  # noqa: N803
+    """The scans' per-step expert log-weights of a weighted MoPoE: fp32 ``[B, T, 3]`` (audio, vision, fused), contiguous, or None
+    (1/3 each everywhere).  The kernels take them as given: they are not normalised."""
+    if expert_logw is None:
+        return None
+    if expert_logw.dtype != torch.float32 or tuple(expert_logw.shape) != (B, T, 3):
+        msg = f"expert log-weights must be float32 [{B}, {T}, 3], got {expert_logw.dtype} {tuple(expert_logw.shape)}"
+        raise ValueError(msg)
+    return _c(expert_logw)
+
+
+def _weighted_modality(modality: Tensor | None, expert_logw: Tensor | None) -> Tensor | None:
+    """The weights ride in the masked kernel instances: without a mask they get the code "both" everywhere."""
+    if modality is None and expert_logw is not None:
+        return torch.full(expert_logw.shape[:2], 3, device=expert_logw.device, dtype=torch.int32)
+    return modality
+
+
 def modality_codes(mask: Tensor) -> Tensor:
     """bool [B, T, 2] (audio, vision) -> the scans' int32 [B, T] codes (bit 0 audio, bit 1 vision)."""
     return (mask[..., 0].to(torch.int32) + 2 * mask[..., 1].to(torch.int32)).contiguous()
@@ -265,6 +283,7 @@ class _MrssmScan(torch.autograd.Function):
     def forward(  # noqa: PLR0913, PLR0914
         ctx, cfg: ScanConfig, xa, pa, pv, deter0, stoch0, u_post, u_prior,  # noqa: ANN001
         w1, w2, b2, wih, bih, whh, bhh, w3, b3, w4, b4, wa1, wa2, ba2, wv1, wv2, bv2, modality=None,  # noqa: ANN001
+        expert_logw=None,  # noqa: ANN001
     ):
         # outputs the loss does not touch get NO gradient tensor (autograd would materialise zeros: a fill kernel per unused output
         # and a read of it in the backward scan); the kernels take null pointers for absent gradients
@@ -284,7 +303,8 @@ class _MrssmScan(torch.autograd.Function):
             msg = "weight shapes are inconsistent with (deter, stoch, action, embed)"
             raise ValueError(msg)
         xa, pa, pv, deter0, stoch0, u_post = map(_c, (xa, pa, pv, deter0, stoch0, u_post))
-        modality = _modality(modality, B, T)
+        expert_logw = check_expert_logw(expert_logw, B, T)
+        modality = _weighted_modality(_modality(modality, B, T), expert_logw)
         u_prior = _opt(u_prior)
         # forward layouts (include/mtrssm.h: wide outputs stream W^T, narrow outputs stream W)
         w1s_t = _c(w1[:, A:].t())
@@ -302,7 +322,7 @@ class _MrssmScan(torch.autograd.Function):
         io = _lib.fill(
             _lib.MrssmFwdIO(), xa=xa, pa=pa, pv=pv, deter0=deter0, stoch0=stoch0, u_post=u_post, u_prior=u_prior,
             deter=deter, prior_logits=prior_logits, prior_stoch=prior_stoch, post_logits=post_logits, post_stoch=post_stoch,
-            kl=kl, **sv, modality=modality,
+            kl=kl, **sv, modality=modality, expert_logw=expert_logw,
         )
         wp, wq = cfg.kl_weights
         dims = _lib.MrssmDims(B, T, D, H, cfg.cats, cfg.classes, cfg.act, 1, wp, wq, cfg.rows_per_block, cfg.threads)
@@ -347,7 +367,7 @@ class _MrssmScan(torch.autograd.Function):
                                         _lib.stream_ptr(xa.device), flops=2.0 * B * T * macs, nbytes=4.0 * B * T * per_bt),
                        "mtrssm_mrssm_rollout_fwd")
         if need_grad:
-            ctx.cfg, ctx.A, ctx.modality = cfg, A, modality
+            ctx.cfg, ctx.A, ctx.modality, ctx.expert_logw = cfg, A, modality, expert_logw
             ctx.biases, ctx.w3 = (b2, bih, bhh, b3, b4, ba2, bv2), w3
             ctx.save_for_backward(deter0, stoch0, deter, prior_logits, post_logits, post_stoch, sv["sv_h1"], sv["sv_h2"],
                                   sv["sv_gates"], sv["sv_heads"], sv["sv_la"], sv["sv_lv"], w1s_t, wh1,
@@ -376,13 +396,14 @@ class _MrssmScan(torch.autograd.Function):
         d_gi, d_gh = _new(deter, B, T, 3 * D), _new(deter, B, T, 3 * D)
         d_zh = _new(deter, B, T, 3 * H)
         d_lp, d_la, d_lv = (_new(deter, B, T, S) for _ in range(3))
+        g_logw = _new(deter, B, T, 3) if ctx.expert_logw is not None and ctx.needs_input_grad[-1] else None
         io = _lib.fill(
             _lib.MrssmBwdIO(), deter0=deter0, deter=deter, prior_logits=prior_logits, post_logits=post_logits, sv_h1=sv_h1,
             sv_h2=sv_h2, sv_gates=sv_gates, sv_heads=sv_heads, sv_la=sv_la, sv_lv=sv_lv,
             g_deter=_opt(g_deter), g_post_stoch=_opt(g_post_stoch), g_prior_stoch=_opt(g_prior_stoch),
             g_post_logits=_opt(g_post_logits), g_prior_logits=_opt(g_prior_logits), g_kl=_opt(g_kl),
             g_deter0=g_deter0, g_stoch0=g_stoch0, d_z1=d_z1, d_h2=d_h2, d_gi=d_gi, d_gh=d_gh, d_zh=d_zh, d_lp=d_lp, d_la=d_la,
-            d_lv=d_lv, modality=ctx.modality,
+            d_lv=d_lv, modality=ctx.modality, expert_logw=ctx.expert_logw, g_expert_logw=g_logw,
         )
         wp, wq = cfg.kl_weights
         dims = _lib.MrssmDims(B, T, D, H, cfg.cats, cfg.classes, cfg.act, 1, wp, wq, cfg.rows_per_block, cfg.threads)
@@ -440,15 +461,18 @@ class _MrssmScan(torch.autograd.Function):
         r = wg.result
         return (None, d_z1, g_pa, g_pv, g_deter0, g_stoch0, None, None,
                 r(w1), r(w2), r(b2), r(wih), r(bih), r(whh), r(bhh), r(w3), r(b3), r(w4), r(b4), r(wa1), r(wa2), r(ba2), r(wv1), r(wv2),
-                r(bv2), None)
+                r(bv2), None, g_logw)
 
 
 def mrssm_posterior_rollout(  # noqa: PLR0913
     transition, audio_rep, vision_rep, actions: Tensor, audio_embed: Tensor, vision_embed: Tensor,  # noqa: ANN001
     deter0: Tensor, stoch0: Tensor, u_post: Tensor, u_prior: Tensor | None, *, balancing: bool, rows_per_block: int = 0,
-    threads: int = 0, modality: Tensor | None = None,
+    threads: int = 0, modality: Tensor | None = None, expert_logw: Tensor | None = None,
 ) -> dict[str, Tensor]:
     """Run ``mrssm/mopoe_mrssm/core.py:221-256`` for all T steps on the GPU.
+
+    ``expert_logw``: optional fp32 ``[B, T, 3]`` log-weights of the (audio, vision, fused) experts of a weighted MoPoE
+    (``experts.ExpertWeights``), read where both modalities are present; None = 1/3 each.
 
     ``modality``: optional int32 ``[B, T]`` codes (bit 0 audio, bit 1 vision; ``modality_codes``) of a missing-modality
     rollout.  An embedding may then be ``None`` when its modality is absent at every step: its projection is not run."""
@@ -474,7 +498,7 @@ def mrssm_posterior_rollout(  # noqa: PLR0913
     deter, prior_logits, post_logits, post_stoch, prior_stoch, kl = _MrssmScan.apply(
         cfg, xa, pa, pv, deter0, stoch0, u_post, u_prior,
         l1.weight, l2.weight, l2.bias, cell.weight_ih, cell.bias_ih, cell.weight_hh, cell.bias_hh,
-        p1.weight, p1.bias, p2.weight, p2.bias, a1.weight, a2.weight, a2.bias, v1.weight, v2.weight, v2.bias, modality,
+        p1.weight, p1.bias, p2.weight, p2.bias, a1.weight, a2.weight, a2.bias, v1.weight, v2.weight, v2.bias, modality, expert_logw,
     )
     return {"deter": deter, "prior_logits": prior_logits, "post_logits": post_logits, "post_stoch": post_stoch,
             "prior_stoch": prior_stoch if u_prior is not None else None, "kl": kl}
@@ -593,7 +617,7 @@ class _MmtrssmScan(torch.autograd.Function):
         ctx, cfg: MTScanConfig, xl, pa, pv, deter_l0, deter_h0, hidden_l0, hidden_h0, stoch_l0, stoch_h0,  # noqa: ANN001
         u_post_l, u_post_h, u_prior_l, u_prior_h,  # noqa: ANN001
         wxl, wdl, wxh, wdh, bh, wlp1, blp1, wlp2, blp2, wa1, wa2, ba2, wv1, wv2, bv2, whp1, bhp1, whp2, bhp2, whq1, bhq1, whq2, bhq2,  # noqa: ANN001
-        modality=None,  # noqa: ANN001
+        modality=None, expert_logw=None,  # noqa: ANN001
     ):
         # outputs the loss does not touch get NO gradient tensor (autograd would materialise zeros: a fill kernel per unused output
         # and a read of it in the backward scan); the kernels take null pointers for absent gradients
@@ -636,7 +660,8 @@ class _MmtrssmScan(torch.autograd.Function):
             post_logits_l=_new(xl, B, T, LS), post_logits_h=_new(xl, B, T, HS),
             post_stoch_l=_new(xl, B, T, LS), post_stoch_h=_new(xl, B, T, HS), kl_l=_new(xl, B, T), kl_h=_new(xl, B, T),
         )
-        modality = _modality(modality, B, T)
+        expert_logw = check_expert_logw(expert_logw, B, T)
+        modality = _weighted_modality(_modality(modality, B, T), expert_logw)
         need_grad = any(ctx.needs_input_grad)
         sv = dict(sv_l1=None, sv_h1=None, sv_la=None, sv_lv=None)
         if need_grad:
@@ -644,7 +669,7 @@ class _MmtrssmScan(torch.autograd.Function):
         io = _lib.fill(
             _lib.MmtrssmFwdIO(), xl=xl, pa=pa, pv=pv, deter_l0=deter_l0, deter_h0=deter_h0, hidden_l0=hidden_l0,
             hidden_h0=hidden_h0, stoch_l0=stoch_l0, stoch_h0=stoch_h0, u_post_l=u_post_l, u_post_h=u_post_h,
-            u_prior_l=u_prior_l, u_prior_h=u_prior_h, **o, **sv, modality=modality,
+            u_prior_l=u_prior_l, u_prior_h=u_prior_h, **o, **sv, modality=modality, expert_logw=expert_logw,
         )
         dims = cfg.dims(B, T, LD, HD, H, 1)
         macs = (LS + HS) * LD + LD * LD + HS * HD + HD * HD + 4 * H * LD + 2 * H * HD + 3 * LS * H + 2 * HS * H
@@ -663,7 +688,7 @@ class _MmtrssmScan(torch.autograd.Function):
                        "mtrssm_mmtrssm_rollout_fwd")
         del tensors
         if need_grad:
-            ctx.cfg, ctx.A, ctx.modality = cfg, A, modality
+            ctx.cfg, ctx.A, ctx.modality, ctx.expert_logw = cfg, A, modality, expert_logw
             ctx.biases, ctx.first_layers = (bh, blp1, blp2, ba2, bv2, bhp1, bhp2, bhq1, bhq2), (wlp1, whp1)
             ctx.save_for_backward(
                 deter_l0, deter_h0, stoch_l0, stoch_h0, o["deter_l"], o["deter_h"], o["prior_logits_l"], o["prior_logits_h"],
@@ -698,6 +723,7 @@ class _MmtrssmScan(torch.autograd.Function):
         d = dict(d_ul=_new(deter_l, B, T, LD), d_uh=_new(deter_l, B, T, HD), d_zl1=_new(deter_l, B, T, 4 * H),
                  d_zh1=_new(deter_l, B, T, H), d_lpl=_new(deter_l, B, T, LS), d_la=_new(deter_l, B, T, LS),
                  d_lv=_new(deter_l, B, T, LS), d_lph=_new(deter_l, B, T, HS), d_lqh=_new(deter_l, B, T, HS))
+        g_logw = _new(deter_l, B, T, 3) if ctx.expert_logw is not None and ctx.needs_input_grad[-1] else None
         io = _lib.fill(
             _lib.MmtrssmBwdIO(), deter_l0=deter_l0, deter_h0=deter_h0, deter_l=deter_l, deter_h=deter_h,
             prior_logits_l=prior_logits_l, prior_logits_h=prior_logits_h, post_logits_l=post_logits_l, post_logits_h=post_logits_h,
@@ -705,7 +731,8 @@ class _MmtrssmScan(torch.autograd.Function):
             g_deter_l=_opt(g_dl), g_deter_h=_opt(g_dh), g_hidden_l=_opt(g_hl), g_hidden_h=_opt(g_hh),
             g_post_stoch_l=_opt(g_qsl), g_post_stoch_h=_opt(g_qsh), g_prior_stoch_l=_opt(g_psl), g_prior_stoch_h=_opt(g_psh),
             g_post_logits_l=_opt(g_qll), g_post_logits_h=_opt(g_qlh), g_prior_logits_l=_opt(g_pll), g_prior_logits_h=_opt(g_plh),
-            g_kl_l=_opt(g_kll), g_kl_h=_opt(g_klh), **g0, **d, modality=ctx.modality,
+            g_kl_l=_opt(g_kll), g_kl_h=_opt(g_klh), **g0, **d, modality=ctx.modality, expert_logw=ctx.expert_logw,
+            g_expert_logw=g_logw,
         )
         dims = cfg.dims(B, T, LD, HD, H, 1)
         macs = (LS + HS) * LD + LD * LD + HS * HD + HD * HD + 4 * H * LD + 2 * H * HD + 3 * LS * H + 2 * HS * H
@@ -753,7 +780,7 @@ class _MmtrssmScan(torch.autograd.Function):
         return (None, d["d_ul"], zl[..., H : 2 * H], zl[..., 2 * H : 3 * H], g0["g_deter_l0"], g0["g_deter_h0"], g0["g_hidden_l0"],
                 g0["g_hidden_h0"], g0["g_stoch_l0"], g0["g_stoch_h0"], None, None, None, None,
                 r(wxl), r(wdl), r(wxh), r(wdh), r(bh), r(wlp1), r(blp1), r(wlp2), r(blp2), r(wa1), r(wa2), r(ba2), r(wv1), r(wv2), r(bv2),
-                r(whp1), r(bhp1), r(whp2), r(bhp2), r(whq1), r(bhq1), r(whq2), r(bhq2), None)
+                r(whp1), r(bhp1), r(whp2), r(bhp2), r(whq1), r(bhq1), r(whq2), r(bhq2), None, g_logw)
 
 
 def _mt_act(model) -> int:  # noqa: ANN001
@@ -768,8 +795,9 @@ def _mt_act(model) -> int:  # noqa: ANN001
 
 def mmtrssm_posterior_rollout(model, actions: Tensor, audio_embed: Tensor, vision_embed: Tensor, state0: dict[str, Tensor],  # noqa: ANN001
                               noise: dict[str, Tensor | None], *, rows_per_block: int = 0, threads: int = 0,
-                              modality: Tensor | None = None) -> dict[str, Tensor]:
-    """Run ``mmtrssm/mopoe_mmtrssm/core.py:405-490`` for all T steps on the GPU (``modality``: as ``mrssm_posterior_rollout``)."""
+                              modality: Tensor | None = None, expert_logw: Tensor | None = None) -> dict[str, Tensor]:
+    """Run ``mmtrssm/mopoe_mmtrssm/core.py:405-490`` for all T steps on the GPU (``modality`` / ``expert_logw``: as
+    ``mrssm_posterior_rollout``; the weights act on the lower level's mixture)."""
     LD = model.ld_dim
     A = actions.shape[-1]
     cfg = MTScanConfig(model.l_dist.category_size, model.l_dist.class_size, model.h_dist.category_size, model.h_dist.class_size,
@@ -790,7 +818,7 @@ def mmtrssm_posterior_rollout(model, actions: Tensor, audio_embed: Tensor, visio
         state0["stoch_h"], noise["u_post_l"], noise["u_post_h"], noise.get("u_prior_l"), noise.get("u_prior_h"),
         lr._input2h.weight, lr._d2h.weight, hr._input2h.weight, hr._d2h.weight, bh,  # noqa: SLF001
         lp1.weight, lp1.bias, lp2.weight, lp2.bias, a1.weight, a2.weight, a2.bias, v1.weight, v2.weight, v2.bias,
-        hp1.weight, hp1.bias, hp2.weight, hp2.bias, hq1.weight, hq1.bias, hq2.weight, hq2.bias, modality,
+        hp1.weight, hp1.bias, hp2.weight, hp2.bias, hq1.weight, hq1.bias, hq2.weight, hq2.bias, modality, expert_logw,
     )
     names = ("deter_l", "deter_h", "hidden_l", "hidden_h", "prior_logits_l", "prior_logits_h", "post_logits_l", "post_logits_h",
              "post_stoch_l", "post_stoch_h", "prior_stoch_l", "prior_stoch_h", "kl_l", "kl_h")
