@@ -836,6 +836,29 @@ int mtrssm_ensemble_score(const float* pred, const float* target, const int32_t*
 int mtrssm_horizon_table(const float* planes, int64_t P, const int32_t* context, const int32_t* valid, int64_t B, int64_t T,
                          float* sums, float* counts, void* stream);
 
+/* Digit reader: the inference path of the classifier that reads a digit off a predicted vision frame
+ * (conv 3x3 1->32, ReLU, pool 2x2, conv 3x3 32->64, ReLU, pool 2x2, Linear 4096->128, ReLU, Linear 128->10; 32 x 32 frames).
+ * mtrssm_digit_features: the convolutional trunk of a frame in one launch.  pred [frames][1024] is the decoder's RAW output;
+ *   output n reads frame select[n] (int32 [N] in DEVICE memory; NULL: frame n, then N <= frames) as
+ *   x = clamp((act(pred) + 1) / 2, 0, 1), `act` MTRSSM_ACT_IDENTITY or MTRSSM_ACT_TANH.  conv1_w [32][1][3][3], conv1_b [32],
+ *   conv2_w [64][32][3][3], conv2_b [64] (torch's layouts, fp32); features [N][4096] in the view(-1, 64 * 8 * 8) order.  conv1 is
+ *   fp32; conv2 multiplies two bf16 pieces per operand (three products, fp32 sums).  Neither intermediate is written to memory.  A
+ *   select[n] outside [0, frames) reads nothing and leaves NaN in row n.  A frame's result depends on that frame only.
+ *   Null pointers (select excepted), frames or N outside (0, 2^31), N > frames without select, another `act`, pred / features not
+ *   16-byte aligned return -1 without a launch.
+ * mtrssm_digit_head: logits[n][k] = b[k] + sum_j w[k][j] hidden[n][j] (hidden [N][128] is fc1's ACTIVATED output, w [10][128]) in
+ *   fp32, digit[n] = the lowest index among the largest logits (torch.max's first occurrence).  select / frames (select may be NULL)
+ *   are mtrssm_digit_features' own: a frame it could not read (fc1's ReLU has swallowed the NaN features) or whose logits hold a
+ *   NaN gets NaN logits and digit 10, the failure bin.  logits [N][10] may be NULL.
+ * mtrssm_word_counts: counts[word[n]][digit[n]] += 1 over the frames with word[n] in 0 .. 9 and digit[n] in 0 .. 10 (others are
+ *   skipped: word -1 is silence); counts [10][11] fp32 is IN/OUT, column 10 the failure bin.  Integer counting, no float atomics: two
+ *   runs agree bitwise.  N outside (0, 2^24) returns -1 (the fp32 counts are exact below 2^24). */
+int mtrssm_digit_features(const float* pred, int64_t frames, const int32_t* select, int64_t N, int32_t act, const float* conv1_w,
+                          const float* conv1_b, const float* conv2_w, const float* conv2_b, float* features, void* stream);
+int mtrssm_digit_head(const float* hidden, const float* w, const float* b, int64_t N, const int32_t* select, int64_t frames, int32_t* digit,
+                      float* logits, void* stream);
+int mtrssm_word_counts(const int32_t* word, const int32_t* digit, int64_t N, float* counts, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Fused AdamW over one flat fp32 parameter buffer, with global-norm gradient clipping
  * (yaml: torch.optim.AdamW lr 1e-3; trainer.gradient_clip_val 10 -- default.yaml:103-107,119).

@@ -10,6 +10,7 @@ from multimodal_mtrssm_amd.carry import StateCarry
 from multimodal_mtrssm_amd.cnn import Decoder, Encoder
 from multimodal_mtrssm_amd.core import MoPoE_MMTRSSM, MoPoE_MRSSM, WeightedMoPoE_MMTRSSM, WeightedMoPoE_MRSSM
 from multimodal_mtrssm_amd.dataset import DeviceEpisodeLoader, EpisodeBatch, EpisodeDataModule, EpisodeDataModuleConfig
+from multimodal_mtrssm_amd.digits import DigitClassifier
 from multimodal_mtrssm_amd.distributions import (
     Distribution,
     MultiOneHot,
@@ -29,13 +30,14 @@ from multimodal_mtrssm_amd.optim import FlatAdamW, ReduceLROnPlateau, load_refer
 from multimodal_mtrssm_amd.parallel import FlatDataParallel, GlobalRowNoise
 from multimodal_mtrssm_amd.schedule import ElboSchedule
 from multimodal_mtrssm_amd.skill import ForecastSkill, SkillTable
+from multimodal_mtrssm_amd.words import TransitionTable, WordTransitions
 from multimodal_mtrssm_amd.state import MTState, State, cat_mtstates, cat_states, stack_mtstates, stack_states
 
 __version__ = "0.1.0"
 
 __all__ = [
-    "MLP", "MTRNN", "Decoder", "DeviceEpisodeLoader", "Distribution", "Encoder", "EpisodeBatch", "EpisodeDataModule", "ElboSchedule", "EpisodeDataModuleConfig", "ExpertWeights", "FlatAdamW", "FlatDataParallel", "Forecast", "ForecastSkill", "GlobalRowNoise", "MTState", "MoPoE_MMTRSSM",
-    "MoPoE_MRSSM", "ModalityDropout", "MultiOneHot", "MultiOneHotFactory", "ReduceLROnPlateau", "Representation", "SkillTable", "State", "StateCarry", "Transition", "WeightedMoPoE_MMTRSSM", "WeightedMoPoE_MRSSM", "cat_distribution",
+    "MLP", "MTRNN", "Decoder", "DeviceEpisodeLoader", "DigitClassifier", "Distribution", "Encoder", "EpisodeBatch", "EpisodeDataModule", "ElboSchedule", "EpisodeDataModuleConfig", "ExpertWeights", "FlatAdamW", "FlatDataParallel", "Forecast", "ForecastSkill", "GlobalRowNoise", "MTState", "MoPoE_MMTRSSM",
+    "MoPoE_MRSSM", "ModalityDropout", "MultiOneHot", "MultiOneHotFactory", "ReduceLROnPlateau", "Representation", "SkillTable", "State", "StateCarry", "Transition", "TransitionTable", "WeightedMoPoE_MMTRSSM", "WeightedMoPoE_MRSSM", "WordTransitions", "cat_distribution",
     "cat_mtstates", "cat_states", "inject_uniforms", "kl_divergence", "likelihood", "load_reference_checkpoint", "make_mmtrssm", "make_mrssm",
     "stack_distribution", "stack_mtstates", "stack_states",
 ]

@@ -157,6 +157,9 @@ SYMBOLS: dict[str, tuple[type | None, list[type]]] = {
                                             _p, _p, _p, _p, _p, _p]),
     "mtrssm_ensemble_score": (C.c_int, [_p, _p, _p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _i, _p, _p, _p, _p, _p, _p]),
     "mtrssm_horizon_table": (C.c_int, [_p, C.c_int64, _p, _p, C.c_int64, C.c_int64, _p, _p, _p]),
+    "mtrssm_digit_features": (C.c_int, [_p, C.c_int64, _p, C.c_int64, _i, _p, _p, _p, _p, _p, _p]),
+    "mtrssm_digit_head": (C.c_int, [_p, _p, _p, C.c_int64, _p, C.c_int64, _p, _p, _p]),
+    "mtrssm_word_counts": (C.c_int, [_p, _p, C.c_int64, _p, _p]),
     "mtrssm_elbo_combine_counted_fwd": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int64, C.c_float, C.c_float, _p, _p, _p, _p, _p]),
     "mtrssm_elbo_combine_counted_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int64, C.c_float, C.c_float, _p, _p, _p, _p, _p]),
     "mtrssm_elbo_schedule_fwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, C.c_int64, ElboSchedule, _p, _p, _p, _p, _p, _p, _p]),

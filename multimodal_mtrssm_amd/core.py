@@ -22,6 +22,7 @@ from torch import Tensor, nn
 from multimodal_mtrssm_amd import cnn, conv, scan
 from multimodal_mtrssm_amd.carry import StateCarry
 from multimodal_mtrssm_amd.distributions import MultiOneHot, MultiOneHotFactory, draw_uniforms, kl_divergence, onehot_from_uniforms
+from multimodal_mtrssm_amd.digits import DigitClassifier, word_counts
 from multimodal_mtrssm_amd.dropout import ModalityDropout, StepMask, ragged_step_mask
 from multimodal_mtrssm_amd.experts import ExpertWeights
 from multimodal_mtrssm_amd.forecast import Forecast
@@ -29,6 +30,7 @@ from multimodal_mtrssm_amd.networks import MTRNN, Representation, Transition
 from multimodal_mtrssm_amd.objective import likelihood
 from multimodal_mtrssm_amd.schedule import ElboSchedule, ElboTerms
 from multimodal_mtrssm_amd.skill import ForecastSkill, SkillTable
+from multimodal_mtrssm_amd.words import TransitionTable, WordTransitions
 from multimodal_mtrssm_amd.state import MTState, State
 
 try:  # the real trainer, when it is installed next to the reference
@@ -680,36 +682,14 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
 
     _POST_KEYS = ("u_post",)  # the rollout's posterior uniforms; a skill step composes each with its "u_tail" twin
 
-    @torch.no_grad()
-    def forecast_skill(self, batch: tuple[Tensor, ...], skill: ForecastSkill, noise: Noise | None = None, lengths: Tensor | None = None,  # noqa: PLR0913, PLR0914
-                       table: SkillTable | None = None, *, keep_states: bool = False, expert_log_weights: Tensor | None = None) -> SkillTable:
-        """One skill step (DESIGN.md section 6h): observe ``skill.context`` frames (of ``skill.observe``), roll ``skill.samples`` sampled
-        futures per row open loop in ONE masked posterior rollout over ``B * S`` rows (row ``b * S + s``; the copies of a row share
-        ``noise["u_post"]`` on the context and read ``noise["u_tail"][b, s]`` after it), decode, and score every live frame of both
-        modalities as an ensemble (``mtrssm_ensemble_score``); the planes are folded by horizon into ``table`` (a new one when None),
-        which is returned.  ``best`` is the best sample per FRAME.  ``lengths`` (or a batch that carries ``valid_global``) as in
-        ``forecast_rollout``: nothing is observed or scored at or past a row's end.  ``keep_states``: ``table.states`` is the posterior
-        state sequence ``[B * S, T, .]`` and ``table.planes`` the step's score planes ``[8, B, T]``.  Every row starts from its own
-        frame 0: no masked (7-tuple) batch, no ``state_carry``.  A weighted model (DESIGN.md section 6i) runs its gate once per row and
-        repeats the weights for the row's copies; ``expert_log_weights`` (fp32 ``[B, T, 3]``, or ``[B * S, T, 3]`` already repeated)
-        gives them explicitly."""
-        if not isinstance(skill, ForecastSkill):
-            msg = f"skill must be a ForecastSkill, got {type(skill).__name__}"
-            raise ValueError(msg)
-        if self.get_modality_mask_from_batch(batch) is not None:
-            msg = "a skill step decides what the model observes: a masked (7-tuple) batch already says what is seen"
-            raise ValueError(msg)
-        if self.state_carry is not None:
-            msg = "a skill step starts every row from its own frame 0: it does not combine with a set state_carry"
-            raise ValueError(msg)
+    def _skill_rollout(self, batch: tuple[Tensor, ...], skill: ForecastSkill, noise: Noise | None, lengths: Tensor | None,
+                       expert_log_weights: Tensor | None) -> tuple[dict[str, Tensor], Tensor | None]:
+        """The rollout of a skill step (``forecast_skill``, ``word_transitions``): both encoders, the initial state of every row, the
+        composed noise and ONE masked posterior rollout over ``B * S`` rows.  Returns the scan's outputs and the rows' lengths (or None)."""
         actions = batch[0]
         audio_obs, vision_obs = self.get_observations_from_batch(batch)
-        targets = self.get_targets_from_batch(batch)
         B, T = actions.shape[:2]
         S, dev = skill.samples, actions.device
-        if table is not None and (not isinstance(table, SkillTable) or table.steps != T or table.buffer.device != dev):
-            msg = f"table must be a SkillTable of {T} steps on {dev}"
-            raise ValueError(msg)
         valid = None
         ragged = self._lengths_of(batch, lengths, None, None)
         if ragged is not None:
@@ -740,6 +720,38 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
             logw = None if logw is None else wide(logw)  # ... repeated for its S copies
         out = self._rollout_embedded(wide(actions), wide(audio_embed), wide(vision_embed), state0, noise, sample_prior=False, modality=wide(codes),
                                      expert_log_weights=logw)
+        return out, valid
+
+    @torch.no_grad()
+    def forecast_skill(self, batch: tuple[Tensor, ...], skill: ForecastSkill, noise: Noise | None = None, lengths: Tensor | None = None,  # noqa: PLR0913, PLR0914
+                       table: SkillTable | None = None, *, keep_states: bool = False, expert_log_weights: Tensor | None = None) -> SkillTable:
+        """One skill step (DESIGN.md section 6h): observe ``skill.context`` frames (of ``skill.observe``), roll ``skill.samples`` sampled
+        futures per row open loop in ONE masked posterior rollout over ``B * S`` rows (row ``b * S + s``; the copies of a row share
+        ``noise["u_post"]`` on the context and read ``noise["u_tail"][b, s]`` after it), decode, and score every live frame of both
+        modalities as an ensemble (``mtrssm_ensemble_score``); the planes are folded by horizon into ``table`` (a new one when None),
+        which is returned.  ``best`` is the best sample per FRAME.  ``lengths`` (or a batch that carries ``valid_global``) as in
+        ``forecast_rollout``: nothing is observed or scored at or past a row's end.  ``keep_states``: ``table.states`` is the posterior
+        state sequence ``[B * S, T, .]`` and ``table.planes`` the step's score planes ``[8, B, T]``.  Every row starts from its own
+        frame 0: no masked (7-tuple) batch, no ``state_carry``.  A weighted model (DESIGN.md section 6i) runs its gate once per row and
+        repeats the weights for the row's copies; ``expert_log_weights`` (fp32 ``[B, T, 3]``, or ``[B * S, T, 3]`` already repeated)
+        gives them explicitly."""
+        if not isinstance(skill, ForecastSkill):
+            msg = f"skill must be a ForecastSkill, got {type(skill).__name__}"
+            raise ValueError(msg)
+        if self.get_modality_mask_from_batch(batch) is not None:
+            msg = "a skill step decides what the model observes: a masked (7-tuple) batch already says what is seen"
+            raise ValueError(msg)
+        if self.state_carry is not None:
+            msg = "a skill step starts every row from its own frame 0: it does not combine with a set state_carry"
+            raise ValueError(msg)
+        actions = batch[0]
+        targets = self.get_targets_from_batch(batch)
+        B, T = actions.shape[:2]
+        S, dev = skill.samples, actions.device
+        if table is not None and (not isinstance(table, SkillTable) or table.steps != T or table.buffer.device != dev):
+            msg = f"table must be a SkillTable of {T} steps on {dev}"
+            raise ValueError(msg)
+        out, valid = self._skill_rollout(batch, skill, noise, lengths, expert_log_weights)
         feature = self._feature_of(out)
         da, dv = self.audio_decoder, self.vision_decoder
         fused = isinstance(da, cnn.Decoder) and isinstance(dv, cnn.Decoder) and da.out_act_id is not None and dv.out_act_id is not None
@@ -766,6 +778,105 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         ForecastSkill.table_add(planes, context, valid, table.sums, table.counts)
         table.planes = planes if keep_states else None
         table.states = self._posterior_from_rollout(out) if keep_states else None
+        return table
+
+    def _read_vision(self, feature: Tensor, classifier: DigitClassifier) -> Tensor:
+        """The digits (int32, ``feature``'s leading shape) the classifier reads off the vision frames decoded from ``feature``; the
+        decoder's raw output goes to the reader, which applies the output activation itself."""
+        dv = self.vision_decoder
+        fused = isinstance(dv, cnn.Decoder) and dv.out_act_id is not None
+        pred = dv(feature, raw=True) if fused else dv(feature)
+        if pred.numel() != feature[..., 0].numel() * 32 * 32:
+            msg = f"the digit classifier reads 1 x 32 x 32 vision frames, the decoder gives {tuple(pred.shape[feature.dim() - 1 :])}"
+            raise ValueError(msg)
+        return classifier.digits(pred, dv.out_act_id if fused else 0).reshape(feature.shape[:-1])
+
+    @torch.no_grad()
+    def word_transitions(self, batch: tuple[Tensor, ...], labels: Tensor, wt: WordTransitions, classifier: DigitClassifier,  # noqa: PLR0913, PLR0914
+                         noise: Noise | None = None, table: TransitionTable | None = None, *,
+                         expert_log_weights: Tensor | None = None) -> TransitionTable:
+        """One transition step (``words.py``): sample ``wt.samples`` futures per row, read the predicted vision
+        frame of each with ``classifier`` and add ``q_counts[word][digit] += 1`` into ``table`` (a new one when None), which is
+        returned.  ``labels``: int ``[B, T]`` on the device, -1 = silence; row b's current word is ``labels[b, wt.query - 1]`` and a
+        silent row is skipped.  ``protocol="context"``: ``forecast_skill``'s masked rollout (the same noise: ``u_post`` / ``u_tail``),
+        frame ``wt.query - 1 + wt.read_at`` is read; only that frame is decoded, or -- ``wt.by_horizon`` -- chunks of whole rows of at
+        most ``wt.max_frames`` frames, every frame read and the ``hit`` / ``any`` planes folded by horizon.  ``protocol="reference"``:
+        the initial state of frame 0, then a prior-only step with the interval's last action ``batch[0][:, wt.query - 1]``
+        (``noise["u_prior"]``: ``[B, S, 1, K]``), whose frame is read.  No masked (7-tuple) batch, no ``state_carry``.  A weighted model
+        runs its gate as in ``forecast_skill``."""
+        if not isinstance(wt, WordTransitions):
+            msg = f"wt must be a WordTransitions, got {type(wt).__name__}"
+            raise ValueError(msg)
+        if not isinstance(classifier, DigitClassifier):
+            msg = f"classifier must be a DigitClassifier, got {type(classifier).__name__}"
+            raise ValueError(msg)
+        if self.get_modality_mask_from_batch(batch) is not None:
+            msg = "a skill step decides what the model observes: a masked (7-tuple) batch already says what is seen"
+            raise ValueError(msg)
+        if self.state_carry is not None:
+            msg = "a skill step starts every row from its own frame 0: it does not combine with a set state_carry"
+            raise ValueError(msg)
+        actions = batch[0]
+        B, T = actions.shape[:2]
+        S, dev, q = wt.samples, actions.device, wt.query
+        if tuple(labels.shape) != (B, T) or labels.dtype not in (torch.int32, torch.int64) or labels.device != dev:
+            msg = f"labels must be an int32 / int64 tensor of shape {(B, T)} on {dev}, got {labels.dtype} {tuple(labels.shape)} on {labels.device}"
+            raise ValueError(msg)
+        if q > T:
+            msg = f"a batch of {T} frames has no context of {q}"
+            raise ValueError(msg)
+        if table is not None and (not isinstance(table, TransitionTable) or table.steps != T or table.buffer.device != dev):
+            msg = f"table must be a TransitionTable of {T} steps on {dev}"
+            raise ValueError(msg)
+        labels = labels.to(torch.int32)
+        wide = lambda x: x.repeat_interleave(S, dim=0)  # noqa: E731  (row (b, s) -> b * S + s)
+        word = wide(labels[:, q - 1]).contiguous()
+        if table is None:
+            table = TransitionTable(T, dev)
+        if wt.protocol == "reference":
+            noise = dict(noise or {})
+            audio_obs, vision_obs = self.get_observations_from_batch(batch)
+            conv.begin_step(dev)
+            state0 = self.initial_state((audio_obs[:, 0], vision_obs[:, 0]), noise)
+            state0 = self._state_like(state0, {k: wide(getattr(state0, k)) for k in self._FRESH_KEYS})
+            prior_noise = {}
+            for key in self._POST_KEYS:
+                prior_key = key.replace("post", "prior")
+                u = noise.get(prior_key)
+                k = self._category_size_of(key)
+                if u is not None and tuple(u.shape) != (B, S, 1, k):
+                    msg = f"noise[{prior_key!r}] must have shape {(B, S, 1, k)}, got {tuple(u.shape)}"
+                    raise ValueError(msg)
+                prior_noise[prior_key] = _rand(actions, B * S, 1, k) if u is None else u.reshape(B * S, 1, k).contiguous()
+            prior = self.rollout_transition(actions=wide(actions[:, q - 1 : q]).contiguous(), prev_state=state0, noise=prior_noise)
+            digits = self._read_vision(prior.feature, classifier)[:, 0]
+            word_counts(word, digits.contiguous(), table.q_counts)
+            return table
+        t_read = wt.read_frame(T)
+        out, _ = self._skill_rollout(batch, wt.skill, noise, None, expert_log_weights)
+        feature = self._feature_of(out)
+        if not wt.by_horizon:
+            digits = self._read_vision(feature[:, t_read : t_read + 1].contiguous(), classifier)[:, 0]
+            word_counts(word, digits.contiguous(), table.q_counts)
+            return table
+        planes = torch.empty(3, B, T, device=dev, dtype=torch.float32)
+        read = torch.empty(B * S, device=dev, dtype=torch.int32)
+        rows = max(1, int(wt.max_frames) // (S * T))
+        for r0 in range(0, B, rows):
+            r1 = min(B, r0 + rows)
+            d = self._read_vision(feature[r0 * S : r1 * S], classifier).reshape(r1 - r0, S, T)
+            read[r0 * S : r1 * S] = d[:, :, t_read].reshape(-1)
+            lab = labels[r0:r1]
+            live = lab >= 0
+            same = (d == lab[:, None]).sum(1).to(torch.float32)  # copies that read the frame's label
+            zero = torch.zeros((), device=dev)
+            planes[0, r0:r1] = torch.where(live, same / float(S), zero)
+            planes[1, r0:r1] = torch.where(live, (same > 0).to(torch.float32), zero)
+            planes[2, r0:r1] = live.to(torch.float32)
+        word_counts(word, read, table.q_counts)
+        context = torch.full((B,), q, dtype=torch.int32, device=dev)
+        frames = torch.zeros(T, device=dev)  # (the kernel's own count of all frames per bin: the table keeps the labelled ones)
+        ForecastSkill.table_add(planes, context, None, table.horizon, frames)
         return table
 
     def _category_size_of(self, key: str) -> int:  # noqa: ARG002

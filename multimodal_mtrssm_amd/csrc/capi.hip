@@ -88,6 +88,10 @@ int nll_masked_bwd_launch(const float*, const float*, const float*, const float*
 int ensemble_score_launch(const float*, const float*, const int32_t*, int64_t, int64_t, int64_t, int64_t, int, float*, float*, float*, float*, float*,
                           hipStream_t);
 int horizon_table_launch(const float*, int64_t, const int32_t*, const int32_t*, int64_t, int64_t, float*, float*, hipStream_t);
+int digit_features_launch(const float*, int64_t, const int32_t*, int64_t, int, const float*, const float*, const float*, const float*, float*,
+                          hipStream_t);
+int digit_head_launch(const float*, const float*, const float*, int64_t, const int32_t*, int64_t, int32_t*, float*, hipStream_t);
+int word_counts_launch(const int32_t*, const int32_t*, int64_t, float*, hipStream_t);
 int modality_dropout_launch(const float*, int64_t, int64_t, int64_t, float, float, int64_t, int64_t, int32_t*, float*, float*, unsigned char*, float*,
                             hipStream_t);
 int sumsq_launch(const float*, int64_t, float*, hipStream_t);
@@ -472,4 +476,15 @@ MTRSSM_API int mtrssm_ensemble_score(const float* pred, const float* target, con
 MTRSSM_API int mtrssm_horizon_table(const float* planes, int64_t P, const int32_t* context, const int32_t* valid, int64_t B, int64_t T,
                                     float* sums, float* counts, void* stream) {
   return horizon_table_launch(planes, P, context, valid, B, T, sums, counts, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_digit_features(const float* pred, int64_t frames, const int32_t* select, int64_t N, int32_t act, const float* conv1_w,
+                                     const float* conv1_b, const float* conv2_w, const float* conv2_b, float* features, void* stream) {
+  return digit_features_launch(pred, frames, select, N, act, conv1_w, conv1_b, conv2_w, conv2_b, features, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_digit_head(const float* hidden, const float* w, const float* b, int64_t N, const int32_t* select, int64_t frames,
+                                 int32_t* digit, float* logits, void* stream) {
+  return digit_head_launch(hidden, w, b, N, select, frames, digit, logits, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_word_counts(const int32_t* word, const int32_t* digit, int64_t N, float* counts, void* stream) {
+  return word_counts_launch(word, digit, N, counts, static_cast<hipStream_t>(stream));
 }
