@@ -306,13 +306,19 @@ __global__ void categorical_sample_fwd_kernel(const float* __restrict__ logits, 
   for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
   float sum = 0.f;
   for (int c = 0; c < C; ++c) sum += expf(x[c] - m);
-  const float ls = logf(sum), uu = u[i];
+  // The log-probabilities reach |logp| > 8, where `(x - m) - logf(sum)` in fp32 is three roundings of up to half an ulp
+  // (4.8e-7) each: the log-sum and the differences in double, one rounding at the end (a thread per categorical, once per
+  // rollout: no cost).  Probabilities and the sample stay the fp32 left fold the scans and the host use.
+  double dsum = 0.0;
+  for (int c = 0; c < C; ++c) dsum += exp((double)x[c] - (double)m);
+  const double ls = log(dsum);
+  const float uu = u[i];
   float acc = 0.f;
   int idx = 0;
   for (int c = 0; c < C; ++c) {
     const float p = expf(x[c] - m) / sum;
     probs[i * C + c] = p;
-    logp[i * C + c] = (x[c] - m) - ls;
+    logp[i * C + c] = (float)(((double)x[c] - (double)m) - ls);
     acc += p;
     if (c + 1 < C && acc <= uu) ++idx;
   }

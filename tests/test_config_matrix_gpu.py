@@ -71,27 +71,25 @@ def _scan_kernels(family: str, case, pieces: int) -> tuple[str, str]:  # noqa: A
 _WIDE_PIECES = 3  # the wide families run on three bf16 pieces per operand: what the value tolerance below is stated for
 
 
-@pytest.mark.parametrize("option_set", OPTION_SETS)
-@pytest.mark.parametrize("case_id", list(SCAN_CASES))
-def test_scan_family_with_options_matches_oracle(case_id: str, option_set: str, lib_loaded: None) -> None:  # noqa: PLR0914, PLR0915
-    """One scan family (single-CU MRSSM / cluster 32, 64, 128, 200 / wide MRSSM with D != H / single-CU and wide MMTRSSM) under one
-    option set (ReLU; Tanh with plain KL, kl_coeff 0.7, w_kl_h 0.3; Identity) against the oracle: the rollout's values and
-    samples, every loss and every parameter gradient, and the names of the forward and BPTT kernels that ran."""
+def compare_scan_family(case, family: str, oracle, batch, noise, *, pieces: int = _WIDE_PIECES, grads: bool = True):  # noqa: ANN001, ANN201, PLR0913, PLR0914, PLR0915
+    """One train step of ``case`` on the GPU against ``oracle`` on the same batch and noise: the rollout's values and samples,
+    every loss, every parameter gradient (unless ``grads`` is off) and the names of the forward and BPTT kernels that ran, which
+    must be ``family``'s.  The wide families run on ``pieces`` bf16 pieces per operand; the tolerances are the docstring's at
+    three pieces, and at two those ``scan.py`` states for them (probabilities 1e-5 + 5e-6, losses 1e-4 relative, gradients 1e-3;
+    deter / hidden carry no stated bound there and are left to the three-piece run).  Returns (model, train step's output,
+    initial state, posterior, prior) for further checks."""
     from multimodal_mtrssm_amd import _lib, scan
 
-    base, family = SCAN_CASES[case_id]
-    case = with_options(base, **options(base, option_set))
     d = case.dims
     wide = family in {"wide", "mt_wide"}
-    oracle = build_model(case)
-    batch = build_batch(case)
-    noise, _margin, _seed = screened(case, oracle, batch, relu_margin_for(case_id, option_set))
+    two = wide and pieces == 2  # noqa: PLR2004
     ref = oracle.shared_step(batch, noise)
+    oracle.zero_grad(set_to_none=True)
     ref["loss"].backward()
     model = product_from_case(case, oracle, DEV)
     gbatch, gnoise = tuple(b.to(DEV) for b in batch), _to(noise, DEV)
     saved = scan.WIDE_PIECES
-    scan.WIDE_PIECES = _WIDE_PIECES
+    scan.WIDE_PIECES = pieces
     _lib.TIMERS.enable()
     try:
         with torch.no_grad():
@@ -107,7 +105,7 @@ def test_scan_family_with_options_matches_oracle(case_id: str, option_set: str, 
         scan.WIDE_PIECES = saved
     # (2) the family that ran: the scan kernels among the timed launches are exactly the intended forward and BPTT kernels
     # (a silent fallback to the single-CU scan would pass everything below for the wrong kernel)
-    fwd, bwd = _scan_kernels(family, case, _WIDE_PIECES)
+    fwd, bwd = _scan_kernels(family, case, pieces)
     scans = {k for k in launched if k.startswith(("mtrssm::mrssm_", "mtrssm::mmtrssm_"))}
     assert any(k.startswith(fwd) for k in scans), (fwd, sorted(scans))
     assert any(k.startswith(bwd) for k in scans), (bwd, sorted(scans))
@@ -117,13 +115,15 @@ def test_scan_family_with_options_matches_oracle(case_id: str, option_set: str, 
     if case.kind == "mrssm":
         np.testing.assert_allclose(_np(state0.deter), ref["_deter0"].detach().numpy(), atol=1e-5)
         assert (_index(state0.stoch, d.cats, d.classes) == _index(ref["_stoch0"], d.cats, d.classes)).all()
-        np.testing.assert_allclose(_np(post.deter), ref["_deter"].detach().numpy(), atol=atol, err_msg="deter")
+        if not two:
+            np.testing.assert_allclose(_np(post.deter), ref["_deter"].detach().numpy(), atol=atol, err_msg="deter")
         pairs = [(post.distribution.probs, ref["_post_logits"], post.stoch, ref["_post_stoch"], d.cats, d.classes),
                  (prior.distribution.probs, ref["_prior_logits"], prior.stoch, ref["_prior_stoch"], d.cats, d.classes)]
     else:
         for k in ("deter_l", "deter_h", "hidden_l", "hidden_h"):
             np.testing.assert_allclose(_np(getattr(state0, k)), ref[f"_init_{k}"].detach().numpy(), atol=1e-5, err_msg=f"init {k}")
-            np.testing.assert_allclose(_np(getattr(post, k)), ref[f"_{k}"].detach().numpy(), atol=atol, err_msg=k)
+            if not two:
+                np.testing.assert_allclose(_np(getattr(post, k)), ref[f"_{k}"].detach().numpy(), atol=atol, err_msg=k)
         assert (_index(state0.stoch_l, d.ls_cats, d.ls_classes) == _index(ref["_init_stoch_l"], d.ls_cats, d.ls_classes)).all()
         assert (_index(state0.stoch_h, d.hs_cats, d.hs_classes) == _index(ref["_init_stoch_h"], d.hs_cats, d.hs_classes)).all()
         pairs = [(post.distribution_l.probs, ref["_post_logits_l"], post.stoch_l, ref["_post_stoch_l"], d.ls_cats, d.ls_classes),
@@ -139,8 +139,8 @@ def test_scan_family_with_options_matches_oracle(case_id: str, option_set: str, 
     # (4) losses and gradients
     assert set(out) == {k for k in ref if not k.startswith("_")}
     for k in out:
-        np.testing.assert_allclose(float(out[k].detach()), float(ref[k].detach()), rtol=2e-5, err_msg=k)
-    if not (option_set == "relu" and case_id in RELU_VALUES_ONLY):
+        np.testing.assert_allclose(float(out[k].detach()), float(ref[k].detach()), rtol=1e-4 if two else 2e-5, err_msg=k)
+    if grads:
         want = {k: p.grad for k, p in oracle.named_parameters() if p.grad is not None}
         got = dict(model.named_parameters())
         assert len(want) > 40
@@ -152,6 +152,21 @@ def test_scan_family_with_options_matches_oracle(case_id: str, option_set: str, 
     # (5) no cooperative launch gave up on an exchange
     if family != "scan" and family != "mt_scan":
         scan.check_cluster_status()
+    return model, out, state0, post, prior
+
+
+@pytest.mark.parametrize("option_set", OPTION_SETS)
+@pytest.mark.parametrize("case_id", list(SCAN_CASES))
+def test_scan_family_with_options_matches_oracle(case_id: str, option_set: str, lib_loaded: None) -> None:
+    """One scan family (single-CU MRSSM / cluster 32, 64, 128, 200 / wide MRSSM with D != H / single-CU and wide MMTRSSM) under one
+    option set (ReLU; Tanh with plain KL, kl_coeff 0.7, w_kl_h 0.3; Identity) against the oracle: the rollout's values and
+    samples, every loss and every parameter gradient, and the names of the forward and BPTT kernels that ran."""
+    base, family = SCAN_CASES[case_id]
+    case = with_options(base, **options(base, option_set))
+    oracle = build_model(case)
+    batch = build_batch(case)
+    noise, _margin, _seed = screened(case, oracle, batch, relu_margin_for(case_id, option_set))
+    compare_scan_family(case, family, oracle, batch, noise, grads=not (option_set == "relu" and case_id in RELU_VALUES_ONLY))
 
 
 @pytest.mark.parametrize("case_id", ["mrssm_nonsquare", "mmtrssm_default"])
