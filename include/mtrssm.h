@@ -239,6 +239,85 @@ int mtrssm_mrssm_rollout_bwd_wide(const MtrssmMrssmDims* dims, const MtrssmMrssm
 int mtrssm_mrssm_rollout_bwd(const MtrssmMrssmDims* dims, const MtrssmMrssmBwdWeights* w,
                              const MtrssmMrssmBwdIO* io, void* stream);
 
+/* The initial state of a rollout in one launch each way (csrc/init_state.hip; replaces core.py:121-135 = the mean of the two
+ * frame-0 embeddings, init_proj, the prior head, the categorical head -- and their autograd):
+ *   e = mean over the present modalities of (ea, ev);  z1 = wi1 e + bi1;  deter0 = wi2 act_i(z1) + bi2;
+ *   zp = wp1 deter0 + bp1;  logits = wp2 act_p(zp) + bp2;  (logp, probs, stoch) = the categorical head of
+ *   mtrssm_categorical_sample_fwd (same device code) on K categoricals of C classes with the uniforms u.
+ * _bwd: from g_deter0 / g_stoch0 / g_logp / g_probs (each may be NULL = zero) it writes the pre-activation gradients d_logits,
+ * d_zp, g_deter (= g_deter0 + the head's), d_z1 and the frame-0 embedding gradients g_ea / g_ev (either may be NULL; a row's
+ * absent modality gets zeros; _bwd never reads through ea / ev, it only asks whether each is NULL, so any non-NULL pointer
+ * with a stride >= E stands for "given").  Weight and bias gradients are GEMMs of these with (e, z1, deter0, zp): the caller's.
+ * One workgroup per batch row, no workspace, capturable.  _supported() = 0 for everything the kernels were not written for (an
+ * unknown activation id, depth != 1, a layer wider than 1024, more than 2 MB of weights -- every row's workgroup streams them
+ * all, which pays only while they are a small L2-resident set): run the layer-by-layer path then. */
+typedef struct MtrssmInitialState {
+  const float* ea;         /* frame-0 audio embedding rows, row b at ea + b * ea_stride; NULL = absent for every row */
+  const float* ev;         /* the same for vision; at least one of the two */
+  int64_t ea_stride, ev_stride;
+  const uint8_t* mask0;    /* [B][2] (audio, vision) presence at t = 0, NULL = both; read when both embeddings are given */
+  const float* u;          /* [B][K] uniforms */
+  const float* wi1;        /* [cells][E]  init_proj.0 */
+  const float* bi1;
+  const float* wi2;        /* [D][cells]  init_proj.2 */
+  const float* bi2;
+  const float* wp1;        /* [H][D]      rnn_to_prior_projector.0 */
+  const float* bp1;
+  const float* wp2;        /* [K*C][H]    rnn_to_prior_projector.2 */
+  const float* bp2;
+  int32_t ld_wi1, ld_wi2, ld_wp1, ld_wp2;   /* floats per weight row */
+  int32_t B, E, cells, D, H, K, C, act_i, act_p, depth_i, depth_p;
+  float* e;                /* [B][E]      forward outputs (the backward reads z1, zp, probs) */
+  float* z1;               /* [B][cells] */
+  float* deter0;           /* [B][D] */
+  float* zp;               /* [B][H] */
+  float* logp;             /* [B][K][C] */
+  float* probs;            /* [B][K][C] */
+  float* stoch;            /* [B][K*C]    one-hot sample */
+  const float* g_deter0;   /* [B][D]      backward inputs */
+  const float* g_stoch0;   /* [B][K*C] */
+  const float* g_logp;     /* [B][K][C] */
+  const float* g_probs;    /* [B][K][C] */
+  float* d_logits;         /* [B][K*C]    backward outputs */
+  float* d_zp;             /* [B][H] */
+  float* g_deter;          /* [B][D] */
+  float* d_z1;             /* [B][cells] */
+  float* g_ea;             /* [B][E] */
+  float* g_ev;             /* [B][E] */
+} MtrssmInitialState;
+int mtrssm_initial_state_supported(const MtrssmInitialState* p);
+int mtrssm_initial_state_fwd(const MtrssmInitialState* p, void* stream);
+int mtrssm_initial_state_bwd(const MtrssmInitialState* p, void* stream);
+
+/* The weight layouts of MtrssmMrssmClusterWeights in ONE launch from the raw parameters (csrc/scan_prepare.hip), into one
+ * caller-owned buffer `out` of mtrssm_mrssm_scan_prepare_layout() floats:
+ *   w1s_t [S][H] = w1[:, A:]^T,  whh_t [D][3D] = whh^T,  wh1_t [D][3H] = [w3 ; wa1[:, :D] ; wv1[:, :D]]^T   (exact copies)
+ *   wf_t [H][3D]: wf_t[k][j] = sum_h w2[h][k] wih[j][h],  bf [3D]: bf[j] = sum_h b2[h] wih[j][h] + bih[j]      (product != 0)
+ * each sum ONE fp32 fma chain over ascending h starting from zero (bih added last): mtrssm_gemm's arithmetic when it does not
+ * split its reduction.  product = 0 leaves wf_t and bf unwritten (the caller forms them with mtrssm_gemm: at large H the
+ * MFMA tile kernel is the faster tool); w2, b2, wih, bih may then be NULL.  Every matrix comes with its leading dimension
+ * (floats per row): views of a flat parameter buffer need no copy.  Independent tiles, no workspace, capturable. */
+typedef struct MtrssmScanPrepare {
+  const float* w1;   /* [H][A+S] action_state_projector.0.weight */
+  const float* w2;   /* [H][H] */
+  const float* b2;   /* [H] */
+  const float* wih;  /* [3D][H] */
+  const float* bih;  /* [3D] */
+  const float* whh;  /* [3D][D] */
+  const float* w3;   /* [H][D]   prior head, layer 0 */
+  const float* wa1;  /* [H][D+E] audio posterior head, layer 0 (columns [0, D) are read) */
+  const float* wv1;  /* [H][D+E] vision posterior head, layer 0 */
+  int32_t ld_w1, ld_w2, ld_wih, ld_whh, ld_w3, ld_wa1, ld_wv1;
+  int32_t D, H, S, A;
+  int32_t product;
+  float* out;
+  int64_t out_floats;
+} MtrssmScanPrepare;
+/* Size of `out` in floats (0: bad dims); offsets[5] (may be NULL) receives where w1s_t, whh_t, wh1_t, wf_t, bf start, each a
+ * multiple of 64 floats. */
+int64_t mtrssm_mrssm_scan_prepare_layout(int32_t D, int32_t H, int32_t S, int64_t* offsets);
+int mtrssm_mrssm_scan_prepare(const MtrssmScanPrepare* p, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * MoPoE-MMTRSSM scan (two-timescale MTState variant).  Replaces the T loop of
  * MoPoE_MMTRSSM.rollout_representation (mmtrssm/mopoe_mmtrssm/core.py:405-490): MTRNN (:59-60),

@@ -50,6 +50,16 @@ MrssmBwdIO = _struct("MtrssmMrssmBwdIO", _ptrs(
     "g_deter", "g_post_stoch", "g_prior_stoch", "g_post_logits", "g_prior_logits", "g_kl",
     "g_deter0", "g_stoch0", "d_z1", "d_h2", "d_gi", "d_gh", "d_zh", "d_lp", "d_la", "d_lv", "expert_logw", "g_expert_logw", "modality"))
 
+ScanPrepare = _struct("MtrssmScanPrepare", _ptrs("w1", "w2", "b2", "wih", "bih", "whh", "w3", "wa1", "wv1") + [(n, _i) for n in (
+    "ld_w1", "ld_w2", "ld_wih", "ld_whh", "ld_w3", "ld_wa1", "ld_wv1", "D", "H", "S", "A", "product")]
+    + [("out", _p), ("out_floats", C.c_int64)])
+
+InitialState = _struct("MtrssmInitialState", _ptrs("ea", "ev") + [("ea_stride", C.c_int64), ("ev_stride", C.c_int64)] + _ptrs(
+    "mask0", "u", "wi1", "bi1", "wi2", "bi2", "wp1", "bp1", "wp2", "bp2") + [(n, _i) for n in (
+    "ld_wi1", "ld_wi2", "ld_wp1", "ld_wp2", "B", "E", "cells", "D", "H", "K", "C", "act_i", "act_p", "depth_i", "depth_p")] + _ptrs(
+    "e", "z1", "deter0", "zp", "logp", "probs", "stoch", "g_deter0", "g_stoch0", "g_logp", "g_probs",
+    "d_logits", "d_zp", "g_deter", "d_z1", "g_ea", "g_ev"))
+
 MmtrssmDims = _struct("MtrssmMmtrssmDims", [
     ("B", _i), ("T", _i), ("LD", _i), ("HD", _i), ("H", _i), ("KL", _i), ("CL", _i), ("KH", _i), ("CH", _i),
     ("act", _i), ("post", _i), ("tau_l", _f), ("tau_h", _f), ("keep_l", _f), ("keep_h", _f),
@@ -106,6 +116,11 @@ SYMBOLS: dict[str, tuple[type | None, list[type]]] = {
     "mtrssm_mrssm_rollout_fwd_wide": (C.c_int, [C.POINTER(MrssmDims), C.POINTER(MrssmClusterWeights), C.POINTER(MrssmFwdIO), _i, _p, C.c_int64, _p]),
     "mtrssm_mrssm_rollout_bwd_wide": (C.c_int, [C.POINTER(MrssmDims), C.POINTER(MrssmClusterWeights), C.POINTER(MrssmBwdIO), _i, _p, C.c_int64, _p]),
     "mtrssm_mrssm_rollout_bwd": (C.c_int, [C.POINTER(MrssmDims), C.POINTER(MrssmBwdWeights), C.POINTER(MrssmBwdIO), _p]),
+    "mtrssm_initial_state_supported": (C.c_int, [C.POINTER(InitialState)]),
+    "mtrssm_initial_state_fwd": (C.c_int, [C.POINTER(InitialState), _p]),
+    "mtrssm_initial_state_bwd": (C.c_int, [C.POINTER(InitialState), _p]),
+    "mtrssm_mrssm_scan_prepare_layout": (C.c_int64, [_i, _i, _i, C.POINTER(C.c_int64)]),
+    "mtrssm_mrssm_scan_prepare": (C.c_int, [C.POINTER(ScanPrepare), _p]),
     "mtrssm_mmtrssm_rollout_fwd": (C.c_int, [C.POINTER(MmtrssmDims), C.POINTER(MmtrssmFwdWeights), C.POINTER(MmtrssmFwdIO), _p]),
     "mtrssm_mmtrssm_rollout_bwd": (C.c_int, [C.POINTER(MmtrssmDims), C.POINTER(MmtrssmBwdWeights), C.POINTER(MmtrssmBwdIO), _p]),
     "mtrssm_mmtrssm_wide_supported": (C.c_int, [C.POINTER(MmtrssmDims), _i]),

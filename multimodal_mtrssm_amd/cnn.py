@@ -30,7 +30,7 @@ import torch
 from torch import Tensor, nn
 
 from multimodal_mtrssm_amd import _lib
-from multimodal_mtrssm_amd.linear import linear
+from multimodal_mtrssm_amd.linear import SPLIT_MIN_FLOPS, linear, linear_group
 from multimodal_mtrssm_amd.conv import (
     gemm_pieces,
     conv2d,
@@ -124,7 +124,14 @@ def decode_pair(dec_a: "Decoder", dec_b: "Decoder", fa: Tensor, fb: Tensor, *, r
     """``(dec_a(fa), dec_b(fb))`` with the layers of the two stacks that have the same shape sharing their launches.
     ``raw``: without the final ``out_activation`` (the fused Gaussian NLL applies it while it reads the prediction)."""
     lead_a, lead_b = fa.shape[:-1], fb.shape[:-1]
-    xa, xb = dec_a.stem(fa), dec_b.stem(fb)
+    first_a = first_b = None
+    # the two first Linear layers are independent: one launch each way (latency-bound ones; a large one keeps its own launch and
+    # the stack's operand format)
+    if len(dec_a.linears) > 0 and len(dec_b.linears) > 0 and all(
+            2.0 * f.numel() * d.linears[0].weight.shape[0] < SPLIT_MIN_FLOPS for f, d in ((fa, dec_a), (fb, dec_b))):
+        first_a, first_b = linear_group([(f.reshape(-1, f.shape[-1]), d.linears[0].weight, d.linears[0].bias, 0)
+                                         for f, d in ((fa, dec_a), (fb, dec_b))])
+    xa, xb = dec_a.stem(fa, first_a), dec_b.stem(fb, first_b)
     xa, xb = _res_pair(dec_a.res, dec_b.res, xa, xb)
     if len(dec_a.deconvs) != len(dec_b.deconvs) or (len(dec_a.res) > 0) != (len(dec_b.res) > 0):
         return dec_a.tail(xa, lead_a, raw=raw), dec_b.tail(xb, lead_b, raw=raw)
@@ -264,12 +271,16 @@ class Decoder(nn.Module):
         name = type(self.out_act).__name__
         return {"Identity": 0, "Tanh": 3}.get(name)
 
-    def stem(self, f: Tensor) -> Tensor:
+    def stem(self, f: Tensor, first: Tensor | None = None) -> Tensor:
+        """``first``: the first Linear's output where the caller has formed it already (``decode_pair``)."""
         if len(self.linears) == 0:
             self.materialize(f.shape[-1])
             self.to(f.device)
         x = f.reshape(-1, f.shape[-1])
         for i, lin in enumerate(self.linears):
+            if i == 0 and first is not None:
+                x = first
+                continue
             x = linear(x, lin.weight, lin.bias, pre_act=self.act_id if i > 0 else 0, pieces=gemm_pieces())
         return x.reshape(-1, *self.conv_in_shape)
 

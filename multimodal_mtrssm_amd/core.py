@@ -106,6 +106,112 @@ class _CategoricalHead(torch.autograd.Function):
         return d, None, None, None
 
 
+FUSED_INITIAL_STATE = True  # False: the initial state layer by layer (A/B runs, tests)
+
+
+def _initial_state_problem(ea, ev, mask0, u, params, acts, depths, cats: int, classes: int):  # noqa: ANN001, ANN202, PLR0913
+    """The ``MtrssmInitialState`` of one call with its extents, strides, activations and depths set and every pointer NULL
+    (``_InitialState`` fills them in), or None where an operand is not what the kernels take (then the layer-by-layer path
+    runs).  ``u`` may be None: whether the kernels apply is decided BEFORE the uniforms are drawn, so that a refused call leaves
+    the draw to the path that runs.  ``params``: init_proj.0 / .2 and prior head .0 / .2 weights and biases; the embeddings are
+    ``[B, E]`` views (frame 0 of ``[B, T, E]``: read in place through their row stride)."""
+    from multimodal_mtrssm_amd import _lib  # noqa: PLC0415
+
+    ref = ea if ea is not None else ev
+    if ref is None or any(p is None for p in params) or any(a is None for a in acts):
+        return None
+    tensors = [t for t in (ea, ev, u, *params) if t is not None]
+    if not all(t.is_cuda and t.dtype == torch.float32 for t in tensors) or ref.dim() != 2 or any(t.stride(-1) != 1 for t in tensors):  # noqa: PLR2004
+        return None
+    if any(e is not None and (e.shape != ref.shape or (e.shape[0] > 1 and e.stride(0) < e.shape[1])) for e in (ea, ev)):
+        return None
+    if mask0 is not None and (mask0.dtype != torch.bool or tuple(mask0.shape) != (ref.shape[0], 2) or not mask0.is_contiguous()):
+        return None
+    wi1, bi1, wi2, bi2, wp1, bp1, wp2, bp2 = params
+    B, E = ref.shape
+    cells, D, H, S = wi1.shape[0], wi2.shape[0], wp1.shape[0], wp2.shape[0]
+    if (wi1.shape[1], wi2.shape[1], wp1.shape[1], wp2.shape[1], S) != (E, cells, D, H, cats * classes):
+        return None
+    if u is not None and (tuple(u.shape) != (B, cats) or not u.is_contiguous()):
+        return None
+    if any(b.shape != (w.shape[0],) or not b.is_contiguous() for w, b in ((wi1, bi1), (wi2, bi2), (wp1, bp1), (wp2, bp2))):
+        return None
+    p = _lib.InitialState()
+    p.ea_stride = 0 if ea is None else max(int(ea.stride(0)), E)
+    p.ev_stride = 0 if ev is None else max(int(ev.stride(0)), E)
+    p.ld_wi1, p.ld_wi2, p.ld_wp1, p.ld_wp2 = (max(int(w.stride(0)), w.shape[1]) for w in (wi1, wi2, wp1, wp2))
+    p.B, p.E, p.cells, p.D, p.H, p.K, p.C = B, E, cells, D, H, cats, classes
+    p.act_i, p.act_p = acts
+    p.depth_i, p.depth_p = depths
+    if not _lib.load().mtrssm_initial_state_supported(p):
+        return None
+    return p
+
+
+class _InitialState(torch.autograd.Function):
+    """The whole initial state -- masked mean of the frame-0 embeddings, ``init_proj``, the prior head, the categorical head --
+    in ONE launch each way (``mtrssm_initial_state_fwd`` / ``_bwd``, csrc/init_state.hip).  Same values as the layer-by-layer
+    path (``MLP.forward`` + ``_CategoricalHead``) up to the order of the fp32 sums.  The weight and bias gradients stay GEMMs on
+    the pre-activation gradients the backward kernel leaves behind: ``linear.weight_grad``, straight into the flat gradient
+    buffer and deferred to the end of the pass like every other Linear's.  ``problem``: ``_initial_state_problem``'s struct for
+    exactly these operands (its bytes are kept; every tensor the backward reads goes through ``save_for_backward``; the
+    embeddings are not among them: the backward kernel only asks which of the two was given)."""
+
+    @staticmethod
+    def forward(ctx, problem, mask0, ea, ev, u, wi1, bi1, wi2, bi2, wp1, bp1, wp2, bp2):  # noqa: ANN001, ANN205, PLR0913
+        from multimodal_mtrssm_amd import _lib  # noqa: PLC0415
+
+        ctx.set_materialize_grads(False)
+        params = (wi1, bi1, wi2, bi2, wp1, bp1, wp2, bp2)
+        p = type(problem).from_buffer_copy(problem)
+        new = lambda *shape: torch.empty(shape, device=u.device, dtype=torch.float32)  # noqa: E731
+        e, z1, deter0, zp = new(p.B, p.E), new(p.B, p.cells), new(p.B, p.D), new(p.B, p.H)
+        logp, probs, stoch = new(p.B, p.K, p.C), new(p.B, p.K, p.C), new(p.B, p.K * p.C)
+        p.ea, p.ev, p.mask0, p.u = _lib.raw_ptr(ea), _lib.raw_ptr(ev), _lib.raw_ptr(mask0), _lib.ptr(u)
+        p.wi1, p.bi1, p.wi2, p.bi2, p.wp1, p.bp1, p.wp2, p.bp2 = map(_lib.raw_ptr, params)
+        p.e, p.z1, p.deter0, p.zp, p.logp, p.probs, p.stoch = map(_lib.ptr, (e, z1, deter0, zp, logp, probs, stoch))
+        _lib.check(_lib.TIMERS.call("mtrssm_initial_state_fwd", _lib.load().mtrssm_initial_state_fwd, p, _lib.stream_ptr(u.device)),
+                   "mtrssm_initial_state_fwd")
+        ctx.plan, ctx.given, ctx.has_mask = bytes(problem), (ea is not None, ev is not None), mask0 is not None
+        saved = (e, z1, deter0, zp, probs, *params) + ((mask0,) if mask0 is not None else ())
+        ctx.save_for_backward(*saved)
+        ctx.mark_non_differentiable(e)
+        return deter0, stoch, logp, probs, e
+
+    @staticmethod
+    def backward(ctx, g_deter0, g_stoch, g_logp, g_probs, _g_e):  # noqa: ANN001, ANN205
+        from multimodal_mtrssm_amd import _lib  # noqa: PLC0415
+        from multimodal_mtrssm_amd.linear import weight_grad  # noqa: PLC0415
+
+        if g_deter0 is None and g_stoch is None and g_logp is None and g_probs is None:
+            return (None,) * 13
+        e, z1, deter0, zp, probs, *rest = ctx.saved_tensors
+        params, mask0 = rest[:8], (rest[8] if ctx.has_mask else None)
+        p = _lib.InitialState.from_buffer_copy(ctx.plan)
+        new = lambda *shape: torch.empty(shape, device=e.device, dtype=torch.float32)  # noqa: E731
+        gs = [None if g is None else g.contiguous().float() for g in (g_deter0, g_stoch, g_logp, g_probs)]
+        d_logits, d_zp, g_deter, d_z1 = new(p.B, p.K * p.C), new(p.B, p.H), new(p.B, p.D), new(p.B, p.cells)
+        g_ea = new(p.B, p.E) if ctx.needs_input_grad[2] else None
+        g_ev = new(p.B, p.E) if ctx.needs_input_grad[3] else None
+        # (the backward kernel reads of ea / ev only whether each was given: the mean embedding stands in for the pointer)
+        p.ea, p.ev = (_lib.ptr(e) if given else None for given in ctx.given)
+        p.ea_stride, p.ev_stride = (p.E if given else 0 for given in ctx.given)
+        p.mask0 = _lib.raw_ptr(mask0)
+        p.wi1, p.bi1, p.wi2, p.bi2, p.wp1, p.bp1, p.wp2, p.bp2 = map(_lib.raw_ptr, params)
+        p.z1, p.zp, p.probs = _lib.ptr(z1), _lib.ptr(zp), _lib.ptr(probs)
+        p.g_deter0, p.g_stoch0, p.g_logp, p.g_probs = map(_lib.ptr, gs)
+        p.d_logits, p.d_zp, p.g_deter, p.d_z1, p.g_ea, p.g_ev = map(_lib.ptr, (d_logits, d_zp, g_deter, d_z1, g_ea, g_ev))
+        _lib.check(_lib.TIMERS.call("mtrssm_initial_state_bwd", _lib.load().mtrssm_initial_state_bwd, p, _lib.stream_ptr(e.device)),
+                   "mtrssm_initial_state_bwd")
+        wi1, bi1, wi2, bi2, wp1, bp1, wp2, bp2 = params
+        need = ctx.needs_input_grad
+        grads = []
+        for j, (gy, x, w, b, act) in enumerate(((d_z1, e, wi1, bi1, 0), (g_deter, z1, wi2, bi2, p.act_i), (d_zp, deter0, wp1, bp1, 0),
+                                                (d_logits, zp, wp2, bp2, p.act_p))):
+            grads += weight_grad(gy, x, w, b, act_x=act, want_weight=need[5 + 2 * j], want_bias=need[6 + 2 * j])
+        return (None, None, g_ea, g_ev, None, *grads)
+
+
 class _ElboCombine(torch.autograd.Function):
     """``recon = nll_a + nll_v; kl_j = coeff_j mean(kl_bt_j); loss = recon + sum kl_j`` in one launch each way
     (``mtrssm_elbo_combine_fwd / _bwd``) instead of the eager add / mean / mul / add chain and its autograd nodes."""
@@ -506,7 +612,34 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         return {"recon": audio + vision, "recon/audio": audio, "recon/vision": vision}
 
     # -- states ---------------------------------------------------------------------------------
+    def _initial_fused(self, ea: Tensor | None, ev: Tensor | None, mask0: Tensor | None, u_init: Tensor | None) -> State | None:
+        """The initial state of the mean embedding of (``ea``, ``ev``) -- ``[B, E]`` each, one may be None -- in one launch
+        (``_InitialState``), or None where the kernels do not apply (then the caller runs the layer-by-layer path)."""
+        from multimodal_mtrssm_amd import _lib  # noqa: PLC0415
+        from multimodal_mtrssm_amd.networks import MLP  # noqa: PLC0415
+
+        proj, head = self.init_proj, self.transition.rnn_to_prior_projector
+        ref = ea if ea is not None else ev
+        if not FUSED_INITIAL_STATE or ref is None or not ref.is_cuda or not isinstance(proj, MLP) or not isinstance(head, MLP):
+            return None
+        if len(proj) != 3 or len(head) != 3 or proj.activate_last_layer or head.activate_last_layer:  # noqa: PLR2004
+            return None
+        factory = self.representation.distribution_factory
+        params = (proj[0].weight, proj[0].bias, proj[2].weight, proj[2].bias, head[0].weight, head[0].bias, head[2].weight, head[2].bias)
+        acts = (_lib.ACT_IDS.get(proj.activation_name), _lib.ACT_IDS.get(head.activation_name))
+        u = None if u_init is None else u_init.to(ref).contiguous()
+        problem = _initial_state_problem(ea, ev, mask0, u, params, acts, (proj.depth, head.depth), factory.category_size, factory.class_size)
+        if problem is None:
+            return None  # (nothing has been drawn: the layer-by-layer path makes its own draw)
+        if u is None:  # (the draw MultiOneHot.rsample would make: injected noise tape or the device generator)
+            u = draw_uniforms((ref.shape[0], factory.category_size), ref).contiguous()
+        deter, stoch, logp, probs, _ = _InitialState.apply(problem, mask0, ea, ev, u, *params)
+        return State(deter=deter, distribution=MultiOneHot(logp, probs), stoch=stoch)
+
     def _initial_from_embed(self, obs_embed: Tensor, u_init: Tensor | None) -> State:
+        fused = self._initial_fused(obs_embed, None, None, u_init) if obs_embed.dim() == 2 else None  # noqa: PLR2004
+        if fused is not None:
+            return fused
         deter = self.init_proj(obs_embed)
         logits = self.transition.rnn_to_prior_projector(deter)
         dist, stoch = _sampled_head(self.representation.distribution_factory, logits, u_init)
@@ -1112,8 +1245,10 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         conv.begin_step(audio_obs.device)
         audio_embed, vision_embed = self._encode_both(audio_obs, vision_obs)
         u_init = None if noise is None else noise.get("u_init")
-        state0 = self._initial_from_embed(_masked_mean_embed(audio_embed[:, 0], vision_embed[:, 0], None if sm is None else sm.mask0),
-                                          u_init)
+        mask0 = None if sm is None else sm.mask0
+        state0 = self._initial_fused(audio_embed[:, 0], vision_embed[:, 0], mask0, u_init)  # (the mean is inside the launch)
+        if state0 is None:
+            state0 = self._initial_from_embed(_masked_mean_embed(audio_embed[:, 0], vision_embed[:, 0], mask0), u_init)
         state0 = self._state0(state0, carry)
         out = self._rollout_embedded(action_input, audio_embed, vision_embed, state0, noise, sample_prior=False,
                                      modality=None if sm is None else sm.codes, expert_log_weights=expert_log_weights)

@@ -113,6 +113,11 @@ size_t mrssm_wide_workspace_bytes(const MtrssmMrssmDims*, int);
 size_t mrssm_wide_bwd_workspace_bytes(const MtrssmMrssmDims*, int);
 int mrssm_wide_fwd_launch(const MtrssmMrssmDims*, const MtrssmMrssmClusterWeights*, const MtrssmMrssmFwdIO*, int, void*, size_t, hipStream_t);
 int mrssm_wide_bwd_launch(const MtrssmMrssmDims*, const MtrssmMrssmClusterWeights*, const MtrssmMrssmBwdIO*, int, void*, size_t, hipStream_t);
+int64_t mrssm_scan_prepare_layout(int, int, int, int64_t*);
+int initial_state_supported(const MtrssmInitialState*);
+int initial_state_fwd_launch(const MtrssmInitialState*, hipStream_t);
+int initial_state_bwd_launch(const MtrssmInitialState*, hipStream_t);
+int mrssm_scan_prepare_launch(const MtrssmScanPrepare*, hipStream_t);
 int adamw_prepare_launch(const float*, int64_t, float*, float*, const int*, float, float, hipStream_t);
 int adamw_apply_launch(float*, const float*, float*, float*, const unsigned char*, int64_t, const float*, const float*, const int*, float, float, float,
                        float, float, float, hipStream_t);
@@ -282,6 +287,19 @@ MTRSSM_API int mtrssm_mmtrssm_rollout_bwd_wide(const MtrssmMmtrssmDims* d, const
 MTRSSM_API int mtrssm_gemm(const MtrssmGemm* g, void* stream) { return gemm_launch(g, static_cast<hipStream_t>(stream)); }
 MTRSSM_API int mtrssm_gemm_group(const MtrssmGemm* problems, int32_t count, void* stream) {
   return gemm_group_launch(problems, count, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_initial_state_supported(const MtrssmInitialState* p) { return initial_state_supported(p); }
+MTRSSM_API int mtrssm_initial_state_fwd(const MtrssmInitialState* p, void* stream) {
+  return initial_state_fwd_launch(p, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_initial_state_bwd(const MtrssmInitialState* p, void* stream) {
+  return initial_state_bwd_launch(p, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int64_t mtrssm_mrssm_scan_prepare_layout(int32_t D, int32_t H, int32_t S, int64_t* offsets) {
+  return mrssm_scan_prepare_layout(D, H, S, offsets);
+}
+MTRSSM_API int mtrssm_mrssm_scan_prepare(const MtrssmScanPrepare* p, void* stream) {
+  return mrssm_scan_prepare_launch(p, static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int mtrssm_clear(void* p, int64_t bytes, void* stream) {
   return clear_async(p, bytes < 0 ? 0 : (size_t)bytes, static_cast<hipStream_t>(stream));

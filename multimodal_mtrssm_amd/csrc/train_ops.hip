@@ -3,6 +3,7 @@
 // coalesced accesses, grid-stride over <= 2048 workgroups, wave64 shuffle reductions, one atomic
 // per workgroup.
 #include "scan_common.h"
+#include "categorical.h"
 
 namespace mtrssm {
 
@@ -301,50 +302,15 @@ __global__ void categorical_sample_fwd_kernel(const float* __restrict__ logits, 
                                               float* __restrict__ logp, float* __restrict__ probs, float* __restrict__ onehot) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // (row, categorical)
   if (i >= n) return;
-  const float* x = logits + i * C;
-  float m = x[0];
-  for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
-  float sum = 0.f;
-  for (int c = 0; c < C; ++c) sum += expf(x[c] - m);
-  // The log-probabilities reach |logp| > 8, where `(x - m) - logf(sum)` in fp32 is three roundings of up to half an ulp
-  // (4.8e-7) each: the log-sum and the differences in double, one rounding at the end (a thread per categorical, once per
-  // rollout: no cost).  Probabilities and the sample stay the fp32 left fold the scans and the host use.
-  double dsum = 0.0;
-  for (int c = 0; c < C; ++c) dsum += exp((double)x[c] - (double)m);
-  const double ls = log(dsum);
-  const float uu = u[i];
-  float acc = 0.f;
-  int idx = 0;
-  for (int c = 0; c < C; ++c) {
-    const float p = expf(x[c] - m) / sum;
-    probs[i * C + c] = p;
-    logp[i * C + c] = (float)(((double)x[c] - (double)m) - ls);
-    acc += p;
-    if (c + 1 < C && acc <= uu) ++idx;
-  }
-  for (int c = 0; c < C; ++c) onehot[i * C + c] = c == idx ? 1.f : 0.f;
+  categorical_sample_one(logits + i * C, u[i], C, logp + i * C, probs + i * C, onehot + i * C);   // (categorical.h)
 }
 
-// d logits of the same head: through the probabilities (g_p: the straight-through sample's gradient plus any gradient of the
-// probabilities themselves; may be null) and through the log-probabilities (g_l, may be null):
-//   d x_c = p_c (g_p[c] - sum_j p_j g_p[j]) + g_l[c] - p_c sum_j g_l[j]
+// d logits of the same head (categorical.h: categorical_grad_one); g_p and g_l may be null
 __global__ void categorical_sample_bwd_kernel(const float* __restrict__ probs, const float* __restrict__ g_p, const float* __restrict__ g_l,
                                               int64_t n, int C, float* __restrict__ d_logits) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  float dot = 0.f, sl = 0.f;
-  for (int c = 0; c < C; ++c) {
-    const float p = probs[i * C + c];
-    if (g_p) dot += p * g_p[i * C + c];
-    if (g_l) sl += g_l[i * C + c];
-  }
-  for (int c = 0; c < C; ++c) {
-    const float p = probs[i * C + c];
-    float d = 0.f;
-    if (g_p) d += p * (g_p[i * C + c] - dot);
-    if (g_l) d += g_l[i * C + c] - p * sl;
-    d_logits[i * C + c] = d;
-  }
+  categorical_grad_one(probs + i * C, g_p ? g_p + i * C : nullptr, g_l ? g_l + i * C : nullptr, C, d_logits + i * C);
 }
 
 int categorical_sample_fwd_launch(const float* logits, const float* u, int64_t rows, int K, int C, float* logp, float* probs, float* onehot,

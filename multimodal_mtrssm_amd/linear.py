@@ -157,16 +157,38 @@ def _span(t: Tensor) -> tuple[int, int]:
     return lo, lo + 4 * (sum((n - 1) * st for n, st in zip(t.shape, t.stride(), strict=True)) + 1 if t.numel() else 0)
 
 
+def _columns(t: Tensor) -> tuple[int, int, int] | None:
+    """``(pitch, first, width)`` in floats of a row-major matrix view: every element's float address is ``first + c`` modulo the
+    pitch with ``c < width`` (an interval of the circle of residues), else None."""
+    if t.dim() != 2 or t.stride(1) != 1 or t.shape[0] <= 1 or t.stride(0) < t.shape[1]:  # noqa: PLR2004
+        return None
+    pitch = int(t.stride(0))
+    return pitch, (t.data_ptr() // 4) % pitch, int(t.shape[1])
+
+
+def _disjoint(s: tuple, t: tuple) -> bool:
+    """Two outputs ``(lo, hi, columns)`` share no element: their byte ranges do not meet, or they are column views of one row
+    pitch whose column intervals do not meet (``wa1[:, :D]`` from the scan and ``wa1[:, D:]`` from the projection: interleaved
+    in memory, but every problem touches only its own elements)."""
+    (lo, hi, cols), (lo2, hi2, cols2) = s, t
+    if hi <= lo2 or hi2 <= lo:
+        return True
+    if cols is None or cols2 is None or cols[0] != cols2[0]:
+        return False
+    pitch = cols[0]  # equal residues modulo the pitch are necessary for equal addresses: disjoint intervals of residues suffice
+    return (cols2[1] - cols[1]) % pitch >= cols[2] and (cols[1] - cols2[1]) % pitch >= cols2[2]
+
+
 def _rounds(problems: list) -> list[list]:
     """Problems whose outputs (C, column sums) may touch the same memory must not share a launch (a problem whose reduction is
     not split accumulates by plain read-modify-write): e.g. the prior head's weights collect a gradient from the initial state
-    AND one from the scan.  Greedy rounds by byte range; interleaved column views of one matrix land in different rounds too."""
+    AND one from the scan.  Greedy rounds by byte range; disjoint column views of one matrix may share a round (``_disjoint``)."""
     rounds: list[tuple[list, list]] = []
     for problem in problems:
         (_a, _b, c), kw = problem
-        spans = [_span(c)] + ([_span(kw["colsum"])] if kw.get("colsum") is not None else [])
+        spans = [(*_span(c), _columns(c))] + ([(*_span(kw["colsum"]), None)] if kw.get("colsum") is not None else [])
         for members, taken in rounds:
-            if all(hi <= lo2 or hi2 <= lo for lo, hi in spans for lo2, hi2 in taken):
+            if all(_disjoint(s, t) for s in spans for t in taken):
                 members.append(problem)
                 taken.extend(spans)
                 break
@@ -191,6 +213,15 @@ def gemm_group(problems: list[tuple[tuple[Tensor, Tensor, Tensor], dict]]) -> No
             gemm_group(members)
         return
     built = [_problem(a, b, c, **{**kw, "mfma_split": 0}) for (a, b, c), kw in problems]
+    at = 0
+    for g, _, _ in built:  # problems of one launch must not share ticket words: each gets its own run of the device's buffer
+        if g.tickets:
+            tiles = ((g.M + 63) // 64) * ((g.N + 63) // 64)
+            if at + tiles <= _N_TICKETS:
+                g.tickets, g.n_tickets = g.tickets + 4 * at, tiles
+                at += tiles
+            else:
+                g.tickets, g.n_tickets = None, 0  # (no words left: this problem's reduction is not split)
     arr = (_lib.Gemm * len(built))(*[g for g, _, _ in built])
     dev = problems[0][0][0].device
     lib = _lib.load()
@@ -312,6 +343,78 @@ class _Linear(torch.autograd.Function):
         gw, gb = weight_grad(gy2, x2, weight, bias, act_x=ctx.pre_act, want_weight=ctx.needs_input_grad[1],
                              want_bias=ctx.has_bias and ctx.needs_input_grad[2], pieces=ctx.pieces)
         return gx, gw, gb, None, None
+
+
+def _side_by_side(problems: list) -> None:
+    """Independent problems of one pass: the latency-bound ones (below ``SPLIT_MIN_FLOPS``: the fp32 MFMA kernel either way) in
+    one ``mtrssm_gemm_group`` launch per operand layout, a large one as its own launch on the kernel ``_problem`` picks for it."""
+    small = [p for p in problems if 2.0 * p[0][2].numel() * (p[0][0].shape[0] if p[1]["a_rmajor"] else p[0][0].shape[1]) < SPLIT_MIN_FLOPS]
+    gemm_group(small)
+    for (a, b, c), kw in problems:
+        if not any(c is s[0][2] for s in small):
+            gemm(a, b, c, **kw)
+
+
+class _LinearGroup(torch.autograd.Function):
+    """``linear()`` of several independent (x, weight, bias) at once: one group launch forward, one for the data gradients
+    that are needed; weight gradients through ``weight_grad`` as for ``_Linear``.  Per problem the arithmetic of ``linear()``
+    (sharing a launch changes how finely a reduction is cut, so sums may differ in their last bits)."""
+
+    @staticmethod
+    def forward(ctx, pre_acts: tuple[int, ...], *flat: Tensor | None):  # noqa: ANN001, ANN205
+        items, leads, problems, ys = [], [], [], []
+        for i, pre_act in enumerate(pre_acts):
+            x, weight, bias = flat[3 * i : 3 * i + 3]
+            x2 = x.reshape(-1, x.shape[-1])
+            if x2.stride(1) != 1:
+                x2 = x2.contiguous()
+            w = weight if weight.stride(1) == 1 else weight.contiguous()
+            y = torch.empty(x2.shape[0], w.shape[0], device=x.device, dtype=torch.float32)
+            problems.append(((x2, w, y), dict(a_rmajor=False, b_rmajor=False, bias=None if bias is None else bias.contiguous(), act_a=pre_act)))
+            items += [x2, weight, bias if bias is not None else x2.new_zeros(0)]
+            leads.append((x.shape[:-1], bias is not None))
+            ys.append(y.reshape(*x.shape[:-1], w.shape[0]))
+        _side_by_side(problems)
+        ctx.save_for_backward(*items)
+        ctx.leads, ctx.pre_acts = leads, pre_acts
+        return tuple(ys)
+
+    @staticmethod
+    def backward(ctx, *gys: Tensor | None):  # noqa: ANN205
+        saved = ctx.saved_tensors
+        items = [(saved[3 * i], saved[3 * i + 1], saved[3 * i + 2] if has_bias else None, lead) for i, (lead, has_bias) in enumerate(ctx.leads)]
+        problems, grads, gy2s = [], [], []
+        for i, ((x2, weight, _bias, lead), pre_act, gy) in enumerate(zip(items, ctx.pre_acts, gys, strict=True)):
+            gx = gy2 = None
+            if gy is not None:
+                gy2 = gy.reshape(-1, gy.shape[-1])
+                if gy2.stride(1) != 1:
+                    gy2 = gy2.contiguous()
+                if ctx.needs_input_grad[1 + 3 * i]:
+                    w = weight if weight.stride(1) == 1 else weight.contiguous()
+                    gx = torch.empty_like(x2)
+                    problems.append(((gy2, w, gx), dict(a_rmajor=False, b_rmajor=True, zgrad=x2 if pre_act else None, act_z=pre_act)))
+                    gx = gx.reshape(*lead, x2.shape[1])
+            gy2s.append(gy2)
+            grads.append(gx)
+        _side_by_side(problems)
+        out: list = [None]
+        for i, ((x2, weight, bias, _lead), pre_act, gy2, gx) in enumerate(zip(items, ctx.pre_acts, gy2s, grads, strict=True)):
+            gw = gb = None
+            if gy2 is not None:
+                gw, gb = weight_grad(gy2, x2, weight, bias, act_x=pre_act, want_weight=ctx.needs_input_grad[2 + 3 * i],
+                                     want_bias=bias is not None and ctx.needs_input_grad[3 + 3 * i])
+            out += [gx, gw, gb]
+        return tuple(out)
+
+
+def linear_group(items: list[tuple[Tensor, Tensor, Tensor | None, int]]) -> list[Tensor]:
+    """``[linear(x, weight, bias, pre_act=pre_act) for (x, weight, bias, pre_act) in items]`` for INDEPENDENT items (no output
+    is an input of another) with the launches shared: the hoisted projections of a rollout, a layer of both decoders."""
+    if len(items) == 1 or not GROUP_GEMMS:
+        return [linear(x, w, b, pre_act=a) for x, w, b, a in items]
+    flat = [t for x, w, b, _ in items for t in (x, w, b)]
+    return list(_LinearGroup.apply(tuple(int(a) for *_, a in items), *flat))
 
 
 def linear(x: Tensor, weight: Tensor, bias: Tensor | None = None, *, pre_act: int = 0, pieces: int | None = None) -> Tensor:

@@ -26,7 +26,7 @@ from torch import Tensor
 from multimodal_mtrssm_amd import _lib
 from multimodal_mtrssm_amd.distributions import KL_BALANCE_ALPHA
 from multimodal_mtrssm_amd import linear as _linear
-from multimodal_mtrssm_amd.linear import gemm, gemm_group, grad_target, linear
+from multimodal_mtrssm_amd.linear import gemm, gemm_group, grad_target, linear, linear_group
 
 
 @dataclass(frozen=True)
@@ -273,6 +273,63 @@ def _expect(**named: tuple[Tensor | None, tuple[int, ...]]) -> None:
             raise ValueError(msg)
 
 
+def _head_rows(w3: Tensor, wa1: Tensor, wv1: Tensor, D: int) -> Tensor:  # noqa: N803
+    """``[prior.0 ; audio post.0[:, :D] ; vision post.0[:, :D]]`` as one ``[3H, D]`` matrix: the one-CU kernels' ``wh1``."""
+    return torch.cat([w3, wa1[:, :D], wv1[:, :D]], dim=0)
+
+
+SCAN_PREPARE = True  # False: the cooperative scans' layouts from torch copies and two GEMM launches (A/B runs, tests)
+
+
+def _row_major(t: Tensor) -> Tensor:
+    return t if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1] else _c(t)  # noqa: PLR2004
+
+
+def _cluster_layouts(w1, w2, b2, wih, bih, whh, w3, wa1, wv1, D: int, H: int, S: int, A: int):  # noqa: ANN001, ANN202, N803, PLR0913
+    """``(w1s_t, whh_t, wh1_t, wf_t, bf)`` of ``MtrssmMrssmClusterWeights``: views of ONE buffer written by
+    ``mtrssm_mrssm_scan_prepare`` from the raw parameters (strided views of a flat parameter buffer are read in place).  Where
+    the fused-input product is large enough for the bf16-piece MFMA tile kernel (``linear.SPLIT_MIN_FLOPS``: the Large dims)
+    the launch leaves ``wf_t`` / ``bf`` to the two GEMMs, which are the faster tool there."""
+    if not SCAN_PREPARE:
+        w1s_t, whh_t = _c(w1[:, A:].t()), _c(whh.t())
+        wh1_t = _c(_head_rows(w3, wa1, wv1, D).t())
+        wf_t, bf = _new(w1, H, 3 * D), _new(w1, 1, 3 * D)
+        gemm(w2, wih, wf_t, a_rmajor=True, b_rmajor=False)            # wf_t[k][j] = sum_h W2[h][k] W_ih[j][h]
+        gemm(b2.reshape(1, H), wih, bf, a_rmajor=False, b_rmajor=False, bias=_c(bih))
+        return w1s_t, whh_t, wh1_t, wf_t, bf.reshape(-1)
+    lib = _lib.load()
+    off = (C.c_int64 * 5)()
+    total = int(lib.mtrssm_mrssm_scan_prepare_layout(D, H, S, off))
+    if total <= 0:
+        msg = f"mtrssm_mrssm_scan_prepare_layout refused D = {D}, H = {H}, S = {S}"
+        raise _lib.MtrssmLibraryError(msg)
+    buf = _new(w1, total)
+    w1, w2, wih, whh, w3, wa1, wv1 = map(_row_major, (w1, w2, wih, whh, w3, wa1, wv1))
+    b2, bih = _c(b2), _c(bih)
+    product = 2.0 * H * 3 * D * H < _linear.SPLIT_MIN_FLOPS
+    p = _lib.ScanPrepare()
+    p._refs = (w1, w2, b2, wih, bih, whh, w3, wa1, wv1, buf)  # noqa: SLF001
+    p.w1, p.w2, p.b2, p.wih, p.bih = map(_lib.raw_ptr, (w1, w2, b2, wih, bih))
+    p.whh, p.w3, p.wa1, p.wv1 = map(_lib.raw_ptr, (whh, w3, wa1, wv1))
+    p.ld_w1, p.ld_w2, p.ld_wih, p.ld_whh = w1.stride(0), w2.stride(0), wih.stride(0), whh.stride(0)
+    p.ld_w3, p.ld_wa1, p.ld_wv1 = w3.stride(0), wa1.stride(0), wv1.stride(0)
+    p.D, p.H, p.S, p.A, p.product = D, H, S, A, int(product)
+    p.out, p.out_floats = buf.data_ptr(), total
+    _lib.check(_lib.TIMERS.call("mtrssm_mrssm_scan_prepare", lib.mtrssm_mrssm_scan_prepare, C.byref(p), _lib.stream_ptr(buf.device),
+                                flops=2.0 * (H + 1) * 3 * D * H if product else 0.0,
+                                nbytes=4.0 * (2 * (S * H + 3 * D * D + 3 * H * D) + (H * H + 2 * 3 * D * H if product else 0))),
+               "mtrssm_mrssm_scan_prepare")
+    w1s_t = buf[off[0] : off[0] + S * H].view(S, H)
+    whh_t = buf[off[1] : off[1] + D * 3 * D].view(D, 3 * D)
+    wh1_t = buf[off[2] : off[2] + D * 3 * H].view(D, 3 * H)
+    wf_t = buf[off[3] : off[3] + H * 3 * D].view(H, 3 * D)
+    bf = buf[off[4] : off[4] + 3 * D]
+    if not product:
+        gemm(w2, wih, wf_t, a_rmajor=True, b_rmajor=False)
+        gemm(b2.reshape(1, H), wih, bf.view(1, 3 * D), a_rmajor=False, b_rmajor=False, bias=bih)
+    return w1s_t, whh_t, wh1_t, wf_t, bf
+
+
 # ============================================================================================
 # MRSSM
 # ============================================================================================
@@ -306,10 +363,6 @@ class _MrssmScan(torch.autograd.Function):
         expert_logw = check_expert_logw(expert_logw, B, T)
         modality = _weighted_modality(_modality(modality, B, T), expert_logw)
         u_prior = _opt(u_prior)
-        # forward layouts (include/mtrssm.h: wide outputs stream W^T, narrow outputs stream W)
-        w1s_t = _c(w1[:, A:].t())
-        wh1 = torch.cat([w3, wa1[:, :D], wv1[:, :D]], dim=0)  # [3H, D]
-        whh_t, wh1_t = _c(whh.t()), _c(wh1.t())
         deter = _new(xa, B, T, D)
         prior_logits, post_logits, post_stoch = (_new(xa, B, T, S) for _ in range(3))
         prior_stoch = _new(xa, B, T, S) if u_prior is not None else None
@@ -334,12 +387,11 @@ class _MrssmScan(torch.autograd.Function):
         cluster = CLUSTER_SCAN and plain and bool(lib.mtrssm_mrssm_cluster_supported(C.byref(dims)))
         wide = WIDE_SCAN and plain and not cluster and bool(lib.mtrssm_mrssm_wide_supported(C.byref(dims), WIDE_PIECES))
         ctx.scan_kind = "cluster" if cluster else ("wide" if wide else None)
+        wh1 = None
         if cluster or wide:
-            # fused GRU input path: gi = (W_ih W2) h1 + (W_ih b2 + b_ih); two small GEMMs per launch (weights change every step)
-            wf_t = _new(xa, H, 3 * D)
-            gemm(w2, wih, wf_t, a_rmajor=True, b_rmajor=False)            # wf_t[k][j] = sum_h W2[h][k] W_ih[j][h]
-            bf = _new(xa, 1, 3 * D)
-            gemm(b2.reshape(1, H), wih, bf, a_rmajor=False, b_rmajor=False, bias=_c(bih))
+            # forward layouts and the fused GRU input path gi = (W_ih W2) h1 + (W_ih b2 + b_ih) in one launch from the raw
+            # parameters (csrc/scan_prepare.hip; nothing is kept across steps: the weights change every step)
+            w1s_t, whh_t, wh1_t, wf_t, bf = _cluster_layouts(w1, w2, b2, wih, bih, whh, w3, wa1, wv1, D, H, S, A)
             cw = _lib.fill(_lib.MrssmClusterWeights(), w1s_t=w1s_t, wf_t=wf_t, bf=bf.reshape(-1), whh_t=whh_t, bhh=_c(bhh),
                            wh1_t=wh1_t, b3=_c(b3), w4=_c(w4), b4=_c(b4), wa2=_c(wa2), ba2=_c(ba2), wv2=_c(wv2), bv2=_c(bv2))
             io.sv_h2 = None  # not produced on this path: recomputed in the backward where dW_ih needs it
@@ -358,6 +410,10 @@ class _MrssmScan(torch.autograd.Function):
             ctx.cluster_w = (wf_t, whh_t, wh1_t)
         else:
             ctx.cluster_w = None
+            # forward layouts (include/mtrssm.h: wide outputs stream W^T, narrow outputs stream W)
+            w1s_t = _c(w1[:, A:].t())
+            wh1 = _head_rows(w3, wa1, wv1, D)
+            whh_t, wh1_t = _c(whh.t()), _c(wh1.t())
             # (the one-CU kernel takes W2 and W_ih themselves, transposed: two copies the fused-path kernels never need)
             fw = _lib.fill(
                 _lib.MrssmFwdWeights(), w1s_t=w1s_t, w2_t=_c(w2.t()), b2=_c(b2), wih_t=_c(wih.t()), bih=_c(bih), whh_t=whh_t,
@@ -389,8 +445,6 @@ class _MrssmScan(torch.autograd.Function):
             g_prior_stoch = None
         _expect(g_deter=(g_deter, (B, T, D)), g_prior_logits=(g_prior_logits, (B, T, S)), g_post_logits=(g_post_logits, (B, T, S)),
                 g_post_stoch=(g_post_stoch, (B, T, S)), g_prior_stoch=(g_prior_stoch, (B, T, S)), g_kl=(g_kl, (B, T)))
-        bw = _lib.fill(_lib.MrssmBwdWeights(), w1s_t=w1s_t, w2=_c(w2), wih=_c(wih), whh=_c(whh), wh1=wh1, w4=_c(w4), wa2=_c(wa2),
-                       wv2=_c(wv2))
         g_deter0, g_stoch0 = _new(deter, B, D), _new(deter, B, S)
         d_z1, d_h2 = _new(deter, B, T, H), _new(deter, B, T, H)
         d_gi, d_gh = _new(deter, B, T, 3 * D), _new(deter, B, T, 3 * D)
@@ -431,6 +485,10 @@ class _MrssmScan(torch.autograd.Function):
             # d_h2 = d_gi . W_ih for all (b, t) at once (the fused input path has no h2 inside the scan)
             gemm(_flat2(d_gi), wih, _flat2(d_h2), a_rmajor=False, b_rmajor=True)
         else:
+            if wh1 is None:  # a cooperative forward whose reverse scan runs on one CU: the untransposed head rows were not built
+                wh1 = _head_rows(ctx.w3, wa1, wv1, D)
+            bw = _lib.fill(_lib.MrssmBwdWeights(), w1s_t=w1s_t, w2=_c(w2), wih=_c(wih), whh=_c(whh), wh1=wh1, w4=_c(w4), wa2=_c(wa2),
+                           wv2=_c(wv2))
             _lib.check(_lib.TIMERS.call("mtrssm_mrssm_rollout_bwd", lib.mtrssm_mrssm_rollout_bwd, C.byref(dims), C.byref(bw), C.byref(io),
                                         _lib.stream_ptr(deter.device), flops=2.0 * B * T * macs, nbytes=4.0 * B * T * per_bt),
                        "mtrssm_mrssm_rollout_bwd")
@@ -491,9 +549,12 @@ def mrssm_posterior_rollout(  # noqa: PLR0913
         raise NotImplementedError(msg)
     cfg = ScanConfig(K, Cc, _lib.ACT_IDS[act_names.pop()], balancing, rows_per_block, threads)
     # hoisted, recurrence-independent halves of the first layers: plain library GEMMs
-    xa = linear(actions, l1.weight[:, :A], l1.bias)
-    pa = _projection(audio_embed, a1, D, xa)
-    pv = _projection(vision_embed, v1, D, xa)
+    # (independent of each other: side by side in one launch each way; an absent modality's projection is not run)
+    present = [(embed, layer) for embed, layer in ((audio_embed, a1), (vision_embed, v1)) if embed is not None]
+    outs = linear_group([(actions, l1.weight[:, :A], l1.bias, 0)] + [(embed, layer.weight[:, D:], layer.bias, 0) for embed, layer in present])
+    xa, rest = outs[0], outs[1:]
+    pa = rest.pop(0) if audio_embed is not None else _projection(None, a1, D, xa)
+    pv = rest.pop(0) if vision_embed is not None else _projection(None, v1, D, xa)
     cell = transition.rnn_cell
     deter, prior_logits, post_logits, post_stoch, prior_stoch, kl = _MrssmScan.apply(
         cfg, xa, pa, pv, deter0, stoch0, u_post, u_prior,
