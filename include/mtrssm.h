@@ -915,6 +915,35 @@ int mtrssm_ensemble_score(const float* pred, const float* target, const int32_t*
 int mtrssm_horizon_table(const float* planes, int64_t P, const int32_t* context, const int32_t* valid, int64_t B, int64_t T,
                          float* sums, float* counts, void* stream);
 
+/* Held-out likelihood: the importance-weighted bound of S sampled posterior trajectories per row.
+ * mtrssm_latent_log_ratio: post_logits / prior_logits / stoch [rows][K * C] (a rollout's logits and its one-hot posterior sample);
+ *   out[row] = sum_k ( log p_k(c*) - log q_k(c*) ),  p_k / q_k the softmax of categorical k's C prior / posterior logits, c* the
+ *   first c with stoch[k][c] > 0.5 (class 0 when there is none).  Any C >= 1.  Each categorical's max, log-sum and differences are
+ *   computed in double, the categoricals summed in ascending k, the result rounded to fp32 once; accumulate = 1 adds the double sum
+ *   onto out[row] before that one rounding (MMTRSSM's second level), accumulate = 0 overwrites.  Bitwise-equal post and prior
+ *   logits (a step that observes nothing) give exactly 0.  Loads are coalesced (consecutive lanes read consecutive floats of a
+ *   row; the spans are staged in LDS, C > 512 is walked class by class); a row's result depends on that row only.
+ *   Null pointers, rows, K or C <= 0, an accumulate other than 0 / 1 or rows * K * C >= 2^31 return -1 without a launch.
+ * mtrssm_iw_bound: se_audio / se_vision [B][S][T] (the data terms mtrssm_ensemble_score writes into se_samples) and log_ratio
+ *   [B][S][T] (the sum of the levels' mtrssm_latent_log_ratio); each may be NULL (that term is off), not all three.  valid [B] int32
+ *   in DEVICE memory (NULL: every frame is live; (b, t) is live iff t < valid[b]).  On a live frame, per sample s:
+ *     a = -se_audio - 0.5 event_audio log 2 pi;  v likewise;  r = log_ratio;  l = (a + v) + r;  cum[s][t] = cum[s][t-1] + l
+ *   (a left fold over t; a dead frame adds 0), and into planes [8][B][T], each exactly 0 on a dead frame:
+ *     0 iw  = L[t] - L[t-1],  L[t] = max_s cum + log sum_s exp(cum - max_s cum) - log S,  L[-1] = 0
+ *     1 elbo = M[t] - M[t-1],  M[t] = (sum_s cum) / S,  M[-1] = 0
+ *     2, 3, 4 audio, vision, latent = (sum_s a) / S, (sum_s v) / S, (sum_s r) / S   (0 when the term is off)
+ *     5 ess  = (sum_s w)^2 / sum_s w^2,  w = exp(cum - max_s cum)
+ *     6, 7 iw_prefix, elbo_prefix = L[t], M[t]
+ *   The fold over t, the sums over s (a fixed butterfly inside a 16-lane DPP row, one row of lanes per b) and the ESS run in
+ *   double without atomics; each output is rounded to fp32 once.  L[t] >= M[t]; at S = 1 planes 0 / 6 equal planes 1 / 7 bit for
+ *   bit.  A row's result depends on that row only and two calls agree bitwise.
+ *   Null planes, all three inputs NULL, B or T <= 0, an event size <= 0 of a given data term, S outside 1 .. 16 or B * T >= 2^24
+ *   return -1 without a launch. */
+int mtrssm_latent_log_ratio(const float* post_logits, const float* prior_logits, const float* stoch, int64_t rows, int64_t K, int64_t C,
+                            int32_t accumulate, float* out, void* stream);
+int mtrssm_iw_bound(const float* se_audio, const float* se_vision, const float* log_ratio, const int32_t* valid, int64_t B, int64_t S,
+                    int64_t T, int64_t event_audio, int64_t event_vision, float* planes, void* stream);
+
 /* Digit reader: the inference path of the classifier that reads a digit off a predicted vision frame
  * (conv 3x3 1->32, ReLU, pool 2x2, conv 3x3 32->64, ReLU, pool 2x2, Linear 4096->128, ReLU, Linear 128->10; 32 x 32 frames).
  * mtrssm_digit_features: the convolutional trunk of a frame in one launch.  pred [frames][1024] is the decoder's RAW output;

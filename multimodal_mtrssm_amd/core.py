@@ -26,6 +26,8 @@ from multimodal_mtrssm_amd.digits import DigitClassifier, word_counts
 from multimodal_mtrssm_amd.dropout import ModalityDropout, StepMask, ragged_step_mask
 from multimodal_mtrssm_amd.experts import ExpertWeights
 from multimodal_mtrssm_amd.forecast import Forecast
+from multimodal_mtrssm_amd.likelihood import PLANES as LIKELIHOOD_PLANES
+from multimodal_mtrssm_amd.likelihood import LikelihoodBound, LikelihoodTable
 from multimodal_mtrssm_amd.networks import MTRNN, Representation, Transition
 from multimodal_mtrssm_amd.objective import likelihood
 from multimodal_mtrssm_amd.schedule import ElboSchedule, ElboTerms
@@ -525,6 +527,8 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         self.elbo_schedule: ElboSchedule | None = None  # training_step (never validation_step) weighs the loss terms with it
         self.val_skill: ForecastSkill | None = None  # validation_step adds a skill step into self.skill_table
         self.skill_table: SkillTable | None = None  # ... logged as val/skill/* and cleared by on_validation_epoch_end
+        self.val_likelihood: LikelihoodBound | None = None  # validation_step adds a likelihood step into self.likelihood_table
+        self.likelihood_table: LikelihoodTable | None = None  # ... logged as val/loglik/* and cleared by on_validation_epoch_end
         # weighted MoPoE: assign an ExpertWeights (a submodule: before FlatParameters is built); None = 1/3 each, no new
         # state-dict keys.  After every posterior rollout with weights, weights_timeseries is ExpertWeights.table(...) [B, T, 3]
         self.expert_weights: ExpertWeights | None = None
@@ -815,10 +819,25 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
 
     _POST_KEYS = ("u_post",)  # the rollout's posterior uniforms; a skill step composes each with its "u_tail" twin
 
-    def _skill_rollout(self, batch: tuple[Tensor, ...], skill: ForecastSkill, noise: Noise | None, lengths: Tensor | None,
-                       expert_log_weights: Tensor | None) -> tuple[dict[str, Tensor], Tensor | None]:
+    def _per_copy_noise(self, noise: Noise, keys: tuple[str, ...], B: int, S: int, *mid: int) -> None:  # noqa: N803
+        """In place: a likelihood step's uniforms ``(B, S, *mid, K)`` become the scan's rows ``b * S + s`` as they lie (absent: left to
+        the consumer's own draw)."""
+        for key in keys:
+            u = noise.get(key)
+            if u is None:
+                continue
+            want = (B, S, *mid, self._category_size_of(key))
+            if tuple(u.shape) != want:
+                msg = f"noise[{key!r}] must have shape {want}, got {tuple(u.shape)}"
+                raise ValueError(msg)
+            noise[key] = u.reshape(B * S, *want[2:]).contiguous()
+
+    def _skill_rollout(self, batch: tuple[Tensor, ...], skill: ForecastSkill | LikelihoodBound, noise: Noise | None, lengths: Tensor | None,  # noqa: PLR0913
+                       expert_log_weights: Tensor | None, *, per_copy: bool = False) -> tuple[dict[str, Tensor], Tensor | None]:
         """The rollout of a skill step (``forecast_skill``, ``word_transitions``): both encoders, the initial state of every row, the
-        composed noise and ONE masked posterior rollout over ``B * S`` rows.  Returns the scan's outputs and the rows' lengths (or None)."""
+        composed noise and ONE masked posterior rollout over ``B * S`` rows.  Returns the scan's outputs and the rows' lengths (or None).
+        ``per_copy`` (``likelihood_bound``): every live frame is observed, and each copy of a row draws its own initial state and its own
+        posterior (``u_init`` ``(B, S, K)``, ``u_post`` ``(B, S, T, K)``) instead of sharing the row's."""
         actions = batch[0]
         audio_obs, vision_obs = self.get_observations_from_batch(batch)
         B, T = actions.shape[:2]
@@ -832,20 +851,27 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         noise = dict(noise or {})
         conv.begin_step(dev)
         audio_embed, vision_embed = self._encode_both(audio_obs, vision_obs)
-        sm = Forecast(skill.context).sample(torch.zeros(B, device=dev), T, valid)  # (a fixed context: the uniforms do not matter)
+        context = T if per_copy else skill.context
+        sm = Forecast(context).sample(torch.zeros(B, device=dev), T, valid)  # (a fixed context: the uniforms do not matter)
         bits = skill.bits
         codes = sm.codes & bits
         mask0 = sm.mask0 & skill.observed(dev)
-        state0 = self._initial_for_step(_masked_mean_embed(audio_embed[:, 0], vision_embed[:, 0], mask0), noise)
+        embed0 = _masked_mean_embed(audio_embed[:, 0], vision_embed[:, 0], mask0)
         wide = lambda x: x.repeat_interleave(S, dim=0)  # noqa: E731  (row (b, s) -> b * S + s)
-        state0 = self._state_like(state0, {k: wide(getattr(state0, k)) for k in self._FRESH_KEYS})
-        for key in self._POST_KEYS:
-            tail_key = key.replace("post", "tail")
-            u_post, u_tail = noise.get(key), noise.get(tail_key)
-            k = self._category_size_of(key)
-            u_post = _rand(actions, B, T, k) if u_post is None else u_post
-            u_tail = _rand(actions, B, S, T, k) if u_tail is None else u_tail
-            noise[key] = skill.compose_noise(u_post, u_tail)
+        if per_copy:
+            self._per_copy_noise(noise, self._INIT_KEYS, B, S)
+            self._per_copy_noise(noise, self._POST_KEYS, B, S, T)
+            state0 = self._initial_for_step(wide(embed0), noise)
+        else:
+            state0 = self._initial_for_step(embed0, noise)
+            state0 = self._state_like(state0, {k: wide(getattr(state0, k)) for k in self._FRESH_KEYS})
+            for key in self._POST_KEYS:
+                tail_key = key.replace("post", "tail")
+                u_post, u_tail = noise.get(key), noise.get(tail_key)
+                k = self._category_size_of(key)
+                u_post = _rand(actions, B, T, k) if u_post is None else u_post
+                u_tail = _rand(actions, B, S, T, k) if u_tail is None else u_tail
+                noise[key] = skill.compose_noise(u_post, u_tail)
         if expert_log_weights is not None and expert_log_weights.shape[0] == B * S:
             logw = expert_log_weights  # (checked by the rollout)
         else:
@@ -886,20 +912,11 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
             raise ValueError(msg)
         out, valid = self._skill_rollout(batch, skill, noise, lengths, expert_log_weights)
         feature = self._feature_of(out)
-        da, dv = self.audio_decoder, self.vision_decoder
-        fused = isinstance(da, cnn.Decoder) and isinstance(dv, cnn.Decoder) and da.out_act_id is not None and dv.out_act_id is not None
-        acts = (da.out_act_id, dv.out_act_id) if fused else (0, 0)
         planes = torch.empty(SkillTable.ROWS, B, T, device=dev, dtype=torch.float32)
         rows = max(1, int(skill.max_frames) // (S * T))
         for r0 in range(0, B, rows):
             r1 = min(B, r0 + rows)
-            f = feature[r0 * S : r1 * S]
-            if fused and _pairable(da, dv, cnn.Decoder):
-                preds = cnn.decode_pair(da, dv, f, f, raw=True)
-            elif fused:
-                preds = da(f, raw=True), dv(f, raw=True)
-            else:
-                preds = da(f), dv(f)
+            preds, acts = self._decode_for_score(feature[r0 * S : r1 * S])
             part = torch.empty(SkillTable.ROWS, r1 - r0, T, device=dev, dtype=torch.float32)
             for j, (pred, key) in enumerate(zip(preds, ("recon/audio", "recon/vision"), strict=True)):
                 ForecastSkill.score(pred.reshape(r1 - r0, S, T, -1), targets[key][r0:r1].reshape(r1 - r0, T, -1),
@@ -909,6 +926,85 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
             table = SkillTable(T, dev)
         context = torch.full((B,), min(skill.context, (1 << 31) - 1), dtype=torch.int32, device=dev)
         ForecastSkill.table_add(planes, context, valid, table.sums, table.counts)
+        table.planes = planes if keep_states else None
+        table.states = self._posterior_from_rollout(out) if keep_states else None
+        return table
+
+    def _decode_for_score(self, feature: Tensor, *, audio: bool = True, vision: bool = True) -> tuple[tuple[Tensor | None, Tensor | None], tuple[int, int]]:
+        """``(audio, vision)`` predictions of ``feature`` for the ensemble scorer and the output activations it applies while reading
+        them: this package's decoders hand over their RAW output (paired when they pair).  A modality that is not asked for is None."""
+        da, dv = self.audio_decoder, self.vision_decoder
+        fused = isinstance(da, cnn.Decoder) and isinstance(dv, cnn.Decoder) and da.out_act_id is not None and dv.out_act_id is not None
+        acts = (da.out_act_id, dv.out_act_id) if fused else (0, 0)
+        if audio and vision and fused and _pairable(da, dv, cnn.Decoder):
+            return cnn.decode_pair(da, dv, feature, feature, raw=True), acts
+        kw = {"raw": True} if fused else {}
+        return (da(feature, **kw) if audio else None, dv(feature, **kw) if vision else None), acts
+
+    def _latent_levels(self) -> tuple[tuple[str, MultiOneHotFactory], ...]:
+        """The latent levels of a posterior rollout: the suffix of their scan outputs and the factory that knows their K and C."""
+        return (("", self.transition.distribution_factory),)
+
+    @torch.no_grad()
+    def likelihood_bound(self, batch: tuple[Tensor, ...], bound: LikelihoodBound, noise: Noise | None = None, lengths: Tensor | None = None,  # noqa: PLR0913, PLR0914
+                         table: LikelihoodTable | None = None, *, keep_states: bool = False,
+                         expert_log_weights: Tensor | None = None) -> LikelihoodTable:
+        """One likelihood step (``likelihood.py`` states the quantity): ``bound.samples`` posterior trajectories
+        per row in ONE masked posterior rollout over ``B * S`` rows (row ``b * S + s``; the posterior sees ``bound.observe`` on every live
+        step and nothing after a row's end; every copy starts from its row's frame 0 with its own ``noise["u_init"][b, s]`` and reads
+        ``noise["u_post"][b, s]``), the latent log-ratio of the sampled classes (``mtrssm_latent_log_ratio``, one launch per level), the
+        decoders over chunks of whole rows, the per-sample errors (``mtrssm_ensemble_score``) and the bound (``mtrssm_iw_bound``); the
+        planes are folded by frame position into ``table`` (a new one when None), which is returned.  ``lengths`` (or a batch that
+        carries ``valid_global``): nothing is observed or scored at or past a row's end.  ``keep_states``: ``table.states`` is the
+        posterior state sequence ``[B * S, T, .]`` and ``table.planes`` the step's planes ``[8, B, T]``.  No masked (7-tuple) batch, no
+        ``state_carry``.  A weighted model runs its gate as in ``forecast_skill``."""
+        if not isinstance(bound, LikelihoodBound):
+            msg = f"bound must be a LikelihoodBound, got {type(bound).__name__}"
+            raise ValueError(msg)
+        if self.get_modality_mask_from_batch(batch) is not None:
+            msg = "a likelihood step decides what the model observes: a masked (7-tuple) batch already says what is seen"
+            raise ValueError(msg)
+        if self.state_carry is not None:
+            msg = "a likelihood step starts every row from its own frame 0: it does not combine with a set state_carry"
+            raise ValueError(msg)
+        actions = batch[0]
+        targets = self.get_targets_from_batch(batch)
+        B, T = actions.shape[:2]
+        S, dev = bound.samples, actions.device
+        if table is not None and (not isinstance(table, LikelihoodTable) or table.steps != T or table.buffer.device != dev):
+            msg = f"table must be a LikelihoodTable of {T} steps on {dev}"
+            raise ValueError(msg)
+        out, valid = self._skill_rollout(batch, bound, noise, lengths, expert_log_weights, per_copy=True)
+        ratio = None
+        if bound.latent:
+            for suffix, factory in self._latent_levels():
+                ratio = LikelihoodBound.log_ratio(out[f"post_logits{suffix}"], out[f"prior_logits{suffix}"], out[f"post_stoch{suffix}"],
+                                                  factory.category_size, factory.class_size, out=ratio, accumulate=ratio is not None)
+            ratio = ratio.reshape(B, S, T)
+        if table is None:
+            table = LikelihoodTable(T, dev)
+        audio, vision = "audio" in bound.score, "vision" in bound.score
+        feature = self._feature_of(out) if bound.score else None
+        planes = torch.empty(len(LIKELIHOOD_PLANES), B, T, device=dev, dtype=torch.float32)
+        rows = max(1, int(bound.max_frames) // (S * T)) if bound.score else B
+        for r0 in range(0, B, rows):
+            r1 = min(B, r0 + rows)
+            n = r1 - r0
+            chunk_valid = None if valid is None else valid[r0:r1]
+            se, events = [None, None], [0, 0]
+            if bound.score:
+                preds, acts = self._decode_for_score(feature[r0 * S : r1 * S], audio=audio, vision=vision)
+                for j, (pred, key) in enumerate(zip(preds, ("recon/audio", "recon/vision"), strict=True)):
+                    if pred is None:
+                        continue
+                    pred = pred.reshape(n, S, T, -1)  # noqa: PLW2901
+                    events[j] = pred.shape[-1]
+                    se[j] = ForecastSkill.score(pred, targets[key][r0:r1].reshape(n, T, -1), chunk_valid, acts[j], se_samples=True).se_samples
+            part = planes if n == B else torch.empty(len(LIKELIHOOD_PLANES), n, T, device=dev, dtype=torch.float32)
+            LikelihoodBound.bound(se[0], se[1], None if ratio is None else ratio[r0:r1], chunk_valid, events[0], events[1], out=part)
+            table.fold(part, chunk_valid)
+            if n != B:
+                planes[:, r0:r1] = part
         table.planes = planes if keep_states else None
         table.states = self._posterior_from_rollout(out) if keep_states else None
         return table
@@ -1218,6 +1314,7 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         return state_carry, prefix, reset.to(dev).contiguous()
 
     _FRESH_KEYS = ("deter", "stoch")  # State attributes the scan starts from
+    _INIT_KEYS = ("u_init",)  # the initial state's uniforms
     _LAST_KEYS = {"deter": "deter", "stoch": "post_stoch"}  # ... and the scan outputs that continue them
 
     def _state0(self, fresh: State | MTState, carry: tuple[StateCarry, str, Tensor] | None) -> State | MTState:
@@ -1300,17 +1397,25 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
             logged.update(fore)
         if self.val_skill is not None:  # (after everything above: the draws of val/* are what they are without it)
             self.skill_table = self.forecast_skill(batch, self.val_skill, table=self.skill_table)
+        if self.val_likelihood is not None:  # (last, for the same reason)
+            self.likelihood_table = self.likelihood_bound(batch, self.val_likelihood, table=self.likelihood_table)
         return logged
 
     def on_validation_epoch_end(self) -> dict[str, Tensor]:
-        """Logs the epoch's ``val/skill/{audio,vision}/{mean,ens,best,spread}/{obs,h1,h2,h4,h8}`` (all-reduced once when a process group is
-        initialised; the group is the one ``FlatDataParallel.skill`` bound) and clears the table.  Without a table: nothing."""
+        """Logs the epoch's ``val/skill/{audio,vision}/{mean,ens,best,spread}/{obs,h1,h2,h4,h8}`` and
+        ``val/loglik/{iw,elbo,audio,vision,latent,ess,gap}`` (each table all-reduced once when a process group is initialised; the group is
+        the one ``FlatDataParallel.skill`` / ``.likelihood`` bound) and clears the tables.  Without a table: nothing."""
+        logged: dict[str, Tensor] = {}
         table, self.skill_table = self.skill_table, None
-        if table is None:
-            return {}
-        table.all_reduce(getattr(self.val_skill, "group", None))
-        logged = table.scalars("val/skill")
-        self.log_dict(logged, prog_bar=False, sync_dist=False, on_step=False, on_epoch=True)
+        if table is not None:
+            table.all_reduce(getattr(self.val_skill, "group", None))
+            logged.update(table.scalars("val/skill"))
+        loglik, self.likelihood_table = self.likelihood_table, None
+        if loglik is not None:
+            loglik.all_reduce(getattr(self.val_likelihood, "group", None))
+            logged.update(loglik.scalars("val/loglik"))
+        if logged:
+            self.log_dict(logged, prog_bar=False, sync_dist=False, on_step=False, on_epoch=True)
         return logged
 
 
@@ -1484,6 +1589,10 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
         return (self.l_dist if key.endswith("_l") else self.h_dist).category_size
 
     _FRESH_KEYS = ("deter_l", "deter_h", "stoch_l", "stoch_h", "hidden_l", "hidden_h")
+    _INIT_KEYS = ("u_init_h", "u_init_l")
+
+    def _latent_levels(self) -> tuple[tuple[str, MultiOneHotFactory], ...]:
+        return (("_l", self.l_dist), ("_h", self.h_dist))
     _LAST_KEYS = {"deter_l": "deter_l", "deter_h": "deter_h", "stoch_l": "post_stoch_l", "stoch_h": "post_stoch_h", "hidden_l": "hidden_l",  # noqa: RUF012
                   "hidden_h": "hidden_h"}
 

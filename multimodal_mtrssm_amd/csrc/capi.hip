@@ -88,6 +88,8 @@ int nll_masked_bwd_launch(const float*, const float*, const float*, const float*
 int ensemble_score_launch(const float*, const float*, const int32_t*, int64_t, int64_t, int64_t, int64_t, int, float*, float*, float*, float*, float*,
                           hipStream_t);
 int horizon_table_launch(const float*, int64_t, const int32_t*, const int32_t*, int64_t, int64_t, float*, float*, hipStream_t);
+int latent_log_ratio_launch(const float*, const float*, const float*, int64_t, int64_t, int64_t, int, float*, hipStream_t);
+int iw_bound_launch(const float*, const float*, const float*, const int32_t*, int64_t, int64_t, int64_t, int64_t, int64_t, float*, hipStream_t);
 int digit_features_launch(const float*, int64_t, const int32_t*, int64_t, int, const float*, const float*, const float*, const float*, float*,
                           hipStream_t);
 int digit_head_launch(const float*, const float*, const float*, int64_t, const int32_t*, int64_t, int32_t*, float*, hipStream_t);
@@ -494,6 +496,14 @@ MTRSSM_API int mtrssm_ensemble_score(const float* pred, const float* target, con
 MTRSSM_API int mtrssm_horizon_table(const float* planes, int64_t P, const int32_t* context, const int32_t* valid, int64_t B, int64_t T,
                                     float* sums, float* counts, void* stream) {
   return horizon_table_launch(planes, P, context, valid, B, T, sums, counts, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_latent_log_ratio(const float* post_logits, const float* prior_logits, const float* stoch, int64_t rows, int64_t K,
+                                       int64_t C, int32_t accumulate, float* out, void* stream) {
+  return latent_log_ratio_launch(post_logits, prior_logits, stoch, rows, K, C, accumulate, out, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_iw_bound(const float* se_audio, const float* se_vision, const float* log_ratio, const int32_t* valid, int64_t B, int64_t S,
+                               int64_t T, int64_t event_audio, int64_t event_vision, float* planes, void* stream) {
+  return iw_bound_launch(se_audio, se_vision, log_ratio, valid, B, S, T, event_audio, event_vision, planes, static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int mtrssm_digit_features(const float* pred, int64_t frames, const int32_t* select, int64_t N, int32_t act, const float* conv1_w,
                                      const float* conv1_b, const float* conv2_w, const float* conv2_b, float* features, void* stream) {

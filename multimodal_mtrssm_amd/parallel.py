@@ -20,6 +20,7 @@ from multimodal_mtrssm_amd import conv, linear
 from multimodal_mtrssm_amd.dropout import ModalityDropout
 from multimodal_mtrssm_amd.forecast import Forecast
 from multimodal_mtrssm_amd.optim import FlatParameters
+from multimodal_mtrssm_amd.likelihood import LikelihoodBound
 from multimodal_mtrssm_amd.skill import ForecastSkill
 
 
@@ -98,6 +99,11 @@ class FlatDataParallel:
         """``skill`` bound to this object's process group: set the result as ``model.val_skill`` and ``on_validation_epoch_end``
         all-reduces the skill table over that group (its uniforms' batch dimension comes first: draw them with ``noise_source``)."""
         return skill.for_group(self.group)
+
+    def likelihood(self, bound: LikelihoodBound) -> LikelihoodBound:
+        """``bound`` bound to this object's process group: set the result as ``model.val_likelihood`` and ``on_validation_epoch_end``
+        all-reduces the likelihood table over that group (its uniforms' batch dimension comes first: draw them with ``noise_source``)."""
+        return bound.for_group(self.group)
 
     @property
     def grad_scale(self) -> float:
