@@ -944,6 +944,27 @@ int mtrssm_latent_log_ratio(const float* post_logits, const float* prior_logits,
 int mtrssm_iw_bound(const float* se_audio, const float* se_vision, const float* log_ratio, const int32_t* valid, int64_t B, int64_t S,
                     int64_t T, int64_t event_audio, int64_t event_vision, float* planes, void* stream);
 
+/* Linear word probes: one fused step of G multinomial-logistic classifiers over N feature rows.
+ *   x [G][N][ld] fp32, of which columns [col0, col0 + F) are read; labels [N] int32 in DEVICE memory, shared by the groups: frame n is
+ *   live iff 0 <= labels[n] < C (-1 = silence, a frame past its row's end); weight [G][C][F], bias [G][C].  Per group g and live frame n:
+ *     z = W_g x_n + b_g;  nll = logsumexp(z) - z[label];  pred = the lowest index among the largest z;  hit = (pred == label)
+ *     stats[g] = (sum nll, sum hit, live count);  g_weight[g] = sum_n (softmax(z) - onehot) x_n^T;  g_bias[g] = sum_n (softmax(z) - onehot)
+ *   (normalize = 1: both gradients divided by max(count, 1)).  A dead frame is not read, has nll = hit = 0 and pred = -1 and adds
+ *   nothing; with no live frame every sum is exactly 0.  g_weight / g_bias both NULL: evaluation only, the gradient work is skipped.
+ *   The planes nll / hit / pred [G][N] may each be NULL.
+ * A tile of 16 rows is staged in LDS once and serves both contractions on v_mfma_f32_16x16x4_f32 (fp32 operands and accumulation,
+ * classes padded to 16); logits and probabilities never reach memory; exp / log in fp32, the three stats sums in double.  Workgroup
+ * partials go to `workspace` (mtrssm_linear_probe_workspace_bytes(G, N, C, F) bytes, 8-byte aligned) and a second small kernel adds
+ * them in a fixed order (runs of consecutive partial sets in ascending order, then the runs; the stats by a fixed tree): no float
+ * atomics, a grid that depends on the shapes only, two calls agree bitwise.
+ * Null required pointers, only one of g_weight / g_bias, G < 1, N outside [1, 2^24), C outside 2 .. 16, F outside 1 .. 2048,
+ * col0 < 0, col0 + F > ld, G * N * ld >= 2^31, a normalize other than 0 / 1 or a short workspace return -1 without a launch (the
+ * size query returns -1 for sizes out of range). */
+int64_t mtrssm_linear_probe_workspace_bytes(int64_t G, int64_t N, int64_t C, int64_t F);
+int mtrssm_linear_probe_step(const float* x, int64_t ld, int64_t col0, const int32_t* labels, const float* weight, const float* bias,
+                             int64_t G, int64_t N, int64_t C, int64_t F, int32_t normalize, float* g_weight, float* g_bias, float* stats,
+                             float* nll, float* hit, int32_t* pred, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Digit reader: the inference path of the classifier that reads a digit off a predicted vision frame
  * (conv 3x3 1->32, ReLU, pool 2x2, conv 3x3 32->64, ReLU, pool 2x2, Linear 4096->128, ReLU, Linear 128->10; 32 x 32 frames).
  * mtrssm_digit_features: the convolutional trunk of a frame in one launch.  pred [frames][1024] is the decoder's RAW output;

@@ -174,6 +174,9 @@ SYMBOLS: dict[str, tuple[type | None, list[type]]] = {
     "mtrssm_horizon_table": (C.c_int, [_p, C.c_int64, _p, _p, C.c_int64, C.c_int64, _p, _p, _p]),
     "mtrssm_latent_log_ratio": (C.c_int, [_p, _p, _p, C.c_int64, C.c_int64, C.c_int64, _i, _p, _p]),
     "mtrssm_iw_bound": (C.c_int, [_p, _p, _p, _p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _p, _p]),
+    "mtrssm_linear_probe_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    "mtrssm_linear_probe_step": (C.c_int, [_p, C.c_int64, C.c_int64, _p, _p, _p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _i, _p, _p, _p, _p, _p, _p,
+                                           _p, C.c_int64, _p]),
     "mtrssm_digit_features": (C.c_int, [_p, C.c_int64, _p, C.c_int64, _i, _p, _p, _p, _p, _p, _p]),
     "mtrssm_digit_head": (C.c_int, [_p, _p, _p, C.c_int64, _p, C.c_int64, _p, _p, _p]),
     "mtrssm_word_counts": (C.c_int, [_p, _p, C.c_int64, _p, _p]),

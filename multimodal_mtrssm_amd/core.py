@@ -30,6 +30,7 @@ from multimodal_mtrssm_amd.likelihood import PLANES as LIKELIHOOD_PLANES
 from multimodal_mtrssm_amd.likelihood import LikelihoodBound, LikelihoodTable
 from multimodal_mtrssm_amd.networks import MTRNN, Representation, Transition
 from multimodal_mtrssm_amd.objective import likelihood
+from multimodal_mtrssm_amd.probe import LatentProbe, LinearProbe, ProbeTable, frame_labels
 from multimodal_mtrssm_amd.schedule import ElboSchedule, ElboTerms
 from multimodal_mtrssm_amd.skill import ForecastSkill, SkillTable
 from multimodal_mtrssm_amd.words import TransitionTable, WordTransitions
@@ -832,12 +833,16 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
                 raise ValueError(msg)
             noise[key] = u.reshape(B * S, *want[2:]).contiguous()
 
-    def _skill_rollout(self, batch: tuple[Tensor, ...], skill: ForecastSkill | LikelihoodBound, noise: Noise | None, lengths: Tensor | None,  # noqa: PLR0913
-                       expert_log_weights: Tensor | None, *, per_copy: bool = False) -> tuple[dict[str, Tensor], Tensor | None]:
+    def _skill_rollout(self, batch: tuple[Tensor, ...], skill: ForecastSkill | LikelihoodBound | LatentProbe, noise: Noise | None,  # noqa: PLR0913
+                       lengths: Tensor | None,
+                       expert_log_weights: Tensor | None, *, per_copy: bool = False,
+                       copy_bits: bool = False) -> tuple[dict[str, Tensor], Tensor | None]:
         """The rollout of a skill step (``forecast_skill``, ``word_transitions``): both encoders, the initial state of every row, the
         composed noise and ONE masked posterior rollout over ``B * S`` rows.  Returns the scan's outputs and the rows' lengths (or None).
         ``per_copy`` (``likelihood_bound``): every live frame is observed, and each copy of a row draws its own initial state and its own
-        posterior (``u_init`` ``(B, S, K)``, ``u_post`` ``(B, S, T, K)``) instead of sharing the row's."""
+        posterior (``u_init`` ``(B, S, K)``, ``u_post`` ``(B, S, T, K)``) instead of sharing the row's.  ``copy_bits``
+        (``probe_features``): every live frame is observed, copy ``s`` of a row sees the modalities ``skill.copy_bits()[s]`` (at frame 0
+        too) and the copies share the row's uniforms (``u_init`` ``(B, K)``, ``u_post`` ``(B, T, K)``)."""
         actions = batch[0]
         audio_obs, vision_obs = self.get_observations_from_batch(batch)
         B, T = actions.shape[:2]
@@ -851,13 +856,31 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         noise = dict(noise or {})
         conv.begin_step(dev)
         audio_embed, vision_embed = self._encode_both(audio_obs, vision_obs)
-        context = T if per_copy else skill.context
+        context = T if per_copy or copy_bits else skill.context
         sm = Forecast(context).sample(torch.zeros(B, device=dev), T, valid)  # (a fixed context: the uniforms do not matter)
+        wide = lambda x: x.repeat_interleave(S, dim=0)  # noqa: E731  (row (b, s) -> b * S + s)
+        if copy_bits:
+            codes = (sm.codes[:, None, :] & skill.copy_bits(dev)[None, :, None]).reshape(B * S, T)
+            mask0 = (sm.mask0[:, None, :] & skill.copy_observed(dev)[None]).reshape(B * S, 2)
+            embed0 = _masked_mean_embed(wide(audio_embed[:, 0]), wide(vision_embed[:, 0]), mask0)
+            for key, mid in (*((k, ()) for k in self._INIT_KEYS), *((k, (T,)) for k in self._POST_KEYS)):
+                want = (B, *mid, self._category_size_of(key))
+                u = noise.get(key)
+                u = _rand(actions, *want) if u is None else u  # (drawn per ROW: the copies of a row share their uniforms)
+                if tuple(u.shape) != want:
+                    msg = f"noise[{key!r}] must have shape {want}, got {tuple(u.shape)}"
+                    raise ValueError(msg)
+                noise[key] = wide(u).contiguous()
+            state0 = self._initial_for_step(embed0, noise)
+            logw = self._expert_logw(audio_embed, vision_embed, expert_log_weights, B, T)  # the gate once per row ...
+            logw = None if logw is None else wide(logw)  # ... repeated for its S copies
+            out = self._rollout_embedded(wide(actions), wide(audio_embed), wide(vision_embed), state0, noise, sample_prior=False, modality=codes,
+                                         expert_log_weights=logw)
+            return out, valid
         bits = skill.bits
         codes = sm.codes & bits
         mask0 = sm.mask0 & skill.observed(dev)
         embed0 = _masked_mean_embed(audio_embed[:, 0], vision_embed[:, 0], mask0)
-        wide = lambda x: x.repeat_interleave(S, dim=0)  # noqa: E731  (row (b, s) -> b * S + s)
         if per_copy:
             self._per_copy_noise(noise, self._INIT_KEYS, B, S)
             self._per_copy_noise(noise, self._POST_KEYS, B, S, T)
@@ -1007,6 +1030,66 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
                 planes[:, r0:r1] = part
         table.planes = planes if keep_states else None
         table.states = self._posterior_from_rollout(out) if keep_states else None
+        return table
+
+    def _check_probe_step(self, batch: tuple[Tensor, ...], probe: LatentProbe) -> None:
+        if not isinstance(probe, LatentProbe):
+            msg = f"probe must be a LatentProbe, got {type(probe).__name__}"
+            raise ValueError(msg)
+        if self.get_modality_mask_from_batch(batch) is not None:
+            msg = "a skill step decides what the model observes: a masked (7-tuple) batch already says what is seen"
+            raise ValueError(msg)
+        if self.state_carry is not None:
+            msg = "a skill step starts every row from its own frame 0: it does not combine with a set state_carry"
+            raise ValueError(msg)
+
+    @torch.no_grad()
+    def probe_features(self, batch: tuple[Tensor, ...], probe: LatentProbe, noise: Noise | None = None, lengths: Tensor | None = None, *,
+                       expert_log_weights: Tensor | None = None) -> tuple[Tensor, Tensor | None]:
+        """The features a linear probe reads: ``x [G, B, T, Ffull]`` and the rows' lengths ``valid`` (int32 ``[B]``, or
+        None).  Both encoders run once, then ONE masked posterior rollout over ``B * G`` rows (row ``b * G + g``): copy ``g`` of a row
+        observes ``probe.observe[g]`` on every live step and at frame 0, nothing at or past the row's end, and the copies share the
+        row's uniforms (``probe.noise_shapes``).  ``x[g]`` is the feature the decoders would read of that posterior; ``probe.columns(self)``
+        names the part to probe in place.  No masked (7-tuple) batch, no ``state_carry``; a weighted model runs its gate once per row."""
+        self._check_probe_step(batch, probe)
+        B, T = batch[0].shape[:2]
+        out, valid = self._skill_rollout(batch, probe, noise, lengths, expert_log_weights, copy_bits=True)
+        feature = self._feature_of(out)  # [B * G, T, Ffull]
+        return feature.reshape(B, probe.groups, T, -1).permute(1, 0, 2, 3).contiguous(), valid
+
+    @torch.no_grad()
+    def probe_evaluate(self, batch: tuple[Tensor, ...], labels: Tensor, probe: LatentProbe, linear: LinearProbe,  # noqa: PLR0913
+                       table: ProbeTable | None = None, noise: Noise | None = None, lengths: Tensor | None = None, *,
+                       expert_log_weights: Tensor | None = None) -> ProbeTable:
+        """One evaluation step of a fitted probe: ``probe_features``, ONE evaluation-only ``linear.step`` with planes on
+        ``probe.columns(self)`` and the fold of ``hit`` / ``nll`` by frame position into ``table`` (a new one when None), which is
+        returned; ``table.stats`` keeps the step's ``ProbeStats`` (planes ``[G, B * T]``).  ``labels``: int ``[B, T]`` on the device,
+        -1 = silence; a frame at or past its row's end is dead whatever its label."""
+        self._check_probe_step(batch, probe)
+        if not isinstance(linear, LinearProbe):
+            msg = f"linear must be a LinearProbe, got {type(linear).__name__}"
+            raise ValueError(msg)
+        actions = batch[0]
+        B, T = actions.shape[:2]
+        G, dev = probe.groups, actions.device
+        col0, width = probe.columns(self)
+        if linear.groups != G or linear.features != width:
+            msg = f"{probe!r} on {type(self).__name__} needs a LinearProbe of {G} groups and {width} features, got {linear.groups} and {linear.features}"
+            raise ValueError(msg)
+        if tuple(labels.shape) != (B, T) or labels.dtype not in (torch.int32, torch.int64) or labels.device != dev:
+            msg = f"labels must be an int32 / int64 tensor of shape {(B, T)} on {dev}, got {labels.dtype} {tuple(labels.shape)} on {labels.device}"
+            raise ValueError(msg)
+        if table is not None and (not isinstance(table, ProbeTable) or table.steps != T or table.groups != G or table.buffer.device != dev):
+            msg = f"table must be a ProbeTable of {G} groups and {T} steps on {dev}"
+            raise ValueError(msg)
+        x, valid = self.probe_features(batch, probe, noise, lengths, expert_log_weights=expert_log_weights)
+        flat = frame_labels(labels, valid)
+        stats = linear.step(x.reshape(G, B * T, -1), flat, col0=col0, grad=False, planes=True)
+        if table is None:
+            table = ProbeTable(G, T, dev, probe.observe)
+        live = ((flat >= 0) & (flat < linear.classes)).reshape(B, T)
+        table.fold(stats.hit.reshape(G, B, T), stats.nll.reshape(G, B, T), live)
+        table.stats = stats
         return table
 
     def _read_vision(self, feature: Tensor, classifier: DigitClassifier) -> Tensor:

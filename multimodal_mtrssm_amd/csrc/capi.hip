@@ -90,6 +90,9 @@ int ensemble_score_launch(const float*, const float*, const int32_t*, int64_t, i
 int horizon_table_launch(const float*, int64_t, const int32_t*, const int32_t*, int64_t, int64_t, float*, float*, hipStream_t);
 int latent_log_ratio_launch(const float*, const float*, const float*, int64_t, int64_t, int64_t, int, float*, hipStream_t);
 int iw_bound_launch(const float*, const float*, const float*, const int32_t*, int64_t, int64_t, int64_t, int64_t, int64_t, float*, hipStream_t);
+int64_t linear_probe_workspace_bytes(int64_t, int64_t, int64_t, int64_t);
+int linear_probe_step_launch(const float*, int64_t, int64_t, const int32_t*, const float*, const float*, int64_t, int64_t, int64_t, int64_t, int, float*,
+                             float*, float*, float*, float*, int32_t*, void*, int64_t, hipStream_t);
 int digit_features_launch(const float*, int64_t, const int32_t*, int64_t, int, const float*, const float*, const float*, const float*, float*,
                           hipStream_t);
 int digit_head_launch(const float*, const float*, const float*, int64_t, const int32_t*, int64_t, int32_t*, float*, hipStream_t);
@@ -504,6 +507,15 @@ MTRSSM_API int mtrssm_latent_log_ratio(const float* post_logits, const float* pr
 MTRSSM_API int mtrssm_iw_bound(const float* se_audio, const float* se_vision, const float* log_ratio, const int32_t* valid, int64_t B, int64_t S,
                                int64_t T, int64_t event_audio, int64_t event_vision, float* planes, void* stream) {
   return iw_bound_launch(se_audio, se_vision, log_ratio, valid, B, S, T, event_audio, event_vision, planes, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int64_t mtrssm_linear_probe_workspace_bytes(int64_t G, int64_t N, int64_t C, int64_t F) {
+  return linear_probe_workspace_bytes(G, N, C, F);
+}
+MTRSSM_API int mtrssm_linear_probe_step(const float* x, int64_t ld, int64_t col0, const int32_t* labels, const float* weight, const float* bias,
+                                        int64_t G, int64_t N, int64_t C, int64_t F, int32_t normalize, float* g_weight, float* g_bias, float* stats,
+                                        float* nll, float* hit, int32_t* pred, void* workspace, int64_t workspace_bytes, void* stream) {
+  return linear_probe_step_launch(x, ld, col0, labels, weight, bias, G, N, C, F, normalize, g_weight, g_bias, stats, nll, hit, pred, workspace,
+                                  workspace_bytes, static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int mtrssm_digit_features(const float* pred, int64_t frames, const int32_t* select, int64_t N, int32_t act, const float* conv1_w,
                                      const float* conv1_b, const float* conv2_w, const float* conv2_b, float* features, void* stream) {

@@ -21,6 +21,7 @@ from multimodal_mtrssm_amd.dropout import ModalityDropout
 from multimodal_mtrssm_amd.forecast import Forecast
 from multimodal_mtrssm_amd.optim import FlatParameters
 from multimodal_mtrssm_amd.likelihood import LikelihoodBound
+from multimodal_mtrssm_amd.probe import LatentProbe
 from multimodal_mtrssm_amd.skill import ForecastSkill
 
 
@@ -104,6 +105,11 @@ class FlatDataParallel:
         """``bound`` bound to this object's process group: set the result as ``model.val_likelihood`` and ``on_validation_epoch_end``
         all-reduces the likelihood table over that group (its uniforms' batch dimension comes first: draw them with ``noise_source``)."""
         return bound.for_group(self.group)
+
+    def probe(self, probe: LatentProbe) -> LatentProbe:
+        """``probe`` bound to this object's process group: ``ProbeTable.all_reduce(probe.group)`` and ``LinearProbe.fit(..., group=
+        probe.group)`` then work over the rows of every rank (its uniforms' batch dimension comes first: draw them with ``noise_source``)."""
+        return probe.for_group(self.group)
 
     @property
     def grad_scale(self) -> float:
