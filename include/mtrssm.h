@@ -988,6 +988,41 @@ int mtrssm_digit_head(const float* hidden, const float* w, const float* b, int64
                       float* logits, void* stream);
 int mtrssm_word_counts(const int32_t* word, const int32_t* digit, int64_t N, float* counts, void* stream);
 
+/* Training the digit reader.
+ * mtrssm_digit_features_train: mtrssm_digit_features (same arguments, bit-identical features) that also writes the TAPE,
+ *   uint8 [N][8192 + 4096], 16-byte aligned: one byte per pooled unit of conv1 ([32][16][16]) and of conv2 ([64][8][8], the feature
+ *   order) -- the member 2 dy + dx of its 2 x 2 window that holds the maximum (the first in row-major order among equal maxima:
+ *   torch's max_pool2d backward), 4 when max + bias <= 0 (a dead unit: relu' = 0).
+ * mtrssm_digit_trunk_bwd: the gradients of conv1 / conv2 from g_features [N][4096], with the pool and ReLU choices the tape states
+ *   (so the result is a linear function of g_features).  labels int32 [N] in DEVICE memory: row n is live iff 0 <= labels[n] < 10;
+ *   a dead row (and one whose select index lies outside [0, frames)) is not read and adds exactly nothing.  pred / frames / select /
+ *   N / act as in mtrssm_digit_features.  g_conv1_w [32][1][3][3], g_conv1_b [32], g_conv2_w [64][32][3][3], g_conv2_b [64] are
+ *   overwritten, or added to when accumulate = 1.  fp32 arithmetic on exact operands; per frame the kernel reads the frame, its
+ *   g_features row and its tape row.  Every workgroup (min(N, CUs) of them) writes one partial set into `workspace`
+ *   (mtrssm_digit_trunk_bwd_workspace_bytes(N) bytes, 16-byte aligned; -1 for N outside (0, 2^31)); a second launch adds the sets in
+ *   ascending order: no atomics between workgroups, two calls agree bitwise.  No input gradient is produced.
+ * mtrssm_digit_head_train: the head with dropout, its loss and its backward, one wave per row.  hidden [N][128] is fc1's ACTIVATED
+ *   output h, w [10][128], b [10].  Unit j of row n is kept iff (x >> 8) 2^-24 >= p, x = word j & 3 of
+ *   Philox4x32-10(counter = (j >> 2, row0 + rows[n], step, 0), key = (key0, key1)) -- rows int32 [N] in DEVICE memory are the rows' global
+ *   numbers (NULL: rows[n] = n), so a row draws the same mask in whatever batch or shard it arrives; p = 0 keeps everything.  With m = keep / (1 - p):
+ *   z = w (h m) + b, nll[n] = logsumexp(z) - z[label], pred[n] = the lowest index among the largest z, d = softmax(z) - onehot
+ *   (normalize = 1: divided by max(live count, 1)), g_hidden[n] = (w^T d) m [h > 0], g_w (+)= sum_n d (h m)^T, g_b (+)= sum_n d,
+ *   stats[3] = (sum nll, sum hit, live count).  A dead row has nll 0, pred -1, a zero g_hidden row and adds nothing.  nll / pred may
+ *   be NULL.  Workgroup partial sums go through `workspace` (mtrssm_digit_head_train_workspace_bytes(N) bytes) and are added in a
+ *   fixed order.  Null pointers, N outside (0, 2^31), p outside [0, 1), row0 / step that are no 32-bit words, flags other than
+ *   0 / 1, misaligned buffers or a short workspace return -1 without a launch. */
+int mtrssm_digit_features_train(const float* pred, int64_t frames, const int32_t* select, int64_t N, int32_t act, const float* conv1_w,
+                                const float* conv1_b, const float* conv2_w, const float* conv2_b, float* features, uint8_t* tape, void* stream);
+int64_t mtrssm_digit_trunk_bwd_workspace_bytes(int64_t N);
+int mtrssm_digit_trunk_bwd(const float* pred, int64_t frames, const int32_t* select, int64_t N, int32_t act, const uint8_t* tape,
+                           const float* g_features, const int32_t* labels, const float* conv1_w, const float* conv1_b, const float* conv2_w,
+                           float* g_conv1_w, float* g_conv1_b, float* g_conv2_w, float* g_conv2_b, int32_t accumulate, void* workspace,
+                           int64_t workspace_bytes, void* stream);
+int64_t mtrssm_digit_head_train_workspace_bytes(int64_t N);
+int mtrssm_digit_head_train(const float* hidden, const float* w, const float* b, const int32_t* labels, const int32_t* rows, int64_t N, int64_t row0,
+                            int64_t step, uint32_t key0, uint32_t key1, float p, int32_t normalize, float* nll, int32_t* pred, float* stats, float* g_hidden,
+                            float* g_w, float* g_b, int32_t accumulate, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Fused AdamW over one flat fp32 parameter buffer, with global-norm gradient clipping
  * (yaml: torch.optim.AdamW lr 1e-3; trainer.gradient_clip_val 10 -- default.yaml:103-107,119).

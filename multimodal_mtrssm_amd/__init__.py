@@ -10,6 +10,7 @@ from multimodal_mtrssm_amd.carry import StateCarry
 from multimodal_mtrssm_amd.cnn import Decoder, Encoder
 from multimodal_mtrssm_amd.core import MoPoE_MMTRSSM, MoPoE_MRSSM, WeightedMoPoE_MMTRSSM, WeightedMoPoE_MRSSM
 from multimodal_mtrssm_amd.dataset import DeviceEpisodeLoader, EpisodeBatch, EpisodeDataModule, EpisodeDataModuleConfig
+from multimodal_mtrssm_amd.digit_train import DigitStats, DigitTrainer, dropout_mask_reference, tape_reference
 from multimodal_mtrssm_amd.digits import DigitClassifier
 from multimodal_mtrssm_amd.distributions import (
     Distribution,
@@ -38,8 +39,8 @@ from multimodal_mtrssm_amd.state import MTState, State, cat_mtstates, cat_states
 __version__ = "0.1.0"
 
 __all__ = [
-    "MLP", "MTRNN", "Decoder", "DeviceEpisodeLoader", "DigitClassifier", "Distribution", "Encoder", "EpisodeBatch", "EpisodeDataModule", "ElboSchedule", "EpisodeDataModuleConfig", "ExpertWeights", "FlatAdamW", "FlatDataParallel", "Forecast", "ForecastSkill", "GlobalRowNoise", "LatentProbe", "LikelihoodBound", "LikelihoodTable", "LinearProbe", "MTState", "MoPoE_MMTRSSM",
+    "MLP", "MTRNN", "Decoder", "DeviceEpisodeLoader", "DigitClassifier", "DigitStats", "DigitTrainer", "Distribution", "Encoder", "EpisodeBatch", "EpisodeDataModule", "ElboSchedule", "EpisodeDataModuleConfig", "ExpertWeights", "FlatAdamW", "FlatDataParallel", "Forecast", "ForecastSkill", "GlobalRowNoise", "LatentProbe", "LikelihoodBound", "LikelihoodTable", "LinearProbe", "MTState", "MoPoE_MMTRSSM",
     "MoPoE_MRSSM", "ModalityDropout", "MultiOneHot", "MultiOneHotFactory", "ProbeStats", "ProbeTable", "ReduceLROnPlateau", "Representation", "SkillTable", "State", "StateCarry", "Transition", "TransitionTable", "WeightedMoPoE_MMTRSSM", "WeightedMoPoE_MRSSM", "WordTransitions", "cat_distribution",
     "cat_mtstates", "cat_states", "inject_uniforms", "kl_divergence", "likelihood", "load_reference_checkpoint", "make_mmtrssm", "make_mrssm",
-    "stack_distribution", "stack_mtstates", "stack_states",
+    "stack_distribution", "stack_mtstates", "stack_states", "dropout_mask_reference", "tape_reference",
 ]

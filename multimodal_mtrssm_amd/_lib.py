@@ -180,6 +180,12 @@ SYMBOLS: dict[str, tuple[type | None, list[type]]] = {
     "mtrssm_digit_features": (C.c_int, [_p, C.c_int64, _p, C.c_int64, _i, _p, _p, _p, _p, _p, _p]),
     "mtrssm_digit_head": (C.c_int, [_p, _p, _p, C.c_int64, _p, C.c_int64, _p, _p, _p]),
     "mtrssm_word_counts": (C.c_int, [_p, _p, C.c_int64, _p, _p]),
+    "mtrssm_digit_features_train": (C.c_int, [_p, C.c_int64, _p, C.c_int64, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "mtrssm_digit_trunk_bwd_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "mtrssm_digit_trunk_bwd": (C.c_int, [_p, C.c_int64, _p, C.c_int64, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, C.c_int64, _p]),
+    "mtrssm_digit_head_train_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "mtrssm_digit_head_train": (C.c_int, [_p, _p, _p, _p, _p, C.c_int64, C.c_int64, C.c_int64, C.c_uint32, C.c_uint32, C.c_float, _i, _p, _p, _p, _p, _p, _p,
+                                          _i, _p, C.c_int64, _p]),
     "mtrssm_elbo_combine_counted_fwd": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int64, C.c_float, C.c_float, _p, _p, _p, _p, _p]),
     "mtrssm_elbo_combine_counted_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int64, C.c_float, C.c_float, _p, _p, _p, _p, _p]),
     "mtrssm_elbo_schedule_fwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, C.c_int64, ElboSchedule, _p, _p, _p, _p, _p, _p, _p]),

@@ -97,6 +97,14 @@ int digit_features_launch(const float*, int64_t, const int32_t*, int64_t, int, c
                           hipStream_t);
 int digit_head_launch(const float*, const float*, const float*, int64_t, const int32_t*, int64_t, int32_t*, float*, hipStream_t);
 int word_counts_launch(const int32_t*, const int32_t*, int64_t, float*, hipStream_t);
+int digit_features_train_launch(const float*, int64_t, const int32_t*, int64_t, int, const float*, const float*, const float*, const float*, float*,
+                                unsigned char*, hipStream_t);
+int64_t digit_trunk_bwd_workspace_bytes(int64_t);
+int digit_trunk_bwd_launch(const float*, int64_t, const int32_t*, int64_t, int, const unsigned char*, const float*, const int32_t*, const float*,
+                           const float*, const float*, float*, float*, float*, float*, int, void*, int64_t, hipStream_t);
+int64_t digit_head_train_workspace_bytes(int64_t);
+int digit_head_train_launch(const float*, const float*, const float*, const int32_t*, const int32_t*, int64_t, int64_t, int64_t, uint32_t, uint32_t, float, int, float*,
+                            int32_t*, float*, float*, float*, float*, int, void*, int64_t, hipStream_t);
 int modality_dropout_launch(const float*, int64_t, int64_t, int64_t, float, float, int64_t, int64_t, int32_t*, float*, float*, unsigned char*, float*,
                             hipStream_t);
 int sumsq_launch(const float*, int64_t, float*, hipStream_t);
@@ -527,4 +535,25 @@ MTRSSM_API int mtrssm_digit_head(const float* hidden, const float* w, const floa
 }
 MTRSSM_API int mtrssm_word_counts(const int32_t* word, const int32_t* digit, int64_t N, float* counts, void* stream) {
   return word_counts_launch(word, digit, N, counts, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_digit_features_train(const float* pred, int64_t frames, const int32_t* select, int64_t N, int32_t act, const float* conv1_w,
+                                           const float* conv1_b, const float* conv2_w, const float* conv2_b, float* features, uint8_t* tape,
+                                           void* stream) {
+  return digit_features_train_launch(pred, frames, select, N, act, conv1_w, conv1_b, conv2_w, conv2_b, features, tape, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int64_t mtrssm_digit_trunk_bwd_workspace_bytes(int64_t N) { return digit_trunk_bwd_workspace_bytes(N); }
+MTRSSM_API int mtrssm_digit_trunk_bwd(const float* pred, int64_t frames, const int32_t* select, int64_t N, int32_t act, const uint8_t* tape,
+                                      const float* g_features, const int32_t* labels, const float* conv1_w, const float* conv1_b,
+                                      const float* conv2_w, float* g_conv1_w, float* g_conv1_b, float* g_conv2_w, float* g_conv2_b,
+                                      int32_t accumulate, void* workspace, int64_t workspace_bytes, void* stream) {
+  return digit_trunk_bwd_launch(pred, frames, select, N, act, tape, g_features, labels, conv1_w, conv1_b, conv2_w, g_conv1_w, g_conv1_b, g_conv2_w,
+                                g_conv2_b, accumulate, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int64_t mtrssm_digit_head_train_workspace_bytes(int64_t N) { return digit_head_train_workspace_bytes(N); }
+MTRSSM_API int mtrssm_digit_head_train(const float* hidden, const float* w, const float* b, const int32_t* labels, const int32_t* rows, int64_t N,
+                                       int64_t row0, int64_t step, uint32_t key0, uint32_t key1, float p, int32_t normalize, float* nll, int32_t* pred,
+                                       float* stats, float* g_hidden, float* g_w, float* g_b, int32_t accumulate, void* workspace,
+                                       int64_t workspace_bytes, void* stream) {
+  return digit_head_train_launch(hidden, w, b, labels, rows, N, row0, step, key0, key1, p, normalize, nll, pred, stats, g_hidden, g_w, g_b, accumulate,
+                                 workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }

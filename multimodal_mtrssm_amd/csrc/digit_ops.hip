@@ -14,6 +14,8 @@
 // pixel -- stored as 128-byte runs in the view(-1, 4096) order.  The 16 image positions (dy + ty, dx + tx) a lane needs are
 // read once per channel block (32 ds_read_b128) and serve all 36 (window member, tap) pairs.  The A operands (both pieces of
 // 32 output channels x 288) stay in registers for the whole launch.  Arithmetic: bf16x2 -- p0 q0 + p0 q1 + p1 q0, fp32 sums.
+// The same kernel with TAPE set is the training forward (section 6m, mtrssm_digit_features_train): identical features, plus one byte
+// per pooled unit naming the window member that held the maximum; csrc/digit_train.hip has the backward that reads it.
 #include "scan_common.h"
 
 namespace mtrssm {
@@ -31,6 +33,7 @@ constexpr int kThreads = 256;
 constexpr int kPix = 1024;             // 32 x 32 input pixels
 constexpr int kC1 = 32, kC2 = 64;      // channels after conv1 / conv2
 constexpr int kFeat = kC2 * 64;        // 4096
+constexpr int kTape = kC1 * 256 + kFeat;  // bytes of a frame's tape: conv1's pooled units, then conv2's in the feature order
 constexpr int kXW = 34;                // haloed input row
 constexpr int kPW = 18;                // haloed pooled row
 constexpr int kRowB = kC1 * 2 + 16;    // bytes per image row: one position, 32 bf16 channels, padded to an odd number of 16-byte slots
@@ -45,12 +48,14 @@ __device__ __forceinline__ void split2(float x, unsigned short& hi, unsigned sho
   lo = __builtin_bit_cast(unsigned short, l);
 }
 
-template <bool TANH>
+// TAPE (the training forward, section 6m): the same arithmetic, plus one byte per pooled unit -- the member 2 dy + dx of its 2 x 2
+// window that holds the maximum (the first among equal maxima: a strict > over members 0 .. 3), 4 when max + bias <= 0.
+template <bool TANH, bool TAPE>
 __global__ __launch_bounds__(kThreads, 1) void digit_features_kernel(const float* __restrict__ pred, int64_t frames,
                                                                      const int32_t* __restrict__ select, int N,
                                                                      const float* __restrict__ w1, const float* __restrict__ b1,
                                                                      const float* __restrict__ w2, const float* __restrict__ b2,
-                                                                     float* __restrict__ features) {
+                                                                     float* __restrict__ features, unsigned char* __restrict__ tape) {
   __shared__ __attribute__((aligned(16))) float xin[kXW * kXW];
   __shared__ __attribute__((aligned(16))) float w1s[kC1 * kW1Row];
   __shared__ __attribute__((aligned(16))) unsigned char img[2 * kImgB];
@@ -151,15 +156,18 @@ __global__ __launch_bounds__(kThreads, 1) void digit_features_kernel(const float
             const float4 wc = *reinterpret_cast<const float4*>(w1s + c * kW1Row + 8);
             const float w[9] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w, wc.x};
             float best = 0.f;
+            int arg = 0;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
               const int dy = q >> 1, dx = q & 1;
               float s = 0.f;
 #pragma unroll
               for (int t = 0; t < 9; ++t) s = fmaf(w[t], p[dy + t / 3][dx + t % 3], s);
+              if (TAPE && q > 0 && s > best) arg = q;
               best = q == 0 ? s : fmaxf(best, s);
             }
             best += wc.y;  // bias
+            if (TAPE) tape[(size_t)n * kTape + c * 256 + tid] = (unsigned char)(best <= 0.f ? 4 : arg);
             best = best > 0.f ? best : 0.f;
             split2(best, h[u], l[u]);
           }
@@ -207,6 +215,14 @@ __global__ __launch_bounds__(kThreads, 1) void digit_features_kernel(const float
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         float v = fmaxf(fmaxf(acc[0][r], acc[1][r]), fmaxf(acc[2][r], acc[3][r])) + bv[r];
+        if (TAPE) {  // the four members are this lane's four accumulators: compares only
+          int arg = 0;
+          float best = acc[0][r];
+#pragma unroll
+          for (int q = 1; q < 4; ++q)
+            if (acc[q][r] > best) { best = acc[q][r]; arg = q; }
+          tape[(size_t)n * kTape + kC1 * 256 + (cbase + (r & 3) + 8 * (r >> 2)) * 64 + ph * 32 + il] = (unsigned char)(v <= 0.f ? 4 : arg);
+        }
         v = v > 0.f ? v : 0.f;
         if (bad) v = __builtin_nanf("");
         out[((r & 3) + 8 * (r >> 2)) * 64] = v;
@@ -282,8 +298,25 @@ int cu_count() {
 
 }  // namespace
 
+namespace {
+int digit_features_any(const float* pred, int64_t frames, const int32_t* select, int64_t N, int act, const float* w1, const float* b1,
+                       const float* w2, const float* b2, float* features, unsigned char* tape, hipStream_t s);
+}
+
 int digit_features_launch(const float* pred, int64_t frames, const int32_t* select, int64_t N, int act, const float* w1, const float* b1,
                           const float* w2, const float* b2, float* features, hipStream_t s) {
+  return digit_features_any(pred, frames, select, N, act, w1, b1, w2, b2, features, nullptr, s);
+}
+
+int digit_features_train_launch(const float* pred, int64_t frames, const int32_t* select, int64_t N, int act, const float* w1, const float* b1,
+                                const float* w2, const float* b2, float* features, unsigned char* tape, hipStream_t s) {
+  if (!tape) { set_error("digit_features_train: null tape"); return MTRSSM_EINVAL; }
+  return digit_features_any(pred, frames, select, N, act, w1, b1, w2, b2, features, tape, s);
+}
+
+namespace {
+int digit_features_any(const float* pred, int64_t frames, const int32_t* select, int64_t N, int act, const float* w1, const float* b1,
+                       const float* w2, const float* b2, float* features, unsigned char* tape, hipStream_t s) {
   if (!pred || !w1 || !b1 || !w2 || !b2 || !features) { set_error("digit_features: null pointer"); return MTRSSM_EINVAL; }
   if (frames <= 0 || N <= 0 || frames >= (int64_t)1 << 31 || N >= (int64_t)1 << 31) {
     set_error("digit_features: need 0 < frames, N < 2^31 (got %lld %lld)", (long long)frames, (long long)N);
@@ -301,15 +334,23 @@ int digit_features_launch(const float* pred, int64_t frames, const int32_t* sele
   }
   const int cus = cu_count();
   const int grid = (int)(N < cus ? N : cus);
+#define MTRSSM_DIGIT_FEATURES(TANH, TAPE)                                                                                              \
+  do {                                                                                                                                \
+    set_last_kernel("mtrssm::digit_features_kernel<" #TANH ", " #TAPE ">");                                                           \
+    hipLaunchKernelGGL((digit_features_kernel<TANH, TAPE>), dim3(grid), dim3(kThreads), 0, s, pred, frames, select, (int)N, w1, b1, w2, \
+                       b2, features, tape);                                                                                           \
+  } while (0)
   if (act == MTRSSM_ACT_TANH) {
-    set_last_kernel("mtrssm::digit_features_kernel<true>");
-    hipLaunchKernelGGL((digit_features_kernel<true>), dim3(grid), dim3(kThreads), 0, s, pred, frames, select, (int)N, w1, b1, w2, b2, features);
+    if (tape) MTRSSM_DIGIT_FEATURES(true, true);
+    else MTRSSM_DIGIT_FEATURES(true, false);
   } else {
-    set_last_kernel("mtrssm::digit_features_kernel<false>");
-    hipLaunchKernelGGL((digit_features_kernel<false>), dim3(grid), dim3(kThreads), 0, s, pred, frames, select, (int)N, w1, b1, w2, b2, features);
+    if (tape) MTRSSM_DIGIT_FEATURES(false, true);
+    else MTRSSM_DIGIT_FEATURES(false, false);
   }
+#undef MTRSSM_DIGIT_FEATURES
   return check_launch("digit_features");
 }
+}  // namespace
 
 int digit_head_launch(const float* hidden, const float* w, const float* b, int64_t N, const int32_t* select, int64_t frames, int32_t* digit,
                       float* logits, hipStream_t s) {

@@ -1,4 +1,4 @@
-"""The digit reader: the small CNN that reads a digit off a predicted vision frame, inference only.
+"""The digit reader: the small CNN that reads a digit off a predicted vision frame (inference; ``digit_train.py`` fits it).
 
 The network is the evaluation's classifier, layer for layer and name for name (a checkpoint of it loads with ``strict=True``):
 
@@ -10,7 +10,8 @@ The network is the evaluation's classifier, layer for layer and name for name (a
 ``reference_logits`` states this in torch for any float dtype: it is the checker, and what runs for non-GPU tensors.  On the GPU the
 trunk is ONE ``mtrssm_digit_features`` launch (neither intermediate is written to memory; conv2 multiplies two bf16 pieces per
 operand), fc1 one ``mtrssm_gemm`` with its bias + ReLU epilogue, the head one ``mtrssm_digit_head`` launch.  ``select`` (int32
-``[N]``) picks the frames to read out of a larger decode without a copy.  Training the classifier is not part of this package.
+``[N]``) picks the frames to read out of a larger decode without a copy.  ``DigitClassifier()`` is frozen and in ``eval()``; ``digit_train.DigitTrainer``
+trains it on labelled frames and hands it back frozen.
 """
 
 from __future__ import annotations

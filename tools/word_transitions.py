@@ -13,8 +13,8 @@ own procedure: frame 0 of the interval gives the initial state, the last action 
 
 The test data are `.npz` episodes with `audio (T, 32, 32)`, `image (T, 1, 32, 32)`, `label (T,)` (-1 = silence) and `speaker (T, 6)`
 one-hot.  The model is built at `--dims deter,hidden,classes,cats,embed` (default: the reference's default.yaml) and the checkpoint is
-loaded by parameter name.  The classifier checkpoint is a state dict of the evaluation's classifier; training one is not part of
-this package.
+loaded by parameter name.  The classifier checkpoint is a state dict of the evaluation's classifier: `tools/train_digit_classifier.py`
+writes one from the labelled frames of such episodes, and one trained by the evaluation itself loads as well.
 """
 
 from __future__ import annotations
