@@ -1023,6 +1023,43 @@ int mtrssm_digit_head_train(const float* hidden, const float* w, const float* b,
                             int64_t step, uint32_t key0, uint32_t key1, float p, int32_t normalize, float* nll, int32_t* pred, float* stats, float* g_hidden,
                             float* g_w, float* g_b, int32_t accumulate, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Episode panels: the finished uint8 video `prior | observation | posterior (| error)` of N episodes, vision on
+ * the top row and magma-coloured audio on the bottom row, in one launch.  Replaces the logging callback's host composition
+ * (mrssm/callback.py:250-340 create_multimodal_combined_video; 689-905 log_multimodal_video with its per-frame numpy, matplotlib
+ * and PIL loops).
+ *   Inputs fp32 [N][T][C][H][W] per modality, ACTIVATED values in [-1, 1] (targets or decoder outputs; there is no fused tanh).
+ *   Pixel rule, fp32 in this order, no FMA contraction, correctly rounded division:
+ *     x = min(max((v + 1) / 2, 0), 1), NaN -> 0
+ *     vision byte = trunc(x * 255); Cv = 1 is replicated to RGB, Cv = 3 used as is
+ *     audio (channel 0): n = x * 2 - 1; db = (n + 1) / 2 * 80 - 80; s = clamp((clamp(db, -80, 0) - (-80)) / 80, 0, 1);
+ *       rgb = MAGMA[min(trunc(s * 256), 255)], MAGMA[k] = trunc(matplotlib magma(k)[:3] * 255)
+ *     error column: e = |prior01 - observation01| (Cv = 3: ((e0 + e1) + e2) / 3), rgb = MAGMA[min(trunc(e * 256), 255)]
+ *   Canvas: cw = max(Wv, Wa) * scale, Wc = J cw + (J - 1) gap, Hc = bar + Hv scale + gap + Ha scale, J = n_columns.  Cell (vision, j)
+ *   starts at (bar, j (cw + gap)), cell (audio, j) at (bar + Hv scale + gap, j (cw + gap)); a frame is drawn left-aligned, nearest
+ *   neighbour (canvas[y0 + y][x0 + x] = frame[y / scale][x / scale]), the rest of its cell is 0.  Gap pixels are (64, 64, 64).  The
+ *   `bar` top rows are (0, 160, 0) while t < context[n] and (255, 140, 0) from there on.  codes [N][T] int32 (bit 0 audio, bit 1
+ *   vision; NULL: both everywhere): with blank_unseen the OBSERVATION cell of a modality that is not seen at (n, t) is black.  valid
+ *   [N] int32 (NULL: T everywhere): a frame t >= valid[n] is black altogether.  label = p > 0: the decimal digits of frame0 + t in a
+ *   3 x 5 font of p x p pixels (p between digits, a margin of p) white on a black box whose corner is the canvas' (0, 0), drawn last.
+ *   out: uint8 [N][T][Hc][Wc][3], 4-byte aligned, mtrssm_episode_panel_bytes(geom, &Hc, &Wc) bytes (Hc / Wc may be NULL).
+ * One launch: a lane writes 4 consecutive pixels of the flat video as 3 whole dwords (only the video's final 1 .. 3 bytes, when
+ * N T Hc Wc is no multiple of 4, are byte stores); a source element is coloured once for the `scale` pixels of a row it serves.  No
+ * atomics; every byte depends on the inputs alone.
+ * Bad geometry (sizes < 1, Cv not 1 / 3, scale outside 1 .. 64, gap / bar outside 0 .. 64, label outside 0 .. 16, columns outside
+ * 0 .. 3 or repeated, n_columns outside 1 .. 4, a canvas above 32768 either way, frame0 < 0), null context / out, a null input that a
+ * column reads or a misaligned buffer return -1 without a launch (the size query returns -1 too). */
+#define MTRSSM_PANEL_PRIOR 0
+#define MTRSSM_PANEL_OBSERVATION 1
+#define MTRSSM_PANEL_POSTERIOR 2
+#define MTRSSM_PANEL_ERROR 3
+typedef struct MtrssmPanelGeom {
+  int32_t N, T, Ca, Ha, Wa, Cv, Hv, Wv, scale, gap, bar, label, frame0, columns[4], n_columns, blank_unseen;
+} MtrssmPanelGeom;
+int64_t mtrssm_episode_panel_bytes(const MtrssmPanelGeom* geom, int32_t* Hc, int32_t* Wc);
+int mtrssm_episode_panel(const MtrssmPanelGeom* geom, const float* obs_a, const float* post_a, const float* prior_a, const float* obs_v,
+                         const float* post_v, const float* prior_v, const int32_t* codes, const int32_t* valid, const int32_t* context,
+                         uint8_t* out, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Fused AdamW over one flat fp32 parameter buffer, with global-norm gradient clipping
  * (yaml: torch.optim.AdamW lr 1e-3; trainer.gradient_clip_val 10 -- default.yaml:103-107,119).

@@ -29,6 +29,7 @@ from multimodal_mtrssm_amd.likelihood import LikelihoodBound, LikelihoodTable
 from multimodal_mtrssm_amd.networks import MLP, MTRNN, Representation, Transition
 from multimodal_mtrssm_amd.objective import likelihood
 from multimodal_mtrssm_amd.optim import FlatAdamW, ReduceLROnPlateau, load_reference_checkpoint
+from multimodal_mtrssm_amd.panel import EpisodePanel, EpisodePanelLogger, EpisodeVideo
 from multimodal_mtrssm_amd.parallel import FlatDataParallel, GlobalRowNoise
 from multimodal_mtrssm_amd.probe import LatentProbe, LinearProbe, ProbeStats, ProbeTable
 from multimodal_mtrssm_amd.schedule import ElboSchedule
@@ -39,7 +40,7 @@ from multimodal_mtrssm_amd.state import MTState, State, cat_mtstates, cat_states
 __version__ = "0.1.0"
 
 __all__ = [
-    "MLP", "MTRNN", "Decoder", "DeviceEpisodeLoader", "DigitClassifier", "DigitStats", "DigitTrainer", "Distribution", "Encoder", "EpisodeBatch", "EpisodeDataModule", "ElboSchedule", "EpisodeDataModuleConfig", "ExpertWeights", "FlatAdamW", "FlatDataParallel", "Forecast", "ForecastSkill", "GlobalRowNoise", "LatentProbe", "LikelihoodBound", "LikelihoodTable", "LinearProbe", "MTState", "MoPoE_MMTRSSM",
+    "MLP", "MTRNN", "Decoder", "DeviceEpisodeLoader", "DigitClassifier", "DigitStats", "DigitTrainer", "Distribution", "Encoder", "EpisodeBatch", "EpisodeDataModule", "ElboSchedule", "EpisodeDataModuleConfig", "EpisodePanel", "EpisodePanelLogger", "EpisodeVideo", "ExpertWeights", "FlatAdamW", "FlatDataParallel", "Forecast", "ForecastSkill", "GlobalRowNoise", "LatentProbe", "LikelihoodBound", "LikelihoodTable", "LinearProbe", "MTState", "MoPoE_MMTRSSM",
     "MoPoE_MRSSM", "ModalityDropout", "MultiOneHot", "MultiOneHotFactory", "ProbeStats", "ProbeTable", "ReduceLROnPlateau", "Representation", "SkillTable", "State", "StateCarry", "Transition", "TransitionTable", "WeightedMoPoE_MMTRSSM", "WeightedMoPoE_MRSSM", "WordTransitions", "cat_distribution",
     "cat_mtstates", "cat_states", "inject_uniforms", "kl_divergence", "likelihood", "load_reference_checkpoint", "make_mmtrssm", "make_mrssm",
     "stack_distribution", "stack_mtstates", "stack_states", "dropout_mask_reference", "tape_reference",

@@ -99,6 +99,10 @@ StateTable = _struct("MtrssmStateTable", [
     ("count", _i), ("width", _i * STATE_MAX), ("src_stride", C.c_int64 * STATE_MAX), ("src", _p * STATE_MAX), ("alt", _p * STATE_MAX),
     ("dst", _p * STATE_MAX)])
 
+PANEL_COLUMNS = {"prior": 0, "observation": 1, "posterior": 2, "error": 3}  # MTRSSM_PANEL_*
+PanelGeom = _struct("MtrssmPanelGeom", [(n, _i) for n in ("N", "T", "Ca", "Ha", "Wa", "Cv", "Hv", "Wv", "scale", "gap", "bar", "label", "frame0")]
+                    + [("columns", _i * 4), ("n_columns", _i), ("blank_unseen", _i)])
+
 # every symbol include/mtrssm.h declares (tests/test_capi.py checks the header against this list)
 SYMBOLS: dict[str, tuple[type | None, list[type]]] = {
     "mtrssm_version": (C.c_int, []),
@@ -177,6 +181,8 @@ SYMBOLS: dict[str, tuple[type | None, list[type]]] = {
     "mtrssm_linear_probe_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "mtrssm_linear_probe_step": (C.c_int, [_p, C.c_int64, C.c_int64, _p, _p, _p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _i, _p, _p, _p, _p, _p, _p,
                                            _p, C.c_int64, _p]),
+    "mtrssm_episode_panel_bytes": (C.c_int64, [C.POINTER(PanelGeom), C.POINTER(_i), C.POINTER(_i)]),
+    "mtrssm_episode_panel": (C.c_int, [C.POINTER(PanelGeom), _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "mtrssm_digit_features": (C.c_int, [_p, C.c_int64, _p, C.c_int64, _i, _p, _p, _p, _p, _p, _p]),
     "mtrssm_digit_head": (C.c_int, [_p, _p, _p, C.c_int64, _p, C.c_int64, _p, _p, _p]),
     "mtrssm_word_counts": (C.c_int, [_p, _p, C.c_int64, _p, _p]),

@@ -30,6 +30,7 @@ from multimodal_mtrssm_amd.likelihood import PLANES as LIKELIHOOD_PLANES
 from multimodal_mtrssm_amd.likelihood import LikelihoodBound, LikelihoodTable
 from multimodal_mtrssm_amd.networks import MTRNN, Representation, Transition
 from multimodal_mtrssm_amd.objective import likelihood
+from multimodal_mtrssm_amd.panel import EpisodePanel, EpisodeVideo
 from multimodal_mtrssm_amd.probe import LatentProbe, LinearProbe, ProbeTable, frame_labels
 from multimodal_mtrssm_amd.schedule import ElboSchedule, ElboTerms
 from multimodal_mtrssm_amd.skill import ForecastSkill, SkillTable
@@ -963,6 +964,102 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
             return cnn.decode_pair(da, dv, feature, feature, raw=True), acts
         kw = {"raw": True} if fused else {}
         return (da(feature, **kw) if audio else None, dv(feature, **kw) if vision else None), acts
+
+    @torch.no_grad()
+    def render_episodes(self, batch: tuple[Tensor, ...], panel: EpisodePanel, noise: Noise | None = None, lengths: Tensor | None = None, *,  # noqa: PLR0913, PLR0914
+                        rows: Tensor | list[int] | None = None, frame0: int = 0, keep_states: bool = False,
+                        expert_log_weights: Tensor | None = None) -> EpisodeVideo:
+        """The episode panels of a batch: what the reference's logging callback shows per episode -- the open-loop
+        prior, the observation and the closed-loop posterior, vision over audio -- as one finished uint8 video.  Both encoders run once,
+        then ONE masked posterior rollout over ``2 N`` rows: rows ``[0, N)`` observe ``panel.observe`` on every live frame (the
+        posterior), rows ``[N, 2 N)`` observe it on ``t < panel.query_length`` and nothing after (the prior).  Both halves start from the
+        same initial state and read the same ``noise["u_post"]`` (MMTRSSM: the ``_l`` / ``_h`` pairs), so on the context the prior is
+        the posterior bit for bit: the callback's ``cat_states([posterior[:, :q], prior])``.  Both halves are decoded in chunks of whole
+        rows through the decoders' activated path and one ``mtrssm_episode_panel`` launch writes the video.  ``rows`` (an index tensor or
+        list) picks the episodes before anything runs, ``noise`` and ``lengths`` with them; ``frame0`` is the number drawn on frame 0.
+        ``lengths`` (or a batch that carries ``valid_global``): nothing is observed at or past a row's end and those frames are black.
+        ``keep_states``: the video carries the rollout's posterior states ``[2 N, T, .]`` and the decoded frames.  No masked (7-tuple)
+        batch, no ``state_carry``; a weighted model runs its gate once per row and repeats it for the row's second copy."""
+        if not isinstance(panel, EpisodePanel):
+            msg = f"panel must be an EpisodePanel, got {type(panel).__name__}"
+            raise ValueError(msg)
+        if self.get_modality_mask_from_batch(batch) is not None:
+            msg = "a skill step decides what the model observes: a masked (7-tuple) batch already says what is seen"
+            raise ValueError(msg)
+        if self.state_carry is not None:
+            msg = "a skill step starts every row from its own frame 0: it does not combine with a set state_carry"
+            raise ValueError(msg)
+        dev = batch[0].device
+        valid = None
+        ragged = self._lengths_of(batch, lengths, None, None)
+        if ragged is not None:
+            valid_global, world, rank = ragged
+            rows_all = batch[0].shape[0]
+            _check_lengths(valid_global, rows_all * world, dev)
+            valid = valid_global[rank * rows_all : (rank + 1) * rows_all].contiguous()
+        noise = dict(noise or {})
+        if rows is not None:
+            pick = torch.as_tensor(rows, dtype=torch.int64, device=dev).reshape(-1)
+            if pick.numel() == 0:
+                msg = "rows picks no episode"
+                raise ValueError(msg)
+            batch = tuple(b.index_select(0, pick) for b in batch[:6])
+            valid = None if valid is None else valid.index_select(0, pick).contiguous()
+            noise = {k: (None if u is None else u.index_select(0, pick)) for k, u in noise.items()}
+            if expert_log_weights is not None:
+                expert_log_weights = expert_log_weights.index_select(0, pick)
+        actions = batch[0]
+        audio_obs, vision_obs = self.get_observations_from_batch(batch)
+        targets = self.get_targets_from_batch(batch)
+        N, T = actions.shape[:2]
+        conv.begin_step(dev)
+        audio_embed, vision_embed = self._encode_both(audio_obs, vision_obs)
+        zeros = torch.zeros(N, device=dev)  # (fixed contexts: the uniforms do not matter)
+        closed, opened = Forecast(T).sample(zeros, T, valid), Forecast(panel.query_length).sample(zeros, T, valid)
+        seen = (closed.codes & panel.bits).contiguous()
+        codes = torch.cat([seen, opened.codes & panel.bits], dim=0).contiguous()
+        twice = lambda x: torch.cat([x, x], dim=0)  # noqa: E731  (row n closed loop, row N + n open loop)
+        embed0 = _masked_mean_embed(audio_embed[:, 0], vision_embed[:, 0], closed.mask0 & panel.observed(dev))
+        state0 = self._initial_for_step(embed0, noise)
+        state0 = self._state_like(state0, {k: twice(getattr(state0, k)) for k in self._FRESH_KEYS})
+        for key in self._POST_KEYS:
+            k = self._category_size_of(key)
+            u = noise.get(key)
+            u = _rand(actions, N, T, k) if u is None else u
+            if tuple(u.shape) != (N, T, k):
+                msg = f"noise[{key!r}] must have shape {(N, T, k)}, got {tuple(u.shape)}"
+                raise ValueError(msg)
+            noise[key] = twice(u).contiguous()
+        logw = self._expert_logw(audio_embed, vision_embed, expert_log_weights, N, T)  # the gate once per row ...
+        logw = None if logw is None else twice(logw)  # ... repeated for its second copy
+        out = self._rollout_embedded(twice(actions), twice(audio_embed), twice(vision_embed), state0, noise, sample_prior=False, modality=codes,
+                                     expert_log_weights=logw)
+        feature = self._feature_of(out)  # [2 N, T, F]
+        da, dv = self.audio_decoder, self.vision_decoder
+        decoded: dict[str, Tensor] = {}
+        per = max(1, int(panel.max_frames) // (2 * T))
+        for r0 in range(0, N, per):
+            r1 = min(N, r0 + per)
+            both = torch.cat([feature[r0:r1], feature[N + r0 : N + r1]], dim=0)
+            ya, yv = cnn.decode_pair(da, dv, both, both) if _pairable(da, dv, cnn.Decoder) else (da(both), dv(both))
+            for name, y in (("audio", ya), ("vision", yv)):
+                y = y.to(torch.float32)  # noqa: PLW2901
+                if per >= N:
+                    decoded[f"posterior/{name}"], decoded[f"prior/{name}"] = y[: r1 - r0], y[r1 - r0 :]
+                    continue
+                if r0 == 0:
+                    decoded[f"posterior/{name}"] = torch.empty(N, *y.shape[1:], device=dev, dtype=torch.float32)
+                    decoded[f"prior/{name}"] = torch.empty(N, *y.shape[1:], device=dev, dtype=torch.float32)
+                decoded[f"posterior/{name}"][r0:r1], decoded[f"prior/{name}"][r0:r1] = y[: r1 - r0], y[r1 - r0 :]
+        decoded["observation/audio"] = targets["recon/audio"].to(torch.float32).contiguous()
+        decoded["observation/vision"] = targets["recon/vision"].to(torch.float32).contiguous()
+        context = torch.full((N,), min(panel.query_length, (1 << 31) - 1), dtype=torch.int32, device=dev)
+        frames = panel.render(decoded["observation/audio"], decoded["posterior/audio"], decoded["prior/audio"], decoded["observation/vision"],
+                              decoded["posterior/vision"], decoded["prior/vision"], codes=seen, valid=valid, context=context, frame0=frame0)
+        video = EpisodeVideo(frames, context, valid)
+        if keep_states:
+            video.states, video.decoded = self._posterior_from_rollout(out), decoded
+        return video
 
     def _latent_levels(self) -> tuple[tuple[str, MultiOneHotFactory], ...]:
         """The latent levels of a posterior rollout: the suffix of their scan outputs and the factory that knows their K and C."""

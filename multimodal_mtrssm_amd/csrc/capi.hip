@@ -93,6 +93,9 @@ int iw_bound_launch(const float*, const float*, const float*, const int32_t*, in
 int64_t linear_probe_workspace_bytes(int64_t, int64_t, int64_t, int64_t);
 int linear_probe_step_launch(const float*, int64_t, int64_t, const int32_t*, const float*, const float*, int64_t, int64_t, int64_t, int64_t, int, float*,
                              float*, float*, float*, float*, int32_t*, void*, int64_t, hipStream_t);
+int64_t episode_panel_bytes(const MtrssmPanelGeom*, int32_t*, int32_t*);
+int episode_panel_launch(const MtrssmPanelGeom*, const float*, const float*, const float*, const float*, const float*, const float*, const int32_t*,
+                         const int32_t*, const int32_t*, unsigned char*, hipStream_t);
 int digit_features_launch(const float*, int64_t, const int32_t*, int64_t, int, const float*, const float*, const float*, const float*, float*,
                           hipStream_t);
 int digit_head_launch(const float*, const float*, const float*, int64_t, const int32_t*, int64_t, int32_t*, float*, hipStream_t);
@@ -524,6 +527,12 @@ MTRSSM_API int mtrssm_linear_probe_step(const float* x, int64_t ld, int64_t col0
                                         float* nll, float* hit, int32_t* pred, void* workspace, int64_t workspace_bytes, void* stream) {
   return linear_probe_step_launch(x, ld, col0, labels, weight, bias, G, N, C, F, normalize, g_weight, g_bias, stats, nll, hit, pred, workspace,
                                   workspace_bytes, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int64_t mtrssm_episode_panel_bytes(const MtrssmPanelGeom* geom, int32_t* Hc, int32_t* Wc) { return episode_panel_bytes(geom, Hc, Wc); }
+MTRSSM_API int mtrssm_episode_panel(const MtrssmPanelGeom* geom, const float* obs_a, const float* post_a, const float* prior_a, const float* obs_v,
+                                    const float* post_v, const float* prior_v, const int32_t* codes, const int32_t* valid, const int32_t* context,
+                                    uint8_t* out, void* stream) {
+  return episode_panel_launch(geom, obs_a, post_a, prior_a, obs_v, post_v, prior_v, codes, valid, context, out, static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int mtrssm_digit_features(const float* pred, int64_t frames, const int32_t* select, int64_t N, int32_t act, const float* conv1_w,
                                      const float* conv1_b, const float* conv2_w, const float* conv2_b, float* features, void* stream) {
