@@ -20,21 +20,18 @@ import torch
 from torch import Tensor, nn
 
 from multimodal_mtrssm_amd import cnn, conv, scan
+from multimodal_mtrssm_amd._shared import _check_lengths, _masked_mean_embed, _pairable, _rand
 from multimodal_mtrssm_amd.carry import StateCarry
 from multimodal_mtrssm_amd.distributions import MultiOneHot, MultiOneHotFactory, draw_uniforms, kl_divergence, onehot_from_uniforms
-from multimodal_mtrssm_amd.digits import DigitClassifier, word_counts
 from multimodal_mtrssm_amd.dropout import ModalityDropout, StepMask, ragged_step_mask
+from multimodal_mtrssm_amd.evaluation import _Evaluators
 from multimodal_mtrssm_amd.experts import ExpertWeights
 from multimodal_mtrssm_amd.forecast import Forecast
-from multimodal_mtrssm_amd.likelihood import PLANES as LIKELIHOOD_PLANES
 from multimodal_mtrssm_amd.likelihood import LikelihoodBound, LikelihoodTable
 from multimodal_mtrssm_amd.networks import MTRNN, Representation, Transition
 from multimodal_mtrssm_amd.objective import likelihood
-from multimodal_mtrssm_amd.panel import EpisodePanel, EpisodeVideo
-from multimodal_mtrssm_amd.probe import LatentProbe, LinearProbe, ProbeTable, frame_labels
 from multimodal_mtrssm_amd.schedule import ElboSchedule, ElboTerms
 from multimodal_mtrssm_amd.skill import ForecastSkill, SkillTable
-from multimodal_mtrssm_amd.words import TransitionTable, WordTransitions
 from multimodal_mtrssm_amd.state import MTState, State
 
 try:  # the real trainer, when it is installed next to the reference
@@ -53,13 +50,6 @@ except ImportError:  # this image: a LightningModule-shaped nn.Module
 
 
 Noise = dict[str, Tensor | None]
-
-def _pairable(a: nn.Module, b: nn.Module, kind: type) -> bool:
-    """Paired launches (``conv.paired``): the audio and the vision stack's equal layers share one grid (this package's own
-    stacks only).  Everything runs on ONE stream: a two-stream variant of the step was removed in round 2 (it bought nothing
-    once the layers were paired and stalled the GPU in about one run in fifteen, profiles/round1_notes.md)."""
-    return conv.PAIR_LAUNCH and isinstance(a, kind) and isinstance(b, kind)
-
 
 def _st_onehot(dist: MultiOneHot, u: Tensor | None) -> Tensor:
     """Straight-through one-hot sample of ``dist`` from uniforms ``u`` (drawn on device when None)."""
@@ -405,10 +395,6 @@ def _sampled_head(factory, logits: Tensor, u: Tensor | None) -> tuple[MultiOneHo
     return MultiOneHot(logp, probs), stoch
 
 
-def _rand(like: Tensor, *shape: int) -> Tensor:
-    return torch.rand(shape, device=like.device, dtype=torch.float32)
-
-
 def _check_modality_mask(mask: Tensor, B: int, T: int | None, device: torch.device, *, first_step: bool) -> None:  # noqa: N803
     """Host-side checks of a modality mask (DESIGN.md "Missing modalities"): bool ``[B, T, 2]`` (``[B, 2]`` when ``T`` is
     None) on ``device``; ``first_step``: every row observes something at t = 0 (the initial state averages those embeddings)."""
@@ -453,16 +439,6 @@ def _resolve_modality_mask(observations: tuple, mask: Tensor | None, B: int, T: 
     return mask
 
 
-def _check_lengths(valid: Tensor, rows: int, device: torch.device) -> None:
-    """A ragged batch's live-step counts: int32 ``[rows]`` on ``device`` (not read back)."""
-    if not isinstance(valid, Tensor) or valid.dtype != torch.int32 or tuple(valid.shape) != (rows,):
-        msg = f"lengths must be an int32 tensor of shape ({rows},), got {getattr(valid, 'dtype', type(valid))} {tuple(getattr(valid, 'shape', ()))}"
-        raise ValueError(msg)
-    if valid.device != torch.device(device):
-        msg = f"lengths is on {valid.device}, the model's tensors on {device}"
-        raise ValueError(msg)
-
-
 def check_ragged_rows(valid_host: Tensor, reset_host: Tensor | None) -> None:
     """The host rule of a ragged step: a row that resets needs a frame at t = 0 -- ``reset_host[b]`` implies
     ``valid_host[b] >= 1`` (``reset_host`` None: every row resets).  Raises before anything is launched."""
@@ -478,18 +454,7 @@ def check_ragged_rows(valid_host: Tensor, reset_host: Tensor | None) -> None:
         raise ValueError(msg)
 
 
-def _masked_mean_embed(ea: Tensor | None, ev: Tensor | None, mask0: Tensor | None) -> Tensor:
-    """t = 0 embedding: the mean over the present modalities of each row; both present is exactly ``(ea + ev) / 2``."""
-    if ea is None or ev is None:
-        return ea if ev is None else ev
-    both = (ea + ev) / 2.0
-    if mask0 is None:
-        return both
-    a, v = mask0[:, 0:1], mask0[:, 1:2]
-    return torch.where(a & v, both, torch.where(a, ea, ev))
-
-
-class MoPoE_MRSSM(_Base):  # noqa: N801
+class MoPoE_MRSSM(_Evaluators, _Base):  # noqa: N801
     """Multimodal RSSM with MoPoE posteriors: PoE of {audio, vision}, then MoE over {A, V, A+V}."""
 
     def __init__(  # noqa: PLR0913
@@ -819,474 +784,7 @@ class MoPoE_MRSSM(_Base):  # noqa: N801
         """What the decoders read of a posterior rollout."""
         return torch.cat([out["deter"], out["post_stoch"]], dim=-1)
 
-    _POST_KEYS = ("u_post",)  # the rollout's posterior uniforms; a skill step composes each with its "u_tail" twin
-
-    def _per_copy_noise(self, noise: Noise, keys: tuple[str, ...], B: int, S: int, *mid: int) -> None:  # noqa: N803
-        """In place: a likelihood step's uniforms ``(B, S, *mid, K)`` become the scan's rows ``b * S + s`` as they lie (absent: left to
-        the consumer's own draw)."""
-        for key in keys:
-            u = noise.get(key)
-            if u is None:
-                continue
-            want = (B, S, *mid, self._category_size_of(key))
-            if tuple(u.shape) != want:
-                msg = f"noise[{key!r}] must have shape {want}, got {tuple(u.shape)}"
-                raise ValueError(msg)
-            noise[key] = u.reshape(B * S, *want[2:]).contiguous()
-
-    def _skill_rollout(self, batch: tuple[Tensor, ...], skill: ForecastSkill | LikelihoodBound | LatentProbe, noise: Noise | None,  # noqa: PLR0913
-                       lengths: Tensor | None,
-                       expert_log_weights: Tensor | None, *, per_copy: bool = False,
-                       copy_bits: bool = False) -> tuple[dict[str, Tensor], Tensor | None]:
-        """The rollout of a skill step (``forecast_skill``, ``word_transitions``): both encoders, the initial state of every row, the
-        composed noise and ONE masked posterior rollout over ``B * S`` rows.  Returns the scan's outputs and the rows' lengths (or None).
-        ``per_copy`` (``likelihood_bound``): every live frame is observed, and each copy of a row draws its own initial state and its own
-        posterior (``u_init`` ``(B, S, K)``, ``u_post`` ``(B, S, T, K)``) instead of sharing the row's.  ``copy_bits``
-        (``probe_features``): every live frame is observed, copy ``s`` of a row sees the modalities ``skill.copy_bits()[s]`` (at frame 0
-        too) and the copies share the row's uniforms (``u_init`` ``(B, K)``, ``u_post`` ``(B, T, K)``)."""
-        actions = batch[0]
-        audio_obs, vision_obs = self.get_observations_from_batch(batch)
-        B, T = actions.shape[:2]
-        S, dev = skill.samples, actions.device
-        valid = None
-        ragged = self._lengths_of(batch, lengths, None, None)
-        if ragged is not None:
-            valid_global, world, rank = ragged
-            _check_lengths(valid_global, B * world, dev)
-            valid = valid_global[rank * B : (rank + 1) * B].contiguous()
-        noise = dict(noise or {})
-        conv.begin_step(dev)
-        audio_embed, vision_embed = self._encode_both(audio_obs, vision_obs)
-        context = T if per_copy or copy_bits else skill.context
-        sm = Forecast(context).sample(torch.zeros(B, device=dev), T, valid)  # (a fixed context: the uniforms do not matter)
-        wide = lambda x: x.repeat_interleave(S, dim=0)  # noqa: E731  (row (b, s) -> b * S + s)
-        if copy_bits:
-            codes = (sm.codes[:, None, :] & skill.copy_bits(dev)[None, :, None]).reshape(B * S, T)
-            mask0 = (sm.mask0[:, None, :] & skill.copy_observed(dev)[None]).reshape(B * S, 2)
-            embed0 = _masked_mean_embed(wide(audio_embed[:, 0]), wide(vision_embed[:, 0]), mask0)
-            for key, mid in (*((k, ()) for k in self._INIT_KEYS), *((k, (T,)) for k in self._POST_KEYS)):
-                want = (B, *mid, self._category_size_of(key))
-                u = noise.get(key)
-                u = _rand(actions, *want) if u is None else u  # (drawn per ROW: the copies of a row share their uniforms)
-                if tuple(u.shape) != want:
-                    msg = f"noise[{key!r}] must have shape {want}, got {tuple(u.shape)}"
-                    raise ValueError(msg)
-                noise[key] = wide(u).contiguous()
-            state0 = self._initial_for_step(embed0, noise)
-            logw = self._expert_logw(audio_embed, vision_embed, expert_log_weights, B, T)  # the gate once per row ...
-            logw = None if logw is None else wide(logw)  # ... repeated for its S copies
-            out = self._rollout_embedded(wide(actions), wide(audio_embed), wide(vision_embed), state0, noise, sample_prior=False, modality=codes,
-                                         expert_log_weights=logw)
-            return out, valid
-        bits = skill.bits
-        codes = sm.codes & bits
-        mask0 = sm.mask0 & skill.observed(dev)
-        embed0 = _masked_mean_embed(audio_embed[:, 0], vision_embed[:, 0], mask0)
-        if per_copy:
-            self._per_copy_noise(noise, self._INIT_KEYS, B, S)
-            self._per_copy_noise(noise, self._POST_KEYS, B, S, T)
-            state0 = self._initial_for_step(wide(embed0), noise)
-        else:
-            state0 = self._initial_for_step(embed0, noise)
-            state0 = self._state_like(state0, {k: wide(getattr(state0, k)) for k in self._FRESH_KEYS})
-            for key in self._POST_KEYS:
-                tail_key = key.replace("post", "tail")
-                u_post, u_tail = noise.get(key), noise.get(tail_key)
-                k = self._category_size_of(key)
-                u_post = _rand(actions, B, T, k) if u_post is None else u_post
-                u_tail = _rand(actions, B, S, T, k) if u_tail is None else u_tail
-                noise[key] = skill.compose_noise(u_post, u_tail)
-        if expert_log_weights is not None and expert_log_weights.shape[0] == B * S:
-            logw = expert_log_weights  # (checked by the rollout)
-        else:
-            logw = self._expert_logw(audio_embed, vision_embed, expert_log_weights, B, T)  # the gate once per row ...
-            logw = None if logw is None else wide(logw)  # ... repeated for its S copies
-        out = self._rollout_embedded(wide(actions), wide(audio_embed), wide(vision_embed), state0, noise, sample_prior=False, modality=wide(codes),
-                                     expert_log_weights=logw)
-        return out, valid
-
-    @torch.no_grad()
-    def forecast_skill(self, batch: tuple[Tensor, ...], skill: ForecastSkill, noise: Noise | None = None, lengths: Tensor | None = None,  # noqa: PLR0913, PLR0914
-                       table: SkillTable | None = None, *, keep_states: bool = False, expert_log_weights: Tensor | None = None) -> SkillTable:
-        """One skill step: observe ``skill.context`` frames (of ``skill.observe``), roll ``skill.samples`` sampled
-        futures per row open loop in ONE masked posterior rollout over ``B * S`` rows (row ``b * S + s``; the copies of a row share
-        ``noise["u_post"]`` on the context and read ``noise["u_tail"][b, s]`` after it), decode, and score every live frame of both
-        modalities as an ensemble (``mtrssm_ensemble_score``); the planes are folded by horizon into ``table`` (a new one when None),
-        which is returned.  ``best`` is the best sample per FRAME.  ``lengths`` (or a batch that carries ``valid_global``) as in
-        ``forecast_rollout``: nothing is observed or scored at or past a row's end.  ``keep_states``: ``table.states`` is the posterior
-        state sequence ``[B * S, T, .]`` and ``table.planes`` the step's score planes ``[8, B, T]``.  Every row starts from its own
-        frame 0: no masked (7-tuple) batch, no ``state_carry``.  A weighted model runs its gate once per row and
-        repeats the weights for the row's copies; ``expert_log_weights`` (fp32 ``[B, T, 3]``, or ``[B * S, T, 3]`` already repeated)
-        gives them explicitly."""
-        if not isinstance(skill, ForecastSkill):
-            msg = f"skill must be a ForecastSkill, got {type(skill).__name__}"
-            raise ValueError(msg)
-        if self.get_modality_mask_from_batch(batch) is not None:
-            msg = "a skill step decides what the model observes: a masked (7-tuple) batch already says what is seen"
-            raise ValueError(msg)
-        if self.state_carry is not None:
-            msg = "a skill step starts every row from its own frame 0: it does not combine with a set state_carry"
-            raise ValueError(msg)
-        actions = batch[0]
-        targets = self.get_targets_from_batch(batch)
-        B, T = actions.shape[:2]
-        S, dev = skill.samples, actions.device
-        if table is not None and (not isinstance(table, SkillTable) or table.steps != T or table.buffer.device != dev):
-            msg = f"table must be a SkillTable of {T} steps on {dev}"
-            raise ValueError(msg)
-        out, valid = self._skill_rollout(batch, skill, noise, lengths, expert_log_weights)
-        feature = self._feature_of(out)
-        planes = torch.empty(SkillTable.ROWS, B, T, device=dev, dtype=torch.float32)
-        rows = max(1, int(skill.max_frames) // (S * T))
-        for r0 in range(0, B, rows):
-            r1 = min(B, r0 + rows)
-            preds, acts = self._decode_for_score(feature[r0 * S : r1 * S])
-            part = torch.empty(SkillTable.ROWS, r1 - r0, T, device=dev, dtype=torch.float32)
-            for j, (pred, key) in enumerate(zip(preds, ("recon/audio", "recon/vision"), strict=True)):
-                ForecastSkill.score(pred.reshape(r1 - r0, S, T, -1), targets[key][r0:r1].reshape(r1 - r0, T, -1),
-                                    None if valid is None else valid[r0:r1], acts[j], out=part[4 * j : 4 * j + 4])
-            planes[:, r0:r1] = part
-        if table is None:
-            table = SkillTable(T, dev)
-        context = torch.full((B,), min(skill.context, (1 << 31) - 1), dtype=torch.int32, device=dev)
-        ForecastSkill.table_add(planes, context, valid, table.sums, table.counts)
-        table.planes = planes if keep_states else None
-        table.states = self._posterior_from_rollout(out) if keep_states else None
-        return table
-
-    def _decode_for_score(self, feature: Tensor, *, audio: bool = True, vision: bool = True) -> tuple[tuple[Tensor | None, Tensor | None], tuple[int, int]]:
-        """``(audio, vision)`` predictions of ``feature`` for the ensemble scorer and the output activations it applies while reading
-        them: this package's decoders hand over their RAW output (paired when they pair).  A modality that is not asked for is None."""
-        da, dv = self.audio_decoder, self.vision_decoder
-        fused = isinstance(da, cnn.Decoder) and isinstance(dv, cnn.Decoder) and da.out_act_id is not None and dv.out_act_id is not None
-        acts = (da.out_act_id, dv.out_act_id) if fused else (0, 0)
-        if audio and vision and fused and _pairable(da, dv, cnn.Decoder):
-            return cnn.decode_pair(da, dv, feature, feature, raw=True), acts
-        kw = {"raw": True} if fused else {}
-        return (da(feature, **kw) if audio else None, dv(feature, **kw) if vision else None), acts
-
-    @torch.no_grad()
-    def render_episodes(self, batch: tuple[Tensor, ...], panel: EpisodePanel, noise: Noise | None = None, lengths: Tensor | None = None, *,  # noqa: PLR0913, PLR0914
-                        rows: Tensor | list[int] | None = None, frame0: int = 0, keep_states: bool = False,
-                        expert_log_weights: Tensor | None = None) -> EpisodeVideo:
-        """The episode panels of a batch: what the reference's logging callback shows per episode -- the open-loop
-        prior, the observation and the closed-loop posterior, vision over audio -- as one finished uint8 video.  Both encoders run once,
-        then ONE masked posterior rollout over ``2 N`` rows: rows ``[0, N)`` observe ``panel.observe`` on every live frame (the
-        posterior), rows ``[N, 2 N)`` observe it on ``t < panel.query_length`` and nothing after (the prior).  Both halves start from the
-        same initial state and read the same ``noise["u_post"]`` (MMTRSSM: the ``_l`` / ``_h`` pairs), so on the context the prior is
-        the posterior bit for bit: the callback's ``cat_states([posterior[:, :q], prior])``.  Both halves are decoded in chunks of whole
-        rows through the decoders' activated path and one ``mtrssm_episode_panel`` launch writes the video.  ``rows`` (an index tensor or
-        list) picks the episodes before anything runs, ``noise`` and ``lengths`` with them; ``frame0`` is the number drawn on frame 0.
-        ``lengths`` (or a batch that carries ``valid_global``): nothing is observed at or past a row's end and those frames are black.
-        ``keep_states``: the video carries the rollout's posterior states ``[2 N, T, .]`` and the decoded frames.  No masked (7-tuple)
-        batch, no ``state_carry``; a weighted model runs its gate once per row and repeats it for the row's second copy."""
-        if not isinstance(panel, EpisodePanel):
-            msg = f"panel must be an EpisodePanel, got {type(panel).__name__}"
-            raise ValueError(msg)
-        if self.get_modality_mask_from_batch(batch) is not None:
-            msg = "a skill step decides what the model observes: a masked (7-tuple) batch already says what is seen"
-            raise ValueError(msg)
-        if self.state_carry is not None:
-            msg = "a skill step starts every row from its own frame 0: it does not combine with a set state_carry"
-            raise ValueError(msg)
-        dev = batch[0].device
-        valid = None
-        ragged = self._lengths_of(batch, lengths, None, None)
-        if ragged is not None:
-            valid_global, world, rank = ragged
-            rows_all = batch[0].shape[0]
-            _check_lengths(valid_global, rows_all * world, dev)
-            valid = valid_global[rank * rows_all : (rank + 1) * rows_all].contiguous()
-        noise = dict(noise or {})
-        if rows is not None:
-            pick = torch.as_tensor(rows, dtype=torch.int64, device=dev).reshape(-1)
-            if pick.numel() == 0:
-                msg = "rows picks no episode"
-                raise ValueError(msg)
-            batch = tuple(b.index_select(0, pick) for b in batch[:6])
-            valid = None if valid is None else valid.index_select(0, pick).contiguous()
-            noise = {k: (None if u is None else u.index_select(0, pick)) for k, u in noise.items()}
-            if expert_log_weights is not None:
-                expert_log_weights = expert_log_weights.index_select(0, pick)
-        actions = batch[0]
-        audio_obs, vision_obs = self.get_observations_from_batch(batch)
-        targets = self.get_targets_from_batch(batch)
-        N, T = actions.shape[:2]
-        conv.begin_step(dev)
-        audio_embed, vision_embed = self._encode_both(audio_obs, vision_obs)
-        zeros = torch.zeros(N, device=dev)  # (fixed contexts: the uniforms do not matter)
-        closed, opened = Forecast(T).sample(zeros, T, valid), Forecast(panel.query_length).sample(zeros, T, valid)
-        seen = (closed.codes & panel.bits).contiguous()
-        codes = torch.cat([seen, opened.codes & panel.bits], dim=0).contiguous()
-        twice = lambda x: torch.cat([x, x], dim=0)  # noqa: E731  (row n closed loop, row N + n open loop)
-        embed0 = _masked_mean_embed(audio_embed[:, 0], vision_embed[:, 0], closed.mask0 & panel.observed(dev))
-        state0 = self._initial_for_step(embed0, noise)
-        state0 = self._state_like(state0, {k: twice(getattr(state0, k)) for k in self._FRESH_KEYS})
-        for key in self._POST_KEYS:
-            k = self._category_size_of(key)
-            u = noise.get(key)
-            u = _rand(actions, N, T, k) if u is None else u
-            if tuple(u.shape) != (N, T, k):
-                msg = f"noise[{key!r}] must have shape {(N, T, k)}, got {tuple(u.shape)}"
-                raise ValueError(msg)
-            noise[key] = twice(u).contiguous()
-        logw = self._expert_logw(audio_embed, vision_embed, expert_log_weights, N, T)  # the gate once per row ...
-        logw = None if logw is None else twice(logw)  # ... repeated for its second copy
-        out = self._rollout_embedded(twice(actions), twice(audio_embed), twice(vision_embed), state0, noise, sample_prior=False, modality=codes,
-                                     expert_log_weights=logw)
-        feature = self._feature_of(out)  # [2 N, T, F]
-        da, dv = self.audio_decoder, self.vision_decoder
-        decoded: dict[str, Tensor] = {}
-        per = max(1, int(panel.max_frames) // (2 * T))
-        for r0 in range(0, N, per):
-            r1 = min(N, r0 + per)
-            both = torch.cat([feature[r0:r1], feature[N + r0 : N + r1]], dim=0)
-            ya, yv = cnn.decode_pair(da, dv, both, both) if _pairable(da, dv, cnn.Decoder) else (da(both), dv(both))
-            for name, y in (("audio", ya), ("vision", yv)):
-                y = y.to(torch.float32)  # noqa: PLW2901
-                if per >= N:
-                    decoded[f"posterior/{name}"], decoded[f"prior/{name}"] = y[: r1 - r0], y[r1 - r0 :]
-                    continue
-                if r0 == 0:
-                    decoded[f"posterior/{name}"] = torch.empty(N, *y.shape[1:], device=dev, dtype=torch.float32)
-                    decoded[f"prior/{name}"] = torch.empty(N, *y.shape[1:], device=dev, dtype=torch.float32)
-                decoded[f"posterior/{name}"][r0:r1], decoded[f"prior/{name}"][r0:r1] = y[: r1 - r0], y[r1 - r0 :]
-        decoded["observation/audio"] = targets["recon/audio"].to(torch.float32).contiguous()
-        decoded["observation/vision"] = targets["recon/vision"].to(torch.float32).contiguous()
-        context = torch.full((N,), min(panel.query_length, (1 << 31) - 1), dtype=torch.int32, device=dev)
-        frames = panel.render(decoded["observation/audio"], decoded["posterior/audio"], decoded["prior/audio"], decoded["observation/vision"],
-                              decoded["posterior/vision"], decoded["prior/vision"], codes=seen, valid=valid, context=context, frame0=frame0)
-        video = EpisodeVideo(frames, context, valid)
-        if keep_states:
-            video.states, video.decoded = self._posterior_from_rollout(out), decoded
-        return video
-
-    def _latent_levels(self) -> tuple[tuple[str, MultiOneHotFactory], ...]:
-        """The latent levels of a posterior rollout: the suffix of their scan outputs and the factory that knows their K and C."""
-        return (("", self.transition.distribution_factory),)
-
-    @torch.no_grad()
-    def likelihood_bound(self, batch: tuple[Tensor, ...], bound: LikelihoodBound, noise: Noise | None = None, lengths: Tensor | None = None,  # noqa: PLR0913, PLR0914
-                         table: LikelihoodTable | None = None, *, keep_states: bool = False,
-                         expert_log_weights: Tensor | None = None) -> LikelihoodTable:
-        """One likelihood step (``likelihood.py`` states the quantity): ``bound.samples`` posterior trajectories
-        per row in ONE masked posterior rollout over ``B * S`` rows (row ``b * S + s``; the posterior sees ``bound.observe`` on every live
-        step and nothing after a row's end; every copy starts from its row's frame 0 with its own ``noise["u_init"][b, s]`` and reads
-        ``noise["u_post"][b, s]``), the latent log-ratio of the sampled classes (``mtrssm_latent_log_ratio``, one launch per level), the
-        decoders over chunks of whole rows, the per-sample errors (``mtrssm_ensemble_score``) and the bound (``mtrssm_iw_bound``); the
-        planes are folded by frame position into ``table`` (a new one when None), which is returned.  ``lengths`` (or a batch that
-        carries ``valid_global``): nothing is observed or scored at or past a row's end.  ``keep_states``: ``table.states`` is the
-        posterior state sequence ``[B * S, T, .]`` and ``table.planes`` the step's planes ``[8, B, T]``.  No masked (7-tuple) batch, no
-        ``state_carry``.  A weighted model runs its gate as in ``forecast_skill``."""
-        if not isinstance(bound, LikelihoodBound):
-            msg = f"bound must be a LikelihoodBound, got {type(bound).__name__}"
-            raise ValueError(msg)
-        if self.get_modality_mask_from_batch(batch) is not None:
-            msg = "a likelihood step decides what the model observes: a masked (7-tuple) batch already says what is seen"
-            raise ValueError(msg)
-        if self.state_carry is not None:
-            msg = "a likelihood step starts every row from its own frame 0: it does not combine with a set state_carry"
-            raise ValueError(msg)
-        actions = batch[0]
-        targets = self.get_targets_from_batch(batch)
-        B, T = actions.shape[:2]
-        S, dev = bound.samples, actions.device
-        if table is not None and (not isinstance(table, LikelihoodTable) or table.steps != T or table.buffer.device != dev):
-            msg = f"table must be a LikelihoodTable of {T} steps on {dev}"
-            raise ValueError(msg)
-        out, valid = self._skill_rollout(batch, bound, noise, lengths, expert_log_weights, per_copy=True)
-        ratio = None
-        if bound.latent:
-            for suffix, factory in self._latent_levels():
-                ratio = LikelihoodBound.log_ratio(out[f"post_logits{suffix}"], out[f"prior_logits{suffix}"], out[f"post_stoch{suffix}"],
-                                                  factory.category_size, factory.class_size, out=ratio, accumulate=ratio is not None)
-            ratio = ratio.reshape(B, S, T)
-        if table is None:
-            table = LikelihoodTable(T, dev)
-        audio, vision = "audio" in bound.score, "vision" in bound.score
-        feature = self._feature_of(out) if bound.score else None
-        planes = torch.empty(len(LIKELIHOOD_PLANES), B, T, device=dev, dtype=torch.float32)
-        rows = max(1, int(bound.max_frames) // (S * T)) if bound.score else B
-        for r0 in range(0, B, rows):
-            r1 = min(B, r0 + rows)
-            n = r1 - r0
-            chunk_valid = None if valid is None else valid[r0:r1]
-            se, events = [None, None], [0, 0]
-            if bound.score:
-                preds, acts = self._decode_for_score(feature[r0 * S : r1 * S], audio=audio, vision=vision)
-                for j, (pred, key) in enumerate(zip(preds, ("recon/audio", "recon/vision"), strict=True)):
-                    if pred is None:
-                        continue
-                    pred = pred.reshape(n, S, T, -1)  # noqa: PLW2901
-                    events[j] = pred.shape[-1]
-                    se[j] = ForecastSkill.score(pred, targets[key][r0:r1].reshape(n, T, -1), chunk_valid, acts[j], se_samples=True).se_samples
-            part = planes if n == B else torch.empty(len(LIKELIHOOD_PLANES), n, T, device=dev, dtype=torch.float32)
-            LikelihoodBound.bound(se[0], se[1], None if ratio is None else ratio[r0:r1], chunk_valid, events[0], events[1], out=part)
-            table.fold(part, chunk_valid)
-            if n != B:
-                planes[:, r0:r1] = part
-        table.planes = planes if keep_states else None
-        table.states = self._posterior_from_rollout(out) if keep_states else None
-        return table
-
-    def _check_probe_step(self, batch: tuple[Tensor, ...], probe: LatentProbe) -> None:
-        if not isinstance(probe, LatentProbe):
-            msg = f"probe must be a LatentProbe, got {type(probe).__name__}"
-            raise ValueError(msg)
-        if self.get_modality_mask_from_batch(batch) is not None:
-            msg = "a skill step decides what the model observes: a masked (7-tuple) batch already says what is seen"
-            raise ValueError(msg)
-        if self.state_carry is not None:
-            msg = "a skill step starts every row from its own frame 0: it does not combine with a set state_carry"
-            raise ValueError(msg)
-
-    @torch.no_grad()
-    def probe_features(self, batch: tuple[Tensor, ...], probe: LatentProbe, noise: Noise | None = None, lengths: Tensor | None = None, *,
-                       expert_log_weights: Tensor | None = None) -> tuple[Tensor, Tensor | None]:
-        """The features a linear probe reads: ``x [G, B, T, Ffull]`` and the rows' lengths ``valid`` (int32 ``[B]``, or
-        None).  Both encoders run once, then ONE masked posterior rollout over ``B * G`` rows (row ``b * G + g``): copy ``g`` of a row
-        observes ``probe.observe[g]`` on every live step and at frame 0, nothing at or past the row's end, and the copies share the
-        row's uniforms (``probe.noise_shapes``).  ``x[g]`` is the feature the decoders would read of that posterior; ``probe.columns(self)``
-        names the part to probe in place.  No masked (7-tuple) batch, no ``state_carry``; a weighted model runs its gate once per row."""
-        self._check_probe_step(batch, probe)
-        B, T = batch[0].shape[:2]
-        out, valid = self._skill_rollout(batch, probe, noise, lengths, expert_log_weights, copy_bits=True)
-        feature = self._feature_of(out)  # [B * G, T, Ffull]
-        return feature.reshape(B, probe.groups, T, -1).permute(1, 0, 2, 3).contiguous(), valid
-
-    @torch.no_grad()
-    def probe_evaluate(self, batch: tuple[Tensor, ...], labels: Tensor, probe: LatentProbe, linear: LinearProbe,  # noqa: PLR0913
-                       table: ProbeTable | None = None, noise: Noise | None = None, lengths: Tensor | None = None, *,
-                       expert_log_weights: Tensor | None = None) -> ProbeTable:
-        """One evaluation step of a fitted probe: ``probe_features``, ONE evaluation-only ``linear.step`` with planes on
-        ``probe.columns(self)`` and the fold of ``hit`` / ``nll`` by frame position into ``table`` (a new one when None), which is
-        returned; ``table.stats`` keeps the step's ``ProbeStats`` (planes ``[G, B * T]``).  ``labels``: int ``[B, T]`` on the device,
-        -1 = silence; a frame at or past its row's end is dead whatever its label."""
-        self._check_probe_step(batch, probe)
-        if not isinstance(linear, LinearProbe):
-            msg = f"linear must be a LinearProbe, got {type(linear).__name__}"
-            raise ValueError(msg)
-        actions = batch[0]
-        B, T = actions.shape[:2]
-        G, dev = probe.groups, actions.device
-        col0, width = probe.columns(self)
-        if linear.groups != G or linear.features != width:
-            msg = f"{probe!r} on {type(self).__name__} needs a LinearProbe of {G} groups and {width} features, got {linear.groups} and {linear.features}"
-            raise ValueError(msg)
-        if tuple(labels.shape) != (B, T) or labels.dtype not in (torch.int32, torch.int64) or labels.device != dev:
-            msg = f"labels must be an int32 / int64 tensor of shape {(B, T)} on {dev}, got {labels.dtype} {tuple(labels.shape)} on {labels.device}"
-            raise ValueError(msg)
-        if table is not None and (not isinstance(table, ProbeTable) or table.steps != T or table.groups != G or table.buffer.device != dev):
-            msg = f"table must be a ProbeTable of {G} groups and {T} steps on {dev}"
-            raise ValueError(msg)
-        x, valid = self.probe_features(batch, probe, noise, lengths, expert_log_weights=expert_log_weights)
-        flat = frame_labels(labels, valid)
-        stats = linear.step(x.reshape(G, B * T, -1), flat, col0=col0, grad=False, planes=True)
-        if table is None:
-            table = ProbeTable(G, T, dev, probe.observe)
-        live = ((flat >= 0) & (flat < linear.classes)).reshape(B, T)
-        table.fold(stats.hit.reshape(G, B, T), stats.nll.reshape(G, B, T), live)
-        table.stats = stats
-        return table
-
-    def _read_vision(self, feature: Tensor, classifier: DigitClassifier) -> Tensor:
-        """The digits (int32, ``feature``'s leading shape) the classifier reads off the vision frames decoded from ``feature``; the
-        decoder's raw output goes to the reader, which applies the output activation itself."""
-        dv = self.vision_decoder
-        fused = isinstance(dv, cnn.Decoder) and dv.out_act_id is not None
-        pred = dv(feature, raw=True) if fused else dv(feature)
-        if pred.numel() != feature[..., 0].numel() * 32 * 32:
-            msg = f"the digit classifier reads 1 x 32 x 32 vision frames, the decoder gives {tuple(pred.shape[feature.dim() - 1 :])}"
-            raise ValueError(msg)
-        return classifier.digits(pred, dv.out_act_id if fused else 0).reshape(feature.shape[:-1])
-
-    @torch.no_grad()
-    def word_transitions(self, batch: tuple[Tensor, ...], labels: Tensor, wt: WordTransitions, classifier: DigitClassifier,  # noqa: PLR0913, PLR0914
-                         noise: Noise | None = None, table: TransitionTable | None = None, *,
-                         expert_log_weights: Tensor | None = None) -> TransitionTable:
-        """One transition step (``words.py``): sample ``wt.samples`` futures per row, read the predicted vision
-        frame of each with ``classifier`` and add ``q_counts[word][digit] += 1`` into ``table`` (a new one when None), which is
-        returned.  ``labels``: int ``[B, T]`` on the device, -1 = silence; row b's current word is ``labels[b, wt.query - 1]`` and a
-        silent row is skipped.  ``protocol="context"``: ``forecast_skill``'s masked rollout (the same noise: ``u_post`` / ``u_tail``),
-        frame ``wt.query - 1 + wt.read_at`` is read; only that frame is decoded, or -- ``wt.by_horizon`` -- chunks of whole rows of at
-        most ``wt.max_frames`` frames, every frame read and the ``hit`` / ``any`` planes folded by horizon.  ``protocol="reference"``:
-        the initial state of frame 0, then a prior-only step with the interval's last action ``batch[0][:, wt.query - 1]``
-        (``noise["u_prior"]``: ``[B, S, 1, K]``), whose frame is read.  No masked (7-tuple) batch, no ``state_carry``.  A weighted model
-        runs its gate as in ``forecast_skill``."""
-        if not isinstance(wt, WordTransitions):
-            msg = f"wt must be a WordTransitions, got {type(wt).__name__}"
-            raise ValueError(msg)
-        if not isinstance(classifier, DigitClassifier):
-            msg = f"classifier must be a DigitClassifier, got {type(classifier).__name__}"
-            raise ValueError(msg)
-        if self.get_modality_mask_from_batch(batch) is not None:
-            msg = "a skill step decides what the model observes: a masked (7-tuple) batch already says what is seen"
-            raise ValueError(msg)
-        if self.state_carry is not None:
-            msg = "a skill step starts every row from its own frame 0: it does not combine with a set state_carry"
-            raise ValueError(msg)
-        actions = batch[0]
-        B, T = actions.shape[:2]
-        S, dev, q = wt.samples, actions.device, wt.query
-        if tuple(labels.shape) != (B, T) or labels.dtype not in (torch.int32, torch.int64) or labels.device != dev:
-            msg = f"labels must be an int32 / int64 tensor of shape {(B, T)} on {dev}, got {labels.dtype} {tuple(labels.shape)} on {labels.device}"
-            raise ValueError(msg)
-        if q > T:
-            msg = f"a batch of {T} frames has no context of {q}"
-            raise ValueError(msg)
-        if table is not None and (not isinstance(table, TransitionTable) or table.steps != T or table.buffer.device != dev):
-            msg = f"table must be a TransitionTable of {T} steps on {dev}"
-            raise ValueError(msg)
-        labels = labels.to(torch.int32)
-        wide = lambda x: x.repeat_interleave(S, dim=0)  # noqa: E731  (row (b, s) -> b * S + s)
-        word = wide(labels[:, q - 1]).contiguous()
-        if table is None:
-            table = TransitionTable(T, dev)
-        if wt.protocol == "reference":
-            noise = dict(noise or {})
-            audio_obs, vision_obs = self.get_observations_from_batch(batch)
-            conv.begin_step(dev)
-            state0 = self.initial_state((audio_obs[:, 0], vision_obs[:, 0]), noise)
-            state0 = self._state_like(state0, {k: wide(getattr(state0, k)) for k in self._FRESH_KEYS})
-            prior_noise = {}
-            for key in self._POST_KEYS:
-                prior_key = key.replace("post", "prior")
-                u = noise.get(prior_key)
-                k = self._category_size_of(key)
-                if u is not None and tuple(u.shape) != (B, S, 1, k):
-                    msg = f"noise[{prior_key!r}] must have shape {(B, S, 1, k)}, got {tuple(u.shape)}"
-                    raise ValueError(msg)
-                prior_noise[prior_key] = _rand(actions, B * S, 1, k) if u is None else u.reshape(B * S, 1, k).contiguous()
-            prior = self.rollout_transition(actions=wide(actions[:, q - 1 : q]).contiguous(), prev_state=state0, noise=prior_noise)
-            digits = self._read_vision(prior.feature, classifier)[:, 0]
-            word_counts(word, digits.contiguous(), table.q_counts)
-            return table
-        t_read = wt.read_frame(T)
-        out, _ = self._skill_rollout(batch, wt.skill, noise, None, expert_log_weights)
-        feature = self._feature_of(out)
-        if not wt.by_horizon:
-            digits = self._read_vision(feature[:, t_read : t_read + 1].contiguous(), classifier)[:, 0]
-            word_counts(word, digits.contiguous(), table.q_counts)
-            return table
-        planes = torch.empty(3, B, T, device=dev, dtype=torch.float32)
-        read = torch.empty(B * S, device=dev, dtype=torch.int32)
-        rows = max(1, int(wt.max_frames) // (S * T))
-        for r0 in range(0, B, rows):
-            r1 = min(B, r0 + rows)
-            d = self._read_vision(feature[r0 * S : r1 * S], classifier).reshape(r1 - r0, S, T)
-            read[r0 * S : r1 * S] = d[:, :, t_read].reshape(-1)
-            lab = labels[r0:r1]
-            live = lab >= 0
-            same = (d == lab[:, None]).sum(1).to(torch.float32)  # copies that read the frame's label
-            zero = torch.zeros((), device=dev)
-            planes[0, r0:r1] = torch.where(live, same / float(S), zero)
-            planes[1, r0:r1] = torch.where(live, (same > 0).to(torch.float32), zero)
-            planes[2, r0:r1] = live.to(torch.float32)
-        word_counts(word, read, table.q_counts)
-        context = torch.full((B,), q, dtype=torch.int32, device=dev)
-        frames = torch.zeros(T, device=dev)  # (the kernel's own count of all frames per bin: the table keeps the labelled ones)
-        ForecastSkill.table_add(planes, context, None, table.horizon, frames)
-        return table
+    _POST_KEYS = ("u_post",)  # the rollout's posterior uniforms; a skill step composes each with its "u_tail" twin (evaluation.CopyPlan)
 
     def _category_size_of(self, key: str) -> int:  # noqa: ARG002
         return self.transition.distribution_factory.category_size

@@ -1,0 +1,544 @@
+"""The evaluation steps of the models: forecast skill, word transitions, held-out likelihood, latent probes and
+episode panels.
+
+Every one of them runs ONE masked posterior rollout over ``B x copies`` rows and then scores it.  What differs between them is what a
+copy of a row is -- what it observes, up to which frame, whether it shares the row's uniforms, where it lies among the scan's rows -- and
+that is a ``CopyPlan``, which every config object builds for itself (``ForecastSkill.plan()`` ...).  ``_Evaluators._evaluation_rollout``
+turns a batch and a plan into the scan's outputs; the public methods are a guard, that rollout and a scorer.  A new evaluator adds a
+plan and a scorer, not a rollout.
+
+``_Evaluators`` is a mixin of ``core.MoPoE_MRSSM`` and reaches the model through ``self`` only; this module does not import ``core``.
+"""
+
+from __future__ import annotations
+
+from collections.abc import Callable, Iterator
+from dataclasses import dataclass
+
+import torch
+from torch import Tensor
+
+from multimodal_mtrssm_amd import cnn, conv
+from multimodal_mtrssm_amd._shared import _check_lengths, _masked_mean_embed, _pairable, _rand
+from multimodal_mtrssm_amd.digits import DigitClassifier, word_counts
+from multimodal_mtrssm_amd.distributions import MultiOneHotFactory
+from multimodal_mtrssm_amd.forecast import Forecast
+from multimodal_mtrssm_amd.likelihood import PLANES as LIKELIHOOD_PLANES
+from multimodal_mtrssm_amd.likelihood import LikelihoodBound, LikelihoodTable
+from multimodal_mtrssm_amd.panel import EpisodePanel, EpisodeVideo
+from multimodal_mtrssm_amd.probe import LatentProbe, LinearProbe, ProbeTable, frame_labels
+from multimodal_mtrssm_amd.skill import ForecastSkill, SkillTable, observed_bits
+from multimodal_mtrssm_amd.words import TransitionTable, WordTransitions
+
+Noise = dict[str, Tensor | None]
+_LAYOUTS = {"init": ("row", "copy"), "post": ("row", "copy", "tail", "prior"), "order": ("row", "copy")}
+
+
+@dataclass(frozen=True)
+class CopyPlan:
+    """What the copies of a row are in an evaluation rollout over ``B * copies`` rows.
+
+    ``bits``: the modality code an observed step of a copy sees (bit 0 audio, bit 1 vision) -- one for all copies, or one per copy.
+    ``context``: the frames a copy observes (None: every live frame; more than ``T``: as ``T``) -- one for all copies, or one per copy.
+    ``init``: ``"row"`` the copies share the row's initial uniforms ``(B, K)``, ``"copy"`` each has its own ``(B, S, K)``.
+    ``post``: ``"row"`` shared posterior uniforms ``(B, T, K)``; ``"copy"`` own ``(B, S, T, K)``; ``"tail"`` shared on the context, own
+    ``u_tail (B, S, T, K)`` after it; ``"prior"`` no posterior step at all: own ``u_prior (B, S, 1, K)`` for one prior step (the reference
+    protocol of ``word_transitions``).  ``order``: ``"row"`` copy ``s`` of row ``b`` is scan row ``b * S + s``, ``"copy"`` it is
+    ``s * B + b``.  Everything here is plain torch on any device."""
+
+    copies: int
+    bits: int | tuple[int, ...]
+    context: int | None | tuple[int | None, ...]
+    init: str = "row"
+    post: str = "row"
+    order: str = "row"
+
+    def __post_init__(self) -> None:
+        for name, allowed in _LAYOUTS.items():
+            if getattr(self, name) not in allowed:
+                msg = f"{name} must be one of {allowed}, got {getattr(self, name)!r}"
+                raise ValueError(msg)
+        if self.copies < 1 or any(isinstance(v, tuple) and len(v) != self.copies for v in (self.bits, self.context)):
+            msg = f"need copies >= 1 and one entry per copy, got {self}"
+            raise ValueError(msg)
+        if self.post == "tail" and not isinstance(self.context, int):
+            msg = f"tail uniforms begin after ONE context, got {self.context!r}"
+            raise ValueError(msg)
+
+    def per_copy(self, value):  # noqa: ANN001, ANN201
+        """``value`` (``bits`` or ``context``) as a tuple with one entry per copy."""
+        return value if isinstance(value, tuple) else (value,) * self.copies
+
+    @property
+    def contexts(self) -> tuple[int | None, ...]:
+        """The DISTINCT contexts, in the order of their first copy: one ``Forecast.sample`` launch each."""
+        return tuple(dict.fromkeys(self.per_copy(self.context)))
+
+    @property
+    def shares_frame0(self) -> bool:
+        """The copies of a row see the same modalities at frame 0 (every context observes it): one mean embedding per row."""
+        return isinstance(self.bits, int)
+
+    # -- rows ------------------------------------------------------------------------------------------------------------------------------
+    def rows(self, x: Tensor) -> Tensor:
+        """``[B, S, ...]`` -> the scan's rows ``[B * S, ...]``."""
+        if self.order == "copy":
+            x = x.transpose(0, 1)
+        return x.reshape(x.shape[0] * x.shape[1], *x.shape[2:])
+
+    def spread(self, x: Tensor) -> Tensor:
+        """``[B, ...]`` -> ``[B * S, ...]``: every copy of a row gets the row's ``x`` (actions, embeddings, gate weights, states)."""
+        return self.rows(x.unsqueeze(1).expand(x.shape[0], self.copies, *x.shape[1:]))
+
+    def first(self, x: Tensor) -> Tensor:
+        """``[B * S, ...]`` -> ``[B, ...]``: copy 0 of every row (a view)."""
+        return x[: x.shape[0] // self.copies] if self.order == "copy" else x[:: self.copies]
+
+    # -- uniforms --------------------------------------------------------------------------------------------------------------------------
+    def uniforms(self, key: str, u: Tensor, layout: str, batch: int, *tail: int) -> Tensor:
+        """``noise[key]`` as the scan's rows: ``layout`` ``"row"`` ``(B, *tail)`` is repeated for a row's copies, ``"copy"``
+        ``(B, S, *tail)`` taken as it lies."""
+        want = (batch, *tail) if layout == "row" else (batch, self.copies, *tail)
+        if tuple(u.shape) != want:
+            msg = f"noise[{key!r}] must have shape {want}, got {tuple(u.shape)}"
+            raise ValueError(msg)
+        return (self.spread(u) if layout == "row" else self.rows(u)).contiguous()
+
+    def tail_uniforms(self, key: str, u_post: Tensor, u_tail: Tensor) -> Tensor:
+        """``[B * S, T, K]``: copy ``s`` of row ``b`` reads ``u_post[b, t]`` on ``t < q`` and ``u_tail[b, s, t]`` from ``q`` on."""
+        b, t, k = u_post.shape
+        tail_key = key.replace("post", "tail")
+        if tuple(u_tail.shape) != (b, self.copies, t, k):
+            msg = f"noise[{tail_key!r}] must have shape {(b, self.copies, t, k)}, got {tuple(u_tail.shape)}"
+            raise ValueError(msg)
+        q = min(self.context, t)
+        return self.rows(torch.cat([u_post[:, None, :q].expand(b, self.copies, q, k), u_tail[:, :, q:]], dim=2)).contiguous()
+
+    def noise_shapes(self, model, batch: int, steps: int) -> dict[str, tuple[int, ...]]:  # noqa: ANN001
+        """The uniforms of one step under this plan, batch dimension first, for either model (``model._INIT_KEYS`` / ``_POST_KEYS``)."""
+        s = self.copies
+        shapes = {key: (batch, *(() if self.init == "row" else (s,)), model._category_size_of(key)) for key in model._INIT_KEYS}  # noqa: SLF001
+        sizes = {key: model._category_size_of(key) for key in model._POST_KEYS}  # noqa: SLF001
+        if self.post == "prior":
+            return shapes | {key.replace("post", "prior"): (batch, s, 1, k) for key, k in sizes.items()}
+        shapes |= {key: (batch, s, steps, k) if self.post == "copy" else (batch, steps, k) for key, k in sizes.items()}
+        if self.post == "tail":
+            shapes |= {key.replace("post", "tail"): (batch, s, steps, k) for key, k in sizes.items()}
+        return shapes
+
+    # -- the expansion ---------------------------------------------------------------------------------------------------------------------
+    def expand(self, base: dict[int | None, tuple[Tensor, Tensor]], noise: Noise | None,
+               sizes: dict[str, int]) -> tuple[Tensor, Tensor, Noise, Callable[[Tensor], Tensor]]:
+        """``(codes [B * S, T], mask0 [B * S, 2], noise, spread)`` of the scan's rows.  ``base``: per distinct context the ``codes``
+        int32 ``[B, T]`` and ``mask0`` bool ``[B, 2]`` of a row that observes both modalities on that context.  ``sizes``: ``K`` of the
+        uniforms to widen -- ``u_init*`` by ``init``, ``u_post*`` by ``post`` (``"tail"``: composed with their ``u_tail*`` twins).  A
+        shared uniform that is absent is drawn per ROW; an absent own one is left to its consumer's draw."""
+        if self.post == "prior":
+            msg = "a plan without posterior uniforms (post='prior') has no posterior rollout to expand"
+            raise ValueError(msg)
+        per = [base[c][0] for c in self.per_copy(self.context)]
+        ref = per[0]
+        (b, t), dev = ref.shape, ref.device
+        bits, seen = observed_bits(self.per_copy(self.bits), dev)
+        stacked = ref[:, None, :] if len(self.contexts) == 1 else torch.stack(per, dim=1)
+        codes = self.rows(stacked & bits[None, :, None]).contiguous()
+        mask0 = self.rows(base[self.contexts[0]][1][:, None, :] & seen[None])  # (frame 0 is inside every context)
+        noise = dict(noise or {})
+        for key, k in sizes.items():
+            layout, mid = (self.init, ()) if key.startswith("u_init") else (self.post, (t,))
+            u = noise.get(key)
+            if layout == "tail":
+                u_tail = noise.get(key.replace("post", "tail"))
+                u = _rand(ref, b, t, k) if u is None else u
+                if tuple(u.shape) != (b, t, k):
+                    msg = f"noise[{key!r}] must have shape {(b, t, k)}, got {tuple(u.shape)}"
+                    raise ValueError(msg)
+                noise[key] = self.tail_uniforms(key, u, _rand(ref, b, self.copies, t, k) if u_tail is None else u_tail)
+            elif layout == "row":
+                noise[key] = self.uniforms(key, _rand(ref, b, *mid, k) if u is None else u, "row", b, *mid, k)
+            elif u is not None:
+                noise[key] = self.uniforms(key, u, "copy", b, *mid, k)
+        return codes, mask0, noise, self.spread
+
+
+def _must_be(name: str, value: object, kind: type) -> None:
+    if not isinstance(value, kind):
+        msg = f"{name} must be a {kind.__name__}, got {type(value).__name__}"
+        raise ValueError(msg)
+
+
+def _check_labels(labels: Tensor, batch: tuple[Tensor, ...]) -> None:
+    (b, t), dev = batch[0].shape[:2], batch[0].device
+    if tuple(labels.shape) != (b, t) or labels.dtype not in (torch.int32, torch.int64) or labels.device != dev:
+        msg = f"labels must be an int32 / int64 tensor of shape {(b, t)} on {dev}, got {labels.dtype} {tuple(labels.shape)} on {labels.device}"
+        raise ValueError(msg)
+
+
+def _row_chunks(rows: int, frames_per_row: int, max_frames: int) -> Iterator[tuple[int, int]]:
+    """``(r0, r1)``: ``rows`` rows in chunks of whole rows of at most ``max_frames`` frames (one row at least)."""
+    per = max(1, int(max_frames) // frames_per_row)
+    for r0 in range(0, rows, per):
+        yield r0, min(rows, r0 + per)
+
+
+class _Evaluators:
+    """The evaluation steps of ``MoPoE_MRSSM`` (and, through its overrides, ``MoPoE_MMTRSSM``)."""
+
+    def _check_evaluation_step(self, batch: tuple[Tensor, ...], what: str, config: object, kind: type, table: object = None,  # noqa: PLR0913
+                               table_kind: type | None = None) -> None:
+        """The refusals every evaluation step shares: ``config`` (the argument ``what``) is a ``kind``; the batch carries no modality
+        mask; no ``state_carry`` is set; a given ``table`` is a ``table_kind`` of the batch's steps (and of ``config.groups``, where a
+        config has groups) on its device."""
+        _must_be(what, config, kind)
+        groups = getattr(config, "groups", None)
+        if self.get_modality_mask_from_batch(batch) is not None:
+            msg = "an evaluation step decides what the model observes: a masked (7-tuple) batch already says what is seen"
+            raise ValueError(msg)
+        if self.state_carry is not None:
+            msg = "an evaluation step starts every row from its own frame 0: it does not combine with a set state_carry"
+            raise ValueError(msg)
+        steps, dev = batch[0].shape[1], batch[0].device
+        if table is not None and (not isinstance(table, table_kind) or table.steps != steps or table.buffer.device != dev
+                                  or (groups is not None and table.groups != groups)):
+            of = f"{steps} steps" if groups is None else f"{groups} groups and {steps} steps"
+            msg = f"table must be a {table_kind.__name__} of {of} on {dev}"
+            raise ValueError(msg)
+
+    def _local_lengths(self, batch: tuple[Tensor, ...], lengths: Tensor | None) -> Tensor | None:
+        """This rank's rows' lengths (int32 ``[B]``) from ``lengths`` or a batch that carries ``valid_global``; None without either."""
+        ragged = self._lengths_of(batch, lengths, None, None)
+        if ragged is None:
+            return None
+        valid_global, world, rank = ragged
+        rows = batch[0].shape[0]
+        _check_lengths(valid_global, rows * world, batch[0].device)
+        return valid_global[rank * rows : (rank + 1) * rows].contiguous()
+
+    def _spread_state(self, state, spread: Callable[[Tensor], Tensor]):  # noqa: ANN001, ANN202
+        return self._state_like(state, {k: spread(getattr(state, k)) for k in self._FRESH_KEYS})
+
+    def _evaluation_rollout(self, batch: tuple[Tensor, ...], plan: CopyPlan, noise: Noise | None, lengths: Tensor | None,  # noqa: PLR0914
+                            expert_log_weights: Tensor | None) -> tuple[dict[str, Tensor], Tensor | None]:
+        """The rollout of every evaluation step: both encoders once, one ``Forecast.sample`` per distinct context of ``plan``, its
+        expansion, the initial state, the gate once per row and ONE masked posterior rollout over ``B * copies`` rows.  Returns the scan's
+        outputs -- with ``"codes"``, the rows' modality codes -- and the rows' lengths (or None).  The initial state is computed on ``B``
+        rows and spread when the copies share their frame-0 mask and their initial uniforms, else on the wide rows (from one mean
+        embedding per row when they share the mask).  ``expert_log_weights``: ``[B, T, 3]``, or ``[B * copies, T, 3]`` taken as it is."""
+        actions = batch[0]
+        audio_obs, vision_obs = self.get_observations_from_batch(batch)
+        (B, T), dev = actions.shape[:2], actions.device  # noqa: N806
+        valid = self._local_lengths(batch, lengths)
+        conv.begin_step(dev)
+        audio_embed, vision_embed = self._encode_both(audio_obs, vision_obs)
+        zeros = torch.zeros(B, device=dev)  # (fixed contexts: the uniforms do not matter)
+        base = {}
+        for c in plan.contexts:
+            sm = Forecast(T if c is None else c).sample(zeros, T, valid)
+            base[c] = (sm.codes, sm.mask0)
+        per_row = plan.shares_frame0 and plan.init == "row"
+        keys = self._POST_KEYS if per_row else (*self._INIT_KEYS, *self._POST_KEYS)
+        codes, mask0, wide_noise, spread = plan.expand(base, noise, {key: self._category_size_of(key) for key in keys})
+        if plan.shares_frame0:
+            embed0 = _masked_mean_embed(audio_embed[:, 0], vision_embed[:, 0], plan.first(mask0))
+            if per_row:
+                state0 = self._spread_state(self._initial_for_step(embed0, noise), spread)
+            else:
+                state0 = self._initial_for_step(spread(embed0), wide_noise)
+        else:
+            state0 = self._initial_for_step(_masked_mean_embed(spread(audio_embed[:, 0]), spread(vision_embed[:, 0]), mask0), wide_noise)
+        if expert_log_weights is not None and expert_log_weights.shape[0] == B * plan.copies:
+            logw = expert_log_weights  # (checked by the rollout)
+        else:
+            logw = self._expert_logw(audio_embed, vision_embed, expert_log_weights, B, T)  # the gate once per row ...
+            logw = None if logw is None else spread(logw)  # ... repeated for its copies
+        out = self._rollout_embedded(spread(actions), spread(audio_embed), spread(vision_embed), state0, wide_noise, sample_prior=False,
+                                     modality=codes, expert_log_weights=logw)
+        out["codes"] = codes
+        return out, valid
+
+    # -- forecast skill -------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def forecast_skill(self, batch: tuple[Tensor, ...], skill: ForecastSkill, noise: Noise | None = None, lengths: Tensor | None = None,  # noqa: PLR0913, PLR0914
+                       table: SkillTable | None = None, *, keep_states: bool = False, expert_log_weights: Tensor | None = None) -> SkillTable:
+        """One skill step: observe ``skill.context`` frames (of ``skill.observe``), roll ``skill.samples`` sampled
+        futures per row open loop in ONE masked posterior rollout over ``B * S`` rows (row ``b * S + s``; the copies of a row share
+        ``noise["u_post"]`` on the context and read ``noise["u_tail"][b, s]`` after it), decode, and score every live frame of both
+        modalities as an ensemble (``mtrssm_ensemble_score``); the planes are folded by horizon into ``table`` (a new one when None),
+        which is returned.  ``best`` is the best sample per FRAME.  ``lengths`` (or a batch that carries ``valid_global``) as in
+        ``forecast_rollout``: nothing is observed or scored at or past a row's end.  ``keep_states``: ``table.states`` is the posterior
+        state sequence ``[B * S, T, .]`` and ``table.planes`` the step's score planes ``[8, B, T]``.  Every row starts from its own
+        frame 0: no masked (7-tuple) batch, no ``state_carry``.  A weighted model runs its gate once per row and
+        repeats the weights for the row's copies; ``expert_log_weights`` (fp32 ``[B, T, 3]``, or ``[B * S, T, 3]`` already repeated)
+        gives them explicitly."""
+        self._check_evaluation_step(batch, "skill", skill, ForecastSkill, table, SkillTable)
+        actions = batch[0]
+        targets = self.get_targets_from_batch(batch)
+        B, T = actions.shape[:2]  # noqa: N806
+        S, dev = skill.samples, actions.device  # noqa: N806
+        out, valid = self._evaluation_rollout(batch, skill.plan(), noise, lengths, expert_log_weights)
+        feature = self._feature_of(out)
+        planes = torch.empty(SkillTable.ROWS, B, T, device=dev, dtype=torch.float32)
+        for r0, r1 in _row_chunks(B, S * T, skill.max_frames):
+            preds, acts = self._decode_for_score(feature[r0 * S : r1 * S])
+            part = torch.empty(SkillTable.ROWS, r1 - r0, T, device=dev, dtype=torch.float32)
+            for j, (pred, key) in enumerate(zip(preds, ("recon/audio", "recon/vision"), strict=True)):
+                ForecastSkill.score(pred.reshape(r1 - r0, S, T, -1), targets[key][r0:r1].reshape(r1 - r0, T, -1),
+                                    None if valid is None else valid[r0:r1], acts[j], out=part[4 * j : 4 * j + 4])
+            planes[:, r0:r1] = part
+        if table is None:
+            table = SkillTable(T, dev)
+        context = torch.full((B,), min(skill.context, (1 << 31) - 1), dtype=torch.int32, device=dev)
+        ForecastSkill.table_add(planes, context, valid, table.sums, table.counts)
+        table.planes = planes if keep_states else None
+        table.states = self._posterior_from_rollout(out) if keep_states else None
+        return table
+
+    def _decode_for_score(self, feature: Tensor, *, audio: bool = True, vision: bool = True) -> tuple[tuple[Tensor | None, Tensor | None], tuple[int, int]]:
+        """``(audio, vision)`` predictions of ``feature`` for the ensemble scorer and the output activations it applies while reading
+        them: this package's decoders hand over their RAW output (paired when they pair).  A modality that is not asked for is None."""
+        da, dv = self.audio_decoder, self.vision_decoder
+        fused = isinstance(da, cnn.Decoder) and isinstance(dv, cnn.Decoder) and da.out_act_id is not None and dv.out_act_id is not None
+        acts = (da.out_act_id, dv.out_act_id) if fused else (0, 0)
+        if audio and vision and fused and _pairable(da, dv, cnn.Decoder):
+            return cnn.decode_pair(da, dv, feature, feature, raw=True), acts
+        kw = {"raw": True} if fused else {}
+        return (da(feature, **kw) if audio else None, dv(feature, **kw) if vision else None), acts
+
+    # -- episode panels -------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def render_episodes(self, batch: tuple[Tensor, ...], panel: EpisodePanel, noise: Noise | None = None, lengths: Tensor | None = None, *,  # noqa: PLR0913, PLR0914
+                        rows: Tensor | list[int] | None = None, frame0: int = 0, keep_states: bool = False,
+                        expert_log_weights: Tensor | None = None) -> EpisodeVideo:
+        """The episode panels of a batch: what the reference's logging callback shows per episode -- the open-loop
+        prior, the observation and the closed-loop posterior, vision over audio -- as one finished uint8 video.  Both encoders run once,
+        then ONE masked posterior rollout over ``2 N`` rows: rows ``[0, N)`` observe ``panel.observe`` on every live frame (the
+        posterior), rows ``[N, 2 N)`` observe it on ``t < panel.query_length`` and nothing after (the prior).  Both halves start from the
+        same initial state and read the same ``noise["u_post"]`` (MMTRSSM: the ``_l`` / ``_h`` pairs), so on the context the prior is
+        the posterior bit for bit: the callback's ``cat_states([posterior[:, :q], prior])``.  Both halves are decoded in chunks of whole
+        rows through the decoders' activated path and one ``mtrssm_episode_panel`` launch writes the video.  ``rows`` (an index tensor or
+        list) picks the episodes before anything runs, ``noise`` and ``lengths`` with them; ``frame0`` is the number drawn on frame 0.
+        ``lengths`` (or a batch that carries ``valid_global``): nothing is observed at or past a row's end and those frames are black.
+        ``keep_states``: the video carries the rollout's posterior states ``[2 N, T, .]`` and the decoded frames.  No masked (7-tuple)
+        batch, no ``state_carry``; a weighted model runs its gate once per row and repeats it for the row's second copy."""
+        self._check_evaluation_step(batch, "panel", panel, EpisodePanel)
+        dev = batch[0].device
+        if rows is not None:
+            pick = torch.as_tensor(rows, dtype=torch.int64, device=dev).reshape(-1)
+            if pick.numel() == 0:
+                msg = "rows picks no episode"
+                raise ValueError(msg)
+            lengths = self._local_lengths(batch, lengths)
+            lengths = None if lengths is None else lengths.index_select(0, pick).contiguous()
+            batch = tuple(b.index_select(0, pick) for b in batch[:6])
+            noise = {k: (None if u is None else u.index_select(0, pick)) for k, u in (noise or {}).items()}
+            if expert_log_weights is not None:
+                expert_log_weights = expert_log_weights.index_select(0, pick)
+        targets = self.get_targets_from_batch(batch)
+        N, T = batch[0].shape[:2]  # noqa: N806
+        plan = panel.plan()
+        out, valid = self._evaluation_rollout(batch, plan, noise, lengths, expert_log_weights)
+        feature = self._feature_of(out)  # [2 N, T, F]
+        da, dv = self.audio_decoder, self.vision_decoder
+        decoded: dict[str, Tensor] = {}
+        for r0, r1 in _row_chunks(N, 2 * T, panel.max_frames):
+            both = torch.cat([feature[r0:r1], feature[N + r0 : N + r1]], dim=0)
+            ya, yv = cnn.decode_pair(da, dv, both, both) if _pairable(da, dv, cnn.Decoder) else (da(both), dv(both))
+            for name, y in (("audio", ya), ("vision", yv)):
+                y = y.to(torch.float32)  # noqa: PLW2901
+                if (r0, r1) == (0, N):
+                    decoded[f"posterior/{name}"], decoded[f"prior/{name}"] = y[:N], y[N:]
+                    continue
+                if r0 == 0:
+                    decoded[f"posterior/{name}"] = torch.empty(N, *y.shape[1:], device=dev, dtype=torch.float32)
+                    decoded[f"prior/{name}"] = torch.empty(N, *y.shape[1:], device=dev, dtype=torch.float32)
+                decoded[f"posterior/{name}"][r0:r1], decoded[f"prior/{name}"][r0:r1] = y[: r1 - r0], y[r1 - r0 :]
+        decoded["observation/audio"] = targets["recon/audio"].to(torch.float32).contiguous()
+        decoded["observation/vision"] = targets["recon/vision"].to(torch.float32).contiguous()
+        context = torch.full((N,), min(panel.query_length, (1 << 31) - 1), dtype=torch.int32, device=dev)
+        frames = panel.render(decoded["observation/audio"], decoded["posterior/audio"], decoded["prior/audio"], decoded["observation/vision"],
+                              decoded["posterior/vision"], decoded["prior/vision"], codes=plan.first(out["codes"]), valid=valid, context=context,
+                              frame0=frame0)
+        video = EpisodeVideo(frames, context, valid)
+        if keep_states:
+            video.states, video.decoded = self._posterior_from_rollout(out), decoded
+        return video
+
+    # -- held-out likelihood --------------------------------------------------------------------------------------------------
+    def _latent_levels(self) -> tuple[tuple[str, MultiOneHotFactory], ...]:
+        """The latent levels of a posterior rollout: the suffix of their scan outputs and the factory that knows their K and C."""
+        return (("", self.transition.distribution_factory),)
+
+    @torch.no_grad()
+    def likelihood_bound(self, batch: tuple[Tensor, ...], bound: LikelihoodBound, noise: Noise | None = None, lengths: Tensor | None = None,  # noqa: PLR0913, PLR0914
+                         table: LikelihoodTable | None = None, *, keep_states: bool = False,
+                         expert_log_weights: Tensor | None = None) -> LikelihoodTable:
+        """One likelihood step (``likelihood.py`` states the quantity): ``bound.samples`` posterior trajectories
+        per row in ONE masked posterior rollout over ``B * S`` rows (row ``b * S + s``; the posterior sees ``bound.observe`` on every live
+        step and nothing after a row's end; every copy starts from its row's frame 0 with its own ``noise["u_init"][b, s]`` and reads
+        ``noise["u_post"][b, s]``), the latent log-ratio of the sampled classes (``mtrssm_latent_log_ratio``, one launch per level), the
+        decoders over chunks of whole rows, the per-sample errors (``mtrssm_ensemble_score``) and the bound (``mtrssm_iw_bound``); the
+        planes are folded by frame position into ``table`` (a new one when None), which is returned.  ``lengths`` (or a batch that
+        carries ``valid_global``): nothing is observed or scored at or past a row's end.  ``keep_states``: ``table.states`` is the
+        posterior state sequence ``[B * S, T, .]`` and ``table.planes`` the step's planes ``[8, B, T]``.  No masked (7-tuple) batch, no
+        ``state_carry``.  A weighted model runs its gate as in ``forecast_skill``."""
+        self._check_evaluation_step(batch, "bound", bound, LikelihoodBound, table, LikelihoodTable)
+        actions = batch[0]
+        targets = self.get_targets_from_batch(batch)
+        B, T = actions.shape[:2]  # noqa: N806
+        S, dev = bound.samples, actions.device  # noqa: N806
+        out, valid = self._evaluation_rollout(batch, bound.plan(), noise, lengths, expert_log_weights)
+        ratio = None
+        if bound.latent:
+            for suffix, factory in self._latent_levels():
+                ratio = LikelihoodBound.log_ratio(out[f"post_logits{suffix}"], out[f"prior_logits{suffix}"], out[f"post_stoch{suffix}"],
+                                                  factory.category_size, factory.class_size, out=ratio, accumulate=ratio is not None)
+            ratio = ratio.reshape(B, S, T)
+        if table is None:
+            table = LikelihoodTable(T, dev)
+        audio, vision = "audio" in bound.score, "vision" in bound.score
+        feature = self._feature_of(out) if bound.score else None
+        planes = torch.empty(len(LIKELIHOOD_PLANES), B, T, device=dev, dtype=torch.float32)
+        for r0, r1 in _row_chunks(B, S * T, bound.max_frames if bound.score else B * S * T):  # (nothing to decode: one chunk)
+            n = r1 - r0
+            chunk_valid = None if valid is None else valid[r0:r1]
+            se, events = [None, None], [0, 0]
+            if bound.score:
+                preds, acts = self._decode_for_score(feature[r0 * S : r1 * S], audio=audio, vision=vision)
+                for j, (pred, key) in enumerate(zip(preds, ("recon/audio", "recon/vision"), strict=True)):
+                    if pred is None:
+                        continue
+                    pred = pred.reshape(n, S, T, -1)  # noqa: PLW2901
+                    events[j] = pred.shape[-1]
+                    se[j] = ForecastSkill.score(pred, targets[key][r0:r1].reshape(n, T, -1), chunk_valid, acts[j], se_samples=True).se_samples
+            part = planes if n == B else torch.empty(len(LIKELIHOOD_PLANES), n, T, device=dev, dtype=torch.float32)
+            LikelihoodBound.bound(se[0], se[1], None if ratio is None else ratio[r0:r1], chunk_valid, events[0], events[1], out=part)
+            table.fold(part, chunk_valid)
+            if n != B:
+                planes[:, r0:r1] = part
+        table.planes = planes if keep_states else None
+        table.states = self._posterior_from_rollout(out) if keep_states else None
+        return table
+
+    # -- latent probes --------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def probe_features(self, batch: tuple[Tensor, ...], probe: LatentProbe, noise: Noise | None = None, lengths: Tensor | None = None, *,
+                       expert_log_weights: Tensor | None = None) -> tuple[Tensor, Tensor | None]:
+        """The features a linear probe reads: ``x [G, B, T, Ffull]`` and the rows' lengths ``valid`` (int32 ``[B]``, or
+        None).  Both encoders run once, then ONE masked posterior rollout over ``B * G`` rows (row ``b * G + g``): copy ``g`` of a row
+        observes ``probe.observe[g]`` on every live step and at frame 0, nothing at or past the row's end, and the copies share the
+        row's uniforms (``probe.noise_shapes``).  ``x[g]`` is the feature the decoders would read of that posterior; ``probe.columns(self)``
+        names the part to probe in place.  No masked (7-tuple) batch, no ``state_carry``; a weighted model runs its gate once per row."""
+        self._check_evaluation_step(batch, "probe", probe, LatentProbe)
+        B, T = batch[0].shape[:2]  # noqa: N806
+        out, valid = self._evaluation_rollout(batch, probe.plan(), noise, lengths, expert_log_weights)
+        feature = self._feature_of(out)  # [B * G, T, Ffull]
+        return feature.reshape(B, probe.groups, T, -1).permute(1, 0, 2, 3).contiguous(), valid
+
+    @torch.no_grad()
+    def probe_evaluate(self, batch: tuple[Tensor, ...], labels: Tensor, probe: LatentProbe, linear: LinearProbe,  # noqa: PLR0913
+                       table: ProbeTable | None = None, noise: Noise | None = None, lengths: Tensor | None = None, *,
+                       expert_log_weights: Tensor | None = None) -> ProbeTable:
+        """One evaluation step of a fitted probe: ``probe_features``, ONE evaluation-only ``linear.step`` with planes on
+        ``probe.columns(self)`` and the fold of ``hit`` / ``nll`` by frame position into ``table`` (a new one when None), which is
+        returned; ``table.stats`` keeps the step's ``ProbeStats`` (planes ``[G, B * T]``).  ``labels``: int ``[B, T]`` on the device,
+        -1 = silence; a frame at or past its row's end is dead whatever its label."""
+        self._check_evaluation_step(batch, "probe", probe, LatentProbe, table, ProbeTable)
+        _must_be("linear", linear, LinearProbe)
+        actions = batch[0]
+        B, T = actions.shape[:2]  # noqa: N806
+        G, dev = probe.groups, actions.device  # noqa: N806
+        col0, width = probe.columns(self)
+        if linear.groups != G or linear.features != width:
+            msg = f"{probe!r} on {type(self).__name__} needs a LinearProbe of {G} groups and {width} features, got {linear.groups} and {linear.features}"
+            raise ValueError(msg)
+        _check_labels(labels, batch)
+        x, valid = self.probe_features(batch, probe, noise, lengths, expert_log_weights=expert_log_weights)
+        flat = frame_labels(labels, valid)
+        stats = linear.step(x.reshape(G, B * T, -1), flat, col0=col0, grad=False, planes=True)
+        if table is None:
+            table = ProbeTable(G, T, dev, probe.observe)
+        live = ((flat >= 0) & (flat < linear.classes)).reshape(B, T)
+        table.fold(stats.hit.reshape(G, B, T), stats.nll.reshape(G, B, T), live)
+        table.stats = stats
+        return table
+
+    # -- word transitions -----------------------------------------------------------------------------------------------------
+    def _read_vision(self, feature: Tensor, classifier: DigitClassifier) -> Tensor:
+        """The digits (int32, ``feature``'s leading shape) the classifier reads off the vision frames decoded from ``feature``; the
+        decoder's raw output goes to the reader, which applies the output activation itself."""
+        dv = self.vision_decoder
+        fused = isinstance(dv, cnn.Decoder) and dv.out_act_id is not None
+        pred = dv(feature, raw=True) if fused else dv(feature)
+        if pred.numel() != feature[..., 0].numel() * 32 * 32:
+            msg = f"the digit classifier reads 1 x 32 x 32 vision frames, the decoder gives {tuple(pred.shape[feature.dim() - 1 :])}"
+            raise ValueError(msg)
+        return classifier.digits(pred, dv.out_act_id if fused else 0).reshape(feature.shape[:-1])
+
+    @torch.no_grad()
+    def word_transitions(self, batch: tuple[Tensor, ...], labels: Tensor, wt: WordTransitions, classifier: DigitClassifier,  # noqa: PLR0913, PLR0914
+                         noise: Noise | None = None, table: TransitionTable | None = None, *,
+                         expert_log_weights: Tensor | None = None) -> TransitionTable:
+        """One transition step (``words.py``): sample ``wt.samples`` futures per row, read the predicted vision
+        frame of each with ``classifier`` and add ``q_counts[word][digit] += 1`` into ``table`` (a new one when None), which is
+        returned.  ``labels``: int ``[B, T]`` on the device, -1 = silence; row b's current word is ``labels[b, wt.query - 1]`` and a
+        silent row is skipped.  ``protocol="context"``: ``forecast_skill``'s masked rollout (the same noise: ``u_post`` / ``u_tail``),
+        frame ``wt.query - 1 + wt.read_at`` is read; only that frame is decoded, or -- ``wt.by_horizon`` -- chunks of whole rows of at
+        most ``wt.max_frames`` frames, every frame read and the ``hit`` / ``any`` planes folded by horizon.  ``protocol="reference"``:
+        the initial state of frame 0, then a prior-only step with the interval's last action ``batch[0][:, wt.query - 1]``
+        (``noise["u_prior"]``: ``[B, S, 1, K]``), whose frame is read.  No masked (7-tuple) batch, no ``state_carry``.  A weighted model
+        runs its gate as in ``forecast_skill``."""
+        self._check_evaluation_step(batch, "wt", wt, WordTransitions, table, TransitionTable)
+        _must_be("classifier", classifier, DigitClassifier)
+        actions = batch[0]
+        B, T = actions.shape[:2]  # noqa: N806
+        S, dev, q = wt.samples, actions.device, wt.query  # noqa: N806
+        _check_labels(labels, batch)
+        if q > T:
+            msg = f"a batch of {T} frames has no context of {q}"
+            raise ValueError(msg)
+        labels = labels.to(torch.int32)
+        plan = wt.plan()
+        word = plan.spread(labels[:, q - 1]).contiguous()
+        if table is None:
+            table = TransitionTable(T, dev)
+        if wt.protocol == "reference":
+            noise = dict(noise or {})
+            audio_obs, vision_obs = self.get_observations_from_batch(batch)
+            conv.begin_step(dev)
+            state0 = self._spread_state(self.initial_state((audio_obs[:, 0], vision_obs[:, 0]), noise), plan.spread)
+            prior_noise = {}
+            for key in self._POST_KEYS:
+                prior_key, k = key.replace("post", "prior"), self._category_size_of(key)
+                u = noise.get(prior_key)
+                prior_noise[prior_key] = _rand(actions, B * S, 1, k) if u is None else plan.uniforms(prior_key, u, "copy", B, 1, k)
+            prior = self.rollout_transition(actions=plan.spread(actions[:, q - 1 : q]).contiguous(), prev_state=state0, noise=prior_noise)
+            digits = self._read_vision(prior.feature, classifier)[:, 0]
+            word_counts(word, digits.contiguous(), table.q_counts)
+            return table
+        t_read = wt.read_frame(T)
+        out, _ = self._evaluation_rollout(batch, plan, noise, None, expert_log_weights)
+        feature = self._feature_of(out)
+        if not wt.by_horizon:
+            digits = self._read_vision(feature[:, t_read : t_read + 1].contiguous(), classifier)[:, 0]
+            word_counts(word, digits.contiguous(), table.q_counts)
+            return table
+        planes = torch.empty(3, B, T, device=dev, dtype=torch.float32)
+        read = torch.empty(B * S, device=dev, dtype=torch.int32)
+        for r0, r1 in _row_chunks(B, S * T, wt.max_frames):
+            d = self._read_vision(feature[r0 * S : r1 * S], classifier).reshape(r1 - r0, S, T)
+            read[r0 * S : r1 * S] = d[:, :, t_read].reshape(-1)
+            lab = labels[r0:r1]
+            live = lab >= 0
+            same = (d == lab[:, None]).sum(1).to(torch.float32)  # copies that read the frame's label
+            zero = torch.zeros((), device=dev)
+            planes[0, r0:r1] = torch.where(live, same / float(S), zero)
+            planes[1, r0:r1] = torch.where(live, (same > 0).to(torch.float32), zero)
+            planes[2, r0:r1] = live.to(torch.float32)
+        word_counts(word, read, table.q_counts)
+        context = torch.full((B,), q, dtype=torch.int32, device=dev)
+        frames = torch.zeros(T, device=dev)  # (the kernel's own count of all frames per bin: the table keeps the labelled ones)
+        ForecastSkill.table_add(planes, context, None, table.horizon, frames)
+        return table
+
+
+__all__ = ["CopyPlan"]

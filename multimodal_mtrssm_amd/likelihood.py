@@ -28,21 +28,20 @@ Per ``(b, t)`` eight planes ``[8, B, T]`` (``PLANES``), each exactly 0 on dead f
 
 from __future__ import annotations
 
-import copy
 import math
 
 import torch
 from torch import Tensor
 
 from multimodal_mtrssm_amd import _lib
-from multimodal_mtrssm_amd.skill import MAX_SAMPLES, MODALITIES, OBSERVE_BITS, ForecastSkill
+from multimodal_mtrssm_amd.skill import MAX_SAMPLES, MODALITIES, OBSERVE_BITS, ForecastSkill, ObservingConfig, PlaneTable
 
 PLANES = ("iw", "elbo", "audio", "vision", "latent", "ess", "iw_prefix", "elbo_prefix")
 TABLE_ROWS = PLANES[:6]  # what a LikelihoodTable folds by frame position
 HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
 
 
-class LikelihoodBound:
+class LikelihoodBound(ObservingConfig):
     """``LikelihoodBound(samples=S, observe=..., score=..., latent=...)``: ``S`` (1 .. 16) posterior trajectories per row, sampled
     from the posterior that sees ``observe`` (both modalities, audio only or vision only) at every live step; ``score`` names the
     modalities whose data terms enter and ``latent`` switches the latent log-ratio.  ``score=("vision",), latent=False,
@@ -69,39 +68,16 @@ class LikelihoodBound:
         self.score = tuple(m for m in MODALITIES if m in score)
         self.max_frames = 4096
         self.group = None  # the process group LikelihoodTable.all_reduce uses (FlatDataParallel.likelihood binds it)
-        self._observed: dict[torch.device, Tensor] = {}
 
     def __repr__(self) -> str:
         return f"LikelihoodBound(samples={self.samples}, observe={self.observe!r}, score={self.score!r}, latent={self.latent})"
 
-    @property
-    def bits(self) -> int:
-        """The scans' modality code of a live step: bit 0 audio, bit 1 vision."""
-        return OBSERVE_BITS[self.observe]
+    def plan(self):  # noqa: ANN201
+        """``S`` copies of a row observe ``observe`` on every live frame; each has its own initial draw ``u_init (B, S, K)`` and its own
+        posterior draws ``u_post (B, S, T, K)``."""
+        from multimodal_mtrssm_amd.evaluation import CopyPlan  # noqa: PLC0415  (evaluation imports this module)
 
-    def observed(self, device: torch.device) -> Tensor:
-        """Bool ``[2]`` (audio, vision) on ``device``: what a live step sees; made once per device."""
-        device = torch.device(device)
-        if device not in self._observed:
-            self._observed[device] = torch.tensor([bool(self.bits & 1), bool(self.bits & 2)], device=device)
-        return self._observed[device]
-
-    def for_group(self, group) -> LikelihoodBound:  # noqa: ANN001
-        """A copy whose table is all-reduced over ``group`` (``FlatDataParallel.likelihood`` calls this)."""
-        bound = copy.copy(self)
-        bound.group = group
-        return bound
-
-    def noise_shapes(self, model, batch: int, steps: int) -> dict[str, tuple[int, ...]]:  # noqa: ANN001
-        """The uniforms of one likelihood step, batch dimension first (``GlobalRowNoise`` shards them as they are): every copy of a
-        row has its own initial draw ``u_init (B, S, K)`` and its own posterior draws ``u_post (B, S, T, K)`` (MMTRSSM: the ``_l`` /
-        ``_h`` pairs); row ``(b, s)`` is scan row ``b * S + s``."""
-        s = self.samples
-        if hasattr(model, "l_dist"):
-            kl, kh = model.l_dist.category_size, model.h_dist.category_size
-            return {"u_init_h": (batch, s, kh), "u_init_l": (batch, s, kl), "u_post_l": (batch, s, steps, kl), "u_post_h": (batch, s, steps, kh)}
-        k = model.transition.distribution_factory.category_size
-        return {"u_init": (batch, s, k), "u_post": (batch, s, steps, k)}
+        return CopyPlan(self.samples, self.bits, None, init="copy", post="copy")
 
     # -- the rules in torch, in float64 ------------------------------------------------------------------------------------------------
     @staticmethod
@@ -261,32 +237,11 @@ class LikelihoodBound:
         return out
 
 
-class LikelihoodTable:
+class LikelihoodTable(PlaneTable):
     """The accumulated bound of any number of likelihood steps in ONE fp32 buffer ``[6 + 1, T]``: the planes ``TABLE_ROWS`` (iw, elbo,
-    audio, vision, latent, ess) summed by frame position, then the counts of live frames.  A step run with ``keep_states`` also leaves
-    its planes (``planes``, ``[8, B, T]``) and its rollout (``states``) here; otherwise both are None."""
+    audio, vision, latent, ess) summed by frame position, then the counts of live frames."""
 
     ROWS = len(TABLE_ROWS)
-
-    def __init__(self, steps: int, device: torch.device | str = "cpu") -> None:
-        if steps < 1:
-            msg = f"need steps >= 1, got {steps}"
-            raise ValueError(msg)
-        self.buffer = torch.zeros(self.ROWS + 1, steps, dtype=torch.float32, device=device)
-        self.planes: Tensor | None = None
-        self.states = None
-
-    @property
-    def steps(self) -> int:
-        return self.buffer.shape[1]
-
-    @property
-    def sums(self) -> Tensor:
-        return self.buffer[: self.ROWS]
-
-    @property
-    def counts(self) -> Tensor:
-        return self.buffer[self.ROWS]
 
     def fold(self, planes: Tensor, valid: Tensor | None = None) -> LikelihoodTable:
         """Adds a step's planes (``[8, B, T]`` or their first six) by frame position: ``mtrssm_horizon_table`` with ``context = 1``, whose
@@ -298,32 +253,14 @@ class LikelihoodTable:
         ForecastSkill.table_add(planes[: self.ROWS], context, valid, self.sums, self.counts)
         return self
 
-    def add(self, other: LikelihoodTable) -> LikelihoodTable:
-        if tuple(other.buffer.shape) != tuple(self.buffer.shape):
-            msg = f"tables of {self.steps} and {other.steps} steps do not add"
-            raise ValueError(msg)
-        self.buffer += other.buffer.to(self.buffer.device)
-        return self
-
-    def all_reduce(self, group=None) -> LikelihoodTable:  # noqa: ANN001
-        """One SUM all-reduce of the buffer (counts stay exact below 2^24 frames per bin); a no-op without a process group."""
-        import torch.distributed as dist  # noqa: PLC0415
-
-        if dist.is_available() and dist.is_initialized():
-            dist.all_reduce(self.buffer, op=dist.ReduceOp.SUM, group=group)
-        return self
-
     def curves(self) -> dict[str, Tensor]:
         """``sums / counts`` per plane, ``[T]`` each: the mean over the rows that are live at frame ``t``; an empty bin gives NaN."""
-        counts = self.counts
-        nan = torch.full_like(counts, float("nan"))
-        return {name: torch.where(counts > 0, row / counts, nan) for name, row in zip(TABLE_ROWS, self.sums, strict=True)}
+        return {name: self._mean(row, self.counts) for name, row in zip(TABLE_ROWS, self.sums, strict=True)}
 
     def per_frame(self) -> dict[str, Tensor]:
         """Each plane's summed row over the summed counts: nats per live frame (``ess``: its mean); NaN for an empty table."""
         total = self.counts.sum()
-        nan = torch.full_like(total, float("nan"))
-        return {name: torch.where(total > 0, row.sum() / total, nan) for name, row in zip(TABLE_ROWS, self.sums, strict=True)}
+        return {name: self._mean(row.sum(), total) for name, row in zip(TABLE_ROWS, self.sums, strict=True)}
 
     def scalars(self, prefix: str) -> dict[str, Tensor]:
         """``prefix/{iw,elbo,audio,vision,latent,ess,gap}``: ``per_frame`` as a flat dict, ``gap = iw - elbo`` (>= 0 up to rounding)."""

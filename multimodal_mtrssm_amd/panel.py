@@ -35,7 +35,7 @@ import torch
 from torch import Tensor
 
 from multimodal_mtrssm_amd import _lib
-from multimodal_mtrssm_amd.skill import OBSERVE_BITS
+from multimodal_mtrssm_amd.skill import OBSERVE_BITS, ObservingConfig
 
 COLUMNS = ("prior", "observation", "posterior", "error")
 GAP_COLOUR = (64, 64, 64)
@@ -112,7 +112,7 @@ def _frame_chw(name: str, chw: tuple[int, int, int]) -> tuple[int, int, int]:
     return chw  # type: ignore[return-value]
 
 
-class EpisodePanel:
+class EpisodePanel(ObservingConfig):
     """``EpisodePanel(q, observe=..., columns=..., scale=2, gap=1, bar=2, label=1, blank_unseen=True)``: the model observes ``q >= 1``
     frames (of ``observe``: both modalities, audio only or vision only) and then the prior runs open loop; ``columns`` is a choice of
     ``"prior"``, ``"observation"``, ``"posterior"`` and ``"error"`` (|prior - observation| through magma) without repeats, left to right.
@@ -140,7 +140,6 @@ class EpisodePanel:
         self.label = _whole("label", label, *_LIMITS["label"])
         self.blank_unseen = blank_unseen
         self.max_frames = 4096
-        self._observed: dict[torch.device, Tensor] = {}
 
     def __repr__(self) -> str:
         return (f"EpisodePanel({self.query_length}, observe={self.observe!r}, columns={self.columns!r}, scale={self.scale}, gap={self.gap}, "
@@ -150,17 +149,12 @@ class EpisodePanel:
     def context(self) -> int:
         return self.query_length
 
-    @property
-    def bits(self) -> int:
-        """The scans' modality code of an observed step: bit 0 audio, bit 1 vision."""
-        return OBSERVE_BITS[self.observe]
+    def plan(self):  # noqa: ANN201
+        """Two copies of a row in copy order: rows ``[0, N)`` observe every live frame (the posterior), rows ``[N, 2 N)`` the first
+        ``query_length`` (the prior); both share the row's uniforms, so they agree bit for bit on the context."""
+        from multimodal_mtrssm_amd.evaluation import CopyPlan  # noqa: PLC0415  (evaluation imports this module)
 
-    def observed(self, device: torch.device) -> Tensor:
-        """Bool ``[2]`` (audio, vision) on ``device``: what an observed step sees; made once per device."""
-        device = torch.device(device)
-        if device not in self._observed:
-            self._observed[device] = torch.tensor([bool(self.bits & 1), bool(self.bits & 2)], device=device)
-        return self._observed[device]
+        return CopyPlan(2, self.bits, (None, self.query_length), order="copy")
 
     # -- geometry ----------------------------------------------------------------------------------------------------------------------
     def shape(self, audio_chw: tuple[int, int, int], vision_chw: tuple[int, int, int]) -> tuple[int, int]:

@@ -18,14 +18,13 @@ float64; ``mtrssm_linear_probe_step`` is the kernel, used for GPU tensors; elsew
 
 from __future__ import annotations
 
-import copy
 from typing import NamedTuple
 
 import torch
 from torch import Tensor, nn
 
 from multimodal_mtrssm_amd import _lib
-from multimodal_mtrssm_amd.skill import OBSERVE_BITS, ForecastSkill
+from multimodal_mtrssm_amd.skill import OBSERVE_BITS, ForecastSkill, ObservingConfig, SumTable, observed_bits
 
 MAX_CLASSES = 16
 MAX_FEATURES = 2048  # the kernel stages 16 rows of F floats in LDS
@@ -218,7 +217,7 @@ class LinearProbe(nn.Module):
         return stats
 
 
-class LatentProbe:
+class LatentProbe(ObservingConfig):
     """``LatentProbe(observe=("both", "audio", "vision"), part="feature")``: which posteriors are probed and which part of their feature.
     Copy ``g`` of every row observes subset ``observe[g]`` on every live step (and at frame 0); the copies share the row's uniforms, so
     the subsets differ only in what they observe.  ``part``: ``feature`` (all of it), ``deter`` / ``stoch`` (MRSSM's two halves) or, for
@@ -234,7 +233,6 @@ class LatentProbe:
             raise ValueError(msg)
         self.observe, self.part = tuple(observe), part
         self.group = None  # the process group ProbeTable.all_reduce and LinearProbe.fit use (FlatDataParallel.probe binds it)
-        self._bits: dict[torch.device, tuple[Tensor, Tensor]] = {}
 
     def __repr__(self) -> str:
         return f"LatentProbe(observe={self.observe!r}, part={self.part!r})"
@@ -246,35 +244,19 @@ class LatentProbe:
 
     groups = samples
 
-    def _per_copy(self, device: torch.device) -> tuple[Tensor, Tensor]:
-        device = torch.device(device)
-        if device not in self._bits:
-            bits = [OBSERVE_BITS[o] for o in self.observe]
-            self._bits[device] = (torch.tensor(bits, dtype=torch.int32, device=device),
-                                  torch.tensor([[bool(b & 1), bool(b & 2)] for b in bits], device=device))
-        return self._bits[device]
-
     def copy_bits(self, device: torch.device) -> Tensor:
         """int32 ``[G]`` on ``device``: the scans' modality code of a live step of copy ``g`` (bit 0 audio, bit 1 vision)."""
-        return self._per_copy(device)[0]
+        return observed_bits(self.bits, torch.device(device))[0]
 
     def copy_observed(self, device: torch.device) -> Tensor:
         """Bool ``[G, 2]`` (audio, vision) on ``device``: what a live step of copy ``g`` sees."""
-        return self._per_copy(device)[1]
+        return self.observed(device)
 
-    def for_group(self, group) -> LatentProbe:  # noqa: ANN001
-        """A copy bound to ``group`` (``FlatDataParallel.probe`` calls this)."""
-        bound = copy.copy(self)
-        bound.group = group
-        return bound
+    def plan(self):  # noqa: ANN201
+        """Copy ``g`` of a row observes ``observe[g]`` on every live frame; the copies share the row's uniforms (the model's own shapes)."""
+        from multimodal_mtrssm_amd.evaluation import CopyPlan  # noqa: PLC0415  (evaluation imports this module)
 
-    def noise_shapes(self, model, batch: int, steps: int) -> dict[str, tuple[int, ...]]:  # noqa: ANN001
-        """The uniforms of one probe step, batch dimension first: the model's own, shared by the copies of a row."""
-        if hasattr(model, "l_dist"):
-            kl, kh = model.l_dist.category_size, model.h_dist.category_size
-            return {"u_init_h": (batch, kh), "u_init_l": (batch, kl), "u_post_l": (batch, steps, kl), "u_post_h": (batch, steps, kh)}
-        k = model.transition.distribution_factory.category_size
-        return {"u_init": (batch, k), "u_post": (batch, steps, k)}
+        return CopyPlan(self.groups, self.bits, None)
 
     @staticmethod
     def layout(model) -> dict[str, tuple[int, int]]:  # noqa: ANN001
@@ -299,7 +281,7 @@ class LatentProbe:
         return LinearProbe(self.groups, self.columns(model)[1], classes).to(next(model.parameters()).device)
 
 
-class ProbeTable:
+class ProbeTable(SumTable):
     """The accumulated evaluation of any number of probe steps in ONE fp32 buffer ``[2 G + 1, T]``: ``hit`` of the ``G`` groups, then
     their ``nll``, summed by frame position over the live (labelled) frames, then the counts of those frames."""
 
@@ -315,10 +297,6 @@ class ProbeTable:
                                                                    tuple(f"g{i}" for i in range(groups)))
         self.buffer = torch.zeros(2 * groups + 1, steps, dtype=torch.float32, device=device)
         self.stats: ProbeStats | None = None  # the last step's, kept by probe_evaluate
-
-    @property
-    def steps(self) -> int:
-        return self.buffer.shape[1]
 
     @property
     def hit(self) -> Tensor:
@@ -346,36 +324,20 @@ class ProbeTable:
         ForecastSkill.table_add(planes, context, None, self.buffer, frames)
         return self
 
-    def add(self, other: ProbeTable) -> ProbeTable:
-        if tuple(other.buffer.shape) != tuple(self.buffer.shape):
-            msg = f"tables of {tuple(self.buffer.shape)} and {tuple(other.buffer.shape)} do not add"
-            raise ValueError(msg)
-        self.buffer += other.buffer.to(self.buffer.device)
-        return self
-
-    def all_reduce(self, group=None) -> ProbeTable:  # noqa: ANN001
-        """One SUM all-reduce of the buffer (counts stay exact below 2^24 frames per bin); a no-op without a process group."""
-        import torch.distributed as dist  # noqa: PLC0415
-
-        if dist.is_available() and dist.is_initialized():
-            dist.all_reduce(self.buffer, op=dist.ReduceOp.SUM, group=group)
-        return self
+    def _sizes(self, other: SumTable) -> str:
+        return f"{tuple(self.buffer.shape)} and {tuple(other.buffer.shape)}"
 
     def curves(self) -> dict[str, dict[str, Tensor]]:
         """``{subset: {"acc", "nll"}}``, ``[T]`` each: the mean over the labelled frames at position ``t``; an empty bin gives NaN."""
-        counts = self.counts
-        nan = torch.full_like(counts, float("nan"))
-        return {name: {"acc": torch.where(counts > 0, self.hit[i] / counts, nan), "nll": torch.where(counts > 0, self.nll[i] / counts, nan)}
-                for i, name in enumerate(self.observe)}
+        return {name: {"acc": self._mean(self.hit[i], self.counts), "nll": self._mean(self.nll[i], self.counts)} for i, name in enumerate(self.observe)}
 
     def scalars(self, prefix: str) -> dict[str, Tensor]:
         """``prefix/{both,audio,vision}/{acc,nll}``: summed rows over the summed counts; NaN for an empty table."""
         total = self.counts.sum()
-        nan = torch.full_like(total, float("nan"))
         out = {}
         for i, name in enumerate(self.observe):
-            out[f"{prefix}/{name}/acc"] = torch.where(total > 0, self.hit[i].sum() / total, nan)
-            out[f"{prefix}/{name}/nll"] = torch.where(total > 0, self.nll[i].sum() / total, nan)
+            out[f"{prefix}/{name}/acc"] = self._mean(self.hit[i].sum(), total)
+            out[f"{prefix}/{name}/nll"] = self._mean(self.nll[i].sum(), total)
         return out
 
 

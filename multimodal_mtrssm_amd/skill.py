@@ -21,6 +21,7 @@ kernels, used for GPU tensors; elsewhere the torch rule runs.
 from __future__ import annotations
 
 import copy
+import functools
 from typing import NamedTuple
 
 import torch
@@ -45,7 +46,100 @@ class SkillPlanes(NamedTuple):
     se_samples: Tensor | None
 
 
-class ForecastSkill:
+class ObservingConfig:
+    """What the evaluation configs that decide what the model observes share (``ForecastSkill``, ``LikelihoodBound``, ``LatentProbe``,
+    ``EpisodePanel``): the modality code of ``observe``, its device tensors, the binding to a process group and the uniforms of a step.
+    A subclass sets ``observe`` and ``group`` and states the copies of a row in ``plan`` (``evaluation.CopyPlan``)."""
+
+    observe: str | tuple[str, ...]
+    group = None  # the process group the config's table is all-reduced over (FlatDataParallel binds it)
+
+    @property
+    def bits(self) -> int | tuple[int, ...]:
+        """The scans' modality code of an observed step: bit 0 audio, bit 1 vision (a tuple of ``observe``: one code per copy of a row)."""
+        return OBSERVE_BITS[self.observe] if isinstance(self.observe, str) else tuple(OBSERVE_BITS[o] for o in self.observe)
+
+    def observed(self, device: torch.device) -> Tensor:
+        """Bool ``[2]`` (audio, vision) on ``device``: what an observed step sees (``[G, 2]`` for per-copy ``bits``); made once per device."""
+        bits = self.bits
+        if isinstance(bits, tuple):
+            return observed_bits(bits, torch.device(device))[1]
+        return observed_bits((bits,), torch.device(device))[1][0]
+
+    def for_group(self, group):  # noqa: ANN001, ANN201
+        """A copy bound to ``group`` (``FlatDataParallel.skill`` / ``.likelihood`` / ``.probe`` call this)."""
+        bound = copy.copy(self)
+        bound.group = group
+        return bound
+
+    def noise_shapes(self, model, batch: int, steps: int) -> dict[str, tuple[int, ...]]:  # noqa: ANN001
+        """The uniforms of one step, batch dimension first (``GlobalRowNoise`` shards them as they are): what ``plan`` says of the
+        copies of a row -- shared ``(B, K)`` / ``(B, T, K)``, own ``(B, S, K)`` / ``(B, S, T, K)``, or shared on the context with own tails
+        ``u_tail (B, S, T, K)`` (MMTRSSM: the ``_l`` / ``_h`` pairs); row ``(b, s)`` is scan row ``b * S + s``."""
+        return self.plan().noise_shapes(model, batch, steps)
+
+
+@functools.lru_cache(maxsize=None)
+def observed_bits(bits: tuple[int, ...], device: torch.device) -> tuple[Tensor, Tensor]:
+    """``(int32 [G], bool [G, 2])`` on ``device`` for the modality codes ``bits``: the codes and what each sees (audio, vision).  Made
+    once per device; never written to."""
+    return (torch.tensor(bits, dtype=torch.int32, device=device), torch.tensor([[bool(b & 1), bool(b & 2)] for b in bits], device=device))
+
+
+class SumTable:
+    """What the evaluation tables share: ONE fp32 ``buffer`` of sums and counts (so that one all-reduce, one ``add`` and one state entry
+    carry a table), ``steps`` in its last dimension, the NaN-on-empty division and the horizon bins."""
+
+    buffer: Tensor
+
+    @staticmethod
+    def _checked_steps(steps: int) -> int:
+        if steps < 1:
+            msg = f"need steps >= 1, got {steps}"
+            raise ValueError(msg)
+        return steps
+
+    @property
+    def steps(self) -> int:
+        return self.buffer.shape[-1]
+
+    def _sizes(self, other: SumTable) -> str:
+        return f"{self.steps} and {other.steps} steps"
+
+    def add(self, other):  # noqa: ANN001, ANN201
+        if tuple(other.buffer.shape) != tuple(self.buffer.shape):
+            msg = f"tables of {self._sizes(other)} do not add"
+            raise ValueError(msg)
+        self.buffer += other.buffer.to(self.buffer.device)
+        return self
+
+    def all_reduce(self, group=None):  # noqa: ANN001, ANN201
+        """One SUM all-reduce of the buffer (counts stay exact below 2^24 frames per bin); a no-op without a process group."""
+        import torch.distributed as dist  # noqa: PLC0415
+
+        if dist.is_available() and dist.is_initialized():
+            dist.all_reduce(self.buffer, op=dist.ReduceOp.SUM, group=group)
+        return self
+
+    @staticmethod
+    def _mean(sums: Tensor, counts: Tensor) -> Tensor:
+        """``sums / counts``, NaN where nothing was counted."""
+        return torch.where(counts > 0, sums / counts, float("nan"))
+
+    def _bin_slices(self, edges: tuple[int, ...]) -> list[tuple[str, slice]]:
+        """``(1, 2, 4, 8)`` names bin 0 ``obs`` and the horizons ``[1, 2) [2, 4) [4, 8) [8, T)`` ``h1 h2 h4 h8``."""
+        edges = tuple(int(e) for e in edges)
+        if not edges or edges[0] < 1 or any(a >= b for a, b in zip(edges, edges[1:])):  # noqa: RUF007
+            msg = f"edges must be ascending horizons >= 1, got {edges}"
+            raise ValueError(msg)
+        t = self.steps
+        out = [("obs", slice(0, 1))]
+        for lo, hi in zip(edges, (*edges[1:], t)):
+            out.append((f"h{lo}", slice(min(lo, t), min(max(hi, lo), t))))
+        return out
+
+
+class ForecastSkill(ObservingConfig):
     """``ForecastSkill(q, samples=S, observe=...)``: every row observes ``q >= 1`` frames (``observe``: of both modalities, of audio
     only or of vision only), then ``S`` (1 .. 16) sampled futures per row run open loop.  ``max_frames``: the decoders and the scorer
     run over chunks of whole rows (all ``S`` copies of a row together) of at most this many frames."""
@@ -63,49 +157,20 @@ class ForecastSkill:
         self.context, self.samples, self.observe = context, samples, observe
         self.max_frames = 4096
         self.group = None  # the process group SkillTable.all_reduce uses (FlatDataParallel.skill binds it)
-        self._observed: dict[torch.device, Tensor] = {}
 
     def __repr__(self) -> str:
         return f"ForecastSkill({self.context}, samples={self.samples}, observe={self.observe!r})"
 
-    @property
-    def bits(self) -> int:
-        """The scans' modality code of an observed step: bit 0 audio, bit 1 vision."""
-        return OBSERVE_BITS[self.observe]
+    def plan(self):  # noqa: ANN201
+        """``S`` copies of a row observe ``q`` frames of ``observe``; they share the row's initial uniforms and ``u_post`` on the context and
+        read their own ``u_tail[b, s]`` after it."""
+        from multimodal_mtrssm_amd.evaluation import CopyPlan  # noqa: PLC0415  (evaluation imports this module)
 
-    def observed(self, device: torch.device) -> Tensor:
-        """Bool ``[2]`` (audio, vision) on ``device``: what an observed step sees; made once per device."""
-        device = torch.device(device)
-        if device not in self._observed:
-            self._observed[device] = torch.tensor([bool(self.bits & 1), bool(self.bits & 2)], device=device)
-        return self._observed[device]
-
-    def for_group(self, group) -> ForecastSkill:  # noqa: ANN001
-        """A copy whose table is all-reduced over ``group`` (``FlatDataParallel.skill`` calls this)."""
-        bound = copy.copy(self)
-        bound.group = group
-        return bound
-
-    def noise_shapes(self, model, batch: int, steps: int) -> dict[str, tuple[int, ...]]:  # noqa: ANN001
-        """The uniforms of one skill step, batch dimension first (``GlobalRowNoise`` shards them as they are): the initial state's, the
-        context's ``u_post (B, T, K)`` shared by a row's copies and the tails' ``u_tail (B, S, T, K)`` (MMTRSSM: the ``_l`` / ``_h`` pairs)."""
-        s = self.samples
-        if hasattr(model, "l_dist"):
-            kl, kh = model.l_dist.category_size, model.h_dist.category_size
-            return {"u_init_h": (batch, kh), "u_init_l": (batch, kl), "u_post_l": (batch, steps, kl), "u_post_h": (batch, steps, kh),
-                    "u_tail_l": (batch, s, steps, kl), "u_tail_h": (batch, s, steps, kh)}
-        k = model.transition.distribution_factory.category_size
-        return {"u_init": (batch, k), "u_post": (batch, steps, k), "u_tail": (batch, s, steps, k)}
+        return CopyPlan(self.samples, self.bits, self.context, post="tail")
 
     def compose_noise(self, u_post: Tensor, u_tail: Tensor) -> Tensor:
         """``[B * S, T, K]``: row ``b * S + s`` reads ``u_post[b, t]`` on ``t < q`` and ``u_tail[b, s, t]`` from ``q`` on."""
-        b, t, k = u_post.shape
-        s = self.samples
-        if tuple(u_tail.shape) != (b, s, t, k):
-            msg = f"the tail uniforms must have shape {(b, s, t, k)}, got {tuple(u_tail.shape)}"
-            raise ValueError(msg)
-        q = min(self.context, t)
-        return torch.cat([u_post[:, None, :q].expand(b, s, q, k), u_tail[:, :, q:]], dim=2).reshape(b * s, t, k).contiguous()
+        return self.plan().tail_uniforms("u_post", u_post, u_tail)
 
     # -- the rule in torch -----------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -225,24 +290,17 @@ class ForecastSkill:
                                                     _lib.ptr(counts), _lib.stream_ptr(planes.device)), "mtrssm_horizon_table")
 
 
-class SkillTable:
-    """The accumulated skill of any number of skill steps in ONE fp32 buffer ``[2 * 4 + 1, T]``: audio then vision x (mean, ens, best,
-    spread), then the counts.  A step run with ``keep_states`` also leaves its score planes (``planes``, ``[8, B, T]``) and its rollout
-    (``states``) here; otherwise both are None and the table holds nothing of a batch."""
+class PlaneTable(SumTable):
+    """A ``SumTable`` of ``ROWS`` summed planes and, behind them, the counts of the frames they were summed over: ``[ROWS + 1, T]``.  A
+    step run with ``keep_states`` also leaves its planes (``planes``, ``[8, B, T]``) and its rollout (``states``) here; otherwise both
+    are None and the table holds nothing of a batch."""
 
-    ROWS = len(MODALITIES) * len(SCORES)
+    ROWS: int
 
     def __init__(self, steps: int, device: torch.device | str = "cpu") -> None:
-        if steps < 1:
-            msg = f"need steps >= 1, got {steps}"
-            raise ValueError(msg)
-        self.buffer = torch.zeros(self.ROWS + 1, steps, dtype=torch.float32, device=device)
+        self.buffer = torch.zeros(self.ROWS + 1, self._checked_steps(steps), dtype=torch.float32, device=device)
         self.planes: Tensor | None = None
         self.states = None
-
-    @property
-    def steps(self) -> int:
-        return self.buffer.shape[1]
 
     @property
     def sums(self) -> Tensor:
@@ -252,52 +310,30 @@ class SkillTable:
     def counts(self) -> Tensor:
         return self.buffer[self.ROWS]
 
-    def add(self, other: SkillTable) -> SkillTable:
-        if tuple(other.buffer.shape) != tuple(self.buffer.shape):
-            msg = f"tables of {self.steps} and {other.steps} steps do not add"
-            raise ValueError(msg)
-        self.buffer += other.buffer.to(self.buffer.device)
-        return self
 
-    def all_reduce(self, group=None) -> SkillTable:  # noqa: ANN001
-        """One SUM all-reduce of the buffer (counts stay exact below 2^24 frames per bin); a no-op without a process group."""
-        import torch.distributed as dist  # noqa: PLC0415
+class SkillTable(PlaneTable):
+    """The accumulated skill of any number of skill steps in ONE fp32 buffer ``[2 * 4 + 1, T]``: audio then vision x (mean, ens, best,
+    spread), then the counts."""
 
-        if dist.is_available() and dist.is_initialized():
-            dist.all_reduce(self.buffer, op=dist.ReduceOp.SUM, group=group)
-        return self
+    ROWS = len(MODALITIES) * len(SCORES)
 
     def curves(self) -> dict[str, dict[str, Tensor]]:
         """``sums / counts`` per modality and score, ``[T]`` each; an empty bin gives NaN."""
-        counts = self.counts
-        nan = torch.full_like(counts, float("nan"))
         rows = iter(self.sums)
-        return {m: {k: torch.where(counts > 0, next(rows) / counts, nan) for k in SCORES} for m in MODALITIES}
-
-    def _bin_slices(self, edges: tuple[int, ...]) -> list[tuple[str, slice]]:
-        edges = tuple(int(e) for e in edges)
-        if not edges or edges[0] < 1 or any(a >= b for a, b in zip(edges, edges[1:])):  # noqa: RUF007
-            msg = f"edges must be ascending horizons >= 1, got {edges}"
-            raise ValueError(msg)
-        t = self.steps
-        out = [("obs", slice(0, 1))]
-        for lo, hi in zip(edges, (*edges[1:], t)):
-            out.append((f"h{lo}", slice(min(lo, t), min(max(hi, lo), t))))
-        return out
+        return {m: {k: self._mean(next(rows), self.counts) for k in SCORES} for m in MODALITIES}
 
     def binned(self, edges: tuple[int, ...] = (1, 2, 4, 8)) -> dict[str, dict[str, Tensor]]:
         """The curves over horizon bins: ``(1, 2, 4, 8)`` gives bin 0 and ``[1, 2) [2, 4) [4, 8) [8, T)`` -- each the bin's summed scores
         over its summed counts (NaN for a bin without frames)."""
         slices = self._bin_slices(edges)
         counts = torch.stack([self.counts[s].sum() for _, s in slices])
-        nan = torch.full_like(counts, float("nan"))
         rows = iter(self.sums)
         out: dict[str, dict[str, Tensor]] = {}
         for m in MODALITIES:
             out[m] = {}
             for k in SCORES:
                 row = next(rows)
-                out[m][k] = torch.where(counts > 0, torch.stack([row[s].sum() for _, s in slices]) / counts, nan)
+                out[m][k] = self._mean(torch.stack([row[s].sum() for _, s in slices]), counts)
         return out
 
     def scalars(self, prefix: str, edges: tuple[int, ...] = (1, 2, 4, 8)) -> dict[str, Tensor]:
@@ -307,4 +343,4 @@ class SkillTable:
         return {f"{prefix}/{m}/{k}/{n}": binned[m][k][i] for m in MODALITIES for k in SCORES for i, n in enumerate(names)}
 
 
-__all__ = ["ForecastSkill", "SkillPlanes", "SkillTable"]
+__all__ = ["ForecastSkill", "ObservingConfig", "PlaneTable", "SkillPlanes", "SkillTable", "SumTable", "observed_bits"]

@@ -26,6 +26,7 @@ The host functions restate the evaluation's bookkeeping on label sequences (``tr
 
 from __future__ import annotations
 
+import dataclasses
 from collections.abc import Iterable, Sequence
 
 import numpy as np
@@ -33,7 +34,7 @@ import torch
 from torch import Tensor
 
 from multimodal_mtrssm_amd.digits import CLASSES
-from multimodal_mtrssm_amd.skill import MAX_SAMPLES, ForecastSkill
+from multimodal_mtrssm_amd.skill import MAX_SAMPLES, ForecastSkill, SumTable
 
 WORDS = tuple(range(CLASSES))
 BINS = CLASSES + 1          # the ten words and "wf", the failure bin
@@ -77,29 +78,25 @@ class WordTransitions:
             raise ValueError(msg)
         return t
 
+    def plan(self):  # noqa: ANN201
+        """The skill's plan (context protocol); reference protocol: its copies with no posterior uniforms, each reads its own
+        ``u_prior[b, s]`` ``(B, S, 1, K)`` for the one prior step."""
+        plan = self.skill.plan()
+        return plan if self.protocol == "context" else dataclasses.replace(plan, post="prior")
+
     def noise_shapes(self, model, batch: int, steps: int) -> dict[str, tuple[int, ...]]:  # noqa: ANN001
         """The uniforms of one step, batch dimension first.  Context protocol: ``ForecastSkill.noise_shapes``.  Reference protocol: the
         initial state's and ``u_prior (B, S, 1, K)`` (MMTRSSM: the ``_l`` / ``_h`` pairs)."""
-        if self.protocol == "context":
-            return self.skill.noise_shapes(model, batch, steps)
-        s = self.samples
-        if hasattr(model, "l_dist"):
-            kl, kh = model.l_dist.category_size, model.h_dist.category_size
-            return {"u_init_h": (batch, kh), "u_init_l": (batch, kl), "u_prior_l": (batch, s, 1, kl), "u_prior_h": (batch, s, 1, kh)}
-        k = model.transition.distribution_factory.category_size
-        return {"u_init": (batch, k), "u_prior": (batch, s, 1, k)}
+        return self.plan().noise_shapes(model, batch, steps)
 
 
-class TransitionTable:
+class TransitionTable(SumTable):
     """The accumulated counts of any number of transition steps in ONE fp32 buffer: ``q_counts [10, 11]`` (row = current word,
     column = digit read, column 10 = "wf") and, behind it, ``horizon [2 + 1, T]``: the by-horizon sums of ``hit`` and ``any`` and the
     live (labelled) frames per horizon bin (zeros unless a step ran ``by_horizon``)."""
 
     def __init__(self, steps: int = 1, device: torch.device | str = "cpu") -> None:
-        if steps < 1:
-            msg = f"need steps >= 1, got {steps}"
-            raise ValueError(msg)
-        self.buffer = torch.zeros(CLASSES * BINS + _HORIZON_ROWS * steps, dtype=torch.float32, device=device)
+        self.buffer = torch.zeros(CLASSES * BINS + _HORIZON_ROWS * self._checked_steps(steps), dtype=torch.float32, device=device)
 
     @property
     def steps(self) -> int:
@@ -113,21 +110,6 @@ class TransitionTable:
     def horizon(self) -> Tensor:
         return self.buffer[CLASSES * BINS :].view(_HORIZON_ROWS, self.steps)
 
-    def add(self, other: TransitionTable) -> TransitionTable:
-        if tuple(other.buffer.shape) != tuple(self.buffer.shape):
-            msg = f"tables of {self.steps} and {other.steps} steps do not add"
-            raise ValueError(msg)
-        self.buffer += other.buffer.to(self.buffer.device)
-        return self
-
-    def all_reduce(self, group=None) -> TransitionTable:  # noqa: ANN001
-        """One SUM all-reduce of the buffer (whole numbers below 2^24 stay exact); a no-op without a process group."""
-        import torch.distributed as dist  # noqa: PLC0415
-
-        if dist.is_available() and dist.is_initialized():
-            dist.all_reduce(self.buffer, op=dist.ReduceOp.SUM, group=group)
-        return self
-
     def q_distribution(self, word: int) -> dict[int | str, float]:
         """``q(w | word)`` with the key ``"wf"`` for the failure bin; all zeros when nothing was counted."""
         row = self.q_counts[word].double().cpu()
@@ -138,23 +120,16 @@ class TransitionTable:
     def accuracy(self) -> dict[str, Tensor]:
         """``hit`` and ``any`` per horizon bin (``[T]`` each: sums over the live frames; NaN for a bin without one) and ``count``."""
         hit, any_, live = self.horizon
-        nan = torch.full_like(live, float("nan"))
-        return {"hit": torch.where(live > 0, hit / live, nan), "any": torch.where(live > 0, any_ / live, nan), "count": live}
+        return {"hit": self._mean(hit, live), "any": self._mean(any_, live), "count": live}
 
     def scalars(self, prefix: str, edges: tuple[int, ...] = (1, 2, 4, 8)) -> dict[str, Tensor]:
         """``prefix/{hit,any}/{obs,h1,h2,...}`` over ``SkillTable``'s horizon bins, and ``prefix/reads`` = the futures counted."""
-        edges = tuple(int(e) for e in edges)
-        if not edges or edges[0] < 1 or any(a >= b for a, b in zip(edges, edges[1:])):  # noqa: RUF007
-            msg = f"edges must be ascending horizons >= 1, got {edges}"
-            raise ValueError(msg)
-        t = self.steps
-        slices = [("obs", slice(0, 1))] + [(f"h{lo}", slice(min(lo, t), min(max(hi, lo), t))) for lo, hi in zip(edges, (*edges[1:], t))]
+        slices = self._bin_slices(edges)
         hit, any_, live = self.horizon
         out = {f"{prefix}/reads": self.q_counts.sum()}
         for name, row in (("hit", hit), ("any", any_)):
             for label, s in slices:
-                n = live[s].sum()
-                out[f"{prefix}/{name}/{label}"] = torch.where(n > 0, row[s].sum() / n, torch.full_like(n, float("nan")))
+                out[f"{prefix}/{name}/{label}"] = self._mean(row[s].sum(), live[s].sum())
         return out
 
 
