@@ -1090,6 +1090,53 @@ int mtrssm_adamw_apply(float* param, const float* grad, float* exp_avg, float* e
                        float beta2, float eps, float weight_decay, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The fit loop's per-step fold (no reference counterpart: Lightning's on_epoch=True logging and its gradient
+ * norm callbacks read scalars back per step).  Called once after every train step, behind the optimizer (which leaves the reduced,
+ * unclipped gradient in place), on the caller's stream; two launches, no atomics, nothing allocated.
+ *   grad, param: the flat fp32 buffers, numel floats each (numel a multiple of 4), 16-byte aligned.
+ *   offsets: G + 1 ascending DEVICE int64 offsets, multiples of 4, offsets[0] = 0, offsets[G] = numel: G <= 32 segments.
+ *   group: G DEVICE int32 (NULL: group[s] = s): the first segment of the name segment s belongs to (group[s] <= s,
+ *     group[group[s]] = group[s]); the norms of a name are the roots of the summed squares of its segments, kept at its first one.
+ *   scalars: K <= 8 DEVICE floats (the all-reduced loss scalars of the gradient buffer's tail), each times scalar_scale (1 / world).
+ *   weight: ONE device float, the step's weight (global batch rows).  The step's index is flags[MTRSSM_FIT_FLAG_STEP], which every
+ *     call advances by one: the caller writes it when an epoch begins or a run resumes, and no by-value argument changes per step.
+ * Per segment: sum(g^2), sum(p^2) -- every product and sum in double -- and the count of non-finite gradient elements.  A
+ * workgroup sums one chunk (mtrssm_fit_fold_workspace_bytes reports its floats) of one segment; chunk sums meet in an order fixed by
+ * numel and offsets alone: two calls on the same buffers are bitwise equal.  The call leaves them in the workspace's first
+ * 3 x 32 doubles: [0][s] sum(g^2), [1][s] sum(p^2), [2][s] the count.
+ * A step is FINITE when every scalar and every gradient element is.  acc (doubles) then gains, with norm(x) = sqrt(sum x^2):
+ *   [MTRSSM_FIT_ACC_WEIGHT] += w;  [_STEPS] += 1;  [_CLIPPED] += (norm(g) grad_scale > clip_norm > 0);
+ *   [_GRAD_SUM] += norm(g) grad_scale;  [_GRAD_MAX] = max(., norm(g) grad_scale);  [_PARAM] = norm(p)          (all segments)
+ *   [_SCALARS + k] += w * scalars[k] * scalar_scale                                                            (k < K)
+ *   [_SEGMENTS + 3 s + 0 / 1 / 2]: the same sum / max / last norm(p) of the name whose first segment is s       (s < G)
+ * Otherwise acc stays as it was, bit for bit, and flags (int32) record the step: [_BAD_STEPS] += 1, [_FIRST_BAD] = the step's index
+ * if it is the first, [_BAD_SEGMENTS] |= bit s of every segment with a non-finite gradient element, [_BAD_SCALARS] |= bit k.
+ * The caller zeroes both blocks (first bad step: -1) when an epoch begins; MTRSSM_FIT_ACC_DOUBLES / MTRSSM_FIT_FLAG_INTS are their sizes.
+ * ------------------------------------------------------------------------------------------ */
+#define MTRSSM_FIT_MAX_SEGMENTS 32
+#define MTRSSM_FIT_MAX_SCALARS 8
+#define MTRSSM_FIT_ACC_WEIGHT 0
+#define MTRSSM_FIT_ACC_STEPS 1
+#define MTRSSM_FIT_ACC_CLIPPED 2
+#define MTRSSM_FIT_ACC_GRAD_SUM 3
+#define MTRSSM_FIT_ACC_GRAD_MAX 4
+#define MTRSSM_FIT_ACC_PARAM 5
+#define MTRSSM_FIT_ACC_SCALARS 6
+#define MTRSSM_FIT_ACC_SEGMENTS 14
+#define MTRSSM_FIT_ACC_DOUBLES 110
+#define MTRSSM_FIT_FLAG_BAD_STEPS 0
+#define MTRSSM_FIT_FLAG_FIRST_BAD 1
+#define MTRSSM_FIT_FLAG_BAD_SEGMENTS 2
+#define MTRSSM_FIT_FLAG_BAD_SCALARS 3
+#define MTRSSM_FIT_FLAG_STEP 4
+#define MTRSSM_FIT_FLAG_INTS 8
+/* Bytes of the caller-owned workspace (-1: numel or G out of range); *chunk_floats (may be NULL) receives the floats of a chunk. */
+int64_t mtrssm_fit_fold_workspace_bytes(int64_t numel, int32_t G, int64_t* chunk_floats);
+int mtrssm_fit_fold(const float* grad, const float* param, int64_t numel, const int64_t* offsets, const int32_t* group, int32_t G,
+                    const float* scalars, int32_t K, float scalar_scale, float grad_scale, float clip_norm, const float* weight,
+                    double* acc, int32_t* flags, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Dense fp32 GEMM on the fp32 MFMA with the elementwise neighbours fused in.  Replaces the nn.Linear / MLP calls around
  * the recurrence and their autograd (torchrl MLP at networks.py:57-64,130-145; cnn's Linear layers; init_proj,
  * core.py:132-133) and the weight gradients of the scan:

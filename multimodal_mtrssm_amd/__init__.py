@@ -23,6 +23,7 @@ from multimodal_mtrssm_amd.distributions import (
 )
 from multimodal_mtrssm_amd.dropout import ModalityDropout
 from multimodal_mtrssm_amd.experts import ExpertWeights
+from multimodal_mtrssm_amd.fit import EarlyStopping, EpochMetrics, Trainer
 from multimodal_mtrssm_amd.forecast import Forecast
 from multimodal_mtrssm_amd.factory import make_mmtrssm, make_mrssm
 from multimodal_mtrssm_amd.likelihood import LikelihoodBound, LikelihoodTable
@@ -43,5 +44,5 @@ __all__ = [
     "MLP", "MTRNN", "Decoder", "DeviceEpisodeLoader", "DigitClassifier", "DigitStats", "DigitTrainer", "Distribution", "Encoder", "EpisodeBatch", "EpisodeDataModule", "ElboSchedule", "EpisodeDataModuleConfig", "EpisodePanel", "EpisodePanelLogger", "EpisodeVideo", "ExpertWeights", "FlatAdamW", "FlatDataParallel", "Forecast", "ForecastSkill", "GlobalRowNoise", "LatentProbe", "LikelihoodBound", "LikelihoodTable", "LinearProbe", "MTState", "MoPoE_MMTRSSM",
     "MoPoE_MRSSM", "ModalityDropout", "MultiOneHot", "MultiOneHotFactory", "ProbeStats", "ProbeTable", "ReduceLROnPlateau", "Representation", "SkillTable", "State", "StateCarry", "Transition", "TransitionTable", "WeightedMoPoE_MMTRSSM", "WeightedMoPoE_MRSSM", "WordTransitions", "cat_distribution",
     "cat_mtstates", "cat_states", "inject_uniforms", "kl_divergence", "likelihood", "load_reference_checkpoint", "make_mmtrssm", "make_mrssm",
-    "stack_distribution", "stack_mtstates", "stack_states", "dropout_mask_reference", "tape_reference",
+    "stack_distribution", "stack_mtstates", "stack_states", "dropout_mask_reference", "tape_reference", "EarlyStopping", "EpochMetrics", "Trainer",
 ]

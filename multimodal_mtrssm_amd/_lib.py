@@ -212,6 +212,8 @@ SYMBOLS: dict[str, tuple[type | None, list[type]]] = {
     "mtrssm_clear": (C.c_int, [_p, C.c_int64, _p]),
     "mtrssm_adamw_prepare": (C.c_int, [_p, C.c_int64, _p, _p, _p, _f, _f, _p]),
     "mtrssm_adamw_apply": (C.c_int, [_p, _p, _p, _p, _p, C.c_int64, _p, _p, _p, _f, _f, _f, _f, _f, _f, _p]),
+    "mtrssm_fit_fold_workspace_bytes": (C.c_int64, [C.c_int64, _i, C.POINTER(C.c_int64)]),
+    "mtrssm_fit_fold": (C.c_int, [_p, _p, C.c_int64, _p, _p, _i, _p, _i, _f, _f, _f, _p, _p, _p, _p, C.c_int64, _p]),
 }
 
 _LIB: C.CDLL | None = None

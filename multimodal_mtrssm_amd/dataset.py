@@ -560,7 +560,17 @@ class DeviceEpisodeLoader:
             yield rows
 
     def __iter__(self) -> Iterator[tuple[Tensor, ...]]:
-        for rows, start, reset, valid_global, row0 in self.schedule_ragged():
+        return self.batches(0)
+
+    def batches(self, skip: int = 0) -> Iterator[tuple[Tensor, ...]]:
+        """The current epoch's batches from entry ``skip`` of its schedule on: the first ``skip`` entries are walked on the host and
+        nothing of them is gathered (a run resumed mid-epoch, ``fit.Trainer``).  ``batches(0)`` is ``__iter__``."""
+        if isinstance(skip, bool) or not isinstance(skip, int) or skip < 0:
+            msg = f"skip must be an integer >= 0, got {skip!r}"
+            raise ValueError(msg)
+        for k, (rows, start, reset, valid_global, row0) in enumerate(self.schedule_ragged()):
+            if k < skip:
+                continue
             if start is None:
                 yield self.batch(rows)
             elif valid_global is None:
