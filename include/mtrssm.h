@@ -944,6 +944,37 @@ int mtrssm_latent_log_ratio(const float* post_logits, const float* prior_logits,
 int mtrssm_iw_bound(const float* se_audio, const float* se_vision, const float* log_ratio, const int32_t* valid, int64_t B, int64_t S,
                     int64_t T, int64_t event_audio, int64_t event_vision, float* planes, void* stream);
 
+/* Particle-filter likelihood: the bound of mtrssm_iw_bound weighted per frame, with the particles resampled
+ * between time segments.  Row b has S particles (1 .. 16); a call folds ONE segment of c frames, the frames t0 .. t0 + c - 1.
+ * mtrssm_particle_fold: se_audio / se_vision / log_ratio [B][S][c] as in mtrssm_iw_bound (each may be NULL, not all three); valid [B]
+ *   int32 in DEVICE memory (NULL: every frame is live; frame t is live iff t < valid[b]); carry [B][S + 2] double in DEVICE memory,
+ *   read and written: lw[0 .. S), base, prev (all zero before a row's first segment).  On a live frame, per particle s:
+ *     l = (a + v) + r as in mtrssm_iw_bound;  lw[s] += l;  top = max_s lw;  w_s = exp(lw_s - top);
+ *     L = base + (top + log sum_s w_s) - log S
+ *   and into planes [8][B][c], each exactly 0 on a dead frame:
+ *     0 smc = L - prev (then prev = L);  1 mean = (sum_s l) / S;  2, 3, 4 audio, vision, latent as in mtrssm_iw_bound;
+ *     5 ess = (sum_s w)^2 / sum_s w^2;  6 resampled = 1 when the particles were resampled after this frame;  7 smc_prefix = L
+ *   Resampling is considered at the segment's last frame t = t0 + c - 1 only, and only with last_segment = 0: it happens iff t is live,
+ *   t + 1 < valid[b] and ess <= threshold * S (0 <= threshold <= 1).  It is systematic with ONE uniform u[b * u_stride] (fp32, DEVICE
+ *   memory; not read with last_segment = 1): c_s the prefix sums of w in ascending s, target_i = ((u + i) / S) * c_{S-1},
+ *   ancestor[b][i] = min(S - 1, #{s : c_s <= target_i}); then base = L and lw[:] = 0.  Otherwise ancestor[b][i] = i.
+ *   ancestor [B][S] int32 is written by every call.  The max and the sums over s are the double butterflies of mtrssm_iw_bound, the
+ *   prefix sums a walk in lane order (a left fold); every plane is rounded to fp32 once; no atomics; a row's result depends on that
+ *   row only and two calls agree bitwise.
+ *   Null carry / planes / ancestor, all three inputs NULL, a NULL u or u_stride < 1 with last_segment = 0, B or c <= 0, t0 < 0, an
+ *   event size <= 0 of a given data term, S outside 1 .. 16, a threshold outside [0, 1], last_segment outside {0, 1} or
+ *   B * c >= 2^24 return -1 without a launch.
+ * mtrssm_particle_gather: one launch for all tensors of a state (entries as in mtrssm_state_save: src[k] [B * S][steps][width[k]]
+ *   contiguous, dst[k] [B * S][width[k]]; src_stride and alt are ignored):
+ *     dst[k][b * S + i, :] = src[k][b * S + ancestor[b][i], steps - 1, :]
+ *   (an ancestor outside 0 .. S - 1 is clamped into it).  16 bytes per lane where width[k] % 4 == 0 and both rows are 16-byte
+ *   aligned, else 4.  A null table or ancestor, count outside 1 .. MTRSSM_STATE_MAX, B or steps <= 0, S outside 1 .. 16, a null or
+ *   misaligned entry, src[k] == dst[k] or B * S * steps * width >= 2^31 return -1 without a launch. */
+int mtrssm_particle_fold(const float* se_audio, const float* se_vision, const float* log_ratio, const int32_t* valid, const float* u,
+                         int64_t u_stride, int64_t t0, int64_t B, int64_t S, int64_t c, int64_t event_audio, int64_t event_vision,
+                         double threshold, int32_t last_segment, double* carry, float* planes, int32_t* ancestor, void* stream);
+int mtrssm_particle_gather(const MtrssmStateTable* table, const int32_t* ancestor, int64_t B, int64_t S, int64_t steps, void* stream);
+
 /* Linear word probes: one fused step of G multinomial-logistic classifiers over N feature rows.
  *   x [G][N][ld] fp32, of which columns [col0, col0 + F) are read; labels [N] int32 in DEVICE memory, shared by the groups: frame n is
  *   live iff 0 <= labels[n] < C (-1 = silence, a frame past its row's end); weight [G][C][F], bias [G][C].  Per group g and live frame n:

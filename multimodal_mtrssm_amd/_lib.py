@@ -178,6 +178,9 @@ SYMBOLS: dict[str, tuple[type | None, list[type]]] = {
     "mtrssm_horizon_table": (C.c_int, [_p, C.c_int64, _p, _p, C.c_int64, C.c_int64, _p, _p, _p]),
     "mtrssm_latent_log_ratio": (C.c_int, [_p, _p, _p, C.c_int64, C.c_int64, C.c_int64, _i, _p, _p]),
     "mtrssm_iw_bound": (C.c_int, [_p, _p, _p, _p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _p, _p]),
+    "mtrssm_particle_fold": (C.c_int, [_p, _p, _p, _p, _p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_double, _i,
+                                       _p, _p, _p, _p]),
+    "mtrssm_particle_gather": (C.c_int, [C.POINTER(StateTable), _p, C.c_int64, C.c_int64, C.c_int64, _p]),
     "mtrssm_linear_probe_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "mtrssm_linear_probe_step": (C.c_int, [_p, C.c_int64, C.c_int64, _p, _p, _p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _i, _p, _p, _p, _p, _p, _p,
                                            _p, C.c_int64, _p]),

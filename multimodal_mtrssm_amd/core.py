@@ -30,6 +30,7 @@ from multimodal_mtrssm_amd.forecast import Forecast
 from multimodal_mtrssm_amd.likelihood import LikelihoodBound, LikelihoodTable
 from multimodal_mtrssm_amd.networks import MTRNN, Representation, Transition
 from multimodal_mtrssm_amd.objective import likelihood
+from multimodal_mtrssm_amd.particle import ParticleFilter, ParticleTable
 from multimodal_mtrssm_amd.schedule import ElboSchedule, ElboTerms
 from multimodal_mtrssm_amd.skill import ForecastSkill, SkillTable
 from multimodal_mtrssm_amd.state import MTState, State
@@ -496,6 +497,8 @@ class MoPoE_MRSSM(_Evaluators, _Base):  # noqa: N801
         self.skill_table: SkillTable | None = None  # ... logged as val/skill/* and cleared by on_validation_epoch_end
         self.val_likelihood: LikelihoodBound | None = None  # validation_step adds a likelihood step into self.likelihood_table
         self.likelihood_table: LikelihoodTable | None = None  # ... logged as val/loglik/* and cleared by on_validation_epoch_end
+        self.val_particle: ParticleFilter | None = None  # validation_step adds a particle-filter step into self.particle_table
+        self.particle_table: ParticleTable | None = None  # ... logged as val/smc/* and cleared by on_validation_epoch_end
         # weighted MoPoE: assign an ExpertWeights (a submodule: before FlatParameters is built); None = 1/3 each, no new
         # state-dict keys.  After every posterior rollout with weights, weights_timeseries is ExpertWeights.table(...) [B, T, 3]
         self.expert_weights: ExpertWeights | None = None
@@ -1077,12 +1080,15 @@ class MoPoE_MRSSM(_Evaluators, _Base):  # noqa: N801
             self.skill_table = self.forecast_skill(batch, self.val_skill, table=self.skill_table)
         if self.val_likelihood is not None:  # (last, for the same reason)
             self.likelihood_table = self.likelihood_bound(batch, self.val_likelihood, table=self.likelihood_table)
+        if self.val_particle is not None:  # (after the likelihood step: every draw above is what it is without it)
+            self.particle_table = self.particle_filter(batch, self.val_particle, table=self.particle_table)
         return logged
 
     def on_validation_epoch_end(self) -> dict[str, Tensor]:
         """Logs the epoch's ``val/skill/{audio,vision}/{mean,ens,best,spread}/{obs,h1,h2,h4,h8}`` and
-        ``val/loglik/{iw,elbo,audio,vision,latent,ess,gap}`` (each table all-reduced once when a process group is initialised; the group is
-        the one ``FlatDataParallel.skill`` / ``.likelihood`` bound) and clears the tables.  Without a table: nothing."""
+        ``val/loglik/{iw,elbo,audio,vision,latent,ess,gap}`` and ``val/smc/{smc,mean,audio,vision,latent,ess,resampled}`` (each table
+        all-reduced once when a process group is initialised; the group is the one ``FlatDataParallel.skill`` / ``.likelihood`` /
+        ``.particle`` bound) and clears the tables.  Without a table: nothing."""
         logged: dict[str, Tensor] = {}
         table, self.skill_table = self.skill_table, None
         if table is not None:
@@ -1092,6 +1098,10 @@ class MoPoE_MRSSM(_Evaluators, _Base):  # noqa: N801
         if loglik is not None:
             loglik.all_reduce(getattr(self.val_likelihood, "group", None))
             logged.update(loglik.scalars("val/loglik"))
+        smc, self.particle_table = self.particle_table, None
+        if smc is not None:
+            smc.all_reduce(getattr(self.val_particle, "group", None))
+            logged.update(smc.scalars("val/smc"))
         if logged:
             self.log_dict(logged, prog_bar=False, sync_dist=False, on_step=False, on_epoch=True)
         return logged

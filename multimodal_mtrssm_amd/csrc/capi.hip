@@ -90,6 +90,9 @@ int ensemble_score_launch(const float*, const float*, const int32_t*, int64_t, i
 int horizon_table_launch(const float*, int64_t, const int32_t*, const int32_t*, int64_t, int64_t, float*, float*, hipStream_t);
 int latent_log_ratio_launch(const float*, const float*, const float*, int64_t, int64_t, int64_t, int, float*, hipStream_t);
 int iw_bound_launch(const float*, const float*, const float*, const int32_t*, int64_t, int64_t, int64_t, int64_t, int64_t, float*, hipStream_t);
+int particle_fold_launch(const float*, const float*, const float*, const int32_t*, const float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+                         int64_t, double, int, double*, float*, int32_t*, hipStream_t);
+int particle_gather_launch(const MtrssmStateTable*, const int32_t*, int64_t, int64_t, int64_t, hipStream_t);
 int64_t linear_probe_workspace_bytes(int64_t, int64_t, int64_t, int64_t);
 int linear_probe_step_launch(const float*, int64_t, int64_t, const int32_t*, const float*, const float*, int64_t, int64_t, int64_t, int64_t, int, float*,
                              float*, float*, float*, float*, int32_t*, void*, int64_t, hipStream_t);
@@ -518,6 +521,15 @@ MTRSSM_API int mtrssm_latent_log_ratio(const float* post_logits, const float* pr
 MTRSSM_API int mtrssm_iw_bound(const float* se_audio, const float* se_vision, const float* log_ratio, const int32_t* valid, int64_t B, int64_t S,
                                int64_t T, int64_t event_audio, int64_t event_vision, float* planes, void* stream) {
   return iw_bound_launch(se_audio, se_vision, log_ratio, valid, B, S, T, event_audio, event_vision, planes, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_particle_fold(const float* se_audio, const float* se_vision, const float* log_ratio, const int32_t* valid, const float* u,
+                                    int64_t u_stride, int64_t t0, int64_t B, int64_t S, int64_t c, int64_t event_audio, int64_t event_vision,
+                                    double threshold, int32_t last_segment, double* carry, float* planes, int32_t* ancestor, void* stream) {
+  return particle_fold_launch(se_audio, se_vision, log_ratio, valid, u, u_stride, t0, B, S, c, event_audio, event_vision, threshold, last_segment,
+                              carry, planes, ancestor, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_particle_gather(const MtrssmStateTable* table, const int32_t* ancestor, int64_t B, int64_t S, int64_t steps, void* stream) {
+  return particle_gather_launch(table, ancestor, B, S, steps, static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int64_t mtrssm_linear_probe_workspace_bytes(int64_t G, int64_t N, int64_t C, int64_t F) {
   return linear_probe_workspace_bytes(G, N, C, F);

@@ -1,6 +1,7 @@
 // Held-out likelihood for gfx950: the latent log-ratio of the classes a sampled posterior took, and the
 // importance-weighted bound folded over time from S sampled trajectories per row.  Both kernels compute in double, reduce in a fixed
 // order without atomics and round every output to fp32 once, so their results are bitwise reproducible.
+#include "row_fold.h"
 #include "scan_common.h"
 
 namespace mtrssm {
@@ -111,30 +112,7 @@ __global__ __launch_bounds__(kThreads) void latent_log_ratio_long_kernel(const f
   }
 }
 
-// One DPP step of a double: both halves move through the same lane permutation.
-template <int CTRL>
-__device__ __forceinline__ double dpp_move_d(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
-  return __hiloint2double(hi, lo);
-}
-// Sum / max over a 16-lane DPP row (every lane of the row gets the result, bitwise the same: each step adds two values that
-// the partner lane adds in the other order).  All 64 lanes must be active.
-__device__ __forceinline__ double row_sum_d(double v) {
-  v += dpp_move_d<0xB1>(v);   // quad_perm [1, 0, 3, 2]
-  v += dpp_move_d<0x4E>(v);   // quad_perm [2, 3, 0, 1]
-  v += dpp_move_d<0x141>(v);  // row_half_mirror
-  v += dpp_move_d<0x140>(v);  // row_mirror
-  return v;
-}
-__device__ __forceinline__ double row_max_d(double v) {
-  v = fmax(v, dpp_move_d<0xB1>(v));
-  v = fmax(v, dpp_move_d<0x4E>(v));
-  v = fmax(v, dpp_move_d<0x141>(v));
-  v = fmax(v, dpp_move_d<0x140>(v));
-  return v;
-}
-
+// (the sums and the max over a 16-lane DPP row, row_sum_d / row_max_d, are in row_fold.h: mtrssm_particle_fold uses them too)
 // A 16-lane DPP row per batch row b (four per wave), lane s of it owns sample s and walks the frames serially, carrying
 // cum[b][s] in a register; the lanes s >= S carry the neutral element of every reduction.  No lane leaves before the end: the DPP
 // steps need the whole wave.  Lane 0 of a row writes the eight planes of a frame.

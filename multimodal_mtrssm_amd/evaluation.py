@@ -26,6 +26,8 @@ from multimodal_mtrssm_amd.forecast import Forecast
 from multimodal_mtrssm_amd.likelihood import PLANES as LIKELIHOOD_PLANES
 from multimodal_mtrssm_amd.likelihood import LikelihoodBound, LikelihoodTable
 from multimodal_mtrssm_amd.panel import EpisodePanel, EpisodeVideo
+from multimodal_mtrssm_amd.particle import PLANES as PARTICLE_PLANES
+from multimodal_mtrssm_amd.particle import ParticleFilter, ParticleTable
 from multimodal_mtrssm_amd.probe import LatentProbe, LinearProbe, ProbeTable, frame_labels
 from multimodal_mtrssm_amd.skill import ForecastSkill, SkillTable, observed_bits
 from multimodal_mtrssm_amd.words import TransitionTable, WordTransitions
@@ -217,13 +219,14 @@ class _Evaluators:
     def _spread_state(self, state, spread: Callable[[Tensor], Tensor]):  # noqa: ANN001, ANN202
         return self._state_like(state, {k: spread(getattr(state, k)) for k in self._FRESH_KEYS})
 
-    def _evaluation_rollout(self, batch: tuple[Tensor, ...], plan: CopyPlan, noise: Noise | None, lengths: Tensor | None,  # noqa: PLR0914
-                            expert_log_weights: Tensor | None) -> tuple[dict[str, Tensor], Tensor | None]:
-        """The rollout of every evaluation step: both encoders once, one ``Forecast.sample`` per distinct context of ``plan``, its
-        expansion, the initial state, the gate once per row and ONE masked posterior rollout over ``B * copies`` rows.  Returns the scan's
-        outputs -- with ``"codes"``, the rows' modality codes -- and the rows' lengths (or None).  The initial state is computed on ``B``
-        rows and spread when the copies share their frame-0 mask and their initial uniforms, else on the wide rows (from one mean
-        embedding per row when they share the mask).  ``expert_log_weights``: ``[B, T, 3]``, or ``[B * copies, T, 3]`` taken as it is."""
+    def _evaluation_inputs(self, batch: tuple[Tensor, ...], plan: CopyPlan, noise: Noise | None, lengths: Tensor | None,  # noqa: PLR0914
+                           expert_log_weights: Tensor | None) -> tuple[dict[str, object], Tensor | None]:
+        """What the rollout of an evaluation step reads, on the scan's ``B * copies`` rows: both encoders once, one ``Forecast.sample``
+        per distinct context of ``plan``, its expansion, the initial state and the gate once per row.  Returns ``{"actions",
+        "audio_embed", "vision_embed", "state0", "noise", "codes", "logw"}`` and the rows' lengths (or None).  The initial state is
+        computed on ``B`` rows and spread when the copies share their frame-0 mask and their initial uniforms, else on the wide rows
+        (from one mean embedding per row when they share the mask).  ``expert_log_weights``: ``[B, T, 3]``, or ``[B * copies, T, 3]``
+        taken as it is."""
         actions = batch[0]
         audio_obs, vision_obs = self.get_observations_from_batch(batch)
         (B, T), dev = actions.shape[:2], actions.device  # noqa: N806
@@ -251,9 +254,17 @@ class _Evaluators:
         else:
             logw = self._expert_logw(audio_embed, vision_embed, expert_log_weights, B, T)  # the gate once per row ...
             logw = None if logw is None else spread(logw)  # ... repeated for its copies
-        out = self._rollout_embedded(spread(actions), spread(audio_embed), spread(vision_embed), state0, wide_noise, sample_prior=False,
-                                     modality=codes, expert_log_weights=logw)
-        out["codes"] = codes
+        return {"actions": spread(actions), "audio_embed": spread(audio_embed), "vision_embed": spread(vision_embed), "state0": state0,
+                "noise": wide_noise, "codes": codes, "logw": logw}, valid
+
+    def _evaluation_rollout(self, batch: tuple[Tensor, ...], plan: CopyPlan, noise: Noise | None, lengths: Tensor | None,
+                            expert_log_weights: Tensor | None) -> tuple[dict[str, Tensor], Tensor | None]:
+        """The rollout of every evaluation step: ``_evaluation_inputs`` and ONE masked posterior rollout over ``B * copies`` rows.
+        Returns the scan's outputs -- with ``"codes"``, the rows' modality codes -- and the rows' lengths (or None)."""
+        inp, valid = self._evaluation_inputs(batch, plan, noise, lengths, expert_log_weights)
+        out = self._rollout_embedded(inp["actions"], inp["audio_embed"], inp["vision_embed"], inp["state0"], inp["noise"], sample_prior=False,
+                                     modality=inp["codes"], expert_log_weights=inp["logw"])
+        out["codes"] = inp["codes"]
         return out, valid
 
     # -- forecast skill (DESIGN.md 6h) -------------------------------------------------------------------------------------------------------
@@ -417,6 +428,90 @@ class _Evaluators:
                 planes[:, r0:r1] = part
         table.planes = planes if keep_states else None
         table.states = self._posterior_from_rollout(out) if keep_states else None
+        return table
+
+    # -- particle-filter likelihood -------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def particle_filter(self, batch: tuple[Tensor, ...], pf: ParticleFilter, noise: Noise | None = None, lengths: Tensor | None = None,  # noqa: PLR0913, PLR0914, PLR0915
+                        table: ParticleTable | None = None, *, keep_states: bool = False,
+                        expert_log_weights: Tensor | None = None) -> ParticleTable:
+        """One particle-filter step (``particle.py`` states the quantity): ``pf.samples`` particles per row (scan
+        row ``b * S + s``), proposed as the samples of ``likelihood_bound`` are.  Encoders, gate, codes and the initial state run once;
+        then, per time segment of ``pf.resample_every`` frames: the masked posterior rollout of the segment from the carried particle
+        states, the latent log-ratio (one launch per level), the decoders and the scorer over chunks of whole rows,
+        ``mtrssm_particle_fold`` -- which carries the weights in double, decides the resampling on the device and writes the ancestors --
+        and ``mtrssm_particle_gather`` of the scan's last step by ancestor.  Nothing is read back to the host.  Planes 0 .. 6 are folded
+        by frame position into ``table`` (a new one when None), which is returned.  ``noise``: the plan's uniforms and ``u_resample``
+        ``(B, T)`` (absent ones are drawn).  ``lengths`` (or a batch that carries ``valid_global``): nothing is observed, scored or
+        resampled at or past a row's end.  ``keep_states``: ``table.planes`` ``[8, B, T]``, ``table.ancestors`` int32 ``[B, S, J]`` and
+        ``table.inputs`` (``se_audio``, ``se_vision``, ``ratio``: fp32 ``[B, S, T]`` as the fold saw them, None for a term that is off).
+        No masked (7-tuple) batch, no ``state_carry``; a weighted model runs its gate as in ``forecast_skill``."""
+        self._check_evaluation_step(batch, "pf", pf, ParticleFilter, table, ParticleTable)
+        targets = self.get_targets_from_batch(batch)
+        B, T = batch[0].shape[:2]  # noqa: N806
+        S, dev = pf.samples, batch[0].device  # noqa: N806
+        inp, valid = self._evaluation_inputs(batch, pf.plan(), noise, lengths, expert_log_weights)
+        u_resample = (noise or {}).get("u_resample")
+        if u_resample is None:
+            u_resample = _rand(batch[0], B, T)
+        if tuple(u_resample.shape) != (B, T) or u_resample.dtype != torch.float32 or u_resample.device != dev:
+            msg = f"noise['u_resample'] must be a float32 tensor of shape {(B, T)} on {dev}, got {u_resample.dtype} {tuple(u_resample.shape)}"
+            raise ValueError(msg)
+        segments = pf.segments(T)
+        audio, vision = "audio" in pf.score, "vision" in pf.score
+        planes = torch.empty(len(PARTICLE_PLANES), B, T, device=dev, dtype=torch.float32)
+        carry = ParticleFilter.new_carry(B, S, dev)
+        ancestor = torch.empty(B, S, device=dev, dtype=torch.int32)
+        kept_ancestors = torch.empty(B, S, len(segments), device=dev, dtype=torch.int32) if keep_states else None
+        kept: dict[str, Tensor | None] = {"se_audio": None, "se_vision": None, "ratio": None}
+        state, wide_noise, logw_all = inp["state0"], inp["noise"], inp["logw"]
+        for j, (t0, t1) in enumerate(segments):
+            c, last = t1 - t0, t1 == T
+            cut = (lambda x: x) if c == T else (lambda x: x[:, t0:t1].contiguous())  # noqa: B023
+            seg_noise = {k: (cut(u) if k in self._POST_KEYS and u is not None else u) for k, u in wide_noise.items()}
+            out = self._rollout_embedded(cut(inp["actions"]), cut(inp["audio_embed"]), cut(inp["vision_embed"]), state, seg_noise,
+                                         sample_prior=False, modality=cut(inp["codes"]), expert_log_weights=None if logw_all is None else cut(logw_all))
+            ratio = None
+            if pf.latent:
+                for suffix, factory in self._latent_levels():
+                    ratio = LikelihoodBound.log_ratio(out[f"post_logits{suffix}"], out[f"prior_logits{suffix}"], out[f"post_stoch{suffix}"],
+                                                      factory.category_size, factory.class_size, out=ratio, accumulate=ratio is not None)
+                ratio = ratio.reshape(B, S, c)
+            seg_valid = None if valid is None else (valid - t0).clamp_(min=0)  # the scorer counts frames from the segment's first
+            feature = self._feature_of(out) if pf.score else None
+            for r0, r1 in _row_chunks(B, S * c, pf.max_frames if pf.score else B * S * c):  # (nothing to decode: one chunk)
+                n = r1 - r0
+                se, events = [None, None], [0, 0]
+                if pf.score:
+                    preds, acts = self._decode_for_score(feature[r0 * S : r1 * S], audio=audio, vision=vision)
+                    for m, (pred, key) in enumerate(zip(preds, ("recon/audio", "recon/vision"), strict=True)):
+                        if pred is None:
+                            continue
+                        pred = pred.reshape(n, S, c, -1)  # noqa: PLW2901
+                        events[m] = pred.shape[-1]
+                        se[m] = ForecastSkill.score(pred, targets[key][r0:r1, t0:t1].reshape(n, c, -1), None if seg_valid is None else seg_valid[r0:r1],
+                                                    acts[m], se_samples=True).se_samples
+                part, _ = ParticleFilter.fold(se[0], se[1], None if ratio is None else ratio[r0:r1], None if valid is None else valid[r0:r1],
+                                              None if last else u_resample[r0:r1, t1 - 1], t0, pf.threshold, last, carry[r0:r1], events[0], events[1],
+                                              ancestor=ancestor[r0:r1])
+                planes[:, r0:r1, t0:t1] = part
+                if keep_states:
+                    for name, x in (("se_audio", se[0]), ("se_vision", se[1]), ("ratio", None if ratio is None else ratio[r0:r1])):
+                        if x is not None:
+                            if kept[name] is None:
+                                kept[name] = torch.zeros(B, S, T, device=dev, dtype=torch.float32)
+                            kept[name][r0:r1, :, t0:t1] = x
+            if keep_states:
+                kept_ancestors[:, :, j] = ancestor
+            if not last:
+                moved = ParticleFilter.gather([out[self._LAST_KEYS[k]] for k in self._FRESH_KEYS], ancestor)
+                state = self._state_like(state, dict(zip(self._FRESH_KEYS, moved, strict=True)))
+        if table is None:
+            table = ParticleTable(T, dev)
+        table.fold(planes, valid)
+        table.planes = planes if keep_states else None
+        table.ancestors = kept_ancestors
+        table.inputs = kept if keep_states else None
         return table
 
     # -- latent probes (DESIGN.md 6l) --------------------------------------------------------------------------------------------------------

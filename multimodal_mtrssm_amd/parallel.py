@@ -21,6 +21,7 @@ from multimodal_mtrssm_amd.dropout import ModalityDropout
 from multimodal_mtrssm_amd.forecast import Forecast
 from multimodal_mtrssm_amd.optim import FlatParameters
 from multimodal_mtrssm_amd.likelihood import LikelihoodBound
+from multimodal_mtrssm_amd.particle import ParticleFilter
 from multimodal_mtrssm_amd.probe import LatentProbe
 from multimodal_mtrssm_amd.skill import ForecastSkill
 
@@ -105,6 +106,11 @@ class FlatDataParallel:
         """``bound`` bound to this object's process group: set the result as ``model.val_likelihood`` and ``on_validation_epoch_end``
         all-reduces the likelihood table over that group (its uniforms' batch dimension comes first: draw them with ``noise_source``)."""
         return bound.for_group(self.group)
+
+    def particle(self, pf: ParticleFilter) -> ParticleFilter:
+        """``pf`` bound to this object's process group: set the result as ``model.val_particle`` and ``on_validation_epoch_end``
+        all-reduces the particle table over that group (its uniforms' batch dimension comes first: draw them with ``noise_source``)."""
+        return pf.for_group(self.group)
 
     def probe(self, probe: LatentProbe) -> LatentProbe:
         """``probe`` bound to this object's process group: ``ProbeTable.all_reduce(probe.group)`` and ``LinearProbe.fit(..., group=
