@@ -975,6 +975,50 @@ int mtrssm_particle_fold(const float* se_audio, const float* se_vision, const fl
                          double threshold, int32_t last_segment, double* carry, float* planes, int32_t* ancestor, void* stream);
 int mtrssm_particle_gather(const MtrssmStateTable* table, const int32_t* ancestor, int64_t B, int64_t S, int64_t steps, void* stream);
 
+/* Latent overshooting: the KL between the closed-loop posterior at frame t0 + k and the prior rolled k steps
+ * open loop from the posterior at t0, k = 1 .. D.  Starts t0_i = o + i * s for i < N = (T - 2 - o) / s + 1; overshoot row
+ * r = b * N + i; step j (0-based) of a row is the k = j + 1 step prior for frame t = t0_i + j + 1.  Term (r, k) is live iff
+ * t < clamp(valid[b], 0, T) (valid NULL: iff t < T).
+ * mtrssm_overshoot_gather: ONE launch for all tensors of a state and the action windows.  Entries as in mtrssm_state_save: src[k]
+ *   [B][T][width[k]] contiguous, read in place, dst[k] [B * N][width[k]] (src_stride and alt are ignored):
+ *     dst[k][b * N + i, :] = src[k][b, t0_i, :];   windows[b * N + i][j][:] = actions[b, t0_i + 1 + j, :], zeros where that frame >= T
+ *   actions [B][T][A], windows [B * N][D][A].  16 bytes per lane where a width is a multiple of 4 and both pointers are 16-byte
+ *   aligned, else 4.
+ * mtrssm_overshoot_scatter: its backward for the state tensors, one launch.  src[k] = g_dst [B * N][width[k]], dst[k] = g_src
+ *   [B][T][width[k]]:  g_src[k][b, t, :] = g_dst[k][b * N + i, :] where t = t0_i, 0 elsewhere; every element of g_src is written
+ *   exactly once (no memset beforehand).
+ *   Both: a null table / entry / actions / windows, count outside 1 .. MTRSSM_STATE_MAX, B <= 0, T < 2, s < 1, o outside 0 .. T - 2,
+ *   D < 2, A <= 0, an N other than (T - 2 - o) / s + 1, src[k] == dst[k], a pointer that is not 4-byte aligned or a tensor of 2^31
+ *   elements or more return -1 without a launch.
+ * mtrssm_overshoot_kl_fwd: post_logits [b_local][T][K * C] (the rank's closed-loop posterior), os_logits [b_local * N][D][K * C] (the
+ *   overshoot rows' prior logits); valid [b_global] int32 in DEVICE memory (ALL rows of the global batch, NULL: every frame is live);
+ *   the rank holds the global rows row0 .. row0 + b_local - 1.  Per live term, with lq / lp the log-softmax per categorical of the
+ *   posterior / overshoot logits and q = exp(lq):   kl(r, k) = sum_cat sum_c q_c (lq_c - lp_c)   (a class with q_c = 0 adds 0).
+ *   Each categorical's max, log-sum and differences in double, categoricals in ascending order, rounded to fp32 once (as
+ *   mtrssm_latent_log_ratio).  Outputs: plane [b_local * N][D] fp32, exactly 0 on a dead term; table [2][D] double: per k the sum
+ *   and the count of the rank's live terms; count [1] fp32: the live terms with k >= 2 of ALL b_global rows; term [1] fp32: the sum of
+ *   the rank's live k >= 2 terms / max(count, 1).  A wave stages both rows in LDS with coalesced loads (any C >= 1; C > 512 reads
+ *   in place); the per-term doubles go to `workspace` (mtrssm_overshoot_kl_workspace_bytes(b_local, N, D) bytes, 8-byte aligned, -1
+ *   for sizes out of range) and a second one-workgroup launch folds them in a fixed order: no atomics, two calls agree bitwise.
+ * mtrssm_overshoot_kl_bwd: g_term [1] (the gradient arriving at `term`) and count [1] in DEVICE memory; scale = g_term / max(count, 1).
+ *     g_os_logits [b_local * N][D][K * C] = scale * w_prior * (p - q) on live k >= 2 terms, exactly 0 elsewhere
+ *     g_post_logits [b_local][T][K * C] = the sum, over the rows that target (b, t) -- t0 = t - k for k = 2 .. D in ascending k with
+ *       t0 >= o, (t0 - o) % s == 0 and (t0 - o) / s < N -- of scale * w_post * q_c ((lq_c - lp_c) - kl_cat); written everywhere
+ *   g_post_logits must be NULL exactly when w_post == 0 (then nothing of it is written).  One launch.
+ *   Both: null required pointers, rows outside the global batch, K or C <= 0, the size rules above, b_local * N * D * K * C,
+ *   b_local * T * K * C or b_global * N >= 2^31, misaligned buffers, a short workspace, negative weights or a gradient buffer that
+ *   aliases another buffer return -1 without a launch. */
+int mtrssm_overshoot_gather(const MtrssmStateTable* table, const float* actions, float* windows, int64_t B, int64_t T, int64_t N, int64_t s,
+                            int64_t o, int64_t D, int64_t A, void* stream);
+int mtrssm_overshoot_scatter(const MtrssmStateTable* table, int64_t B, int64_t T, int64_t N, int64_t s, int64_t o, void* stream);
+int64_t mtrssm_overshoot_kl_workspace_bytes(int64_t b_local, int64_t N, int64_t D);
+int mtrssm_overshoot_kl_fwd(const float* post_logits, const float* os_logits, const int32_t* valid, int64_t b_global, int64_t row0,
+                            int64_t b_local, int64_t T, int64_t N, int64_t s, int64_t o, int64_t D, int64_t K, int64_t C, float* plane,
+                            double* table, float* count, float* term, void* workspace, int64_t workspace_bytes, void* stream);
+int mtrssm_overshoot_kl_bwd(const float* post_logits, const float* os_logits, const int32_t* valid, const float* g_term, const float* count,
+                            int64_t b_global, int64_t row0, int64_t b_local, int64_t T, int64_t N, int64_t s, int64_t o, int64_t D, int64_t K,
+                            int64_t C, float w_prior, float w_post, float* g_os_logits, float* g_post_logits, void* stream);
+
 /* Linear word probes: one fused step of G multinomial-logistic classifiers over N feature rows.
  *   x [G][N][ld] fp32, of which columns [col0, col0 + F) are read; labels [N] int32 in DEVICE memory, shared by the groups: frame n is
  *   live iff 0 <= labels[n] < C (-1 = silence, a frame past its row's end); weight [G][C][F], bias [G][C].  Per group g and live frame n:

@@ -32,6 +32,7 @@ from multimodal_mtrssm_amd.objective import likelihood
 from multimodal_mtrssm_amd.optim import FlatAdamW, ReduceLROnPlateau, load_reference_checkpoint
 from multimodal_mtrssm_amd.panel import EpisodePanel, EpisodePanelLogger, EpisodeVideo
 from multimodal_mtrssm_amd.parallel import FlatDataParallel, GlobalRowNoise
+from multimodal_mtrssm_amd.overshoot import LatentOvershoot, OvershootTable
 from multimodal_mtrssm_amd.particle import ParticleFilter, ParticleTable
 from multimodal_mtrssm_amd.probe import LatentProbe, LinearProbe, ProbeStats, ProbeTable
 from multimodal_mtrssm_amd.schedule import ElboSchedule
@@ -46,5 +47,5 @@ __all__ = [
     "MoPoE_MRSSM", "ModalityDropout", "MultiOneHot", "MultiOneHotFactory", "ProbeStats", "ProbeTable", "ReduceLROnPlateau", "Representation", "SkillTable", "State", "StateCarry", "Transition", "TransitionTable", "WeightedMoPoE_MMTRSSM", "WeightedMoPoE_MRSSM", "WordTransitions", "cat_distribution",
     "cat_mtstates", "cat_states", "inject_uniforms", "kl_divergence", "likelihood", "load_reference_checkpoint", "make_mmtrssm", "make_mrssm",
     "stack_distribution", "stack_mtstates", "stack_states", "dropout_mask_reference", "tape_reference", "EarlyStopping", "EpochMetrics", "Trainer",
-    "ParticleFilter", "ParticleTable",
+    "LatentOvershoot", "OvershootTable", "ParticleFilter", "ParticleTable",
 ]

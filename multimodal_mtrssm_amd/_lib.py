@@ -181,6 +181,11 @@ SYMBOLS: dict[str, tuple[type | None, list[type]]] = {
     "mtrssm_particle_fold": (C.c_int, [_p, _p, _p, _p, _p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_double, _i,
                                        _p, _p, _p, _p]),
     "mtrssm_particle_gather": (C.c_int, [C.POINTER(StateTable), _p, C.c_int64, C.c_int64, C.c_int64, _p]),
+    "mtrssm_overshoot_gather": (C.c_int, [C.POINTER(StateTable), _p, _p] + [C.c_int64] * 7 + [_p]),
+    "mtrssm_overshoot_scatter": (C.c_int, [C.POINTER(StateTable)] + [C.c_int64] * 5 + [_p]),
+    "mtrssm_overshoot_kl_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
+    "mtrssm_overshoot_kl_fwd": (C.c_int, [_p, _p, _p] + [C.c_int64] * 10 + [_p, _p, _p, _p, _p, C.c_int64, _p]),
+    "mtrssm_overshoot_kl_bwd": (C.c_int, [_p, _p, _p, _p, _p] + [C.c_int64] * 10 + [_f, _f, _p, _p, _p]),
     "mtrssm_linear_probe_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "mtrssm_linear_probe_step": (C.c_int, [_p, C.c_int64, C.c_int64, _p, _p, _p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _i, _p, _p, _p, _p, _p, _p,
                                            _p, C.c_int64, _p]),

@@ -27,6 +27,7 @@ from multimodal_mtrssm_amd.dropout import ModalityDropout, StepMask, ragged_step
 from multimodal_mtrssm_amd.evaluation import _Evaluators
 from multimodal_mtrssm_amd.experts import ExpertWeights
 from multimodal_mtrssm_amd.forecast import Forecast
+from multimodal_mtrssm_amd.overshoot import LatentOvershoot, OvershootTable, OvershootTerms
 from multimodal_mtrssm_amd.likelihood import LikelihoodBound, LikelihoodTable
 from multimodal_mtrssm_amd.networks import MTRNN, Representation, Transition
 from multimodal_mtrssm_amd.objective import likelihood
@@ -499,6 +500,10 @@ class MoPoE_MRSSM(_Evaluators, _Base):  # noqa: N801
         self.likelihood_table: LikelihoodTable | None = None  # ... logged as val/loglik/* and cleared by on_validation_epoch_end
         self.val_particle: ParticleFilter | None = None  # validation_step adds a particle-filter step into self.particle_table
         self.particle_table: ParticleTable | None = None  # ... logged as val/smc/* and cleared by on_validation_epoch_end
+        self.overshoot: LatentOvershoot | None = None  # training_step adds the latent-overshooting term with it
+        self.val_overshoot: LatentOvershoot | None = None  # validation_step adds an overshoot pass into self.overshoot_table
+        self.overshoot_table: OvershootTable | None = None  # ... logged as val/overshoot/* and cleared by on_validation_epoch_end
+        self._overshoot_terms_last: list[OvershootTerms] | None = None  # the last overshoot step's terms per level (detached use only)
         # weighted MoPoE: assign an ExpertWeights (a submodule: before FlatParameters is built); None = 1/3 each, no new
         # state-dict keys.  After every posterior rollout with weights, weights_timeseries is ExpertWeights.table(...) [B, T, 3]
         self.expert_weights: ExpertWeights | None = None
@@ -648,11 +653,14 @@ class MoPoE_MRSSM(_Evaluators, _Base):  # noqa: N801
     def _with_mask_noise(self, shapes: dict[str, tuple[int, ...]], batch: int, steps: int) -> dict[str, tuple[int, ...]]:
         """With ``self.modality_dropout`` set, the key ``u_mask`` joins (``GlobalRowNoise`` hands every rank ALL its rows: the
         sampler counts the global batch's present frames), with ``self.forecast`` set ``u_context`` (likewise); without, ``shapes``
-        as it is."""
+        as it is.  With ``self.overshoot`` set ``u_overshoot`` (MMTRSSM: ``u_overshoot_l`` / ``u_overshoot_h``) joins, batch row first."""
         if self.modality_dropout is not None:
             shapes["u_mask"] = self.modality_dropout.noise_shape(batch, steps)
         if self.forecast is not None:
             shapes["u_context"] = self.forecast.noise_shape(batch)
+        if self.overshoot is not None:
+            for key in self._POST_KEYS:
+                shapes[self._overshoot_key(key)] = self.overshoot.noise_shape(batch, steps, self._category_size_of(key))
         return shapes
 
     def _rollout_embedded(self, actions: Tensor, audio_embed: Tensor | None, vision_embed: Tensor | None, prev_state: State,  # noqa: PLR0913
@@ -918,11 +926,86 @@ class MoPoE_MRSSM(_Evaluators, _Base):  # noqa: N801
             raise ValueError(msg)
         return modality_dropout.sample(self._dropout_uniforms(batch, noise, modality_dropout, modality_dropout.world), T).step_mask()
 
+    @staticmethod
+    def _overshoot_key(post_key: str) -> str:
+        """``u_post`` -> ``u_overshoot``, ``u_post_l`` -> ``u_overshoot_l``: the uniforms of a level's overshoot rows."""
+        return "u_overshoot" + post_key[len("u_post"):]
+
+    def _overshoot_plan(self, batch: tuple[Tensor, ...], overshoot: LatentOvershoot, lengths: Tensor | None,
+                        modality_dropout: ModalityDropout | None) -> tuple[LatentOvershoot, Tensor | None, int]:
+        """``(overshoot bound to the batch's rank, valid of ALL global rows or None, row0)`` of a step; host rules only."""
+        if not isinstance(overshoot, LatentOvershoot):
+            msg = f"overshoot must be a LatentOvershoot, got {type(overshoot).__name__}"
+            raise ValueError(msg)
+        B, T = batch[0].shape[:2]
+        overshoot.rows(T)  # (offset <= T - 2, or ValueError)
+        if lengths is not None and overshoot.world != 1:
+            msg = "lengths= describes one rank's own rows: with data parallelism use a batch that carries valid_global"
+            raise ValueError(msg)
+        ragged = self._lengths_of(batch, lengths, modality_dropout, None, trust_reset=True)  # (the step's mask checked the t = 0 rule)
+        valid, world, rank = (None, overshoot.world, overshoot.rank) if ragged is None else ragged
+        if overshoot.world not in (1, world) or (overshoot.world == world and overshoot.rank != rank):
+            msg = f"overshoot is bound to rank {overshoot.rank} of {overshoot.world}, the batch to rank {rank} of {world}"
+            raise ValueError(msg)
+        bound = overshoot if overshoot.world == world else overshoot.for_rank(world, rank)
+        return bound, valid, rank * B
+
+    def _overshoot_terms(self, actions: Tensor, out: dict[str, Tensor], noise: Noise | None,
+                         plan: tuple[LatentOvershoot, Tensor | None, int]) -> list[OvershootTerms]:
+        """The overshoot pass behind the closed-loop scan ``out``: gather the start states and action windows, roll the
+        ``B * N`` rows ``D`` steps open loop (modality code 0, no embeddings) and take the KL pair per latent level.  Nothing is read
+        back."""
+        from types import SimpleNamespace  # noqa: PLC0415
+
+        lo, valid, row0 = plan
+        noise = noise or {}
+        B, T = actions.shape[:2]
+        n, d = lo.rows(T), lo.depth
+        starts, windows = lo.gather([out[self._LAST_KEYS[k]] for k in self._FRESH_KEYS], actions)
+        state = SimpleNamespace(**dict(zip(self._FRESH_KEYS, starts, strict=True)))
+        os_noise: dict[str, Tensor] = {}
+        for key in self._POST_KEYS:
+            k = self._category_size_of(key)
+            u = noise.get(self._overshoot_key(key))
+            if u is None:
+                u = _rand(actions, B, n, d, k)
+            if tuple(u.shape) != (B, n, d, k):
+                msg = f"noise[{self._overshoot_key(key)!r}] must have shape {(B, n, d, k)}, got {tuple(u.shape)}"
+                raise ValueError(msg)
+            os_noise[key] = u.to(actions).reshape(B * n, d, k)
+        codes = torch.zeros(B * n, d, dtype=torch.int32, device=actions.device)
+        reported = (self.weights_timeseries, self._weights_both)  # (the closed-loop step's: the overshoot rows have no gate to report)
+        os_out = self._rollout_embedded(windows, None, None, state, os_noise, sample_prior=False, modality=codes)
+        self.weights_timeseries, self._weights_both = reported
+        weights = lo.kl_weights(bool(self.use_kl_balancing))
+        terms = []
+        for key in self._POST_KEYS:
+            level = key[len("u_post"):]
+            terms.append(lo.kl(out["post_logits" + level], os_out["prior_logits" + level], self._category_size_of(key), valid, row0, weights))
+        self._overshoot_terms_last = terms
+        return terms
+
+    def _add_overshoot(self, result: dict[str, Tensor], terms: list[OvershootTerms], lo: LatentOvershoot,
+                       schedule: ElboSchedule | None) -> dict[str, Tensor]:
+        """``loss += kl_coeff * weight * (overshoot [+ w_kl_h * overshoot_h])``, times the step's beta under a schedule; free nats do
+        not apply.  The new keys come after the existing ones."""
+        extra = terms[0].term
+        if len(terms) > 1:
+            extra = extra + float(self.w_kl_h) * terms[1].term
+        extra = extra * (float(self.kl_coeff) * lo.weight)
+        if schedule is not None:
+            extra = extra * schedule.stats["beta"].to(extra)
+        result["loss"] = result["loss"] + extra
+        result["overshoot"] = terms[0].term
+        if len(terms) > 1:
+            result["overshoot_h"] = terms[1].term
+        return result
+
     def shared_step(self, batch: tuple[Tensor, ...], noise: Noise | None = None, modality_mask: Tensor | None = None,  # noqa: PLR0913
                     modality_dropout: ModalityDropout | None = None, state_carry: StateCarry | None = None,
                     reset: Tensor | None = None, *, carry_prefix: str = "train", lengths: Tensor | None = None,
                     forecast: Forecast | None = None, elbo_schedule: ElboSchedule | None = None,
-                    expert_log_weights: Tensor | None = None) -> dict[str, Tensor]:
+                    expert_log_weights: Tensor | None = None, overshoot: LatentOvershoot | None = None) -> dict[str, Tensor]:
         """``core.py:187-221``: ``loss = recon + kl_coeff * KL(post || prior)`` (MMTRSSM, ``mmtrssm core.py:563-606``:
         ``recon + kl_coeff KL_l + kl_coeff w_kl_h KL_h``).  ``modality_mask`` (or a 7th batch entry, bool ``[B, T, 2]``): each
         recon term averages over the frames where its modality is present; the KL stays the mean over all B*T (0 on steps with
@@ -951,7 +1034,17 @@ class MoPoE_MRSSM(_Evaluators, _Base):  # noqa: N801
         (``kl_h_raw``), the unscheduled term, after the existing keys.
 
         ``expert_log_weights``: explicit expert log-weights as in ``rollout_representation``; a weighted model
-        (``self.expert_weights``) needs none, its gate runs inside the step."""
+        (``self.expert_weights``) needs none, its gate runs inside the step.
+
+        ``overshoot`` (a ``LatentOvershoot``): behind the closed-loop scan the posterior states at every
+        ``stride``-th frame start ``depth`` open-loop steps (uniforms ``noise["u_overshoot"]``, MMTRSSM ``u_overshoot_l`` / ``_h``,
+        drawn here when absent) and ``loss += kl_coeff * weight * overshoot (+ kl_coeff * weight * w_kl_h * overshoot_h)``, times the
+        step's beta under an ``elbo_schedule``; the dict gains ``overshoot`` (``overshoot_h``) after the existing keys.  With every
+        option above except ``forecast`` (its tail's states are not posteriors)."""
+        if forecast is not None and overshoot is not None:
+            msg = "overshoot= does not combine with forecast=: the states of a forecast step's tail are not posteriors"
+            raise ValueError(msg)
+        plan = None if overshoot is None else self._overshoot_plan(batch, overshoot, lengths, modality_dropout)
         if forecast is not None:
             if modality_mask is not None or self.get_modality_mask_from_batch(batch) is not None:
                 msg = "forecast= decides what the model observes: a modality_mask (or a 7-tuple batch) already says what is seen, give one of them"
@@ -967,9 +1060,9 @@ class MoPoE_MRSSM(_Evaluators, _Base):  # noqa: N801
         on_device = state_carry is not None and isinstance(reset, Tensor) and reset.is_cuda  # (trusted, as the carry trusts it)
         sm = self._step_mask(batch, noise, modality_mask, modality_dropout, lengths, reset_host, trust_reset=on_device)
         if state_carry is None:
-            return self._elbo_step(batch, noise, sm, schedule=elbo_schedule, expert_log_weights=expert_log_weights)
+            return self._elbo_step(batch, noise, sm, schedule=elbo_schedule, expert_log_weights=expert_log_weights, overshoot=plan)
         return self._elbo_step(batch, noise, sm, self._carry_of(batch, state_carry, reset, carry_prefix), schedule=elbo_schedule,
-                               expert_log_weights=expert_log_weights)
+                               expert_log_weights=expert_log_weights, overshoot=plan)
 
     @staticmethod
     def _carry_of(batch: tuple[Tensor, ...], state_carry: StateCarry, reset: Tensor | None, prefix: str) -> tuple[StateCarry, str, Tensor]:
@@ -1016,7 +1109,8 @@ class MoPoE_MRSSM(_Evaluators, _Base):  # noqa: N801
 
     def _elbo_step(self, batch: tuple[Tensor, ...], noise: Noise | None, sm: StepMask | None,
                    carry: tuple[StateCarry, str, Tensor] | None = None, schedule: ElboSchedule | None = None,
-                   expert_log_weights: Tensor | None = None) -> dict[str, Tensor]:
+                   expert_log_weights: Tensor | None = None,
+                   overshoot: tuple[LatentOvershoot, Tensor | None, int] | None = None) -> dict[str, Tensor]:
         """``shared_step`` behind the mask handling (the captured step enters here with a mask it validated itself)."""
         action_input = batch[0]
         audio_obs, vision_obs = self.get_observations_from_batch(batch)
@@ -1034,20 +1128,24 @@ class MoPoE_MRSSM(_Evaluators, _Base):  # noqa: N801
         feature = torch.cat([out["deter"], out["post_stoch"]], dim=-1)
         parts = self._reconstruction_losses(feature, self.get_targets_from_batch(batch), sum_recon=False, step_mask=sm)
         recon, kl_div, _, loss = _elbo(parts["recon/audio"], parts["recon/vision"], out["kl"], float(self.kl_coeff), step_mask=sm, schedule=schedule)
+        result = {"recon": recon, **parts, "kl": kl_div, "loss": loss}
         if schedule is not None:
-            return {"recon": recon, **parts, "kl": kl_div, "loss": loss, "kl_raw": schedule.stats["kl_raw"]}
-        return {"recon": recon, **parts, "kl": kl_div, "loss": loss}
+            result["kl_raw"] = schedule.stats["kl_raw"]
+        if overshoot is not None:
+            return self._add_overshoot(result, self._overshoot_terms(action_input, out, noise, overshoot), overshoot[0], schedule)
+        return result
 
     def _step(self, batch: tuple[Tensor, ...], prefix: str, *, with_loss_key: bool, modality_dropout: ModalityDropout | None = None,  # noqa: PLR0913
-              forecast: Forecast | None = None, elbo_schedule: ElboSchedule | None = None) -> dict[str, Tensor]:
-        if forecast is not None:  # (with a state_carry set too, shared_step refuses)
+              forecast: Forecast | None = None, elbo_schedule: ElboSchedule | None = None,
+              overshoot: LatentOvershoot | None = None) -> dict[str, Tensor]:
+        if forecast is not None:  # (with a state_carry or an overshoot set too, shared_step refuses)
             loss_dict = self.shared_step(batch, modality_dropout=modality_dropout, state_carry=self.state_carry, forecast=forecast,
-                                         elbo_schedule=elbo_schedule)
+                                         elbo_schedule=elbo_schedule, overshoot=overshoot)
         elif self.state_carry is None:
-            loss_dict = self.shared_step(batch, modality_dropout=modality_dropout, elbo_schedule=elbo_schedule)
+            loss_dict = self.shared_step(batch, modality_dropout=modality_dropout, elbo_schedule=elbo_schedule, overshoot=overshoot)
         else:
             loss_dict = self.shared_step(batch, modality_dropout=modality_dropout, state_carry=self.state_carry, carry_prefix=prefix,
-                                         elbo_schedule=elbo_schedule)
+                                         elbo_schedule=elbo_schedule, overshoot=overshoot)
         renamed = {"loss": loss_dict["loss"]} if with_loss_key else {}
         renamed[f"{prefix}/loss"] = loss_dict["loss"]
         for key, value in loss_dict.items():
@@ -1058,7 +1156,7 @@ class MoPoE_MRSSM(_Evaluators, _Base):  # noqa: N801
 
     def training_step(self, batch: tuple[Tensor, ...], _: int = 0) -> dict[str, Tensor]:
         return self._step(batch, "train", with_loss_key=True, modality_dropout=self.modality_dropout, forecast=self.forecast,
-                          elbo_schedule=self.elbo_schedule)
+                          elbo_schedule=self.elbo_schedule, overshoot=self.overshoot)
 
     def validation_step(self, batch: tuple[Tensor, ...], _batch_index: int = 0) -> dict[str, Tensor]:
         """``val/*`` of the closed-loop step; with ``self.val_forecast`` set, a second step on the same batch observes that context and
@@ -1082,6 +1180,13 @@ class MoPoE_MRSSM(_Evaluators, _Base):  # noqa: N801
             self.likelihood_table = self.likelihood_bound(batch, self.val_likelihood, table=self.likelihood_table)
         if self.val_particle is not None:  # (after the likelihood step: every draw above is what it is without it)
             self.particle_table = self.particle_filter(batch, self.val_particle, table=self.particle_table)
+        if self.val_overshoot is not None:  # (last: every draw above is what it is without it)
+            with torch.no_grad():
+                self.shared_step(batch, overshoot=self.val_overshoot)
+            terms = self._overshoot_terms_last
+            if self.overshoot_table is None:
+                self.overshoot_table = OvershootTable(len(terms), self.val_overshoot.depth, terms[0].table.device)
+            self.overshoot_table.fold([t.table for t in terms])
         return logged
 
     def on_validation_epoch_end(self) -> dict[str, Tensor]:
@@ -1102,6 +1207,10 @@ class MoPoE_MRSSM(_Evaluators, _Base):  # noqa: N801
         if smc is not None:
             smc.all_reduce(getattr(self.val_particle, "group", None))
             logged.update(smc.scalars("val/smc"))
+        curve, self.overshoot_table = self.overshoot_table, None
+        if curve is not None:
+            curve.all_reduce(getattr(self.val_overshoot, "group", None))
+            logged.update(curve.scalars("val/overshoot"))
         if logged:
             self.log_dict(logged, prog_bar=False, sync_dist=False, on_step=False, on_epoch=True)
         return logged
@@ -1290,7 +1399,8 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
 
     def _elbo_step(self, batch: tuple[Tensor, ...], noise: Noise | None, sm: StepMask | None,
                    carry: tuple[StateCarry, str, Tensor] | None = None, schedule: ElboSchedule | None = None,
-                   expert_log_weights: Tensor | None = None) -> dict[str, Tensor]:
+                   expert_log_weights: Tensor | None = None,
+                   overshoot: tuple[LatentOvershoot, Tensor | None, int] | None = None) -> dict[str, Tensor]:
         """``mmtrssm core.py:563-606``: ``loss = recon + kl_coeff KL_l + kl_coeff w_kl_h KL_h`` (``shared_step``'s body)."""
         action_input = batch[0]
         audio_obs, vision_obs = self.get_observations_from_batch(batch)
@@ -1306,10 +1416,12 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
         parts = self._reconstruction_losses(feature, self.get_targets_from_batch(batch), sum_recon=False, step_mask=sm)
         recon, kl_div_l, kl_div_h, loss = _elbo(parts["recon/audio"], parts["recon/vision"], out["kl_l"], float(self.kl_coeff), out["kl_h"],
                                                 float(self.kl_coeff * self.w_kl_h), step_mask=sm, schedule=schedule)
+        result = {"recon": recon, **parts, "kl": kl_div_l, "kl_h": kl_div_h, "loss": loss}
         if schedule is not None:
-            return {"recon": recon, **parts, "kl": kl_div_l, "kl_h": kl_div_h, "loss": loss, "kl_raw": schedule.stats["kl_raw"],
-                    "kl_h_raw": schedule.stats["kl_h_raw"]}
-        return {"recon": recon, **parts, "kl": kl_div_l, "kl_h": kl_div_h, "loss": loss}
+            result.update({"kl_raw": schedule.stats["kl_raw"], "kl_h_raw": schedule.stats["kl_h_raw"]})
+        if overshoot is not None:
+            return self._add_overshoot(result, self._overshoot_terms(action_input, out, noise, overshoot), overshoot[0], schedule)
+        return result
 
 
 def _gate_for(model: MoPoE_MRSSM, mode: str) -> ExpertWeights:

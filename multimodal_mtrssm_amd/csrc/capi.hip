@@ -93,6 +93,13 @@ int iw_bound_launch(const float*, const float*, const float*, const int32_t*, in
 int particle_fold_launch(const float*, const float*, const float*, const int32_t*, const float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                          int64_t, double, int, double*, float*, int32_t*, hipStream_t);
 int particle_gather_launch(const MtrssmStateTable*, const int32_t*, int64_t, int64_t, int64_t, hipStream_t);
+int overshoot_gather_launch(const MtrssmStateTable*, const float*, float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, hipStream_t);
+int overshoot_scatter_launch(const MtrssmStateTable*, int64_t, int64_t, int64_t, int64_t, int64_t, hipStream_t);
+int64_t overshoot_kl_workspace_bytes(int64_t, int64_t, int64_t);
+int overshoot_kl_fwd_launch(const float*, const float*, const int32_t*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+                            int64_t, float*, double*, float*, float*, void*, int64_t, hipStream_t);
+int overshoot_kl_bwd_launch(const float*, const float*, const int32_t*, const float*, const float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+                            int64_t, int64_t, int64_t, int64_t, float, float, float*, float*, hipStream_t);
 int64_t linear_probe_workspace_bytes(int64_t, int64_t, int64_t, int64_t);
 int linear_probe_step_launch(const float*, int64_t, int64_t, const int32_t*, const float*, const float*, int64_t, int64_t, int64_t, int64_t, int, float*,
                              float*, float*, float*, float*, int32_t*, void*, int64_t, hipStream_t);
@@ -530,6 +537,27 @@ MTRSSM_API int mtrssm_particle_fold(const float* se_audio, const float* se_visio
 }
 MTRSSM_API int mtrssm_particle_gather(const MtrssmStateTable* table, const int32_t* ancestor, int64_t B, int64_t S, int64_t steps, void* stream) {
   return particle_gather_launch(table, ancestor, B, S, steps, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_overshoot_gather(const MtrssmStateTable* table, const float* actions, float* windows, int64_t B, int64_t T, int64_t N,
+                                       int64_t s, int64_t o, int64_t D, int64_t A, void* stream) {
+  return overshoot_gather_launch(table, actions, windows, B, T, N, s, o, D, A, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_overshoot_scatter(const MtrssmStateTable* table, int64_t B, int64_t T, int64_t N, int64_t s, int64_t o, void* stream) {
+  return overshoot_scatter_launch(table, B, T, N, s, o, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int64_t mtrssm_overshoot_kl_workspace_bytes(int64_t b_local, int64_t N, int64_t D) { return overshoot_kl_workspace_bytes(b_local, N, D); }
+MTRSSM_API int mtrssm_overshoot_kl_fwd(const float* post_logits, const float* os_logits, const int32_t* valid, int64_t b_global, int64_t row0,
+                                       int64_t b_local, int64_t T, int64_t N, int64_t s, int64_t o, int64_t D, int64_t K, int64_t C, float* plane,
+                                       double* table, float* count, float* term, void* workspace, int64_t workspace_bytes, void* stream) {
+  return overshoot_kl_fwd_launch(post_logits, os_logits, valid, b_global, row0, b_local, T, N, s, o, D, K, C, plane, table, count, term, workspace,
+                                 workspace_bytes, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_overshoot_kl_bwd(const float* post_logits, const float* os_logits, const int32_t* valid, const float* g_term,
+                                       const float* count, int64_t b_global, int64_t row0, int64_t b_local, int64_t T, int64_t N, int64_t s,
+                                       int64_t o, int64_t D, int64_t K, int64_t C, float w_prior, float w_post, float* g_os_logits,
+                                       float* g_post_logits, void* stream) {
+  return overshoot_kl_bwd_launch(post_logits, os_logits, valid, g_term, count, b_global, row0, b_local, T, N, s, o, D, K, C, w_prior, w_post,
+                                 g_os_logits, g_post_logits, static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int64_t mtrssm_linear_probe_workspace_bytes(int64_t G, int64_t N, int64_t C, int64_t F) {
   return linear_probe_workspace_bytes(G, N, C, F);

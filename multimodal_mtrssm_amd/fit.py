@@ -375,7 +375,7 @@ class Trainer:
     """``Trainer(model, flat, opt, dp, seed=..., max_epochs=..., directory=...).fit(train_loader, val_loader)``.
 
     One train step is ``model._step``'s dispatch on the model's ``modality_dropout`` / ``forecast`` / ``elbo_schedule`` /
-    ``state_carry`` attributes with uniforms from ``dp.noise_source(seed)``: ``opt.zero_grad()``, backward, ``dp.sync(scalars)``,
+    ``state_carry`` / ``overshoot`` attributes with uniforms from ``dp.noise_source(seed)``: ``opt.zero_grad()``, backward, ``dp.sync(scalars)``,
     ``opt.step(grad_scale=dp.grad_scale)``, then ``EpochMetrics.fold``.  ``train_step`` (``batch -> {key: device scalar}``) replaces
     everything from zero_grad to the optimizer: a ``CapturedTrainStep.step`` fits (the Trainer itself captures no graph), and so does a
     stub.  Loaders yield this rank's rows; a loader with ``set_epoch`` is told the epoch, one with ``batches(skip)`` resumes mid-epoch
@@ -439,7 +439,9 @@ class Trainer:
         b, t = batch[0].shape[:2]
         dropout = None if model.modality_dropout is None else model.modality_dropout.for_rank(dp.world, dp.rank)
         forecast = None if model.forecast is None else model.forecast.for_rank(dp.world, dp.rank)
-        shapes = dict(model.noise_shapes(b, t))  # (assembled as CapturedTrainStep does)
+        overshoot = getattr(model, "overshoot", None)
+        overshoot = None if overshoot is None else overshoot.for_rank(dp.world, dp.rank)
+        shapes = dict(model.noise_shapes(b, t))  # (assembled as CapturedTrainStep does; with model.overshoot its uniforms are in)
         if dropout is not None:
             shapes["u_mask"] = dropout.noise_shape(b, t)
         if forecast is not None:
@@ -448,12 +450,12 @@ class Trainer:
         opt.zero_grad()
         if forecast is not None:  # (with a state_carry set too, shared_step refuses)
             out = model.shared_step(batch, noise, modality_dropout=dropout, state_carry=model.state_carry, forecast=forecast,
-                                    elbo_schedule=model.elbo_schedule)
+                                    elbo_schedule=model.elbo_schedule, overshoot=overshoot)
         elif model.state_carry is None:
-            out = model.shared_step(batch, noise, modality_dropout=dropout, elbo_schedule=model.elbo_schedule)
+            out = model.shared_step(batch, noise, modality_dropout=dropout, elbo_schedule=model.elbo_schedule, overshoot=overshoot)
         else:
             out = model.shared_step(batch, noise, modality_dropout=dropout, state_carry=model.state_carry, carry_prefix="train",
-                                    elbo_schedule=model.elbo_schedule)
+                                    elbo_schedule=model.elbo_schedule, overshoot=overshoot)
         out["loss"].backward()
         logs = dp.sync({k: out[k] for k in out})
         opt.step(grad_scale=dp.grad_scale)

@@ -42,6 +42,10 @@ what is seen) nor with ``state_carry=`` (the state such a step ends with is an o
 optimizer's device-resident count of steps taken, which the captured epilogue reads, so every replay sees its own beta (the warm-up
 steps of the construction put that count back with the rest of ``opt.state``).
 
+``overshoot=`` captures the latent-overshooting term with every mode above except ``forecast=``: the
+``u_overshoot`` uniforms are drawn outside the graph into fixed buffers with the others; the gather, the overshoot rows' scan and the
+KL pair are inside.
+
 Observations that are ``None`` stay eager-only: a capture cannot drop an encoder per step.
 
 With more than one rank the gradient all-reduce (RCCL) and the optimizer run eagerly after the replay: the
@@ -59,6 +63,7 @@ from multimodal_mtrssm_amd.core import _check_modality_mask, check_ragged_rows
 from multimodal_mtrssm_amd.dropout import ModalityDropout, StepMask
 from multimodal_mtrssm_amd.forecast import Forecast
 from multimodal_mtrssm_amd.optim import FlatAdamW, FlatParameters
+from multimodal_mtrssm_amd.overshoot import LatentOvershoot
 from multimodal_mtrssm_amd.parallel import FlatDataParallel, GlobalRowNoise
 from multimodal_mtrssm_amd.schedule import ElboSchedule
 
@@ -94,7 +99,8 @@ class CapturedTrainStep:
     def __init__(self, model: torch.nn.Module, flat: FlatParameters, opt: FlatAdamW, dp: FlatDataParallel,  # noqa: PLR0913
                  batch: tuple[Tensor, ...], noise: GlobalRowNoise, *, warmup: int = 3,
                  modality_dropout: ModalityDropout | None = None, masked: bool = False, state_carry: StateCarry | None = None,
-                 ragged: bool = False, forecast: Forecast | None = None, elbo_schedule: ElboSchedule | None = None) -> None:
+                 ragged: bool = False, forecast: Forecast | None = None, elbo_schedule: ElboSchedule | None = None,
+                 overshoot: LatentOvershoot | None = None) -> None:
         if state_carry is not None and not isinstance(state_carry, StateCarry):
             msg = f"state_carry must be a StateCarry, got {type(state_carry).__name__}"
             raise ValueError(msg)
@@ -116,12 +122,19 @@ class CapturedTrainStep:
         if forecast is not None and state_carry is not None:
             msg = "forecast= does not combine with state_carry=: the state a forecast step ends with is an open-loop state"
             raise ValueError(msg)
+        if overshoot is not None and not isinstance(overshoot, LatentOvershoot):
+            msg = f"overshoot must be a LatentOvershoot, got {type(overshoot).__name__}"
+            raise ValueError(msg)
+        if overshoot is not None and forecast is not None:
+            msg = "overshoot= does not combine with forecast=: the states of a forecast step's tail are not posteriors"
+            raise ValueError(msg)
         if elbo_schedule is not None and not isinstance(elbo_schedule, ElboSchedule):
             msg = f"elbo_schedule must be an ElboSchedule, got {type(elbo_schedule).__name__}"
             raise ValueError(msg)
         self.model, self.masked, self.dropout, self.ragged = model, bool(masked), modality_dropout, bool(ragged)
         self.schedule = None if elbo_schedule is None else elbo_schedule.bind(opt)  # (beta follows opt.state[1], read on the device)
         self.forecast = None if forecast is None else forecast.for_rank(dp.world, dp.rank)
+        self.overshoot = None if overshoot is None else overshoot.for_rank(dp.world, dp.rank)
         self._check_batch_kind(batch)
         self.flat, self.opt, self.dp, self.noise = flat, opt, dp, noise
         b, t = batch[0].shape[:2]
@@ -149,6 +162,9 @@ class CapturedTrainStep:
             self.shapes["u_mask"] = self.dropout.noise_shape(b, t)
         if self.forecast is not None:
             self.shapes["u_context"] = self.forecast.noise_shape(b)
+        if self.overshoot is not None:
+            for key in model._POST_KEYS:  # noqa: SLF001
+                self.shapes[model._overshoot_key(key)] = self.overshoot.noise_shape(b, t, model._category_size_of(key))  # noqa: SLF001
         # (a GLOBAL_KEYS entry keeps the rows of every rank: GlobalRowNoise.draw)
         self.uniforms = {k: torch.empty((s[0] * noise.world if k in noise.GLOBAL_KEYS else s[0], *s[1:]), device=dev, dtype=torch.float32)
                          for k, s in self.shapes.items()}
@@ -194,20 +210,24 @@ class CapturedTrainStep:
     def _body(self) -> list[str]:
         self.opt.zero_grad()
         carry = None if self.carry is None else (self.carry, "train", self.reset)  # (its host rules were checked by step())
+        plan = None  # (the overshoot term's rows: this rank's of the global batch, whose lengths a ragged graph holds)
+        if self.overshoot is not None:
+            plan = (self.overshoot, self.valid_global if self.ragged else None, self.dp.rank * self.batch[0].shape[0])
         if self.masked:  # (validated on the host by step(); codes, planes and counts are derived here, inside the capture)
-            out = self.model._elbo_step(self.batch, self.uniforms, StepMask.from_mask(self.mask), carry, self.schedule)  # noqa: SLF001
+            out = self.model._elbo_step(self.batch, self.uniforms, StepMask.from_mask(self.mask), carry, self.schedule, overshoot=plan)  # noqa: SLF001
         elif self.forecast is not None:  # (a ragged batch's host rule was checked by step(); context AND lengths AND dropout in one launch)
             ragged = (self.valid_global, self.dp.world, self.dp.rank) if self.ragged else None
             sm = self.model._forecast_step_mask(self.batch, self.uniforms, self.forecast, self.dropout, ragged=ragged)  # noqa: SLF001
             out = self.model._elbo_step(self.batch, self.uniforms, sm, schedule=self.schedule)  # noqa: SLF001
         elif self.ragged:  # (the host rule was checked by step(); lengths AND dropout in one launch, inside the capture)
             sm = self.model._ragged_step_mask(self.batch, self.uniforms, self.dropout, self.valid_global, self.dp.world, self.dp.rank)  # noqa: SLF001
-            out = self.model._elbo_step(self.batch, self.uniforms, sm, carry, self.schedule)  # noqa: SLF001
+            out = self.model._elbo_step(self.batch, self.uniforms, sm, carry, self.schedule, overshoot=plan)  # noqa: SLF001
         elif carry is not None:
             sm = self.model._step_mask(self.batch, self.uniforms, None, self.dropout)  # noqa: SLF001
-            out = self.model._elbo_step(self.batch, self.uniforms, sm, carry, self.schedule)  # noqa: SLF001
+            out = self.model._elbo_step(self.batch, self.uniforms, sm, carry, self.schedule, overshoot=plan)  # noqa: SLF001
         else:
-            out = self.model.shared_step(self.batch, self.uniforms, modality_dropout=self.dropout, elbo_schedule=self.schedule)
+            out = self.model.shared_step(self.batch, self.uniforms, modality_dropout=self.dropout, elbo_schedule=self.schedule,
+                                         overshoot=self.overshoot)
         out["loss"].backward()
         keys = list(out)
         if self.fused_optimizer:

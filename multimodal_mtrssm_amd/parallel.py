@@ -21,6 +21,7 @@ from multimodal_mtrssm_amd.dropout import ModalityDropout
 from multimodal_mtrssm_amd.forecast import Forecast
 from multimodal_mtrssm_amd.optim import FlatParameters
 from multimodal_mtrssm_amd.likelihood import LikelihoodBound
+from multimodal_mtrssm_amd.overshoot import LatentOvershoot
 from multimodal_mtrssm_amd.particle import ParticleFilter
 from multimodal_mtrssm_amd.probe import LatentProbe
 from multimodal_mtrssm_amd.skill import ForecastSkill
@@ -96,6 +97,14 @@ class FlatDataParallel:
         """``forecast`` bound to this rank's rows of the global batch: pass the result as ``shared_step``'s ``forecast`` (or set it as
         ``model.forecast``) and draw ``u_context`` with ``noise_source``."""
         return forecast.for_rank(self.world, self.rank)
+
+    def overshoot(self, overshoot: LatentOvershoot) -> LatentOvershoot:
+        """``overshoot`` bound to this rank's rows of the global batch and to this object's process group: pass the result as
+        ``shared_step``'s ``overshoot`` (or set it as ``model.overshoot`` / ``model.val_overshoot``) and draw ``u_overshoot`` with
+        ``noise_source`` (batch row first: every rank keeps its own rows).  A batch with lengths carries ``valid_global``."""
+        bound = overshoot.for_rank(self.world, self.rank)
+        bound.group = self.group
+        return bound
 
     def skill(self, skill: ForecastSkill) -> ForecastSkill:
         """``skill`` bound to this object's process group: set the result as ``model.val_skill`` and ``on_validation_epoch_end``

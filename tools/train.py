@@ -10,11 +10,12 @@
                  "scheduler": {"factor": 0.5, "patience": 50}, "early_stopping": {"patience": 100}, "monitor": "val/loss",
                  "max_steps": null, "save_every_n_steps": null, "check_every_n_steps": 50,
                  "modality_dropout": {"p_audio": 0.3, "p_vision": 0.3, "span": 5}, "elbo_schedule": {"free_nats": 1.0}, "state_carry": false,
+                 "overshoot": {"depth": 5, "stride": 5}, "val_overshoot": {"depth": 5},
                  "panel_logger": {"every_n_epochs": 10, "indices": [0, 1, 2], "query_length": 10, "fps": 10.0}},
      "panel": {"scale": 2}}
 
 `model` / `dims` are `word_transitions.py`'s `--model` / `--dims`; every key of `trainer` is optional (the values above are the defaults,
-which are the reference's `default.yaml:103-155`; the four objects at the end default to none; `panel` holds `render_episodes.py`'s
+which are the reference's `default.yaml:103-155`; the objects from `modality_dropout` on default to none; `panel` holds `render_episodes.py`'s
 keywords of `EpisodePanel` for the logger's videos, so one file serves both tools).  The data are `word_transitions.py`'s
 `.npz` episodes (`audio (T, 32, 32)`, `image (T, 1, 32, 32)`, `speaker (T, 6)`), cut to their common length, split 80 / 20 in sorted
 file order as the reference's data module splits its files.  A config with the `data:` block of INTEGRATION.md section 2b (`class_path`
@@ -105,7 +106,7 @@ def main() -> None:
     dev = "cuda:0"
     torch.manual_seed(args.seed)
     model = build_model(cfg.get("model", "mrssm"), tuple(int(x) for x in cfg.get("dims", (32, 32, 4, 4, 64))), dev)
-    flat = FlatParameters(model)
+    flat = FlatParameters(model, extra=12 if tc.get("overshoot") else 8)  # (the overshoot term adds up to two logged scalars)
     dp = mt.FlatDataParallel(flat)
     dp.broadcast_parameters(0)
     opt = mt.FlatAdamW(flat, lr=float(tc.get("lr", 1e-3)), clip_norm=float(tc.get("clip_norm", 10.0)))
@@ -125,6 +126,10 @@ def main() -> None:
         model.modality_dropout = mt.ModalityDropout(**tc["modality_dropout"])
     if tc.get("elbo_schedule"):
         model.elbo_schedule = mt.ElboSchedule(**tc["elbo_schedule"])
+    if tc.get("overshoot"):
+        model.overshoot = mt.LatentOvershoot(**tc["overshoot"])
+    if tc.get("val_overshoot"):
+        model.val_overshoot = dp.overshoot(mt.LatentOvershoot(**tc["val_overshoot"]))
     if tc.get("state_carry"):
         model.state_carry = mt.StateCarry.for_model(model, train.batch_size // dp.world)
     sched, stop = tc.get("scheduler", {"factor": 0.5, "patience": 50}), tc.get("early_stopping", {"patience": 100})
