@@ -1019,6 +1019,42 @@ int mtrssm_overshoot_kl_bwd(const float* post_logits, const float* os_logits, co
                             int64_t b_global, int64_t row0, int64_t b_local, int64_t T, int64_t N, int64_t s, int64_t o, int64_t D, int64_t K,
                             int64_t C, float w_prior, float w_post, float* g_os_logits, float* g_post_logits, void* stream);
 
+/* Latent census: what the categorical latent of a posterior rollout does, per categorical, in one pass.
+ * A census step gives row b G copies (1 <= G <= 4) that share the row's uniforms; copy g is scan row r = b * G + g.  Frame t of row b
+ * is live iff t < clamp(valid[b], 0, T) (valid [B] int32 in DEVICE memory; NULL: every frame is live).
+ * mtrssm_latent_census: post_logits / prior_logits / stoch [B * G][T][K * C] (one level of a rollout: its logits and its one-hot
+ *   posterior sample).  Per live frame and categorical k, with lq / lp the log-softmax of the posterior / prior logits (max, log-sum
+ *   and differences in double, classes in ascending order, as mtrssm_latent_log_ratio), q = exp(lq), p = exp(lp), c* the first class
+ *   with stoch > 0.5 (class 0 when there is none) and lq0 the lq of scan row b * G (the row's first copy):
+ *     hq_k = -sum_c q_c lq_c;  hp_k = -sum_c p_c lp_c                         (a class with probability 0 adds 0)
+ *     kl_k = sum_c q_c (lq_c - lp_c);  cross_k = sum_c q0_c (lq0_c - lq_c)   (exactly 0 for g = 0 and for bitwise-equal logits)
+ *     sw_k = 1 if t >= 1 and c*_k(t) != c*_k(t - 1), else 0
+ *   planes [5][B * G][T] fp32 (may be NULL): post_entropy, prior_entropy, kl, cross, switches -- each the sum over k in ascending k of
+ *   the quantity above, rounded to fp32 once, exactly 0 on a dead frame; kl and cross are not clamped.
+ *   table [G][GS] double, IN/OUT (batches add up in it), GS = 3 K C + 5 K + 2 + 6 T; a group's block holds, in this order:
+ *     n [K][C] (live frames with c*_k = c), qsum [K][C] (sum of q_c), psum [K][C] (sum of p_c),
+ *     hq, hp, kl, cross, sw [K] each (sums of the per-categorical values), frames (live frames), pairs (live frames with t >= 1),
+ *     the position sums [5][T] (the fp32 planes read back as doubles) and the live rows per position [T].
+ *   Fold order, fixed by the shapes alone: a row's partial of every cell of n .. sw is a left fold from +0 over its live frames in
+ *   ascending t; the step's sum of a cell is a left fold from +0 over the rows' partials in ascending b; that sum is added, in one
+ *   add, onto what the table's cell holds.  The position sums likewise: plane[p][b * G + g][t] in ascending b from +0 (dead frames,
+ *   exactly 0, included), then one add onto the cell -- a float64 left fold of the returned planes on the host reproduces a step's
+ *   sums bit for bit, and a second call of the same step doubles the table exactly.  The counts are whole numbers.  No atomics;
+ *   two calls agree bitwise; a row's planes depend on that row and on its first copy only.
+ *   Two launches.  The first gives a scan row to one wave: lane j owns categorical k0 + j of a span of at most 64 categoricals; with
+ *   C <= 512 the span's 3 (g > 0: 4) x nk x C floats are staged in LDS with coalesced loads, C > 512 is read in place; with K <= 64
+ *   and K * C <= 512 the row's partial stays in LDS until the row ends, else the owning lane updates it in `workspace`.  The second
+ *   adds the partials and the planes, one thread per cell of the table.  Any C >= 1.
+ *   `workspace`: mtrssm_latent_census_workspace_bytes(B, G, T, K, C) bytes, 8-byte aligned (the row partials, the planes of a call
+ *   without them, the previous classes); -1 for sizes out of range.  Runs on the caller's stream; nothing is allocated or read back.
+ *   Null post_logits / prior_logits / stoch / table / workspace, B, T, K or C <= 0, G outside 1 .. 4, B * G * T >= 2^24,
+ *   B * G * T * K * C >= 2^31, a pointer that is not 4-byte (table, workspace: 8-byte) aligned or a short workspace return -1 without
+ *   a launch. */
+int64_t mtrssm_latent_census_workspace_bytes(int64_t B, int64_t G, int64_t T, int64_t K, int64_t C);
+int mtrssm_latent_census(const float* post_logits, const float* prior_logits, const float* stoch, const int32_t* valid, int64_t B, int64_t G,
+                         int64_t T, int64_t K, int64_t C, float* planes, double* table, void* workspace, int64_t workspace_bytes,
+                         void* stream);
+
 /* Linear word probes: one fused step of G multinomial-logistic classifiers over N feature rows.
  *   x [G][N][ld] fp32, of which columns [col0, col0 + F) are read; labels [N] int32 in DEVICE memory, shared by the groups: frame n is
  *   live iff 0 <= labels[n] < C (-1 = silence, a frame past its row's end); weight [G][C][F], bias [G][C].  Per group g and live frame n:

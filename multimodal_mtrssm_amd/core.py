@@ -22,6 +22,7 @@ from torch import Tensor, nn
 from multimodal_mtrssm_amd import cnn, conv, scan
 from multimodal_mtrssm_amd._shared import _check_lengths, _masked_mean_embed, _pairable, _rand
 from multimodal_mtrssm_amd.carry import StateCarry
+from multimodal_mtrssm_amd.census import CensusTable, LatentCensus
 from multimodal_mtrssm_amd.distributions import MultiOneHot, MultiOneHotFactory, draw_uniforms, kl_divergence, onehot_from_uniforms
 from multimodal_mtrssm_amd.dropout import ModalityDropout, StepMask, ragged_step_mask
 from multimodal_mtrssm_amd.evaluation import _Evaluators
@@ -504,6 +505,8 @@ class MoPoE_MRSSM(_Evaluators, _Base):  # noqa: N801
         self.val_overshoot: LatentOvershoot | None = None  # validation_step adds an overshoot pass into self.overshoot_table
         self.overshoot_table: OvershootTable | None = None  # ... logged as val/overshoot/* and cleared by on_validation_epoch_end
         self._overshoot_terms_last: list[OvershootTerms] | None = None  # the last overshoot step's terms per level (detached use only)
+        self.val_census: LatentCensus | None = None  # validation_step adds a census step into self.census_table
+        self.census_table: CensusTable | None = None  # ... logged as val/latent/* and cleared by on_validation_epoch_end
         # weighted MoPoE: assign an ExpertWeights (a submodule: before FlatParameters is built); None = 1/3 each, no new
         # state-dict keys.  After every posterior rollout with weights, weights_timeseries is ExpertWeights.table(...) [B, T, 3]
         self.expert_weights: ExpertWeights | None = None
@@ -1187,13 +1190,16 @@ class MoPoE_MRSSM(_Evaluators, _Base):  # noqa: N801
             if self.overshoot_table is None:
                 self.overshoot_table = OvershootTable(len(terms), self.val_overshoot.depth, terms[0].table.device)
             self.overshoot_table.fold([t.table for t in terms])
+        if self.val_census is not None:  # (last: every draw above is what it is without it)
+            self.census_table = self.latent_census(batch, self.val_census, table=self.census_table)
         return logged
 
     def on_validation_epoch_end(self) -> dict[str, Tensor]:
         """Logs the epoch's ``val/skill/{audio,vision}/{mean,ens,best,spread}/{obs,h1,h2,h4,h8}`` and
         ``val/loglik/{iw,elbo,audio,vision,latent,ess,gap}`` and ``val/smc/{smc,mean,audio,vision,latent,ess,resampled}`` (each table
         all-reduced once when a process group is initialised; the group is the one ``FlatDataParallel.skill`` / ``.likelihood`` /
-        ``.particle`` bound) and clears the tables.  Without a table: nothing."""
+        ``.particle`` bound) and clears the tables; likewise ``val/overshoot/*`` and the census's ``val/latent/*`` (``CensusTable.scalars``).
+        Without a table: nothing."""
         logged: dict[str, Tensor] = {}
         table, self.skill_table = self.skill_table, None
         if table is not None:
@@ -1211,6 +1217,10 @@ class MoPoE_MRSSM(_Evaluators, _Base):  # noqa: N801
         if curve is not None:
             curve.all_reduce(getattr(self.val_overshoot, "group", None))
             logged.update(curve.scalars("val/overshoot"))
+        census, self.census_table = self.census_table, None
+        if census is not None:
+            census.all_reduce(getattr(self.val_census, "group", None))
+            logged.update(census.scalars("val/latent"))
         if logged:
             self.log_dict(logged, prog_bar=False, sync_dist=False, on_step=False, on_epoch=True)
         return logged

@@ -100,6 +100,9 @@ int overshoot_kl_fwd_launch(const float*, const float*, const int32_t*, int64_t,
                             int64_t, float*, double*, float*, float*, void*, int64_t, hipStream_t);
 int overshoot_kl_bwd_launch(const float*, const float*, const int32_t*, const float*, const float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                             int64_t, int64_t, int64_t, int64_t, float, float, float*, float*, hipStream_t);
+int64_t latent_census_workspace_bytes(int64_t, int64_t, int64_t, int64_t, int64_t);
+int latent_census_launch(const float*, const float*, const float*, const int32_t*, int64_t, int64_t, int64_t, int64_t, int64_t, float*, double*, void*,
+                         int64_t, hipStream_t);
 int64_t linear_probe_workspace_bytes(int64_t, int64_t, int64_t, int64_t);
 int linear_probe_step_launch(const float*, int64_t, int64_t, const int32_t*, const float*, const float*, int64_t, int64_t, int64_t, int64_t, int, float*,
                              float*, float*, float*, float*, int32_t*, void*, int64_t, hipStream_t);
@@ -558,6 +561,15 @@ MTRSSM_API int mtrssm_overshoot_kl_bwd(const float* post_logits, const float* os
                                        float* g_post_logits, void* stream) {
   return overshoot_kl_bwd_launch(post_logits, os_logits, valid, g_term, count, b_global, row0, b_local, T, N, s, o, D, K, C, w_prior, w_post,
                                  g_os_logits, g_post_logits, static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int64_t mtrssm_latent_census_workspace_bytes(int64_t B, int64_t G, int64_t T, int64_t K, int64_t C) {
+  return latent_census_workspace_bytes(B, G, T, K, C);
+}
+MTRSSM_API int mtrssm_latent_census(const float* post_logits, const float* prior_logits, const float* stoch, const int32_t* valid, int64_t B,
+                                    int64_t G, int64_t T, int64_t K, int64_t C, float* planes, double* table, void* workspace,
+                                    int64_t workspace_bytes, void* stream) {
+  return latent_census_launch(post_logits, prior_logits, stoch, valid, B, G, T, K, C, planes, table, workspace, workspace_bytes,
+                              static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int64_t mtrssm_linear_probe_workspace_bytes(int64_t G, int64_t N, int64_t C, int64_t F) {
   return linear_probe_workspace_bytes(G, N, C, F);

@@ -1,5 +1,5 @@
-"""The evaluation steps of the models: forecast skill, word transitions, held-out likelihood, latent probes and
-episode panels.
+"""The evaluation steps of the models: forecast skill, word transitions, held-out likelihood, latent probes,
+episode panels and the latent census.
 
 Every one of them runs ONE masked posterior rollout over ``B x copies`` rows and then scores it.  What differs between them is what a
 copy of a row is -- what it observes, up to which frame, whether it shares the row's uniforms, where it lies among the scan's rows -- and
@@ -20,6 +20,7 @@ from torch import Tensor
 
 from multimodal_mtrssm_amd import cnn, conv
 from multimodal_mtrssm_amd._shared import _check_lengths, _masked_mean_embed, _pairable, _rand
+from multimodal_mtrssm_amd.census import CensusTable, LatentCensus
 from multimodal_mtrssm_amd.digits import DigitClassifier, word_counts
 from multimodal_mtrssm_amd.distributions import MultiOneHotFactory
 from multimodal_mtrssm_amd.forecast import Forecast
@@ -555,6 +556,42 @@ class _Evaluators:
         live = ((flat >= 0) & (flat < linear.classes)).reshape(B, T)
         table.fold(stats.hit.reshape(G, B, T), stats.nll.reshape(G, B, T), live)
         table.stats = stats
+        return table
+
+    # -- latent census --------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def latent_census(self, batch: tuple[Tensor, ...], census: LatentCensus, noise: Noise | None = None, lengths: Tensor | None = None,  # noqa: PLR0913
+                      table: CensusTable | None = None, *, keep_states: bool = False, expert_log_weights: Tensor | None = None) -> CensusTable:
+        """One census step (``census.py`` states the quantity): both encoders once, then ONE masked posterior
+        rollout over ``B * G`` rows (row ``b * G + g``; copy ``g`` observes ``census.observe[g]`` on every live step and nothing after a
+        row's end; the copies share the row's uniforms, ``census.noise_shapes``) and one ``LatentCensus.fold`` per latent level
+        (``mtrssm_latent_census``), added into ``table`` (a new one when None), which is returned.  No decoder runs and nothing is read
+        back.  ``lengths`` (or a batch that carries ``valid_global``) as in ``likelihood_bound``.  ``keep_states``: ``table.planes`` is
+        the step's planes per level (fp32 ``[5, B * G, T]`` each), ``table.inputs`` what each level's fold read (``post_logits``,
+        ``prior_logits``, ``post_stoch``: the scan's raw outputs ``[B * G, T, K * C]``), ``table.valid`` the rows' lengths (or None) and
+        ``table.states`` the posterior state sequence ``[B * G, T, .]``, whose distributions hold normalised logits.
+        No masked (7-tuple) batch, no ``state_carry``; a weighted model runs its gate once per row."""
+        self._check_evaluation_step(batch, "census", census, LatentCensus, table, CensusTable)
+        (B, T), dev = batch[0].shape[:2], batch[0].device  # noqa: N806
+        levels = tuple((suffix.lstrip("_"), factory.category_size, factory.class_size) for suffix, factory in self._latent_levels())
+        if table is not None and table.levels != levels:
+            msg = f"table must be a CensusTable of the levels {levels}, got {table.levels}"
+            raise ValueError(msg)
+        out, valid = self._evaluation_rollout(batch, census.plan(), noise, lengths, expert_log_weights)
+        if table is None:
+            table = CensusTable(levels, census.groups, T, dev, census.observe)
+        table.active_nats = census.active_nats
+        planes, inputs = [], []
+        for level, (suffix, factory) in enumerate(self._latent_levels()):
+            read = tuple(out[f"{name}{suffix}"].float() for name in ("post_logits", "prior_logits", "post_stoch"))
+            got, _ = LatentCensus.fold(*read, census.groups, factory.category_size, factory.class_size, valid, table=table.level_view(level),
+                                       planes=keep_states)
+            planes.append(got)
+            inputs.append(read)
+        table.planes = planes if keep_states else None
+        table.inputs = inputs if keep_states else None
+        table.states = self._posterior_from_rollout(out) if keep_states else None
+        table.valid = valid if keep_states else None
         return table
 
     # -- word transitions (DESIGN.md 6j) -----------------------------------------------------------------------------------------------------

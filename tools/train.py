@@ -11,6 +11,7 @@
                  "max_steps": null, "save_every_n_steps": null, "check_every_n_steps": 50,
                  "modality_dropout": {"p_audio": 0.3, "p_vision": 0.3, "span": 5}, "elbo_schedule": {"free_nats": 1.0}, "state_carry": false,
                  "overshoot": {"depth": 5, "stride": 5}, "val_overshoot": {"depth": 5},
+                 "val_census": {"observe": ["both", "audio", "vision"], "active_nats": 0.01},
                  "panel_logger": {"every_n_epochs": 10, "indices": [0, 1, 2], "query_length": 10, "fps": 10.0}},
      "panel": {"scale": 2}}
 
@@ -130,6 +131,11 @@ def main() -> None:
         model.overshoot = mt.LatentOvershoot(**tc["overshoot"])
     if tc.get("val_overshoot"):
         model.val_overshoot = dp.overshoot(mt.LatentOvershoot(**tc["val_overshoot"]))
+    if tc.get("val_census"):
+        block = dict(tc["val_census"])
+        if "observe" in block:
+            block["observe"] = tuple(block["observe"])
+        model.val_census = dp.census(mt.LatentCensus(**block))
     if tc.get("state_carry"):
         model.state_carry = mt.StateCarry.for_model(model, train.batch_size // dp.world)
     sched, stop = tc.get("scheduler", {"factor": 0.5, "patience": 50}), tc.get("early_stopping", {"patience": 100})
