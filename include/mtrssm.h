@@ -1055,6 +1055,27 @@ int mtrssm_latent_census(const float* post_logits, const float* prior_logits, co
                          int64_t T, int64_t K, int64_t C, float* planes, double* table, void* workspace, int64_t workspace_bytes,
                          void* stream);
 
+/* Feature moments by bin: the sufficient statistic of a Frechet distance between Gaussian fits.
+ * mtrssm_feature_moments: x fp32, row n at x + n * ldx (ldx >= D: a padded buffer is read in place); bin [N] int32 in DEVICE memory:
+ *   bin[n] in [0, J) names row n's bin, any other value (-1 by convention) skips the row.
+ *   table [J][1 + D + D * D] double, IN/OUT (calls add up in it); bin j's block holds the count of its rows, sum_n x_n [D] and
+ *   sum_n x_n x_n^T [D][D] -- a full matrix: both triangles are written and are bit-identical.
+ *   Every product x_ni * x_nj is formed in double (exact) on v_mfma_f64_16x16x4_f64 with the contraction over rows; sums in double;
+ *   no atomics.  Bins by masking: for bin j the operands of rows in other bins are zeros (and a group of four rows without a row of
+ *   bin j is skipped, which adds nothing either way).  Order of addition, fixed by (N, D, J) alone: the rows are cut into
+ *   S = min(16, ceil(N / 32)) slices of ceil(N / S) consecutive rows; a slice's partial of a cell starts at +0 and takes its rows four
+ *   at a time in ascending order (the four in the MFMA's own fixed order); the call's sum is a left fold from +0 over the slices
+ *   in ascending order and is added, in one add, onto what the table's cell holds.  Two calls on the same inputs agree bitwise.
+ *   Two launches: one wave per (16 x 16 tile on or above the diagonal, slice) plus one per (16 columns of the sums, slice); then
+ *   one thread per cell of the table, which mirrors the tiles below the diagonal.  Nothing is allocated or read back.
+ *   `workspace`: mtrssm_feature_moments_workspace_bytes(N, D, J) = 8 * S * J * ((P + DT) * 256 + 1) bytes, 8-byte aligned, with
+ *   DT = ceil(D / 16) and P = DT * (DT + 1) / 2 (the slices' tiles, then their counts); -1 for sizes out of range.
+ *   Null x / bin / table / workspace, x or bin not 4-byte (table, workspace: 8-byte) aligned, N < 1, D outside 1 .. 256, J outside
+ *   1 .. 16, N * ldx >= 2^31 (or a product that overflows), ldx < D or a short workspace return -1 without a launch. */
+int64_t mtrssm_feature_moments_workspace_bytes(int64_t N, int D, int J);
+int mtrssm_feature_moments(const float* x, int64_t ldx, const int32_t* bin, int64_t N, int D, int J, double* table, void* workspace,
+                           int64_t workspace_bytes, void* stream);
+
 /* Linear word probes: one fused step of G multinomial-logistic classifiers over N feature rows.
  *   x [G][N][ld] fp32, of which columns [col0, col0 + F) are read; labels [N] int32 in DEVICE memory, shared by the groups: frame n is
  *   live iff 0 <= labels[n] < C (-1 = silence, a frame past its row's end); weight [G][C][F], bias [G][C].  Per group g and live frame n:

@@ -23,6 +23,8 @@ from multimodal_mtrssm_amd import cnn, conv, scan
 from multimodal_mtrssm_amd._shared import _check_lengths, _masked_mean_embed, _pairable, _rand
 from multimodal_mtrssm_amd.carry import StateCarry
 from multimodal_mtrssm_amd.census import CensusTable, LatentCensus
+from multimodal_mtrssm_amd.digits import DigitClassifier
+from multimodal_mtrssm_amd.frechet import FrechetDistance, FrechetTable
 from multimodal_mtrssm_amd.distributions import MultiOneHot, MultiOneHotFactory, draw_uniforms, kl_divergence, onehot_from_uniforms
 from multimodal_mtrssm_amd.dropout import ModalityDropout, StepMask, ragged_step_mask
 from multimodal_mtrssm_amd.evaluation import _Evaluators
@@ -460,6 +462,12 @@ def check_ragged_rows(valid_host: Tensor, reset_host: Tensor | None) -> None:
 class MoPoE_MRSSM(_Evaluators, _Base):  # noqa: N801
     """Multimodal RSSM with MoPoE posteriors: PoE of {audio, vision}, then MoE over {A, V, A+V}."""
 
+    def __setattr__(self, name: str, value: object) -> None:
+        if name == "frechet_classifier":  # an evaluation tool, not a part of the model: no submodule, no state-dict keys
+            object.__setattr__(self, name, value)
+            return
+        super().__setattr__(name, value)
+
     def __init__(  # noqa: PLR0913
         self,
         *,
@@ -507,6 +515,9 @@ class MoPoE_MRSSM(_Evaluators, _Base):  # noqa: N801
         self._overshoot_terms_last: list[OvershootTerms] | None = None  # the last overshoot step's terms per level (detached use only)
         self.val_census: LatentCensus | None = None  # validation_step adds a census step into self.census_table
         self.census_table: CensusTable | None = None  # ... logged as val/latent/* and cleared by on_validation_epoch_end
+        self.val_frechet: FrechetDistance | None = None  # validation_step adds a Frechet step into self.frechet_table
+        self.frechet_table: FrechetTable | None = None  # ... logged as val/frechet/* and cleared by on_validation_epoch_end
+        self.frechet_classifier: DigitClassifier | None = None  # the reader of val_frechet's features="reader" (not a submodule)
         # weighted MoPoE: assign an ExpertWeights (a submodule: before FlatParameters is built); None = 1/3 each, no new
         # state-dict keys.  After every posterior rollout with weights, weights_timeseries is ExpertWeights.table(...) [B, T, 3]
         self.expert_weights: ExpertWeights | None = None
@@ -1192,13 +1203,16 @@ class MoPoE_MRSSM(_Evaluators, _Base):  # noqa: N801
             self.overshoot_table.fold([t.table for t in terms])
         if self.val_census is not None:  # (last: every draw above is what it is without it)
             self.census_table = self.latent_census(batch, self.val_census, table=self.census_table)
+        if self.val_frechet is not None:  # (last: every draw above is what it is without it)
+            self.frechet_table = self.frechet_distance(batch, self.val_frechet, self.frechet_classifier, table=self.frechet_table)
         return logged
 
     def on_validation_epoch_end(self) -> dict[str, Tensor]:
         """Logs the epoch's ``val/skill/{audio,vision}/{mean,ens,best,spread}/{obs,h1,h2,h4,h8}`` and
         ``val/loglik/{iw,elbo,audio,vision,latent,ess,gap}`` and ``val/smc/{smc,mean,audio,vision,latent,ess,resampled}`` (each table
         all-reduced once when a process group is initialised; the group is the one ``FlatDataParallel.skill`` / ``.likelihood`` /
-        ``.particle`` bound) and clears the tables; likewise ``val/overshoot/*`` and the census's ``val/latent/*`` (``CensusTable.scalars``).
+        ``.particle`` bound) and clears the tables; likewise ``val/overshoot/*``, the census's ``val/latent/*`` (``CensusTable.scalars``)
+        and the Frechet distances ``val/frechet/*`` (``FrechetTable.scalars``).
         Without a table: nothing."""
         logged: dict[str, Tensor] = {}
         table, self.skill_table = self.skill_table, None
@@ -1221,6 +1235,10 @@ class MoPoE_MRSSM(_Evaluators, _Base):  # noqa: N801
         if census is not None:
             census.all_reduce(getattr(self.val_census, "group", None))
             logged.update(census.scalars("val/latent"))
+        moments, self.frechet_table = self.frechet_table, None
+        if moments is not None:
+            moments.all_reduce(getattr(self.val_frechet, "group", None))
+            logged.update(moments.scalars("val/frechet"))
         if logged:
             self.log_dict(logged, prog_bar=False, sync_dist=False, on_step=False, on_epoch=True)
         return logged

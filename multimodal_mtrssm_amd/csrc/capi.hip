@@ -103,6 +103,8 @@ int overshoot_kl_bwd_launch(const float*, const float*, const int32_t*, const fl
 int64_t latent_census_workspace_bytes(int64_t, int64_t, int64_t, int64_t, int64_t);
 int latent_census_launch(const float*, const float*, const float*, const int32_t*, int64_t, int64_t, int64_t, int64_t, int64_t, float*, double*, void*,
                          int64_t, hipStream_t);
+int64_t feature_moments_workspace_bytes(int64_t, int, int);
+int feature_moments_launch(const float*, int64_t, const int32_t*, int64_t, int, int, double*, void*, int64_t, hipStream_t);
 int64_t linear_probe_workspace_bytes(int64_t, int64_t, int64_t, int64_t);
 int linear_probe_step_launch(const float*, int64_t, int64_t, const int32_t*, const float*, const float*, int64_t, int64_t, int64_t, int64_t, int, float*,
                              float*, float*, float*, float*, int32_t*, void*, int64_t, hipStream_t);
@@ -570,6 +572,11 @@ MTRSSM_API int mtrssm_latent_census(const float* post_logits, const float* prior
                                     int64_t workspace_bytes, void* stream) {
   return latent_census_launch(post_logits, prior_logits, stoch, valid, B, G, T, K, C, planes, table, workspace, workspace_bytes,
                               static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int64_t mtrssm_feature_moments_workspace_bytes(int64_t N, int D, int J) { return feature_moments_workspace_bytes(N, D, J); }
+MTRSSM_API int mtrssm_feature_moments(const float* x, int64_t ldx, const int32_t* bin, int64_t N, int D, int J, double* table, void* workspace,
+                                      int64_t workspace_bytes, void* stream) {
+  return feature_moments_launch(x, ldx, bin, N, D, J, table, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int64_t mtrssm_linear_probe_workspace_bytes(int64_t G, int64_t N, int64_t C, int64_t F) {
   return linear_probe_workspace_bytes(G, N, C, F);

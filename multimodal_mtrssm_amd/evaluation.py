@@ -1,5 +1,5 @@
-"""The evaluation steps of the models (DESIGN.md 6h - 6o, 6q, 6s): forecast skill, word transitions, held-out likelihood, latent probes,
-episode panels and the latent census.
+"""The evaluation steps of the models (DESIGN.md 6h - 6o, 6q, 6s, 6t): forecast skill, word transitions, held-out likelihood, latent probes,
+episode panels, the latent census and the Frechet distance of sampled frames.
 
 Every one of them runs ONE masked posterior rollout over ``B x copies`` rows and then scores it.  What differs between them is what a
 copy of a row is -- what it observes, up to which frame, whether it shares the row's uniforms, where it lies among the scan's rows -- and
@@ -18,12 +18,13 @@ from dataclasses import dataclass
 import torch
 from torch import Tensor
 
-from multimodal_mtrssm_amd import cnn, conv
+from multimodal_mtrssm_amd import cnn, conv, digits, frechet, linear
 from multimodal_mtrssm_amd._shared import _check_lengths, _masked_mean_embed, _pairable, _rand
 from multimodal_mtrssm_amd.census import CensusTable, LatentCensus
 from multimodal_mtrssm_amd.digits import DigitClassifier, word_counts
 from multimodal_mtrssm_amd.distributions import MultiOneHotFactory
 from multimodal_mtrssm_amd.forecast import Forecast
+from multimodal_mtrssm_amd.frechet import FrechetDistance, FrechetTable
 from multimodal_mtrssm_amd.likelihood import PLANES as LIKELIHOOD_PLANES
 from multimodal_mtrssm_amd.likelihood import LikelihoodBound, LikelihoodTable
 from multimodal_mtrssm_amd.panel import EpisodePanel, EpisodeVideo
@@ -592,6 +593,97 @@ class _Evaluators:
         table.inputs = inputs if keep_states else None
         table.states = self._posterior_from_rollout(out) if keep_states else None
         table.valid = valid if keep_states else None
+        return table
+
+    # -- Frechet distance on reader / encoder features ------------------------------------------------------------------------
+    @staticmethod
+    def _reader_features(classifier: DigitClassifier, frames: Tensor, act: int) -> Tensor:
+        """``[>= N, 128]`` fp32: ``classifier.hidden(classifier.features(frames, act))`` of ``N`` 32 x 32 frames -- the trunk writes into a
+        buffer padded to whole 128-row tiles when ``fc1`` is large enough for the tile GEMM (as ``DigitClassifier.read`` does; the pad
+        rows are zeros and rows do not mix); the first ``N`` rows are the frames'.  Non-GPU tensors take the torch rule."""
+        n = frames.numel() // digits.PIXELS
+        if not frames.is_cuda:
+            f = classifier.reference_features(frames, act)
+            return torch.relu(torch.nn.functional.linear(f, classifier.fc1.weight, classifier.fc1.bias))
+        rows = n
+        if 2.0 * n * digits.HIDDEN * digits.FEATURES >= linear.SPLIT_MIN_FLOPS:
+            rows = -(-n // 128) * 128
+        buf = torch.empty(rows, digits.FEATURES, device=frames.device, dtype=torch.float32)
+        if rows > n:
+            buf[n:].zero_()
+        classifier.features(frames, act, out=buf)
+        return classifier.hidden(buf)
+
+    def _check_frechet(self, fd: FrechetDistance, classifier: DigitClassifier | None) -> int:
+        """The refusals of a Frechet step beyond the shared ones; returns ``D``."""
+        if fd.features == "reader":
+            _must_be("classifier", classifier, DigitClassifier)
+            return digits.HIDDEN
+        embed = int(self.audio_representation.obs_embed_size)
+        if embed > frechet.MAX_DIM:
+            msg = f"features='encoder' keeps a full {embed} x {embed} second moment per bin: the embedding may have at most {frechet.MAX_DIM} features"
+            raise ValueError(msg)
+        return embed
+
+    @torch.no_grad()
+    def frechet_distance(self, batch: tuple[Tensor, ...], fd: FrechetDistance, classifier: DigitClassifier | None = None,  # noqa: PLR0913, PLR0914
+                         noise: Noise | None = None, lengths: Tensor | None = None, table: FrechetTable | None = None, *,
+                         keep_states: bool = False, expert_log_weights: Tensor | None = None) -> FrechetTable:
+        """One Frechet step (``frechet.py`` states the quantity): ``forecast_skill``'s rollout (the same plan and
+        noise: ``fd.samples`` futures per row after ``fd.context`` observed frames, scan row ``b * S + s``), the decoders over chunks of
+        whole rows, the frames embedded -- ``fd.features == "reader"``: the vision frames through ``classifier.features`` and
+        ``classifier.hidden`` (the decoder must give 1 x 32 x 32 frames; only vision is decoded); ``"encoder"``: both modalities'
+        activated frames through the model's own encoders -- and one ``FrechetDistance.fold`` (``mtrssm_feature_moments``) per chunk
+        and stream into the generated side of ``table`` (a new one when None), which is returned.  The real side takes the TARGET frames
+        of the batch through the same feature path, once per ``(b, t)``, with the same bins.  A frame's bin is its horizon's
+        (``fd.edges``); a dead frame (``lengths``, or a batch that carries ``valid_global``) has bin -1.  Nothing is read back.
+        ``keep_states``: ``table.features[stream] = (real [B * T, D], generated [B * S * T, D])``, ``table.bins = (real, generated)``
+        and ``table.states``.  No masked (7-tuple) batch, no ``state_carry``; a weighted model runs its gate as in ``forecast_skill``."""
+        self._check_evaluation_step(batch, "fd", fd, FrechetDistance)
+        dim = self._check_frechet(fd, classifier)
+        (B, T), dev = batch[0].shape[:2], batch[0].device  # noqa: N806
+        S, names, reader = fd.samples, fd.bin_names, fd.features == "reader"  # noqa: N806
+        J = len(names)  # noqa: N806
+        if table is not None and (not isinstance(table, FrechetTable) or not table.matches(fd.streams, dim, names) or table.buffer.device != dev):
+            msg = f"table must be a FrechetTable of the streams {fd.streams}, {dim} features and the bins {names} on {dev}"
+            raise ValueError(msg)
+        targets = self.get_targets_from_batch(batch)
+        if reader and targets["recon/vision"][0, 0].numel() != digits.PIXELS:
+            msg = f"the digit classifier reads 1 x 32 x 32 vision frames, the batch holds {tuple(targets['recon/vision'].shape[2:])}"
+            raise ValueError(msg)
+        out, valid = self._evaluation_rollout(batch, fd.plan(), noise, lengths, expert_log_weights)
+        feature = self._feature_of(out)
+        if table is None:
+            table = FrechetTable(fd.streams, dim, names, dev)
+        bins_real = fd.bins(B, T, valid, dev)  # [B, T]
+        bins_gen = bins_real[:, None, :].expand(B, S, T).contiguous()  # row (b, s, t)
+        kept: dict[str, tuple[list[Tensor], list[Tensor]]] = {name: ([], []) for name in fd.streams}
+        for r0, r1 in _row_chunks(B, S * T, fd.max_frames):
+            n = r1 - r0
+            preds, acts = self._decode_for_score(feature[r0 * S : r1 * S], audio=not reader)
+            if reader:
+                pred = preds[1]
+                if pred.numel() != n * S * T * digits.PIXELS:
+                    msg = f"the digit classifier reads 1 x 32 x 32 vision frames, the decoder gives {tuple(pred.shape[2:])}"
+                    raise ValueError(msg)
+                sides = {"vision": (self._reader_features(classifier, targets["recon/vision"][r0:r1], 0),
+                                    self._reader_features(classifier, pred, acts[1]))}
+            else:
+                ya, yv = (torch.tanh(p) if a == 3 else p for p, a in zip(preds, acts, strict=True))  # noqa: PLR2004
+                ea_g, ev_g = self._encode_both(ya.to(torch.float32), yv.to(torch.float32))
+                ea_r, ev_r = self._encode_both(targets["recon/audio"][r0:r1], targets["recon/vision"][r0:r1])
+                sides = {"audio": (ea_r.reshape(n * T, -1), ea_g.reshape(n * S * T, -1)),
+                         "vision": (ev_r.reshape(n * T, -1), ev_g.reshape(n * S * T, -1))}
+            for name, (real, gen) in sides.items():
+                real, gen = real[: n * T].to(torch.float32), gen[: n * S * T].to(torch.float32)  # noqa: PLW2901  (views: the pad rows stay behind)
+                FrechetDistance.fold(real, bins_real[r0:r1].reshape(-1), J, table.block(name, 0))
+                FrechetDistance.fold(gen, bins_gen[r0:r1].reshape(-1), J, table.block(name, 1))
+                if keep_states:
+                    kept[name][0].append(real)
+                    kept[name][1].append(gen)
+        table.features = {name: (torch.cat(r), torch.cat(g)) for name, (r, g) in kept.items()} if keep_states else None
+        table.bins = (bins_real.reshape(-1), bins_gen.reshape(-1)) if keep_states else None
+        table.states = self._posterior_from_rollout(out) if keep_states else None
         return table
 
     # -- word transitions (DESIGN.md 6j) -----------------------------------------------------------------------------------------------------

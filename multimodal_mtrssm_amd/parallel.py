@@ -18,6 +18,7 @@ from torch import Tensor
 
 from multimodal_mtrssm_amd import conv, linear
 from multimodal_mtrssm_amd.census import LatentCensus
+from multimodal_mtrssm_amd.frechet import FrechetDistance
 from multimodal_mtrssm_amd.dropout import ModalityDropout
 from multimodal_mtrssm_amd.forecast import Forecast
 from multimodal_mtrssm_amd.optim import FlatParameters
@@ -126,6 +127,11 @@ class FlatDataParallel:
         """``census`` bound to this object's process group: set the result as ``model.val_census`` and ``on_validation_epoch_end``
         all-reduces the census table over that group (its uniforms' batch dimension comes first: draw them with ``noise_source``)."""
         return census.for_group(self.group)
+
+    def frechet(self, fd: FrechetDistance) -> FrechetDistance:
+        """``fd`` bound to this object's process group: set the result as ``model.val_frechet`` and ``on_validation_epoch_end``
+        all-reduces the moment table over that group (its uniforms' batch dimension comes first: draw them with ``noise_source``)."""
+        return fd.for_group(self.group)
 
     def probe(self, probe: LatentProbe) -> LatentProbe:
         """``probe`` bound to this object's process group: ``ProbeTable.all_reduce(probe.group)`` and ``LinearProbe.fit(..., group=
