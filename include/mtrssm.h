@@ -678,6 +678,36 @@ int mtrssm_convt_k4s2_thin(int32_t N, int32_t C, int32_t Hs, int32_t Ws, int32_t
 int mtrssm_convt_k4s2_band_supported(int32_t N, int32_t C, int32_t Hs, int32_t Ws, int32_t Cout);
 int mtrssm_convt_k4s2_band(int32_t N, int32_t C, int32_t Hs, int32_t Ws, int32_t Cout, const float* src, const float* w,
                            const float* bias, int32_t pre_act, int32_t act, float* out, void* stream);
+/* The encoders' strided stem (default.yaml:31-60) in ONE launch: three Conv2d(k = 3, s = 2, p = 1) layers with channels
+ * (frame + 2 coordinate planes) -> 8 -> 16 -> 32 and the activation between them,
+ *   y1 = b1 + Conv(src ++ coords),  y2 = b2 + Conv(act(y1)),  y3 = b3 + Conv(act(y2)),
+ * one pass per frame: the frame is read once, y1 / y2 / y3 are written once (the backward pass reads all three), the activated
+ * bf16 pieces of y1 and y2 stay on the chip (csrc/conv_stem.h: encoder_stem_kernel).  Arithmetic of the bf16x2 conv mode (two
+ * bf16 pieces per operand, three products, fp32 accumulation); the coordinate planes' contribution is formed once per
+ * workgroup in fp32.  y2 is bit-identical to mtrssm_conv_gather_gemm's on the same y1; y1 and y3 sum in another order.
+ * wp1 / wq1, wq2, wq3: the layers' packed weights (mtrssm_pack_conv_weight(s): OPad = 32, IPad = 16, two pieces); biases may be
+ * NULL; every tensor contiguous and 16-byte aligned.  A second problem (b != NULL: the other modality, its own plane shape and
+ * frame count) rides in the same grid.
+ * mtrssm_encoder_stem_supported: 1 / 0, a host-side query of the SHAPE fields only (mfma_split == 2, C == 1, C2 == 2,
+ * Cout1..3 == 8, 16, 32, Hs x Ws == 64 x 64 or 128 x 32, act Identity / ReLU / ELU, N * 8192 < 2^31); mtrssm_encoder_stem_fwd on
+ * anything else returns MTRSSM_EINVAL and the caller keeps the per-layer path. */
+typedef struct MtrssmEncoderStem {
+  const float* src;    /* [N][1][Hs][Ws] */
+  const float* coords; /* [2][Hs][Ws] */
+  const float* wp1;
+  const uint16_t* wq1;
+  const float* bias1;
+  const uint16_t* wq2;
+  const float* bias2;
+  const uint16_t* wq3;
+  const float* bias3;
+  float* y1; /* [N][8][Hs/2][Ws/2] */
+  float* y2; /* [N][16][Hs/4][Ws/4] */
+  float* y3; /* [N][32][Hs/8][Ws/8] */
+  int32_t N, C, C2, Hs, Ws, Cout1, Cout2, Cout3, act, mfma_split;
+} MtrssmEncoderStem;
+int mtrssm_encoder_stem_supported(const MtrssmEncoderStem* p);
+int mtrssm_encoder_stem_fwd(const MtrssmEncoderStem* a, const MtrssmEncoderStem* b, void* stream);
 /* Conv2d backward-data / ConvTranspose2d forward with <= 8 output channels, all output parity classes in ONE pass (the general
  * path, mtrssm_conv_gather_gemm, takes one launch per parity class of a strided layer; replaces the backward-data of the
  * encoders' second conv, cnn.Encoder at mrssm core.py:179-180):

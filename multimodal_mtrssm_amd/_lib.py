@@ -88,7 +88,11 @@ ConvGeom = _struct("MtrssmConvGeom", [(n, _i) for n in (
     "N", "C", "Hs", "Ws", "C2", "Cpad", "KH", "KW", "SS", "TS", "OFFY", "OFFX", "Hq", "Wq", "OS", "QY", "QX", "Ho", "Wo",
     "Cout", "CoutPad", "pre_act", "act", "mfma_split")])
 
-Gemm = _struct("MtrssmGemm", _ptrs("A", "B", "C", "bias", "zgrad", "colsum") + [(n, _i) for n in (
+EncoderStem = _struct("MtrssmEncoderStem", _ptrs(
+    "src", "coords", "wp1", "wq1", "bias1", "wq2", "bias2", "wq3", "bias3", "y1", "y2", "y3") + [(n, _i) for n in (
+    "N", "C", "C2", "Hs", "Ws", "Cout1", "Cout2", "Cout3", "act", "mfma_split")])
+
+Gemm = _struct("MtrssmGemm",_ptrs("A", "B", "C", "bias", "zgrad", "colsum") + [(n, _i) for n in (
     "M", "N", "R", "lda", "ldb", "ldc", "ldz", "a_rmajor", "b_rmajor", "act_a", "act_b", "act_out", "act_z", "accumulate", "split_r")]
     + [("tickets", _p), ("n_tickets", _i), ("mfma_split", _i)])
 
@@ -159,6 +163,8 @@ SYMBOLS: dict[str, tuple[type | None, list[type]]] = {
     "mtrssm_convt_k4s2_thin": (C.c_int, [_i, _i, _i, _i, _i, _p, _p, _p, _i, _i, _p, _p]),
     "mtrssm_convt_k4s2_band_supported": (C.c_int, [_i, _i, _i, _i, _i]),
     "mtrssm_convt_k4s2_band": (C.c_int, [_i, _i, _i, _i, _i, _p, _p, _p, _i, _i, _p, _p]),
+    "mtrssm_encoder_stem_supported": (C.c_int, [C.POINTER(EncoderStem)]),
+    "mtrssm_encoder_stem_fwd": (C.c_int, [C.POINTER(EncoderStem), C.POINTER(EncoderStem), _p]),
     "mtrssm_convt_quad_supported": (C.c_int, [C.POINTER(ConvGeom)]),
     "mtrssm_convt_quad": (C.c_int, [C.POINTER(ConvGeom), _p, C.POINTER(C.c_void_p), _p, _p, _p, C.POINTER(ConvGeom), _p, C.POINTER(C.c_void_p),
                                     _p, _p, _p, _p]),

@@ -37,6 +37,7 @@ from multimodal_mtrssm_amd.conv import (
     conv2d_pair,
     conv_transpose2d,
     conv_transpose2d_pair,
+    encoder_stem,
     residual_block,
     residual_block_pair,
 )
@@ -109,9 +110,11 @@ def encode_pair(enc_a: "Encoder", enc_b: "Encoder", xa: Tensor, xb: Tensor) -> t
     xa, ca = enc_a.prepare(xa)
     xb, cb = enc_b.prepare(xb)
     if len(enc_a.convs) == len(enc_b.convs) and (enc_a.res_in is None) == (enc_b.res_in is None):
-        for i, (ma, mb) in enumerate(zip(enc_a.convs, enc_b.convs, strict=True)):
-            xa, xb = _conv_pair(xa, ma, ca if i == 0 else None, xb, mb, cb if i == 0 else None, pre_act=i > 0, act_a=enc_a.act_id,
-                                act_b=enc_b.act_id)
+        # (both strided stems as one launch where the fused kernel has them: the conv calls below then return its outputs)
+        with encoder_stem([enc_a.stem_job(xa, ca), enc_b.stem_job(xb, cb)]):
+            for i, (ma, mb) in enumerate(zip(enc_a.convs, enc_b.convs, strict=True)):
+                xa, xb = _conv_pair(xa, ma, ca if i == 0 else None, xb, mb, cb if i == 0 else None, pre_act=i > 0, act_a=enc_a.act_id,
+                                    act_b=enc_b.act_id)
         if enc_a.res_in is not None:
             xa, xb = _conv_pair(xa, enc_a.res_in, None, xb, enc_b.res_in, None, pre_act=True, act_a=enc_a.act_id, act_b=enc_b.act_id)
     else:
@@ -208,9 +211,14 @@ class Encoder(nn.Module):
         # the coordinate channels are frame-independent: the first conv gathers them from one [2,H,W] plane
         return x, (self._coord_channels(x) if self.coord_conv else None)
 
+    def stem_job(self, x: Tensor, coords: Tensor | None) -> tuple:
+        """This encoder's strided convs as ``conv.encoder_stem`` takes them."""
+        return x, coords, [(m.weight, m.bias, m.stride[0], m.padding[0]) for m in self.convs], self.act_id
+
     def stem_convs(self, x: Tensor, coords: Tensor | None) -> Tensor:
-        for i, conv in enumerate(self.convs):
-            x = _conv(x, conv, pre_act=i > 0, act=self.act_id, coords=coords if i == 0 else None)
+        with encoder_stem([self.stem_job(x, coords)]):
+            for i, conv in enumerate(self.convs):
+                x = _conv(x, conv, pre_act=i > 0, act=self.act_id, coords=coords if i == 0 else None)
         if self.res_in is not None:
             x = _conv(x, self.res_in, pre_act=True, act=self.act_id)
         return x

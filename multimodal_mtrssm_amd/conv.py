@@ -13,6 +13,7 @@ permutes -- a few KB per layer.
 
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import weakref
@@ -315,6 +316,10 @@ def _conv_forward_gather(x: Tensor, coords: Tensor | None, w: Tensor, bias: Tens
     if i != c + c2:
         msg = f"weight expects {i} input channels, got {c}+{c2}"
         raise ValueError(msg)
+    if _STEM_FILLED is not None and actgrad_in is None and add_in is None:
+        out = _STEM_FILLED.pop((x.data_ptr(), w.data_ptr()), None)
+        if out is not None:  # the fused stem launch has computed this layer already (``encoder_stem``)
+            return out
     ho = (hs + 2 * pad - kh) // stride + 1
     wo = (ws + 2 * pad - kw) // stride + 1
     wpq = pack_weight(w)
@@ -324,6 +329,82 @@ def _conv_forward_gather(x: Tensor, coords: Tensor | None, w: Tensor, bias: Tens
                  Hq=ho, Wq=wo, OS=1, QY=0, QX=0, Ho=ho, Wo=wo, Cout=o, CoutPad=wp.shape[0], pre_act=int(pre_act), act=act)
     _gather_gemm(geom, x, coords, wpq, bias, actgrad_in, out, add_in)
     return out
+
+
+# The encoders' strided stem (three Conv2d k3 s2 p1, channels 1 + 2 coordinate planes -> 8 -> 16 -> 32) as ONE launch
+# (``mtrssm_encoder_stem_fwd``, csrc/conv_stem.h).  The autograd graph keeps its three conv nodes: inside ``encoder_stem`` the
+# launch fills y1, y2, y3 first and ``_conv_forward_gather`` then hands each layer the tensor that is already there, keyed by
+# (input, weight), so saved tensors and every backward launch are those of the per-layer path.  MTRSSM_ENCODER_STEM=0: off.
+ENCODER_STEM = os.environ.get("MTRSSM_ENCODER_STEM", "1") != "0"
+_STEM_FILLED: dict[tuple[int, int], Tensor] | None = None
+
+
+def _stem_desc(x: Tensor, coords: Tensor | None, layers: list[tuple], act: int) -> C.Structure | None:
+    """Shape fields of one encoder's fused-stem problem, or None where the fused launch does not apply.
+    ``layers``: ``(weight, bias, stride, padding)`` per conv."""
+    if not ENCODER_STEM or coords is None or len(layers) != 3 or x.dim() != 4 or x.dtype != torch.float32:  # noqa: PLR2004
+        return None
+    if not (x.is_contiguous() and coords.is_contiguous() and coords.dim() == 3 and coords.shape[1:] == x.shape[2:]):  # noqa: PLR2004
+        return None
+    if x.data_ptr() % 16 or coords.data_ptr() % 16 or coords.dtype != torch.float32:
+        return None
+    cin = x.shape[1] + coords.shape[0]
+    for w, b, stride, pad in layers:
+        if (tuple(w.shape[2:]) != (3, 3) or w.shape[1] != cin or stride != 2 or pad != 1 or not w.is_contiguous()  # noqa: PLR2004
+                or (b is not None and not b.is_contiguous())):
+            return None
+        cin = w.shape[0]
+    p = _lib.EncoderStem()
+    p.N, p.C, p.Hs, p.Ws = (int(v) for v in x.shape)
+    p.C2 = int(coords.shape[0])
+    p.Cout1, p.Cout2, p.Cout3 = (int(w.shape[0]) for w, *_ in layers)
+    p.act, p.mfma_split = int(act), _MFMA_SPLIT
+    return p if _lib.load().mtrssm_encoder_stem_supported(C.byref(p)) else None
+
+
+def _stem_launch(jobs: list[tuple]) -> dict[tuple[int, int], Tensor]:
+    """One fused launch for one or two encoders; returns {(layer input address, weight address): filled output}."""
+    filled: dict[tuple[int, int], Tensor] = {}
+    flops = nbytes = 0.0
+    for k, (p, x, coords, layers) in enumerate(jobs):
+        n, _, h, w_ = x.shape
+        src, outs, packs = x, [], []
+        nbytes += 4.0 * x.numel()
+        for w, _b, _s, _p in layers:
+            packs.append(pack_weight(w, sub=100 + k))  # (outside a step's plan: the two encoders' equal-shaped weights apart)
+            h, w_ = h // 2, w_ // 2
+            out = torch.empty(n, w.shape[0], h, w_, device=x.device, dtype=torch.float32)
+            filled[(src.data_ptr(), w.data_ptr())] = out
+            flops += 2.0 * out.numel() * 9 * w.shape[1]
+            nbytes += 4.0 * out.numel()
+            outs.append(out)
+            src = out
+        p.src, p.coords = _lib.ptr(x), _lib.ptr(coords)
+        p.wp1, p.wq1, p.wq2, p.wq3 = _lib.ptr(packs[0][0]), _lib.raw_ptr(packs[0][1]), _lib.raw_ptr(packs[1][1]), _lib.raw_ptr(packs[2][1])
+        p.bias1, p.bias2, p.bias3 = (_lib.ptr(b) for _w, b, _s, _p in layers)
+        p.y1, p.y2, p.y3 = (_lib.ptr(o) for o in outs)
+    lib = _lib.load()
+    _lib.check(_lib.TIMERS.call("mtrssm_encoder_stem_fwd", lib.mtrssm_encoder_stem_fwd, C.byref(jobs[0][0]),
+                                C.byref(jobs[1][0]) if len(jobs) > 1 else None, _lib.stream_ptr(jobs[0][1].device), flops=flops,
+                                nbytes=nbytes), "mtrssm_encoder_stem_fwd")
+    return filled
+
+
+@contextlib.contextmanager
+def encoder_stem(jobs: list[tuple]):  # noqa: ANN201
+    """``jobs``: ``(x, coords, [(weight, bias, stride, padding)] * 3, act)`` for one or two encoders.  When the fused stem
+    supports every one of them it is launched here, and the conv calls made inside the block (the usual per-layer code) return
+    its outputs instead of launching; otherwise the block runs the per-layer path unchanged.  Yields whether it launched."""
+    global _STEM_FILLED  # noqa: PLW0603
+    descs = [_stem_desc(x, coords, layers, act) if x.is_cuda else None for x, coords, layers, act in jobs]
+    if _STEM_FILLED is not None or not descs or len(descs) > 2 or any(d is None for d in descs):  # noqa: PLR2004
+        yield False
+        return
+    _STEM_FILLED = _stem_launch([(d, x, coords, layers) for d, (x, coords, layers, _a) in zip(descs, jobs, strict=True)])
+    try:
+        yield True
+    finally:
+        _STEM_FILLED = None
 
 
 def _conv_transposed_gather(y: Tensor, w: Tensor, bias: Tensor | None, stride: int, pad: int, out_hw: tuple[int, int],  # noqa: PLR0913

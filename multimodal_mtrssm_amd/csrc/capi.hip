@@ -71,6 +71,8 @@ int conv_weight_grad_src_bias_launch(const MtrssmConvGeom*, const float*, const 
 int channel_sum_launch(const float*, int, int, int, float*, hipStream_t);
 int convt_k4s2_band_supported(int, int, int, int, int);
 int convt_k4s2_band_launch(int, int, int, int, int, const float*, const float*, const float*, int, int, float*, hipStream_t);
+int encoder_stem_supported(const MtrssmEncoderStem*);
+int encoder_stem_launch(const MtrssmEncoderStem*, const MtrssmEncoderStem*, hipStream_t);
 int convt_k4s2_thin_launch(int, int, int, int, int, const float*, const float*, const float*, int, int, float*, hipStream_t);
 int conv_convt_quad_supported(const MtrssmConvGeom*);
 int conv_convt_quad_launch(const MtrssmConvGeom*, const float*, const unsigned short* const*, const float*, const float*, float*,
@@ -505,6 +507,10 @@ MTRSSM_API int mtrssm_convt_quad(const MtrssmConvGeom* ga4, const float* srca, c
   return conv_convt_quad_launch(ga4, srca, reinterpret_cast<const unsigned short* const*>(wqa4), biasa, actgrada, outa, gb4, srcb,
                                 reinterpret_cast<const unsigned short* const*>(wqb4), biasb, actgradb, outb,
                                 static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_encoder_stem_supported(const MtrssmEncoderStem* p) { return encoder_stem_supported(p); }
+MTRSSM_API int mtrssm_encoder_stem_fwd(const MtrssmEncoderStem* a, const MtrssmEncoderStem* b, void* stream) {
+  return encoder_stem_launch(a, b, static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int mtrssm_convt_k4s2_band_supported(int32_t N, int32_t C, int32_t Hs, int32_t Ws, int32_t Cout) {
   return convt_k4s2_band_supported(N, C, Hs, Ws, Cout);

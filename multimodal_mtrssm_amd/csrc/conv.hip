@@ -658,6 +658,7 @@ __global__ __launch_bounds__(kConvThreads) void conv_gather_gemm_patch_kernel(
 #include "conv_split.h"
 #include "conv_resident.h"
 #include "conv_s2_band.h"
+#include "conv_stem.h"
 #include "conv_wgrad_resident.h"
 
 namespace mtrssm {
@@ -2659,6 +2660,63 @@ int convt_k4s2_band_launch(int N, int C, int Hs, int Ws, int Cout, const float* 
   set_last_kernel("mtrssm::convt4s2_band_kernel");
   hipLaunchKernelGGL(convt4s2_band_kernel, dim3((unsigned)p.nx), dim3(256), lds, stream, p, none);
   return launched("convt_k4s2_band");
+}
+
+// The encoders' strided stem in one launch (conv_stem.h: encoder_stem_kernel).  Supported: bf16x2, three Conv2d(k 3, s 2, p 1) with
+// channels (1 + 2 coordinate planes) -> 8 -> 16 -> 32 on 64 x 64 or 128 x 32 planes, an activation the band kernel stages
+// (not Tanh), and the band kernel's index range.  A shape query only: pointers are checked by the launch.
+int encoder_stem_supported(const MtrssmEncoderStem* p) {
+  return p && p->N > 0 && p->mfma_split == 2 && p->C == 1 && p->C2 == 2 && p->Cout1 == 8 && p->Cout2 == 16 && p->Cout3 == 32 &&
+                 ((p->Hs == 64 && p->Ws == 64) || (p->Hs == 128 && p->Ws == 32)) && p->act >= MTRSSM_ACT_IDENTITY && p->act < MTRSSM_ACT_TANH &&
+                 (long)p->N * 8 * 1024 < (1L << 31)
+             ? 1
+             : 0;
+}
+int encoder_stem_launch(const MtrssmEncoderStem* a, const MtrssmEncoderStem* b, hipStream_t stream) {
+  auto fill = [](const MtrssmEncoderStem* p, StemProblem& q) {
+    if (!encoder_stem_supported(p)) {
+      set_error("encoder_stem_fwd: needs bf16x2, channels 1 + 2 -> 8 -> 16 -> 32, 64 x 64 or 128 x 32 planes and a non-Tanh activation");
+      return MTRSSM_EINVAL;
+    }
+    if (!p->src || !p->coords || !p->wp1 || !p->wq1 || !p->wq2 || !p->wq3 || !p->y1 || !p->y2 || !p->y3) {
+      set_error("encoder_stem_fwd: null pointer");
+      return MTRSSM_EINVAL;
+    }
+    if (((uintptr_t)p->src | (uintptr_t)p->coords | (uintptr_t)p->wp1 | (uintptr_t)p->wq1 | (uintptr_t)p->wq2 | (uintptr_t)p->wq3 | (uintptr_t)p->y1 |
+         (uintptr_t)p->y2 | (uintptr_t)p->y3) & 15) {
+      set_error("encoder_stem_fwd: tensors must be 16-byte aligned");
+      return MTRSSM_EINVAL;
+    }
+    q.src = p->src; q.coords = p->coords; q.wp1 = p->wp1; q.wq1 = p->wq1; q.wq2 = p->wq2; q.wq3 = p->wq3;
+    q.b1 = p->bias1; q.b2 = p->bias2; q.b3 = p->bias3; q.y1 = p->y1; q.y2 = p->y2; q.y3 = p->y3;
+    q.N = p->N; q.Ws = p->Ws; q.act = p->act;
+    return MTRSSM_OK;
+  };
+  StemProblem qa{}, qb{};
+  if (int rc = fill(a, qa)) return rc;
+  if (b) {
+    if (int rc = fill(b, qb)) return rc;
+  }
+  const long ta = qa.N, tb = b ? qb.N : 0;
+  const int slots = cu_count();  // one 512-thread workgroup per CU
+  if (tb == 0) {
+    qa.nx = (int)(ta < slots ? ta : slots);
+    qb.nx = 0;
+  } else {
+    long na = (slots * ta + (ta + tb) / 2) / (ta + tb);
+    na = na < 1 ? 1 : (na > slots - 1 ? slots - 1 : na);
+    qa.nx = (int)(na < ta ? na : ta);
+    qb.nx = (int)(slots - na < tb ? slots - na : tb);
+  }
+  static bool attr_done_dev[64] = {};
+  bool& attr_done = attr_done_dev[device_slot()];
+  if (!attr_done) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(encoder_stem_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kStemLds);
+    attr_done = true;
+  }
+  set_last_kernel("mtrssm::encoder_stem_kernel");
+  hipLaunchKernelGGL(encoder_stem_kernel, dim3((unsigned)(qa.nx + qb.nx)), dim3(kStemThreads), (size_t)kStemLds, stream, qa, qb);
+  return launched("encoder_stem_fwd");
 }
 
 int convt_k4s2_thin_launch(int N, int C, int Hs, int Ws, int Cout, const float* src, const float* w, const float* bias, int pre_act,

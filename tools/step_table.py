@@ -30,7 +30,7 @@ def group(k: str) -> str:
         return "conv weight gradients (staged kernels)"
     if "quad" in k or "rows" in k:
         return "all-parity-class transposed kernels (ConvTranspose forward, stride-2 conv backward-data)"
-    if "thin" in k or "gather_split" in k or "band" in k:
+    if "thin" in k or "gather_split" in k or "band" in k or "encoder_stem" in k:
         return "stride-2 / thin gathers (band, split, VALU kernels)"
     if "mtrssm::" in k:
         return "other library kernels (NLL, AdamW, sums, pack, unpack, clear, feed, categorical head, scalar epilogue)"
