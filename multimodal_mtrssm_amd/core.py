@@ -211,138 +211,95 @@ class _InitialState(torch.autograd.Function):
         return (None, None, g_ea, g_ev, None, *grads)
 
 
-class _ElboCombine(torch.autograd.Function):
-    """``recon = nll_a + nll_v; kl_j = coeff_j mean(kl_bt_j); loss = recon + sum kl_j`` in one launch each way
-    (``mtrssm_elbo_combine_fwd / _bwd``) instead of the eager add / mean / mul / add chain and its autograd nodes."""
-
-    @staticmethod
-    def forward(ctx, nll_a: Tensor, nll_v: Tensor, kl0: Tensor, kl1: Tensor | None, c0: float, c1: float):  # noqa: ANN001, ANN205, PLR0913
-        from multimodal_mtrssm_amd import _lib  # noqa: PLC0415
-
-        ctx.set_materialize_grads(False)
-        nll_a, nll_v, kl0 = nll_a.contiguous().float(), nll_v.contiguous().float(), kl0.contiguous().float()
-        kl1 = None if kl1 is None else kl1.contiguous().float()
-        outs = [torch.empty((), device=kl0.device, dtype=torch.float32) for _ in range(4)]
-        _lib.check(_lib.load().mtrssm_elbo_combine_fwd(_lib.ptr(nll_a), _lib.ptr(nll_v), _lib.ptr(kl0), _lib.ptr(kl1), kl0.numel(), float(c0), float(c1),
-                                                       _lib.ptr(outs[0]), _lib.ptr(outs[1]), _lib.ptr(outs[2]) if kl1 is not None else None,
-                                                       _lib.ptr(outs[3]), _lib.stream_ptr(kl0.device)), "mtrssm_elbo_combine_fwd")
-        ctx.meta = (kl0.shape, None if kl1 is None else kl1.shape, float(c0), float(c1))
-        ctx.dev = kl0.device
-        return outs[0], outs[1], outs[2], outs[3]
-
-    @staticmethod
-    def backward(ctx, g_recon, g_k0, g_k1, g_loss):  # noqa: ANN001, ANN205
-        from multimodal_mtrssm_amd import _lib  # noqa: PLC0415
-
-        shape0, shape1, c0, c1 = ctx.meta
-        n = 1
-        for d in shape0:
-            n *= d
-        g_a, g_v = (torch.empty((), device=ctx.dev, dtype=torch.float32) for _ in range(2))
-        g_kl0 = torch.empty(shape0, device=ctx.dev, dtype=torch.float32)
-        g_kl1 = None if shape1 is None else torch.empty(shape1, device=ctx.dev, dtype=torch.float32)
-        opt = lambda t: None if t is None else _lib.ptr(t.contiguous().float())  # noqa: E731
-        _lib.check(_lib.load().mtrssm_elbo_combine_bwd(opt(g_recon), opt(g_k0), opt(g_k1) if shape1 is not None else None, opt(g_loss), n, c0, c1,
-                                                       _lib.ptr(g_a), _lib.ptr(g_v), _lib.ptr(g_kl0), _lib.ptr(g_kl1), _lib.stream_ptr(ctx.dev)),
-                   "mtrssm_elbo_combine_bwd")
-        return g_a, g_v, g_kl0, g_kl1, None, None
-
-
-class _ElboCombineCounted(torch.autograd.Function):
-    """``_ElboCombine`` for ragged batches (``mtrssm_elbo_combine_counted_fwd / _bwd``):
-    ``kl_j = coeff_j sum(live kl_bt_j) / count``, ``live`` float ``[B * T]`` in {0, 1}, ``count`` a device scalar."""
-
-    @staticmethod
-    def forward(ctx, nll_a: Tensor, nll_v: Tensor, kl0: Tensor, kl1: Tensor | None, live: Tensor, count: Tensor, c0: float, c1: float):  # noqa: ANN001, ANN205, PLR0913
-        from multimodal_mtrssm_amd import _lib  # noqa: PLC0415
-
-        ctx.set_materialize_grads(False)
-        nll_a, nll_v, kl0 = nll_a.contiguous().float(), nll_v.contiguous().float(), kl0.contiguous().float()
-        kl1 = None if kl1 is None else kl1.contiguous().float()
-        live, count = live.contiguous().float(), count.contiguous().float()
-        if live.numel() != kl0.numel() or count.numel() != 1:
-            msg = f"live must have one entry per KL step ({kl0.numel()}), count one; got {live.numel()} and {count.numel()}"
-            raise ValueError(msg)
-        outs = [torch.empty((), device=kl0.device, dtype=torch.float32) for _ in range(4)]
-        _lib.check(_lib.load().mtrssm_elbo_combine_counted_fwd(
-            _lib.ptr(nll_a), _lib.ptr(nll_v), _lib.ptr(kl0), _lib.ptr(kl1), _lib.ptr(live), _lib.ptr(count), kl0.numel(), float(c0), float(c1),
-            _lib.ptr(outs[0]), _lib.ptr(outs[1]), _lib.ptr(outs[2]) if kl1 is not None else None, _lib.ptr(outs[3]),
-            _lib.stream_ptr(kl0.device)), "mtrssm_elbo_combine_counted_fwd")
-        ctx.meta = (kl0.shape, None if kl1 is None else kl1.shape, float(c0), float(c1))
-        ctx.dev = kl0.device
-        ctx.save_for_backward(live, count)
-        return outs[0], outs[1], outs[2], outs[3]
-
-    @staticmethod
-    def backward(ctx, g_recon, g_k0, g_k1, g_loss):  # noqa: ANN001, ANN205
-        from multimodal_mtrssm_amd import _lib  # noqa: PLC0415
-
-        shape0, shape1, c0, c1 = ctx.meta
-        live, count = ctx.saved_tensors
-        g_a, g_v = (torch.empty((), device=ctx.dev, dtype=torch.float32) for _ in range(2))
-        g_kl0 = torch.empty(shape0, device=ctx.dev, dtype=torch.float32)
-        g_kl1 = None if shape1 is None else torch.empty(shape1, device=ctx.dev, dtype=torch.float32)
-        opt = lambda t: None if t is None else _lib.ptr(t.contiguous().float())  # noqa: E731
-        _lib.check(_lib.load().mtrssm_elbo_combine_counted_bwd(
-            opt(g_recon), opt(g_k0), opt(g_k1) if shape1 is not None else None, opt(g_loss), _lib.ptr(live), _lib.ptr(count), live.numel(), c0, c1,
-            _lib.ptr(g_a), _lib.ptr(g_v), _lib.ptr(g_kl0), _lib.ptr(g_kl1), _lib.stream_ptr(ctx.dev)), "mtrssm_elbo_combine_counted_bwd")
-        return g_a, g_v, g_kl0, g_kl1, None, None, None, None
-
-
-class _ElboScheduled(torch.autograd.Function):
-    """The epilogue under an ``ElboSchedule`` (``mtrssm_elbo_schedule_fwd / _bwd``), one launch each way for every
-    case: ``live`` / ``count`` None or given, ``kl1`` None or given.  Returns ``(recon, k_0, k_1, loss, beta, stats)``, ``stats`` float32
-    ``[4]`` = raw_0, raw_1, active_0, active_1; ``beta`` and ``stats`` carry no gradient.  The backward reads the stored ``beta``."""
+class _ElboEpilogue(torch.autograd.Function):
+    """``recon = nll_a + nll_v; kl_j = coeff_j mean(kl_bt_j); loss = recon + sum kl_j`` in one launch each way instead of the eager
+    add / mean / mul / add chain and its autograd nodes.  ``live`` / ``count`` given (ragged batches):
+    ``kl_j = coeff_j sum(live kl_bt_j) / count``, ``live`` float ``[B * T]`` in {0, 1}, ``count`` a device scalar.  Without ``sched`` the
+    result is ``(recon, k_0, k_1, loss)`` (``mtrssm_elbo_combine_fwd / _bwd`` or ``mtrssm_elbo_combine_counted_fwd / _bwd``).  Under an
+    ``ElboSchedule`` (``mtrssm_elbo_schedule_fwd / _bwd``) it is ``(recon, k_0, k_1, loss, beta, stats)``, ``stats``
+    float32 ``[4]`` = raw_0, raw_1, active_0, active_1; ``beta`` and ``stats`` carry no gradient and the backward reads the stored ``beta``."""
 
     @staticmethod
     def forward(ctx, nll_a: Tensor, nll_v: Tensor, kl0: Tensor, kl1: Tensor | None, live: Tensor | None, count: Tensor | None,  # noqa: ANN001, ANN205, PLR0913
-                step: Tensor | None, sched: ElboSchedule, c0: float, c1: float):
+                step: Tensor | None, sched: ElboSchedule | None, c0: float, c1: float):
         from multimodal_mtrssm_amd import _lib  # noqa: PLC0415
 
         ctx.set_materialize_grads(False)
-        nll_a, nll_v, kl0 = nll_a.contiguous().float(), nll_v.contiguous().float(), kl0.contiguous().float()
-        kl1 = None if kl1 is None else kl1.contiguous().float()
-        if live is not None:
-            live, count = live.contiguous().float(), count.contiguous().float()
-            if live.numel() != kl0.numel() or count.numel() != 1:
-                msg = f"live must have one entry per KL step ({kl0.numel()}), count one; got {live.numel()} and {count.numel()}"
-                raise ValueError(msg)
-        if kl1 is not None and kl1.numel() != kl0.numel():
-            msg = f"the two KL planes must have the same number of steps, got {kl0.numel()} and {kl1.numel()}"
+        nll_a, nll_v, kl0, kl1, live, count, step = (None if t is None else t.contiguous().float() for t in (nll_a, nll_v, kl0, kl1, live, count, step))
+        n = kl0.numel()
+        if (live is None) != (count is None):
+            msg = "live and count come together (both None: every step is live)"
             raise ValueError(msg)
-        if step is not None:
-            step = step.contiguous().float()
-            if step.numel() != 1:
-                msg = f"step must be one device scalar, got {step.numel()} entries"
-                raise ValueError(msg)
-        par = _lib.ElboSchedule(float(c0), float(c1), sched.free_nats, sched.free_nats_h, sched.recon_weights[0], sched.recon_weights[1],
-                                sched.beta_start, float(sched.warmup_steps))
-        outs = [torch.empty((), device=kl0.device, dtype=torch.float32) for _ in range(5)]
-        stats = torch.empty(4, device=kl0.device, dtype=torch.float32)
-        _lib.check(_lib.load().mtrssm_elbo_schedule_fwd(
-            _lib.ptr(nll_a), _lib.ptr(nll_v), _lib.ptr(kl0), _lib.ptr(kl1), _lib.ptr(live), _lib.ptr(count), _lib.ptr(step), kl0.numel(), par,
-            *(_lib.ptr(o) for o in outs), _lib.ptr(stats), _lib.stream_ptr(kl0.device)), "mtrssm_elbo_schedule_fwd")
-        ctx.meta = (kl0.shape, None if kl1 is None else kl1.shape, par)
+        if live is not None and (live.numel() != n or count.numel() != 1):
+            msg = f"live must have one entry per KL step ({n}), count one; got {live.numel()} and {count.numel()}"
+            raise ValueError(msg)
+        if kl1 is not None and kl1.numel() != n:
+            msg = f"the two KL planes must have the same number of steps, got {n} and {kl1.numel()}"
+            raise ValueError(msg)
+        if step is not None and step.numel() != 1:
+            msg = f"step must be one device scalar, got {step.numel()} entries"
+            raise ValueError(msg)
+        lib, ptr, stream = _lib.load(), _lib.ptr, _lib.stream_ptr(kl0.device)
+        outs = [torch.empty((), device=kl0.device, dtype=torch.float32) for _ in range(4 if sched is None else 5)]
+        planes = (ptr(nll_a), ptr(nll_v), ptr(kl0), ptr(kl1))
+        four = (ptr(outs[0]), ptr(outs[1]), ptr(outs[2]) if kl1 is not None else None, ptr(outs[3]))  # (no kl1: k_1 is left unwritten)
+        par, extra = (float(c0), float(c1)), ()
+        if sched is not None:
+            par = _lib.ElboSchedule(float(c0), float(c1), sched.free_nats, sched.free_nats_h, sched.recon_weights[0], sched.recon_weights[1],
+                                    sched.beta_start, float(sched.warmup_steps))
+            stats = torch.empty(4, device=kl0.device, dtype=torch.float32)
+            _lib.check(lib.mtrssm_elbo_schedule_fwd(*planes, ptr(live), ptr(count), ptr(step), n, par, *map(ptr, outs), ptr(stats), stream),
+                       "mtrssm_elbo_schedule_fwd")
+            ctx.save_for_backward(kl0, kl1, live, count, outs[4])
+            ctx.mark_non_differentiable(outs[4], stats)
+            extra = (stats,)
+        elif live is not None:
+            _lib.check(lib.mtrssm_elbo_combine_counted_fwd(*planes, ptr(live), ptr(count), n, *par, *four, stream), "mtrssm_elbo_combine_counted_fwd")
+            ctx.save_for_backward(None, None, live, count, None)
+        else:
+            _lib.check(lib.mtrssm_elbo_combine_fwd(*planes, n, *par, *four, stream), "mtrssm_elbo_combine_fwd")
+            ctx.save_for_backward(None, None, None, None, None)
+        ctx.meta = (kl0.shape, None if kl1 is None else kl1.shape, n, par, sched is not None)
         ctx.dev = kl0.device
-        ctx.save_for_backward(kl0, kl1, live, count, outs[4])
-        ctx.mark_non_differentiable(outs[4], stats)
-        return outs[0], outs[1], outs[2], outs[3], outs[4], stats
+        return (*outs, *extra)
 
     @staticmethod
-    def backward(ctx, g_recon, g_k0, g_k1, g_loss, _g_beta, _g_stats):  # noqa: ANN001, ANN205, PLR0913
+    def backward(ctx, g_recon, g_k0, g_k1, g_loss, *_g_beta_stats):  # noqa: ANN001, ANN002, ANN205
         from multimodal_mtrssm_amd import _lib  # noqa: PLC0415
 
-        shape0, shape1, par = ctx.meta
+        shape0, shape1, n, par, scheduled = ctx.meta
         kl0, kl1, live, count, beta = ctx.saved_tensors
+        lib, ptr, stream = _lib.load(), _lib.ptr, _lib.stream_ptr(ctx.dev)
         g_a, g_v = (torch.empty((), device=ctx.dev, dtype=torch.float32) for _ in range(2))
         g_kl0 = torch.empty(shape0, device=ctx.dev, dtype=torch.float32)
         g_kl1 = None if shape1 is None else torch.empty(shape1, device=ctx.dev, dtype=torch.float32)
-        opt = lambda t: None if t is None else _lib.ptr(t.contiguous().float())  # noqa: E731
-        _lib.check(_lib.load().mtrssm_elbo_schedule_bwd(
-            opt(g_recon), opt(g_k0), opt(g_k1) if shape1 is not None else None, opt(g_loss), _lib.ptr(kl0), _lib.ptr(kl1), _lib.ptr(live),
-            _lib.ptr(count), _lib.ptr(beta), kl0.numel(), par, _lib.ptr(g_a), _lib.ptr(g_v), _lib.ptr(g_kl0), _lib.ptr(g_kl1),
-            _lib.stream_ptr(ctx.dev)), "mtrssm_elbo_schedule_bwd")
+        opt = lambda t: None if t is None else ptr(t.contiguous().float())  # noqa: E731
+        gs = (opt(g_recon), opt(g_k0), opt(g_k1) if shape1 is not None else None, opt(g_loss))
+        grads = (ptr(g_a), ptr(g_v), ptr(g_kl0), ptr(g_kl1))
+        if scheduled:
+            _lib.check(lib.mtrssm_elbo_schedule_bwd(*gs, ptr(kl0), ptr(kl1), ptr(live), ptr(count), ptr(beta), n, par, *grads, stream),
+                       "mtrssm_elbo_schedule_bwd")
+        elif live is not None:
+            _lib.check(lib.mtrssm_elbo_combine_counted_bwd(*gs, ptr(live), ptr(count), n, *par, *grads, stream), "mtrssm_elbo_combine_counted_bwd")
+        else:
+            _lib.check(lib.mtrssm_elbo_combine_bwd(*gs, n, *par, *grads, stream), "mtrssm_elbo_combine_bwd")
         return g_a, g_v, g_kl0, g_kl1, None, None, None, None, None, None
+
+
+# The three call shapes of the epilogue (plain, counted, scheduled): every one is _ElboEpilogue.
+_ElboScheduled = _ElboEpilogue
+
+
+class _ElboCombineCounted:
+    @staticmethod
+    def apply(nll_a: Tensor, nll_v: Tensor, kl0: Tensor, kl1: Tensor | None, live: Tensor, count: Tensor, c0: float, c1: float):  # noqa: ANN205, PLR0913
+        return _ElboEpilogue.apply(nll_a, nll_v, kl0, kl1, live, count, None, None, c0, c1)
+
+
+class _ElboCombine:
+    @staticmethod
+    def apply(nll_a: Tensor, nll_v: Tensor, kl0: Tensor, kl1: Tensor | None, c0: float, c1: float):  # noqa: ANN205, PLR0913
+        return _ElboEpilogue.apply(nll_a, nll_v, kl0, kl1, None, None, None, None, c0, c1)
 
 
 def _elbo_scheduled(nll_a: Tensor, nll_v: Tensor, kl0: Tensor, c0: float, kl1: Tensor | None, c1: float, step_mask: StepMask | None,  # noqa: PLR0913

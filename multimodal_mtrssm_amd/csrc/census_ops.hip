@@ -6,9 +6,6 @@
 
 namespace mtrssm {
 
-void set_error(const char* fmt, ...);
-void set_last_kernel(const char* name);
-
 namespace {
 
 constexpr int kRowThreads = kWave;  // one wave per scan row: its barriers cost nothing and a CU holds many rows
@@ -182,15 +179,6 @@ __global__ __launch_bounds__(kFoldThreads) void census_fold_kernel(const double*
     }
     table[x] += v;
   }
-}
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s launch failed: %s", what, hipGetErrorString(e));
-    return MTRSSM_ELAUNCH;
-  }
-  return MTRSSM_OK;
 }
 
 int64_t round8(int64_t bytes) { return (bytes + 7) & ~(int64_t)7; }

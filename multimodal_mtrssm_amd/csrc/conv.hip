@@ -32,9 +32,6 @@
 
 namespace mtrssm {
 
-void set_error(const char* fmt, ...);
-void set_last_kernel(const char* name);
-
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 constexpr int kKC = 16;          // channels per K chunk

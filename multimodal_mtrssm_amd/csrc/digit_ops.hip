@@ -20,9 +20,6 @@
 
 namespace mtrssm {
 
-void set_error(const char* fmt, ...);
-void set_last_kernel(const char* name);
-
 namespace {
 
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
@@ -276,15 +273,6 @@ __global__ __launch_bounds__(kCountThreads) void word_counts_kernel(const int32_
   }
   __syncthreads();
   if (threadIdx.x < kClasses * kBins) counts[threadIdx.x] += (float)hist[threadIdx.x];
-}
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s launch failed: %s", what, hipGetErrorString(e));
-    return MTRSSM_ELAUNCH;
-  }
-  return MTRSSM_OK;
 }
 
 int cu_count() {

@@ -28,9 +28,6 @@
 
 namespace mtrssm {
 
-void set_error(const char* fmt, ...);
-void set_last_kernel(const char* name);
-
 namespace {
 
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
@@ -423,15 +420,6 @@ __global__ __launch_bounds__(kThreads) void digit_head_reduce_kernel(const float
   for (int s = 0; s < S; ++s) total += part[(size_t)s * kHeadSet + e];
   float* dst = e < kClasses * kHidden ? g_w + e : g_b + (e - kClasses * kHidden);
   *dst = accumulate ? *dst + total : total;
-}
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s launch failed: %s", what, hipGetErrorString(e));
-    return MTRSSM_ELAUNCH;
-  }
-  return MTRSSM_OK;
 }
 
 int cu_count() {

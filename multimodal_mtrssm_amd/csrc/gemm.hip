@@ -21,8 +21,6 @@
 
 namespace mtrssm {
 
-void set_error(const char* fmt, ...);
-void set_last_kernel(const char* name);
 int device_cu_count();
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;

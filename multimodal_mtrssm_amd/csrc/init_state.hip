@@ -21,9 +21,6 @@
 
 namespace mtrssm {
 
-void set_error(const char* fmt, ...);
-void set_last_kernel(const char* name);
-
 constexpr int kInitThreads = 1024;
 constexpr int kInitMax = 1024;   // largest layer width (and K * C) whose activations fit the static LDS vectors
 constexpr int kInitRows = 4;     // output rows a wave has in flight in the forward

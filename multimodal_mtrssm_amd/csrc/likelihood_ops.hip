@@ -6,9 +6,6 @@
 
 namespace mtrssm {
 
-void set_error(const char* fmt, ...);
-void set_last_kernel(const char* name);
-
 namespace {
 
 constexpr int kThreads = 256;
@@ -176,15 +173,6 @@ __global__ __launch_bounds__(kThreads) void iw_bound_kernel(const float* __restr
       for (int p = 0; p < 8; ++p) planes[p * plane + out0 + t] = o[p];
     }
   }
-}
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s launch failed: %s", what, hipGetErrorString(e));
-    return MTRSSM_ELAUNCH;
-  }
-  return MTRSSM_OK;
 }
 
 }  // namespace

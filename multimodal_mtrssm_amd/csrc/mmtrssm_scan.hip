@@ -8,9 +8,6 @@
 
 namespace mtrssm {
 
-void set_error(const char* fmt, ...);
-void set_last_kernel(const char* name);
-
 struct MmtLds {
   // slh = [stoch_l ; stoch_h] contiguous (the MTRNN input vector without the action part)
   int slh, dl0, dl1, hl, dh0, dh1, hh, tmp, l1, h1, hq, lpl, la, lv, mx, lph, lqh, stride;

@@ -6,9 +6,6 @@
 
 namespace mtrssm {
 
-void set_error(const char* fmt, ...);
-void set_last_kernel(const char* name);
-
 namespace {
 
 constexpr int kTileDim = 16;     // a tile of the second moment: one MFMA accumulator

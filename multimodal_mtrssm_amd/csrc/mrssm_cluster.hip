@@ -28,8 +28,6 @@
 
 namespace mtrssm {
 
-void set_error(const char* fmt, ...);
-void set_last_kernel(const char* name);
 int device_cu_count();
 
 constexpr int kClu = 4;            // workgroups (CUs) per row

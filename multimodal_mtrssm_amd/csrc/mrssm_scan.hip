@@ -339,8 +339,6 @@ __global__ __launch_bounds__(1024) void mrssm_bwd_kernel(const MtrssmMrssmDims d
 // ------------------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------------------
-void set_error(const char* fmt, ...);
-void set_last_kernel(const char* name);
 
 static int pick_rows(int B, int requested, size_t bytes_per_row, size_t extra_bytes) {
   if (requested > 0) return requested;

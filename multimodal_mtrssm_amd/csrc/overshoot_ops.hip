@@ -6,9 +6,6 @@
 
 namespace mtrssm {
 
-void set_error(const char* fmt, ...);
-void set_last_kernel(const char* name);
-
 namespace {
 
 constexpr int kThreads = 256;
@@ -334,15 +331,6 @@ __global__ __launch_bounds__(kThreads) void overshoot_scatter_kernel(const OsRow
       dst[frame * w + q] = start ? src[r * w + q] : 0.f;
     }
   }
-}
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s launch failed: %s", what, hipGetErrorString(e));
-    return MTRSSM_ELAUNCH;
-  }
-  return MTRSSM_OK;
 }
 
 // T >= 2, s >= 1, 0 <= o <= T - 2, N = (T - 2 - o) / s + 1, D >= 2: every start lies in [0, T - 2].

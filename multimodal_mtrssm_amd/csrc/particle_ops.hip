@@ -7,9 +7,6 @@
 
 namespace mtrssm {
 
-void set_error(const char* fmt, ...);
-void set_last_kernel(const char* name);
-
 namespace {
 
 constexpr int kThreads = 256;
@@ -143,15 +140,6 @@ __global__ __launch_bounds__(kThreads) void particle_gather_kernel(const Particl
     if (t.vec[k]) reinterpret_cast<float4*>(dst + r * w)[q] = reinterpret_cast<const float4*>(src + from * stride)[q];
     else dst[r * w + q] = src[from * stride + q];
   }
-}
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s launch failed: %s", what, hipGetErrorString(e));
-    return MTRSSM_ELAUNCH;
-  }
-  return MTRSSM_OK;
 }
 
 }  // namespace

@@ -14,6 +14,19 @@ constexpr int kWave = 64;
 // went together with foreign bytes at the head of the buffer on replay (ROCm 7.2: the kernel arguments of an unrelated eager
 // launch showed up there), so no memset node is ever recorded.
 int clear_async(void* p, size_t bytes, hipStream_t stream);
+
+// The error channel every launcher reports through (capi.hip), and the check that follows each launch.
+void set_error(const char* fmt, ...);
+void set_last_kernel(const char* name);
+inline int check_launch(const char* what) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    set_error("%s launch failed: %s", what, hipGetErrorString(e));
+    return MTRSSM_ELAUNCH;
+  }
+  return MTRSSM_OK;
+}
+
 constexpr float kLogThird = -1.0986122886681098f;  // log(1/3), mrssm/mopoe_mrssm/core.py:141-142
 
 __device__ __forceinline__ float act_fwd(float z, int act) {

@@ -16,9 +16,6 @@
 
 namespace mtrssm {
 
-void set_error(const char* fmt, ...);
-void set_last_kernel(const char* name);
-
 constexpr int kPrepTile = 32;    // output tile edge
 constexpr int kPrepChunk = 64;   // h values per staged chunk of a product tile
 constexpr int kPrepThreads = 256;

@@ -5,9 +5,6 @@
 
 namespace mtrssm {
 
-void set_error(const char* fmt, ...);
-void set_last_kernel(const char* name);
-
 namespace {
 
 constexpr int kThreads = 256;
@@ -147,15 +144,6 @@ __global__ __launch_bounds__(kThreads) void horizon_table_kernel(const float* __
     }
   }
   *dst = acc;
-}
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s launch failed: %s", what, hipGetErrorString(e));
-    return MTRSSM_ELAUNCH;
-  }
-  return MTRSSM_OK;
 }
 
 template <int S>

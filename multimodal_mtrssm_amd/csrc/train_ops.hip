@@ -7,9 +7,6 @@
 
 namespace mtrssm {
 
-void set_error(const char* fmt, ...);
-void set_last_kernel(const char* name);
-
 constexpr int kThreads = 256;
 
 __device__ __forceinline__ float block_sum(float v, float* red) {
@@ -283,15 +280,6 @@ static int grid_for(int64_t n) {
   return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
 }
 
-static int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s launch failed: %s", what, hipGetErrorString(e));
-    return MTRSSM_ELAUNCH;
-  }
-  return MTRSSM_OK;
-}
-
 // ------------------------------------------------------------------------------------------------
 // Categorical head of the INITIAL state (core.py:121-135; mmtrssm core.py:321-362): flat logits [rows][K * C] + one uniform per
 // categorical -> log-probabilities, probabilities and the inverse-CDF one-hot sample, one thread per (row, categorical), the
@@ -332,228 +320,171 @@ int categorical_sample_bwd_launch(const float* probs, const float* g_p, const fl
 }
 
 // ------------------------------------------------------------------------------------------------
-// The scalar end of shared_step (core.py:187-221; mmtrssm core.py:563-606) in one launch each way:
-//   recon = nll_a + nll_v;  kl_j = coeff_j * mean(kl_bt_j)  (j < nkl <= 2);  loss = recon + sum_j kl_j
-// Four scalar outputs (o_k1 may be null).  Backward: g = { g_recon, g_kl_0, g_kl_1, g_loss } (any may be null = 0) ->
-// g_nll_a = g_nll_v = g_recon + g_loss;  g_kl_bt_j[i] = (g_kl_j + g_loss) * coeff_j / n.
-// ------------------------------------------------------------------------------------------------
-__global__ void elbo_combine_fwd_kernel(const float* __restrict__ nll_a, const float* __restrict__ nll_v, const float* __restrict__ kl0,
-                                        const float* __restrict__ kl1, int64_t n, float c0, float c1, float* __restrict__ o_recon, float* __restrict__ o_k0,
-                                        float* __restrict__ o_k1, float* __restrict__ o_loss) {
-  __shared__ float red[kThreads / kWave];
-  float a0 = 0.f, a1 = 0.f;
-  for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
-    a0 += kl0[i];
-    if (kl1) a1 += kl1[i];
-  }
-  const float s0 = block_sum(a0, red);
-  __syncthreads();
-  const float s1 = block_sum(a1, red);
-  if (threadIdx.x == 0) {
-    const float recon = nll_a[0] + nll_v[0];
-    const float k0 = s0 / (float)n * c0, k1 = kl1 ? s1 / (float)n * c1 : 0.f;
-    o_recon[0] = recon; o_k0[0] = k0; if (o_k1) o_k1[0] = k1; o_loss[0] = recon + k0 + k1;
-  }
-}
-__global__ void elbo_combine_bwd_kernel(const float* __restrict__ g_recon, const float* __restrict__ g_k0, const float* __restrict__ g_k1,
-                                        const float* __restrict__ g_loss, int64_t n, float c0, float c1, float* __restrict__ g_nll_a,
-                                        float* __restrict__ g_nll_v, float* __restrict__ g_kl0, float* __restrict__ g_kl1) {
-  const float gl = g_loss ? g_loss[0] : 0.f;
-  const float gn = (g_recon ? g_recon[0] : 0.f) + gl;
-  const float v0 = ((g_k0 ? g_k0[0] : 0.f) + gl) * c0 / (float)n, v1 = ((g_k1 ? g_k1[0] : 0.f) + gl) * c1 / (float)n;
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i == 0) { g_nll_a[0] = gn; g_nll_v[0] = gn; }
-  if (i < n) {
-    g_kl0[i] = v0;
-    if (g_kl1) g_kl1[i] = v1;
-  }
-}
-int elbo_combine_fwd_launch(const float* nll_a, const float* nll_v, const float* kl0, const float* kl1, int64_t n, float c0, float c1,
-                            float* o_recon, float* o_k0, float* o_k1, float* o_loss, hipStream_t s) {
-  if (!nll_a || !nll_v || !kl0 || !o_recon || !o_k0 || !o_loss || n <= 0) { set_error("elbo_combine_fwd: bad argument"); return MTRSSM_EINVAL; }
-  set_last_kernel("mtrssm::elbo_combine_fwd_kernel");
-  hipLaunchKernelGGL(elbo_combine_fwd_kernel, dim3(1), dim3(kThreads), 0, s, nll_a, nll_v, kl0, kl1, n, c0, c1, o_recon, o_k0, o_k1, o_loss);
-  return check_launch("elbo_combine_fwd");
-}
-int elbo_combine_bwd_launch(const float* g_recon, const float* g_k0, const float* g_k1, const float* g_loss, int64_t n, float c0, float c1,
-                            float* g_nll_a, float* g_nll_v, float* g_kl0, float* g_kl1, hipStream_t s) {
-  if (!g_nll_a || !g_nll_v || !g_kl0 || n <= 0) { set_error("elbo_combine_bwd: bad argument"); return MTRSSM_EINVAL; }
-  set_last_kernel("mtrssm::elbo_combine_bwd_kernel");
-  hipLaunchKernelGGL(elbo_combine_bwd_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, g_recon, g_k0, g_k1, g_loss, n,
-                     c0, c1, g_nll_a, g_nll_v, g_kl0, g_kl1);
-  return check_launch("elbo_combine_bwd");
-}
-
-// The same epilogue for ragged batches: the KL sums run over the LIVE steps (live[i] in {0, 1}) and are
-// divided by the device scalar *count (the global batch's live steps / world; 0 -> the term is 0) instead of n.  Same loop, same
-// reduction order as elbo_combine_fwd_kernel: with every step live and *count == n the four scalars are bitwise its.
-// Backward: g_kl_bt_j[i] = live[i] ? (g_kl_j + g_loss) * coeff_j / count : 0 -- a dead step gets an explicit zero.
-__global__ void elbo_combine_counted_fwd_kernel(const float* __restrict__ nll_a, const float* __restrict__ nll_v, const float* __restrict__ kl0,
-                                                const float* __restrict__ kl1, const float* __restrict__ live, const float* __restrict__ count,
-                                                int64_t n, float c0, float c1, float* __restrict__ o_recon, float* __restrict__ o_k0,
-                                                float* __restrict__ o_k1, float* __restrict__ o_loss) {
-  __shared__ float red[kThreads / kWave];
-  float a0 = 0.f, a1 = 0.f;
-  for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
-    const bool on = live[i] != 0.f;
-    a0 += on ? kl0[i] : 0.f;
-    if (kl1) a1 += on ? kl1[i] : 0.f;
-  }
-  const float s0 = block_sum(a0, red);
-  __syncthreads();
-  const float s1 = block_sum(a1, red);
-  if (threadIdx.x == 0) {
-    const float cnt = count[0];
-    const float recon = nll_a[0] + nll_v[0];
-    const float k0 = cnt > 0.f ? s0 / cnt * c0 : 0.f, k1 = kl1 && cnt > 0.f ? s1 / cnt * c1 : 0.f;
-    o_recon[0] = recon; o_k0[0] = k0; if (o_k1) o_k1[0] = k1; o_loss[0] = recon + k0 + k1;
-  }
-}
-__global__ void elbo_combine_counted_bwd_kernel(const float* __restrict__ g_recon, const float* __restrict__ g_k0, const float* __restrict__ g_k1,
-                                                const float* __restrict__ g_loss, const float* __restrict__ live, const float* __restrict__ count,
-                                                int64_t n, float c0, float c1, float* __restrict__ g_nll_a, float* __restrict__ g_nll_v,
-                                                float* __restrict__ g_kl0, float* __restrict__ g_kl1) {
-  const float gl = g_loss ? g_loss[0] : 0.f;
-  const float gn = (g_recon ? g_recon[0] : 0.f) + gl;
-  const float cnt = count[0];
-  const float v0 = cnt > 0.f ? ((g_k0 ? g_k0[0] : 0.f) + gl) * c0 / cnt : 0.f;
-  const float v1 = cnt > 0.f ? ((g_k1 ? g_k1[0] : 0.f) + gl) * c1 / cnt : 0.f;
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i == 0) { g_nll_a[0] = gn; g_nll_v[0] = gn; }
-  if (i < n) {
-    const bool on = live[i] != 0.f;
-    g_kl0[i] = on ? v0 : 0.f;
-    if (g_kl1) g_kl1[i] = on ? v1 : 0.f;
-  }
-}
-int elbo_combine_counted_fwd_launch(const float* nll_a, const float* nll_v, const float* kl0, const float* kl1, const float* live,
-                                    const float* count, int64_t n, float c0, float c1, float* o_recon, float* o_k0, float* o_k1, float* o_loss,
-                                    hipStream_t s) {
-  if (!nll_a || !nll_v || !kl0 || !live || !count || !o_recon || !o_k0 || !o_loss || n <= 0) {
-    set_error("elbo_combine_counted_fwd: bad argument");
-    return MTRSSM_EINVAL;
-  }
-  set_last_kernel("mtrssm::elbo_combine_counted_fwd_kernel");
-  hipLaunchKernelGGL(elbo_combine_counted_fwd_kernel, dim3(1), dim3(kThreads), 0, s, nll_a, nll_v, kl0, kl1, live, count, n, c0, c1, o_recon, o_k0,
-                     o_k1, o_loss);
-  return check_launch("elbo_combine_counted_fwd");
-}
-int elbo_combine_counted_bwd_launch(const float* g_recon, const float* g_k0, const float* g_k1, const float* g_loss, const float* live,
-                                    const float* count, int64_t n, float c0, float c1, float* g_nll_a, float* g_nll_v, float* g_kl0, float* g_kl1,
-                                    hipStream_t s) {
-  if (!live || !count || !g_nll_a || !g_nll_v || !g_kl0 || n <= 0) { set_error("elbo_combine_counted_bwd: bad argument"); return MTRSSM_EINVAL; }
-  set_last_kernel("mtrssm::elbo_combine_counted_bwd_kernel");
-  hipLaunchKernelGGL(elbo_combine_counted_bwd_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, g_recon, g_k0, g_k1,
-                     g_loss, live, count, n, c0, c1, g_nll_a, g_nll_v, g_kl0, g_kl1);
-  return check_launch("elbo_combine_counted_bwd");
-}
-
-// The epilogue under an ElboSchedule: free bits per (b, t), a beta warm-up read from the device scalar
-// *step, per-modality reconstruction weights.  ONE pair for live / count null (N = n) or given (N = *count) and kl1 null or given.
+// The scalar end of shared_step (core.py:187-221; mmtrssm core.py:563-606) in one launch each way, ONE kernel pair for every case:
+//   recon = nll_a + nll_v;  kl_j = coeff_j * sum_live(kl_bt_j) / N  (j < nkl <= 2);  loss = recon + sum_j kl_j
+// live / count null: every step is live and N = n.  Given (ragged batches): live[i] in {0, 1} and N = the
+// device scalar *count (the global batch's live steps / world; 0 -> the term is 0).  Four scalar outputs (o_k1 may be null).
+// SCHED (an ElboSchedule): free bits per (b, t), a beta warm-up read from the device scalar *step,
+// per-modality reconstruction weights; beside the four scalars it writes beta and stats = { raw_0, raw_1, active_0, active_1 } from
+//   s[3j .. 3j + 2] = sum_live clip_j, sum_live kl_j, #{live, not kl_j < free_j}.
+// Without SCHED nothing is clipped (a negative entry counts as it is) and one sum per plane is kept, s[j] = sum_live kl_j.
 // Every operation is rounded on its own (contraction is switched off in both kernels): schedule.py's torch rule reproduces beta and
-// the gradient planes bit for bit.  The sums take elbo_combine*_fwd_kernel's loop and block_sum's order (wave_sum, one partial per
-// wave, wave_sum over the partials), six of them behind one barrier: the neutral schedule gives those kernels' scalars bitwise.
-//   s[0..2] = sum_live clip_0, sum_live kl_0, #{live, not kl_0 < free_0};  s[3..5] the same for kl_1
-__global__ void elbo_schedule_fwd_kernel(const float* __restrict__ nll_a, const float* __restrict__ nll_v, const float* __restrict__ kl0,
-                                         const float* __restrict__ kl1, const float* __restrict__ live, const float* __restrict__ count,
-                                         const float* __restrict__ step, int64_t n, MtrssmElboSchedule p, float* __restrict__ o_recon,
-                                         float* __restrict__ o_k0, float* __restrict__ o_k1, float* __restrict__ o_loss, float* __restrict__ o_beta,
-                                         float* __restrict__ o_stats) {
+// the gradient planes bit for bit.  The sums take block_sum's order (wave_sum, one partial per wave, wave_sum over the partials),
+// all of them behind one barrier: the neutral schedule gives the unscheduled scalars bitwise, and with every step live and
+// *count == n the counted scalars are the uncounted ones.
+// Backward: g = { g_recon, g_kl_0, g_kl_1, g_loss } (any may be null = 0) -> g_nll_a, g_nll_v = g_recon + g_loss (times w_a, w_v);
+//   g_kl_bt_j[i] = (g_kl_j + g_loss) * coeff_j (* the beta the forward stored) / N;  a step that is dead or below its threshold
+//   gets an explicit zero.
+// ------------------------------------------------------------------------------------------------
+template <bool SCHED>
+__global__ void elbo_fwd_kernel(const float* __restrict__ nll_a, const float* __restrict__ nll_v, const float* __restrict__ kl0,
+                                const float* __restrict__ kl1, const float* __restrict__ live, const float* __restrict__ count,
+                                const float* __restrict__ step, int64_t n, MtrssmElboSchedule p, float* __restrict__ o_recon,
+                                float* __restrict__ o_k0, float* __restrict__ o_k1, float* __restrict__ o_loss, float* __restrict__ o_beta,
+                                float* __restrict__ o_stats) {
 #pragma clang fp contract(off)
-  __shared__ float red[6][kThreads / kWave];
-  float a[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  constexpr int K = SCHED ? 3 : 1;  // sums per KL plane
+  __shared__ float red[2 * K][kThreads / kWave];
+  float a[2 * K] = {};
   for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
     const bool on = !live || live[i] != 0.f;
-    const float x0 = kl0[i];
-    const bool low0 = x0 < p.free0;
-    a[0] += on ? (low0 ? p.free0 : x0) : 0.f;
-    a[1] += on ? x0 : 0.f;
-    a[2] += on && !low0 ? 1.f : 0.f;
-    if (kl1) {
-      const float x1 = kl1[i];
-      const bool low1 = x1 < p.free1;
-      a[3] += on ? (low1 ? p.free1 : x1) : 0.f;
-      a[4] += on ? x1 : 0.f;
-      a[5] += on && !low1 ? 1.f : 0.f;
-    }
+    auto add = [&](float* acc, float x, float free) {
+      if constexpr (SCHED) {
+        const bool low = x < free;
+        acc[0] += on ? (low ? free : x) : 0.f;
+        acc[1] += on ? x : 0.f;
+        acc[2] += on && !low ? 1.f : 0.f;
+      } else {
+        acc[0] += on ? x : 0.f;
+      }
+    };
+    add(a, kl0[i], p.free0);
+    if (kl1) add(a + K, kl1[i], p.free1);
   }
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
 #pragma unroll
-  for (int k = 0; k < 6; ++k) {
+  for (int k = 0; k < 2 * K; ++k) {
     const float v = wave_sum(a[k]);
     if (lane == 0) red[k][wave] = v;
   }
   __syncthreads();
   if (threadIdx.x >= kWave) return;
-  float s[6];
+  float s[2 * K];
 #pragma unroll
-  for (int k = 0; k < 6; ++k) s[k] = wave_sum(threadIdx.x < blockDim.x / kWave ? red[k][threadIdx.x] : 0.f);
+  for (int k = 0; k < 2 * K; ++k) s[k] = wave_sum(threadIdx.x < blockDim.x / kWave ? red[k][threadIdx.x] : 0.f);
   if (threadIdx.x == 0) {
     const float cnt = live ? count[0] : (float)n;
-    const bool some = cnt > 0.f;
+    const bool some = !live || cnt > 0.f;
     float beta = 1.f;
-    if (p.warmup > 0.f) {
+    if (SCHED && p.warmup > 0.f) {
       const float r = step[0] / p.warmup;
       beta = p.beta_start + (1.f - p.beta_start) * (r > 1.f ? 1.f : r);
     }
-    const float recon = p.w_a * nll_a[0] + p.w_v * nll_v[0];
-    const float k0 = some ? s[0] / cnt * p.c0 * beta : 0.f, k1 = kl1 && some ? s[3] / cnt * p.c1 * beta : 0.f;
-    o_recon[0] = recon; o_k0[0] = k0; if (o_k1) o_k1[0] = k1; o_loss[0] = recon + k0 + k1; o_beta[0] = beta;
-    o_stats[0] = some ? s[1] / cnt * p.c0 : 0.f;
-    o_stats[1] = kl1 && some ? s[4] / cnt * p.c1 : 0.f;
-    o_stats[2] = some ? s[2] / cnt : 0.f;
-    o_stats[3] = kl1 && some ? s[5] / cnt : 0.f;
+    auto term = [&](float sum, float c) {
+      const float k = sum / cnt * c;
+      return SCHED ? k * beta : k;
+    };
+    const float recon = SCHED ? p.w_a * nll_a[0] + p.w_v * nll_v[0] : nll_a[0] + nll_v[0];
+    const float k0 = some ? term(s[0], p.c0) : 0.f, k1 = kl1 && some ? term(s[K], p.c1) : 0.f;
+    o_recon[0] = recon; o_k0[0] = k0; if (o_k1) o_k1[0] = k1; o_loss[0] = recon + k0 + k1;
+    if constexpr (SCHED) {
+      o_beta[0] = beta;
+      o_stats[0] = some ? s[1] / cnt * p.c0 : 0.f;
+      o_stats[1] = kl1 && some ? s[4] / cnt * p.c1 : 0.f;
+      o_stats[2] = some ? s[2] / cnt : 0.f;
+      o_stats[3] = kl1 && some ? s[5] / cnt : 0.f;
+    }
   }
 }
-// Backward: reads the beta the forward stored.  A step that is dead or below its threshold gets an explicit zero.
-__global__ void elbo_schedule_bwd_kernel(const float* __restrict__ g_recon, const float* __restrict__ g_k0, const float* __restrict__ g_k1,
-                                         const float* __restrict__ g_loss, const float* __restrict__ kl0, const float* __restrict__ kl1,
-                                         const float* __restrict__ live, const float* __restrict__ count, const float* __restrict__ beta,
-                                         int64_t n, MtrssmElboSchedule p, float* __restrict__ g_nll_a, float* __restrict__ g_nll_v,
-                                         float* __restrict__ g_kl0, float* __restrict__ g_kl1) {
+template <bool SCHED>
+__global__ void elbo_bwd_kernel(const float* __restrict__ g_recon, const float* __restrict__ g_k0, const float* __restrict__ g_k1,
+                                const float* __restrict__ g_loss, const float* __restrict__ kl0, const float* __restrict__ kl1,
+                                const float* __restrict__ live, const float* __restrict__ count, const float* __restrict__ beta, int64_t n,
+                                MtrssmElboSchedule p, float* __restrict__ g_nll_a, float* __restrict__ g_nll_v, float* __restrict__ g_kl0,
+                                float* __restrict__ g_kl1) {
 #pragma clang fp contract(off)
   const float gl = g_loss ? g_loss[0] : 0.f;
   const float gn = (g_recon ? g_recon[0] : 0.f) + gl;
   const float cnt = live ? count[0] : (float)n;
-  const float b = beta[0];
-  const float v0 = cnt > 0.f ? ((g_k0 ? g_k0[0] : 0.f) + gl) * p.c0 * b / cnt : 0.f;
-  const float v1 = cnt > 0.f ? ((g_k1 ? g_k1[0] : 0.f) + gl) * p.c1 * b / cnt : 0.f;
+  const bool some = !live || cnt > 0.f;
+  auto plane = [&](const float* g, float c) {
+    const float v = ((g ? g[0] : 0.f) + gl) * c;
+    return (SCHED ? v * beta[0] : v) / cnt;
+  };
+  const float v0 = some ? plane(g_k0, p.c0) : 0.f, v1 = some ? plane(g_k1, p.c1) : 0.f;
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i == 0) { g_nll_a[0] = p.w_a * gn; g_nll_v[0] = p.w_v * gn; }
+  if (i == 0) { g_nll_a[0] = SCHED ? p.w_a * gn : gn; g_nll_v[0] = SCHED ? p.w_v * gn : gn; }
   if (i < n) {
     const bool on = !live || live[i] != 0.f;
-    g_kl0[i] = on && !(kl0[i] < p.free0) ? v0 : 0.f;
-    if (g_kl1) g_kl1[i] = on && !(kl1[i] < p.free1) ? v1 : 0.f;
+    g_kl0[i] = on && !(SCHED && kl0[i] < p.free0) ? v0 : 0.f;
+    if (g_kl1) g_kl1[i] = on && !(SCHED && kl1[i] < p.free1) ? v1 : 0.f;
   }
 }
-static bool elbo_schedule_ok(const char* what, const MtrssmElboSchedule& p, const float* live, const float* count) {
+
+// The six entry points' launchers: `sched` picks the instantiation (and asks for what only it reads), `what` is the entry's name.
+static bool elbo_args_ok(const char* what, bool sched, const MtrssmElboSchedule& p, const float* live, const float* count) {
   if ((live == nullptr) != (count == nullptr)) { set_error("%s: live and count come together (both null: every step is live)", what); return false; }
-  if (!(p.warmup >= 0.f) || !(p.warmup < 16777216.f)) { set_error("%s: warmup must lie in [0, 2^24), got %g", what, (double)p.warmup); return false; }
+  if (sched && (!(p.warmup >= 0.f) || !(p.warmup < 16777216.f))) { set_error("%s: warmup must lie in [0, 2^24), got %g", what, (double)p.warmup); return false; }
   return true;
+}
+static int elbo_fwd(const char* what, bool sched, const float* nll_a, const float* nll_v, const float* kl0, const float* kl1, const float* live,
+                    const float* count, const float* step, int64_t n, MtrssmElboSchedule p, float* o_recon, float* o_k0, float* o_k1,
+                    float* o_loss, float* o_beta, float* o_stats, hipStream_t s) {
+  if (!nll_a || !nll_v || !kl0 || !o_recon || !o_k0 || !o_loss || (sched && (!o_beta || !o_stats)) || n <= 0) {
+    set_error("%s: bad argument", what);
+    return MTRSSM_EINVAL;
+  }
+  if (!elbo_args_ok(what, sched, p, live, count)) return MTRSSM_EINVAL;
+  if (sched && p.warmup > 0.f && !step) { set_error("%s: a warm-up of %g steps needs the device scalar step (null)", what, (double)p.warmup); return MTRSSM_EINVAL; }
+  set_last_kernel(sched ? "mtrssm::elbo_fwd_kernel<scheduled>" : "mtrssm::elbo_fwd_kernel<unscheduled>");
+  hipLaunchKernelGGL(sched ? elbo_fwd_kernel<true> : elbo_fwd_kernel<false>, dim3(1), dim3(kThreads), 0, s, nll_a, nll_v, kl0, kl1, live, count,
+                     step, n, p, o_recon, o_k0, o_k1, o_loss, o_beta, o_stats);
+  return check_launch(what);
+}
+static int elbo_bwd(const char* what, bool sched, const float* g_recon, const float* g_k0, const float* g_k1, const float* g_loss, const float* kl0,
+                    const float* kl1, const float* live, const float* count, const float* beta, int64_t n, MtrssmElboSchedule p,
+                    float* g_nll_a, float* g_nll_v, float* g_kl0, float* g_kl1, hipStream_t s) {
+  if (!g_nll_a || !g_nll_v || !g_kl0 || (sched && (!kl0 || !beta || (g_kl1 && !kl1))) || n <= 0) { set_error("%s: bad argument", what); return MTRSSM_EINVAL; }
+  if (!elbo_args_ok(what, sched, p, live, count)) return MTRSSM_EINVAL;
+  set_last_kernel(sched ? "mtrssm::elbo_bwd_kernel<scheduled>" : "mtrssm::elbo_bwd_kernel<unscheduled>");
+  hipLaunchKernelGGL(sched ? elbo_bwd_kernel<true> : elbo_bwd_kernel<false>, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
+                     g_recon, g_k0, g_k1, g_loss, kl0, kl1, live, count, beta, n, p, g_nll_a, g_nll_v, g_kl0, g_kl1);
+  return check_launch(what);
+}
+
+int elbo_combine_fwd_launch(const float* nll_a, const float* nll_v, const float* kl0, const float* kl1, int64_t n, float c0, float c1,
+                            float* o_recon, float* o_k0, float* o_k1, float* o_loss, hipStream_t s) {
+  return elbo_fwd("elbo_combine_fwd", false, nll_a, nll_v, kl0, kl1, nullptr, nullptr, nullptr, n, MtrssmElboSchedule{c0, c1}, o_recon, o_k0, o_k1,
+                  o_loss, nullptr, nullptr, s);
+}
+int elbo_combine_bwd_launch(const float* g_recon, const float* g_k0, const float* g_k1, const float* g_loss, int64_t n, float c0, float c1,
+                            float* g_nll_a, float* g_nll_v, float* g_kl0, float* g_kl1, hipStream_t s) {
+  return elbo_bwd("elbo_combine_bwd", false, g_recon, g_k0, g_k1, g_loss, nullptr, nullptr, nullptr, nullptr, nullptr, n, MtrssmElboSchedule{c0, c1},
+                  g_nll_a, g_nll_v, g_kl0, g_kl1, s);
+}
+int elbo_combine_counted_fwd_launch(const float* nll_a, const float* nll_v, const float* kl0, const float* kl1, const float* live,
+                                    const float* count, int64_t n, float c0, float c1, float* o_recon, float* o_k0, float* o_k1, float* o_loss,
+                                    hipStream_t s) {
+  if (!live || !count) { set_error("elbo_combine_counted_fwd: bad argument"); return MTRSSM_EINVAL; }
+  return elbo_fwd("elbo_combine_counted_fwd", false, nll_a, nll_v, kl0, kl1, live, count, nullptr, n, MtrssmElboSchedule{c0, c1}, o_recon, o_k0,
+                  o_k1, o_loss, nullptr, nullptr, s);
+}
+int elbo_combine_counted_bwd_launch(const float* g_recon, const float* g_k0, const float* g_k1, const float* g_loss, const float* live,
+                                    const float* count, int64_t n, float c0, float c1, float* g_nll_a, float* g_nll_v, float* g_kl0, float* g_kl1,
+                                    hipStream_t s) {
+  if (!live || !count) { set_error("elbo_combine_counted_bwd: bad argument"); return MTRSSM_EINVAL; }
+  return elbo_bwd("elbo_combine_counted_bwd", false, g_recon, g_k0, g_k1, g_loss, nullptr, nullptr, live, count, nullptr, n,
+                  MtrssmElboSchedule{c0, c1}, g_nll_a, g_nll_v, g_kl0, g_kl1, s);
 }
 int elbo_schedule_fwd_launch(const float* nll_a, const float* nll_v, const float* kl0, const float* kl1, const float* live, const float* count,
                              const float* step, int64_t n, MtrssmElboSchedule p, float* o_recon, float* o_k0, float* o_k1, float* o_loss,
                              float* o_beta, float* o_stats, hipStream_t s) {
-  if (!nll_a || !nll_v || !kl0 || !o_recon || !o_k0 || !o_loss || !o_beta || !o_stats || n <= 0) {
-    set_error("elbo_schedule_fwd: bad argument");
-    return MTRSSM_EINVAL;
-  }
-  if (!elbo_schedule_ok("elbo_schedule_fwd", p, live, count)) return MTRSSM_EINVAL;
-  if (p.warmup > 0.f && !step) { set_error("elbo_schedule_fwd: a warm-up of %g steps needs the device scalar step (null)", (double)p.warmup); return MTRSSM_EINVAL; }
-  set_last_kernel("mtrssm::elbo_schedule_fwd_kernel");
-  hipLaunchKernelGGL(elbo_schedule_fwd_kernel, dim3(1), dim3(kThreads), 0, s, nll_a, nll_v, kl0, kl1, live, count, step, n, p, o_recon, o_k0, o_k1,
-                     o_loss, o_beta, o_stats);
-  return check_launch("elbo_schedule_fwd");
+  return elbo_fwd("elbo_schedule_fwd", true, nll_a, nll_v, kl0, kl1, live, count, step, n, p, o_recon, o_k0, o_k1, o_loss, o_beta, o_stats, s);
 }
 int elbo_schedule_bwd_launch(const float* g_recon, const float* g_k0, const float* g_k1, const float* g_loss, const float* kl0, const float* kl1,
                              const float* live, const float* count, const float* beta, int64_t n, MtrssmElboSchedule p, float* g_nll_a,
                              float* g_nll_v, float* g_kl0, float* g_kl1, hipStream_t s) {
-  if (!kl0 || !beta || !g_nll_a || !g_nll_v || !g_kl0 || (g_kl1 && !kl1) || n <= 0) { set_error("elbo_schedule_bwd: bad argument"); return MTRSSM_EINVAL; }
-  if (!elbo_schedule_ok("elbo_schedule_bwd", p, live, count)) return MTRSSM_EINVAL;
-  set_last_kernel("mtrssm::elbo_schedule_bwd_kernel");
-  hipLaunchKernelGGL(elbo_schedule_bwd_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, g_recon, g_k0, g_k1, g_loss,
-                     kl0, kl1, live, count, beta, n, p, g_nll_a, g_nll_v, g_kl0, g_kl1);
-  return check_launch("elbo_schedule_bwd");
+  return elbo_bwd("elbo_schedule_bwd", true, g_recon, g_k0, g_k1, g_loss, kl0, kl1, live, count, beta, n, p, g_nll_a, g_nll_v, g_kl0, g_kl1, s);
 }
 
 int nll_fwd_launch(const float* pred, const float* target, int64_t frames, int64_t event, int act, float* out, hipStream_t s) {
@@ -633,12 +564,23 @@ int nll_masked_bwd_launch(const float* pred, const float* target, const float* p
 }
 
 // ------------------------------------------------------------------------------------------------
-// Modality dropout: uniforms -> everything a masked train step reads, no host involvement.
+// Step masks: uniforms, lengths and contexts -> everything a masked train step reads, no host involvement.  ONE kernel, three KINDs.
+// Every (b, t) of the GLOBAL batch is visited (grid-stride); the rank's rows [row0, row0 + b_local) are written out, all rows are
+// counted: wave shuffle + LDS reduction, then ONE vector atomic per workgroup and count.  The counts are whole numbers below
+// 2^24 (checked by the launch), so the fp32 atomic sums are exact whatever order they arrive in.
+// Modality dropout:
 //   present_m(b, t) = u[b, t / span, m] >= p_m   (fp32 compare), m = 0 audio, 1 vision;
 //   at t = 0 only, a row with neither present gets the modality with the larger u (tie: audio).
-// Every (b, t) of the GLOBAL batch is visited (grid-stride); the rank's rows [row0, row0 + b_local) are written out, all rows are
-// counted: wave shuffle + LDS reduction, then ONE vector atomic per workgroup and modality.  The counts are whole numbers
-// below 2^24 (checked by the launch), so the fp32 atomic sums are exact whatever order they arrive in.
+// kMaskDropout: that rule alone; codes, the two present planes, mask0; counts = {audio, vision}.
+// kMaskRagged: row b of the global batch has valid[b] live steps (clamped into [0, T] here), step (b, t) is
+//   live iff t < valid[b].  A modality is present iff the step is live AND (no dropout -- u == nullptr -- or the dropout rule says
+//   so, its t = 0 fix-up applied BEFORE the AND).  Beside the dropout outputs: the `live` plane the counted ELBO epilogue reads,
+//   last[r] = valid - 1 (-1: an empty row) for the carry's save, and a third count, the live steps.
+// kMaskForecast: row b observes a context of c_b = lo + min(int(u_context[b] * float(n)), n - 1) frames,
+//   n = hi - lo + 1 (ONE fp32 multiply, truncated), and runs open loop after it.  live as above (valid == nullptr: T), observed =
+//   live AND t < c_b; a modality is SEEN iff the step is observed AND (no dropout or the dropout rule says present, fix-up BEFORE
+//   the AND).  What is seen (codes, plane_a / plane_v, mask0) and what is reconstructed (plane_live, the target) are different
+//   planes here; plane_obs is the KL's plane.  counts = {live, observed}.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void dropout_present(const float* __restrict__ u, long b, int t, int span, int S, float p_audio, float p_vision,
                                                 bool& a, bool& v) {
@@ -651,110 +593,109 @@ __device__ __forceinline__ void dropout_present(const float* __restrict__ u, lon
   }
 }
 
-__global__ __launch_bounds__(kThreads) void modality_dropout_kernel(
-    const float* __restrict__ u, float p_audio, float p_vision, int span, int T, int S, long b_global, long row0, long b_local,
-    int* __restrict__ codes, float* __restrict__ present_audio, float* __restrict__ present_vision, unsigned char* __restrict__ mask0,
-    float* __restrict__ counts) {
-  __shared__ float red_a[kThreads / kWave], red_v[kThreads / kWave];
+enum { kMaskDropout, kMaskRagged, kMaskForecast };
+
+template <int KIND>
+__global__ __launch_bounds__(kThreads) void step_mask_kernel(
+    const int* __restrict__ valid, const float* __restrict__ u, const float* __restrict__ u_context, float p_audio, float p_vision, int span,
+    int T, int S, int lo, int n_bins, long b_global, long row0, long b_local, int* __restrict__ codes, float* __restrict__ plane_a,
+    float* __restrict__ plane_v, float* __restrict__ plane_live, float* __restrict__ plane_obs, unsigned char* __restrict__ mask0,
+    int* __restrict__ last, float* __restrict__ counts) {
+  constexpr int NC = KIND == kMaskRagged ? 3 : 2;
+  __shared__ float red[NC][kThreads / kWave];
   const long total = b_global * T;
-  float na = 0.f, nv = 0.f;
+  float cnt[NC] = {};
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const long b = i / T;
     const int t = (int)(i - b * T);
-    bool a, v;
-    dropout_present(u, b, t, span, S, p_audio, p_vision, a, v);
-    na += a ? 1.f : 0.f;
-    nv += v ? 1.f : 0.f;
+    int n = T;
+    if (KIND == kMaskRagged || (KIND == kMaskForecast && valid)) n = valid[b];
+    n = n < 0 ? 0 : (n > T ? T : n);
+    const bool on = KIND == kMaskDropout || t < n;
+    bool obs = on;
+    if constexpr (KIND == kMaskForecast) {
+      const long long bin = (long long)(u_context[b] * (float)n_bins);  // (64-bit, then clamped: above 2^24 (float)n_bins may round up, to as much as 2^31)
+      obs = on && t < lo + (int)(bin < n_bins - 1 ? bin : n_bins - 1);
+    }
+    bool a = true, v = true;
+    if (KIND == kMaskDropout || u) dropout_present(u, b, t, span, S, p_audio, p_vision, a, v);
+    a = a && obs;
+    v = v && obs;
+    if constexpr (KIND == kMaskForecast) {
+      cnt[0] += on ? 1.f : 0.f;
+      cnt[1] += obs ? 1.f : 0.f;
+    } else {
+      cnt[0] += a ? 1.f : 0.f;
+      cnt[1] += v ? 1.f : 0.f;
+      if constexpr (KIND == kMaskRagged) cnt[2] += on ? 1.f : 0.f;
+    }
     const long r = b - row0;
     if (r >= 0 && r < b_local) {
       const long o = r * T + t;
       codes[o] = (a ? 1 : 0) | (v ? 2 : 0);
-      present_audio[o] = a ? 1.f : 0.f;
-      present_vision[o] = v ? 1.f : 0.f;
+      plane_a[o] = a ? 1.f : 0.f;
+      plane_v[o] = v ? 1.f : 0.f;
+      if constexpr (KIND != kMaskDropout) plane_live[o] = on ? 1.f : 0.f;
+      if constexpr (KIND == kMaskForecast) plane_obs[o] = obs ? 1.f : 0.f;
       if (t == 0) {
         mask0[2 * r] = a ? 1 : 0;
         mask0[2 * r + 1] = v ? 1 : 0;
+        if constexpr (KIND != kMaskDropout) last[r] = n - 1;
       }
     }
   }
-  const float ta = block_sum(na, red_a), tv = block_sum(nv, red_v);
+  float tot[NC];
+#pragma unroll
+  for (int k = 0; k < NC; ++k) tot[k] = block_sum(cnt[k], red[k]);
   if (threadIdx.x == 0) {
-    atomicAdd(counts, ta);
-    atomicAdd(counts + 1, tv);
+#pragma unroll
+    for (int k = 0; k < NC; ++k) atomicAdd(counts + k, tot[k]);
   }
+}
+
+// The three entry points' shared checks and launch; `what` is the entry's name, the caller has checked its own pointers.
+static int step_mask_launch(const char* what, int kind, const int32_t* valid, const float* u, const float* u_context, int64_t b_global, int64_t T,
+                            int64_t span, float p_audio, float p_vision, int64_t lo, int64_t hi, int64_t row0, int64_t b_local, int32_t* codes,
+                            float* plane_a, float* plane_v, float* plane_live, float* plane_obs, unsigned char* mask0, int32_t* last,
+                            float* counts, hipStream_t s) {
+  if (b_global <= 0 || T <= 0 || span <= 0 || b_local <= 0 || row0 < 0 || row0 + b_local > b_global) {
+    set_error("%s: need B_global, T, span, B_local > 0 and 0 <= row0 <= B_global - B_local (got %lld %lld %lld %lld %lld)", what,
+              (long long)b_global, (long long)T, (long long)span, (long long)b_local, (long long)row0);
+    return MTRSSM_EINVAL;
+  }
+  if (kind == kMaskForecast && (lo < 1 || hi < lo || hi >= (int64_t)1 << 31)) {
+    set_error("%s: need 1 <= lo <= hi < 2^31 (got %lld, %lld)", what, (long long)lo, (long long)hi);
+    return MTRSSM_EINVAL;
+  }
+  if (u && (!(p_audio >= 0.f && p_audio < 1.f) || !(p_vision >= 0.f && p_vision < 1.f))) {
+    set_error("%s: probabilities must be in [0, 1) (got %g, %g)", what, (double)p_audio, (double)p_vision);
+    return MTRSSM_EINVAL;
+  }
+  if (b_global * T >= (int64_t)1 << 24) {
+    set_error("%s: %lld frames (the fp32 counts are exact below 2^24)", what, (long long)(b_global * T));
+    return MTRSSM_EINVAL;
+  }
+  if (span >= (int64_t)1 << 31) { set_error("%s: span %lld does not fit 31 bits", what, (long long)span); return MTRSSM_EINVAL; }
+  if (((uintptr_t)u & 7) || (((uintptr_t)valid | (uintptr_t)u_context) & 3)) {
+    set_error("%s: the mask uniforms must be 8-byte, valid and u_context 4-byte aligned", what);
+    return MTRSSM_EINVAL;
+  }
+  if (int rc = clear_async(counts, (kind == kMaskRagged ? 3 : 2) * sizeof(float), s)) return rc;
+  const int grid = grid_for(b_global * T) < 64 ? grid_for(b_global * T) : 64;
+  const auto kernel = kind == kMaskDropout ? step_mask_kernel<kMaskDropout> : kind == kMaskRagged ? step_mask_kernel<kMaskRagged> : step_mask_kernel<kMaskForecast>;
+  set_last_kernel(kind == kMaskDropout ? "mtrssm::step_mask_kernel<dropout>" : kind == kMaskRagged ? "mtrssm::step_mask_kernel<ragged>" : "mtrssm::step_mask_kernel<forecast>");
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), 0, s, reinterpret_cast<const int*>(valid), u, u_context, p_audio, p_vision, (int)span,
+                     (int)T, (int)((T + span - 1) / span), (int)lo, (int)(hi - lo + 1), (long)b_global, (long)row0, (long)b_local,
+                     reinterpret_cast<int*>(codes), plane_a, plane_v, plane_live, plane_obs, mask0, reinterpret_cast<int*>(last), counts);
+  return check_launch(what);
 }
 
 int modality_dropout_launch(const float* u, int64_t b_global, int64_t T, int64_t span, float p_audio, float p_vision, int64_t row0,
                             int64_t b_local, int32_t* codes, float* present_audio, float* present_vision, unsigned char* mask0,
                             float* counts, hipStream_t s) {
   if (!u || !codes || !present_audio || !present_vision || !mask0 || !counts) { set_error("modality_dropout: null pointer"); return MTRSSM_EINVAL; }
-  if (b_global <= 0 || T <= 0 || span <= 0 || b_local <= 0 || row0 < 0 || row0 + b_local > b_global) {
-    set_error("modality_dropout: need B_global, T, span, B_local > 0 and 0 <= row0 <= B_global - B_local (got %lld %lld %lld %lld %lld)",
-              (long long)b_global, (long long)T, (long long)span, (long long)b_local, (long long)row0);
-    return MTRSSM_EINVAL;
-  }
-  if (!(p_audio >= 0.f && p_audio < 1.f) || !(p_vision >= 0.f && p_vision < 1.f)) {
-    set_error("modality_dropout: probabilities must be in [0, 1) (got %g, %g)", (double)p_audio, (double)p_vision);
-    return MTRSSM_EINVAL;
-  }
-  if (b_global * T >= (int64_t)1 << 24 || span >= (int64_t)1 << 31) {
-    set_error("modality_dropout: %lld frames (the fp32 present-frame counts are exact below 2^24)", (long long)(b_global * T));
-    return MTRSSM_EINVAL;
-  }
-  if ((uintptr_t)u & 7) { set_error("modality_dropout: u must be 8-byte aligned"); return MTRSSM_EINVAL; }
-  if (int rc = clear_async(counts, 2 * sizeof(float), s)) return rc;
-  const int64_t S = (T + span - 1) / span;
-  set_last_kernel("mtrssm::modality_dropout_kernel");
-  hipLaunchKernelGGL(modality_dropout_kernel, dim3(grid_for(b_global * T) < 64 ? grid_for(b_global * T) : 64), dim3(kThreads), 0, s, u, p_audio,
-                     p_vision, (int)span, (int)T, (int)S, (long)b_global, (long)row0, (long)b_local, codes, present_audio, present_vision,
-                     mask0, counts);
-  return check_launch("modality_dropout");
-}
-
-// Ragged batches: row b of the global batch has valid[b] live steps (clamped into [0, T] here), step
-// (b, t) is live iff t < valid[b].  A modality is present iff the step is live AND (no dropout -- u == nullptr -- or the dropout
-// rule above says so, its t = 0 fix-up applied BEFORE the AND).  Beside modality_dropout_kernel's outputs: the `live` plane the
-// counted ELBO epilogue reads, last[r] = valid - 1 (-1: an empty row) for the carry's save, and a third count, the live steps.
-__global__ __launch_bounds__(kThreads) void step_mask_ragged_kernel(
-    const int* __restrict__ valid, const float* __restrict__ u, float p_audio, float p_vision, int span, int T, int S, long b_global, long row0,
-    long b_local, int* __restrict__ codes, float* __restrict__ present_audio, float* __restrict__ present_vision, float* __restrict__ live,
-    unsigned char* __restrict__ mask0, int* __restrict__ last, float* __restrict__ counts) {
-  __shared__ float red_a[kThreads / kWave], red_v[kThreads / kWave], red_l[kThreads / kWave];
-  const long total = b_global * T;
-  float na = 0.f, nv = 0.f, nl = 0.f;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const long b = i / T;
-    const int t = (int)(i - b * T);
-    int n = valid[b];
-    n = n < 0 ? 0 : (n > T ? T : n);
-    const bool on = t < n;
-    bool a = true, v = true;
-    if (u) dropout_present(u, b, t, span, S, p_audio, p_vision, a, v);
-    a = a && on;
-    v = v && on;
-    na += a ? 1.f : 0.f;
-    nv += v ? 1.f : 0.f;
-    nl += on ? 1.f : 0.f;
-    const long r = b - row0;
-    if (r >= 0 && r < b_local) {
-      const long o = r * T + t;
-      codes[o] = (a ? 1 : 0) | (v ? 2 : 0);
-      present_audio[o] = a ? 1.f : 0.f;
-      present_vision[o] = v ? 1.f : 0.f;
-      live[o] = on ? 1.f : 0.f;
-      if (t == 0) {
-        mask0[2 * r] = a ? 1 : 0;
-        mask0[2 * r + 1] = v ? 1 : 0;
-        last[r] = n - 1;
-      }
-    }
-  }
-  const float ta = block_sum(na, red_a), tv = block_sum(nv, red_v), tl = block_sum(nl, red_l);
-  if (threadIdx.x == 0) {
-    atomicAdd(counts, ta);
-    atomicAdd(counts + 1, tv);
-    atomicAdd(counts + 2, tl);
-  }
+  return step_mask_launch("modality_dropout", kMaskDropout, nullptr, u, nullptr, b_global, T, span, p_audio, p_vision, 1, 1, row0, b_local, codes,
+                          present_audio, present_vision, nullptr, nullptr, mask0, nullptr, counts, s);
 }
 
 int step_mask_ragged_launch(const int32_t* valid, const float* u, int64_t b_global, int64_t T, int64_t span, float p_audio, float p_vision,
@@ -764,77 +705,8 @@ int step_mask_ragged_launch(const int32_t* valid, const float* u, int64_t b_glob
     set_error("step_mask_ragged: null pointer");
     return MTRSSM_EINVAL;
   }
-  if (b_global <= 0 || T <= 0 || span <= 0 || b_local <= 0 || row0 < 0 || row0 + b_local > b_global) {
-    set_error("step_mask_ragged: need B_global, T, span, B_local > 0 and 0 <= row0 <= B_global - B_local (got %lld %lld %lld %lld %lld)",
-              (long long)b_global, (long long)T, (long long)span, (long long)b_local, (long long)row0);
-    return MTRSSM_EINVAL;
-  }
-  if (u && (!(p_audio >= 0.f && p_audio < 1.f) || !(p_vision >= 0.f && p_vision < 1.f))) {
-    set_error("step_mask_ragged: probabilities must be in [0, 1) (got %g, %g)", (double)p_audio, (double)p_vision);
-    return MTRSSM_EINVAL;
-  }
-  if (b_global * T >= (int64_t)1 << 24) {
-    set_error("step_mask_ragged: %lld frames (the fp32 counts are exact below 2^24)", (long long)(b_global * T));
-    return MTRSSM_EINVAL;
-  }
-  if (span >= (int64_t)1 << 31) { set_error("step_mask_ragged: span %lld does not fit 31 bits", (long long)span); return MTRSSM_EINVAL; }
-  if (((uintptr_t)u & 7) || ((uintptr_t)valid & 3)) { set_error("step_mask_ragged: u must be 8-byte, valid 4-byte aligned"); return MTRSSM_EINVAL; }
-  if (int rc = clear_async(counts, 3 * sizeof(float), s)) return rc;
-  const int64_t S = (T + span - 1) / span;
-  set_last_kernel("mtrssm::step_mask_ragged_kernel");
-  hipLaunchKernelGGL(step_mask_ragged_kernel, dim3(grid_for(b_global * T) < 64 ? grid_for(b_global * T) : 64), dim3(kThreads), 0, s, valid, u,
-                     p_audio, p_vision, (int)span, (int)T, (int)S, (long)b_global, (long)row0, (long)b_local, codes, present_audio,
-                     present_vision, live, mask0, last, counts);
-  return check_launch("step_mask_ragged");
-}
-
-// Forecast objective: row b observes a context of c_b = lo + min(int(u_context[b] * float(n)), n - 1) frames,
-// n = hi - lo + 1 (ONE fp32 multiply, truncated), and runs open loop after it.  live = t < valid[b] as above (valid == nullptr: T),
-// observed = live AND t < c_b; a modality is SEEN iff the step is observed AND (no dropout -- u_mask == nullptr -- or the dropout
-// rule says present, its t = 0 fix-up applied BEFORE the AND).  What is seen (codes, seen_*, mask0) and what is reconstructed
-// (`target` = live) are different planes here; `observed` is the KL's plane.  counts = {live, observed} over the global batch.
-__global__ __launch_bounds__(kThreads) void step_mask_forecast_kernel(
-    const int* __restrict__ valid, const float* __restrict__ u_mask, const float* __restrict__ u_context, float p_audio, float p_vision,
-    int span, int T, int S, int lo, int n_bins, long b_global, long row0, long b_local, int* __restrict__ codes,
-    float* __restrict__ seen_audio, float* __restrict__ seen_vision, float* __restrict__ target, float* __restrict__ observed,
-    unsigned char* __restrict__ mask0, int* __restrict__ last, float* __restrict__ counts) {
-  __shared__ float red_l[kThreads / kWave], red_o[kThreads / kWave];
-  const long total = b_global * T;
-  float nl = 0.f, no = 0.f;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const long b = i / T;
-    const int t = (int)(i - b * T);
-    int n = valid ? valid[b] : T;
-    n = n < 0 ? 0 : (n > T ? T : n);
-    const long long bin = (long long)(u_context[b] * (float)n_bins);  // (64-bit, then clamped: above 2^24 (float)n_bins may round up, to as much as 2^31)
-    const int c = lo + (int)(bin < n_bins - 1 ? bin : n_bins - 1);
-    const bool on = t < n, obs = on && t < c;
-    bool a = true, v = true;
-    if (u_mask) dropout_present(u_mask, b, t, span, S, p_audio, p_vision, a, v);
-    a = a && obs;
-    v = v && obs;
-    nl += on ? 1.f : 0.f;
-    no += obs ? 1.f : 0.f;
-    const long r = b - row0;
-    if (r >= 0 && r < b_local) {
-      const long o = r * T + t;
-      codes[o] = (a ? 1 : 0) | (v ? 2 : 0);
-      seen_audio[o] = a ? 1.f : 0.f;
-      seen_vision[o] = v ? 1.f : 0.f;
-      target[o] = on ? 1.f : 0.f;
-      observed[o] = obs ? 1.f : 0.f;
-      if (t == 0) {
-        mask0[2 * r] = a ? 1 : 0;
-        mask0[2 * r + 1] = v ? 1 : 0;
-        last[r] = n - 1;
-      }
-    }
-  }
-  const float tl = block_sum(nl, red_l), to = block_sum(no, red_o);
-  if (threadIdx.x == 0) {
-    atomicAdd(counts, tl);
-    atomicAdd(counts + 1, to);
-  }
+  return step_mask_launch("step_mask_ragged", kMaskRagged, valid, u, nullptr, b_global, T, span, p_audio, p_vision, 1, 1, row0, b_local, codes,
+                          present_audio, present_vision, live, nullptr, mask0, last, counts, s);
 }
 
 int step_mask_forecast_launch(const int32_t* valid, const float* u_mask, const float* u_context, int64_t b_global, int64_t T, int64_t span,
@@ -845,35 +717,8 @@ int step_mask_forecast_launch(const int32_t* valid, const float* u_mask, const f
     set_error("step_mask_forecast: null pointer");
     return MTRSSM_EINVAL;
   }
-  if (b_global <= 0 || T <= 0 || span <= 0 || b_local <= 0 || row0 < 0 || row0 + b_local > b_global) {
-    set_error("step_mask_forecast: need B_global, T, span, B_local > 0 and 0 <= row0 <= B_global - B_local (got %lld %lld %lld %lld %lld)",
-              (long long)b_global, (long long)T, (long long)span, (long long)b_local, (long long)row0);
-    return MTRSSM_EINVAL;
-  }
-  if (lo < 1 || hi < lo || hi >= (int64_t)1 << 31) {
-    set_error("step_mask_forecast: need 1 <= lo <= hi < 2^31 (got %lld, %lld)", (long long)lo, (long long)hi);
-    return MTRSSM_EINVAL;
-  }
-  if (u_mask && (!(p_audio >= 0.f && p_audio < 1.f) || !(p_vision >= 0.f && p_vision < 1.f))) {
-    set_error("step_mask_forecast: probabilities must be in [0, 1) (got %g, %g)", (double)p_audio, (double)p_vision);
-    return MTRSSM_EINVAL;
-  }
-  if (b_global * T >= (int64_t)1 << 24) {
-    set_error("step_mask_forecast: %lld frames (the fp32 counts are exact below 2^24)", (long long)(b_global * T));
-    return MTRSSM_EINVAL;
-  }
-  if (span >= (int64_t)1 << 31) { set_error("step_mask_forecast: span %lld does not fit 31 bits", (long long)span); return MTRSSM_EINVAL; }
-  if (((uintptr_t)u_mask & 7) || (((uintptr_t)valid | (uintptr_t)u_context) & 3)) {
-    set_error("step_mask_forecast: u_mask must be 8-byte, valid and u_context 4-byte aligned");
-    return MTRSSM_EINVAL;
-  }
-  if (int rc = clear_async(counts, 2 * sizeof(float), s)) return rc;
-  const int64_t S = (T + span - 1) / span;
-  set_last_kernel("mtrssm::step_mask_forecast_kernel");
-  hipLaunchKernelGGL(step_mask_forecast_kernel, dim3(grid_for(b_global * T) < 64 ? grid_for(b_global * T) : 64), dim3(kThreads), 0, s, valid,
-                     u_mask, u_context, p_audio, p_vision, (int)span, (int)T, (int)S, (int)lo, (int)(hi - lo + 1), (long)b_global, (long)row0,
-                     (long)b_local, codes, seen_audio, seen_vision, target, observed, mask0, last, counts);
-  return check_launch("step_mask_forecast");
+  return step_mask_launch("step_mask_forecast", kMaskForecast, valid, u_mask, u_context, b_global, T, span, p_audio, p_vision, lo, hi, row0, b_local,
+                          codes, seen_audio, seen_vision, target, observed, mask0, last, counts, s);
 }
 
 int sumsq_launch(const float* x, int64_t n, float* out, hipStream_t s) {
@@ -947,170 +792,20 @@ int unpack_conv_grads_launch(const int64_t* table, int count, int blocks_per_ent
 //   target[b, t, :] = store[idx[b], t, :]            (TakeFirstN: t < T <= Tfull, transform.py:31-52)
 //   input [b, t, :] = target + noise[b, t, :] * std  (GaussianNoise, transform.py:55-72: two roundings, mul then add)
 // Replaces EpisodeDataset.__getitem__ + default collate of the 6-tuple StackDataset (dataset.py:84-112,
-// mrssm/dataset.py:155-183).  One float4 per thread; rows are E floats, E % 4 == 0.
+// mrssm/dataset.py:155-183).  One float4 per thread; rows are E floats, E % 4 == 0.  ONE kernel, three MODEs:
+// kGatherFirst: the first T frames, as above.
+// kGatherWindow: a WINDOW of each episode, target[b, t, :] = store[idx[b], start[b] + t, :].  start[b] is read on the device (a
+//   replayed graph takes new windows without a host round trip), so the launcher cannot range-check it: the kernel clamps it into
+//   [0, Tfull - T] and the host validates the starts where it makes them (dataset.py).  A start shifts a row by whole frames of E
+//   floats, E % 4 == 0: every access stays a 16-byte one.  (Neither of these two modes clamps idx[b].)
+// kGatherRagged: the window gather for episodes of different lengths: frame start[b] + t of episode idx[b] is
+//   LIVE iff it lies before lengths[idx[b]]; a dead frame is exactly 0 in target and input (no noise added) and issues no load and
+//   no generator work.  start[b] is clamped into [0, Tfull] (a chunk may hang over the end of the store: the length test keeps
+//   every read inside it), lengths into [0, Tfull], idx[b] into [0, n_episodes).  valid_out[b] (optional) = clamp(length - start,
+//   0, T), the row's live steps.
+// The noise is the `noise` plane (null: input = target), or with SEEDED the generator below.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void episode_gather_kernel(
-    const float* __restrict__ store, const long* __restrict__ idx, const float* __restrict__ noise, long B, long T, long Tfull,
-    long E4, float std_, float* __restrict__ input, float* __restrict__ target) {
-#pragma clang fp contract(off)  // mul then add, each rounded (torch's `data + randn * std`): hipcc would contract to v_pk_fma_f32
-  const long per_b = T * E4;
-  const long total = B * per_b;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const long b = i / per_b, r = i - b * per_b;  // r = t * E4 + e4
-    const float4 x = reinterpret_cast<const float4*>(store)[idx[b] * Tfull * E4 + r];
-    if (target) reinterpret_cast<float4*>(target)[i] = x;
-    if (input) {
-      float4 y = x;
-      if (noise) {
-        const float4 n = reinterpret_cast<const float4*>(noise)[i];
-        const float px = n.x * std_, py = n.y * std_, pz = n.z * std_, pw = n.w * std_;  // plain expressions: the pragma
-        y.x = x.x + px;                                                                  // above does not reach into the
-        y.y = x.y + py;                                                                  // headers' __fmul_rn / __fadd_rn
-        y.z = x.z + pz;
-        y.w = x.w + pw;
-      }
-      reinterpret_cast<float4*>(input)[i] = y;
-    }
-  }
-}
-
-int episode_gather_launch(const float* store, const int64_t* idx, const float* noise, int64_t n_episodes, int64_t B, int64_t T,
-                          int64_t Tfull, int64_t E, float std_, float* input, float* target, hipStream_t s) {
-  if (!store || !idx || (!input && !target) || n_episodes <= 0 || B <= 0 || T <= 0 || Tfull < T || E <= 0) {
-    set_error("episode_gather: bad argument (need 0 < T <= Tfull, B, E > 0, an output)");
-    return MTRSSM_EINVAL;
-  }
-  if (E % 4) { set_error("episode_gather: the event size %ld must be a multiple of 4 floats", (long)E); return MTRSSM_EINVAL; }
-  if (((uintptr_t)store | (uintptr_t)noise | (uintptr_t)input | (uintptr_t)target) & 15) {
-    set_error("episode_gather: buffers must be 16-byte aligned");
-    return MTRSSM_EINVAL;
-  }
-  set_last_kernel("mtrssm::episode_gather_kernel");
-  hipLaunchKernelGGL(episode_gather_kernel, dim3(grid_for(B * T * E / 4)), dim3(kThreads), 0, s, store, reinterpret_cast<const long*>(idx),
-                     noise, (long)B, (long)T, (long)Tfull, (long)(E / 4), std_, input, target);
-  return check_launch("episode_gather");
-}
-
-// The same pair from a WINDOW of each episode: target[b, t, :] = store[idx[b], start[b] + t, :].  start[b] is read on the device
-// (a replayed graph takes new windows without a host round trip), so the launcher cannot range-check it: the kernel clamps it
-// into [0, Tfull - T] and the host validates the starts where it makes them (dataset.py).  A start shifts a row by whole frames
-// of E floats, E % 4 == 0: every access stays a 16-byte one.
-__global__ __launch_bounds__(kThreads) void episode_gather_window_kernel(
-    const float* __restrict__ store, const long* __restrict__ idx, const int* __restrict__ start, const float* __restrict__ noise,
-    long B, long T, long Tfull, long E4, float std_, float* __restrict__ input, float* __restrict__ target) {
-#pragma clang fp contract(off)  // (as episode_gather_kernel: mul then add, each rounded)
-  const long per_b = T * E4;
-  const long total = B * per_b;
-  const long last = Tfull - T;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const long b = i / per_b, r = i - b * per_b;  // r = t * E4 + e4
-    long s = start[b];
-    s = s < 0 ? 0 : (s > last ? last : s);
-    const float4 x = reinterpret_cast<const float4*>(store)[(idx[b] * Tfull + s) * E4 + r];
-    if (target) reinterpret_cast<float4*>(target)[i] = x;
-    if (input) {
-      float4 y = x;
-      if (noise) {
-        const float4 n = reinterpret_cast<const float4*>(noise)[i];
-        const float px = n.x * std_, py = n.y * std_, pz = n.z * std_, pw = n.w * std_;
-        y.x = x.x + px;
-        y.y = x.y + py;
-        y.z = x.z + pz;
-        y.w = x.w + pw;
-      }
-      reinterpret_cast<float4*>(input)[i] = y;
-    }
-  }
-}
-
-int episode_gather_window_launch(const float* store, const int64_t* idx, const int32_t* start, const float* noise, int64_t n_episodes,
-                                 int64_t B, int64_t T, int64_t Tfull, int64_t E, float std_, float* input, float* target, hipStream_t s) {
-  if (!store || !idx || (!input && !target) || n_episodes <= 0 || B <= 0 || T <= 0 || Tfull < T || E <= 0) {
-    set_error("episode_gather_window: bad argument (need 0 < T <= Tfull, B, E > 0, an output)");
-    return MTRSSM_EINVAL;
-  }
-  if (!start) { set_error("episode_gather_window: start is null (mtrssm_episode_gather reads the first T frames)"); return MTRSSM_EINVAL; }
-  if (E % 4) { set_error("episode_gather_window: the event size %ld must be a multiple of 4 floats", (long)E); return MTRSSM_EINVAL; }
-  if (((uintptr_t)store | (uintptr_t)noise | (uintptr_t)input | (uintptr_t)target) & 15) {
-    set_error("episode_gather_window: buffers must be 16-byte aligned");
-    return MTRSSM_EINVAL;
-  }
-  if ((uintptr_t)start & 3) { set_error("episode_gather_window: start must be 4-byte aligned"); return MTRSSM_EINVAL; }
-  set_last_kernel("mtrssm::episode_gather_window_kernel");
-  hipLaunchKernelGGL(episode_gather_window_kernel, dim3(grid_for(B * T * E / 4)), dim3(kThreads), 0, s, store,
-                     reinterpret_cast<const long*>(idx), reinterpret_cast<const int*>(start), noise, (long)B, (long)T, (long)Tfull,
-                     (long)(E / 4), std_, input, target);
-  return check_launch("episode_gather_window");
-}
-
-// The window gather for episodes of different lengths: frame start[b] + t of episode idx[b] is LIVE iff it
-// lies before lengths[idx[b]]; a dead frame is exactly 0 in target and input (no noise added) and issues no load.  start[b] is
-// clamped into [0, Tfull] (a chunk may hang over the end of the store: the length test keeps every read inside it), lengths into
-// [0, Tfull], idx[b] into [0, n_episodes).  valid_out[b] (optional) = clamp(length - start, 0, T), the row's live steps.
-__global__ __launch_bounds__(kThreads) void episode_gather_ragged_kernel(
-    const float* __restrict__ store, const long* __restrict__ idx, const int* __restrict__ start, const int* __restrict__ lengths,
-    const float* __restrict__ noise, long n_episodes, long B, long T, long Tfull, long E4, float std_, float* __restrict__ input,
-    float* __restrict__ target, int* __restrict__ valid_out) {
-#pragma clang fp contract(off)  // (as episode_gather_kernel: mul then add, each rounded)
-  const long per_b = T * E4;
-  const long total = B * per_b;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const long b = i / per_b, r = i - b * per_b;  // r = t * E4 + e4
-    const long t = r / E4;
-    long s = start[b];
-    s = s < 0 ? 0 : (s > Tfull ? Tfull : s);
-    long ep = idx[b];
-    ep = ep < 0 ? 0 : (ep >= n_episodes ? n_episodes - 1 : ep);
-    long len = lengths[ep];
-    len = len < 0 ? 0 : (len > Tfull ? Tfull : len);
-    const bool on = s + t < len;  // (< Tfull: the read below stays inside the episode)
-    if (valid_out && r == 0) {
-      const long n = len - s;
-      valid_out[b] = (int)(n < 0 ? 0 : (n > T ? T : n));
-    }
-    float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (on) x = reinterpret_cast<const float4*>(store)[(ep * Tfull + s) * E4 + r];
-    if (target) reinterpret_cast<float4*>(target)[i] = x;
-    if (input) {
-      float4 y = x;
-      if (noise && on) {
-        const float4 n = reinterpret_cast<const float4*>(noise)[i];
-        const float px = n.x * std_, py = n.y * std_, pz = n.z * std_, pw = n.w * std_;
-        y.x = x.x + px;
-        y.y = x.y + py;
-        y.z = x.z + pz;
-        y.w = x.w + pw;
-      }
-      reinterpret_cast<float4*>(input)[i] = y;
-    }
-  }
-}
-
-int episode_gather_ragged_launch(const float* store, const int64_t* idx, const int32_t* start, const int32_t* lengths, const float* noise,
-                                 int64_t n_episodes, int64_t B, int64_t T, int64_t Tfull, int64_t E, float std_, float* input, float* target,
-                                 int32_t* valid_out, hipStream_t s) {
-  if (!store || !idx || (!input && !target) || n_episodes <= 0 || B <= 0 || T <= 0 || Tfull < T || E <= 0) {
-    set_error("episode_gather_ragged: bad argument (need 0 < T <= Tfull, B, E > 0, an output)");
-    return MTRSSM_EINVAL;
-  }
-  if (!start || !lengths) { set_error("episode_gather_ragged: start or lengths is null"); return MTRSSM_EINVAL; }
-  if (E % 4) { set_error("episode_gather_ragged: the event size %ld must be a multiple of 4 floats", (long)E); return MTRSSM_EINVAL; }
-  if (((uintptr_t)store | (uintptr_t)noise | (uintptr_t)input | (uintptr_t)target) & 15) {
-    set_error("episode_gather_ragged: buffers must be 16-byte aligned");
-    return MTRSSM_EINVAL;
-  }
-  if (((uintptr_t)start | (uintptr_t)lengths | (uintptr_t)valid_out) & 3) {
-    set_error("episode_gather_ragged: start, lengths and valid_out must be 4-byte aligned");
-    return MTRSSM_EINVAL;
-  }
-  set_last_kernel("mtrssm::episode_gather_ragged_kernel");
-  hipLaunchKernelGGL(episode_gather_ragged_kernel, dim3(grid_for(B * T * E / 4)), dim3(kThreads), 0, s, store,
-                     reinterpret_cast<const long*>(idx), reinterpret_cast<const int*>(start), reinterpret_cast<const int*>(lengths), noise,
-                     (long)n_episodes, (long)B, (long)T, (long)Tfull, (long)(E / 4), std_, input, target, reinterpret_cast<int*>(valid_out));
-  return check_launch("episode_gather_ragged");
-}
-
-// The three gathers above with the standard normals made in the kernel: the noise of a frame is a pure
+// SEEDED: the standard normals are made in the kernel: the noise of a frame is a pure
 // function of (key, epoch, episode, absolute frame, element), never stored, whatever row of whatever batch the frame lands in.
 //   x[0..3] = Philox4x32-10(counter = (e4, frame, low 32 bits of episode, epoch), key = (key0, key1))
 //   two Box-Muller pairs, (x0, x1) -> elements 4 e4 + 0, 1 and (x2, x3) -> elements 4 e4 + 2, 3:
@@ -1143,27 +838,28 @@ __device__ __forceinline__ void box_muller(unsigned xa, unsigned xb, float& z0, 
   z1 = r * sn;
 }
 
-// MODE 0: the first T frames; 1: windows (start clamped as episode_gather_window_kernel clamps it); 2: ragged (start, lengths, idx
-// clamped and valid_out written as episode_gather_ragged_kernel does; a dead frame issues no load and no generator work).
-template <int MODE>
-__global__ __launch_bounds__(kThreads) void episode_gather_seeded_kernel(
+enum { kGatherFirst, kGatherWindow, kGatherRagged };
+
+template <int MODE, bool SEEDED>
+__global__ __launch_bounds__(kThreads) void episode_gather_kernel(
     const float* __restrict__ store, const long* __restrict__ idx, const int* __restrict__ start, const int* __restrict__ lengths,
-    unsigned key0, unsigned key1, unsigned epoch, long n_episodes, long B, long T, long Tfull, long E4, float std_,
-    float* __restrict__ input, float* __restrict__ target, int* __restrict__ valid_out) {
-#pragma clang fp contract(off)  // (as episode_gather_kernel: mul then add, each rounded)
+    const float* __restrict__ noise, unsigned key0, unsigned key1, unsigned epoch, long n_episodes, long B, long T, long Tfull, long E4,
+    float std_, float* __restrict__ input, float* __restrict__ target, int* __restrict__ valid_out) {
+#pragma clang fp contract(off)  // mul then add, each rounded (torch's `data + randn * std`): hipcc would contract to v_pk_fma_f32
   const long per_b = T * E4;
   const long total = B * per_b;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const long b = i / per_b, r = i - b * per_b;  // r = t * E4 + e4
-    const long t = r / E4, e4 = r - t * E4;
+    long t = 0;
+    if constexpr (MODE == kGatherRagged || SEEDED) t = r / E4;
     long ep = idx[b], s = 0;
     bool on = true;
-    if constexpr (MODE == 1) {
+    if constexpr (MODE == kGatherWindow) {
       const long last = Tfull - T;
       s = start[b];
       s = s < 0 ? 0 : (s > last ? last : s);
     }
-    if constexpr (MODE == 2) {
+    if constexpr (MODE == kGatherRagged) {
       s = start[b];
       s = s < 0 ? 0 : (s > Tfull ? Tfull : s);
       ep = ep < 0 ? 0 : (ep >= n_episodes ? n_episodes - 1 : ep);
@@ -1180,15 +876,19 @@ __global__ __launch_bounds__(kThreads) void episode_gather_seeded_kernel(
     if (target) reinterpret_cast<float4*>(target)[i] = x;
     if (input) {
       float4 y = x;
-      if (on) {
-        unsigned w[4];
-        philox4x32_10((unsigned)e4, (unsigned)(s + t), (unsigned)ep, epoch, key0, key1, w);
+      if (on && (SEEDED || noise)) {
         float4 n;
-        box_muller(w[0], w[1], n.x, n.y);
-        box_muller(w[2], w[3], n.z, n.w);
-        const float px = n.x * std_, py = n.y * std_, pz = n.z * std_, pw = n.w * std_;
-        y.x = x.x + px;
-        y.y = x.y + py;
+        if constexpr (SEEDED) {
+          unsigned w[4];
+          philox4x32_10((unsigned)(r - t * E4), (unsigned)(s + t), (unsigned)ep, epoch, key0, key1, w);
+          box_muller(w[0], w[1], n.x, n.y);
+          box_muller(w[2], w[3], n.z, n.w);
+        } else {
+          n = reinterpret_cast<const float4*>(noise)[i];
+        }
+        const float px = n.x * std_, py = n.y * std_, pz = n.z * std_, pw = n.w * std_;  // plain expressions: the pragma
+        y.x = x.x + px;                                                                  // above does not reach into the
+        y.y = x.y + py;                                                                  // headers' __fmul_rn / __fadd_rn
         y.z = x.z + pz;
         y.w = x.w + pw;
       }
@@ -1197,36 +897,70 @@ __global__ __launch_bounds__(kThreads) void episode_gather_seeded_kernel(
   }
 }
 
-int episode_gather_seeded_launch(const float* store, const int64_t* idx, const int32_t* start, const int32_t* lengths, int32_t* valid_out,
-                                 uint32_t key0, uint32_t key1, uint32_t epoch, int64_t n_episodes, int64_t B, int64_t T, int64_t Tfull,
-                                 int64_t E, float std_, float* input, float* target, hipStream_t s) {
+// The four entry points' shared checks and launch; `what` is the entry's name, the caller has checked which of start / lengths /
+// valid_out it needs.  lengths given: ragged; else start given: windows; else the first T frames.
+static int episode_gather(const char* what, bool seeded, const float* store, const int64_t* idx, const int32_t* start, const int32_t* lengths,
+                          const float* noise, uint32_t key0, uint32_t key1, uint32_t epoch, int64_t n_episodes, int64_t B, int64_t T,
+                          int64_t Tfull, int64_t E, float std_, float* input, float* target, int32_t* valid_out, hipStream_t s) {
   if (!store || !idx || (!input && !target) || n_episodes <= 0 || B <= 0 || T <= 0 || Tfull < T || E <= 0) {
-    set_error("episode_gather_seeded: bad argument (need 0 < T <= Tfull, B, E > 0, an output)");
+    set_error("%s: bad argument (need 0 < T <= Tfull, B, E > 0, an output)", what);
     return MTRSSM_EINVAL;
   }
-  if (lengths && !start) { set_error("episode_gather_seeded: lengths without start (a ragged batch needs its windows' starts)"); return MTRSSM_EINVAL; }
-  if (valid_out && !lengths) { set_error("episode_gather_seeded: valid_out without lengths"); return MTRSSM_EINVAL; }
-  if (E % 4) { set_error("episode_gather_seeded: the event size %ld must be a multiple of 4 floats", (long)E); return MTRSSM_EINVAL; }
-  if (E / 4 > 0xffffffffL) { set_error("episode_gather_seeded: the event size %ld exceeds the 32-bit element counter", (long)E); return MTRSSM_EINVAL; }
-  if (((uintptr_t)store | (uintptr_t)input | (uintptr_t)target) & 15) {
-    set_error("episode_gather_seeded: buffers must be 16-byte aligned");
+  if (E % 4) { set_error("%s: the event size %ld must be a multiple of 4 floats", what, (long)E); return MTRSSM_EINVAL; }
+  if (seeded && E / 4 > 0xffffffffL) { set_error("%s: the event size %ld exceeds the 32-bit element counter", what, (long)E); return MTRSSM_EINVAL; }
+  if (((uintptr_t)store | (uintptr_t)noise | (uintptr_t)input | (uintptr_t)target) & 15) {
+    set_error("%s: buffers must be 16-byte aligned", what);
     return MTRSSM_EINVAL;
   }
   if (((uintptr_t)start | (uintptr_t)lengths | (uintptr_t)valid_out) & 3) {
-    set_error("episode_gather_seeded: start, lengths and valid_out must be 4-byte aligned");
+    set_error("%s: start, lengths and valid_out must be 4-byte aligned", what);
     return MTRSSM_EINVAL;
   }
-  set_last_kernel("mtrssm::episode_gather_seeded_kernel");
-#define MTRSSM_SEEDED(MODE)                                                                                                                \
-  hipLaunchKernelGGL(episode_gather_seeded_kernel<MODE>, dim3(grid_for(B * T * E / 4)), dim3(kThreads), 0, s, store,                        \
-                     reinterpret_cast<const long*>(idx), reinterpret_cast<const int*>(start), reinterpret_cast<const int*>(lengths), key0, \
-                     key1, epoch, (long)n_episodes, (long)B, (long)T, (long)Tfull, (long)(E / 4), std_, input, target,                     \
-                     reinterpret_cast<int*>(valid_out))
-  if (lengths) MTRSSM_SEEDED(2);
-  else if (start) MTRSSM_SEEDED(1);
-  else MTRSSM_SEEDED(0);
-#undef MTRSSM_SEEDED
-  return check_launch("episode_gather_seeded");
+  const int mode = lengths ? kGatherRagged : (start ? kGatherWindow : kGatherFirst);
+  static const struct {
+    decltype(&episode_gather_kernel<kGatherFirst, false>) kernel;
+    const char* name;
+  } table[2][3] = {{{episode_gather_kernel<kGatherFirst, false>, "mtrssm::episode_gather_kernel<first>"},
+                    {episode_gather_kernel<kGatherWindow, false>, "mtrssm::episode_gather_kernel<window>"},
+                    {episode_gather_kernel<kGatherRagged, false>, "mtrssm::episode_gather_kernel<ragged>"}},
+                   {{episode_gather_kernel<kGatherFirst, true>, "mtrssm::episode_gather_kernel<first, seeded>"},
+                    {episode_gather_kernel<kGatherWindow, true>, "mtrssm::episode_gather_kernel<window, seeded>"},
+                    {episode_gather_kernel<kGatherRagged, true>, "mtrssm::episode_gather_kernel<ragged, seeded>"}}};
+  set_last_kernel(table[seeded][mode].name);
+  hipLaunchKernelGGL(table[seeded][mode].kernel, dim3(grid_for(B * T * E / 4)), dim3(kThreads), 0, s, store, reinterpret_cast<const long*>(idx),
+                     reinterpret_cast<const int*>(start), reinterpret_cast<const int*>(lengths), noise, key0, key1, epoch, (long)n_episodes,
+                     (long)B, (long)T, (long)Tfull, (long)(E / 4), std_, input, target, reinterpret_cast<int*>(valid_out));
+  return check_launch(what);
+}
+
+int episode_gather_launch(const float* store, const int64_t* idx, const float* noise, int64_t n_episodes, int64_t B, int64_t T,
+                          int64_t Tfull, int64_t E, float std_, float* input, float* target, hipStream_t s) {
+  return episode_gather("episode_gather", false, store, idx, nullptr, nullptr, noise, 0, 0, 0, n_episodes, B, T, Tfull, E, std_, input, target,
+                        nullptr, s);
+}
+
+int episode_gather_window_launch(const float* store, const int64_t* idx, const int32_t* start, const float* noise, int64_t n_episodes,
+                                 int64_t B, int64_t T, int64_t Tfull, int64_t E, float std_, float* input, float* target, hipStream_t s) {
+  if (!start) { set_error("episode_gather_window: start is null (mtrssm_episode_gather reads the first T frames)"); return MTRSSM_EINVAL; }
+  return episode_gather("episode_gather_window", false, store, idx, start, nullptr, noise, 0, 0, 0, n_episodes, B, T, Tfull, E, std_, input,
+                        target, nullptr, s);
+}
+
+int episode_gather_ragged_launch(const float* store, const int64_t* idx, const int32_t* start, const int32_t* lengths, const float* noise,
+                                 int64_t n_episodes, int64_t B, int64_t T, int64_t Tfull, int64_t E, float std_, float* input, float* target,
+                                 int32_t* valid_out, hipStream_t s) {
+  if (!start || !lengths) { set_error("episode_gather_ragged: start or lengths is null"); return MTRSSM_EINVAL; }
+  return episode_gather("episode_gather_ragged", false, store, idx, start, lengths, noise, 0, 0, 0, n_episodes, B, T, Tfull, E, std_, input,
+                        target, valid_out, s);
+}
+
+int episode_gather_seeded_launch(const float* store, const int64_t* idx, const int32_t* start, const int32_t* lengths, int32_t* valid_out,
+                                 uint32_t key0, uint32_t key1, uint32_t epoch, int64_t n_episodes, int64_t B, int64_t T, int64_t Tfull,
+                                 int64_t E, float std_, float* input, float* target, hipStream_t s) {
+  if (lengths && !start) { set_error("episode_gather_seeded: lengths without start (a ragged batch needs its windows' starts)"); return MTRSSM_EINVAL; }
+  if (valid_out && !lengths) { set_error("episode_gather_seeded: valid_out without lengths"); return MTRSSM_EINVAL; }
+  return episode_gather("episode_gather_seeded", true, store, idx, start, lengths, nullptr, key0, key1, epoch, n_episodes, B, T, Tfull, E, std_,
+                        input, target, valid_out, s);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -17,8 +17,6 @@
 
 namespace mtrssm {
 
-void set_error(const char* fmt, ...);        // capi.hip
-void set_last_kernel(const char* name);
 int device_cu_count();
 
 constexpr int kWT = 256;                 // threads per workgroup: one wave per SIMD (512 registers each), the K range of a tile split over them

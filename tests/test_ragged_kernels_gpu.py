@@ -7,7 +7,7 @@ import ctypes as C
 import pytest
 import torch
 
-from multimodal_mtrssm_amd import _lib, carry, dropout, scan
+from multimodal_mtrssm_amd import ElboSchedule, _lib, carry, dropout, scan
 from multimodal_mtrssm_amd import dataset as ds
 from multimodal_mtrssm_amd import transform as tr
 from multimodal_mtrssm_amd.core import _elbo
@@ -146,6 +146,39 @@ def test_counted_combine(two: bool) -> None:  # noqa: FBT001
     z_out, z_grads = run(_mask_with(torch.zeros(n, device=DEV), torch.zeros((), device=DEV)))
     assert float(z_out[1]) == 0.0 and float(z_out[2]) == 0.0 and torch.equal(z_out[3], z_out[0])
     assert all(not bool(gk.any()) for gk in z_grads[2:])
+
+
+def test_unscheduled_epilogue_keeps_negative_kl_and_refuses_mismatched_planes() -> None:
+    """Without a schedule nothing is clipped: negative per-step KLs enter the plain and the counted sums as they are (n = 257: one
+    step past a block).  Reference: ``_elbo``'s eager rule on the same fp32 values in float64; 2e-6 as ``test_counted_combine``.  And
+    two KL planes of different sizes raise before any launch on every path."""
+    n, c0, c1 = 257, 0.7, 0.3
+    g = torch.Generator().manual_seed(8)
+    nll = [torch.rand((), generator=g) for _ in range(2)]
+    kls = [torch.rand(n, generator=g) * 3.0 - 0.75, torch.rand(n, generator=g) * 2.0 - 0.5]
+    assert all(bool((kl < 0).any()) for kl in kls)
+    live = (torch.rand(n, generator=g) < 0.6).float()
+    live[kls[0].argmin()] = 1.0  # (the most negative step is a live one)
+    count = live.sum() / 2.0
+    for two, counted in ((False, False), (True, False), (False, True), (True, True)):
+        runs = []
+        for where, dtype in (("cpu", torch.float64), (DEV, torch.float32)):
+            a, v, k0, k1 = (x.to(where, dtype).requires_grad_() for x in (*nll, *kls))
+            z = torch.zeros(1, device=where)
+            sm = StepMask(z, z, z, z, z, z, live.to(where), count.to(where), None) if counted else None
+            out = _elbo(a, v, k0, c0, k1 if two else None, c1, step_mask=sm)
+            (out[3] + 0.5 * out[1] + (0.25 * out[2] if two else 0.0)).backward()
+            keep = (0, 1, 2, 3) if two else (0, 1, 3)
+            runs.append([out[j].detach().cpu().double() for j in keep] + [x.grad.cpu().double() for x in (a, v, k0, *([k1] if two else []))])
+        for want, got in zip(*runs, strict=True):
+            torch.testing.assert_close(got, want, rtol=2e-6, atol=0)
+        clipped = c0 * (kls[0].double().clamp(min=0) * (live.double() if counted else 1.0)).sum() / (float(count) if counted else n)
+        assert float(runs[1][1]) < float(clipped) * (1 - 1e-3)  # (what free bits of 0 would have given)
+    short = torch.rand(4, device=DEV)
+    masks = (None, StepMask(*(torch.zeros(1, device=DEV),) * 6, torch.ones(6, device=DEV), torch.tensor(6.0, device=DEV), None))
+    for sm, schedule in ((masks[0], None), (masks[1], None), (masks[0], ElboSchedule()), (masks[1], ElboSchedule())):
+        with pytest.raises(ValueError, match="same number of steps"):
+            _elbo(nll[0].to(DEV), nll[1].to(DEV), torch.rand(6, device=DEV), c0, short, c1, step_mask=sm, schedule=schedule)
 
 
 # 4. save-at ----------------------------------------------------------------------------------------------------------------------

@@ -4,7 +4,7 @@
 
 feed   the 6-tuple feed (B = 64, T = 50, bench.py's frame sizes, T_full = 180 stored steps) in the modes first / random /
        sequential, all three in ONE process on the same stores, alternating `rounds` times: seq-steps/s per mode and round.
-       `first` launches episode_gather_kernel, the other two episode_gather_window_kernel, on the same shape, so a
+       `first` launches episode_gather_kernel<first>, the other two episode_gather_kernel<window>, on the same shape, so a
        `rocprofv3 --kernel-trace --stats -- python tools/window_feed_bench.py --skip-step` run compares the two per launch.
 step   one unmasked MoPoE-MRSSM train step, eager and captured, without and with a StateCarry (reset on every third step, as
        a three-chunk episode): ms per step, bench.py's warm-up / step discipline.
