@@ -870,11 +870,15 @@ int mtrssm_gaussian_nll_bwd(const float* pred, const float* target, const float*
                             int64_t frames, int64_t event, int32_t act, float* g_pred, void* stream);
 
 /* The same loss over the frames where a modality is present (missing-modality training, DESIGN.md section "Missing
- * modalities"): present[n] in {0, 1} per frame, count = sum_n present[n],
- *   nll = sum_n present[n] sum_e [ 0.5 (target - pred)^2 + 0.5 log(2 pi) ] / count   (0 when count = 0),
- * d pred = g_out * present[n] * (act(pred) - target) * act'(pred) / count (0 when count = 0).  `count` is a device scalar
- * (float) the caller forms, so neither call reads anything back to the host.  With every frame present the result is bitwise
- * the unmasked call's.  Null pointers, non-positive sizes or frames * event >= 2^31 return -1 without a launch. */
+ * modalities"): present[n] per frame (a frame counts when present[n] != 0), count = the divisor,
+ *   nll = sum_{n present} sum_e [ 0.5 (target - pred)^2 + 0.5 log(2 pi) ] / count   (0 when count <= 0),
+ * d pred = g_out * [n present] * (act(pred) - target) * act'(pred) / count (0 when count <= 0).  `count` is a device scalar
+ * (float) the caller forms, so neither call reads anything back to the host.  It is usually the number of present frames, but
+ * need not be: a data-parallel rank hands in (present frames of the global batch) / world, so that the mean over ranks is the
+ * global batch's loss.  The WHOLE per-frame term is divided by it, the constant included: the forward counts the present frames
+ * and adds 0.5 log(2 pi) * event * (present frames) / count, which is exactly the constant when count is their number.
+ * The prediction of an absent frame is never used, whatever it holds (NaN and Inf included): its gradient is 0.  With every
+ * frame present and count = frames the result is bitwise the unmasked call's.  Null pointers, non-positive sizes or frames * event >= 2^31 return -1 without a launch. */
 int mtrssm_gaussian_nll_masked_fwd(const float* pred, const float* target, const float* present, const float* count,
                                    int64_t frames, int64_t event, int32_t act, float* out, void* stream);
 int mtrssm_gaussian_nll_masked_bwd(const float* pred, const float* target, const float* present, const float* count,

@@ -84,17 +84,20 @@ __global__ void nll_bwd_kernel(const float* __restrict__ pred, const float* __re
 }
 
 // The NLL over the frames a modality is present in (core.py, missing modalities): an element of frame n counts when
-// present[n] != 0, the sum is divided by the device scalar *count (0 -> the loss is 0).  An absent element's difference is
-// zeroed before it is squared, so with every frame present the arithmetic -- and the launch shape -- is nll_fwd_kernel's.
+// present[n] != 0, the sum is divided by the device scalar *count (0 -> the loss is 0).  *count need not be the number of
+// present frames (a data-parallel rank: the global batch's / world); the constant 0.5 log(2 pi) per element belongs to the
+// per-frame term and is divided by it too: constant * (present frames) / count.  An absent element is taken out with a select
+// (forward: the difference before it is squared; backward: the finished product), so it may hold NaN or Inf, and with every
+// frame present the arithmetic -- and the launch shape -- is nll_fwd_kernel's.
 // EV4: event % 4 == 0, one frame per quad (one frame index per quad).  Frame indices are 32-bit divisions: the launchers
 // take n < 2^31 elements only.
 __device__ __forceinline__ bool frame_present(const float* __restrict__ present, uint32_t e, uint32_t event) {
   return present[e / event] != 0.f;
 }
 
+// the elements of the quad starting at element e0 that lie in absent frames set to 0 (a select: whatever they held, NaN included)
 template <bool EV4>
-__device__ __forceinline__ float4 masked_diff(const float* __restrict__ present, uint32_t e0, uint32_t event, float4 t, float4 p) {
-  float4 a = make_float4(t.x - p.x, t.y - p.y, t.z - p.z, t.w - p.w);
+__device__ __forceinline__ float4 masked_zero(const float* __restrict__ present, uint32_t e0, uint32_t event, float4 a) {
   if (EV4) {
     if (!frame_present(present, e0, event)) a = make_float4(0.f, 0.f, 0.f, 0.f);
   } else {
@@ -104,6 +107,11 @@ __device__ __forceinline__ float4 masked_diff(const float* __restrict__ present,
     if (!frame_present(present, e0 + 3, event)) a.w = 0.f;
   }
   return a;
+}
+
+template <bool EV4>
+__device__ __forceinline__ float4 masked_diff(const float* __restrict__ present, uint32_t e0, uint32_t event, float4 t, float4 p) {
+  return masked_zero<EV4>(present, e0, event, make_float4(t.x - p.x, t.y - p.y, t.z - p.z, t.w - p.w));
 }
 
 template <bool TANH, bool EV4>
@@ -136,7 +144,16 @@ __global__ void nll_masked_fwd_kernel(const float* __restrict__ pred, const floa
   }
   const float tot = block_sum(acc, red);
   const float cnt = count[0];
-  if (threadIdx.x == 0 && cnt > 0.f) atomicAdd(out, tot * (1.f / cnt) + (blockIdx.x == 0 ? constant : 0.f));
+  // the constant is a term of every PRESENT frame and is divided by *count like the rest: constant * sum(present) / count.
+  // Block 0 counts the frames (whole numbers in fp32: exact below 2^24); with count = sum(present) the quotient is exactly 1.
+  float share = 0.f;
+  if (blockIdx.x == 0) {
+    __syncthreads();  // `red` is read by wave 0 above
+    float np = 0.f;
+    for (int64_t f = threadIdx.x; f < n / event; f += blockDim.x) np += present[f] != 0.f ? 1.f : 0.f;
+    share = block_sum(np, red) / cnt;
+  }
+  if (threadIdx.x == 0 && cnt > 0.f) atomicAdd(out, tot * (1.f / cnt) + (blockIdx.x == 0 ? constant * share : 0.f));
 }
 
 template <bool TANH, bool EV4>
@@ -157,9 +174,10 @@ __global__ void nll_masked_bwd_kernel(const float* __restrict__ pred, const floa
       p.x = tanh_fast(p.x); p.y = tanh_fast(p.y); p.z = tanh_fast(p.z); p.w = tanh_fast(p.w);
       d = make_float4(1.f - p.x * p.x, 1.f - p.y * p.y, 1.f - p.z * p.z, 1.f - p.w * p.w);
     }
-    // (p - t) with absent elements zeroed: the negated masked difference
-    const float4 q = masked_diff<EV4>(present, (uint32_t)(4 * i), (uint32_t)event, p, t);
-    o4[i] = make_float4(g * q.x * d.x, g * q.y * d.y, g * q.z * d.z, g * q.w * d.w);
+    // absent elements are zeroed AFTER the product, as in the tail below: an absent frame's prediction may be anything (NaN: a
+    // frame nobody computed), and 0 * (1 - tanh(NaN)^2) is NaN.  With every frame present this is nll_bwd_kernel's arithmetic.
+    const float4 r = make_float4(g * (p.x - t.x) * d.x, g * (p.y - t.y) * d.y, g * (p.z - t.z) * d.z, g * (p.w - t.w) * d.w);
+    o4[i] = masked_zero<EV4>(present, (uint32_t)(4 * i), (uint32_t)event, r);
   }
   if (blockIdx.x == 0)
     for (int64_t i = n4 * 4 + threadIdx.x; i < n; i += blockDim.x) {

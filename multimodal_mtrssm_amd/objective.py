@@ -15,11 +15,26 @@ from torch import Tensor
 from multimodal_mtrssm_amd import _lib
 
 
+def _aligned(t: Tensor) -> Tensor:
+    """``t`` contiguous at a 16-byte aligned address, as the kernels' 16 B / lane accesses need it: ``t`` itself when it already
+    is (no launch), else a copy -- a contiguous slice such as ``x[1:]`` of an odd event size starts anywhere."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _fresh_like(pred: Tensor) -> Tensor:
+    """The gradient buffer: a new allocation, which the caching allocator hands out on far more than 16 bytes.  Nothing is ever
+    copied here (there is nothing to copy yet); should an allocator break that, the launch below would refuse the pointer."""
+    g_pred = torch.empty_like(pred)
+    assert g_pred.data_ptr() % 16 == 0, "a fresh allocation is 16-byte aligned"  # noqa: S101
+    return g_pred
+
+
 class _GaussianNLL(torch.autograd.Function):
     @staticmethod
     def forward(ctx, prediction: Tensor, target: Tensor, event_ndims: int, act: int = 0) -> Tensor:  # noqa: ANN001
         lib = _lib.load()
-        pred, tgt = prediction.contiguous(), target.contiguous()
+        pred, tgt = _aligned(prediction), _aligned(target)
         event = math.prod(pred.shape[-event_ndims:])
         frames = pred.numel() // event
         out = torch.empty((), device=pred.device, dtype=torch.float32)
@@ -34,7 +49,7 @@ class _GaussianNLL(torch.autograd.Function):
     def backward(ctx, g_out: Tensor):  # noqa: ANN001, ANN205
         lib = _lib.load()
         pred, tgt = ctx.saved_tensors
-        g_pred = torch.empty_like(pred)
+        g_pred = _fresh_like(pred)
         g = g_out.contiguous()
         _lib.check(_lib.TIMERS.call("mtrssm_gaussian_nll_bwd", lib.mtrssm_gaussian_nll_bwd, _lib.ptr(pred), _lib.ptr(tgt), _lib.ptr(g), ctx.frames,
                                     ctx.event, ctx.act, _lib.ptr(g_pred), _lib.stream_ptr(pred.device), nbytes=12.0 * pred.numel()),
@@ -49,7 +64,7 @@ class _GaussianNLLMasked(torch.autograd.Function):
     @staticmethod
     def forward(ctx, prediction: Tensor, target: Tensor, present: Tensor, count: Tensor, event_ndims: int, act: int = 0) -> Tensor:  # noqa: ANN001, PLR0913
         lib = _lib.load()
-        pred, tgt = prediction.contiguous(), target.contiguous()
+        pred, tgt = _aligned(prediction), _aligned(target)
         event = math.prod(pred.shape[-event_ndims:])
         frames = pred.numel() // event
         out = torch.empty((), device=pred.device, dtype=torch.float32)
@@ -64,7 +79,7 @@ class _GaussianNLLMasked(torch.autograd.Function):
     def backward(ctx, g_out: Tensor):  # noqa: ANN001, ANN205
         lib = _lib.load()
         pred, tgt, present, count = ctx.saved_tensors
-        g_pred = torch.empty_like(pred)
+        g_pred = _fresh_like(pred)
         g = g_out.contiguous()
         _lib.check(_lib.TIMERS.call("mtrssm_gaussian_nll_masked_bwd", lib.mtrssm_gaussian_nll_masked_bwd, _lib.ptr(pred), _lib.ptr(tgt),
                                     _lib.ptr(present), _lib.ptr(count), _lib.ptr(g), ctx.frames, ctx.event, ctx.act, _lib.ptr(g_pred),
@@ -108,7 +123,9 @@ def likelihood(prediction: Tensor, target: Tensor, event_ndims: int, scale: floa
             if out_act:
                 prediction = torch.tanh(prediction) if out_act == 3 else prediction  # noqa: PLR2004
             unit = _GaussianNLLMasked.apply(prediction / scale, target / scale, present, count, event_ndims, 0)
-            return unit + (count > 0).to(unit) * (math.prod(prediction.shape[-event_ndims:]) * math.log(scale))
+            # log(scale) is a term of every present frame, divided by count like the rest (count may be a rank's share)
+            share = torch.where(count > 0, (present != 0).sum() / count, torch.zeros_like(count)).reshape(())  # counted as the kernel does
+            return unit + share * (math.prod(prediction.shape[-event_ndims:]) * math.log(scale))
         return _GaussianNLLMasked.apply(prediction, target, present, count, event_ndims, int(out_act))
     if scale != 1.0:
         # Normal(pred, s): 0.5 ((t-p)/s)^2 + log s + 0.5 log 2pi, by rescaling the unit-scale kernel
