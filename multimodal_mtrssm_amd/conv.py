@@ -861,7 +861,7 @@ class _ConvTranspose2d(torch.autograd.Function):
 
 
 CONVT_BIAS_FUSE = True  # ConvTranspose2d bias gradients inside the weight-gradient kernels (mtrssm_conv_weight_grad_src_bias)
-RESBLOCK_FUSE = True  # the blocks' forward as ONE launch where the library has a fused kernel (mtrssm_residual_block_fwd)
+RESBLOCK_FUSE = os.environ.get("MTRSSM_RESBLOCK_FUSE", "1") != "0"  # the blocks' forward as ONE launch where the library has a fused kernel (mtrssm_residual_block_fwd)
 
 
 def _residual_job(x: Tensor, w3: Tensor, b3: Tensor, w1: Tensor, b1: Tensor, act: int, sub: int = 0) -> tuple | None:  # noqa: PLR0913

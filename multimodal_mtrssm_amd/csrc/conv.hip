@@ -1340,26 +1340,19 @@ struct SplitPlan {
   }
 };
 
-// MTRSSM_CONV_RESIDENT=0: the patch-staged kernel for every layer (A/B runs of conv3x3_resident_kernel)
-static bool resident_enabled() {
-  static const bool on = [] { const char* e = getenv("MTRSSM_CONV_RESIDENT"); return !(e && e[0] == '0'); }();
-  return on;
-}
-
-// MTRSSM_PATCH_768=0: 641..768-position patches (the k=4 s=2 backward-data gathers, 648 positions) back on the fp32 patch
-// kernel.  Round 1 measured that kernel faster for them (283 us per modality); with audio + vision paired into one launch the
-// split kernel takes 182 us for both (round 2), so it is the default now.
-static bool patch_limit_768() {
-  static const bool on = [] { const char* e = getenv("MTRSSM_PATCH_768"); return !(e && e[0] == '0'); }();
-  return on;
-}
-
-// hipFuncSetAttribute is per device: the "done" flags of the launch macros are kept per device (a process that drives several
-// GPUs -- not this package's one-process-per-GPU model, but nothing forbids it -- sets the attribute on each)
-static int device_slot() {
+// Dynamic LDS above the default limit has to be allowed per kernel, and hipFuncSetAttribute is per device: one granted size per
+// (instantiation, device), raised only when a launch asks for more -- for a fixed size that is once, and never while another
+// stream may be running the kernel.  (A process that drives several GPUs is not this package's one-process-per-GPU model, but
+// nothing forbids it.)
+template <auto Kernel>
+static void allow_lds(int bytes) {
+  static int granted_dev[64] = {};
   int dev = 0;
   (void)hipGetDevice(&dev);
-  return dev & 63;
+  int& granted = granted_dev[dev & 63];
+  if (bytes <= granted) return;
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  granted = bytes;
 }
 
 static int cu_count() {
@@ -1369,6 +1362,29 @@ static int cu_count() {
     return v;
   }();
   return n;
+}
+
+// Persistent workgroups of a launch that carries one or two problems: `slots` workgroups shared in proportion to the work items
+// ta : tb (rounded to nearest, at least one each), no problem with more workgroups than items.  tb == 0: one problem.
+struct PairSplit {
+  int na, nb;
+};
+static PairSplit split_slots(long ta, long tb, int slots) {
+  if (tb == 0) return {(int)(ta < slots ? ta : slots), 0};
+  long na = (slots * ta + (ta + tb) / 2) / (ta + tb);
+  na = na < 1 ? 1 : (na > slots - 1 ? slots - 1 : na);
+  return {(int)(na < ta ? na : ta), (int)(slots - na < tb ? slots - na : tb)};
+}
+
+// N frames over at most `slots` workgroups: frames per workgroup, and the workgroups that then have any
+struct FramesGrid {
+  int per, blocks;
+};
+static FramesGrid frames_grid(int N, int slots) {
+  int wgs = slots < 1 ? 1 : slots;
+  if (wgs > N) wgs = N;
+  const int per = (N + wgs - 1) / wgs;
+  return {per, (N + per - 1) / per};
 }
 
 static SplitPlan plan_split(const MtrssmConvGeom* g, bool has_wq) {
@@ -1386,7 +1402,7 @@ static SplitPlan plan_split(const MtrssmConvGeom* g, bool has_wq) {
   pl.sp = sp;
   if ((long)g->N * g->Cout * g->Ho * g->Wo >= (1L << 31)) return pl;
   // 3x3 / stride 1 / pad 1 layers of the residual stacks on 64-pixel planes (8x8, 16x4, 4x16): weights resident in registers (conv_resident.h)
-  if (sp == 2 && resident_enabled() && g->KH == 3 && g->KW == 3 && g->SS == 1 && g->OS == 1 && g->QY == 0 && g->QX == 0 && g->C2 == 0 &&
+  if (sp == 2 && g->KH == 3 && g->KW == 3 && g->SS == 1 && g->OS == 1 && g->QY == 0 && g->QX == 0 && g->C2 == 0 &&
       (g->Ws == 4 || g->Ws == 8 || g->Ws == 16) && g->Hs * g->Ws == 64 && g->Hq == g->Hs && g->Wq == g->Ws && g->Ho == g->Hs && g->Wo == g->Ws && g->Cpad == g->C && g->OFFY == -g->TS &&
       g->OFFX == -g->TS && (long)g->N * g->C * 64 < (1L << 31) && g->act != MTRSSM_ACT_TANH) {
     const int key = g->C * 1000 + g->Cout;
@@ -1405,7 +1421,7 @@ static SplitPlan plan_split(const MtrssmConvGeom* g, bool has_wq) {
     pl.kind = 1;
     pl.lds = (size_t)sp * (kTP + pl.tco) * 128;
     const int key = g->C * 1000 + g->Cout;
-    if (sp == 2 && resident_enabled() && (key == 64064 || key == 128064 || key == 64128) && g->Cpad == g->C && g->CoutPad == g->Cout &&
+    if (sp == 2 && (key == 64064 || key == 128064 || key == 64128) && g->Cpad == g->C && g->CoutPad == g->Cout &&
         (g->Hq * g->Wq) % 32 == 0 && g->act != MTRSSM_ACT_TANH && (long)g->N * g->C * g->Hq * g->Wq < (1L << 31))
       pl.stream = key;
     return pl;
@@ -1418,7 +1434,7 @@ static SplitPlan plan_split(const MtrssmConvGeom* g, bool has_wq) {
   pl.ngroups = taps / tgs;
   pl.lds = lds_of(tgs);
   pl.pit = pg.ps_raw <= 384 ? 3 : 6;
-  if (pl.lds <= 80 * 1024 && pg.ps_raw <= (patch_limit_768() ? 768 : 640) && (long)pg.ipg * g->C * g->Hs * g->Ws < (1L << 31) &&
+  if (pl.lds <= 80 * 1024 && pg.ps_raw <= 768 && (long)pg.ipg * g->C * g->Hs * g->Ws < (1L << 31) &&
       (long)sp * g->CoutPad * taps * g->Cpad < (1L << 31))
     pl.kind = 2;
   return pl;
@@ -1446,27 +1462,15 @@ static int launch_split(const SplitPlan& pl, size_t lds, const GatherProblem& pa
     }
     const int fpt = pl.res == 64064 || pl.res == 32064 || pl.res == 64032 ? 2 : 1;  // frames per tile
     const long ta = (pa.nx + fpt - 1) / fpt, tb = (pb.nx + fpt - 1) / fpt;
-    const int ncu = cu_count();
+    const PairSplit wg = split_slots(ta, tb, cu_count());
     GatherProblem qa = pa, qb = pb;
-    if (tb == 0) {
-      qa.nx = (int)(ta < ncu ? ta : ncu);
-      qb.nx = 0;
-    } else {
-      long na = (ncu * ta + (ta + tb) / 2) / (ta + tb);
-      na = na < 1 ? 1 : (na > ncu - 1 ? ncu - 1 : na);
-      qa.nx = (int)(na < ta ? na : ta);
-      qb.nx = (int)(ncu - na < tb ? ncu - na : tb);
-    }
+    qa.nx = wg.na;
+    qb.nx = wg.nb;
     const dim3 rgrid((unsigned)(qa.nx + qb.nx));
 #define MTRSSM_RES_LAUNCH_E(CIN_, NCT_, KS_, EPI_)                                                                   \
   {                                                                                                                   \
-    static bool attr_done_dev[64] = {}; bool& attr_done = attr_done_dev[device_slot()];                                                                                    \
     const size_t rl = res_lds_bytes<CIN_, NCT_, KS_>();                                                               \
-    if (!attr_done) {                                                                                                 \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_resident_kernel<CIN_, NCT_, KS_, EPI_>),        \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)rl);                                 \
-      attr_done = true;                                                                                               \
-    }                                                                                                                 \
+    allow_lds<conv3x3_resident_kernel<CIN_, NCT_, KS_, EPI_>>((int)rl);                                               \
     set_last_kernel("mtrssm::conv3x3_resident_kernel<" #CIN_ ", " #NCT_ ", " #KS_ ", " #EPI_ ">");                      \
     hipLaunchKernelGGL((conv3x3_resident_kernel<CIN_, NCT_, KS_, EPI_>), rgrid, dim3(kResThreads), rl, stream, qa, qb); \
     return launched("conv_gather_gemm(resident)");                                                                    \
@@ -1492,17 +1496,10 @@ static int launch_split(const SplitPlan& pl, size_t lds, const GatherProblem& pa
     if (da != 0 && da == db && same_shape) {
       const long ta = (long)pa.g.N * (pa.g.Hq * pa.g.Wq / 32), tb = pb.nx > 0 ? (long)pb.g.N * (pb.g.Hq * pb.g.Wq / 32) : 0;
       const long wa = (ta + 3) / 4, wb = (tb + 3) / 4;  // workgroups that would get at least one tile per wave
-      const int ncu = cu_count();
+      const PairSplit wg = split_slots(ta, tb, cu_count());  // shares by tiles; wa <= ta and wb <= tb cap them further
       GatherProblem qa = pa, qb = pb;
-      if (tb == 0) {
-        qa.nx = (int)(wa < ncu ? wa : ncu);
-        qb.nx = 0;
-      } else {
-        long na = (ncu * ta + (ta + tb) / 2) / (ta + tb);
-        na = na < 1 ? 1 : (na > ncu - 1 ? ncu - 1 : na);
-        qa.nx = (int)(na < wa ? na : wa);
-        qb.nx = (int)(ncu - na < wb ? ncu - na : wb);
-      }
+      qa.nx = (int)(wg.na < wa ? wg.na : wa);
+      qb.nx = (int)(wg.nb < wb ? wg.nb : wb);
       const dim3 sgrid((unsigned)(qa.nx + qb.nx));
 #define MTRSSM_STREAM_LAUNCH(CIN_, COUT_, FWD_)                                                                      \
   {                                                                                                                   \
@@ -1518,18 +1515,10 @@ static int launch_split(const SplitPlan& pl, size_t lds, const GatherProblem& pa
   }
   const dim3 grid((unsigned)(pa.nx + pb.nx), pl.ny);
   const int sp = pl.sp;
-#define MTRSSM_ATTR_ONCE(K_)                                                                                         \
-  {                                                                                                                   \
-    static bool attr_done_dev[64] = {}; bool& attr_done = attr_done_dev[device_slot()];                                                                                    \
-    if (!attr_done) {                                                                                                 \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(K_), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); \
-      attr_done = true;                                                                                               \
-    }                                                                                                                 \
-  }
   if (pl.kind == 1) {
 #define MTRSSM_1X1_LAUNCH(NT_, SP_)                                                                                  \
   {                                                                                                                   \
-    MTRSSM_ATTR_ONCE((conv1x1_split_kernel<NT_, SP_>))                                                               \
+    allow_lds<conv1x1_split_kernel<NT_, SP_>>(80 * 1024);                                                            \
     set_last_kernel("mtrssm::conv1x1_split_kernel<" #NT_ ", " #SP_ ">");                                               \
     hipLaunchKernelGGL((conv1x1_split_kernel<NT_, SP_>), grid, dim3(kConvThreads), lds, stream, pa, pb);              \
     return launched("conv_gather_gemm(1x1)");                                                                         \
@@ -1540,7 +1529,7 @@ static int launch_split(const SplitPlan& pl, size_t lds, const GatherProblem& pa
   }
 #define MTRSSM_SPLIT_LAUNCH(NT_, SP_, PIT_)                                                                          \
   {                                                                                                                   \
-    MTRSSM_ATTR_ONCE((conv_gather_split_kernel<NT_, SP_, PIT_>))                                                     \
+    allow_lds<conv_gather_split_kernel<NT_, SP_, PIT_>>(80 * 1024);                                                  \
     set_last_kernel("mtrssm::conv_gather_split_kernel<" #NT_ ", " #SP_ ", " #PIT_ ">");                                \
     hipLaunchKernelGGL((conv_gather_split_kernel<NT_, SP_, PIT_>), grid, dim3(kConvThreads), lds, stream, pa, pb);    \
     return launched("conv_gather_gemm(split)");                                                                       \
@@ -1556,7 +1545,6 @@ static int launch_split(const SplitPlan& pl, size_t lds, const GatherProblem& pa
     else { if (pit == 3) MTRSSM_SPLIT_LAUNCH(1, 1, 3) else MTRSSM_SPLIT_LAUNCH(1, 1, 6) }
   }
 #undef MTRSSM_SPLIT_LAUNCH
-#undef MTRSSM_ATTR_ONCE
   set_error("conv_gather_gemm: no split kernel for this plan");
   return MTRSSM_EINVAL;
 }
@@ -1591,14 +1579,9 @@ int pack_conv_weights_launch(const int64_t* table, int count, int blocks_per_wei
   return launched("pack_conv_weights");
 }
 
-// MTRSSM_CONV_S2_BAND=0: the thin / patch-staged kernels for the encoders' first two layers (A/B runs of conv3x3s2_band_kernel)
-static bool s2_band_enabled() {
-  static const bool on = [] { const char* e = getenv("MTRSSM_CONV_S2_BAND"); return !(e && e[0] == '0'); }();
-  return on;
-}
 // conv3x3s2_band_kernel's shapes: Conv2d(k 3, s 2, p 1) forward, <= 8 input channels (coordinate channels included), <= 16 outputs
 static bool s2_band_covers(const MtrssmConvGeom* g, bool has_wq, bool has_epilogue_operand) {
-  return s2_band_enabled() && g->mfma_split == 2 && has_wq && !has_epilogue_operand && g->KH == 3 && g->KW == 3 && g->SS == 2 && g->TS == 1 &&
+  return g->mfma_split == 2 && has_wq && !has_epilogue_operand && g->KH == 3 && g->KW == 3 && g->SS == 2 && g->TS == 1 &&
          g->OFFY == -1 && g->OFFX == -1 && g->OS == 1 && g->QY == 0 && g->QX == 0 && g->Hs == 2 * g->Hq && g->Ws == 2 * g->Wq &&
          g->Ho == g->Hq && g->Wo == g->Wq && (g->Wq == 8 || g->Wq == 16 || g->Wq == 32) && g->Hq % (kBandPx / g->Wq) == 0 &&
          ((g->C == 1 && g->C2 == 2) || (g->C == 8 && g->C2 == 0)) && g->Cout <= 16 && g->CoutPad == 32 && g->Cpad == 16 && g->act != MTRSSM_ACT_TANH &&
@@ -1606,18 +1589,11 @@ static bool s2_band_covers(const MtrssmConvGeom* g, bool has_wq, bool has_epilog
 }
 static int launch_s2_band(const GatherProblem& pa, const GatherProblem* pb, hipStream_t stream) {
   const long ta = (long)pa.g.N * (pa.g.Hq * pa.g.Wq / kBandPx), tb = pb ? (long)pb->g.N * (pb->g.Hq * pb->g.Wq / kBandPx) : 0;
-  const int slots = 2 * cu_count();  // two workgroups per CU
+  const PairSplit wg = split_slots(ta, tb, 2 * cu_count());  // two workgroups per CU
   GatherProblem qa = pa, qb{};
   if (pb) qb = *pb;
-  if (tb == 0) {
-    qa.nx = (int)(ta < slots ? ta : slots);
-    qb.nx = 0;
-  } else {
-    long na = (slots * ta + (ta + tb) / 2) / (ta + tb);
-    na = na < 1 ? 1 : (na > slots - 1 ? slots - 1 : na);
-    qa.nx = (int)(na < ta ? na : ta);
-    qb.nx = (int)(slots - na < tb ? slots - na : tb);
-  }
+  qa.nx = wg.na;
+  qb.nx = wg.nb;
   const int wmax = pb && pb->g.Wq < pa.g.Wq ? pb->g.Wq : pa.g.Wq;  // the narrower plane has the taller band: the larger image
   const size_t lds = (size_t)band_lds_bytes(wmax);
   if (pa.g.C == 1) {
@@ -1631,10 +1607,9 @@ static int launch_s2_band(const GatherProblem& pa, const GatherProblem* pb, hipS
 }
 
 // conv4s2_band_kernel's shapes: Conv2d(k 4, s 2, p 1) gather, 16 -> 32 channels on frames of 1024 positions and 32 -> 64 on frames of
-// 256 (the backward-data of the decoders' second and first ConvTranspose layers); MTRSSM_CONV_S2_BAND=0 switches it off with the
-// other band kernels
+// 256 (the backward-data of the decoders' second and first ConvTranspose layers)
 static int s2k4_band_covers(const MtrssmConvGeom* g, bool has_wq, bool has_add) {   // 0: no; 1: 16 -> 32 on 1024 positions; 2: 32 -> 64 on 256
-  if (!(s2_band_enabled() && g->mfma_split == 2 && has_wq && !has_add && g->KH == 4 && g->KW == 4 && g->SS == 2 && g->TS == 1 &&
+  if (!(g->mfma_split == 2 && has_wq && !has_add && g->KH == 4 && g->KW == 4 && g->SS == 2 && g->TS == 1 &&
         g->OFFY == -1 && g->OFFX == -1 && g->OS == 1 && g->QY == 0 && g->QX == 0 && g->C2 == 0 && g->Hq * 2 == g->Hs && g->Wq * 2 == g->Ws &&
         g->Ho == g->Hq && g->Wo == g->Wq && g->act != MTRSSM_ACT_TANH && g->Cpad == g->C && g->CoutPad == g->Cout &&
         (long)g->N * g->C * g->Hs * g->Ws < (1L << 29)))
@@ -1643,107 +1618,105 @@ static int s2k4_band_covers(const MtrssmConvGeom* g, bool has_wq, bool has_add) 
   if (g->C == 32 && g->Cout == 64 && g->Hs * g->Ws == 256 && (g->Ws == 8 || g->Ws == 16)) return 2;
   return 0;
 }
-static int launch_s2k4_band(const GatherProblem& pa, const GatherProblem* pb, hipStream_t stream) {
-  const long ta = pa.g.N, tb = pb ? pb->g.N : 0;
-  const int slots = cu_count();  // one 512-thread workgroup per CU
+static int launch_s2k4_band(int kind, const GatherProblem& pa, const GatherProblem* pb, hipStream_t stream) {
+  const PairSplit wg = split_slots(pa.g.N, pb ? pb->g.N : 0, cu_count());  // one 512-thread workgroup per CU
   GatherProblem qa = pa, qb{};
   if (pb) qb = *pb;
-  if (tb == 0) {
-    qa.nx = (int)(ta < slots ? ta : slots);
-    qb.nx = 0;
-  } else {
-    long na = (slots * ta + (ta + tb) / 2) / (ta + tb);
-    na = na < 1 ? 1 : (na > slots - 1 ? slots - 1 : na);
-    qa.nx = (int)(na < ta ? na : ta);
-    qb.nx = (int)(slots - na < tb ? slots - na : tb);
-  }
-  const int kind = s2k4_band_covers(&pa.g, true, false);
+  qa.nx = wg.na;
+  qb.nx = wg.nb;
   const int oct = pa.g.C / 8;
   auto lds_of = [&](const MtrssmConvGeom& q) { return 2 * oct * ((q.Hs + 2) * (q.Ws + 2) + 1) * 16; };
   const int la = lds_of(pa.g), lb = pb ? lds_of(pb->g) : 0;
   const size_t lds = (size_t)(la > lb ? la : lb);
-  static bool attr_done_dev[64][2] = {};
-  bool& attr_done = attr_done_dev[device_slot()][kind - 1];
   if (kind == 1) {
-    if (!attr_done) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv4s2_band_kernel<16, 32, 1024>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-      attr_done = true;
-    }
+    allow_lds<conv4s2_band_kernel<16, 32, 1024>>(80 * 1024);
     set_last_kernel("mtrssm::conv4s2_band_kernel<16, 32, 1024>");
     hipLaunchKernelGGL((conv4s2_band_kernel<16, 32, 1024>), dim3((unsigned)(qa.nx + qb.nx)), dim3(512), lds, stream, qa, qb);
   } else {
-    if (!attr_done) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv4s2_band_kernel<32, 64, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-      attr_done = true;
-    }
+    allow_lds<conv4s2_band_kernel<32, 64, 256>>(80 * 1024);
     set_last_kernel("mtrssm::conv4s2_band_kernel<32, 64, 256>");
     hipLaunchKernelGGL((conv4s2_band_kernel<32, 64, 256>), dim3((unsigned)(qa.nx + qb.nx)), dim3(256), lds, stream, qa, qb);
   }
   return launched("conv_gather_gemm(s2 k4 band)");
 }
 
-int conv_gather_gemm_launch(const MtrssmConvGeom* g, const float* src, const float* src2, const float* wp, const unsigned short* wq,
-                            const float* bias, const float* actgrad_in, const float* add_in, float* out, hipStream_t stream) {
-  if (int rc = check_geom(g, "conv_gather_gemm")) return rc;
-  if (!src || !wp || !out || (g->C2 > 0 && !src2)) { set_error("conv_gather_gemm: null pointer"); return MTRSSM_EINVAL; }
-  if ((uintptr_t)wp & 15) { set_error("conv_gather_gemm: packed weights must be 16-byte aligned"); return MTRSSM_EINVAL; }
-  const long ptot = (long)g->N * g->Hq * g->Wq;
-  if (s2_band_covers(g, wq != nullptr, actgrad_in || add_in)) {
-    GatherProblem p{};
-    p.g = *g; p.src = src; p.src2 = src2; p.wq = wq; p.bias = bias; p.out = out;
-    return launch_s2_band(p, nullptr, stream);
+// ---- which gather kernel takes a problem: asked once per problem by the single launch, the pair query and the pair launch
+enum GatherKind { kGatherS2Band, kGatherS2k4Band, kGatherThin16, kGatherThin, kGatherSplit, kGatherPatch, kGatherGeneral };
+struct GatherRoute {
+  GatherKind kind = kGatherGeneral;
+  int k4 = 0;      // kGatherS2k4Band: which of its two shapes
+  SplitPlan plan;  // kGatherSplit
+  // one grid for two problems: the kernels that take a second problem, on the same instantiation
+  bool merges_with(const GatherRoute& o, const MtrssmConvGeom* g, const MtrssmConvGeom* go) const {
+    if (kind != o.kind) return false;
+    if (kind == kGatherS2Band) return g->C == go->C;
+    if (kind == kGatherS2k4Band) return k4 == o.k4;
+    return kind == kGatherSplit && plan.same_kernel(o.plan);
   }
-  if (s2k4_band_covers(g, wq != nullptr, add_in != nullptr)) {
-    GatherProblem p{};
-    p.g = *g; p.src = src; p.wq = wq; p.bias = bias; p.actgrad_in = actgrad_in; p.out = out;
-    return launch_s2k4_band(p, nullptr, stream);
-  }
-  // MTRSSM_THIN16_PAIRS=0: conv_gather_thin_kernel<16> for the one-channel k = 4 stride-2 gather too (A/B runs)
-  static const bool thin16_pairs = [] { const char* e = getenv("MTRSSM_THIN16_PAIRS"); return !(e && e[0] == '0'); }();
-  if (thin16_pairs && g->C == 1 && g->C2 == 0 && g->Cout == 16 && g->KH == 4 && g->KW == 4 && g->SS == 2 && g->TS == 1 && g->OFFY == -1 && g->OFFX == -1 &&
-      g->OS == 1 && g->QY == 0 && g->QX == 0 && g->pre_act == 0 && !add_in && g->Hs == 2 * g->Hq && g->Ws == 2 * g->Wq && g->Ho == g->Hq &&
-      g->Wo == g->Wq && g->Wq % 2 == 0 && g->Ws % 2 == 0 && g->act != MTRSSM_ACT_TANH && !((uintptr_t)src & 7) && !((uintptr_t)out & 7) && !((uintptr_t)actgrad_in & 7) &&
-      kConvThreads == 256) {
-    const long pairs = (long)g->N * g->Hq * (g->Wq / 2);
-    set_last_kernel("mtrssm::conv4s2_c1_thin16_kernel");
-    hipLaunchKernelGGL(conv4s2_c1_thin16_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, stream, *g, src, wp, bias, actgrad_in, out);
-    return launched("conv_gather_gemm(thin16 pairs)");
+};
+// ptr_bits: src | out | actgrad_in addresses or-ed together (0 where they are not known yet: aligned)
+static GatherRoute gather_route(const MtrssmConvGeom* g, bool has_wq, bool has_actgrad, bool has_add, uintptr_t ptr_bits) {
+  GatherRoute r;
+  if (s2_band_covers(g, has_wq, has_actgrad || has_add)) { r.kind = kGatherS2Band; return r; }
+  if ((r.k4 = s2k4_band_covers(g, has_wq, has_add)) != 0) { r.kind = kGatherS2k4Band; return r; }
+  // the one-channel k = 4 stride-2 gather (backward-data of the decoders' last layer): two pixels per thread
+  if (g->C == 1 && g->C2 == 0 && g->Cout == 16 && g->KH == 4 && g->KW == 4 && g->SS == 2 && g->TS == 1 && g->OFFY == -1 && g->OFFX == -1 &&
+      g->OS == 1 && g->QY == 0 && g->QX == 0 && g->pre_act == 0 && !has_add && g->Hs == 2 * g->Hq && g->Ws == 2 * g->Wq && g->Ho == g->Hq &&
+      g->Wo == g->Wq && g->Wq % 2 == 0 && g->Ws % 2 == 0 && g->act != MTRSSM_ACT_TANH && !(ptr_bits & 7) && kConvThreads == 256) {
+    r.kind = kGatherThin16;
+    return r;
   }
   if ((g->Cout <= 8 || g->C + g->C2 <= 2) && g->Cout <= 16 && g->KH * g->KW * (g->C + g->C2) <= kThinMaxK) {  // thin layer: VALU kernel
-    const dim3 grid((unsigned)((ptot + kConvThreads - 1) / kConvThreads));
-    if (g->Cout <= 2)
-      { set_last_kernel("mtrssm::conv_gather_thin_kernel<2>"); hipLaunchKernelGGL(conv_gather_thin_kernel<2>, grid, dim3(kConvThreads), 0, stream, *g, src, src2, wp, bias, actgrad_in, add_in, out); }
-    else if (g->Cout <= 8)
-      { set_last_kernel("mtrssm::conv_gather_thin_kernel<8>"); hipLaunchKernelGGL(conv_gather_thin_kernel<8>, grid, dim3(kConvThreads), 0, stream, *g, src, src2, wp, bias, actgrad_in, add_in, out); }
-    else
-      { set_last_kernel("mtrssm::conv_gather_thin_kernel<16>"); hipLaunchKernelGGL(conv_gather_thin_kernel<16>, grid, dim3(kConvThreads), 0, stream, *g, src, src2, wp, bias, actgrad_in, add_in, out); }
-    return launched("conv_gather_gemm(thin)");
+    r.kind = kGatherThin;
+    return r;
   }
-  const int gx = (int)((ptot + kTP - 1) / kTP);
-  if ((g->TS == 1 || g->TS == -1) && g->KH * g->KW > 0 && plane_fits_26bit(g)) {
-    // Tile choice is occupancy-driven (measured, profiles/round1_notes.md): this kernel's MFMA pipe is fed by MANY
-    // co-resident waves, not by big register tiles.  On the 64-channel 3x3 layers: 128 px x 64 ch workgroup tiles
-    // (32 x 64 per wave) 177 us; 256 x 64 (64 x 64 per wave, NP = 2) 235 us; 128 x 32 (twice the workgroups) 176 us.
+  r.plan = plan_split(g, has_wq);
+  if (r.plan.kind != 0) { r.kind = kGatherSplit; return r; }
+  if ((g->TS == 1 || g->TS == -1) && g->KH * g->KW > 0 && plane_fits_26bit(g) && g->Wq <= kTP && kTP % g->Wq == 0) {
+    const PatchGeom pg(*g, kTP);
     const int tco = g->Cout > 32 ? 64 : 32;
-    const int ny = g->CoutPad / tco;
-    for (int np = 1; np >= 1; --np) {
-      const int tpx = kTP * np;
-      if (g->Wq > tpx || tpx % g->Wq) continue;
-      const PatchGeom pg(*g, tpx);
-      const bool tiles = (g->Hq % pg.rpg == 0) || (pg.rpg % g->Hq == 0);
+    const size_t lds = ((size_t)kKC * pg.ps + 2 * (size_t)tco * (kKC + 1) + pg.ps_raw) * sizeof(float);
+    if (((g->Hq % pg.rpg == 0) || (pg.rpg % g->Hq == 0)) && pg.ipg < 32 && lds <= 64 * 1024) r.kind = kGatherPatch;
+  }
+  return r;
+}
+
+static int launch_gather(const GatherRoute& r, const MtrssmConvGeom* g, const float* src, const float* src2, const float* wp,
+                         const unsigned short* wq, const float* bias, const float* actgrad_in, const float* add_in, float* out, hipStream_t stream) {
+  const GatherProblem p = make_problem(g, r.plan, src, src2, wq, bias, actgrad_in, add_in, out);
+  const long ptot = (long)g->N * g->Hq * g->Wq;
+  const int gx = (int)((ptot + kTP - 1) / kTP);
+  switch (r.kind) {
+    case kGatherS2Band: return launch_s2_band(p, nullptr, stream);
+    case kGatherS2k4Band: return launch_s2k4_band(r.k4, p, nullptr, stream);
+    case kGatherThin16: {
+      const long pairs = (long)g->N * g->Hq * (g->Wq / 2);
+      set_last_kernel("mtrssm::conv4s2_c1_thin16_kernel");
+      hipLaunchKernelGGL(conv4s2_c1_thin16_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, stream, *g, src, wp, bias, actgrad_in, out);
+      return launched("conv_gather_gemm(thin16 pairs)");
+    }
+    case kGatherThin: {
+      const dim3 grid((unsigned)((ptot + kConvThreads - 1) / kConvThreads));
+      if (g->Cout <= 2)
+        { set_last_kernel("mtrssm::conv_gather_thin_kernel<2>"); hipLaunchKernelGGL(conv_gather_thin_kernel<2>, grid, dim3(kConvThreads), 0, stream, *g, src, src2, wp, bias, actgrad_in, add_in, out); }
+      else if (g->Cout <= 8)
+        { set_last_kernel("mtrssm::conv_gather_thin_kernel<8>"); hipLaunchKernelGGL(conv_gather_thin_kernel<8>, grid, dim3(kConvThreads), 0, stream, *g, src, src2, wp, bias, actgrad_in, add_in, out); }
+      else
+        { set_last_kernel("mtrssm::conv_gather_thin_kernel<16>"); hipLaunchKernelGGL(conv_gather_thin_kernel<16>, grid, dim3(kConvThreads), 0, stream, *g, src, src2, wp, bias, actgrad_in, add_in, out); }
+      return launched("conv_gather_gemm(thin)");
+    }
+    case kGatherSplit: {
+      GatherProblem none{};
+      return launch_split(r.plan, r.plan.lds, p, none, stream);
+    }
+    case kGatherPatch: {
+      // Tile choice is occupancy-driven (measured, profiles/round1_notes.md): this kernel's MFMA pipe is fed by MANY
+      // co-resident waves, not by big register tiles.  On the 64-channel 3x3 layers: 128 px x 64 ch workgroup tiles
+      // (32 x 64 per wave) 177 us; 256 x 64 (64 x 64 per wave, NP = 2) 235 us; 128 x 32 (twice the workgroups) 176 us.
+      const PatchGeom pg(*g, kTP);
+      const int tco = g->Cout > 32 ? 64 : 32;
       const size_t lds = ((size_t)kKC * pg.ps + 2 * (size_t)tco * (kKC + 1) + pg.ps_raw) * sizeof(float);
-      const long nx = (ptot + tpx - 1) / tpx;
-      if (!tiles || pg.ipg >= 32) continue;
-      const dim3 grid((unsigned)nx, ny);
-      {
-        const SplitPlan pl = plan_split(g, wq != nullptr);
-        if (pl.kind != 0) {
-          GatherProblem none{};
-          none.nx = 0;
-          return launch_split(pl, pl.lds, make_problem(g, pl, src, src2, wq, bias, actgrad_in, add_in, out), none, stream);
-        }
-      }
-      if (lds > 64 * 1024) continue;
+      const dim3 grid((unsigned)gx, g->CoutPad / tco);
       if (tco == 64) {
         { set_last_kernel("mtrssm::conv_gather_gemm_patch_kernel<2, 1>"); hipLaunchKernelGGL((conv_gather_gemm_patch_kernel<2, 1>), grid, dim3(kConvThreads), lds, stream, *g, src, src2, wp, bias, actgrad_in, add_in, out); }
       } else {
@@ -1751,6 +1724,7 @@ int conv_gather_gemm_launch(const MtrssmConvGeom* g, const float* src, const flo
       }
       return launched("conv_gather_gemm(patch)");
     }
+    case kGatherGeneral: break;
   }
   if (g->Cout > 32) {
     dim3 grid(gx, g->CoutPad / 64);
@@ -1762,63 +1736,50 @@ int conv_gather_gemm_launch(const MtrssmConvGeom* g, const float* src, const flo
   return launched("conv_gather_gemm");
 }
 
-// Two gather problems in one launch when they map to the same split kernel (the audio and the vision branch of one layer);
-// otherwise two launches.
-// 1 when the two problems run the same split kernel and therefore go out as ONE grid (mtrssm_conv_gather_pair_merges)
+int conv_gather_gemm_launch(const MtrssmConvGeom* g, const float* src, const float* src2, const float* wp, const unsigned short* wq,
+                            const float* bias, const float* actgrad_in, const float* add_in, float* out, hipStream_t stream) {
+  if (int rc = check_geom(g, "conv_gather_gemm")) return rc;
+  if (!src || !wp || !out || (g->C2 > 0 && !src2)) { set_error("conv_gather_gemm: null pointer"); return MTRSSM_EINVAL; }
+  if ((uintptr_t)wp & 15) { set_error("conv_gather_gemm: packed weights must be 16-byte aligned"); return MTRSSM_EINVAL; }
+  const GatherRoute r = gather_route(g, wq != nullptr, actgrad_in != nullptr, add_in != nullptr, (uintptr_t)src | (uintptr_t)out | (uintptr_t)actgrad_in);
+  return launch_gather(r, g, src, src2, wp, wq, bias, actgrad_in, add_in, out, stream);
+}
+
+// Two gather problems in one launch when they map to the same kernel of those that take a second problem (the audio and the
+// vision branch of one layer); otherwise two launches.
+// 1 when the two problems go out as ONE grid (mtrssm_conv_gather_pair_merges); asked before the operands exist, so for problems
+// without epilogue operands
 int conv_gather_pair_merges(const MtrssmConvGeom* ga, const MtrssmConvGeom* gb, bool has_wq) {
   if (!ga || !gb || check_geom(ga, "conv_gather_gemm_pair") || check_geom(gb, "conv_gather_gemm_pair")) return 0;
-  // (the band kernel's pair: epilogue operands are checked again at launch, where a pair with one falls back to two launches)
-  if (s2_band_covers(ga, has_wq, false) && s2_band_covers(gb, has_wq, false) && ga->C == gb->C) return 1;
-  if (s2k4_band_covers(ga, has_wq, false) && s2k4_band_covers(ga, has_wq, false) == s2k4_band_covers(gb, has_wq, false)) return 1;
-  const bool thin_a = (ga->Cout <= 8 || ga->C + ga->C2 <= 2) && ga->Cout <= 16;
-  const bool thin_b = (gb->Cout <= 8 || gb->C + gb->C2 <= 2) && gb->Cout <= 16;
-  if (thin_a || thin_b) return 0;
-  const SplitPlan pa = plan_split(ga, has_wq), pb = plan_split(gb, has_wq);
-  return pa.same_kernel(pb) ? 1 : 0;
+  return gather_route(ga, has_wq, false, false, 0).merges_with(gather_route(gb, has_wq, false, false, 0), ga, gb) ? 1 : 0;
 }
 
 int conv_gather_gemm_pair_launch(const MtrssmConvGeom* ga, const float* srca, const float* src2a, const float* wpa, const unsigned short* wqa,
                                  const float* biasa, const float* actgrada, const float* adda, float* outa, const MtrssmConvGeom* gb,
                                  const float* srcb, const float* src2b, const float* wpb, const unsigned short* wqb, const float* biasb,
                                  const float* actgradb, const float* addb, float* outb, hipStream_t stream) {
+  // anything wrong with the arguments: the single launches report it
   if (srca && srcb && outa && outb && ga && gb && !(ga->C2 > 0 && !src2a) && !(gb->C2 > 0 && !src2b) && !check_geom(ga, "conv_gather_gemm_pair") &&
-      !check_geom(gb, "conv_gather_gemm_pair") && s2_band_covers(ga, wqa != nullptr, actgrada || adda) && s2_band_covers(gb, wqb != nullptr, actgradb || addb) && ga->C == gb->C) {
-    GatherProblem p{}, q{};
-    p.g = *ga; p.src = srca; p.src2 = src2a; p.wq = wqa; p.bias = biasa; p.out = outa;
-    q.g = *gb; q.src = srcb; q.src2 = src2b; q.wq = wqb; q.bias = biasb; q.out = outb;
-    return launch_s2_band(p, &q, stream);
-  }
-  if (srca && srcb && outa && outb && ga && gb && !check_geom(ga, "conv_gather_gemm_pair") && !check_geom(gb, "conv_gather_gemm_pair") &&
-      s2k4_band_covers(ga, wqa != nullptr, adda != nullptr) &&
-      s2k4_band_covers(ga, wqa != nullptr, adda != nullptr) == s2k4_band_covers(gb, wqb != nullptr, addb != nullptr)) {
-    GatherProblem p{}, q{};
-    p.g = *ga; p.src = srca; p.wq = wqa; p.bias = biasa; p.actgrad_in = actgrada; p.out = outa;
-    q.g = *gb; q.src = srcb; q.wq = wqb; q.bias = biasb; q.actgrad_in = actgradb; q.out = outb;
-    return launch_s2k4_band(p, &q, stream);
-  }
-  if (srca && srcb && outa && outb && !(ga && ga->C2 > 0 && !src2a) && !(gb && gb->C2 > 0 && !src2b) &&
-      conv_gather_pair_merges(ga, gb, wqa != nullptr && wqb != nullptr) &&
-      !(s2_band_covers(ga, true, false) && s2_band_covers(gb, true, false) && ga->C == gb->C) &&
-      !(s2k4_band_covers(ga, true, false) && s2k4_band_covers(ga, true, false) == s2k4_band_covers(gb, true, false))) {
-    const SplitPlan pa = plan_split(ga, true), pb = plan_split(gb, true);
-    return launch_split(pa, pa.lds > pb.lds ? pa.lds : pb.lds, make_problem(ga, pa, srca, src2a, wqa, biasa, actgrada, adda, outa),
-                        make_problem(gb, pb, srcb, src2b, wqb, biasb, actgradb, addb, outb), stream);
+      !check_geom(gb, "conv_gather_gemm_pair")) {
+    const GatherRoute ra = gather_route(ga, wqa != nullptr, actgrada != nullptr, adda != nullptr, (uintptr_t)srca | (uintptr_t)outa | (uintptr_t)actgrada);
+    const GatherRoute rb = gather_route(gb, wqb != nullptr, actgradb != nullptr, addb != nullptr, (uintptr_t)srcb | (uintptr_t)outb | (uintptr_t)actgradb);
+    if (ra.merges_with(rb, ga, gb)) {
+      const GatherProblem pa = make_problem(ga, ra.plan, srca, src2a, wqa, biasa, actgrada, adda, outa);
+      const GatherProblem pb = make_problem(gb, rb.plan, srcb, src2b, wqb, biasb, actgradb, addb, outb);
+      if (ra.kind == kGatherS2Band) return launch_s2_band(pa, &pb, stream);
+      if (ra.kind == kGatherS2k4Band) return launch_s2k4_band(ra.k4, pa, &pb, stream);
+      return launch_split(ra.plan, ra.plan.lds > rb.plan.lds ? ra.plan.lds : rb.plan.lds, pa, pb, stream);
+    }
   }
   if (int rc = conv_gather_gemm_launch(ga, srca, src2a, wpa, wqa, biasa, actgrada, adda, outa, stream)) return rc;
   return conv_gather_gemm_launch(gb, srcb, src2b, wpb, wqb, biasb, actgradb, addb, outb, stream);
-}
-
-// MTRSSM_RESBLOCK_FUSE=0: the residual blocks' forward as two launches (3x3, then 1x1 + skip) instead of the fused kernel
-static bool resblock_fuse_enabled() {
-  static const bool on = [] { const char* e = getenv("MTRSSM_RESBLOCK_FUSE"); return !(e && e[0] == '0'); }();
-  return on;
 }
 
 // Forward of a whole residual block  y = x + Conv1x1(act(h)),  h = b3 + Conv3x3(act(x))  in one launch
 // (conv3x3_resident_kernel<..., FUSE>): g is the 3x3's geometry exactly as for conv_gather_gemm (pre_act = 1), w1 [C][Cout] and
 // b1 [C] the 1x1 module's own fp32 parameters.  Returns the kernel key (> 0) when the shape has a fused instance.
 int conv_residual_fwd_supported(const MtrssmConvGeom* g) {
-  if (!g || !resblock_fuse_enabled() || g->pre_act == 0 || g->mfma_split != 2 || g->C2 != 0) return 0;
+  if (!g || g->pre_act == 0 || g->mfma_split != 2 || g->C2 != 0) return 0;
   const SplitPlan pl = plan_split(g, true);
   return pl.kind == 3 && (pl.res == 64128 || pl.res == 64064) ? pl.res : 0;
 }
@@ -1826,28 +1787,15 @@ int conv_residual_fwd_supported(const MtrssmConvGeom* g) {
 static int residual_fwd_one_grid(const GatherProblem& pa, const GatherProblem& pb, int key, hipStream_t stream) {
   const int fpt = key == 64064 ? 2 : 1;  // frames per tile (the plan takes whole tiles only)
   const long ta = pa.nx / fpt, tb = pb.nx / fpt;
-  const int ncu = cu_count();
+  const PairSplit wg = split_slots(ta, tb, cu_count());
   GatherProblem qa = pa, qb = pb;
-  if (tb == 0) {
-    qa.nx = (int)(ta < ncu ? ta : ncu);
-    qb.nx = 0;
-  } else {
-    long na = (ncu * ta + (ta + tb) / 2) / (ta + tb);
-    na = na < 1 ? 1 : (na > ncu - 1 ? ncu - 1 : na);
-    qa.nx = (int)(na < ta ? na : ta);
-    qb.nx = (int)(ncu - na < tb ? ncu - na : tb);
-  }
+  qa.nx = wg.na;
+  qb.nx = wg.nb;
   const dim3 rgrid((unsigned)(qa.nx + qb.nx));
 #define MTRSSM_FUSE_LAUNCH(NCT_)                                                                                        \
   {                                                                                                                    \
-    static bool attr_done_dev[64] = {};                                                                                \
-    bool& attr_done = attr_done_dev[device_slot()];                                                                    \
     const size_t rl = res_lds_bytes<64, NCT_, 1>() + res_fuse_bytes<64, NCT_>();                                       \
-    if (!attr_done) {                                                                                                  \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_resident_kernel<64, NCT_, 1, false, true>),      \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)rl);                                  \
-      attr_done = true;                                                                                                \
-    }                                                                                                                  \
+    allow_lds<conv3x3_resident_kernel<64, NCT_, 1, false, true>>((int)rl);                                             \
     set_last_kernel("mtrssm::conv3x3_resident_kernel<64, " #NCT_ ", 1, false, true>");                                  \
     hipLaunchKernelGGL((conv3x3_resident_kernel<64, NCT_, 1, false, true>), rgrid, dim3(kResThreads), rl, stream, qa, qb); \
     return launched("residual_block_fwd");                                                                             \
@@ -1897,46 +1845,68 @@ int conv_residual_fwd_launch(const MtrssmConvGeom* ga, const float* xa, const un
 
 int channel_sum_launch(const float* x, int N, int C, int HW, float* out, hipStream_t stream);
 
-// MTRSSM_NO_DIRECT_WGRAD=1: the patch-staged kernels for every layer (A/B runs of the register-direct 3x3 kernel)
-// MTRSSM_WGRAD_RESIDENT=0: the register-direct 3x3 kernel instead of the staged-input one (A/B runs)
-static bool wgrad_resident_enabled() {
-  static const bool on = [] { const char* e = getenv("MTRSSM_WGRAD_RESIDENT"); return !(e && e[0] == '0'); }();
-  return on;
-}
-// MTRSSM_WGRAD_RESIDENT_C32=0: the 32-channel input layer on the register-direct kernel (A/B runs)
-static bool wgrad_resident_c32() {
-  static const bool on = [] { const char* e = getenv("MTRSSM_WGRAD_RESIDENT_C32"); return !(e && e[0] == '0'); }();
-  return on;
-}
-// MTRSSM_WGRAD_1X1_STAGED=0: the register-direct 1x1 kernel instead of the staged one (A/B runs)
-static bool wgrad_1x1_staged_enabled() {
-  static const bool on = [] { const char* e = getenv("MTRSSM_WGRAD_1X1_STAGED"); return !(e && e[0] == '0'); }();
-  return on;
-}
-// MTRSSM_WGRAD_S2_STAGED=0: the patch-staged kernel for the second encoder layer instead of the staged one (A/B runs)
-static bool wgrad_s2_staged_enabled() {
-  static const bool on = [] { const char* e = getenv("MTRSSM_WGRAD_S2_STAGED"); return !(e && e[0] == '0'); }();
-  return on;
-}
-// MTRSSM_WGRAD_PARTIALS=0: the staged-input kernel adds its tiles to dwp by atomics instead of storing partial sets
+// MTRSSM_WGRAD_PARTIALS=0: the staged-input kernels add their tiles to dwp by atomics instead of storing partial sets
 static bool wgrad_partials_enabled() {
   static const bool on = [] { const char* e = getenv("MTRSSM_WGRAD_PARTIALS"); return !(e && e[0] == '0'); }();
   return on;
 }
-// Partial tile sets of the staged weight-gradient kernels live in the CALLER's workspace (the library allocates nothing).  In
-// query mode the launch function reports the size and returns before any launch.
-#define MTRSSM_WGRAD_PART(bytes_expr)                                                                                              \
-  float* part = nullptr;                                                                                                         \
-  {                                                                                                                              \
-    const size_t need_ = (bytes_expr);                                                                                           \
-    if (query) { *query = wgrad_partials_enabled() ? need_ : 0; return MTRSSM_OK; }                                              \
-    if (wgrad_partials_enabled() && workspace && workspace_bytes >= need_) part = static_cast<float*>(workspace);                \
-  }
+// Partial tile sets of the staged weight-gradient kernels live in the CALLER's workspace (the library allocates nothing): the
+// workspace when it holds `need` bytes, else NULL = the atomics form of the same kernel
+static float* wgrad_partials(void* workspace, size_t workspace_bytes, size_t need) {
+  return wgrad_partials_enabled() && workspace && workspace_bytes >= need ? static_cast<float*>(workspace) : nullptr;
+}
 #define MTRSSM_WGRAD_NO_PART \
   if (query) { *query = 0; return MTRSSM_OK; }
-static bool no_direct_wgrad() {
-  static const bool off = getenv("MTRSSM_NO_DIRECT_WGRAD") != nullptr;
-  return off;
+
+// One launch of a staged weight-gradient kernel (conv_wgrad_resident.h).  They all end their arguments with (part, bias, per) and
+// leave one partial set per workgroup for their reduce variant; what differs comes in here, the leading kernel arguments as `head`.
+struct StagedWgrad {
+  const char* who;      // for the launch error
+  int N, slots;         // frames, and the x blocks they may take
+  int ygroups;          // grid.y: groups of 64 output channels
+  int threads;
+  size_t set_floats;    // one workgroup's partial set
+  int red, rblocks;     // reduce variant and its x blocks (one more with a bias); its grid.y is ygroups
+  int cpad;
+  float* dwp;
+  float* bias;          // the kernel's fused bias sums (NULL: none)
+  void* workspace;
+  size_t workspace_bytes;
+  size_t* query;        // != NULL: store the bytes this launch wants for its partial sets and return WITHOUT launching
+};
+template <auto Kernel, typename... Head>
+static int launch_staged_wgrad(const char* kernel_name, int lds, const StagedWgrad& s, hipStream_t stream, Head... head) {
+  const FramesGrid fg = frames_grid(s.N, s.slots);
+  const size_t need = (size_t)fg.blocks * s.ygroups * s.set_floats * sizeof(float);
+  if (s.query) { *s.query = wgrad_partials_enabled() ? need : 0; return MTRSSM_OK; }
+  float* const part = wgrad_partials(s.workspace, s.workspace_bytes, need);
+  allow_lds<Kernel>(lds);
+  set_last_kernel(kernel_name);
+  hipLaunchKernelGGL(Kernel, dim3((unsigned)fg.blocks, s.ygroups), dim3(s.threads), lds, stream, head..., part, s.bias, fg.per);
+  if (part)
+    if (int rc = reduce_now_or_later(s.red, dim3((unsigned)(s.rblocks + (s.bias ? 1 : 0)), s.ygroups), part, fg.blocks, s.cpad, s.dwp, s.bias, stream)) return rc;
+  return launched(s.who);
+}
+template <int SPLIT, int W>
+constexpr int wgs2c_lds_bytes_w() { return wgs2c_lds_bytes<SPLIT>(); }  // this one's LDS does not depend on the plane width
+// the four instantiations <pieces, X_> of one family (the macros stringise the template arguments for mtrssm_last_kernel)
+#define MTRSSM_STAGED_ONE(K_, LDS_, SP_, X_, ...) \
+  launch_staged_wgrad<K_<SP_, X_>>("mtrssm::" #K_ "<" #SP_ ", " #X_ ">", LDS_<SP_, X_>(), sw, stream, __VA_ARGS__)
+#define MTRSSM_STAGED(K_, LDS_, x_, XA_, XB_, ...)                                                                              \
+  ((x_) == XA_ ? (g->mfma_split == 2 ? MTRSSM_STAGED_ONE(K_, LDS_, 2, XA_, __VA_ARGS__) : MTRSSM_STAGED_ONE(K_, LDS_, 1, XA_, __VA_ARGS__)) \
+               : (g->mfma_split == 2 ? MTRSSM_STAGED_ONE(K_, LDS_, 2, XB_, __VA_ARGS__) : MTRSSM_STAGED_ONE(K_, LDS_, 1, XB_, __VA_ARGS__)))
+// the reduces of a paired launch's two problems (Bwd1x1Problem, WgresProblem)
+template <typename Problem>
+static int reduce_pair(const Problem* pr, int red, int rblocks, int ygroups, int defer, hipStream_t stream) {
+  for (int i = 0; i < 2; ++i) {
+    if (!pr[i].part) continue;
+    const dim3 rgrid((unsigned)(rblocks + (pr[i].dbias ? 1 : 0)), ygroups);  // + the bias block
+    tl_defer_reduce = defer != 0;
+    const int rc = reduce_now_or_later(red, rgrid, pr[i].part, pr[i].xblocks, pr[i].cpad, pr[i].dwp, pr[i].dbias, stream);
+    tl_defer_reduce = false;
+    if (rc) return rc;
+  }
+  return MTRSSM_OK;
 }
 
 // workspace: caller-owned device memory for the partial tile sets of the staged kernels (mtrssm_conv_weight_grad_workspace_bytes);
@@ -1993,10 +1963,8 @@ int conv_weight_grad_deferred_launch(const MtrssmConvGeom* g, const float* a, co
 }
 
 // ---- whole backward of a residual block's 1x1 layer in one pass (conv_wgrad_resident.h: conv1x1_bwd_fused_kernel) ----
-// MTRSSM_BWD1X1_FUSED=0: refuse every shape (A/B runs of the two-launch path through the same Python code)
 int conv_residual_bwd1x1_supported(const MtrssmConvGeom* g) {
-  static const bool on = [] { const char* e = getenv("MTRSSM_BWD1X1_FUSED"); return !(e && e[0] == '0'); }();
-  if (!g || !on || !wgrad_1x1_staged_enabled()) return 0;
+  if (!g) return 0;
   return g->mfma_split == 2 && g->KH == 1 && g->KW == 1 && g->SS == 1 && g->OFFY == 0 && g->OFFX == 0 && g->C2 == 0 && g->Hs == g->Hq &&
          g->Ws == g->Wq && g->Hq * g->Wq == 64 && (g->C == 64 || g->C == 128) && g->Cout == 64 && g->Cpad >= g->C && g->N >= 1 &&
          g->OS == 1 && g->QY == 0 && g->QX == 0 && g->pre_act != 0 &&
@@ -2013,35 +1981,14 @@ int conv_residual_bwd1x1_launch(const MtrssmConvGeom* g, const float* gy, const 
     set_error("residual_bwd1x1: g_y, h and the weight pieces must be 16-byte aligned, the workspace 256-byte aligned");
     return MTRSSM_EINVAL;
   }
-  int wgs = cu_count();  // the grid of conv1x1_wgrad_staged_kernel: mtrssm_conv_weight_grad_workspace_bytes sizes the workspace
-  if (wgs > g->N) wgs = g->N;
-  const int per = (g->N + wgs - 1) / wgs;
-  const dim3 grid((unsigned)((g->N + per - 1) / per));
-  float* part = nullptr;
-  if (wgrad_partials_enabled() && workspace && workspace_bytes >= (size_t)grid.x * kWg1x1SetFloats * sizeof(float)) part = static_cast<float*>(workspace);
-#define MTRSSM_BW1_LAUNCH(C_)                                                                                                   \
-  {                                                                                                                             \
-    static bool attr_done_dev[64] = {}; bool& attr_done = attr_done_dev[device_slot()];                                         \
-    constexpr int lds_b = bwd1x1_lds_bytes<C_>();                                                                               \
-    if (!attr_done) {                                                                                                           \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_bwd_fused_kernel<C_>),                                    \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_b);                                             \
-      attr_done = true;                                                                                                         \
-    }                                                                                                                           \
-    set_last_kernel("mtrssm::conv1x1_bwd_fused_kernel<" #C_ ">");                                                               \
-    hipLaunchKernelGGL((conv1x1_bwd_fused_kernel<C_>), grid, dim3(512), lds_b, stream, *g, gy, h, wq1t, gh, dwp, part, dbias,   \
-                       per);                                                                                                    \
-  }
-  if (g->C == 64) MTRSSM_BW1_LAUNCH(64) else MTRSSM_BW1_LAUNCH(128)
-#undef MTRSSM_BW1_LAUNCH
-  if (part) {
-    const dim3 rgrid((unsigned)(2 * (g->C / 32) * 256 / 32 + (dbias ? 1 : 0)), 1);  // + the bias block
-    tl_defer_reduce = defer != 0;
-    const int rc = reduce_now_or_later(g->C == 64 ? kRed1x1_64 : kRed1x1_128, rgrid, part, (int)grid.x, g->Cpad, dwp, dbias, stream);
-    tl_defer_reduce = false;
-    if (rc) return rc;
-  }
-  return launched("residual_bwd1x1");
+  // the grid of conv1x1_wgrad_staged_kernel: mtrssm_conv_weight_grad_workspace_bytes sizes the workspace
+  const StagedWgrad sw{"residual_bwd1x1", g->N, cu_count(), 1, 512, kWg1x1SetFloats, g->C == 64 ? kRed1x1_64 : kRed1x1_128, 2 * (g->C / 32) * 256 / 32,
+                       g->Cpad, dwp, dbias, workspace, workspace_bytes, nullptr};
+  tl_defer_reduce = defer != 0;
+  const int rc = g->C == 64 ? launch_staged_wgrad<conv1x1_bwd_fused_kernel<64>>("mtrssm::conv1x1_bwd_fused_kernel<64>", bwd1x1_lds_bytes<64>(), sw, stream, *g, gy, h, wq1t, gh, dwp)
+                            : launch_staged_wgrad<conv1x1_bwd_fused_kernel<128>>("mtrssm::conv1x1_bwd_fused_kernel<128>", bwd1x1_lds_bytes<128>(), sw, stream, *g, gy, h, wq1t, gh, dwp);
+  tl_defer_reduce = false;
+  return rc;
 }
 
 // MTRSSM_PAIR_WGRAD=0: both paired queries below refuse every shape (A/B runs of the one-launch-per-modality path through the
@@ -2087,36 +2034,21 @@ int conv_residual_bwd1x1_pair_launch(const MtrssmConvGeom* ga, const float* gya,
       set_error("residual_bwd1x1_pair: g_y, h and the weight pieces must be 16-byte aligned, the workspaces 256-byte aligned");
       return MTRSSM_EINVAL;
     }
-    const int wgs = slots < s.g->N ? slots : s.g->N;
-    const int per = (s.g->N + wgs - 1) / wgs;
-    const int xb = (s.g->N + per - 1) / per;
-    float* part = nullptr;
-    if (wgrad_partials_enabled() && s.workspace && s.workspace_bytes >= (size_t)xb * kWg1x1SetFloats * sizeof(float)) part = static_cast<float*>(s.workspace);
-    pr[i] = Bwd1x1Problem{s.gy, s.h, s.wq1t, s.gh, s.dwp, part, s.dbias, s.g->N, s.g->act, s.g->Cpad, per, xb};
+    const FramesGrid fg = frames_grid(s.g->N, slots);
+    float* const part = wgrad_partials(s.workspace, s.workspace_bytes, (size_t)fg.blocks * kWg1x1SetFloats * sizeof(float));
+    pr[i] = Bwd1x1Problem{s.gy, s.h, s.wq1t, s.gh, s.dwp, part, s.dbias, s.g->N, s.g->act, s.g->Cpad, fg.per, fg.blocks};
   }
   const dim3 grid((unsigned)(pr[0].xblocks + pr[1].xblocks));
 #define MTRSSM_BW1P_LAUNCH(C_)                                                                                                  \
   {                                                                                                                             \
-    static bool attr_done_dev[64] = {}; bool& attr_done = attr_done_dev[device_slot()];                                         \
     constexpr int lds_b = bwd1x1_lds_bytes<C_>();                                                                               \
-    if (!attr_done) {                                                                                                           \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_bwd_fused_pair_kernel<C_>),                               \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_b);                                             \
-      attr_done = true;                                                                                                         \
-    }                                                                                                                           \
+    allow_lds<conv1x1_bwd_fused_pair_kernel<C_>>(lds_b);                                                                        \
     set_last_kernel("mtrssm::conv1x1_bwd_fused_pair_kernel<" #C_ ">");                                                          \
     hipLaunchKernelGGL((conv1x1_bwd_fused_pair_kernel<C_>), grid, dim3(512), lds_b, stream, pr[0], pr[1]);                      \
   }
   if (C_ == 64) MTRSSM_BW1P_LAUNCH(64) else MTRSSM_BW1P_LAUNCH(128)
 #undef MTRSSM_BW1P_LAUNCH
-  for (int i = 0; i < 2; ++i) {
-    if (!pr[i].part) continue;
-    const dim3 rgrid((unsigned)(2 * (C_ / 32) * 256 / 32 + (pr[i].dbias ? 1 : 0)), 1);  // + the bias block
-    tl_defer_reduce = defer != 0;
-    const int rc = reduce_now_or_later(C_ == 64 ? kRed1x1_64 : kRed1x1_128, rgrid, pr[i].part, pr[i].xblocks, pr[i].cpad, pr[i].dwp, pr[i].dbias, stream);
-    tl_defer_reduce = false;
-    if (rc) return rc;
-  }
+  if (int rc = reduce_pair(pr, C_ == 64 ? kRed1x1_64 : kRed1x1_128, 2 * (C_ / 32) * 256 / 32, 1, defer, stream)) return rc;
   return launched("residual_bwd1x1_pair");
 }
 
@@ -2125,8 +2057,8 @@ int conv_residual_bwd1x1_pair_launch(const MtrssmConvGeom* ga, const float* gya,
 static bool wgrad_resident_takes(const MtrssmConvGeom* g, int pre_act_a) {
   return (g->mfma_split == 1 || g->mfma_split == 2) && g->KH == 3 && g->KW == 3 && g->SS == 1 && g->TS == 1 && g->OFFY == -1 && g->OFFX == -1 &&
          g->C2 == 0 && g->Hs == g->Hq && g->Ws == g->Wq && (g->Wq == 8 || g->Wq == 4) && g->Hq * g->Wq == 64 &&
-         (g->C == 64 || (g->C == 32 && wgrad_resident_c32())) && g->Cout % 64 == 0 && g->Cout <= 65535 * 64 && g->Cpad >= g->C && !pre_act_a &&
-         (g->act == MTRSSM_ACT_IDENTITY || g->act == MTRSSM_ACT_ELU || g->act == MTRSSM_ACT_RELU) && wgrad_resident_enabled() && !no_direct_wgrad();
+         (g->C == 64 || g->C == 32) && g->Cout % 64 == 0 && g->Cout <= 65535 * 64 && g->Cpad >= g->C && !pre_act_a &&
+         (g->act == MTRSSM_ACT_IDENTITY || g->act == MTRSSM_ACT_ELU || g->act == MTRSSM_ACT_RELU);
 }
 // one 4-wide and one 8-wide plane, the same layer otherwise (frame counts may differ), two bf16 pieces
 int conv_weight_grad_pair_supported(const MtrssmConvGeom* ga, const MtrssmConvGeom* gb) {
@@ -2157,8 +2089,7 @@ int conv_weight_grad_pair_launch(const MtrssmConvGeom* ga, const float* aa, cons
   const WgradPairSide* const sides[2] = {swap ? &s1 : &s0, swap ? &s0 : &s1};
   const int C_ = s0.g->C, cogroups = s0.g->Cout / 64;
   // one wave per SIMD over the chip, as the single launch, half of the x blocks for each problem
-  int slots = (C_ == 64 ? cu_count() : 2 * cu_count()) / (2 * cogroups);
-  if (slots < 1) slots = 1;
+  const int slots = (C_ == 64 ? cu_count() : 2 * cu_count()) / (2 * cogroups);
   WgresProblem pr[2];
   for (int i = 0; i < 2; ++i) {
     const WgradPairSide& s = *sides[i];
@@ -2167,38 +2098,22 @@ int conv_weight_grad_pair_launch(const MtrssmConvGeom* ga, const float* aa, cons
       set_error("conv_weight_grad_pair: a, src and dwp must be 16-byte aligned, the workspaces 256-byte aligned");
       return MTRSSM_EINVAL;
     }
-    const int wgs = slots < s.g->N ? slots : s.g->N;
-    const int per = (s.g->N + wgs - 1) / wgs;
-    const int xb = (s.g->N + per - 1) / per;
-    float* part = nullptr;
-    if (wgrad_partials_enabled() && s.workspace && s.workspace_bytes >= (size_t)xb * cogroups * wgres_set_floats(C_) * sizeof(float))
-      part = static_cast<float*>(s.workspace);
-    pr[i] = WgresProblem{s.a, s.src, s.dwp, part, s.dbias, s.g->N, s.g->Cout, s.g->Cpad, s.g->act, s.g->pre_act, per, xb};
+    const FramesGrid fg = frames_grid(s.g->N, slots);
+    float* const part = wgrad_partials(s.workspace, s.workspace_bytes, (size_t)fg.blocks * cogroups * wgres_set_floats(C_) * sizeof(float));
+    pr[i] = WgresProblem{s.a, s.src, s.dwp, part, s.dbias, s.g->N, s.g->Cout, s.g->Cpad, s.g->act, s.g->pre_act, fg.per, fg.blocks};
   }
   const dim3 grid((unsigned)(pr[0].xblocks + pr[1].xblocks), cogroups);
 #define MTRSSM_WGRESP_LAUNCH(C_)                                                                                                \
   {                                                                                                                             \
-    static bool attr_done_dev[64] = {}; bool& attr_done = attr_done_dev[device_slot()];                                         \
     constexpr int lds_a = wgres_lds_bytes<2, C_, 4>(), lds_8 = wgres_lds_bytes<2, C_, 8>(), lds_b = lds_a > lds_8 ? lds_a : lds_8; \
-    if (!attr_done) {                                                                                                           \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wgrad_pair_resident_kernel<2, C_, 4, 8>),                 \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_b);                                             \
-      attr_done = true;                                                                                                         \
-    }                                                                                                                           \
+    allow_lds<conv3x3_wgrad_pair_resident_kernel<2, C_, 4, 8>>(lds_b);                                                          \
     set_last_kernel("mtrssm::conv3x3_wgrad_pair_resident_kernel<2, " #C_ ", 4, 8>");                                            \
     hipLaunchKernelGGL((conv3x3_wgrad_pair_resident_kernel<2, C_, 4, 8>), grid, dim3(64 * 2 * (C_ / 32)), lds_b, stream, pr[0],  \
                        pr[1]);                                                                                                  \
   }
   if (C_ == 64) MTRSSM_WGRESP_LAUNCH(64) else MTRSSM_WGRESP_LAUNCH(32)
 #undef MTRSSM_WGRESP_LAUNCH
-  for (int i = 0; i < 2; ++i) {
-    if (!pr[i].part) continue;
-    const dim3 rgrid((unsigned)(wgres_tile_floats(C_) / 4 / 32 + (pr[i].dbias ? 1 : 0)), cogroups);  // + the bias block
-    tl_defer_reduce = defer != 0;
-    const int rc = reduce_now_or_later(C_ == 64 ? kRedRes64 : kRedRes32, rgrid, pr[i].part, pr[i].xblocks, pr[i].cpad, pr[i].dwp, pr[i].dbias, stream);
-    tl_defer_reduce = false;
-    if (rc) return rc;
-  }
+  if (int rc = reduce_pair(pr, C_ == 64 ? kRedRes64 : kRedRes32, wgres_tile_floats(C_) / 4 / 32, cogroups, defer, stream)) return rc;
   return launched("conv_weight_grad_pair");
 }
 
@@ -2212,40 +2127,19 @@ int conv_weight_grad_launch_ex(const MtrssmConvGeom* g, const float* a, const fl
   const long ptot = (long)g->N * g->Hq * g->Wq;
   const int taps = g->KH * g->KW;
   const int ctot = g->C + g->C2;
+  // a staged branch's launch values: the call's own, and what the branch adds
+  auto staged = [&](const char* who, int slots, int ygroups, int threads, size_t set_floats, int red, int rblocks, float* bias) {
+    return StagedWgrad{who, g->N, slots, ygroups, threads, set_floats, red, rblocks, g->Cpad, dwp, bias, workspace, workspace_bytes, query};
+  };
   if ((g->mfma_split == 1 || g->mfma_split == 2) && taps == 1 && g->SS == 1 && g->OFFY == 0 && g->OFFX == 0 && g->C2 == 0 && g->Hs == g->Hq &&
       g->Ws == g->Wq && g->Hq * g->Wq == 64 && (g->C == 64 || g->C == 128) && g->Cout % 64 == 0 && g->Cout <= 65535 * 64 && g->Cpad >= g->C &&
       !pre_act_a && (g->act == MTRSSM_ACT_IDENTITY || g->act == MTRSSM_ACT_ELU || g->act == MTRSSM_ACT_RELU) && !((uintptr_t)a & 15) &&
-      !((uintptr_t)src & 15) && wgrad_1x1_staged_enabled()) {
+      !((uintptr_t)src & 15)) {
     // 1x1 layers of the residual stacks on 64-pixel planes: operands staged once per frame (conv_wgrad_resident.h)
     const int cogroups = g->Cout / 64;
-    int wgs = cu_count() / cogroups;
-    if (wgs < 1) wgs = 1;
-    if (wgs > g->N) wgs = g->N;
-    const int per = (g->N + wgs - 1) / wgs;
-    const dim3 grid((unsigned)((g->N + per - 1) / per), cogroups);
-    MTRSSM_WGRAD_PART((size_t)grid.x * cogroups * kWg1x1SetFloats * sizeof(float))
-#define MTRSSM_WG1_LAUNCH(SP_, C_)                                                                                              \
-  {                                                                                                                             \
-    static bool attr_done_dev[64] = {}; bool& attr_done = attr_done_dev[device_slot()]; /* once per instantiation: never while another stream may be running the kernel */       \
-    constexpr int lds_b = wg1x1_lds_bytes<SP_, C_>();                                                                           \
-    if (!attr_done) {                                                                                                           \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_wgrad_staged_kernel<SP_, C_>),                            \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_b);                                             \
-      attr_done = true;                                                                                                         \
-    }                                                                                                                           \
-    set_last_kernel("mtrssm::conv1x1_wgrad_staged_kernel<" #SP_ ", " #C_ ">");                                                  \
-    hipLaunchKernelGGL((conv1x1_wgrad_staged_kernel<SP_, C_>), grid, dim3(512), lds_b, stream, *g, a, src, dwp, part, dbias,    \
-                       per);                                                                                                    \
-  }
-    const int sp = g->mfma_split;
-    if (g->C == 64) { if (sp == 2) MTRSSM_WG1_LAUNCH(2, 64) else MTRSSM_WG1_LAUNCH(1, 64) }
-    else { if (sp == 2) MTRSSM_WG1_LAUNCH(2, 128) else MTRSSM_WG1_LAUNCH(1, 128) }
-#undef MTRSSM_WG1_LAUNCH
-    if (part) {
-      const dim3 rgrid((unsigned)(2 * (g->C / 32) * 256 / 32 + (dbias ? 1 : 0)), cogroups);  // + the bias block
-      if (int rc = reduce_now_or_later(g->C == 64 ? kRed1x1_64 : kRed1x1_128, rgrid, part, (int)grid.x, g->Cpad, dwp, dbias, stream)) return rc;
-    }
-    return launched("conv_weight_grad(1x1 staged)");
+    const StagedWgrad sw = staged("conv_weight_grad(1x1 staged)", cu_count() / cogroups, cogroups, 512, kWg1x1SetFloats,
+                                  g->C == 64 ? kRed1x1_64 : kRed1x1_128, 2 * (g->C / 32) * 256 / 32, dbias);
+    return MTRSSM_STAGED(conv1x1_wgrad_staged_kernel, wg1x1_lds_bytes, g->C, 64, 128, *g, a, src, dwp);
   }
   if (g->mfma_split >= 1 && taps == 1 && g->SS == 1 && g->OFFY == 0 && g->OFFX == 0 && g->C2 == 0 && g->Hs == g->Hq && g->Ws == g->Wq &&
       (g->Hq * g->Wq) % 16 == 0 && g->Cout <= 128 && g->C <= 128 && g->C >= 8 && !((uintptr_t)a & 15) && !((uintptr_t)src & 15) &&
@@ -2269,44 +2163,23 @@ int conv_weight_grad_launch_ex(const MtrssmConvGeom* g, const float* a, const fl
   if (wgrad_resident_takes(g, pre_act_a) && !((uintptr_t)a & 15) && !((uintptr_t)src & 15) && !((uintptr_t)dwp & 15)) {
     // 3x3 layers of the residual stacks on 64-pixel planes: both operands staged once per frame (conv_wgrad_resident.h)
     const int cogroups = g->Cout / 64;
-    int wgs = (g->C == 64 ? cu_count() : 2 * cu_count()) / cogroups;  // one wave per SIMD over the chip
-    if (wgs < 1) wgs = 1;
-    if (wgs > g->N) wgs = g->N;
-    const int per = (g->N + wgs - 1) / wgs;
-    const dim3 grid((unsigned)((g->N + per - 1) / per), cogroups);
-    const size_t set_floats = (size_t)wgres_set_floats(g->C);
-    MTRSSM_WGRAD_PART((size_t)grid.x * cogroups * set_floats * sizeof(float))
-#define MTRSSM_WGRES_LAUNCH(SP_, C_, W_)                                                                                         \
-  {                                                                                                                             \
-    static bool attr_done_dev[64] = {}; bool& attr_done = attr_done_dev[device_slot()]; /* once per instantiation: never while another stream may be running the kernel */       \
-    constexpr int lds_b = wgres_lds_bytes<SP_, C_, W_>();                                                                       \
-    if (!attr_done) {                                                                                                           \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wgrad_resident_kernel<SP_, C_, W_>),                       \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_b);                                             \
-      attr_done = true;                                                                                                         \
-    }                                                                                                                           \
-    set_last_kernel("mtrssm::conv3x3_wgrad_resident_kernel<" #SP_ ", " #C_ ", " #W_ ">");                                        \
-    hipLaunchKernelGGL((conv3x3_wgrad_resident_kernel<SP_, C_, W_>), grid, dim3(64 * 2 * (C_ / 32)), lds_b, stream, *g, a, src,  \
-                       dwp, part, dbias, per);                                                                                  \
-  }
+    const StagedWgrad sw = staged("conv_weight_grad(3x3 resident)", (g->C == 64 ? cu_count() : 2 * cu_count()) / cogroups /* one wave per SIMD over the chip */,
+                                  cogroups, 64 * 2 * (g->C / 32), wgres_set_floats(g->C), g->C == 64 ? kRedRes64 : kRedRes32, wgres_tile_floats(g->C) / 4 / 32, dbias);
+#define MTRSSM_WGRES_LAUNCH(SP_, C_, W_)                                                                                        \
+  launch_staged_wgrad<conv3x3_wgrad_resident_kernel<SP_, C_, W_>>("mtrssm::conv3x3_wgrad_resident_kernel<" #SP_ ", " #C_ ", " #W_ ">", \
+                                                                  wgres_lds_bytes<SP_, C_, W_>(), sw, stream, *g, a, src, dwp)
     const int sp = g->mfma_split;
     if (g->C == 64) {
-      if (g->Wq == 8) { if (sp == 2) MTRSSM_WGRES_LAUNCH(2, 64, 8) else MTRSSM_WGRES_LAUNCH(1, 64, 8) }
-      else { if (sp == 2) MTRSSM_WGRES_LAUNCH(2, 64, 4) else MTRSSM_WGRES_LAUNCH(1, 64, 4) }
-    } else {
-      if (g->Wq == 8) { if (sp == 2) MTRSSM_WGRES_LAUNCH(2, 32, 8) else MTRSSM_WGRES_LAUNCH(1, 32, 8) }
-      else { if (sp == 2) MTRSSM_WGRES_LAUNCH(2, 32, 4) else MTRSSM_WGRES_LAUNCH(1, 32, 4) }
+      if (g->Wq == 8) return sp == 2 ? MTRSSM_WGRES_LAUNCH(2, 64, 8) : MTRSSM_WGRES_LAUNCH(1, 64, 8);
+      return sp == 2 ? MTRSSM_WGRES_LAUNCH(2, 64, 4) : MTRSSM_WGRES_LAUNCH(1, 64, 4);
     }
+    if (g->Wq == 8) return sp == 2 ? MTRSSM_WGRES_LAUNCH(2, 32, 8) : MTRSSM_WGRES_LAUNCH(1, 32, 8);
+    return sp == 2 ? MTRSSM_WGRES_LAUNCH(2, 32, 4) : MTRSSM_WGRES_LAUNCH(1, 32, 4);
 #undef MTRSSM_WGRES_LAUNCH
-    if (part) {
-      const dim3 rgrid((unsigned)(wgres_tile_floats(g->C) / 4 / 32 + (dbias ? 1 : 0)), cogroups);  // + the bias block
-      if (int rc = reduce_now_or_later(g->C == 64 ? kRedRes64 : kRedRes32, rgrid, part, (int)grid.x, g->Cpad, dwp, dbias, stream)) return rc;
-    }
-    return launched("conv_weight_grad(3x3 resident)");
   }
   if (g->mfma_split >= 1 && g->KH == 3 && g->KW == 3 && g->SS == 1 && g->TS == 1 && g->OFFY == -1 && g->OFFX == -1 && g->C2 == 0 &&
       g->Hs == g->Hq && g->Ws == g->Wq && (g->Wq == 8 || g->Wq == 4) && (g->Hq * g->Wq) % 16 == 0 && g->C <= 64 && g->C >= 8 &&
-      g->Cout <= 65535 * 64 && !((uintptr_t)a & 15) && !((uintptr_t)src & 15) && ptot < (1L << 31) && !no_direct_wgrad()) {
+      g->Cout <= 65535 * 64 && !((uintptr_t)a & 15) && !((uintptr_t)src & 15) && ptot < (1L << 31)) {
     // 3x3 layers of the residual stacks: register-direct (conv_split.h: conv3x3_weight_grad_split_kernel)
     MTRSSM_WGRAD_NO_PART
     const int cogroups = (g->Cout + 63) / 64;
@@ -2333,69 +2206,23 @@ int conv_weight_grad_launch_ex(const MtrssmConvGeom* g, const float* a, const fl
   if ((g->mfma_split == 1 || g->mfma_split == 2) && g->KH == 3 && g->KW == 3 && g->SS == 2 && g->TS == 1 && g->OFFY == -1 && g->OFFX == -1 &&
       g->C == 1 && g->C2 == 2 && g->Cout == 8 && g->Hq * g->Wq == 1024 && (g->Wq == 32 || g->Wq == 16) && g->Hs == 2 * g->Hq && g->Ws == 2 * g->Wq &&
       g->Cpad >= 3 && !pre_act_a && (g->act == MTRSSM_ACT_IDENTITY || g->act == MTRSSM_ACT_ELU || g->act == MTRSSM_ACT_RELU || !g->pre_act) &&
-      !((uintptr_t)a & 15) && !((uintptr_t)src & 15) && !((uintptr_t)src2 & 15) && wgrad_s2_staged_enabled()) {
+      !((uintptr_t)a & 15) && !((uintptr_t)src & 15) && !((uintptr_t)src2 & 15)) {
     // first encoder layer (3x3 / stride 2, frame channel + 2 coordinate channels -> 8, 1024-pixel output planes): staged
-    int wgs = cu_count();
-    if (wgs > g->N) wgs = g->N;
-    const int per = (g->N + wgs - 1) / wgs;
-    const dim3 grid((unsigned)((g->N + per - 1) / per));
-    MTRSSM_WGRAD_PART((size_t)grid.x * kWgThinSetFloats * sizeof(float))
-#define MTRSSM_WGTHIN_LAUNCH(SP_, W_)                                                                                            \
-  {                                                                                                                             \
-    static bool attr_done_dev[64] = {}; bool& attr_done = attr_done_dev[device_slot()]; /* once per instantiation: never while another stream may be running the kernel */       \
-    constexpr int lds_b = wgthin_lds_bytes<SP_, W_>();                                                                          \
-    if (!attr_done) {                                                                                                           \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3s2_thin_wgrad_staged_kernel<SP_, W_>),                      \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_b);                                             \
-      attr_done = true;                                                                                                         \
-    }                                                                                                                           \
-    set_last_kernel("mtrssm::conv3x3s2_thin_wgrad_staged_kernel<" #SP_ ", " #W_ ">");                                            \
-    hipLaunchKernelGGL((conv3x3s2_thin_wgrad_staged_kernel<SP_, W_>), grid, dim3(512), lds_b, stream, *g, a, src, src2, dwp,     \
-                       part, dbias, per);                                                                                       \
-  }
-    const int sp = g->mfma_split;
-    if (g->Wq == 32) { if (sp == 2) MTRSSM_WGTHIN_LAUNCH(2, 32) else MTRSSM_WGTHIN_LAUNCH(1, 32) }
-    else { if (sp == 2) MTRSSM_WGTHIN_LAUNCH(2, 16) else MTRSSM_WGTHIN_LAUNCH(1, 16) }
-#undef MTRSSM_WGTHIN_LAUNCH
-    if (part)
-      if (int rc = reduce_now_or_later(kRedThin, dim3(dbias ? 9 : 8), part, (int)grid.x, g->Cpad, dwp, dbias, stream)) return rc;
-    return launched("conv_weight_grad(3x3 s2 thin staged)");
+    const StagedWgrad sw = staged("conv_weight_grad(3x3 s2 thin staged)", cu_count(), 1, 512, kWgThinSetFloats, kRedThin, 8, dbias);
+    return MTRSSM_STAGED(conv3x3s2_thin_wgrad_staged_kernel, wgthin_lds_bytes, g->Wq, 32, 16, *g, a, src, src2, dwp);
   }
   if ((g->mfma_split == 1 || g->mfma_split == 2) && g->KH == 4 && g->KW == 4 && g->SS == 2 && g->TS == 1 && g->OFFY == -1 && g->OFFX == -1 &&
       g->C == 1 && g->C2 == 0 && g->Cout == 16 && g->Hq * g->Wq == 1024 && (g->Wq == 32 || g->Wq == 16) && g->Hs == 2 * g->Hq && g->Ws == 2 * g->Wq &&
       g->Cpad >= 1 && !g->pre_act && !dbias && (g->act == MTRSSM_ACT_IDENTITY || g->act == MTRSSM_ACT_ELU || g->act == MTRSSM_ACT_RELU || !pre_act_a) &&
-      !((uintptr_t)a & 15) && !((uintptr_t)src & 15) && wgrad_s2_staged_enabled()) {
+      !((uintptr_t)a & 15) && !((uintptr_t)src & 15)) {
     // the decoders' last ConvTranspose2d (k = 4 / stride 2, 16 -> 1, 1024-pixel input planes): operands staged once per frame
-    int wgs = cu_count();
-    if (wgs > g->N) wgs = g->N;
-    const int per = (g->N + wgs - 1) / wgs;
-    const dim3 grid((unsigned)((g->N + per - 1) / per));
     if (sb) sb->fused = true;
     float* const dsrcbias = sb ? sb->target : nullptr;
-    MTRSSM_WGRAD_PART((size_t)grid.x * kWgThinTSetFloats * sizeof(float))
-#define MTRSSM_WGTHINT_LAUNCH(SP_, W_)                                                                                           \
-  {                                                                                                                             \
-    static bool attr_done_dev[64] = {}; bool& attr_done = attr_done_dev[device_slot()]; /* once per instantiation: never while another stream may be running the kernel */       \
-    constexpr int lds_b = wgthint_lds_bytes<SP_, W_>();                                                                         \
-    if (!attr_done) {                                                                                                           \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(convt4s2_thin_wgrad_staged_kernel<SP_, W_>),                       \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_b);                                             \
-      attr_done = true;                                                                                                         \
-    }                                                                                                                           \
-    set_last_kernel("mtrssm::convt4s2_thin_wgrad_staged_kernel<" #SP_ ", " #W_ ">");                                             \
-    hipLaunchKernelGGL((convt4s2_thin_wgrad_staged_kernel<SP_, W_>), grid, dim3(512), lds_b, stream, *g, a, src, pre_act_a, dwp, \
-                       part, dsrcbias, per);                                                                                    \
-  }
-    const int sp = g->mfma_split;
-    if (g->Wq == 32) { if (sp == 2) MTRSSM_WGTHINT_LAUNCH(2, 32) else MTRSSM_WGTHINT_LAUNCH(1, 32) }
-    else { if (sp == 2) MTRSSM_WGTHINT_LAUNCH(2, 16) else MTRSSM_WGTHINT_LAUNCH(1, 16) }
-#undef MTRSSM_WGTHINT_LAUNCH
-    if (part)
-      if (int rc = reduce_now_or_later(kRedThinT, dim3(dsrcbias ? 17 : 16), part, (int)grid.x, g->Cpad, dwp, dsrcbias, stream)) return rc;
-    return launched("conv_weight_grad(k4 s2 thin staged)");
+    const StagedWgrad sw = staged("conv_weight_grad(k4 s2 thin staged)", cu_count(), 1, 512, kWgThinTSetFloats, kRedThinT, 16, dsrcbias);
+    return MTRSSM_STAGED(convt4s2_thin_wgrad_staged_kernel, wgthint_lds_bytes, g->Wq, 32, 16, *g, a, src, pre_act_a, dwp);
   }
   if (g->mfma_split >= 1 && g->Cout <= 32 && taps * ctot <= 32 && g->Wq >= 8 && (g->Wq & (g->Wq - 1)) == 0 && (g->Hq * g->Wq) % 16 == 0 &&
-      !((uintptr_t)a & 15) && ptot < (1L << 31) && (long)g->N * g->C * g->Hs * g->Ws < (1L << 40) && !no_direct_wgrad()) {
+      !((uintptr_t)a & 15) && ptot < (1L << 31) && (long)g->N * g->C * g->Hs * g->Ws < (1L << 40)) {
     // thin strided layers: one MFMA tile, A straight from HBM, B gathered per lane (conv_split.h: conv_weight_grad_thin_split_kernel)
     MTRSSM_WGRAD_NO_PART
     int log2_wq = 0;
@@ -2416,123 +2243,38 @@ int conv_weight_grad_launch_ex(const MtrssmConvGeom* g, const float* a, const fl
   if ((g->mfma_split == 1 || g->mfma_split == 2) && g->KH == 3 && g->KW == 3 && g->SS == 2 && g->TS == 1 && g->OFFY == -1 && g->OFFX == -1 &&
       g->C2 == 0 && g->C == 8 && g->Cout == 16 && g->Hq * g->Wq == 256 && (g->Wq == 16 || g->Wq == 8) && g->Hs == 2 * g->Hq && g->Ws == 2 * g->Wq &&
       g->Cpad >= 8 && !pre_act_a && (g->act == MTRSSM_ACT_IDENTITY || g->act == MTRSSM_ACT_ELU || g->act == MTRSSM_ACT_RELU) &&
-      !((uintptr_t)a & 15) && !((uintptr_t)src & 15) && wgrad_s2_staged_enabled()) {
+      !((uintptr_t)a & 15) && !((uintptr_t)src & 15)) {
     // second encoder layer (3x3 / stride 2, 8 -> 16, 256-pixel output planes): operands staged once per frame (conv_wgrad_resident.h)
-    int wgs = cu_count();
-    if (wgs > g->N) wgs = g->N;
-    const int per = (g->N + wgs - 1) / wgs;
-    const dim3 grid((unsigned)((g->N + per - 1) / per));
-    MTRSSM_WGRAD_PART((size_t)grid.x * kWgS2SetFloats * sizeof(float))
-#define MTRSSM_WGS2_LAUNCH(SP_, W_)                                                                                              \
-  {                                                                                                                             \
-    static bool attr_done_dev[64] = {}; bool& attr_done = attr_done_dev[device_slot()]; /* once per instantiation: never while another stream may be running the kernel */       \
-    constexpr int lds_b = wgs2_lds_bytes<SP_, W_>();                                                                            \
-    if (!attr_done) {                                                                                                           \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3s2_wgrad_staged_kernel<SP_, W_>),                           \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_b);                                             \
-      attr_done = true;                                                                                                         \
-    }                                                                                                                           \
-    set_last_kernel("mtrssm::conv3x3s2_wgrad_staged_kernel<" #SP_ ", " #W_ ">");                                                 \
-    hipLaunchKernelGGL((conv3x3s2_wgrad_staged_kernel<SP_, W_>), grid, dim3(512), lds_b, stream, *g, a, src, dwp, part, dbias,   \
-                       per);                                                                                                    \
-  }
-    const int sp = g->mfma_split;
-    if (g->Wq == 16) { if (sp == 2) MTRSSM_WGS2_LAUNCH(2, 16) else MTRSSM_WGS2_LAUNCH(1, 16) }
-    else { if (sp == 2) MTRSSM_WGS2_LAUNCH(2, 8) else MTRSSM_WGS2_LAUNCH(1, 8) }
-#undef MTRSSM_WGS2_LAUNCH
-    if (part)
-      if (int rc = reduce_now_or_later(kRedS2, dim3(dbias ? 49 : 48), part, (int)grid.x, g->Cpad, dwp, dbias, stream)) return rc;
-    return launched("conv_weight_grad(3x3 s2 staged)");
+    const StagedWgrad sw = staged("conv_weight_grad(3x3 s2 staged)", cu_count(), 1, 512, kWgS2SetFloats, kRedS2, 48, dbias);
+    return MTRSSM_STAGED(conv3x3s2_wgrad_staged_kernel, wgs2_lds_bytes, g->Wq, 16, 8, *g, a, src, dwp);
   }
   if ((g->mfma_split == 1 || g->mfma_split == 2) && g->KH == 4 && g->KW == 4 && g->SS == 2 && g->TS == 1 && g->OFFY == -1 && g->OFFX == -1 &&
       g->C2 == 0 && g->C == 16 && g->Cout == 32 && g->Hq * g->Wq == 256 && (g->Wq == 16 || g->Wq == 8) && g->Hs == 2 * g->Hq && g->Ws == 2 * g->Wq &&
       g->Cpad >= 16 && !g->pre_act && !dbias && (g->act == MTRSSM_ACT_IDENTITY || g->act == MTRSSM_ACT_ELU || g->act == MTRSSM_ACT_RELU || !pre_act_a) &&
-      !((uintptr_t)a & 15) && !((uintptr_t)src & 15) && wgrad_s2_staged_enabled()) {
+      !((uintptr_t)a & 15) && !((uintptr_t)src & 15)) {
     // the decoders' second ConvTranspose2d (k = 4 / stride 2, 32 -> 16, 256-pixel input planes): operands staged once per frame
-    int wgs = cu_count();
-    if (wgs > g->N) wgs = g->N;
-    const int per = (g->N + wgs - 1) / wgs;
-    const dim3 grid((unsigned)((g->N + per - 1) / per));
     if (sb) sb->fused = true;
     float* const dsrcbias = sb ? sb->target : nullptr;
-    MTRSSM_WGRAD_PART((size_t)grid.x * kWgT4SetFloats * sizeof(float))
-#define MTRSSM_WGT4_LAUNCH(SP_, W_)                                                                                              \
-  {                                                                                                                             \
-    static bool attr_done_dev[64] = {}; bool& attr_done = attr_done_dev[device_slot()]; /* once per instantiation: never while another stream may be running the kernel */       \
-    constexpr int lds_b = wgt4_lds_bytes<SP_, W_>();                                                                            \
-    if (!attr_done) {                                                                                                           \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(convt4s2_wgrad_staged_kernel<SP_, W_>),                            \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_b);                                             \
-      attr_done = true;                                                                                                         \
-    }                                                                                                                           \
-    set_last_kernel("mtrssm::convt4s2_wgrad_staged_kernel<" #SP_ ", " #W_ ">");                                                  \
-    hipLaunchKernelGGL((convt4s2_wgrad_staged_kernel<SP_, W_>), grid, dim3(512), lds_b, stream, *g, a, src, pre_act_a, dwp,      \
-                       part, dsrcbias, per);                                                                                    \
-  }
-    const int sp = g->mfma_split;
-    if (g->Wq == 16) { if (sp == 2) MTRSSM_WGT4_LAUNCH(2, 16) else MTRSSM_WGT4_LAUNCH(1, 16) }
-    else { if (sp == 2) MTRSSM_WGT4_LAUNCH(2, 8) else MTRSSM_WGT4_LAUNCH(1, 8) }
-#undef MTRSSM_WGT4_LAUNCH
-    if (part)
-      if (int rc = reduce_now_or_later(kRedT4, dim3(kWgT4TileFloats / 4 / 8 + (dsrcbias ? 1 : 0)), part, (int)grid.x, g->Cpad, dwp, dsrcbias, stream)) return rc;
-    return launched("conv_weight_grad(k4 s2 staged)");
+    const StagedWgrad sw = staged("conv_weight_grad(k4 s2 staged)", cu_count(), 1, 512, kWgT4SetFloats, kRedT4, kWgT4TileFloats / 4 / 8, dsrcbias);
+    return MTRSSM_STAGED(convt4s2_wgrad_staged_kernel, wgt4_lds_bytes, g->Wq, 16, 8, *g, a, src, pre_act_a, dwp);
   }
   if ((g->mfma_split == 1 || g->mfma_split == 2) && g->KH == 4 && g->KW == 4 && g->SS == 2 && g->TS == 1 && g->OFFY == -1 && g->OFFX == -1 &&
       g->C2 == 0 && g->C == 32 && g->Cout == 64 && g->Hq * g->Wq == 64 && (g->Wq == 8 || g->Wq == 4) && g->Hs == 2 * g->Hq && g->Ws == 2 * g->Wq &&
       g->Cpad >= 32 && !g->pre_act && !dbias && (g->act == MTRSSM_ACT_IDENTITY || g->act == MTRSSM_ACT_ELU || g->act == MTRSSM_ACT_RELU || !pre_act_a) &&
-      !((uintptr_t)a & 15) && !((uintptr_t)src & 15) && wgrad_s2_staged_enabled()) {
+      !((uintptr_t)a & 15) && !((uintptr_t)src & 15)) {
     // the decoders' first ConvTranspose2d (k = 4 / stride 2, 64 -> 32, 64-pixel input planes): operands staged once per frame
-    int wgs = cu_count();
-    if (wgs > g->N) wgs = g->N;
-    const int per = (g->N + wgs - 1) / wgs;
-    const dim3 grid((unsigned)((g->N + per - 1) / per));
     if (sb) sb->fused = true;
     float* const dsrcbias = sb ? sb->target : nullptr;
-    MTRSSM_WGRAD_PART((size_t)grid.x * kWgT4bSetFloats * sizeof(float))
-#define MTRSSM_WGT4B_LAUNCH(SP_, W_)                                                                                             \
-  {                                                                                                                             \
-    static bool attr_done_dev[64] = {}; bool& attr_done = attr_done_dev[device_slot()]; /* once per instantiation: never while another stream may be running the kernel */       \
-    constexpr int lds_b = wgt4b_lds_bytes<SP_, W_>();                                                                           \
-    if (!attr_done) {                                                                                                           \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(convt4s2b_wgrad_staged_kernel<SP_, W_>),                           \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_b);                                             \
-      attr_done = true;                                                                                                         \
-    }                                                                                                                           \
-    set_last_kernel("mtrssm::convt4s2b_wgrad_staged_kernel<" #SP_ ", " #W_ ">");                                                 \
-    hipLaunchKernelGGL((convt4s2b_wgrad_staged_kernel<SP_, W_>), grid, dim3(512), lds_b, stream, *g, a, src, pre_act_a, dwp,     \
-                       part, dsrcbias, per);                                                                                    \
-  }
-    const int sp = g->mfma_split;
-    if (g->Wq == 8) { if (sp == 2) MTRSSM_WGT4B_LAUNCH(2, 8) else MTRSSM_WGT4B_LAUNCH(1, 8) }
-    else { if (sp == 2) MTRSSM_WGT4B_LAUNCH(2, 4) else MTRSSM_WGT4B_LAUNCH(1, 4) }
-#undef MTRSSM_WGT4B_LAUNCH
-    if (part)
-      if (int rc = reduce_now_or_later(kRedT4b, dim3(kWgT4bTileFloats / 4 / 8 + (dsrcbias ? 1 : 0)), part, (int)grid.x, g->Cpad, dwp, dsrcbias, stream)) return rc;
-    return launched("conv_weight_grad(k4 s2 staged, 64 rows)");
+    const StagedWgrad sw = staged("conv_weight_grad(k4 s2 staged, 64 rows)", cu_count(), 1, 512, kWgT4bSetFloats, kRedT4b, kWgT4bTileFloats / 4 / 8, dsrcbias);
+    return MTRSSM_STAGED(convt4s2b_wgrad_staged_kernel, wgt4b_lds_bytes, g->Wq, 8, 4, *g, a, src, pre_act_a, dwp);
   }
   if ((g->mfma_split == 1 || g->mfma_split == 2) && g->KH == 3 && g->KW == 3 && g->SS == 2 && g->TS == 1 && g->OFFY == -1 && g->OFFX == -1 &&
       g->C2 == 0 && g->C == 16 && g->Cout == 32 && g->Hq * g->Wq == 64 && (g->Wq == 8 || g->Wq == 4) && g->Hs == 2 * g->Hq && g->Ws == 2 * g->Wq &&
       g->Cpad >= 16 && !pre_act_a && (g->act == MTRSSM_ACT_IDENTITY || g->act == MTRSSM_ACT_ELU || g->act == MTRSSM_ACT_RELU) &&
-      !((uintptr_t)a & 15) && !((uintptr_t)src & 15) && wgrad_s2_staged_enabled()) {
+      !((uintptr_t)a & 15) && !((uintptr_t)src & 15)) {
     // third encoder layer (3x3 / stride 2, 16 -> 32, 64-pixel output planes): operands staged once per frame
-    int wgs = cu_count();
-    if (wgs > g->N) wgs = g->N;
-    const int per = (g->N + wgs - 1) / wgs;
-    const dim3 grid((unsigned)((g->N + per - 1) / per));
-    MTRSSM_WGRAD_PART((size_t)grid.x * kWgS2cSetFloats * sizeof(float))
-#define MTRSSM_WGS2C_LAUNCH(SP_, W_)                                                                                             \
-  {                                                                                                                             \
-    set_last_kernel("mtrssm::conv3x3s2c_wgrad_staged_kernel<" #SP_ ", " #W_ ">");                                                \
-    hipLaunchKernelGGL((conv3x3s2c_wgrad_staged_kernel<SP_, W_>), grid, dim3(512), wgs2c_lds_bytes<SP_>(), stream, *g, a, src,   \
-                       dwp, part, dbias, per);                                                                                  \
-  }
-    const int sp = g->mfma_split;
-    if (g->Wq == 8) { if (sp == 2) MTRSSM_WGS2C_LAUNCH(2, 8) else MTRSSM_WGS2C_LAUNCH(1, 8) }
-    else { if (sp == 2) MTRSSM_WGS2C_LAUNCH(2, 4) else MTRSSM_WGS2C_LAUNCH(1, 4) }
-#undef MTRSSM_WGS2C_LAUNCH
-    if (part)
-      if (int rc = reduce_now_or_later(kRedS2c, dim3(dbias ? 161 : 160), part, (int)grid.x, g->Cpad, dwp, dbias, stream)) return rc;
-    return launched("conv_weight_grad(3x3 s2 staged, 16 -> 32)");
+    const StagedWgrad sw = staged("conv_weight_grad(3x3 s2 staged, 16 -> 32)", cu_count(), 1, 512, kWgS2cSetFloats, kRedS2c, 160, dbias);
+    return MTRSSM_STAGED(conv3x3s2c_wgrad_staged_kernel, wgs2c_lds_bytes_w, g->Wq, 8, 4, *g, a, src, dwp);
   }
   MTRSSM_WGRAD_NO_PART
   // ---- patch-staged kernel when the 64-pixel groups tile the frames exactly
@@ -2544,8 +2286,6 @@ int conv_weight_grad_launch_ex(const MtrssmConvGeom* g, const float* a, const fl
     const size_t lds = (2 * ((size_t)tco * kLDA + (size_t)ctot * pg.ps) + kGP) * sizeof(float);
     const int n_out = g->Cout * taps * ctot;
     const size_t lds_thin = (2 * ((size_t)g->Cout * kLDA + (size_t)ctot * pg.ps) + kGP + ((pg.ps_raw + 63) & ~63)) * sizeof(float);
-    const bool mfma_ok = nq <= 4 * kMaxQ && lds <= 150 * 1024;
-    (void)mfma_ok;
     if (tiles && n_out <= kThinOut * kConvThreads && lds_thin <= 64 * 1024 && ptot < (1L << 31) && pg.ps_raw < 1024 && pg.ipg < 1024 &&
         !(g->mfma_split >= 1 && ctot >= 8 && (g->Hq * g->Wq) % 8 == 0)) {  // thin layer: staging-bound, VALU reduction is faster
       const long groups = (ptot + kGP - 1) / kGP;
@@ -2576,12 +2316,7 @@ int conv_weight_grad_launch_ex(const MtrssmConvGeom* g, const float* a, const fl
         dim3 grid((unsigned)splits, cotiles);
 #define MTRSSM_WG_SPLIT_LAUNCH(NT_, SP_)                                                                                       \
   {                                                                                                                             \
-    static bool attr_done_dev[64] = {}; bool& attr_done = attr_done_dev[device_slot()]; /* once per instantiation: never while another stream may be running the kernel */       \
-    if (!attr_done) {                                                                                                           \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_weight_grad_split_kernel<NT_, SP_>),                         \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);                                        \
-      attr_done = true;                                                                                                         \
-    }                                                                                                                           \
+    allow_lds<conv_weight_grad_split_kernel<NT_, SP_>>(156 * 1024);                                                             \
     set_last_kernel("mtrssm::conv_weight_grad_split_kernel<" #NT_ ", " #SP_ ">");                                                \
     hipLaunchKernelGGL((conv_weight_grad_split_kernel<NT_, SP_>), grid, dim3(2 * kConvThreads), lds_s, stream, *g, a, src, src2, \
                        pre_act_a, dwp, dbias, cp2, nbuf);                                                                             \
@@ -2600,10 +2335,10 @@ int conv_weight_grad_launch_ex(const MtrssmConvGeom* g, const float* a, const fl
       if (splits < 1) splits = 1;
       dim3 grid((unsigned)splits, cotiles);
       if (g->Cout > 32) {
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_weight_grad_patch_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (lds > 64 * 1024) allow_lds<conv_weight_grad_patch_kernel<2>>((int)lds);
         { set_last_kernel("mtrssm::conv_weight_grad_patch_kernel<2>"); hipLaunchKernelGGL(conv_weight_grad_patch_kernel<2>, grid, dim3(2 * kConvThreads), lds, stream, *g, a, src, src2, pre_act_a, dwp, dbias); }
       } else {
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_weight_grad_patch_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (lds > 64 * 1024) allow_lds<conv_weight_grad_patch_kernel<1>>((int)lds);
         { set_last_kernel("mtrssm::conv_weight_grad_patch_kernel<1>"); hipLaunchKernelGGL(conv_weight_grad_patch_kernel<1>, grid, dim3(2 * kConvThreads), lds, stream, *g, a, src, src2, pre_act_a, dwp, dbias); }
       }
       return launched("conv_weight_grad(patch)");
@@ -2627,6 +2362,8 @@ int conv_weight_grad_launch_ex(const MtrssmConvGeom* g, const float* a, const fl
     { set_last_kernel("mtrssm::conv_weight_grad_kernel<1>"); hipLaunchKernelGGL(conv_weight_grad_kernel<1>, grid, dim3(kConvThreads), 0, stream, *g, a, src, src2, pre_act_a, dwp); }
   return launched("conv_weight_grad");
 }
+#undef MTRSSM_STAGED
+#undef MTRSSM_STAGED_ONE
 
 // The decoders' last layer on the MFMA (conv_s2_band.h: convt4s2_band_kernel): 16 input channels, <= 2 output channels, frames
 // of 1024 positions (64 x 16 or 32 x 32); two bf16 pieces per operand.  Returns MTRSSM_EINVAL outside these shapes (the caller
@@ -2648,12 +2385,7 @@ int convt_k4s2_band_launch(int N, int C, int Hs, int Ws, int Cout, const float* 
   p.nx = N < slots ? N : slots;
   none.nx = 0;
   const size_t lds = (size_t)convt_band_lds_bytes(Hs, Ws);
-  static bool attr_done_dev[64] = {};
-  bool& attr_done = attr_done_dev[device_slot()];
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(convt4s2_band_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    attr_done = true;
-  }
+  allow_lds<convt4s2_band_kernel>(80 * 1024);
   set_last_kernel("mtrssm::convt4s2_band_kernel");
   hipLaunchKernelGGL(convt4s2_band_kernel, dim3((unsigned)p.nx), dim3(256), lds, stream, p, none);
   return launched("convt_k4s2_band");
@@ -2694,23 +2426,10 @@ int encoder_stem_launch(const MtrssmEncoderStem* a, const MtrssmEncoderStem* b, 
   if (b) {
     if (int rc = fill(b, qb)) return rc;
   }
-  const long ta = qa.N, tb = b ? qb.N : 0;
-  const int slots = cu_count();  // one 512-thread workgroup per CU
-  if (tb == 0) {
-    qa.nx = (int)(ta < slots ? ta : slots);
-    qb.nx = 0;
-  } else {
-    long na = (slots * ta + (ta + tb) / 2) / (ta + tb);
-    na = na < 1 ? 1 : (na > slots - 1 ? slots - 1 : na);
-    qa.nx = (int)(na < ta ? na : ta);
-    qb.nx = (int)(slots - na < tb ? slots - na : tb);
-  }
-  static bool attr_done_dev[64] = {};
-  bool& attr_done = attr_done_dev[device_slot()];
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(encoder_stem_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kStemLds);
-    attr_done = true;
-  }
+  const PairSplit wg = split_slots(qa.N, b ? qb.N : 0, cu_count());  // one 512-thread workgroup per CU
+  qa.nx = wg.na;
+  qb.nx = wg.nb;
+  allow_lds<encoder_stem_kernel>(kStemLds);
   set_last_kernel("mtrssm::encoder_stem_kernel");
   hipLaunchKernelGGL(encoder_stem_kernel, dim3((unsigned)(qa.nx + qb.nx)), dim3(kStemThreads), (size_t)kStemLds, stream, qa, qb);
   return launched("encoder_stem_fwd");
@@ -2780,7 +2499,7 @@ static int quad_key(const MtrssmConvGeom* g4) {
   return 0;
 }
 
-int conv_convt_quad_supported(const MtrssmConvGeom* g4) { return resident_enabled() ? quad_key(g4) : 0; }
+int conv_convt_quad_supported(const MtrssmConvGeom* g4) { return quad_key(g4); }
 
 int conv_convt_quad_launch(const MtrssmConvGeom* ga4, const float* srca, const unsigned short* const* wqa4, const float* biasa,
                            const float* actgrada, float* outa, const MtrssmConvGeom* gb4, const float* srcb,
@@ -2801,85 +2520,39 @@ int conv_convt_quad_launch(const MtrssmConvGeom* ga4, const float* srca, const u
   qa.src = srca; qa.bias = biasa; qa.actgrad = actgrada; qa.out = outa;
   qb.src = srcb; qb.bias = biasb; qb.actgrad = actgradb; qb.out = outb;
   const long ta = ga4[0].N, tb = gb4 ? gb4[0].N : 0;
-  const int ncu = cu_count();
-  if (tb == 0) {
-    qa.nx = (int)(ta < ncu ? ta : ncu);
-    qb.nx = 0;
-  } else {
-    long na = (ncu * ta + (ta + tb) / 2) / (ta + tb);
-    na = na < 1 ? 1 : (na > ncu - 1 ? ncu - 1 : na);
-    qa.nx = (int)(na < ta ? na : ta);
-    qb.nx = (int)(ncu - na < tb ? ncu - na : tb);
-  }
-  const dim3 grid((unsigned)(qa.nx + qb.nx));
+  // persistent workgroups: `wgs` per CU (the kernel's share of a CU), split between the two tensors by their frames
+  auto share = [&](int wgs) {
+    const PairSplit wg = split_slots(ta, tb, cu_count() * wgs);
+    qa.nx = wg.na;
+    qb.nx = wg.nb;
+    return dim3((unsigned)(wg.na + wg.nb));
+  };
   // The classes as tile rows (convt4s2_rows_kernel) where that form is faster: 32 -> 16 on 256-position frames (198 -> 158 us
   // paired) and 16 -> 8 with the act' operand (144 -> 88 us); the 64-position frames stay on one wave per class (the rows form
-  // multiplies 2.25 x as much: 124 -> 189 us, 80 -> 103 us).  MTRSSM_CONVT_ROWS=<digits>: the keys (1..4) that use it ("0": none).
-  static const unsigned rows_mask = [] {
-    const char* e = getenv("MTRSSM_CONVT_ROWS");
-    if (!e) return (1u << 2) | (1u << 4);
-    unsigned m = 0;
-    for (; *e; ++e)
-      if (*e >= '1' && *e <= '4') m |= 1u << (*e - '0');
-    return m;
-  }();
+  // multiplies 2.25 x as much: 124 -> 189 us, 80 -> 103 us).
 #define MTRSSM_ROWS_LAUNCH(CIN_, COUT_, PLANE_, EPI_)                                                                \
   {                                                                                                                   \
-    static bool attr_done_dev[64] = {}; bool& attr_done = attr_done_dev[device_slot()];                               \
     const size_t ql = convt_rows_lds_bytes<CIN_, PLANE_>();                                                           \
-    const int slots = ncu * convt_rows_wgs(CIN_, COUT_, PLANE_);   /* persistent workgroups: this kernel's share of a CU */ \
-    if (tb == 0) {                                                                                                    \
-      qa.nx = (int)(ta < slots ? ta : slots);                                                                         \
-    } else {                                                                                                          \
-      long na = (slots * ta + (ta + tb) / 2) / (ta + tb);                                                             \
-      na = na < 1 ? 1 : (na > slots - 1 ? slots - 1 : na);                                                            \
-      qa.nx = (int)(na < ta ? na : ta);                                                                               \
-      qb.nx = (int)(slots - na < tb ? slots - na : tb);                                                               \
-    }                                                                                                                 \
-    const dim3 grid((unsigned)(qa.nx + qb.nx));                                                                       \
-    if (!attr_done) {                                                                                                 \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(convt4s2_rows_kernel<CIN_, COUT_, PLANE_, EPI_>),       \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)ql);                                 \
-      attr_done = true;                                                                                               \
-    }                                                                                                                 \
+    const dim3 grid = share(convt_rows_wgs(CIN_, COUT_, PLANE_));                                                     \
+    allow_lds<convt4s2_rows_kernel<CIN_, COUT_, PLANE_, EPI_>>((int)ql);                                              \
     set_last_kernel("mtrssm::convt4s2_rows_kernel<" #CIN_ ", " #COUT_ ", " #PLANE_ ", " #EPI_ ">");                      \
     hipLaunchKernelGGL((convt4s2_rows_kernel<CIN_, COUT_, PLANE_, EPI_>), grid, dim3(64 * ((PLANE_ + 63) / 64) * (COUT_ / 8)), ql, stream, qa, qb); \
     return launched("convt_quad(rows)");                                                                              \
   }
-  if (rows_mask & (1u << key)) {
-    if (key == 1) MTRSSM_ROWS_LAUNCH(64, 32, 64, false)
-    if (key == 2) MTRSSM_ROWS_LAUNCH(32, 16, 256, false)
-    if (key == 3) MTRSSM_ROWS_LAUNCH(32, 16, 64, true)
-    if (key == 4) MTRSSM_ROWS_LAUNCH(16, 8, 256, true)
-  }
-#undef MTRSSM_ROWS_LAUNCH
 #define MTRSSM_QUAD_LAUNCH(CIN_, COUT_, PLANE_, EPI_)                                                                \
   {                                                                                                                   \
-    static bool attr_done_dev[64] = {}; bool& attr_done = attr_done_dev[device_slot()];                                                                                    \
     const size_t ql = quad_lds_bytes<CIN_, PLANE_>();                                                                 \
-    const int slots = ncu * quad_wgs(CIN_, PLANE_);                                                                         \
-    if (tb == 0) {                                                                                                    \
-      qa.nx = (int)(ta < slots ? ta : slots);                                                                         \
-    } else {                                                                                                          \
-      long na = (slots * ta + (ta + tb) / 2) / (ta + tb);                                                             \
-      na = na < 1 ? 1 : (na > slots - 1 ? slots - 1 : na);                                                            \
-      qa.nx = (int)(na < ta ? na : ta);                                                                               \
-      qb.nx = (int)(slots - na < tb ? slots - na : tb);                                                               \
-    }                                                                                                                 \
-    const dim3 grid((unsigned)(qa.nx + qb.nx));                                                                       \
-    if (!attr_done) {                                                                                                 \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(convt_quad_resident_kernel<CIN_, COUT_, PLANE_, EPI_>), \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)ql);                                 \
-      attr_done = true;                                                                                               \
-    }                                                                                                                 \
+    const dim3 grid = share(quad_wgs(CIN_, PLANE_));                                                                  \
+    allow_lds<convt_quad_resident_kernel<CIN_, COUT_, PLANE_, EPI_>>((int)ql);                                        \
     set_last_kernel("mtrssm::convt_quad_resident_kernel<" #CIN_ ", " #COUT_ ", " #PLANE_ ", " #EPI_ ">");                \
     hipLaunchKernelGGL((convt_quad_resident_kernel<CIN_, COUT_, PLANE_, EPI_>), grid, dim3(kResThreads), ql, stream, qa, qb); \
     return launched("convt_quad");                                                                                    \
   }
   if (key == 1) MTRSSM_QUAD_LAUNCH(64, 32, 64, false)
-  if (key == 2) MTRSSM_QUAD_LAUNCH(32, 16, 256, false)
-  if (key == 4) MTRSSM_QUAD_LAUNCH(16, 8, 256, true)
+  if (key == 2) MTRSSM_ROWS_LAUNCH(32, 16, 256, false)
+  if (key == 4) MTRSSM_ROWS_LAUNCH(16, 8, 256, true)
   MTRSSM_QUAD_LAUNCH(32, 16, 64, true)
+#undef MTRSSM_ROWS_LAUNCH
 #undef MTRSSM_QUAD_LAUNCH
 }
 
