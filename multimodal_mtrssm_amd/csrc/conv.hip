@@ -653,6 +653,7 @@ __global__ __launch_bounds__(kConvThreads) void conv_gather_gemm_patch_kernel(
 
 }  // namespace mtrssm
 #include "conv_split.h"
+#include "conv_wgrad_stage.h"
 #include "conv_resident.h"
 #include "conv_s2_band.h"
 #include "conv_stem.h"
@@ -680,25 +681,32 @@ struct ReduceBatch {
   int first[kReduceBatchMax + 1];   // first block of job j; first[count] = the grid
   ReduceJob job[kReduceBatchMax];
 };
-__device__ __forceinline__ void wgrad_reduce_dispatch(const ReduceJob& j, int bx, int by) {
+// One `red` buffer for whichever layout the workgroup's job has (both shapes are 256 float4).
+__device__ __forceinline__ void wgrad_reduce_dispatch(float4* const red, const ReduceJob& j, int bx, int by) {
+#define MTRSSM_REDUCE(...) wgrad_reduce_sets<__VA_ARGS__>(red, j.part, j.S, j.cpad, j.dwp, j.dbias, bx, by)
   switch (j.variant) {  // block-uniform
-    case kRedRes64: wgrad_reduce_partials_body<64>(j.part, j.S, j.cpad, j.dwp, j.dbias, bx, by); break;
-    case kRedRes32: wgrad_reduce_partials_body<32>(j.part, j.S, j.cpad, j.dwp, j.dbias, bx, by); break;
-    case kRed1x1_64: wgrad_reduce_partials1x1_body<64>(j.part, j.S, j.cpad, j.dwp, j.dbias, bx, by); break;
-    case kRed1x1_128: wgrad_reduce_partials1x1_body<128>(j.part, j.S, j.cpad, j.dwp, j.dbias, bx, by); break;
-    case kRedThin: wgrad_reduce_partials_thin_body(j.part, j.S, j.cpad, j.dwp, j.dbias, bx, by); break;
-    case kRedThinT: wgrad_reduce_partials_thint_body(j.part, j.S, j.cpad, j.dwp, j.dbias, bx, by); break;
-    case kRedS2: wgrad_reduce_partials_s2_body(j.part, j.S, j.cpad, j.dwp, j.dbias, bx, by); break;
-    case kRedT4: wgrad_reduce_partials_t4_body(j.part, j.S, j.cpad, j.dwp, j.dbias, bx, by); break;
-    case kRedT4b: wgrad_reduce_partials_t4b_body(j.part, j.S, j.cpad, j.dwp, j.dbias, bx, by); break;
-    default: wgrad_reduce_partials_s2c_body(j.part, j.S, j.cpad, j.dwp, j.dbias, bx, by); break;
+    case kRedRes64: MTRSSM_REDUCE(WgRedRes<64>); break;
+    case kRedRes32: MTRSSM_REDUCE(WgRedRes<32>); break;
+    case kRed1x1_64: MTRSSM_REDUCE(WgRed1x1<64>); break;
+    case kRed1x1_128: MTRSSM_REDUCE(WgRed1x1<128>); break;
+    case kRedThin: MTRSSM_REDUCE(WgRedThin); break;
+    case kRedThinT:
+      if (bx >= 16) wgrad_reduce_thint_bias(red, j.part, j.S, j.dbias);
+      else MTRSSM_REDUCE(WgRedThinT);
+      break;
+    case kRedS2: MTRSSM_REDUCE(WgRedS2); break;
+    case kRedT4: MTRSSM_REDUCE(WgRedT4); break;
+    case kRedT4b: MTRSSM_REDUCE(WgRedT4b); break;
+    default: MTRSSM_REDUCE(WgRedS2c); break;
   }
+#undef MTRSSM_REDUCE
 }
 __global__ __launch_bounds__(256) void wgrad_reduce_batch_kernel(const ReduceBatch b) {
+  __shared__ float4 red[256];
   int j = 0;
   while (j + 1 < b.count && (int)blockIdx.x >= b.first[j + 1]) ++j;  // scalar: <= 48 steps
   const int lb = (int)blockIdx.x - b.first[j], gx = b.job[j].gx;
-  wgrad_reduce_dispatch(b.job[j], lb % gx, lb / gx);
+  wgrad_reduce_dispatch(red, b.job[j], lb % gx, lb / gx);
 }
 
 // jobs recorded per stream.  Two jobs of one batch never add into the same dwp / dbias words unless the SAME layer ran twice

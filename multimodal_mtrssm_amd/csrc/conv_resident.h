@@ -234,12 +234,7 @@ __global__ __launch_bounds__(kResThreads, 1) void conv3x3_resident_kernel(const 
   const int spos = ((lane >> wsh) + 1) * pw + (lane & (g.Wq - 1)) + 1;  // staging: lane = pixel of the frame
   // activation switches as lane-uniform selects (no branch inside the MFMA loop: a branch ends a scheduling region)
   const bool act_elu = g.act == MTRSSM_ACT_ELU, act_relu = g.act == MTRSSM_ACT_RELU, pre = g.pre_act != 0;
-  auto act_fwd_sel = [&](float x) {  // pre-activation of a staged value
-    float e = __expf(x) - 1.f;
-    asm volatile("" : "+v"(e));  // computed unconditionally: the compiler would branch around the exponential
-    const float neg = act_elu ? e : (act_relu ? 0.f : x);
-    return (x > 0.f || !pre) ? x : neg;
-  };
+  auto act_fwd_sel = [&](float x) { return WgActSel{act_elu, act_relu, pre}(x); };  // pre-activation of a staged value
   auto act_grad_sel = [&](float x) {  // act'(x) from the layer input
     float e = __expf(x);
     asm volatile("" : "+v"(e));
@@ -611,12 +606,7 @@ __global__ __launch_bounds__(kResThreads, quad_wgs(CIN, PLANE)) void convt_quad_
   const int Ws = g.Ws, pw = Ws + 2, wsh = 31 - __builtin_clz(Ws);  // host: Ws a power of two, Hs * Ws == PLANE
   const int plane_o = g.Ho * g.Wo;
   const bool act_elu = g.act == MTRSSM_ACT_ELU, act_relu = g.act == MTRSSM_ACT_RELU, pre = g.pre_act != 0;
-  auto act_fwd_sel = [&](float x) {
-    float e = __expf(x) - 1.f;
-    asm volatile("" : "+v"(e));
-    const float neg = act_elu ? e : (act_relu ? 0.f : x);
-    return (x > 0.f || !pre) ? x : neg;
-  };
+  auto act_fwd_sel = [&](float x) { return WgActSel{act_elu, act_relu, pre}(x); };
   float pv[NIT][8];
   auto stage_load_part = [&](int tile, int part, int nparts) {
     constexpr int TOT = NIT * 8;

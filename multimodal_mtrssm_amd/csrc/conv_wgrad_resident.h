@@ -1,4 +1,5 @@
-// Staged weight-gradient kernels (included by conv.hip after conv_split.h): a workgroup per CU owns a run of frames, loads
+// Staged weight-gradient kernels (included by conv.hip after conv_split.h and conv_wgrad_stage.h, which holds the pieces they
+// share and the one body that sums their partial sets): a workgroup per CU owns a run of frames, loads
 // every frame of both operands once, converts it once, keeps it in LDS for the MFMAs and leaves ONE partial set for a
 // reduce kernel.  In this file: the 3x3 / stride 1 layers of the residual stacks (first, with the reasoning), their 1x1
 // layers, the encoders' three 3x3 / stride-2 convolutions and the decoders' three k = 4 / stride-2 transposed convolutions.
@@ -25,7 +26,7 @@
 //   * gives each wave nine accumulator tiles chosen so that it reads two image rows instead of three: the two waves of a
 //     ci tile hold {co tile 0: taps 0-4, co tile 1: taps 0-3} and {co tile 1: taps 4-8, co tile 0: taps 5-8};
 //   * writes its partial tiles with plain 16-byte stores, in accumulator order, to a scratch slice of its own (`part`),
-//     summed and scattered into dwp by wgrad_reduce_partials_kernel right behind it in the stream: no atomics, run-to-run
+//     summed and scattered into dwp by wgrad_reduce_batch_kernel (layout WgRedRes) right behind it in the stream: no atomics, run-to-run
 //     deterministic.  With part == NULL (no scratch: first call inside a stream capture, or MTRSSM_WGRAD_PARTIALS=0) the
 //     tiles leave by fp32 atomics in the dwp layout [co][tap][Cpad], as in the other kernels.
 // One barrier per frame.
@@ -51,19 +52,6 @@ __host__ __device__ constexpr int wgres_tile_floats(int c) { return 2 * (c / 32)
 // ... followed by the workgroup's 64 bias-gradient sums (256 workgroups adding to the same 64 addresses took 10-25 us)
 __host__ __device__ constexpr int wgres_set_floats(int c) { return wgres_tile_floats(c) + 64; }
 constexpr int kWg1x1SetFloats = 8 * 1024 + 64;  // conv1x1_wgrad_staged_kernel: 8 waves x one tile, + 64 bias sums
-
-using wg_bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-using wg_f32x2 = __attribute__((ext_vector_type(2))) float;
-using wg_f32x4 = __attribute__((ext_vector_type(4))) float;  // a register quadruple inline asm can name (float4 is a struct)
-// two values -> packed bf16 pieces (round to nearest even, as split_bf16): d[s] = piece s of (f0 low half, f1 high half)
-template <int SPLIT>
-__device__ __forceinline__ void wg_split_pair(const float f0, const float f1, unsigned (&d)[SPLIT]) {
-  d[0] = __builtin_bit_cast(unsigned, __builtin_convertvector(wg_f32x2{f0, f1}, wg_bf16x2));
-  if constexpr (SPLIT >= 2) {
-    const float r0 = f0 - __builtin_bit_cast(float, d[0] << 16), r1 = f1 - __builtin_bit_cast(float, d[0] & 0xffff0000u);  // exact
-    d[1] = __builtin_bit_cast(unsigned, __builtin_convertvector(wg_f32x2{r0, r1}, wg_bf16x2));
-  }
-}
 
 // One problem's work of one workgroup: bx of the problem's nbx x blocks (its run of frames_per_wg frames), co group blockIdx.y.
 // The kernels below are wrappers: one problem per grid, or two (audio and vision planes) side by side in one grid.
@@ -92,14 +80,8 @@ __device__ __forceinline__ void conv3x3_wgrad_resident_body(
   unsigned long long* const prof = (tid == 0 && blockIdx.y == 0 && g_res_prof) ? (bx == 0 ? g_res_prof + 32 : (bx == nbx / 2 ? g_res_prof + 40 : nullptr)) : nullptr;
   if (prof) prof[0] = __builtin_readcyclecounter();
 
-  // activation switches as lane-uniform selects (no branch inside the MFMA loop: a branch ends a scheduling region)
   const bool act_elu = act == MTRSSM_ACT_ELU, act_relu = act == MTRSSM_ACT_RELU, pre = pre_act != 0;
-  auto act_sel = [&](float x) __attribute__((always_inline)) {
-    float e = __expf(x) - 1.f;
-    asm volatile("" : "+v"(e));  // computed unconditionally: the compiler would branch around the exponential
-    const float neg = act_elu ? e : (act_relu ? 0.f : x);
-    return (x > 0.f || !pre) ? x : neg;
-  };
+  const WgActSel act_sel{act_elu, act_relu, pre};
 
   // ---- zero everything once: the halo rows are never written again
   for (int o = tid * 16; o < wgres_lds_bytes<SPLIT, C, W>(); o += NT * 16) *reinterpret_cast<uint4*>(lds + o) = make_uint4(0u, 0u, 0u, 0u);
@@ -172,13 +154,9 @@ __device__ __forceinline__ void conv3x3_wgrad_resident_body(
       }
     }
   };
-  auto ab = [](const unsigned hi, const unsigned lo) __attribute__((always_inline)) { return __builtin_amdgcn_alignbit(hi, lo, 16); };
-  auto shr1 = [&](const u32x4 f) __attribute__((always_inline)) {  // pixel x <- x - 1, zero into every row's first pixel
-    return W == 8 ? u32x4{f.x << 16, ab(f.y, f.x), ab(f.z, f.y), ab(f.w, f.z)} : u32x4{f.x << 16, ab(f.y, f.x), f.z << 16, ab(f.w, f.z)};
-  };
-  auto shl1 = [&](const u32x4 f) __attribute__((always_inline)) {  // pixel x <- x + 1, zero into every row's last pixel
-    return W == 8 ? u32x4{ab(f.y, f.x), ab(f.z, f.y), ab(f.w, f.z), f.w >> 16} : u32x4{ab(f.y, f.x), f.y >> 16, ab(f.w, f.z), f.w >> 16};
-  };
+  constexpr int FR = W == 8 ? 1 : 2;  // image rows per fragment
+  auto shr1 = [](const u32x4 f) __attribute__((always_inline)) { return wg_rows_shift_in_front<FR>(f); };  // pixel x <- x - 1
+  auto shl1 = [](const u32x4 f) __attribute__((always_inline)) { return wg_rows_shift_behind<FR>(f); };    // pixel x <- x + 1
   auto mfmas = [&](const int set) __attribute__((always_inline)) {
     u32x4 qb[5][SPLIT];
 #pragma unroll
@@ -218,13 +196,7 @@ __device__ __forceinline__ void conv3x3_wgrad_resident_body(
       asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(raw[rs][it]) : "v"(ptr));
     }
   };
-  auto raw_wait = [&](const int rs) __attribute__((always_inline)) {  // every request so far has landed
-    if constexpr (NI == 8) {
-      asm volatile("s_waitcnt vmcnt(0)" : "+v"(raw[rs][0]), "+v"(raw[rs][1]), "+v"(raw[rs][2]), "+v"(raw[rs][3]), "+v"(raw[rs][4]), "+v"(raw[rs][5]), "+v"(raw[rs][6]), "+v"(raw[rs][7]));
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" : "+v"(raw[rs][0]), "+v"(raw[rs][1]), "+v"(raw[rs][2]), "+v"(raw[rs][3]), "+v"(raw[rs][4]), "+v"(raw[rs][5]), "+v"(raw[rs][6]), "+v"(raw[rs][7]), "+v"(raw[rs][8]), "+v"(raw[rs][9]), "+v"(raw[rs][10]), "+v"(raw[rs][11]));
-    }
-  };
+  auto raw_wait = [&](const int rs) __attribute__((always_inline)) { wg_raw_wait<0>(raw[rs]); };  // every request so far has landed
   auto stage = [&](const int rs, const int it, const unsigned xo, const unsigned ao, const float keep) __attribute__((always_inline)) {
     const float4 v = make_float4(raw[rs][it].x, raw[rs][it].y, raw[rs][it].z, raw[rs][it].w);
     if (it < XI) stage_x(v, it, xo); else stage_a(v, it - XI, ao, keep);
@@ -291,12 +263,10 @@ __device__ __forceinline__ void conv3x3_wgrad_resident_body(
 
   if (part) {
     // accumulator order: float4 number ((wave * 9 + j) * 4 + r / 4) * 64 + lane of this workgroup's set -- every store
-    // instruction writes 1 KiB in a row (wgrad_reduce_partials_kernel maps it back to dwp)
+    // instruction writes 1 KiB in a row (WgRedRes::scatter maps it back to dwp)
     float4* const ps = reinterpret_cast<float4*>(part) + ((size_t)blockIdx.y * nbx + bx) * (wgres_set_floats(C) / 4) + (size_t)wave * (9 * 4 * 64) + lane;
 #pragma unroll
-    for (int j = 0; j < 9; ++j)
-#pragma unroll
-      for (int gq = 0; gq < 4; ++gq) ps[(j * 4 + gq) * 64] = make_float4(acc[j][4 * gq], acc[j][4 * gq + 1], acc[j][4 * gq + 2], acc[j][4 * gq + 3]);
+    for (int j = 0; j < 9; ++j) wg_store_tile(ps + j * 256, acc[j]);
   } else {
     const int ci = tci * 32 + il;
 #pragma unroll
@@ -306,7 +276,7 @@ __device__ __forceinline__ void conv3x3_wgrad_resident_body(
       const int cot = cob + (j < 5 ? coA : coB) * 32;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = cot + (r & 3) + 8 * (r >> 2) + 4 * kl;
+        const int row = wg_tile_row(r, kl, cot);
         atomicAdd(&dwp[((size_t)row * 9 + tap) * cpad + ci], acc[j][r]);
       }
     }
@@ -314,11 +284,7 @@ __device__ __forceinline__ void conv3x3_wgrad_resident_body(
   if (dbias != nullptr) {
 #pragma unroll
     for (int j = 0; j < AI; ++j) {  // the 16 lanes of a DPP row share a channel
-      float v = bsum[j];
-      v += dpp_move<0xB1, 0xF>(0.f, v);   // quad_perm [1, 0, 3, 2]
-      v += dpp_move<0x4E, 0xF>(0.f, v);   // quad_perm [2, 3, 0, 1]
-      v += dpp_move<0x141, 0xF>(0.f, v);  // row_half_mirror
-      v += dpp_move<0x140, 0xF>(0.f, v);  // row_mirror
+      const float v = wg_row16_sum(bsum[j]);
       if (xi == 0) {
         const int ch = (tid >> 4) + j * (NT / 16);
         if (part) part[((size_t)blockIdx.y * nbx + bx) * wgres_set_floats(C) + wgres_tile_floats(C) + ch] = v;
@@ -360,65 +326,24 @@ __global__ __launch_bounds__(64 * 2 * (C / 32), 1) void conv3x3_wgrad_pair_resid
   else conv3x3_wgrad_resident_body<SPLIT, C, WB>(pb.N, pb.Cout, pb.cpad, pb.act, pb.pre_act, pb.a, pb.src, pb.dwp, pb.part, pb.dbias, pb.frames_per_wg, bx - pa.xblocks, pb.xblocks);
 }
 
-// Sum of the S partial tile sets of every co group (part [cogroups][S][set floats], accumulator order) into dwp.  Thread =
-// one float4 of the set (rows r .. r + 3 of one accumulator column) x one of 8 slice groups of S (four loads in flight), the
-// groups met in LDS; 32 lanes read 512 contiguous bytes of a set (with 128-byte pieces 147 KB apart the 520 MB of these sets
-// streamed at 3 TB/s).  dwp is read-modified-written without atomics: launches that accumulate into one dwp chunk are ordered
-// by their stream.
+// Partial sets of conv3x3_wgrad_resident_body (and its pair form): float4 f = ((wave * 9 + j) * 4 + gq) * 64 + lane, then the
+// 64 bias sums of the co group (16 float4 of the bias block's 32).
 template <int C>
-__device__ __forceinline__ void wgrad_reduce_partials_body(const float4* __restrict__ part, const int S, const int cpad,
-                                                                    float* __restrict__ dwp, float* __restrict__ dbias, const int bx, const int by) {
-  constexpr int SET4 = wgres_set_floats(C) / 4, TILE4 = wgres_tile_floats(C) / 4;
-  constexpr int NL = 32, NG = 8;  // 32 float4 columns (512 bytes of a set) x 8 slice groups of S per workgroup
-  static_assert(TILE4 % NL == 0, "whole blocks");
-  __shared__ float4 red[NG][NL];
-  const int li = threadIdx.x & (NL - 1), sg = threadIdx.x / NL;
-  const int f = bx * NL + li;  // host: grid.x * 32 == TILE4 (+ 32: the bias block, 16 float4 of it in use, launched when dbias != NULL)
-  const float4* const p = part + (size_t)by * S * SET4 + (f < SET4 ? f : SET4 - 1);
-  float4 acc4[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) acc4[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-  int s = sg;
-  for (; s + 3 * NG < S; s += 4 * NG) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const float4 v = p[(size_t)(s + NG * u) * SET4];
-      acc4[u].x += v.x; acc4[u].y += v.y; acc4[u].z += v.z; acc4[u].w += v.w;
-    }
+struct WgRedRes {
+  static constexpr int NL = 32, NG = 8, U = 4, KS = 1, SET4 = wgres_set_floats(C) / 4, TILE4 = wgres_tile_floats(C) / 4;
+  static_assert(TILE4 % NL == 0, "whole blocks");  // host: grid.x * 32 == TILE4 (+ 32: the bias block)
+  static __device__ __forceinline__ WgRedCol column(const int f, const int by) {
+    return {(size_t)f, 0, f >= TILE4 ? by * 64 + 4 * (f - TILE4) : -1, f >= SET4};
   }
-  for (; s < S; s += NG) {
-    const float4 v = p[(size_t)s * SET4];
-    acc4[0].x += v.x; acc4[0].y += v.y; acc4[0].z += v.z; acc4[0].w += v.w;
-  }
-  red[sg][li] = make_float4((acc4[0].x + acc4[1].x) + (acc4[2].x + acc4[3].x), (acc4[0].y + acc4[1].y) + (acc4[2].y + acc4[3].y),
-                            (acc4[0].z + acc4[1].z) + (acc4[2].z + acc4[3].z), (acc4[0].w + acc4[1].w) + (acc4[2].w + acc4[3].w));
-  __syncthreads();
-  if (sg == 0) {
-    float4 t = red[0][li];
-#pragma unroll
-    for (int k = 1; k < NG; ++k) { t.x += red[k][li].x; t.y += red[k][li].y; t.z += red[k][li].z; t.w += red[k][li].w; }
-    if (f >= TILE4) {  // block-uniform: the bias sums of channels 4 (f - TILE4) .. + 3 of this co group (16 float4)
-      if (f - TILE4 < 16) {
-        float* const o = dbias + by * 64 + 4 * (f - TILE4);
-        o[0] += t.x; o[1] += t.y; o[2] += t.z; o[3] += t.w;
-      }
-      return;
-    }
-    // f = ((wave * 9 + j) * 4 + gq) * 64 + lane  ->  rows cot + 8 gq + 4 kl + {0..3}, tap, ci (the kernel's tile assignment)
+  // rows cot + 8 gq + 4 kl + {0..3}, tap, ci (the kernel's tile assignment)
+  static __device__ __forceinline__ void scatter(const int f, const int by, const float4 v, const int cpad, float* __restrict__ dwp) {
     const int lane = f & 63, gq = (f >> 6) & 3, wj = f >> 8, j = wj % 9, wave = wj / 9;
     const int il = lane & 31, kl = lane >> 5, tci = wave >> 1, half = wave & 1;
     const int k = j < 5 ? j : j - 5, tap = k < 3 ? (half ? 6 : 0) + k : (k == 3 ? (half ? 5 : 3) : 4);
     const int row = by * 64 + (j < 5 ? half : half ^ 1) * 32 + 8 * gq + 4 * kl;
-    float* const o = dwp + ((size_t)row * 9 + tap) * cpad + tci * 32 + il;
-    const size_t rs = (size_t)9 * cpad;
-    o[0] += t.x; o[rs] += t.y; o[2 * rs] += t.z; o[3 * rs] += t.w;
+    wg_red_add_rows(dwp + ((size_t)row * 9 + tap) * cpad + tci * 32 + il, (size_t)9 * cpad, v);
   }
-}
-template <int C>
-__global__ __launch_bounds__(256) void wgrad_reduce_partials_kernel(const float4* __restrict__ part, const int S, const int cpad,
-                                                                    float* __restrict__ dwp, float* __restrict__ dbias) {
-  wgrad_reduce_partials_body<C>(part, S, cpad, dwp, dbias, (int)blockIdx.x, (int)blockIdx.y);
-}
+};
 
 // ------------------------------------------------------------------------------------------------
 // Weight gradient of the 1x1 layers of the residual stacks on 64-pixel planes (64 -> 64 in the encoders, 128 -> 64 in the
@@ -432,7 +357,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_partials_kernel(const float4
 // register sets: one frame in flight per CU does not cover the HBM latency at this rate) and writes it to
 // double-buffered [channel][64 pixels + 8] bf16 images; the MFMA work is small (6 or 12 per wave and frame): wave w holds
 // tile w % NTILE and, with four tiles, half of the k-steps of every frame.  One barrier per frame; partial tiles stored
-// (32 KiB per workgroup) and summed by wgrad_reduce_partials1x1_kernel, or by fp32 atomics when part == NULL.
+// (32 KiB per workgroup) and summed by wgrad_reduce_batch_kernel (layout WgRed1x1), or by fp32 atomics when part == NULL.
 // ------------------------------------------------------------------------------------------------
 template <int SPLIT, int C>
 __host__ __device__ constexpr int wg1x1_lds_bytes() { return 2 * SPLIT * (64 + C) * kWgresAPitch; }
@@ -463,12 +388,7 @@ __global__ __launch_bounds__(512, 1) void conv1x1_wgrad_staged_kernel(
   if (prof) prof[0] = __builtin_readcyclecounter();
 
   const bool act_elu = g.act == MTRSSM_ACT_ELU, act_relu = g.act == MTRSSM_ACT_RELU, pre = g.pre_act != 0;
-  auto act_sel = [&](float x) __attribute__((always_inline)) {
-    float e = __expf(x) - 1.f;
-    asm volatile("" : "+v"(e));  // computed unconditionally: the compiler would branch around the exponential
-    const float neg = act_elu ? e : (act_relu ? 0.f : x);
-    return (x > 0.f || !pre) ? x : neg;
-  };
+  const WgActSel act_sel{act_elu, act_relu, pre};
 
   // staging: item j = float4 number tid + 512 j of the frame: 4 consecutive pixels of channel (tid >> 4) + 32 j
   const float4* const xsrc = reinterpret_cast<const float4*>(src) + tid;
@@ -479,17 +399,8 @@ __global__ __launch_bounds__(512, 1) void conv1x1_wgrad_staged_kernel(
 #pragma unroll
   for (int j = 0; j < AI; ++j) bsum[j] = 0.f;
   wg_f32x4 raw[3][NI];  // [set][a items, x items]
-  auto raw_load = [&](const int rs, const int n) __attribute__((always_inline)) {
-#pragma unroll
-    for (int it = 0; it < NI; ++it) {
-      const float4* const ptr = it < AI ? asrc + (size_t)n * afr + NT * it : xsrc + (size_t)n * xfr + NT * (it - AI);
-      asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(raw[rs][it]) : "v"(ptr));
-    }
-  };
-  auto raw_wait = [&](const int rs) __attribute__((always_inline)) {  // the two younger sets may still be in flight
-    if constexpr (NI == 4) asm volatile("s_waitcnt vmcnt(8)" : "+v"(raw[rs][0]), "+v"(raw[rs][1]), "+v"(raw[rs][2]), "+v"(raw[rs][3]));
-    else asm volatile("s_waitcnt vmcnt(12)" : "+v"(raw[rs][0]), "+v"(raw[rs][1]), "+v"(raw[rs][2]), "+v"(raw[rs][3]), "+v"(raw[rs][4]), "+v"(raw[rs][5]));
-  };
+  auto raw_load = [&](const int rs, const int n) __attribute__((always_inline)) { wg_raw_load<NT, AI, XI>(raw[rs], asrc, afr, xsrc, xfr, n); };
+  auto raw_wait = [&](const int rs) __attribute__((always_inline)) { wg_raw_wait<2 * NI>(raw[rs]); };  // the two younger sets may still be in flight
   auto stage = [&](const int rs, const unsigned bufoff) __attribute__((always_inline)) {
 #pragma unroll
     for (int it = 0; it < NI; ++it) {
@@ -535,11 +446,7 @@ __global__ __launch_bounds__(512, 1) void conv1x1_wgrad_staged_kernel(
         qa[p] = *reinterpret_cast<const u32x4*>(lds + bufoff + lane_a + (unsigned)(p * APB) + (unsigned)(q * 32));
         qb[p] = *reinterpret_cast<const u32x4*>(lds + bufoff + lane_b + (unsigned)(p * XPB) + (unsigned)(q * 32));
       }
-#pragma unroll
-      for (int ord = SPLIT - 1; ord >= 0; --ord)
-#pragma unroll
-        for (int sa = 0; sa <= ord; ++sa)
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, qa[sa]), __builtin_bit_cast(bf16x8, qb[ord - sa]), acc, 0, 0, 0);
+      wg_mfma_pieces<SPLIT>(acc, qa, qb);
     }
   };
 #pragma unroll 1
@@ -556,26 +463,21 @@ __global__ __launch_bounds__(512, 1) void conv1x1_wgrad_staged_kernel(
 
   if (part) {
     // one tile per wave, accumulator order: float4 number (wave * 4 + r / 4) * 64 + lane of this workgroup's set (2048 atomic
-    // adders per address took 9-27 us of a 41 us launch; wgrad_reduce_partials1x1_kernel sums the sets behind this kernel)
+    // adders per address took 9-27 us of a 41 us launch; wgrad_reduce_batch_kernel sums the sets behind this kernel)
     float4* const ps = reinterpret_cast<float4*>(part) + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (kWg1x1SetFloats / 4) + (size_t)wave * 256 + lane;
-#pragma unroll
-    for (int gq = 0; gq < 4; ++gq) ps[gq * 64] = make_float4(acc[4 * gq], acc[4 * gq + 1], acc[4 * gq + 2], acc[4 * gq + 3]);
+    wg_store_tile(ps, acc);
   } else {
     const int ci = tci * 32 + il;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int row = cob + tco * 32 + (r & 3) + 8 * (r >> 2) + 4 * kl;
+      const int row = wg_tile_row(r, kl, cob + tco * 32);
       atomicAdd(&dwp[(size_t)row * g.Cpad + ci], acc[r]);
     }
   }
   if (dbias != nullptr) {
 #pragma unroll
     for (int j = 0; j < AI; ++j) {  // the 16 lanes of a DPP row share a channel
-      float v = bsum[j];
-      v += dpp_move<0xB1, 0xF>(0.f, v);
-      v += dpp_move<0x4E, 0xF>(0.f, v);
-      v += dpp_move<0x141, 0xF>(0.f, v);
-      v += dpp_move<0x140, 0xF>(0.f, v);
+      const float v = wg_row16_sum(bsum[j]);
       if ((tid & 15) == 0) {
         const int ch = (tid >> 4) + j * 32;
         if (part) part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kWg1x1SetFloats + 8 * 1024 + ch] = v;
@@ -589,62 +491,23 @@ __global__ __launch_bounds__(512, 1) void conv1x1_wgrad_staged_kernel(
   }
 }
 
-// Partial tiles of conv1x1_wgrad_staged_kernel (part [cogroups][S][8 waves][256] float4, accumulator order) into dwp; a
-// workgroup's waves w and w + NTILE hold the same tile (k-halves), so the kernel sums 8 / NTILE x S slices per tile.
+// Partial tiles of conv1x1_wgrad_staged_kernel and conv1x1_bwd_fused_body (a set = [8 waves][256] float4, accumulator order,
+// then 64 bias sums); a workgroup's waves w and w + NTILE hold the same tile (k-halves): 8 / NTILE x S slices per tile.
 template <int C>
-__device__ __forceinline__ void wgrad_reduce_partials1x1_body(const float4* __restrict__ part, const int S, const int cpad,
-                                                                       float* __restrict__ dwp, float* __restrict__ dbias, const int bx, const int by) {
-  constexpr int NTILE = 2 * (C / 32), KS = 8 / NTILE, TILE4 = 256, SET4 = kWg1x1SetFloats / 4;
-  constexpr int NL = 32, NG = 8;  // 32 float4 columns (512 bytes of a slice) x 8 slice groups per workgroup
-  __shared__ float4 red[NG][NL];
-  const int li = threadIdx.x & (NL - 1), sg = threadIdx.x / NL;
-  const int f = bx * NL + li;  // float4 of the NTILE tiles; host: grid.x * 32 == NTILE * 256 (+ 32: the bias block, 16 float4 in use)
-  const bool bias = f >= NTILE * TILE4;  // block-uniform
-  const int tile = f / TILE4, ft = f - tile * TILE4;
-  const float4* const p = part + (size_t)by * S * SET4 + (bias ? (size_t)(8 * TILE4 + (f - NTILE * TILE4 < 16 ? f - NTILE * TILE4 : 15)) : (size_t)tile * TILE4 + ft);
-  float4 acc4[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) acc4[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-  const int ks = bias ? 1 : KS;
-  const int slices = S * ks;  // slice i = (workgroup i / ks, k-half i % ks)
-  int i = sg;
-  for (; i + 3 * NG < slices; i += 4 * NG) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int ii = i + NG * u;
-      const float4 v = p[(size_t)(ii / ks) * SET4 + (size_t)(ii % ks) * (NTILE * TILE4)];
-      acc4[u].x += v.x; acc4[u].y += v.y; acc4[u].z += v.z; acc4[u].w += v.w;
-    }
+struct WgRed1x1 {
+  static constexpr int NTILE = 2 * (C / 32), TILE4 = 256;
+  static constexpr int NL = 32, NG = 8, U = 4, KS = 8 / NTILE, SET4 = kWg1x1SetFloats / 4;  // host: grid.x * 32 == NTILE * 256 (+ 32)
+  static __device__ __forceinline__ WgRedCol column(const int f, const int by) {
+    const int fb = f - NTILE * TILE4;  // >= 0: the bias block, 16 float4 of it in use
+    return {(size_t)(fb >= 0 ? 8 * TILE4 + fb : f), NTILE * TILE4, fb >= 0 ? by * 64 + 4 * fb : -1, fb >= 16};
   }
-  for (; i < slices; i += NG) {
-    const float4 v = p[(size_t)(i / ks) * SET4 + (size_t)(i % ks) * (NTILE * TILE4)];
-    acc4[0].x += v.x; acc4[0].y += v.y; acc4[0].z += v.z; acc4[0].w += v.w;
-  }
-  red[sg][li] = make_float4((acc4[0].x + acc4[1].x) + (acc4[2].x + acc4[3].x), (acc4[0].y + acc4[1].y) + (acc4[2].y + acc4[3].y),
-                            (acc4[0].z + acc4[1].z) + (acc4[2].z + acc4[3].z), (acc4[0].w + acc4[1].w) + (acc4[2].w + acc4[3].w));
-  __syncthreads();
-  if (sg == 0) {
-    float4 v = red[0][li];
-#pragma unroll
-    for (int k = 1; k < NG; ++k) { v.x += red[k][li].x; v.y += red[k][li].y; v.z += red[k][li].z; v.w += red[k][li].w; }
-    if (bias) {
-      if (f - NTILE * TILE4 < 16) {
-        float* const o = dbias + by * 64 + 4 * (f - NTILE * TILE4);
-        o[0] += v.x; o[1] += v.y; o[2] += v.z; o[3] += v.w;
-      }
-      return;
-    }
+  static __device__ __forceinline__ void scatter(const int f, const int by, const float4 v, const int cpad, float* __restrict__ dwp) {
+    const int tile = f / TILE4, ft = f - tile * TILE4;
     const int lane = ft & 63, gq = ft >> 6, il = lane & 31, kl = lane >> 5;
     const int tco = tile & 1, tci = tile >> 1;
-    float* const o = dwp + (size_t)(by * 64 + tco * 32 + 8 * gq + 4 * kl) * cpad + tci * 32 + il;
-    o[0] += v.x; o[cpad] += v.y; o[2 * (size_t)cpad] += v.z; o[3 * (size_t)cpad] += v.w;
+    wg_red_add_rows(dwp + (size_t)(by * 64 + tco * 32 + 8 * gq + 4 * kl) * cpad + tci * 32 + il, (size_t)cpad, v);
   }
-}
-template <int C>
-__global__ __launch_bounds__(256) void wgrad_reduce_partials1x1_kernel(const float4* __restrict__ part, const int S, const int cpad,
-                                                                       float* __restrict__ dwp, float* __restrict__ dbias) {
-  wgrad_reduce_partials1x1_body<C>(part, S, cpad, dwp, dbias, (int)blockIdx.x, (int)blockIdx.y);
-}
+};
 
 // ------------------------------------------------------------------------------------------------
 // The WHOLE backward of a residual block's 1x1 layer (C = 128 or 64 mid channels -> 64, 64-pixel planes, two bf16 pieces) in
@@ -720,17 +583,8 @@ __device__ __forceinline__ void conv1x1_bwd_fused_body(
 #pragma unroll
   for (int j = 0; j < AI; ++j) bsum[j] = 0.f;
   wg_f32x4 raw[3][NI];  // [set][a items, x items]
-  auto raw_load = [&](const int rs, const int n) __attribute__((always_inline)) {
-#pragma unroll
-    for (int it = 0; it < NI; ++it) {
-      const float4* const ptr = it < AI ? asrc + (size_t)n * afr + NT * it : xsrc + (size_t)n * xfr + NT * (it - AI);
-      asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(raw[rs][it]) : "v"(ptr));
-    }
-  };
-  auto raw_wait = [&](const int rs) __attribute__((always_inline)) {  // loads behind this set: 2 raw sets + 2 act' sets
-    if constexpr (NI == 4) asm volatile("s_waitcnt vmcnt(40)" : "+v"(raw[rs][0]), "+v"(raw[rs][1]), "+v"(raw[rs][2]), "+v"(raw[rs][3]));
-    else asm volatile("s_waitcnt vmcnt(44)" : "+v"(raw[rs][0]), "+v"(raw[rs][1]), "+v"(raw[rs][2]), "+v"(raw[rs][3]), "+v"(raw[rs][4]), "+v"(raw[rs][5]));
-  };
+  auto raw_load = [&](const int rs, const int n) __attribute__((always_inline)) { wg_raw_load<NT, AI, XI>(raw[rs], asrc, afr, xsrc, xfr, n); };
+  auto raw_wait = [&](const int rs) __attribute__((always_inline)) { wg_raw_wait<2 * NI + 2 * 16>(raw[rs]); };  // loads behind this set: 2 raw sets + 2 act' sets
   // act' operand: h in accumulator layout (row (r & 3) + 8 (r >> 2) + 4 kl of the wave's channel tile, this lane's pixel)
   const float* const hop = src + (size_t)(bct * 32 + 4 * kl) * 64 + bhalf * 32 + il;
   float* const ghp = gh + (size_t)(bct * 32 + 4 * kl) * 64 + bhalf * 32 + il;
@@ -745,8 +599,7 @@ __device__ __forceinline__ void conv1x1_bwd_fused_body(
   auto op_wait = [&](const int os) __attribute__((always_inline)) {  // loads behind this set: 2 raw sets + 1 act' set
 #define MTRSSM_OPV(os_, b_) "+v"(opv[os_][b_]), "+v"(opv[os_][b_ + 1]), "+v"(opv[os_][b_ + 2]), "+v"(opv[os_][b_ + 3]), "+v"(opv[os_][b_ + 4]), \
                             "+v"(opv[os_][b_ + 5]), "+v"(opv[os_][b_ + 6]), "+v"(opv[os_][b_ + 7])
-    if constexpr (NI == 4) asm volatile("s_waitcnt vmcnt(24)" : MTRSSM_OPV(os, 0));
-    else asm volatile("s_waitcnt vmcnt(28)" : MTRSSM_OPV(os, 0));
+    asm volatile("s_waitcnt vmcnt(%8)" : MTRSSM_OPV(os, 0) : "n"(2 * NI + 16));
     asm volatile("" : MTRSSM_OPV(os, 8));  // (volatile: stays behind the wait)
 #undef MTRSSM_OPV
   };
@@ -805,11 +658,7 @@ __device__ __forceinline__ void conv1x1_bwd_fused_body(
         qa[p] = *reinterpret_cast<const u32x4*>(lds + bufoff + lane_a + (unsigned)(p * APB) + (unsigned)(q * 32));
         qb[p] = *reinterpret_cast<const u32x4*>(lds + bufoff + lane_b + (unsigned)(p * XPB) + (unsigned)(q * 32));
       }
-#pragma unroll
-      for (int ord = SPLIT - 1; ord >= 0; --ord)
-#pragma unroll
-        for (int sa = 0; sa <= ord; ++sa)
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, qa[sa]), __builtin_bit_cast(bf16x8, qb[ord - sa]), acc, 0, 0, 0);
+      wg_mfma_pieces<SPLIT>(acc, qa, qb);
     }
     // backward-data: 4 k-blocks of 16 output channels x 3 products
     f32x16 accb;
@@ -846,10 +695,9 @@ __device__ __forceinline__ void conv1x1_bwd_fused_body(
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the clamped requests of the last frames
 
-  if (part) {  // the partial set of conv1x1_wgrad_staged_kernel: wgrad_reduce_partials1x1_body sums it
+  if (part) {  // the partial set of conv1x1_wgrad_staged_kernel: layout WgRed1x1 of the reduce
     float4* const ps = reinterpret_cast<float4*>(part) + (size_t)bx * (kWg1x1SetFloats / 4) + (size_t)wave * 256 + lane;
-#pragma unroll
-    for (int gq = 0; gq < 4; ++gq) ps[gq * 64] = make_float4(acc[4 * gq], acc[4 * gq + 1], acc[4 * gq + 2], acc[4 * gq + 3]);
+    wg_store_tile(ps, acc);
   } else {
     const int ci = tci * 32 + il;
 #pragma unroll
@@ -861,11 +709,7 @@ __device__ __forceinline__ void conv1x1_bwd_fused_body(
   if (dbias != nullptr) {
 #pragma unroll
     for (int j = 0; j < AI; ++j) {  // the 16 lanes of a DPP row share a channel
-      float v = bsum[j];
-      v += dpp_move<0xB1, 0xF>(0.f, v);
-      v += dpp_move<0x4E, 0xF>(0.f, v);
-      v += dpp_move<0x141, 0xF>(0.f, v);
-      v += dpp_move<0x140, 0xF>(0.f, v);
+      const float v = wg_row16_sum(bsum[j]);
       if ((tid & 15) == 0) {
         const int ch = (tid >> 4) + j * 32;
         if (part) part[(size_t)bx * kWg1x1SetFloats + 8 * 1024 + ch] = v;
@@ -948,12 +792,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_wgrad_staged_kernel(
   const int nlast = n1 - 1;
 
   const bool act_elu = g.act == MTRSSM_ACT_ELU, act_relu = g.act == MTRSSM_ACT_RELU, pre = g.pre_act != 0;
-  auto act_sel = [&](float x) __attribute__((always_inline)) {
-    float e = __expf(x) - 1.f;
-    asm volatile("" : "+v"(e));  // computed unconditionally: the compiler would branch around the exponential
-    const float neg = act_elu ? e : (act_relu ? 0.f : x);
-    return (x > 0.f || !pre) ? x : neg;
-  };
+  const WgActSel act_sel{act_elu, act_relu, pre};
 
   // zero both buffers once: the halo rows are never written again
   for (int o = tid * 16; o < 2 * BUFB; o += NT * 16) *reinterpret_cast<uint4*>(lds + o) = make_uint4(0u, 0u, 0u, 0u);
@@ -967,17 +806,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_wgrad_staged_kernel(
 #pragma unroll
   for (int j = 0; j < AI; ++j) bsum[j] = 0.f;
   wg_f32x4 raw[3][NI];  // [set][a items, src items]
-  auto raw_load = [&](const int rs, const int n) __attribute__((always_inline)) {
-#pragma unroll
-    for (int it = 0; it < NI; ++it) {
-      const float4* const ptr = it < AI ? asrc + (size_t)n * afr + NT * it : xsrc + (size_t)n * xfr + NT * (it - AI);
-      asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(raw[rs][it]) : "v"(ptr));
-    }
-  };
-  auto raw_wait = [&](const int rs) __attribute__((always_inline)) {  // the two younger sets may still be in flight
-    static_assert(NI == 6, "six items");
-    asm volatile("s_waitcnt vmcnt(12)" : "+v"(raw[rs][0]), "+v"(raw[rs][1]), "+v"(raw[rs][2]), "+v"(raw[rs][3]), "+v"(raw[rs][4]), "+v"(raw[rs][5]));
-  };
+  auto raw_load = [&](const int rs, const int n) __attribute__((always_inline)) { wg_raw_load<NT, AI, XI>(raw[rs], asrc, afr, xsrc, xfr, n); };
+  auto raw_wait = [&](const int rs) __attribute__((always_inline)) { wg_raw_wait<2 * NI>(raw[rs]); };  // the two younger sets may still be in flight
   auto stage = [&](const int rs, const unsigned bufoff) __attribute__((always_inline)) {
 #pragma unroll
     for (int it = 0; it < NI; ++it) {
@@ -1043,7 +873,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_wgrad_staged_kernel(
           // row's first half (WO = 16, second half) or the zero left of the row
           unsigned prev = 0u;
           if (WO == 16) prev = kl ? (unsigned)*reinterpret_cast<const unsigned short*>(lds + bo - 2) : 0u;
-          const u32x4 sh = u32x4{(f.x << 16) | prev, __builtin_amdgcn_alignbit(f.y, f.x, 16), __builtin_amdgcn_alignbit(f.z, f.y, 16), __builtin_amdgcn_alignbit(f.w, f.z, 16)};
+          const u32x4 sh = wg_shift_in_front(f, prev);
           qb[p] = shifted ? sh : f;
         }
 #pragma unroll
@@ -1081,7 +911,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_wgrad_staged_kernel(
     if (ct < 3 && col < 72) {
 #pragma unroll
       for (int r = 0; r < 8; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * kl;
+        const int row = wg_tile_row(r, kl);
         atomicAdd(&dwp[((size_t)row * 9 + tap) * g.Cpad + ci], acc[r]);
       }
     }
@@ -1095,62 +925,19 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_wgrad_staged_kernel(
   }
 }
 
-// Partial sets of conv3x3s2_wgrad_staged_kernel into dwp / dbias: 72 columns x 16 rows, two k-halves per workgroup.
-__device__ __forceinline__ void wgrad_reduce_partials_s2_body(const float4* __restrict__ part, const int S, const int cpad,
-                                                                       float* __restrict__ dwp, float* __restrict__ dbias, const int bx, const int by) {
-  constexpr int SET4 = kWgS2SetFloats / 4, NL = 8, NG = 32;
-  __shared__ float4 red[NG][NL];
-  const int li = threadIdx.x & (NL - 1), sg = threadIdx.x / NL;
-  const int f = bx * NL + li;  // float4 (ct * 2 + half) * 64 + lane of the three column tiles: 384 of them, then 4 bias float4
-  const bool bias = f >= 384;          // block-uniform (48 tile blocks, then one bias block of which 4 columns are used)
-  if (bias && f >= 388) {              // padding columns of the bias block: nothing to read
-    red[sg][li] = make_float4(0.f, 0.f, 0.f, 0.f);
+// Partial sets of conv3x3s2_wgrad_staged_kernel: 72 columns x 16 rows, two k-halves per workgroup (waves ct and ct + 4).
+// float4 f = (ct * 2 + half) * 64 + lane of the three column tiles: 384 (48 blocks), then 4 bias float4.
+struct WgRedS2 {
+  static constexpr int NL = 8, NG = 32, U = 2, KS = 2, SET4 = kWgS2SetFloats / 4;
+  static __device__ __forceinline__ WgRedCol column(const int f, const int by) {
+    return {(size_t)(f >= 384 ? 8 * 128 + (f - 384) : f), 4 * 128, f >= 384 ? 4 * (f - 384) : -1, f >= 388};
   }
-  const int ct = f >> 7, rem = f & 127;
-  float4 acc4[2];
-  acc4[0] = acc4[1] = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (!(bias && f >= 388)) {
-    const int ks = bias ? 1 : 2;
-    const int slices = S * ks;  // slice i = (workgroup i / ks, k-half i % ks): waves ct and ct + 4
-    const float4* const p = part + (bias ? (size_t)(8 * 128 + (f - 384)) : (size_t)ct * 128 + rem);
-    int i = sg;
-    for (; i + NG < slices; i += 2 * NG) {
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int ii = i + NG * u;
-        const float4 v = p[(size_t)(ii / ks) * SET4 + (size_t)(ii % ks) * (4 * 128)];
-        acc4[u].x += v.x; acc4[u].y += v.y; acc4[u].z += v.z; acc4[u].w += v.w;
-      }
-    }
-    for (; i < slices; i += NG) {
-      const float4 v = p[(size_t)(i / ks) * SET4 + (size_t)(i % ks) * (4 * 128)];
-      acc4[0].x += v.x; acc4[0].y += v.y; acc4[0].z += v.z; acc4[0].w += v.w;
-    }
-    red[sg][li] = make_float4(acc4[0].x + acc4[1].x, acc4[0].y + acc4[1].y, acc4[0].z + acc4[1].z, acc4[0].w + acc4[1].w);
-  }
-  __syncthreads();
-  if (sg == 0) {
-    float4 v = red[0][li];
-#pragma unroll
-    for (int k = 1; k < NG; ++k) { v.x += red[k][li].x; v.y += red[k][li].y; v.z += red[k][li].z; v.w += red[k][li].w; }
-    if (bias) {
-      if (f < 388) { float* const o = dbias + 4 * (f - 384); o[0] += v.x; o[1] += v.y; o[2] += v.z; o[3] += v.w; }
-      return;
-    }
-    const int half = rem >> 6, lane = rem & 63, il = lane & 31, kl = lane >> 5;
+  static __device__ __forceinline__ void scatter(const int f, const int by, const float4 v, const int cpad, float* __restrict__ dwp) {
+    const int ct = f >> 7, rem = f & 127, half = rem >> 6, lane = rem & 63, il = lane & 31, kl = lane >> 5;
     const int col = ct * 32 + il;
-    if (col < 72) {
-      const int tap = col >> 3, ci = col & 7, row = 8 * half + 4 * kl;
-      float* const o = dwp + ((size_t)row * 9 + tap) * cpad + ci;
-      const size_t rs = (size_t)9 * cpad;
-      o[0] += v.x; o[rs] += v.y; o[2 * rs] += v.z; o[3 * rs] += v.w;
-    }
+    if (col < 72) wg_red_add_rows(dwp + ((size_t)(8 * half + 4 * kl) * 9 + (col >> 3)) * cpad + (col & 7), (size_t)9 * cpad, v);
   }
-}
-__global__ __launch_bounds__(256) void wgrad_reduce_partials_s2_kernel(const float4* __restrict__ part, const int S, const int cpad,
-                                                                       float* __restrict__ dwp, float* __restrict__ dbias) {
-  wgrad_reduce_partials_s2_body(part, S, cpad, dwp, dbias, (int)blockIdx.x, (int)blockIdx.y);
-}
+};
 
 // ------------------------------------------------------------------------------------------------
 // Weight gradient of the decoders' second ConvTranspose2d (k = 4, stride 2, pad 1, 32 -> 16 channels; input planes of 256
@@ -1195,12 +982,7 @@ __global__ __launch_bounds__(512, 1) void convt4s2_wgrad_staged_kernel(
   const int nlast = n1 - 1;
 
   const bool act_elu = g.act == MTRSSM_ACT_ELU, act_relu = g.act == MTRSSM_ACT_RELU, pre = pre_act_a != 0;
-  auto act_sel = [&](float x) __attribute__((always_inline)) {
-    float e = __expf(x) - 1.f;
-    asm volatile("" : "+v"(e));  // computed unconditionally: the compiler would branch around the exponential
-    const float neg = act_elu ? e : (act_relu ? 0.f : x);
-    return (x > 0.f || !pre) ? x : neg;
-  };
+  const WgActSel act_sel{act_elu, act_relu, pre};
 
   // zero the buffer once: the halo rows are never written again
   for (int o = tid * 16; o < wgt4_lds_bytes<SPLIT, WO>(); o += NT * 16) *reinterpret_cast<uint4*>(lds + o) = make_uint4(0u, 0u, 0u, 0u);
@@ -1213,18 +995,8 @@ __global__ __launch_bounds__(512, 1) void convt4s2_wgrad_staged_kernel(
 #pragma unroll
   for (int j = 0; j < XI; ++j) bsum[j] = 0.f;
   wg_f32x4 raw[3][NI];  // [set][a items, src items]
-  auto raw_load = [&](const int rs, const int n) __attribute__((always_inline)) {
-#pragma unroll
-    for (int it = 0; it < NI; ++it) {
-      const float4* const ptr = it < AI ? asrc + (size_t)n * afr + NT * it : xsrc + (size_t)n * xfr + NT * (it - AI);
-      asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(raw[rs][it]) : "v"(ptr));
-    }
-  };
-  auto raw_wait = [&](const int rs) __attribute__((always_inline)) {  // the two younger sets may still be in flight
-    static_assert(NI == 12, "twelve items");
-    asm volatile("s_waitcnt vmcnt(24)" : "+v"(raw[rs][0]), "+v"(raw[rs][1]), "+v"(raw[rs][2]), "+v"(raw[rs][3]), "+v"(raw[rs][4]), "+v"(raw[rs][5]),
-                 "+v"(raw[rs][6]), "+v"(raw[rs][7]), "+v"(raw[rs][8]), "+v"(raw[rs][9]), "+v"(raw[rs][10]), "+v"(raw[rs][11]));
-  };
+  auto raw_load = [&](const int rs, const int n) __attribute__((always_inline)) { wg_raw_load<NT, AI, XI>(raw[rs], asrc, afr, xsrc, xfr, n); };
+  auto raw_wait = [&](const int rs) __attribute__((always_inline)) { wg_raw_wait<2 * NI>(raw[rs]); };  // the two younger sets may still be in flight
   auto stage = [&](const int rs) __attribute__((always_inline)) {
 #pragma unroll
     for (int it = 0; it < NI; ++it) {
@@ -1292,11 +1064,7 @@ __global__ __launch_bounds__(512, 1) void convt4s2_wgrad_staged_kernel(
         const u32x4 shl = u32x4{__builtin_amdgcn_alignbit(f.y, f.x, 16), __builtin_amdgcn_alignbit(f.z, f.y, 16), __builtin_amdgcn_alignbit(f.w, f.z, 16), (f.w >> 16) | (next << 16)};
         qb[p] = kx == 0 ? shr : (kx == 3 ? shl : f);
       }
-#pragma unroll
-      for (int ord = SPLIT - 1; ord >= 0; --ord)
-#pragma unroll
-        for (int sa = 0; sa <= ord; ++sa)
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, qa[sa]), __builtin_bit_cast(bf16x8, qb[ord - sa]), acc, 0, 0, 0);
+      wg_mfma_pieces<SPLIT>(acc, qa, qb);
     }
   };
 #pragma unroll 1
@@ -1319,12 +1087,11 @@ __global__ __launch_bounds__(512, 1) void convt4s2_wgrad_staged_kernel(
   }
   if (part) {
     float4* const ps = reinterpret_cast<float4*>(part) + (size_t)blockIdx.x * (kWgT4SetFloats / 4) + (size_t)wave * 256 + lane;
-#pragma unroll
-    for (int gq = 0; gq < 4; ++gq) ps[gq * 64] = make_float4(acc[4 * gq], acc[4 * gq + 1], acc[4 * gq + 2], acc[4 * gq + 3]);
+    wg_store_tile(ps, acc);
   } else {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int row = (r & 3) + 8 * (r >> 2) + 4 * kl;
+      const int row = wg_tile_row(r, kl);
       atomicAdd(&dwp[((size_t)row * 16 + tap) * g.Cpad + co], acc[r]);
     }
   }
@@ -1336,51 +1103,19 @@ __global__ __launch_bounds__(512, 1) void convt4s2_wgrad_staged_kernel(
   }
 }
 
-// Partial sets of convt4s2_wgrad_staged_kernel into dwp / dbias (the sums of src).
-__device__ __forceinline__ void wgrad_reduce_partials_t4_body(const float4* __restrict__ part, const int S, const int cpad,
-                                                                       float* __restrict__ dwp, float* __restrict__ dbias, const int bx, const int by) {
-  constexpr int SET4 = kWgT4SetFloats / 4, TILE4 = kWgT4TileFloats / 4, NL = 8, NG = 32;
-  __shared__ float4 red[NG][NL];
-  const int li = threadIdx.x & (NL - 1), sg = threadIdx.x / NL;
-  const int f = bx * NL + li;  // host: grid.x * 8 == TILE4 (+ 8: the bias block, 4 float4 of it in use, launched when dbias != NULL)
-  const float4* const p = part + (f < SET4 ? f : SET4 - 1);
-  float4 acc4[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) acc4[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-  int s = sg;
-  for (; s + 3 * NG < S; s += 4 * NG) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const float4 v = p[(size_t)(s + NG * u) * SET4];
-      acc4[u].x += v.x; acc4[u].y += v.y; acc4[u].z += v.z; acc4[u].w += v.w;
-    }
+// Partial sets of convt4s2_wgrad_staged_kernel into dwp / dbias (the sums of src): float4 f = (wave * 4 + gq) * 64 + lane,
+// then 4 bias float4 (host: grid.x * 8 == TILE4, + 8).
+struct WgRedT4 {
+  static constexpr int NL = 8, NG = 32, U = 4, KS = 1, SET4 = kWgT4SetFloats / 4, TILE4 = kWgT4TileFloats / 4;
+  static __device__ __forceinline__ WgRedCol column(const int f, const int by) {
+    return {(size_t)f, 0, f >= TILE4 ? 4 * (f - TILE4) : -1, f >= SET4};
   }
-  for (; s < S; s += NG) {
-    const float4 v = p[(size_t)s * SET4];
-    acc4[0].x += v.x; acc4[0].y += v.y; acc4[0].z += v.z; acc4[0].w += v.w;
-  }
-  red[sg][li] = make_float4((acc4[0].x + acc4[1].x) + (acc4[2].x + acc4[3].x), (acc4[0].y + acc4[1].y) + (acc4[2].y + acc4[3].y),
-                            (acc4[0].z + acc4[1].z) + (acc4[2].z + acc4[3].z), (acc4[0].w + acc4[1].w) + (acc4[2].w + acc4[3].w));
-  __syncthreads();
-  if (sg == 0) {
-    float4 v = red[0][li];
-#pragma unroll
-    for (int k = 1; k < NG; ++k) { v.x += red[k][li].x; v.y += red[k][li].y; v.z += red[k][li].z; v.w += red[k][li].w; }
-    if (f >= TILE4) {  // block-uniform: the bias sums of channels 4 (f - TILE4) .. + 3
-      if (f < SET4) { float* const o = dbias + 4 * (f - TILE4); o[0] += v.x; o[1] += v.y; o[2] += v.z; o[3] += v.w; }
-      return;
-    }
+  static __device__ __forceinline__ void scatter(const int f, const int by, const float4 v, const int cpad, float* __restrict__ dwp) {
     const int lane = f & 63, gq = (f >> 6) & 3, wave = f >> 8, il = lane & 31, kl = lane >> 5;
     const int col = wave * 32 + il, tap = col >> 4, co = col & 15, row = 8 * gq + 4 * kl;
-    float* const o = dwp + ((size_t)row * 16 + tap) * cpad + co;
-    const size_t rs = (size_t)16 * cpad;
-    o[0] += v.x; o[rs] += v.y; o[2 * rs] += v.z; o[3 * rs] += v.w;
+    wg_red_add_rows(dwp + ((size_t)row * 16 + tap) * cpad + co, (size_t)16 * cpad, v);
   }
-}
-__global__ __launch_bounds__(256) void wgrad_reduce_partials_t4_kernel(const float4* __restrict__ part, const int S, const int cpad,
-                                                                       float* __restrict__ dwp, float* __restrict__ dbias) {
-  wgrad_reduce_partials_t4_body(part, S, cpad, dwp, dbias, (int)blockIdx.x, (int)blockIdx.y);
-}
+};
 
 // ------------------------------------------------------------------------------------------------
 // ... and of the decoders' FIRST ConvTranspose2d (k = 4, stride 2, pad 1, 64 -> 32 channels; input planes of 64 pixels: 8x8
@@ -1421,12 +1156,7 @@ __global__ __launch_bounds__(512, 1) void convt4s2b_wgrad_staged_kernel(
   const int nlast = n1 - 1;
 
   const bool act_elu = g.act == MTRSSM_ACT_ELU, act_relu = g.act == MTRSSM_ACT_RELU, pre = pre_act_a != 0;
-  auto act_sel = [&](float x) __attribute__((always_inline)) {
-    float e = __expf(x) - 1.f;
-    asm volatile("" : "+v"(e));  // computed unconditionally: the compiler would branch around the exponential
-    const float neg = act_elu ? e : (act_relu ? 0.f : x);
-    return (x > 0.f || !pre) ? x : neg;
-  };
+  const WgActSel act_sel{act_elu, act_relu, pre};
 
   for (int o = tid * 16; o < wgt4b_lds_bytes<SPLIT, WO>(); o += NT * 16) *reinterpret_cast<uint4*>(lds + o) = make_uint4(0u, 0u, 0u, 0u);
 
@@ -1438,17 +1168,8 @@ __global__ __launch_bounds__(512, 1) void convt4s2b_wgrad_staged_kernel(
 #pragma unroll
   for (int j = 0; j < XI; ++j) bsum[j] = 0.f;
   wg_f32x4 raw[3][NI];  // [set][a items, src items]
-  auto raw_load = [&](const int rs, const int n) __attribute__((always_inline)) {
-#pragma unroll
-    for (int it = 0; it < NI; ++it) {
-      const float4* const ptr = it < AI ? asrc + (size_t)n * afr + NT * it : xsrc + (size_t)n * xfr + NT * (it - AI);
-      asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(raw[rs][it]) : "v"(ptr));
-    }
-  };
-  auto raw_wait = [&](const int rs) __attribute__((always_inline)) {  // the two younger sets may still be in flight
-    static_assert(NI == 6, "six items");
-    asm volatile("s_waitcnt vmcnt(12)" : "+v"(raw[rs][0]), "+v"(raw[rs][1]), "+v"(raw[rs][2]), "+v"(raw[rs][3]), "+v"(raw[rs][4]), "+v"(raw[rs][5]));
-  };
+  auto raw_load = [&](const int rs, const int n) __attribute__((always_inline)) { wg_raw_load<NT, AI, XI>(raw[rs], asrc, afr, xsrc, xfr, n); };
+  auto raw_wait = [&](const int rs) __attribute__((always_inline)) { wg_raw_wait<2 * NI>(raw[rs]); };  // the two younger sets may still be in flight
   auto stage = [&](const int rs) __attribute__((always_inline)) {
 #pragma unroll
     for (int it = 0; it < NI; ++it) {
@@ -1490,13 +1211,9 @@ __global__ __launch_bounds__(512, 1) void convt4s2b_wgrad_staged_kernel(
   for (int t = 0; t < 4; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-  auto ab = [](const unsigned h, const unsigned l) __attribute__((always_inline)) { return __builtin_amdgcn_alignbit(h, l, 16); };
-  auto shr1 = [&](const u32x4 f) __attribute__((always_inline)) {  // element x <- x - 1, zero into every row's first element
-    return WO == 8 ? u32x4{f.x << 16, ab(f.y, f.x), ab(f.z, f.y), ab(f.w, f.z)} : u32x4{f.x << 16, ab(f.y, f.x), f.z << 16, ab(f.w, f.z)};
-  };
-  auto shl1 = [&](const u32x4 f) __attribute__((always_inline)) {  // element x <- x + 1, zero into every row's last element
-    return WO == 8 ? u32x4{ab(f.y, f.x), ab(f.z, f.y), ab(f.w, f.z), f.w >> 16} : u32x4{ab(f.y, f.x), f.y >> 16, ab(f.w, f.z), f.w >> 16};
-  };
+  constexpr int FR = WO == 8 ? 1 : 2;  // image rows per fragment
+  auto shr1 = [](const u32x4 f) __attribute__((always_inline)) { return wg_rows_shift_in_front<FR>(f); };  // element x <- x - 1
+  auto shl1 = [](const u32x4 f) __attribute__((always_inline)) { return wg_rows_shift_behind<FR>(f); };    // element x <- x + 1
   auto read_frag = [&](const unsigned off) __attribute__((always_inline)) {
     if (WO == 8) return *reinterpret_cast<const u32x4*>(lds + off);
     const uint2 r0 = *reinterpret_cast<const uint2*>(lds + off), r1 = *reinterpret_cast<const uint2*>(lds + off + 2 * ROWB);
@@ -1544,15 +1261,13 @@ __global__ __launch_bounds__(512, 1) void convt4s2b_wgrad_staged_kernel(
   if (part) {
     float4* const ps = reinterpret_cast<float4*>(part) + (size_t)blockIdx.x * (kWgT4bSetFloats / 4) + (size_t)wave * 1024 + lane;
 #pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int gq = 0; gq < 4; ++gq) ps[(t * 4 + gq) * 64] = make_float4(acc[t][4 * gq], acc[t][4 * gq + 1], acc[t][4 * gq + 2], acc[t][4 * gq + 3]);
+    for (int t = 0; t < 4; ++t) wg_store_tile(ps + t * 256, acc[t]);
   } else {
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = (t >> 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kl;
+        const int row = wg_tile_row(r, kl, (t >> 1) * 32);
         atomicAdd(&dwp[((size_t)row * 16 + 2 * wave + (t & 1)) * g.Cpad + il], acc[t][r]);
       }
   }
@@ -1568,52 +1283,19 @@ __global__ __launch_bounds__(512, 1) void convt4s2b_wgrad_staged_kernel(
   }
 }
 
-// Partial sets of convt4s2b_wgrad_staged_kernel into dwp / dbias (the sums of src).
-__device__ __forceinline__ void wgrad_reduce_partials_t4b_body(const float4* __restrict__ part, const int S, const int cpad,
-                                                                        float* __restrict__ dwp, float* __restrict__ dbias, const int bx, const int by) {
-  constexpr int SET4 = kWgT4bSetFloats / 4, TILE4 = kWgT4bTileFloats / 4, NL = 8, NG = 32;
-  __shared__ float4 red[NG][NL];
-  const int li = threadIdx.x & (NL - 1), sg = threadIdx.x / NL;
-  const int f = bx * NL + li;  // host: grid.x * 8 == TILE4 (+ 8: the bias block, launched when dbias != NULL)
-  const float4* const p = part + f;
-  float4 acc4[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) acc4[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-  int s = sg;
-  for (; s + 3 * NG < S; s += 4 * NG) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const float4 v = p[(size_t)(s + NG * u) * SET4];
-      acc4[u].x += v.x; acc4[u].y += v.y; acc4[u].z += v.z; acc4[u].w += v.w;
-    }
+// Partial sets of convt4s2b_wgrad_staged_kernel into dwp / dbias (the sums of src): float4 f = ((wave * 4 + t) * 4 + gq) * 64
+// + lane, then the bias block's 8 float4, all in use (host: grid.x * 8 == TILE4, + 8).
+struct WgRedT4b {
+  static constexpr int NL = 8, NG = 32, U = 4, KS = 1, SET4 = kWgT4bSetFloats / 4, TILE4 = kWgT4bTileFloats / 4;
+  static __device__ __forceinline__ WgRedCol column(const int f, const int by) {
+    return {(size_t)f, 0, f >= TILE4 ? 4 * (f - TILE4) : -1, false};
   }
-  for (; s < S; s += NG) {
-    const float4 v = p[(size_t)s * SET4];
-    acc4[0].x += v.x; acc4[0].y += v.y; acc4[0].z += v.z; acc4[0].w += v.w;
-  }
-  red[sg][li] = make_float4((acc4[0].x + acc4[1].x) + (acc4[2].x + acc4[3].x), (acc4[0].y + acc4[1].y) + (acc4[2].y + acc4[3].y),
-                            (acc4[0].z + acc4[1].z) + (acc4[2].z + acc4[3].z), (acc4[0].w + acc4[1].w) + (acc4[2].w + acc4[3].w));
-  __syncthreads();
-  if (sg == 0) {
-    float4 v = red[0][li];
-#pragma unroll
-    for (int k = 1; k < NG; ++k) { v.x += red[k][li].x; v.y += red[k][li].y; v.z += red[k][li].z; v.w += red[k][li].w; }
-    if (f >= TILE4) {  // block-uniform: the bias sums of channels 4 (f - TILE4) .. + 3
-      float* const o = dbias + 4 * (f - TILE4);
-      o[0] += v.x; o[1] += v.y; o[2] += v.z; o[3] += v.w;
-      return;
-    }
+  static __device__ __forceinline__ void scatter(const int f, const int by, const float4 v, const int cpad, float* __restrict__ dwp) {
     const int lane = f & 63, gq = (f >> 6) & 3, t = (f >> 8) & 3, wave = f >> 10, il = lane & 31, kl = lane >> 5;
     const int tap = 2 * wave + (t & 1), row = (t >> 1) * 32 + 8 * gq + 4 * kl;
-    float* const o = dwp + ((size_t)row * 16 + tap) * cpad + il;
-    const size_t rs = (size_t)16 * cpad;
-    o[0] += v.x; o[rs] += v.y; o[2 * rs] += v.z; o[3 * rs] += v.w;
+    wg_red_add_rows(dwp + ((size_t)row * 16 + tap) * cpad + il, (size_t)16 * cpad, v);
   }
-}
-__global__ __launch_bounds__(256) void wgrad_reduce_partials_t4b_kernel(const float4* __restrict__ part, const int S, const int cpad,
-                                                                        float* __restrict__ dwp, float* __restrict__ dbias) {
-  wgrad_reduce_partials_t4b_body(part, S, cpad, dwp, dbias, (int)blockIdx.x, (int)blockIdx.y);
-}
+};
 
 // ------------------------------------------------------------------------------------------------
 // Weight gradient of the FIRST encoder layer (3x3 / stride 2 / pad 1; one frame channel + two frame-independent
@@ -1653,12 +1335,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_thin_wgrad_staged_kernel(
   const int nlast = n1 - 1;
 
   const bool act_elu = g.act == MTRSSM_ACT_ELU, act_relu = g.act == MTRSSM_ACT_RELU, pre = g.pre_act != 0;
-  auto act_sel = [&](float x) __attribute__((always_inline)) {
-    float e = __expf(x) - 1.f;
-    asm volatile("" : "+v"(e));  // computed unconditionally: the compiler would branch around the exponential
-    const float neg = act_elu ? e : (act_relu ? 0.f : x);
-    return (x > 0.f || !pre) ? x : neg;
-  };
+  const WgActSel act_sel{act_elu, act_relu, pre};
 
   for (int o = tid * 16; o < wgthin_lds_bytes<SPLIT, WO>(); o += NT * 16) *reinterpret_cast<uint4*>(lds + o) = make_uint4(0u, 0u, 0u, 0u);
 
@@ -1683,17 +1360,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_thin_wgrad_staged_kernel(
 #pragma unroll
   for (int j = 0; j < AI; ++j) bsum[j] = 0.f;
   wg_f32x4 raw[3][NI];  // [set][a items, src items]
-  auto raw_load = [&](const int rs, const int n) __attribute__((always_inline)) {
-#pragma unroll
-    for (int it = 0; it < NI; ++it) {
-      const float4* const ptr = it < AI ? asrc + (size_t)n * afr + NT * it : xsrc + (size_t)n * xfr + NT * (it - AI);
-      asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(raw[rs][it]) : "v"(ptr));
-    }
-  };
-  auto raw_wait = [&](const int rs) __attribute__((always_inline)) {  // the two younger sets may still be in flight
-    static_assert(NI == 6, "six items");
-    asm volatile("s_waitcnt vmcnt(12)" : "+v"(raw[rs][0]), "+v"(raw[rs][1]), "+v"(raw[rs][2]), "+v"(raw[rs][3]), "+v"(raw[rs][4]), "+v"(raw[rs][5]));
-  };
+  auto raw_load = [&](const int rs, const int n) __attribute__((always_inline)) { wg_raw_load<NT, AI, XI>(raw[rs], asrc, afr, xsrc, xfr, n); };
+  auto raw_wait = [&](const int rs) __attribute__((always_inline)) { wg_raw_wait<2 * NI>(raw[rs]); };  // the two younger sets may still be in flight
   auto stage = [&](const int rs) __attribute__((always_inline)) {
 #pragma unroll
     for (int it = 0; it < NI; ++it) {
@@ -1750,7 +1418,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_thin_wgrad_staged_kernel(
         const unsigned bo = lane_b + (unsigned)(p * 2 * XCOPY) + soff;
         const u32x4 f = *reinterpret_cast<const u32x4*>(lds + bo);
         const unsigned prev = has_prev ? (unsigned)*reinterpret_cast<const unsigned short*>(lds + bo - 2) : 0u;
-        const u32x4 sh = u32x4{(f.x << 16) | prev, __builtin_amdgcn_alignbit(f.y, f.x, 16), __builtin_amdgcn_alignbit(f.z, f.y, 16), __builtin_amdgcn_alignbit(f.w, f.z, 16)};
+        const u32x4 sh = wg_shift_in_front(f, prev);
         qb[p] = shifted ? sh : f;
       }
 #pragma unroll
@@ -1798,57 +1466,18 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_thin_wgrad_staged_kernel(
   }
 }
 
-// Partial sets of conv3x3s2_thin_wgrad_staged_kernel into dwp / dbias: one tile, eight k-parts per workgroup.
-__device__ __forceinline__ void wgrad_reduce_partials_thin_body(const float4* __restrict__ part, const int S, const int cpad,
-                                                                         float* __restrict__ dwp, float* __restrict__ dbias, const int bx, const int by) {
-  constexpr int SET4 = kWgThinSetFloats / 4, NL = 8, NG = 32;
-  __shared__ float4 red[NG][NL];
-  const int li = threadIdx.x & (NL - 1), sg = threadIdx.x / NL;
-  const int f = bx * NL + li;  // lane's float4 (64 of them: 8 blocks), then the bias block (2 float4 used)
-  const bool bias = f >= 64;           // block-uniform
-  float4 acc4[2];
-  acc4[0] = acc4[1] = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (!(bias && f >= 66)) {
-    const int ks = bias ? 1 : 8;
-    const int slices = S * ks;  // slice i = (workgroup i / ks, wave i % ks)
-    const float4* const p = part + (bias ? (size_t)(8 * 64 + (f - 64)) : (size_t)f);
-    int i = sg;
-    for (; i + NG < slices; i += 2 * NG) {
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int ii = i + NG * u;
-        const float4 v = p[(size_t)(ii / ks) * SET4 + (size_t)(ii % ks) * 64];
-        acc4[u].x += v.x; acc4[u].y += v.y; acc4[u].z += v.z; acc4[u].w += v.w;
-      }
-    }
-    for (; i < slices; i += NG) {
-      const float4 v = p[(size_t)(i / ks) * SET4 + (size_t)(i % ks) * 64];
-      acc4[0].x += v.x; acc4[0].y += v.y; acc4[0].z += v.z; acc4[0].w += v.w;
-    }
+// Partial sets of conv3x3s2_thin_wgrad_staged_kernel: one tile, eight k-parts (waves) per workgroup.  float4 f = the lane's
+// (64 of them: 8 blocks), then the bias block (2 float4 in use).
+struct WgRedThin {
+  static constexpr int NL = 8, NG = 32, U = 2, KS = 8, SET4 = kWgThinSetFloats / 4;
+  static __device__ __forceinline__ WgRedCol column(const int f, const int by) {
+    return {(size_t)(f >= 64 ? 8 * 64 + (f - 64) : f), 64, f >= 64 ? 4 * (f - 64) : -1, f >= 66};
   }
-  red[sg][li] = make_float4(acc4[0].x + acc4[1].x, acc4[0].y + acc4[1].y, acc4[0].z + acc4[1].z, acc4[0].w + acc4[1].w);
-  __syncthreads();
-  if (sg == 0) {
-    float4 v = red[0][li];
-#pragma unroll
-    for (int k = 1; k < NG; ++k) { v.x += red[k][li].x; v.y += red[k][li].y; v.z += red[k][li].z; v.w += red[k][li].w; }
-    if (bias) {
-      if (f < 66) { float* const o = dbias + 4 * (f - 64); o[0] += v.x; o[1] += v.y; o[2] += v.z; o[3] += v.w; }
-      return;
-    }
-    const int il = f & 31, kl = f >> 5;
-    if (il < 27) {
-      const int tap = il / 3, ch = il - 3 * tap;
-      float* const o = dwp + ((size_t)(4 * kl) * 9 + tap) * cpad + ch;
-      const size_t rs = (size_t)9 * cpad;
-      o[0] += v.x; o[rs] += v.y; o[2 * rs] += v.z; o[3 * rs] += v.w;
-    }
+  static __device__ __forceinline__ void scatter(const int f, const int by, const float4 v, const int cpad, float* __restrict__ dwp) {
+    const int il = f & 31, kl = f >> 5, tap = il / 3, ch = il - 3 * tap;
+    if (il < 27) wg_red_add_rows(dwp + ((size_t)(4 * kl) * 9 + tap) * cpad + ch, (size_t)9 * cpad, v);
   }
-}
-__global__ __launch_bounds__(256) void wgrad_reduce_partials_thin_kernel(const float4* __restrict__ part, const int S, const int cpad,
-                                                                         float* __restrict__ dwp, float* __restrict__ dbias) {
-  wgrad_reduce_partials_thin_body(part, S, cpad, dwp, dbias, (int)blockIdx.x, (int)blockIdx.y);
-}
+};
 
 // ------------------------------------------------------------------------------------------------
 // Weight gradient of the decoders' LAST ConvTranspose2d (k = 4, stride 2, pad 1, 16 -> 1 channel; input planes of 1024
@@ -1885,12 +1514,7 @@ __global__ __launch_bounds__(512, 1) void convt4s2_thin_wgrad_staged_kernel(
   const int nlast = n1 - 1;
 
   const bool act_elu = g.act == MTRSSM_ACT_ELU, act_relu = g.act == MTRSSM_ACT_RELU, pre = pre_act_a != 0;
-  auto act_sel = [&](float x) __attribute__((always_inline)) {
-    float e = __expf(x) - 1.f;
-    asm volatile("" : "+v"(e));  // computed unconditionally: the compiler would branch around the exponential
-    const float neg = act_elu ? e : (act_relu ? 0.f : x);
-    return (x > 0.f || !pre) ? x : neg;
-  };
+  const WgActSel act_sel{act_elu, act_relu, pre};
 
   for (int o = tid * 16; o < wgthint_lds_bytes<SPLIT, WO>(); o += NT * 16) *reinterpret_cast<uint4*>(lds + o) = make_uint4(0u, 0u, 0u, 0u);
 
@@ -1899,18 +1523,8 @@ __global__ __launch_bounds__(512, 1) void convt4s2_thin_wgrad_staged_kernel(
   constexpr size_t xfr = (size_t)HS * WS / 4, afr = (size_t)CO * 1024 / 4;  // float4 per frame
   float bsum = 0.f;  // this thread's share of the one src channel
   wg_f32x4 raw[3][NI];  // [set][a items, src items]
-  auto raw_load = [&](const int rs, const int n) __attribute__((always_inline)) {
-#pragma unroll
-    for (int it = 0; it < NI; ++it) {
-      const float4* const ptr = it < AI ? asrc + (size_t)n * afr + NT * it : xsrc + (size_t)n * xfr + NT * (it - AI);
-      asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(raw[rs][it]) : "v"(ptr));
-    }
-  };
-  auto raw_wait = [&](const int rs) __attribute__((always_inline)) {  // the two younger sets may still be in flight
-    static_assert(NI == 10, "ten items");
-    asm volatile("s_waitcnt vmcnt(20)" : "+v"(raw[rs][0]), "+v"(raw[rs][1]), "+v"(raw[rs][2]), "+v"(raw[rs][3]), "+v"(raw[rs][4]), "+v"(raw[rs][5]),
-                 "+v"(raw[rs][6]), "+v"(raw[rs][7]), "+v"(raw[rs][8]), "+v"(raw[rs][9]));
-  };
+  auto raw_load = [&](const int rs, const int n) __attribute__((always_inline)) { wg_raw_load<NT, AI, XI>(raw[rs], asrc, afr, xsrc, xfr, n); };
+  auto raw_wait = [&](const int rs) __attribute__((always_inline)) { wg_raw_wait<2 * NI>(raw[rs]); };  // the two younger sets may still be in flight
   auto stage = [&](const int rs) __attribute__((always_inline)) {
 #pragma unroll
     for (int it = 0; it < NI; ++it) {
@@ -1975,11 +1589,7 @@ __global__ __launch_bounds__(512, 1) void convt4s2_thin_wgrad_staged_kernel(
         const u32x4 shl = u32x4{__builtin_amdgcn_alignbit(f.y, f.x, 16), __builtin_amdgcn_alignbit(f.z, f.y, 16), __builtin_amdgcn_alignbit(f.w, f.z, 16), (f.w >> 16) | (next << 16)};
         qb[p] = kx == 0 ? shr : (kx == 3 ? shl : f);
       }
-#pragma unroll
-      for (int ord = SPLIT - 1; ord >= 0; --ord)
-#pragma unroll
-        for (int sa = 0; sa <= ord; ++sa)
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, qa[sa]), __builtin_bit_cast(bf16x8, qb[ord - sa]), acc, 0, 0, 0);
+      wg_mfma_pieces<SPLIT>(acc, qa, qb);
     }
   };
 #pragma unroll 1
@@ -1996,7 +1606,7 @@ __global__ __launch_bounds__(512, 1) void convt4s2_thin_wgrad_staged_kernel(
     ps[64] = make_float4(acc[4], acc[5], acc[6], acc[7]);  // rows 8 + 4 kl + 0 .. 3
   } else if (il < 16) {
 #pragma unroll
-    for (int r = 0; r < 8; ++r) atomicAdd(&dwp[((size_t)((r & 3) + 8 * (r >> 2) + 4 * kl) * 16 + tap) * g.Cpad], acc[r]);
+    for (int r = 0; r < 8; ++r) atomicAdd(&dwp[((size_t)wg_tile_row(r, kl) * 16 + tap) * g.Cpad], acc[r]);
   }
   if (dsrcbias != nullptr) {
     const float v = wave_sum(bsum);
@@ -2007,62 +1617,31 @@ __global__ __launch_bounds__(512, 1) void convt4s2_thin_wgrad_staged_kernel(
   }
 }
 
-// Partial sets of convt4s2_thin_wgrad_staged_kernel into dwp: one tile, eight k-parts per workgroup; block 16 (launched when
-// dbias != NULL): the 8 S wave sums of src into dbias[0].
-__device__ __forceinline__ void wgrad_reduce_partials_thint_body(const float4* __restrict__ part, const int S, const int cpad,
-                                                                          float* __restrict__ dwp, float* __restrict__ dbias, const int bx, const int by) {
-  constexpr int SET4 = kWgThinTSetFloats / 4, NL = 8, NG = 32;
-  __shared__ float4 red[NG][NL];
-  const int li = threadIdx.x & (NL - 1), sg = threadIdx.x / NL;
-  if (bx >= 16) {  // block-uniform
-    const float* const pb = reinterpret_cast<const float*>(part) + kWgThinTTileFloats + li;  // wave li of every workgroup
-    float t = 0.f;
-    for (int s = sg; s < S; s += NG) t += pb[(size_t)s * kWgThinTSetFloats];
-    red[sg][li].x = t;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      float v = 0.f;
-      for (int k = 0; k < NG; ++k)
-        for (int w = 0; w < NL; ++w) v += red[k][w].x;
-      dbias[0] += v;
-    }
-    return;
-  }
-  const int f = bx * NL + li;  // half * 64 + lane: 128 of them (host: 16 blocks)
-  const float4* const p = part + f;
-  float4 acc4[2];
-  acc4[0] = acc4[1] = make_float4(0.f, 0.f, 0.f, 0.f);
-  const int slices = S * 8;  // slice i = (workgroup i / 8, wave i % 8)
-  int i = sg;
-  for (; i + NG < slices; i += 2 * NG) {
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int ii = i + NG * u;
-      const float4 v = p[(size_t)(ii >> 3) * SET4 + (size_t)(ii & 7) * 128];
-      acc4[u].x += v.x; acc4[u].y += v.y; acc4[u].z += v.z; acc4[u].w += v.w;
-    }
-  }
-  for (; i < slices; i += NG) {
-    const float4 v = p[(size_t)(i >> 3) * SET4 + (size_t)(i & 7) * 128];
-    acc4[0].x += v.x; acc4[0].y += v.y; acc4[0].z += v.z; acc4[0].w += v.w;
-  }
-  red[sg][li] = make_float4(acc4[0].x + acc4[1].x, acc4[0].y + acc4[1].y, acc4[0].z + acc4[1].z, acc4[0].w + acc4[1].w);
-  __syncthreads();
-  if (sg == 0) {
-    float4 v = red[0][li];
-#pragma unroll
-    for (int k = 1; k < NG; ++k) { v.x += red[k][li].x; v.y += red[k][li].y; v.z += red[k][li].z; v.w += red[k][li].w; }
+// Partial sets of convt4s2_thin_wgrad_staged_kernel into dwp: one tile, eight k-parts (waves) per workgroup; float4 f = half *
+// 64 + lane, 128 of them (host: 16 blocks).  Its bias is ONE word: block 16 (launched when dbias != NULL) is
+// wgrad_reduce_thint_bias below, not a column of this layout.
+struct WgRedThinT {
+  static constexpr int NL = 8, NG = 32, U = 2, KS = 8, SET4 = kWgThinTSetFloats / 4;
+  static __device__ __forceinline__ WgRedCol column(const int f, const int by) { return {(size_t)f, 128, -1, false}; }
+  static __device__ __forceinline__ void scatter(const int f, const int by, const float4 v, const int cpad, float* __restrict__ dwp) {
     const int half = f >> 6, lane = f & 63, il = lane & 31, kl = lane >> 5;
-    if (il < 16) {
-      float* const o = dwp + ((size_t)(8 * half + 4 * kl) * 16 + il) * cpad;
-      const size_t rs = (size_t)16 * cpad;
-      o[0] += v.x; o[rs] += v.y; o[2 * rs] += v.z; o[3 * rs] += v.w;
-    }
+    if (il < 16) wg_red_add_rows(dwp + ((size_t)(8 * half + 4 * kl) * 16 + il) * cpad, (size_t)16 * cpad, v);
   }
-}
-__global__ __launch_bounds__(256) void wgrad_reduce_partials_thint_kernel(const float4* __restrict__ part, const int S, const int cpad,
-                                                                          float* __restrict__ dwp, float* __restrict__ dbias) {
-  wgrad_reduce_partials_thint_body(part, S, cpad, dwp, dbias, (int)blockIdx.x, (int)blockIdx.y);
+};
+// the 8 S wave sums of src (one float per wave behind every set's tile) into dbias[0]
+__device__ __forceinline__ void wgrad_reduce_thint_bias(float4* const red /* [32][8] */, const float4* __restrict__ part, const int S, float* __restrict__ dbias) {
+  constexpr int NL = 8, NG = 32;
+  const int li = threadIdx.x & (NL - 1), sg = threadIdx.x / NL;
+  const float* const pb = reinterpret_cast<const float*>(part) + kWgThinTTileFloats + li;  // wave li of every workgroup
+  float t = 0.f;
+  for (int s = sg; s < S; s += NG) t += pb[(size_t)s * kWgThinTSetFloats];
+  red[sg * NL + li].x = t;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float v = 0.f;
+    for (int k = 0; k < NG * NL; ++k) v += red[k].x;
+    dbias[0] += v;
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2098,12 +1677,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2c_wgrad_staged_kernel(
   const int nlast = n1 - 1;
 
   const bool act_elu = g.act == MTRSSM_ACT_ELU, act_relu = g.act == MTRSSM_ACT_RELU, pre = g.pre_act != 0;
-  auto act_sel = [&](float x) __attribute__((always_inline)) {
-    float e = __expf(x) - 1.f;
-    asm volatile("" : "+v"(e));  // computed unconditionally: the compiler would branch around the exponential
-    const float neg = act_elu ? e : (act_relu ? 0.f : x);
-    return (x > 0.f || !pre) ? x : neg;
-  };
+  const WgActSel act_sel{act_elu, act_relu, pre};
 
   for (int o = tid * 16; o < wgs2c_lds_bytes<SPLIT>(); o += NT * 16) *reinterpret_cast<uint4*>(lds + o) = make_uint4(0u, 0u, 0u, 0u);
 
@@ -2112,17 +1686,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2c_wgrad_staged_kernel(
   constexpr size_t xfr = (size_t)C * HS * WS / 4, afr = (size_t)CO * 64 / 4;  // float4 per frame
   float bsum = 0.f;  // this thread's share of channel tid / 16
   wg_f32x4 raw[3][NI];  // [set][a item, src items]
-  auto raw_load = [&](const int rs, const int n) __attribute__((always_inline)) {
-#pragma unroll
-    for (int it = 0; it < NI; ++it) {
-      const float4* const ptr = it < AI ? asrc + (size_t)n * afr + NT * it : xsrc + (size_t)n * xfr + NT * (it - AI);
-      asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(raw[rs][it]) : "v"(ptr));
-    }
-  };
-  auto raw_wait = [&](const int rs) __attribute__((always_inline)) {  // the two younger sets may still be in flight
-    static_assert(NI == 3, "three items");
-    asm volatile("s_waitcnt vmcnt(6)" : "+v"(raw[rs][0]), "+v"(raw[rs][1]), "+v"(raw[rs][2]));
-  };
+  auto raw_load = [&](const int rs, const int n) __attribute__((always_inline)) { wg_raw_load<NT, AI, XI>(raw[rs], asrc, afr, xsrc, xfr, n); };
+  auto raw_wait = [&](const int rs) __attribute__((always_inline)) { wg_raw_wait<2 * NI>(raw[rs]); };  // the two younger sets may still be in flight
   auto stage = [&](const int rs) __attribute__((always_inline)) {
 #pragma unroll
     for (int it = 0; it < NI; ++it) {
@@ -2186,8 +1751,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2c_wgrad_staged_kernel(
             const uint2 r0 = *reinterpret_cast<const uint2*>(lds + bo), r1 = *reinterpret_cast<const uint2*>(lds + bo + 2 * ROWB);
             f = u32x4{r0.x, r0.y, r1.x, r1.y};
           }
-          const u32x4 sh = WO == 8 ? u32x4{f.x << 16, __builtin_amdgcn_alignbit(f.y, f.x, 16), __builtin_amdgcn_alignbit(f.z, f.y, 16), __builtin_amdgcn_alignbit(f.w, f.z, 16)}
-                                   : u32x4{f.x << 16, __builtin_amdgcn_alignbit(f.y, f.x, 16), f.z << 16, __builtin_amdgcn_alignbit(f.w, f.z, 16)};
+          const u32x4 sh = wg_rows_shift_in_front<WO == 8 ? 1 : 2>(f);
           qb[p] = shifted ? sh : f;
         }
 #pragma unroll
@@ -2206,77 +1770,35 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2c_wgrad_staged_kernel(
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the clamped requests of the last frames
 
-  float bv = bsum;  // the 16 lanes of a DPP row share channel tid / 16
-  bv += dpp_move<0xB1, 0xF>(0.f, bv);
-  bv += dpp_move<0x4E, 0xF>(0.f, bv);
-  bv += dpp_move<0x141, 0xF>(0.f, bv);
-  bv += dpp_move<0x140, 0xF>(0.f, bv);
+  const float bv = wg_row16_sum(bsum);  // the 16 lanes of a DPP row share channel tid / 16
   if (part) {
     float* const set = part + (size_t)blockIdx.x * kWgS2cSetFloats;
     if (wave < 5) {
       float4* const ps = reinterpret_cast<float4*>(set) + (size_t)wave * 256 + lane;
-#pragma unroll
-      for (int gq = 0; gq < 4; ++gq) ps[gq * 64] = make_float4(acc[4 * gq], acc[4 * gq + 1], acc[4 * gq + 2], acc[4 * gq + 3]);
+      wg_store_tile(ps, acc);
     }
     if (dbias != nullptr && (tid & 15) == 0) set[8 * 4 * 64 * 4 + (tid >> 4)] = bv;
   } else {
     if (wave < 5 && col < 144) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) atomicAdd(&dwp[((size_t)((r & 3) + 8 * (r >> 2) + 4 * kl) * 9 + tap) * g.Cpad + ci], acc[r]);
+      for (int r = 0; r < 16; ++r) atomicAdd(&dwp[((size_t)wg_tile_row(r, kl) * 9 + tap) * g.Cpad + ci], acc[r]);
     }
     if (dbias != nullptr && (tid & 15) == 0) atomicAdd(&dbias[tid >> 4], bv);
   }
 }
 
-// Partial sets of conv3x3s2c_wgrad_staged_kernel into dwp / dbias.
-__device__ __forceinline__ void wgrad_reduce_partials_s2c_body(const float4* __restrict__ part, const int S, const int cpad,
-                                                                        float* __restrict__ dwp, float* __restrict__ dbias, const int bx, const int by) {
-  constexpr int SET4 = kWgS2cSetFloats / 4, NL = 8, NG = 32;
-  __shared__ float4 red[NG][NL];
-  const int li = threadIdx.x & (NL - 1), sg = threadIdx.x / NL;
-  const int f = bx * NL + li;  // float4 of the five column tiles: 1280 (160 blocks), then 8 bias float4 (one block)
-  const bool bias = f >= 1280;         // block-uniform
-  const float4* const p = part + (bias ? (size_t)(8 * 256 + (f - 1280)) : (size_t)f);
-  float4 acc4[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) acc4[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-  int s = sg;
-  for (; s + 3 * NG < S; s += 4 * NG) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const float4 v = p[(size_t)(s + NG * u) * SET4];
-      acc4[u].x += v.x; acc4[u].y += v.y; acc4[u].z += v.z; acc4[u].w += v.w;
-    }
+// Partial sets of conv3x3s2c_wgrad_staged_kernel: float4 f = (wave * 4 + gq) * 64 + lane of the five column tiles: 1280 (160
+// blocks), then the bias block's 8 float4, all in use.
+struct WgRedS2c {
+  static constexpr int NL = 8, NG = 32, U = 4, KS = 1, SET4 = kWgS2cSetFloats / 4;
+  static __device__ __forceinline__ WgRedCol column(const int f, const int by) {
+    return {(size_t)(f >= 1280 ? 8 * 256 + (f - 1280) : f), 0, f >= 1280 ? 4 * (f - 1280) : -1, false};
   }
-  for (; s < S; s += NG) {
-    const float4 v = p[(size_t)s * SET4];
-    acc4[0].x += v.x; acc4[0].y += v.y; acc4[0].z += v.z; acc4[0].w += v.w;
-  }
-  red[sg][li] = make_float4((acc4[0].x + acc4[1].x) + (acc4[2].x + acc4[3].x), (acc4[0].y + acc4[1].y) + (acc4[2].y + acc4[3].y),
-                            (acc4[0].z + acc4[1].z) + (acc4[2].z + acc4[3].z), (acc4[0].w + acc4[1].w) + (acc4[2].w + acc4[3].w));
-  __syncthreads();
-  if (sg == 0) {
-    float4 v = red[0][li];
-#pragma unroll
-    for (int k = 1; k < NG; ++k) { v.x += red[k][li].x; v.y += red[k][li].y; v.z += red[k][li].z; v.w += red[k][li].w; }
-    if (bias) {
-      float* const o = dbias + 4 * (f - 1280);
-      o[0] += v.x; o[1] += v.y; o[2] += v.z; o[3] += v.w;
-      return;
-    }
+  static __device__ __forceinline__ void scatter(const int f, const int by, const float4 v, const int cpad, float* __restrict__ dwp) {
     const int lane = f & 63, gq = (f >> 6) & 3, wave = f >> 8, il = lane & 31, kl = lane >> 5;
-    const int col = wave * 32 + il;
-    if (col < 144) {
-      const int tap = col >> 4, ci = col & 15, row = 8 * gq + 4 * kl;
-      float* const o = dwp + ((size_t)row * 9 + tap) * cpad + ci;
-      const size_t rs = (size_t)9 * cpad;
-      o[0] += v.x; o[rs] += v.y; o[2 * rs] += v.z; o[3 * rs] += v.w;
-    }
+    const int col = wave * 32 + il, tap = col >> 4, ci = col & 15, row = 8 * gq + 4 * kl;
+    if (col < 144) wg_red_add_rows(dwp + ((size_t)row * 9 + tap) * cpad + ci, (size_t)9 * cpad, v);
   }
-}
-__global__ __launch_bounds__(256) void wgrad_reduce_partials_s2c_kernel(const float4* __restrict__ part, const int S, const int cpad,
-                                                                        float* __restrict__ dwp, float* __restrict__ dbias) {
-  wgrad_reduce_partials_s2c_body(part, S, cpad, dwp, dbias, (int)blockIdx.x, (int)blockIdx.y);
-}
+};
 
 }  // namespace mtrssm
