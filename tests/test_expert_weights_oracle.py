@@ -50,14 +50,9 @@ def seeded_gate(mode: str, embed: int) -> ExpertWeights:
     return gate
 
 
-def weighted_mrssm_step(m, batch, noise, codes: Tensor, lw_of) -> dict[str, Tensor]:  # noqa: ANN001
+def weighted_mrssm_rollout(m, act_in, audio_embed, vision_embed, deter, stoch, noise, codes: Tensor, lw) -> dict[str, Tensor]:  # noqa: ANN001, PLR0913
+    """The weighted and masked T loop from a given initial state: the rollout's outputs, each stacked over time."""
     d = m.dims
-    act_in, audio_in, vision_in, _, audio_tgt, vision_tgt = batch
-    audio_embed, vision_embed = m.audio_encoder(audio_in), m.vision_encoder(vision_in)
-    lw = lw_of(audio_embed, vision_embed)
-    deter = m.init_proj(masked_embed0(audio_embed[:, 0], vision_embed[:, 0], codes[:, 0]))
-    logits0 = m.transition.rnn_to_prior_projector(deter)
-    stoch = st_sample(cat_probs(logits0, d.cats, d.classes)[1], noise["u_init"])
     keep: dict[str, list[Tensor]] = {k: [] for k in ("deter", "prior_logits", "prior_stoch", "post_logits", "post_stoch")}
     for t in range(act_in.shape[1]):
         deter, prior_logits, prior_stoch = m._prior_step(act_in[:, t], deter, stoch, noise["u_prior"][:, t])  # noqa: SLF001
@@ -67,7 +62,18 @@ def weighted_mrssm_step(m, batch, noise, codes: Tensor, lw_of) -> dict[str, Tens
         stoch = st_sample(cat_probs(post_logits, d.cats, d.classes)[1], noise["u_post"][:, t])
         for k, v in zip(keep, (deter, prior_logits, prior_stoch, post_logits, stoch), strict=True):
             keep[k].append(v)
-    roll = {k: torch.stack(v, dim=1) for k, v in keep.items()}
+    return {k: torch.stack(v, dim=1) for k, v in keep.items()}
+
+
+def weighted_mrssm_step(m, batch, noise, codes: Tensor, lw_of) -> dict[str, Tensor]:  # noqa: ANN001
+    d = m.dims
+    act_in, audio_in, vision_in, _, audio_tgt, vision_tgt = batch
+    audio_embed, vision_embed = m.audio_encoder(audio_in), m.vision_encoder(vision_in)
+    lw = lw_of(audio_embed, vision_embed)
+    deter = m.init_proj(masked_embed0(audio_embed[:, 0], vision_embed[:, 0], codes[:, 0]))
+    logits0 = m.transition.rnn_to_prior_projector(deter)
+    stoch = st_sample(cat_probs(logits0, d.cats, d.classes)[1], noise["u_init"])
+    roll = weighted_mrssm_rollout(m, act_in, audio_embed, vision_embed, deter, stoch, noise, codes, lw)
     feature = torch.cat([roll["deter"], roll["post_stoch"]], dim=-1)
     mask = mask_of(codes)
     nll_a = masked_nll(m.audio_decoder(feature), audio_tgt, mask[..., 0])
@@ -79,17 +85,11 @@ def weighted_mrssm_step(m, batch, noise, codes: Tensor, lw_of) -> dict[str, Tens
     return out
 
 
-def weighted_mmtrssm_step(m, batch, noise, codes: Tensor, lw_of) -> dict[str, Tensor]:  # noqa: ANN001, PLR0914
+def weighted_mmtrssm_rollout(m, act_in, audio_embed, vision_embed, state0: dict[str, Tensor], noise, codes: Tensor, lw) -> dict[str, Tensor]:  # noqa: ANN001, PLR0913, PLR0914
+    """The weighted and masked T loop from a given initial state: the rollout's outputs, each stacked over time."""
     d = m.dims
-    act_in, audio_in, vision_in, _, audio_tgt, vision_tgt = batch
-    audio_embed, vision_embed = m.audio_encoder(audio_in), m.vision_encoder(vision_in)
-    lw = lw_of(audio_embed, vision_embed)
-    h = m.init_proj(masked_embed0(audio_embed[:, 0], vision_embed[:, 0], codes[:, 0]))
-    deter_h, deter_l = h[..., : d.hd], h[..., d.hd :]
-    hidden_h, hidden_l = deter_h, deter_l
-    init_h, init_l = m.h_prior(deter_h), m.l_prior(deter_l)
-    stoch_h = st_sample(cat_probs(init_h, d.hs_cats, d.hs_classes)[1], noise["u_init_h"])
-    stoch_l = st_sample(cat_probs(init_l, d.ls_cats, d.ls_classes)[1], noise["u_init_l"])
+    deter_l, deter_h, hidden_l, hidden_h = state0["deter_l"], state0["deter_h"], state0["hidden_l"], state0["hidden_h"]
+    stoch_l, stoch_h = state0["stoch_l"], state0["stoch_h"]
     names = ("deter_l", "deter_h", "hidden_l", "hidden_h", "prior_logits_l", "prior_logits_h", "prior_stoch_l", "prior_stoch_h",
              "post_logits_l", "post_logits_h", "post_stoch_l", "post_stoch_h")
     keep: dict[str, list[Tensor]] = {k: [] for k in names}
@@ -112,7 +112,22 @@ def weighted_mmtrssm_step(m, batch, noise, codes: Tensor, lw_of) -> dict[str, Te
                 post_logits_h, stoch_l, stoch_h)
         for k, v in zip(names, vals, strict=True):
             keep[k].append(v)
-    roll = {k: torch.stack(v, dim=1) for k, v in keep.items()}
+    return {k: torch.stack(v, dim=1) for k, v in keep.items()}
+
+
+def weighted_mmtrssm_step(m, batch, noise, codes: Tensor, lw_of) -> dict[str, Tensor]:  # noqa: ANN001, PLR0914
+    d = m.dims
+    act_in, audio_in, vision_in, _, audio_tgt, vision_tgt = batch
+    audio_embed, vision_embed = m.audio_encoder(audio_in), m.vision_encoder(vision_in)
+    lw = lw_of(audio_embed, vision_embed)
+    h = m.init_proj(masked_embed0(audio_embed[:, 0], vision_embed[:, 0], codes[:, 0]))
+    deter_h, deter_l = h[..., : d.hd], h[..., d.hd :]
+    hidden_h, hidden_l = deter_h, deter_l
+    init_h, init_l = m.h_prior(deter_h), m.l_prior(deter_l)
+    stoch_h = st_sample(cat_probs(init_h, d.hs_cats, d.hs_classes)[1], noise["u_init_h"])
+    stoch_l = st_sample(cat_probs(init_l, d.ls_cats, d.ls_classes)[1], noise["u_init_l"])
+    state0 = {"deter_l": deter_l, "deter_h": deter_h, "hidden_l": hidden_l, "hidden_h": hidden_h, "stoch_l": stoch_l, "stoch_h": stoch_h}
+    roll = weighted_mmtrssm_rollout(m, act_in, audio_embed, vision_embed, state0, noise, codes, lw)
     feature = torch.cat([roll["deter_h"], roll["post_stoch_h"], roll["deter_l"], roll["post_stoch_l"]], dim=-1)
     mask = mask_of(codes)
     nll_a = masked_nll(m.audio_decoder(feature), audio_tgt, mask[..., 0])
