@@ -25,6 +25,7 @@
 // reduction over all N*H*W pixels split across workgroups, partial tiles combined with fp32 atomics.
 #include <map>
 #include <mutex>
+#include <string>
 #include <unordered_map>
 #include <utility>
 
@@ -1456,13 +1457,62 @@ static GatherProblem make_problem(const MtrssmConvGeom* g, const SplitPlan& pl, 
   return p;
 }
 
+// One launch of conv3x3_resident_kernel (plan kind 3): which instantiation the launch's switches ask for.
+//   epi && pre   a pre-activated source WITH epilogue operands: a residual block whose second conv is 3x3 (conv.py runs it
+//                as a gather with the skip as add_in), any of the five shapes; the run-time-select body
+//   epi          backward-data (nothing activated while staging, act'(x) and / or the skip gradient as operands)
+//   !pre         a plain gather without activation: its kind never enters the kernel
+//   pre          the pre-activated forward
+// ELU instances (the activation's kind compiled in) exist where the default models run them: the backward-data direction of
+// ELU_BWD shapes, the forward of ELU_FWD shapes; everything else runs the run-time-select body.
+struct ResidentLaunch {
+  bool epi, pre, elu;
+  dim3 grid;
+  const GatherProblem& qa;
+  const GatherProblem& qb;
+  hipStream_t stream;
+
+  template <int CIN, int NCT, int KS, bool PRE, bool ELU, bool EPI>
+  int launch() const {
+    static const std::string name = [] {  // as rocprofv3 prints it: the whole argument list
+      char buf[96];
+      auto tf = [](bool b) { return b ? "true" : "false"; };
+      snprintf(buf, sizeof buf, "mtrssm::conv3x3_resident_kernel<%d, %d, %d, %s, %s, %s, false>", CIN, NCT, KS, tf(PRE), tf(ELU), tf(EPI));
+      return std::string(buf);
+    }();
+    const size_t lds = res_lds_bytes<CIN, NCT, KS>();
+    allow_lds<conv3x3_resident_kernel<CIN, NCT, KS, PRE, ELU, EPI, false>>((int)lds);
+    set_last_kernel(name.c_str());
+    hipLaunchKernelGGL((conv3x3_resident_kernel<CIN, NCT, KS, PRE, ELU, EPI, false>), grid, dim3(kResThreads), lds, stream, qa, qb);
+    return launched("conv_gather_gemm(resident)");
+  }
+  template <int CIN, int NCT, int KS, bool ELU_BWD, bool ELU_FWD>
+  int run() const {
+    if (epi && pre) return launch<CIN, NCT, KS, true, false, true>();
+    if (epi) {
+      if constexpr (ELU_BWD)
+        if (elu) return launch<CIN, NCT, KS, false, true, true>();
+      return launch<CIN, NCT, KS, false, false, true>();
+    }
+    if (!pre) return launch<CIN, NCT, KS, false, false, false>();
+    if constexpr (ELU_FWD)
+      if (elu) return launch<CIN, NCT, KS, true, true, false>();
+    return launch<CIN, NCT, KS, true, false, false>();
+  }
+};
+
 // launches pa (and pb when pb.nx > 0: same kernel, its workgroups appended to the grid)
 static int launch_split(const SplitPlan& pl, size_t lds, const GatherProblem& pa, const GatherProblem& pb, hipStream_t stream) {
   if (pl.kind == 3) {
     // persistent workgroups, one per CU; a pair shares the CUs in proportion to its frames (each workgroup keeps ONE
     // problem's weights in registers)
-    const bool epi_a = pa.actgrad_in || pa.add_in, epi_b = pb.actgrad_in || pb.add_in;  // template switch of the kernel
-    if (pb.nx > 0 && epi_a != epi_b) {
+    // template switches of the kernel: epilogue operands and pre-activation have to agree within a pair; the activation's
+    // kind is compiled in where every problem of the launch is ELU and the shape has such an instance (the run-time body
+    // takes each problem's own kind)
+    const bool epi_a = pa.actgrad_in || pa.add_in, epi_b = pb.actgrad_in || pb.add_in;
+    const bool pre_a = pa.g.pre_act != 0, pre_b = pb.g.pre_act != 0;
+    const bool elu = pa.g.act == MTRSSM_ACT_ELU && (pb.nx == 0 || pb.g.act == MTRSSM_ACT_ELU);
+    if (pb.nx > 0 && (epi_a != epi_b || pre_a != pre_b)) {
       GatherProblem none{};
       none.nx = 0;
       if (int rc = launch_split(pl, lds, pa, none, stream)) return rc;
@@ -1475,23 +1525,12 @@ static int launch_split(const SplitPlan& pl, size_t lds, const GatherProblem& pa
     qa.nx = wg.na;
     qb.nx = wg.nb;
     const dim3 rgrid((unsigned)(qa.nx + qb.nx));
-#define MTRSSM_RES_LAUNCH_E(CIN_, NCT_, KS_, EPI_)                                                                   \
-  {                                                                                                                   \
-    const size_t rl = res_lds_bytes<CIN_, NCT_, KS_>();                                                               \
-    allow_lds<conv3x3_resident_kernel<CIN_, NCT_, KS_, EPI_>>((int)rl);                                               \
-    set_last_kernel("mtrssm::conv3x3_resident_kernel<" #CIN_ ", " #NCT_ ", " #KS_ ", " #EPI_ ">");                      \
-    hipLaunchKernelGGL((conv3x3_resident_kernel<CIN_, NCT_, KS_, EPI_>), rgrid, dim3(kResThreads), rl, stream, qa, qb); \
-    return launched("conv_gather_gemm(resident)");                                                                    \
-  }
-#define MTRSSM_RES_LAUNCH(CIN_, NCT_, KS_) \
-  { if (epi_a) MTRSSM_RES_LAUNCH_E(CIN_, NCT_, KS_, true) else MTRSSM_RES_LAUNCH_E(CIN_, NCT_, KS_, false) }
-    if (pl.res == 64064) MTRSSM_RES_LAUNCH(64, 2, 1)
-    if (pl.res == 64128) MTRSSM_RES_LAUNCH(64, 4, 1)
-    if (pl.res == 128064) MTRSSM_RES_LAUNCH(128, 2, 2)
-    if (pl.res == 32064) MTRSSM_RES_LAUNCH(32, 2, 1)
-    if (pl.res == 64032) MTRSSM_RES_LAUNCH(64, 1, 2)   // the first stack conv's backward-data: 32 output channels, K split over wave pairs, two frames per tile
-#undef MTRSSM_RES_LAUNCH_E
-#undef MTRSSM_RES_LAUNCH
+    const ResidentLaunch rl{epi_a, pre_a, elu, rgrid, qa, qb, stream};
+    if (pl.res == 64064) return rl.run<64, 2, 1, true, false>();
+    if (pl.res == 64128) return rl.run<64, 4, 1, false, false>();
+    if (pl.res == 128064) return rl.run<128, 2, 2, true, false>();
+    if (pl.res == 32064) return rl.run<32, 2, 1, false, true>();   // the encoders' first stack conv
+    if (pl.res == 64032) return rl.run<64, 1, 2, true, false>();   // its backward-data: 32 output channels, K split over wave pairs, two frames per tile
     set_error("conv_gather_gemm: no resident kernel for this plan");
     return MTRSSM_EINVAL;
   }
@@ -1800,16 +1839,21 @@ static int residual_fwd_one_grid(const GatherProblem& pa, const GatherProblem& p
   qa.nx = wg.na;
   qb.nx = wg.nb;
   const dim3 rgrid((unsigned)(qa.nx + qb.nx));
-#define MTRSSM_FUSE_LAUNCH(NCT_)                                                                                        \
-  {                                                                                                                    \
-    const size_t rl = res_lds_bytes<64, NCT_, 1>() + res_fuse_bytes<64, NCT_>();                                       \
-    allow_lds<conv3x3_resident_kernel<64, NCT_, 1, false, true>>((int)rl);                                             \
-    set_last_kernel("mtrssm::conv3x3_resident_kernel<64, " #NCT_ ", 1, false, true>");                                  \
-    hipLaunchKernelGGL((conv3x3_resident_kernel<64, NCT_, 1, false, true>), rgrid, dim3(kResThreads), rl, stream, qa, qb); \
-    return launched("residual_block_fwd");                                                                             \
+  // the activation's kind is compiled in when every problem of the launch is ELU (conv_residual_fwd_supported: pre_act is set)
+  const bool elu = pa.g.act == MTRSSM_ACT_ELU && (pb.nx == 0 || pb.g.act == MTRSSM_ACT_ELU);
+#define MTRSSM_FUSE_LAUNCH_V(NCT_, ELU_)                                                                                             \
+  {                                                                                                                                  \
+    const size_t rl = res_lds_bytes<64, NCT_, 1>() + res_fuse_bytes<64, NCT_>();                                                     \
+    allow_lds<conv3x3_resident_kernel<64, NCT_, 1, true, ELU_, false, true>>((int)rl);                                               \
+    set_last_kernel("mtrssm::conv3x3_resident_kernel<64, " #NCT_ ", 1, true, " #ELU_ ", false, true>");                               \
+    hipLaunchKernelGGL((conv3x3_resident_kernel<64, NCT_, 1, true, ELU_, false, true>), rgrid, dim3(kResThreads), rl, stream, qa, qb); \
+    return launched("residual_block_fwd");                                                                                           \
   }
+#define MTRSSM_FUSE_LAUNCH(NCT_) \
+  { if (elu) MTRSSM_FUSE_LAUNCH_V(NCT_, true) else MTRSSM_FUSE_LAUNCH_V(NCT_, false) }
   if (key == 64128) MTRSSM_FUSE_LAUNCH(4)
   if (key == 64064) MTRSSM_FUSE_LAUNCH(2)
+#undef MTRSSM_FUSE_LAUNCH_V
 #undef MTRSSM_FUSE_LAUNCH
   set_error("residual_block_fwd: no fused kernel for this shape");
   return MTRSSM_EINVAL;

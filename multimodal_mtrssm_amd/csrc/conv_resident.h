@@ -18,7 +18,8 @@
 // epilogue rows (bias is the accumulator's start value; act'(x) and the skip gradient are requested a unit ahead), the
 // requests for the next tile's frames (unit 0) and their conversion into the other image (unit 1).  One LDS-only
 // barrier per tile.  KS = 2 (K = 1152) exchanges half of the rows through LDS after every unit.
-// Measured (profiles/round2_notes.md): paired 64 -> 64 layer 200 -> 93 us forward, 122 us backward-data.
+// Measured (profiles/round2_notes.md): paired 64 -> 64 layer 200 -> 93 us forward, 122 us backward-data; 98 us backward-data
+// since the operands are counted global loads and nothing dead is staged (profiles/resident_diet_notes.md).
 #pragma once
 
 namespace mtrssm {
@@ -49,6 +50,10 @@ __host__ __device__ constexpr int res_group_rows(int cin) { return cin >= 128 ? 
 // third k-block, right behind the newest requests.  LDS operations return in order, so "at most 4 outstanding" releases the
 // fragment requested two blocks ago whatever else (the staging writes) is in flight; res_wait ties the fragment registers
 // to that wait.  (Measured: no change of the unit time -- the schedule just no longer depends on the compiler's choice.)
+// The count is only right while LDS operations are all that counts in LGKM_CNT inside the tile loop: no scalar memory read,
+// no flat_* access (a pointer the compiler cannot prove global: flat loads count in BOTH counters and return out of order,
+// so the compiler drains vmcnt and lgkmcnt to zero at their first use), no s_sendmsg.  Every global access of the loop goes
+// through a pointer of known address space (res_gptr below) and counts in VM_CNT alone.
 template <int IMGB>
 __device__ __forceinline__ void res_read_pair(bf16x8& hi, bf16x8& lo, unsigned addr, int cb) {
   switch (cb) {
@@ -61,6 +66,17 @@ __device__ __forceinline__ void res_read_pair(bf16x8& hi, bf16x8& lo, unsigned a
 template <int N>
 __device__ __forceinline__ void res_wait(bf16x8& b0, bf16x8& b1) {
   asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(b0), "+v"(b1) : "n"(N));
+}
+
+
+// Epilogue operands: one laundered base pointer per operand and half of the rows, so the row offsets stay immediates of the
+// load (res_row_off).  The pointer keeps its GLOBAL address space through the laundering: the loads are global_load_dword,
+// counted in VM_CNT, in order, with the compiler's own counted vmcnt(N) at their use a unit later.
+using res_gptr = const __attribute__((address_space(1))) float*;
+__device__ __forceinline__ res_gptr res_launder(const float* p) {
+  res_gptr q = (res_gptr)p;
+  asm volatile("" : "+v"(q));
+  return q;
 }
 
 template <int CIN, int NCT, int KS>
@@ -86,10 +102,14 @@ __host__ __device__ constexpr size_t res_fuse_bytes() {
   return (size_t)NCT * (CIN / 32) * 2 * 2 * 64 * 16 + (size_t)4 * (NCT == 2 ? 16 : CIN / 2) * 64 * sizeof(float);
 }
 
-template <int CIN, int NCT, int KS, bool EPI, bool FUSE = false>  // EPI: the epilogue has operands (act'(x) input and / or skip gradient)
+// PRE: the staged values are activated (g.pre_act; backward-data stages a gradient as it stands: no exponential, no select).
+// ELU: the activation is ELU at compile time (the default models: one select per activated value); otherwise its kind is a
+// lane-uniform run-time select (ReLU, identity -- and ELU, where no ELU instance is built).  The launcher picks both.
+template <int CIN, int NCT, int KS, bool PRE, bool ELU, bool EPI, bool FUSE = false>  // EPI: the epilogue has operands (act'(x) input and / or skip gradient)
 __global__ __launch_bounds__(kResThreads, 1) void conv3x3_resident_kernel(const GatherProblem pa, const GatherProblem pb) {
   static_assert(NCT * KS == 4 || NCT * KS == 2 || NCT * KS == 1, "4 waves");
-  static_assert(!FUSE || (KS == 1 && !EPI && CIN % 32 == 0), "fused block: whole K per wave, no epilogue operands");
+  static_assert(!FUSE || (KS == 1 && !EPI && PRE && CIN % 32 == 0), "fused block: whole K per wave, no epilogue operands");
+  static_assert(!ELU || PRE || EPI, "an instance without any activation has no kind to compile in");
   constexpr int NPG = 4 / (NCT * KS);  // frames per tile
   constexpr int CW = CIN / KS;         // input channels per wave
   constexpr int CB = CW / 16;          // 16-channel k-blocks per tap
@@ -123,7 +143,10 @@ __global__ __launch_bounds__(kResThreads, 1) void conv3x3_resident_kernel(const 
   const int kh = (wave / NCT) % KS;
   const int pgi = wave / (NCT * KS);
 
-  unsigned long long* prof = (blockIdx.x == 0 && tid == 0) ? g_res_prof : nullptr;
+  // (a global pointer: as a generic one its stamps are flat stores, and one pending flat access turns every counted
+  // vmcnt(N) the compiler places behind it into vmcnt(0))
+  using prof_ptr = __attribute__((address_space(1))) unsigned long long*;
+  const prof_ptr prof = (blockIdx.x == 0 && tid == 0) ? (prof_ptr)g_res_prof : nullptr;
   if (prof) prof[0] = __builtin_readcyclecounter();
   // ---- this wave's weights: MFMA A operands (row = output channel il of tile ct, 8 k-values per lane) for every k-block.
   // Read straight from the packed layout a lane's 16 bytes sit 18 * CIN bytes from its neighbour's: every load touches 32
@@ -194,13 +217,12 @@ __global__ __launch_bounds__(kResThreads, 1) void conv3x3_resident_kernel(const 
       unsigned hi[4], lo[4];
 #pragma unroll
       for (int e2 = 0; e2 < 4; ++e2) {
-        unsigned short p0[2], p1[2];
+        unsigned d[2];
         const int e = 2 * e2;
         const int k0 = ct * 32 + 4 * kl + (e & 3) + 8 * (2 * kb2 + (e >> 2));
-        split_bf16<2>(w1[(size_t)(ot * 32 + il) * CMID + k0], p0);
-        split_bf16<2>(w1[(size_t)(ot * 32 + il) * CMID + k0 + 1], p1);
-        hi[e2] = (unsigned)p0[0] | ((unsigned)p1[0] << 16);
-        lo[e2] = (unsigned)p0[1] | ((unsigned)p1[1] << 16);
+        wg_split_pair<2>(w1[(size_t)(ot * 32 + il) * CMID + k0], w1[(size_t)(ot * 32 + il) * CMID + k0 + 1], d);
+        hi[e2] = d[0];
+        lo[e2] = d[1];
       }
       unsigned char* dst = w1l + ((size_t)((ct * NF + f) * 2) * 64 + lane) * 16;
       *reinterpret_cast<u32x4*>(dst) = u32x4{hi[0], hi[1], hi[2], hi[3]};
@@ -233,17 +255,24 @@ __global__ __launch_bounds__(kResThreads, 1) void conv3x3_resident_kernel(const 
   }
   const int spos = ((lane >> wsh) + 1) * pw + (lane & (g.Wq - 1)) + 1;  // staging: lane = pixel of the frame
   // activation switches as lane-uniform selects (no branch inside the MFMA loop: a branch ends a scheduling region)
-  const bool act_elu = g.act == MTRSSM_ACT_ELU, act_relu = g.act == MTRSSM_ACT_RELU, pre = g.pre_act != 0;
-  auto act_fwd_sel = [&](float x) { return WgActSel{act_elu, act_relu, pre}(x); };  // pre-activation of a staged value
+  // (host: ELU instances run with g.act == MTRSSM_ACT_ELU, PRE == (g.pre_act != 0))
+  const bool act_elu = ELU || g.act == MTRSSM_ACT_ELU, act_relu = !ELU && g.act == MTRSSM_ACT_RELU;
+  auto act_fwd_sel = [&](float x) {  // pre-activation of a staged value
+    if constexpr (!PRE) return x;
+    float e = __expf(x) - 1.f;
+    asm volatile("" : "+v"(e));  // computed unconditionally: the compiler would branch around the exponential
+    const float neg = ELU ? e : (act_elu ? e : (act_relu ? 0.f : x));
+    return x > 0.f ? x : neg;
+  };
   auto act_grad_sel = [&](float x) {  // act'(x) from the layer input
     float e = __expf(x);
     asm volatile("" : "+v"(e));
-    const float neg = act_elu ? e : (act_relu ? 0.f : 1.f);
+    const float neg = ELU ? e : (act_elu ? e : (act_relu ? 0.f : 1.f));
     return x > 0.f ? 1.f : neg;
   };
   auto act_mid_sel = [&](float x) {  // FUSE: the block's activation on the intermediate
     const float e = __expf(x) - 1.f;
-    const float neg = act_elu ? e : (act_relu ? 0.f : x);
+    const float neg = ELU ? e : (act_elu ? e : (act_relu ? 0.f : x));
     return x > 0.f ? x : neg;
   };
 
@@ -265,14 +294,13 @@ __global__ __launch_bounds__(kResThreads, 1) void conv3x3_resident_kernel(const 
   auto stage_store_chunk = [&](int buf, int c) {  // chunk c: channels 2 * (c % 4), +1 of item c / 4 -> 4 bytes per piece
     const int it = c / 4, u2 = c % 4;
     const int q = wave * NIT + it, fi = q / OCT, o = q % OCT;
-    unsigned short p0[2], p1[2];
-    split_bf16<2>(act_fwd_sel(pv[it][2 * u2]), p0);
-    split_bf16<2>(act_fwd_sel(pv[it][2 * u2 + 1]), p1);
+    unsigned d[2];  // both channels' pieces, packed as the image holds them
+    wg_split_pair<2>(act_fwd_sel(pv[it][2 * u2]), act_fwd_sel(pv[it][2 * u2 + 1]), d);
     int opaque = 0;
     asm volatile("" : "+s"(opaque));
     unsigned char* dst = patch + (size_t)buf * 2 * IMG + (fi * kResPos + spos + opaque) * RB + o * 16 + u2 * 4;
-    *reinterpret_cast<unsigned*>(dst) = (unsigned)p0[0] | ((unsigned)p1[0] << 16);
-    *reinterpret_cast<unsigned*>(dst + IMG) = (unsigned)p0[1] | ((unsigned)p1[1] << 16);
+    *reinterpret_cast<unsigned*>(dst) = d[0];
+    *reinterpret_cast<unsigned*>(dst + IMG) = d[1];
   };
   constexpr int NSC = NIT * 4;  // staging chunks per tile
 
@@ -395,9 +423,7 @@ __global__ __launch_bounds__(kResThreads, 1) void conv3x3_resident_kernel(const 
           for (int i = 0; i < RPL; ++i) {
             const int j = kb * RPL + i;
             const unsigned ob2 = ob_cur + (KS == 2 ? (unsigned)(kh * 16 * 64) : 0u) + (j >= 8 ? 16u * 64u : 0u);
-            const float* gp = gsrc + ob2;
-            const float* ap = asrc + ob2;
-            asm volatile("" : "+v"(gp), "+v"(ap));
+            const res_gptr gp = res_launder(gsrc + ob2), ap = res_launder(asrc + ob2);
             gvs[h][j] = gp[row_off(j & 7)];
             avs[h][j] = ap[row_off(j & 7)];
           }
@@ -421,13 +447,19 @@ __global__ __launch_bounds__(kResThreads, 1) void conv3x3_resident_kernel(const 
       if (KS == 2) {  // the two halves of K meet: each wave hands over the rows it does not finish
         float* mine = red + ((size_t)((pgi * NCT + ct) * 2 + kh) * 8) * 64 + lane;
         const float* theirs = red + ((size_t)((pgi * NCT + ct) * 2 + (kh ^ 1)) * 8) * 64 + lane;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) mine[j * 64] = kh == 0 ? acc[8 + j] : acc[j];
+        // both halves of the rows leave the AGPRs as they stand; which half stays is a wave-uniform select between two
+        // registers (a select between two ELEMENTS of acc becomes an indexed register read: s_set_gpr_idx_on per row)
+        float lo8[8], hi8[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          fin[j] = kh == 0 ? acc[j] : acc[8 + j];
-          asm volatile("" : "+v"(fin[j]));  // architectural VGPRs: a store sourcing an AGPR stalls like the read does
+          lo8[j] = acc[j];
+          hi8[j] = acc[8 + j];
+          asm volatile("" : "+v"(lo8[j]), "+v"(hi8[j]));  // architectural VGPRs: a store sourcing an AGPR stalls like the read does
         }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) mine[j * 64] = kh == 0 ? hi8[j] : lo8[j];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) fin[j] = kh == 0 ? lo8[j] : hi8[j];
         lds_barrier();
 #pragma unroll
         for (int j = 0; j < 8; ++j) part[j] = theirs[j * 64];
@@ -446,11 +478,10 @@ __global__ __launch_bounds__(kResThreads, 1) void conv3x3_resident_kernel(const 
           unsigned hi[4], lo[4];
 #pragma unroll
           for (int e2 = 0; e2 < 4; ++e2) {
-            unsigned short p0[2], p1[2];
-            split_bf16<2>(act_mid_sel(fin[8 * kb2 + 2 * e2]), p0);
-            split_bf16<2>(act_mid_sel(fin[8 * kb2 + 2 * e2 + 1]), p1);
-            hi[e2] = (unsigned)p0[0] | ((unsigned)p1[0] << 16);
-            lo[e2] = (unsigned)p0[1] | ((unsigned)p1[1] << 16);
+            unsigned d[2];
+            wg_split_pair<2>(act_mid_sel(fin[8 * kb2 + 2 * e2]), act_mid_sel(fin[8 * kb2 + 2 * e2 + 1]), d);
+            hi[e2] = d[0];
+            lo[e2] = d[1];
           }
           mb[kb2][0] = __builtin_bit_cast(bf16x8, u32x4{hi[0], hi[1], hi[2], hi[3]});
           mb[kb2][1] = __builtin_bit_cast(bf16x8, u32x4{lo[0], lo[1], lo[2], lo[3]});
