@@ -73,6 +73,10 @@ typedef struct MtrssmMrssmDims {
   float kl_w_prior;      /* share sent to the prior (alpha with balancing, else 1) */
   int32_t rows_per_block; /* 0 = library default */
   int32_t threads;        /* 0 = library default */
+  float unimix;           /* eps in [0, 1): every categorical the scan forms (the prior, the posterior after the MoPoE mix) is
+                             (1 - eps) * softmax(logits) + eps / C, applied as logits <- log of that before anything reads the
+                             logits; 0 = off (no new arithmetic runs).  Outside [0, 1) or NaN: MTRSSM_EINVAL ("unimix") from every
+                             scan entry point, before the pointer checks.  The *_supported functions ignore it. */
 } MtrssmMrssmDims;
 
 typedef struct MtrssmMrssmFwdWeights {
@@ -105,9 +109,11 @@ typedef struct MtrssmMrssmFwdIO {
   const float* u_prior; /* [B,T,K] uniforms for the prior sample (NULL: not sampled when post=1) */
   /* outputs */
   float* deter;         /* [B,T,D] */
-  float* prior_logits;  /* [B,T,S] raw prior logits */
+  float* prior_logits;  /* [B,T,S] raw prior logits; with dims.unimix > 0 the log-probabilities of the mixed prior */
   float* prior_stoch;   /* [B,T,S] one-hot prior sample (NULL allowed when post=1) */
-  float* post_logits;   /* [B,T,S] mixed log-probs (post only) */
+  float* post_logits;   /* [B,T,S] MoPoE-mixed log-probs (post only); with dims.unimix > 0 the log-probabilities of the
+                           uniform-mixed posterior (a per-categorical softmax of either output gives the distribution the
+                           scan sampled from and took the KL of) */
   float* post_stoch;    /* [B,T,S] one-hot posterior sample (post only) */
   float* kl;            /* [B,T]   sum_K KL(q_k || p_k) (post only, NULL allowed) */
   /* activations saved for the backward scan (all NULL = inference) */
@@ -339,6 +345,8 @@ typedef struct MtrssmMmtrssmDims {
   float kl_w_post, kl_w_prior;
   int32_t rows_per_block;
   int32_t threads;
+  float unimix;          /* eps in [0, 1), as MtrssmMrssmDims.unimix: the lower prior, the lower posterior after the mix, the
+                            higher prior and the higher posterior (CL resp. CH in the eps / C term); 0 = off */
 } MtrssmMmtrssmDims;
 
 typedef struct MtrssmMmtrssmFwdWeights {
@@ -382,8 +390,8 @@ typedef struct MtrssmMmtrssmFwdIO {
   float* deter_h;         /* [B,T,HD] */
   float* hidden_l;        /* [B,T,LD] */
   float* hidden_h;        /* [B,T,HD] */
-  float* prior_logits_l;  /* [B,T,LS] */
-  float* prior_logits_h;  /* [B,T,HS] */
+  float* prior_logits_l;  /* [B,T,LS] raw; with dims.unimix > 0 all four logits outputs are the log-probabilities of the */
+  float* prior_logits_h;  /* [B,T,HS] uniform-mixed distributions, as in MtrssmMrssmFwdIO */
   float* prior_stoch_l;   /* [B,T,LS] (NULL allowed when post=1) */
   float* prior_stoch_h;   /* [B,T,HS] */
   float* post_logits_l;   /* [B,T,LS] mixed log-probs */

@@ -34,7 +34,7 @@ def _ptrs(*names: str) -> list[tuple[str, type]]:
 
 MrssmDims = _struct("MtrssmMrssmDims", [
     ("B", _i), ("T", _i), ("D", _i), ("H", _i), ("K", _i), ("C", _i), ("act", _i), ("post", _i),
-    ("kl_w_post", _f), ("kl_w_prior", _f), ("rows_per_block", _i), ("threads", _i),
+    ("kl_w_post", _f), ("kl_w_prior", _f), ("rows_per_block", _i), ("threads", _i), ("unimix", _f),
 ])
 MrssmFwdWeights = _struct("MtrssmMrssmFwdWeights", _ptrs(
     "w1s_t", "w2_t", "b2", "wih_t", "bih", "whh_t", "bhh", "wh1_t", "b3", "w4", "b4", "wa2", "ba2", "wv2", "bv2"))
@@ -63,7 +63,7 @@ InitialState = _struct("MtrssmInitialState", _ptrs("ea", "ev") + [("ea_stride", 
 MmtrssmDims = _struct("MtrssmMmtrssmDims", [
     ("B", _i), ("T", _i), ("LD", _i), ("HD", _i), ("H", _i), ("KL", _i), ("CL", _i), ("KH", _i), ("CH", _i),
     ("act", _i), ("post", _i), ("tau_l", _f), ("tau_h", _f), ("keep_l", _f), ("keep_h", _f),
-    ("kl_w_post", _f), ("kl_w_prior", _f), ("rows_per_block", _i), ("threads", _i),
+    ("kl_w_post", _f), ("kl_w_prior", _f), ("rows_per_block", _i), ("threads", _i), ("unimix", _f),
 ])
 MmtrssmFwdWeights = _struct("MtrssmMmtrssmFwdWeights", _ptrs(
     "wxl_s_t", "wdl_t", "wxh_t", "wdh_t", "bh", "wl1_t", "bl1", "wh1_t", "bh1",

@@ -25,7 +25,7 @@ from multimodal_mtrssm_amd.carry import StateCarry
 from multimodal_mtrssm_amd.census import CensusTable, LatentCensus
 from multimodal_mtrssm_amd.digits import DigitClassifier
 from multimodal_mtrssm_amd.frechet import FrechetDistance, FrechetTable
-from multimodal_mtrssm_amd.distributions import MultiOneHot, MultiOneHotFactory, draw_uniforms, kl_divergence, onehot_from_uniforms
+from multimodal_mtrssm_amd.distributions import MultiOneHot, MultiOneHotFactory, check_unimix, draw_uniforms, kl_divergence, onehot_from_uniforms
 from multimodal_mtrssm_amd.dropout import ModalityDropout, StepMask, ragged_step_mask
 from multimodal_mtrssm_amd.evaluation import _Evaluators
 from multimodal_mtrssm_amd.experts import ExpertWeights
@@ -349,7 +349,7 @@ def _elbo(nll_a: Tensor, nll_v: Tensor, kl0: Tensor, c0: float, kl1: Tensor | No
 def _sampled_head(factory, logits: Tensor, u: Tensor | None) -> tuple[MultiOneHot, Tensor]:  # noqa: ANN001
     """``(factory(logits), straight-through sample)``: one fused launch on the GPU when the uniforms are given."""
     if not logits.is_cuda:
-        dist = factory(logits)
+        dist = factory.unmixed(logits)  # (the initial state's head: never uniform-mixed, DESIGN.md section 6u)
         return dist, _st_onehot(dist, u)
     if u is None:  # (the draw MultiOneHot.rsample would make: injected noise tape or the device generator)
         u = draw_uniforms((*logits.shape[:-1], factory.category_size), logits)
@@ -438,6 +438,7 @@ class MoPoE_MRSSM(_Evaluators, _Base):  # noqa: N801
         init_proj: nn.Module,
         kl_coeff: float,
         use_kl_balancing: bool,
+        unimix: float = 0.0,
     ) -> None:
         super().__init__()
         # registration order and the double registration of the audio head follow the reference
@@ -480,6 +481,24 @@ class MoPoE_MRSSM(_Evaluators, _Base):  # noqa: N801
         self.expert_weights: ExpertWeights | None = None
         self.weights_timeseries: Tensor | None = None
         self._weights_both: Tensor | None = None  # bool [B, T]: where weights_timeseries belongs to a step with both modalities
+        self.unimix = unimix  # uniform mixing of every categorical the scans form; config, not checkpoint
+
+    def _distribution_factories(self) -> list[MultiOneHotFactory]:
+        owned = [self.transition.distribution_factory, self.audio_representation.distribution_factory,
+                 self.vision_representation.distribution_factory]
+        return owned + [f for f in (getattr(self, "l_dist", None), getattr(self, "h_dist", None)) if f is not None]
+
+    @property
+    def unimix(self) -> float:
+        """eps of the uniform mixing ``(1 - eps) softmax + eps / C`` of every prior and posterior categorical:
+        one value on every distribution factory the model owns; 0 = off.  No parameter, buffer or state-dict key."""
+        return scan.unimix_of(*self._distribution_factories())
+
+    @unimix.setter
+    def unimix(self, value: float) -> None:
+        eps = check_unimix(value)
+        for factory in self._distribution_factories():
+            factory.unimix = eps
 
     # -- batch accessors (mrssm core.py:310-355) --------------------------------------------
     @staticmethod
@@ -676,13 +695,13 @@ class MoPoE_MRSSM(_Evaluators, _Base):  # noqa: N801
             self.weights_timeseries = ExpertWeights.table(logw, codes & 3)
 
     def _posterior_from_rollout(self, out: dict[str, Tensor]) -> State:
-        post = State(deter=out["deter"], distribution=self.audio_representation.distribution_factory(out["post_logits"]), stoch=out["post_stoch"])
+        post = State(deter=out["deter"], distribution=self.audio_representation.distribution_factory.unmixed(out["post_logits"]), stoch=out["post_stoch"])
         post.kl_per_step = out["kl"]  # sum_K KL(q||p) per (b, t), straight from the scan kernel
         return post
 
     def _states_from_rollout(self, out: dict[str, Tensor]) -> tuple[State, State]:
         factory = self.audio_representation.distribution_factory
-        prior = State(deter=out["deter"], distribution=factory(out["prior_logits"]), stoch=out["prior_stoch"])
+        prior = State(deter=out["deter"], distribution=factory.unmixed(out["prior_logits"]), stoch=out["prior_stoch"])
         return self._posterior_from_rollout(out), prior
 
     def rollout_representation(
@@ -735,7 +754,7 @@ class MoPoE_MRSSM(_Evaluators, _Base):  # noqa: N801
         u = None if noise is None else noise.get("u_prior")
         out = scan.mrssm_prior_rollout(self.transition, actions, prev_state.deter, prev_state.stoch, u,
                                        rows_per_block=self.scan_rows_per_block, threads=self.scan_threads)
-        dist = self.transition.distribution_factory(out["prior_logits"])
+        dist = self.transition.distribution_factory.unmixed(out["prior_logits"])
         return State(deter=out["deter"], distribution=dist, stoch=out["prior_stoch"])
 
     @torch.no_grad()
@@ -1230,6 +1249,7 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
         l_dist: MultiOneHotFactory,
         h_dist: MultiOneHotFactory,
         w_kl_h: float = 1.0,
+        unimix: float = 0.0,
     ) -> None:
         # the reference registers a never-trained Transition (A=1, S=1) for its base class (core.py:143-151);
         # kept so that state-dicts interchange
@@ -1239,7 +1259,7 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
             audio_representation=audio_representation, vision_representation=vision_representation,
             transition=dummy_transition, audio_encoder=audio_encoder, vision_encoder=vision_encoder,
             audio_decoder=audio_decoder, vision_decoder=vision_decoder, init_proj=init_proj, kl_coeff=kl_coeff,
-            use_kl_balancing=use_kl_balancing,
+            use_kl_balancing=use_kl_balancing, unimix=unimix,
         )
         self.action_dim = action_size
         self.hd_dim, self.hs_dim, self.ld_dim, self.ls_dim = hd_dim, hs_dim, ld_dim, ls_dim
@@ -1252,6 +1272,7 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
         self.h_posterior = h_posterior
         self.l_dist = l_dist
         self.h_dist = h_dist
+        self.unimix = unimix  # (again: now l_dist and h_dist are among the factories)
 
     @property
     def feature_dim(self) -> int:
@@ -1305,14 +1326,14 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
                                               expert_logw=logw)
 
     def _posterior_from_rollout(self, out: dict[str, Tensor]) -> MTState:  # type: ignore[override]
-        post = MTState(distribution_h=self.h_dist(out["post_logits_h"]), distribution_l=self.l_dist(out["post_logits_l"]),
+        post = MTState(distribution_h=self.h_dist.unmixed(out["post_logits_h"]), distribution_l=self.l_dist.unmixed(out["post_logits_l"]),
                        stoch_h=out["post_stoch_h"], stoch_l=out["post_stoch_l"], deter_h=out["deter_h"], deter_l=out["deter_l"],
                        hidden_h=out["hidden_h"], hidden_l=out["hidden_l"])
         post.kl_per_step, post.kl_h_per_step = out["kl_l"], out["kl_h"]
         return post
 
     def _states_from_rollout(self, out: dict[str, Tensor]) -> tuple[MTState, MTState]:  # type: ignore[override]
-        prior = MTState(distribution_h=self.h_dist(out["prior_logits_h"]), distribution_l=self.l_dist(out["prior_logits_l"]),
+        prior = MTState(distribution_h=self.h_dist.unmixed(out["prior_logits_h"]), distribution_l=self.l_dist.unmixed(out["prior_logits_l"]),
                         stoch_h=out["prior_stoch_h"], stoch_l=out["prior_stoch_l"], deter_h=out["deter_h"], deter_l=out["deter_l"],
                         hidden_h=out["hidden_h"], hidden_l=out["hidden_l"])
         return self._posterior_from_rollout(out), prior
@@ -1353,8 +1374,8 @@ class MoPoE_MMTRSSM(MoPoE_MRSSM):  # noqa: N801
         out = scan.mmtrssm_prior_rollout(self, actions, self._state_dict_of(prev_state), noise or {},
                                          rows_per_block=self.scan_rows_per_block, threads=self.scan_threads)
         return MTState(
-            deter_h=out["deter_h"], deter_l=out["deter_l"], distribution_h=self.h_dist(out["prior_logits_h"]),
-            distribution_l=self.l_dist(out["prior_logits_l"]), hidden_h=out["hidden_h"], hidden_l=out["hidden_l"],
+            deter_h=out["deter_h"], deter_l=out["deter_l"], distribution_h=self.h_dist.unmixed(out["prior_logits_h"]),
+            distribution_l=self.l_dist.unmixed(out["prior_logits_l"]), hidden_h=out["hidden_h"], hidden_l=out["hidden_l"],
             stoch_h=out["prior_stoch_h"], stoch_l=out["prior_stoch_l"],
         )
 

@@ -152,6 +152,14 @@ __global__ __launch_bounds__(1024) void mmtrssm_fwd_kernel(const MtrssmMmtrssmDi
       const int code = modality_code<MASKED>(io.modality, q);
       if (POST) wave_mopoe_mix_masked<false, MASKED>(r + L.la, r + L.lv, r + L.lpl, r + L.mx, LS, lane, code, expert_logw<MASKED>(io.expert_logw, q));
       if (POST && MASKED && code == 0) wave_copy(r + L.lph, r + L.lqh, HS, lane);  // no modality: higher posterior = prior
+      if (unimix_on(dm.unimix)) {  // uniform mixing of all four, before the logits are stored, sampled or enter the KL
+        wave_unimix_fwd(r + L.lpl, KL, CL, lane, dm.unimix);
+        wave_unimix_fwd(r + L.lph, KH, CH, lane, dm.unimix);
+        if (POST) {
+          wave_unimix_fwd(r + L.mx, KL, CL, lane, dm.unimix);
+          wave_unimix_fwd(r + L.lqh, KH, CH, lane, dm.unimix);
+        }
+      }
       if (ok) {
         for (int s = lane; s < LS; s += kWave) {
           io.prior_logits_l[q * LS + s] = r[L.lpl + s];
@@ -274,10 +282,18 @@ __global__ __launch_bounds__(1024) void mmtrssm_bwd_kernel(const MtrssmMmtrssmDi
                     io.g_prior_logits_h ? io.g_prior_logits_h + q * HS : nullptr, io.g_kl_h ? io.g_kl_h[q] : 0.f,
                     dm.kl_w_post, dm.kl_w_prior, r + L.dlqh, r + L.dlph);
       const int code = modality_code<MASKED>(io.modality, q);
+      const ExpertLogW lw = expert_logw<MASKED>(io.expert_logw, q);
+      if (unimix_on(dm.unimix)) {  // d x' -> d x at the raw logits; then the raw lower mix back in place of the staged x'
+        wave_unimix_bwd(r + L.mx, r + L.dmx, KL, CL, lane, dm.unimix);
+        wave_unimix_bwd(r + L.lpl, r + L.dlpl, KL, CL, lane, dm.unimix);
+        wave_unimix_bwd(r + L.lqh, r + L.dlqh, KH, CH, lane, dm.unimix);
+        wave_unimix_bwd(r + L.lph, r + L.dlph, KH, CH, lane, dm.unimix);
+        wave_mopoe_remix<false, MASKED>(r + L.la, r + L.lv, r + L.mx, LS, lane, code, lw);
+      }
       if (MASKED && code == 0) wave_route_to_prior(r + L.dlqh, r + L.dlph, HS, lane);
       const ExpertLogW g_lw =
           wave_mopoe_mix_bwd_masked<false, MASKED>(r + L.la, r + L.lv, r + L.mx, r + L.dmx, r + L.dla, r + L.dlv, r + L.dlpl, LS, lane, code,
-                                                   expert_logw<MASKED>(io.expert_logw, q), MASKED && io.expert_logw != nullptr);
+                                                   lw, MASKED && io.expert_logw != nullptr);
       if (MASKED) store_g_expert_logw(io.g_expert_logw, q, g_lw, lane, valid[rb]);
       if (valid[rb]) {
         for (int s = lane; s < LS; s += kWave) {
@@ -404,6 +420,7 @@ static int check_mmt_dims(const MtrssmMmtrssmDims* d) {
     set_error("mmtrssm: unknown activation id %d", d->act);
     return MTRSSM_EINVAL;
   }
+  if (int rc = check_unimix("mmtrssm", d->unimix)) return rc;
   if (d->threads < 0 || d->threads > 1024 || d->threads % kWave) {
     set_error("mmtrssm: threads must be a multiple of 64 in [64, 1024] (0 = default)");
     return MTRSSM_EINVAL;

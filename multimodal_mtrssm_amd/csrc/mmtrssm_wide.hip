@@ -143,6 +143,10 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_fwd_kernel(const MmtWideFwdA
           MTRSSM_WIDE_STAMP(10);
           if (wave == 0) {   // lower level: MoPoE mix, categorical block
             wave_mopoe_mix_masked<true, MASKED>(Lla, Llv, Llpl, Lmx, LS, lane, code, lw);
+            if (unimix_on(a.dm.unimix)) {  // uniform mixing, before the logits are stored, sampled or enter the KL
+              wave_unimix_fwd_coop(Llpl, KL, CL, lane, a.dm.unimix);
+              wave_unimix_fwd_coop(Lmx, KL, CL, lane, a.dm.unimix);
+            }
             for (int s2 = lane; s2 < LS; s2 += kWave) {
               io.prior_logits_l[q * LS + s2] = Llpl[s2];
               io.post_logits_l[q * LS + s2] = Lmx[s2];
@@ -157,6 +161,10 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_fwd_kernel(const MmtWideFwdA
             MTRSSM_WIDE_STAMP(11);
           } else if (wave == 1) {   // higher level, beside it on another SIMD
             if (MASKED && code == 0) wave_copy(Llph, Llqh, HS, lane);  // no modality: higher posterior = prior
+            if (unimix_on(a.dm.unimix)) {
+              wave_unimix_fwd_coop(Llph, KH, CH, lane, a.dm.unimix);
+              wave_unimix_fwd_coop(Llqh, KH, CH, lane, a.dm.unimix);
+            }
             for (int s2 = lane; s2 < HS; s2 += kWave) {
               io.prior_logits_h[q * HS + s2] = Llph[s2];
               io.post_logits_h[q * HS + s2] = Llqh[s2];
@@ -358,6 +366,11 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_bwd_kernel(const MmtWideBwdA
           const float* gprl = io.g_prior_logits_l ? io.g_prior_logits_l + q * LS : nullptr;
           if (CL <= 8) cat_block_bwd_fast8(Lmx, Llpl, KL, CL, lane, Lgps, Lcs, gpsl, gpll, gprl, gkl, a.dm.kl_w_post, a.dm.kl_w_prior, Ldmx, Ldlpl);
           else cat_block_bwd<true>(Lmx, Llpl, KL, CL, lane, Lgps, Lcs, gpsl, gpll, gprl, gkl, a.dm.kl_w_post, a.dm.kl_w_prior, Ldmx, Ldlpl);
+          if (unimix_on(a.dm.unimix)) {  // d x' -> d x at the raw logits; then the raw mix back in place of the staged x'
+            wave_unimix_bwd_coop(Lmx, Ldmx, KL, CL, lane, a.dm.unimix);
+            wave_unimix_bwd_coop(Llpl, Ldlpl, KL, CL, lane, a.dm.unimix);
+            wave_mopoe_remix<true, MASKED>(Lla, Llv, Lmx, LS, lane, code, lw);
+          }
           const ExpertLogW g_lw =
               wave_mopoe_mix_bwd_masked<true, MASKED>(Lla, Llv, Lmx, Ldmx, Ldla, Ldlv, Ldlpl, LS, lane, code, lw, MASKED && io.expert_logw != nullptr);
           if (MASKED) store_g_expert_logw(io.g_expert_logw, q, g_lw, lane, true);
@@ -369,6 +382,10 @@ __global__ __launch_bounds__(kWT) void mmtrssm_wide_bwd_kernel(const MmtWideBwdA
           const float* gprh = io.g_prior_logits_h ? io.g_prior_logits_h + q * HS : nullptr;
           if (CH <= 8) cat_block_bwd_fast8(Llqh, Llph, KH, CH, lane, Lgps + LS, Lcs + LS, gpsh, gplh, gprh, gkh, a.dm.kl_w_post, a.dm.kl_w_prior, Ldlqh, Ldlph);
           else cat_block_bwd<true>(Llqh, Llph, KH, CH, lane, Lgps + LS, Lcs + LS, gpsh, gplh, gprh, gkh, a.dm.kl_w_post, a.dm.kl_w_prior, Ldlqh, Ldlph);
+          if (unimix_on(a.dm.unimix)) {
+            wave_unimix_bwd_coop(Llqh, Ldlqh, KH, CH, lane, a.dm.unimix);
+            wave_unimix_bwd_coop(Llph, Ldlph, KH, CH, lane, a.dm.unimix);
+          }
           if (MASKED && code == 0) wave_route_to_prior(Ldlqh, Ldlph, HS, lane);
         }
         lds_barrier();
@@ -577,6 +594,8 @@ static size_t mmt_bwd_lds(const MmtWideGeom& G) {
 
 int mmtrssm_wide_fwd_launch(const MtrssmMmtrssmDims* d, const MtrssmMmtrssmFwdWeights* w, const MtrssmMmtrssmFwdIO* io, int pieces,
                             void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  if (d)
+    if (int rc = check_unimix("mmtrssm_rollout_fwd_wide", d->unimix)) return rc;
   if (!mmtrssm_wide_supported(d, pieces)) return wide_not_supported("mmtrssm_rollout_fwd_wide", "mmtrssm");
   if (!w || !io || !workspace || !w->wxl_s_t || !w->wdl_t || !w->wxh_t || !w->wdh_t || !w->bh || !w->wl1_t || !w->bl1 || !w->wh1_t || !w->bh1 ||
       !w->wlp2 || !w->blp2 || !w->wa2 || !w->ba2 || !w->wv2 || !w->bv2 || !w->whp2 || !w->bhp2 || !w->whq2 || !w->bhq2 || !io->xl || !io->pa ||
@@ -635,6 +654,8 @@ int mmtrssm_wide_fwd_launch(const MtrssmMmtrssmDims* d, const MtrssmMmtrssmFwdWe
 
 int mmtrssm_wide_bwd_launch(const MtrssmMmtrssmDims* d, const MtrssmMmtrssmBwdWeights* w, const MtrssmMmtrssmBwdIO* io, int pieces,
                             void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  if (d)
+    if (int rc = check_unimix("mmtrssm_rollout_bwd_wide", d->unimix)) return rc;
   if (!mmtrssm_wide_supported(d, pieces)) return wide_not_supported("mmtrssm_rollout_bwd_wide", "mmtrssm");
   if (!w || !io || !workspace || !w->wxl_s_t || !w->wdl || !w->wxh_t || !w->wdh || !w->wl1 || !w->wh1 || !w->wlp2 || !w->wa2 || !w->wv2 ||
       !w->whp2 || !w->whq2 || !io->deter_l0 || !io->deter_h0 || !io->deter_l || !io->deter_h || !io->prior_logits_l || !io->prior_logits_h ||

@@ -76,7 +76,7 @@ __device__ __forceinline__ bool wave_gather(const unsigned long long* g, float* 
 
 // DH: D = H (compile time: every stride an immediate).  The 2 * 3 * DH / 4 gate columns are cut into NP pieces of KP = DH / NP
 // reduction terms; thread t holds pieces t * PPT .. t * PPT + PPT - 1 (column = piece / NP, part = piece % NP).
-template <int DH, int NP, int PPT, bool MASKED>
+template <int DH, int NP, int PPT, bool MASKED, bool UNIMIX>
 __global__ __launch_bounds__(kCluThreads) void mrssm_fwd_cluster_kernel(const MtrssmMrssmDims dm, const MtrssmMrssmClusterWeights w,
                                                                         const MtrssmMrssmFwdIO io, unsigned long long* __restrict__ gran,
                                                                         int* __restrict__ status, int nclusters) {
@@ -345,6 +345,10 @@ __global__ __launch_bounds__(kCluThreads) void mrssm_fwd_cluster_kernel(const Mt
           lds[(which == 0 ? Llp : (which == 1 ? Lla : Llv)) + s2] = v;
         }
         wave_mopoe_mix_masked<true, MASKED>(lds + Lla, lds + Llv, lds + Llp, lds + Lmx, S, lane, code, lw);
+        if (UNIMIX) {  // uniform mixing, before the logits are stored, sampled or enter the KL (dm.unimix > 0: the launcher's choice)
+          wave_unimix_fwd_coop(lds + Llp, K, C, lane, dm.unimix);
+          wave_unimix_fwd_coop(lds + Lmx, K, C, lane, dm.unimix);
+        }
         for (int s = lane; s < S; s += kWave) {
           if (writer) {
             io.prior_logits[bt * S + s] = lds[Llp + s];
@@ -408,9 +412,19 @@ __device__ __forceinline__ bool wave_gather_map(int total, unsigned epoch, int l
   }
 }
 
+// The backward's unimix step (UNIMIX instances only) as a CALL: the reverse kernel holds its weight columns in registers at the
+// allocator's limit; out of line the step's registers are the callee's and the columns stay where they are.
+template <bool MASKED>
+__device__ __noinline__ void cluster_unimix_bwd(float* mx, const float* lp, float* dmx, float* dlp, const float* la, const float* lv, int K,
+                                                int C, int lane, int code, const ExpertLogW lw, float eps) {
+  wave_unimix_bwd_coop(mx, dmx, K, C, lane, eps);
+  wave_unimix_bwd_coop(lp, dlp, K, C, lane, eps);
+  wave_mopoe_remix<true, MASKED>(la, lv, mx, K * C, lane, code, lw);
+}
+
 // NPB parts of KPB = 3 UD / NPB own gate columns per row piece; thread t holds row pieces t * PPT .. (row = piece / NPB of
 // the stacked [W_hh^T rows ; (W_ih W2)^T rows] (2 DH rows), part = piece % NPB).
-template <int DH, int NPB, int PPT, bool MASKED>
+template <int DH, int NPB, int PPT, bool MASKED, bool UNIMIX>
 __global__ __launch_bounds__(kCluThreads) void mrssm_bwd_cluster_kernel(const MtrssmMrssmDims dm, const MtrssmMrssmClusterWeights w,
                                                                         const MtrssmMrssmBwdIO io, unsigned long long* __restrict__ gran,
                                                                         int* __restrict__ status, int nclusters) {
@@ -576,6 +590,8 @@ __global__ __launch_bounds__(kCluThreads) void mrssm_bwd_cluster_kernel(const Mt
           cat_block_bwd<true>(lds + Lmx, lds + Llp, K, C, lane, lds + Lgps, lds + Lcs, io.g_prior_stoch ? io.g_prior_stoch + bt * S : nullptr,
                               io.g_post_logits ? io.g_post_logits + bt * S : nullptr, io.g_prior_logits ? io.g_prior_logits + bt * S : nullptr,
                               *gk_lds, dm.kl_w_post, dm.kl_w_prior, lds + Ldmx, lds + Ldlp);
+        if (UNIMIX)  // d x' -> d x at the raw logits; then the raw mix back in place of the staged x'
+          cluster_unimix_bwd<MASKED>(lds + Lmx, lds + Llp, lds + Ldmx, lds + Ldlp, lds + Lla, lds + Llv, K, C, lane, code, lw, dm.unimix);
         const ExpertLogW g_lw = wave_mopoe_mix_bwd_masked<true, MASKED>(lds + Lla, lds + Llv, lds + Lmx, lds + Ldmx, lds + Ldla, lds + Ldlv,
                                                                         lds + Ldlp, S, lane, code, lw, MASKED && io.expert_logw != nullptr);
         if (MASKED) store_g_expert_logw(io.g_expert_logw, bt, g_lw, lane, member == 0);
@@ -777,6 +793,8 @@ int mrssm_cluster_supported(const MtrssmMrssmDims* d);
 
 int mrssm_bwd_cluster_launch(const MtrssmMrssmDims* d, const MtrssmMrssmClusterWeights* w, const MtrssmMrssmBwdIO* io, void* workspace,
                              size_t workspace_bytes, hipStream_t stream) {
+  if (d)
+    if (int rc = check_unimix("mrssm_rollout_bwd_cluster", d->unimix)) return rc;
   if (!mrssm_cluster_supported(d) || d->K * d->C > 32) {
     set_error("mrssm_rollout_bwd_cluster: dims outside the cluster kernel's regime (ask mtrssm_mrssm_cluster_supported first; S <= 32)");
     return MTRSSM_EINVAL;
@@ -801,21 +819,24 @@ int mrssm_bwd_cluster_launch(const MtrssmMrssmDims* d, const MtrssmMrssmClusterW
   hipError_t e = hipSuccess;
   int* status = reinterpret_cast<int*>(workspace);
   unsigned long long* gran = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(workspace) + 16);
-#define MTRSSM_CLUB_LAUNCH_M(DHV, NPV, PPTV, MV)                                                                                    \
+#define MTRSSM_CLUB_LAUNCH_M(DHV, NPV, PPTV, MV, UV)                                                                                   \
   {                                                                                                                               \
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(mrssm_bwd_cluster_kernel<DHV, NPV, PPTV, MV>),                          \
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(mrssm_bwd_cluster_kernel<DHV, NPV, PPTV, MV, UV>),                          \
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                               \
     if (e != hipSuccess) { set_error("hipFuncSetAttribute(max dynamic LDS=%zu): %s", lds, hipGetErrorString(e)); return MTRSSM_ELAUNCH; } \
-    set_last_kernel("mtrssm::mrssm_bwd_cluster_kernel<" #DHV ", " #NPV ", " #PPTV ", " #MV ">");                                 \
-    hipLaunchKernelGGL((mrssm_bwd_cluster_kernel<DHV, NPV, PPTV, MV>), dim3(grid), dim3(kCluThreads), lds, stream, *d, *w, *io,     \
+    set_last_kernel("mtrssm::mrssm_bwd_cluster_kernel<" #DHV ", " #NPV ", " #PPTV ", " #MV ", " #UV ">");                                 \
+    hipLaunchKernelGGL((mrssm_bwd_cluster_kernel<DHV, NPV, PPTV, MV, UV>), dim3(grid), dim3(kCluThreads), lds, stream, *d, *w, *io,     \
                        gran, status, nclusters);                                                                                  \
   }
 #define MTRSSM_CLUB_LAUNCH(DHV, NPV, PPTV)                      \
   {                                                            \
-    if (io->modality) MTRSSM_CLUB_LAUNCH_M(DHV, NPV, PPTV, true) \
-    else MTRSSM_CLUB_LAUNCH_M(DHV, NPV, PPTV, false)             \
+    if (io->modality && mixing) MTRSSM_CLUB_LAUNCH_M(DHV, NPV, PPTV, true, true)  \
+    else if (io->modality) MTRSSM_CLUB_LAUNCH_M(DHV, NPV, PPTV, true, false)       \
+    else if (mixing) MTRSSM_CLUB_LAUNCH_M(DHV, NPV, PPTV, false, true)             \
+    else MTRSSM_CLUB_LAUNCH_M(DHV, NPV, PPTV, false, false)                        \
   }
   // row pieces per thread = ceil(2 DH NPB / 256)
+  const bool mixing = d->unimix > 0.f;  // its own instances: the default launch runs the code it ran before the option existed
   if (d->D == 32) MTRSSM_CLUB_LAUNCH(32, 1, 1)
   else if (d->D == 64) MTRSSM_CLUB_LAUNCH(64, 1, 1)
   else if (d->D == 128) MTRSSM_CLUB_LAUNCH(128, 3, 3)
@@ -876,6 +897,8 @@ int mrssm_cluster_supported(const MtrssmMrssmDims* d) {
 
 int mrssm_fwd_cluster_launch(const MtrssmMrssmDims* d, const MtrssmMrssmClusterWeights* w, const MtrssmMrssmFwdIO* io, void* workspace,
                              size_t workspace_bytes, hipStream_t stream) {
+  if (d)
+    if (int rc = check_unimix("mrssm_rollout_fwd_cluster", d->unimix)) return rc;
   if (!mrssm_cluster_supported(d)) {
     set_error("mrssm_rollout_fwd_cluster: dims outside the cluster kernel's regime (ask mtrssm_mrssm_cluster_supported first)");
     return MTRSSM_EINVAL;
@@ -902,21 +925,24 @@ int mrssm_fwd_cluster_launch(const MtrssmMrssmDims* d, const MtrssmMrssmClusterW
   int* status = reinterpret_cast<int*>(workspace);
   unsigned long long* gran = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(workspace) + 16);
   const int kw = cluster_kw(d->D, d->H);
-#define MTRSSM_CLU_LAUNCH_M(DHV, NPV, PPTV, MV)                                                                                     \
+#define MTRSSM_CLU_LAUNCH_M(DHV, NPV, PPTV, MV, UV)                                                                                    \
   {                                                                                                                               \
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(mrssm_fwd_cluster_kernel<DHV, NPV, PPTV, MV>),                          \
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(mrssm_fwd_cluster_kernel<DHV, NPV, PPTV, MV, UV>),                          \
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                               \
     if (e != hipSuccess) { set_error("hipFuncSetAttribute(max dynamic LDS=%zu): %s", lds, hipGetErrorString(e)); return MTRSSM_ELAUNCH; } \
-    set_last_kernel("mtrssm::mrssm_fwd_cluster_kernel<" #DHV ", " #NPV ", " #PPTV ", " #MV ">");                                 \
-    hipLaunchKernelGGL((mrssm_fwd_cluster_kernel<DHV, NPV, PPTV, MV>), dim3(grid), dim3(kCluThreads), lds, stream, *d, *w, *io,     \
+    set_last_kernel("mtrssm::mrssm_fwd_cluster_kernel<" #DHV ", " #NPV ", " #PPTV ", " #MV ", " #UV ">");                                 \
+    hipLaunchKernelGGL((mrssm_fwd_cluster_kernel<DHV, NPV, PPTV, MV, UV>), dim3(grid), dim3(kCluThreads), lds, stream, *d, *w, *io,     \
                        gran, status, nclusters);                                                                                  \
   }
 #define MTRSSM_CLU_LAUNCH(DHV, NPV, PPTV)                      \
   {                                                           \
-    if (io->modality) MTRSSM_CLU_LAUNCH_M(DHV, NPV, PPTV, true) \
-    else MTRSSM_CLU_LAUNCH_M(DHV, NPV, PPTV, false)             \
+    if (io->modality && mixing) MTRSSM_CLU_LAUNCH_M(DHV, NPV, PPTV, true, true)  \
+    else if (io->modality) MTRSSM_CLU_LAUNCH_M(DHV, NPV, PPTV, true, false)       \
+    else if (mixing) MTRSSM_CLU_LAUNCH_M(DHV, NPV, PPTV, false, true)             \
+    else MTRSSM_CLU_LAUNCH_M(DHV, NPV, PPTV, false, false)                        \
   }
   // pieces per thread = ceil(2 * (3 DH / 4) * NP / 256)
+  const bool mixing = d->unimix > 0.f;  // its own instances, as in the backward launcher
   if (kw == 32) MTRSSM_CLU_LAUNCH(32, 1, 1)
   else if (kw == 64) MTRSSM_CLU_LAUNCH(64, 2, 1)
   else if (kw == 128) MTRSSM_CLU_LAUNCH(128, 4, 3)

@@ -138,6 +138,10 @@ __global__ __launch_bounds__(1024) void mrssm_fwd_kernel(const MtrssmMrssmDims d
       if (POST)
         wave_mopoe_mix_masked<false, MASKED>(r_ + L.la, r_ + L.lv, r_ + L.lp, r_ + L.mx, S, lane, modality_code<MASKED>(io.modality, q),
                                              expert_logw<MASKED>(io.expert_logw, q));
+      if (unimix_on(dm.unimix)) {  // uniform mixing, before the logits are stored, sampled or enter the KL
+        wave_unimix_fwd(r_ + L.lp, K, C, lane, dm.unimix);
+        if (POST) wave_unimix_fwd(r_ + L.mx, K, C, lane, dm.unimix);
+      }
       for (int s = lane; s < S; s += kWave) {
         if (ok) {
           io.prior_logits[q * S + s] = r_[L.lp + s];
@@ -234,11 +238,17 @@ __global__ __launch_bounds__(1024) void mrssm_bwd_kernel(const MtrssmMrssmDims d
                     io.g_post_logits ? io.g_post_logits + q * S : nullptr,
                     io.g_prior_logits ? io.g_prior_logits + q * S : nullptr, gk, dm.kl_w_post, dm.kl_w_prior,
                     r + L.dmx, r + L.dlp);
+      const int code = modality_code<MASKED>(io.modality, q);
+      const ExpertLogW lw = expert_logw<MASKED>(io.expert_logw, q);
+      if (unimix_on(dm.unimix)) {  // d x' -> d x at the raw logits; then the raw mix back in place of the staged x'
+        wave_unimix_bwd(r + L.mx, r + L.dmx, K, C, lane, dm.unimix);
+        wave_unimix_bwd(r + L.lp, r + L.dlp, K, C, lane, dm.unimix);
+        wave_mopoe_remix<false, MASKED>(r + L.la, r + L.lv, r + L.mx, S, lane, code, lw);
+      }
       // back through logsumexp over {A, V, A+V} and the two flat log-softmaxes (masked: over the present experts)
       const ExpertLogW g_lw =
           wave_mopoe_mix_bwd_masked<false, MASKED>(r + L.la, r + L.lv, r + L.mx, r + L.dmx, r + L.dla, r + L.dlv, r + L.dlp, S, lane,
-                                                   modality_code<MASKED>(io.modality, q), expert_logw<MASKED>(io.expert_logw, q),
-                                                   MASKED && io.expert_logw != nullptr);
+                                                   code, lw, MASKED && io.expert_logw != nullptr);
       if (MASKED) store_g_expert_logw(io.g_expert_logw, q, g_lw, lane, valid[rb]);
       if (valid[rb]) {
         for (int s = lane; s < S; s += kWave) {
@@ -387,6 +397,7 @@ static int check_dims(const MtrssmMrssmDims* d) {
     set_error("mrssm: unknown activation id %d", d->act);
     return MTRSSM_EINVAL;
   }
+  if (int rc = check_unimix("mrssm", d->unimix)) return rc;
   if (d->threads < 0 || d->threads > 1024 || d->threads % kWave) {
     set_error("mrssm: threads must be a multiple of 64 in [64, 1024] (0 = default)");
     return MTRSSM_EINVAL;

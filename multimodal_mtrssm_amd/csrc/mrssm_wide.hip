@@ -181,6 +181,10 @@ __global__ __launch_bounds__(kWT) void mrssm_wide_fwd_kernel(const WideFwdArgs a
           MTRSSM_WIDE_STAMP(10);
           if (wave == 0) {
             wave_mopoe_mix_masked<true, MASKED>(Lla, Llv, Llp, Lmx, S, lane, code, lw);
+            if (unimix_on(a.dm.unimix)) {  // uniform mixing, before the logits are stored, sampled or enter the KL
+              wave_unimix_fwd_coop(Llp, K, C, lane, a.dm.unimix);
+              wave_unimix_fwd_coop(Lmx, K, C, lane, a.dm.unimix);
+            }
             MTRSSM_WIDE_STAMP(11);
             for (int s2 = lane; s2 < S; s2 += kWave) {
               io.prior_logits[q * S + s2] = Llp[s2];
@@ -446,6 +450,11 @@ __global__ __launch_bounds__(kWT) void mrssm_wide_bwd_kernel(const WideBwdArgs a
             cat_block_bwd<true>(Lmx, Llp, K, C, lane, Lgps, Lcs, io.g_prior_stoch ? io.g_prior_stoch + q * S : nullptr,
                                 io.g_post_logits ? io.g_post_logits + q * S : nullptr, io.g_prior_logits ? io.g_prior_logits + q * S : nullptr,
                                 gk, a.dm.kl_w_post, a.dm.kl_w_prior, Ldmx, Ldlp);
+          if (unimix_on(a.dm.unimix)) {  // d x' -> d x at the raw logits; then the raw mix back in place of the staged x'
+            wave_unimix_bwd_coop(Lmx, Ldmx, K, C, lane, a.dm.unimix);
+            wave_unimix_bwd_coop(Llp, Ldlp, K, C, lane, a.dm.unimix);
+            wave_mopoe_remix<true, MASKED>(Lla, Llv, Lmx, S, lane, code, lw);
+          }
           MTRSSM_WIDE_STAMP(12);
           const ExpertLogW g_lw =
               wave_mopoe_mix_bwd_masked<true, MASKED>(Lla, Llv, Lmx, Ldmx, Ldla, Ldlv, Ldlp, S, lane, code, lw, MASKED && io.expert_logw != nullptr);
@@ -674,6 +683,8 @@ static size_t wide_bwd_lds(const MtrssmMrssmDims* d) {
 
 int mrssm_wide_fwd_launch(const MtrssmMrssmDims* d, const MtrssmMrssmClusterWeights* w, const MtrssmMrssmFwdIO* io, int pieces,
                           void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  if (d)
+    if (int rc = check_unimix("mrssm_rollout_fwd_wide", d->unimix)) return rc;
   if (!mrssm_wide_supported(d, pieces)) return wide_not_supported("mrssm_rollout_fwd_wide", "mrssm");
   if (!w || !io || !workspace || !w->w1s_t || !w->wf_t || !w->bf || !w->whh_t || !w->bhh || !w->wh1_t || !w->b3 || !w->w4 || !w->b4 ||
       !w->wa2 || !w->ba2 || !w->wv2 || !w->bv2 || !io->xa || !io->pa || !io->pv || !io->deter0 || !io->stoch0 || !io->u_post ||
@@ -720,6 +731,8 @@ int mrssm_wide_fwd_launch(const MtrssmMrssmDims* d, const MtrssmMrssmClusterWeig
 
 int mrssm_wide_bwd_launch(const MtrssmMrssmDims* d, const MtrssmMrssmClusterWeights* w, const MtrssmMrssmBwdIO* io, int pieces,
                           void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  if (d)
+    if (int rc = check_unimix("mrssm_rollout_bwd_wide", d->unimix)) return rc;
   if (!mrssm_wide_supported(d, pieces)) return wide_not_supported("mrssm_rollout_bwd_wide", "mrssm");
   if (!w || !io || !workspace || !w->w1s_t || !w->wf_t || !w->whh_t || !w->wh1_t || !w->w4 || !w->wa2 || !w->wv2 || !io->deter0 ||
       !io->deter || !io->prior_logits || !io->post_logits || !io->sv_h1 || !io->sv_gates || !io->sv_heads || !io->sv_la || !io->sv_lv ||

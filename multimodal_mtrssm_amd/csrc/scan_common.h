@@ -27,6 +27,13 @@ inline int check_launch(const char* what) {
   return MTRSSM_OK;
 }
 
+// dims.unimix of either scan: eps in [0, 1); NaN fails both comparisons.  Every scan entry point checks it first.
+inline int check_unimix(const char* who, float eps) {
+  if (eps >= 0.f && eps < 1.f) return MTRSSM_OK;
+  set_error("%s: unimix must lie in [0, 1) (got %g)", who, (double)eps);
+  return MTRSSM_EINVAL;
+}
+
 constexpr float kLogThird = -1.0986122886681098f;  // log(1/3), mrssm/mopoe_mrssm/core.py:141-142
 
 __device__ __forceinline__ float act_fwd(float z, int act) {
@@ -301,6 +308,16 @@ __device__ __forceinline__ void wave_mopoe_mix_masked(const float* la, const flo
   for (int s = lane; s < S; s += kWave) mixed[s] = (l[s] - m) - ls;
 }
 
+// With unimix on, the backward scans stage x' (the stored posterior logits) where wave_mopoe_mix_bwd expects the raw flat mix
+// with its offset: recompute it from the staged experts with the forward's own helper (the same bits), after the categorical
+// block and the unimix backward have read x'.  Only the both-present branch of the mix backward reads `mixed`.
+template <bool FAST, bool MASKED>
+__device__ __forceinline__ void wave_mopoe_remix(const float* la, const float* lv, float* mixed, int S, int lane, int code,
+                                                 const ExpertLogW lw = kThirds) {
+  if (!MASKED) wave_mopoe_mix<FAST>(la, lv, mixed, S, lane);
+  else if (code == kModBoth) wave_mopoe_mix<FAST>(la, lv, mixed, S, lane, lw);
+}
+
 // Per-categorical softmax statistics for category k: max and log-sum
 template <bool FAST = false>
 __device__ __forceinline__ void cat_stats(const float* x, int C, float& mx, float& sum) {
@@ -310,6 +327,105 @@ __device__ __forceinline__ void cat_stats(const float* x, int C, float& mx, floa
   for (int c = 0; c < C; ++c) s += cexp<FAST>(x[c] - m);
   mx = m;
   sum = s;
+}
+
+// ---------------------------------------------------------------------------------------
+// Uniform mixing ("unimix", dims.unimix = eps in (0, 1)), one wave per row, lane k owns categorical k, in place on the LDS logits:
+//   x'_c = log((1 - eps) softmax(x)_c + eps / C)
+// so that softmax(x') is the mixed distribution and the categorical blocks run on x' unchanged.  Callers guard every call with a
+// wave-uniform `eps > 0` on the kernel argument: an eps == 0 launch runs none of this.  The same call on the same bits gives the
+// same bits, which is what keeps posterior == prior exact on a masked step with no modality (the raw prior logits are copied
+// first, then both sides are mixed).
+// ---------------------------------------------------------------------------------------
+// The guard of the call sites in the single-CU and the wide scans: wave-uniform on the kernel argument, marked unlikely so that the
+// default launch (eps == 0) keeps the straight path.  (The cluster kernels take the setting as a template parameter instead.)
+__device__ __forceinline__ bool unimix_on(float eps) { return __builtin_expect(eps > 0.f, 0); }
+
+template <bool FAST = false>
+__device__ __forceinline__ void wave_unimix_fwd(float* x, int K, int C, int lane, float eps) {
+  const float keep = 1.f - eps, floor_p = eps / (float)C;
+  for (int k = lane; k < K; k += kWave) {
+    float* xl = x + k * C;
+    float m, s;
+    cat_stats<FAST>(xl, C, m, s);
+    for (int c = 0; c < C; ++c) xl[c] = clog<FAST>(fmaf(keep, cexp<FAST>(xl[c] - m) / s, floor_p));
+  }
+}
+
+// The register form for the cooperative kernels' critical path (C <= 8, hardware exp / log, one reciprocal).
+__device__ __forceinline__ void wave_unimix_fwd_fast8(float* x, int K, int C, int lane, float eps) {
+  const float keep = 1.f - eps, floor_p = eps / (float)C;
+  for (int k = lane; k < K; k += kWave) {
+    float* xl = x + k * C;
+    float v[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) v[c] = c < C ? xl[c] : -INFINITY;
+    float m = v[0];
+#pragma unroll
+    for (int c = 1; c < 8; ++c) m = fmaxf(m, v[c]);
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      v[c] = c < C ? __expf(v[c] - m) : 0.f;
+      s += v[c];
+    }
+    const float r = keep * __frcp_rn(s);
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+      if (c < C) xl[c] = __logf(fmaf(v[c], r, floor_p));
+  }
+}
+
+// Backward of the transform, in place on dx (d x' on entry, d x on exit), from the staged x' alone: the raw softmax is
+//   m_c = exp(x'_c),  s_c = max(0, (m_c - eps / C) / (1 - eps)),  h_c = (1 - eps) dx'_c / m_c,  dx_c = s_c (h_c - sum_j s_j h_j).
+template <bool FAST = false>
+__device__ __forceinline__ void wave_unimix_bwd(const float* xp, float* dx, int K, int C, int lane, float eps) {
+  const float keep = 1.f - eps, floor_p = eps / (float)C, rkeep = 1.f / keep;
+  for (int k = lane; k < K; k += kWave) {
+    const float* xl = xp + k * C;
+    float* dl = dx + k * C;
+    float dot = 0.f;
+    for (int c = 0; c < C; ++c) {
+      const float m = cexp<FAST>(xl[c]);
+      const float s = fmaxf(0.f, (m - floor_p) * rkeep);
+      dot = fmaf(s, keep * dl[c] / m, dot);
+    }
+    for (int c = 0; c < C; ++c) {
+      const float m = cexp<FAST>(xl[c]);
+      const float s = fmaxf(0.f, (m - floor_p) * rkeep);
+      dl[c] = s * (keep * dl[c] / m - dot);
+    }
+  }
+}
+
+__device__ __forceinline__ void wave_unimix_bwd_fast8(const float* xp, float* dx, int K, int C, int lane, float eps) {
+  const float keep = 1.f - eps, floor_p = eps / (float)C, rkeep = __frcp_rn(keep);
+  for (int k = lane; k < K; k += kWave) {
+    const float* xl = xp + k * C;
+    float* dl = dx + k * C;
+    float s[8], h[8], dot = 0.f;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      const bool in = c < C;
+      const float m = in ? __expf(xl[c]) : 1.f;
+      s[c] = in ? fmaxf(0.f, (m - floor_p) * rkeep) : 0.f;
+      h[c] = in ? keep * dl[c] * __frcp_rn(m) : 0.f;
+      dot = fmaf(s[c], h[c], dot);
+    }
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+      if (c < C) dl[c] = s[c] * (h[c] - dot);
+  }
+}
+
+// The forms the cooperative kernels call: registers where the class count allows it.
+__device__ __forceinline__ void wave_unimix_fwd_coop(float* x, int K, int C, int lane, float eps) {
+  if (C <= 8) wave_unimix_fwd_fast8(x, K, C, lane, eps);
+  else wave_unimix_fwd<true>(x, K, C, lane, eps);
+}
+__device__ __forceinline__ void wave_unimix_bwd_coop(const float* xp, float* dx, int K, int C, int lane, float eps) {
+  if (C <= 8) wave_unimix_bwd_fast8(xp, dx, K, C, lane, eps);
+  else wave_unimix_bwd<true>(xp, dx, K, C, lane, eps);
 }
 
 // inverse-CDF index: number of c in [0, C-2] whose inclusive cumulative probability is <= u

@@ -110,15 +110,44 @@ class MultiOneHot:
 Distribution = MultiOneHot
 
 
-class MultiOneHotFactory(nn.Module):
-    """``forward(flat_logits[*, K*C]) -> MultiOneHot`` (YAML: ``l_dist`` / ``h_dist``, mmtrssm yaml 138-147)."""
+def check_unimix(value: float) -> float:
+    """``unimix`` as a float in ``[0, 1)`` (NaN fails both comparisons), else ValueError."""
+    eps = float(value)
+    if not (0.0 <= eps < 1.0):
+        msg = f"unimix must lie in [0, 1), got {value!r}"
+        raise ValueError(msg)
+    return eps
 
-    def __init__(self, class_size: int, category_size: int) -> None:
+
+def unimix_logits(flat: Tensor, category_size: int, class_size: int, eps: float) -> Tensor:
+    """``log((1 - eps) softmax(x) + eps / C)`` per categorical of flat logits ``[*, K*C]``: the
+    logits-to-logits form of uniform mixing the scan kernels apply (``csrc/scan_common.h: wave_unimix_fwd``)."""
+    shaped = flat.reshape(*flat.shape[:-1], category_size, class_size)
+    mixed = (1.0 - eps) * torch.softmax(shaped, dim=-1) + eps / class_size
+    return mixed.log().reshape(flat.shape)
+
+
+class MultiOneHotFactory(nn.Module):
+    """``forward(flat_logits[*, K*C]) -> MultiOneHot`` (YAML: ``l_dist`` / ``h_dist``, mmtrssm yaml 138-147).
+
+    ``unimix`` = eps in ``[0, 1)``: ``forward`` returns the distribution ``(1 - eps) softmax + eps / C`` per
+    categorical, and the scans read eps from here and mix inside the kernels.  A plain attribute (no parameter, buffer or
+    state-dict key); 0 = the reference's distribution, the same bits as without it."""
+
+    def __init__(self, class_size: int, category_size: int, unimix: float = 0.0) -> None:
         super().__init__()
         self.class_size = int(class_size)
         self.category_size = int(category_size)
+        self.unimix = check_unimix(unimix)
 
     def forward(self, logits: Tensor) -> MultiOneHot:
+        if self.unimix > 0.0:
+            logits = unimix_logits(logits, self.category_size, self.class_size, self.unimix)
+        return MultiOneHot.from_flat_logits(logits, self.category_size, self.class_size)
+
+    def unmixed(self, logits: Tensor) -> MultiOneHot:
+        """The distribution of ``logits`` as they are: for the scans' outputs (with ``unimix`` they already are the mixed
+        log-probabilities) and for the initial state's head, which is never mixed."""
         return MultiOneHot.from_flat_logits(logits, self.category_size, self.class_size)
 
 

@@ -42,9 +42,10 @@ def decoder_config(in_features: int, out_shape: tuple[int, int, int], channels: 
 def make_mrssm(*, deter: int, hidden: int, classes: int, cats: int, action: int, embed: int,  # noqa: PLR0913
                enc_audio: dict[str, Any], enc_vision: dict[str, Any], dec_audio: dict[str, Any], dec_vision: dict[str, Any],
                activation: str = "ELU", init_cells: int = 200, kl_coeff: float = 1.0,
-               use_kl_balancing: bool = True, expert_weights: str | None = None) -> MoPoE_MRSSM:
+               use_kl_balancing: bool = True, expert_weights: str | None = None, unimix: float = 0.0) -> MoPoE_MRSSM:
     """``expert_weights``: None (the reference's 1/3 each, its state-dict keys), or ``"static"`` / ``"gated"``: a
-    ``WeightedMoPoE_MRSSM`` with that ``ExpertWeights`` (the YAML key of the same name)."""
+    ``WeightedMoPoE_MRSSM`` with that ``ExpertWeights`` (the YAML key of the same name).  ``unimix``: eps of the
+    uniform mixing of the categorical latents, 0 = off."""
     rep = {"deterministic_size": deter, "hidden_size": hidden, "obs_embed_size": embed,
            "distribution_config": [classes, cats], "activation_name": activation}
     weighted = {} if expert_weights is None else {"expert_weights": expert_weights}
@@ -55,7 +56,7 @@ def make_mrssm(*, deter: int, hidden: int, classes: int, cats: int, action: int,
         audio_encoder=Encoder(enc_audio), vision_encoder=Encoder(enc_vision),
         audio_decoder=Decoder(dec_audio), vision_decoder=Decoder(dec_vision),
         init_proj=MLP(in_features=embed, out_features=deter, num_cells=init_cells, depth=1),
-        kl_coeff=kl_coeff, use_kl_balancing=use_kl_balancing, **weighted,
+        kl_coeff=kl_coeff, use_kl_balancing=use_kl_balancing, unimix=unimix, **weighted,
     )
 
 
@@ -63,9 +64,9 @@ def make_mmtrssm(*, hd: int, hs: tuple[int, int], ld: int, ls: tuple[int, int], 
                  enc_audio: dict[str, Any], enc_vision: dict[str, Any], dec_audio: dict[str, Any],
                  dec_vision: dict[str, Any], l_tau: float = 2.0, h_tau: float = 4.0, activation: str = "ELU",
                  init_cells: int = 200, kl_coeff: float = 1.0, w_kl_h: float = 1.0,
-                 use_kl_balancing: bool = True, expert_weights: str | None = None) -> MoPoE_MMTRSSM:
-    """``hs`` / ``ls`` = (class_size, category_size) of ``h_dist`` / ``l_dist`` (mmtrssm yaml 138-147).  ``expert_weights``: as
-    ``make_mrssm``."""
+                 use_kl_balancing: bool = True, expert_weights: str | None = None, unimix: float = 0.0) -> MoPoE_MMTRSSM:
+    """``hs`` / ``ls`` = (class_size, category_size) of ``h_dist`` / ``l_dist`` (mmtrssm yaml 138-147).  ``expert_weights`` and
+    ``unimix``: as ``make_mrssm``."""
     hs_dim, ls_dim = hs[0] * hs[1], ls[0] * ls[1]
     rep = {"deterministic_size": ld, "hidden_size": hidden, "obs_embed_size": embed,
            "distribution_config": [ls[0], ls[1]], "activation_name": activation}
@@ -82,5 +83,5 @@ def make_mmtrssm(*, hd: int, hs: tuple[int, int], ld: int, ls: tuple[int, int], 
         h_prior=MLP(hd, hs_dim, hidden, 1, act), h_posterior=MLP(ld + hd, hs_dim, hidden, 1, act),
         l_dist=MultiOneHotFactory(class_size=ls[0], category_size=ls[1]),
         h_dist=MultiOneHotFactory(class_size=hs[0], category_size=hs[1]),
-        w_kl_h=w_kl_h, **weighted,
+        w_kl_h=w_kl_h, unimix=unimix, **weighted,
     )

@@ -152,7 +152,7 @@ class Transition(nn.Module):
         from multimodal_mtrssm_amd.scan import mrssm_prior_rollout  # noqa: PLC0415
 
         out = mrssm_prior_rollout(self, action.unsqueeze(1), prev_state.deter, prev_state.stoch, u_prior=None)
-        dist = self.distribution_factory(out["prior_logits"][:, 0])
+        dist = self.distribution_factory.unmixed(out["prior_logits"][:, 0])  # (the scan has mixed them)
         return State(deter=out["deter"][:, 0], distribution=dist, stoch=out["prior_stoch"][:, 0])
 
 

@@ -37,10 +37,21 @@ class ScanConfig:
     balancing: bool = True
     rows_per_block: int = 0
     threads: int = 0
+    unimix: float = 0.0  # eps of the uniform mixing inside the kernels; read from the factories
 
     @property
     def kl_weights(self) -> tuple[float, float]:
         return (1.0 - KL_BALANCE_ALPHA, KL_BALANCE_ALPHA) if self.balancing else (1.0, 1.0)
+
+
+def unimix_of(*factories) -> float:  # noqa: ANN002
+    """The one ``unimix`` the distribution factories of a scan agree on (one constant kernel argument serves every categorical
+    the scan forms); ValueError if they differ."""
+    values = {float(getattr(f, "unimix", 0.0)) for f in factories}
+    if len(values) != 1:
+        msg = f"the distribution factories of one scan disagree on unimix: {sorted(values)} (set model.unimix)"
+        raise ValueError(msg)
+    return values.pop()
 
 
 KERNEL_TIMERS = _lib.TIMERS
@@ -378,7 +389,7 @@ class _MrssmScan(torch.autograd.Function):
             kl=kl, **sv, modality=modality, expert_logw=expert_logw,
         )
         wp, wq = cfg.kl_weights
-        dims = _lib.MrssmDims(B, T, D, H, cfg.cats, cfg.classes, cfg.act, 1, wp, wq, cfg.rows_per_block, cfg.threads)
+        dims = _lib.MrssmDims(B, T, D, H, cfg.cats, cfg.classes, cfg.act, 1, wp, wq, cfg.rows_per_block, cfg.threads, cfg.unimix)
         # algorithmic work: per (b,t) the scan reads xa,pa,pv + two uniform rows and writes deter, three
         # S-wide rows, kl and (training) the saved activations; FLOPs = 2 x every weight element touched per row-step
         per_bt = 3 * H + 2 * K + D + 3 * S + 1 + (2 * H + 4 * D + 3 * H + 2 * S if need_grad else 0)
@@ -460,7 +471,7 @@ class _MrssmScan(torch.autograd.Function):
             d_lv=d_lv, modality=ctx.modality, expert_logw=ctx.expert_logw, g_expert_logw=g_logw,
         )
         wp, wq = cfg.kl_weights
-        dims = _lib.MrssmDims(B, T, D, H, cfg.cats, cfg.classes, cfg.act, 1, wp, wq, cfg.rows_per_block, cfg.threads)
+        dims = _lib.MrssmDims(B, T, D, H, cfg.cats, cfg.classes, cfg.act, 1, wp, wq, cfg.rows_per_block, cfg.threads, cfg.unimix)
         per_bt = (2 * H + 4 * D + 3 * H + 2 * S) + D + 2 * S + (D + S + 1) + 2 * H + 6 * D + 3 * H + 3 * S
         macs = S * H + H * H + 3 * D * H + 3 * D * D + 3 * H * D + 3 * S * H
         cw3 = getattr(ctx, "cluster_w", None)
@@ -547,7 +558,8 @@ def mrssm_posterior_rollout(  # noqa: PLR0913
     if len(act_names) != 1:
         msg = f"the HIP scan uses one activation for all heads, got {sorted(act_names)}"
         raise NotImplementedError(msg)
-    cfg = ScanConfig(K, Cc, _lib.ACT_IDS[act_names.pop()], balancing, rows_per_block, threads)
+    cfg = ScanConfig(K, Cc, _lib.ACT_IDS[act_names.pop()], balancing, rows_per_block, threads,
+                     unimix_of(factory, audio_rep.distribution_factory, vision_rep.distribution_factory))
     # hoisted, recurrence-independent halves of the first layers: plain library GEMMs
     # (independent of each other: side by side in one launch each way; an absent modality's projection is not run)
     present = [(embed, layer) for embed, layer in ((audio_embed, a1), (vision_embed, v1)) if embed is not None]
@@ -565,14 +577,17 @@ def mrssm_posterior_rollout(  # noqa: PLR0913
             "prior_stoch": prior_stoch if u_prior is not None else None, "kl": kl}
 
 
-def _st_sample(logits: Tensor, cats: int, classes: int, u: Tensor) -> tuple[Tensor, Tensor]:
+def _st_sample(logits: Tensor, cats: int, classes: int, u: Tensor, unimix: float = 0.0) -> tuple[Tensor, Tensor, Tensor]:
     """Straight-through one-hot sample of K C-way categoricals from flat logits and given uniforms (inverse CDF on the detached
-    probabilities, ``onehot + probs - probs.detach()``: distributions.MultiOneHot.rsample)."""
-    from multimodal_mtrssm_amd.distributions import onehot_from_uniforms  # noqa: PLC0415
+    probabilities, ``onehot + probs - probs.detach()``: distributions.MultiOneHot.rsample).  With ``unimix`` the logits are mixed
+    first; returns (sample, probabilities, the logits sampled from)."""
+    from multimodal_mtrssm_amd.distributions import onehot_from_uniforms, unimix_logits  # noqa: PLC0415
 
+    if unimix > 0.0:
+        logits = unimix_logits(logits, cats, classes, unimix)
     probs = torch.softmax(logits.reshape(*logits.shape[:-1], cats, classes), dim=-1)
     onehot = onehot_from_uniforms(probs.detach(), u)
-    return (onehot + (probs - probs.detach())).flatten(start_dim=-2), probs
+    return (onehot + (probs - probs.detach())).flatten(start_dim=-2), probs, logits
 
 
 def _mrssm_prior_rollout_differentiable(transition, actions: Tensor, deter0: Tensor, stoch0: Tensor,  # noqa: ANN001
@@ -599,7 +614,7 @@ def _mrssm_prior_rollout_differentiable(transition, actions: Tensor, deter0: Ten
         r, z = torch.sigmoid(i_r + h_r), torch.sigmoid(i_z + h_z)
         deter = (1.0 - z) * torch.tanh(i_n + r * h_n) + z * deter   # torch.nn.GRUCell's update
         logits = transition.rnn_to_prior_projector(_c(deter))
-        stoch, _ = _st_sample(logits, cats, classes, u_prior[:, t])
+        stoch, _, logits = _st_sample(logits, cats, classes, u_prior[:, t], factory.unimix)
         deters.append(deter)
         logits_all.append(logits)
         stochs.append(stoch)
@@ -638,7 +653,7 @@ def mrssm_prior_rollout(transition, actions: Tensor, deter0: Tensor, stoch0: Ten
         io = _lib.fill(_lib.MrssmFwdIO(), xa=xa, deter0=deter0, stoch0=stoch0, u_prior=u_prior, deter=deter,
                        prior_logits=prior_logits, prior_stoch=prior_stoch)
         act = _lib.ACT_IDS[transition.action_state_projector.activation_name]
-        dims = _lib.MrssmDims(B, T, D, H, K, Cc, act, 0, 1.0, 1.0, rows_per_block, threads)
+        dims = _lib.MrssmDims(B, T, D, H, K, Cc, act, 0, 1.0, 1.0, rows_per_block, threads, unimix_of(factory))
         _lib.check(lib.mtrssm_mrssm_rollout_fwd(C.byref(dims), C.byref(fw), C.byref(io), _lib.stream_ptr(xa.device)),
                    "mtrssm_mrssm_rollout_fwd(prior-only)")
         del tensors
@@ -660,6 +675,7 @@ class MTScanConfig:
     balancing: bool = True
     rows_per_block: int = 0
     threads: int = 0
+    unimix: float = 0.0  # as ScanConfig.unimix: one eps for both levels
 
     @property
     def kl_weights(self) -> tuple[float, float]:
@@ -669,7 +685,7 @@ class MTScanConfig:
         wp, wq = self.kl_weights
         return _lib.MmtrssmDims(B, T, LD, HD, H, self.kl_cats, self.kl_classes, self.kh_cats, self.kh_classes, self.act, post,
                                 self.tau_l, self.tau_h, 1.0 - 1.0 / self.tau_l, 1.0 - 1.0 / self.tau_h, wp, wq,
-                                self.rows_per_block, self.threads)
+                                self.rows_per_block, self.threads, self.unimix)
 
 
 class _MmtrssmScan(torch.autograd.Function):
@@ -854,6 +870,12 @@ def _mt_act(model) -> int:  # noqa: ANN001
     return _lib.ACT_IDS[names.pop()]
 
 
+def _mt_unimix(model) -> float:  # noqa: ANN001
+    """The eps of an MMTRSSM posterior rollout: ``l_dist``, ``h_dist`` and the two posterior heads' factories must agree."""
+    return unimix_of(model.l_dist, model.h_dist, model.audio_representation.distribution_factory,
+                     model.vision_representation.distribution_factory)
+
+
 def mmtrssm_posterior_rollout(model, actions: Tensor, audio_embed: Tensor, vision_embed: Tensor, state0: dict[str, Tensor],  # noqa: ANN001
                               noise: dict[str, Tensor | None], *, rows_per_block: int = 0, threads: int = 0,
                               modality: Tensor | None = None, expert_logw: Tensor | None = None) -> dict[str, Tensor]:
@@ -863,7 +885,7 @@ def mmtrssm_posterior_rollout(model, actions: Tensor, audio_embed: Tensor, visio
     A = actions.shape[-1]
     cfg = MTScanConfig(model.l_dist.category_size, model.l_dist.class_size, model.h_dist.category_size, model.h_dist.class_size,
                        _mt_act(model), float(model.l_rnn.tau), float(model.h_rnn.tau), bool(model.use_kl_balancing),
-                       rows_per_block, threads)
+                       rows_per_block, threads, _mt_unimix(model))
     lp1, lp2 = model.l_prior.two_layer()
     hp1, hp2 = model.h_prior.two_layer()
     hq1, hq2 = model.h_posterior.two_layer()
@@ -918,8 +940,9 @@ def _mmtrssm_prior_rollout_differentiable(model, actions: Tensor, state0: dict[s
         logits_l = model.l_prior(_c(deter_l))
         deter_h, hidden_h = _mtrnn_step(model.h_rnn, stoch_h, deter_h, hidden_h)
         logits_h = model.h_prior(_c(deter_h))
-        stoch_h, _ = _st_sample(logits_h, kh, ch, u_h[:, t])
-        stoch_l, _ = _st_sample(logits_l, kl, cl, u_l[:, t])
+        eps = unimix_of(model.l_dist, model.h_dist)
+        stoch_h, _, logits_h = _st_sample(logits_h, kh, ch, u_h[:, t], eps)
+        stoch_l, _, logits_l = _st_sample(logits_l, kl, cl, u_l[:, t], eps)
         for k, v in zip(names, (deter_l, deter_h, hidden_l, hidden_h, logits_l, logits_h, stoch_l, stoch_h), strict=True):
             keep[k].append(v)
     return {k: torch.stack(v, dim=1) for k, v in keep.items()}
@@ -939,7 +962,7 @@ def mmtrssm_prior_rollout(model, actions: Tensor, state0: dict[str, Tensor], noi
         B, T, A = actions.shape
         cfg = MTScanConfig(model.l_dist.category_size, model.l_dist.class_size, model.h_dist.category_size,
                            model.h_dist.class_size, _mt_act(model), float(model.l_rnn.tau), float(model.h_rnn.tau), True,
-                           rows_per_block, threads)
+                           rows_per_block, threads, unimix_of(model.l_dist, model.h_dist))
         LS, HS = cfg.kl_cats * cfg.kl_classes, cfg.kh_cats * cfg.kh_classes
         lp1, lp2 = model.l_prior.two_layer()
         hp1, hp2 = model.h_prior.two_layer()
