@@ -1097,6 +1097,42 @@ int mtrssm_latent_census(const float* post_logits, const float* prior_logits, co
                          int64_t T, int64_t K, int64_t C, float* planes, double* table, void* workspace, int64_t workspace_bytes,
                          void* stream);
 
+/* Generation coherence: do the two decodes of a sampled rollout read as the same digit, and as the right one.
+ * A coherence step gives row b G * S copies (1 <= G <= 4 observed subsets of 1 <= S <= 16 samples); copy (g, s) is scan row
+ * (b * G + g) * S + s.  Frame t of row b is live iff t < clamp(valid[b], 0, T) (valid [B] int32 in DEVICE memory; NULL: no row ends
+ * early) and 0 <= labels[b][t] <= 9 (labels [B][T] int32 in DEVICE memory; -1 = silence).  With c = min(context, T) frame t has horizon
+ * h = 0 for t < c (phase 0) and h = t - c + 1 from c on (phase 1).
+ * mtrssm_coherence_fold: logits_v / logits_a [B * G * S][T][10] fp32, the vision / audio reader's logits zv / za of every copy-frame.
+ *   Per copy of a live frame, in double:
+ *     dv = the lowest index among the largest zv, or 10 (the failure bin) when any of the 10 is not finite; da likewise of za
+ *     vision = [dv == label];  audio = [da == label];  agree = [dv == da and dv < 10];  joint = [dv == da == label]
+ *     pv_k = exp(zv_k - max zv) / (the left fold over ascending k of exp(zv_k - max zv)); pa_k likewise
+ *     soft = the left fold over ascending k of pv_k * pa_k (each product and sum rounded on its own), exactly 0 when a reader failed
+ *     pairs[phase][dv][da] += 1
+ *   u[p][b * G + g][t] (double) is the left fold from +0 over s = 0 .. S - 1 of plane p's per-copy value, exactly +0 on a dead frame.
+ *   planes [5][B * G][T] fp32 (may be NULL): vision, audio, agree, joint, soft -- u / S, rounded to fp32 once.
+ *   table [G][GS] double, IN/OUT (steps add up in it), GS = 6 T + 2 * 121; a group's block holds, in this order:
+ *     sums [5][T] by horizon (the per-copy values added up, not the means), counts [T] (the live copy-frames per horizon: S per live
+ *     frame), pairs [2][11][11].
+ *   Fold order, fixed by the shapes alone: cell (g, p, h) of sums is a left fold from +0 over b ascending and, within a row, over t
+ *   ascending, of u[p][b * G + g][t] over the frames with h(t) = h (a dead frame's +0 changes nothing); that sum is added, in one add,
+ *   onto what the table's cell holds -- a second call of the same step doubles the table exactly.  counts and pairs are whole numbers,
+ *   and so are all sums but soft's.  No atomics on floating point and none between workgroups; two calls agree bitwise; a row's planes
+ *   depend on that row only.
+ *   Two launches.  The first gives (b, g) to one workgroup: spans of 16 frames of its S copies' 2 x 10 logits are staged in LDS with
+ *   coalesced loads, a thread scores one copy-frame, then one thread per (plane, frame) adds over s; the (phase, dv, da) counts are
+ *   integers in an LDS histogram that the workgroup writes out as its partial set.  The second folds u in the order above, one thread
+ *   per cell of the table, and sums the integer partial sets.
+ *   `workspace`: mtrssm_coherence_fold_workspace_bytes(B, G, S, T) bytes, 8-byte aligned; its first 5 * B * G * T doubles are u
+ *   [5][B * G][T] after the call, the workgroups' pair counts follow; -1 for sizes out of range.  Runs on the caller's stream; nothing is
+ *   allocated or read back.
+ *   Null logits_v / logits_a / labels / table / workspace, B, T, S or context <= 0, G outside 1 .. 4, S > 16, B * G * S * T >= 2^24, a
+ *   pointer that is not 4-byte (table, workspace: 8-byte) aligned or a short workspace return -1 without a launch. */
+int64_t mtrssm_coherence_fold_workspace_bytes(int64_t B, int64_t G, int64_t S, int64_t T);
+int mtrssm_coherence_fold(const float* logits_v, const float* logits_a, const int32_t* labels, const int32_t* valid, int64_t B, int64_t G,
+                          int64_t S, int64_t T, int64_t context, float* planes, double* table, void* workspace, int64_t workspace_bytes,
+                          void* stream);
+
 /* Feature moments by bin: the sufficient statistic of a Frechet distance between Gaussian fits.
  * mtrssm_feature_moments: x fp32, row n at x + n * ldx (ldx >= D: a padded buffer is read in place); bin [N] int32 in DEVICE memory:
  *   bin[n] in [0, J) names row n's bin, any other value (-1 by convention) skips the row.

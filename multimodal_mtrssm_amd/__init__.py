@@ -22,6 +22,7 @@ from multimodal_mtrssm_amd.distributions import (
     stack_distribution,
 )
 from multimodal_mtrssm_amd.census import CensusTable, LatentCensus
+from multimodal_mtrssm_amd.coherence import CoherenceTable, GenerationCoherence
 from multimodal_mtrssm_amd.frechet import FrechetDistance, FrechetTable
 from multimodal_mtrssm_amd.dropout import ModalityDropout
 from multimodal_mtrssm_amd.experts import ExpertWeights
@@ -50,4 +51,5 @@ __all__ = [
     "cat_mtstates", "cat_states", "inject_uniforms", "kl_divergence", "likelihood", "load_reference_checkpoint", "make_mmtrssm", "make_mrssm",
     "stack_distribution", "stack_mtstates", "stack_states", "dropout_mask_reference", "tape_reference", "EarlyStopping", "EpochMetrics", "Trainer",
     "LatentOvershoot", "OvershootTable", "ParticleFilter", "ParticleTable", "CensusTable", "LatentCensus", "FrechetDistance", "FrechetTable",
+    "CoherenceTable", "GenerationCoherence",
 ]

@@ -194,6 +194,8 @@ SYMBOLS: dict[str, tuple[type | None, list[type]]] = {
     "mtrssm_overshoot_kl_bwd": (C.c_int, [_p, _p, _p, _p, _p] + [C.c_int64] * 10 + [_f, _f, _p, _p, _p]),
     "mtrssm_latent_census_workspace_bytes": (C.c_int64, [C.c_int64] * 5),
     "mtrssm_latent_census": (C.c_int, [_p, _p, _p, _p] + [C.c_int64] * 5 + [_p, _p, _p, C.c_int64, _p]),
+    "mtrssm_coherence_fold_workspace_bytes": (C.c_int64, [C.c_int64] * 4),
+    "mtrssm_coherence_fold": (C.c_int, [_p, _p, _p, _p] + [C.c_int64] * 5 + [_p, _p, _p, C.c_int64, _p]),
     "mtrssm_feature_moments_workspace_bytes": (C.c_int64, [C.c_int64, _i, _i]),
     "mtrssm_feature_moments": (C.c_int, [_p, C.c_int64, _p, C.c_int64, _i, _i, _p, _p, C.c_int64, _p]),
     "mtrssm_linear_probe_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),

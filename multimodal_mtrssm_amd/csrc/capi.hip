@@ -105,6 +105,9 @@ int overshoot_kl_bwd_launch(const float*, const float*, const int32_t*, const fl
 int64_t latent_census_workspace_bytes(int64_t, int64_t, int64_t, int64_t, int64_t);
 int latent_census_launch(const float*, const float*, const float*, const int32_t*, int64_t, int64_t, int64_t, int64_t, int64_t, float*, double*, void*,
                          int64_t, hipStream_t);
+int64_t coherence_fold_workspace_bytes(int64_t, int64_t, int64_t, int64_t);
+int coherence_fold_launch(const float*, const float*, const int32_t*, const int32_t*, int64_t, int64_t, int64_t, int64_t, int64_t, float*, double*, void*,
+                          int64_t, hipStream_t);
 int64_t feature_moments_workspace_bytes(int64_t, int, int);
 int feature_moments_launch(const float*, int64_t, const int32_t*, int64_t, int, int, double*, void*, int64_t, hipStream_t);
 int64_t linear_probe_workspace_bytes(int64_t, int64_t, int64_t, int64_t);
@@ -578,6 +581,15 @@ MTRSSM_API int mtrssm_latent_census(const float* post_logits, const float* prior
                                     int64_t workspace_bytes, void* stream) {
   return latent_census_launch(post_logits, prior_logits, stoch, valid, B, G, T, K, C, planes, table, workspace, workspace_bytes,
                               static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int64_t mtrssm_coherence_fold_workspace_bytes(int64_t B, int64_t G, int64_t S, int64_t T) {
+  return coherence_fold_workspace_bytes(B, G, S, T);
+}
+MTRSSM_API int mtrssm_coherence_fold(const float* logits_v, const float* logits_a, const int32_t* labels, const int32_t* valid, int64_t B, int64_t G,
+                                     int64_t S, int64_t T, int64_t context, float* planes, double* table, void* workspace, int64_t workspace_bytes,
+                                     void* stream) {
+  return coherence_fold_launch(logits_v, logits_a, labels, valid, B, G, S, T, context, planes, table, workspace, workspace_bytes,
+                               static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int64_t mtrssm_feature_moments_workspace_bytes(int64_t N, int D, int J) { return feature_moments_workspace_bytes(N, D, J); }
 MTRSSM_API int mtrssm_feature_moments(const float* x, int64_t ldx, const int32_t* bin, int64_t N, int D, int J, double* table, void* workspace,

@@ -1,5 +1,5 @@
-"""The evaluation steps of the models: forecast skill, word transitions, held-out likelihood, latent probes,
-episode panels, the latent census and the Frechet distance of sampled frames.
+"""The evaluation steps of the models: forecast skill, word transitions, held-out likelihood, latent
+probes, episode panels, the latent census, the Frechet distance of sampled frames and the coherence of the two generated modalities.
 
 Every one of them runs ONE masked posterior rollout over ``B x copies`` rows and then scores it.  What differs between them is what a
 copy of a row is -- what it observes, up to which frame, whether it shares the row's uniforms, where it lies among the scan's rows -- and
@@ -21,6 +21,7 @@ from torch import Tensor
 from multimodal_mtrssm_amd import cnn, conv, digits, frechet, linear
 from multimodal_mtrssm_amd._shared import _check_lengths, _masked_mean_embed, _pairable, _rand
 from multimodal_mtrssm_amd.census import CensusTable, LatentCensus
+from multimodal_mtrssm_amd.coherence import CoherenceTable, GenerationCoherence
 from multimodal_mtrssm_amd.digits import DigitClassifier, word_counts
 from multimodal_mtrssm_amd.distributions import MultiOneHotFactory
 from multimodal_mtrssm_amd.forecast import Forecast
@@ -263,9 +264,10 @@ class _Evaluators:
                             expert_log_weights: Tensor | None) -> tuple[dict[str, Tensor], Tensor | None]:
         """The rollout of every evaluation step: ``_evaluation_inputs`` and ONE masked posterior rollout over ``B * copies`` rows.
         Returns the scan's outputs -- with ``"codes"``, the rows' modality codes -- and the rows' lengths (or None)."""
-        inp, valid = self._evaluation_inputs(batch, plan, noise, lengths, expert_log_weights)
-        out = self._rollout_embedded(inp["actions"], inp["audio_embed"], inp["vision_embed"], inp["state0"], inp["noise"], sample_prior=False,
-                                     modality=inp["codes"], expert_log_weights=inp["logw"])
+        with linear.ordered_sums():  # (no split reductions: two steps on the same rows agree bitwise, whatever their other rows)
+            inp, valid = self._evaluation_inputs(batch, plan, noise, lengths, expert_log_weights)
+            out = self._rollout_embedded(inp["actions"], inp["audio_embed"], inp["vision_embed"], inp["state0"], inp["noise"], sample_prior=False,
+                                         modality=inp["codes"], expert_log_weights=inp["logw"])
         out["codes"] = inp["codes"]
         return out, valid
 
@@ -683,6 +685,57 @@ class _Evaluators:
                     kept[name][1].append(gen)
         table.features = {name: (torch.cat(r), torch.cat(g)) for name, (r, g) in kept.items()} if keep_states else None
         table.bins = (bins_real.reshape(-1), bins_gen.reshape(-1)) if keep_states else None
+        table.states = self._posterior_from_rollout(out) if keep_states else None
+        return table
+
+    # -- generation coherence -------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def generation_coherence(self, batch: tuple[Tensor, ...], labels: Tensor, gc: GenerationCoherence, readers: dict[str, DigitClassifier],  # noqa: PLR0913, PLR0914
+                             noise: Noise | None = None, lengths: Tensor | None = None, table: CoherenceTable | None = None, *,
+                             keep_states: bool = False, expert_log_weights: Tensor | None = None) -> CoherenceTable:
+        """One coherence step (``coherence.py`` states the quantity): both encoders once, then ONE masked posterior
+        rollout over ``B * G * S`` rows (copy ``g * S + s`` of row ``b`` is scan row ``b * G * S + g * S + s``: it observes
+        ``gc.observe[g]`` on ``gc.context`` frames and runs open loop after them; with ``observe[0] == "both"`` the first ``S`` copies are
+        ``forecast_skill``'s rollout under the same noise), both decoders over chunks of whole rows (paired when they pair), every
+        decoded frame read by ``readers["vision"]`` / ``readers["audio"]`` (each a ``DigitClassifier`` for 1 x 32 x 32 frames; the
+        decoder's raw output goes to the reader, which applies the output activation itself) and ONE ``GenerationCoherence.fold``
+        (``mtrssm_coherence_fold``) of the two ``[B * G * S, T, 10]`` logit buffers into ``table`` (a new one when None), which is
+        returned.  Nothing is read back.  ``labels``: int ``[B, T]`` on the device, the digit shown and spoken at each frame (-1 =
+        silence; anything outside 0 .. 9 is dead).  ``lengths`` (or a batch that carries ``valid_global``): nothing is observed or scored
+        at or past a row's end.  ``keep_states``: ``table.planes`` fp32 ``[5, B * G, T]``, ``table.logits = (vision, audio)`` and
+        ``table.states``, the posterior state sequence ``[B * G * S, T, .]``.  No masked (7-tuple) batch, no ``state_carry``; a weighted
+        model runs its gate as in ``forecast_skill``."""
+        self._check_evaluation_step(batch, "gc", gc, GenerationCoherence, table, CoherenceTable)
+        names = ("audio", "vision")
+        if not isinstance(readers, dict) or any(not isinstance(readers.get(name), DigitClassifier) for name in names):
+            msg = "readers must be {'vision': DigitClassifier, 'audio': DigitClassifier}: generation coherence reads both decodes"
+            raise ValueError(msg)
+        _check_labels(labels, batch)
+        targets = self.get_targets_from_batch(batch)
+        for name in names:
+            if targets[f"recon/{name}"][0, 0].numel() != digits.PIXELS:
+                msg = f"the digit classifier reads 1 x 32 x 32 {name} frames, the batch holds {tuple(targets[f'recon/{name}'].shape[2:])}"
+                raise ValueError(msg)
+        (B, T), dev = batch[0].shape[:2], batch[0].device  # noqa: N806
+        G, S = gc.groups, gc.samples  # noqa: N806
+        copies = G * S
+        out, valid = self._evaluation_rollout(batch, gc.plan(), noise, lengths, expert_log_weights)
+        feature = self._feature_of(out)
+        logits = {name: torch.empty(B * copies, T, digits.CLASSES, device=dev, dtype=torch.float32) for name in names}
+        for r0, r1 in _row_chunks(B, copies * T, gc.max_frames):
+            rows = (r1 - r0) * copies
+            preds, acts = self._decode_for_score(feature[r0 * copies : r1 * copies])
+            for name, pred, act in zip(names, preds, acts, strict=True):
+                if pred.numel() != rows * T * digits.PIXELS:
+                    msg = f"the digit classifier reads 1 x 32 x 32 {name} frames, the decoder gives {tuple(pred.shape[2:])}"
+                    raise ValueError(msg)
+                logits[name][r0 * copies : r1 * copies] = readers[name].read(pred, act)[1].reshape(rows, T, digits.CLASSES)
+        if table is None:
+            table = CoherenceTable(G, T, dev, gc.observe)
+        got = GenerationCoherence.fold(logits["vision"], logits["audio"], labels.to(torch.int32), G, S, gc.context, valid, table=table.buffer,
+                                       planes=keep_states)
+        table.planes = got[0] if keep_states else None
+        table.logits = (logits["vision"], logits["audio"]) if keep_states else None
         table.states = self._posterior_from_rollout(out) if keep_states else None
         return table
 

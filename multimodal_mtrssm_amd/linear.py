@@ -23,6 +23,7 @@ largest entry).  ``mtrssm_gemm``'s ``split_r = 1`` forces one slice per tile -- 
 from __future__ import annotations
 
 import bisect
+import contextlib
 import ctypes as C
 import weakref
 
@@ -102,6 +103,23 @@ import os as _os  # noqa: E402
 SPLIT_PIECES = int(_os.environ.get("MTRSSM_GEMM_PIECES", "2"))
 SPLIT_MIN_FLOPS = 5.0e8
 
+# True inside ``ordered_sums()``: a problem that leaves the cut of its reduction to the library (``split_r = 0``) runs ONE slice per
+# tile, so every output element is a k-ordered chain that depends neither on the run nor on how many rows share the launch.
+ORDERED_SUMS = False
+
+
+@contextlib.contextmanager
+def ordered_sums():  # noqa: ANN201
+    """Within the block every ``mtrssm_gemm`` problem built here is pinned to one reduction slice (``split_r = 1``): no fp32 atomics
+    meet, two runs agree bitwise and a row's result does not depend on the other rows of the launch -- at the cost of the grid fill
+    of small problems.  The evaluation steps run their encoders, gate and rollout under it."""
+    global ORDERED_SUMS  # noqa: PLW0603
+    before, ORDERED_SUMS = ORDERED_SUMS, True
+    try:
+        yield
+    finally:
+        ORDERED_SUMS = before
+
 
 def _problem(a: Tensor, b: Tensor, c: Tensor, *, a_rmajor: bool, b_rmajor: bool, bias: Tensor | None = None, zgrad: Tensor | None = None,  # noqa: PLR0913
              colsum: Tensor | None = None, act_a: int = 0, act_b: int = 0, act_z: int = 0, accumulate: bool = False, split_r: int = 0,
@@ -123,7 +141,7 @@ def _problem(a: Tensor, b: Tensor, c: Tensor, *, a_rmajor: bool, b_rmajor: bool,
     g.ldz = _ld(zgrad) if zgrad is not None else 0
     g.a_rmajor, g.b_rmajor = int(a_rmajor), int(b_rmajor)
     g.act_a, g.act_b, g.act_out, g.act_z = int(act_a), int(act_b), 0, int(act_z)
-    g.accumulate, g.split_r = int(accumulate), int(split_r)
+    g.accumulate, g.split_r = int(accumulate), int(split_r) or int(ORDERED_SUMS)
     if mfma_split is None:
         mfma_split = SPLIT_PIECES if 2.0 * m * n * r >= SPLIT_MIN_FLOPS else 0
     g.mfma_split = int(mfma_split)

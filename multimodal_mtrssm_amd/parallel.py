@@ -18,6 +18,7 @@ from torch import Tensor
 
 from multimodal_mtrssm_amd import conv, linear
 from multimodal_mtrssm_amd.census import LatentCensus
+from multimodal_mtrssm_amd.coherence import GenerationCoherence
 from multimodal_mtrssm_amd.frechet import FrechetDistance
 from multimodal_mtrssm_amd.dropout import ModalityDropout
 from multimodal_mtrssm_amd.forecast import Forecast
@@ -127,6 +128,11 @@ class FlatDataParallel:
         """``census`` bound to this object's process group: set the result as ``model.val_census`` and ``on_validation_epoch_end``
         all-reduces the census table over that group (its uniforms' batch dimension comes first: draw them with ``noise_source``)."""
         return census.for_group(self.group)
+
+    def coherence(self, gc: GenerationCoherence) -> GenerationCoherence:
+        """``gc`` bound to this object's process group: ``CoherenceTable.all_reduce(gc.group)`` then sums the coherence tables of every
+        rank's rows (its uniforms' batch dimension comes first: draw them with ``noise_source``)."""
+        return gc.for_group(self.group)
 
     def frechet(self, fd: FrechetDistance) -> FrechetDistance:
         """``fd`` bound to this object's process group: set the result as ``model.val_frechet`` and ``on_validation_epoch_end``

@@ -8,7 +8,11 @@
 The data are `.npz` episodes with `image (T, 1, 32, 32)` in [0, 255] and `label (T,)` (-1 = silence).  Every labelled frame goes through
 `NormalizeVisionImage` (the decoder's target range, read with `act = 0`); a seeded `--holdout` share of them is kept out of the fit and
 its accuracy printed after every epoch.  The recipe is the evaluation's: Adam at 1e-3, batches of 64, `Dropout(0.5)`, cross-entropy,
-5 epochs.  On the GPU every step runs the HIP kernels; `--device cpu` runs the float64 rule (slow: for small sets)."""
+5 epochs.  On the GPU every step runs the HIP kernels; `--device cpu` runs the float64 rule (slow: for small sets).
+
+`--modality audio` fits the reader of the AUDIO decode instead (`tools/generation_coherence.py --audio-reader`): the
+frames are `audio (T, 32, 32)` mel spectrograms next to the same `label`, mapped through `NormalizeAudioMelSpectrogram(--audio-min,
+--audio-max)` (default -80 and 0, the values `tools/word_transitions.py` feeds the model with) to the decoder's target range."""
 
 from __future__ import annotations
 
@@ -23,16 +27,26 @@ ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 
 
-def load_labelled_frames(folder: Path) -> tuple[torch.Tensor, torch.Tensor]:
-    """fp32 ``[N, 1024]`` raw frames in [-1, 1] and int32 ``[N]`` digits of every labelled frame of every episode."""
-    from multimodal_mtrssm_amd.transform import NormalizeVisionImage
+def load_labelled_frames(folder: Path, modality: str = "vision", audio_min: float = -80.0, audio_max: float = 0.0) -> tuple[torch.Tensor, torch.Tensor]:
+    """fp32 ``[N, 1024]`` raw frames in [-1, 1] and int32 ``[N]`` digits of every labelled frame of every episode: ``image`` frames
+    through ``NormalizeVisionImage``, or (``modality="audio"``) ``audio`` frames through ``NormalizeAudioMelSpectrogram(audio_min,
+    audio_max)``."""
+    from multimodal_mtrssm_amd.transform import NormalizeAudioMelSpectrogram, NormalizeVisionImage
 
+    if modality not in ("vision", "audio"):
+        msg = f"modality must be 'vision' or 'audio', got {modality!r}"
+        raise ValueError(msg)
+    key, shape = ("image", "(T, 1, 32, 32)") if modality == "vision" else ("audio", "(T, 32, 32)")
     frames, labels = [], []
     for path in sorted(folder.glob("*.npz")):
         with np.load(path, allow_pickle=False) as z:
-            image, label = np.asarray(z["image"]), np.asarray(z["label"]).astype(np.int64)
-        if image.shape[0] != label.shape[0] or image.reshape(image.shape[0], -1).shape[1] != 1024:  # noqa: PLR2004
-            msg = f"{path}: image {image.shape} and label {label.shape} are not (T, 1, 32, 32) and (T,)"
+            image, label = np.asarray(z[key]), np.asarray(z["label"]).astype(np.int64)
+        if modality == "vision":
+            bad = image.shape[0] != label.shape[0] or image.reshape(image.shape[0], -1).shape[1] != 1024  # noqa: PLR2004
+        else:
+            bad = image.ndim != 3 or image.shape[0] != label.shape[0] or tuple(image.shape[1:]) != (32, 32)  # noqa: PLR2004
+        if bad:
+            msg = f"{path}: {key} {image.shape} and label {label.shape} are not {shape} and (T,)"
             raise ValueError(msg)
         keep = (label >= 0) & (label < 10)  # noqa: PLR2004
         frames.append(torch.from_numpy(image[keep]).float().reshape(-1, 1024))
@@ -40,7 +54,8 @@ def load_labelled_frames(folder: Path) -> tuple[torch.Tensor, torch.Tensor]:
     if not frames:
         msg = f"no .npz episodes in {folder}"
         raise ValueError(msg)
-    return NormalizeVisionImage()(torch.cat(frames)), torch.cat(labels)
+    transform = NormalizeVisionImage() if modality == "vision" else NormalizeAudioMelSpectrogram(min_value=audio_min, max_value=audio_max)
+    return transform(torch.cat(frames)), torch.cat(labels)
 
 
 def main() -> None:
@@ -54,6 +69,9 @@ def main() -> None:
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--dropout", type=float, default=0.5)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--modality", choices=("vision", "audio"), default="vision", help="which frames the reader is fitted on")
+    ap.add_argument("--audio-min", type=float, default=-80.0, help="--modality audio: the spectrogram value mapped to -1")
+    ap.add_argument("--audio-max", type=float, default=0.0, help="--modality audio: the spectrogram value mapped to +1")
     args = ap.parse_args()
     if not 0.0 <= args.holdout < 1.0:
         ap.error("--holdout lies in [0, 1)")
@@ -62,7 +80,7 @@ def main() -> None:
 
     import multimodal_mtrssm_amd as mt
 
-    frames, labels = load_labelled_frames(Path(args.data_dir))
+    frames, labels = load_labelled_frames(Path(args.data_dir), args.modality, args.audio_min, args.audio_max)
     n = frames.shape[0]
     order = torch.randperm(n, generator=torch.Generator().manual_seed(args.seed))
     held = int(round(args.holdout * n))
