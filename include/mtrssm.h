@@ -780,6 +780,38 @@ int mtrssm_episode_gather_ragged(const float* store, const int64_t* idx, const i
 int mtrssm_episode_gather_seeded(const float* store, const int64_t* idx, const int32_t* start, const int32_t* lengths, int32_t* valid_out,
                                  uint32_t key0, uint32_t key1, uint32_t epoch, int64_t n_episodes, int64_t B, int64_t T, int64_t Tfull,
                                  int64_t E, float std_, float* input, float* target, void* stream);
+/* The seeded gather with a seeded AUGMENTATION of the frames: one integer shift per episode and up to
+ * MTRSSM_AUGMENT_MAX_BANDS (row band, column band) masks per frame or per episode, then the seeded noise.  The event is [C, H, W],
+ * E = C H W.  Everything below is exact 32-bit integer arithmetic, umulhi(a, n) = (a * n) >> 32 for a 32-bit a; Philox4x32-10, the
+ * absolute frame f, the form selection by start / lengths, the clamps of start, lengths and idx, the dead frames (exactly zero, no
+ * load, no generator work) and valid_out are those of mtrssm_episode_gather_seeded.  (akey0, akey1) is the augmentation's key:
+ * dataset.augment_key(seed, stream) = stream_key(seed, stream + 3), apart from the noise keys of streams 0, 1, 2.
+ *   shift, one draw per (key, epoch, episode), the same for every frame of the episode:
+ *     P = Philox4x32-10(counter = (0, 0, idx[b] & 0xffffffff, epoch), key = (akey0, akey1))
+ *     dy = umulhi(P0, 2 sy + 1) - sy    dx = umulhi(P1, 2 sx + 1) - sx     (positive: content moves down / right)
+ *   band j = 0 .. bands - 1:
+ *     Q = Philox4x32-10(counter = (1 + j, per_frame ? f + 1 : 0, idx[b] & 0xffffffff, epoch), key = (akey0, akey1))
+ *     h = umulhi(Q0, max_rows + 1)   r0 = umulhi(Q1, H - h + 1)   w = umulhi(Q2, max_cols + 1)   c0 = umulhi(Q3, W - w + 1)
+ *     pixel (y, x) of every channel is masked iff, for some j, r0 <= y < r0 + h or c0 <= x < c0 + w   (output coordinates)
+ *   live frame, channel c, pixel (y, x), output element e = (c H + y) W + x:
+ *     target = (0 <= y - dy < H and 0 <= x - dx < W) ? store[idx[b], f, c, y - dy, x - dx] : fill    (shifted, never masked)
+ *     base   = masked(y, x) ? fill : target
+ *     input  = noisy ? base + z * std : base      (mul then add, each rounded; z = the seeded entry's normal of (key0, key1), epoch,
+ *                                                  episode, f and OUTPUT element e)
+ * A vacated pixel reads nothing.  With sy = sx = bands = 0 the call writes what mtrssm_episode_gather_seeded writes (noisy = 1), bit
+ * for bit.  Returns -1 without a launch for: a null aug; sy outside [0, H), sx outside [0, W); bands outside
+ * [0, MTRSSM_AUGMENT_MAX_BANDS]; max_rows outside [0, H], max_cols outside [0, W]; per_frame or noisy outside {0, 1}; a fill that is
+ * not finite; C, H, W <= 0, W % 4 != 0, C H W >= 2^31 or B T >= 2^31 (one workgroup per frame); and whatever
+ * mtrssm_episode_gather_seeded refuses. */
+#define MTRSSM_AUGMENT_MAX_BANDS 4
+typedef struct MtrssmFeedAugment {
+  int32_t sy, sx, bands, max_rows, max_cols, per_frame;
+  float fill;
+} MtrssmFeedAugment;
+int mtrssm_episode_gather_augmented(const MtrssmFeedAugment* aug, const float* store, const int64_t* idx, const int32_t* start,
+                                    const int32_t* lengths, int32_t* valid_out, uint32_t key0, uint32_t key1, uint32_t akey0, uint32_t akey1,
+                                    uint32_t epoch, int64_t n_episodes, int64_t B, int64_t T, int64_t Tfull, int64_t C, int64_t H, int64_t W,
+                                    int32_t noisy, float std_, float* input, float* target, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Carried state of truncated BPTT: the initial state of a train step is, per batch row, either the

@@ -9,7 +9,16 @@ Importing the package does not need a GPU; running a rollout does, and fails lou
 from multimodal_mtrssm_amd.carry import StateCarry
 from multimodal_mtrssm_amd.cnn import Decoder, Encoder
 from multimodal_mtrssm_amd.core import MoPoE_MMTRSSM, MoPoE_MRSSM, WeightedMoPoE_MMTRSSM, WeightedMoPoE_MRSSM
-from multimodal_mtrssm_amd.dataset import DeviceEpisodeLoader, EpisodeBatch, EpisodeDataModule, EpisodeDataModuleConfig
+from multimodal_mtrssm_amd.dataset import (
+    DeviceEpisodeLoader,
+    EpisodeBatch,
+    EpisodeDataModule,
+    EpisodeDataModuleConfig,
+    FeedAugment,
+    augment_key,
+    feed_augment_parameters,
+    feed_augment_reference,
+)
 from multimodal_mtrssm_amd.digit_train import DigitStats, DigitTrainer, dropout_mask_reference, tape_reference
 from multimodal_mtrssm_amd.digits import DigitClassifier
 from multimodal_mtrssm_amd.distributions import (
@@ -51,5 +60,5 @@ __all__ = [
     "cat_mtstates", "cat_states", "inject_uniforms", "kl_divergence", "likelihood", "load_reference_checkpoint", "make_mmtrssm", "make_mrssm",
     "stack_distribution", "stack_mtstates", "stack_states", "dropout_mask_reference", "tape_reference", "EarlyStopping", "EpochMetrics", "Trainer",
     "LatentOvershoot", "OvershootTable", "ParticleFilter", "ParticleTable", "CensusTable", "LatentCensus", "FrechetDistance", "FrechetTable",
-    "CoherenceTable", "GenerationCoherence",
+    "CoherenceTable", "GenerationCoherence", "FeedAugment", "augment_key", "feed_augment_parameters", "feed_augment_reference",
 ]

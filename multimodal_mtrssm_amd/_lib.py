@@ -103,6 +103,10 @@ StateTable = _struct("MtrssmStateTable", [
     ("count", _i), ("width", _i * STATE_MAX), ("src_stride", C.c_int64 * STATE_MAX), ("src", _p * STATE_MAX), ("alt", _p * STATE_MAX),
     ("dst", _p * STATE_MAX)])
 
+AUGMENT_MAX_BANDS = 4  # MTRSSM_AUGMENT_MAX_BANDS
+FeedAugment = _struct("MtrssmFeedAugment", [("sy", _i), ("sx", _i), ("bands", _i), ("max_rows", _i), ("max_cols", _i), ("per_frame", _i),
+                                            ("fill", _f)])
+
 PANEL_COLUMNS = {"prior": 0, "observation": 1, "posterior": 2, "error": 3}  # MTRSSM_PANEL_*
 PanelGeom = _struct("MtrssmPanelGeom", [(n, _i) for n in ("N", "T", "Ca", "Ha", "Wa", "Cv", "Hv", "Wv", "scale", "gap", "bar", "label", "frame0")]
                     + [("columns", _i * 4), ("n_columns", _i), ("blank_unseen", _i)])
@@ -177,6 +181,8 @@ SYMBOLS: dict[str, tuple[type | None, list[type]]] = {
     "mtrssm_episode_gather_ragged": (C.c_int, [_p, _p, _p, _p, _p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _f, _p, _p, _p, _p]),
     "mtrssm_episode_gather_seeded": (C.c_int, [_p, _p, _p, _p, _p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                                C.c_int64, _f, _p, _p, _p]),
+    "mtrssm_episode_gather_augmented": (C.c_int, [C.POINTER(FeedAugment), _p, _p, _p, _p, _p] + [C.c_uint32] * 5 + [C.c_int64] * 7
+                                        + [_i, _f, _p, _p, _p]),
     "mtrssm_step_mask_ragged": (C.c_int, [_p, _p, C.c_int64, C.c_int64, C.c_int64, _f, _f, C.c_int64, C.c_int64, _p, _p, _p, _p, _p, _p, _p, _p]),
     "mtrssm_step_mask_forecast": (C.c_int, [_p, _p, _p, C.c_int64, C.c_int64, C.c_int64, _f, _f, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _p, _p, _p,
                                             _p, _p, _p, _p, _p, _p]),

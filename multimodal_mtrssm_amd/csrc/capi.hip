@@ -33,6 +33,9 @@ int episode_gather_ragged_launch(const float*, const int64_t*, const int32_t*, c
                                  int64_t, float, float*, float*, int32_t*, hipStream_t);
 int episode_gather_seeded_launch(const float*, const int64_t*, const int32_t*, const int32_t*, int32_t*, uint32_t, uint32_t, uint32_t, int64_t, int64_t,
                                  int64_t, int64_t, int64_t, float, float*, float*, hipStream_t);
+int episode_gather_augmented_launch(const MtrssmFeedAugment*, const float*, const int64_t*, const int32_t*, const int32_t*, int32_t*, uint32_t, uint32_t,
+                                    uint32_t, uint32_t, uint32_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int32_t, float, float*,
+                                    float*, hipStream_t);
 int step_mask_ragged_launch(const int32_t*, const float*, int64_t, int64_t, int64_t, float, float, int64_t, int64_t, int32_t*, float*, float*, float*,
                             unsigned char*, int32_t*, float*, hipStream_t);
 int step_mask_forecast_launch(const int32_t*, const float*, const float*, int64_t, int64_t, int64_t, float, float, int64_t, int64_t, int64_t, int64_t,
@@ -382,6 +385,13 @@ MTRSSM_API int mtrssm_episode_gather_seeded(const float* store, const int64_t* i
                                             int64_t T, int64_t Tfull, int64_t E, float std_, float* input, float* target, void* stream) {
   return episode_gather_seeded_launch(store, idx, start, lengths, valid_out, key0, key1, epoch, n_episodes, B, T, Tfull, E, std_, input, target,
                                       static_cast<hipStream_t>(stream));
+}
+MTRSSM_API int mtrssm_episode_gather_augmented(const MtrssmFeedAugment* aug, const float* store, const int64_t* idx, const int32_t* start,
+                                               const int32_t* lengths, int32_t* valid_out, uint32_t key0, uint32_t key1, uint32_t akey0,
+                                               uint32_t akey1, uint32_t epoch, int64_t n_episodes, int64_t B, int64_t T, int64_t Tfull, int64_t C,
+                                               int64_t H, int64_t W, int32_t noisy, float std_, float* input, float* target, void* stream) {
+  return episode_gather_augmented_launch(aug, store, idx, start, lengths, valid_out, key0, key1, akey0, akey1, epoch, n_episodes, B, T, Tfull, C, H,
+                                         W, noisy, std_, input, target, static_cast<hipStream_t>(stream));
 }
 MTRSSM_API int mtrssm_step_mask_ragged(const int32_t* valid, const float* u, int64_t b_global, int64_t steps, int64_t span, float p_audio,
                                        float p_vision, int64_t row0, int64_t b_local, int32_t* codes, float* present_audio,

@@ -982,6 +982,191 @@ int episode_gather_seeded_launch(const float* store, const int64_t* idx, const i
 }
 
 // ------------------------------------------------------------------------------------------------
+// AUGMENTED: the seeded gather with a seeded shift and band masks (include/mtrssm.h states the rule).  The
+// shift (dy, dx) and the bands (r0, h, c0, w) are uniform per (row, frame), so the work is mapped one WORKGROUP per frame
+// (blockIdx.x = b * T + t; no loop over frames, which kept twice the scalar registers live): lane j <= bands of the first wave makes Philox call j (call 0: the shift, call
+// 1 + j: band j) and leaves four integers in LDS, a barrier, and every lane reads them back -- 1 + bands Philox calls per frame, none
+// per float4.  Lane q then walks the frame's output quads q, q + 256, ...: quad q is pixels x0 .. x0 + 3 of row y of channel c, its source
+// the four floats from column x0 - dx of row y - dy of the same channel.  A source row outside [0, H) reads nothing.  Inside, the
+// source quad is covered by the aligned float4s at a = floor((x0 - dx) / 4) and a + 1 of that ROW (W % 4 == 0: every row begins on 16
+// bytes); each is loaded only if it lies inside the row, stands for fill otherwise, and the second only when dx % 4 != 0 (uniform per
+// frame).  So no access leaves the source row, whatever dx: a vacated pixel never sees the neighbouring row, channel or frame.
+// Stores are whole float4s.  MODE as in episode_gather_kernel, with its clamps; the liveness of a frame is uniform per workgroup,
+// so the barrier stands in uniform control flow.
+// ------------------------------------------------------------------------------------------------
+template <int MODE>
+__global__ __launch_bounds__(kThreads) void episode_gather_augmented_kernel(
+    MtrssmFeedAugment aug, const float* __restrict__ store, const long* __restrict__ idx, const int* __restrict__ start,
+    const int* __restrict__ lengths, unsigned key0, unsigned key1, unsigned akey0, unsigned akey1, unsigned epoch, long n_episodes,
+    long T, long Tfull, int C, int H, int W, int noisy, float std_, float* __restrict__ input, float* __restrict__ target,
+    int* __restrict__ valid_out) {
+#pragma clang fp contract(off)  // mul then add, each rounded, as episode_gather_kernel
+  __shared__ int4 prm[1 + MTRSSM_AUGMENT_MAX_BANDS];  // [0]: (dy, dx, -, -); [1 + j]: (r0, h, c0, w) of band j
+  const unsigned W4 = (unsigned)W >> 2, E4 = (unsigned)(C * H) * W4;
+  const float4 fill4 = make_float4(aug.fill, aug.fill, aug.fill, aug.fill);
+  // Quad q = (c H + y) W4 + x4.  A lane's quads are q = threadIdx.x + 256 k: divisions give the lane's first quad and the step of 256
+  // quads (the step's are scalar), and the quad loop walks (c, y, x4) by additions.
+  const unsigned cy_first = threadIdx.x / W4, x4_first = threadIdx.x - cy_first * W4;
+  const unsigned c_first = cy_first / (unsigned)H, y_first = cy_first - c_first * (unsigned)H;
+  const unsigned step_cy = kThreads / W4, step_x = kThreads - step_cy * W4;
+  const unsigned step_c = step_cy / (unsigned)H, step_y = step_cy - step_c * (unsigned)H;
+  {
+    const long fr = blockIdx.x;  // < B * T < 2^31 (the launcher's check)
+    const long b = (unsigned)fr / (unsigned)T, t = fr - b * T;
+    long ep = idx[b], s = 0;
+    bool on = true;
+    if constexpr (MODE == kGatherWindow) {
+      const long last = Tfull - T;
+      s = start[b];
+      s = s < 0 ? 0 : (s > last ? last : s);
+    }
+    if constexpr (MODE == kGatherRagged) {
+      s = start[b];
+      s = s < 0 ? 0 : (s > Tfull ? Tfull : s);
+      ep = ep < 0 ? 0 : (ep >= n_episodes ? n_episodes - 1 : ep);
+      long len = lengths[ep];
+      len = len < 0 ? 0 : (len > Tfull ? Tfull : len);
+      on = s + t < len;  // (< Tfull: the reads below stay inside the episode)
+      if (valid_out && t == 0 && threadIdx.x == 0) {
+        const long n = len - s;
+        valid_out[b] = (int)(n < 0 ? 0 : (n > T ? T : n));
+      }
+    }
+    float4* const tgt = target ? reinterpret_cast<float4*>(target) + fr * E4 : nullptr;
+    float4* const inp = input ? reinterpret_cast<float4*>(input) + fr * E4 : nullptr;
+    if (!on) {  // a dead frame: zeros, no load, no generator work
+      const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (unsigned q = threadIdx.x; q < E4; q += kThreads) {
+        if (tgt) tgt[q] = zero;
+        if (inp) inp[q] = zero;
+      }
+      return;
+    }
+    const unsigned f = (unsigned)(s + t);
+    if (threadIdx.x <= (unsigned)aug.bands) {
+      const unsigned j = threadIdx.x;
+      unsigned w[4];
+      philox4x32_10(j, (j && aug.per_frame) ? f + 1u : 0u, (unsigned)ep, epoch, akey0, akey1, w);
+      int4 p = make_int4(0, 0, 0, 0);
+      if (j == 0) {
+        p.x = (int)__umulhi(w[0], 2u * aug.sy + 1u) - aug.sy;  // dy
+        p.y = (int)__umulhi(w[1], 2u * aug.sx + 1u) - aug.sx;  // dx
+      } else {
+        p.y = (int)__umulhi(w[0], (unsigned)aug.max_rows + 1u);  // h
+        p.x = (int)__umulhi(w[1], (unsigned)(H - p.y) + 1u);     // r0
+        p.w = (int)__umulhi(w[2], (unsigned)aug.max_cols + 1u);  // w
+        p.z = (int)__umulhi(w[3], (unsigned)(W - p.w) + 1u);     // c0
+      }
+      prm[j] = p;
+    }
+    __syncthreads();
+    const int dy = __builtin_amdgcn_readfirstlane(prm[0].x), dx = __builtin_amdgcn_readfirstlane(prm[0].y);
+    const int sh = (-dx) & 3;  // the source quad begins `sh` floats into an aligned one (two's complement: right for dx > 0 too)
+    const float4* const src = reinterpret_cast<const float4*>(store) + (ep * Tfull + (long)f) * E4;
+    unsigned c = c_first, y = y_first, x4 = x4_first;
+    for (unsigned q = threadIdx.x; q < E4; q += kThreads) {
+      const unsigned x0 = x4 * 4u;
+      const int ys = (int)y - dy;
+      float4 x = fill4;
+      if ((unsigned)ys < (unsigned)H) {
+        const float4* const row = src + (c * (unsigned)H + (unsigned)ys) * W4;
+        const int a = ((int)x0 - dx) >> 2;  // floor: the aligned quad that holds source column x0 - dx
+        float4 lo = fill4, hi = fill4;
+        if ((unsigned)a < W4) lo = row[a];
+        if (sh && (unsigned)(a + 1) < W4) hi = row[a + 1];
+        x = sh == 0 ? lo : (sh == 1 ? make_float4(lo.y, lo.z, lo.w, hi.x) : (sh == 2 ? make_float4(lo.z, lo.w, hi.x, hi.y)
+                                                                                     : make_float4(lo.w, hi.x, hi.y, hi.z)));
+      }
+      if (tgt) tgt[q] = x;
+      if (inp) {
+        bool m0 = false, m1 = false, m2 = false, m3 = false;
+        for (int j = 1; j <= aug.bands; ++j) {  // (a uniform trip count; band j is one broadcast 16-byte LDS read)
+          const int4 p = prm[j];
+          const bool rowm = y - (unsigned)p.x < (unsigned)p.y;  // r0 <= y < r0 + h in one unsigned test; h = 0 never holds
+          m0 |= rowm | (x0 - (unsigned)p.z < (unsigned)p.w);
+          m1 |= rowm | (x0 + 1u - (unsigned)p.z < (unsigned)p.w);
+          m2 |= rowm | (x0 + 2u - (unsigned)p.z < (unsigned)p.w);
+          m3 |= rowm | (x0 + 3u - (unsigned)p.z < (unsigned)p.w);
+        }
+        float4 v = make_float4(m0 ? aug.fill : x.x, m1 ? aug.fill : x.y, m2 ? aug.fill : x.z, m3 ? aug.fill : x.w);
+        if (noisy) {
+          unsigned w[4];
+          float4 n;
+          philox4x32_10(q, f, (unsigned)ep, epoch, key0, key1, w);
+          box_muller(w[0], w[1], n.x, n.y);
+          box_muller(w[2], w[3], n.z, n.w);
+          const float px = n.x * std_, py = n.y * std_, pz = n.z * std_, pw = n.w * std_;
+          v.x = v.x + px;
+          v.y = v.y + py;
+          v.z = v.z + pz;
+          v.w = v.w + pw;
+        }
+        inp[q] = v;
+      }
+      // the lane's next quad, 256 further on: x4 < 2 W4 and y < 2 H before the corrections, one of each is enough
+      x4 += step_x;
+      const unsigned carry = x4 >= W4 ? 1u : 0u;
+      x4 -= carry ? W4 : 0u;
+      y += step_y + carry;
+      c += step_c;
+      if (y >= (unsigned)H) y -= (unsigned)H, ++c;
+    }
+  }
+}
+
+int episode_gather_augmented_launch(const MtrssmFeedAugment* aug, const float* store, const int64_t* idx, const int32_t* start,
+                                    const int32_t* lengths, int32_t* valid_out, uint32_t key0, uint32_t key1, uint32_t akey0, uint32_t akey1,
+                                    uint32_t epoch, int64_t n_episodes, int64_t B, int64_t T, int64_t Tfull, int64_t C, int64_t H, int64_t W,
+                                    int32_t noisy, float std_, float* input, float* target, hipStream_t s) {
+  const char* what = "episode_gather_augmented";
+  if (!aug) { set_error("%s: aug is null", what); return MTRSSM_EINVAL; }
+  if (lengths && !start) { set_error("%s: lengths without start (a ragged batch needs its windows' starts)", what); return MTRSSM_EINVAL; }
+  if (valid_out && !lengths) { set_error("%s: valid_out without lengths", what); return MTRSSM_EINVAL; }
+  if (!store || !idx || (!input && !target) || n_episodes <= 0 || B <= 0 || T <= 0 || Tfull < T || C <= 0 || H <= 0 || W <= 0) {
+    set_error("%s: bad argument (need 0 < T <= Tfull, B, C, H, W > 0, an output)", what);
+    return MTRSSM_EINVAL;
+  }
+  if (W % 4) { set_error("%s: the row length W = %ld must be a multiple of 4 floats", what, (long)W); return MTRSSM_EINVAL; }
+  if (C > 0x7fffffffL || H > 0x7fffffffL || W > 0x7fffffffL || C * H > 0x7fffffffL / W) {
+    set_error("%s: the event %ld x %ld x %ld exceeds 2^31 - 1 floats", what, (long)C, (long)H, (long)W);
+    return MTRSSM_EINVAL;
+  }
+  if (aug->sy < 0 || aug->sy >= H || aug->sx < 0 || aug->sx >= W) {
+    set_error("%s: the shift (%d, %d) must lie in [0, H) x [0, W) = [0, %ld) x [0, %ld)", what, aug->sy, aug->sx, (long)H, (long)W);
+    return MTRSSM_EINVAL;
+  }
+  if (aug->bands < 0 || aug->bands > MTRSSM_AUGMENT_MAX_BANDS) {
+    set_error("%s: bands = %d must lie in [0, %d]", what, aug->bands, MTRSSM_AUGMENT_MAX_BANDS);
+    return MTRSSM_EINVAL;
+  }
+  if (aug->max_rows < 0 || aug->max_rows > H || aug->max_cols < 0 || aug->max_cols > W) {
+    set_error("%s: max_rows = %d, max_cols = %d must lie in [0, H = %ld], [0, W = %ld]", what, aug->max_rows, aug->max_cols, (long)H, (long)W);
+    return MTRSSM_EINVAL;
+  }
+  if ((aug->per_frame & ~1) || (noisy & ~1)) { set_error("%s: per_frame and noisy are 0 or 1", what); return MTRSSM_EINVAL; }
+  if (!(aug->fill - aug->fill == 0.f)) { set_error("%s: fill must be finite", what); return MTRSSM_EINVAL; }
+  if (((uintptr_t)store | (uintptr_t)input | (uintptr_t)target) & 15) { set_error("%s: buffers must be 16-byte aligned", what); return MTRSSM_EINVAL; }
+  if (((uintptr_t)start | (uintptr_t)lengths | (uintptr_t)valid_out) & 3) {
+    set_error("%s: start, lengths and valid_out must be 4-byte aligned", what);
+    return MTRSSM_EINVAL;
+  }
+  const int mode = lengths ? kGatherRagged : (start ? kGatherWindow : kGatherFirst);
+  static const struct {
+    decltype(&episode_gather_augmented_kernel<kGatherFirst>) kernel;
+    const char* name;
+  } table[3] = {{episode_gather_augmented_kernel<kGatherFirst>, "mtrssm::episode_gather_augmented_kernel<first>"},
+                {episode_gather_augmented_kernel<kGatherWindow>, "mtrssm::episode_gather_augmented_kernel<window>"},
+                {episode_gather_augmented_kernel<kGatherRagged>, "mtrssm::episode_gather_augmented_kernel<ragged>"}};
+  if (B > 0x7fffffffL / T) { set_error("%s: B * T = %ld x %ld exceeds 2^31 - 1 frames (one workgroup each)", what, (long)B, (long)T); return MTRSSM_EINVAL; }
+  set_last_kernel(table[mode].name);
+  hipLaunchKernelGGL(table[mode].kernel, dim3((unsigned)(B * T)), dim3(kThreads), 0, s, *aug, store,
+                     reinterpret_cast<const long*>(idx), reinterpret_cast<const int*>(start), reinterpret_cast<const int*>(lengths), key0, key1, akey0,
+                     akey1, epoch, (long)n_episodes, (long)T, (long)Tfull, (int)C, (int)H, (int)W, (int)noisy, std_, input, target,
+                     reinterpret_cast<int*>(valid_out));
+  return check_launch(what);
+}
+
+// ------------------------------------------------------------------------------------------------
 // Carried state of truncated BPTT: up to MTRSSM_STATE_MAX row-major [B, width] tensors per launch, the
 // table of pointers passed by value.  For entry k and row b:
 //   dst[b, :] = (!reset || reset[b]) ? src[b * stride : +width] : (alt ? alt[b, :] : 0)

@@ -19,11 +19,14 @@ episodes end at different frames; the store keeps them padded to ``T_full``, a b
 past them are exactly zero (``mtrssm_episode_gather_ragged``).  ``noise_seed``: the input noise is generated
 inside the gather (``mtrssm_episode_gather_seeded``) as a pure function of ``(seed, stream, epoch, episode, absolute frame, element)``,
 the same on any number of ranks and replayed by ``set_epoch``; without it the normals come from ``torch.randn`` as before.
+``augment``: a seeded integer shift per episode and band masks per frame or episode, made in the same launch
+(``mtrssm_episode_gather_augmented``) under the same contract; ``FeedAugment`` holds a stream's parameters.
 """
 
 from __future__ import annotations
 
-from collections.abc import Iterator
+import math
+from collections.abc import Iterator, Mapping
 from dataclasses import dataclass
 from pathlib import Path
 
@@ -75,6 +78,60 @@ def normalize_observation_shape(observations: Tensor) -> Tensor:
     return observations
 
 
+def _is_int(v: object) -> bool:
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+@dataclass(frozen=True)
+class FeedAugment:
+    """Seeded augmentation of one stream's frames ``[C, H, W]`` inside the gather: ``shift = (sy, sx)``, the
+    largest shift in rows / columns (one draw per episode, uniform on ``[-sy, sy] x [-sx, sx]``); ``bands`` pairs of a row band of
+    ``0 .. max_rows`` rows and a column band of ``0 .. max_cols`` columns, redrawn per frame (``per_frame``) or once per episode;
+    ``fill``, the value of vacated and masked pixels (-1: the background of data normalised to [-1, 1]).  The target is shifted and
+    never masked.  Checked here against nothing but itself; the loader checks it against the stream's ``H`` and ``W``."""
+
+    shift: tuple[int, int] = (0, 0)
+    bands: int = 0
+    max_rows: int = 0
+    max_cols: int = 0
+    per_frame: bool = False
+    fill: float = -1.0
+
+    def __post_init__(self) -> None:
+        shift = tuple(self.shift) if isinstance(self.shift, (tuple, list)) else self.shift
+        if not isinstance(shift, tuple) or len(shift) != 2 or not all(_is_int(v) and v >= 0 for v in shift):  # noqa: PLR2004
+            msg = f"shift must be two integers (sy, sx) >= 0, got {self.shift!r}"
+            raise ValueError(msg)
+        object.__setattr__(self, "shift", (int(shift[0]), int(shift[1])))
+        if not _is_int(self.bands) or not 0 <= self.bands <= _lib.AUGMENT_MAX_BANDS:
+            msg = f"bands must be an integer in [0, {_lib.AUGMENT_MAX_BANDS}], got {self.bands!r}"
+            raise ValueError(msg)
+        for name in ("max_rows", "max_cols"):
+            if not _is_int(getattr(self, name)) or getattr(self, name) < 0:
+                msg = f"{name} must be an integer >= 0, got {getattr(self, name)!r}"
+                raise ValueError(msg)
+        if not isinstance(self.per_frame, bool):
+            msg = f"per_frame must be a bool, got {self.per_frame!r}"
+            raise ValueError(msg)
+        if isinstance(self.fill, bool) or not isinstance(self.fill, (int, float)) or not math.isfinite(self.fill):
+            msg = f"fill must be a finite number, got {self.fill!r}"
+            raise ValueError(msg)
+        object.__setattr__(self, "fill", float(self.fill))
+
+    def check_frame(self, H: int, W: int) -> None:  # noqa: N803
+        """Raises ``ValueError`` unless the parameters fit a frame of ``H`` rows and ``W`` columns."""
+        sy, sx = self.shift
+        if sy >= H or sx >= W:
+            msg = f"shift {self.shift} must stay below the frame: sy < H = {H}, sx < W = {W}"
+            raise ValueError(msg)
+        if self.max_rows > H or self.max_cols > W:
+            msg = f"max_rows = {self.max_rows}, max_cols = {self.max_cols} exceed the frame (H = {H}, W = {W})"
+            raise ValueError(msg)
+
+    def c_struct(self) -> _lib.FeedAugment:
+        return _lib.FeedAugment(*self.shift, self.bands, self.max_rows, self.max_cols, int(self.per_frame), self.fill)
+
+
 @dataclass
 class EpisodeDataModuleConfig:
     """Fields of ``BaseEpisodeDataModuleConfig`` + the multimodal ``EpisodeDataModuleConfig`` (``dataset.py:115-128``,
@@ -98,6 +155,9 @@ class EpisodeDataModuleConfig:
     data_root: Path = Path("data")
     lengths: Tensor | None = None  # host int tensor [N]: valid frames of each episode of the SORTED file list, 1 .. T_full (None: all)
     noise_seed: int | None = None  # in [0, 2**64): seeded input noise made inside the gather; None: torch.randn
+    # {"audio": FeedAugment(...), "vision": FeedAugment(...)} (or the FeedAugment fields as dicts): seeded shift and band masks of the
+    # TRAIN loader's frames (needs noise_seed); None: none.  Validation is never augmented.
+    augment: Mapping | None = None
     window: str = "first"  # "first" | "random" | "sequential": which T frames of an episode a batch holds (DeviceEpisodeLoader)
 
     @property
@@ -158,14 +218,19 @@ class _Stream:
 
     def batch(self, idx: Tensor, noise: Tensor | None, start: Tensor | None = None, start_host: list[int] | None = None,  # noqa: PLR0913
               lengths: Tensor | None = None, valid_out: Tensor | None = None, lengths_host: Tensor | None = None,
-              seeded: tuple[int, int, int] | None = None) -> tuple[Tensor, Tensor]:
+              seeded: tuple[int, int, int] | None = None, augment: tuple | None = None) -> tuple[Tensor, Tensor]:
         """``(input, target)`` for the episodes ``idx``; fused when both chains are the YAML's and E % 4 == 0.  ``start`` (int32
         ``[B]`` on the device, ``start_host`` its host copy): the window ``[start, start + T)`` instead of the first T frames.
         ``lengths`` (int32 ``[N]`` on the device): frames at or past an episode's length are exactly zero, ``valid_out`` (int32
         ``[B]``) receives each row's live steps; ``lengths_host`` is the host copy the unfused path reads.  ``seeded`` = ``(key0, key1,
-        epoch)``: a fused stream with noise and no injected ``noise`` generates its normals in the kernel (``feed_noise_reference``)."""
+        epoch)``: a fused stream with noise and no injected ``noise`` generates its normals in the kernel (``feed_noise_reference``).
+        ``augment`` = ``(FeedAugment, key0, key1, akey0, akey1, epoch)``: the fused stream's frames are shifted and masked in the
+        gather (``feed_augment_reference``), its noise, if its chain has one, is the seeded one; ``noise`` cannot be injected."""
         cin, ctg = self.chains
         n_ep, t_full = self.store.shape[:2]
+        if augment is not None and (noise is not None or not self.fused):
+            msg = "an augmented stream runs in the gather kernel and makes its own noise: noise= cannot be injected"
+            raise ValueError(msg)
         if lengths is not None and start is None:
             msg = "episode lengths need window starts"
             raise ValueError(msg)
@@ -183,6 +248,17 @@ class _Stream:
         std = cin[1]
         inp = torch.empty(b, t, *self.event_shape, device=self.store.device, dtype=torch.float32)
         tgt = torch.empty_like(inp)
+        if augment is not None:
+            if start is not None and tuple(start.shape) != (b,):
+                msg = f"start must have shape ({b},), got {tuple(start.shape)}"
+                raise ValueError(msg)
+            aug, *words = augment
+            _lib.check(_lib.TIMERS.call(
+                "mtrssm_episode_gather_augmented", _lib.load().mtrssm_episode_gather_augmented, aug.c_struct(), _lib.ptr(self.store),
+                _lib.raw_ptr(idx), _lib.index_ptr(start), _lib.index_ptr(lengths), _lib.index_ptr(valid_out), *(int(w) & _M32 for w in words), n_ep,
+                b, t, t_full, *self.event_shape, int(std is not None), float(std or 0.0), _lib.ptr(inp), _lib.ptr(tgt),
+                _lib.stream_ptr(self.store.device), nbytes=4.0 * b * t * self.event * 3), "mtrssm_episode_gather_augmented")
+            return inp, tgt
         if std is not None and noise is None and seeded is not None:
             if start is not None and tuple(start.shape) != (b,):
                 msg = f"start must have shape ({b},), got {tuple(start.shape)}"
@@ -324,6 +400,75 @@ def feed_noise_reference(key: tuple[int, int], epoch: int, episodes: Tensor, fra
     return torch.from_numpy(out.reshape(*fr.shape, event))
 
 
+def augment_key(seed: int, stream: int) -> tuple[int, int]:
+    """The key of stream ``stream``'s augmentation words under ``seed``: ``stream_key(seed, stream + 3)``, apart from the noise keys of
+    streams 0, 1, 2."""
+    return stream_key(seed, stream + 3)
+
+
+def _umulhi(a: np.ndarray, n: int | np.ndarray) -> np.ndarray:
+    """``(a * n) >> 32`` for 32-bit ``a`` (a ``uint64`` array) and ``n <= 2**32``: the uniform draw on ``[0, n)``, as int64."""
+    return ((a * np.asarray(n, dtype=np.uint64)) >> np.uint64(32)).astype(np.int64)
+
+
+def feed_augment_parameters(key: tuple[int, int], epoch: int, episodes: Tensor, frames: Tensor, aug: FeedAugment, H: int,  # noqa: N803, PLR0913
+                            W: int) -> dict[str, np.ndarray]:  # noqa: N803
+    """The shift and bands of ``mtrssm_episode_gather_augmented`` in exact integers: ``key`` =
+    ``augment_key(seed, stream)``, ``episodes`` ``[B]``, ``frames`` ``[B, T]`` (ABSOLUTE frame numbers), ``H`` x ``W`` the frame.
+    Returns int64 arrays: ``dy``, ``dx`` ``[B]`` (one draw per episode: ``Philox((0, 0, episode, epoch))``, ``umulhi(P0, 2 sy + 1) - sy``,
+    ``umulhi(P1, 2 sx + 1) - sx``) and ``h``, ``r0``, ``w``, ``c0`` ``[B, T, bands]`` (band j: ``Philox((1 + j, per_frame ? frame + 1 : 0,
+    episode, epoch))``, ``umulhi(Q0, max_rows + 1)``, ``umulhi(Q1, H - h + 1)``, ``umulhi(Q2, max_cols + 1)``, ``umulhi(Q3, W - w + 1)``)."""
+    aug.check_frame(H, W)
+    ep = np.asarray(torch.as_tensor(episodes).cpu(), dtype=np.int64)
+    fr = np.asarray(torch.as_tensor(frames).cpu(), dtype=np.int64)
+    if fr.shape[:1] != ep.shape or fr.ndim != 2:  # noqa: PLR2004
+        msg = f"episodes must be [B] and frames [B, T], got {ep.shape} and {fr.shape}"
+        raise ValueError(msg)
+    sy, sx = aug.shift
+    p = philox4x32_10((0, 0, ep & _M32, int(epoch) & _M32), key)
+    out = {"dy": _umulhi(p[0], 2 * sy + 1) - sy, "dx": _umulhi(p[1], 2 * sx + 1) - sx}
+    j = np.arange(aug.bands, dtype=np.int64)[None, None, :]
+    word1 = ((fr[:, :, None] + 1) & _M32) if aug.per_frame else np.zeros_like(fr[:, :, None])
+    q = [np.broadcast_to(x, (*fr.shape, aug.bands)) for x in philox4x32_10((1 + j, word1, ep[:, None, None] & _M32, int(epoch) & _M32), key)]
+    out["h"] = _umulhi(q[0], aug.max_rows + 1)
+    out["r0"] = _umulhi(q[1], (H - out["h"] + 1).astype(np.uint64))
+    out["w"] = _umulhi(q[2], aug.max_cols + 1)
+    out["c0"] = _umulhi(q[3], (W - out["w"] + 1).astype(np.uint64))
+    return out
+
+
+def feed_augment_reference(store: Tensor, episodes: Tensor, frames: Tensor, key: tuple[int, int], epoch: int, aug: FeedAugment,  # noqa: PLR0913
+                           live: Tensor | None = None) -> tuple[Tensor, Tensor]:
+    """``(input_base, target)`` of ``mtrssm_episode_gather_augmented`` on the host, bit for bit: ``store`` ``[N, T_full, C, H, W]``,
+    ``episodes`` ``[B]``, ``frames`` ``[B, T]`` absolute frame numbers, ``key`` = ``augment_key(seed, stream)``, ``live`` ``[B, T]``
+    bool (None: all; a dead frame is zero in both and its frame number is not read).  ``target[b, t, c, y, x] = store[ep, f, c, y - dy,
+    x - dx]`` inside the frame, ``fill`` outside; ``input_base`` = ``fill`` on the masked pixels, ``target`` elsewhere.  The whole input
+    of a noisy stream is ``input_base + feed_noise_reference(stream_key(seed, stream), ...) * std`` on the live frames."""
+    st = np.asarray(torch.as_tensor(store).cpu(), dtype=np.float32)
+    if st.ndim != 5:  # noqa: PLR2004
+        msg = f"store must be [N, T_full, C, H, W], got {st.shape}"
+        raise ValueError(msg)
+    H, W = st.shape[3:]  # noqa: N806
+    prm = feed_augment_parameters(key, epoch, episodes, frames, aug, H, W)
+    ep = np.asarray(torch.as_tensor(episodes).cpu(), dtype=np.int64)
+    fr = np.asarray(torch.as_tensor(frames).cpu(), dtype=np.int64)
+    on = np.ones(fr.shape, dtype=bool) if live is None else np.asarray(torch.as_tensor(live).cpu(), dtype=bool)
+    fill = np.float32(aug.fill)
+    target = np.full((*fr.shape, *st.shape[2:]), fill, dtype=np.float32)
+    for b in range(fr.shape[0]):
+        dy, dx = int(prm["dy"][b]), int(prm["dx"][b])
+        y0, y1, x0, x1 = max(dy, 0), min(H, H + dy), max(dx, 0), min(W, W + dx)  # the output pixels whose source lies inside the frame
+        src = st[ep[b], np.where(on[b], fr[b], 0)]
+        target[b, :, :, y0:y1, x0:x1] = src[:, :, y0 - dy: y1 - dy, x0 - dx: x1 - dx]
+    y, x = np.arange(H)[None, None, None, :], np.arange(W)[None, None, None, :]
+    rows = ((prm["r0"][..., None] <= y) & (y < (prm["r0"] + prm["h"])[..., None])).any(axis=2)  # [B, T, H]
+    cols = ((prm["c0"][..., None] <= x) & (x < (prm["c0"] + prm["w"])[..., None])).any(axis=2)  # [B, T, W]
+    masked = rows[:, :, None, :, None] | cols[:, :, None, None, :]
+    base = np.where(masked, fill, target)
+    dead = ~on[:, :, None, None, None]
+    return torch.from_numpy(np.where(dead, np.float32(0), base)), torch.from_numpy(np.where(dead, np.float32(0), target))
+
+
 class EpisodeBatch(tuple):
     """The 6-tuple of a windowed batch (``len == 6``, indexing as ever) plus where its windows lie: ``start`` (int32 ``[B]``) and
     ``reset`` (bool ``[B]``, True = the row starts an episode) on the device, ``start_host`` / ``reset_host`` their host copies (the
@@ -368,11 +513,17 @@ class DeviceEpisodeLoader:
     ranks, at any batch size and window start, and ``set_epoch(e)`` replays epoch e bitwise.  The epoch word is the value the epoch
     counter had when the epoch's iteration began (the one that seeds the permutation); ``noise_epoch="fixed"`` keeps it 0 and draws
     epoch 0's order and window starts every epoch, so the loader yields the same batches each epoch (validation: losses of two epochs
-    are computed on the same inputs).  None (the default): ``torch.randn`` from the device generator, as before."""
+    are computed on the same inputs).  None (the default): ``torch.randn`` from the device generator, as before.
+
+    ``augment`` (``{"audio": FeedAugment(...), "vision": FeedAugment(...)}``, either key optional; needs
+    ``noise_seed``): the named stream's frames are shifted by one seeded draw per episode and masked by seeded row / column bands inside
+    the gather (``mtrssm_episode_gather_augmented``), keyed by ``augment_key(noise_seed, stream)`` and the same epoch word as the noise --
+    the same invariances, the same replay, fixed by ``noise_epoch="fixed"`` too.  The stream must run in the gather kernel and hold
+    ``[C, H, W]`` frames with ``W % 4 == 0``.  A stream that is not named makes exactly the call it made before."""
 
     def __init__(self, streams: tuple[_Stream, _Stream, _Stream], batch_size: int, *, shuffle: bool, rank: int = 0, world: int = 1,  # noqa: PLR0913
                  seed: int = 0, window: str = "first", lengths: Tensor | None = None, noise_seed: int | None = None,
-                 noise_epoch: str = "advance") -> None:
+                 noise_epoch: str = "advance", augment: Mapping | None = None) -> None:
         if window not in WINDOWS:
             msg = f"window must be one of {WINDOWS}, got {window!r}"
             raise ValueError(msg)
@@ -389,6 +540,7 @@ class DeviceEpisodeLoader:
                            f"[TakeFirstN, GaussianNoise] / [TakeFirstN] and its event size a multiple of 4, got {s.event})")
                     raise ValueError(msg)
         self.noise_seed, self.noise_epoch = noise_seed, noise_epoch
+        self.augment = self._checked_augment(augment, streams, noise_seed)  # per stream: a FeedAugment or None
         self.noise_word = 0  # the epoch word of the seeded noise: set where an epoch's iteration begins, and by set_epoch
         self.streams = streams
         self.batch_size = int(batch_size)
@@ -418,6 +570,45 @@ class DeviceEpisodeLoader:
                 self.n_chunks = -(-int(self.lengths_host.max()) // self.steps)
 
     @staticmethod
+    def _checked_augment(augment: Mapping | None, streams: tuple[_Stream, ...], noise_seed: int | None) -> tuple[FeedAugment | None, ...]:
+        """The loader's ``augment`` mapping as one entry per stream (None: not augmented), checked against the streams."""
+        if not augment:
+            return (None,) * len(streams)
+        if not isinstance(augment, Mapping):
+            msg = f"augment must map stream names to FeedAugment, got {type(augment).__name__}"
+            raise ValueError(msg)  # noqa: TRY004
+        for name in augment:
+            if name == "action" or name not in STREAM_NAMES:
+                msg = f"augment: {name!r} cannot be augmented (only the image streams {STREAM_NAMES[1:]} hold frames)"
+                raise ValueError(msg)
+        if noise_seed is None:
+            msg = f"augment: the augmentation of {sorted(augment)} is seeded: it needs noise_seed"
+            raise ValueError(msg)
+        out: list[FeedAugment | None] = []
+        for name, s in zip(STREAM_NAMES, streams, strict=True):
+            aug = augment.get(name)
+            if isinstance(aug, Mapping):  # (a config file's plain keys)
+                aug = FeedAugment(**aug)
+            if aug is not None and not isinstance(aug, FeedAugment):
+                msg = f"augment: the {name} entry must be a FeedAugment, got {type(aug).__name__}"
+                raise ValueError(msg)  # noqa: TRY004
+            if aug is not None:
+                if not s.fused:
+                    msg = (f"augment: the {name} stream does not run in the gather kernel (its transforms must be [TakeFirstN, GaussianNoise] "
+                           f"/ [TakeFirstN] and its event size a multiple of 4, got {s.event})")
+                    raise ValueError(msg)
+                if len(s.event_shape) != 3 or s.event_shape[2] % 4:  # noqa: PLR2004
+                    msg = f"augment: the {name} stream's frames must be [C, H, W] with W % 4 == 0, got {list(s.event_shape)}"
+                    raise ValueError(msg)
+                try:
+                    aug.check_frame(*s.event_shape[1:])
+                except ValueError as err:
+                    msg = f"augment: the {name} stream: {err}"
+                    raise ValueError(msg) from None
+            out.append(aug)
+        return tuple(out)
+
+    @staticmethod
     def _checked_lengths(lengths: Tensor, n: int, t_full: int) -> Tensor:
         if not isinstance(lengths, Tensor) or lengths.is_cuda or lengths.is_floating_point() or lengths.dtype == torch.bool:
             msg = f"lengths must be a host integer tensor, got {getattr(lengths, 'dtype', type(lengths))}"
@@ -443,6 +634,20 @@ class DeviceEpisodeLoader:
             return [None] * len(self.streams)
         return [(*stream_key(self.noise_seed, k), self.noise_word & _M32) if s.noisy else None for k, s in enumerate(self.streams)]
 
+    def _batch_keywords(self, noise: tuple) -> list[dict]:
+        """Per stream: the ``seeded`` / ``augment`` keywords of ``_Stream.batch``.  An augmented stream gets ``augment`` = ``(FeedAugment,
+        noise key, augmentation key, epoch word)``; every other stream exactly what it got before there was augmentation."""
+        out = []
+        for k, (name, sd, aug, n) in enumerate(zip(STREAM_NAMES, self._seeded(), self.augment, noise, strict=True)):
+            if aug is None:
+                out.append({"seeded": sd})
+                continue
+            if n is not None:
+                msg = f"the {name} stream is augmented in the gather kernel, which makes its noise: noise= cannot be injected for it"
+                raise ValueError(msg)
+            out.append({"augment": (aug, *stream_key(self.noise_seed, k), *augment_key(self.noise_seed, k), self.noise_word & _M32)})
+        return out
+
     def batch(self, idx: Tensor, noise: tuple[Tensor | None, Tensor | None, Tensor | None] = (None, None, None),  # noqa: PLR0913
               start: Tensor | None = None, reset: Tensor | None = None, *, valid_host: Tensor | None = None,
               valid_global: Tensor | None = None, row0: int = 0) -> tuple[Tensor, ...]:
@@ -458,9 +663,9 @@ class DeviceEpisodeLoader:
         if start is None and self.lengths is not None:
             msg = "a loader with lengths needs start= (the windows' first frames)"
             raise ValueError(msg)
-        seeded = self._seeded()
+        keywords = self._batch_keywords(noise)
         if start is None:
-            pairs = [s.batch(idx, n, seeded=k) for s, n, k in zip(self.streams, noise, seeded, strict=True)]
+            pairs = [s.batch(idx, n, **kw) for s, n, kw in zip(self.streams, noise, keywords, strict=True)]
             return (pairs[0][0], pairs[1][0], pairs[2][0], pairs[0][1], pairs[1][1], pairs[2][1])
         dev = self.streams[0].store.device
         start_host = None
@@ -474,14 +679,14 @@ class DeviceEpisodeLoader:
         reset_host = torch.ones(idx.numel(), dtype=torch.bool) if reset is None else reset.to("cpu", torch.bool)
         hosts = None if start_host is None else start_host.tolist()
         if self.lengths is None:
-            pairs = [s.batch(idx, n, start.contiguous(), hosts, seeded=k) for s, n, k in zip(self.streams, noise, seeded, strict=True)]
+            pairs = [s.batch(idx, n, start.contiguous(), hosts, **kw) for s, n, kw in zip(self.streams, noise, keywords, strict=True)]
             items = (pairs[0][0], pairs[1][0], pairs[2][0], pairs[0][1], pairs[1][1], pairs[2][1])
             return EpisodeBatch(items, start, reset_host.to(dev), start_host, reset_host)
         valid = torch.empty(idx.numel(), dtype=torch.int32, device=dev)
         # written by ONE launch: the first stream the gather kernel takes (a batch of unfused streams only: by the per-episode path)
         writer = next((k for k, s in enumerate(self.streams) if s.fused), 0)
-        pairs = [s.batch(idx, n, start.contiguous(), hosts, self.lengths, valid if k == writer else None, self.lengths_host, seeded=sd)
-                 for k, (s, n, sd) in enumerate(zip(self.streams, noise, seeded, strict=True))]
+        pairs = [s.batch(idx, n, start.contiguous(), hosts, self.lengths, valid if k == writer else None, self.lengths_host, **kw)
+                 for k, (s, n, kw) in enumerate(zip(self.streams, noise, keywords, strict=True))]
         items = (pairs[0][0], pairs[1][0], pairs[2][0], pairs[0][1], pairs[1][1], pairs[2][1])
         vg = None if valid_global is None else valid_global.to(dev, torch.int32)
         return EpisodeBatch(items, start, reset_host.to(dev), start_host, reset_host, valid=valid,
@@ -692,7 +897,8 @@ class EpisodeDataModule(_Base):
             msg = "train_dataset is not set. Call setup() first."
             raise RuntimeError(msg)
         return DeviceEpisodeLoader(self.train_streams, self.config.batch_size, shuffle=True, rank=self.rank, world=self.world,
-                                   window=self.config.window, lengths=self._lengths(True), noise_seed=self.config.noise_seed)
+                                   window=self.config.window, lengths=self._lengths(True), noise_seed=self.config.noise_seed,
+                                   augment=self.config.augment)  # (the train loader only: validation inputs stay fixed and whole)
 
     def val_dataloader(self) -> DeviceEpisodeLoader:
         if self.val_streams is None:

@@ -10,6 +10,7 @@
                  "scheduler": {"factor": 0.5, "patience": 50}, "early_stopping": {"patience": 100}, "monitor": "val/loss",
                  "max_steps": null, "save_every_n_steps": null, "check_every_n_steps": 50,
                  "modality_dropout": {"p_audio": 0.3, "p_vision": 0.3, "span": 5}, "elbo_schedule": {"free_nats": 1.0}, "state_carry": false,
+                 "augment": {"vision": {"shift": [2, 2]}, "audio": {"bands": 2, "max_rows": 4, "max_cols": 4, "per_frame": true}},
                  "overshoot": {"depth": 5, "stride": 5}, "val_overshoot": {"depth": 5},
                  "val_census": {"observe": ["both", "audio", "vision"], "active_nats": 0.01},
                  "panel_logger": {"every_n_epochs": 10, "indices": [0, 1, 2], "query_length": 10, "fps": 10.0}},
@@ -81,7 +82,8 @@ def npz_loaders(folder: Path, cfg: dict, dev: str, rank: int, world: int):  # no
         return tuple(ds._Stream(s[lo:hi].to(dev), plain if k == 0 else noisy, plain) for k, s in enumerate(stores))  # noqa: SLF001
 
     bs = int(cfg.get("batch_size", 32))
-    train = ds.DeviceEpisodeLoader(streams(0, split), bs, shuffle=True, **kw)
+    # (`augment`: {"audio": {"shift": [2, 3], "bands": 2, "max_rows": 4, ...}, "vision": {...}}, FeedAugment's fields; train loader only)
+    train = ds.DeviceEpisodeLoader(streams(0, split), bs, shuffle=True, augment=cfg.get("augment"), **kw)
     val = ds.DeviceEpisodeLoader(streams(split, len(episodes)), bs, shuffle=False, noise_epoch="fixed", **kw) if split < len(episodes) else None
     return train, val
 
